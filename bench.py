@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- catchment-days/s of the SimplyP time-stepping engine on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5] [--scaling weak|strong] [--dump-outputs DIR]
 
 Default workload (config.workload): BASELINE.json's Tarland Monte-Carlo parameter ensemble (config C3): the shipped
 Tarland workbook + 30-year daily met series (1981-2010, 10 957 days, 1 sub-catchment, Dynamic_EPC0 = 'y'), ONE ensemble of
@@ -30,6 +30,10 @@ at its stated size (ONE pass of 10 000 members x 256 reaches x 18 262 days), a C
 goodness-of-fit table (simplyp_gof), and `strong_1m`: ONE 1 000 000-member fp64 ensemble split over the ranks (annual sums) --
 the leg that can show strong scaling.  C4, C5 and strong_1m carry a sample of their benchmarked table checked against the CPU
 oracle.  The whole default run takes about three minutes.
+
+--dump-outputs DIR writes what the last timed step returned (rank 0: its block of the table, the gathered per-member day-sums and
+status) as float64 .npy files, a seeded member sample where the whole would exceed 64 MB; the inputs are seeded, so two builds run with
+the same arguments can be compared output for output.  `ms_per_step` is the wall time of one timed step; --steps sets their number.
 
 With --gpus N > 1 from a plain shell the script starts its own N ranks (torch.distributed.run) before anything touches
 the GPU and relays rank 0's line.  Prints ONE JSON line on rank 0.
@@ -106,7 +110,15 @@ def parse_args(argv=None):
     ap.add_argument('--no-secondary', action='store_true', help='skip the secondary legs (c2, c5, c4, strong_1m, c3 -> goodness of fit only, value_weak)')
     ap.add_argument('--secondary-scale', type=float, default=None,
                     help='rehearsals: run the secondary legs (also beside a non-default --members) with their member counts times this factor')
-    return ap.parse_args(argv)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64, at most 64 MB '
+                         'in all: a seeded member sample of the table, every member\'s day-sums and status)')
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.warmup < 0:
+        ap.error('--warmup must not be negative')
+    return args
 
 
 def launch_ranks(args):
@@ -382,6 +394,69 @@ class Leg(object):
         return self.cfg['bytes_per_cd'] * self.cd_rank / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: everything written, in all
+DUMP_TABLE_MEMBERS = 64        # members of the output table in the dump at most
+DUMP_SEED = 2718
+
+
+def dump_members(n, cap, seed):
+    """Sorted seeded sample of min(n, cap) members out of n (all of them when they fit): the same for every run of the same shape."""
+    import numpy as np
+    if n <= cap:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, cap, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirname, table, member_of_slot, summaries, all_status):
+    """--dump-outputs: what a caller of the timed path received from its last step, in MEMBER order, as float64 .npy files.
+
+    table        this rank's output table [n_cols, rows, n_out_reaches, E_local], columns in slot order when
+                 ``member_of_slot`` is given (the pinned host copy when the table was streamed, else the device tensor)
+    summaries    the gathered day-sums [n_cols, n_out_reaches, E_total] (member order), all_status [E_total]
+
+    Larger outputs are cut to a seeded member sample (``*_members.npy`` holds the indices) so that the files stay within
+    DUMP_BYTES; returns {name: shape}."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+
+    def save(name, a):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(dirname, name + '.npy'), a)
+        written[name] = list(a.shape)
+        return a.nbytes
+
+    budget = DUMP_BYTES - (1 << 20)                  # room for the index files and the .npy headers
+    summ = summaries.cpu().numpy() if torch.is_tensor(summaries) else np.asarray(summaries)
+    stat = all_status.cpu().numpy() if torch.is_tensor(all_status) else np.asarray(all_status)
+    e_total = summ.shape[-1]
+    per_member = (int(np.prod(summ.shape[:-1])) + 1) * 8
+    m = dump_members(e_total, max(1, (budget // 4) // per_member), DUMP_SEED)
+    if len(m) < e_total:
+        save('summaries_members', m)
+    budget -= save('summaries', summ[..., m]) + save('status', stat[m])
+
+    n_cols, rows, n_or, e_local = table.shape
+    per_member = n_cols * rows * n_or * 8
+    if per_member > budget:
+        raise SystemExit("--dump-outputs: one member's table (%d B) exceeds what is left of the %d B budget" % (per_member, DUMP_BYTES))
+    m = dump_members(e_local, min(DUMP_TABLE_MEMBERS, budget // per_member), DUMP_SEED + 1)
+    if member_of_slot is None:
+        slots = m
+    else:
+        slot_of = np.empty(e_local, dtype=np.int64)
+        slot_of[member_of_slot.cpu().numpy().astype(np.int64)] = np.arange(e_local)
+        slots = slot_of[m]
+    if torch.is_tensor(table):
+        got = table.index_select(3, torch.as_tensor(slots, device=table.device)).cpu().numpy()
+    else:
+        got = np.take(table, slots, axis=3)
+    save('table_members', m)
+    save('table', got)
+    return written
+
+
 def main():
     args = parse_args()
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -419,6 +494,10 @@ def main():
         leg.one_step(host_out)
     elapsed, res, step_stats = leg.timed(args.steps, host_out, what(host_out))
     status, stats = res['status'], res['stats']
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, host_out if host_out is not None else out,
+                              stats.get('member_of_slot') if opts.out_slot_order else None, res['summaries'], res['all_status'])
     n_bad = int((status != 0).sum().item())
     k_ms = float(np.mean([s['kernel_ms'] for s in step_stats]))
     k_ms_ranks = b.per_rank(k_ms)
@@ -506,6 +585,8 @@ def main():
             "queue": {k: int(stats.get(k, 0)) for k in ('queue_waits', 'queue_longest_wait_polls', 'queue_longest_stall_polls')},
             "members_flagged": n_bad,
         }
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if not args.no_parity:
             b.progress("parity sample against the CPU oracle")
             line["parity"] = parity(args, b.eng, leg.prob, opts, out, host_out, stats, e_local)
