@@ -16,9 +16,11 @@
  * The integrator itself is NOT the reference's: the reference calls SciPy odeint = ODEPACK
  * LSODA (scipy is un-vendored; reference pins scipy 1.2.0 in README.md:39, 1.15.3 here) at
  * rtol=0.01 (model.py:640).  LSODA's step/order heuristics are not restated; the oracle
- * integrates the same right-hand side with classical RK4 or Cash-Karp 5(4) (literal system, or the
- * augmented transcendental-free form described at ode_aug), the schemes the device kernel implements.  For the LSODA-at-rtol=0.01 trajectory itself: parity
- * unpinned (the reference's own shipped CSVs pin it only to ~3e-3).
+ * integrates the same right-hand side with the schemes the device kernel implements: classical RK4,
+ * Cash-Karp 5(4) on the literal system, Cash-Karp on the augmented transcendental-free form described
+ * at ode_aug (with the second pair of opts.stiff_pair), and that scheme's fp32-stage mirror (config C5).
+ * For the LSODA-at-rtol=0.01 trajectory itself: parity unpinned (the reference's own shipped CSVs pin it
+ * only to ~3e-3).
  */
 #include <math.h>
 #include <stdint.h>
@@ -150,76 +152,21 @@ static void rk4_day(double* y, const ode_params* p, double T, int n, integ_stats
     st->rhs += 4u * (uint64_t)n; st->steps += (uint64_t)n;
 }
 
-/* Cash-Karp 5(4) embedded pair (Cash & Karp, ACM TOMS 16 (1990) 201-222). */
-static const double CK_A[6][5] = {
-    {0},
-    {1.0 / 5},
-    {3.0 / 40, 9.0 / 40},
-    {3.0 / 10, -9.0 / 10, 6.0 / 5},
-    {-11.0 / 54, 5.0 / 2, -70.0 / 27, 35.0 / 27},
-    {1631.0 / 55296, 175.0 / 512, 575.0 / 13824, 44275.0 / 110592, 253.0 / 4096}};
-static const double CK_B[6] = {37.0 / 378, 0, 250.0 / 621, 125.0 / 594, 0, 512.0 / 1771};
-static const double CK_E[6] = {37.0 / 378 - 2825.0 / 27648, 0, 250.0 / 621 - 18575.0 / 48384,
-                               125.0 / 594 - 13525.0 / 55296, -277.0 / 14336, 512.0 / 1771 - 1.0 / 4};   /* b - bhat */
-
-/* An explicit embedded Runge-Kutta pair as data: what cashkarp_aug_day's driver (erk_aug_day) steps with.  Cash-Karp is the one
- * the device kernels implement; Tsitouras 5(4) exists here for the round-3 probe only (tools/probe_pair.py: would another pair
- * need fewer right-hand sides under the same knee-aware controller?  oracle-only integrator id ORACLE_INTEG_TSIT5_AUG). */
-#define ERK_MAX_STAGES 13
+/* An explicit embedded Runge-Kutta pair of six stages as data.  Cash-Karp 5(4) (Cash & Karp, ACM TOMS 16 (1990) 201-222) is what
+ * cashkarp_day, erk_aug_day and the fp32 mirror step with; TAB_STIFF (below) is the second pair of opts.stiff_pair. */
+#define ERK_STAGES 6
 typedef struct {
-    int ns;                          /* stages */
-    int fsal;                        /* 1: the last stage is the derivative at the new point (b == last row of A) */
-    double A[ERK_MAX_STAGES][ERK_MAX_STAGES - 1];
-    double B[ERK_MAX_STAGES], E[ERK_MAX_STAGES];      /* weights of the higher-order solution; b - bhat */
-    double E3[ERK_MAX_STAGES];       /* second estimator (Dormand-Prince 8(5,3) only; all zero otherwise): the error of a component is then
-                                        |e5|^2 / sqrt(e5^2 + 0.01 e3^2), Hairer's combination, applied per component under the max norm */
-    int two_est;
-    double err_exp;                  /* step-size factor = SAFETY * err^err_exp: -1/5 for the 5(4) pairs, -1/8 for the 8(5,3) pair */
+    double A[ERK_STAGES][ERK_STAGES - 1];
+    double B[ERK_STAGES], E[ERK_STAGES];      /* weights of the higher-order solution; b - bhat */
+    double err_exp;                  /* step-size factor = SAFETY * err^err_exp: -1/5 for Cash-Karp, SIMPLYP_STIFF_ERR_EXP for the second pair */
 } erk_tableau;
 
 static const erk_tableau TAB_CASHKARP = {
-    6, 0,
     {{0}, {1.0 / 5}, {3.0 / 40, 9.0 / 40}, {3.0 / 10, -9.0 / 10, 6.0 / 5}, {-11.0 / 54, 5.0 / 2, -70.0 / 27, 35.0 / 27},
      {1631.0 / 55296, 175.0 / 512, 575.0 / 13824, 44275.0 / 110592, 253.0 / 4096}},
     {37.0 / 378, 0, 250.0 / 621, 125.0 / 594, 0, 512.0 / 1771},
     {37.0 / 378 - 2825.0 / 27648, 0, 250.0 / 621 - 18575.0 / 48384, 125.0 / 594 - 13525.0 / 55296, -277.0 / 14336, 512.0 / 1771 - 1.0 / 4},
-    {0}, 0, -0.2};
-
-/* Ch. Tsitouras, "Runge-Kutta pairs of order 5(4) satisfying only the first column simplifying assumption", Computers &
- * Mathematics with Applications 62 (2011) 770-775.  7 stages, FSAL: 6 new right-hand sides per step.  (The 17 order
- * conditions of order 5 hold for B to 1e-15 and those of order 4 for B - E: checked when the table was typed in.) */
-static const erk_tableau TAB_TSIT5 = {
-    7, 1,
-    {{0}, {0.161}, {-0.008480655492356989, 0.335480655492357},
-     {2.8971530571054935, -6.359448489975075, 4.3622954328695815},
-     {5.325864828439257, -11.748883564062828, 7.4955393428898365, -0.09249506636175525},
-     {5.86145544294642, -12.92096931784711, 8.159367898576159, -0.071584973281401, -0.028269050394068383},
-     {0.09646076681806523, 0.01, 0.4798896504144996, 1.379008574103742, -3.290069515436081, 2.324710524099774}},
-    {0.09646076681806523, 0.01, 0.4798896504144996, 1.379008574103742, -3.290069515436081, 2.324710524099774, 0.0},
-    {-0.00178001105222577714, -0.0008164344596567469, 0.007880878010261995, -0.1447110071732629, 0.5823571654525552,
-     -0.45808210592918697, 0.015151515151515152},
-    {0}, 0, -0.2};
-#define ORACLE_INTEG_TSIT5_AUG 12      /* not in include/simplyp.h: a probe of this file only */
-#define ORACLE_INTEG_DOP853_AUG 13     /* likewise: Dormand-Prince 8(5,3) under the same controller */
-#include "dop853_tableau.inc"
-static erk_tableau TAB_DOP853;
-static int tab_dop853_ready = 0;
-static const erk_tableau* tab_dop853(void)
-{
-    if (!tab_dop853_ready) {
-#pragma omp critical
-        {
-            memset(&TAB_DOP853, 0, sizeof(TAB_DOP853));
-            TAB_DOP853.ns = 13; TAB_DOP853.fsal = 1; TAB_DOP853.two_est = 1; TAB_DOP853.err_exp = -0.125;
-            for (int s = 0; s < 13; ++s) {
-                for (int j = 0; j < 12; ++j) TAB_DOP853.A[s][j] = DOP853_A[s][j];
-                TAB_DOP853.B[s] = DOP853_B[s]; TAB_DOP853.E[s] = DOP853_E5[s]; TAB_DOP853.E3[s] = DOP853_E3[s];
-            }
-            tab_dop853_ready = 1;
-        }
-    }
-    return &TAB_DOP853;
-}
+    -0.2};
 
 static int state_finite(const double* y)
 {   /* the 8 carried states (slots 0-4, 6, 8, 10) */
@@ -258,7 +205,7 @@ static void cashkarp_day(double* y, const ode_params* p, double T, double rtol, 
         for (int s = 1; s < 6; ++s) {
             for (int i = 0; i < NY; ++i) {
                 double acc = 0.0;
-                for (int j = 0; j < s; ++j) acc += CK_A[s][j] * k[j][i];
+                for (int j = 0; j < s; ++j) acc += TAB_CASHKARP.A[s][j] * k[j][i];
                 yt[i] = y[i] + hh * acc;
             }
             ode_f(yt, p, k[s]);
@@ -267,7 +214,7 @@ static void cashkarp_day(double* y, const ode_params* p, double T, double rtol, 
         double err = 0.0; int bad = 0;
         for (int i = 0; i < NY; ++i) {
             double inc = 0.0, ee = 0.0;
-            for (int s = 0; s < 6; ++s) { inc += CK_B[s] * k[s][i]; ee += CK_E[s] * k[s][i]; }
+            for (int s = 0; s < 6; ++s) { inc += TAB_CASHKARP.B[s] * k[s][i]; ee += TAB_CASHKARP.E[s] * k[s][i]; }
             yn[i] = y[i] + hh * inc;
             /* scale: the state and its Euler predictor (the kernel forms the 5th-order increment only for accepted steps);
              * the four daily integrals (5, 7, 9, 11), accumulated outside the stages there, use their new value */
@@ -370,41 +317,25 @@ static void ode_aug(const double* z, const ode_params* p, double invKv, double* 
     dz[11] = Qr; dz[12] = oM; dz[13] = oT; dz[14] = oP;                                         /* :132,:147,:168,:180 */
 }
 
-/* Same step-size rule as cashkarp_day (the kernel mirrors both).  y is the reference's 12-vector; slot 3
- * (Vr) is returned on its invariant. */
-/* Probe hooks of tools/probe_c4_steps.py (round 4: where do a reach network's attempts go?), off by default.
- *   reach trace: [S][12] doubles per reach -- [0] attempts, [1] rejected, [2..7] accepted steps binned by h x (cQ Qr**b_Q), the step in
- *   units of the reach's relaxation time: < 0.5, < 1, < 2, < 3, < 4, >= 4 (Cash-Karp's real stability interval ends at 3.73);
- *   [8] sum of that rate over the attempts, [9] rejections with h x rate >= 2.  (Counters are shared by the OpenMP threads: a benign
- *   race, the probe's figures are statistics.)
- *   stability cap: attempts are cut to h x rate <= cap (0 = off): what a controller that never probes the stability limit would do. */
-static double* g_reach_trace = NULL;
-static _Thread_local int g_trace_reach = 0;
-static double g_stab_cap = 0.0;
-void simplyp_oracle_set_reach_trace(double* buf) { g_reach_trace = buf; }
-void simplyp_oracle_set_stab_cap(double c) { g_stab_cap = c; }
-
 /* The stability-optimised pair of integrator 2 (opts.stiff_pair; include/simplyp_controller.h SIMPLYP_STIFF_*, derived by
  * tools/derive_stiff_pair.py): 6 stages, order 4 with an embedded order 3, stable on the real axis down to -9.01 with every
  * stage polynomial <= 1.5 there, the sparsity of Cash-Karp's weights.  erk_aug_day uses it, attempt by attempt, where the
  * step is bound by the stability of Cash-Karp (|h x rate| <= 3.73, rate = cQ Qr**b_Q: a reach far down a network), not by
  * accuracy -- the rule is in erk_aug_day and mirrored by ck_day<SysAug, true> / ck_day_quad<true> in the kernels. */
 static const erk_tableau TAB_STIFF = {
-    6, 0,
     {{0}, {SIMPLYP_STIFF_A21}, {SIMPLYP_STIFF_A31, SIMPLYP_STIFF_A32}, {SIMPLYP_STIFF_A41, SIMPLYP_STIFF_A42, SIMPLYP_STIFF_A43},
      {SIMPLYP_STIFF_A51, SIMPLYP_STIFF_A52, SIMPLYP_STIFF_A53, SIMPLYP_STIFF_A54},
      {SIMPLYP_STIFF_A61, SIMPLYP_STIFF_A62, SIMPLYP_STIFF_A63, SIMPLYP_STIFF_A64, SIMPLYP_STIFF_A65}},
     {SIMPLYP_STIFF_B1, 0, SIMPLYP_STIFF_B3, SIMPLYP_STIFF_B4, 0, SIMPLYP_STIFF_B6},
     {SIMPLYP_STIFF_E1, 0, SIMPLYP_STIFF_E3, SIMPLYP_STIFF_E4, SIMPLYP_STIFF_E5, SIMPLYP_STIFF_E6},
-    {0}, 0, SIMPLYP_STIFF_ERR_EXP};
+    SIMPLYP_STIFF_ERR_EXP};
 
-static void erk_aug_day(const erk_tableau* tab, const erk_tableau* stiff, double* y, const ode_params* p, double T, double rtol, double atol,
+/* Same step-size rule as cashkarp_day (the kernel mirrors both) with Cash-Karp ck, and the second pair where the step is bound by
+ * stability when stiff is not NULL.  y is the reference's 12-vector; slot 3 (Vr) is returned on its invariant. */
+static void erk_aug_day(const erk_tableau* ck, const erk_tableau* stiff, double* y, const ode_params* p, double T, double rtol, double atol,
                         int max_steps, double* h_carry, integ_stats* st)
 {
-    double k[ERK_MAX_STAGES][NZ], zt[NZ], zn[NZ], z[NZ];
-    const int ns = tab->ns;
-    const erk_tableau* const tab_default = tab;
-    int have_k0 = 0;                 /* FSAL pairs: k[0] already holds the derivative at the current point */
+    double k[ERK_STAGES][NZ], zt[NZ], zn[NZ], z[NZ];
     /* (the step size carried over the day boundary belongs to the smooth end of a day; the forcing jumps at midnight and the first
      * attempt of the new day with it was rejected on 85 % of the member-days: SysAug::DAY_START of it is the better guess) */
     double t = 0.0, h = *h_carry * AUG_DAY_START;
@@ -429,8 +360,7 @@ static void erk_aug_day(const erk_tableau* tab, const erk_tableau* stiff, double
          * stability interval ends at 9.01); the rate is the carried state cQ Qr**b_Q itself */
         const double stiff_rate = (p->a_Q * (8.64 * 10000) / ((1 - p->b_Q) * (p->L_reach))) * z[9];
         if (stiff && !last_chance && hh * stiff_rate > SIMPLYP_STIFF_CAP) hh = SIMPLYP_STIFF_CAP / stiff_rate;
-        if (g_stab_cap > 0.0 && !last_chance && hh * stiff_rate > g_stab_cap) hh = g_stab_cap / stiff_rate;      /* (probe hook) */
-        if (!have_k0) { ode_aug(z, p, invKv, k[0]); st->rhs += 1; }
+        ode_aug(z, p, invKv, k[0]);
         /* Aim at the knee (SysAug::KNEE_*): time to the nearest knee of a gate along the first slope; a knee inside the step
          * ends the step just past it, so that the right-hand side is smooth over all but its last few percent. */
         int targeted = 0, kink = 0, kink_gw = 0;
@@ -463,12 +393,12 @@ static void erk_aug_day(const erk_tableau* tab, const erk_tableau* stiff, double
          * knee of a gate within reach or was aimed at one: its estimate is what the knee rules were tuned on (with the second pair there a
          * storm day of a 256-reach chain came out at 4.7e-7 instead of 1.2e-7), so such an attempt is shortened to Cash-Karp's interval
          * instead.  A lane's choice depends on its own state only: results do not depend on which members share a wavefront. */
-        tab = tab_default;
+        const erk_tableau* tab = ck;
         if (stiff && hh * stiff_rate > SIMPLYP_STIFF_Z_ON) {
             if (!(kink || kink_gw || targeted)) tab = stiff;
             else if (!last_chance) hh = SIMPLYP_STIFF_Z_ON / stiff_rate;
         }
-        for (int s = 1; s < ns; ++s) {
+        for (int s = 1; s < ERK_STAGES; ++s) {
             for (int i = 0; i < NZ; ++i) {
                 double acc = 0.0;
                 for (int j = 0; j < s; ++j) acc += tab->A[s][j] * k[j][i];
@@ -476,11 +406,11 @@ static void erk_aug_day(const erk_tableau* tab, const erk_tableau* stiff, double
             }
             ode_aug(zt, p, invKv, k[s]);
         }
-        st->rhs += (uint64_t)(ns - 1);
+        st->rhs += ERK_STAGES;
         double err = 0.0, err_fast = 0.0; int bad = 0;
         for (int i = 0; i < NZ; ++i) {
-            double inc = 0.0, ee = 0.0, e3 = 0.0;
-            for (int s = 0; s < ns; ++s) { inc += tab->B[s] * k[s][i]; ee += tab->E[s] * k[s][i]; e3 += tab->E3[s] * k[s][i]; }
+            double inc = 0.0, ee = 0.0;
+            for (int s = 0; s < ERK_STAGES; ++s) { inc += tab->B[s] * k[s][i]; ee += tab->E[s] * k[s][i]; }
             zn[i] = z[i] + hh * inc;
             /* error norm: the 7 physical states (see below), and Qr**k_M (z[10]) at AUG_AUX_WEIGHT x the tolerance: on a day
              * when a nearly dry reach is wetted it grows 200-fold, and its own truncation error then showed in the sediment
@@ -498,10 +428,6 @@ static void erk_aug_day(const erk_tableau* tab, const erk_tableau* stiff, double
             double sc = atol + rtol * w;
             if (i == 10) sc = AUG_AUX_WEIGHT * atol + (AUG_AUX_WEIGHT * rtol) * w;
             double r = fabs(hh * ee) / sc;
-            if (tab->two_est) {
-                const double r3 = fabs(hh * e3) / sc, den = sqrt(r * r + 0.01 * r3 * r3);
-                r = den > 0.0 ? r * r / den : 0.0;
-            }
             /* (the reach's flow, its three masses and Qr**k_M apart: their estimate may be discounted, below) */
             if ((i >= 3 && i <= 6) || i == 10) { if (r > err_fast) err_fast = r; }
             else if (r > err) err = r;
@@ -525,14 +451,6 @@ static void erk_aug_day(const erk_tableau* tab, const erk_tableau* stiff, double
         if (!(err < 1.0e300)) bad = 1;
         for (int i = 0; i < 11; ++i) if (!(fabs(zn[i]) < 1.0e300)) bad = 1;
         ++attempts;
-        if (g_reach_trace) {      /* (probe hook) */
-            double* tr = g_reach_trace + 12 * (size_t)g_trace_reach;
-            const double hl = hh * stiff_rate;
-            const int acc = !bad && (err <= 1.0 || last_chance);
-            tr[0] += 1; tr[8] += stiff_rate;
-            if (!acc) { tr[1] += 1; if (hl >= 2.0) tr[9] += 1; }
-            else tr[2 + (hl < 0.5 ? 0 : hl < 1 ? 1 : hl < 2 ? 2 : hl < 3 ? 3 : hl < 4 ? 4 : 5)] += 1;
-        }
         if (last_chance) st->capped = 1;
         if (bad && (last_chance || hh <= 1.0e-9 * T)) {
             for (int i = 0; i < NY; ++i) y[i] = NAN;
@@ -543,17 +461,14 @@ static void erk_aug_day(const erk_tableau* tab, const erk_tableau* stiff, double
             memcpy(z, zn, sizeof(zn));
             t = (hh == rem) ? T : t + hh;
             st->steps++;
-            /* first same as last: the last stage was evaluated at the new point */
-            if (tab->fsal) { memcpy(k[0], k[ns - 1], sizeof(k[0])); have_k0 = 1; }
         } else {
-            st->rejected++;              /* (k[0] stays valid: same point) */
-            if (tab->fsal) have_k0 = 1;
+            st->rejected++;
         }
         /* pb, pk ride a neutrally stable manifold (nothing damps their drift from Qr**b, Qr**k) and are not in the error
          * norm, so on a storm day of 100+ steps the local errors would add up: re-evaluate them after every AUG_RESYNC-th
          * attempt of the day, accepted or not (a member's attempts are its own history; in the kernel the lanes of a
          * wavefront attempt in lockstep, so this test is wave-uniform there) */
-        if (attempts % AUG_RESYNC == 0 && t < T) { z[9] = pow(z[3], p->b_Q); z[10] = pow(z[3], p->k_M); have_k0 = 0; }
+        if (attempts % AUG_RESYNC == 0 && t < T) { z[9] = pow(z[3], p->b_Q); z[10] = pow(z[3], p->k_M); }
         double fac;
         if (bad) fac = SIMPLYP_CTRL_FAC_MIN;
         else if (err == 0.0) fac = SIMPLYP_CTRL_FAC_MAX;
@@ -672,7 +587,10 @@ static void cashkarp_aug_f32_day(double* y, const ode_params* p, double T_, doub
     enum { NS = 11 };
     const float T = (float)T_, rtol = (float)rtol_, atol = (float)atol_;
     float A[6][5], B[6], Ee[6];
-    for (int s = 0; s < 6; ++s) { B[s] = (float)CK_B[s]; Ee[s] = (float)CK_E[s]; for (int j = 0; j < 5; ++j) A[s][j] = (float)CK_A[s][j]; }
+    for (int s = 0; s < 6; ++s) {
+        B[s] = (float)TAB_CASHKARP.B[s]; Ee[s] = (float)TAB_CASHKARP.E[s];
+        for (int j = 0; j < 5; ++j) A[s][j] = (float)TAB_CASHKARP.A[s][j];
+    }
     float z[NS], zt[NS], k[6][NS], kq[4], sq[4];
     double yq[4] = {0.0, 0.0, 0.0, 0.0};
     float t = 0.0f, h = (float)*h_carry;
@@ -757,322 +675,8 @@ static void cashkarp_aug_f32_day(double* y, const ode_params* p, double T_, doub
     y[3] = Kv * pow(y[4], 1.0 - p->b_Q);
 }
 
-
-/* ------------------------------------------------------------------------------------- */
-/*
- * ORACLE_INTEG_SPLIT_AUG -- a PROBE of this file only (tools/probe_split.py; not in include/simplyp.h, no kernel): scheme 2 with the
- * slow stores split off, the numerical design behind DESIGN.md section 7 "Next for C4".
- *
- * The two soil boxes and the groundwater store do not depend on the reach's own states (model.py:105-124: forcing, member parameters
- * and the land-use shares only), and they are slow: a handful of steps a day resolve them where the reach -- whose flow equation
- * relaxes in 1/400 to 1/15 of a day and restarts a transient at every midnight -- takes ~30.  A day is integrated in two passes per
- * segment:
- *   slow pass:  w = VsA VsS Vg EA ES by Cash-Karp under the knee-aware controller (all three gates live here), tolerances
- *               g_split_slow_tol x the run's; each accepted step leaves one interval of a record: its length and the Hermite
- *               polynomials (cubic, or quintic with the second derivatives), in the time since the interval's start, of the two
- *               combinations the reach sees --
- *                   L = (1 - beta)(f_A QsA + f_S QsS) + Qg      (land-phase inflow, :127-129)
- *                   M = tA QsA + tS QsS + tg Qg                 (its TDP load, :154-163)
- *               with their exact time derivatives at the knots (chain rule through the gates);
- *   reach pass: z = Qr Msus TDPr PPr pb pk (+ the four daily integrals) over the record's intervals, one after the other, a step
- *               never crossing an interval's end -- same pairs, same controller as scheme 2 for what is left: no gate, hence no knee rule.
- * A segment holds at most g_split_ni intervals (a kernel would keep the record in LDS).
- * What it showed (profiles/r04_c4/split_prototype.log): the split itself is sound (2.5e-10 from the converged scheme at rtol 1e-11),
- * the reach pass needs 6 instead of 11 states and a right-hand side a third the size -- but the record, not the slow integration,
- * sets the slow pass's step: a gate's zone is 1 % of its threshold wide and the flow through it a quartic of the store, so a cubic
- * record needs ~14-20 knots a day to hold the references' fixtures at 2e-7, and a quintic one (exact on the quartic) is thrown by the
- * jump of L'' at a gate's upper knee unless it has as many.
- */
-#define ORACLE_INTEG_SPLIT_AUG 14
-#define SPLIT_NI_MAX 64
-typedef struct { int n; double hk[SPLIT_NI_MAX], L[SPLIT_NI_MAX][6], M[SPLIT_NI_MAX][6]; } split_record;
-static double g_split_slow_tol = 1.0e-4;
-static int g_split_ni = 6, g_split_carry = 1, g_split_cut_keeps = 1;
-static double g_split_h0 = 0.05;
-static int g_split_order = 5;
-void simplyp_oracle_split_order(int o) { g_split_order = o; }
-static uint64_t g_split_slow_attempts = 0, g_split_reach_attempts = 0, g_split_segments = 0, g_split_slow_max = 0;
-void simplyp_oracle_split_config(double slow_tol, int ni, int carry, int cut_keeps, double h0)
-{
-    g_split_slow_tol = slow_tol; g_split_ni = ni; g_split_carry = carry; g_split_cut_keeps = cut_keeps; g_split_h0 = h0;
-    g_split_slow_attempts = g_split_reach_attempts = g_split_segments = g_split_slow_max = 0;
-}
-void simplyp_oracle_split_counts(uint64_t* c4) { c4[0] = g_split_slow_attempts; c4[1] = g_split_reach_attempts; c4[2] = g_split_segments; c4[3] = g_split_slow_max; }
-
-typedef struct {            /* the day's constants in the kernel's grouping (DayConst) */
-    double c0, aE, mu, fc, inv_d, invTsA, invTsS, invTg, Qgmin, inv_dg, beta, fA, fS, omb, tA, tS, tg, dgate, dgq;
-} slow_const;
-
-static double gate_d(double u, double inv_d, double* dg, double* d2g)      /* f_x as one clamped cubic; its first and second derivative in u */
-{
-    double sc = u * inv_d;
-    const int inside = sc > 0.0 && sc < 1.0;
-    sc = fmin(fmax(sc, 0.0), 1.0);
-    *dg = 6.0 * sc * (1.0 - sc) * inv_d;
-    *d2g = inside ? (6.0 - 12.0 * sc) * inv_d * inv_d : 0.0;
-    return sc * sc * (3.0 - 2.0 * sc);
-}
-
-/* dw/dt of the slow stores; lm = L, M and (dlm) their first and second time derivatives at this point: dlm = L', M', L'', M'' */
-static void slow_rhs(const double* w, const slow_const* c, double* dw, double* lm, double* dlm)
-{
-    double dgA, dgS, dgG, hgA, hgS, hgG;
-    const double uA = w[0] - c->fc, uS = w[1] - c->fc;
-    const double gA = gate_d(uA, c->inv_d, &dgA, &hgA), gS = gate_d(uS, c->inv_d, &dgS, &hgS);
-    const double QsA = uA * c->invTsA * gA, QsS = uS * c->invTsS * gS;
-    dw[0] = c->c0 + c->aE * (w[3] - 1.0) - QsA;
-    dw[1] = c->c0 + c->aE * (w[4] - 1.0) - QsS;
-    const double Qsum = c->fA * QsA + c->fS * QsS;
-    const double ug = w[2] * c->invTg - c->Qgmin;
-    const double gG = gate_d(ug, c->inv_dg, &dgG, &hgG);
-    const double Qg = c->Qgmin + gG * ug;
-    dw[2] = c->beta * Qsum - Qg;
-    dw[3] = -c->mu * w[3] * dw[0];
-    dw[4] = -c->mu * w[4] * dw[1];
-    lm[0] = c->omb * Qsum + Qg;
-    lm[1] = c->tA * QsA + c->tS * QsS + c->tg * Qg;
-    if (dlm) {
-        const double qA1 = (gA + uA * dgA) * c->invTsA, qS1 = (gS + uS * dgS) * c->invTsS, qG1 = gG + ug * dgG;       /* dQ/du */
-        const double qA2 = (2.0 * dgA + uA * hgA) * c->invTsA, qS2 = (2.0 * dgS + uS * hgS) * c->invTsS, qG2 = 2.0 * dgG + ug * hgG;
-        const double dQsA = qA1 * dw[0], dQsS = qS1 * dw[1];
-        const double ugd = c->invTg * dw[2];
-        const double dQg = qG1 * ugd;
-        const double uA2 = c->aE * dw[3] - dQsA, uS2 = c->aE * dw[4] - dQsS;           /* d2 Vs / dt2 */
-        const double ug2 = c->invTg * (c->beta * (c->fA * dQsA + c->fS * dQsS) - dQg);
-        const double d2QsA = qA2 * dw[0] * dw[0] + qA1 * uA2, d2QsS = qS2 * dw[1] * dw[1] + qS1 * uS2;
-        const double d2Qg = qG2 * ugd * ugd + qG1 * ug2;
-        dlm[0] = c->omb * (c->fA * dQsA + c->fS * dQsS) + dQg;
-        dlm[1] = c->tA * dQsA + c->tS * dQsS + c->tg * dQg;
-        dlm[2] = c->omb * (c->fA * d2QsA + c->fS * d2QsS) + d2Qg;
-        dlm[3] = c->tA * d2QsA + c->tS * d2QsS + c->tg * d2Qg;
-    }
-}
-
-/* Hermite interpolant on [0, hk] in powers of the time since the interval's start: cubic from values and slopes (order 3), quintic
- * with the second derivatives too (order 5; c[4], c[5] are 0 for the cubic) */
-static void hermite(int order, double f0, double d0, double s0, double f1, double d1, double s1, double hk, double* c)
-{
-    const double ih = 1.0 / hk, sl = (f1 - f0) * ih;
-    c[0] = f0; c[1] = d0;
-    if (order == 3) {
-        c[2] = (3.0 * sl - 2.0 * d0 - d1) * ih;
-        c[3] = ((d0 + d1) - 2.0 * sl) * ih * ih;
-        c[4] = c[5] = 0.0;
-    } else {
-        const double a = s0 * hk, b = s1 * hk;      /* second derivatives x hk: same units as the slopes */
-        c[2] = 0.5 * s0;
-        c[3] = 0.5 * (20.0 * sl - 8.0 * d1 - 12.0 * d0 - (3.0 * a - b)) * ih * ih;
-        c[4] = 0.5 * (-30.0 * sl + 14.0 * d1 + 16.0 * d0 + (3.0 * a - 2.0 * b)) * ih * ih * ih;
-        c[5] = 0.5 * (12.0 * sl - 6.0 * (d1 + d0) - (a - b)) * ih * ih * ih * ih;
-    }
-}
-
-typedef struct { double qin, cQ, bQ, kM, Esum, MsusUS, tconst, cPP, PPrUS, invKv; } reach_const;
-#define NRZ 10     /* Qr Msus TDPr PPr pb pk | Qr_av Msus_out TDP_out PP_out */
-static void reach_rhs(double tau, const double* z, const reach_const* c, const double* cl, const double* cm, double* dz)
-{
-    const double L = cl[0] + tau * (cl[1] + tau * (cl[2] + tau * (cl[3] + tau * (cl[4] + tau * cl[5]))));
-    const double M = cm[0] + tau * (cm[1] + tau * (cm[2] + tau * (cm[3] + tau * (cm[4] + tau * cm[5]))));
-    const double Qr = z[0], pb = z[4], pk = z[5];
-    const double inflow = (L + c->qin) - Qr;
-    const double dQr = inflow * (c->cQ * pb);
-    const double kap = pb * c->invKv;
-    const double oM = z[1] * kap, oT = z[2] * kap, oP = z[3] * kap;
-    dz[0] = dQr;
-    dz[1] = c->Esum * pk + c->MsusUS - oM;
-    dz[2] = (M + c->tconst) - oT;
-    dz[3] = c->cPP * pk + c->PPrUS - oP;
-    const double r = dQr / Qr;
-    dz[4] = c->bQ * pb * r; dz[5] = c->kM * pk * r;
-    dz[6] = Qr; dz[7] = oM; dz[8] = oT; dz[9] = oP;
-}
-
-static void split_day(double* y, const ode_params* p, double T, double rtol, double atol, int max_steps,
-                      double* h_carry, double* h_slow, integ_stats* st, int use_stiff)
-{
-    static const double CN[6] = {0.0, 1.0 / 5, 3.0 / 10, 3.0 / 5, 1.0, 7.0 / 8};       /* Cash-Karp's nodes */
-    double cS[6]; { cS[0] = 0.0; for (int s = 1; s < 6; ++s) { double a = 0; for (int j = 0; j < s; ++j) a += TAB_STIFF.A[s][j]; cS[s] = a; } }
-    slow_const sc; reach_const rc;
-    if (!state_finite(y)) { y[5] = y[7] = y[9] = y[11] = NAN; st->poisoned = 1; return; }
-    {
-        const double wA = p->f_A * (1 - p->f_NC_A), wNC = p->f_A * p->f_NC_A + p->f_S * p->f_NC_S;
-        sc.c0 = p->P * (1 - p->f_quick); sc.aE = p->alpha * p->E; sc.mu = p->mu; sc.fc = p->fc; sc.inv_d = 1.0 / (0.01 * p->fc);
-        sc.invTsA = 1.0 / p->T_s_A; sc.invTsS = 1.0 / p->T_s_S; sc.invTg = 1.0 / p->T_g; sc.Qgmin = p->Qg_min;
-        sc.inv_dg = (p->Qg_min * 0.01 > 0.0) ? 1.0 / (p->Qg_min * 0.01) : 1.0e300;
-        sc.beta = p->beta; sc.fA = p->f_A; sc.fS = p->f_S; sc.omb = 1.0 - p->beta;
-        const double tNC = sc.omb * wNC * p->conc_TDPs_NC;
-        sc.tA = sc.omb * wA * p->conc_TDPs_A + (p->NC_type == 1 ? tNC : 0.0);
-        sc.tS = (p->NC_type == 1 ? 0.0 : tNC);
-        sc.tg = p->TDPg * p->A_catch; sc.dgate = 0.01 * p->fc; sc.dgq = 0.01 * p->Qg_min;
-        rc.qin = p->Qq_i + p->Qr_US_i;
-        rc.cQ = p->a_Q * (8.64 * 10000) / ((1 - p->b_Q) * (p->L_reach)); rc.bQ = p->b_Q; rc.kM = p->k_M;
-        rc.Esum = p->f_Ar * p->Esus_A + p->f_IG * p->Esus_IG + p->f_S * p->Esus_S; rc.MsusUS = p->Msus_US_i;
-        rc.tconst = p->Qq_i * (wA * p->conc_TDPs_A + wNC * p->conc_TDPs_NC) + p->TDPeff + p->TDPr_US_i;
-        const double pA = (p->PlabA_i + p->P_inactive) / p->Msoil, pN = (p->PlabNC_i + p->P_inactive) / p->Msoil, p0 = p->P_inactive / p->Msoil;
-        rc.cPP = p->E_PP * (p->f_Ar * p->Esus_A * ((1 - p->f_NC_Ar) * pA + p->f_NC_Ar * pN)
-                            + p->f_IG * p->Esus_IG * ((1 - p->f_NC_IG) * pA + p->f_NC_IG * pN)
-                            + p->f_S * p->Esus_S * ((1 - p->f_NC_S) * p0 + p->f_NC_S * pN));
-        rc.PPrUS = p->PPr_US_i;
-        rc.invKv = (p->a_Q * 8.64 * 10000) / p->L_reach;
-    }
-    const double rtol_s = rtol * g_split_slow_tol, atol_s = atol * g_split_slow_tol;
-    double w[5] = {y[0], y[1], y[2], exp(-p->mu * y[0]), exp(-p->mu * y[1])};
-    double z[NRZ] = {y[4], y[6], y[8], y[10], pow(y[4], p->b_Q), pow(y[4], p->k_M), 0.0, 0.0, 0.0, 0.0};
-    double ts = 0.0, hs = g_split_carry ? *h_slow : g_split_h0 * T;
-    double h = *h_carry * AUG_DAY_START;
-    int slow_attempts = 0, attempts = 0;
-    if (!(hs > 0.0) || hs > T) hs = T;
-    if (!(h > 0.0) || h > T) h = T;
-    if (use_stiff && h * rc.cQ * z[4] > SIMPLYP_STIFF_Z_START) h = SIMPLYP_STIFF_Z_START / (rc.cQ * z[4]);
-    split_record rec;
-    while (ts < T) {
-        /* ---- slow pass: up to g_split_ni accepted steps ---- */
-        double k[6][5], wt[5], wn[5], F[2], dF[4], Fn[2], dFn[4], kn[5], lms[2];
-        const erk_tableau* ck = &TAB_CASHKARP;
-        rec.n = 0; ++g_split_segments;
-        slow_rhs(w, &sc, k[0], F, dF);
-        while (ts < T && rec.n < g_split_ni) {
-            double rem = T - ts, hh = hs;
-            if (rem <= 1.1 * hs) hh = rem; else if (rem < 2.0 * hs) hh = 0.5 * rem;
-            const int last_chance = (slow_attempts + 1 >= max_steps);
-            if (last_chance) hh = rem;
-            int targeted = 0, kink = 0, kink_gw = 0;
-            {
-                double hsl = 1.0e300, hg = 1.0e300, ugd = 0.0;
-                const double tlo = AUG_KNEE_LO * hh;
-                for (int i = 0; i < 3; ++i) {
-                    const double g = (i < 2) ? w[i] - sc.fc : w[2] * sc.invTg - sc.Qgmin;
-                    const double sl = (i < 2) ? k[0][i] : k[0][2] * sc.invTg;
-                    const double gd = (i < 2) ? sc.dgate : sc.dgq;
-                    const double gdg = gd - g;
-                    const double t0 = (0.0 - g) / sl, t1 = gdg / sl;
-                    double tn = 1.0e300;
-                    if (t0 > tlo && t0 < tn) tn = t0;
-                    if (t1 > tlo && t1 < tn) tn = t1;
-                    if (i < 2) { if (tn < hsl) hsl = tn; } else { hg = tn; ugd = gdg; }
-                }
-                const double hk = fmin(hsl, hg);
-                if (!last_chance && hk * AUG_KNEE_OVER < AUG_KNEE_HI * hh) { hh = hk * AUG_KNEE_OVER; targeted = 1; }
-                const double look = AUG_KINK_REACH * hh;
-                kink = hsl < look;
-                kink_gw = (hg < look) | (kink & (ugd > 0.0));
-            }
-            for (int s = 1; s < 6; ++s) {
-                for (int i = 0; i < 5; ++i) {
-                    double acc = 0.0;
-                    for (int j = 0; j < s; ++j) acc += ck->A[s][j] * k[j][i];
-                    wt[i] = w[i] + hh * acc;
-                }
-                slow_rhs(wt, &sc, k[s], lms, NULL);
-            }
-            double err = 0.0; int bad = 0;
-            for (int i = 0; i < 5; ++i) {
-                double inc = 0.0, ee = 0.0;
-                for (int s = 0; s < 6; ++s) { inc += ck->B[s] * k[s][i]; ee += ck->E[s] * k[s][i]; }
-                wn[i] = w[i] + hh * inc;
-                if (!(fabs(wn[i]) < 1.0e300)) bad = 1;
-                if (i >= 3) continue;
-                const double ref = (i < 2) ? w[i] - sc.fc : w[i], pred = ref + hh * k[0][i];
-                double wgt = fmax(fabs(ref), fabs(pred));
-                if (i < 2) wgt = fmax(wgt, sc.dgate);
-                const double r = fabs(hh * ee) / (atol_s + rtol_s * wgt);
-                if (r > err) err = r;
-            }
-            if (kink_gw) err *= targeted ? AUG_KNEE_GW : AUG_KINK_GW;
-            else if (kink && !targeted) err *= AUG_KINK_SOIL;
-            if (!(err < 1.0e300)) bad = 1;
-            ++slow_attempts; ++g_split_slow_attempts; st->rhs += 6;
-            if (last_chance) st->capped = 1;
-            if (bad && (last_chance || hh <= 1.0e-9 * T)) { for (int i = 0; i < NY; ++i) y[i] = NAN; st->poisoned = 1; return; }
-            else if (!bad && (err <= 1.0 || last_chance)) {
-                slow_rhs(wn, &sc, kn, Fn, dFn);
-                const int n = rec.n;
-                rec.hk[n] = hh;
-                hermite(g_split_order, F[0], dF[0], dF[2], Fn[0], dFn[0], dFn[2], hh, rec.L[n]);
-                hermite(g_split_order, F[1], dF[1], dF[3], Fn[1], dFn[1], dFn[3], hh, rec.M[n]);
-                rec.n = n + 1;
-                memcpy(w, wn, sizeof(wn)); memcpy(k[0], kn, sizeof(kn)); memcpy(F, Fn, sizeof(Fn)); memcpy(dF, dFn, sizeof(dFn));
-                ts = (hh == rem) ? T : ts + hh;
-                st->steps++;
-            } else st->rejected++;
-            double fac;
-            if (bad) fac = SIMPLYP_CTRL_FAC_MIN;
-            else if (err == 0.0) fac = SIMPLYP_CTRL_FAC_MAX;
-            else { fac = SIMPLYP_CTRL_SAFETY * pow(err, -0.2); if (fac < SIMPLYP_CTRL_FAC_MIN) fac = SIMPLYP_CTRL_FAC_MIN; if (fac > SIMPLYP_CTRL_FAC_MAX) fac = SIMPLYP_CTRL_FAC_MAX; }
-            if (!(targeted && !bad && err <= 1.0 && hh * fac < hs)) hs = hh * fac;
-        }
-        /* ---- reach pass over the record ---- */
-        for (int iv = 0; iv < rec.n; ++iv) {
-            const double hk = rec.hk[iv];
-            const double* cl = rec.L[iv]; const double* cm = rec.M[iv];
-            double tau = 0.0, kz[6][NRZ], zt[NRZ], zn[NRZ];
-            while (tau < hk) {
-                double rem = hk - tau, hh = h;
-                if (rem <= 1.1 * h) hh = rem; else if (rem < 2.0 * h) hh = 0.5 * rem;
-                const int last_chance = (attempts + 1 >= max_steps);
-                if (last_chance) hh = rem;
-                const double rate = rc.cQ * z[4];
-                if (use_stiff && !last_chance && hh * rate > SIMPLYP_STIFF_CAP) hh = SIMPLYP_STIFF_CAP / rate;
-                const int cut = hh < h;
-                const erk_tableau* tab = &TAB_CASHKARP;
-                const double* cn = CN;
-                if (use_stiff && hh * rate > SIMPLYP_STIFF_Z_ON) { tab = &TAB_STIFF; cn = cS; }
-                reach_rhs(tau, z, &rc, cl, cm, kz[0]);
-                for (int s = 1; s < 6; ++s) {
-                    for (int i = 0; i < NRZ; ++i) {
-                        double acc = 0.0;
-                        for (int j = 0; j < s; ++j) acc += tab->A[s][j] * kz[j][i];
-                        zt[i] = z[i] + hh * acc;
-                    }
-                    reach_rhs(tau + cn[s] * hh, zt, &rc, cl, cm, kz[s]);
-                }
-                st->rhs += 6;
-                double err = 0.0; int bad = 0;
-                for (int i = 0; i < NRZ; ++i) {
-                    double inc = 0.0, ee = 0.0;
-                    for (int s = 0; s < 6; ++s) { inc += tab->B[s] * kz[s][i]; ee += tab->E[s] * kz[s][i]; }
-                    zn[i] = z[i] + hh * inc;
-                    if (i < 6 && !(fabs(zn[i]) < 1.0e300)) bad = 1;
-                    if (i >= 4 && i != 5) continue;
-                    const double wgt = fmax(fabs(z[i]), fabs(z[i] + hh * kz[0][i]));
-                    double scl = atol + rtol * wgt;
-                    if (i == 5) scl = AUG_AUX_WEIGHT * atol + (AUG_AUX_WEIGHT * rtol) * wgt;
-                    const double r = fabs(hh * ee) / scl;
-                    if (r > err) err = r;
-                }
-                if (rc.bQ * kz[0][0] > z[0] * rate) err *= SIMPLYP_CTRL_EXPAND;
-                if (!(err < 1.0e300)) bad = 1;
-                ++attempts; ++g_split_reach_attempts;
-                if (last_chance) st->capped = 1;
-                const int accept = !bad && (err <= 1.0 || last_chance);
-                if (bad && (last_chance || hh <= 1.0e-9 * T)) { for (int i = 0; i < NY; ++i) y[i] = NAN; st->poisoned = 1; *h_carry = h; return; }
-                else if (accept) { memcpy(z, zn, sizeof(zn)); tau = (hh == rem) ? hk : tau + hh; st->steps++; }
-                else st->rejected++;
-                if (attempts % AUG_RESYNC == 0) { z[4] = pow(z[0], rc.bQ); z[5] = pow(z[0], rc.kM); }
-                double fac;
-                if (bad) fac = SIMPLYP_CTRL_FAC_MIN;
-                else if (err == 0.0) fac = SIMPLYP_CTRL_FAC_MAX;
-                else { fac = SIMPLYP_CTRL_SAFETY * pow(err, tab->err_exp); if (fac < SIMPLYP_CTRL_FAC_MIN) fac = SIMPLYP_CTRL_FAC_MIN; if (fac > SIMPLYP_CTRL_FAC_MAX) fac = SIMPLYP_CTRL_FAC_MAX; }
-                /* (a step that was cut short -- by the interval's end or the cap -- and accepted does not shorten the step size carried on) */
-                if (!(g_split_cut_keeps && cut && accept && hh * fac < h)) h = hh * fac;
-            }
-        }
-    }
-    if ((uint64_t)slow_attempts > g_split_slow_max) g_split_slow_max = (uint64_t)slow_attempts;
-    *h_carry = h; *h_slow = hs;
-    y[0] = w[0]; y[1] = w[1]; y[2] = w[2];
-    y[4] = z[0]; y[6] = z[1]; y[8] = z[2]; y[10] = z[3];
-    y[5] = z[6]; y[7] = z[7]; y[9] = z[8]; y[11] = z[9];
-    y[3] = p->L_reach / (p->a_Q * 8.64 * 10000) * pow(y[4], 1.0 - p->b_Q);
-}
-
 /* ------------------------------------------------------------------------------------- */
 /* One member: the SC loop (model.py:365) around the day loop (model.py:491).              */
-
-/* Optional trace for tools/probe_async.py: attempted steps (accepted + rejected) of every member and day, [E][D] uint16,
- * single-reach runs.  NULL = off. */
-static uint16_t* g_day_attempts = NULL;
-void simplyp_oracle_set_trace(uint16_t* day_attempts) { g_day_attempts = day_attempts; }
 
 #define MP(name) (mp[(size_t)SIMPLYP_PM_##name * E + e])
 #define RP(name, s) (rp[((size_t)SIMPLYP_PR_##name * S + (s)) * E + e])
@@ -1154,7 +758,6 @@ static void run_member(int e, const simplyp_dims* dims, const simplyp_opts* o, c
         const double S_reach = RP(S_REACH, s), f_spr = RP(F_SPR, s);
 
         double h_carry = o->step_len / (o->substeps > 0 ? o->substeps : 1);
-        double h_slow = g_split_h0 * o->step_len;        /* SIMPLYP_INTEG_SPLIT: the slow stores' own step size */
         double D_snow = o->snow ? MP(D_SNOW_0) : 0.0;                                            /* inputs.py:198 */
 
         for (int idx = 0; idx < D; ++idx) {                                                      /* :491 */
@@ -1230,28 +833,19 @@ static void run_member(int e, const simplyp_dims* dims, const simplyp_opts* o, c
             op.TDPg = MP(TDPG); op.E_PP = MP(E_PP); op.P_inactive = P_inactive; op.Qg_min = Qg_min;
 
             /* model.py:640 -- the one place that is not a restatement (see header) */
-            const uint64_t attempts_before = st->steps + st->rejected;
-            g_trace_reach = s;
             if (n_integ == SIMPLYP_INTEG_RK4) rk4_day(y, &op, o->step_len, o->substeps, st);
             else if (n_integ == SIMPLYP_INTEG_CASHKARP_AUG)
                 cashkarp_aug_day(y, &op, o->step_len, o->rtol, o->atol, o->max_steps, &h_carry, st, stiff_pair);
             else if (n_integ == SIMPLYP_INTEG_CASHKARP_AUG_F32)
                 cashkarp_aug_f32_day(y, &op, o->step_len, o->rtol, o->atol, o->max_steps, &h_carry, st);
-            else if (n_integ == ORACLE_INTEG_SPLIT_AUG)
-                split_day(y, &op, o->step_len, o->rtol, o->atol, o->max_steps, &h_carry, &h_slow, st, 1);
-            else if (n_integ == ORACLE_INTEG_TSIT5_AUG)
-                erk_aug_day(&TAB_TSIT5, NULL, y, &op, o->step_len, o->rtol, o->atol, o->max_steps, &h_carry, st);
-            else if (n_integ == ORACLE_INTEG_DOP853_AUG)
-                erk_aug_day(tab_dop853(), NULL, y, &op, o->step_len, o->rtol, o->atol, o->max_steps, &h_carry, st);
-            else cashkarp_day(y, &op, o->step_len, o->rtol, o->atol, o->max_steps, &h_carry, st);
-            if (o->project_vr && n_integ != SIMPLYP_INTEG_CASHKARP_AUG && n_integ != SIMPLYP_INTEG_CASHKARP_AUG_F32 && n_integ != ORACLE_INTEG_TSIT5_AUG && n_integ != ORACLE_INTEG_DOP853_AUG && n_integ != ORACLE_INTEG_SPLIT_AUG) {
+            else cashkarp_day(y, &op, o->step_len, o->rtol, o->atol, o->max_steps, &h_carry, st);      /* SIMPLYP_INTEG_CASHKARP */
+            if (o->project_vr && (n_integ == SIMPLYP_INTEG_RK4 || n_integ == SIMPLYP_INTEG_CASHKARP)) {
                 /* Drift control (not in the reference).  The reference's own equations (:127-131) imply
                  * dVr = dQr * (1-b_Q) L / (a_Q 86400 Qr^b_Q), and Vr0 (:457-459) starts on that curve, so
                  * Vr == L Qr^(1-b_Q) / (a_Q 86400) for all t; Vr has no restoring term and a one-step
                  * integrator random-walks off it.  Re-impose it once per day. */
                 y[3] = L_reach * pow(y[4], 1.0 - b_Q) / (a_Q * 8.64 * 10000);
             }
-            if (g_day_attempts && S == 1) g_day_attempts[(size_t)e * D + idx] = (uint16_t)(st->steps + st->rejected - attempts_before);
             const double* res = y;                                                               /* :643 */
             for (int i = 0; i < NY; ++i) if (!isfinite(res[i])) stat |= SIMPLYP_STATUS_NONFINITE;
 
@@ -1318,6 +912,10 @@ int simplyp_oracle_run(const simplyp_dims* dims, const simplyp_opts* opts,
                        double* out, int32_t* member_status, simplyp_stats* stats, int n_threads)
 {
     if (!dims || !opts || dims->E <= 0 || dims->S <= 0 || dims->D <= 0) return SIMPLYP_ERR_ARG;
+    /* the integrators the library accepts (check_args in simplyp_amd/csrc/simplyp_hip.hip); any other id is refused, not run as another */
+    if (opts->integrator != SIMPLYP_INTEG_RK4 && opts->integrator != SIMPLYP_INTEG_CASHKARP &&
+        opts->integrator != SIMPLYP_INTEG_CASHKARP_AUG && opts->integrator != SIMPLYP_INTEG_CASHKARP_AUG_F32)
+        return SIMPLYP_ERR_ARG;
     const int S = dims->S;
     int32_t* out_slot = (int32_t*)malloc(sizeof(int32_t) * S);
     for (int s = 0; s < S; ++s) out_slot[s] = out_reaches ? -1 : s;

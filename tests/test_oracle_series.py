@@ -146,6 +146,21 @@ def test_oracle_flags_poisoned_member(oracle_lib):
     assert np.array_equal(out[..., 0], out[..., 2])
 
 
+def test_oracle_refuses_unknown_integrator_ids(oracle_lib):
+    """The oracle accepts the integrators the library accepts (0-3, check_args) and refuses any other id instead of running
+    another scheme under it."""
+    m = helpers.marshal_scenario('tarland_2004_static')
+    args = (m['forcing'], m['doy'], m['member_params'], m['reach_params'], m['up_ptr'], m['up_idx'], m['opts'])
+    for integ in (-1, 4, 12, 13, 14):
+        m['opts'].integrator = integ
+        with pytest.raises(RuntimeError, match='simplyp_oracle_run failed'):
+            oracle_lib.run(*args)
+    for integ in (0, 1, 2, 3):
+        m['opts'].integrator = integ
+        out, status, stats = oracle_lib.run(*args)
+        assert status.max() == 0 and stats['rhs_evals'] > 0 and np.isfinite(out).all(), integ
+
+
 def test_oracle_default_solver_across_parameter_distribution(oracle_lib):
     """8 members of the bench's Monte-Carlo distribution (BASELINE config C3), 3 years each, against the
     unmodified reference at rtol=atol=1e-12 (tests/golden/monte_carlo_members.npz): <= 1e-6 on all reach outputs

@@ -2,7 +2,7 @@
 
 A reach far down a network relaxes to its quasi-steady flow at rate = cQ Qr**b_Q of up to several hundred per day; once the
 transient that follows midnight has died away, Cash-Karp's steps there are bound by its real stability interval (|h x rate| <=
-3.73), not by accuracy (tools/probe_c4_steps.py).  For those steps the kernel switches, per lane, to a second explicit 6-stage
+3.73), not by accuracy (profiles/r04_c4/steps_by_reach.log).  For those steps the kernel switches, per lane, to a second explicit 6-stage
 pair made for the purpose -- same stage count, same sparsity of the weights as Cash-Karp (b2 = b5 = 0, e2 = 0), so the attempt
 loop runs the same instructions with other constants:
 
