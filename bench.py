@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- catchment-days/s of the SimplyP time-stepping engine on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5] [--scaling weak|strong] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5] [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 Default workload (config.workload): BASELINE.json's Tarland Monte-Carlo parameter ensemble (config C3): the shipped
 Tarland workbook + 30-year daily met series (1981-2010, 10 957 days, 1 sub-catchment, Dynamic_EPC0 = 'y'), ONE ensemble of
@@ -16,20 +16,24 @@ model.py:644, :721-724): the library streams every finished 64-day chunk over PC
 chunks compute (simplyp_stream_out), and the step ends when the last byte has arrived and rank 0 holds the per-member
 summaries.  `value` is that transfer-inclusive rate -- the same definition at every N: if the page-locked staging cannot be
 had the bench exits non-zero instead of quietly measuring something else (--no-stream asks for the device-resident rate
-explicitly).  `value_device_resident` (table left in HBM) and `value_h2d_inclusive` (plus the upload of the inputs) are
-reported beside it.
+explicitly).  `value_h2d_inclusive` (plus the upload of the inputs, timed while setting up) is reported beside it.
 
 Members shard across GPUs with no data-path collective (ensemble.run_sharded); the only exchange is the final gather of
 per-member summaries to rank 0 over RCCL.  --scaling: strong = one ensemble of `--members` split over the ranks (default for
 c3: BASELINE C3 is "a 100k-member ensemble sharded across 1 -> 8 GPUs"); weak = every rank brings its own `--members`
-(default for the other configs).  With the default strong C3 line at N > 1 the weak figure (100 000 members per GPU) is
-measured after the timed region and carried in the same line as `value_weak`.
+(default for the other configs).
 
-After the timed region of the default run the line also gets `secondary`: BASELINE configs C2, C5 (a few passes each) and C4
-at its stated size (ONE pass of 10 000 members x 256 reaches x 18 262 days), a C3 pass that leaves only the members'
-goodness-of-fit table (simplyp_gof), and `strong_1m`: ONE 1 000 000-member fp64 ensemble split over the ranks (annual sums) --
-the leg that can show strong scaling.  C4, C5 and strong_1m carry a sample of their benchmarked table checked against the CPU
-oracle.  The whole default run takes about three minutes.
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the line
+(the roofline, occupancy and transfer figures in it come from the timed steps; `value_device_resident` is null).  --full then
+measures and checks everything else, after the timed region: `value_device_resident` (a few passes with the table left in HBM),
+`parity` (golden tables of the reference and a sample of the benchmarked table against the CPU oracle; left out with
+--no-parity) and `cpu_baseline` (the CPU oracle on the host's cores; left out with --no-cpu-baseline).  Beside the default
+workload a --full line also gets (unless --no-secondary) `secondary`: BASELINE configs C2, C5 (a few passes each) and C4 at its
+stated size (ONE pass of 10 000 members x 256 reaches x 18 262 days), a C3 pass that leaves only the members' goodness-of-fit
+table (simplyp_gof), and `strong_1m`: ONE 1 000 000-member fp64 ensemble split over the ranks (annual sums) -- the leg that can
+show strong scaling; C4, C5 and strong_1m carry a sample of their benchmarked table checked against the CPU oracle.  It also
+gets `value_weak`: at N > 1 the weak figure (100 000 members per GPU) beside the strong headline.  A --full run of the default
+workload takes about two minutes.
 
 --dump-outputs DIR writes what the last timed step returned (rank 0: its block of the table, the gathered per-member day-sums and
 status) as float64 .npy files, a seeded member sample where the whole would exceed 64 MB; the inputs are seeded, so two builds run with
@@ -105,11 +109,14 @@ def parse_args(argv=None):
     ap.add_argument('--chunk-days', type=int, default=None, help='opts.time_chunk_days (experiments; default: the library chooses)')
     ap.add_argument('--lanes-per-member', type=int, default=None, help='opts.lanes_per_member (experiments; default: the library chooses)')
     ap.add_argument('--no-stream', action='store_true', help='leave the output table in HBM (value = device-resident rate)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-parity', action='store_true', help='skip the accuracy checks (keeps a profile to one kernel shape)')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the secondary legs (c2, c5, c4, strong_1m, c3 -> goodness of fit only, value_weak)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, measure and check everything else: device-resident rate, parity, CPU baseline and, '
+                         'beside the default workload, the secondary legs and value_weak (about two minutes in all)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-parity', action='store_true', help='with --full: skip the accuracy checks')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the secondary legs (c2, c5, c4, strong_1m, c3 -> goodness of fit only, value_weak)')
     ap.add_argument('--secondary-scale', type=float, default=None,
-                    help='rehearsals: run the secondary legs (also beside a non-default --members) with their member counts times this factor')
+                    help='with --full, rehearsals: run the secondary legs (also beside a non-default --members) with their member counts times this factor')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64, at most 64 MB '
                          'in all: a seeded member sample of the table, every member\'s day-sums and status)')
@@ -503,10 +510,10 @@ def main():
     k_ms_ranks = b.per_rank(k_ms)
     wall_ms_ranks = b.per_rank(float(np.mean([s['wall_ms'] for s in step_stats])))
 
-    # the device-resident rate beside it (same kernel, table left in HBM)
+    # --full: the device-resident rate beside it (same kernel, table left in HBM)
     elapsed_dev = None
     n_dev_steps = max(1, min(args.steps, 3))
-    if host_out is not None:
+    if args.full and host_out is not None:
         leg.one_step(None)
         elapsed_dev, _, _ = leg.timed(n_dev_steps, None, what(None))
         # leave a streamed run's table on both sides for the parity sample below
@@ -587,13 +594,13 @@ def main():
         }
         if dumped is not None:
             line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
-        if not args.no_parity:
+        if args.full and not args.no_parity:
             b.progress("parity sample against the CPU oracle")
             line["parity"] = parity(args, b.eng, leg.prob, opts, out, host_out, stats, e_local)
 
-    # ---- secondary legs: only beside the default workload (the driver's run); every rank takes part ----
+    # ---- secondary legs: only in a --full run of the default workload; every rank takes part ----
     secondary = {}
-    default_run = (args.config == 'c3' and args.rtol is None and args.chunk_days is None and args.lanes_per_member is None
+    default_run = (args.full and args.config == 'c3' and args.rtol is None and args.chunk_days is None and args.lanes_per_member is None
                    and not args.no_stream and not args.no_secondary and (args.members is None or args.secondary_scale is not None))
     if default_run:
         secondary['c3_gof_only'] = leg_gof_only(b, leg)
@@ -614,7 +621,7 @@ def main():
     if rank == 0:
         if secondary:
             line['secondary'] = secondary
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # on rank 0 at any world size (the other ranks wait at the barrier below), on all the cores this process may use
             b.restore_affinity()
             b.progress("cpu baseline")

@@ -42,6 +42,16 @@ def test_steps_must_be_positive():
         bench.parse_args(['--steps', '0'])
 
 
+def test_full_is_off_by_default():
+    """A plain run times the headline alone; everything else the bench measures waits for --full."""
+    import importlib
+    import sys
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module('bench')
+    assert bench.parse_args([]).full is False
+    assert bench.parse_args(['--full', '--no-secondary']).full is True
+
+
 def test_dump_outputs_in_member_order_and_within_budget(tmp_path):
     """--dump-outputs: the table's slot order is resolved to member order, a table larger than the budget is cut to a seeded
     member sample (the same one on every call), everything is float64 and the files stay under 64 MB in all."""

@@ -276,7 +276,7 @@ def test_config_c3_at_100k_members_through_the_benched_path(engine0, oracle_lib)
 
 
 def test_bench_starts_its_own_ranks(tmp_path):
-    """`python bench.py --gpus 2` from a plain shell: the parent must spawn its ranks before touching the GPU (gloo
+    """`python bench.py --gpus 2 --full` from a plain shell: the parent must spawn its ranks before touching the GPU (gloo
     rehearsal: two ranks share this box's one GPU) and relay rank 0's ONE JSON line.  Default scaling = strong (BASELINE C3 is
     one ensemble split over the GPUs): members_total stays what was asked for; the line carries cpu_baseline at world size 2,
     per-rank kernel times and the collective's rank count (0 here: gloo rehearsal, no RCCL).  The tables are streamed to
@@ -288,7 +288,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     env.pop('WORLD_SIZE', None); env.pop('RANK', None); env.pop('LOCAL_RANK', None)
     for scaling, per_gpu, total in ((None, 1500, 3000), ('weak', 1500, 3000)):
         members = per_gpu if scaling == 'weak' else total
-        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '0', '--members', str(members)]
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '0', '--members', str(members), '--full']
         cmd += ['--scaling', scaling, '--no-cpu-baseline'] if scaling else ['--secondary-scale', '0.002']
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
@@ -320,14 +320,14 @@ def test_bench_starts_its_own_ranks(tmp_path):
 
 
 def test_default_bench_line_carries_the_secondary_legs(tmp_path):
-    """The driver's `python bench.py` (N = 1, no flags): the headline C3 line plus, after the timed region, BASELINE C2, C5, C4 AT ITS
+    """`python bench.py --full` on the default workload (N = 1): the headline C3 line plus, after the timed region, BASELINE C2, C5, C4 AT ITS
     STATED SIZE (one pass of 10 000 x 256 x 18 262) and the 1M-member strong-scaling leg, each with a sample of its benchmarked table
     against the CPU oracle, the goodness-of-fit-only pass, cpu_baseline on every usable core, value_weak (= value at N = 1).
     Run here with 1 step."""
     import json
     env = dict(os.environ)
     env.pop('WORLD_SIZE', None); env.pop('RANK', None); env.pop('LOCAL_RANK', None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '1', '--warmup', '1'],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '1', '--warmup', '1', '--full'],
                        env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -349,6 +349,27 @@ def test_default_bench_line_carries_the_secondary_legs(tmp_path):
     assert j['parity']['golden']['dry_members']['worst_member_max_rel_err'] < j['parity']['golden']['dry_members']['bar']
     assert sec['c3_gof_only']['value'] > j['value'] and sec['c3_gof_only']['gof_ms'] > 0 and sec['c3_gof_only']['best_member_nse_q'] > 0.0
     assert j['value_weak']['same_run_as_value'] is True and j['value_weak']['value'] == j['value']
+
+
+def test_plain_bench_line_is_the_headline_alone(tmp_path):
+    """`python bench.py` without --full: after the timed steps only --dump-outputs and the line, which carries the headline and
+    the figures taken from the timed steps and none of what --full measures.  Small ensemble, 1 GPU."""
+    import json
+    env = dict(os.environ)
+    env.pop('WORLD_SIZE', None); env.pop('RANK', None); env.pop('LOCAL_RANK', None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--members', '3000',
+                        '--dump-outputs', str(tmp_path / 'dump')], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j['metric'] == 'catchment-days/sec (ensemble x reaches x days)' and j['unit'] == 'catchment-days/s'
+    assert j['higher_is_better'] is True and j['dtype'] == 'f64' and j['steps'] == 2 and j['warmup'] == 1
+    cd = j['members_total'] * j['config']['reaches'] * j['config']['days']
+    assert j['members_total'] == 3000 and j['value'] > 0 and abs(j['value'] * j['ms_per_step'] * 1e-3 / cd - 1.0) < 1e-9
+    assert j['members_flagged'] == 0 and j['roofline']['kernel_ms'] > 0 and j['value_includes'].startswith('output table delivered to pinned host memory')
+    assert j['value_device_resident'] is None and not {'parity', 'secondary', 'value_weak', 'cpu_baseline'} & set(j)
+    assert set(j['dumped_outputs']['arrays']) >= {'table', 'table_members', 'summaries', 'status'}
 
 
 @pytest.mark.parametrize('lanes', [1, 13, 32])

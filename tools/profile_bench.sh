@@ -14,7 +14,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 Q="--no-cpu-baseline --no-parity"
 if [ -z "$ONLY_TRACE" ]; then
-python3 bench.py --steps $STEPS --warmup $WARMUP $EXTRA > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --steps $STEPS --warmup $WARMUP --full $EXTRA > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json
 fi
 # the traced passes leave the table in HBM: under the profiler the streamed chunk copies sometimes run as shader blits that share
