@@ -916,6 +916,7 @@ int simplyp_oracle_run(const simplyp_dims* dims, const simplyp_opts* opts,
     if (opts->integrator != SIMPLYP_INTEG_RK4 && opts->integrator != SIMPLYP_INTEG_CASHKARP &&
         opts->integrator != SIMPLYP_INTEG_CASHKARP_AUG && opts->integrator != SIMPLYP_INTEG_CASHKARP_AUG_F32)
         return SIMPLYP_ERR_ARG;
+    if (!(opts->step_len > 0.0) || !isfinite(opts->step_len)) return SIMPLYP_ERR_ARG;      /* as check_args */
     const int S = dims->S;
     int32_t* out_slot = (int32_t*)malloc(sizeof(int32_t) * S);
     for (int s = 0; s < S; ++s) out_slot[s] = out_reaches ? -1 : s;

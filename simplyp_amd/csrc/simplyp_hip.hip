@@ -416,7 +416,8 @@ int check_args(simplyp_ctx* ctx, const simplyp_dims* dims, const simplyp_opts* o
         return fail(ctx, SIMPLYP_ERR_ARG, "lanes_per_member = 4 exists for integrator 2 (Cash-Karp on the augmented system) only");
     if (opts->stiff_pair > 0 && opts->integrator != SIMPLYP_INTEG_CASHKARP_AUG)
         return fail(ctx, SIMPLYP_ERR_ARG, "stiff_pair > 0 (the stability-optimised second pair) exists for integrator 2 (Cash-Karp on the augmented system) only");
-    if (!(opts->step_len > 0.0)) return fail(ctx, SIMPLYP_ERR_ARG, "step_len must be > 0");
+    if (!(opts->step_len > 0.0) || !std::isfinite(opts->step_len))
+        return fail(ctx, SIMPLYP_ERR_ARG, "step_len must be finite and > 0 (got %g)", opts->step_len);
     if (opts->sc_qr0 < 0 || opts->sc_qr0 >= dims->S) return fail(ctx, SIMPLYP_ERR_ARG, "sc_qr0 out of range");
     if (opts->out_mask == 0u || (opts->out_mask & ~(SIMPLYP_MASK_ALL | SIMPLYP_MASK_D_SNOW)) != 0u)
         return fail(ctx, SIMPLYP_ERR_ARG, "out_mask must select 1..%d of the columns", (int)SIMPLYP_N_OUT);

@@ -252,7 +252,7 @@ def run_reference(mods, switch, sc, tight):
         import warnings
         with warnings.catch_warnings():
             warnings.simplefilter('ignore')
-            df_TC, df_R, Kf, od = model.run_simply_p(met, p_struc, p_SU, p_LU, p_SC, p, dyn)
+            df_TC, df_R, Kf, od = model.run_simply_p(met, p_struc, p_SU, p_LU, p_SC, p, dyn, step_len=sc.get('step_len', 1.0))
     wall = time.time() - t0
     return dict(df_TC=df_TC, df_R=df_R, Kf=Kf, met=met, p_LU=p_LU, p_SC=p_SC, wall=wall,
                 nfe_per_day=switch.nfe / max(switch.calls, 1), stdout=buf.getvalue())
@@ -569,6 +569,107 @@ def c4_members_fixture(n_proc, fname='c4_members.npz', shape=None):
     print(fname, 'written')
 
 
+# step_len != 1 (--only steplen): the reference integrates every row over [0, step_len] (model.py:345) while its soil-P update and its
+# upstream routing keep their one-day forms (model.py:44, :524-528).  Three of the scenarios above, unchanged but for step_len, at
+# rtol = atol = 1e-12: the 9 reach columns of every reach, and the terrestrial columns where one reach keeps the file small.
+STEPLEN_CASES = [('tarland_2004_dynamic', 0.5), ('tarland_2004_dynamic', 2.0), ('chain4_val_2004', 0.5), ('chain4_val_2004', 2.0),
+                 ('stiff_chain12_2004', 0.25), ('stiff_chain12_2004', 2.0)]
+STEPLEN_TC = ('tarland_2004_dynamic',)
+
+
+def _steplen_worker(case):
+    name, step_len = case
+    mods = load_reference()
+    switch = OdeintSwitch()
+    mods['model'].odeint = switch
+    sc = dict(scenarios(False)[name], step_len=step_len)
+    r = run_reference(mods, switch, sc, 1e-12)
+    print('%s step_len %g: wall %.1f s  nfe/day %.1f' % (name, step_len, r['wall'], r['nfe_per_day']), flush=True)
+    from simplyp_amd import marshal
+    R = {SC: r['df_R'][SC][REACH_COLS].to_numpy(dtype=float) for SC in r['df_R']}
+    TC = {}
+    if name in STEPLEN_TC:
+        for SC in r['df_TC']:
+            cols = [c for c in marshal.OUT_COLUMNS if c in r['df_TC'][SC].columns]
+            TC[SC] = (cols, r['df_TC'][SC][cols].to_numpy(dtype=float))
+    return R, TC
+
+
+def steplen_fixture(n_proc):
+    import multiprocessing as mp
+    order = sorted(range(len(STEPLEN_CASES)), key=lambda i: (STEPLEN_CASES[i][0] != 'stiff_chain12_2004', -STEPLEN_CASES[i][1]))
+    with mp.get_context('fork').Pool(min(n_proc, len(STEPLEN_CASES))) as pool:
+        res = pool.map(_steplen_worker, [STEPLEN_CASES[i] for i in order], chunksize=1)
+    res = [res[order.index(i)] for i in range(len(STEPLEN_CASES))]
+    arrays = {'names': np.array([n for n, _ in STEPLEN_CASES]), 'step_len': np.array([s for _, s in STEPLEN_CASES]),
+              'odeint_rtol_atol': np.array((1e-12, 1e-12)), 'columns': np.array(REACH_COLS)}
+    for k, (R, TC) in enumerate(res):
+        for SC, tab in R.items():
+            arrays['R/%d/%d' % (k, SC)] = tab
+        for SC, (cols, tab) in TC.items():
+            arrays['TC/%d/%d' % (k, SC)] = tab
+            arrays['TC/%d/%d/columns' % (k, SC)] = np.array(cols)
+    np.savez_compressed(os.path.join(HERE, 'step_len.npz'), **arrays)
+    print('step_len.npz written')
+
+
+# The dry network (--only drynet): config C4's chain, upper 32 reaches, members of a 256-member draw of C4's distribution (C4_SEED, both
+# dynamic options on), 1981-1982 on the dry fixture's climate (DRY_PSCALE) and odeint tolerances (DRY_TOLS, for the reasons given
+# there) -- where the network scheme (second pair, damping-aware weights) meets reaches that nearly dry up.  Chosen with
+# tools/sweep_dry_network.py (CPU oracle, default solver against Cash-Karp alone at rtol 1e-11 / atol 1e-13, this period, all 32
+# reaches, the 9 reach columns): worst 6.8e-7, median 3.0e-7, 117 right-hand sides per catchment-day.  Members 112, 67, 76: the three
+# largest errors (6.8e-7, 5.9e-7, 5.8e-7, all at reach 3); 181, 250: the smallest minimum daily Qr of the headwater (2.9e-3, 4.2e-3
+# mm/d: their Qg_min are the draw's smallest; the driest two Tarland years, 1989-1990, bring no headwater lower).  Kept reaches, per
+# member (a two-year table is 53 kB, so not every member keeps every reach): the headwater, the outlet, the member's worst reach in
+# the sweep (3 / 21 / 30), and one of reaches 2, 8, 16 for the first three.
+DRYNET_REACHES, DRYNET_DRAW, DRYNET_YEARS = 32, 256, ('1981-01-01', '1982-12-31')
+DRYNET_KEEP = {112: (1, 2, 3, 32), 67: (1, 3, 8, 32), 76: (1, 3, 16, 32), 181: (1, 21, 32), 250: (1, 30, 32)}
+
+
+def _drynet_worker(member):
+    from simplyp_amd import synthetic, marshal
+    mods = load_reference()
+    switch = OdeintSwitch()
+    mods['model'].odeint = switch
+    st_dt, end_dt = DRYNET_YEARS
+    p_SU, p, p_LU, _, _, met = tarland_inputs(st_dt, end_dt)
+    _, p_struc, _, _, p_SC, p4, _ = synthetic.c4_inputs(DRYNET_REACHES, synthetic.C4_SEED, st_dt, end_dt)
+    p = p.copy()
+    p['SC_list'], p['SC_Qr0'] = p4['SC_list'], p4['SC_Qr0']
+    p_SU = p_SU.copy()
+    p_SU['n_SC'] = DRYNET_REACHES
+    over = synthetic.monte_carlo_overrides(p, p_LU, DRYNET_DRAW, seed=synthetic.C4_SEED)
+    sc = dict(p_SU=p_SU, p=p, p_LU=p_LU.copy(), p_SC=p_SC, p_struc=p_struc, met=met, pscale=DRY_PSCALE,
+              dyn=dict(Dynamic_EPC0='y', Dynamic_erodibility='y'))
+    for name in over:
+        src = dict(marshal.PM_SPEC)[name]
+        if src[0] == 'p':
+            sc['p'][src[1]] = float(over[name][member])
+        else:
+            sc['p_LU'].loc[src[1], src[2]] = float(over[name][member])
+    r = run_reference(mods, switch, sc, DRY_TOLS)
+    print('dry network member %d: wall %.1f s  nfe/day %.1f' % (member, r['wall'], r['nfe_per_day']), flush=True)
+    return ({sc_id: r['df_R'][sc_id][REACH_COLS].to_numpy(dtype=float) for sc_id in DRYNET_KEEP[member]},
+            {k: float(over[k][member]) for k in sorted(over)})
+
+
+def drynet_fixture(n_proc):
+    import multiprocessing as mp
+    members = list(DRYNET_KEEP)
+    with mp.get_context('fork').Pool(min(n_proc, len(members))) as pool:
+        res = pool.map(_drynet_worker, members, chunksize=1)
+    keep = sorted(set(r for rs in DRYNET_KEEP.values() for r in rs))
+    arrays = {'n_reaches': np.array(DRYNET_REACHES), 'n_draw': np.array(DRYNET_DRAW), 'members': np.array(members),
+              'reaches': np.array(keep), 'years': np.array(DRYNET_YEARS), 'pscale': np.array(DRY_PSCALE),
+              'odeint_rtol_atol': np.array(DRY_TOLS), 'columns': np.array(REACH_COLS), 'names': np.array(sorted(res[0][1])),
+              'values': np.array([[ov[k] for (_, ov) in res] for k in sorted(res[0][1])])}
+    for m, (tabs, _) in zip(members, res):
+        for sc_id, R in tabs.items():
+            arrays['R/%d/%d' % (m, sc_id)] = R
+    np.savez_compressed(os.path.join(HERE, 'dry_network.npz'), **arrays)
+    print('dry_network.npz written')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--long', action='store_true', help='also run the 1981-2010 scenario (minutes)')
@@ -584,6 +685,12 @@ def main():
         return
     if args.only == 'dry':
         dry_fixture(args.procs)
+        return
+    if args.only == 'steplen':
+        steplen_fixture(args.procs)
+        return
+    if args.only == 'drynet':
+        drynet_fixture(args.procs)
         return
     if args.only == 'c4mc':
         c4_members_fixture(args.procs)

@@ -229,3 +229,88 @@ def c4_members_worst(got, tables):
     cols = ['Vr', 'Qr_EndOfDay', 'Qr', 'Msus_EndOfDay', 'Msus_kg/day', 'TDPr_EndOfDay', 'TDP_kg/day', 'PPr_EndOfDay', 'PP_kg/day']
     return {key: max(max_rel_err(got[marshal.OUT_COLUMNS.index(c), :, key[1], key[0]], tab[:, j], floor=1e-300) for j, c in enumerate(cols))
             for key, tab in tables.items()}
+
+
+REACH_COLS = ['Vr', 'Qr_EndOfDay', 'Qr', 'Msus_EndOfDay', 'Msus_kg/day', 'TDPr_EndOfDay', 'TDP_kg/day', 'PPr_EndOfDay', 'PP_kg/day']
+
+
+def dry_network_inputs(n_draw, n_reaches, st_dt, end_dt, pscale=0.6, solver=None, out_mask=None, out_reaches=None):
+    """Config C4's chain (its upper `n_reaches` reaches), every member of an `n_draw`-member draw of C4's distribution (C4_SEED, both
+    dynamic options on), Tarland's forcing over [st_dt, end_dt] with the hydrological input x pscale and PET / pscale -- the dry
+    network of tests/golden/dry_network.npz and of tools/sweep_dry_network.py.  The run starts at st_dt: initial conditions come from
+    the parameters, as in the reference."""
+    from simplyp_amd import synthetic, marshal, abi
+    met_df, p_struc, p_SU, p_LU, p_SC, p, dyn = synthetic.c4_inputs(n_reaches, synthetic.C4_SEED, st_dt, end_dt)
+    marshal.prologue(p_SU, p_LU, p_SC, p)
+    up_ptr, up_idx, _ = marshal.topology(p_struc, p)
+    over = synthetic.monte_carlo_overrides(p, p_LU, n_draw, synthetic.C4_SEED)
+    mp = marshal.member_params(p, p_LU, n_draw, over)
+    rp = marshal.reach_params(p_SC, p, n_draw)
+    forcing, doy = marshal.forcing_arrays(met_df)
+    forcing = forcing.copy()
+    forcing[:, 0] *= pscale                                            # as make_golden.run_reference applies `pscale`
+    forcing[:, 1] /= pscale
+    opts = abi.make_opts(solver, dynamic_epc0=True, dynamic_erod=True, run_mode_cal=True, sc_qr0=int(n_reaches) - 1,
+                         out_mask=marshal.MASK_ALL if out_mask is None else out_mask)
+    return dict(forcing=forcing, doy=doy, member_params=mp, reach_params=rp, up_ptr=up_ptr, up_idx=up_idx, opts=opts,
+                out_reaches=out_reaches, met=met_df)
+
+
+def dry_network_problem(solver=None):
+    """Arrays + opts for tests/golden/dry_network.npz -- members of config C4's draw on the upper reaches of its chain on the dry
+    climate (0.6 x precipitation, PET / 0.6), two years, run through the unmodified reference at odeint (1e-12, 1e-15)
+    (tests/golden/make_golden.py --only drynet) -- and the reference tables: (problem dict with all 25 columns of the kept reaches and
+    only the fixture's members, {(position among the members, position among the kept reaches): table[D, 9]} for the (member, reach)
+    pairs the fixture holds -- c4_members_worst compares against it).  The parameter values are regenerated from the recorded seed and
+    checked against what the fixture recorded."""
+    from simplyp_amd import marshal
+    z = np.load(os.path.join(GOLDEN, 'dry_network.npz'), allow_pickle=False)
+    members = [int(m) for m in z['members']]
+    keep = [int(r) for r in z['reaches']]
+    st_dt, end_dt = (str(y) for y in z['years'])
+    pr = dry_network_inputs(int(z['n_draw']), int(z['n_reaches']), st_dt, end_dt, float(z['pscale']), solver=solver,
+                            out_reaches=[r - 1 for r in keep])
+    pr['member_params'] = np.ascontiguousarray(pr['member_params'][:, members])
+    pr['reach_params'] = np.ascontiguousarray(pr['reach_params'][:, :, members])
+    for k, nm in enumerate(str(n) for n in z['names']):                 # the generator still draws what the fixture recorded
+        np.testing.assert_array_equal(pr['member_params'][marshal.PM_NAMES.index(nm)], z['values'][k])
+    assert [str(c) for c in z['columns']] == REACH_COLS
+    D = pr['forcing'].shape[2]
+    tables = {(k, j): z['R/%d/%d' % (m, r)] for k, m in enumerate(members) for j, r in enumerate(keep) if 'R/%d/%d' % (m, r) in z.files}
+    assert all(t.shape == (D, 9) for t in tables.values())
+    pr['members'], pr['reaches'] = members, keep
+    return pr, tables
+
+
+def steplen_cases():
+    """[(scenario name, step_len)] of tests/golden/step_len.npz (tests/golden/make_golden.py --only steplen)."""
+    z = np.load(os.path.join(GOLDEN, 'step_len.npz'), allow_pickle=False)
+    return [(str(n), float(s)) for n, s in zip(z['names'], z['step_len'])]
+
+
+def steplen_problem(case, E=1, solver=None):
+    """Arrays + opts of case `case` of tests/golden/step_len.npz -- a golden scenario (marshal_scenario) run by the unmodified reference
+    with run_simply_p(..., step_len=s) at rtol = atol = 1e-12 -- and its tables: (problem dict with opts.step_len = s,
+    {SC: {column: series}} with the 9 reach columns of every reach and, where stored, the terrestrial columns)."""
+    z = np.load(os.path.join(GOLDEN, 'step_len.npz'), allow_pickle=False)
+    name, step_len = str(z['names'][case]), float(z['step_len'][case])
+    m = marshal_scenario(name, E=E, solver=solver)
+    m['opts'].step_len = step_len
+    tables = {}
+    for sc in m['scs']:
+        t = dict(zip(REACH_COLS, z['R/%d/%d' % (case, sc)].T))
+        if 'TC/%d/%d' % (case, sc) in z.files:
+            t.update(zip((str(c) for c in z['TC/%d/%d/columns' % (case, sc)]), z['TC/%d/%d' % (case, sc)].T))
+        tables[sc] = t
+    m['name'], m['step_len'] = name, step_len
+    return m, tables
+
+
+def steplen_errors(out, scs, tables, columns, member=0):
+    """{column: max relative error over the reaches} of out[n_cols, D, S, E] (columns = `columns`) against steplen_problem's tables,
+    over every column the fixture holds."""
+    errs = {}
+    for j, sc in enumerate(scs):
+        for c, ref in tables[sc].items():
+            errs[c] = max(errs.get(c, 0.0), max_rel_err(out[columns.index(c), :, j, member], ref, floor=1e-300))
+    return errs

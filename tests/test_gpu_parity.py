@@ -199,6 +199,10 @@ def test_argument_errors_come_back_as_exceptions(engine0):
     with pytest.raises(ValueError):
         engine0.run(m['forcing'][:, :, :100], m['doy'], m['member_params'], m['reach_params'],
                     m['up_ptr'], m['up_idx'], m['opts'])
+    for step_len in (0.0, -1.0, float('nan'), float('inf')):        # refused by check_args before any launch
+        with pytest.raises(engine.EngineError, match='step_len'):
+            engine0.run(m['forcing'], m['doy'], m['member_params'], m['reach_params'], m['up_ptr'], m['up_idx'],
+                        abi.make_opts(step_len=step_len))
 
 
 # ---------------------------------------------------------------------------------------------------

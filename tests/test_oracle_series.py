@@ -375,3 +375,80 @@ def test_oracle_default_solver_on_members_of_the_c4_distribution_against_the_ref
         worst = helpers.c4_members_worst(out, tables)
         assert max(worst.values()) < 1e-6, (stiff, worst)
     pr['opts'].stiff_pair = 0
+
+
+# ---------------------------------------------------------------------------------------------------
+# step_len != 1 (tests/golden/step_len.npz) and a dry reach network (tests/golden/dry_network.npz)
+
+STEPLEN_CASES = list(range(6))      # tarland_2004_dynamic at 0.5 and 2, chain4_val_2004 at 0.5 and 2, stiff_chain12_2004 at 0.25 and 2
+
+
+def test_steplen_fixture_holds_the_cases_it_names():
+    assert helpers.steplen_cases() == [('tarland_2004_dynamic', 0.5), ('tarland_2004_dynamic', 2.0), ('chain4_val_2004', 0.5),
+                                       ('chain4_val_2004', 2.0), ('stiff_chain12_2004', 0.25), ('stiff_chain12_2004', 2.0)]
+
+
+@pytest.mark.parametrize('case', STEPLEN_CASES)
+def test_oracle_at_step_len_against_the_reference(oracle_lib, case):
+    """run_simply_p(..., step_len=s) integrates every row over [0, s] (model.py:345) while the soil-P update and the upstream routing keep
+    their one-day forms (model.py:44, :524-528); the damping-aware weights scale with the span.  Against the unmodified reference at
+    rtol=atol=1e-12: the default solver within north_star's bar on every reach column of every reach (measured 5e-8 ... 3.0e-7, the
+    stiff chain at step_len 2 the largest), and converged Cash-Karp at rtol 1e-11 within 3e-9 (measured <= 1.6e-9: the fixture is
+    converged in the relative sense).  Where the terrestrial columns are stored, the drop-in test's bars hold on those too."""
+    errs = {}
+    for key, solver in (('default', None), ('converged', dict(integrator='cashkarp_aug', rtol=1e-11, atol=1e-13))):
+        m, tables = helpers.steplen_problem(case, solver=solver)
+        assert m['opts'].step_len == m['step_len'] != 1.0
+        out, status, _ = oracle_lib.run(m['forcing'], m['doy'], m['member_params'], m['reach_params'], m['up_ptr'], m['up_idx'], m['opts'])
+        assert status.max() == 0
+        errs[key] = helpers.steplen_errors(out, m['scs'], tables, marshal.OUT_COLUMNS)
+    reach = {k: max(e[c] for c in REACH_COLS) for k, e in errs.items()}
+    assert reach['default'] < 1e-6, (m['name'], m['step_len'], errs['default'])
+    assert reach['converged'] < 3e-9, (m['name'], m['step_len'], errs['converged'])
+    for c, e in errs['default'].items():
+        if c not in REACH_COLS:
+            assert e < (2e-5 if c in ('QsA', 'QsS', 'QsNC') else 1e-6), (m['name'], m['step_len'], c, e)
+
+
+def test_oracle_refuses_a_step_len_that_is_not_finite_and_positive(oracle_lib):
+    """As the library's check_args: 0, negative, NaN and infinite spans are refused before anything runs."""
+    m = helpers.marshal_scenario('tarland_2004_static')
+    for step_len in (0.0, -1.0, float('nan'), float('inf'), -float('inf')):
+        m['opts'].step_len = step_len
+        with pytest.raises(RuntimeError, match='simplyp_oracle_run failed'):
+            oracle_lib.run(m['forcing'], m['doy'], m['member_params'], m['reach_params'], m['up_ptr'], m['up_idx'], m['opts'])
+
+
+# the headwater's smallest daily mean flow in the reference's own table, below which the fixture counts as the dry-network regime
+DRY_NETWORK_HEADWATER_QR = 5e-3
+
+
+def test_dry_network_fixture_is_in_the_dry_regime():
+    """Read from the reference's tables themselves: some member's headwater nearly dries up (min daily Qr 2.9e-3 mm/d, against ~0.1 ... 0.6
+    for most of the draw), and its tables are those of the dry climate and of odeint at (1e-12, 1e-15)."""
+    import numpy as np
+    z = np.load(os.path.join(helpers.GOLDEN, 'dry_network.npz'), allow_pickle=False)
+    assert float(z['pscale']) == 0.6 and tuple(z['odeint_rtol_atol']) == (1e-12, 1e-15)
+    qr = REACH_COLS.index('Qr')
+    head = [float(z['R/%d/1' % m][:, qr].min()) for m in z['members']]
+    assert min(head) < DRY_NETWORK_HEADWATER_QR, head
+
+
+def test_oracle_on_a_dry_reach_network_against_the_reference(oracle_lib):
+    """tests/golden/dry_network.npz: members of config C4's draw on the upper 32 reaches of its chain, 1981-1982, on the dry fixture's
+    climate (0.6 x precipitation, PET / 0.6), through the unmodified reference at odeint (1e-12, 1e-15) -- the network scheme (second
+    pair, damping-aware weights) where headwaters nearly dry up; the kept reaches include each member's worst reach of the selection
+    sweep (tools/sweep_dry_network.py), not only the outlet.  Default solver (second pair on: a network): north_star's bar on every kept
+    reach (measured 6.8e-7, member 112 at reach 3; Cash-Karp alone at the default tolerance: 3.6e-7); Cash-Karp alone at rtol 1e-11:
+    within 2e-8 (measured 5.8e-9: the reference's tables are converged in the relative sense where the reach nearly dries up)."""
+    res = {}
+    for key, solver, stiff in (('default', None, 0), ('converged', dict(rtol=1e-11, atol=1e-13), -1)):
+        pr, tables = helpers.dry_network_problem(solver=solver)
+        pr['opts'].stiff_pair = stiff
+        out, status, stats = oracle_lib.run(pr['forcing'], pr['doy'], pr['member_params'], pr['reach_params'], pr['up_ptr'], pr['up_idx'],
+                                            pr['opts'], out_reaches=pr['out_reaches'], n_threads=8)
+        assert status.max() == 0
+        res[key] = helpers.c4_members_worst(out, tables)
+    worst = {k: max(v.values()) for k, v in res.items()}
+    assert worst['default'] < 1e-6, res['default']
+    assert worst['converged'] < 2e-8, res['converged']
