@@ -70,13 +70,8 @@ struct simplyp_ctx {
     int streamed_chunks = 0;            // chunks whose copy started before the kernel had finished
     bool copy_pending = false;
     std::chrono::steady_clock::time_point t_begin;
-    int lanes = 64;           // member slots per wavefront of the last run
-    int team = 1;             // lanes per member of the last run (1, or 4 = one member per DPP quad)
-    int stiff = 0;            // last run used the stability-optimised second pair (opts.stiff_pair)
-    int queued = 0;           // last run used the task-queue kernel
     int n_simd_slots = 1024;  // CUs x 4 SIMDs: wave slots at one resident wave per SIMD
-    int balanced = 0;         // last run used the cost-sorted member order
-    int n_launches = 0;
+    simplyp_stats last = {};  // what the shape of the last run decides of its stats (simplyp_sync adds the measurements)
     bool pending = false;
     std::string error;
 };
@@ -390,11 +385,11 @@ void copier_main(simplyp_ctx* ctx)
     if (err != hipSuccess && !ctx->copy_error) ctx->copy_error = (int)err;
 }
 
-int check_args(simplyp_ctx* ctx, const simplyp_dims* dims, const simplyp_opts* opts, const void* forcing,
-               const void* mp, const void* rp, const int32_t* up_ptr, const void* out, const void* status,
-               const int32_t* out_reaches, int32_t n_out_reaches)
+int check_args(simplyp_ctx* ctx, const simplyp_dims* dims, const simplyp_opts* opts, const void* forcing, const int32_t* doy,
+               const int32_t* period_of_day, const void* mp, const void* rp, const int32_t* up_ptr, const int32_t* up_idx,
+               const void* out, const void* status, const int32_t* member_of_slot, const int32_t* out_reaches,
+               int32_t n_out_reaches, const double* host_out, int64_t host_out_bytes)
 {
-    if (!ctx) return SIMPLYP_ERR_ARG;
     if (!dims || !opts) return fail(ctx, SIMPLYP_ERR_ARG, "dims/opts is NULL");
     if (dims->E <= 0 || dims->S <= 0 || dims->D <= 0 || dims->n_forcing_sets <= 0)
         return fail(ctx, SIMPLYP_ERR_ARG, "bad dims E=%d S=%d D=%d n_forcing_sets=%d", dims->E, dims->S, dims->D,
@@ -428,7 +423,370 @@ int check_args(simplyp_ctx* ctx, const simplyp_dims* dims, const simplyp_opts* o
         for (int k = 0; k < n_out_reaches; ++k)
             if (out_reaches[k] < 0 || out_reaches[k] >= dims->S) return fail(ctx, SIMPLYP_ERR_ARG, "out_reaches[%d] out of range", k);
     }
+    if (host_out && host_out_bytes < simplyp_out_bytes(dims, opts, out_reaches ? n_out_reaches : dims->S))
+        return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_stream_out: host buffer of %lld bytes is smaller than the output table (%lld)",
+                    (long long)host_out_bytes, (long long)simplyp_out_bytes(dims, opts, out_reaches ? n_out_reaches : dims->S));
+    if (opts->dynamic_erod && !doy) return fail(ctx, SIMPLYP_ERR_ARG, "doy is required when dynamic_erod is set");
+    if (opts->n_periods < 0 || (opts->n_periods > 0 && !period_of_day))
+        return fail(ctx, SIMPLYP_ERR_ARG, "n_periods > 0 needs period_of_day (and n_periods must not be negative)");
+    if (opts->out_slot_order && !member_of_slot)
+        return fail(ctx, SIMPLYP_ERR_ARG, "out_slot_order = 1 needs member_of_slot");
+    if (up_ptr[dims->S] > 0 && !up_idx) return fail(ctx, SIMPLYP_ERR_ARG, "up_idx is NULL but up_ptr lists upstream reaches");
     return SIMPLYP_OK;
+}
+
+// The shape of a run: how members map to lanes and waves, which pair and kernel run it, how it cuts time and whether a pilot
+// balances it first.  Decided from the arguments, the chip's wave slots and whether a streamed output is armed; no HIP call.
+struct RunShape {
+    int team = 1;                  // lanes per member: 1, or 4 = one member per DPP quad
+    int lanes = simplyp::WAVE;     // member slots per wavefront
+    unsigned gx = 0;               // member groups: waves per chain
+    bool stiff = false;            // integrator 2 with the stability-optimised second pair
+    bool stream_chunks = false;    // a streamed output wants the table in time chunks
+    int chunk_days = 0, n_chunks = 0;
+    bool want_queue = false;       // the task-queue kernel as wanted (launch_queue falls back to the chain kernel if it does not fit)
+    int pilot_days = 0;
+    bool balance = false;          // a pilot run orders the members by cost
+};
+
+RunShape plan_run(const simplyp_dims& dims, const simplyp_opts& opts, int n_simd_slots, bool streamed)
+{
+    const int E = dims.E, S = dims.S, D = dims.D;
+    RunShape r;
+    // Member slots per wavefront.  64 unless the ensemble cannot fill the chip with full waves: a single-reach ensemble under an
+    // adaptive integrator is then spread over as many waves as there are SIMDs (a wave's day costs its slowest lane's attempts;
+    // idle SIMDs cost nothing).  Results do not depend on it (members are independent).
+    // Lanes per member: 1, or 4 -- a member's Cash-Karp attempt spread over a DPP quad (ck_day_quad: ~1.4 x shorter attempts,
+    // bit-identical results) -- when the ensemble is so small that even then every (member group, reach) finds a resident wave
+    // of its own: the run is bound by one member's serial chain of attempts, not by throughput.  A single-reach ensemble may be
+    // up to 1.75 x larger than that: its quads then run through the work-conserving task queue in ~1.5 rounds of waves that all
+    // SIMDs share, where the one-lane kernel would keep a third of the SIMDs busy for one long round (measured, MI355X:
+    // 25 000 members 477 against 598 ms, 30 000 members 571 against 600, 40 000 members 759 against 610).
+    const long long quad_waves = (long long)((E + 15) / 16) * S;
+    if (opts.integrator == SIMPLYP_INTEG_CASHKARP_AUG &&
+        (opts.lanes_per_member == 4 ||
+         (opts.lanes_per_member == 0 && (quad_waves <= (long long)n_simd_slots ||
+                                         (S == 1 && quad_waves * 4 <= 7LL * n_simd_slots)))))
+        r.team = 4;
+    const int max_lanes = simplyp::WAVE / r.team;
+    r.lanes = max_lanes;
+    if (opts.lanes_per_wave > 0) r.lanes = std::min<int>(max_lanes, opts.lanes_per_wave);
+    else if (opts.integrator != SIMPLYP_INTEG_RK4 && S == 1 && (E + max_lanes - 1) / max_lanes < n_simd_slots)
+        r.lanes = std::max(1, (E + n_simd_slots - 1) / n_simd_slots);
+    r.gx = (unsigned)((E + r.lanes - 1) / r.lanes);
+    // opts.stiff_pair (integrator 2): attempts bound by Cash-Karp's stability interval go to the second pair; auto = reach networks
+    r.stiff = opts.integrator == SIMPLYP_INTEG_CASHKARP_AUG && SIMPLYP_STIFF_PAIR_ON(opts.stiff_pair, S);
+    // (a streamed output wants time chunks: their rows travel to the host while later chunks compute -- and short ones, so that
+    // the first copy starts early: the copies, not the kernel, bound a streamed pass; 64 days cost ~0.4 % in task overhead)
+    r.stream_chunks = streamed && opts.n_periods == 0;
+    r.chunk_days = opts.time_chunk_days > 0 ? opts.time_chunk_days : ((r.stream_chunks && S == 1) ? 64 : 256);
+    r.chunk_days = ((r.chunk_days + 63) / 64) * 64;
+    r.n_chunks = (D + r.chunk_days - 1) / r.chunk_days;
+    // task-queue kernel, auto: when the chain kernel would leave SIMDs idle -- a single-reach ensemble that needs more waves than
+    // the chip holds at once, or a multi-reach network (a chain walked by one thread per member cannot use more than E lanes)
+    r.want_queue = opts.integrator != SIMPLYP_INTEG_RK4 && D > r.chunk_days &&
+        (opts.time_chunk_days > 0 || (r.stream_chunks && opts.time_chunk_days == 0) ||
+         (opts.time_chunk_days == 0 && ((S == 1 && (int)r.gx > n_simd_slots) || (S > 1 && (int)r.gx < n_simd_slots))));
+    // Load balance (Cash-Karp only: members differ in the steps they need).
+    // With more waves than the chip holds at once, the run takes as long as the unluckiest SIMD's queue.
+    // A short pilot run measures each member's cost; members are then handed to lane slots in order of
+    // decreasing cost, so (a) the lanes of a wave need similar step counts and (b) the dispatcher starts
+    // the long waves first and back-fills with the short ones (longest-processing-time-first).
+    r.pilot_days = opts.balance_pilot_days > 0 ? opts.balance_pilot_days : 64;
+    if (r.pilot_days > D) r.pilot_days = D;
+    // auto: a single-reach ensemble that needs more waves than the chip holds at once; a reach network that will run through
+    // the task queue with at least four member groups (there every SIMD works through many tasks, so homogeneous groups pay;
+    // with one wave per SIMD sorting only makes the slowest wave slower).  It reads the queue as wanted: a queue that does not
+    // fit and falls back to the chain kernel leaves the decision as it is.
+    r.balance = opts.integrator != SIMPLYP_INTEG_RK4 && r.pilot_days * 4 <= D &&
+        (opts.balance == 1 ||
+         (opts.balance == 2 && ((int)r.gx > n_simd_slots || (S > 1 && r.want_queue && r.gx >= 4u))));
+    return r;
+}
+
+// Pilot launches of the load balancer on a reach network: the routing schedule cut off PILOT_LEVELS reaches below the
+// headwaters (chains keep their first elements; the slot assignments of the full schedule stay valid for a subset run
+// in the same order).  Every reach of a member shares the member's parameters, so its cost rank among the members
+// carries over to the reaches further down; a 256-reach chain is sampled by its first 8 reaches.
+constexpr int PILOT_LEVELS = 8;
+
+// What the pilot and the task queue derive from the reach graph.
+struct Topology {
+    std::vector<int> level;                        // [S] longest path from a headwater
+    std::vector<Launch> pilot;                     // the pilot's launches (those left with no reach are dropped)
+    std::vector<int> down_ptr, down_idx, qslot;    // queue: downstream CSR; [S] ring buffer of a reach read downstream, or -1
+    int n_route = 0, ring_chunks = 0;              // ring buffers, time chunks a ring buffer holds
+};
+
+Topology derive_topology(int S, const int32_t* up_ptr, const int32_t* up_idx, const Schedule& sch, int n_chunks)
+{
+    Topology t;
+    t.level.assign(S, 0);
+    for (int s = 0; s < S; ++s)
+        for (int k = up_ptr[s]; k < up_ptr[s + 1]; ++k) t.level[s] = std::max(t.level[s], t.level[up_idx[k]] + 1);
+    for (const Launch& L : sch.launches) {
+        Launch P;
+        P.chain_ptr.push_back(0);
+        for (size_t c = 0; c + 1 < L.chain_ptr.size(); ++c) {
+            for (int i = L.chain_ptr[c]; i < L.chain_ptr[c + 1] && t.level[L.chain_reach[i]] < PILOT_LEVELS; ++i)
+                P.chain_reach.push_back(L.chain_reach[i]);
+            if ((int)P.chain_reach.size() > P.chain_ptr.back()) P.chain_ptr.push_back((int)P.chain_reach.size());
+        }
+        if (!P.chain_reach.empty()) t.pilot.push_back(std::move(P));
+    }
+    std::vector<int> n_down(S, 0);
+    int max_jump = 0;
+    for (int s = 0; s < S; ++s)
+        for (int k = up_ptr[s]; k < up_ptr[s + 1]; ++k) { max_jump = std::max(max_jump, t.level[s] - t.level[up_idx[k]]); ++n_down[up_idx[k]]; }
+    t.ring_chunks = std::min(n_chunks, max_jump + 1);
+    t.down_ptr.assign(S + 1, 0);
+    t.down_idx.assign((size_t)std::max(1, (int)up_ptr[S]), 0);
+    t.qslot.assign(S, -1);
+    for (int s = 0; s < S; ++s) t.down_ptr[s + 1] = t.down_ptr[s] + n_down[s];
+    { std::vector<int> fill(t.down_ptr.begin(), t.down_ptr.end() - 1);
+      for (int s = 0; s < S; ++s) for (int k = up_ptr[s]; k < up_ptr[s + 1]; ++k) t.down_idx[fill[up_idx[k]]++] = s; }
+    for (int s = 0; s < S; ++s) if (n_down[s] > 0) t.qslot[s] = t.n_route++;
+    return t;
+}
+
+template <int V> using Int = std::integral_constant<int, V>;
+
+// Calls fn(integrator, snow, team, stiff), each a std::integral_constant, for the run's kernel: RK4, Cash-Karp and the fp32
+// mirror at one lane per member, integrator 2 at one or four lanes with or without the stiff pair; each with snow on and off.
+template <class F>
+void dispatch_kernel(const simplyp_opts& opts, const RunShape& shape, F&& fn)
+{
+    auto with_snow = [&](auto integ, auto team, auto stiff) {
+        if (opts.snow) fn(integ, std::true_type{}, team, stiff);
+        else fn(integ, std::false_type{}, team, stiff);
+    };
+    auto with_team = [&](auto stiff) {          // integrator 2
+        if (shape.team == 4) with_snow(Int<SIMPLYP_INTEG_CASHKARP_AUG>{}, Int<4>{}, stiff);
+        else with_snow(Int<SIMPLYP_INTEG_CASHKARP_AUG>{}, Int<1>{}, stiff);
+    };
+    if (opts.integrator == SIMPLYP_INTEG_RK4) with_snow(Int<SIMPLYP_INTEG_RK4>{}, Int<1>{}, std::false_type{});
+    else if (opts.integrator == SIMPLYP_INTEG_CASHKARP) with_snow(Int<SIMPLYP_INTEG_CASHKARP>{}, Int<1>{}, std::false_type{});
+    else if (opts.integrator == SIMPLYP_INTEG_CASHKARP_AUG_F32) with_snow(Int<SIMPLYP_INTEG_CASHKARP_AUG_F32>{}, Int<1>{}, std::false_type{});
+    else if (shape.stiff) with_team(std::true_type{});
+    else with_team(std::false_type{});
+}
+
+// One launch of the chain kernel: n_chains mutually independent chains, at these offsets of the uploaded schedule block.
+struct ChainLaunch { size_t off_ptr, off_reach; unsigned n_chains; };
+
+int launch_chains(simplyp_ctx* ctx, const simplyp_opts& opts, const RunShape& shape, simplyp::KernelArgs k, const ChainLaunch& c,
+                  unsigned n_windows = 1u)
+{
+    k.chain_ptr = (const int*)ctx->sched.ptr + c.off_ptr;
+    k.chain_reach = (const int*)ctx->sched.ptr + c.off_reach;
+    const dim3 grid(shape.gx, c.n_chains, n_windows), block(simplyp::WAVE, 1, 1);
+    dispatch_kernel(opts, shape, [&](auto integ, auto snow, auto team, auto stiff) {
+        hipLaunchKernelGGL((simplyp::simplyp_chain_kernel<integ, snow, team, stiff>), grid, block, 0, ctx->stream, k);
+    });
+    HIP_TRY(ctx, hipGetLastError());
+    return SIMPLYP_OK;
+}
+
+// Uploads the int32 schedule block -- up_ptr | up_idx | route_slot | out_slot | per launch: chain_ptr | chain_reach, the
+// schedule's launches, then the pilot's -- and zeroes the counters and the per-member outputs; `a` then points at both.
+int upload_schedule(simplyp_ctx* ctx, const Schedule& sch, const Topology& topo, const int32_t* up_ptr, const int32_t* up_idx,
+                    const int32_t* out_reaches, simplyp::KernelArgs& a, std::vector<ChainLaunch>& launches,
+                    std::vector<ChainLaunch>& pilot)
+{
+    const int S = a.S;
+    if (int rc = ensure(ctx, ctx->counters, simplyp_ctx::N_COUNTERS * sizeof(unsigned long long))) return rc;
+    std::vector<int> out_slot(S, -1);
+    if (out_reaches) for (int k = 0; k < a.n_out_reaches; ++k) out_slot[out_reaches[k]] = k;
+    else std::iota(out_slot.begin(), out_slot.end(), 0);
+    std::vector<int> host;
+    auto put = [&](const int* v, size_t n) { const size_t at = host.size(); host.insert(host.end(), v, v + n); return at; };
+    const size_t off_up_ptr = put(up_ptr, S + 1), off_up_idx = put(up_idx, up_ptr[S]);
+    const size_t off_rslot = put(sch.route_slot.data(), S), off_oslot = put(out_slot.data(), S);
+    auto put_launches = [&](const std::vector<Launch>& ls, std::vector<ChainLaunch>& to) {
+        for (const Launch& L : ls) {
+            const size_t off_ptr = put(L.chain_ptr.data(), L.chain_ptr.size());
+            to.push_back({off_ptr, put(L.chain_reach.data(), L.chain_reach.size()), (unsigned)L.chain_ptr.size() - 1u});
+        }
+    };
+    put_launches(sch.launches, launches);
+    put_launches(topo.pilot, pilot);
+    if (int rc = ensure(ctx, ctx->sched, host.size() * sizeof(int))) return rc;
+    // pageable source: the copy is staged before hipMemcpyAsync returns, `host` may go out of scope
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->sched.ptr, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.ptr, 0, simplyp_ctx::N_COUNTERS * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(a.status, 0, (size_t)a.E * sizeof(int32_t), ctx->stream));
+    if (a.member_rhs) HIP_TRY(ctx, hipMemsetAsync(a.member_rhs, 0, (size_t)a.E * sizeof(uint32_t), ctx->stream));
+    const int* dsched = (const int*)ctx->sched.ptr;
+    a.up_ptr = dsched + off_up_ptr; a.up_idx = dsched + off_up_idx;
+    a.route_slot = dsched + off_rslot; a.out_slot = dsched + off_oslot;
+    a.counters = (unsigned long long*)ctx->counters.ptr;
+    return SIMPLYP_OK;
+}
+
+// The pilot: PILOT_WINDOWS short runs from the initial conditions, each over a different stretch of the forcing (spread over
+// the first two years when the run is long enough, so that the seasons are sampled), one cost counter per member and window.
+// Then the members' lane-slot order (order_members), and slot-ordered copies of the parameter tables for `a`.
+int balance_members(simplyp_ctx* ctx, const simplyp_opts& opts, const RunShape& shape, const Schedule& sch,
+                    const std::vector<ChainLaunch>& pilot, simplyp::KernelArgs& a)
+{
+    const int E = a.E, S = a.S, D = a.D;
+    constexpr int PILOT_WINDOWS = 8;
+    const int win_days = std::max(1, shape.pilot_days / PILOT_WINDOWS);
+    const int win_stride = std::max(win_days, std::min(80, (D - win_days) / (PILOT_WINDOWS - 1)));      // ~1.6 years covered
+    if (int rc = ensure(ctx, ctx->balance, (size_t)E * (PILOT_WINDOWS * sizeof(uint32_t) + sizeof(int32_t)))) return rc;
+    uint32_t* d_cost = (uint32_t*)ctx->balance.ptr;
+    int32_t* d_perm = (int32_t*)(d_cost + (size_t)PILOT_WINDOWS * E);
+    HIP_TRY(ctx, hipMemsetAsync(d_cost, 0, (size_t)PILOT_WINDOWS * E * sizeof(uint32_t), ctx->stream));
+    simplyp::KernelArgs p = a;
+    p.D = win_days;                   // forcing rows keep their stride of D days
+    p.route_days = win_days;
+    const size_t win_route = (size_t)sch.n_slots * 4 * win_days * E;      // doubles of routing scratch per window
+    if (sch.n_slots > 0) {
+        if (int rc = ensure(ctx, ctx->route, (size_t)PILOT_WINDOWS * win_route * sizeof(double))) return rc;
+        p.route = (double*)ctx->route.ptr;
+    }
+    // all windows in one launch per schedule level (blockIdx.z = window): 8 x 1563 waves fill the chip's rounds, where
+    // 8 launches of 1563 waves would each leave a half-empty second round
+    p.win_stride = win_stride;
+    p.win_route_stride = (long long)win_route;
+    p.member_rhs = d_cost;
+    for (const ChainLaunch& c : pilot)
+        if (int rc = launch_chains(ctx, opts, shape, p, c, (unsigned)PILOT_WINDOWS)) return rc;
+    std::vector<uint32_t> cost((size_t)PILOT_WINDOWS * E);
+    HIP_TRY(ctx, hipMemcpyAsync(cost.data(), d_cost, cost.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<int32_t> perm;
+    order_members(cost, PILOT_WINDOWS, E, perm);
+    HIP_TRY(ctx, hipMemcpyAsync(d_perm, perm.data(), (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // the pilot's bookkeeping must not leak into the real run
+    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.ptr, 0, simplyp_ctx::N_COUNTERS * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(a.status, 0, (size_t)E * sizeof(int32_t), ctx->stream));
+    a.perm = d_perm;
+    // slot-ordered copies of the parameter tables: the main kernels then read them coalesced
+    const size_t n_mp = (size_t)SIMPLYP_NP_M * E, n_rp = (size_t)SIMPLYP_NP_R * S * E;
+    const size_t bytes = (n_mp + n_rp) * sizeof(double) + (a.forcing_of_member ? (size_t)E * sizeof(int32_t) : 0);
+    if (int rc = ensure(ctx, ctx->sorted_params, bytes)) return rc;
+    double* s_mp = (double*)ctx->sorted_params.ptr;
+    double* s_rp = s_mp + n_mp;
+    int32_t* s_fom = (int32_t*)(s_rp + n_rp);
+    const dim3 gb(256), gg((unsigned)((E + 255) / 256), 16);
+    hipLaunchKernelGGL(simplyp::gather_columns_kernel<double>, gg, gb, 0, ctx->stream, a.mp, s_mp, d_perm, (int)SIMPLYP_NP_M, E);
+    hipLaunchKernelGGL(simplyp::gather_columns_kernel<double>, gg, gb, 0, ctx->stream, a.rp, s_rp, d_perm, (int)SIMPLYP_NP_R * S, E);
+    if (a.forcing_of_member)
+        hipLaunchKernelGGL(simplyp::gather_columns_kernel<int32_t>, dim3(gg.x, 1), gb, 0, ctx->stream, a.forcing_of_member, s_fom, d_perm, 1, E);
+    HIP_TRY(ctx, hipGetLastError());
+    a.mp = s_mp; a.rp = s_rp;
+    if (a.forcing_of_member) a.forcing_of_member = s_fom;
+    a.params_by_slot = 1;
+    return SIMPLYP_OK;
+}
+
+// Task-queue kernel: (reach, time chunk, member group) tasks pulled by one persistent wave per SIMD.  `queued` stays false, and
+// nothing is enqueued, when the ring buffers of the routing series do not fit: the run then takes the chain kernel.
+int launch_queue(simplyp_ctx* ctx, const simplyp_opts& opts, const RunShape& shape, const Topology& topo,
+                 const simplyp::KernelArgs& a, bool& queued)
+{
+    const int E = a.E, S = a.S, G = (int)shape.gx, n_chunks = shape.n_chunks, chunk_days = shape.chunk_days;
+    const size_t ring_days = (size_t)topo.ring_chunks * chunk_days;
+    const size_t route_bytes = (size_t)topo.n_route * 4 * ring_days * E * sizeof(double);
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    if (route_bytes > ctx->route.bytes && route_bytes - ctx->route.bytes > free_b / 10 * 9) return SIMPLYP_OK;   // does not fit: chain kernel
+    // (reach, chunk) pairs in dependency order: by level + chunk, then reach
+    std::vector<int> pair_idx((size_t)S * n_chunks);
+    std::iota(pair_idx.begin(), pair_idx.end(), 0);
+    std::stable_sort(pair_idx.begin(), pair_idx.end(), [&](int x, int y) {
+        const int kx = topo.level[x / n_chunks] + x % n_chunks, ky = topo.level[y / n_chunks] + y % n_chunks;
+        return kx != ky ? kx < ky : x < y;
+    });
+    std::vector<int> qi;                       // task_reach | task_chunk | down_ptr | down_idx | qslot
+    for (int v : pair_idx) qi.push_back(v / n_chunks);
+    for (int v : pair_idx) qi.push_back(v % n_chunks);
+    const size_t off_dptr = qi.size(); qi.insert(qi.end(), topo.down_ptr.begin(), topo.down_ptr.end());
+    const size_t off_didx = qi.size(); qi.insert(qi.end(), topo.down_idx.begin(), topo.down_idx.end());
+    const size_t off_qslot = qi.size(); qi.insert(qi.end(), topo.qslot.begin(), topo.qslot.end());
+    const size_t flags_bytes = (((size_t)S * G + 4) * sizeof(unsigned) + 255) / 256 * 256;      // ticket, error, progress, (pad), done[S][G]
+    const size_t ints_bytes = (qi.size() * sizeof(int) + 255) / 256 * 256;
+    if (int rc = ensure(ctx, ctx->queue, flags_bytes + ints_bytes + (size_t)S * simplyp::CKPT_N * E * sizeof(double))) return rc;
+    if (route_bytes) { if (int rc = ensure(ctx, ctx->route, route_bytes)) return rc; }
+    char* base = (char*)ctx->queue.ptr;
+    HIP_TRY(ctx, hipMemsetAsync(base, 0, flags_bytes, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(base + flags_bytes, qi.data(), qi.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    simplyp::QueueArgs q;
+    unsigned* flags = (unsigned*)base;
+    const int* dq = (const int*)(base + flags_bytes);
+    q.ticket = flags; q.error = flags + 1; q.progress = flags + 2; q.done = flags + 4;
+    q.task_reach = dq; q.task_chunk = dq + pair_idx.size();
+    q.down_ptr = dq + off_dptr; q.down_idx = dq + off_didx;
+    q.ckpt = (double*)(base + flags_bytes + ints_bytes);
+    q.n_groups = G; q.n_pairs = (int)pair_idx.size(); q.chunk_days = chunk_days; q.ring_chunks = topo.ring_chunks;
+    q.chunk_count = nullptr; q.host_ready = nullptr; q.tasks_per_chunk = (unsigned)S * (unsigned)G;
+    if (shape.stream_chunks) {
+        if (int rc = ensure(ctx, ctx->chunk_count, (size_t)n_chunks * sizeof(unsigned))) return rc;
+        if ((size_t)n_chunks > ctx->host_ready_cap) {
+            if (ctx->host_ready) { (void)hipHostFree(ctx->host_ready); ctx->host_ready = nullptr; ctx->host_ready_cap = 0; }
+            // COHERENT (fine-grained) host memory, asked for explicitly: a flag raised by a running kernel must reach the
+            // polling host thread before the kernel ends, which only fine-grained memory promises
+            HIP_TRY(ctx, hipHostMalloc((void**)&ctx->host_ready, (size_t)n_chunks * sizeof(uint32_t),
+                                       hipHostMallocCoherent | hipHostMallocMapped));
+            ctx->host_ready_cap = (size_t)n_chunks;
+        }
+        memset(ctx->host_ready, 0, (size_t)n_chunks * sizeof(uint32_t));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->chunk_count.ptr, 0, (size_t)n_chunks * sizeof(unsigned), ctx->stream));
+        q.chunk_count = (unsigned*)ctx->chunk_count.ptr;
+        q.host_ready = ctx->host_ready;
+        ctx->copy_plan.n_chunks = n_chunks;
+        ctx->copy_plan.chunk_days = chunk_days;
+    }
+    q.max_polls = 20000000u;      // x (s_sleep 64 ~ 2 us): ~40 s in which NO task of the run completed means something is broken
+    if (const char* mp_env = getenv("SIMPLYP_QUEUE_MAX_POLLS")) q.max_polls = (unsigned)strtoul(mp_env, nullptr, 10);
+    simplyp::KernelArgs k = a;
+    k.route = (double*)ctx->route.ptr;
+    k.route_days = (int)ring_days;
+    k.route_slot = dq + off_qslot;
+    const unsigned workers = (unsigned)std::min<long long>((long long)pair_idx.size() * G, ctx->n_simd_slots);
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_main, ctx->stream));
+    dispatch_kernel(opts, shape, [&](auto integ, auto snow, auto team, auto stiff) {
+        if constexpr (integ != SIMPLYP_INTEG_RK4)      // (plan_run never queues RK4)
+            hipLaunchKernelGGL((simplyp::simplyp_queue_kernel<integ, snow, team, stiff>), dim3(workers), dim3(simplyp::WAVE), 0,
+                               ctx->stream, k, q);
+    });
+    HIP_TRY(ctx, hipGetLastError());
+    if (getenv("SIMPLYP_DEBUG")) fprintf(stderr, "[simplyp] queue kernel launched: S=%d G=%d pairs=%zu chunk=%d ring=%d workers=%u max_polls=%u\n", S, G, pair_idx.size(), chunk_days, topo.ring_chunks, workers, q.max_polls);
+    queued = true;
+    return SIMPLYP_OK;
+}
+
+// The copy of the output table to the buffer simplyp_stream_out armed: chunk by chunk beside the queue kernel (`chunked`), or
+// the whole table behind the last launch.
+int arm_copy(simplyp_ctx* ctx, double* host_out, const simplyp_opts& opts, const simplyp::KernelArgs& a, bool chunked)
+{
+    simplyp_ctx::CopyPlan& cp = ctx->copy_plan;
+    cp.dev = a.out; cp.host = host_out;
+    cp.ncols = popcount32(a.out_mask);
+    cp.D = (size_t)(opts.n_periods > 0 ? opts.n_periods : a.D);
+    cp.row_doubles = (size_t)a.n_out_reaches * a.E;
+    if (chunked) {
+        ctx->run_over.store(0, std::memory_order_release);
+        ctx->copier = std::thread(copier_main, ctx);       // chunk by chunk, beside the kernel
+    } else {
+        // no time chunks in this run (chain kernel, RK4, time-reduced rows): the whole table follows the last launch
+        HIP_TRY(ctx, hipMemcpyAsync(host_out, a.out, cp.ncols * cp.D * cp.row_doubles * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_copy_done, ctx->stream));
+    }
+    ctx->copy_pending = true;
+    return SIMPLYP_OK;
+}
+
+// Tells the copier thread that the run is over (whatever chunk flag is still down stays down) and joins it: every chunk's
+// copy is enqueued when it returns.
+void stop_copier(simplyp_ctx* ctx)
+{
+    ctx->run_over.store(1, std::memory_order_release);
+    if (ctx->copier.joinable()) ctx->copier.join();
 }
 
 }  // namespace
@@ -502,8 +860,7 @@ void simplyp_ctx_destroy(simplyp_ctx* ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    ctx->run_over.store(1, std::memory_order_release);
-    if (ctx->copier.joinable()) ctx->copier.join();
+    stop_copier(ctx);
     for (int i = 0; i < simplyp_ctx::N_COPY_STREAMS; ++i) {
         if (ctx->copy_streams[i]) { (void)hipStreamSynchronize(ctx->copy_streams[i]); (void)hipStreamDestroy(ctx->copy_streams[i]); }
         if (ctx->ev_copy_join[i]) (void)hipEventDestroy(ctx->ev_copy_join[i]);
@@ -594,270 +951,42 @@ static int run_async_body(simplyp_ctx* ctx, const simplyp_dims* dims, const simp
     double* const host_out = ctx->stream_host;
     const int64_t host_out_bytes = ctx->stream_host_bytes;
     ctx->stream_host = nullptr; ctx->stream_host_bytes = 0;
-    int rc = check_args(ctx, dims, opts, forcing, member_params, reach_params, up_ptr, out, member_status,
-                        out_reaches, n_out_reaches);
-    if (rc != SIMPLYP_OK) return rc;
+    if (int rc = check_args(ctx, dims, opts, forcing, doy, period_of_day, member_params, reach_params, up_ptr, up_idx, out,
+                            member_status, member_of_slot, out_reaches, n_out_reaches, host_out, host_out_bytes))
+        return rc;
     ctx->t_begin = std::chrono::steady_clock::now();
     ctx->copy_pending = false; ctx->copy_error = 0; ctx->streamed_chunks = 0;
     ctx->copy_plan.n_chunks = 0;
-    if (host_out && host_out_bytes < simplyp_out_bytes(dims, opts, out_reaches ? n_out_reaches : dims->S))
-        return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_stream_out: host buffer of %lld bytes is smaller than the output table (%lld)",
-                    (long long)host_out_bytes, (long long)simplyp_out_bytes(dims, opts, out_reaches ? n_out_reaches : dims->S));
-    if (opts->dynamic_erod && !doy) return fail(ctx, SIMPLYP_ERR_ARG, "doy is required when dynamic_erod is set");
-    if (opts->n_periods < 0 || (opts->n_periods > 0 && !period_of_day))
-        return fail(ctx, SIMPLYP_ERR_ARG, "n_periods > 0 needs period_of_day (and n_periods must not be negative)");
-    if (opts->out_slot_order && !member_of_slot)
-        return fail(ctx, SIMPLYP_ERR_ARG, "out_slot_order = 1 needs member_of_slot");
     const int E = dims->E, S = dims->S, D = dims->D;
-    if (up_ptr[S] > 0 && !up_idx) return fail(ctx, SIMPLYP_ERR_ARG, "up_idx is NULL but up_ptr lists upstream reaches");
-
     Schedule sch;
-    rc = build_schedule(ctx, S, up_ptr, up_idx, sch);
+    int rc = build_schedule(ctx, S, up_ptr, up_idx, sch);
     if (rc != SIMPLYP_OK) return rc;
+    const RunShape shape = plan_run(*dims, *opts, ctx->n_simd_slots, host_out != nullptr);
+    const Topology topo = derive_topology(S, up_ptr, up_idx, sch, shape.n_chunks);
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-
-    // ---- device scratch: schedule, counters (the routing series are sized where their length is known: pilot windows,
-    // ring buffers of the task queue, or whole-run series of the chain kernel) ----
-    rc = ensure(ctx, ctx->counters, simplyp_ctx::N_COUNTERS * sizeof(unsigned long long));
-    if (rc != SIMPLYP_OK) return rc;
-
-    // int32 schedule block: up_ptr | up_idx | route_slot | out_slot | per launch: chain_ptr | chain_reach
-    std::vector<int> out_slot(S, out_reaches ? -1 : 0);
-    if (out_reaches) for (int k = 0; k < n_out_reaches; ++k) out_slot[out_reaches[k]] = k;
-    else { for (int s = 0; s < S; ++s) out_slot[s] = s; n_out_reaches = S; }
-    std::vector<int> host;
-    const size_t off_up_ptr = host.size(); host.insert(host.end(), up_ptr, up_ptr + S + 1);
-    const size_t off_up_idx = host.size(); if (up_ptr[S] > 0) host.insert(host.end(), up_idx, up_idx + up_ptr[S]);
-    const size_t off_rslot = host.size(); host.insert(host.end(), sch.route_slot.begin(), sch.route_slot.end());
-    const size_t off_oslot = host.size(); host.insert(host.end(), out_slot.begin(), out_slot.end());
-    std::vector<size_t> off_cptr, off_creach;
-    for (const Launch& L : sch.launches) {
-        off_cptr.push_back(host.size()); host.insert(host.end(), L.chain_ptr.begin(), L.chain_ptr.end());
-        off_creach.push_back(host.size()); host.insert(host.end(), L.chain_reach.begin(), L.chain_reach.end());
-    }
-    // Pilot launches of the load balancer on a reach network: the routing schedule cut off PILOT_LEVELS reaches below the
-    // headwaters (chains keep their first elements; the slot assignments of the full schedule stay valid for a subset run
-    // in the same order).  Every reach of a member shares the member's parameters, so its cost rank among the members
-    // carries over to the reaches further down; a 256-reach chain is sampled by its first 8 reaches.
-    constexpr int PILOT_LEVELS = 8;
-    std::vector<int> level(S, 0);
-    for (int s = 0; s < S; ++s)
-        for (int k = up_ptr[s]; k < up_ptr[s + 1]; ++k) level[s] = std::max(level[s], level[up_idx[k]] + 1);
-    std::vector<size_t> off_pilot_cptr, off_pilot_creach;
-    std::vector<unsigned> pilot_n_chains;
-    for (const Launch& L : sch.launches) {
-        std::vector<int> cptr(1, 0), creach;
-        for (size_t c = 0; c + 1 < L.chain_ptr.size(); ++c) {
-            for (int i = L.chain_ptr[c]; i < L.chain_ptr[c + 1] && level[L.chain_reach[i]] < PILOT_LEVELS; ++i)
-                creach.push_back(L.chain_reach[i]);
-            if ((int)creach.size() > cptr.back()) cptr.push_back((int)creach.size());
-        }
-        if (creach.empty()) continue;
-        pilot_n_chains.push_back((unsigned)cptr.size() - 1u);
-        off_pilot_cptr.push_back(host.size()); host.insert(host.end(), cptr.begin(), cptr.end());
-        off_pilot_creach.push_back(host.size()); host.insert(host.end(), creach.begin(), creach.end());
-    }
-    rc = ensure(ctx, ctx->sched, host.size() * sizeof(int));
-    if (rc != SIMPLYP_OK) return rc;
-    // pageable source: the copy is staged before hipMemcpyAsync returns, `host` may go out of scope
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->sched.ptr, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.ptr, 0, simplyp_ctx::N_COUNTERS * sizeof(unsigned long long), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(member_status, 0, (size_t)E * sizeof(int32_t), ctx->stream));
-    if (member_rhs_evals) HIP_TRY(ctx, hipMemsetAsync(member_rhs_evals, 0, (size_t)E * sizeof(uint32_t), ctx->stream));
-
-    const int* dsched = (const int*)ctx->sched.ptr;
-    simplyp::KernelArgs a;
+    simplyp::KernelArgs a{};          // (zeros: no pilot window, members in their own order, tables by member)
     a.E = E; a.S = S; a.D = D; a.n_sets = dims->n_forcing_sets;
     a.forcing = forcing; a.doy = doy; a.forcing_of_member = forcing_of_member;
     a.period_of_day = period_of_day; a.n_periods = opts->n_periods;
     a.mp = member_params; a.rp = reach_params;
-    a.out = out; a.status = member_status;
-    a.counters = (unsigned long long*)ctx->counters.ptr;
+    a.out = out; a.status = member_status; a.member_rhs = member_rhs_evals;
     a.route = (double*)ctx->route.ptr;
-    a.up_ptr = dsched + off_up_ptr; a.up_idx = dsched + off_up_idx;
-    a.route_slot = dsched + off_rslot; a.out_slot = dsched + off_oslot;
-    a.n_out_reaches = n_out_reaches;
+    a.n_out_reaches = out_reaches ? n_out_reaches : S;
     a.out_mask = opts->out_mask & (SIMPLYP_MASK_ALL | SIMPLYP_MASK_D_SNOW);
     a.integrator = opts->integrator; a.substeps = opts->substeps; a.max_steps = opts->max_steps;
     a.dynamic_epc0 = opts->dynamic_epc0; a.dynamic_erod = opts->dynamic_erod;
     a.run_mode_cal = opts->run_mode_cal; a.sc_qr0 = opts->sc_qr0; a.project_vr = opts->project_vr;
     a.rtol = opts->rtol; a.atol = opts->atol; a.step_len = opts->step_len;
-
-    a.D_stride = D;
-    a.win_stride = 0; a.win_route_stride = 0;
-    a.route_days = D;
-    a.perm = nullptr;
-    a.out_by_slot = 0;
-    a.params_by_slot = 0;
-    a.member_rhs = member_rhs_evals;
-    // Member slots per wavefront.  64 unless the ensemble cannot fill the chip with full waves: a single-reach ensemble under an
-    // adaptive integrator is then spread over as many waves as there are SIMDs (a wave's day costs its slowest lane's attempts;
-    // idle SIMDs cost nothing).  Results do not depend on it (members are independent).
-    // Lanes per member: 1, or 4 -- a member's Cash-Karp attempt spread over a DPP quad (ck_day_quad: ~1.4 x shorter attempts,
-    // bit-identical results) -- when the ensemble is so small that even then every (member group, reach) finds a resident wave
-    // of its own: the run is bound by one member's serial chain of attempts, not by throughput.  A single-reach ensemble may be
-    // up to 1.75 x larger than that: its quads then run through the work-conserving task queue in ~1.5 rounds of waves that all
-    // SIMDs share, where the one-lane kernel would keep a third of the SIMDs busy for one long round (measured, MI355X:
-    // 25 000 members 477 against 598 ms, 30 000 members 571 against 600, 40 000 members 759 against 610).
-    int team = 1;
-    const long long quad_waves = (long long)((E + 15) / 16) * S;
-    if (opts->integrator == SIMPLYP_INTEG_CASHKARP_AUG &&
-        (opts->lanes_per_member == 4 ||
-         (opts->lanes_per_member == 0 && (quad_waves <= (long long)ctx->n_simd_slots ||
-                                          (S == 1 && quad_waves * 4 <= 7LL * ctx->n_simd_slots)))))
-        team = 4;
-    a.team_shift = team == 4 ? 2 : 0;
-    ctx->team = team;
-    const int max_lanes = simplyp::WAVE / team;
-    int lanes = max_lanes;
-    if (opts->lanes_per_wave > 0) lanes = std::min<int>(max_lanes, opts->lanes_per_wave);
-    else if (opts->integrator != SIMPLYP_INTEG_RK4 && S == 1 && (E + max_lanes - 1) / max_lanes < ctx->n_simd_slots)
-        lanes = std::max(1, (E + ctx->n_simd_slots - 1) / ctx->n_simd_slots);
-    a.lanes = lanes;
-    ctx->lanes = lanes;
-    const unsigned gx = (unsigned)((E + lanes - 1) / lanes);
-    const bool snow = opts->snow != 0;
-    // opts.stiff_pair (integrator 2): attempts bound by Cash-Karp's stability interval go to the second pair; auto = reach networks
-    const bool stiff = opts->integrator == SIMPLYP_INTEG_CASHKARP_AUG && SIMPLYP_STIFF_PAIR_ON(opts->stiff_pair, S);
-    ctx->stiff = stiff ? 1 : 0;
-    // one launch of the chain kernel: k.chain_ptr / k.chain_reach describe n_chains mutually independent chains
-    auto launch_chains = [&](const simplyp::KernelArgs& k, unsigned n_chains, unsigned n_windows = 1u) -> int {
-        dim3 grid(gx, n_chains, n_windows), block(simplyp::WAVE, 1, 1);
-#define SIMPLYP_LAUNCH_CHAIN(INTEG, TEAM)                                                                                   \
-    do {                                                                                                                    \
-        if (snow) hipLaunchKernelGGL((simplyp::simplyp_chain_kernel<INTEG, true, TEAM>), grid, block, 0, ctx->stream, k);   \
-        else hipLaunchKernelGGL((simplyp::simplyp_chain_kernel<INTEG, false, TEAM>), grid, block, 0, ctx->stream, k);       \
-    } while (0)
-        if (opts->integrator == SIMPLYP_INTEG_RK4) SIMPLYP_LAUNCH_CHAIN(SIMPLYP_INTEG_RK4, 1);
-        else if (opts->integrator == SIMPLYP_INTEG_CASHKARP) SIMPLYP_LAUNCH_CHAIN(SIMPLYP_INTEG_CASHKARP, 1);
-        else if (opts->integrator == SIMPLYP_INTEG_CASHKARP_AUG_F32) SIMPLYP_LAUNCH_CHAIN(SIMPLYP_INTEG_CASHKARP_AUG_F32, 1);
-        else if (stiff) {
-#define SIMPLYP_LAUNCH_CHAIN_STIFF(TEAM)                                                                                                        \
-    do {                                                                                                                                        \
-        if (snow) hipLaunchKernelGGL((simplyp::simplyp_chain_kernel<SIMPLYP_INTEG_CASHKARP_AUG, true, TEAM, true>), grid, block, 0, ctx->stream, k);   \
-        else hipLaunchKernelGGL((simplyp::simplyp_chain_kernel<SIMPLYP_INTEG_CASHKARP_AUG, false, TEAM, true>), grid, block, 0, ctx->stream, k);       \
-    } while (0)
-            if (team == 4) SIMPLYP_LAUNCH_CHAIN_STIFF(4); else SIMPLYP_LAUNCH_CHAIN_STIFF(1);
-#undef SIMPLYP_LAUNCH_CHAIN_STIFF
-        }
-        else if (team == 4) SIMPLYP_LAUNCH_CHAIN(SIMPLYP_INTEG_CASHKARP_AUG, 4);
-        else SIMPLYP_LAUNCH_CHAIN(SIMPLYP_INTEG_CASHKARP_AUG, 1);
-#undef SIMPLYP_LAUNCH_CHAIN
-        HIP_TRY(ctx, hipGetLastError());
-        return SIMPLYP_OK;
-    };
-    auto launch_all = [&](const simplyp::KernelArgs& base) -> int {
-        simplyp::KernelArgs k = base;
-        for (size_t l = 0; l < sch.launches.size(); ++l) {
-            k.chain_ptr = dsched + off_cptr[l];
-            k.chain_reach = dsched + off_creach[l];
-            if (int rc_l = launch_chains(k, (unsigned)sch.launches[l].chain_ptr.size() - 1u)) return rc_l;
-            HIP_TRY(ctx, hipGetLastError());
-        }
-        return SIMPLYP_OK;
-    };
+    a.D_stride = D; a.route_days = D;
+    a.lanes = shape.lanes; a.team_shift = shape.team == 4 ? 2 : 0;
+    std::vector<ChainLaunch> launches, pilot;
+    if ((rc = upload_schedule(ctx, sch, topo, up_ptr, up_idx, out_reaches, a, launches, pilot)) != SIMPLYP_OK) return rc;
 
     HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-
-    // ---- load balance (Cash-Karp only: members differ in the steps they need) --------------------
-    // With more waves than the chip holds at once, the run takes as long as the unluckiest SIMD's queue.
-    // A short pilot run measures each member's cost; members are then handed to lane slots in order of
-    // decreasing cost, so (a) the lanes of a wave need similar step counts and (b) the dispatcher starts
-    // the long waves first and back-fills with the short ones (longest-processing-time-first).
-    // (a streamed output wants time chunks: their rows travel to the host while later chunks compute -- and short ones, so that
-    // the first copy starts early: the copies, not the kernel, bound a streamed pass; 64 days cost ~0.4 % in task overhead)
-    const bool stream_chunks = host_out && opts->n_periods == 0;
-    int chunk_days = opts->time_chunk_days > 0 ? opts->time_chunk_days : ((stream_chunks && S == 1) ? 64 : 256);
-    chunk_days = ((chunk_days + 63) / 64) * 64;
-    bool want_queue = opts->integrator != SIMPLYP_INTEG_RK4 && D > chunk_days &&
-        (opts->time_chunk_days > 0 || (stream_chunks && opts->time_chunk_days == 0) ||
-         (opts->time_chunk_days == 0 && ((S == 1 && (int)gx > ctx->n_simd_slots) || (S > 1 && (int)gx < ctx->n_simd_slots))));
-    int pilot_days = opts->balance_pilot_days > 0 ? opts->balance_pilot_days : 64;
-    if (pilot_days > D) pilot_days = D;
-    // auto: a single-reach ensemble that needs more waves than the chip holds at once; a reach network that will run through
-    // the task queue with at least four member groups (there every SIMD works through many tasks, so homogeneous groups pay;
-    // with one wave per SIMD sorting only makes the slowest wave slower)
-    const bool want_balance = opts->integrator != SIMPLYP_INTEG_RK4 && pilot_days * 4 <= D &&
-        (opts->balance == 1 ||
-         (opts->balance == 2 && ((int)gx > ctx->n_simd_slots || (S > 1 && want_queue && gx >= 4u))));
-    ctx->balanced = 0;
-    if (want_balance) {
-        // The pilot: PILOT_WINDOWS short runs from the initial conditions, each over a different stretch of the forcing
-        // (spread over the first two years when the run is long enough, so that the seasons are sampled), one cost
-        // counter per member and window.
-        constexpr int PILOT_WINDOWS = 8;
-        const int win_days = std::max(1, pilot_days / PILOT_WINDOWS);
-        const int win_stride = std::max(win_days, std::min(80, (D - win_days) / (PILOT_WINDOWS - 1)));      // ~1.6 years covered
-        rc = ensure(ctx, ctx->balance, (size_t)E * (PILOT_WINDOWS * sizeof(uint32_t) + sizeof(int32_t)));
-        if (rc != SIMPLYP_OK) return rc;
-        uint32_t* d_cost = (uint32_t*)ctx->balance.ptr;
-        int32_t* d_perm = (int32_t*)(d_cost + (size_t)PILOT_WINDOWS * E);
-        HIP_TRY(ctx, hipMemsetAsync(d_cost, 0, (size_t)PILOT_WINDOWS * E * sizeof(uint32_t), ctx->stream));
-        simplyp::KernelArgs p = a;
-        p.D = win_days;                   // forcing rows keep their stride of D days
-        p.route_days = win_days;
-        const size_t win_route = (size_t)sch.n_slots * 4 * win_days * E;      // doubles of routing scratch per window
-        if (sch.n_slots > 0) {
-            rc = ensure(ctx, ctx->route, (size_t)PILOT_WINDOWS * win_route * sizeof(double));
-            if (rc != SIMPLYP_OK) return rc;
-            p.route = (double*)ctx->route.ptr;
-        }
-        // all windows in one launch per schedule level (blockIdx.z = window): 8 x 1563 waves fill the chip's rounds, where
-        // 8 launches of 1563 waves would each leave a half-empty second round
-        p.win_stride = win_stride;
-        p.win_route_stride = (long long)win_route;
-        p.member_rhs = d_cost;
-        if (getenv("SIMPLYP_PILOT_ALL_REACHES")) {               // diagnostics: times the full-network pilot
-            for (int w = 0; w < PILOT_WINDOWS && rc == SIMPLYP_OK; ++w) {
-                simplyp::KernelArgs pw = p;
-                pw.win_stride = 0;
-                pw.forcing = a.forcing + (size_t)w * win_stride;
-                pw.doy = a.doy ? a.doy + (size_t)w * win_stride : nullptr;
-                pw.member_rhs = d_cost + (size_t)w * E;
-                rc = launch_all(pw);
-            }
-        } else {
-            for (size_t l = 0; l < pilot_n_chains.size() && rc == SIMPLYP_OK; ++l) {
-                p.chain_ptr = dsched + off_pilot_cptr[l];
-                p.chain_reach = dsched + off_pilot_creach[l];
-                rc = launch_chains(p, pilot_n_chains[l], (unsigned)PILOT_WINDOWS);
-            }
-        }
-        if (rc != SIMPLYP_OK) return rc;
-        std::vector<uint32_t> cost((size_t)PILOT_WINDOWS * E);
-        HIP_TRY(ctx, hipMemcpyAsync(cost.data(), d_cost, cost.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        std::vector<int32_t> perm;
-        order_members(cost, PILOT_WINDOWS, E, perm);
-        HIP_TRY(ctx, hipMemcpyAsync(d_perm, perm.data(), (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        // the pilot's bookkeeping must not leak into the real run
-        HIP_TRY(ctx, hipMemsetAsync(ctx->counters.ptr, 0, simplyp_ctx::N_COUNTERS * sizeof(unsigned long long), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(member_status, 0, (size_t)E * sizeof(int32_t), ctx->stream));
-        a.perm = d_perm;
-        ctx->balanced = 1;
-        // slot-ordered copies of the parameter tables: the main kernels then read them coalesced
-        const size_t n_mp = (size_t)SIMPLYP_NP_M * E, n_rp = (size_t)SIMPLYP_NP_R * S * E;
-        const size_t bytes = (n_mp + n_rp) * sizeof(double) + (forcing_of_member ? (size_t)E * sizeof(int32_t) : 0);
-        rc = ensure(ctx, ctx->sorted_params, bytes);
-        if (rc != SIMPLYP_OK) return rc;
-        double* s_mp = (double*)ctx->sorted_params.ptr;
-        double* s_rp = s_mp + n_mp;
-        int32_t* s_fom = (int32_t*)(s_rp + n_rp);
-        const dim3 gb(256), gg((unsigned)((E + 255) / 256), 16);
-        hipLaunchKernelGGL(simplyp::gather_columns_kernel<double>, gg, gb, 0, ctx->stream, member_params, s_mp, d_perm, (int)SIMPLYP_NP_M, E);
-        hipLaunchKernelGGL(simplyp::gather_columns_kernel<double>, gg, gb, 0, ctx->stream, reach_params, s_rp, d_perm, (int)SIMPLYP_NP_R * S, E);
-        if (forcing_of_member)
-            hipLaunchKernelGGL(simplyp::gather_columns_kernel<int32_t>, dim3(gg.x, 1), gb, 0, ctx->stream, forcing_of_member, s_fom, d_perm, 1, E);
-        HIP_TRY(ctx, hipGetLastError());
-        a.mp = s_mp; a.rp = s_rp;
-        if (forcing_of_member) a.forcing_of_member = s_fom;
-        a.params_by_slot = 1;
-    }
+    if (shape.balance && (rc = balance_members(ctx, *opts, shape, sch, pilot, a)) != SIMPLYP_OK) return rc;
     if (member_of_slot) {
-        if (ctx->balanced) {
+        if (shape.balance) {
             HIP_TRY(ctx, hipMemcpyAsync(member_of_slot, a.perm, (size_t)E * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
         } else {
             std::vector<int32_t> ident((size_t)E);
@@ -868,145 +997,23 @@ static int run_async_body(simplyp_ctx* ctx, const simplyp_dims* dims, const simp
     }
     a.out_by_slot = opts->out_slot_order ? 1 : 0;
     if (opts->n_periods > 0)       // running sums start from zero
-        HIP_TRY(ctx, hipMemsetAsync(out, 0, (size_t)simplyp_out_bytes(dims, opts, n_out_reaches), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(out, 0, (size_t)simplyp_out_bytes(dims, opts, a.n_out_reaches), ctx->stream));
 
-    // ---- task-queue kernel: (reach, time chunk, member group) tasks pulled by one persistent wave per SIMD ----
-    // auto: when the chain kernel would leave SIMDs idle -- a single-reach ensemble that needs more waves than the chip
-    // holds at once, or a multi-reach network (a chain walked by one thread per member cannot use more than E lanes)
-    ctx->queued = 0;
-    if (want_queue) {
-        const int G = (int)gx, n_chunks = (D + chunk_days - 1) / chunk_days;
-        // levels, ring depth, downstream CSR, routing buffers
-        std::vector<int> n_down(S, 0);
-        int max_jump = 0;
-        for (int s = 0; s < S; ++s)
-            for (int k = up_ptr[s]; k < up_ptr[s + 1]; ++k) { max_jump = std::max(max_jump, level[s] - level[up_idx[k]]); ++n_down[up_idx[k]]; }
-        const int ring_chunks = std::min(n_chunks, max_jump + 1);
-        std::vector<int> down_ptr(S + 1, 0), down_idx((size_t)std::max(1, (int)up_ptr[S])), qslot(S, -1);
-        for (int s = 0; s < S; ++s) down_ptr[s + 1] = down_ptr[s] + n_down[s];
-        { std::vector<int> fill(down_ptr.begin(), down_ptr.end() - 1);
-          for (int s = 0; s < S; ++s) for (int k = up_ptr[s]; k < up_ptr[s + 1]; ++k) down_idx[fill[up_idx[k]]++] = s; }
-        int n_route = 0;
-        for (int s = 0; s < S; ++s) if (n_down[s] > 0) qslot[s] = n_route++;
-        const size_t ring_days = (size_t)ring_chunks * chunk_days;
-        const size_t route_bytes = (size_t)n_route * 4 * ring_days * E * sizeof(double);
-        size_t free_b = 0, total_b = 0;
-        (void)hipMemGetInfo(&free_b, &total_b);
-        if (route_bytes > ctx->route.bytes && route_bytes - ctx->route.bytes > free_b / 10 * 9) want_queue = false;   // does not fit: chain kernel
-        if (want_queue) {
-            // (reach, chunk) pairs in dependency order: by level + chunk, then reach
-            std::vector<int> pair_idx((size_t)S * n_chunks);
-            std::iota(pair_idx.begin(), pair_idx.end(), 0);
-            std::stable_sort(pair_idx.begin(), pair_idx.end(), [&](int x, int y) {
-                const int kx = level[x / n_chunks] + x % n_chunks, ky = level[y / n_chunks] + y % n_chunks;
-                return kx != ky ? kx < ky : x < y;
-            });
-            std::vector<int> qi;                       // task_reach | task_chunk | down_ptr | down_idx | qslot
-            for (int v : pair_idx) qi.push_back(v / n_chunks);
-            for (int v : pair_idx) qi.push_back(v % n_chunks);
-            const size_t off_dptr = qi.size(); qi.insert(qi.end(), down_ptr.begin(), down_ptr.end());
-            const size_t off_didx = qi.size(); qi.insert(qi.end(), down_idx.begin(), down_idx.end());
-            const size_t off_qslot = qi.size(); qi.insert(qi.end(), qslot.begin(), qslot.end());
-            const size_t flags_bytes = (((size_t)S * G + 4) * sizeof(unsigned) + 255) / 256 * 256;      // ticket, error, progress, (pad), done[S][G]
-            const size_t ints_bytes = (qi.size() * sizeof(int) + 255) / 256 * 256;
-            rc = ensure(ctx, ctx->queue, flags_bytes + ints_bytes + (size_t)S * simplyp::CKPT_N * E * sizeof(double));
-            if (rc != SIMPLYP_OK) return rc;
-            if (route_bytes) { rc = ensure(ctx, ctx->route, route_bytes); if (rc != SIMPLYP_OK) return rc; }
-            char* base = (char*)ctx->queue.ptr;
-            HIP_TRY(ctx, hipMemsetAsync(base, 0, flags_bytes, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(base + flags_bytes, qi.data(), qi.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            simplyp::QueueArgs q;
-            unsigned* flags = (unsigned*)base;
-            const int* dq = (const int*)(base + flags_bytes);
-            q.ticket = flags; q.error = flags + 1; q.progress = flags + 2; q.done = flags + 4;
-            q.task_reach = dq; q.task_chunk = dq + pair_idx.size();
-            q.down_ptr = dq + off_dptr; q.down_idx = dq + off_didx;
-            q.ckpt = (double*)(base + flags_bytes + ints_bytes);
-            q.n_groups = G; q.n_pairs = (int)pair_idx.size(); q.chunk_days = chunk_days; q.ring_chunks = ring_chunks;
-            q.chunk_count = nullptr; q.host_ready = nullptr; q.tasks_per_chunk = (unsigned)S * (unsigned)G;
-            if (stream_chunks) {
-                rc = ensure(ctx, ctx->chunk_count, (size_t)n_chunks * sizeof(unsigned));
-                if (rc != SIMPLYP_OK) return rc;
-                if ((size_t)n_chunks > ctx->host_ready_cap) {
-                    if (ctx->host_ready) { (void)hipHostFree(ctx->host_ready); ctx->host_ready = nullptr; ctx->host_ready_cap = 0; }
-                    // COHERENT (fine-grained) host memory, asked for explicitly: a flag raised by a running kernel must reach the
-                    // polling host thread before the kernel ends, which only fine-grained memory promises
-                    HIP_TRY(ctx, hipHostMalloc((void**)&ctx->host_ready, (size_t)n_chunks * sizeof(uint32_t),
-                                               hipHostMallocCoherent | hipHostMallocMapped));
-                    ctx->host_ready_cap = (size_t)n_chunks;
-                }
-                memset(ctx->host_ready, 0, (size_t)n_chunks * sizeof(uint32_t));
-                HIP_TRY(ctx, hipMemsetAsync(ctx->chunk_count.ptr, 0, (size_t)n_chunks * sizeof(unsigned), ctx->stream));
-                q.chunk_count = (unsigned*)ctx->chunk_count.ptr;
-                q.host_ready = ctx->host_ready;
-                ctx->copy_plan.n_chunks = n_chunks;
-                ctx->copy_plan.chunk_days = chunk_days;
-            }
-            q.max_polls = 20000000u;      // x (s_sleep 64 ~ 2 us): ~40 s in which NO task of the run completed means something is broken
-            if (const char* mp_env = getenv("SIMPLYP_QUEUE_MAX_POLLS")) q.max_polls = (unsigned)strtoul(mp_env, nullptr, 10);
-            simplyp::KernelArgs k = a;
-            k.route = (double*)ctx->route.ptr;
-            k.route_days = (int)ring_days;
-            k.route_slot = dq + off_qslot;
-            k.chain_ptr = nullptr; k.chain_reach = nullptr;
-            const long long n_tasks = (long long)pair_idx.size() * G;
-            unsigned workers = (unsigned)std::min<long long>(n_tasks, ctx->n_simd_slots);
-            if (const char* w_env = getenv("SIMPLYP_QUEUE_WORKERS")) workers = std::max(1u, std::min(workers, (unsigned)strtoul(w_env, nullptr, 10)));
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_main, ctx->stream));
-#define SIMPLYP_LAUNCH_QUEUE(INTEG, TEAM)                                                                                                       \
-    do {                                                                                                                                        \
-        if (snow) hipLaunchKernelGGL((simplyp::simplyp_queue_kernel<INTEG, true, TEAM>), dim3(workers), dim3(simplyp::WAVE), 0, ctx->stream, k, q);  \
-        else hipLaunchKernelGGL((simplyp::simplyp_queue_kernel<INTEG, false, TEAM>), dim3(workers), dim3(simplyp::WAVE), 0, ctx->stream, k, q);      \
-    } while (0)
-            if (opts->integrator == SIMPLYP_INTEG_CASHKARP) SIMPLYP_LAUNCH_QUEUE(SIMPLYP_INTEG_CASHKARP, 1);
-            else if (opts->integrator == SIMPLYP_INTEG_CASHKARP_AUG_F32) SIMPLYP_LAUNCH_QUEUE(SIMPLYP_INTEG_CASHKARP_AUG_F32, 1);
-            else if (stiff) {
-#define SIMPLYP_LAUNCH_QUEUE_STIFF(TEAM)                                                                                                                 \
-    do {                                                                                                                                                 \
-        if (snow) hipLaunchKernelGGL((simplyp::simplyp_queue_kernel<SIMPLYP_INTEG_CASHKARP_AUG, true, TEAM, true>), dim3(workers), dim3(simplyp::WAVE), 0, ctx->stream, k, q);  \
-        else hipLaunchKernelGGL((simplyp::simplyp_queue_kernel<SIMPLYP_INTEG_CASHKARP_AUG, false, TEAM, true>), dim3(workers), dim3(simplyp::WAVE), 0, ctx->stream, k, q);      \
-    } while (0)
-                if (team == 4) SIMPLYP_LAUNCH_QUEUE_STIFF(4); else SIMPLYP_LAUNCH_QUEUE_STIFF(1);
-#undef SIMPLYP_LAUNCH_QUEUE_STIFF
-            }
-            else if (team == 4) SIMPLYP_LAUNCH_QUEUE(SIMPLYP_INTEG_CASHKARP_AUG, 4);
-            else SIMPLYP_LAUNCH_QUEUE(SIMPLYP_INTEG_CASHKARP_AUG, 1);
-#undef SIMPLYP_LAUNCH_QUEUE
-            HIP_TRY(ctx, hipGetLastError());
-            if (getenv("SIMPLYP_DEBUG")) fprintf(stderr, "[simplyp] queue kernel launched: S=%d G=%d pairs=%zu chunk=%d ring=%d workers=%u max_polls=%u\n", S, G, pair_idx.size(), chunk_days, ring_chunks, workers, q.max_polls);
-            ctx->queued = 1;
-            ctx->n_launches = 1;
-        }
-    }
-    if (!want_queue) {
-        if (sch.n_slots > 0) {           // whole-run daily series of every reach that is read downstream
-            rc = ensure(ctx, ctx->route, (size_t)sch.n_slots * 4 * D * E * sizeof(double));
-            if (rc != SIMPLYP_OK) return rc;
-        }
+    bool queued = false;
+    if (shape.want_queue && (rc = launch_queue(ctx, *opts, shape, topo, a, queued)) != SIMPLYP_OK) return rc;
+    if (!queued) {
+        // whole-run daily series of every reach that is read downstream
+        if (sch.n_slots > 0 && (rc = ensure(ctx, ctx->route, (size_t)sch.n_slots * 4 * D * E * sizeof(double))) != SIMPLYP_OK) return rc;
         a.route = (double*)ctx->route.ptr;
         HIP_TRY(ctx, hipEventRecord(ctx->ev_main, ctx->stream));
-        rc = launch_all(a);
-        if (rc != SIMPLYP_OK) return rc;
-        ctx->n_launches = (int)sch.launches.size();
+        for (const ChainLaunch& c : launches)
+            if ((rc = launch_chains(ctx, *opts, shape, a, c)) != SIMPLYP_OK) return rc;
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
-    if (host_out) {
-        simplyp_ctx::CopyPlan& cp = ctx->copy_plan;
-        cp.dev = out; cp.host = host_out;
-        cp.ncols = popcount32(a.out_mask);
-        cp.D = (size_t)(opts->n_periods > 0 ? opts->n_periods : D);
-        cp.row_doubles = (size_t)n_out_reaches * E;
-        if (ctx->queued && stream_chunks) {
-            ctx->run_over.store(0, std::memory_order_release);
-            ctx->copier = std::thread(copier_main, ctx);       // chunk by chunk, beside the kernel
-        } else {
-            // no time chunks in this run (chain kernel, RK4, time-reduced rows): the whole table follows the last launch
-            HIP_TRY(ctx, hipMemcpyAsync(host_out, out, cp.ncols * cp.D * cp.row_doubles * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_copy_done, ctx->stream));
-        }
-        ctx->copy_pending = true;
-    }
+    ctx->last = simplyp_stats{};
+    ctx->last.lanes_per_wave = shape.lanes; ctx->last.lanes_per_member = shape.team; ctx->last.stiff_pair = shape.stiff;
+    ctx->last.balanced = shape.balance; ctx->last.queued = queued; ctx->last.n_launches = queued ? 1 : (int)launches.size();
+    if (host_out && (rc = arm_copy(ctx, host_out, *opts, a, queued && shape.stream_chunks)) != SIMPLYP_OK) return rc;
     ctx->pending = true;
     return SIMPLYP_OK;
 }
@@ -1016,8 +1023,7 @@ static int run_async_body(simplyp_ctx* ctx, const simplyp_dims* dims, const simp
 // (std::thread::operator= on a joinable thread would call std::terminate).
 static void quiesce_streaming(simplyp_ctx* ctx)
 {
-    ctx->run_over.store(1, std::memory_order_release);     // whatever chunk flag is still down stays down
-    if (ctx->copier.joinable()) ctx->copier.join();        // every chunk's copy is enqueued when it returns
+    stop_copier(ctx);
     for (int i = 0; i < simplyp_ctx::N_COPY_STREAMS; ++i)
         if (ctx->copy_streams[i]) (void)hipStreamSynchronize(ctx->copy_streams[i]);
     ctx->copy_pending = false;
@@ -1065,13 +1071,12 @@ static int sync_impl(simplyp_ctx* ctx, simplyp_stats* stats)
     double stream_gbs = 0.0;
     const bool copied = ctx->copy_pending;
     if (copied) {
-        ctx->run_over.store(1, std::memory_order_release);     // the launches are done: whatever flag is still down stays down
-        if (ctx->copier.joinable()) ctx->copier.join();        // every chunk's copy is enqueued when it returns
+        stop_copier(ctx);                                      // the launches are done
         if (ctx->copy_error)
             return fail(ctx, SIMPLYP_ERR_DEVICE, "streamed output: a device-to-host copy failed: %s", hipGetErrorString((hipError_t)ctx->copy_error));
         HIP_TRY(ctx, hipEventSynchronize(ctx->ev_copy_done));
         HIP_TRY(ctx, hipEventElapsedTime(&ms_tail, ctx->ev_stop, ctx->ev_copy_done));
-        if (ctx->queued && ctx->copy_plan.n_chunks > 0) {
+        if (ctx->last.queued && ctx->copy_plan.n_chunks > 0) {
             // chunked run: the rate the table travelled at
             float ms_run = 0.f;
             HIP_TRY(ctx, hipEventElapsedTime(&ms_run, ctx->ev_main, ctx->ev_copy_done));
@@ -1082,7 +1087,7 @@ static int sync_impl(simplyp_ctx* ctx, simplyp_stats* stats)
     }
     unsigned long long c[simplyp_ctx::N_COUNTERS] = {};
     HIP_TRY(ctx, hipMemcpy(c, ctx->counters.ptr, sizeof(c), hipMemcpyDeviceToHost));
-    if (ctx->queued) {
+    if (ctx->last.queued) {
         unsigned err = 0;
         HIP_TRY(ctx, hipMemcpy(&err, (unsigned*)ctx->queue.ptr + 1, sizeof(err), hipMemcpyDeviceToHost));
         if (err)
@@ -1093,25 +1098,19 @@ static int sync_impl(simplyp_ctx* ctx, simplyp_stats* stats)
         float ms = 0.f, ms_pilot = 0.f;
         HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_main, ctx->ev_stop));
         HIP_TRY(ctx, hipEventElapsedTime(&ms_pilot, ctx->ev_start, ctx->ev_main));
-        memset(stats, 0, sizeof(*stats));
+        *stats = ctx->last;                                    // the fields the run's shape decided, the rest zero
         stats->rhs_evals = c[0]; stats->steps = c[1]; stats->rejected = c[2];
         stats->kernel_ms = ms;
         // lanes doing useful work per issued attempt: (attempts summed over lanes) / (64 x wave-level attempts)
         // (of all 64 lanes, also when a wave carries fewer members; a member spread over several lanes occupies them all)
-        stats->simt_efficiency = c[3] ? (double)(c[0] / 6) * ctx->team / (64.0 * (double)c[3]) : 1.0;
-        stats->pilot_ms = ctx->balanced ? ms_pilot : 0.0;
-        stats->n_launches = ctx->n_launches;
-        stats->balanced = ctx->balanced;
-        stats->queued = ctx->queued;
-        stats->lanes_per_wave = ctx->lanes;
-        stats->lanes_per_member = ctx->team;
-        stats->stiff_pair = ctx->stiff;
+        stats->simt_efficiency = c[3] ? (double)(c[0] / 6) * ctx->last.lanes_per_member / (64.0 * (double)c[3]) : 1.0;
+        stats->pilot_ms = ctx->last.balanced ? ms_pilot : 0.0;
         stats->streamed_chunks = copied ? ctx->streamed_chunks : 0;
         stats->d2h_tail_ms = copied ? ms_tail : 0.0;
         stats->stream_gbs = stream_gbs;
-        stats->queue_waits = ctx->queued ? c[4] : 0;
-        stats->queue_longest_wait_polls = ctx->queued ? c[5] : 0;
-        stats->queue_longest_stall_polls = ctx->queued ? c[6] : 0;
+        stats->queue_waits = ctx->last.queued ? c[4] : 0;
+        stats->queue_longest_wait_polls = ctx->last.queued ? c[5] : 0;
+        stats->queue_longest_stall_polls = ctx->last.queued ? c[6] : 0;
         stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->t_begin).count();
     }
     return SIMPLYP_OK;
@@ -1158,34 +1157,52 @@ int simplyp_run(simplyp_ctx* ctx, const simplyp_dims* dims, const simplyp_opts* 
     return simplyp_sync(ctx, stats);
 }
 
+// The table simplyp_gof, simplyp_gof_spearman and simplyp_waterbody read: its sizes, its output reaches, and the slots among
+// its columns of the four series the statistics and sums are built from.
+struct TableView {
+    int E, S, D, R;
+    std::vector<int32_t> reach_of;      // [R] the reach of each output row
+    int col[4];
+};
+
+// Checks shared by the table reductions (`ptrs_ok`: the caller's required pointers are set).  waterbody == true: `out` is a
+// table written by simplyp_waterbody, `out_mask` its wb_mask, and the series its summed discharge and fluxes.
+static int check_table(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask, const int32_t* out_reaches,
+                       int32_t n_out_reaches, bool ptrs_ok, bool waterbody, TableView& t)
+{
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "a run is pending on this context; call simplyp_sync first");
+    if (!dims || dims->E <= 0 || (!waterbody && dims->S <= 0) || dims->D <= 0) return fail(ctx, SIMPLYP_ERR_ARG, "bad dims");
+    if (!ptrs_ok) return fail(ctx, SIMPLYP_ERR_ARG, "a required pointer is NULL");
+    static const int reach_cols[4] = {SIMPLYP_OUT_QR, SIMPLYP_OUT_MSUS_FLUX, SIMPLYP_OUT_TDP_FLUX, SIMPLYP_OUT_PP_FLUX};
+    static const int wb_cols[4] = {SIMPLYP_WB_Q_CUMECS, SIMPLYP_WB_MSUS_FLUX, SIMPLYP_WB_TDP_FLUX, SIMPLYP_WB_PP_FLUX};
+    const int* want = waterbody ? wb_cols : reach_cols;
+    const uint32_t need = (1u << want[0]) | (1u << want[1]) | (1u << want[2]) | (1u << want[3]);
+    if ((out_mask & need) != need || (out_mask & ~(waterbody ? SIMPLYP_WB_MASK_ALL : (SIMPLYP_MASK_ALL | SIMPLYP_MASK_D_SNOW))) != 0u)
+        return fail(ctx, SIMPLYP_ERR_ARG, waterbody ? "wb_mask must contain Q_cumecs, Msus_kg/day, TDP_kg/day and PP_kg/day"
+                                                    : "out_mask must contain Qr, Msus_kg/day, TDP_kg/day and PP_kg/day");
+    t.E = dims->E; t.S = waterbody ? 1 : dims->S; t.D = dims->D;
+    t.R = out_reaches ? n_out_reaches : t.S;
+    if (t.R <= 0 || t.R > t.S) return fail(ctx, SIMPLYP_ERR_ARG, "bad n_out_reaches");
+    t.reach_of.resize(t.R);
+    for (int r = 0; r < t.R; ++r) {
+        t.reach_of[r] = out_reaches ? out_reaches[r] : r;
+        if (t.reach_of[r] < 0 || t.reach_of[r] >= t.S) return fail(ctx, SIMPLYP_ERR_ARG, "out_reaches[%d] out of range", r);
+    }
+    for (int i = 0; i < 4; ++i) t.col[i] = popcount32(out_mask & ((1u << want[i]) - 1u));
+    return SIMPLYP_OK;
+}
+
 static int gof_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
                     const int32_t* out_reaches, int32_t n_out_reaches,
                     const double* out, const int32_t* member_of_slot,
                     const double* f_tdp, const double* reach_params,
                     const double* obs, double* gof, simplyp_gof_info* info, bool waterbody = false)
 {
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "a run is pending on this context; call simplyp_sync first");
-    if (!dims || dims->E <= 0 || (!waterbody && dims->S <= 0) || dims->D <= 0) return fail(ctx, SIMPLYP_ERR_ARG, "bad dims");
-    if (!out || !f_tdp || (!waterbody && !reach_params) || !obs || !gof) return fail(ctx, SIMPLYP_ERR_ARG, "a required pointer is NULL");
-    // the four series the statistics are built from: reach table columns, or (waterbody == true: `out` is a table written by
-    // simplyp_waterbody and `out_mask` its wb_mask) the summed discharge and fluxes
-    const int want[4] = {waterbody ? (int)SIMPLYP_WB_Q_CUMECS : (int)SIMPLYP_OUT_QR,
-                         waterbody ? (int)SIMPLYP_WB_MSUS_FLUX : (int)SIMPLYP_OUT_MSUS_FLUX,
-                         waterbody ? (int)SIMPLYP_WB_TDP_FLUX : (int)SIMPLYP_OUT_TDP_FLUX,
-                         waterbody ? (int)SIMPLYP_WB_PP_FLUX : (int)SIMPLYP_OUT_PP_FLUX};
-    const uint32_t need = (1u << want[0]) | (1u << want[1]) | (1u << want[2]) | (1u << want[3]);
-    if ((out_mask & need) != need || (out_mask & ~(waterbody ? SIMPLYP_WB_MASK_ALL : (SIMPLYP_MASK_ALL | SIMPLYP_MASK_D_SNOW))) != 0u)
-        return fail(ctx, SIMPLYP_ERR_ARG, waterbody ? "wb_mask must contain Q_cumecs, Msus_kg/day, TDP_kg/day and PP_kg/day"
-                                                    : "out_mask must contain Qr, Msus_kg/day, TDP_kg/day and PP_kg/day");
-    const int E = dims->E, S = waterbody ? 1 : dims->S, D = dims->D;
-    const int R = out_reaches ? n_out_reaches : S;
-    if (R <= 0 || R > S) return fail(ctx, SIMPLYP_ERR_ARG, "bad n_out_reaches");
-    std::vector<int32_t> reach_of(R);
-    for (int r = 0; r < R; ++r) {
-        reach_of[r] = out_reaches ? out_reaches[r] : r;
-        if (reach_of[r] < 0 || reach_of[r] >= S) return fail(ctx, SIMPLYP_ERR_ARG, "out_reaches[%d] out of range", r);
-    }
+    TableView t;
+    const bool ptrs_ok = out && f_tdp && (waterbody || reach_params) && obs && gof;
+    if (int rc = check_table(ctx, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, waterbody, t)) return rc;
+    const int E = t.E, S = t.S, D = t.D, R = t.R;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
     // Observation side, shared by all members: counts, conditioning shifts, compact day lists.
@@ -1228,9 +1245,8 @@ static int gof_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mas
         c_ptr[r + 1] = (int32_t)c_day.size();
     }
 
-    // column slots inside `out`
     simplyp::GofArgs g{};
-    for (int i = 0; i < 4; ++i) g.col[i] = popcount32(out_mask & ((1u << want[i]) - 1u));
+    std::copy(t.col, t.col + 4, g.col);
 
     const int groups = (E + simplyp::WAVE - 1) / simplyp::WAVE;
     // Slices per day list.  All waves of a launch take the same time, so what matters is how many rounds the chip needs:
@@ -1259,7 +1275,7 @@ static int gof_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mas
     // one upload: int32 block then double block
     std::vector<int32_t> ints;
     auto put_i = [&](const std::vector<int32_t>& v) { size_t at = ints.size(); ints.insert(ints.end(), v.begin(), v.end()); return at; };
-    const size_t o_reach = put_i(reach_of), o_qp = put_i(q_ptr), o_cp = put_i(c_ptr), o_qd = put_i(q_day), o_cd = put_i(c_day);
+    const size_t o_reach = put_i(t.reach_of), o_qp = put_i(q_ptr), o_cp = put_i(c_ptr), o_qd = put_i(q_day), o_cd = put_i(c_day);
     if (ints.size() & 1) ints.push_back(0);
     std::vector<double> dbl;
     auto put_d = [&](const std::vector<double>& v) { size_t at = dbl.size(); dbl.insert(dbl.end(), v.begin(), v.end()); return at; };
@@ -1327,19 +1343,10 @@ static int spearman_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t ou
                          const double* f_tdp, const double* reach_params,
                          const double* obs, double* rho, simplyp_gof_info* info)
 {
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "a run is pending on this context; call simplyp_sync first");
-    if (!dims || dims->E <= 0 || dims->S <= 0 || dims->D <= 0) return fail(ctx, SIMPLYP_ERR_ARG, "bad dims");
-    if (!out || !f_tdp || !reach_params || !obs || !rho) return fail(ctx, SIMPLYP_ERR_ARG, "a required pointer is NULL");
-    const int want[4] = {SIMPLYP_OUT_QR, SIMPLYP_OUT_MSUS_FLUX, SIMPLYP_OUT_TDP_FLUX, SIMPLYP_OUT_PP_FLUX};
-    const uint32_t need = (1u << want[0]) | (1u << want[1]) | (1u << want[2]) | (1u << want[3]);
-    if ((out_mask & need) != need || (out_mask & ~(SIMPLYP_MASK_ALL | SIMPLYP_MASK_D_SNOW)) != 0u)
-        return fail(ctx, SIMPLYP_ERR_ARG, "out_mask must contain Qr, Msus_kg/day, TDP_kg/day and PP_kg/day");
-    const int E = dims->E, S = dims->S, D = dims->D;
-    const int R = out_reaches ? n_out_reaches : S;
-    if (R <= 0 || R > S) return fail(ctx, SIMPLYP_ERR_ARG, "bad n_out_reaches");
-    for (int r = 0; r < R; ++r)
-        if (out_reaches && (out_reaches[r] < 0 || out_reaches[r] >= S)) return fail(ctx, SIMPLYP_ERR_ARG, "out_reaches[%d] out of range", r);
+    TableView t;
+    const bool ptrs_ok = out && f_tdp && reach_params && obs && rho;
+    if (int rc = check_table(ctx, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, false, t)) return rc;
+    const int E = t.E, S = t.S, D = t.D, R = t.R;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     constexpr int NV = SIMPLYP_N_GOF_VARS;
     {   // variables without (enough) observations stay NaN (visualise_results.py:430, :453)
@@ -1348,7 +1355,7 @@ static int spearman_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t ou
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     simplyp::SpearmanArgs g{};
-    for (int i = 0; i < 4; ++i) g.col[i] = popcount32(out_mask & ((1u << want[i]) - 1u));
+    std::copy(t.col, t.col + 4, g.col);
     g.E = E; g.R = R; g.D = D;
     g.out = out; g.col_stride = (long long)D * R * E;
     g.member_of_slot = member_of_slot; g.f_tdp = f_tdp; g.rho = rho;
@@ -1357,7 +1364,6 @@ static int spearman_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t ou
     long long pairs = 0;
     int n_q = 0, n_c = 0;
     for (int r = 0; r < R; ++r) {
-        const int reach = out_reaches ? out_reaches[r] : r;
         for (int v = 0; v < NV; ++v) {
             const double* ob = obs + ((size_t)r * NV + v) * D;
             std::vector<int32_t> day;
@@ -1388,7 +1394,7 @@ static int spearman_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t ou
             HIP_TRY(ctx, hipMemcpyAsync(base + list_bytes, rk.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));        // the host vectors go out of scope at the end of this iteration
             g.n = n; g.var = v; g.r = r;
-            g.a_catch = reach_params + ((size_t)SIMPLYP_PR_A_CATCH * S + reach) * E;
+            g.a_catch = reach_params + ((size_t)SIMPLYP_PR_A_CATCH * S + t.reach_of[r]) * E;
             g.day = (const int32_t*)base; g.rank_obs = (const double*)(base + list_bytes);
             g.sum_ro = sum_ro; g.sum_ro2 = sum_ro2;
             g.vals = (double*)ctx->gof_partial.ptr; g.partial = g.vals + (size_t)n * E; g.n_blocks = n_blocks;
@@ -1440,19 +1446,12 @@ static int waterbody_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t o
                           const int32_t* sum_reaches, int32_t n_sum,
                           uint32_t wb_mask, double* wb, simplyp_wb_info* info)
 {
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "a run is pending on this context; call simplyp_sync first");
-    if (!dims || dims->E <= 0 || dims->S <= 0 || dims->D <= 0) return fail(ctx, SIMPLYP_ERR_ARG, "bad dims");
-    if (!out || !f_tdp || !reach_params || !sum_reaches || !wb) return fail(ctx, SIMPLYP_ERR_ARG, "a required pointer is NULL");
-    const uint32_t need = (1u << SIMPLYP_OUT_QR) | (1u << SIMPLYP_OUT_MSUS_FLUX) | (1u << SIMPLYP_OUT_TDP_FLUX) |
-                          (1u << SIMPLYP_OUT_PP_FLUX);
-    if ((out_mask & need) != need || (out_mask & ~(SIMPLYP_MASK_ALL | SIMPLYP_MASK_D_SNOW)) != 0u)
-        return fail(ctx, SIMPLYP_ERR_ARG, "out_mask must contain Qr, Msus_kg/day, TDP_kg/day and PP_kg/day");
+    TableView t;
+    const bool ptrs_ok = out && f_tdp && reach_params && sum_reaches && wb;
+    if (int rc = check_table(ctx, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, false, t)) return rc;
+    const int E = t.E, S = t.S, D = t.D, R = t.R;
     if ((wb_mask & SIMPLYP_WB_MASK_ALL) == 0u || (wb_mask & ~SIMPLYP_WB_MASK_ALL) != 0u)
         return fail(ctx, SIMPLYP_ERR_ARG, "wb_mask must select 1..%d of the waterbody columns", (int)SIMPLYP_N_WB);
-    const int E = dims->E, S = dims->S, D = dims->D;
-    const int R = out_reaches ? n_out_reaches : S;
-    if (R <= 0 || R > S) return fail(ctx, SIMPLYP_ERR_ARG, "bad n_out_reaches");
     if (n_sum < 1 || n_sum > simplyp::WB_MAX_REACHES)
         return fail(ctx, SIMPLYP_ERR_ARG, "n_sum must be in [1, %d] (got %d)", simplyp::WB_MAX_REACHES, n_sum);
     simplyp::WaterbodyArgs g{};
@@ -1461,14 +1460,12 @@ static int waterbody_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t o
         if (s < 0 || s >= S) return fail(ctx, SIMPLYP_ERR_ARG, "sum_reaches[%d] = %d out of range", k, s);
         if (k > 0 && s <= sum_reaches[k - 1]) return fail(ctx, SIMPLYP_ERR_ARG, "sum_reaches must be strictly ascending");
         int pos = -1;
-        if (!out_reaches) pos = s;
-        else for (int r = 0; r < R; ++r) if (out_reaches[r] == s) pos = r;
+        for (int r = 0; r < R; ++r) if (t.reach_of[r] == s) pos = r;
         if (pos < 0) return fail(ctx, SIMPLYP_ERR_ARG, "reach %d is not among the table's output reaches", s);
         g.pos[k] = pos; g.reach[k] = s;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int want[4] = {SIMPLYP_OUT_QR, SIMPLYP_OUT_MSUS_FLUX, SIMPLYP_OUT_TDP_FLUX, SIMPLYP_OUT_PP_FLUX};
-    for (int i = 0; i < 4; ++i) g.col[i] = popcount32(out_mask & ((1u << want[i]) - 1u));
+    std::copy(t.col, t.col + 4, g.col);
     g.E = E; g.R = R; g.D = D;
     g.out = out; g.col_stride = (long long)D * R * E;
     g.n_sum = n_sum;
