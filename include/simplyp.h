@@ -175,7 +175,10 @@ typedef struct {
                                 networks (S > 1), off for a single reach; > 0 on; < 0 off.  The same switch turns on the
                                 damping-aware error weights (SIMPLYP_DAMP_*: the estimate of what a fast reach forgets within a
                                 fraction of the day -- its flow, its three masses -- is discounted accordingly).  Same <= 1e-6
-                                parity bar; 40 % fewer right-hand sides on BASELINE config C4.                    */
+                                parity bar; 40 % fewer right-hand sides on BASELINE config C4.  Pinned to reference-made
+                                tables on chains (C4's, the stiff 12-reach one, dry headwaters), a one-level confluence and a
+                                branching 22-reach network (tests/golden/branch_network.npz: 3.2e-7 there, 1.1 x Cash-Karp
+                                alone); other topologies and regimes are not.  -1 is the conservative switch: Cash-Karp alone. */
 } simplyp_opts;
 
 typedef struct {

@@ -85,9 +85,16 @@
  * expansive regime, where lam < 0).  A reach that relaxes 15 times a day or less -- every single-reach problem of the benchmarks -- has
  * F = 1.  On config C4's chain (oracle, 4 members x 256 reaches x 200 days): attempts 31.0 -> 26.6 per reach-day, worst error against
  * the converged solution 1.1e-7 -> 2.1e-7; against the reference's tables: stiff 12-reach chain 1.5e-7 -> 2.1e-7, C4's members 1.5e-7
- * -> 1.4e-7 (profiles/r04_experiments.md section 7; PHI 30: 28.2 attempts, PHI 10: 25.8 and 2.8e-7 on the stiff chain). */
+ * -> 1.4e-7 (profiles/r04_experiments.md section 7; PHI 30: 28.2 attempts, PHI 10: 25.8 and 2.8e-7 on the stiff chain).
+ * FMAX was 16 on that chain.  On a branching network (tests/golden/branch_network.npz, oracle) it left the confluence of two stiff
+ * tributaries (member 17, reach 13) and the reach a headwater joins 9 levels down (member 0, reach 19) at 6.7e-7 / 6.5e-7 against
+ * the reference, 3.5 x Cash-Karp alone at the same reaches (1.9e-7) and 2.3 x its worst (2.9e-7): the discount assumes a component
+ * forgets at lam, but the three masses forget at the flushing rate Qr / Vr = (1 - b_Q) x rate only, and a day's many local errors add
+ * up.  FMAX 4: worst 3.2e-7 there (1.1 x Cash-Karp alone) at 0.68 x its right-hand sides; C4's whole chain 1.9e-7 at 3.7 % more
+ * right-hand sides than FMAX 16 (FMAX 8: 7.2e-7 on the branching network, FMAX 2: 3.0e-7 at 8 % more; PHI 30 / 60 with FMAX 16:
+ * 4.0e-7 / 3.5e-7). */
 #define SIMPLYP_DAMP_PHI 15.0
-#define SIMPLYP_DAMP_FMAX 16.0
+#define SIMPLYP_DAMP_FMAX 4.0
 #define SIMPLYP_STIFF_A21 0.12853527643260251
 #define SIMPLYP_STIFF_A31 0.16351994308561854
 #define SIMPLYP_STIFF_A32 0.19797306142138452
@@ -113,7 +120,11 @@
 #define SIMPLYP_STIFF_E5 -0.12955476832078688
 #define SIMPLYP_STIFF_E6 0.10808001308258683
 /* opts.stiff_pair: 0 = auto (on for a reach network, S > 1: a single reach is never far from its headwater), > 0 on, < 0 off;
- * integrator 2 only */
+ * integrator 2 only.  The constants above were tuned on config C4's linear chain, SIMPLYP_DAMP_FMAX on a branching network too;
+ * reference-made tables pin the scheme on chains (tests/golden/c4_deep.npz, c4_members.npz, dry_network.npz, stiff_chain12_2004.npz),
+ * a one-level confluence (confluence3_nc_2004.npz) and a branching network with stiff confluences and level jumps of 6 and 9
+ * (branch_network.npz: 3.2e-7, 1.1 x Cash-Karp alone).  Other topologies and regimes are not pinned: < 0 (Cash-Karp alone) is the
+ * conservative switch. */
 #define SIMPLYP_STIFF_PAIR_ON(opt, S) ((opt) > 0 || ((opt) == 0 && (S) > 1))
 
 #endif /* SIMPLYP_CONTROLLER_H */

@@ -140,6 +140,62 @@ def c4_inputs(n_reaches=256, seed=C4_SEED, st_dt='1981-01-01', end_dt='2010-12-3
     return met_df, p_struc, p_SU, p_LU, p_SC, p, dyn
 
 
+BRANCH_SEED = 20240603
+# The branching network of branch_inputs: {reach id: upstream ids}, ids ascending downstream.  Tributary A (1-7) and tributary B
+# (8-12) meet in the confluence reach 13 (level 7); tributary C (14-16) joins the main stem at 17 (level 8, a level jump of 6); the lone
+# headwater 18 joins at 19 (level 9, a jump of 9); a short main stem (20, 21) ends in the outlet 22 (level 12).
+BRANCH_UPSTREAM = dict([(1, []), *((i, [i - 1]) for i in range(2, 8)), (8, []), *((i, [i - 1]) for i in range(9, 13)),
+                        (13, [7, 12]), (14, []), (15, [14]), (16, [15]), (17, [13, 16]), (18, []), (19, [17, 18]),
+                        (20, [19]), (21, [20]), (22, [21])])
+# short reaches with a small catchment of their own below the confluences: several hundred km2 flow through them (stiff, as the end of
+# the stiff 12-reach chain of the golden scenarios); newly-converted arable land on a few reaches
+BRANCH_SHORT = (13, 17, 22)
+BRANCH_NC = (3, 10, 15, 20)
+
+
+def branch_inputs(seed=BRANCH_SEED, st_dt='1981-01-01', end_dt='2010-12-31'):
+    """The reference-shaped inputs (the 7 arguments of run_simply_p) of a branching reach network (BRANCH_UPSTREAM: 22
+    sub-catchments, three tributaries and a lone headwater, 13 levels deep): the Tarland workbook and forcing, both dynamic options
+    on, per-reach geometry drawn reach by reach from `seed` as in c4_inputs but with larger catchments (A_catch log-uniform 20-60 km2),
+    the reaches of BRANCH_SHORT 2 km long with 5 km2 of their own, f_NC_Ar = 0.1 on the reaches of BRANCH_NC.  The network of
+    tests/golden/branch_network.npz and of tools/sweep_dry_network.py --network branch."""
+    import pandas as pd
+    met_df, p_struc, p_SU, p_LU, p_SC, p, dyn = tarland_inputs(st_dt, end_dt, dynamic_epc0='y', dynamic_erod='y')
+    rng = np.random.default_rng(seed)
+    S = len(BRANCH_UPSTREAM)
+    frac = np.round(rng.dirichlet([2.0, 3.0, 5.0], S) * 1024.0)
+    frac[:, 2] = 1024.0 - frac[:, 0] - frac[:, 1]
+    frac /= 1024.0
+    cols = {}
+    base = p_SC[1]
+    for s in range(S):
+        col = base.copy()
+        col['A_catch'] = float(np.exp(rng.uniform(np.log(20.0), np.log(60.0))))
+        col['L_reach'] = float(rng.uniform(2000.0, 15000.0))
+        col['S_Ar'], col['S_IG'], col['S_SN'] = (float(x) for x in rng.uniform(1.0, 12.0, 3))
+        col['S_reach'] = float(rng.uniform(0.3, 2.5))
+        col['f_Ar'], col['f_IG'], col['f_S'] = (float(x) for x in frac[s])
+        col['f_NC_Ar'] = 0.1 if s + 1 in BRANCH_NC else 0.0
+        col['f_NC_IG'] = 0.0
+        col['f_NC_S'] = 0.0
+        col['TDPeff'] = float(rng.uniform(0.0, 0.3))
+        if s + 1 in BRANCH_SHORT:
+            col['A_catch'], col['L_reach'] = 5.0, 2000.0
+        cols[s + 1] = col
+    p_SC = pd.DataFrame(cols)
+    p = p.copy()
+    p['SC_list'] = np.arange(1, S + 1)
+    p['SC_Qr0'] = float(S)
+    p_SU = p_SU.copy()
+    p_SU['n_SC'] = S
+    ups = [', '.join(str(u) for u in BRANCH_UPSTREAM[i]) if len(BRANCH_UPSTREAM[i]) > 1 else
+           (BRANCH_UPSTREAM[i][0] if BRANCH_UPSTREAM[i] else np.nan) for i in range(1, S + 1)]
+    p_struc = pd.DataFrame({'Upstream_SCs': pd.Series(ups, index=range(1, S + 1), dtype=object),
+                            'In_final_flux?': pd.Series([0] * (S - 1) + [1], index=range(1, S + 1))})
+    p_struc.index.name = 'Reach'
+    return met_df, p_struc, p_SU, p_LU, p_SC, p, dyn
+
+
 def c4_problem(n_members, n_reaches=256, n_days=18262, seed=C4_SEED, solver=None, out_mask=marshal.MASK_REACH5,
                out_reaches='last'):
     """BASELINE config C4: a synthetic linear chain of `n_reaches` sub-catchments (reach i drains reach i-1),

@@ -15,7 +15,7 @@ How the reference is driven:
     either as shipped (rtol=0.01, default atol, mxstep=5000) or at rtol=atol=1e-12
     ("tight": the converged solution of the reference's own equations = the parity oracle).
 
-Usage:  python tests/golden/make_golden.py [--long] [--only NAME|mc|unit|knee|heldout|wide|dry|dry-check|c4mc|c4deep]
+Usage:  python tests/golden/make_golden.py [--long] [--only NAME|mc|unit|knee|heldout|wide|dry|dry-check|c4mc|c4deep|steplen|drynet|branch]
 """
 
 import argparse
@@ -670,6 +670,69 @@ def drynet_fixture(n_proc):
     print('dry_network.npz written')
 
 
+# A branching network (--only branch): simplyp_amd.synthetic.branch_inputs (22 sub-catchments, 13 levels deep: tributaries A (1-7) and
+# B (8-12) meet in the stiff confluence reach 13, tributary C joins at 17, a lone headwater at 19, the outlet 22 is stiff again; both
+# dynamic options on), 1981-1982 on Tarland's own climate, odeint rtol = atol = 1e-12 -- the network scheme (second pair,
+# damping-aware weights) where stiff tributaries meet, and the task queue's ring buffers across level jumps of 6 and 9.  Members: the
+# workbook's own values (-1) and three of a 64-member draw of C4's distribution (C4_SEED), chosen with tools/sweep_dry_network.py
+# --network branch (CPU oracle, default solver against Cash-Karp alone at rtol 1e-11 / atol 1e-13, this period, all 22 reaches, the 9
+# reach columns): worst 6.7e-7, median 3.7e-7, 168 right-hand sides per catchment-day (Cash-Karp at rtol 1e-11: 869).  Members 17 and 0:
+# the two largest errors (6.7e-7 at the confluence 13, 6.5e-7 at 19); 48: the largest mean outlet Qr (475 mm/d of the outlet's own 5 km2).
+# Kept reaches, per member (a two-year table is ~50 kB and a committed file stays under 1 MiB, so not every member keeps every reach):
+# the confluence and the outlet for all; where C joins and where the lone headwater joins for all but member 48; the ends of A and B
+# for the workbook member, the end of A for member 48.
+BRANCH_DRAW, BRANCH_YEARS = 64, ('1981-01-01', '1982-12-31')
+BRANCH_KEEP = {-1: (7, 12, 13, 17, 19, 22), 17: (13, 17, 19, 22), 0: (13, 17, 19, 22), 48: (7, 13, 22)}
+
+
+def _branch_worker(member):
+    from simplyp_amd import synthetic, marshal
+    mods = load_reference()
+    switch = OdeintSwitch()
+    mods['model'].odeint = switch
+    st_dt, end_dt = BRANCH_YEARS
+    p_SU, p, p_LU, _, _, met = tarland_inputs(st_dt, end_dt)
+    _, p_struc, _, _, p_SC, pb, _ = synthetic.branch_inputs(synthetic.BRANCH_SEED, st_dt, end_dt)
+    p = p.copy()
+    p['SC_list'], p['SC_Qr0'] = pb['SC_list'], pb['SC_Qr0']
+    p_SU = p_SU.copy()
+    p_SU['n_SC'] = len(pb['SC_list'])
+    over = synthetic.monte_carlo_overrides(p, p_LU, BRANCH_DRAW, seed=synthetic.C4_SEED)
+    base = marshal.member_params(p, p_LU, 1)[:, 0]
+    values = {k: float(base[marshal.PM_NAMES.index(k)]) if member < 0 else float(over[k][member]) for k in sorted(over)}
+    sc = dict(p_SU=p_SU, p=p, p_LU=p_LU.copy(), p_SC=p_SC, p_struc=p_struc, met=met, dyn=dict(Dynamic_EPC0='y', Dynamic_erodibility='y'))
+    if member >= 0:
+        for name in over:
+            src = dict(marshal.PM_SPEC)[name]
+            if src[0] == 'p':
+                sc['p'][src[1]] = values[name]
+            else:
+                sc['p_LU'].loc[src[1], src[2]] = values[name]
+    r = run_reference(mods, switch, sc, 1e-12)
+    print('branch network member %d: wall %.1f s  nfe/day %.1f' % (member, r['wall'], r['nfe_per_day']), flush=True)
+    return {sc_id: r['df_R'][sc_id][REACH_COLS].to_numpy(dtype=float) for sc_id in BRANCH_KEEP[member]}, values
+
+
+def branch_fixture(n_proc):
+    import multiprocessing as mp
+    from simplyp_amd import synthetic, marshal
+    members = list(BRANCH_KEEP)
+    with mp.get_context('fork').Pool(min(n_proc, len(members))) as pool:
+        res = pool.map(_branch_worker, members, chunksize=1)
+    _, p_struc, _, _, _, pb, _ = synthetic.branch_inputs(synthetic.BRANCH_SEED, *BRANCH_YEARS)
+    up_ptr, up_idx, _ = marshal.topology(p_struc, pb)
+    keep = sorted(set(r for rs in BRANCH_KEEP.values() for r in rs))
+    arrays = {'n_reaches': np.array(len(pb['SC_list'])), 'n_draw': np.array(BRANCH_DRAW), 'members': np.array(members),
+              'reaches': np.array(keep), 'years': np.array(BRANCH_YEARS), 'up_ptr': up_ptr, 'up_idx': up_idx,
+              'odeint_rtol_atol': np.array((1e-12, 1e-12)), 'columns': np.array(REACH_COLS), 'names': np.array(sorted(res[0][1])),
+              'values': np.array([[ov[k] for (_, ov) in res] for k in sorted(res[0][1])])}
+    for m, (tabs, _) in zip(members, res):
+        for sc_id, R in tabs.items():
+            arrays['R/%d/%d' % (m, sc_id)] = R
+    np.savez_compressed(os.path.join(HERE, 'branch_network.npz'), **arrays)
+    print('branch_network.npz written')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--long', action='store_true', help='also run the 1981-2010 scenario (minutes)')
@@ -691,6 +754,9 @@ def main():
         return
     if args.only == 'drynet':
         drynet_fixture(args.procs)
+        return
+    if args.only == 'branch':
+        branch_fixture(args.procs)
         return
     if args.only == 'c4mc':
         c4_members_fixture(args.procs)

@@ -282,6 +282,68 @@ def dry_network_problem(solver=None):
     return pr, tables
 
 
+def branch_network_inputs(n_draw, st_dt, end_dt, members=None, solver=None, out_mask=None, out_reaches=None, snow=False):
+    """The branching reach network of simplyp_amd.synthetic.branch_inputs (22 sub-catchments, 13 levels, both dynamic options on) on
+    Tarland's forcing over [st_dt, end_dt], with members of an `n_draw`-member draw of config C4's distribution (C4_SEED): all of them,
+    or `members` -- positions in the draw, -1 for the workbook's own values -- in that order.  The network of
+    tests/golden/branch_network.npz and of tools/sweep_dry_network.py --network branch.  snow=True: the raw met rows and the snow
+    module in the kernel (opts.snow = 1), as marshal_scenario."""
+    from simplyp_amd import synthetic, marshal, abi
+    met_df, p_struc, p_SU, p_LU, p_SC, p, dyn = synthetic.branch_inputs(synthetic.BRANCH_SEED, st_dt, end_dt)
+    marshal.prologue(p_SU, p_LU, p_SC, p)
+    up_ptr, up_idx, _ = marshal.topology(p_struc, p)
+    over = synthetic.monte_carlo_overrides(p, p_LU, n_draw, synthetic.C4_SEED)
+    if members is not None:
+        base = marshal.member_params(p, p_LU, 1)[:, 0]
+        over = {nm: np.array([base[marshal.PM_NAMES.index(nm)] if m < 0 else v[m] for m in members]) for nm, v in over.items()}
+    E = n_draw if members is None else len(members)
+    mp = marshal.member_params(p, p_LU, E, over)
+    rp = marshal.reach_params(p_SC, p, E)
+    forcing, doy = marshal.forcing_arrays(met_df, snow=snow)
+    opts = abi.make_opts(solver, dynamic_epc0=True, dynamic_erod=True, run_mode_cal=True, sc_qr0=len(marshal.sc_list(p)) - 1,
+                         out_mask=marshal.MASK_ALL if out_mask is None else out_mask, snow=snow)
+    return dict(forcing=forcing, doy=doy, member_params=mp, reach_params=rp, up_ptr=up_ptr, up_idx=up_idx, opts=opts,
+                out_reaches=out_reaches, met=met_df)
+
+
+def network_levels(up_ptr, up_idx):
+    """(level[S] = longest path from a headwater, max_jump = the largest level difference between a reach and a reach directly upstream
+    of it) of a reach graph in CSR form -- what the library's derive_topology computes to size the task queue's ring buffers
+    (min(n_chunks, max_jump + 1) time chunks) and to cut the load balancer's pilot (PILOT_LEVELS)."""
+    S = len(up_ptr) - 1
+    level = [0] * S
+    for s in range(S):
+        for k in range(up_ptr[s], up_ptr[s + 1]):
+            level[s] = max(level[s], level[up_idx[k]] + 1)
+    jump = max([level[s] - level[up_idx[k]] for s in range(S) for k in range(up_ptr[s], up_ptr[s + 1])] or [0])
+    return level, jump
+
+
+def branch_network_problem(solver=None):
+    """Arrays + opts for tests/golden/branch_network.npz -- the workbook member and three members of a 64-member draw of config C4's
+    distribution on the branching network of synthetic.branch_inputs, 1981-1982, run through the unmodified reference at odeint
+    rtol = atol = 1e-12 (tests/golden/make_golden.py --only branch) -- and the reference tables: (problem dict with all 25 columns of
+    the kept reaches and the fixture's members, {(position among the members, position among the kept reaches): table[D, 9]} for the
+    (member, reach) pairs the fixture holds -- c4_members_worst compares against it).  The parameter values are regenerated from the recorded seed and checked against what the
+    fixture recorded, and so is the topology."""
+    from simplyp_amd import marshal
+    z = np.load(os.path.join(GOLDEN, 'branch_network.npz'), allow_pickle=False)
+    members = [int(m) for m in z['members']]
+    keep = [int(r) for r in z['reaches']]
+    st_dt, end_dt = (str(y) for y in z['years'])
+    pr = branch_network_inputs(int(z['n_draw']), st_dt, end_dt, members=members, solver=solver, out_reaches=[r - 1 for r in keep])
+    for k, nm in enumerate(str(n) for n in z['names']):                 # the generator still draws what the fixture recorded
+        np.testing.assert_array_equal(pr['member_params'][marshal.PM_NAMES.index(nm)], z['values'][k])
+    np.testing.assert_array_equal(pr['up_ptr'], z['up_ptr'])
+    np.testing.assert_array_equal(pr['up_idx'], z['up_idx'])
+    assert [str(c) for c in z['columns']] == REACH_COLS
+    D = pr['forcing'].shape[2]
+    tables = {(k, j): z['R/%d/%d' % (m, r)] for k, m in enumerate(members) for j, r in enumerate(keep) if 'R/%d/%d' % (m, r) in z.files}
+    assert all(t.shape == (D, 9) for t in tables.values())
+    pr['members'], pr['reaches'] = members, keep
+    return pr, tables
+
+
 def steplen_cases():
     """[(scenario name, step_len)] of tests/golden/step_len.npz (tests/golden/make_golden.py --only steplen)."""
     z = np.load(os.path.join(GOLDEN, 'step_len.npz'), allow_pickle=False)

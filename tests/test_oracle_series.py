@@ -452,3 +452,69 @@ def test_oracle_on_a_dry_reach_network_against_the_reference(oracle_lib):
     worst = {k: max(v.values()) for k, v in res.items()}
     assert worst['default'] < 1e-6, res['default']
     assert worst['converged'] < 2e-8, res['converged']
+
+
+# ---------------------------------------------------------------------------------------------------
+# a branching reach network (tests/golden/branch_network.npz)
+
+def test_branch_network_fixture_holds_what_it_names():
+    """The fixture's network is the one synthetic.branch_inputs builds today (the topology it recorded), and it is what the tests
+    built on it need: deeper than the load balancer's pilot (PILOT_LEVELS = 8 in the library), a level jump of at least 6 (so that a
+    two-year run in 64-day chunks wraps the task queue's ring buffers of min(n_chunks, max_jump + 1) chunks), and stiff reaches below
+    the confluences -- read from the reference's own tables: the confluence 13 and the outlet 22 (2 km, 5 km2 of their own) carry a
+    mean 170 ... 475 mm/d of their own area's flow, the tributaries' ends 13 ... 20."""
+    from simplyp_amd import synthetic
+    z = np.load(os.path.join(helpers.GOLDEN, 'branch_network.npz'), allow_pickle=False)
+    assert tuple(z['odeint_rtol_atol']) == (1e-12, 1e-12) and [str(y) for y in z['years']] == ['1981-01-01', '1982-12-31']
+    _, p_struc, _, _, p_SC, p, dyn = synthetic.branch_inputs(synthetic.BRANCH_SEED, '1981-01-01', '1982-12-31')
+    up_ptr, up_idx, _ = marshal.topology(p_struc, p)
+    assert np.array_equal(up_ptr, z['up_ptr']) and np.array_equal(up_idx, z['up_idx'])
+    assert dyn['Dynamic_EPC0'] == 'y' and dyn['Dynamic_erodibility'] == 'y' and (p_SC.loc['f_NC_Ar'] > 0).sum() >= 3
+    level, jump = helpers.network_levels(up_ptr, up_idx)
+    assert max(level) + 1 > 8 and 6 <= jump <= 10, (level, jump)
+    assert min(-(-730 // 64), jump + 1) < -(-730 // 64)
+    assert -1 in [int(m) for m in z['members']]                                      # the workbook's own values
+    qr = REACH_COLS.index('Qr')
+    for m in z['members']:
+        for r in (13, 22):
+            assert float(z['R/%d/%d' % (m, r)][:, qr].mean()) > 150.0, (m, r)
+    assert float(z['R/-1/7'][:, qr].mean()) < 30.0 and float(z['R/-1/12'][:, qr].mean()) < 30.0
+
+
+def test_oracle_converged_on_a_branching_network_against_the_reference(oracle_lib):
+    """tests/golden/branch_network.npz: converged Cash-Karp (rtol 1e-10, atol 1e-13, second pair off) meets the reference's tables
+    within 2e-9 on every kept reach and reach column (measured 4.1e-10; c4_deep's chain: 3.1e-10): the oracle's routing on a tree --
+    the area ratios of two upstream reaches, a tributary joining 6 and 9 levels down -- is the reference's, and the fixture is converged."""
+    pr, tables = helpers.branch_network_problem(solver=dict(rtol=1e-10, atol=1e-13))
+    pr['opts'].stiff_pair = -1
+    out, status, _ = oracle_lib.run(pr['forcing'], pr['doy'], pr['member_params'], pr['reach_params'], pr['up_ptr'], pr['up_idx'],
+                                    pr['opts'], out_reaches=pr['out_reaches'], n_threads=4)
+    assert status.max() == 0
+    worst = helpers.c4_members_worst(out, tables)
+    assert max(worst.values()) < 2e-9, worst
+
+
+def _branch_default_solver(oracle_lib):
+    """{stiff_pair: (worst relative error over the kept reaches and reach columns, right-hand sides)} of the default solver on
+    tests/golden/branch_network.npz, with the network scheme on (0 = auto) and off (-1)."""
+    res = {}
+    for stiff in (0, -1):
+        pr, tables = helpers.branch_network_problem()
+        pr['opts'].stiff_pair = stiff
+        out, status, stats = oracle_lib.run(pr['forcing'], pr['doy'], pr['member_params'], pr['reach_params'], pr['up_ptr'], pr['up_idx'],
+                                            pr['opts'], out_reaches=pr['out_reaches'], n_threads=4)
+        assert status.max() == 0
+        res[stiff] = (max(helpers.c4_members_worst(out, tables).values()), stats['rhs_evals'])
+    return res
+
+
+def test_oracle_default_solver_on_a_branching_network_against_the_reference(oracle_lib):
+    """tests/golden/branch_network.npz through the default solver, on every kept reach and reach column: with the network scheme on
+    (stiff_pair 0 = auto: second pair and damping-aware weights) within 4e-7 (measured 3.2e-7) and no worse than 1.2 x Cash-Karp alone;
+    with it off (stiff_pair -1, Cash-Karp alone) within 4e-7 (measured 2.9e-7); the scheme needs fewer right-hand sides (measured 0.68 x).
+    With SIMPLYP_DAMP_FMAX 16, the value tuned on C4's chain, the scheme gave 6.7e-7 here (member 17 at the confluence of two stiff
+    tributaries, reach 13; member 0 at 19, where a headwater joins 9 levels down): 3.5 x Cash-Karp alone at those reaches."""
+    res = _branch_default_solver(oracle_lib)
+    assert res[0][0] < 4e-7 and res[-1][0] < 4e-7, res
+    assert res[0][0] < 1.2 * res[-1][0], res
+    assert res[0][1] < 0.75 * res[-1][1], res
