@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SIMPLYP_ABI_VERSION 16
+#define SIMPLYP_ABI_VERSION 17
 
 typedef enum {
     SIMPLYP_OK = 0,
@@ -449,6 +449,45 @@ int simplyp_waterbody(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_m
 int simplyp_gof_waterbody(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t wb_mask, const double* wb,
                           const int32_t* member_of_slot, const double* f_tdp,
                           const double* obs, double* gof, simplyp_gof_info* info);
+
+/* ---- percentile bands across the members: what the reference's only ensemble caller makes of its runs -- for every day the
+ * 2.5 / 50 / 97.5 percentiles over the sampled parameter sets (Development/2016/MCMC.ipynb, get_uncertainty_intervals:
+ * param_only.T.describe(percentiles=[0.025, 0.5, 0.975])) ---------------------------------------------------------------- */
+typedef struct {
+    double  kernel_ms;     /* all launches of the call, HIP events on the context's stream        */
+    int64_t bytes_table;   /* n_rows * E * 8: the algorithmic read                                  */
+    int32_t n_used;        /* members that took part (popcount of include, or E)                    */
+    int32_t n_passes;      /* sweeps over a row the selection made (diagnostic)                     */
+} simplyp_quantile_info;
+
+/*
+ * simplyp_quantiles -- exact order statistics across the member axis of any table of the library whose fastest axis is the
+ * member axis: the run's `out` (daily or period-reduced), simplyp_waterbody's `wb`, a goodness-of-fit table; the leading
+ * axes flattened to n_rows.  For every row and each probability q[k], with n = members that take part and h = q[k] * (n - 1)
+ * in fp64: k_lo = floor(h), k_hi = min(k_lo + 1, n - 1), and the outputs are the row's k_lo-th and k_hi-th smallest
+ * included values -- numpy's method='linear' indices (DataFrame.describe's too); the caller interpolates with
+ * gamma = h - floor(h).  Exact selection (no sampling): every output is an element of its row, the one np.sort puts at that
+ * index.  NaN sorts after +inf as in np.sort; -0.0 and +0.0 compare equal, either may be returned.  The table is only
+ * read; device workspace is E + 16 bytes, whatever the table's size.  Results are deterministic bit for bit.
+ *
+ *   E, n_rows       row length (members), rows; n_rows == 0 succeeds and launches nothing
+ *   table           device  [n_rows][E] fp64
+ *   member_of_slot  device  [E] or NULL: as for simplyp_gof -- column j of the table belongs to member member_of_slot[j]
+ *                           (tables a run wrote with opts.out_slot_order = 1); `include` is looked up through it
+ *   include         device  [E] uint8 in MEMBER order, or NULL = all members: a member with 0 takes part in no row
+ *                           (members flagged SIMPLYP_STATUS_NONFINITE; GLUE-style "behavioural" subsets).  When no member
+ *                           is left (n == 0) every output is NaN and the call succeeds.
+ *   q, K            HOST    [K] probabilities in [0, 1], 1 <= K <= 16
+ *   order_stats     device  [2][K][n_rows]: plane 0 = x_(k_lo), plane 1 = x_(k_hi)
+ *   info            host    may be NULL
+ * Synchronous, on the context's stream.  SIMPLYP_ERR_ARG (nothing launched) for K outside 1..16, a q outside [0, 1] or
+ * NaN, E < 1, n_rows < 0, NULL table / q / order_stats.
+ */
+int simplyp_quantiles(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double* table,
+                      const int32_t* member_of_slot, const uint8_t* include,
+                      const double* q /* host [K] */, int32_t K,
+                      double* order_stats /* device [2][K][n_rows]: lower, upper */,
+                      simplyp_quantile_info* info);
 
 /*
  * simplyp_eval_units -- the path's scalar device functions on caller-given arguments, one thread per row: how the tests pin the

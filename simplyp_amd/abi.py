@@ -2,7 +2,7 @@
 
 import ctypes as C
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 INTEG_RK4 = 0
 INTEG_CASHKARP = 1
@@ -54,6 +54,14 @@ class GofInfo(C.Structure):
 class WbInfo(C.Structure):
     """simplyp_wb_info of include/simplyp.h."""
     _fields_ = [('kernel_ms', C.c_double), ('bytes_moved', C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class QuantileInfo(C.Structure):
+    """simplyp_quantile_info of include/simplyp.h."""
+    _fields_ = [('kernel_ms', C.c_double), ('bytes_table', C.c_int64), ('n_used', C.c_int32), ('n_passes', C.c_int32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

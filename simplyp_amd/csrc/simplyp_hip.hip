@@ -20,6 +20,7 @@
 #include "simplyp_kernels.hip.h"
 #include "simplyp_gof.hip.h"
 #include "simplyp_waterbody.hip.h"
+#include "simplyp_quantile.hip.h"
 
 namespace {
 
@@ -44,6 +45,7 @@ struct simplyp_ctx {
     DeviceBuf sorted_params;  // slot-ordered copies of member_params, reach_params, forcing_of_member
     DeviceBuf gof_lists;      // goodness-of-fit day lists, observations, shifts (simplyp_gof)
     DeviceBuf gof_partial;    // [n_chunks][R][78][E] partial sums
+    DeviceBuf quant;          // simplyp_quantiles: 2 x int32 (members used, sweeps) | [E] uint8 include mask in column order
     DeviceBuf queue;          // ticket, error, done[n_groups] (uint32) | ckpt[CKPT_N][E] (double)
     // streamed output (simplyp_stream_out): the armed destination, the chunk flags the queue kernel raises in pinned host
     // memory, and the host thread that turns a raised flag into the D2H copies of that chunk's rows on `copy_stream`
@@ -876,6 +878,7 @@ void simplyp_ctx_destroy(simplyp_ctx* ctx)
     if (ctx->queue.ptr) (void)hipFree(ctx->queue.ptr);
     if (ctx->gof_lists.ptr) (void)hipFree(ctx->gof_lists.ptr);
     if (ctx->gof_partial.ptr) (void)hipFree(ctx->gof_partial.ptr);
+    if (ctx->quant.ptr) (void)hipFree(ctx->quant.ptr);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
     if (ctx->ev_main) (void)hipEventDestroy(ctx->ev_main);
@@ -1498,6 +1501,83 @@ int simplyp_waterbody(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_m
 {
     SIMPLYP_GUARD(ctx, waterbody_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
                                       sum_reaches, n_sum, wb_mask, wb, info))
+}
+
+static int quantiles_impl(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double* table,
+                          const int32_t* member_of_slot, const uint8_t* include,
+                          const double* q, int32_t K, double* order_stats, simplyp_quantile_info* info)
+{
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    if (K < 1 || K > simplyp::QUANT_MAX_K)
+        return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_quantiles: K must be in [1, %d] (got %d)", simplyp::QUANT_MAX_K, (int)K);
+    if (E < 1 || n_rows < 0)
+        return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_quantiles: E must be >= 1 and n_rows >= 0 (got E = %d, n_rows = %lld)", (int)E, (long long)n_rows);
+    if (!table || !q || !order_stats) return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_quantiles: table, q and order_stats must not be NULL");
+    for (int k = 0; k < K; ++k)
+        if (!(q[k] >= 0.0 && q[k] <= 1.0))
+            return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_quantiles: q[%d] = %g is not a probability in [0, 1]", k, q[k]);
+    if (info) { info->kernel_ms = 0.0; info->bytes_table = n_rows * (int64_t)E * 8; info->n_used = 0; info->n_passes = 0; }
+    if (n_rows == 0) return SIMPLYP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = ensure(ctx, ctx->quant, 16 + (size_t)E)) return rc;
+    int* d_ints = (int*)ctx->quant.ptr;                       // [0] members used, [1] sweeps
+    uint8_t* d_mask = (uint8_t*)ctx->quant.ptr + 16;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_ints, 0, 16, ctx->stream));
+    int n_used = E;
+    if (include) {
+        hipLaunchKernelGGL(simplyp::quantile_mask_kernel, dim3(1), dim3(1024), 0, ctx->stream, (int)E, include, member_of_slot, d_mask, d_ints);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(&n_used, d_ints, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    const long long n_out = 2LL * K * n_rows;
+    if (n_used == 0) {
+        hipLaunchKernelGGL(simplyp::quantile_fill_nan_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, ctx->stream, order_stats, n_out);
+        HIP_TRY(ctx, hipGetLastError());
+    } else {
+        simplyp::QuantileArgs g{};
+        g.E = E; g.n_rows = n_rows; g.table = table; g.include_slot = include ? d_mask : nullptr;
+        g.T = 2 * K; g.order_stats = order_stats; g.n_passes = d_ints + 1;
+        for (int k = 0; k < K; ++k) {                         // numpy's 'linear' indices
+            const double h = q[k] * (double)(n_used - 1);
+            long long lo = (long long)std::floor(h);
+            lo = std::min<long long>(std::max<long long>(lo, 0), n_used - 1);
+            g.rank[2 * k] = lo;
+            g.rank[2 * k + 1] = std::min<long long>(lo + 1, n_used - 1);
+        }
+        if (E <= simplyp::QSORT_MAX) {
+            int P = 2;
+            while (P < E) P <<= 1;
+            const long long rows_per_block = simplyp::QSORT_MAX / P;
+            const long long blocks = (n_rows + rows_per_block - 1) / rows_per_block;
+            if (blocks > 0x7FFFFFFFLL) return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_quantiles: too many rows for one call (%lld)", (long long)n_rows);
+            hipLaunchKernelGGL(simplyp::quantile_sort_kernel, dim3((unsigned)blocks), dim3(simplyp::QSORT_THREADS), 0, ctx->stream, g, P);
+        } else {
+            const unsigned blocks = (unsigned)std::min<long long>(n_rows, 65536);
+            hipLaunchKernelGGL(simplyp::quantile_select_kernel, dim3(blocks), dim3(simplyp::QSEL_THREADS), 0, ctx->stream, g);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+    int n_passes = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&n_passes, d_ints + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (info) {
+        float ms = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+        info->kernel_ms = ms;
+        info->n_used = n_used;
+        info->n_passes = n_passes;
+    }
+    return SIMPLYP_OK;
+}
+
+int simplyp_quantiles(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double* table,
+                      const int32_t* member_of_slot, const uint8_t* include,
+                      const double* q, int32_t K, double* order_stats, simplyp_quantile_info* info)
+{
+    SIMPLYP_GUARD(ctx, quantiles_impl(ctx, E, n_rows, table, member_of_slot, include, q, K, order_stats, info))
 }
 
 void* simplyp_host_alloc(int64_t bytes)

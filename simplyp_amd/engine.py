@@ -26,7 +26,8 @@ ABI_SYMBOLS = ['simplyp_abi_version', 'simplyp_device_count', 'simplyp_ctx_creat
                'simplyp_last_error', 'simplyp_ctx_set_stream', 'simplyp_out_bytes', 'simplyp_run',
                'simplyp_run_async', 'simplyp_sync', 'simplyp_plan', 'simplyp_host_alloc', 'simplyp_host_free',
                'simplyp_device_alloc', 'simplyp_device_free', 'simplyp_memcpy_h2d', 'simplyp_memcpy_d2h', 'simplyp_gof',
-               'simplyp_stream_out', 'simplyp_waterbody', 'simplyp_gof_waterbody', 'simplyp_gof_spearman', 'simplyp_eval_units']
+               'simplyp_stream_out', 'simplyp_waterbody', 'simplyp_gof_waterbody', 'simplyp_gof_spearman', 'simplyp_eval_units',
+               'simplyp_quantiles']
 
 _lib = None
 
@@ -39,6 +40,7 @@ def build(force=False, verbose=False):
     """Compile the HIP library for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, 'simplyp_hip.hip'), os.path.join(CSRC, 'simplyp_kernels.hip.h'),
             os.path.join(CSRC, 'simplyp_gof.hip.h'), os.path.join(CSRC, 'simplyp_waterbody.hip.h'),
+            os.path.join(CSRC, 'simplyp_quantile.hip.h'),
             os.path.join(INCLUDE, 'simplyp.h'), os.path.join(INCLUDE, 'simplyp_controller.h')]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
@@ -98,6 +100,9 @@ def lib():
     L.simplyp_gof_waterbody.restype = C.c_int
     L.simplyp_gof_waterbody.argtypes = [vp, C.POINTER(abi.Dims), C.c_uint32, dp, i32p, dp, C.POINTER(C.c_double), dp,
                                         C.POINTER(abi.GofInfo)]
+    L.simplyp_quantiles.restype = C.c_int
+    L.simplyp_quantiles.argtypes = [vp, C.c_int32, C.c_int64, dp, i32p, vp, C.POINTER(C.c_double), C.c_int32, dp,
+                                    C.POINTER(abi.QuantileInfo)]
     L.simplyp_stream_out.restype = C.c_int
     L.simplyp_stream_out.argtypes = [vp, vp, C.c_int64]
     L.simplyp_plan.restype = C.c_int
@@ -501,6 +506,63 @@ class Engine(object):
                                          obs.ctypes.data_as(C.POINTER(C.c_double)), gof.data_ptr(), C.byref(info))
         self._check(rc, 'simplyp_gof_waterbody')
         return gof, info.as_dict()
+
+    def quantiles(self, table, q, include=None, member_of_slot=None):
+        """Exact order statistics across the member axis (``simplyp_quantiles``): the two values that bracket numpy's
+        ``method='linear'`` quantile of every row, selected on the device; the table is only read.
+
+        table: contiguous float64 device tensor whose LAST axis is the member axis (a run's ``out``, daily or reduced, a
+        waterbody table, a goodness-of-fit table); q: probabilities in [0, 1], at most 16; include: optional [E] mask in
+        member order (bool / uint8, numpy or device tensor) -- members with 0 take part in no row; member_of_slot: the int32
+        device tensor of a run that wrote slot order (``include`` is looked up through it).
+        Returns (lower, upper, info): device tensors of shape ``(K,) + table.shape[:-1]`` holding x_(floor(h)) and
+        x_(min(floor(h) + 1, n - 1)), h = q (n - 1), n = ``info['n_used']``; ``interpolate_quantiles`` turns them into
+        numpy's values.  All NaN when no member is included."""
+        torch = self.torch
+        if not torch.is_tensor(table) or table.dtype != torch.float64 or not table.is_contiguous() or table.dim() < 1 \
+                or table.device != self.tdev:
+            raise ValueError("table must be a contiguous float64 tensor on %s whose last axis is the member axis" % (self.tdev,))
+        qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+        if qa.ndim != 1:
+            raise ValueError("q must be a list of probabilities")
+        K, E = len(qa), int(table.shape[-1])
+        lead = tuple(int(x) for x in table.shape[:-1])
+        n_rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        inc = None
+        if include is not None:
+            inc = include if torch.is_tensor(include) else torch.from_numpy(np.ascontiguousarray(np.asarray(include) != 0))
+            inc = (inc != 0).to(torch.uint8).to(self.tdev).contiguous()
+            if tuple(inc.shape) != (E,):
+                raise ValueError("include must have one entry per member")
+        if member_of_slot is not None and (member_of_slot.dtype != torch.int32 or tuple(member_of_slot.shape) != (E,)):
+            raise ValueError("member_of_slot must be an int32 device tensor with one entry per member")
+        stats = torch.empty((2, max(K, 1)) + lead, dtype=torch.float64, device=self.tdev)
+        info = abi.QuantileInfo()
+        with torch.cuda.device(self.tdev):
+            self._bind_stream()
+            rc = lib().simplyp_quantiles(self._h, E, n_rows, table.data_ptr(),
+                                         None if member_of_slot is None else member_of_slot.data_ptr(),
+                                         None if inc is None else inc.data_ptr(),
+                                         qa.ctypes.data_as(C.POINTER(C.c_double)), K, stats.data_ptr(), C.byref(info))
+        self._check(rc, 'simplyp_quantiles')
+        return stats[0], stats[1], info.as_dict()
+
+
+def interpolate_quantiles(lower, upper, q, n_used):
+    """numpy's ``method='linear'`` quantile from the two order statistics ``Engine.quantiles`` returns (host arrays
+    [K, ...]): h = q (n - 1) formed exactly as the library forms it, gamma = h - floor(h), and numpy's own lerp --
+    ``lo + (hi - lo) gamma`` for gamma < 0.5, ``hi - (hi - lo) (1 - gamma)`` otherwise."""
+    lower = np.asarray(lower, dtype=np.float64)
+    upper = np.asarray(upper, dtype=np.float64)
+    qa = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if int(n_used) < 1:
+        return np.full(lower.shape, np.nan)
+    h = qa * np.float64(int(n_used) - 1)
+    gamma = (h - np.floor(h)).reshape((-1,) + (1,) * (lower.ndim - 1))
+    diff = upper - lower
+    with np.errstate(invalid='ignore'):
+        data = np.where(gamma >= 0.5, upper - diff * (1 - gamma), lower + diff * gamma)
+    return data
 
 
 _engines = {}

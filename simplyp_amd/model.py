@@ -276,7 +276,8 @@ def _host_table(shape, pin):
 def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, overrides=None, n_members=None,
                           outputs=None, out_reaches=None, step_len=1., solver=None, device=0, to_host=True,
                           reduce=None, obs_dict=None, keep_daily=True, snow_in_kernel=None, forcing_of_member=None,
-                          waterbody=None, waterbody_obs=None, spearman=False, devices=None):
+                          waterbody=None, waterbody_obs=None, spearman=False, devices=None, quantiles=None,
+                          quantile_members=None):
     """Run an ensemble of parameter sets through the engine in one call.
 
     ``overrides``: dict name -> array[E] (member parameters, see ``marshal.PM_NAMES``) or
@@ -319,12 +320,36 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     ``stats`` then holds sums / maxima over the blocks and the per-block dicts under ``'per_device'``; with ``to_host=False``
     ``data`` is the list of the blocks' device tensors (member axis split as ``stats['bounds']``).
 
+    ``quantiles``: a list of at most 16 probabilities, e.g. ``[0.025, 0.5, 0.975]`` -- the percentile band across the members
+    for every row of the table, what the reference's ensemble caller makes of its runs (Development/2016/MCMC.ipynb,
+    get_uncertainty_intervals: ``param_only.T.describe(percentiles=[0.025, 0.5, 0.975])``), selected exactly on the device
+    (``simplyp_quantiles``) so that the table need not leave it.  The result gains ``'quantiles'`` = dict(q,
+    data[K, n_cols, D or n_periods, n_reaches], lower, upper, n_members, info): ``lower`` / ``upper`` are the two order
+    statistics that bracket each quantile, ``data`` numpy's ``method='linear'`` value interpolated from them on the host
+    (``engine.interpolate_quantiles``).  Members whose status carries ``STATUS_NONFINITE`` never take part (``STEPCAP``
+    members do: their rows are finite); ``quantile_members``, a bool array [E], restricts the band further (e.g. the
+    members whose NSE in ``['gof']`` exceeds a threshold); ``n_members`` is how many took part (all NaN when none did).
+    Works on daily rows and with ``reduce`` (bands of annual sums); with ``waterbody`` the summed series get their own band
+    under ``['waterbody']['quantiles']``.  ``keep_daily=False`` together with ``quantiles`` drops the daily table exactly as
+    with ``obs_dict``: no host table is allocated or streamed and ``data`` is None.  ``devices=[...]`` together with
+    ``quantiles`` raises ValueError: a quantile of the whole ensemble is not a function of the member blocks' quantiles, so
+    the band cannot be assembled from per-device results.
+
     Returns ``dict(columns, reaches, data[n_cols, D or n_periods, n_reaches, E], status[E], stats)``; ``data``
     and ``status`` are numpy arrays, or device tensors when ``to_host`` is False.
     The caller's ``p_LU``/``p_SC`` are edited in place exactly as by ``run_simply_p``.
     """
     from . import engine
 
+    if quantiles is not None:
+        if devices is not None:
+            raise ValueError("quantiles cannot be combined with devices=[...]: a quantile of the whole ensemble is not a function "
+                             "of the member blocks' quantiles -- run the band on one device")
+        quantiles = [float(x) for x in np.atleast_1d(np.asarray(quantiles, dtype=np.float64))]
+        if not 1 <= len(quantiles) <= 16 or not all(0.0 <= x <= 1.0 for x in quantiles):
+            raise ValueError("quantiles must be 1 to 16 probabilities in [0, 1]")
+    elif quantile_members is not None:
+        raise ValueError("quantile_members given without quantiles")
     marshal.prologue(p_SU, p_LU, p_SC, p)
     scs = marshal.sc_list(p)
     up_ptr, up_idx, _ = marshal.topology(p_struc, p)
@@ -337,6 +362,10 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
             raise ValueError("cannot infer the ensemble size: give n_members or override arrays of one length")
         n_members = sizes.pop()
     E = int(n_members)
+    if quantile_members is not None:
+        quantile_members = np.ascontiguousarray(np.asarray(quantile_members) != 0)
+        if quantile_members.shape != (E,):
+            raise ValueError("quantile_members needs one flag per member")
     # the SoA arrays are marshalled straight into page-locked host memory: the uploads are asynchronous DMA transfers
     pin = engine.pinned_empty
     mp = marshal.member_params(p, p_LU, E, m_over, alloc=pin)
@@ -406,7 +435,8 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     n_or_ = len(scs) if oreach is None else len(oreach)
     rows_ = len(met_df) if periods is None else len(periods)
     ncols_ = bin(mask).count('1')
-    want_host_table = to_host and (keep_daily or obs_dict is None)
+    reduced_on_device = obs_dict is not None or quantiles is not None     # the caller's product is a reduction of the table
+    want_host_table = to_host and (keep_daily or not reduced_on_device)
     obs = wobs = None
     if obs_dict is not None or (wb_reaches is not None and len(wb_reaches) > 1 and waterbody_obs is not None):
         from . import visualise_results as vr
@@ -443,7 +473,15 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
             if wobs is not None:
                 g_d, ginfo = eng.gof_waterbody(wb_d, winfo['columns'], wobs, ft, member_of_slot=mos)
                 part['wb_gof'] = (g_d.cpu().numpy() if to_host else g_d, ginfo)
-        part['out_d'] = None if (obs_dict is not None and not keep_daily) else out_d
+        if quantiles is not None:
+            # who takes part: a mask in member order, built where the status lies
+            inc = (status_d & abi.STATUS_NONFINITE) == 0
+            if quantile_members is not None:
+                inc = inc & eng.to_device(quantile_members[lo:hi])
+            part['quant'] = eng.quantiles(out_d, quantiles, include=inc, member_of_slot=mos)
+            if 'wb' in part:
+                part['wb_quant'] = eng.quantiles(wb_d, quantiles, include=inc, member_of_slot=mos)
+        part['out_d'] = None if (reduced_on_device and not keep_daily) else out_d
         return part
 
     if devices is None:
@@ -500,7 +538,15 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         else:
             print('One or fewer reaches were selected to be included in the sum, check your reach structure parameters')   # :896
             res['waterbody'] = None
-    if obs_dict is not None and not keep_daily:
+    if quantiles is not None:
+        def band(lower, upper, info):
+            lo_h, up_h = lower.cpu().numpy(), upper.cpu().numpy()
+            return dict(q=list(quantiles), data=engine.interpolate_quantiles(lo_h, up_h, quantiles, info['n_used']),
+                        lower=lo_h if to_host else lower, upper=up_h if to_host else upper, n_members=info['n_used'], info=info)
+        res['quantiles'] = band(*parts[0]['quant'])
+        if res.get('waterbody') is not None:
+            res['waterbody']['quantiles'] = band(*parts[0]['wb_quant'])
+    if reduced_on_device and not keep_daily:
         res['data'] = None
     elif not to_host:
         res['data'] = parts[0]['out_d'] if len(parts) == 1 else [pt['out_d'] for pt in parts]

@@ -88,6 +88,23 @@ def loglik(gof_data, m, stat_names=GOF_DEVICE_STATS):
             - gof_data[stat_names.index('sum_relsq')] / (2 * m * m))
 
 
+def band_coverage(bands_lo, bands_hi, obs):
+    """The reference's ``calc_coverage`` (Development/2016/MCMC.ipynb cell 13): the share of observations that lie inside
+    the band, ``lo <= obs <= hi`` (both ends count, as there).  ``bands_lo`` / ``bands_hi``: e.g. rows 0 and 2 of
+    ``res['quantiles']['data']`` for one column and reach; ``obs``: the observed series on the same days, NaN = no
+    observation (a row of ``observation_array``).  The share is taken over the days that HAVE an observation; the notebook
+    divides by all days (``len(overall)``) only because its observed series is interpolated and has no gaps -- with no gaps
+    the two agree.  Arrays broadcast against each other over leading axes; the last axis is the day axis.  NaN when there
+    is no observation at all."""
+    lo, hi, obs = np.broadcast_arrays(np.asarray(bands_lo, dtype=float), np.asarray(bands_hi, dtype=float),
+                                      np.asarray(obs, dtype=float))
+    have = ~np.isnan(obs)
+    inside = have & (obs >= lo) & (obs <= hi)
+    n = have.sum(axis=-1)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return inside.sum(axis=-1) / np.where(n > 0, n, np.nan).astype(float)
+
+
 def _no_plots(name):
     def f(*args, **kwargs):
         raise NotImplementedError("%s: plotting is outside the scope of simplyp_amd (DESIGN.md section 6); the result "
