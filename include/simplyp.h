@@ -24,6 +24,8 @@
 extern "C" {
 #endif
 
+/* 17 still with simplyp_state_bytes / simplyp_set_state and the SIMPLYP_STATE_* rows: they are purely additive -- no
+ * signature and no struct layout of version 17 changed, a caller built against the earlier header runs unchanged. */
 #define SIMPLYP_ABI_VERSION 17
 
 typedef enum {
@@ -82,6 +84,34 @@ enum {
  * daily fluxes */
 #define SIMPLYP_MASK_REACH5 ((1u << SIMPLYP_OUT_VR) | (1u << SIMPLYP_OUT_QR) | (1u << SIMPLYP_OUT_MSUS_FLUX) | \
                              (1u << SIMPLYP_OUT_TDP_FLUX) | (1u << SIMPLYP_OUT_PP_FLUX))
+
+/* ---- model state: rows of state[S][SIMPLYP_N_STATE][E] (simplyp_set_state) ----------------
+ * Everything a (member, reach) carries from one day to the next, in the reference's terms: the eight carried ODE variables
+ * (model.py:648-658), the soil P stores and concentrations (:696-703), the solver's trial step and the snow depth
+ * (inputs.py:200, :205).  A run of D1 + D2 days and a run of D1 days followed by a run of D2 days started from the first
+ * one's state give the same tables, status bits and right-hand-side counts bit for bit.  The state belongs to the model,
+ * not to a kernel configuration: one written under any integrator, lane layout, member order or kernel path may be consumed
+ * under any other.  Member order always, fp64, device. */
+enum {
+    SIMPLYP_STATE_VSA = 0,       /* VsA, soil water volume, agricultural (mm)                                          */
+    SIMPLYP_STATE_VSS,           /* VsS, soil water volume, semi-natural (mm)                                          */
+    SIMPLYP_STATE_VG,            /* Vg as carried: AFTER the day-end reset, Qg * T_g (:670) -- not the stored 'Vg' column */
+    SIMPLYP_STATE_VR,            /* Vr, reach volume                                                                    */
+    SIMPLYP_STATE_QR,            /* Qr_EndOfDay: the instantaneous flow, not the daily mean 'Qr'                        */
+    SIMPLYP_STATE_MSUS,          /* Msus_EndOfDay: the reach's mass, not the daily flux (the four daily integrals start  */
+    SIMPLYP_STATE_TDPR,          /* TDPr_EndOfDay   from zero every day, :618, and are no state)                         */
+    SIMPLYP_STATE_PPR,           /* PPr_EndOfDay                                                                         */
+    SIMPLYP_STATE_PLAB_A,        /* labile soil P, agricultural (:697)                                                  */
+    SIMPLYP_STATE_TDPS_A,        /* soil-water TDP mass, agricultural (:696)                                            */
+    SIMPLYP_STATE_PLAB_NC,       /* ... newly-converted land (:698-699)                                                 */
+    SIMPLYP_STATE_TDPS_NC,
+    SIMPLYP_STATE_CONC_TDPS_A,   /* soil-water TDP concentration used by the next day's fluxes (:702, :711)             */
+    SIMPLYP_STATE_CONC_TDPS_NC,  /* (:703, :715)                                                                        */
+    SIMPLYP_STATE_H_NEXT,        /* the adaptive solver's next trial step (days).  RK4: written as step_len / substeps,
+                                    ignored on input                                                                    */
+    SIMPLYP_STATE_D_SNOW,        /* snow depth at the end of the day; opts.snow = 0: written as 0.0, ignored on input   */
+    SIMPLYP_N_STATE              /* = 16 */
+};
 
 /* per-member status bits written to member_status[E] */
 #define SIMPLYP_STATUS_NONFINITE 1   /* a state became NaN/Inf                               */
@@ -312,6 +342,25 @@ int simplyp_sync(simplyp_ctx* ctx, simplyp_stats* stats);
  * The device table `out` is written as always (it feeds simplyp_gof / simplyp_waterbody).
  */
 int simplyp_stream_out(simplyp_ctx* ctx, double* host_out, int64_t host_bytes);
+
+/*
+ * simplyp_set_state -- warm start: begin the NEXT run from a saved model state and / or save the state it ends in
+ * (one-shot, with exactly the contract of simplyp_stream_out: the next simplyp_run / simplyp_run_async consumes the arm
+ * whatever its outcome, also when it is refused for its arguments; (NULL, NULL) disarms).
+ *   state_in   device  [S][SIMPLYP_N_STATE][E] or NULL.  Every (member, reach) starts its first day from these rows
+ *                      instead of the reference's cold initial conditions (model.py:377-459); parameters and everything
+ *                      derived from them (mu, Kf, ...) come from member_params / reach_params as always.  The load
+ *                      balancer's pilot keeps starting cold: it only ranks costs, results do not depend on the order.
+ *   state_out  device  [S][SIMPLYP_N_STATE][E] or NULL.  The state after the run's last day; valid when simplyp_run returns /
+ *                      after simplyp_sync.  May alias state_in: each (reach, member) cell is read before the run's first
+ *                      day and written after its last, by tasks that depend on each other.
+ * Both are indexed by MEMBER, whatever opts.balance, opts.out_slot_order, lanes_per_wave and lanes_per_member did.
+ * The status bits of a resumed run start from zero: the status of a run made in pieces is the OR over the pieces (a member
+ * that went non-finite carries the NaN in its state and is flagged again).
+ * simplyp_state_bytes: S * SIMPLYP_N_STATE * E * 8 (host only; -1 for NULL or non-positive dims).
+ */
+int64_t simplyp_state_bytes(const simplyp_dims* dims);
+int simplyp_set_state(simplyp_ctx* ctx, const double* state_in, double* state_out);
 
 /* Host-pinned staging buffers for callers that do not use torch (hipHostMalloc/hipHostFree). */
 void* simplyp_host_alloc(int64_t bytes);

@@ -11,6 +11,11 @@ INTEG_CASHKARP_AUG_F32 = 3
 INTEGRATORS = {'rk4': INTEG_RK4, 'cashkarp': INTEG_CASHKARP, 'ck45': INTEG_CASHKARP,
                'cashkarp_aug': INTEG_CASHKARP_AUG, 'cashkarp_aug_f32': INTEG_CASHKARP_AUG_F32}
 
+# SIMPLYP_STATE_*: rows of the model state [S, N_STATE, E] (simplyp_set_state), in the header's order
+STATE_ROWS = ['VsA', 'VsS', 'Vg', 'Vr', 'Qr', 'Msus', 'TDPr', 'PPr', 'Plab_A', 'TDPs_A', 'Plab_NC', 'TDPs_NC',
+              'conc_TDPs_A', 'conc_TDPs_NC', 'h_next', 'D_snow']
+N_STATE = len(STATE_ROWS)
+
 STATUS_NONFINITE = 1
 STATUS_STEPCAP = 2
 

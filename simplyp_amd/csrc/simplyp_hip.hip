@@ -57,6 +57,8 @@ struct simplyp_ctx {
     int n_copy_streams = 2;
     double* stream_host = nullptr;      // armed for the next run (one-shot)
     int64_t stream_host_bytes = 0;
+    const double* state_in = nullptr;   // simplyp_set_state: armed for the next run (one-shot)
+    double* state_out = nullptr;
     uint32_t* host_ready = nullptr;     // [host_ready_cap] hipHostMalloc
     size_t host_ready_cap = 0;
     DeviceBuf chunk_count;              // [n_chunks] uint32
@@ -954,6 +956,10 @@ static int run_async_body(simplyp_ctx* ctx, const simplyp_dims* dims, const simp
     double* const host_out = ctx->stream_host;
     const int64_t host_out_bytes = ctx->stream_host_bytes;
     ctx->stream_host = nullptr; ctx->stream_host_bytes = 0;
+    // the model state armed by simplyp_set_state: one-shot in the same way
+    const double* const state_in = ctx->state_in;
+    double* const state_out = ctx->state_out;
+    ctx->state_in = nullptr; ctx->state_out = nullptr;
     if (int rc = check_args(ctx, dims, opts, forcing, doy, period_of_day, member_params, reach_params, up_ptr, up_idx, out,
                             member_status, member_of_slot, out_reaches, n_out_reaches, host_out, host_out_bytes))
         return rc;
@@ -999,6 +1005,8 @@ static int run_async_body(simplyp_ctx* ctx, const simplyp_dims* dims, const simp
         }
     }
     a.out_by_slot = opts->out_slot_order ? 1 : 0;
+    // warm start: set behind the pilot, which ranks the members' costs from the cold initial conditions and stores no state
+    a.state_in = state_in; a.state_out = state_out;
     if (opts->n_periods > 0)       // running sums start from zero
         HIP_TRY(ctx, hipMemsetAsync(out, 0, (size_t)simplyp_out_bytes(dims, opts, a.n_out_reaches), ctx->stream));
 
@@ -1141,6 +1149,21 @@ int simplyp_stream_out(simplyp_ctx* ctx, double* host_out, int64_t host_bytes)
     if (host_out && host_bytes <= 0) return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_stream_out: host_bytes must be > 0");
     ctx->stream_host = host_out;
     ctx->stream_host_bytes = host_out ? host_bytes : 0;
+    return SIMPLYP_OK;
+}
+
+int64_t simplyp_state_bytes(const simplyp_dims* dims)
+{
+    if (!dims || dims->E <= 0 || dims->S <= 0) return -1;
+    return (int64_t)dims->S * SIMPLYP_N_STATE * (int64_t)dims->E * (int64_t)sizeof(double);
+}
+
+int simplyp_set_state(simplyp_ctx* ctx, const double* state_in, double* state_out)
+{
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "a run is pending on this context; call simplyp_sync first");
+    ctx->state_in = state_in;
+    ctx->state_out = state_out;
     return SIMPLYP_OK;
 }
 

@@ -67,6 +67,10 @@ struct KernelArgs {
     double rtol, atol, step_len;
     int team_shift;                 // log2(lanes per member): 0, or 2 when a member is spread over a quad (opts.lanes_per_member = 4)
                                     // (last: the argument block of the one-lane kernels keeps the layout it was tuned with)
+    // Warm start (simplyp_set_state): the public model state, [S][SIMPLYP_N_STATE][E] in MEMBER order whatever the lane layout.
+    // Wave-uniform runtime switches read once per (reach, run) outside the day loop; nullptr = cold start / state not wanted.
+    const double* state_in;         // every (reach, member) starts its first day from this instead of the initial conditions
+    double* state_out;              // the state after the run's last day
 };
 
 // ---------------------------------------------------------------------------------------
@@ -1368,8 +1372,10 @@ __device__ __forceinline__ void soil_p_update(double aP, double KfMsoil, double 
 
 // Everything one lane does for one member over days [d_begin, d_end) of every reach of its chain.
 // `ckpt` ([CKPT_N][E], slot-major) carries a member's state across a time-chunk boundary for the queue
-// kernel (single-reach problems); the chain kernel passes nullptr and runs all days of every reach.
-constexpr int CKPT_N = 16;    // y[8], Plab_A, TDPs_A, Plab_NC, TDPs_NC, conc_A, conc_NC, h_carry, snow depth
+// kernel; the chain kernel passes nullptr and runs all days of every reach.  The same 16 rows, in the same order, are the
+// public state (include/simplyp.h, SIMPLYP_STATE_*): a.state_in is loaded where the run's first day starts and a.state_out is
+// stored behind its last, by member id -- the chunk boundary's hand-over, moved to the run's two ends.
+constexpr int CKPT_N = SIMPLYP_N_STATE;    // y[8], Plab_A, TDPs_A, Plab_NC, TDPs_NC, conc_A, conc_NC, h_carry, snow depth
 
 template <int INTEG, bool SNOW, int TEAM, bool STIFF = false>
 __device__ __forceinline__ void run_slot(const KernelArgs& a, double* s_P, double* s_E, double* s_T, int* s_doy,
@@ -1462,12 +1468,18 @@ __device__ __forceinline__ void run_slot(const KernelArgs& a, double* s_P, doubl
         double conc_NC = TDPs_NC / fc;                                                            // :446 (VsA0 == VsS0)
         double h_carry = a.step_len / (double)(a.substeps > 0 ? a.substeps : 1);
         double D_snow = SNOW ? MPv(SIMPLYP_PM_D_SNOW_0) : 0.0;                                    // inputs.py:198
-        if (ckpt && d_begin > 0) {      // resume from the previous time chunk (written by whichever wave ran it)
-            const double* k = ckpt + slot;
+        // resume from the previous time chunk (written by whichever wave ran it), or, on the run's first day, from the state
+        // the caller armed; either way the day-start auxiliary states below are formed from what was loaded
+        const double* k_in = nullptr;
+        if (d_begin > 0) { if (ckpt) k_in = ckpt + slot; }
+        else if (a.state_in) k_in = a.state_in + (size_t)s * CKPT_N * E + e;
+        if (k_in) {
+            const double* k = k_in;
 #pragma unroll
             for (int i = 0; i < 8; ++i) y[i] = k[(size_t)i * E];
             Plab_A = k[(size_t)8 * E]; TDPs_A = k[(size_t)9 * E]; Plab_NC = k[(size_t)10 * E]; TDPs_NC = k[(size_t)11 * E];
-            conc_A = k[(size_t)12 * E]; conc_NC = k[(size_t)13 * E]; h_carry = k[(size_t)14 * E];
+            conc_A = k[(size_t)12 * E]; conc_NC = k[(size_t)13 * E];
+            if (INTEG != SIMPLYP_INTEG_RK4) h_carry = k[(size_t)14 * E];      // (RK4 has no trial step: the row stays step_len / substeps)
             if (SNOW) D_snow = k[(size_t)15 * E];
         }
 
@@ -1770,13 +1782,17 @@ __device__ __forceinline__ void run_slot(const KernelArgs& a, double* s_P, doubl
                 o_day += row_stride;
             }
         }
-        if (ckpt && d_end < D && writer) {      // hand the state to whichever wave runs the next time chunk
-            double* k = ckpt + slot;
+        // hand the state to whichever wave runs the next time chunk, or, behind the run's last day, to the caller
+        double* k_out = nullptr;
+        if (d_end < D) { if (ckpt) k_out = ckpt + slot; }
+        else if (a.state_out) k_out = a.state_out + (size_t)s * CKPT_N * E + e;
+        if (k_out && writer) {
+            double* k = k_out;
 #pragma unroll
             for (int i = 0; i < 8; ++i) k[(size_t)i * E] = y[i];
             k[(size_t)8 * E] = Plab_A; k[(size_t)9 * E] = TDPs_A; k[(size_t)10 * E] = Plab_NC; k[(size_t)11 * E] = TDPs_NC;
             k[(size_t)12 * E] = conc_A; k[(size_t)13 * E] = conc_NC; k[(size_t)14 * E] = h_carry;
-            if (SNOW) k[(size_t)15 * E] = D_snow;
+            if (SNOW || d_end >= D) k[(size_t)15 * E] = D_snow;      // (the public state has the row always: 0.0 without snow)
         }
     }
 #undef MPv

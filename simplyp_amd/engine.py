@@ -27,7 +27,7 @@ ABI_SYMBOLS = ['simplyp_abi_version', 'simplyp_device_count', 'simplyp_ctx_creat
                'simplyp_run_async', 'simplyp_sync', 'simplyp_plan', 'simplyp_host_alloc', 'simplyp_host_free',
                'simplyp_device_alloc', 'simplyp_device_free', 'simplyp_memcpy_h2d', 'simplyp_memcpy_d2h', 'simplyp_gof',
                'simplyp_stream_out', 'simplyp_waterbody', 'simplyp_gof_waterbody', 'simplyp_gof_spearman', 'simplyp_eval_units',
-               'simplyp_quantiles']
+               'simplyp_quantiles', 'simplyp_state_bytes', 'simplyp_set_state']
 
 _lib = None
 
@@ -105,6 +105,10 @@ def lib():
                                     C.POINTER(abi.QuantileInfo)]
     L.simplyp_stream_out.restype = C.c_int
     L.simplyp_stream_out.argtypes = [vp, vp, C.c_int64]
+    L.simplyp_state_bytes.restype = C.c_int64
+    L.simplyp_state_bytes.argtypes = [C.POINTER(abi.Dims)]
+    L.simplyp_set_state.restype = C.c_int
+    L.simplyp_set_state.argtypes = [vp, vp, vp]
     L.simplyp_plan.restype = C.c_int
     L.simplyp_plan.argtypes = [C.c_int32] + [C.POINTER(C.c_int32)] * 8
     L.simplyp_host_alloc.restype = vp
@@ -273,7 +277,7 @@ class Engine(object):
 
     def run(self, forcing, doy, member_params, reach_params, up_ptr, up_idx, opts, forcing_of_member=None,
             out_reaches=None, out=None, member_rhs=None, member_of_slot=None, period_of_day=None, host_out=None,
-            defer_sync=False):
+            defer_sync=False, state_in=None, state_out=None):
         """Integrate every (member, reach) through all days on the device.
 
         forcing [n_sets,2,D] (rows P, PET; [n_sets,3,D] = Precipitation, PET, T_air with ``opts.snow``), doy [D], member_params [NP_M,E], reach_params [NP_R,S,E] may be numpy
@@ -290,7 +294,11 @@ class Engine(object):
         to be current): the call returns as soon as the launches are enqueued (``simplyp_run_async``); work the caller then
         enqueues on that stream runs after the kernel but BESIDE the tail of the streamed copies; the returned dict holds only
         ``member_of_slot`` and ``finish`` -- call ``stats.update(stats.pop('finish')())`` to wait (``simplyp_sync``) and get the
-        statistics.
+        statistics.  ``state_in`` / ``state_out`` (``simplyp_set_state``): the model state ``[S, abi.N_STATE, E]`` (rows
+        ``abi.STATE_ROWS``, member order) the run starts from instead of the cold initial conditions (numpy or device
+        tensor), and a float64 device tensor of that shape that receives the state after the last day (``True`` allocates
+        one; the same tensor may serve as both).  The end state comes back as ``stats['state']``; with ``defer_sync`` it is
+        valid after ``finish``.
         """
         torch = self.torch
         L = lib()
@@ -327,6 +335,23 @@ class Engine(object):
             if (not isinstance(host_out, np.ndarray) or host_out.dtype != np.float64 or not host_out.flags['C_CONTIGUOUS']
                     or host_out.shape != (ncols, rows, n_or, E)):
                 raise ValueError("host_out must be a C-contiguous float64 numpy array of shape %s" % ((ncols, rows, n_or, E),))
+        st_in = None
+        if state_in is not None:
+            st_in = state_in if (torch.is_tensor(state_in) and state_in.device == self.tdev and state_in.dtype == torch.float64
+                                 and state_in.is_contiguous()) else self.to_device(state_in, torch.float64)
+            if tuple(st_in.shape) != (S, abi.N_STATE, E):
+                raise ValueError("state_in must have shape %s, got %s" % ((S, abi.N_STATE, E), tuple(st_in.shape)))
+        if state_out is True:
+            state_out = torch.empty((S, abi.N_STATE, E), dtype=torch.float64, device=self.tdev)
+        elif state_out is False:
+            state_out = None
+        if state_out is not None and (not torch.is_tensor(state_out) or tuple(state_out.shape) != (S, abi.N_STATE, E)
+                                      or state_out.dtype != torch.float64 or not state_out.is_contiguous()
+                                      or state_out.device != self.tdev):
+            raise ValueError("state_out must be True or a contiguous float64 tensor of shape %s on %s"
+                             % ((S, abi.N_STATE, E), self.tdev))
+        if state_out is not None:
+            assert state_out.numel() * 8 == L.simplyp_state_bytes(C.byref(dims))
         status = torch.empty((E,), dtype=torch.int32, device=self.tdev)
         if opts.out_slot_order and member_of_slot is None:
             member_of_slot = torch.empty((E,), dtype=torch.int32, device=self.tdev)
@@ -341,6 +366,10 @@ class Engine(object):
                             'simplyp_stream_out')
             else:
                 self._check(L.simplyp_stream_out(self._h, None, C.c_int64(0)), 'simplyp_stream_out')
+            # one-shot like the stream arm; (None, None) disarms
+            self._check(L.simplyp_set_state(self._h, None if st_in is None else C.c_void_p(st_in.data_ptr()),
+                                            None if state_out is None else C.c_void_p(state_out.data_ptr())),
+                        'simplyp_set_state')
             args = (self._h, C.byref(dims), C.byref(opts), f.data_ptr(), dy.data_ptr(),
                     None if pod is None else pod.data_ptr(),
                     None if fom is None else fom.data_ptr(), mp.data_ptr(), rp.data_ptr(),
@@ -355,7 +384,7 @@ class Engine(object):
                 rc = L.simplyp_run(*(args + (C.byref(stats),)))
         self._check(rc, 'simplyp_run')
         if defer_sync:
-            keep = [f, dy, pod, fom, mp, rp, host_out]          # inputs stay alive until the run is over
+            keep = [f, dy, pod, fom, mp, rp, host_out, st_in]          # inputs stay alive until the run is over
 
             def finish():
                 with torch.cuda.device(self.tdev):
@@ -367,6 +396,8 @@ class Engine(object):
             sd = stats.as_dict()
         if member_of_slot is not None:
             sd['member_of_slot'] = member_of_slot
+        if state_out is not None:
+            sd['state'] = state_out
         return out, status, sd
 
 

@@ -147,3 +147,51 @@ def run_sharded(run_fn, forcing, doy, member_params, reach_params, up_ptr, up_id
         if fin is not None:
             stats.update(fin())
     return res
+
+
+def window_bounds(index, window='annual', reduce=None):
+    """Consecutive time windows of a daily series (pure host): ``[(lo, hi), ...]`` day ranges that tile ``index``.
+
+    ``window``: ``'annual'`` = one window per calendar year of ``index`` (a DatetimeIndex); an int = that many days per
+    window, the last one as short as what is left; a list of start dates, the first of which must be ``index[0]`` (each
+    window runs to the day before the next start, the last to the end).  ``reduce`` (``'annual'`` or an int array of
+    period indices per day, as in ``run_simply_p_ensemble``): a period's sum cannot be split over two tables, so every
+    window boundary must also be a period boundary -- ``ValueError`` otherwise."""
+    D = len(index)
+    if D == 0:
+        raise ValueError("empty index")
+    if isinstance(window, str):
+        if window != 'annual':
+            raise ValueError("window must be 'annual', a number of days or a list of start dates")
+        years = np.asarray(index.year)
+        starts = [0] + [int(i) for i in np.nonzero(years[1:] != years[:-1])[0] + 1]
+    elif isinstance(window, (int, np.integer)):
+        if int(window) < 1:
+            raise ValueError("a window needs at least one day")
+        starts = list(range(0, D, int(window)))
+    else:
+        import pandas as pd
+        dates = [pd.Timestamp(w) for w in window]
+        if not dates:
+            raise ValueError("window: the list of start dates is empty")
+        pos = index.get_indexer(pd.DatetimeIndex(dates))
+        if (pos < 0).any():
+            raise ValueError("window start %s is not a day of the series" % dates[int(np.argmax(pos < 0))].date())
+        starts = [int(x) for x in pos]
+        if starts[0] != 0 or any(b <= a for a, b in zip(starts, starts[1:])):
+            raise ValueError("window starts must begin with the first day of the series (%s) and increase" % index[0].date())
+    bounds = [(lo, hi) for lo, hi in zip(starts, starts[1:] + [D])]
+    if reduce is not None:
+        if isinstance(reduce, str):
+            if reduce != 'annual':
+                raise ValueError("reduce must be None, 'annual' or an array of period indices")
+            period = np.asarray(index.year)
+        else:
+            period = np.asarray(reduce)
+            if period.shape != (D,):
+                raise ValueError("reduce array needs one period index per day")
+        for lo, _ in bounds[1:]:
+            if period[lo] == period[lo - 1]:
+                raise ValueError("window boundary at %s falls inside an output period (reduce): a period's sum cannot be "
+                                 "split over two windows" % (index[lo].date() if hasattr(index[lo], 'date') else lo))
+    return bounds

@@ -168,14 +168,48 @@ def _output_dict(stats, status, solver):
     d['mused'] = np.array([1], dtype=np.int32)
     return d
 
-def run_simply_p(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, step_len=1., solver=None, device=0):
+def _state_blocks(initial_state, scs, E, index, bounds):
+    """Checks an ``initial_state`` (the ``'state'`` dict of an earlier result, or a bare array / device tensor [S, 16, E], or
+    a list of per-block tensors split as ``bounds``) against the run it is to start -- host only, before any device call --
+    and returns one array per member block of ``bounds``."""
+    S = len(scs)
+    data = initial_state
+    if isinstance(initial_state, dict):
+        data = initial_state['data']
+        if [int(r) for r in initial_state['reaches']] != [int(r) for r in scs]:
+            raise ValueError("initial_state holds reaches %s, the run has %s" % (list(initial_state['reaches']), list(scs)))
+        if list(initial_state.get('rows', abi.STATE_ROWS)) != list(abi.STATE_ROWS):
+            raise ValueError("initial_state rows %s are not abi.STATE_ROWS" % (list(initial_state['rows']),))
+        end = initial_state.get('end')
+        if end is not None:
+            first, want = pd.Timestamp(index[0]), pd.Timestamp(end) + pd.Timedelta(days=1)
+            if first != want:
+                raise ValueError("initial_state ends on %s, so the run must start on %s; met_df starts on %s"
+                                 % (pd.Timestamp(end).date(), want.date(), first.date()))
+    if isinstance(data, (list, tuple)):
+        blocks = list(data)
+        if len(blocks) != len(bounds) or any(tuple(b.shape) != (S, abi.N_STATE, hi - lo) for b, (lo, hi) in zip(blocks, bounds)):
+            raise ValueError("initial_state blocks %s do not match [S=%d, %d, members of each device block %s]"
+                             % ([tuple(b.shape) for b in blocks], S, abi.N_STATE, [hi - lo for lo, hi in bounds]))
+        return blocks
+    if tuple(data.shape) != (S, abi.N_STATE, E):
+        raise ValueError("initial_state must have shape [S, %d, E] = %s, got %s" % (abi.N_STATE, (S, abi.N_STATE, E), tuple(data.shape)))
+    if len(bounds) == 1:
+        return [data]
+    return [data[..., lo:hi] for lo, hi in bounds]
+
+
+def run_simply_p(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, step_len=1., solver=None, device=0,
+                 initial_state=None, return_state=False):
     """Simple hydrology, sediment and phosphorus model (reference model.py:193-827).
 
     Same arguments and 4-tuple return ``(df_TC_dict, df_R_dict, Kf, output_dict)`` as the
     reference.  Extra keyword arguments: ``solver`` (dict overriding ``abi.DEFAULT_SOLVER``:
     integrator 'cashkarp'|'rk4', rtol, atol, substeps, max_steps, project_vr) and ``device``.
     ``output_dict`` holds the engine's solver statistics, with LSODA's infodict keys ``nfe``, ``nst``, ``nje``, ``mused``,
-    ``message`` kept as aliases (``_output_dict``).
+    ``message`` kept as aliases (``_output_dict``).  ``initial_state`` / ``return_state``: warm start, as in
+    ``run_simply_p_ensemble`` -- the model state after the last day comes back as ``output_dict['state']``, and a later
+    call over the following dates given that dict as ``initial_state`` continues the run bit for bit.
     """
     from . import engine
 
@@ -187,9 +221,12 @@ def run_simply_p(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, step_len
     rp = marshal.reach_params(p_SC, p, 1)
     forcing, doy = marshal.forcing_arrays(met_df)
     opts = _engine_opts(p_SU, p, dynamic_options, step_len, solver, marshal.MASK_ALL)
+    st_in = None if initial_state is None else _state_blocks(initial_state, scs, 1, met_df.index, [(0, 1)])[0]
 
     eng = engine.get_engine(device)          # raises when the HIP library / device is missing
-    out_d, status_d, stats = eng.run(forcing, doy, mp, rp, up_ptr, up_idx, opts)
+    out_d, status_d, stats = eng.run(forcing, doy, mp, rp, up_ptr, up_idx, opts, state_in=st_in,
+                                     state_out=True if return_state else None)
+    state_d = stats.pop('state', None)
     out = out_d.cpu().numpy()                # [25, D, S, 1]
     status = int(status_d.cpu().numpy()[0])
     marshal.epilogue_mutations(p_SU, p_LU, p_SC, p)
@@ -248,6 +285,8 @@ def run_simply_p(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, step_len
         print('Results saved to csv\n')
 
     output_dict = _output_dict(stats, status, solver)
+    if state_d is not None:
+        output_dict['state'] = dict(rows=list(abi.STATE_ROWS), reaches=list(scs), data=state_d.cpu().numpy(), end=met_df.index[-1])
     return (df_TC_dict, df_R_dict, Kf, output_dict)                                          # :827
 
 
@@ -277,7 +316,7 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
                           outputs=None, out_reaches=None, step_len=1., solver=None, device=0, to_host=True,
                           reduce=None, obs_dict=None, keep_daily=True, snow_in_kernel=None, forcing_of_member=None,
                           waterbody=None, waterbody_obs=None, spearman=False, devices=None, quantiles=None,
-                          quantile_members=None):
+                          quantile_members=None, initial_state=None, return_state=False):
     """Run an ensemble of parameter sets through the engine in one call.
 
     ``overrides``: dict name -> array[E] (member parameters, see ``marshal.PM_NAMES``) or
@@ -335,6 +374,18 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     ``quantiles`` raises ValueError: a quantile of the whole ensemble is not a function of the member blocks' quantiles, so
     the band cannot be assembled from per-device results.
 
+    ``return_state=True``: the result gains ``'state'`` = dict(rows (``abi.STATE_ROWS``), reaches (all sub-catchments),
+    data[S, 16, E], end = ``met_df.index[-1]``): the model state after the last day, in member order (numpy, or a device
+    tensor with ``to_host=False``; ``return_state='device'`` keeps it on the device whatever ``to_host`` says -- with
+    ``devices=[...]`` as the list of the blocks' tensors, split as ``stats['bounds']``).  ``initial_state`` takes that dict,
+    or a bare array [S, 16, E]: every (member, reach) then starts from it instead of the reference's cold initial conditions
+    (model.py:377-459), and a run of D1 days followed by a run of the next D2 days started from its state gives the same
+    tables, status bits (OR over the pieces) and right-hand-side counts as the run of D1 + D2 days, bit for bit -- whatever
+    solver, lane layout, kernel path or member order either piece uses.  Given the dict, ``met_df`` must start on the day after ``end`` and the reaches must
+    match (``ValueError``, before any device call); a bare array skips the date check.  A member flagged non-finite
+    carries the NaN in its state and stays flagged.  ``run_simply_p_ensemble_windows`` threads the state through
+    consecutive time windows of one ensemble.
+
     Returns ``dict(columns, reaches, data[n_cols, D or n_periods, n_reaches, E], status[E], stats)``; ``data``
     and ``status`` are numpy arrays, or device tensors when ``to_host`` is False.
     The caller's ``p_LU``/``p_SC`` are edited in place exactly as by ``run_simply_p``.
@@ -366,6 +417,15 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         quantile_members = np.ascontiguousarray(np.asarray(quantile_members) != 0)
         if quantile_members.shape != (E,):
             raise ValueError("quantile_members needs one flag per member")
+    met_first = met_df[0] if isinstance(met_df, (list, tuple)) else met_df
+    if devices is None:
+        bounds = [(0, E)]
+    else:
+        from . import ensemble
+        if not list(devices):
+            raise ValueError("devices must name at least one GPU")
+        bounds = [b_ for b_ in (ensemble.shard_bounds(E, len(devices), r) for r in range(len(devices))) if b_[1] > b_[0]]
+    state_blocks = None if initial_state is None else _state_blocks(initial_state, scs, E, met_first.index, bounds)
     # the SoA arrays are marshalled straight into page-locked host memory: the uploads are asynchronous DMA transfers
     pin = engine.pinned_empty
     mp = marshal.member_params(p, p_LU, E, m_over, alloc=pin)
@@ -449,6 +509,10 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     def block_pass(eng, lo, hi):
         """Members [lo, hi) on one engine context: the run, then the reductions that want the table where it lies."""
         whole = (lo == 0 and hi == E)
+        st_in = None
+        if state_blocks is not None:
+            st_in = state_blocks[bounds.index((lo, hi))]
+            st_in = st_in.contiguous() if hasattr(st_in, 'contiguous') else np.ascontiguousarray(st_in, dtype=np.float64)
         mp_b = mp if whole else np.ascontiguousarray(mp[:, lo:hi])
         rp_b = rp if whole else np.ascontiguousarray(rp[:, :, lo:hi])
         fom_b = None if forcing_of_member is None else np.ascontiguousarray(forcing_of_member[lo:hi])
@@ -458,8 +522,10 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         # caller only wants the statistics (keep_daily=False)
         host_out = _host_table((ncols_, rows_, n_or_, hi - lo), pin) if want_host_table else None
         out_d, status_d, stats = eng.run(forcing, doy, mp_b, rp_d, up_ptr, up_idx, opts, out_reaches=oreach,
-                                         period_of_day=period_of_day, forcing_of_member=fom_b, host_out=host_out)
-        part = dict(stats=stats, status=status_d.cpu().numpy() if to_host else status_d, host_out=host_out)
+                                         period_of_day=period_of_day, forcing_of_member=fom_b, host_out=host_out,
+                                         state_in=st_in, state_out=True if return_state else None)
+        state_d = stats.pop('state', None)
+        part = dict(stats=stats, state=state_d, status=status_d.cpu().numpy() if to_host else status_d, host_out=host_out)
         mos = stats.get('member_of_slot') if opts.out_slot_order else None
         if obs is not None:
             gof_d, info = eng.gof(out_d, mask, obs, ft, rp_d, out_reaches=oreach, member_of_slot=mos, spearman=spearman)
@@ -485,19 +551,15 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         return part
 
     if devices is None:
-        parts, bounds = [block_pass(engine.get_engine(device), 0, E)], [(0, E)]
+        parts = [block_pass(engine.get_engine(device), 0, E)]
     else:
-        from . import ensemble
         devs = [int(d) for d in devices]
-        if not devs:
-            raise ValueError("devices must name at least one GPU")
         if opts.out_slot_order:
             raise ValueError("devices=[...] returns tables in member order: solver['out_slot_order'] must stay 0")
-        bounds = [ensemble.shard_bounds(E, len(devs), r) for r in range(len(devs))]
+        all_bounds = [ensemble.shard_bounds(E, len(devs), r) for r in range(len(devs))]
         # one context per list entry (a repeated id gets a context of its own: contexts are not re-entrant)
         engs = [engine.get_engine(d, replica=devs[:r].count(d)) for r, d in enumerate(devs)]
-        live = [(eng_, lo, hi) for eng_, (lo, hi) in zip(engs, bounds) if hi > lo]
-        bounds = [(lo, hi) for _, lo, hi in live]
+        live = [(eng_, lo, hi) for eng_, (lo, hi) in zip(engs, all_bounds) if hi > lo]
         if len(live) == 1:
             parts = [block_pass(*live[0])]
         else:
@@ -546,6 +608,15 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         res['quantiles'] = band(*parts[0]['quant'])
         if res.get('waterbody') is not None:
             res['waterbody']['quantiles'] = band(*parts[0]['wb_quant'])
+    if return_state:
+        sts = [pt['state'] for pt in parts]
+        if return_state == 'device':
+            sdata = sts[0] if len(sts) == 1 else sts
+        elif to_host:
+            sdata = np.concatenate([t.cpu().numpy() for t in sts], axis=-1)
+        else:
+            sdata = cat(sts)
+        res['state'] = dict(rows=list(abi.STATE_ROWS), reaches=list(scs), data=sdata, end=met_df.index[-1])
     if reduced_on_device and not keep_daily:
         res['data'] = None
     elif not to_host:
@@ -571,3 +642,44 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
 def _torch_cat(xs):
     import torch
     return torch.cat([x.to(xs[0].device) for x in xs], dim=-1)
+
+
+def run_simply_p_ensemble_windows(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, window='annual', initial_state=None,
+                                  **kwargs):
+    """One ensemble run cut into consecutive time windows: a generator of ``run_simply_p_ensemble`` results, one per window.
+
+    Same arguments as ``run_simply_p_ensemble`` plus ``window`` (``'annual'`` = calendar years, an int = that many days, or
+    a list of start dates: ``ensemble.window_bounds``).  The model state is threaded from window to window on the device
+    (``simplyp_set_state``), so the windows' tables laid end to end ARE the table of the single call, bit for bit, and so
+    are the summed ``rhs_evals`` / ``steps`` / ``rejected``; a window's table exists only while the caller holds its item, so
+    the peak device and host footprint is one window's: the daily series, per-year goodness of fit or percentile bands of
+    an ensemble whose whole table would not fit anywhere.  ``obs_dict`` / ``waterbody`` / ``quantiles`` apply per window.
+    With ``reduce``, window boundaries must fall on period boundaries (``ValueError``).
+
+    Each item also carries ``'window'`` = (first day, last day, lo, hi) and ``'state'`` (on the device; the last item's is
+    where a later run continues).  ``status`` is per window: the status of the whole run is the OR over the items (a
+    member that went non-finite carries the NaN in its state and is flagged in every later window too).  Bad arguments
+    raise when the generator is created, not at its first item."""
+    from . import ensemble
+    met_sets = list(met_df) if isinstance(met_df, (list, tuple)) else [met_df]
+    index = met_sets[0].index
+    reduce = kwargs.get('reduce')
+    bounds = ensemble.window_bounds(index, window, reduce=reduce)
+    if 'return_state' in kwargs:
+        raise ValueError("run_simply_p_ensemble_windows always returns the state (on the device)")
+
+    def gen():
+        state = initial_state
+        for lo, hi in bounds:
+            kw = dict(kwargs)
+            if reduce is not None and not isinstance(reduce, str):
+                part = np.asarray(reduce)[lo:hi]
+                kw['reduce'] = part - part.min()
+            mets = [m.iloc[lo:hi] for m in met_sets]
+            res = run_simply_p_ensemble(mets if isinstance(met_df, (list, tuple)) else mets[0], p_struc, p_SU, p_LU, p_SC, p,
+                                        dynamic_options, initial_state=state, return_state='device', **kw)
+            state = res['state']
+            res['window'] = (index[lo], index[hi - 1], lo, hi)
+            yield res
+            del res
+    return gen()
