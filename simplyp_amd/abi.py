@@ -40,8 +40,8 @@ class Stats(C.Structure):
                 ('kernel_ms', C.c_double), ('pilot_ms', C.c_double), ('simt_efficiency', C.c_double), ('n_launches', C.c_int32), ('balanced', C.c_int32),
                 ('queued', C.c_int32), ('lanes_per_wave', C.c_int32), ('lanes_per_member', C.c_int32), ('streamed_chunks', C.c_int32),
                 ('d2h_tail_ms', C.c_double), ('wall_ms', C.c_double), ('stream_gbs', C.c_double),
-                ('queue_waits', C.c_uint64), ('queue_longest_wait_polls', C.c_uint64), ('queue_longest_stall_polls', C.c_uint64),
-                ('stiff_pair', C.c_int32), ('reserved0', C.c_int32)]
+                ('queue_waits', C.c_uint64), ('queue_longest_wait_polls', C.c_uint32), ('pack_overflow_blocks', C.c_uint32), ('queue_longest_stall_polls', C.c_uint64),
+                ('stiff_pair', C.c_int32), ('packed_records', C.c_int32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}

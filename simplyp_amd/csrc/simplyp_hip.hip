@@ -21,6 +21,7 @@
 #include "simplyp_gof.hip.h"
 #include "simplyp_waterbody.hip.h"
 #include "simplyp_quantile.hip.h"
+#include "simplyp_pack_stream.h"
 
 namespace {
 
@@ -67,7 +68,18 @@ struct simplyp_ctx {
         double* host = nullptr;
         int ncols = 0, n_chunks = 0, chunk_days = 0;
         size_t D = 0, row_doubles = 0;  // rows per column, doubles per row (n_out_reaches * E)
+        // packed stream (simplyp_pack.h): records [n_chunks][ncols] in `pack_dev`, `pack_stride` bytes apart; off when null
+        const unsigned char* pack_dev = nullptr;
+        size_t pack_stride = 0;
+        unsigned pack_cap = 0;
+        int n_packed = 0, n_raw = 0;    // records the copier sent packed / raw
+        unsigned n_overflow = 0;        // overflow blocks of the packed ones
     } copy_plan;
+    DeviceBuf packed;                   // the packed records of a run (grow-only; given back by the first run that does not pack)
+    DeviceBuf pack_count;               // [n_records] uint32 overflow counters
+    uint32_t* host_pack_count = nullptr;    // the same in pinned host memory, written by the wave that completes a chunk
+    size_t host_pack_count_cap = 0;
+    simplyp_pack::PackStream pack;      // staging ring, dispatcher and decode pool
     std::thread copier;
     std::atomic<int> run_over{0};       // set by simplyp_sync once the launches have finished (the copier stops waiting for flags)
     int copy_error = 0;                 // first hipError_t the copier saw
@@ -369,11 +381,33 @@ void copier_main(simplyp_ctx* ctx)
                 fprintf(stderr, "[simplyp] copier: chunk %d ready=%u over=%d at %.1f ms\n", c, ctx->host_ready[c], (int)run_over,
                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->t_begin).count());
         }
+        // a chunk whose flag never rose (the run ended in an error) has no valid counters: it travels raw
+        const bool chunk_packed = p.pack_dev && __atomic_load_n(&ctx->host_ready[c0], __ATOMIC_ACQUIRE) != 0u;
         const size_t d0 = (size_t)c0 * p.chunk_days, nd = std::min<size_t>((size_t)(c1 - c0) * p.chunk_days, p.D - d0);
         // (one plain copy per column: a pitched hipMemcpy2DAsync per chunk does not overlap the persistent kernel at all on this
         // stack -- 1509 ms per pass instead of 803, profiles/r02_experiments.md)
         for (int j = 0; j < p.ncols; ++j) {
             const size_t off = ((size_t)j * p.D + d0) * p.row_doubles;
+            if (chunk_packed) {
+                // the record instead of the rows: into the staging ring, and from there through the decode pool into p.host
+                const size_t rec = (size_t)c0 * p.ncols + j;
+                const unsigned count = ctx->host_pack_count[rec];
+                if (count <= p.pack_cap) {
+                    simplyp_pack::PackJob job;
+                    job.dev_rec = p.pack_dev + rec * p.pack_stride;
+                    job.nd = (int)nd;
+                    job.L = simplyp_pack::layout(p.row_doubles, (int)nd, p.pack_cap);
+                    job.count = count;
+                    job.dst = p.host + off;
+                    job.stride = p.row_doubles;
+                    hipError_t err = ctx->pack.submit(job, ctx->copy_streams[n_issued++ % (unsigned)ctx->n_copy_streams]);
+                    if (err != hipSuccess && !ctx->copy_error) ctx->copy_error = (int)err;
+                    ++ctx->copy_plan.n_packed;
+                    ctx->copy_plan.n_overflow += count;
+                    continue;
+                }
+                ++ctx->copy_plan.n_raw;       // overflow area full: this chunk-column travels as fp64, as below
+            }
             // two streams, taken in turn: the launch gap of one copy dispatch hides behind the other stream's transfer
             hipError_t err = hipMemcpyAsync(p.host + off, p.dev + off, nd * p.row_doubles * sizeof(double),
                                             hipMemcpyDeviceToHost, ctx->copy_streams[n_issued++ % (unsigned)ctx->n_copy_streams]);
@@ -687,6 +721,57 @@ int balance_members(simplyp_ctx* ctx, const simplyp_opts& opts, const RunShape& 
     return SIMPLYP_OK;
 }
 
+// Packed output stream: may this run's streamed table travel as packed records (simplyp_pack.h)?  The pack epilogue of the
+// queue kernel handles the plain case only: daily rows of one reach, one lane per member, full waves, and lane slots that are
+// contiguous in the table (columns in slot order, or no permutation at all).
+bool pack_eligible(const simplyp_opts& opts, const RunShape& shape, const simplyp::KernelArgs& a)
+{
+    return shape.stream_chunks && opts.n_periods == 0 && a.S == 1 && a.n_out_reaches == 1 && shape.team == 1 &&
+           shape.lanes == simplyp::WAVE && (a.out_by_slot || !a.perm);
+}
+
+// SIMPLYP_STREAM_PACK unset: pack only when the raw copies would clearly outlast the kernel.  Per day of
+// the run, the raw table needs n_cols x E x 8 bytes at PACK_LINK_GBS on the link; the kernel needs PACK_KERNEL_NS_PER_MEMBER_DAY
+// per member (the flagship: 533.6 ms for 100 000 members x 10 957 days) but never less than one round of waves
+// (PACK_KERNEL_US_PER_DAY_MIN: 480 ms for the 50 000-member shard that fills 782 of the 1024 wave slots).  Packing saves an
+// eighth of the copy at best, so a run whose copy is not 15 % longer than its kernel gains nothing.
+constexpr double PACK_LINK_GBS = 56.7, PACK_KERNEL_NS_PER_MEMBER_DAY = 0.487, PACK_KERNEL_US_PER_DAY_MIN = 43.8;
+constexpr bool PACK_AUTO_ON = true;       // the gate's verdict (profiles/r06_pack/gate.md)
+
+bool pack_wanted(const simplyp_opts& opts, const RunShape& shape, const simplyp::KernelArgs& a)
+{
+    if (!pack_eligible(opts, shape, a)) return false;
+    if (const char* env = getenv("SIMPLYP_STREAM_PACK")) {
+        if (env[0] == '0') return false;
+        if (env[0] == '1') return true;
+    }
+    const double copy_us = (double)popcount32(a.out_mask) * a.E * 8.0 / (PACK_LINK_GBS * 1e3);
+    const double kernel_us = std::max(PACK_KERNEL_US_PER_DAY_MIN, PACK_KERNEL_NS_PER_MEMBER_DAY * 1e-3 * a.E);
+    return PACK_AUTO_ON && copy_us > 1.15 * kernel_us;
+}
+
+// Buffers of a packed run: the device records, their overflow counters on the device and in pinned host memory (zeroed).
+// `stride` = 0 when the records do not fit the device's free memory: the run then streams raw.
+int ensure_pack_buffers(simplyp_ctx* ctx, size_t row_doubles, int chunk_days, int n_records, size_t& stride, unsigned& cap)
+{
+    cap = simplyp_pack::overflow_capacity((int)((row_doubles + simplyp_pack::GROUP - 1) / simplyp_pack::GROUP));
+    stride = simplyp_pack::layout(row_doubles, chunk_days, cap).bytes;
+    const size_t bytes = (size_t)n_records * stride;
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    if (bytes > ctx->packed.bytes && bytes - ctx->packed.bytes > free_b / 10 * 9) { stride = 0; return SIMPLYP_OK; }
+    if (int rc = ensure(ctx, ctx->packed, bytes)) return rc;
+    if (int rc = ensure(ctx, ctx->pack_count, (size_t)n_records * sizeof(unsigned))) return rc;
+    if ((size_t)n_records > ctx->host_pack_count_cap) {
+        if (ctx->host_pack_count) { (void)hipHostFree(ctx->host_pack_count); ctx->host_pack_count = nullptr; ctx->host_pack_count_cap = 0; }
+        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->host_pack_count, (size_t)n_records * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));
+        ctx->host_pack_count_cap = (size_t)n_records;
+    }
+    memset(ctx->host_pack_count, 0, (size_t)n_records * sizeof(uint32_t));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->pack_count.ptr, 0, (size_t)n_records * sizeof(unsigned), ctx->stream));
+    return SIMPLYP_OK;
+}
+
 // Task-queue kernel: (reach, time chunk, member group) tasks pulled by one persistent wave per SIMD.  `queued` stays false, and
 // nothing is enqueued, when the ring buffers of the routing series do not fit: the run then takes the chain kernel.
 int launch_queue(simplyp_ctx* ctx, const simplyp_opts& opts, const RunShape& shape, const Topology& topo,
@@ -728,6 +813,7 @@ int launch_queue(simplyp_ctx* ctx, const simplyp_opts& opts, const RunShape& sha
     q.ckpt = (double*)(base + flags_bytes + ints_bytes);
     q.n_groups = G; q.n_pairs = (int)pair_idx.size(); q.chunk_days = chunk_days; q.ring_chunks = topo.ring_chunks;
     q.chunk_count = nullptr; q.host_ready = nullptr; q.tasks_per_chunk = (unsigned)S * (unsigned)G;
+    q.pack_buf = nullptr; q.pack_count = nullptr; q.host_pack_count = nullptr; q.pack_stride = 0; q.pack_cap = 0; q.pack_cols = 0;
     if (shape.stream_chunks) {
         if (int rc = ensure(ctx, ctx->chunk_count, (size_t)n_chunks * sizeof(unsigned))) return rc;
         if ((size_t)n_chunks > ctx->host_ready_cap) {
@@ -744,6 +830,17 @@ int launch_queue(simplyp_ctx* ctx, const simplyp_opts& opts, const RunShape& sha
         q.host_ready = ctx->host_ready;
         ctx->copy_plan.n_chunks = n_chunks;
         ctx->copy_plan.chunk_days = chunk_days;
+        if (pack_wanted(opts, shape, a)) {
+            const int ncols = popcount32(a.out_mask);
+            size_t stride = 0;
+            unsigned cap = 0;
+            if (int rc = ensure_pack_buffers(ctx, (size_t)E, chunk_days, n_chunks * ncols, stride, cap)) return rc;
+            if (stride) {
+                q.pack_buf = (unsigned char*)ctx->packed.ptr; q.pack_count = (unsigned*)ctx->pack_count.ptr;
+                q.host_pack_count = ctx->host_pack_count; q.pack_stride = stride; q.pack_cap = cap; q.pack_cols = ncols;
+                ctx->copy_plan.pack_dev = q.pack_buf; ctx->copy_plan.pack_stride = stride; ctx->copy_plan.pack_cap = cap;
+            }
+        }
     }
     q.max_polls = 20000000u;      // x (s_sleep 64 ~ 2 us): ~40 s in which NO task of the run completed means something is broken
     if (const char* mp_env = getenv("SIMPLYP_QUEUE_MAX_POLLS")) q.max_polls = (unsigned)strtoul(mp_env, nullptr, 10);
@@ -774,6 +871,14 @@ int arm_copy(simplyp_ctx* ctx, double* host_out, const simplyp_opts& opts, const
     cp.D = (size_t)(opts.n_periods > 0 ? opts.n_periods : a.D);
     cp.row_doubles = (size_t)a.n_out_reaches * a.E;
     if (chunked) {
+        if (cp.pack_dev) {
+            // ring, dispatcher and decode pool first (the ring is allocated, and so first touched, by the calling thread)
+            hipError_t err = ctx->pack.start(ctx->device, cp.row_doubles, cp.pack_stride, cp.n_chunks * cp.ncols, simplyp_pack::decode_threads());
+            if (err != hipSuccess) {
+                ctx->pack.finish();
+                return fail(ctx, SIMPLYP_ERR_NOMEM, "packed output stream: the pinned staging ring failed: %s", hipGetErrorString(err));
+            }
+        }
         ctx->run_over.store(0, std::memory_order_release);
         ctx->copier = std::thread(copier_main, ctx);       // chunk by chunk, beside the kernel
     } else {
@@ -791,6 +896,7 @@ void stop_copier(simplyp_ctx* ctx)
 {
     ctx->run_over.store(1, std::memory_order_release);
     if (ctx->copier.joinable()) ctx->copier.join();
+    ctx->pack.finish();         // every landed record decoded, every ring slot released, the pool joined (no-op when not packed)
 }
 
 }  // namespace
@@ -869,8 +975,12 @@ void simplyp_ctx_destroy(simplyp_ctx* ctx)
         if (ctx->copy_streams[i]) { (void)hipStreamSynchronize(ctx->copy_streams[i]); (void)hipStreamDestroy(ctx->copy_streams[i]); }
         if (ctx->ev_copy_join[i]) (void)hipEventDestroy(ctx->ev_copy_join[i]);
     }
+    ctx->pack.release();
     if (ctx->ev_copy_done) (void)hipEventDestroy(ctx->ev_copy_done);
     if (ctx->host_ready) (void)hipHostFree(ctx->host_ready);
+    if (ctx->host_pack_count) (void)hipHostFree(ctx->host_pack_count);
+    if (ctx->packed.ptr) (void)hipFree(ctx->packed.ptr);
+    if (ctx->pack_count.ptr) (void)hipFree(ctx->pack_count.ptr);
     if (ctx->chunk_count.ptr) (void)hipFree(ctx->chunk_count.ptr);
     if (ctx->route.ptr) (void)hipFree(ctx->route.ptr);
     if (ctx->sched.ptr) (void)hipFree(ctx->sched.ptr);
@@ -965,7 +1075,8 @@ static int run_async_body(simplyp_ctx* ctx, const simplyp_dims* dims, const simp
         return rc;
     ctx->t_begin = std::chrono::steady_clock::now();
     ctx->copy_pending = false; ctx->copy_error = 0; ctx->streamed_chunks = 0;
-    ctx->copy_plan.n_chunks = 0;
+    ctx->copy_plan.n_chunks = 0; ctx->copy_plan.pack_dev = nullptr;
+    ctx->copy_plan.n_packed = ctx->copy_plan.n_raw = 0; ctx->copy_plan.n_overflow = 0;
     const int E = dims->E, S = dims->S, D = dims->D;
     Schedule sch;
     int rc = build_schedule(ctx, S, up_ptr, up_idx, sch);
@@ -1083,6 +1194,7 @@ static int sync_impl(simplyp_ctx* ctx, simplyp_stats* stats)
     const bool copied = ctx->copy_pending;
     if (copied) {
         stop_copier(ctx);                                      // the launches are done
+        if (!ctx->copy_error && ctx->pack.error()) ctx->copy_error = ctx->pack.error();
         if (ctx->copy_error)
             return fail(ctx, SIMPLYP_ERR_DEVICE, "streamed output: a device-to-host copy failed: %s", hipGetErrorString((hipError_t)ctx->copy_error));
         HIP_TRY(ctx, hipEventSynchronize(ctx->ev_copy_done));
@@ -1120,7 +1232,11 @@ static int sync_impl(simplyp_ctx* ctx, simplyp_stats* stats)
         stats->d2h_tail_ms = copied ? ms_tail : 0.0;
         stats->stream_gbs = stream_gbs;
         stats->queue_waits = ctx->last.queued ? c[4] : 0;
-        stats->queue_longest_wait_polls = ctx->last.queued ? c[5] : 0;
+        stats->queue_longest_wait_polls = ctx->last.queued ? (uint32_t)c[5] : 0;
+        if (copied && ctx->copy_plan.pack_dev) {
+            stats->packed_records = (int32_t)(((uint32_t)ctx->copy_plan.n_raw << 16) | ((uint32_t)ctx->copy_plan.n_packed & 0xFFFFu));
+            stats->pack_overflow_blocks = ctx->copy_plan.n_overflow;
+        }
         stats->queue_longest_stall_polls = ctx->last.queued ? c[6] : 0;
         stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->t_begin).count();
     }
@@ -1139,6 +1255,9 @@ int simplyp_sync(simplyp_ctx* ctx, simplyp_stats* stats)
         rc = fail(ctx, SIMPLYP_ERR_DEVICE, "unexpected host error: %s", e.what());
     }
     quiesce_streaming(ctx);      // on every exit, error or not (a second join / synchronize is a no-op)
+    // The packed records are as large as the table they mirror (44 GB for C3): the buffer stays for the next packed run of the
+    // same kind, but a context that has moved on to other work gives it back, outside the run's wall time
+    if (!ctx->copy_plan.pack_dev && ctx->packed.ptr) { (void)hipFree(ctx->packed.ptr); ctx->packed.ptr = nullptr; ctx->packed.bytes = 0; }
     return rc;
 }
 
@@ -1150,6 +1269,114 @@ int simplyp_stream_out(simplyp_ctx* ctx, double* host_out, int64_t host_bytes)
     ctx->stream_host = host_out;
     ctx->stream_host_bytes = host_out ? host_bytes : 0;
     return SIMPLYP_OK;
+}
+
+// simplyp_fetch_packed: the table is packed by one wave per (chunk, 64-double group), then every record takes the copier's and
+// the decode pool's path of a packed run (raw records are copied from the table, as there).
+static int fetch_packed_impl(simplyp_ctx* ctx, const double* dev_table, int32_t n_cols, int32_t rows, int32_t row_doubles,
+                             int32_t chunk_days, double* host_out, int64_t host_bytes, int32_t* counts)
+{
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "a run is pending on this context; call simplyp_sync first");
+    if (!dev_table || !host_out || n_cols <= 0 || rows <= 0 || row_doubles <= 0 || chunk_days <= 0)
+        return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_fetch_packed: bad table arguments");
+    const size_t table_bytes = (size_t)n_cols * rows * row_doubles * sizeof(double);
+    if (host_bytes < (int64_t)table_bytes)
+        return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_fetch_packed: host buffer of %lld bytes is smaller than the table (%zu)", (long long)host_bytes, table_bytes);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int chunk = (chunk_days + 63) / 64 * 64, n_chunks = (rows + chunk - 1) / chunk;
+    const int G = (row_doubles + simplyp_pack::GROUP - 1) / simplyp_pack::GROUP, n_rec = n_chunks * n_cols;
+    if (n_chunks > 65535) return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_fetch_packed: more than 65535 chunks");
+    size_t stride = 0;
+    unsigned cap = 0;
+    if (int rc = ensure_pack_buffers(ctx, (size_t)row_doubles, chunk, n_rec, stride, cap)) return rc;
+    if (!stride) return fail(ctx, SIMPLYP_ERR_NOMEM, "simplyp_fetch_packed: the packed records do not fit the device's free memory");
+    hipLaunchKernelGGL(simplyp::simplyp_pack_table_kernel, dim3((unsigned)G, (unsigned)n_chunks), dim3(simplyp::WAVE), 0, ctx->stream, dev_table,
+                       n_cols, rows, row_doubles, chunk, (unsigned char*)ctx->packed.ptr, (unsigned*)ctx->pack_count.ptr,
+                       (unsigned long long)stride, cap);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->host_pack_count, ctx->pack_count.ptr, (size_t)n_rec * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    hipError_t err = ctx->pack.start(ctx->device, (size_t)row_doubles, stride, n_rec, simplyp_pack::decode_threads());
+    int n_packed = 0, n_raw = 0;
+    unsigned n_overflow = 0, n_issued = 0;
+    for (int c = 0; c < n_chunks && err == hipSuccess; ++c) {
+        const size_t d0 = (size_t)c * chunk, nd = std::min<size_t>((size_t)chunk, (size_t)rows - d0);
+        for (int j = 0; j < n_cols && err == hipSuccess; ++j) {
+            const size_t rec = (size_t)c * n_cols + j, off = ((size_t)j * rows + d0) * row_doubles;
+            const unsigned count = ctx->host_pack_count[rec];
+            hipStream_t st = ctx->copy_streams[n_issued++ % (unsigned)ctx->n_copy_streams];
+            if (count <= cap) {
+                simplyp_pack::PackJob job;
+                job.dev_rec = (const unsigned char*)ctx->packed.ptr + rec * stride;
+                job.nd = (int)nd;
+                job.L = simplyp_pack::layout((size_t)row_doubles, (int)nd, cap);
+                job.count = count;
+                job.dst = host_out + off;
+                job.stride = (size_t)row_doubles;
+                err = ctx->pack.submit(job, st);
+                ++n_packed; n_overflow += count;
+            } else {
+                err = hipMemcpyAsync(host_out + off, dev_table + off, nd * row_doubles * sizeof(double), hipMemcpyDeviceToHost, st);
+                ++n_raw;
+            }
+        }
+    }
+    for (int i = 0; i < ctx->n_copy_streams; ++i) {
+        hipError_t e2 = hipStreamSynchronize(ctx->copy_streams[i]);
+        if (err == hipSuccess) err = e2;
+    }
+    ctx->pack.finish();
+    if (err == hipSuccess && ctx->pack.error()) err = (hipError_t)ctx->pack.error();
+    if (err != hipSuccess) return fail(ctx, SIMPLYP_ERR_DEVICE, "simplyp_fetch_packed: %s", hipGetErrorString(err));
+    if (counts) { counts[0] = n_packed; counts[1] = (int32_t)n_overflow; counts[2] = n_raw; }
+    return SIMPLYP_OK;
+}
+
+int simplyp_fetch_packed(simplyp_ctx* ctx, const double* dev_table, int32_t n_cols, int32_t rows, int32_t row_doubles,
+                         int32_t chunk_days, double* host_out, int64_t host_bytes, int32_t* counts)
+{
+    SIMPLYP_GUARD(ctx, fetch_packed_impl(ctx, dev_table, n_cols, rows, row_doubles, chunk_days, host_out, host_bytes, counts))
+}
+
+static int pack_roundtrip_host_impl(const double* table, int32_t n_cols, int32_t rows, int32_t row_doubles, int32_t chunk_days,
+                                    double* out, int32_t* counts)
+{
+    if (!table || !out || n_cols <= 0 || rows <= 0 || row_doubles <= 0 || chunk_days <= 0)
+        return fail(nullptr, SIMPLYP_ERR_ARG, "simplyp_pack_roundtrip_host: bad table arguments");
+    const size_t E = (size_t)row_doubles;
+    const int chunk = (chunk_days + 63) / 64 * 64, n_chunks = (rows + chunk - 1) / chunk;
+    const unsigned cap = simplyp_pack::overflow_capacity((int)((E + simplyp_pack::GROUP - 1) / simplyp_pack::GROUP));
+    std::vector<unsigned char> rec(simplyp_pack::layout(E, chunk, cap).bytes);
+    std::vector<uint64_t> run(E);
+    int n_packed = 0, n_raw = 0;
+    unsigned n_overflow = 0;
+    constexpr int RANGES = 3;       // the decoder works on member ranges, as the pool's threads do
+    for (int c = 0; c < n_chunks; ++c) {
+        const size_t d0 = (size_t)c * chunk;
+        const int nd = (int)std::min<size_t>((size_t)chunk, (size_t)rows - d0);
+        const simplyp_pack::Layout L = simplyp_pack::layout(E, nd, cap);
+        for (int j = 0; j < n_cols; ++j) {
+            const size_t off = ((size_t)j * rows + d0) * E;
+            const unsigned count = simplyp_pack::encode_record_host(table + off, E, nd, E, rec.data(), L, cap);
+            if (count > cap) { memcpy(out + off, table + off, (size_t)nd * E * sizeof(double)); ++n_raw; continue; }
+            for (int t = 0; t < RANGES; ++t) {
+                const size_t e0 = t == 0 ? 0 : (E * t / RANGES) / 8 * 8, e1 = t + 1 == RANGES ? E : (E * (t + 1) / RANGES) / 8 * 8;
+                if (e1 > e0) simplyp_pack::decode_range(rec.data(), L, nd, E, e0, e1, out + off, E, run.data());
+            }
+            __builtin_ia32_sfence();
+            simplyp_pack::apply_overflow(rec.data(), L, nd, E, count, out + off, E);
+            ++n_packed; n_overflow += count;
+        }
+    }
+    if (counts) { counts[0] = n_packed; counts[1] = (int32_t)n_overflow; counts[2] = n_raw; }
+    return SIMPLYP_OK;
+}
+
+int simplyp_pack_roundtrip_host(const double* table, int32_t n_cols, int32_t rows, int32_t row_doubles, int32_t chunk_days,
+                                double* out, int32_t* counts)
+{
+    SIMPLYP_GUARD(nullptr, pack_roundtrip_host_impl(table, n_cols, rows, row_doubles, chunk_days, out, counts))
 }
 
 int64_t simplyp_state_bytes(const simplyp_dims* dims)

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/simplyp.h"
+#include "simplyp_pack.h"                           // the codec of the packed output stream (host and device)
 #include "../../include/simplyp_controller.h"     // the step controller's constants, shared with the CPU oracle
 
 namespace simplyp {
@@ -1890,6 +1891,15 @@ struct QueueArgs {
     unsigned* chunk_count;     // [n_chunks] device
     unsigned* host_ready;      // [n_chunks] host-pinned, device-visible
     unsigned tasks_per_chunk;  // S * n_groups
+    // packed output stream (simplyp_pack.h; eligible runs only: one reach, one lane per member, 64 slots per wave, lane slots
+    // contiguous in the table).  The wave packs the rows of its own task into record (chunk, column) before it releases the task;
+    // the wave that completes a chunk hands the records' overflow counters to the host beside the chunk's flag.  nullptr = off.
+    unsigned char* pack_buf;   // [n_chunks][pack_cols] records, pack_stride bytes apart
+    unsigned* pack_count;      // [n_chunks][pack_cols] device: overflow blocks per record
+    unsigned* host_pack_count; // the same, host-pinned
+    unsigned long long pack_stride;
+    unsigned pack_cap;         // overflow slots per record
+    int pack_cols;
 };
 
 // Wait until *flag >= need.  Executed by the whole wave on a wave-uniform address (the 64 identical loads are
@@ -1970,6 +1980,16 @@ __global__ __launch_bounds__(WAVE, 1) void simplyp_queue_kernel(const KernelArgs
             run_slot<INTEG, SNOW, TEAM, STIFF>(a, s_P, s_E, s_T, s_doy, lane, slot_of_lane(a, g, lane), q.task_reach + pair, 1, d_begin, d_end,
                                    q.ckpt + (size_t)s * CKPT_N * (size_t)a.E, s_tab);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (q.pack_buf) {                 // (wave-uniform) the rows just written, still in cache, as 7-byte deltas
+                const int nd = d_end - d_begin;
+                const simplyp_pack::Layout L = simplyp_pack::layout((size_t)a.E, nd, q.pack_cap);
+                for (int j = 0; j < q.pack_cols; ++j) {
+                    const size_t rec = (size_t)c * (size_t)q.pack_cols + (size_t)j;
+                    simplyp_pack::pack_block(a.out + ((size_t)j * (size_t)a.D + (size_t)d_begin) * (size_t)a.E, (size_t)a.E, nd, a.E, g, lane,
+                                             q.pack_buf + rec * q.pack_stride, L, q.pack_count + rec, q.pack_cap);
+                }
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (lane == 0) {
@@ -1983,8 +2003,15 @@ __global__ __launch_bounds__(WAVE, 1) void simplyp_queue_kernel(const KernelArgs
                 unsigned old = 0;
                 if (lane == 0) old = atomicAdd(&q.chunk_count[c], 1u);
                 old = (unsigned)__builtin_amdgcn_readfirstlane((int)old);
-                if (old + 1u == q.tasks_per_chunk && lane == 0)
+                if (old + 1u == q.tasks_per_chunk && lane == 0) {
+                    // (every task of the chunk added to its records' overflow counters before its release, as above)
+                    if (q.pack_buf)
+                        for (int j = 0; j < q.pack_cols; ++j) {
+                            const size_t rec = (size_t)c * (size_t)q.pack_cols + (size_t)j;
+                            q.host_pack_count[rec] = __hip_atomic_load(&q.pack_count[rec], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        }
                     __hip_atomic_store(&q.host_ready[c], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+                }
             }
             k = queue_take_ticket(q, lane);
         } else {
@@ -1996,6 +2023,22 @@ __global__ __launch_bounds__(WAVE, 1) void simplyp_queue_kernel(const KernelArgs
         atomicAdd(&a.counters[4], (unsigned long long)ws.waits);
         atomicMax(&a.counters[5], (unsigned long long)ws.longest_wait);
         atomicMax(&a.counters[6], (unsigned long long)ws.longest_stall);
+    }
+}
+
+// simplyp_fetch_packed: one wave per (time chunk, 64-member group) packs that block of every column of a caller's table
+// [n_cols][rows][row_doubles] with the device function the task-queue kernel uses.
+__global__ __launch_bounds__(WAVE) void simplyp_pack_table_kernel(const double* table, int n_cols, int rows, int row_doubles, int chunk_days,
+                                                                  unsigned char* pack_buf, unsigned* pack_count, unsigned long long pack_stride,
+                                                                  unsigned pack_cap)
+{
+    const int c = blockIdx.y, g = blockIdx.x, lane = threadIdx.x;
+    const int d_begin = c * chunk_days, nd = min(rows, d_begin + chunk_days) - d_begin;
+    const simplyp_pack::Layout L = simplyp_pack::layout((size_t)row_doubles, nd, pack_cap);
+    for (int j = 0; j < n_cols; ++j) {
+        const size_t rec = (size_t)c * (size_t)n_cols + (size_t)j;
+        simplyp_pack::pack_block(table + ((size_t)j * (size_t)rows + (size_t)d_begin) * (size_t)row_doubles, (size_t)row_doubles, nd, row_doubles, g,
+                                 lane, pack_buf + rec * pack_stride, L, pack_count + rec, pack_cap);
     }
 }
 

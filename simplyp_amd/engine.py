@@ -27,7 +27,8 @@ ABI_SYMBOLS = ['simplyp_abi_version', 'simplyp_device_count', 'simplyp_ctx_creat
                'simplyp_run_async', 'simplyp_sync', 'simplyp_plan', 'simplyp_host_alloc', 'simplyp_host_free',
                'simplyp_device_alloc', 'simplyp_device_free', 'simplyp_memcpy_h2d', 'simplyp_memcpy_d2h', 'simplyp_gof',
                'simplyp_stream_out', 'simplyp_waterbody', 'simplyp_gof_waterbody', 'simplyp_gof_spearman', 'simplyp_eval_units',
-               'simplyp_quantiles', 'simplyp_state_bytes', 'simplyp_set_state']
+               'simplyp_quantiles', 'simplyp_state_bytes', 'simplyp_set_state', 'simplyp_fetch_packed',
+               'simplyp_pack_roundtrip_host']
 
 _lib = None
 
@@ -40,7 +41,8 @@ def build(force=False, verbose=False):
     """Compile the HIP library for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, 'simplyp_hip.hip'), os.path.join(CSRC, 'simplyp_kernels.hip.h'),
             os.path.join(CSRC, 'simplyp_gof.hip.h'), os.path.join(CSRC, 'simplyp_waterbody.hip.h'),
-            os.path.join(CSRC, 'simplyp_quantile.hip.h'),
+            os.path.join(CSRC, 'simplyp_quantile.hip.h'), os.path.join(CSRC, 'simplyp_pack.h'),
+            os.path.join(CSRC, 'simplyp_pack_stream.h'),
             os.path.join(INCLUDE, 'simplyp.h'), os.path.join(INCLUDE, 'simplyp_controller.h')]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
@@ -105,6 +107,10 @@ def lib():
                                     C.POINTER(abi.QuantileInfo)]
     L.simplyp_stream_out.restype = C.c_int
     L.simplyp_stream_out.argtypes = [vp, vp, C.c_int64]
+    L.simplyp_fetch_packed.restype = C.c_int
+    L.simplyp_fetch_packed.argtypes = [vp, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int32)]
+    L.simplyp_pack_roundtrip_host.restype = C.c_int
+    L.simplyp_pack_roundtrip_host.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.POINTER(C.c_int32)]
     L.simplyp_state_bytes.restype = C.c_int64
     L.simplyp_state_bytes.argtypes = [C.POINTER(abi.Dims)]
     L.simplyp_set_state.restype = C.c_int
