@@ -28,7 +28,8 @@ extern "C" {
  * signature and no struct layout of version 17 changed, a caller built against the earlier header runs unchanged.
  * 17 still with the packed output stream, for the same reason: simplyp_fetch_packed and simplyp_pack_roundtrip_host are new
  * entry points, and simplyp_stats keeps its size and every offset -- reserved0 (always 0 before) is now packed_records, and
- * the upper half of queue_longest_wait_polls (a 32-bit count on the device: always 0 before) is now pack_overflow_blocks. */
+ * the upper half of queue_longest_wait_polls (a 32-bit count on the device: always 0 before) is now pack_overflow_blocks.
+ * 17 still with simplyp_fetch_packed_pred and simplyp_pack_roundtrip_host_pred: two more entry points, nothing else. */
 #define SIMPLYP_ABI_VERSION 17
 
 typedef enum {
@@ -237,14 +238,14 @@ typedef struct {
     uint64_t queue_waits;    /* task-queue kernel: dependency waits (own previous chunk, upstream reach, ring reader) that
                                 found their flag not yet raised and had to poll                                        */
     uint32_t queue_longest_wait_polls;  /* the longest of them, in polls (~2 us each)                                   */
-    uint32_t pack_overflow_blocks;      /* packed output stream: 64-member blocks that also travelled raw because a day-to-day
-                                delta in them needs more than 56 bits (records sent raw not counted)                  */
+    uint32_t pack_overflow_blocks;      /* packed output stream: 64-member blocks in which a coded difference needs more than
+                                56 bits (records sent raw not counted)                                                */
     uint64_t queue_longest_stall_polls; /* the longest stretch of polls, inside any such wait, during which NO task of the run
                                 completed: what the wait's bound counts (simplyp_sync)                                 */
     int32_t  stiff_pair;     /* 1 when the run used the stability-optimised second pair (opts.stiff_pair resolved to on)  */
     int32_t  packed_records; /* packed output stream (simplyp_stream_out with SIMPLYP_STREAM_PACK): low 16 bits = (time chunk,
-                                column) records delivered as 7-byte deltas and decoded on the host, high 16 bits = records of
-                                such a run sent as raw fp64 because their overflow area was full.  0: the stream was not packed */
+                                column) records delivered packed and decoded on the host, high 16 bits = records of
+                                such a run sent as raw fp64 because they had too many wide blocks.  0: the stream was not packed */
 } simplyp_stats;
 
 typedef struct simplyp_ctx simplyp_ctx;
@@ -353,29 +354,43 @@ int simplyp_stream_out(simplyp_ctx* ctx, double* host_out, int64_t host_bytes);
 
 /*
  * The packed output stream.  The daily table is smooth from day to day: per (column, member), the zigzag-coded difference of
- * consecutive days' 64-bit patterns fits 56 bits for all but a few values per million.  An eligible streamed run -- time
- * chunks through the task queue, daily rows (n_periods = 0), one reach, one lane per member, 64 member slots per wave,
- * lane slots contiguous in the table (opts.out_slot_order = 1, or no load balancing) -- can therefore send each (time chunk,
- * column) as one packed record of 7 bytes per value: the wave that computed a task packs its own rows before it releases the
- * task, the copier sends the record into a pinned staging ring, and a pool of host threads decodes it into `host_out` with
- * non-temporal stores.  A 64-member block with a delta that does not fit travels raw beside the record, exactly; a record with
- * more such blocks than its overflow area holds travels as today.  The result is bit for bit the table of the raw stream; the
- * device table is untouched.  simplyp_sync returns after the pool has drained, on every path.
+ * consecutive days' 64-bit patterns needs about 50 bits, and all 64 members of a block need few bits on the same days.  An
+ * eligible streamed run -- time chunks through the task queue, daily rows (n_periods = 0), one reach, one lane per member, 64
+ * member slots per wave, lane slots contiguous in the table (opts.out_slot_order = 1, or no load balancing) -- can therefore
+ * send each (time chunk, column) as one packed record in which every row of a block (64 members, one day) is stored at the bit
+ * width of its widest difference: the wave that computed a task packs its own rows before it releases the task, the copier
+ * sends the record into a pinned staging ring, and a pool of host threads decodes it into `host_out` with non-temporal stores.
+ * SIMPLYP_OUT_PP_FLUX is coded against Msus[d] * (PP[d-1] / Msus[d-1]) instead of the previous day when SIMPLYP_OUT_MSUS_FLUX
+ * is in the table too.  A block with a difference of more than 56 bits counts as an overflow block (it simply has wide rows); a
+ * record with more of them than an eighth of its blocks plus three, or whose body outgrows 7 bytes per value, travels as raw
+ * fp64.  The result is bit for bit the table of the raw stream; the device table is untouched.  simplyp_sync returns after the
+ * pool has drained, on every path.
  * Environment: SIMPLYP_STREAM_PACK = 0 never, 1 whenever eligible, unset = auto (only when the raw copies
  * would outlast the kernel); SIMPLYP_DECODE_THREADS = size of the decode pool (default: the CPUs this process may run on,
  * capped by OMP_NUM_THREADS, minus two).
  *
  * simplyp_fetch_packed -- a caller's device table [n_cols][rows][row_doubles] to host memory through the same pack device
- * function, copier and decoder (blocks of 64 consecutive doubles of a row; chunk_days is rounded up to a multiple of 64).
+ * function, copier and decoder (blocks of 64 consecutive doubles of a row; chunk_days is rounded up to a multiple of 64; at
+ * most 32 columns).
  * counts (host, may be NULL): [0] records decoded, [1] overflow blocks among them, [2] records sent raw.  Synchronous.
  *
  * simplyp_pack_roundtrip_host -- host only, no device: encodes `table` in plain C++ into records of the same layout and decodes
  * them with the decoder of the stream into `out` (raw records are copied); counts as above.
+ *
+ * simplyp_fetch_packed_pred, simplyp_pack_roundtrip_host_pred -- the same two with a predictor per column and the bytes:
+ * pred_col (host, [n_cols], NULL = all -1): -1 = a column is coded against its previous day, k < the column's own index = against
+ * X[d] * (Y[d-1] / X[d-1]) with X = column k.  bytes (host, may be NULL): [0] bytes of all packed records as they cross the link,
+ * [1] bytes of their raw first rows.
  */
 int simplyp_fetch_packed(simplyp_ctx* ctx, const double* dev_table, int32_t n_cols, int32_t rows, int32_t row_doubles,
                          int32_t chunk_days, double* host_out, int64_t host_bytes, int32_t* counts);
 int simplyp_pack_roundtrip_host(const double* table, int32_t n_cols, int32_t rows, int32_t row_doubles, int32_t chunk_days,
                                 double* out, int32_t* counts);
+int simplyp_fetch_packed_pred(simplyp_ctx* ctx, const double* dev_table, int32_t n_cols, int32_t rows, int32_t row_doubles,
+                              int32_t chunk_days, const int32_t* pred_col, double* host_out, int64_t host_bytes, int32_t* counts,
+                              int64_t* bytes);
+int simplyp_pack_roundtrip_host_pred(const double* table, int32_t n_cols, int32_t rows, int32_t row_doubles, int32_t chunk_days,
+                                     const int32_t* pred_col, double* out, int32_t* counts, int64_t* bytes);
 
 /*
  * simplyp_set_state -- warm start: begin the NEXT run from a saved model state and / or save the state it ends in

@@ -74,9 +74,12 @@ struct simplyp_ctx {
         unsigned pack_cap = 0;
         int n_packed = 0, n_raw = 0;    // records the copier sent packed / raw
         unsigned n_overflow = 0;        // overflow blocks of the packed ones
+        int pack_pred[32];              // per column: the column it is predicted from, or -1 (simplyp_pack.h)
+        size_t packed_bytes = 0;        // what the packed records put on the link
+        int raw_of_col[32];             // records sent raw, per column (SIMPLYP_DEBUG)
     } copy_plan;
     DeviceBuf packed;                   // the packed records of a run (grow-only; given back by the first run that does not pack)
-    DeviceBuf pack_count;               // [n_records] uint32 overflow counters
+    DeviceBuf pack_count;               // [n_records][2] uint32: overflow blocks, body words (then simplyp_fetch_packed's pred_col)
     uint32_t* host_pack_count = nullptr;    // the same in pinned host memory, written by the wave that completes a chunk
     size_t host_pack_count_cap = 0;
     simplyp_pack::PackStream pack;      // staging ring, dispatcher and decode pool
@@ -386,27 +389,35 @@ void copier_main(simplyp_ctx* ctx)
         const size_t d0 = (size_t)c0 * p.chunk_days, nd = std::min<size_t>((size_t)(c1 - c0) * p.chunk_days, p.D - d0);
         // (one plain copy per column: a pitched hipMemcpy2DAsync per chunk does not overlap the persistent kernel at all on this
         // stack -- 1509 ms per pass instead of 803, profiles/r02_experiments.md)
+        bool raw_col[32] = {};
         for (int j = 0; j < p.ncols; ++j) {
             const size_t off = ((size_t)j * p.D + d0) * p.row_doubles;
             if (chunk_packed) {
                 // the record instead of the rows: into the staging ring, and from there through the decode pool into p.host
                 const size_t rec = (size_t)c0 * p.ncols + j;
-                const unsigned count = ctx->host_pack_count[rec];
-                if (count <= p.pack_cap) {
+                const unsigned count = ctx->host_pack_count[2 * rec], words = ctx->host_pack_count[2 * rec + 1];
+                const simplyp_pack::Layout L = simplyp_pack::layout(p.row_doubles, (int)nd, p.pack_cap);
+                // a column predicted from one that travels raw goes raw too: its decoder reads that column's rows from the host
+                // table, where a raw copy lands in no order with the pool
+                const int k = p.pack_pred[j];
+                raw_col[j] = simplyp_pack::travels_raw(L, count, words, p.pack_cap) || (k >= 0 && raw_col[k]);
+                if (!raw_col[j]) {
                     simplyp_pack::PackJob job;
                     job.dev_rec = p.pack_dev + rec * p.pack_stride;
                     job.nd = (int)nd;
-                    job.L = simplyp_pack::layout(p.row_doubles, (int)nd, p.pack_cap);
-                    job.count = count;
+                    job.L = L;
+                    job.copy_bytes = simplyp_pack::copy_bytes(L, words);
                     job.dst = p.host + off;
+                    job.xdst = k >= 0 ? p.host + ((size_t)k * p.D + d0) * p.row_doubles : nullptr;
                     job.stride = p.row_doubles;
                     hipError_t err = ctx->pack.submit(job, ctx->copy_streams[n_issued++ % (unsigned)ctx->n_copy_streams]);
                     if (err != hipSuccess && !ctx->copy_error) ctx->copy_error = (int)err;
                     ++ctx->copy_plan.n_packed;
                     ctx->copy_plan.n_overflow += count;
+                    ctx->copy_plan.packed_bytes += job.copy_bytes;
                     continue;
                 }
-                ++ctx->copy_plan.n_raw;       // overflow area full: this chunk-column travels as fp64, as below
+                ++ctx->copy_plan.n_raw; ++ctx->copy_plan.raw_of_col[j];       // too many wide blocks: this chunk-column travels as fp64, as below
             }
             // two streams, taken in turn: the launch gap of one copy dispatch hides behind the other stream's transfer
             hipError_t err = hipMemcpyAsync(p.host + off, p.dev + off, nd * p.row_doubles * sizeof(double),
@@ -731,12 +742,16 @@ bool pack_eligible(const simplyp_opts& opts, const RunShape& shape, const simply
 }
 
 // SIMPLYP_STREAM_PACK unset: pack only when the raw copies would clearly outlast the kernel.  Per day of
-// the run, the raw table needs n_cols x E x 8 bytes at PACK_LINK_GBS on the link; the kernel needs PACK_KERNEL_NS_PER_MEMBER_DAY
-// per member (the flagship: 533.6 ms for 100 000 members x 10 957 days) but never less than one round of waves
-// (PACK_KERNEL_US_PER_DAY_MIN: 480 ms for the 50 000-member shard that fills 782 of the 1024 wave slots).  Packing saves an
-// eighth of the copy at best, so a run whose copy is not 15 % longer than its kernel gains nothing.
-constexpr double PACK_LINK_GBS = 56.7, PACK_KERNEL_NS_PER_MEMBER_DAY = 0.487, PACK_KERNEL_US_PER_DAY_MIN = 43.8;
-constexpr bool PACK_AUTO_ON = true;       // the gate's verdict (profiles/r06_pack/gate.md)
+// the run, the raw table needs n_cols x E x 8 bytes at PACK_LINK_GBS on the link; the PACKING kernel needs
+// PACK_KERNEL_NS_PER_MEMBER_DAY per member (the flagship with the row-adaptive epilogue: 579 ms for 100 000 members x 10 957
+// days, profiles/r07_pack; 533.6 ms without any epilogue) but never less than one round of waves (PACK_KERNEL_US_PER_DAY_MIN:
+// 480 ms measured for the 50 000-member shard that fills 782 of the 1024 wave slots, scaled by the same 579 / 533.6 -- that
+// product is derived, not measured).  The packed rows cost 6.13 of 8 bytes per value on the model's table, so the packed copy
+// takes 0.77 of the raw one: a run whose raw copy is 10 % longer than its packing kernel ends with the kernel (0.85 < 1) and
+// gains those 10 %; one whose raw copy is no longer than the packing kernel gains nothing.
+constexpr double PACK_LINK_GBS = 56.7, PACK_KERNEL_NS_PER_MEMBER_DAY = 0.528, PACK_KERNEL_US_PER_DAY_MIN = 47.5;
+constexpr double PACK_COPY_OVER_KERNEL = 1.10;
+constexpr bool PACK_AUTO_ON = true;       // the verdict of the full-size runs (profiles/r07_pack/README.md; r06_pack/gate.md before)
 
 bool pack_wanted(const simplyp_opts& opts, const RunShape& shape, const simplyp::KernelArgs& a)
 {
@@ -747,13 +762,15 @@ bool pack_wanted(const simplyp_opts& opts, const RunShape& shape, const simplyp:
     }
     const double copy_us = (double)popcount32(a.out_mask) * a.E * 8.0 / (PACK_LINK_GBS * 1e3);
     const double kernel_us = std::max(PACK_KERNEL_US_PER_DAY_MIN, PACK_KERNEL_NS_PER_MEMBER_DAY * 1e-3 * a.E);
-    return PACK_AUTO_ON && copy_us > 1.15 * kernel_us;
+    return PACK_AUTO_ON && copy_us > PACK_COPY_OVER_KERNEL * kernel_us;
 }
 
-// Buffers of a packed run: the device records, their overflow counters on the device and in pinned host memory (zeroed).
+// Buffers of a packed run: the device records, sized for their capacity, and their two counters each on the device and in
+// pinned host memory (zeroed); `extra_words` more device words follow the counters.
 // `stride` = 0 when the records do not fit the device's free memory: the run then streams raw.
-int ensure_pack_buffers(simplyp_ctx* ctx, size_t row_doubles, int chunk_days, int n_records, size_t& stride, unsigned& cap)
+int ensure_pack_buffers(simplyp_ctx* ctx, size_t row_doubles, int chunk_days, int n_records, size_t& stride, unsigned& cap, int extra_words = 0)
 {
+    const size_t n_words = 2 * (size_t)n_records;
     cap = simplyp_pack::overflow_capacity((int)((row_doubles + simplyp_pack::GROUP - 1) / simplyp_pack::GROUP));
     stride = simplyp_pack::layout(row_doubles, chunk_days, cap).bytes;
     const size_t bytes = (size_t)n_records * stride;
@@ -761,14 +778,14 @@ int ensure_pack_buffers(simplyp_ctx* ctx, size_t row_doubles, int chunk_days, in
     (void)hipMemGetInfo(&free_b, &total_b);
     if (bytes > ctx->packed.bytes && bytes - ctx->packed.bytes > free_b / 10 * 9) { stride = 0; return SIMPLYP_OK; }
     if (int rc = ensure(ctx, ctx->packed, bytes)) return rc;
-    if (int rc = ensure(ctx, ctx->pack_count, (size_t)n_records * sizeof(unsigned))) return rc;
-    if ((size_t)n_records > ctx->host_pack_count_cap) {
+    if (int rc = ensure(ctx, ctx->pack_count, (n_words + (size_t)extra_words) * sizeof(unsigned))) return rc;
+    if (n_words > ctx->host_pack_count_cap) {
         if (ctx->host_pack_count) { (void)hipHostFree(ctx->host_pack_count); ctx->host_pack_count = nullptr; ctx->host_pack_count_cap = 0; }
-        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->host_pack_count, (size_t)n_records * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));
-        ctx->host_pack_count_cap = (size_t)n_records;
+        HIP_TRY(ctx, hipHostMalloc((void**)&ctx->host_pack_count, n_words * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));
+        ctx->host_pack_count_cap = n_words;
     }
-    memset(ctx->host_pack_count, 0, (size_t)n_records * sizeof(uint32_t));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->pack_count.ptr, 0, (size_t)n_records * sizeof(unsigned), ctx->stream));
+    memset(ctx->host_pack_count, 0, n_words * sizeof(uint32_t));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->pack_count.ptr, 0, n_words * sizeof(unsigned), ctx->stream));
     return SIMPLYP_OK;
 }
 
@@ -814,6 +831,7 @@ int launch_queue(simplyp_ctx* ctx, const simplyp_opts& opts, const RunShape& sha
     q.n_groups = G; q.n_pairs = (int)pair_idx.size(); q.chunk_days = chunk_days; q.ring_chunks = topo.ring_chunks;
     q.chunk_count = nullptr; q.host_ready = nullptr; q.tasks_per_chunk = (unsigned)S * (unsigned)G;
     q.pack_buf = nullptr; q.pack_count = nullptr; q.host_pack_count = nullptr; q.pack_stride = 0; q.pack_cap = 0; q.pack_cols = 0;
+    q.pack_pred_y = q.pack_pred_x = -1;
     if (shape.stream_chunks) {
         if (int rc = ensure(ctx, ctx->chunk_count, (size_t)n_chunks * sizeof(unsigned))) return rc;
         if ((size_t)n_chunks > ctx->host_ready_cap) {
@@ -839,6 +857,16 @@ int launch_queue(simplyp_ctx* ctx, const simplyp_opts& opts, const RunShape& sha
                 q.pack_buf = (unsigned char*)ctx->packed.ptr; q.pack_count = (unsigned*)ctx->pack_count.ptr;
                 q.host_pack_count = ctx->host_pack_count; q.pack_stride = stride; q.pack_cap = cap; q.pack_cols = ncols;
                 ctx->copy_plan.pack_dev = q.pack_buf; ctx->copy_plan.pack_stride = stride; ctx->copy_plan.pack_cap = cap;
+                // PP is almost a constant multiple of Msus: predicted from it when both are in the table.
+                // Columns are in ascending SIMPLYP_OUT_* order, so a column's place is the number of mask bits below its own.
+                for (int& k : ctx->copy_plan.pack_pred) k = -1;
+                for (int& k : ctx->copy_plan.raw_of_col) k = 0;
+                const uint32_t bx = 1u << SIMPLYP_OUT_MSUS_FLUX, by = 1u << SIMPLYP_OUT_PP_FLUX;
+                if ((a.out_mask & bx) && (a.out_mask & by)) {
+                    q.pack_pred_x = popcount32(a.out_mask & (bx - 1u));
+                    q.pack_pred_y = popcount32(a.out_mask & (by - 1u));
+                    ctx->copy_plan.pack_pred[q.pack_pred_y] = q.pack_pred_x;
+                }
             }
         }
     }
@@ -1076,7 +1104,7 @@ static int run_async_body(simplyp_ctx* ctx, const simplyp_dims* dims, const simp
     ctx->t_begin = std::chrono::steady_clock::now();
     ctx->copy_pending = false; ctx->copy_error = 0; ctx->streamed_chunks = 0;
     ctx->copy_plan.n_chunks = 0; ctx->copy_plan.pack_dev = nullptr;
-    ctx->copy_plan.n_packed = ctx->copy_plan.n_raw = 0; ctx->copy_plan.n_overflow = 0;
+    ctx->copy_plan.n_packed = ctx->copy_plan.n_raw = 0; ctx->copy_plan.n_overflow = 0; ctx->copy_plan.packed_bytes = 0;
     const int E = dims->E, S = dims->S, D = dims->D;
     Schedule sch;
     int rc = build_schedule(ctx, S, up_ptr, up_idx, sch);
@@ -1217,6 +1245,11 @@ static int sync_impl(simplyp_ctx* ctx, simplyp_stats* stats)
             return fail(ctx, SIMPLYP_ERR_DEVICE, "task-queue kernel: a wave waited for a time chunk while no task of the run completed for "
                         "%llu polls (bound: SIMPLYP_QUEUE_MAX_POLLS); results are incomplete", c[6]);
     }
+    if (copied && ctx->copy_plan.pack_dev && getenv("SIMPLYP_DEBUG"))
+        fprintf(stderr, "[simplyp] packed stream: %d records packed (%zu bytes on the link), %d raw\n", ctx->copy_plan.n_packed,
+                ctx->copy_plan.packed_bytes, ctx->copy_plan.n_raw);
+    if (copied && ctx->copy_plan.pack_dev && ctx->copy_plan.n_raw && getenv("SIMPLYP_DEBUG"))
+        for (int j = 0; j < ctx->copy_plan.ncols; ++j) fprintf(stderr, "[simplyp] packed stream: column %d: %d raw\n", j, ctx->copy_plan.raw_of_col[j]);
     if (stats) {
         float ms = 0.f, ms_pilot = 0.f;
         HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_main, ctx->ev_stop));
@@ -1273,13 +1306,25 @@ int simplyp_stream_out(simplyp_ctx* ctx, double* host_out, int64_t host_bytes)
 
 // simplyp_fetch_packed: the table is packed by one wave per (chunk, 64-double group), then every record takes the copier's and
 // the decode pool's path of a packed run (raw records are copied from the table, as there).
+// pred_col (may be NULL = all -1): per column -1 or an EARLIER column it is predicted from -- records travel in column order,
+// and a decode thread needs its rows of that column in the host table first.
+static bool pred_cols_ok(const int32_t* pred_col, int32_t n_cols)
+{
+    for (int j = 0; pred_col && j < n_cols; ++j)
+        if (pred_col[j] < -1 || pred_col[j] >= j) return false;
+    return n_cols <= 32;
+}
+
 static int fetch_packed_impl(simplyp_ctx* ctx, const double* dev_table, int32_t n_cols, int32_t rows, int32_t row_doubles,
-                             int32_t chunk_days, double* host_out, int64_t host_bytes, int32_t* counts)
+                             int32_t chunk_days, const int32_t* pred_col, double* host_out, int64_t host_bytes, int32_t* counts,
+                             int64_t* bytes)
 {
     if (!ctx) return SIMPLYP_ERR_ARG;
     if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "a run is pending on this context; call simplyp_sync first");
     if (!dev_table || !host_out || n_cols <= 0 || rows <= 0 || row_doubles <= 0 || chunk_days <= 0)
         return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_fetch_packed: bad table arguments");
+    if (!pred_cols_ok(pred_col, n_cols))
+        return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_fetch_packed: at most 32 columns, and pred_col[j] must be -1 or a column before j");
     const size_t table_bytes = (size_t)n_cols * rows * row_doubles * sizeof(double);
     if (host_bytes < (int64_t)table_bytes)
         return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_fetch_packed: host buffer of %lld bytes is smaller than the table (%zu)", (long long)host_bytes, table_bytes);
@@ -1289,33 +1334,43 @@ static int fetch_packed_impl(simplyp_ctx* ctx, const double* dev_table, int32_t 
     if (n_chunks > 65535) return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_fetch_packed: more than 65535 chunks");
     size_t stride = 0;
     unsigned cap = 0;
-    if (int rc = ensure_pack_buffers(ctx, (size_t)row_doubles, chunk, n_rec, stride, cap)) return rc;
+    if (int rc = ensure_pack_buffers(ctx, (size_t)row_doubles, chunk, n_rec, stride, cap, n_cols)) return rc;
     if (!stride) return fail(ctx, SIMPLYP_ERR_NOMEM, "simplyp_fetch_packed: the packed records do not fit the device's free memory");
+    int pred[32];
+    for (int j = 0; j < n_cols; ++j) pred[j] = pred_col ? pred_col[j] : -1;
+    int* dev_pred = (int*)ctx->pack_count.ptr + 2 * (size_t)n_rec;
+    HIP_TRY(ctx, hipMemcpyAsync(dev_pred, pred, (size_t)n_cols * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(simplyp::simplyp_pack_table_kernel, dim3((unsigned)G, (unsigned)n_chunks), dim3(simplyp::WAVE), 0, ctx->stream, dev_table,
                        n_cols, rows, row_doubles, chunk, (unsigned char*)ctx->packed.ptr, (unsigned*)ctx->pack_count.ptr,
-                       (unsigned long long)stride, cap);
+                       (unsigned long long)stride, cap, (const int*)dev_pred);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->host_pack_count, ctx->pack_count.ptr, (size_t)n_rec * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->host_pack_count, ctx->pack_count.ptr, 2 * (size_t)n_rec * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     hipError_t err = ctx->pack.start(ctx->device, (size_t)row_doubles, stride, n_rec, simplyp_pack::decode_threads());
     int n_packed = 0, n_raw = 0;
     unsigned n_overflow = 0, n_issued = 0;
+    int64_t link_bytes = 0;
     for (int c = 0; c < n_chunks && err == hipSuccess; ++c) {
         const size_t d0 = (size_t)c * chunk, nd = std::min<size_t>((size_t)chunk, (size_t)rows - d0);
+        const simplyp_pack::Layout L = simplyp_pack::layout((size_t)row_doubles, (int)nd, cap);
+        bool raw_col[32] = {};
         for (int j = 0; j < n_cols && err == hipSuccess; ++j) {
             const size_t rec = (size_t)c * n_cols + j, off = ((size_t)j * rows + d0) * row_doubles;
-            const unsigned count = ctx->host_pack_count[rec];
+            const unsigned count = ctx->host_pack_count[2 * rec], words = ctx->host_pack_count[2 * rec + 1];
             hipStream_t st = ctx->copy_streams[n_issued++ % (unsigned)ctx->n_copy_streams];
-            if (count <= cap) {
+            raw_col[j] = simplyp_pack::travels_raw(L, count, words, cap) || (pred[j] >= 0 && raw_col[pred[j]]);     // (as the copier)
+            if (!raw_col[j]) {
                 simplyp_pack::PackJob job;
                 job.dev_rec = (const unsigned char*)ctx->packed.ptr + rec * stride;
                 job.nd = (int)nd;
-                job.L = simplyp_pack::layout((size_t)row_doubles, (int)nd, cap);
-                job.count = count;
+                job.L = L;
+                job.copy_bytes = simplyp_pack::copy_bytes(L, words);
                 job.dst = host_out + off;
+                job.xdst = pred[j] >= 0 ? host_out + ((size_t)pred[j] * rows + d0) * row_doubles : nullptr;
                 job.stride = (size_t)row_doubles;
                 err = ctx->pack.submit(job, st);
                 ++n_packed; n_overflow += count;
+                link_bytes += (int64_t)job.copy_bytes;
             } else {
                 err = hipMemcpyAsync(host_out + off, dev_table + off, nd * row_doubles * sizeof(double), hipMemcpyDeviceToHost, st);
                 ++n_raw;
@@ -1330,53 +1385,78 @@ static int fetch_packed_impl(simplyp_ctx* ctx, const double* dev_table, int32_t 
     if (err == hipSuccess && ctx->pack.error()) err = (hipError_t)ctx->pack.error();
     if (err != hipSuccess) return fail(ctx, SIMPLYP_ERR_DEVICE, "simplyp_fetch_packed: %s", hipGetErrorString(err));
     if (counts) { counts[0] = n_packed; counts[1] = (int32_t)n_overflow; counts[2] = n_raw; }
+    if (bytes) { bytes[0] = link_bytes; bytes[1] = (int64_t)n_packed * row_doubles * (int64_t)sizeof(double); }
     return SIMPLYP_OK;
 }
 
 int simplyp_fetch_packed(simplyp_ctx* ctx, const double* dev_table, int32_t n_cols, int32_t rows, int32_t row_doubles,
                          int32_t chunk_days, double* host_out, int64_t host_bytes, int32_t* counts)
 {
-    SIMPLYP_GUARD(ctx, fetch_packed_impl(ctx, dev_table, n_cols, rows, row_doubles, chunk_days, host_out, host_bytes, counts))
+    SIMPLYP_GUARD(ctx, fetch_packed_impl(ctx, dev_table, n_cols, rows, row_doubles, chunk_days, nullptr, host_out, host_bytes, counts, nullptr))
+}
+
+int simplyp_fetch_packed_pred(simplyp_ctx* ctx, const double* dev_table, int32_t n_cols, int32_t rows, int32_t row_doubles,
+                              int32_t chunk_days, const int32_t* pred_col, double* host_out, int64_t host_bytes, int32_t* counts,
+                              int64_t* bytes)
+{
+    SIMPLYP_GUARD(ctx, fetch_packed_impl(ctx, dev_table, n_cols, rows, row_doubles, chunk_days, pred_col, host_out, host_bytes, counts, bytes))
 }
 
 static int pack_roundtrip_host_impl(const double* table, int32_t n_cols, int32_t rows, int32_t row_doubles, int32_t chunk_days,
-                                    double* out, int32_t* counts)
+                                    const int32_t* pred_col, double* out, int32_t* counts, int64_t* bytes)
 {
     if (!table || !out || n_cols <= 0 || rows <= 0 || row_doubles <= 0 || chunk_days <= 0)
         return fail(nullptr, SIMPLYP_ERR_ARG, "simplyp_pack_roundtrip_host: bad table arguments");
+    if (!pred_cols_ok(pred_col, n_cols))
+        return fail(nullptr, SIMPLYP_ERR_ARG, "simplyp_pack_roundtrip_host: at most 32 columns, and pred_col[j] must be -1 or a column before j");
     const size_t E = (size_t)row_doubles;
     const int chunk = (chunk_days + 63) / 64 * 64, n_chunks = (rows + chunk - 1) / chunk;
     const unsigned cap = simplyp_pack::overflow_capacity((int)((E + simplyp_pack::GROUP - 1) / simplyp_pack::GROUP));
     std::vector<unsigned char> rec(simplyp_pack::layout(E, chunk, cap).bytes);
-    std::vector<uint64_t> run(E);
     int n_packed = 0, n_raw = 0;
     unsigned n_overflow = 0;
-    constexpr int RANGES = 3;       // the decoder works on member ranges, as the pool's threads do
+    int64_t link_bytes = 0;
+    constexpr size_t RANGES = 3;    // the decoder works on member ranges of whole blocks, as the pool's threads do
+    const size_t G = (E + simplyp_pack::GROUP - 1) / simplyp_pack::GROUP;
+    simplyp_pack::FpDefault fp;     // (the decode threads hold one each)
+    (void)fp;
     for (int c = 0; c < n_chunks; ++c) {
         const size_t d0 = (size_t)c * chunk;
         const int nd = (int)std::min<size_t>((size_t)chunk, (size_t)rows - d0);
         const simplyp_pack::Layout L = simplyp_pack::layout(E, nd, cap);
+        bool raw_col[32] = {};
         for (int j = 0; j < n_cols; ++j) {
             const size_t off = ((size_t)j * rows + d0) * E;
-            const unsigned count = simplyp_pack::encode_record_host(table + off, E, nd, E, rec.data(), L, cap);
-            if (count > cap) { memcpy(out + off, table + off, (size_t)nd * E * sizeof(double)); ++n_raw; continue; }
-            for (int t = 0; t < RANGES; ++t) {
-                const size_t e0 = t == 0 ? 0 : (E * t / RANGES) / 8 * 8, e1 = t + 1 == RANGES ? E : (E * (t + 1) / RANGES) / 8 * 8;
-                if (e1 > e0) simplyp_pack::decode_range(rec.data(), L, nd, E, e0, e1, out + off, E, run.data());
+            const int k = pred_col ? pred_col[j] : -1;
+            const size_t xoff = k >= 0 ? ((size_t)k * rows + d0) * E : 0;
+            uint64_t cnt[2];
+            simplyp_pack::encode_record_host(table + off, k >= 0 ? table + xoff : nullptr, E, nd, E, rec.data(), L, cnt);
+            raw_col[j] = simplyp_pack::travels_raw(L, (unsigned)cnt[0], (size_t)cnt[1], cap) || (k >= 0 && raw_col[k]);
+            if (raw_col[j]) { memcpy(out + off, table + off, (size_t)nd * E * sizeof(double)); ++n_raw; continue; }
+            for (size_t t = 0; t < RANGES; ++t) {
+                const size_t e0 = G * t / RANGES * simplyp_pack::GROUP, e1 = std::min(E, G * (t + 1) / RANGES * simplyp_pack::GROUP);
+                if (e1 > e0) simplyp_pack::decode_range(rec.data(), L, nd, E, e0, e1, out + off, k >= 0 ? out + xoff : nullptr, E);
             }
             __builtin_ia32_sfence();
-            simplyp_pack::apply_overflow(rec.data(), L, nd, E, count, out + off, E);
-            ++n_packed; n_overflow += count;
+            ++n_packed; n_overflow += (unsigned)cnt[0];
+            link_bytes += (int64_t)simplyp_pack::copy_bytes(L, (size_t)cnt[1]);
         }
     }
     if (counts) { counts[0] = n_packed; counts[1] = (int32_t)n_overflow; counts[2] = n_raw; }
+    if (bytes) { bytes[0] = link_bytes; bytes[1] = (int64_t)n_packed * (int64_t)E * (int64_t)sizeof(double); }
     return SIMPLYP_OK;
 }
 
 int simplyp_pack_roundtrip_host(const double* table, int32_t n_cols, int32_t rows, int32_t row_doubles, int32_t chunk_days,
                                 double* out, int32_t* counts)
 {
-    SIMPLYP_GUARD(nullptr, pack_roundtrip_host_impl(table, n_cols, rows, row_doubles, chunk_days, out, counts))
+    SIMPLYP_GUARD(nullptr, pack_roundtrip_host_impl(table, n_cols, rows, row_doubles, chunk_days, nullptr, out, counts, nullptr))
+}
+
+int simplyp_pack_roundtrip_host_pred(const double* table, int32_t n_cols, int32_t rows, int32_t row_doubles, int32_t chunk_days,
+                                     const int32_t* pred_col, double* out, int32_t* counts, int64_t* bytes)
+{
+    SIMPLYP_GUARD(nullptr, pack_roundtrip_host_impl(table, n_cols, rows, row_doubles, chunk_days, pred_col, out, counts, bytes))
 }
 
 int64_t simplyp_state_bytes(const simplyp_dims* dims)

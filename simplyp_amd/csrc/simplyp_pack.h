@@ -1,21 +1,25 @@
 // simplyp_pack.h -- the lossless codec of the packed output stream: one definition, compiled for the device (the pack
 // epilogue of the task-queue kernel, simplyp_fetch_packed) and for the host (the decode pool, the plain C++ encoder of the
-// CPU test).  No floating-point operation anywhere: values travel as their 64-bit patterns.
+// CPU test).  Values travel as their 64-bit patterns.
 //
-// Per (column, member): z = zigzag(u[d] - u[d-1]) modulo 2^64 on the raw patterns of consecutive days.  On the model's daily
-// table z needs 49-51 bits at the median and fits 56 bits for all but ~6 values per million, so a
-// value travels as 7 bytes.  A 64-member block that holds any z >= 2^56 travels raw as well, exactly.
+// Per (column, member): z = zigzag(u[d] - p[d]) modulo 2^64, where u[d] is the day's pattern and p[d] its prediction:
+//   pred_col = -1   p[d] = u[d-1], the previous day of the same column;
+//   pred_col =  k   p[d] = pattern of X[d] * (Y[d-1] / X[d-1]) in fp64, X = column k of the same chunk, Y = this column --
+//                   one division and one multiplication, each correctly rounded on both sides of the link (predict());
+//                   where that pattern is +-0 or has an all-ones exponent, p[d] = u[d-1] instead.
+// All members see the same weather, so the 64 members of a block have small z on the same days and large z on the same days:
+// every row of a block (64 members, one day) is stored at the bit width of its widest z.
 //
 // One record per (time chunk, column), contiguous so that it is one plain copy:
-//   header   [cap] uint32   member groups whose blocks sit in the overflow area, in slot order (padded to 256 bytes)
-//   row 0    [E] fp64       the chunk's first day, raw: chunks decode independently of each other
-//   planes for rows 1 .. nd-1, member axis fastest (a wave's store is one 256-, 128- or 64-byte segment):
-//            [nd-1][E] uint32   bits  0..31 of z
-//            [nd-1][E] uint16   bits 32..47
-//            [nd-1][E] uint8    bits 48..55
-//   overflow [cap][nd][64] fp64 raw blocks; only the slots in use travel, in the same copy
-// The record's overflow counter lives outside it (one array per run, zeroed with one memset); a counter above `cap` marks the
-// record raw: the copier then sends that chunk-column from the fp64 table.
+//   row 0      [E] fp64          the chunk's first day, raw: chunks decode independently of each other
+//   directory  [G] entries       per 64-member block: [n_spans] uint32 -- where each span of 64 delta rows starts in the body,
+//                                in 8-byte words -- then one width byte (0 .. 64) per delta row (entry padded to 4 bytes)
+//   body                         per span its rows one after the other; a row of width w is the 64 z at w bits each, value i at
+//                                bit i * w: 8 * w bytes.  Spans take their place with one atomic add on the record's word
+//                                cursor, so their order is whatever the run made it.  8 bytes of padding follow the last row.
+// Two counters per record live outside it (one array per run, zeroed with one memset): [0] blocks that hold any z >= 2^56
+// ("overflow blocks"), [1] the word cursor.  A record with more than overflow_capacity() overflow blocks, or whose body passes
+// its fixed capacity, travels raw: the copier then sends that chunk-column from the fp64 table.
 #pragma once
 
 #include <stddef.h>
@@ -34,22 +38,35 @@
 namespace simplyp_pack {
 
 constexpr int GROUP = 64;        // members per block = lanes of a wavefront
-constexpr int Z_BITS = 56;       // what the three planes hold
+constexpr int SPAN = 64;         // delta rows whose widths one wavefront holds, one per lane
+constexpr int Z_BITS = 56;       // a block with a wider z counts as an overflow block; the host's fast path ends here too
 
 SIMPLYP_PACK_HD inline uint64_t zigzag(uint64_t delta) { return (delta << 1) ^ (uint64_t)((int64_t)delta >> 63); }
 SIMPLYP_PACK_HD inline uint64_t unzigzag(uint64_t z) { return (z >> 1) ^ (0ull - (z & 1ull)); }
-SIMPLYP_PACK_HD inline uint64_t encode(uint64_t u, uint64_t prev) { return zigzag(u - prev); }
-SIMPLYP_PACK_HD inline uint64_t decode(uint64_t z, uint64_t prev) { return prev + unzigzag(z); }
+SIMPLYP_PACK_HD inline uint64_t encode(uint64_t u, uint64_t pred) { return zigzag(u - pred); }
+SIMPLYP_PACK_HD inline uint64_t decode(uint64_t z, uint64_t pred) { return pred + unzigzag(z); }
 SIMPLYP_PACK_HD inline bool fits(uint64_t z) { return (z >> Z_BITS) == 0ull; }
+SIMPLYP_PACK_HD inline int width_of(uint64_t z) { return z ? 64 - __builtin_clzll(z) : 0; }
 
-// Overflow slots of a record with n_groups blocks: an eighth of them (the model's flux columns need 2.3 %), and three more
-// so that a small ensemble does not go raw for two unlucky blocks.
+// The ratio predictor.  The only floating-point operations of the codec: IEEE division and multiplication, round to nearest,
+// denormals kept (the host side runs under FpDefault).  Whether the result is used is decided on its pattern.
+SIMPLYP_PACK_HD inline uint64_t predict(uint64_t x, uint64_t x_prev, uint64_t y_prev)
+{
+    const double p = __builtin_bit_cast(double, x) * (__builtin_bit_cast(double, y_prev) / __builtin_bit_cast(double, x_prev));
+    const uint64_t pb = __builtin_bit_cast(uint64_t, p), mag = pb & 0x7FFFFFFFFFFFFFFFull;
+    return (mag == 0ull || (mag >> 52) == 0x7FFull) ? y_prev : pb;
+}
+
+// Overflow blocks a record with n_groups blocks may hold: an eighth of them (the model's flux columns need 2.3 %), and three
+// more so that a small ensemble does not go raw for two unlucky blocks.
 SIMPLYP_PACK_HD inline unsigned overflow_capacity(int n_groups) { return (unsigned)n_groups / 8u + 3u; }
 
 struct Layout {
-    size_t off_row0, off_lo, off_mid, off_hi, off_ovf;   // bytes from the start of the record
-    size_t block_bytes;                                  // one overflow block: nd x 64 doubles
-    size_t bytes;                                        // whole record, overflow area included (a multiple of 256)
+    size_t off_dir, dir_stride, off_widths;   // directory: bytes from the start of the record, bytes per entry, widths inside an entry
+    size_t off_body;
+    size_t body_cap_words;                    // what the body may hold: 7 bytes per value and cap raw blocks, as round 6's record
+    size_t bytes;                             // whole record at capacity, padding included (a multiple of 256)
+    int rows, n_spans;                        // delta rows, spans of them
 };
 
 SIMPLYP_PACK_HD inline size_t round_up(size_t v, size_t to) { return (v + to - 1) / to * to; }
@@ -57,189 +74,397 @@ SIMPLYP_PACK_HD inline size_t round_up(size_t v, size_t to) { return (v + to - 1
 SIMPLYP_PACK_HD inline Layout layout(size_t E, int nd, unsigned cap)
 {
     Layout L;
-    const size_t rows = (size_t)(nd - 1);
-    L.off_row0 = round_up((size_t)cap * sizeof(uint32_t), 256);
-    L.off_lo = L.off_row0 + E * sizeof(double);
-    L.off_mid = L.off_lo + rows * E * sizeof(uint32_t);
-    L.off_hi = L.off_mid + rows * E * sizeof(uint16_t);
-    L.off_ovf = round_up(L.off_hi + rows * E, 256);
-    L.block_bytes = (size_t)nd * GROUP * sizeof(double);
-    L.bytes = L.off_ovf + (size_t)cap * L.block_bytes;
+    const size_t G = (E + GROUP - 1) / GROUP;
+    L.rows = nd - 1;
+    L.n_spans = (L.rows + SPAN - 1) / SPAN;
+    L.off_dir = round_up(E * sizeof(double), 256);
+    L.off_widths = (size_t)L.n_spans * sizeof(uint32_t);
+    L.dir_stride = round_up(L.off_widths + (size_t)L.rows, 4);
+    L.off_body = round_up(L.off_dir + G * L.dir_stride, 256);
+    L.body_cap_words = ((size_t)L.rows * E * 7 + 7) / 8 + (size_t)cap * (size_t)nd * GROUP;
+    L.bytes = round_up(L.off_body + L.body_cap_words * 8 + 8, 256);
     return L;
 }
 
-#if defined(__HIPCC__)
-// One wavefront packs its own block: members g*64 .. g*64+63 of `nd` rows of one column.  `rows` points at the column's first
-// row of the chunk, `stride` is doubles per row.  Loads go out in batches of independent requests; the prediction chain
-// (previous day) stays in a register.  `count` is the record's overflow counter.
-__device__ __forceinline__ void pack_block(const double* rows, size_t stride, int nd, int E, int g, int lane,
-                                           unsigned char* rec, const Layout& L, unsigned* count, unsigned cap)
+// What crosses the link for a record whose cursor stands at `words`.
+SIMPLYP_PACK_HD inline size_t copy_bytes(const Layout& L, size_t words) { return L.off_body + words * 8 + 8; }
+SIMPLYP_PACK_HD inline bool travels_raw(const Layout& L, unsigned overflow_blocks, size_t words, unsigned cap)
 {
-    constexpr int BATCH = 8;
+    return overflow_blocks > cap || words > L.body_cap_words;
+}
+
+#if defined(__HIPCC__)
+constexpr int BATCH = 8;                        // rows a wavefront handles together
+constexpr int LDS_WORDS = BATCH * GROUP;        // LDS a packing wavefront needs: one row image per row of a batch
+
+// v[i]: this lane's value of row i of a batch.  Returns, in every lane, the maximum over all lanes of row (lane & 7): three
+// exchange steps in which a lane gives away the half of the rows its partner keeps, then three plain steps -- 10 shuffles for 8
+// rows, 6 deep, where 8 separate reductions take 48.
+__device__ __forceinline__ int wave_max_rows(const int (&v)[BATCH], int lane)
+{
+    const bool b2 = (lane & 4) != 0, b1 = (lane & 2) != 0, b0 = (lane & 1) != 0;
+    int a[4], b[2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a[j] = max(b2 ? v[j + 4] : v[j], __shfl_xor(b2 ? v[j] : v[j + 4], 4));
+#pragma unroll
+    for (int j = 0; j < 2; ++j) b[j] = max(b1 ? a[j + 2] : a[j], __shfl_xor(b1 ? a[j] : a[j + 2], 2));
+    int c = max(b0 ? b[1] : b[0], __shfl_xor(b0 ? b[0] : b[1], 1));
+    for (int m = 8; m < GROUP; m <<= 1) c = max(c, __shfl_xor(c, m));
+    return c;
+}
+
+// LDS operations of one wavefront execute in order; this keeps the compiler to the order they are written in.
+__device__ __forceinline__ void lds_order()
+{
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// One wavefront packs its own block: members g*64 .. g*64+63 of `nd` rows of one column.  `rows` points at the column's first
+// row of the chunk, `xrows` at the predictor column's (nullptr: previous day), `stride` is doubles per row.  `count` are the
+// record's two counters, `lds` LDS_WORDS words of LDS that belong to this wavefront alone.
+// Per span of 64 delta rows: a first pass finds the widths (lane r keeps row r's, a lane prefix sum gives the row offsets), one
+// atomic add takes the span's place in the body, a second pass reads the rows again (L2) and packs them -- each lane ORs its z
+// into the row's LDS image, which then leaves as w coalesced 8-byte stores.  Both passes take the rows eight at a time, so
+// that a batch costs one round of loads, shuffles and LDS operations, not eight.
+__device__ __forceinline__ void pack_block(const double* rows, const double* xrows, size_t stride, int nd, int E, int g, int lane,
+                                           unsigned char* rec, const Layout& L, unsigned* count, unsigned long long* lds)
+{
     const int e = g * GROUP + lane;
     const bool live = e < E;
     const unsigned long long* src = (const unsigned long long*)rows + (live ? e : 0);
-    uint32_t* lo = (uint32_t*)(rec + L.off_lo) + e;
-    uint16_t* mid = (uint16_t*)(rec + L.off_mid) + e;
-    uint8_t* hi = (uint8_t*)(rec + L.off_hi) + e;
-    unsigned long long prev = live ? src[0] : 0ull;
-    if (live) ((unsigned long long*)(rec + L.off_row0))[e] = prev;
+    const unsigned long long* xsrc = xrows ? (const unsigned long long*)xrows + (live ? e : 0) : src;
+    const bool ratio = xrows != nullptr;                       // wave-uniform
+    if (live) ((unsigned long long*)rec)[e] = src[0];
+    unsigned char* dir = rec + L.off_dir + (size_t)g * L.dir_stride;
+    unsigned long long* body = (unsigned long long*)(rec + L.off_body);
     unsigned long long big = 0ull;
-    for (int d0 = 1; d0 < nd; d0 += BATCH) {
-        unsigned long long u[BATCH];
+    for (int s = 0; s < L.n_spans; ++s) {
+        const int d_first = 1 + s * SPAN, n = min(SPAN, nd - d_first);      // rows d_first .. d_first + n - 1
+        unsigned long long prev = live ? src[(size_t)(d_first - 1) * stride] : 0ull;
+        unsigned long long xprev = (live && ratio) ? xsrc[(size_t)(d_first - 1) * stride] : 0ull;
+        const unsigned long long prev0 = prev, xprev0 = xprev;
+        int wmine = 0;
+        for (int k0 = 0; k0 < n; k0 += BATCH) {
+            unsigned long long u[BATCH], x[BATCH];
 #pragma unroll
-        for (int i = 0; i < BATCH; ++i) u[i] = (live && d0 + i < nd) ? src[(size_t)(d0 + i) * stride] : 0ull;
-#pragma unroll
-        for (int i = 0; i < BATCH; ++i) {
-            if (live && d0 + i < nd) {
-                const unsigned long long z = encode(u[i], prev);
-                prev = u[i];
-                big |= z >> Z_BITS;
-                const size_t at = (size_t)(d0 + i - 1) * (size_t)E;
-                lo[at] = (uint32_t)z;
-                mid[at] = (uint16_t)(z >> 32);
-                hi[at] = (uint8_t)(z >> 48);
+            for (int i = 0; i < BATCH; ++i) {
+                const bool in = live && k0 + i < n;
+                u[i] = in ? src[(size_t)(d_first + k0 + i) * stride] : 0ull;
+                x[i] = (in && ratio) ? xsrc[(size_t)(d_first + k0 + i) * stride] : 0ull;
             }
+            int wv[BATCH];
+#pragma unroll
+            for (int i = 0; i < BATCH; ++i) {
+                const bool in = live && k0 + i < n;
+                const unsigned long long z = in ? encode(u[i], ratio ? predict(x[i], xprev, prev) : prev) : 0ull;
+                prev = u[i]; xprev = x[i];
+                big |= z >> Z_BITS;
+                wv[i] = width_of(z);
+            }
+            const int w = wave_max_rows(wv, lane);             // of row k0 + (lane & 7)
+            if ((lane & ~(BATCH - 1)) == k0) wmine = w;
+        }
+        int inc = wmine;                                       // inclusive lane prefix sum of the widths = words
+        for (int o = 1; o < GROUP; o <<= 1) {
+            const int t = __shfl_up(inc, o);
+            if (lane >= o) inc += t;
+        }
+        const int excl = inc - wmine;
+        const unsigned total = (unsigned)__builtin_amdgcn_readlane(inc, GROUP - 1);
+        unsigned base = 0u;
+        if (total != 0u) {
+            if (lane == 0) base = atomicAdd(count + 1, total);
+            base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+        }
+        if ((size_t)base + total > L.body_cap_words) continue; // (wave-uniform) past the capacity: the record travels raw
+        if (lane == 0) ((uint32_t*)dir)[s] = base;
+        if (lane < n) dir[L.off_widths + (size_t)(d_first - 1 + lane)] = (unsigned char)wmine;
+        if (total == 0u) continue;
+        prev = prev0; xprev = xprev0;
+        for (int k0 = 0; k0 < n; k0 += BATCH) {
+            unsigned long long u[BATCH], x[BATCH];
+#pragma unroll
+            for (int i = 0; i < BATCH; ++i) {
+                const bool in = live && k0 + i < n;
+                u[i] = in ? src[(size_t)(d_first + k0 + i) * stride] : 0ull;
+                x[i] = (in && ratio) ? xsrc[(size_t)(d_first + k0 + i) * stride] : 0ull;
+            }
+#pragma unroll
+            for (int i = 0; i < BATCH; ++i) __hip_atomic_store(&lds[i * GROUP + lane], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            lds_order();
+#pragma unroll
+            for (int i = 0; i < BATCH; ++i) {
+                const bool in = live && k0 + i < n;
+                const unsigned long long z = in ? encode(u[i], ratio ? predict(x[i], xprev, prev) : prev) : 0ull;
+                prev = u[i]; xprev = x[i];
+                const int w = __builtin_amdgcn_readlane(wmine, k0 + i);       // (0 beyond the span's last row)
+                const int bit = lane * w, wi = bit >> 6, sh = bit & 63;
+                if (z != 0ull) {
+                    __hip_atomic_fetch_or(&lds[i * GROUP + wi], z << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (sh + w > 64) __hip_atomic_fetch_or(&lds[i * GROUP + wi + 1], z >> (64 - sh), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+            lds_order();
+#pragma unroll
+            for (int i = 0; i < BATCH; ++i) {
+                const int w = __builtin_amdgcn_readlane(wmine, k0 + i);
+                const int off = __builtin_amdgcn_readlane(excl, k0 + i);
+                if (lane < w)
+                    body[(size_t)base + (size_t)off + (size_t)lane] = __hip_atomic_load(&lds[i * GROUP + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            lds_order();
         }
     }
-    if (__ballot(big != 0ull) == 0ull) return;                 // wave-uniform
-    unsigned slot = 0u;
-    if (lane == 0) slot = atomicAdd(count, 1u);
-    slot = (unsigned)__builtin_amdgcn_readfirstlane((int)slot);
-    if (slot >= cap) return;                                   // the record travels raw
-    if (lane == 0) ((uint32_t*)rec)[slot] = (uint32_t)g;
-    unsigned long long* blk = (unsigned long long*)(rec + L.off_ovf + (size_t)slot * L.block_bytes) + lane;
-    for (int d = 0; d < nd; ++d) blk[(size_t)d * GROUP] = live ? src[(size_t)d * stride] : 0ull;
+    if (__ballot(big != 0ull) != 0ull && lane == 0) atomicAdd(count, 1u);
 }
 #endif
 
 // ---- host half ----
 
-// The encoder in plain C++, block by block like the device's: returns the record's overflow counter (which may pass `cap`;
-// blocks beyond it are not stored).
-inline unsigned encode_record_host(const double* rows, size_t stride, int nd, size_t E, unsigned char* rec, const Layout& L,
-                                   unsigned cap)
+#if defined(__x86_64__)
+// MXCSR at its default (round to nearest, no flush to zero, denormals are not zero) for the life of the object: the encoder,
+// the decoder and the decode threads hold one, so predict() rounds as the device does whatever the caller's thread had set.
+struct FpDefault {
+    unsigned saved;
+    FpDefault() : saved(_mm_getcsr()) { _mm_setcsr(0x1F80u); }
+    ~FpDefault() { _mm_setcsr(saved); }
+    FpDefault(const FpDefault&) = delete;
+    FpDefault& operator=(const FpDefault&) = delete;
+};
+#else
+struct FpDefault {};
+#endif
+
+// The 64 z of one row of width w into the row's image (`w` words, zeroed by the caller).
+inline void pack_row_host(const uint64_t* z, int w, uint64_t* image)
 {
-    const uint64_t* src = (const uint64_t*)rows;
-    unsigned count = 0;
-    const int G = (int)((E + GROUP - 1) / GROUP);
-    memcpy(rec + L.off_row0, src, E * sizeof(uint64_t));
-    for (int g = 0; g < G; ++g) {
-        const size_t e0 = (size_t)g * GROUP, e1 = e0 + GROUP < E ? e0 + GROUP : E;
-        bool big = false;
-        for (size_t e = e0; e < e1; ++e) {
-            uint64_t prev = src[e];
-            for (int d = 1; d < nd; ++d) {
-                const uint64_t u = src[(size_t)d * stride + e], z = encode(u, prev);
-                prev = u;
-                big = big || !fits(z);
-                const size_t at = (size_t)(d - 1) * E + e;
-                const uint32_t l = (uint32_t)z; const uint16_t m = (uint16_t)(z >> 32);
-                memcpy(rec + L.off_lo + at * 4, &l, 4);
-                memcpy(rec + L.off_mid + at * 2, &m, 2);
-                rec[L.off_hi + at] = (uint8_t)(z >> 48);
-            }
-        }
-        if (!big) continue;
-        const unsigned slot = count++;
-        if (slot >= cap) continue;
-        const uint32_t gid = (uint32_t)g;
-        memcpy(rec + (size_t)slot * 4, &gid, 4);
-        uint64_t* blk = (uint64_t*)(rec + L.off_ovf + (size_t)slot * L.block_bytes);
-        for (int d = 0; d < nd; ++d)
-            for (size_t i = 0; i < (size_t)GROUP; ++i) blk[(size_t)d * GROUP + i] = e0 + i < E ? src[(size_t)d * stride + e0 + i] : 0ull;
+    for (int i = 0; i < GROUP; ++i) {
+        const int bit = i * w, wi = bit >> 6, sh = bit & 63;
+        if (!z[i]) continue;
+        image[wi] |= z[i] << sh;
+        if (sh + w > 64) image[wi + 1] |= z[i] >> (64 - sh);
     }
-    return count;
 }
 
-// Members [e0, e1) of a landed record into `dst` (the column's first row of the chunk, `stride` doubles per row), written with
-// non-temporal stores.  `run` holds e1 - e0 words: the running values, which stay in cache from row to row.
-// One row of a range: out[i] = run[i] += unzigzag(planes[i]).
-inline void decode_row_scalar(const unsigned char* lo, const unsigned char* mid, const unsigned char* hi, uint64_t* run,
-                              unsigned long long* out, size_t n)
+// The encoder in plain C++, block by block and span by span like the device's.  counts[0] = overflow blocks, counts[1] = the word
+// cursor (which may pass the capacity; spans beyond it are not stored).
+inline void encode_record_host(const double* rows, const double* xrows, size_t stride, int nd, size_t E, unsigned char* rec,
+                               const Layout& L, uint64_t counts[2])
 {
-    for (size_t i = 0; i < n; ++i) {
-        uint32_t l; uint16_t m;
-        memcpy(&l, lo + i * 4, 4);
-        memcpy(&m, mid + i * 2, 2);
-        const uint64_t z = (uint64_t)l | ((uint64_t)m << 32) | ((uint64_t)hi[i] << 48);
-        const uint64_t u = decode(z, run[i]);
-        run[i] = u;
-        __builtin_nontemporal_store((unsigned long long)u, out + i);
+    FpDefault fp;
+    (void)fp;
+    const uint64_t* src = (const uint64_t*)rows;
+    const uint64_t* xsrc = (const uint64_t*)xrows;
+    const int G = (int)((E + GROUP - 1) / GROUP);
+    memcpy(rec, src, E * sizeof(uint64_t));
+    uint64_t* body = (uint64_t*)(rec + L.off_body);
+    uint64_t n_big = 0, cursor = 0;
+    uint64_t z[SPAN][GROUP];
+    for (int g = 0; g < G; ++g) {
+        const size_t e0 = (size_t)g * GROUP;
+        unsigned char* dir = rec + L.off_dir + (size_t)g * L.dir_stride;
+        bool big = false;
+        for (int s = 0; s < L.n_spans; ++s) {
+            const int d_first = 1 + s * SPAN, n = nd - d_first < SPAN ? nd - d_first : SPAN;
+            int w[SPAN];
+            uint64_t total = 0;
+            for (int k = 0; k < n; ++k) {
+                const size_t d = (size_t)(d_first + k);
+                uint64_t any = 0;
+                for (int i = 0; i < GROUP; ++i) {
+                    const size_t e = e0 + (size_t)i;
+                    uint64_t v = 0;
+                    if (e < E) {
+                        const uint64_t yp = src[(d - 1) * stride + e];
+                        const uint64_t p = xsrc ? predict(xsrc[d * stride + e], xsrc[(d - 1) * stride + e], yp) : yp;
+                        v = encode(src[d * stride + e], p);
+                    }
+                    z[k][i] = v;
+                    any |= v;
+                }
+                big = big || !fits(any);
+                w[k] = width_of(any);
+                total += (uint64_t)w[k];
+            }
+            const uint64_t base = cursor;
+            cursor += total;
+            if (base + total > L.body_cap_words) continue;
+            const uint32_t b32 = (uint32_t)base;
+            memcpy(dir + (size_t)s * 4, &b32, 4);
+            uint64_t* at = body + base;
+            for (int k = 0; k < n; ++k) {
+                dir[L.off_widths + (size_t)(d_first - 1 + k)] = (unsigned char)w[k];
+                memset(at, 0, (size_t)w[k] * 8);
+                pack_row_host(z[k], w[k], at);
+                at += w[k];
+            }
+        }
+        if (big) ++n_big;
     }
+    counts[0] = n_big;
+    counts[1] = cursor;
+}
+
+inline uint64_t load64(const unsigned char* p) { uint64_t v; memcpy(&v, p, 8); return v; }
+
+// The 64 z of a row of any width.  Value i sits at bit i * w: eight bytes from byte (i * w) >> 3, and a ninth where the value
+// ends beyond them (w > 56 only).
+inline void unpack_row_scalar(const unsigned char* row, int w, uint64_t* z)
+{
+    if (w == 0) { memset(z, 0, GROUP * sizeof(uint64_t)); return; }
+    const uint64_t mask = w == 64 ? ~0ull : (1ull << w) - 1ull;
+    for (int i = 0; i < GROUP; ++i) {
+        const int bit = i * w, by = bit >> 3, sh = bit & 7;
+        uint64_t v = load64(row + by) >> sh;
+        if (sh + w > 64) v |= (uint64_t)row[by + 8] << (64 - sh);
+        z[i] = v & mask;
+    }
+}
+
+// out[i] = pred[i] + unzigzag(z[i]) for a whole block row; `z` becomes the row's values (the next row's previous day).
+inline void finish_row_scalar(uint64_t* run, const uint64_t* z, const uint64_t* x, const uint64_t* x_prev, int n)
+{
+    if (x) for (int i = 0; i < n; ++i) run[i] = decode(z[i], predict(x[i], x_prev[i], run[i]));
+    else for (int i = 0; i < GROUP; ++i) run[i] = decode(z[i], run[i]);
+}
+
+inline void store_row(unsigned long long* out, const uint64_t* run, int n)
+{
+    for (int i = 0; i < n; ++i) __builtin_nontemporal_store((unsigned long long)run[i], out + i);
 }
 
 #if defined(__x86_64__)
-// The same with 256-bit integer operations, eight values per turn; `out` must be 32-byte aligned.
-__attribute__((target("avx2"))) inline void decode_row_avx2(const unsigned char* lo, const unsigned char* mid, const unsigned char* hi,
-                                                            uint64_t* run, unsigned long long* out, size_t n)
+// w <= 56: one unaligned 8-byte load per value, a shift by (i * w) & 7 and a mask; the shifts repeat every 8 values (w bytes).
+__attribute__((target("avx2"))) inline void unpack_row_avx2(const unsigned char* row, int w, uint64_t* z)
+{
+    int o[8];
+    long long s[8];
+    for (int t = 0; t < 8; ++t) { o[t] = (t * w) >> 3; s[t] = (t * w) & 7; }
+    const __m256i mask = _mm256_set1_epi64x((long long)((1ull << w) - 1ull));
+    const __m256i s0 = _mm256_set_epi64x(s[3], s[2], s[1], s[0]), s1 = _mm256_set_epi64x(s[7], s[6], s[5], s[4]);
+    for (int m = 0; m < 8; ++m) {
+        const unsigned char* p = row + (size_t)m * (size_t)w;
+        const __m256i a = _mm256_set_epi64x((long long)load64(p + o[3]), (long long)load64(p + o[2]), (long long)load64(p + o[1]),
+                                            (long long)load64(p + o[0]));
+        const __m256i b = _mm256_set_epi64x((long long)load64(p + o[7]), (long long)load64(p + o[6]), (long long)load64(p + o[5]),
+                                            (long long)load64(p + o[4]));
+        _mm256_storeu_si256((__m256i*)(z + m * 8), _mm256_and_si256(_mm256_srlv_epi64(a, s0), mask));
+        _mm256_storeu_si256((__m256i*)(z + m * 8 + 4), _mm256_and_si256(_mm256_srlv_epi64(b, s1), mask));
+    }
+}
+
+// The same arithmetic as finish_row_scalar, four values per turn.  _mm256_div_pd and _mm256_mul_pd are the IEEE operations.
+__attribute__((target("avx2"))) inline void finish_row_avx2(uint64_t* run, const uint64_t* z, const uint64_t* x, const uint64_t* x_prev, int n)
 {
     const __m256i one = _mm256_set1_epi64x(1), zero = _mm256_setzero_si256();
-    size_t i = 0;
-    for (; i + 8 <= n; i += 8) {
-        const __m256i l = _mm256_loadu_si256((const __m256i*)(lo + i * 4));
-        const __m128i m = _mm_loadu_si128((const __m128i*)(mid + i * 2));
-        const __m128i h = _mm_loadl_epi64((const __m128i*)(hi + i));
-        const __m256i z0 = _mm256_or_si256(_mm256_cvtepu32_epi64(_mm256_castsi256_si128(l)),
-                                           _mm256_or_si256(_mm256_slli_epi64(_mm256_cvtepu16_epi64(m), 32),
-                                                           _mm256_slli_epi64(_mm256_cvtepu8_epi64(h), 48)));
-        const __m256i z1 = _mm256_or_si256(_mm256_cvtepu32_epi64(_mm256_extracti128_si256(l, 1)),
-                                           _mm256_or_si256(_mm256_slli_epi64(_mm256_cvtepu16_epi64(_mm_srli_si128(m, 8)), 32),
-                                                           _mm256_slli_epi64(_mm256_cvtepu8_epi64(_mm_srli_si128(h, 4)), 48)));
-        const __m256i d0 = _mm256_xor_si256(_mm256_srli_epi64(z0, 1), _mm256_sub_epi64(zero, _mm256_and_si256(z0, one)));
-        const __m256i d1 = _mm256_xor_si256(_mm256_srli_epi64(z1, 1), _mm256_sub_epi64(zero, _mm256_and_si256(z1, one)));
-        const __m256i u0 = _mm256_add_epi64(_mm256_loadu_si256((const __m256i*)(run + i)), d0);
-        const __m256i u1 = _mm256_add_epi64(_mm256_loadu_si256((const __m256i*)(run + i + 4)), d1);
-        _mm256_storeu_si256((__m256i*)(run + i), u0);
-        _mm256_storeu_si256((__m256i*)(run + i + 4), u1);
-        _mm256_stream_si256((__m256i*)(out + i), u0);
-        _mm256_stream_si256((__m256i*)(out + i + 4), u1);
+    const __m256i absmask = _mm256_set1_epi64x(0x7FFFFFFFFFFFFFFFll), expmask = _mm256_set1_epi64x(0x7FF0000000000000ll);
+    int i = 0;
+    const int n4 = x ? n / 4 * 4 : GROUP;
+    for (; i < n4; i += 4) {
+        const __m256i zz = _mm256_loadu_si256((const __m256i*)(z + i));
+        const __m256i d = _mm256_xor_si256(_mm256_srli_epi64(zz, 1), _mm256_sub_epi64(zero, _mm256_and_si256(zz, one)));
+        __m256i p = _mm256_loadu_si256((const __m256i*)(run + i));
+        if (x) {
+            const __m256d q = _mm256_div_pd(_mm256_castsi256_pd(p), _mm256_loadu_pd((const double*)(x_prev + i)));
+            const __m256i pb = _mm256_castpd_si256(_mm256_mul_pd(_mm256_loadu_pd((const double*)(x + i)), q));
+            const __m256i mag = _mm256_and_si256(pb, absmask);
+            const __m256i bad = _mm256_or_si256(_mm256_cmpeq_epi64(mag, zero), _mm256_cmpeq_epi64(_mm256_and_si256(pb, expmask), expmask));
+            p = _mm256_blendv_epi8(pb, p, bad);
+        }
+        _mm256_storeu_si256((__m256i*)(run + i), _mm256_add_epi64(p, d));
     }
-    decode_row_scalar(lo + i * 4, mid + i * 2, hi + i, run + i, out + i, n - i);
+    if (x) for (; i < n; ++i) run[i] = decode(z[i], predict(x[i], x_prev[i], run[i]));
+}
+
+// The common row in one pass: a full block, 1 <= w <= 56, previous-day prediction, `out` 32-byte aligned.  unpack_row_avx2,
+// finish_row_avx2 and store_row_avx2 without the trip of z through memory: run[i] += unzigzag(z[i]), streamed to out[i].
+__attribute__((target("avx2"))) inline void decode_row_avx2(const unsigned char* row, int w, uint64_t* run, unsigned long long* out)
+{
+    int o[8];
+    long long s[8];
+    for (int t = 0; t < 8; ++t) { o[t] = (t * w) >> 3; s[t] = (t * w) & 7; }
+    const __m256i mask = _mm256_set1_epi64x((long long)((1ull << w) - 1ull)), one = _mm256_set1_epi64x(1), zero = _mm256_setzero_si256();
+    const __m256i s0 = _mm256_set_epi64x(s[3], s[2], s[1], s[0]), s1 = _mm256_set_epi64x(s[7], s[6], s[5], s[4]);
+    for (int m = 0; m < 8; ++m) {
+        const unsigned char* p = row + (size_t)m * (size_t)w;
+        __m256i a = _mm256_set_epi64x((long long)load64(p + o[3]), (long long)load64(p + o[2]), (long long)load64(p + o[1]),
+                                      (long long)load64(p + o[0]));
+        __m256i b = _mm256_set_epi64x((long long)load64(p + o[7]), (long long)load64(p + o[6]), (long long)load64(p + o[5]),
+                                      (long long)load64(p + o[4]));
+        a = _mm256_and_si256(_mm256_srlv_epi64(a, s0), mask);
+        b = _mm256_and_si256(_mm256_srlv_epi64(b, s1), mask);
+        a = _mm256_xor_si256(_mm256_srli_epi64(a, 1), _mm256_sub_epi64(zero, _mm256_and_si256(a, one)));
+        b = _mm256_xor_si256(_mm256_srli_epi64(b, 1), _mm256_sub_epi64(zero, _mm256_and_si256(b, one)));
+        a = _mm256_add_epi64(a, _mm256_load_si256((const __m256i*)(run + m * 8)));
+        b = _mm256_add_epi64(b, _mm256_load_si256((const __m256i*)(run + m * 8 + 4)));
+        _mm256_store_si256((__m256i*)(run + m * 8), a);
+        _mm256_store_si256((__m256i*)(run + m * 8 + 4), b);
+        _mm256_stream_si256((__m256i*)(out + m * 8), a);
+        _mm256_stream_si256((__m256i*)(out + m * 8 + 4), b);
+    }
+}
+
+__attribute__((target("avx2"))) inline void store_row_avx2(unsigned long long* out, const uint64_t* run, int n)
+{
+    int i = 0;
+    if (((uintptr_t)out & 31) == 0)
+        for (; i + 4 <= n; i += 4) _mm256_stream_si256((__m256i*)(out + i), _mm256_loadu_si256((const __m256i*)(run + i)));
+    for (; i < n; ++i) __builtin_nontemporal_store((unsigned long long)run[i], out + i);
 }
 #endif
 
+// Members [e0, e1) of a landed record into `dst` (the column's first row of the chunk, `stride` doubles per row), written with
+// non-temporal stores; e0 is a multiple of 64.  `xdst` is the predictor column's first row of the chunk in the same table,
+// already decoded for these members (nullptr: previous day): its rows are read back from there.  The caller holds an FpDefault.
 inline void decode_range(const unsigned char* rec, const Layout& L, int nd, size_t E, size_t e0, size_t e1, double* dst,
-                         size_t stride, uint64_t* run)
+                         const double* xdst, size_t stride)
 {
-    const size_t n = e1 - e0;
-    memcpy(run, rec + L.off_row0 + e0 * 8, n * 8);
-    unsigned long long* out = (unsigned long long*)dst + e0;       // (doubles: 8-byte aligned)
-    for (size_t i = 0; i < n; ++i) __builtin_nontemporal_store((unsigned long long)run[i], out + i);
 #if defined(__x86_64__)
     static const bool have_avx2 = __builtin_cpu_supports("avx2");
 #endif
-    for (int d = 1; d < nd; ++d) {
-        const size_t at = (size_t)(d - 1) * E + e0;
-        const unsigned char* lo = rec + L.off_lo + at * 4;
-        const unsigned char* mid = rec + L.off_mid + at * 2;
-        const unsigned char* hi = rec + L.off_hi + at;
-        out += stride;
+    alignas(32) uint64_t run[GROUP], z[GROUP];
+    const unsigned char* body = rec + L.off_body;
+    for (size_t b0 = e0; b0 < e1; b0 += GROUP) {
+        const int n = (int)(e1 - b0 < (size_t)GROUP ? e1 - b0 : (size_t)GROUP);
+        const unsigned char* dir = rec + L.off_dir + (b0 / GROUP) * L.dir_stride;
+        memset(run, 0, sizeof(run));
+        memcpy(run, rec + b0 * 8, (size_t)n * 8);
+        unsigned long long* out = (unsigned long long*)dst + b0;
+        const uint64_t* x = xdst ? (const uint64_t*)xdst + b0 : nullptr;
+        store_row(out, run, n);
+        const unsigned char* row = body;
+        for (int d = 1; d < nd; ++d) {
+            if ((d - 1) % SPAN == 0) {
+                uint32_t base;
+                memcpy(&base, dir + (size_t)((d - 1) / SPAN) * 4, 4);
+                row = body + (size_t)base * 8;
+            }
+            const int w = dir[L.off_widths + (size_t)(d - 1)];
+            out += stride;
+            const uint64_t* xd = x ? x + (size_t)d * stride : nullptr;
+            const uint64_t* xp = x ? x + (size_t)(d - 1) * stride : nullptr;
 #if defined(__x86_64__)
-        if (have_avx2) {
-            // scalar up to the first 32-byte boundary of the row, vectors from there
-            size_t head = ((32 - ((uintptr_t)out & 31)) & 31) / 8;
-            if (head > n) head = n;
-            decode_row_scalar(lo, mid, hi, run, out, head);
-            decode_row_avx2(lo + head * 4, mid + head * 2, hi + head, run + head, out + head, n - head);
-            continue;
-        }
+            if (have_avx2) {
+                if (!x && n == GROUP && w >= 1 && w <= Z_BITS && ((uintptr_t)out & 31) == 0) {
+                    decode_row_avx2(row, w, run, out);
+                    row += (size_t)w * 8;
+                    continue;
+                }
+                if (w == 0) memset(z, 0, sizeof(z));
+                else if (w <= Z_BITS) unpack_row_avx2(row, w, z);
+                else unpack_row_scalar(row, w, z);
+                finish_row_avx2(run, z, xd, xp, n);
+                store_row_avx2(out, run, n);
+                row += (size_t)w * 8;
+                continue;
+            }
 #endif
-        decode_row_scalar(lo, mid, hi, run, out, n);
-    }
-}
-
-// The raw blocks of the record's overflow area over what decode_range wrote (after every range of the record is done).
-inline void apply_overflow(const unsigned char* rec, const Layout& L, int nd, size_t E, unsigned count, double* dst, size_t stride)
-{
-    for (unsigned s = 0; s < count; ++s) {
-        uint32_t g;
-        memcpy(&g, rec + (size_t)s * 4, 4);
-        const size_t e0 = (size_t)g * GROUP;
-        if (e0 >= E) continue;
-        const size_t n = e0 + GROUP < E ? (size_t)GROUP : E - e0;
-        const unsigned char* blk = rec + L.off_ovf + (size_t)s * L.block_bytes;
-        for (int d = 0; d < nd; ++d) memcpy(dst + (size_t)d * stride + e0, blk + (size_t)d * GROUP * 8, n * 8);
+            unpack_row_scalar(row, w, z);
+            finish_row_scalar(run, z, xd, xp, n);
+            store_row(out, run, n);
+            row += (size_t)w * 8;
+        }
     }
 }
 

@@ -3,17 +3,20 @@
 // caller's table (simplyp_pack.h is the codec).  Shared by the library (simplyp_hip.hip) and tools/pack_gate.hip.
 //
 // Order of events for record number k (records are numbered in the order submit() is called):
-//   submit      waits until record k - n_slots has been released, enqueues the record's copy (planes and the overflow blocks
-//               in use are contiguous) and an event behind it on the caller's stream;
+//   submit      waits until record k - n_slots has been released, enqueues the record's copy (first row, directory and the body
+//               as far as its cursor went are contiguous) and an event behind it on the caller's stream;
 //   dispatcher  hipEventSynchronize on that event -- its own event, nobody else waits on it -- then marks k landed;
-//   workers     every worker decodes ITS member range of every record, in order; the last one to finish record k applies the
-//               overflow blocks and releases the slot.  Records are therefore released in order.
+//   workers     every worker decodes ITS member range (whole 64-member blocks) of every record, in order; the last one to
+//               finish record k releases the slot.  Records are therefore released in order.  A column predicted from another
+//               one is decoded after that one's record of the same chunk: the worker reads its own rows of it back from the
+//               destination table.
 //   finish      no more records: returns when the dispatcher and every worker have run out of work and are joined.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <sched.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -96,8 +99,9 @@ struct PackJob {
     const unsigned char* dev_rec = nullptr;   // the record in device memory
     Layout L;
     int nd = 0;
-    unsigned count = 0;                       // overflow blocks in use (<= capacity)
+    size_t copy_bytes = 0;                    // what travels: simplyp_pack::copy_bytes(L, the record's word cursor)
     double* dst = nullptr;                    // the column's first row of the chunk in the caller's table
+    const double* xdst = nullptr;             // the predictor column's, in the same table (nullptr: previous day)
     size_t stride = 0;                        // doubles per row of that table
     int slot = 0;
 };
@@ -158,12 +162,12 @@ public:
         }
         j.slot = seq % n_slots_;
         unsigned char* to = ring_ + (size_t)j.slot * slot_bytes_;
-        // one plain copy: the overflow blocks in use follow the planes directly
-        hipError_t err = hipMemcpyAsync(to, j.dev_rec, j.L.off_ovf + (size_t)j.count * j.L.block_bytes, hipMemcpyDeviceToHost, stream);
+        // one plain copy: the body follows the first row and the directory directly
+        hipError_t err = hipMemcpyAsync(to, j.dev_rec, j.copy_bytes, hipMemcpyDeviceToHost, stream);
         hipError_t err2 = hipEventRecord(events_[(size_t)j.slot], stream);      // recorded whatever happened: the dispatcher waits on it
         if (err == hipSuccess) err = err2;
         if (err != hipSuccess && !error_) error_ = (int)err;
-        packed_bytes_ += j.L.off_ovf + (size_t)j.count * j.L.block_bytes;
+        packed_bytes_ += j.copy_bytes;
         jobs_[(size_t)seq] = j;
         remaining_[(size_t)seq].store(T_, std::memory_order_relaxed);
         { std::lock_guard<std::mutex> lk(m_); n_issued_ = seq + 1; }
@@ -222,10 +226,12 @@ private:
     void worker_main(int t)
     {
         (void)bind_thread_to_gpu_node(device_);      // this thread only; the caller's own placement is the caller's business
-        // member ranges start on a cache line of the table's rows
-        const size_t e0 = t == 0 ? 0 : (E_ * (size_t)t / (size_t)T_) / 8 * 8;
-        const size_t e1 = t + 1 == T_ ? E_ : (E_ * (size_t)(t + 1) / (size_t)T_) / 8 * 8;
-        std::vector<uint64_t> run(e1 > e0 ? e1 - e0 : 1);
+        FpDefault fp;                                // the ratio predictor rounds as the device does, whatever the caller had set
+        (void)fp;
+        // member ranges are whole blocks
+        const size_t G = (E_ + GROUP - 1) / GROUP;
+        const size_t e0 = G * (size_t)t / (size_t)T_ * GROUP;
+        const size_t e1 = std::min(E_, G * (size_t)(t + 1) / (size_t)T_ * GROUP);
         for (int seq = 0;; ++seq) {
             {
                 std::unique_lock<std::mutex> lk(m_);
@@ -235,12 +241,10 @@ private:
             const PackJob& j = jobs_[(size_t)seq];
             const unsigned char* rec = ring_ + (size_t)j.slot * slot_bytes_;
             const auto t0 = std::chrono::steady_clock::now();
-            if (e1 > e0 && !error_) decode_range(rec, j.L, j.nd, E_, e0, e1, j.dst, j.stride, run.data());
+            if (e1 > e0 && !error_) decode_range(rec, j.L, j.nd, E_, e0, e1, j.dst, j.xdst, j.stride);
             __builtin_ia32_sfence();      // the non-temporal stores are globally visible before the range counts as done
             busy_s_[(size_t)t] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             if (remaining_[(size_t)seq].fetch_sub(1, std::memory_order_acq_rel) == 1) {
-                // the last range of the record: the raw blocks go over what every range has written
-                if (j.count > 0 && !error_) apply_overflow(rec, j.L, j.nd, E_, j.count, j.dst, j.stride);
                 { std::lock_guard<std::mutex> lk(m_); n_released_ = seq + 1; }
                 cv_.notify_all();
             }

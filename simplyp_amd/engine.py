@@ -28,7 +28,7 @@ ABI_SYMBOLS = ['simplyp_abi_version', 'simplyp_device_count', 'simplyp_ctx_creat
                'simplyp_device_alloc', 'simplyp_device_free', 'simplyp_memcpy_h2d', 'simplyp_memcpy_d2h', 'simplyp_gof',
                'simplyp_stream_out', 'simplyp_waterbody', 'simplyp_gof_waterbody', 'simplyp_gof_spearman', 'simplyp_eval_units',
                'simplyp_quantiles', 'simplyp_state_bytes', 'simplyp_set_state', 'simplyp_fetch_packed',
-               'simplyp_pack_roundtrip_host']
+               'simplyp_pack_roundtrip_host', 'simplyp_fetch_packed_pred', 'simplyp_pack_roundtrip_host_pred']
 
 _lib = None
 
@@ -111,6 +111,12 @@ def lib():
     L.simplyp_fetch_packed.argtypes = [vp, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int32)]
     L.simplyp_pack_roundtrip_host.restype = C.c_int
     L.simplyp_pack_roundtrip_host.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.POINTER(C.c_int32)]
+    L.simplyp_fetch_packed_pred.restype = C.c_int
+    L.simplyp_fetch_packed_pred.argtypes = [vp, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), vp, C.c_int64,
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.simplyp_pack_roundtrip_host_pred.restype = C.c_int
+    L.simplyp_pack_roundtrip_host_pred.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), vp,
+                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.simplyp_state_bytes.restype = C.c_int64
     L.simplyp_state_bytes.argtypes = [C.POINTER(abi.Dims)]
     L.simplyp_set_state.restype = C.c_int

@@ -1,5 +1,7 @@
 // pack_gate.hip -- go / no-go for the packed output stream, without a model run: the real shapes (one pinned destination of
-// the whole table, the pinned staging ring, a device buffer of packed records filled with synthetic deltas), the real schedule
+// the whole table, the pinned staging ring, a device buffer of packed records -- random bits under a valid directory whose row
+// widths are each column's mean on the model's table (51, 51, 52, 52 bits, and 38 for the last column,
+// which is decoded against the third with the ratio predictor) --, the real schedule
 // (two copy streams taken in turn, one record per chunk-column, the library's dispatcher and decode pool from
 // simplyp_pack_stream.h), against the raw copies of the same table in the same session.
 //
@@ -33,6 +35,17 @@ __global__ void fill_kernel(unsigned long long* p, size_t n)
     }
 }
 
+// A valid directory for every block of every record: one span, every row `w` bits wide, blocks in order.
+__global__ void directory_kernel(unsigned char* dev, size_t stride, int n_rec, int n_cols, int G, simplyp_pack::Layout L, const int* width_of_col)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n_rec * G) return;
+    const int rec = (int)(i / G), g = (int)(i % G), w = width_of_col[rec % n_cols];
+    unsigned char* dir = dev + (size_t)rec * stride + L.off_dir + (size_t)g * L.dir_stride;
+    *(uint32_t*)dir = (uint32_t)((size_t)g * L.rows * w);
+    for (int r = 0; r < L.rows; ++r) dir[L.off_widths + r] = (unsigned char)w;
+}
+
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 int main(int argc, char** argv)
@@ -59,6 +72,15 @@ int main(int argc, char** argv)
     if (!getenv("PACK_GATE_NO_BIND")) printf("main thread bound to the GPU's NUMA node: %d (-1 = not bound)\n", simplyp_pack::bind_thread_to_gpu_node(0));
     CHECK(hipMalloc((void**)&dev, dev_bytes));
     hipLaunchKernelGGL(fill_kernel, dim3(4096), dim3(256), 0, 0, (unsigned long long*)dev, dev_bytes / 8);
+    // (the last, shorter chunk keeps the directory of a full one: its decoder reads fewer rows of it)
+    const int widths[5] = {51, 51, 52, 52, 38};
+    std::vector<int> width_of_col((size_t)n_cols);
+    for (int j = 0; j < n_cols; ++j) width_of_col[(size_t)j] = widths[j % 5];
+    int* dev_widths = nullptr;
+    CHECK(hipMalloc((void**)&dev_widths, (size_t)n_cols * sizeof(int)));
+    CHECK(hipMemcpy(dev_widths, width_of_col.data(), (size_t)n_cols * sizeof(int), hipMemcpyHostToDevice));
+    const Layout L_full = layout(E, chunk, cap);
+    hipLaunchKernelGGL(directory_kernel, dim3((unsigned)(((size_t)n_rec * G + 255) / 256)), dim3(256), 0, 0, dev, stride, n_rec, n_cols, G, L_full, dev_widths);
     CHECK(hipDeviceSynchronize());
     double t0 = now_s();
     CHECK(hipHostMalloc((void**)&host, table_bytes, hipHostMallocDefault));
@@ -101,9 +123,10 @@ int main(int argc, char** argv)
                     PackJob job;
                     job.dev_rec = dev + (size_t)(c * n_cols + j) * stride;
                     job.nd = (int)nd;
-                    job.L = layout(E, (int)nd, cap);
-                    job.count = (j == 2 || j == 4) ? (unsigned)(G * 23 / 1000) : 0u;      // the flux columns' 2.3 % of blocks
+                    job.L = L_full;
+                    job.copy_bytes = copy_bytes(L_full, (size_t)G * (size_t)(nd - 1) * (size_t)width_of_col[(size_t)j]);
                     job.dst = host + ((size_t)j * D + d0) * E;
+                    if (j == 4) job.xdst = host + ((size_t)2 * D + d0) * E;                // PP against Msus
                     job.stride = E;
                     CHECK(ps.submit(job, streams[n++ % 2]));
                 }
@@ -124,5 +147,6 @@ int main(int argc, char** argv)
     ps.release();
     (void)hipHostFree(host);
     (void)hipFree(dev);
+    (void)hipFree(dev_widths);
     return 0;
 }
