@@ -55,7 +55,6 @@ struct simplyp_ctx {
     hipStream_t copy_stream = nullptr;                  // = copy_streams[0]: carries ev_copy_done
     hipStream_t copy_streams[N_COPY_STREAMS] = {};      // the chunk copies take these in turn
     hipEvent_t ev_copy_done = nullptr, ev_copy_join[N_COPY_STREAMS] = {};
-    int n_copy_streams = 2;
     double* stream_host = nullptr;      // armed for the next run (one-shot)
     int64_t stream_host_bytes = 0;
     const double* state_in = nullptr;   // simplyp_set_state: armed for the next run (one-shot)
@@ -63,23 +62,16 @@ struct simplyp_ctx {
     uint32_t* host_ready = nullptr;     // [host_ready_cap] hipHostMalloc
     size_t host_ready_cap = 0;
     DeviceBuf chunk_count;              // [n_chunks] uint32
-    struct CopyPlan {
+    struct CopyPlan {                   // what a run decides of its streamed copy
         const double* dev = nullptr;
         double* host = nullptr;
-        int ncols = 0, n_chunks = 0, chunk_days = 0;
-        size_t D = 0, row_doubles = 0;  // rows per column, doubles per row (n_out_reaches * E)
-        // packed stream (simplyp_pack.h): records [n_chunks][ncols] in `pack_dev`, `pack_stride` bytes apart; off when null
-        const unsigned char* pack_dev = nullptr;
-        size_t pack_stride = 0;
-        unsigned pack_cap = 0;
-        int n_packed = 0, n_raw = 0;    // records the copier sent packed / raw
-        unsigned n_overflow = 0;        // overflow blocks of the packed ones
-        int pack_pred[32];              // per column: the column it is predicted from, or -1 (simplyp_pack.h)
-        size_t packed_bytes = 0;        // what the packed records put on the link
-        int raw_of_col[32];             // records sent raw, per column (SIMPLYP_DEBUG)
+        bool chunked = false;           // chunk by chunk beside the queue kernel (`table` says which), not the whole table behind the run
+        simplyp_pack::Table table = {}; // columns, days, doubles per row (n_out_reaches * E), time chunks; the records' geometry
+        const unsigned char* pack_dev = nullptr;    // the packed records (simplyp_pack.h); null: every chunk travels as fp64
     } copy_plan;
+    simplyp_pack::Tally tally;          // what the copier sent packed and raw
     DeviceBuf packed;                   // the packed records of a run (grow-only; given back by the first run that does not pack)
-    DeviceBuf pack_count;               // [n_records][2] uint32: overflow blocks, body words (then simplyp_fetch_packed's pred_col)
+    DeviceBuf pack_count;               // [n_records][2] uint32: overflow blocks, body words; then [n_cols] int32: Table::pred
     uint32_t* host_pack_count = nullptr;    // the same in pinned host memory, written by the wave that completes a chunk
     size_t host_pack_count_cap = 0;
     simplyp_pack::PackStream pack;      // staging ring, dispatcher and decode pool
@@ -364,74 +356,48 @@ void copier_main(simplyp_ctx* ctx)
 {
     (void)hipSetDevice(ctx->device);
     const simplyp_ctx::CopyPlan& p = ctx->copy_plan;
+    const simplyp_pack::Table& t = p.table;
     // No HIP call inside the wait: hipEventQuery on the run's stop event blocks for as long as another thread sits in
     // hipEventSynchronize on it (measured: the first query returned when the kernel ended).  The flags live in host memory;
     // "the run is over" comes from simplyp_sync (or the error paths) through `run_over`.
     bool run_over = false;
     unsigned n_issued = 0;
     const bool dbg = getenv("SIMPLYP_DEBUG") != nullptr;
+    auto note = [&](hipError_t err) { if (err != hipSuccess && !ctx->copy_error) ctx->copy_error = (int)err; };
+    // two streams, taken in turn: the launch gap of one copy dispatch hides behind the other stream's transfer
+    auto next_stream = [&] { return ctx->copy_streams[n_issued++ % (unsigned)simplyp_ctx::N_COPY_STREAMS]; };
+    // (one plain copy per column: a pitched hipMemcpy2DAsync per chunk does not overlap the persistent kernel at all on this
+    // stack -- 1509 ms per pass instead of 803, profiles/r02_experiments.md)
+    auto raw = [&](size_t off, size_t bytes) { note(hipMemcpyAsync(p.host + off, p.dev + off, bytes, hipMemcpyDeviceToHost, next_stream())); };
     // every finished chunk travels at once: one copy per column (51 MB for C3).  Several chunks per copy were tried against the
     // spells at 45-50 instead of 56 GB/s this pool sometimes has, and changed nothing (profiles/r02_experiments.md)
-    for (int c0 = 0; c0 < p.n_chunks; ++c0) {
-        const int c1 = c0 + 1;
-        for (int c = c0; c < c1; ++c) {
-            while (!run_over && __atomic_load_n(&ctx->host_ready[c], __ATOMIC_ACQUIRE) == 0u) {
-                if (ctx->run_over.load(std::memory_order_acquire)) { run_over = true; break; }
-                std::this_thread::sleep_for(std::chrono::microseconds(20));
-            }
-            if (!run_over) ++ctx->streamed_chunks;
-            if (dbg && (c < 3 || c + 2 > p.n_chunks))
-                fprintf(stderr, "[simplyp] copier: chunk %d ready=%u over=%d at %.1f ms\n", c, ctx->host_ready[c], (int)run_over,
-                        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->t_begin).count());
+    for (int c = 0; c < t.n_chunks(); ++c) {
+        while (!run_over && __atomic_load_n(&ctx->host_ready[c], __ATOMIC_ACQUIRE) == 0u) {
+            if (ctx->run_over.load(std::memory_order_acquire)) { run_over = true; break; }
+            std::this_thread::sleep_for(std::chrono::microseconds(20));
         }
+        if (!run_over) ++ctx->streamed_chunks;
+        if (dbg && (c < 3 || c + 2 > t.n_chunks()))
+            fprintf(stderr, "[simplyp] copier: chunk %d ready=%u over=%d at %.1f ms\n", c, ctx->host_ready[c], (int)run_over,
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->t_begin).count());
         // a chunk whose flag never rose (the run ended in an error) has no valid counters: it travels raw
-        const bool chunk_packed = p.pack_dev && __atomic_load_n(&ctx->host_ready[c0], __ATOMIC_ACQUIRE) != 0u;
-        const size_t d0 = (size_t)c0 * p.chunk_days, nd = std::min<size_t>((size_t)(c1 - c0) * p.chunk_days, p.D - d0);
-        // (one plain copy per column: a pitched hipMemcpy2DAsync per chunk does not overlap the persistent kernel at all on this
-        // stack -- 1509 ms per pass instead of 803, profiles/r02_experiments.md)
-        bool raw_col[32] = {};
-        for (int j = 0; j < p.ncols; ++j) {
-            const size_t off = ((size_t)j * p.D + d0) * p.row_doubles;
-            if (chunk_packed) {
-                // the record instead of the rows: into the staging ring, and from there through the decode pool into p.host
-                const size_t rec = (size_t)c0 * p.ncols + j;
-                const unsigned count = ctx->host_pack_count[2 * rec], words = ctx->host_pack_count[2 * rec + 1];
-                const simplyp_pack::Layout L = simplyp_pack::layout(p.row_doubles, (int)nd, p.pack_cap);
-                // a column predicted from one that travels raw goes raw too: its decoder reads that column's rows from the host
-                // table, where a raw copy lands in no order with the pool
-                const int k = p.pack_pred[j];
-                raw_col[j] = simplyp_pack::travels_raw(L, count, words, p.pack_cap) || (k >= 0 && raw_col[k]);
-                if (!raw_col[j]) {
-                    simplyp_pack::PackJob job;
-                    job.dev_rec = p.pack_dev + rec * p.pack_stride;
-                    job.nd = (int)nd;
-                    job.L = L;
-                    job.copy_bytes = simplyp_pack::copy_bytes(L, words);
-                    job.dst = p.host + off;
-                    job.xdst = k >= 0 ? p.host + ((size_t)k * p.D + d0) * p.row_doubles : nullptr;
-                    job.stride = p.row_doubles;
-                    hipError_t err = ctx->pack.submit(job, ctx->copy_streams[n_issued++ % (unsigned)ctx->n_copy_streams]);
-                    if (err != hipSuccess && !ctx->copy_error) ctx->copy_error = (int)err;
-                    ++ctx->copy_plan.n_packed;
-                    ctx->copy_plan.n_overflow += count;
-                    ctx->copy_plan.packed_bytes += job.copy_bytes;
-                    continue;
-                }
-                ++ctx->copy_plan.n_raw; ++ctx->copy_plan.raw_of_col[j];       // too many wide blocks: this chunk-column travels as fp64, as below
-            }
-            // two streams, taken in turn: the launch gap of one copy dispatch hides behind the other stream's transfer
-            hipError_t err = hipMemcpyAsync(p.host + off, p.dev + off, nd * p.row_doubles * sizeof(double),
-                                            hipMemcpyDeviceToHost, ctx->copy_streams[n_issued++ % (unsigned)ctx->n_copy_streams]);
-            if (err != hipSuccess && !ctx->copy_error) ctx->copy_error = (int)err;
+        if (!p.pack_dev || __atomic_load_n(&ctx->host_ready[c], __ATOMIC_ACQUIRE) == 0u) {
+            for (int j = 0; j < t.n_cols; ++j) raw(t.offset(j, c), t.raw_bytes(c));
+            continue;
         }
+        // the records instead of the rows: into the staging ring, and from there through the decode pool into p.host
+        const uint32_t* count = ctx->host_pack_count + 2 * t.record(c, 0);
+        simplyp_pack::route_chunk(t, c, p.pack_dev, p.host, ctx->tally,
+                                  [&](int j, unsigned& overflow_blocks, size_t& words) { overflow_blocks = count[2 * j]; words = count[2 * j + 1]; },
+                                  [&](const simplyp_pack::PackJob& job) { note(ctx->pack.submit(job, next_stream())); }, raw);
     }
     hipError_t err = hipSuccess;
-    for (int i = 1; i < ctx->n_copy_streams && err == hipSuccess; ++i) {        // stream 0 joins the others, then signals
+    for (int i = 1; i < simplyp_ctx::N_COPY_STREAMS && err == hipSuccess; ++i) {        // stream 0 joins the others, then signals
         err = hipEventRecord(ctx->ev_copy_join[i], ctx->copy_streams[i]);
         if (err == hipSuccess) err = hipStreamWaitEvent(ctx->copy_stream, ctx->ev_copy_join[i], 0);
     }
     if (err == hipSuccess) err = hipEventRecord(ctx->ev_copy_done, ctx->copy_stream);
-    if (err != hipSuccess && !ctx->copy_error) ctx->copy_error = (int)err;
+    note(err);
 }
 
 int check_args(simplyp_ctx* ctx, const simplyp_dims* dims, const simplyp_opts* opts, const void* forcing, const int32_t* doy,
@@ -765,27 +731,29 @@ bool pack_wanted(const simplyp_opts& opts, const RunShape& shape, const simplyp:
     return PACK_AUTO_ON && copy_us > PACK_COPY_OVER_KERNEL * kernel_us;
 }
 
-// Buffers of a packed run: the device records, sized for their capacity, and their two counters each on the device and in
-// pinned host memory (zeroed); `extra_words` more device words follow the counters.
-// `stride` = 0 when the records do not fit the device's free memory: the run then streams raw.
-int ensure_pack_buffers(simplyp_ctx* ctx, size_t row_doubles, int chunk_days, int n_records, size_t& stride, unsigned& cap, int extra_words = 0)
+// Buffers of a packed table: the device records, sized for their capacity; their two counters each on the device and in pinned
+// host memory (zeroed); behind the device counters the table's predictor columns (uploaded).  All of it is enqueued on
+// ctx->stream.  `args` is what a packing kernel takes; its `buf` stays null when the records do not fit the device's free memory.
+int ensure_pack_buffers(simplyp_ctx* ctx, const simplyp_pack::Table& t, simplyp_pack::PackArgs& args)
 {
-    const size_t n_words = 2 * (size_t)n_records;
-    cap = simplyp_pack::overflow_capacity((int)((row_doubles + simplyp_pack::GROUP - 1) / simplyp_pack::GROUP));
-    stride = simplyp_pack::layout(row_doubles, chunk_days, cap).bytes;
-    const size_t bytes = (size_t)n_records * stride;
+    const size_t n_records = (size_t)t.n_chunks() * (size_t)t.n_cols, n_words = 2 * n_records, bytes = n_records * t.stride;
+    args = simplyp_pack::PackArgs{};
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
-    if (bytes > ctx->packed.bytes && bytes - ctx->packed.bytes > free_b / 10 * 9) { stride = 0; return SIMPLYP_OK; }
+    if (bytes > ctx->packed.bytes && bytes - ctx->packed.bytes > free_b / 10 * 9) return SIMPLYP_OK;
     if (int rc = ensure(ctx, ctx->packed, bytes)) return rc;
-    if (int rc = ensure(ctx, ctx->pack_count, (n_words + (size_t)extra_words) * sizeof(unsigned))) return rc;
+    if (int rc = ensure(ctx, ctx->pack_count, (n_words + (size_t)t.n_cols) * sizeof(unsigned))) return rc;
     if (n_words > ctx->host_pack_count_cap) {
         if (ctx->host_pack_count) { (void)hipHostFree(ctx->host_pack_count); ctx->host_pack_count = nullptr; ctx->host_pack_count_cap = 0; }
         HIP_TRY(ctx, hipHostMalloc((void**)&ctx->host_pack_count, n_words * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));
         ctx->host_pack_count_cap = n_words;
     }
     memset(ctx->host_pack_count, 0, n_words * sizeof(uint32_t));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->pack_count.ptr, 0, n_words * sizeof(unsigned), ctx->stream));
+    unsigned* count = (unsigned*)ctx->pack_count.ptr;
+    HIP_TRY(ctx, hipMemsetAsync(count, 0, n_words * sizeof(unsigned), ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(count + n_words, t.pred, (size_t)t.n_cols * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    args.buf = (unsigned char*)ctx->packed.ptr; args.count = count; args.host_count = ctx->host_pack_count;
+    args.stride = t.stride; args.cap = t.cap; args.cols = t.n_cols; args.pred = (const int*)(count + n_words);
     return SIMPLYP_OK;
 }
 
@@ -817,21 +785,8 @@ int launch_queue(simplyp_ctx* ctx, const simplyp_opts& opts, const RunShape& sha
     const size_t ints_bytes = (qi.size() * sizeof(int) + 255) / 256 * 256;
     if (int rc = ensure(ctx, ctx->queue, flags_bytes + ints_bytes + (size_t)S * simplyp::CKPT_N * E * sizeof(double))) return rc;
     if (route_bytes) { if (int rc = ensure(ctx, ctx->route, route_bytes)) return rc; }
-    char* base = (char*)ctx->queue.ptr;
-    HIP_TRY(ctx, hipMemsetAsync(base, 0, flags_bytes, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(base + flags_bytes, qi.data(), qi.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    simplyp::QueueArgs q;
-    unsigned* flags = (unsigned*)base;
-    const int* dq = (const int*)(base + flags_bytes);
-    q.ticket = flags; q.error = flags + 1; q.progress = flags + 2; q.done = flags + 4;
-    q.task_reach = dq; q.task_chunk = dq + pair_idx.size();
-    q.down_ptr = dq + off_dptr; q.down_idx = dq + off_didx;
-    q.ckpt = (double*)(base + flags_bytes + ints_bytes);
-    q.n_groups = G; q.n_pairs = (int)pair_idx.size(); q.chunk_days = chunk_days; q.ring_chunks = topo.ring_chunks;
-    q.chunk_count = nullptr; q.host_ready = nullptr; q.tasks_per_chunk = (unsigned)S * (unsigned)G;
-    q.pack_buf = nullptr; q.pack_count = nullptr; q.host_pack_count = nullptr; q.pack_stride = 0; q.pack_cap = 0; q.pack_cols = 0;
-    q.pack_pred_y = q.pack_pred_x = -1;
+    simplyp::QueueArgs q;                      // (q.pack: off)
+    q.chunk_count = nullptr; q.host_ready = nullptr;
     if (shape.stream_chunks) {
         if (int rc = ensure(ctx, ctx->chunk_count, (size_t)n_chunks * sizeof(unsigned))) return rc;
         if ((size_t)n_chunks > ctx->host_ready_cap) {
@@ -846,30 +801,31 @@ int launch_queue(simplyp_ctx* ctx, const simplyp_opts& opts, const RunShape& sha
         HIP_TRY(ctx, hipMemsetAsync(ctx->chunk_count.ptr, 0, (size_t)n_chunks * sizeof(unsigned), ctx->stream));
         q.chunk_count = (unsigned*)ctx->chunk_count.ptr;
         q.host_ready = ctx->host_ready;
-        ctx->copy_plan.n_chunks = n_chunks;
-        ctx->copy_plan.chunk_days = chunk_days;
+        // PP is almost a constant multiple of Msus: predicted from it when both are in the table.
+        // Columns are in ascending SIMPLYP_OUT_* order, so a column's place is the number of mask bits below its own.
+        int32_t pred[32];
+        for (int32_t& k : pred) k = -1;
+        const uint32_t bx = 1u << SIMPLYP_OUT_MSUS_FLUX, by = 1u << SIMPLYP_OUT_PP_FLUX;
+        if ((a.out_mask & bx) && (a.out_mask & by)) pred[popcount32(a.out_mask & (by - 1u))] = popcount32(a.out_mask & (bx - 1u));
+        simplyp_ctx::CopyPlan& cp = ctx->copy_plan;
+        cp.table = simplyp_pack::make_table(popcount32(a.out_mask), a.D, a.n_out_reaches * E, chunk_days, pred);
         if (pack_wanted(opts, shape, a)) {
-            const int ncols = popcount32(a.out_mask);
-            size_t stride = 0;
-            unsigned cap = 0;
-            if (int rc = ensure_pack_buffers(ctx, (size_t)E, chunk_days, n_chunks * ncols, stride, cap)) return rc;
-            if (stride) {
-                q.pack_buf = (unsigned char*)ctx->packed.ptr; q.pack_count = (unsigned*)ctx->pack_count.ptr;
-                q.host_pack_count = ctx->host_pack_count; q.pack_stride = stride; q.pack_cap = cap; q.pack_cols = ncols;
-                ctx->copy_plan.pack_dev = q.pack_buf; ctx->copy_plan.pack_stride = stride; ctx->copy_plan.pack_cap = cap;
-                // PP is almost a constant multiple of Msus: predicted from it when both are in the table.
-                // Columns are in ascending SIMPLYP_OUT_* order, so a column's place is the number of mask bits below its own.
-                for (int& k : ctx->copy_plan.pack_pred) k = -1;
-                for (int& k : ctx->copy_plan.raw_of_col) k = 0;
-                const uint32_t bx = 1u << SIMPLYP_OUT_MSUS_FLUX, by = 1u << SIMPLYP_OUT_PP_FLUX;
-                if ((a.out_mask & bx) && (a.out_mask & by)) {
-                    q.pack_pred_x = popcount32(a.out_mask & (bx - 1u));
-                    q.pack_pred_y = popcount32(a.out_mask & (by - 1u));
-                    ctx->copy_plan.pack_pred[q.pack_pred_y] = q.pack_pred_x;
-                }
-            }
+            if (int rc = ensure_pack_buffers(ctx, cp.table, q.pack)) return rc;
+            cp.pack_dev = q.pack.buf;
         }
     }
+    char* base = (char*)ctx->queue.ptr;
+    HIP_TRY(ctx, hipMemsetAsync(base, 0, flags_bytes, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(base + flags_bytes, qi.data(), qi.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned* flags = (unsigned*)base;
+    const int* dq = (const int*)(base + flags_bytes);
+    q.ticket = flags; q.error = flags + 1; q.progress = flags + 2; q.done = flags + 4;
+    q.task_reach = dq; q.task_chunk = dq + pair_idx.size();
+    q.down_ptr = dq + off_dptr; q.down_idx = dq + off_didx;
+    q.ckpt = (double*)(base + flags_bytes + ints_bytes);
+    q.n_groups = G; q.n_pairs = (int)pair_idx.size(); q.chunk_days = chunk_days; q.ring_chunks = topo.ring_chunks;
+    q.tasks_per_chunk = (unsigned)S * (unsigned)G;
     q.max_polls = 20000000u;      // x (s_sleep 64 ~ 2 us): ~40 s in which NO task of the run completed means something is broken
     if (const char* mp_env = getenv("SIMPLYP_QUEUE_MAX_POLLS")) q.max_polls = (unsigned)strtoul(mp_env, nullptr, 10);
     simplyp::KernelArgs k = a;
@@ -894,14 +850,12 @@ int launch_queue(simplyp_ctx* ctx, const simplyp_opts& opts, const RunShape& sha
 int arm_copy(simplyp_ctx* ctx, double* host_out, const simplyp_opts& opts, const simplyp::KernelArgs& a, bool chunked)
 {
     simplyp_ctx::CopyPlan& cp = ctx->copy_plan;
-    cp.dev = a.out; cp.host = host_out;
-    cp.ncols = popcount32(a.out_mask);
-    cp.D = (size_t)(opts.n_periods > 0 ? opts.n_periods : a.D);
-    cp.row_doubles = (size_t)a.n_out_reaches * a.E;
+    cp.dev = a.out; cp.host = host_out; cp.chunked = chunked;
     if (chunked) {
         if (cp.pack_dev) {
             // ring, dispatcher and decode pool first (the ring is allocated, and so first touched, by the calling thread)
-            hipError_t err = ctx->pack.start(ctx->device, cp.row_doubles, cp.pack_stride, cp.n_chunks * cp.ncols, simplyp_pack::decode_threads());
+            hipError_t err = ctx->pack.start(ctx->device, (size_t)cp.table.E, cp.table.stride, cp.table.n_chunks() * cp.table.n_cols,
+                                             simplyp_pack::decode_threads());
             if (err != hipSuccess) {
                 ctx->pack.finish();
                 return fail(ctx, SIMPLYP_ERR_NOMEM, "packed output stream: the pinned staging ring failed: %s", hipGetErrorString(err));
@@ -911,7 +865,9 @@ int arm_copy(simplyp_ctx* ctx, double* host_out, const simplyp_opts& opts, const
         ctx->copier = std::thread(copier_main, ctx);       // chunk by chunk, beside the kernel
     } else {
         // no time chunks in this run (chain kernel, RK4, time-reduced rows): the whole table follows the last launch
-        HIP_TRY(ctx, hipMemcpyAsync(host_out, a.out, cp.ncols * cp.D * cp.row_doubles * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        const size_t rows = (size_t)(opts.n_periods > 0 ? opts.n_periods : a.D);
+        HIP_TRY(ctx, hipMemcpyAsync(host_out, a.out, (size_t)popcount32(a.out_mask) * rows * (size_t)a.n_out_reaches * (size_t)a.E * sizeof(double),
+                                    hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipEventRecord(ctx->ev_copy_done, ctx->stream));
     }
     ctx->copy_pending = true;
@@ -1103,8 +1059,7 @@ static int run_async_body(simplyp_ctx* ctx, const simplyp_dims* dims, const simp
         return rc;
     ctx->t_begin = std::chrono::steady_clock::now();
     ctx->copy_pending = false; ctx->copy_error = 0; ctx->streamed_chunks = 0;
-    ctx->copy_plan.n_chunks = 0; ctx->copy_plan.pack_dev = nullptr;
-    ctx->copy_plan.n_packed = ctx->copy_plan.n_raw = 0; ctx->copy_plan.n_overflow = 0; ctx->copy_plan.packed_bytes = 0;
+    ctx->copy_plan = simplyp_ctx::CopyPlan{}; ctx->tally = simplyp_pack::Tally{};
     const int E = dims->E, S = dims->S, D = dims->D;
     Schedule sch;
     int rc = build_schedule(ctx, S, up_ptr, up_idx, sch);
@@ -1227,12 +1182,12 @@ static int sync_impl(simplyp_ctx* ctx, simplyp_stats* stats)
             return fail(ctx, SIMPLYP_ERR_DEVICE, "streamed output: a device-to-host copy failed: %s", hipGetErrorString((hipError_t)ctx->copy_error));
         HIP_TRY(ctx, hipEventSynchronize(ctx->ev_copy_done));
         HIP_TRY(ctx, hipEventElapsedTime(&ms_tail, ctx->ev_stop, ctx->ev_copy_done));
-        if (ctx->last.queued && ctx->copy_plan.n_chunks > 0) {
+        if (ctx->copy_plan.chunked) {
             // chunked run: the rate the table travelled at
             float ms_run = 0.f;
             HIP_TRY(ctx, hipEventElapsedTime(&ms_run, ctx->ev_main, ctx->ev_copy_done));
-            const simplyp_ctx::CopyPlan& cp = ctx->copy_plan;
-            const double bytes = (double)cp.ncols * (double)cp.D * (double)cp.row_doubles * sizeof(double);
+            const simplyp_pack::Table& t = ctx->copy_plan.table;
+            const double bytes = (double)t.n_cols * (double)t.rows * (double)t.E * sizeof(double);
             stream_gbs = ms_run > 0.f ? bytes / (ms_run * 1e-3) / 1e9 : 0.0;
         }
     }
@@ -1246,10 +1201,10 @@ static int sync_impl(simplyp_ctx* ctx, simplyp_stats* stats)
                         "%llu polls (bound: SIMPLYP_QUEUE_MAX_POLLS); results are incomplete", c[6]);
     }
     if (copied && ctx->copy_plan.pack_dev && getenv("SIMPLYP_DEBUG"))
-        fprintf(stderr, "[simplyp] packed stream: %d records packed (%zu bytes on the link), %d raw\n", ctx->copy_plan.n_packed,
-                ctx->copy_plan.packed_bytes, ctx->copy_plan.n_raw);
-    if (copied && ctx->copy_plan.pack_dev && ctx->copy_plan.n_raw && getenv("SIMPLYP_DEBUG"))
-        for (int j = 0; j < ctx->copy_plan.ncols; ++j) fprintf(stderr, "[simplyp] packed stream: column %d: %d raw\n", j, ctx->copy_plan.raw_of_col[j]);
+        fprintf(stderr, "[simplyp] packed stream: %d records packed (%zu bytes on the link), %d raw\n", ctx->tally.n_packed,
+                ctx->tally.link_bytes, ctx->tally.n_raw);
+    if (copied && ctx->copy_plan.pack_dev && ctx->tally.n_raw && getenv("SIMPLYP_DEBUG"))
+        for (int j = 0; j < ctx->copy_plan.table.n_cols; ++j) fprintf(stderr, "[simplyp] packed stream: column %d: %d raw\n", j, ctx->tally.raw_of_col[j]);
     if (stats) {
         float ms = 0.f, ms_pilot = 0.f;
         HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_main, ctx->ev_stop));
@@ -1267,8 +1222,8 @@ static int sync_impl(simplyp_ctx* ctx, simplyp_stats* stats)
         stats->queue_waits = ctx->last.queued ? c[4] : 0;
         stats->queue_longest_wait_polls = ctx->last.queued ? (uint32_t)c[5] : 0;
         if (copied && ctx->copy_plan.pack_dev) {
-            stats->packed_records = (int32_t)(((uint32_t)ctx->copy_plan.n_raw << 16) | ((uint32_t)ctx->copy_plan.n_packed & 0xFFFFu));
-            stats->pack_overflow_blocks = ctx->copy_plan.n_overflow;
+            stats->packed_records = (int32_t)(((uint32_t)ctx->tally.n_raw << 16) | ((uint32_t)ctx->tally.n_packed & 0xFFFFu));
+            stats->pack_overflow_blocks = ctx->tally.n_overflow;
         }
         stats->queue_longest_stall_polls = ctx->last.queued ? c[6] : 0;
         stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->t_begin).count();
@@ -1306,15 +1261,7 @@ int simplyp_stream_out(simplyp_ctx* ctx, double* host_out, int64_t host_bytes)
 
 // simplyp_fetch_packed: the table is packed by one wave per (chunk, 64-double group), then every record takes the copier's and
 // the decode pool's path of a packed run (raw records are copied from the table, as there).
-// pred_col (may be NULL = all -1): per column -1 or an EARLIER column it is predicted from -- records travel in column order,
-// and a decode thread needs its rows of that column in the host table first.
-static bool pred_cols_ok(const int32_t* pred_col, int32_t n_cols)
-{
-    for (int j = 0; pred_col && j < n_cols; ++j)
-        if (pred_col[j] < -1 || pred_col[j] >= j) return false;
-    return n_cols <= 32;
-}
-
+// pred_col: simplyp_pack::pred_cols_ok.
 static int fetch_packed_impl(simplyp_ctx* ctx, const double* dev_table, int32_t n_cols, int32_t rows, int32_t row_doubles,
                              int32_t chunk_days, const int32_t* pred_col, double* host_out, int64_t host_bytes, int32_t* counts,
                              int64_t* bytes)
@@ -1323,69 +1270,47 @@ static int fetch_packed_impl(simplyp_ctx* ctx, const double* dev_table, int32_t 
     if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "a run is pending on this context; call simplyp_sync first");
     if (!dev_table || !host_out || n_cols <= 0 || rows <= 0 || row_doubles <= 0 || chunk_days <= 0)
         return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_fetch_packed: bad table arguments");
-    if (!pred_cols_ok(pred_col, n_cols))
+    if (!simplyp_pack::pred_cols_ok(pred_col, n_cols))
         return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_fetch_packed: at most 32 columns, and pred_col[j] must be -1 or a column before j");
     const size_t table_bytes = (size_t)n_cols * rows * row_doubles * sizeof(double);
     if (host_bytes < (int64_t)table_bytes)
         return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_fetch_packed: host buffer of %lld bytes is smaller than the table (%zu)", (long long)host_bytes, table_bytes);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int chunk = (chunk_days + 63) / 64 * 64, n_chunks = (rows + chunk - 1) / chunk;
-    const int G = (row_doubles + simplyp_pack::GROUP - 1) / simplyp_pack::GROUP, n_rec = n_chunks * n_cols;
-    if (n_chunks > 65535) return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_fetch_packed: more than 65535 chunks");
-    size_t stride = 0;
-    unsigned cap = 0;
-    if (int rc = ensure_pack_buffers(ctx, (size_t)row_doubles, chunk, n_rec, stride, cap, n_cols)) return rc;
-    if (!stride) return fail(ctx, SIMPLYP_ERR_NOMEM, "simplyp_fetch_packed: the packed records do not fit the device's free memory");
-    int pred[32];
-    for (int j = 0; j < n_cols; ++j) pred[j] = pred_col ? pred_col[j] : -1;
-    int* dev_pred = (int*)ctx->pack_count.ptr + 2 * (size_t)n_rec;
-    HIP_TRY(ctx, hipMemcpyAsync(dev_pred, pred, (size_t)n_cols * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(simplyp::simplyp_pack_table_kernel, dim3((unsigned)G, (unsigned)n_chunks), dim3(simplyp::WAVE), 0, ctx->stream, dev_table,
-                       n_cols, rows, row_doubles, chunk, (unsigned char*)ctx->packed.ptr, (unsigned*)ctx->pack_count.ptr,
-                       (unsigned long long)stride, cap, (const int*)dev_pred);
+    const simplyp_pack::Table t = simplyp_pack::make_table(n_cols, rows, row_doubles, (chunk_days + 63) / 64 * 64, pred_col);
+    const int n_rec = t.n_chunks() * n_cols;
+    if (t.n_chunks() > 65535) return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_fetch_packed: more than 65535 chunks");
+    simplyp_pack::PackArgs args;
+    if (int rc = ensure_pack_buffers(ctx, t, args)) return rc;
+    if (!args.buf) return fail(ctx, SIMPLYP_ERR_NOMEM, "simplyp_fetch_packed: the packed records do not fit the device's free memory");
+    hipLaunchKernelGGL(simplyp::simplyp_pack_table_kernel, dim3((unsigned)((row_doubles + simplyp_pack::GROUP - 1) / simplyp_pack::GROUP), (unsigned)t.n_chunks()),
+                       dim3(simplyp::WAVE), 0, ctx->stream, dev_table, rows, row_doubles, t.chunk_days, args);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->host_pack_count, ctx->pack_count.ptr, 2 * (size_t)n_rec * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->host_pack_count, args.count, 2 * (size_t)n_rec * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    hipError_t err = ctx->pack.start(ctx->device, (size_t)row_doubles, stride, n_rec, simplyp_pack::decode_threads());
-    int n_packed = 0, n_raw = 0;
-    unsigned n_overflow = 0, n_issued = 0;
-    int64_t link_bytes = 0;
-    for (int c = 0; c < n_chunks && err == hipSuccess; ++c) {
-        const size_t d0 = (size_t)c * chunk, nd = std::min<size_t>((size_t)chunk, (size_t)rows - d0);
-        const simplyp_pack::Layout L = simplyp_pack::layout((size_t)row_doubles, (int)nd, cap);
-        bool raw_col[32] = {};
-        for (int j = 0; j < n_cols && err == hipSuccess; ++j) {
-            const size_t rec = (size_t)c * n_cols + j, off = ((size_t)j * rows + d0) * row_doubles;
-            const unsigned count = ctx->host_pack_count[2 * rec], words = ctx->host_pack_count[2 * rec + 1];
-            hipStream_t st = ctx->copy_streams[n_issued++ % (unsigned)ctx->n_copy_streams];
-            raw_col[j] = simplyp_pack::travels_raw(L, count, words, cap) || (pred[j] >= 0 && raw_col[pred[j]]);     // (as the copier)
-            if (!raw_col[j]) {
-                simplyp_pack::PackJob job;
-                job.dev_rec = (const unsigned char*)ctx->packed.ptr + rec * stride;
-                job.nd = (int)nd;
-                job.L = L;
-                job.copy_bytes = simplyp_pack::copy_bytes(L, words);
-                job.dst = host_out + off;
-                job.xdst = pred[j] >= 0 ? host_out + ((size_t)pred[j] * rows + d0) * row_doubles : nullptr;
-                job.stride = (size_t)row_doubles;
-                err = ctx->pack.submit(job, st);
-                ++n_packed; n_overflow += count;
-                link_bytes += (int64_t)job.copy_bytes;
-            } else {
-                err = hipMemcpyAsync(host_out + off, dev_table + off, nd * row_doubles * sizeof(double), hipMemcpyDeviceToHost, st);
-                ++n_raw;
-            }
-        }
+    hipError_t err = ctx->pack.start(ctx->device, (size_t)row_doubles, t.stride, n_rec, simplyp_pack::decode_threads());
+    simplyp_pack::Tally tally;
+    unsigned n_issued = 0;
+    // the copier's path: the same two streams in turn, and nothing more once a call has failed
+    auto next_stream = [&] { return ctx->copy_streams[n_issued++ % (unsigned)simplyp_ctx::N_COPY_STREAMS]; };
+    for (int c = 0; c < t.n_chunks(); ++c) {
+        const uint32_t* count = ctx->host_pack_count + 2 * t.record(c, 0);
+        simplyp_pack::route_chunk(
+            t, c, args.buf, host_out, tally,
+            [&](int j, unsigned& overflow_blocks, size_t& words) { overflow_blocks = count[2 * j]; words = count[2 * j + 1]; },
+            [&](const simplyp_pack::PackJob& job) { if (err == hipSuccess) err = ctx->pack.submit(job, next_stream()); },
+            [&](size_t off, size_t bytes) {
+                if (err == hipSuccess) err = hipMemcpyAsync(host_out + off, dev_table + off, bytes, hipMemcpyDeviceToHost, next_stream());
+            });
     }
-    for (int i = 0; i < ctx->n_copy_streams; ++i) {
+    for (int i = 0; i < simplyp_ctx::N_COPY_STREAMS; ++i) {
         hipError_t e2 = hipStreamSynchronize(ctx->copy_streams[i]);
         if (err == hipSuccess) err = e2;
     }
     ctx->pack.finish();
     if (err == hipSuccess && ctx->pack.error()) err = (hipError_t)ctx->pack.error();
     if (err != hipSuccess) return fail(ctx, SIMPLYP_ERR_DEVICE, "simplyp_fetch_packed: %s", hipGetErrorString(err));
-    if (counts) { counts[0] = n_packed; counts[1] = (int32_t)n_overflow; counts[2] = n_raw; }
-    if (bytes) { bytes[0] = link_bytes; bytes[1] = (int64_t)n_packed * row_doubles * (int64_t)sizeof(double); }
+    if (counts) { counts[0] = tally.n_packed; counts[1] = (int32_t)tally.n_overflow; counts[2] = tally.n_raw; }
+    if (bytes) { bytes[0] = (int64_t)tally.link_bytes; bytes[1] = (int64_t)tally.n_packed * row_doubles * (int64_t)sizeof(double); }
     return SIMPLYP_OK;
 }
 
@@ -1407,43 +1332,35 @@ static int pack_roundtrip_host_impl(const double* table, int32_t n_cols, int32_t
 {
     if (!table || !out || n_cols <= 0 || rows <= 0 || row_doubles <= 0 || chunk_days <= 0)
         return fail(nullptr, SIMPLYP_ERR_ARG, "simplyp_pack_roundtrip_host: bad table arguments");
-    if (!pred_cols_ok(pred_col, n_cols))
+    if (!simplyp_pack::pred_cols_ok(pred_col, n_cols))
         return fail(nullptr, SIMPLYP_ERR_ARG, "simplyp_pack_roundtrip_host: at most 32 columns, and pred_col[j] must be -1 or a column before j");
-    const size_t E = (size_t)row_doubles;
-    const int chunk = (chunk_days + 63) / 64 * 64, n_chunks = (rows + chunk - 1) / chunk;
-    const unsigned cap = simplyp_pack::overflow_capacity((int)((E + simplyp_pack::GROUP - 1) / simplyp_pack::GROUP));
-    std::vector<unsigned char> rec(simplyp_pack::layout(E, chunk, cap).bytes);
-    int n_packed = 0, n_raw = 0;
-    unsigned n_overflow = 0;
-    int64_t link_bytes = 0;
+    const simplyp_pack::Table t = simplyp_pack::make_table(n_cols, rows, row_doubles, (chunk_days + 63) / 64 * 64, pred_col);
+    const size_t E = (size_t)row_doubles, G = (E + simplyp_pack::GROUP - 1) / simplyp_pack::GROUP;
+    std::vector<unsigned char> rec(t.stride);       // one record at a time: encoded when the router asks for its counters
+    simplyp_pack::Tally tally;
     constexpr size_t RANGES = 3;    // the decoder works on member ranges of whole blocks, as the pool's threads do
-    const size_t G = (E + simplyp_pack::GROUP - 1) / simplyp_pack::GROUP;
     simplyp_pack::FpDefault fp;     // (the decode threads hold one each)
     (void)fp;
-    for (int c = 0; c < n_chunks; ++c) {
-        const size_t d0 = (size_t)c * chunk;
-        const int nd = (int)std::min<size_t>((size_t)chunk, (size_t)rows - d0);
-        const simplyp_pack::Layout L = simplyp_pack::layout(E, nd, cap);
-        bool raw_col[32] = {};
-        for (int j = 0; j < n_cols; ++j) {
-            const size_t off = ((size_t)j * rows + d0) * E;
-            const int k = pred_col ? pred_col[j] : -1;
-            const size_t xoff = k >= 0 ? ((size_t)k * rows + d0) * E : 0;
-            uint64_t cnt[2];
-            simplyp_pack::encode_record_host(table + off, k >= 0 ? table + xoff : nullptr, E, nd, E, rec.data(), L, cnt);
-            raw_col[j] = simplyp_pack::travels_raw(L, (unsigned)cnt[0], (size_t)cnt[1], cap) || (k >= 0 && raw_col[k]);
-            if (raw_col[j]) { memcpy(out + off, table + off, (size_t)nd * E * sizeof(double)); ++n_raw; continue; }
-            for (size_t t = 0; t < RANGES; ++t) {
-                const size_t e0 = G * t / RANGES * simplyp_pack::GROUP, e1 = std::min(E, G * (t + 1) / RANGES * simplyp_pack::GROUP);
-                if (e1 > e0) simplyp_pack::decode_range(rec.data(), L, nd, E, e0, e1, out + off, k >= 0 ? out + xoff : nullptr, E);
-            }
-            __builtin_ia32_sfence();
-            ++n_packed; n_overflow += (unsigned)cnt[0];
-            link_bytes += (int64_t)simplyp_pack::copy_bytes(L, (size_t)cnt[1]);
-        }
-    }
-    if (counts) { counts[0] = n_packed; counts[1] = (int32_t)n_overflow; counts[2] = n_raw; }
-    if (bytes) { bytes[0] = link_bytes; bytes[1] = (int64_t)n_packed * (int64_t)E * (int64_t)sizeof(double); }
+    for (int c = 0; c < t.n_chunks(); ++c)
+        simplyp_pack::route_chunk(
+            t, c, nullptr, out, tally,
+            [&](int j, unsigned& overflow_blocks, size_t& words) {
+                const int k = t.pred[j];
+                uint64_t cnt[2];
+                simplyp_pack::encode_record_host(table + t.offset(j, c), k >= 0 ? table + t.offset(k, c) : nullptr, E, t.days(c), E, rec.data(),
+                                                 t.layout_of(c), cnt);
+                overflow_blocks = (unsigned)cnt[0]; words = (size_t)cnt[1];
+            },
+            [&](const simplyp_pack::PackJob& job) {
+                for (size_t r = 0; r < RANGES; ++r) {
+                    const size_t e0 = G * r / RANGES * simplyp_pack::GROUP, e1 = std::min(E, G * (r + 1) / RANGES * simplyp_pack::GROUP);
+                    if (e1 > e0) simplyp_pack::decode_range(rec.data(), job.L, job.nd, E, e0, e1, job.dst, job.xdst, job.stride);
+                }
+                __builtin_ia32_sfence();
+            },
+            [&](size_t off, size_t bytes) { memcpy(out + off, table + off, bytes); });
+    if (counts) { counts[0] = tally.n_packed; counts[1] = (int32_t)tally.n_overflow; counts[2] = tally.n_raw; }
+    if (bytes) { bytes[0] = (int64_t)tally.link_bytes; bytes[1] = (int64_t)tally.n_packed * (int64_t)E * (int64_t)sizeof(double); }
     return SIMPLYP_OK;
 }
 

@@ -1893,14 +1893,8 @@ struct QueueArgs {
     unsigned tasks_per_chunk;  // S * n_groups
     // packed output stream (simplyp_pack.h; eligible runs only: one reach, one lane per member, 64 slots per wave, lane slots
     // contiguous in the table).  The wave packs the rows of its own task into record (chunk, column) before it releases the task;
-    // the wave that completes a chunk hands the records' counters to the host beside the chunk's flag.  nullptr = off.
-    unsigned char* pack_buf;   // [n_chunks][pack_cols] records, pack_stride bytes apart
-    unsigned* pack_count;      // [n_chunks][pack_cols][2] device: overflow blocks and body words per record
-    unsigned* host_pack_count; // the same, host-pinned
-    unsigned long long pack_stride;
-    unsigned pack_cap;         // overflow blocks a record may hold
-    int pack_cols;
-    int pack_pred_y, pack_pred_x;   // table column pack_pred_y is predicted from column pack_pred_x (PP from Msus); -1: none
+    // the wave that completes a chunk hands the records' counters to the host beside the chunk's flag.
+    simplyp_pack::PackArgs pack;
 };
 
 // Wait until *flag >= need.  Executed by the whole wave on a wave-uniform address (the 64 identical loads are
@@ -1982,15 +1976,8 @@ __global__ __launch_bounds__(WAVE, 1) void simplyp_queue_kernel(const KernelArgs
             run_slot<INTEG, SNOW, TEAM, STIFF>(a, s_P, s_E, s_T, s_doy, lane, slot_of_lane(a, g, lane), q.task_reach + pair, 1, d_begin, d_end,
                                    q.ckpt + (size_t)s * CKPT_N * (size_t)a.E, s_tab);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (q.pack_buf) {                 // (wave-uniform) the rows just written, still in cache, as row-adaptive deltas
-                const int nd = d_end - d_begin;
-                const simplyp_pack::Layout L = simplyp_pack::layout((size_t)a.E, nd, q.pack_cap);
-                for (int j = 0; j < q.pack_cols; ++j) {
-                    const size_t rec = (size_t)c * (size_t)q.pack_cols + (size_t)j;
-                    const double* x = j == q.pack_pred_y ? a.out + ((size_t)q.pack_pred_x * (size_t)a.D + (size_t)d_begin) * (size_t)a.E : nullptr;
-                    simplyp_pack::pack_block(a.out + ((size_t)j * (size_t)a.D + (size_t)d_begin) * (size_t)a.E, x, (size_t)a.E, nd, a.E, g, lane,
-                                             q.pack_buf + rec * q.pack_stride, L, q.pack_count + 2 * rec, s_pack);
-                }
+            if (q.pack.buf) {                 // (wave-uniform) the rows just written, still in cache, as row-adaptive deltas
+                simplyp_pack::pack_chunk(a.out, a.D, a.E, d_begin, d_end - d_begin, g, lane, q.pack, c, s_pack);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -2008,10 +1995,10 @@ __global__ __launch_bounds__(WAVE, 1) void simplyp_queue_kernel(const KernelArgs
                 old = (unsigned)__builtin_amdgcn_readfirstlane((int)old);
                 if (old + 1u == q.tasks_per_chunk && lane == 0) {
                     // (every task of the chunk added to its records' counters before its release, as above)
-                    if (q.pack_buf)
-                        for (int j = 0; j < 2 * q.pack_cols; ++j) {
-                            const size_t w = (size_t)c * 2 * (size_t)q.pack_cols + (size_t)j;
-                            q.host_pack_count[w] = __hip_atomic_load(&q.pack_count[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (q.pack.buf)
+                        for (int j = 0; j < 2 * q.pack.cols; ++j) {
+                            const size_t w = (size_t)c * 2 * (size_t)q.pack.cols + (size_t)j;
+                            q.pack.host_count[w] = __hip_atomic_load(&q.pack.count[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         }
                     __hip_atomic_store(&q.host_ready[c], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
                 }
@@ -2030,23 +2017,13 @@ __global__ __launch_bounds__(WAVE, 1) void simplyp_queue_kernel(const KernelArgs
 }
 
 // simplyp_fetch_packed: one wave per (time chunk, 64-member group) packs that block of every column of a caller's table
-// [n_cols][rows][row_doubles] with the device function the task-queue kernel uses.  pred_col: [n_cols], -1 or the column a column
-// is predicted from.
-__global__ __launch_bounds__(WAVE) void simplyp_pack_table_kernel(const double* table, int n_cols, int rows, int row_doubles, int chunk_days,
-                                                                  unsigned char* pack_buf, unsigned* pack_count, unsigned long long pack_stride,
-                                                                  unsigned pack_cap, const int* pred_col)
+// [pack.cols][rows][row_doubles] with the device function the task-queue kernel uses.
+__global__ __launch_bounds__(WAVE) void simplyp_pack_table_kernel(const double* table, int rows, int row_doubles, int chunk_days,
+                                                                  const simplyp_pack::PackArgs pack)
 {
     __shared__ unsigned long long s_pack[simplyp_pack::LDS_WORDS];
-    const int c = blockIdx.y, g = blockIdx.x, lane = threadIdx.x;
-    const int d_begin = c * chunk_days, nd = min(rows, d_begin + chunk_days) - d_begin;
-    const simplyp_pack::Layout L = simplyp_pack::layout((size_t)row_doubles, nd, pack_cap);
-    for (int j = 0; j < n_cols; ++j) {
-        const size_t rec = (size_t)c * (size_t)n_cols + (size_t)j;
-        const int k = __builtin_amdgcn_readfirstlane(pred_col[j]);
-        const double* x = k >= 0 ? table + ((size_t)k * (size_t)rows + (size_t)d_begin) * (size_t)row_doubles : nullptr;
-        simplyp_pack::pack_block(table + ((size_t)j * (size_t)rows + (size_t)d_begin) * (size_t)row_doubles, x, (size_t)row_doubles, nd, row_doubles,
-                                 g, lane, pack_buf + rec * pack_stride, L, pack_count + 2 * rec, s_pack);
-    }
+    const int c = blockIdx.y, d_begin = c * chunk_days;
+    simplyp_pack::pack_chunk(table, rows, row_doubles, d_begin, min(rows, d_begin + chunk_days) - d_begin, blockIdx.x, threadIdx.x, pack, c, s_pack);
 }
 
 // Gather the columns of a [rows][E] array into lane-slot order: dst[r][i] = src[r][perm[i]].  One pass over the

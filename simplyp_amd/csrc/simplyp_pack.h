@@ -64,7 +64,7 @@ SIMPLYP_PACK_HD inline unsigned overflow_capacity(int n_groups) { return (unsign
 struct Layout {
     size_t off_dir, dir_stride, off_widths;   // directory: bytes from the start of the record, bytes per entry, widths inside an entry
     size_t off_body;
-    size_t body_cap_words;                    // what the body may hold: 7 bytes per value and cap raw blocks, as round 6's record
+    size_t body_cap_words;                    // what the body may hold: 7 bytes per value and `cap` blocks of raw fp64
     size_t bytes;                             // whole record at capacity, padding included (a multiple of 256)
     int rows, n_spans;                        // delta rows, spans of them
 };
@@ -91,6 +91,42 @@ SIMPLYP_PACK_HD inline size_t copy_bytes(const Layout& L, size_t words) { return
 SIMPLYP_PACK_HD inline bool travels_raw(const Layout& L, unsigned overflow_blocks, size_t words, unsigned cap)
 {
     return overflow_blocks > cap || words > L.body_cap_words;
+}
+
+// A [n_cols][rows][E] fp64 table cut into chunks of `chunk_days` rows (the last one may be shorter), and its records: record
+// (c, j) is chunk c of column j, records lie `stride` bytes apart in chunk-major order.
+struct Table {
+    int n_cols, rows, chunk_days, E;
+    unsigned cap;                             // overflow blocks a record may hold
+    size_t stride;                            // bytes between records: a full chunk's record at capacity
+    int pred[32];                             // per column: the EARLIER column it is predicted from, or -1 (previous day)
+
+    SIMPLYP_PACK_HD int n_chunks() const { return (rows + chunk_days - 1) / chunk_days; }
+    SIMPLYP_PACK_HD int first_day(int c) const { return c * chunk_days; }
+    SIMPLYP_PACK_HD int days(int c) const { return rows - first_day(c) < chunk_days ? rows - first_day(c) : chunk_days; }
+    SIMPLYP_PACK_HD size_t record(int c, int j) const { return (size_t)c * (size_t)n_cols + (size_t)j; }
+    SIMPLYP_PACK_HD size_t offset(int j, int c) const { return ((size_t)j * (size_t)rows + (size_t)first_day(c)) * (size_t)E; }   // doubles
+    SIMPLYP_PACK_HD size_t raw_bytes(int c) const { return (size_t)days(c) * (size_t)E * sizeof(double); }    // a column's rows of chunk c
+    SIMPLYP_PACK_HD Layout layout_of(int c) const { return layout((size_t)E, days(c), cap); }
+};
+
+// Records travel in column order and a decode thread needs its rows of the predictor column in the host table first: pred_col
+// (may be NULL = all -1) holds -1 or a column before j, for at most 32 columns.
+SIMPLYP_PACK_HD inline bool pred_cols_ok(const int32_t* pred_col, int n_cols)
+{
+    for (int j = 0; pred_col && j < n_cols; ++j)
+        if (pred_col[j] < -1 || pred_col[j] >= j) return false;
+    return n_cols <= 32;
+}
+
+SIMPLYP_PACK_HD inline Table make_table(int n_cols, int rows, int E, int chunk_days, const int32_t* pred_col)
+{
+    Table t;
+    t.n_cols = n_cols; t.rows = rows; t.chunk_days = chunk_days; t.E = E;
+    t.cap = overflow_capacity((E + GROUP - 1) / GROUP);
+    t.stride = layout((size_t)E, chunk_days, t.cap).bytes;
+    for (int j = 0; j < 32; ++j) t.pred[j] = (pred_col && j < n_cols) ? pred_col[j] : -1;
+    return t;
 }
 
 #if defined(__HIPCC__)
@@ -217,6 +253,32 @@ __device__ __forceinline__ void pack_block(const double* rows, const double* xro
         }
     }
     if (__ballot(big != 0ull) != 0ull && lane == 0) atomicAdd(count, 1u);
+}
+
+// What a packing kernel knows of a run's records (Table's device half); `buf` null = the run does not pack.
+struct PackArgs {
+    unsigned char* buf = nullptr;             // [n_chunks][cols] records, `stride` bytes apart
+    unsigned* count = nullptr;                // [n_chunks][cols][2] device: overflow blocks and body words per record
+    unsigned* host_count = nullptr;           // the same, host-pinned (the task-queue kernel hands a finished chunk's counters over)
+    unsigned long long stride = 0;
+    unsigned cap = 0;                         // overflow blocks a record may hold
+    int cols = 0;
+    const int* pred = nullptr;                // [cols] device: Table::pred
+    SIMPLYP_PACK_HD Layout layout_of(int E, int nd) const { return layout((size_t)E, nd, cap); }     // = Table::layout_of(c)
+};
+
+// One wavefront packs its block g of chunk c -- `nd` rows from d_begin on -- of every column of a [cols][rows][E] table.
+__device__ __forceinline__ void pack_chunk(const double* table, int rows, int E, int d_begin, int nd, int g, int lane, const PackArgs& args,
+                                           int c, unsigned long long* lds)
+{
+    const Layout L = args.layout_of(E, nd);
+    for (int j = 0; j < args.cols; ++j) {
+        const size_t rec = (size_t)c * (size_t)args.cols + (size_t)j;
+        const int k = __builtin_amdgcn_readfirstlane(args.pred[j]);
+        const double* x = k >= 0 ? table + ((size_t)k * (size_t)rows + (size_t)d_begin) * (size_t)E : nullptr;
+        pack_block(table + ((size_t)j * (size_t)rows + (size_t)d_begin) * (size_t)E, x, (size_t)E, nd, E, g, lane,
+                   args.buf + rec * args.stride, L, args.count + 2 * rec, lds);
+    }
 }
 #endif
 

@@ -106,6 +106,48 @@ struct PackJob {
     int slot = 0;
 };
 
+struct Tally {
+    int n_packed = 0, n_raw = 0;              // records routed packed / raw
+    unsigned n_overflow = 0;                  // overflow blocks of the packed ones
+    size_t link_bytes = 0;                    // what the packed ones put on the link
+    int raw_of_col[32] = {};                  // records routed raw, per column
+};
+
+// Packed or raw, for every record of chunk `c` in column order -- the one place that decides it.  counters(j, overflow_blocks,
+// words) hands over record (c, j)'s two counters.  A record travels raw when its own counters say so (travels_raw), and when the
+// column it is predicted from travels raw in this chunk: its decoder reads that column's rows from the host table, where a raw
+// copy lands in no order with the decode pool.  Per column either packed(job) -- the record at `dev_recs` (null: the caller
+// keeps the record itself) to the columns of the table at `host` -- or raw(offset in doubles, bytes) of that table.
+template <class Counters, class Packed, class Raw>
+void route_chunk(const Table& t, int c, const unsigned char* dev_recs, double* host, Tally& tally, Counters&& counters, Packed&& packed,
+                 Raw&& raw)
+{
+    const Layout L = t.layout_of(c);
+    bool is_raw[32] = {};
+    for (int j = 0; j < t.n_cols; ++j) {
+        unsigned overflow_blocks = 0;
+        size_t words = 0;
+        counters(j, overflow_blocks, words);
+        const int k = t.pred[j];
+        is_raw[j] = travels_raw(L, overflow_blocks, words, t.cap) || (k >= 0 && is_raw[k]);
+        if (is_raw[j]) {
+            ++tally.n_raw; ++tally.raw_of_col[j];
+            raw(t.offset(j, c), t.raw_bytes(c));
+            continue;
+        }
+        PackJob job;
+        job.dev_rec = dev_recs ? dev_recs + t.record(c, j) * t.stride : nullptr;
+        job.L = L;
+        job.nd = t.days(c);
+        job.copy_bytes = copy_bytes(L, words);
+        job.dst = host + t.offset(j, c);
+        job.xdst = k >= 0 ? host + t.offset(k, c) : nullptr;
+        job.stride = (size_t)t.E;
+        ++tally.n_packed; tally.n_overflow += overflow_blocks; tally.link_bytes += job.copy_bytes;
+        packed(job);
+    }
+}
+
 class PackStream {
 public:
     static constexpr size_t RING_MAX = (size_t)1 << 30;

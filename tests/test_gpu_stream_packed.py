@@ -1,7 +1,7 @@
-"""The packed output stream (SIMPLYP_STREAM_PACK, simplyp_pack.h): the daily table crosses the link as 7-byte day-to-day
-deltas and is decoded on the host.  Whatever path a (time chunk, column) record takes -- packed, packed with raw overflow blocks,
-or raw because its overflow area is full -- the host table is the device table bit for bit, and the counters say which path it
-was.  Runs the pack epilogue does not handle ignore the switch."""
+"""The packed output stream (SIMPLYP_STREAM_PACK, simplyp_pack.h): the daily table crosses the link as records of row-adaptive
+day-to-day deltas and is decoded on the host.  Whatever path a (time chunk, column) record takes -- packed, packed with overflow
+blocks (rows wider than 56 bits), or raw because it holds too many of them -- the host table is the device table bit for bit,
+and the counters say which path it was.  Runs the pack epilogue does not handle ignore the switch."""
 
 import ctypes as C
 
@@ -35,7 +35,7 @@ def made_up_table():
     Column 0: a smooth base whose deltas need <= 52 bits.  Group 0 carries what a delta cannot hold in 56 bits -- sign flips
     every day, +0 / -0 alternating, +inf / -inf, NaNs with changing payloads, a denormal against a normal -- so its block
     overflows in every chunk.  Group 1 has a single jump of 2^57 (member 70, day 80): one more overflow block, in chunk 1 only.
-    Group 2 has specials that stay put or move slowly and must come through the planes: NaNs with payloads, infinities, zeros,
+    Group 2 has specials that stay put or move slowly and must come through the packed rows: NaNs with payloads, infinities, zeros,
     growing denormals.  Expected: 3 records packed, 1 + 2 + 1 = 4 overflow blocks.
     Column 1: the first member of every group flips its sign every day, so every block of every chunk overflows: 4 > 3, all three
     records come back raw."""
@@ -55,7 +55,7 @@ def made_up_table():
     u[0, :, 4] = np.where(d % np.uint64(2) == 0, np.uint64(5), np.uint64(0x3FF0000000000005))      # a denormal against a normal
     # column 0, group 1: one jump of 2^57 in the pattern, kept from there on
     u[0, 80:, 70] += np.uint64(1) << np.uint64(57)
-    # column 0, group 2: specials that fit the planes
+    # column 0, group 2: specials whose deltas fit 56 bits
     u[0, :, 130] = np.uint64(0x7FF8000000ABCDEF)                                     # a NaN payload that stays
     u[0, :, 131] = np.uint64(0xFFF0000000000000)                                     # -inf
     u[0, :, 132] = sign                                                              # -0

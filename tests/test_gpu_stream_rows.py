@@ -9,7 +9,7 @@ import pytest
 
 from simplyp_amd import engine, marshal
 from test_gpu_stream_packed import FULL_WAVES, made_up_table, perturbed, run
-from test_pack_rows_host import U, f2u, predictor_table, roundtrip, smooth
+from test_pack_rows_host import U, dependency_table, f2u, predictor_table, roundtrip, smooth
 
 CHUNK = 64
 
@@ -40,6 +40,7 @@ TABLES = {
     'widths': (width_table, None),
     'predictor': (predictor_table, [-1, 0]),
     'exact_multiple': (exact_multiple_table, [-1, 0]),
+    'dependency': (dependency_table, [-1, 0, -1]),                   # column 0 raw by its counters, column 1 raw because of it
     'one_member': (lambda: np.ascontiguousarray(predictor_table()[:, :, 100:101]), [-1, 0]),
     'two_spans': (lambda: smooth(np.random.default_rng(2), 2, 130, 65), [-1, 0]),      # 128-day chunks: two spans of rows
 }

@@ -162,6 +162,32 @@ def test_exact_multiple_has_width_zero():
     assert nbytes[0] == only_x[0] + record_overhead(E, rows)
 
 
+def dependency_table(overflowing=True):
+    """[3, 130, 200], 64-day chunks: 4 blocks, so a record may hold 4 / 8 + 3 = 3 overflow blocks.  Column 0: member 64 * g of
+    every block alternates daily between 1.5 and 1.5 * 2**200 -- every block overflows in every chunk, 4 > 3 (`overflowing`
+    False: those members stay at 1.5).  Column 1 = 0.25 * column 0 exactly: coded against column 0 its differences are all zero,
+    so its own counters are clean.  Column 2 is smooth."""
+    rng = np.random.default_rng(31)
+    rows, E = 130, 200
+    x = rng.uniform(0.5, 50.0, (rows, E))
+    for g in range(4):
+        x[:, 64 * g] = np.where(np.arange(rows) % 2 == 1, 1.5 * 2.0 ** 200, 1.5) if overflowing else 1.5
+    return np.stack([f2u(x), f2u(0.25 * x), smooth(rng, 1, rows, E)[0]])
+
+
+def test_column_predicted_from_a_raw_column_travels_raw():
+    """Column 1 can only be raw by the dependency rule: a decoder that read column 0's rows from the host table while a raw
+    copy of them is still on its way would read half-written rows."""
+    u = dependency_table()
+    out, counts, nbytes = roundtrip(u, pred=[-1, 0, -1])
+    assert np.array_equal(out, u)
+    assert counts == [3, 0, 6]                                           # column 2's three records; columns 0 and 1 raw
+    assert nbytes[1] == 3 * 200 * 8
+    quiet = dependency_table(overflowing=False)
+    out, counts, _ = roundtrip(quiet, pred=[-1, 0, -1])
+    assert np.array_equal(out, quiet) and counts == [9, 0, 0]
+
+
 def test_round_trip_with_ftz_daz_in_the_caller():
     """The codec resets MXCSR for itself: a caller that flushes denormals gets the same records and the same table."""
     import platform

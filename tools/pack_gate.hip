@@ -2,7 +2,7 @@
 // the whole table, the pinned staging ring, a device buffer of packed records -- random bits under a valid directory whose row
 // widths are each column's mean on the model's table (51, 51, 52, 52 bits, and 38 for the last column,
 // which is decoded against the third with the ratio predictor) --, the real schedule
-// (two copy streams taken in turn, one record per chunk-column, the library's dispatcher and decode pool from
+// (two copy streams taken in turn, one record per chunk-column, the library's router, dispatcher and decode pool from
 // simplyp_pack_stream.h), against the raw copies of the same table in the same session.
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I simplyp_amd/csrc -o pack_gate tools/pack_gate.hip -lpthread
@@ -36,12 +36,13 @@ __global__ void fill_kernel(unsigned long long* p, size_t n)
 }
 
 // A valid directory for every block of every record: one span, every row `w` bits wide, blocks in order.
-__global__ void directory_kernel(unsigned char* dev, size_t stride, int n_rec, int n_cols, int G, simplyp_pack::Layout L, const int* width_of_col)
+__global__ void directory_kernel(unsigned char* dev, simplyp_pack::Table t, int G, const int* width_of_col)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)n_rec * G) return;
-    const int rec = (int)(i / G), g = (int)(i % G), w = width_of_col[rec % n_cols];
-    unsigned char* dir = dev + (size_t)rec * stride + L.off_dir + (size_t)g * L.dir_stride;
+    if (i >= (size_t)t.n_chunks() * t.n_cols * G) return;
+    const int rec = (int)(i / G), g = (int)(i % G), w = width_of_col[rec % t.n_cols];
+    const simplyp_pack::Layout L = t.layout_of(rec / t.n_cols);
+    unsigned char* dir = dev + (size_t)rec * t.stride + L.off_dir + (size_t)g * L.dir_stride;
     *(uint32_t*)dir = (uint32_t)((size_t)g * L.rows * w);
     for (int r = 0; r < L.rows; ++r) dir[L.off_widths + r] = (unsigned char)w;
 }
@@ -56,13 +57,17 @@ int main(int argc, char** argv)
     const int n_cols = argc > 3 ? atoi(argv[3]) : 5;
     const int chunk = argc > 4 ? atoi(argv[4]) : 64;
     const int repeats = argc > 5 ? atoi(argv[5]) : 3;
-    const int G = (int)((E + GROUP - 1) / GROUP), n_chunks = (int)((D + chunk - 1) / chunk), n_rec = n_chunks * n_cols;
-    const unsigned cap = overflow_capacity(G);
-    const size_t stride = layout(E, chunk, cap).bytes, table_bytes = (size_t)n_cols * D * E * sizeof(double);
-    size_t dev_bytes = (size_t)n_rec * stride;
+    // PP (the fifth column) against Msus (the third)
+    int32_t pred[32];
+    for (int j = 0; j < 32; ++j) pred[j] = j == 4 ? 2 : -1;
+    if (n_cols < 1 || n_cols > 32) { fprintf(stderr, "1 .. 32 columns\n"); return 1; }
+    const Table t = make_table(n_cols, (int)D, (int)E, chunk, pred);
+    const int G = (int)((E + GROUP - 1) / GROUP), n_chunks = t.n_chunks(), n_rec = n_chunks * n_cols;
+    const size_t table_bytes = (size_t)n_cols * D * E * sizeof(double);
+    size_t dev_bytes = (size_t)n_rec * t.stride;
     if (dev_bytes < table_bytes) dev_bytes = table_bytes;
     printf("shape: %zu members x %zu days x %d columns, %d-day chunks: %d records of %.1f MB (overflow capacity %u blocks), table %.2f GB\n",
-           E, D, n_cols, chunk, n_rec, stride / 1e6, cap, table_bytes / 1e9);
+           E, D, n_cols, chunk, n_rec, t.stride / 1e6, t.cap, table_bytes / 1e9);
 
     unsigned char* dev = nullptr;
     double* host = nullptr;
@@ -72,15 +77,13 @@ int main(int argc, char** argv)
     if (!getenv("PACK_GATE_NO_BIND")) printf("main thread bound to the GPU's NUMA node: %d (-1 = not bound)\n", simplyp_pack::bind_thread_to_gpu_node(0));
     CHECK(hipMalloc((void**)&dev, dev_bytes));
     hipLaunchKernelGGL(fill_kernel, dim3(4096), dim3(256), 0, 0, (unsigned long long*)dev, dev_bytes / 8);
-    // (the last, shorter chunk keeps the directory of a full one: its decoder reads fewer rows of it)
     const int widths[5] = {51, 51, 52, 52, 38};
     std::vector<int> width_of_col((size_t)n_cols);
     for (int j = 0; j < n_cols; ++j) width_of_col[(size_t)j] = widths[j % 5];
     int* dev_widths = nullptr;
     CHECK(hipMalloc((void**)&dev_widths, (size_t)n_cols * sizeof(int)));
     CHECK(hipMemcpy(dev_widths, width_of_col.data(), (size_t)n_cols * sizeof(int), hipMemcpyHostToDevice));
-    const Layout L_full = layout(E, chunk, cap);
-    hipLaunchKernelGGL(directory_kernel, dim3((unsigned)(((size_t)n_rec * G + 255) / 256)), dim3(256), 0, 0, dev, stride, n_rec, n_cols, G, L_full, dev_widths);
+    hipLaunchKernelGGL(directory_kernel, dim3((unsigned)(((size_t)n_rec * G + 255) / 256)), dim3(256), 0, 0, dev, t, G, dev_widths);
     CHECK(hipDeviceSynchronize());
     double t0 = now_s();
     CHECK(hipHostMalloc((void**)&host, table_bytes, hipHostMallocDefault));
@@ -93,13 +96,9 @@ int main(int argc, char** argv)
     for (int r = 0; r < repeats; ++r) {
         t0 = now_s();
         unsigned n = 0;
-        for (int c = 0; c < n_chunks; ++c) {
-            const size_t d0 = (size_t)c * chunk, nd = std::min<size_t>(chunk, D - d0);
-            for (int j = 0; j < n_cols; ++j) {
-                const size_t off = ((size_t)j * D + d0) * E;
-                CHECK(hipMemcpyAsync(host + off, (const double*)dev + off, nd * E * sizeof(double), hipMemcpyDeviceToHost, streams[n++ % 2]));
-            }
-        }
+        for (int c = 0; c < n_chunks; ++c)
+            for (int j = 0; j < n_cols; ++j)
+                CHECK(hipMemcpyAsync(host + t.offset(j, c), (const double*)dev + t.offset(j, c), t.raw_bytes(c), hipMemcpyDeviceToHost, streams[n++ % 2]));
         for (hipStream_t s : streams) CHECK(hipStreamSynchronize(s));
         const double dt = now_s() - t0;
         printf("| raw fp64 | %d | %.1f | %.2f | %.2f | - |\n", r, dt * 1e3, table_bytes / dt / 1e9, table_bytes / 1e9);
@@ -113,24 +112,21 @@ int main(int argc, char** argv)
         const int T = modes[mi];
         ps.set_spin(mi == 1);
         for (int r = 0; r < repeats; ++r) {
-            CHECK(ps.start(0, E, stride, n_rec, T));
+            CHECK(ps.start(0, E, t.stride, n_rec, T));
             ps.take_packed_bytes();
             t0 = now_s();
             unsigned n = 0;
-            for (int c = 0; c < n_chunks; ++c) {
-                const size_t d0 = (size_t)c * chunk, nd = std::min<size_t>(chunk, D - d0);
-                for (int j = 0; j < n_cols; ++j) {
-                    PackJob job;
-                    job.dev_rec = dev + (size_t)(c * n_cols + j) * stride;
-                    job.nd = (int)nd;
-                    job.L = L_full;
-                    job.copy_bytes = copy_bytes(L_full, (size_t)G * (size_t)(nd - 1) * (size_t)width_of_col[(size_t)j]);
-                    job.dst = host + ((size_t)j * D + d0) * E;
-                    if (j == 4) job.xdst = host + ((size_t)2 * D + d0) * E;                // PP against Msus
-                    job.stride = E;
-                    CHECK(ps.submit(job, streams[n++ % 2]));
-                }
-            }
+            Tally tally;
+            hipError_t err = hipSuccess;
+            // the library's router on synthetic counters: no overflow blocks, a cursor that is the column's width in every row
+            for (int c = 0; c < n_chunks; ++c)
+                route_chunk(t, c, dev, host, tally,
+                            [&](int j, unsigned& overflow_blocks, size_t& words) {
+                                overflow_blocks = 0; words = (size_t)G * (size_t)(t.days(c) - 1) * (size_t)width_of_col[(size_t)j];
+                            },
+                            [&](const PackJob& job) { if (err == hipSuccess) err = ps.submit(job, streams[n++ % 2]); },
+                            [&](size_t, size_t) { if (err == hipSuccess) err = hipErrorInvalidValue; });     // (no width passes the capacity)
+            CHECK(err);
             for (hipStream_t s : streams) CHECK(hipStreamSynchronize(s));
             const double t_link = now_s() - t0;
             ps.finish();
