@@ -29,7 +29,8 @@ extern "C" {
  * 17 still with the packed output stream, for the same reason: simplyp_fetch_packed and simplyp_pack_roundtrip_host are new
  * entry points, and simplyp_stats keeps its size and every offset -- reserved0 (always 0 before) is now packed_records, and
  * the upper half of queue_longest_wait_polls (a 32-bit count on the device: always 0 before) is now pack_overflow_blocks.
- * 17 still with simplyp_fetch_packed_pred and simplyp_pack_roundtrip_host_pred: two more entry points, nothing else. */
+ * 17 still with simplyp_fetch_packed_pred and simplyp_pack_roundtrip_host_pred: two more entry points, nothing else.
+ * 17 still with simplyp_time_quantiles, simplyp_tq_info and SIMPLYP_TQ_DERIVED: one more entry point with its own info struct. */
 #define SIMPLYP_ABI_VERSION 17
 
 typedef enum {
@@ -586,6 +587,58 @@ int simplyp_quantiles(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double*
                       const double* q /* host [K] */, int32_t K,
                       double* order_stats /* device [2][K][n_rows]: lower, upper */,
                       simplyp_quantile_info* info);
+
+/* ---- order statistics per member over time: what a user of the reference gets from one DataFrame.quantile() call on the
+ * frames run_simply_p returns -- the flow-duration curve (Q95, Q50, Q10), annual maxima (q = 1), the annual 90th percentile
+ * of a concentration, the same for a season only -- for every member of an ensemble, from the table on the device ---------- */
+#define SIMPLYP_TQ_DERIVED 64   /* series id = SIMPLYP_OUT_* (a column in out_mask) or SIMPLYP_TQ_DERIVED + SIMPLYP_GOF_* */
+
+typedef struct {
+    double  kernel_ms;     /* the selection kernel, HIP events on the context's stream                                  */
+    int64_t bytes_read;    /* bytes of the table all sweeps loaded (512 per wave and day row, idle lanes included)       */
+    int32_t n_sweeps;      /* the most sweeps over its period's days any (64 members, period, series, reach) needed      */
+    int32_t n_periods;     /* max(n_periods, 1)                                                                          */
+} simplyp_tq_info;
+
+/*
+ * simplyp_time_quantiles -- exact order statistics along the DAY axis of the daily table a previous simplyp_run left on the
+ * device, for every (series, period, output reach, member).  With n = the period's participating days (the same for all
+ * members) and h = q[k] * (n - 1) in fp64: k_lo = floor(h), k_hi = min(k_lo + 1, n - 1), and the outputs are the k_lo-th and
+ * k_hi-th smallest values of the member's series over those days -- numpy's method='linear' indices; the caller interpolates
+ * with gamma = h - floor(h).  Exact selection: every output is an element of the series, the one np.sort puts at that index.
+ * NaN sorts after +inf as in np.sort; -0.0 and +0.0 compare equal, either may come back.  A period without days gives NaN.
+ * The table is only read; device workspace is a few bytes per day and probability, whatever E and the table's size.
+ * Results are deterministic bit for bit.
+ *
+ *   dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot   as for simplyp_gof (daily rows); D == 0 succeeds
+ *                   (every output NaN)
+ *   f_tdp           device  [E] member order, and
+ *   reach_params    device  as in the run (row SIMPLYP_PR_A_CATCH): read only when a derived series is asked for, else NULL
+ *   series          HOST    [n_series], 1 <= n_series <= 32: SIMPLYP_OUT_c = column c of the table as it stands (must be
+ *                           in out_mask), or SIMPLYP_TQ_DERIVED + SIMPLYP_GOF_v = the df_R series Q_cumecs, SS_mgl, TDP_mgl,
+ *                           PP_mgl, TP_mgl, SRP_mgl of the reach (model.py:784-793, :842-845), computed on the fly with the
+ *                           reference's operations one for one: Qr*A*1000/86400, (flux/Qr)/A, TDP+PP, TDP*f_TDP (out_mask
+ *                           must contain Qr and the three fluxes)
+ *   period_of_day   HOST    [D] in [-1, n_periods): -1 = the day takes part in no period (seasons); the non-negative
+ *                           entries must not decrease.  NULL (n_periods 0) = one period holding every day
+ *   q, K            HOST    [K] probabilities in [0, 1], 1 <= K <= 16
+ *   order_stats     device  [2][K][n_series][max(n_periods, 1)][n_out_reaches][E]: plane 0 = x_(k_lo), plane 1 = x_(k_hi);
+ *                           member axis in the order of `out`'s (slots when the run wrote slot order), as simplyp_waterbody
+ *   n_days          HOST    [max(n_periods, 1)] the periods' participating days, or NULL
+ *   info            host    may be NULL
+ * Synchronous, on the context's stream.  SIMPLYP_ERR_ARG (nothing launched) for K outside 1..16, a q outside [0, 1] or NaN,
+ * a series that is not in the mask, a derived series whose mask lacks Qr or a flux or with NULL f_tdp / reach_params, a
+ * period_of_day that decreases or leaves [-1, n_periods), n_series outside 1..32, NULL out / q / order_stats / series.
+ */
+int simplyp_time_quantiles(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                           const int32_t* out_reaches, int32_t n_out_reaches,
+                           const double* out, const int32_t* member_of_slot,
+                           const double* f_tdp, const double* reach_params,
+                           const int32_t* series /* host [n_series] */, int32_t n_series,
+                           const int32_t* period_of_day /* host [D] or NULL */, int32_t n_periods,
+                           const double* q /* host [K] */, int32_t K,
+                           double* order_stats, int32_t* n_days /* host or NULL */,
+                           simplyp_tq_info* info);
 
 /*
  * simplyp_eval_units -- the path's scalar device functions on caller-given arguments, one thread per row: how the tests pin the

@@ -72,6 +72,17 @@ class QuantileInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class TqInfo(C.Structure):
+    """simplyp_tq_info of include/simplyp.h."""
+    _fields_ = [('kernel_ms', C.c_double), ('bytes_read', C.c_int64), ('n_sweeps', C.c_int32), ('n_periods', C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+TQ_DERIVED = 64                                                                       # SIMPLYP_TQ_DERIVED
+TQ_DERIVED_SERIES = ['Q_cumecs', 'SS_mgl', 'TDP_mgl', 'PP_mgl', 'TP_mgl', 'SRP_mgl']  # df_R names, in SIMPLYP_GOF_* order
+
 # SIMPLYP_WB_*: the reference's df_summed columns in its order (model.py:866, :886-888, :842-845)
 WB_COLUMNS = ['Q_cumecs', 'Msus_kg/day', 'TDP_kg/day', 'PP_kg/day', 'SS_mgl', 'TDP_mgl', 'PP_mgl',
               'TP_mgl', 'TP_kg/day', 'SRP_mgl', 'SRP_kg/day']

@@ -21,6 +21,7 @@
 #include "simplyp_gof.hip.h"
 #include "simplyp_waterbody.hip.h"
 #include "simplyp_quantile.hip.h"
+#include "simplyp_time_quantile.hip.h"
 #include "simplyp_pack_stream.h"
 
 namespace {
@@ -47,6 +48,7 @@ struct simplyp_ctx {
     DeviceBuf gof_lists;      // goodness-of-fit day lists, observations, shifts (simplyp_gof)
     DeviceBuf gof_partial;    // [n_chunks][R][78][E] partial sums
     DeviceBuf quant;          // simplyp_quantiles: 2 x int32 (members used, sweeps) | [E] uint8 include mask in column order
+    DeviceBuf tquant;         // simplyp_time_quantiles: sweeps, rows read | day lists, ranks, output reaches
     DeviceBuf queue;          // ticket, error, done[n_groups] (uint32) | ckpt[CKPT_N][E] (double)
     // streamed output (simplyp_stream_out): the armed destination, the chunk flags the queue kernel raises in pinned host
     // memory, and the host thread that turns a raised flag into the D2H copies of that chunk's rows on `copy_stream`
@@ -975,6 +977,7 @@ void simplyp_ctx_destroy(simplyp_ctx* ctx)
     if (ctx->gof_lists.ptr) (void)hipFree(ctx->gof_lists.ptr);
     if (ctx->gof_partial.ptr) (void)hipFree(ctx->gof_partial.ptr);
     if (ctx->quant.ptr) (void)hipFree(ctx->quant.ptr);
+    if (ctx->tquant.ptr) (void)hipFree(ctx->tquant.ptr);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
     if (ctx->ev_main) (void)hipEventDestroy(ctx->ev_main);
@@ -1825,6 +1828,166 @@ int simplyp_quantiles(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double*
                       const double* q, int32_t K, double* order_stats, simplyp_quantile_info* info)
 {
     SIMPLYP_GUARD(ctx, quantiles_impl(ctx, E, n_rows, table, member_of_slot, include, q, K, order_stats, info))
+}
+
+static int time_quantiles_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                               const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
+                               const double* f_tdp, const double* reach_params,
+                               const int32_t* series, int32_t n_series, const int32_t* period_of_day, int32_t n_periods,
+                               const double* q, int32_t K, double* order_stats, int32_t* n_days, simplyp_tq_info* info)
+{
+    const char* me = "simplyp_time_quantiles";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a run is pending on this context; call simplyp_sync first", me);
+    if (!dims || dims->E < 1 || dims->S < 1 || dims->D < 0)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: bad dims (E and S must be >= 1, D >= 0)", me);
+    if (K < 1 || K > simplyp::TQ_MAX_K) return fail(ctx, SIMPLYP_ERR_ARG, "%s: K must be in [1, %d] (got %d)", me, simplyp::TQ_MAX_K, (int)K);
+    if (!out || !q || !order_stats) return fail(ctx, SIMPLYP_ERR_ARG, "%s: out, q and order_stats must not be NULL", me);
+    for (int k = 0; k < K; ++k)
+        if (!(q[k] >= 0.0 && q[k] <= 1.0))
+            return fail(ctx, SIMPLYP_ERR_ARG, "%s: q[%d] = %g is not a probability in [0, 1]", me, k, q[k]);
+    if (n_series < 1 || n_series > simplyp::TQ_MAX_SERIES || !series)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_series must be in [1, %d] (got %d) and series not NULL", me, simplyp::TQ_MAX_SERIES, (int)n_series);
+    if (out_mask == 0u || (out_mask & ~(SIMPLYP_MASK_ALL | SIMPLYP_MASK_D_SNOW)) != 0u)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: out_mask must select 1..%d of the columns", me, (int)SIMPLYP_N_OUT);
+    const int E = dims->E, S = dims->S, D = dims->D;
+    const int R = out_reaches ? n_out_reaches : S;
+    if (R <= 0 || R > S) return fail(ctx, SIMPLYP_ERR_ARG, "%s: bad n_out_reaches", me);
+    for (int r = 0; r < R; ++r)
+        if (out_reaches && (out_reaches[r] < 0 || out_reaches[r] >= S)) return fail(ctx, SIMPLYP_ERR_ARG, "%s: out_reaches[%d] out of range", me, r);
+    simplyp::TqArgs g{};
+    static const int flux_cols[4] = {SIMPLYP_OUT_QR, SIMPLYP_OUT_MSUS_FLUX, SIMPLYP_OUT_TDP_FLUX, SIMPLYP_OUT_PP_FLUX};
+    const uint32_t need = (1u << flux_cols[0]) | (1u << flux_cols[1]) | (1u << flux_cols[2]) | (1u << flux_cols[3]);
+    bool derived = false;
+    for (int i = 0; i < n_series; ++i) {
+        const int id = series[i];
+        if (id >= 0 && id < SIMPLYP_N_OUT) {
+            if (!((out_mask >> id) & 1u)) return fail(ctx, SIMPLYP_ERR_ARG, "%s: series[%d] = column %d is not in out_mask", me, i, id);
+            g.series[i] = popcount32(out_mask & ((1u << id) - 1u));
+        } else if (id >= SIMPLYP_TQ_DERIVED && id < SIMPLYP_TQ_DERIVED + SIMPLYP_N_GOF_VARS) {
+            if ((out_mask & need) != need)
+                return fail(ctx, SIMPLYP_ERR_ARG, "%s: series[%d] is derived: out_mask must contain Qr, Msus_kg/day, TDP_kg/day and PP_kg/day", me, i);
+            if (!f_tdp || !reach_params) return fail(ctx, SIMPLYP_ERR_ARG, "%s: series[%d] is derived: f_tdp and reach_params must not be NULL", me, i);
+            g.series[i] = -1 - (id - SIMPLYP_TQ_DERIVED);
+            derived = true;
+        } else {
+            return fail(ctx, SIMPLYP_ERR_ARG, "%s: series[%d] = %d is neither a column nor SIMPLYP_TQ_DERIVED + a variable", me, i, id);
+        }
+    }
+    if (n_periods < 0 || (!period_of_day && n_periods > 1) || (period_of_day && n_periods < 1))
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: period_of_day needs n_periods >= 1; without it n_periods is 0 (or 1)", me);
+    const int P = std::max<int>(n_periods, 1);
+    // the periods' day lists (period_of_day's non-negative entries do not decrease: a period is a day range with holes)
+    std::vector<int32_t> day_ptr(P + 1, 0), days;
+    days.reserve((size_t)D);
+    if (!period_of_day) {
+        for (int d = 0; d < D; ++d) days.push_back(d);
+        day_ptr[1] = D;
+    } else {
+        int last = 0;
+        std::vector<int32_t> count(P, 0);
+        for (int d = 0; d < D; ++d) {
+            const int p = period_of_day[d];
+            if (p < -1 || p >= P) return fail(ctx, SIMPLYP_ERR_ARG, "%s: period_of_day[%d] = %d is outside [-1, %d)", me, d, p, P);
+            if (p < 0) continue;
+            if (p < last) return fail(ctx, SIMPLYP_ERR_ARG, "%s: period_of_day decreases at day %d (%d after %d)", me, d, p, last);
+            last = p;
+            days.push_back(d);
+            ++count[p];
+        }
+        for (int p = 0; p < P; ++p) day_ptr[p + 1] = day_ptr[p] + count[p];
+    }
+    if ((long long)n_series * R > 65535) return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_series * n_out_reaches must not exceed 65535", me);
+    if (n_days) for (int p = 0; p < P; ++p) n_days[p] = day_ptr[p + 1] - day_ptr[p];
+    if (info) { info->kernel_ms = 0.0; info->bytes_read = 0; info->n_sweeps = 0; info->n_periods = P; }
+
+    // ranks per period: k_lo, k_hi of every probability, ascending without repeats (rows padded with their last rank)
+    const int T = 2 * K;
+    std::vector<int32_t> ranks((size_t)P * T, 0);
+    std::vector<uint8_t> rank_of((size_t)P * T, 0);
+    for (int p = 0; p < P; ++p) {
+        const long long n = day_ptr[p + 1] - day_ptr[p];
+        if (n <= 0) continue;
+        long long want[2 * simplyp::TQ_MAX_K];
+        for (int k = 0; k < K; ++k) {                          // numpy's 'linear' indices
+            const double h = q[k] * (double)(n - 1);
+            long long lo = (long long)std::floor(h);
+            lo = std::min<long long>(std::max<long long>(lo, 0), n - 1);
+            want[k] = lo;
+            want[K + k] = std::min<long long>(lo + 1, n - 1);
+        }
+        std::vector<long long> u(want, want + T);
+        std::sort(u.begin(), u.end());
+        u.erase(std::unique(u.begin(), u.end()), u.end());
+        for (int t = 0; t < T; ++t) ranks[(size_t)p * T + t] = (int32_t)u[std::min<size_t>(t, u.size() - 1)];
+        for (int k = 0; k < T; ++k)
+            rank_of[(size_t)p * T + k] = (uint8_t)(std::lower_bound(u.begin(), u.end(), want[k]) - u.begin());
+    }
+
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const long long n_out = 2LL * K * n_series * P * R * E;
+    if (days.empty()) {                                        // no day takes part in any period (D = 0 among them): all NaN
+        hipLaunchKernelGGL(simplyp::quantile_fill_nan_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, ctx->stream, order_stats, n_out);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return SIMPLYP_OK;
+    }
+    // device workspace: 16 bytes of counters, then the int32 lists and the byte map -- O(D K), whatever E and the table's size
+    std::vector<int32_t> ints;
+    ints.insert(ints.end(), days.begin(), days.end());
+    const size_t o_ptr = ints.size();
+    ints.insert(ints.end(), day_ptr.begin(), day_ptr.end());
+    const size_t o_ranks = ints.size();
+    ints.insert(ints.end(), ranks.begin(), ranks.end());
+    const size_t o_reach = ints.size();
+    for (int r = 0; r < R; ++r) ints.push_back(out_reaches ? out_reaches[r] : r);
+    const size_t int_bytes = ints.size() * sizeof(int32_t);
+    if (int rc = ensure(ctx, ctx->tquant, 16 + int_bytes + rank_of.size())) return rc;
+    char* base = (char*)ctx->tquant.ptr;
+    int32_t* d_ints = (int32_t*)(base + 16);
+    HIP_TRY(ctx, hipMemsetAsync(base, 0, 16, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_ints, ints.data(), int_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(base + 16 + int_bytes, rank_of.data(), rank_of.size(), hipMemcpyHostToDevice, ctx->stream));
+
+    g.E = E; g.R = R; g.D = D; g.K = K; g.T = T; g.n_series = n_series; g.n_periods = P;
+    g.out = out; g.col_stride = (long long)D * R * E;
+    for (int i = 0; i < 4; ++i) g.col[i] = popcount32(out_mask & ((1u << flux_cols[i]) - 1u));
+    g.member_of_slot = member_of_slot;
+    g.f_tdp = f_tdp;
+    g.a_catch = derived ? reach_params + (size_t)SIMPLYP_PR_A_CATCH * S * E : nullptr;
+    g.day = d_ints; g.day_ptr = d_ints + o_ptr; g.ranks = d_ints + o_ranks; g.reach_of = d_ints + o_reach;
+    g.rank_of = (const uint8_t*)(base + 16 + int_bytes);
+    g.order_stats = order_stats;
+    g.rows_read = (unsigned long long*)base;
+    g.n_sweeps = (int*)(base + 8);
+    const dim3 grid((unsigned)((E + 63) / 64), (unsigned)std::min(P, 65535), (unsigned)(n_series * R));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    // the per-rank state of 8 ranks (K <= 4) leaves room for two workgroups' histograms per CU; 32 ranks for one
+    if (T <= 8) hipLaunchKernelGGL(simplyp::simplyp_time_quantile_kernel<8>, grid, dim3(64), 0, ctx->stream, g);
+    else hipLaunchKernelGGL(simplyp::simplyp_time_quantile_kernel<32>, grid, dim3(64), 0, ctx->stream, g);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+    unsigned long long counters[2] = {0ull, 0ull};
+    HIP_TRY(ctx, hipMemcpyAsync(counters, base, 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (info) {
+        float ms = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+        info->kernel_ms = ms;
+        info->bytes_read = (int64_t)(counters[0] * 512ull);
+        info->n_sweeps = (int32_t)(counters[1] & 0xFFFFFFFFull);
+    }
+    return SIMPLYP_OK;
+}
+
+int simplyp_time_quantiles(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                           const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
+                           const double* f_tdp, const double* reach_params,
+                           const int32_t* series, int32_t n_series, const int32_t* period_of_day, int32_t n_periods,
+                           const double* q, int32_t K, double* order_stats, int32_t* n_days, simplyp_tq_info* info)
+{
+    SIMPLYP_GUARD(ctx, time_quantiles_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
+                                           series, n_series, period_of_day, n_periods, q, K, order_stats, n_days, info))
 }
 
 void* simplyp_host_alloc(int64_t bytes)

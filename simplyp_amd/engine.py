@@ -28,7 +28,8 @@ ABI_SYMBOLS = ['simplyp_abi_version', 'simplyp_device_count', 'simplyp_ctx_creat
                'simplyp_device_alloc', 'simplyp_device_free', 'simplyp_memcpy_h2d', 'simplyp_memcpy_d2h', 'simplyp_gof',
                'simplyp_stream_out', 'simplyp_waterbody', 'simplyp_gof_waterbody', 'simplyp_gof_spearman', 'simplyp_eval_units',
                'simplyp_quantiles', 'simplyp_state_bytes', 'simplyp_set_state', 'simplyp_fetch_packed',
-               'simplyp_pack_roundtrip_host', 'simplyp_fetch_packed_pred', 'simplyp_pack_roundtrip_host_pred']
+               'simplyp_pack_roundtrip_host', 'simplyp_fetch_packed_pred', 'simplyp_pack_roundtrip_host_pred',
+               'simplyp_time_quantiles']
 
 _lib = None
 
@@ -41,7 +42,8 @@ def build(force=False, verbose=False):
     """Compile the HIP library for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, 'simplyp_hip.hip'), os.path.join(CSRC, 'simplyp_kernels.hip.h'),
             os.path.join(CSRC, 'simplyp_gof.hip.h'), os.path.join(CSRC, 'simplyp_waterbody.hip.h'),
-            os.path.join(CSRC, 'simplyp_quantile.hip.h'), os.path.join(CSRC, 'simplyp_pack.h'),
+            os.path.join(CSRC, 'simplyp_quantile.hip.h'), os.path.join(CSRC, 'simplyp_time_quantile.hip.h'),
+            os.path.join(CSRC, 'simplyp_pack.h'),
             os.path.join(CSRC, 'simplyp_pack_stream.h'),
             os.path.join(INCLUDE, 'simplyp.h'), os.path.join(INCLUDE, 'simplyp_controller.h')]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
@@ -105,6 +107,10 @@ def lib():
     L.simplyp_quantiles.restype = C.c_int
     L.simplyp_quantiles.argtypes = [vp, C.c_int32, C.c_int64, dp, i32p, vp, C.POINTER(C.c_double), C.c_int32, dp,
                                     C.POINTER(abi.QuantileInfo)]
+    L.simplyp_time_quantiles.restype = C.c_int
+    L.simplyp_time_quantiles.argtypes = [vp, C.POINTER(abi.Dims), C.c_uint32, C.POINTER(C.c_int32), C.c_int32, dp, i32p, dp, dp,
+                                         C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                         C.POINTER(C.c_double), C.c_int32, dp, C.POINTER(C.c_int32), C.POINTER(abi.TqInfo)]
     L.simplyp_stream_out.restype = C.c_int
     L.simplyp_stream_out.argtypes = [vp, vp, C.c_int64]
     L.simplyp_fetch_packed.restype = C.c_int
@@ -590,6 +596,69 @@ class Engine(object):
         self._check(rc, 'simplyp_quantiles')
         return stats[0], stats[1], info.as_dict()
 
+    def time_quantiles(self, out, out_mask, q, series=None, period_of_day=None, f_tdp=None, reach_params=None,
+                       out_reaches=None, member_of_slot=None, n_periods=None):
+        """Exact order statistics per member along the DAY axis (``simplyp_time_quantiles``) of the daily table ``out``
+        [n_cols, D, n_reaches, E] of a previous ``run`` (written with ``out_mask``): the two values that bracket numpy's
+        ``method='linear'`` quantile of every member's series over each period, selected on the device; the table is only read.
+
+        q: probabilities in [0, 1], at most 16.  series: ids -- ``SIMPLYP_OUT_*`` column numbers (in ``out_mask``) or
+        ``abi.TQ_DERIVED + abi.GOF_VARS.index(v)`` for the df_R series Q_cumecs, SS_mgl, TDP_mgl, PP_mgl, TP_mgl, SRP_mgl,
+        which need ``f_tdp`` (scalar or [E]) and ``reach_params`` [NP_R, S, E]; default: every column of the mask.
+        period_of_day: int array [D] in [-1, n_periods), -1 = the day takes part in no period, the others non-decreasing;
+        None = one period holding every day; n_periods: their number when periods past the last named one exist (default:
+        the largest entry + 1).  Without ``reach_params`` the table's reaches are all S reaches or the
+        ``out_reaches`` given.
+        Returns (lower, upper, info): device tensors [K, n_series, P, n_reaches, E], member axis ordered like ``out``'s, holding
+        x_(floor(h)) and x_(min(floor(h) + 1, n - 1)), h = q (n - 1), n = ``info['n_days'][p]`` (NaN where n = 0);
+        ``interpolate_time_quantiles`` turns them into numpy's values."""
+        torch = self.torch
+        if not torch.is_tensor(out) or out.dim() != 4 or out.dtype != torch.float64 or not out.is_contiguous() \
+                or out.device != self.tdev:
+            raise ValueError("out must be a contiguous float64 tensor [n_cols, D, n_reaches, E] on %s" % (self.tdev,))
+        ncols, D, n_or, E = (int(x) for x in out.shape)
+        oreach = _i32(out_reaches)
+        rp = None if reach_params is None else self.to_device(reach_params, torch.float64)
+        S = int(rp.shape[1]) if rp is not None else (n_or if oreach is None else max(n_or, int(oreach.max()) + 1))
+        if ncols != bin(out_mask).count('1') or n_or != (S if oreach is None else len(oreach)) \
+                or (rp is not None and int(rp.shape[2]) != E):
+            raise ValueError("out %s does not match out_mask / out_reaches / reach_params" % (tuple(out.shape),))
+        qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+        if qa.ndim != 1:
+            raise ValueError("q must be a list of probabilities")
+        K = len(qa)
+        sa = np.ascontiguousarray([c for c in range(32) if (out_mask >> c) & 1] if series is None else series, dtype=np.int32)
+        if sa.ndim != 1:
+            raise ValueError("series must be a list of series ids")
+        pod, P = None, 0
+        if period_of_day is not None:
+            pod = np.ascontiguousarray(period_of_day, dtype=np.int32)
+            if pod.shape != (D,):
+                raise ValueError("period_of_day needs one entry per day")
+            P = max(int(pod.max()) + 1, 1) if D > 0 else 1
+            P = P if n_periods is None else int(n_periods)
+        ft = None if f_tdp is None else self._f_tdp(f_tdp, E)
+        if member_of_slot is not None and (member_of_slot.dtype != torch.int32 or tuple(member_of_slot.shape) != (E,)):
+            raise ValueError("member_of_slot must be an int32 device tensor with one entry per member")
+        stats = torch.empty((2, max(K, 1), max(len(sa), 1), max(P, 1), n_or, E), dtype=torch.float64, device=self.tdev)
+        n_days = np.zeros(max(P, 1), dtype=np.int32)
+        info = abi.TqInfo()
+        dims = abi.Dims(E, S, D, 1)
+        i32 = C.POINTER(C.c_int32)
+        with torch.cuda.device(self.tdev):
+            self._bind_stream()
+            rc = lib().simplyp_time_quantiles(self._h, C.byref(dims), int(out_mask),
+                                              None if oreach is None else oreach.ctypes.data_as(i32), n_or,
+                                              out.data_ptr(), None if member_of_slot is None else member_of_slot.data_ptr(),
+                                              None if ft is None else ft.data_ptr(), None if rp is None else rp.data_ptr(),
+                                              sa.ctypes.data_as(i32), len(sa), None if pod is None else pod.ctypes.data_as(i32), P,
+                                              qa.ctypes.data_as(C.POINTER(C.c_double)), K, stats.data_ptr(),
+                                              n_days.ctypes.data_as(i32), C.byref(info))
+        self._check(rc, 'simplyp_time_quantiles')
+        d = info.as_dict()
+        d['n_days'] = n_days
+        return stats[0], stats[1], d
+
 
 def interpolate_quantiles(lower, upper, q, n_used):
     """numpy's ``method='linear'`` quantile from the two order statistics ``Engine.quantiles`` returns (host arrays
@@ -605,6 +674,21 @@ def interpolate_quantiles(lower, upper, q, n_used):
     diff = upper - lower
     with np.errstate(invalid='ignore'):
         data = np.where(gamma >= 0.5, upper - diff * (1 - gamma), lower + diff * gamma)
+    return data
+
+
+def interpolate_time_quantiles(lower, upper, q, n_days):
+    """numpy's ``method='linear'`` quantile from the two order statistics ``Engine.time_quantiles`` returns (host arrays
+    [K, n_series, P, ...]) with a day count per period (``info['n_days']`` [P]): ``interpolate_quantiles`` -- the same h,
+    gamma and lerp -- period by period; NaN where a period holds no day."""
+    lower = np.asarray(lower, dtype=np.float64)
+    upper = np.asarray(upper, dtype=np.float64)
+    n_days = np.atleast_1d(np.asarray(n_days))
+    if lower.ndim < 3 or lower.shape[2] != len(n_days):
+        raise ValueError("lower / upper must be [K, n_series, P, ...] with P = len(n_days)")
+    data = np.empty(lower.shape, dtype=np.float64)
+    for p, n in enumerate(n_days):
+        data[:, :, p] = interpolate_quantiles(lower[:, :, p], upper[:, :, p], q, int(n))
     return data
 
 

@@ -316,7 +316,8 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
                           outputs=None, out_reaches=None, step_len=1., solver=None, device=0, to_host=True,
                           reduce=None, obs_dict=None, keep_daily=True, snow_in_kernel=None, forcing_of_member=None,
                           waterbody=None, waterbody_obs=None, spearman=False, devices=None, quantiles=None,
-                          quantile_members=None, initial_state=None, return_state=False):
+                          quantile_members=None, initial_state=None, return_state=False, time_quantiles=None,
+                          time_quantile_series=None, time_quantile_periods=None):
     """Run an ensemble of parameter sets through the engine in one call.
 
     ``overrides``: dict name -> array[E] (member parameters, see ``marshal.PM_NAMES``) or
@@ -374,6 +375,25 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     ``quantiles`` raises ValueError: a quantile of the whole ensemble is not a function of the member blocks' quantiles, so
     the band cannot be assembled from per-device results.
 
+    ``time_quantiles``: a list of at most 16 probabilities -- order statistics PER MEMBER OVER TIME, what one
+    ``DataFrame.quantile()`` call on the reference's frames gives for a single run: the flow-duration curve
+    (``[0.05, 0.5, 0.9]`` of ``'Q_cumecs'``: Q95, Q50, Q10), annual maxima (``[1.0]`` with ``time_quantile_periods='annual'``),
+    the annual 90th percentile of ``'SRP_mgl'``, the same for a season only -- selected exactly on the device
+    (``simplyp_time_quantiles``) where the daily table lies.  ``time_quantile_series``: reference column names or the six
+    ``df_R`` names ``Q_cumecs``, ``SS_mgl``, ``TDP_mgl``, ``PP_mgl``, ``TP_mgl``, ``SRP_mgl`` (computed on the fly; they add
+    the four flux columns to the outputs as ``obs_dict`` does; a named column missing from ``outputs`` is added too);
+    default: every column of ``outputs``.  ``time_quantile_periods``: None = the whole run, ``'annual'`` = calendar years,
+    or an int array [D] of period indices, -1 = the day takes part in no period (a season: ``np.where(month in (6, 7, 8),
+    year - year0, -1)``), the others non-decreasing.  The result gains ``'time_quantiles'`` = dict(q, series, periods,
+    data[K, n_series, P, n_reaches, E], lower, upper, n_days[P], info), in member order: ``lower`` / ``upper`` the two order
+    statistics that bracket each quantile, ``data`` numpy's ``method='linear'`` value
+    (``engine.interpolate_time_quantiles``); a period without days is NaN; a member that went non-finite has its NaN sorted
+    last.  A device reduction like ``obs_dict``: with ``keep_daily=False`` no host table is allocated or streamed.  Needs
+    daily rows (``ValueError`` with ``reduce``).  Per member, so it works with ``devices=[...]`` (every block selects where
+    its table lies) and per window in ``run_simply_p_ensemble_windows``.  Together with ``quantiles`` the band across the
+    members of these per-member statistics -- e.g. the ensemble's uncertainty band of the flow-duration curve -- comes back
+    under ``['time_quantiles']['quantiles']`` (same members as the daily band: ``quantile_members``, non-finite ones left out).
+
     ``return_state=True``: the result gains ``'state'`` = dict(rows (``abi.STATE_ROWS``), reaches (all sub-catchments),
     data[S, 16, E], end = ``met_df.index[-1]``): the model state after the last day, in member order (numpy, or a device
     tensor with ``to_host=False``; ``return_state='device'`` keeps it on the device whatever ``to_host`` says -- with
@@ -401,6 +421,35 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
             raise ValueError("quantiles must be 1 to 16 probabilities in [0, 1]")
     elif quantile_members is not None:
         raise ValueError("quantile_members given without quantiles")
+    tq_ids = tq_pod = tq_labels = None
+    if time_quantiles is None:
+        if time_quantile_series is not None or time_quantile_periods is not None:
+            raise ValueError("time_quantile_series / time_quantile_periods given without time_quantiles")
+    else:
+        if reduce is not None:
+            raise ValueError("time_quantiles needs the daily series: it cannot be combined with reduce")
+        time_quantiles = [float(x) for x in np.atleast_1d(np.asarray(time_quantiles, dtype=np.float64))]
+        if not 1 <= len(time_quantiles) <= 16 or not all(0.0 <= x <= 1.0 for x in time_quantiles):
+            raise ValueError("time_quantiles must be 1 to 16 probabilities in [0, 1]")
+        tq_names = list(time_quantile_series) if time_quantile_series is not None else \
+            (list(outputs) if outputs is not None else list(marshal.REACH5_COLUMNS))
+        unknown = [c for c in tq_names if c not in marshal.ALL_COLUMNS and c not in abi.TQ_DERIVED_SERIES]
+        if unknown or not 1 <= len(tq_names) <= 32:
+            raise ValueError("time_quantile_series must be 1 to 32 names among the reference's columns and %s (unknown: %s)"
+                             % (abi.TQ_DERIVED_SERIES, unknown))
+        tq_ids = [abi.TQ_DERIVED + abi.TQ_DERIVED_SERIES.index(c) if c in abi.TQ_DERIVED_SERIES else marshal.ALL_COLUMNS.index(c)
+                  for c in tq_names]
+        if time_quantile_periods is not None and not isinstance(time_quantile_periods, str):
+            tq_pod = np.asarray(time_quantile_periods)
+            if tq_pod.ndim != 1 or tq_pod.dtype.kind not in 'iu' or (tq_pod < -1).any():
+                raise ValueError("time_quantile_periods must be None, 'annual' or an int array [D] of period indices >= -1")
+            named = tq_pod[tq_pod >= 0]
+            if (np.diff(named) < 0).any():
+                raise ValueError("time_quantile_periods must not decrease (apart from -1 = no period)")
+            tq_labels = np.arange(int(named.max()) + 1 if len(named) else 1)
+            tq_pod = np.ascontiguousarray(tq_pod, dtype=np.int32)
+        elif time_quantile_periods is not None and time_quantile_periods != 'annual':
+            raise ValueError("time_quantile_periods must be None, 'annual' or an int array [D] of period indices >= -1")
     marshal.prologue(p_SU, p_LU, p_SC, p)
     scs = marshal.sc_list(p)
     up_ptr, up_idx, _ = marshal.topology(p_struc, p)
@@ -470,6 +519,15 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         if reduce is not None:
             raise ValueError("goodness of fit needs the daily series: obs_dict cannot be combined with reduce")
         cols += [c for c in ('Qr', 'Msus_kg/day', 'TDP_kg/day', 'PP_kg/day') if c not in cols]
+    if time_quantiles is not None:
+        if any(i >= abi.TQ_DERIVED for i in tq_ids):
+            cols += [c for c in ('Qr', 'Msus_kg/day', 'TDP_kg/day', 'PP_kg/day') if c not in cols]
+        cols += [c for c in tq_names if c in marshal.ALL_COLUMNS and c not in cols]
+        if time_quantile_periods is not None and isinstance(time_quantile_periods, str):
+            tq_labels, tq_pod = np.unique(np.asarray(met_df.index.year), return_inverse=True)
+            tq_pod = np.ascontiguousarray(tq_pod, dtype=np.int32)
+        if tq_pod is not None and tq_pod.shape != (len(met_df),):
+            raise ValueError("time_quantile_periods needs one period index per day")
     mask = marshal.mask_of_columns(cols)
     if mask & marshal.MASK_D_SNOW and not snow_in_kernel:
         raise ValueError("output 'D_snow' is the per-member snow depth of the in-kernel snow module: needs snow_in_kernel=True "
@@ -495,7 +553,7 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     n_or_ = len(scs) if oreach is None else len(oreach)
     rows_ = len(met_df) if periods is None else len(periods)
     ncols_ = bin(mask).count('1')
-    reduced_on_device = obs_dict is not None or quantiles is not None     # the caller's product is a reduction of the table
+    reduced_on_device = obs_dict is not None or quantiles is not None or time_quantiles is not None     # the caller's product is a reduction of the table
     want_host_table = to_host and (keep_daily or not reduced_on_device)
     obs = wobs = None
     if obs_dict is not None or (wb_reaches is not None and len(wb_reaches) > 1 and waterbody_obs is not None):
@@ -547,6 +605,18 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
             part['quant'] = eng.quantiles(out_d, quantiles, include=inc, member_of_slot=mos)
             if 'wb' in part:
                 part['wb_quant'] = eng.quantiles(wb_d, quantiles, include=inc, member_of_slot=mos)
+        if time_quantiles is not None:
+            lo_d, up_d, tinfo = eng.time_quantiles(out_d, mask, time_quantiles, series=tq_ids, period_of_day=tq_pod,
+                                                   f_tdp=ft, reach_params=rp_d, out_reaches=oreach, member_of_slot=mos,
+                                                   n_periods=None if tq_labels is None else len(tq_labels))
+            if mos is not None:                  # member order, undone on the small result: slot j holds member mos[j]
+                idx = mos.long()
+                lo_d, up_d = lo_d.new_empty(lo_d.shape).index_copy_(-1, idx, lo_d), up_d.new_empty(up_d.shape).index_copy_(-1, idx, up_d)
+            lo_h, up_h = lo_d.cpu().numpy(), up_d.cpu().numpy()
+            tdata = engine.interpolate_time_quantiles(lo_h, up_h, time_quantiles, tinfo['n_days'])
+            part['tq'] = (lo_h if to_host else lo_d, up_h if to_host else up_d, tdata, tinfo)
+            if quantiles is not None:            # the band across the members of the per-member statistics
+                part['tq_quant'] = eng.quantiles(eng.to_device(tdata), quantiles, include=inc)
         part['out_d'] = None if (reduced_on_device and not keep_daily) else out_d
         return part
 
@@ -608,6 +678,14 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         res['quantiles'] = band(*parts[0]['quant'])
         if res.get('waterbody') is not None:
             res['waterbody']['quantiles'] = band(*parts[0]['wb_quant'])
+    if time_quantiles is not None:
+        tinfo = parts[0]['tq'][3]
+        res['time_quantiles'] = dict(q=list(time_quantiles), series=list(tq_names), periods=tq_labels,
+                                     lower=cat([pt['tq'][0] for pt in parts]), upper=cat([pt['tq'][1] for pt in parts]),
+                                     data=np.concatenate([pt['tq'][2] for pt in parts], axis=-1),
+                                     n_days=np.asarray(tinfo['n_days']), info=tinfo)
+        if quantiles is not None:
+            res['time_quantiles']['quantiles'] = band(*parts[0]['tq_quant'])
     if return_state:
         sts = [pt['state'] for pt in parts]
         if return_state == 'device':
@@ -653,7 +731,8 @@ def run_simply_p_ensemble_windows(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_
     (``simplyp_set_state``), so the windows' tables laid end to end ARE the table of the single call, bit for bit, and so
     are the summed ``rhs_evals`` / ``steps`` / ``rejected``; a window's table exists only while the caller holds its item, so
     the peak device and host footprint is one window's: the daily series, per-year goodness of fit or percentile bands of
-    an ensemble whose whole table would not fit anywhere.  ``obs_dict`` / ``waterbody`` / ``quantiles`` apply per window.
+    an ensemble whose whole table would not fit anywhere.  ``obs_dict`` / ``waterbody`` / ``quantiles`` / ``time_quantiles`` apply per window
+    (an array ``time_quantile_periods`` covers the whole run and is cut with the days).
     With ``reduce``, window boundaries must fall on period boundaries (``ValueError``).
 
     Each item also carries ``'window'`` = (first day, last day, lo, hi) and ``'state'`` (on the device; the last item's is
@@ -675,6 +754,10 @@ def run_simply_p_ensemble_windows(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_
             if reduce is not None and not isinstance(reduce, str):
                 part = np.asarray(reduce)[lo:hi]
                 kw['reduce'] = part - part.min()
+            tqp = kw.get('time_quantile_periods')
+            if tqp is not None and not isinstance(tqp, str):         # the window's days, its periods numbered from 0
+                part = np.asarray(tqp)[lo:hi]
+                kw['time_quantile_periods'] = np.where(part >= 0, part - (part[part >= 0].min() if (part >= 0).any() else 0), -1)
             mets = [m.iloc[lo:hi] for m in met_sets]
             res = run_simply_p_ensemble(mets if isinstance(met_df, (list, tuple)) else mets[0], p_struc, p_SU, p_LU, p_SC, p,
                                         dynamic_options, initial_state=state, return_state='device', **kw)
