@@ -30,7 +30,9 @@ extern "C" {
  * entry points, and simplyp_stats keeps its size and every offset -- reserved0 (always 0 before) is now packed_records, and
  * the upper half of queue_longest_wait_polls (a 32-bit count on the device: always 0 before) is now pack_overflow_blocks.
  * 17 still with simplyp_fetch_packed_pred and simplyp_pack_roundtrip_host_pred: two more entry points, nothing else.
- * 17 still with simplyp_time_quantiles, simplyp_tq_info and SIMPLYP_TQ_DERIVED: one more entry point with its own info struct. */
+ * 17 still with simplyp_time_quantiles, simplyp_tq_info and SIMPLYP_TQ_DERIVED: one more entry point with its own info struct.
+ * 17 still with simplyp_predictive_series, simplyp_predictive_bands and simplyp_pred_info: two more entry points, one more info
+ * struct; no existing struct, enum or entry point changes. */
 #define SIMPLYP_ABI_VERSION 17
 
 typedef enum {
@@ -639,6 +641,71 @@ int simplyp_time_quantiles(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t 
                            const double* q /* host [K] */, int32_t K,
                            double* order_stats, int32_t* n_days /* host or NULL */,
                            simplyp_tq_info* info);
+
+/* ---- predictive bands: the second frame of the reference's get_uncertainty_intervals (Development/2016/MCMC.ipynb, cell 11) --
+ * the percentiles across the members after sim + norm.rvs(loc=0, scale=m*sim) has been added to every member's series -- and
+ * the bands of the six df_R series (and of plain columns) without it, selected on the device from series generated there.
+ *
+ * The draw is counter-based, a pure function of what it belongs to: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl
+ * constants 0x9E3779B9, 0xBB67AE85) with key (seed & 0xffffffff, seed >> 32) and counter (member id, day0 + d,
+ * out_reaches[r] = the zero-based model reach, series id as passed).  From its outputs x0..x3: h1 = ((x0 << 32) | x1) >> 12,
+ * u1 = (h1 + 0.5) 2^-52, h2 / u2 alike from x2, x3 (exact in fp64, u in (0, 1)); z = sqrt(-2 ln u1) cospi(2 u2), |z| <= 8.58;
+ * v' = v + (m v) z, two multiplies and an add.  Neither the launch shape, the slot a member sits in, the chunking, the window
+ * nor the time enters; simplyp_amd/predictive.py restates the stream in NumPy. --------------------------------------------- */
+typedef struct {
+    double  kernel_ms;        /* all launches of the call, HIP events on the context's stream                              */
+    double  gen_ms;           /* of these, the generation kernel's                                                         */
+    int64_t bytes_read;       /* bytes of the run's table the generation read                                              */
+    int64_t bytes_workspace;  /* the chunk of generated series in the context's workspace                                  */
+    int32_t n_used;           /* members that took part                                                                    */
+    int32_t n_passes;         /* sweeps over a row the selection made (diagnostic)                                         */
+    int32_t n_chunks;         /* blocks of whole days generated and selected one after the other                           */
+    int32_t reserved;
+} simplyp_pred_info;
+
+/*
+ * simplyp_predictive_series -- the series themselves: individual noisy realisations (or the normals behind them) of every
+ * member, into a caller-owned device table.
+ *   dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params, series, n_series
+ *                   as for simplyp_time_quantiles: `out` holds daily rows (dims->D of them; D == 0 succeeds, D < 0 is an error)
+ *   err_m           device  [n_series][E] in MEMBER order: the error model's m per series and member, or NULL
+ *   seed, day0      the stream's key; the absolute index of the table's first day (>= 0): windows of one run pass their offset
+ *   which           0: the values -- v' = v + (m v) z with err_m, the series v itself without;  1: the normals z (needs err_m)
+ *   table           device  [n_series][D][n_out_reaches][E], member axis in the order of `out`'s
+ * Synchronous.  SIMPLYP_ERR_ARG (nothing launched) as for simplyp_predictive_bands, and for `which` outside {0, 1}, which = 1
+ * with NULL err_m, NULL table.
+ */
+int simplyp_predictive_series(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                              const int32_t* out_reaches, int32_t n_out_reaches,
+                              const double* out, const int32_t* member_of_slot,
+                              const double* f_tdp, const double* reach_params,
+                              const int32_t* series /* host [n_series] */, int32_t n_series,
+                              const double* err_m, uint64_t seed, int32_t day0, int32_t which, double* table);
+
+/*
+ * simplyp_predictive_bands -- the order statistics across the members, for every (series, day, output reach), of the series
+ * simplyp_predictive_series(which = 0) would write: rank rule, NaN ordering and `include` exactly as simplyp_quantiles.  The
+ * series are generated into a bounded workspace of the context by whole days (256 MiB at most, a day at least; the
+ * environment variable SIMPLYP_PRED_CHUNK_DAYS sets the days per chunk) and each chunk is selected with simplyp_quantiles'
+ * kernels; the include mask and the ranks are formed once per call.  The result does not depend on the chunk length, bit
+ * for bit.  The run's table is only read.
+ *   include         device  [E] uint8 in MEMBER order or NULL, as for simplyp_quantiles; no member left: every output NaN
+ *   err_m           NULL = the parameter-only band of the series: no draws are made
+ *   q, K            HOST    [K] probabilities in [0, 1], 1 <= K <= 16
+ *   order_stats     device  [2][K][n_series][D][n_out_reaches]: plane 0 = x_(k_lo), plane 1 = x_(k_hi)
+ *   info            host    may be NULL
+ * Synchronous, on the context's stream.  SIMPLYP_ERR_ARG (nothing launched) for K outside 1..16, a q outside [0, 1] or NaN,
+ * n_series outside 1..32, a series that is not in the mask, a derived series whose mask lacks Qr or a flux or with NULL
+ * f_tdp / reach_params, day0 < 0, D < 0, NULL out / series / q / order_stats.
+ */
+int simplyp_predictive_bands(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                             const int32_t* out_reaches, int32_t n_out_reaches,
+                             const double* out, const int32_t* member_of_slot, const uint8_t* include,
+                             const double* f_tdp, const double* reach_params,
+                             const int32_t* series /* host [n_series] */, int32_t n_series,
+                             const double* err_m, uint64_t seed, int32_t day0,
+                             const double* q /* host [K] */, int32_t K,
+                             double* order_stats, simplyp_pred_info* info);
 
 /*
  * simplyp_eval_units -- the path's scalar device functions on caller-given arguments, one thread per row: how the tests pin the

@@ -80,6 +80,15 @@ class TqInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class PredInfo(C.Structure):
+    """simplyp_pred_info of include/simplyp.h."""
+    _fields_ = [('kernel_ms', C.c_double), ('gen_ms', C.c_double), ('bytes_read', C.c_int64), ('bytes_workspace', C.c_int64),
+                ('n_used', C.c_int32), ('n_passes', C.c_int32), ('n_chunks', C.c_int32), ('reserved', C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
+
+
 TQ_DERIVED = 64                                                                       # SIMPLYP_TQ_DERIVED
 TQ_DERIVED_SERIES = ['Q_cumecs', 'SS_mgl', 'TDP_mgl', 'PP_mgl', 'TP_mgl', 'SRP_mgl']  # df_R names, in SIMPLYP_GOF_* order
 

@@ -22,6 +22,7 @@
 #include "simplyp_waterbody.hip.h"
 #include "simplyp_quantile.hip.h"
 #include "simplyp_time_quantile.hip.h"
+#include "simplyp_predictive.hip.h"
 #include "simplyp_pack_stream.h"
 
 namespace {
@@ -49,6 +50,7 @@ struct simplyp_ctx {
     DeviceBuf gof_partial;    // [n_chunks][R][78][E] partial sums
     DeviceBuf quant;          // simplyp_quantiles: 2 x int32 (members used, sweeps) | [E] uint8 include mask in column order
     DeviceBuf tquant;         // simplyp_time_quantiles: sweeps, rows read | day lists, ranks, output reaches
+    DeviceBuf pred;           // simplyp_predictive_*: [R] int32 output reaches (256-byte slot) | a chunk of days [n_series][days][R][E]
     DeviceBuf queue;          // ticket, error, done[n_groups] (uint32) | ckpt[CKPT_N][E] (double)
     // streamed output (simplyp_stream_out): the armed destination, the chunk flags the queue kernel raises in pinned host
     // memory, and the host thread that turns a raised flag into the D2H copies of that chunk's rows on `copy_stream`
@@ -978,6 +980,7 @@ void simplyp_ctx_destroy(simplyp_ctx* ctx)
     if (ctx->gof_partial.ptr) (void)hipFree(ctx->gof_partial.ptr);
     if (ctx->quant.ptr) (void)hipFree(ctx->quant.ptr);
     if (ctx->tquant.ptr) (void)hipFree(ctx->tquant.ptr);
+    if (ctx->pred.ptr) (void)hipFree(ctx->pred.ptr);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
     if (ctx->ev_main) (void)hipEventDestroy(ctx->ev_main);
@@ -1753,6 +1756,54 @@ int simplyp_waterbody(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_m
                                       sum_reaches, n_sum, wb_mask, wb, info))
 }
 
+// What a selection across the members decides once per call, whatever it then selects from: the include mask in the table's
+// column order and the members that take part (context workspace: 2 x int32 | [E] uint8), and numpy's 'linear' ranks.
+// Fills g.E, g.include_slot, g.T, g.rank and g.n_passes (the int before it holds n_used); rank stays unset when n_used == 0.
+static int quantile_prepare(simplyp_ctx* ctx, int32_t E, const int32_t* member_of_slot, const uint8_t* include,
+                            const double* q, int32_t K, simplyp::QuantileArgs& g, int& n_used)
+{
+    if (int rc = ensure(ctx, ctx->quant, 16 + (size_t)E)) return rc;
+    int* d_ints = (int*)ctx->quant.ptr;                       // [0] members used, [1] sweeps
+    uint8_t* d_mask = (uint8_t*)ctx->quant.ptr + 16;
+    HIP_TRY(ctx, hipMemsetAsync(d_ints, 0, 16, ctx->stream));
+    n_used = E;
+    if (include) {
+        hipLaunchKernelGGL(simplyp::quantile_mask_kernel, dim3(1), dim3(1024), 0, ctx->stream, (int)E, include, member_of_slot, d_mask, d_ints);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(&n_used, d_ints, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    g.E = E; g.include_slot = include ? d_mask : nullptr;
+    g.T = 2 * K; g.n_passes = d_ints + 1;
+    for (int k = 0; k < K && n_used > 0; ++k) {               // numpy's 'linear' indices
+        const double h = q[k] * (double)(n_used - 1);
+        long long lo = (long long)std::floor(h);
+        lo = std::min<long long>(std::max<long long>(lo, 0), n_used - 1);
+        g.rank[2 * k] = lo;
+        g.rank[2 * k + 1] = std::min<long long>(lo + 1, n_used - 1);
+    }
+    return SIMPLYP_OK;
+}
+
+// The selection of g.n_rows rows of g.table into rows g.out_row0... of g.order_stats: the LDS sort for short rows, the radix
+// select for long ones.
+static int quantile_launch(simplyp_ctx* ctx, const simplyp::QuantileArgs& g, const char* me)
+{
+    if (g.E <= simplyp::QSORT_MAX) {
+        int P = 2;
+        while (P < g.E) P <<= 1;
+        const long long rows_per_block = simplyp::QSORT_MAX / P;
+        const long long blocks = (g.n_rows + rows_per_block - 1) / rows_per_block;
+        if (blocks > 0x7FFFFFFFLL) return fail(ctx, SIMPLYP_ERR_ARG, "%s: too many rows for one call (%lld)", me, g.n_rows);
+        hipLaunchKernelGGL(simplyp::quantile_sort_kernel, dim3((unsigned)blocks), dim3(simplyp::QSORT_THREADS), 0, ctx->stream, g, P);
+    } else {
+        const unsigned blocks = (unsigned)std::min<long long>(g.n_rows, 65536);
+        hipLaunchKernelGGL(simplyp::quantile_select_kernel, dim3(blocks), dim3(simplyp::QSEL_THREADS), 0, ctx->stream, g);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return SIMPLYP_OK;
+}
+
 static int quantiles_impl(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double* table,
                           const int32_t* member_of_slot, const uint8_t* include,
                           const double* q, int32_t K, double* order_stats, simplyp_quantile_info* info)
@@ -1769,45 +1820,18 @@ static int quantiles_impl(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const dou
     if (info) { info->kernel_ms = 0.0; info->bytes_table = n_rows * (int64_t)E * 8; info->n_used = 0; info->n_passes = 0; }
     if (n_rows == 0) return SIMPLYP_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = ensure(ctx, ctx->quant, 16 + (size_t)E)) return rc;
-    int* d_ints = (int*)ctx->quant.ptr;                       // [0] members used, [1] sweeps
-    uint8_t* d_mask = (uint8_t*)ctx->quant.ptr + 16;
     HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(d_ints, 0, 16, ctx->stream));
-    int n_used = E;
-    if (include) {
-        hipLaunchKernelGGL(simplyp::quantile_mask_kernel, dim3(1), dim3(1024), 0, ctx->stream, (int)E, include, member_of_slot, d_mask, d_ints);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(&n_used, d_ints, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    simplyp::QuantileArgs g{};
+    int n_used = 0;
+    if (int rc = quantile_prepare(ctx, E, member_of_slot, include, q, K, g, n_used)) return rc;
+    int* d_ints = g.n_passes - 1;
     const long long n_out = 2LL * K * n_rows;
     if (n_used == 0) {
         hipLaunchKernelGGL(simplyp::quantile_fill_nan_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, ctx->stream, order_stats, n_out);
         HIP_TRY(ctx, hipGetLastError());
     } else {
-        simplyp::QuantileArgs g{};
-        g.E = E; g.n_rows = n_rows; g.table = table; g.include_slot = include ? d_mask : nullptr;
-        g.T = 2 * K; g.order_stats = order_stats; g.n_passes = d_ints + 1;
-        for (int k = 0; k < K; ++k) {                         // numpy's 'linear' indices
-            const double h = q[k] * (double)(n_used - 1);
-            long long lo = (long long)std::floor(h);
-            lo = std::min<long long>(std::max<long long>(lo, 0), n_used - 1);
-            g.rank[2 * k] = lo;
-            g.rank[2 * k + 1] = std::min<long long>(lo + 1, n_used - 1);
-        }
-        if (E <= simplyp::QSORT_MAX) {
-            int P = 2;
-            while (P < E) P <<= 1;
-            const long long rows_per_block = simplyp::QSORT_MAX / P;
-            const long long blocks = (n_rows + rows_per_block - 1) / rows_per_block;
-            if (blocks > 0x7FFFFFFFLL) return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_quantiles: too many rows for one call (%lld)", (long long)n_rows);
-            hipLaunchKernelGGL(simplyp::quantile_sort_kernel, dim3((unsigned)blocks), dim3(simplyp::QSORT_THREADS), 0, ctx->stream, g, P);
-        } else {
-            const unsigned blocks = (unsigned)std::min<long long>(n_rows, 65536);
-            hipLaunchKernelGGL(simplyp::quantile_select_kernel, dim3(blocks), dim3(simplyp::QSEL_THREADS), 0, ctx->stream, g);
-        }
-        HIP_TRY(ctx, hipGetLastError());
+        g.n_rows = n_rows; g.table = table; g.order_stats = order_stats; g.out_row0 = 0; g.out_stride = n_rows;
+        if (int rc = quantile_launch(ctx, g, "simplyp_quantiles")) return rc;
     }
     HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
     int n_passes = 0;
@@ -1988,6 +2012,225 @@ int simplyp_time_quantiles(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t 
 {
     SIMPLYP_GUARD(ctx, time_quantiles_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
                                            series, n_series, period_of_day, n_periods, q, K, order_stats, n_days, info))
+}
+
+// What simplyp_predictive_series and simplyp_predictive_bands share: the checks of the table and the series, and the
+// generation kernel's arguments but for the block of days and its destination.  reach_bytes: the room the device copy of the
+// output reaches takes at the head of ctx->pred.
+static int predictive_setup(simplyp_ctx* ctx, const char* me, const simplyp_dims* dims, uint32_t out_mask,
+                            const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
+                            const double* f_tdp, const double* reach_params, const int32_t* series, int32_t n_series,
+                            const double* err_m, uint64_t seed, int32_t day0, simplyp::PredArgs& g,
+                            std::vector<int32_t>& reach_of, int64_t& loads)
+{
+    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a run is pending on this context; call simplyp_sync first", me);
+    if (!dims || dims->E < 1 || dims->S < 1 || dims->D < 0)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: bad dims (E and S must be >= 1, D >= 0: the table's daily rows)", me);
+    if (!out) return fail(ctx, SIMPLYP_ERR_ARG, "%s: out must not be NULL", me);
+    if (n_series < 1 || n_series > simplyp::PRED_MAX_SERIES || !series)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_series must be in [1, %d] (got %d) and series not NULL", me, simplyp::PRED_MAX_SERIES, (int)n_series);
+    if (out_mask == 0u || (out_mask & ~(SIMPLYP_MASK_ALL | SIMPLYP_MASK_D_SNOW)) != 0u)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: out_mask must select 1..%d of the columns", me, (int)SIMPLYP_N_OUT);
+    if (day0 < 0 || (long long)day0 + dims->D > 0x7FFFFFFFLL)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: day0 must be >= 0 and day0 + D fit 31 bits (got %d)", me, (int)day0);
+    const int E = dims->E, S = dims->S, D = dims->D;
+    const int R = out_reaches ? n_out_reaches : S;
+    if (R <= 0 || R > S) return fail(ctx, SIMPLYP_ERR_ARG, "%s: bad n_out_reaches", me);
+    reach_of.resize(R);
+    for (int r = 0; r < R; ++r) {
+        reach_of[r] = out_reaches ? out_reaches[r] : r;
+        if (reach_of[r] < 0 || reach_of[r] >= S) return fail(ctx, SIMPLYP_ERR_ARG, "%s: out_reaches[%d] out of range", me, r);
+    }
+    if ((long long)n_series * R > 65535) return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_series * n_out_reaches must not exceed 65535", me);
+    static const int flux_cols[4] = {SIMPLYP_OUT_QR, SIMPLYP_OUT_MSUS_FLUX, SIMPLYP_OUT_TDP_FLUX, SIMPLYP_OUT_PP_FLUX};
+    const uint32_t need = (1u << flux_cols[0]) | (1u << flux_cols[1]) | (1u << flux_cols[2]) | (1u << flux_cols[3]);
+    bool derived = false;
+    loads = 0;
+    for (int i = 0; i < n_series; ++i) {
+        const int id = series[i];
+        if (id >= 0 && id < SIMPLYP_N_OUT) {
+            if (!((out_mask >> id) & 1u)) return fail(ctx, SIMPLYP_ERR_ARG, "%s: series[%d] = column %d is not in out_mask", me, i, id);
+            g.series[i] = popcount32(out_mask & ((1u << id) - 1u));
+            loads += 1;
+        } else if (id >= SIMPLYP_TQ_DERIVED && id < SIMPLYP_TQ_DERIVED + SIMPLYP_N_GOF_VARS) {
+            if ((out_mask & need) != need)
+                return fail(ctx, SIMPLYP_ERR_ARG, "%s: series[%d] is derived: out_mask must contain Qr, Msus_kg/day, TDP_kg/day and PP_kg/day", me, i);
+            if (!f_tdp || !reach_params) return fail(ctx, SIMPLYP_ERR_ARG, "%s: series[%d] is derived: f_tdp and reach_params must not be NULL", me, i);
+            const int var = id - SIMPLYP_TQ_DERIVED;
+            g.series[i] = -1 - var;
+            loads += var == SIMPLYP_GOF_Q ? 1 : var == SIMPLYP_GOF_TP ? 3 : 2;
+            derived = true;
+        } else {
+            return fail(ctx, SIMPLYP_ERR_ARG, "%s: series[%d] = %d is neither a column nor SIMPLYP_TQ_DERIVED + a variable", me, i, id);
+        }
+        g.series_id[i] = (uint32_t)id;
+    }
+    g.E = E; g.R = R; g.n_series = n_series;
+    g.out = out; g.col_stride = (long long)D * R * E;
+    for (int i = 0; i < 4; ++i) g.col[i] = popcount32(out_mask & ((1u << flux_cols[i]) - 1u));
+    g.member_of_slot = member_of_slot;
+    g.f_tdp = f_tdp;
+    g.a_catch = derived ? reach_params + (size_t)SIMPLYP_PR_A_CATCH * S * E : nullptr;
+    g.err_m = err_m;
+    g.key0 = (uint32_t)(seed & 0xFFFFFFFFull); g.key1 = (uint32_t)(seed >> 32);
+    g.day0 = (uint32_t)day0;
+    return SIMPLYP_OK;
+}
+
+constexpr size_t PRED_REACH_BYTES = 4 * 65536;      // n_out_reaches <= 65535
+
+// The output reaches to the head of ctx->pred (grown to hold `table_bytes` behind them).
+static int predictive_workspace(simplyp_ctx* ctx, const std::vector<int32_t>& reach_of, size_t table_bytes, simplyp::PredArgs& g)
+{
+    if (int rc = ensure(ctx, ctx->pred, PRED_REACH_BYTES + table_bytes)) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->pred.ptr, reach_of.data(), reach_of.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    g.reach_of = (const int32_t*)ctx->pred.ptr;
+    return SIMPLYP_OK;
+}
+
+static int predictive_launch(simplyp_ctx* ctx, simplyp::PredArgs& g, int d_lo, int n_days, double* dst)
+{
+    g.d_lo = d_lo; g.n_days = n_days; g.dst = dst;
+    const int batches = (n_days + simplyp::PRED_BATCH - 1) / simplyp::PRED_BATCH;
+    const dim3 grid((unsigned)((g.E + simplyp::PRED_THREADS - 1) / simplyp::PRED_THREADS), (unsigned)std::min(batches, 65535),
+                    (unsigned)(g.n_series * g.R));
+    hipLaunchKernelGGL(simplyp::simplyp_predictive_kernel, grid, dim3(simplyp::PRED_THREADS), 0, ctx->stream, g);
+    HIP_TRY(ctx, hipGetLastError());
+    return SIMPLYP_OK;
+}
+
+static int predictive_series_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                                  const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
+                                  const double* f_tdp, const double* reach_params, const int32_t* series, int32_t n_series,
+                                  const double* err_m, uint64_t seed, int32_t day0, int32_t which, double* table)
+{
+    const char* me = "simplyp_predictive_series";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    if (which < 0 || which > 1) return fail(ctx, SIMPLYP_ERR_ARG, "%s: which must be 0 (values) or 1 (normals), got %d", me, (int)which);
+    if (which == 1 && !err_m) return fail(ctx, SIMPLYP_ERR_ARG, "%s: which = 1 (the normals) needs err_m", me);
+    if (!table) return fail(ctx, SIMPLYP_ERR_ARG, "%s: table must not be NULL", me);
+    simplyp::PredArgs g{};
+    std::vector<int32_t> reach_of;
+    int64_t loads = 0;
+    if (int rc = predictive_setup(ctx, me, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
+                                  series, n_series, err_m, seed, day0, g, reach_of, loads)) return rc;
+    if (dims->D == 0) return SIMPLYP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = predictive_workspace(ctx, reach_of, 0, g)) return rc;
+    g.normals = which;
+    if (int rc = predictive_launch(ctx, g, 0, dims->D, table)) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SIMPLYP_OK;
+}
+
+namespace {
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+};
+}  // namespace
+
+static int predictive_bands_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                                 const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
+                                 const uint8_t* include, const double* f_tdp, const double* reach_params,
+                                 const int32_t* series, int32_t n_series, const double* err_m, uint64_t seed, int32_t day0,
+                                 const double* q, int32_t K, double* order_stats, simplyp_pred_info* info)
+{
+    const char* me = "simplyp_predictive_bands";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    if (K < 1 || K > simplyp::QUANT_MAX_K) return fail(ctx, SIMPLYP_ERR_ARG, "%s: K must be in [1, %d] (got %d)", me, simplyp::QUANT_MAX_K, (int)K);
+    if (!q || !order_stats) return fail(ctx, SIMPLYP_ERR_ARG, "%s: q and order_stats must not be NULL", me);
+    for (int k = 0; k < K; ++k)
+        if (!(q[k] >= 0.0 && q[k] <= 1.0))
+            return fail(ctx, SIMPLYP_ERR_ARG, "%s: q[%d] = %g is not a probability in [0, 1]", me, k, q[k]);
+    simplyp::PredArgs g{};
+    std::vector<int32_t> reach_of;
+    int64_t loads = 0;
+    if (int rc = predictive_setup(ctx, me, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
+                                  series, n_series, err_m, seed, day0, g, reach_of, loads)) return rc;
+    const int E = g.E, R = g.R, D = dims->D;
+    if (info) { info->kernel_ms = 0.0; info->gen_ms = 0.0; info->bytes_read = 0; info->bytes_workspace = 0; info->n_used = 0; info->n_passes = 0; info->n_chunks = 0; }
+    if (D == 0) return SIMPLYP_OK;
+    // whole days per chunk: what 256 MiB of generated series hold, or what the environment says
+    const size_t day_bytes = (size_t)n_series * R * E * sizeof(double);
+    long long chunk_days = std::max<long long>(1, (long long)((256ull << 20) / day_bytes));
+    if (const char* env = std::getenv("SIMPLYP_PRED_CHUNK_DAYS")) {
+        const long long v = std::atoll(env);
+        if (v > 0) chunk_days = v;
+    }
+    chunk_days = std::min<long long>(chunk_days, D);
+    const int n_chunks = (int)((D + chunk_days - 1) / chunk_days);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    EventPair ev;
+    HIP_TRY(ctx, hipEventCreate(&ev.a));
+    HIP_TRY(ctx, hipEventCreate(&ev.b));
+    if (int rc = predictive_workspace(ctx, reach_of, (size_t)chunk_days * day_bytes, g)) return rc;
+    double* work = (double*)((char*)ctx->pred.ptr + PRED_REACH_BYTES);
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    simplyp::QuantileArgs s{};
+    int n_used = 0;
+    if (int rc = quantile_prepare(ctx, E, member_of_slot, include, q, K, s, n_used)) return rc;      // once per call
+    const long long n_rows_all = (long long)n_series * D * R;
+    double gen_ms = 0.0;
+    if (n_used == 0) {
+        const long long n_out = 2LL * K * n_rows_all;
+        hipLaunchKernelGGL(simplyp::quantile_fill_nan_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, ctx->stream, order_stats, n_out);
+        HIP_TRY(ctx, hipGetLastError());
+    } else {
+        s.order_stats = order_stats; s.out_stride = n_rows_all;
+        for (int c = 0; c < n_chunks; ++c) {
+            const int d_lo = (int)(c * chunk_days), nd = (int)std::min<long long>(chunk_days, D - d_lo);
+            HIP_TRY(ctx, hipEventRecord(ev.a, ctx->stream));
+            if (int rc = predictive_launch(ctx, g, d_lo, nd, work)) return rc;
+            HIP_TRY(ctx, hipEventRecord(ev.b, ctx->stream));
+            for (int i = 0; i < n_series; ++i) {               // a series' rows of the chunk are one run of rows of the result
+                s.table = work + (size_t)i * nd * R * E;
+                s.n_rows = (long long)nd * R;
+                s.out_row0 = ((long long)i * D + d_lo) * R;
+                if (int rc = quantile_launch(ctx, s, me)) return rc;
+            }
+            // the generation's time, read while the chunk's selections run; the next chunk overwrites the workspace after them
+            HIP_TRY(ctx, hipEventSynchronize(ev.b));
+            float ms = 0.f;
+            HIP_TRY(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
+            gen_ms += ms;
+        }
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+    int n_passes = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&n_passes, s.n_passes, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (info) {
+        float ms = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+        info->kernel_ms = ms;
+        info->gen_ms = gen_ms;
+        info->bytes_read = n_used == 0 ? 0 : loads * (int64_t)D * R * E * 8;
+        info->bytes_workspace = (int64_t)((size_t)chunk_days * day_bytes);
+        info->n_used = n_used;
+        info->n_passes = n_passes;
+        info->n_chunks = n_used == 0 ? 0 : n_chunks;
+    }
+    return SIMPLYP_OK;
+}
+
+int simplyp_predictive_series(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                              const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
+                              const double* f_tdp, const double* reach_params, const int32_t* series, int32_t n_series,
+                              const double* err_m, uint64_t seed, int32_t day0, int32_t which, double* table)
+{
+    SIMPLYP_GUARD(ctx, predictive_series_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
+                                              series, n_series, err_m, seed, day0, which, table))
+}
+
+int simplyp_predictive_bands(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                             const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
+                             const uint8_t* include, const double* f_tdp, const double* reach_params,
+                             const int32_t* series, int32_t n_series, const double* err_m, uint64_t seed, int32_t day0,
+                             const double* q, int32_t K, double* order_stats, simplyp_pred_info* info)
+{
+    SIMPLYP_GUARD(ctx, predictive_bands_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, include, f_tdp,
+                                             reach_params, series, n_series, err_m, seed, day0, q, K, order_stats, info))
 }
 
 void* simplyp_host_alloc(int64_t bytes)

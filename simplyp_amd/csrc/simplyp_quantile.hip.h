@@ -46,7 +46,8 @@ struct QuantileArgs {
     const uint8_t* include_slot;           // [E] in the table's column order, or nullptr = all
     int T;                                 // 2K
     long long rank[QUANT_MAX_T];           // rank[2k] = k_lo, rank[2k+1] = k_hi of probability k; all < n_used
-    double* order_stats;                   // [2][K][n_rows]
+    double* order_stats;                   // [2][K][out_stride]: row r of the table is row out_row0 + r of the result
+    long long out_row0, out_stride;        // (0, n_rows) for a table selected in one launch; a chunk of a larger result otherwise
     int* n_passes;                         // max over rows of the sweeps made (atomicMax)
 };
 
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(QSORT_THREADS) void quantile_sort_kernel(const Quan
     for (int i = threadIdx.x; i < rows_per_block * g.T; i += QSORT_THREADS) {
         const int r = i / g.T, t = i - r * g.T;
         if (row0 + r < g.n_rows)
-            g.order_stats[((size_t)(t & 1) * K + (t >> 1)) * g.n_rows + row0 + r] = quantile_value(keys[r * P + (int)g.rank[t]]);
+            g.order_stats[((size_t)(t & 1) * K + (t >> 1)) * g.out_stride + g.out_row0 + row0 + r] = quantile_value(keys[r * P + (int)g.rank[t]]);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(g.n_passes, 1);
 }
@@ -226,7 +227,7 @@ __global__ __launch_bounds__(QSEL_THREADS) void quantile_select_kernel(const Qua
                             less += o < mine; equal += o == mine;
                         }
                         if (less <= want && want < less + equal)       // lanes holding equal keys store the same value
-                            g.order_stats[((size_t)(t & 1) * K + (t >> 1)) * g.n_rows + r] = quantile_value(mine);
+                            g.order_stats[((size_t)(t & 1) * K + (t >> 1)) * g.out_stride + g.out_row0 + r] = quantile_value(mine);
                     }
                 }
                 done = true;
@@ -264,7 +265,7 @@ __global__ __launch_bounds__(QSEL_THREADS) void quantile_select_kernel(const Qua
             __syncthreads();
         }
         if (!done && tid < T)                      // all 64 bits settled: the prefix is the key
-            g.order_stats[((size_t)(tid & 1) * K + (tid >> 1)) * g.n_rows + r] = quantile_value(s.prefix[s.group[tid]]);
+            g.order_stats[((size_t)(tid & 1) * K + (tid >> 1)) * g.out_stride + g.out_row0 + r] = quantile_value(s.prefix[s.group[tid]]);
         max_sweeps = sweeps > max_sweeps ? sweeps : max_sweeps;
     }
     if (tid == 0 && max_sweeps > 0) atomicMax(g.n_passes, max_sweeps);

@@ -77,14 +77,44 @@ struct TqSeries {
 };
 
 template <int KIND>
+__device__ __forceinline__ double tq_value(const TqSeries& s, double a, double b, double c)
+{
+    if constexpr (KIND == 0) return a;
+    else if constexpr (KIND == 1) return a * s.A * 1000 / 86400;
+    else if constexpr (KIND == 2) return ((b / a) / s.A) * s.f;
+    else return (b / a) / s.A + (c / a) / s.A;
+}
+
+// The series `code` (>= 0: column slot; < 0: derived, -1 - SIMPLYP_GOF_*) at element `base` of a day's rows: its pointers at
+// day 0, A = a_catch[a_index] and f (f_tdp[member] for SRP).  col: the slots of Qr and the three fluxes.  Returns KIND.
+__device__ __forceinline__ int tq_series(TqSeries& sr, int code, const double* out, long long col_stride, const int* col,
+                                         size_t base, const double* a_catch, const double* f_tdp, size_t a_index, int member)
+{
+    sr.p1 = sr.p2 = nullptr;
+    sr.A = sr.f = 1.0;
+    if (code >= 0) {
+        sr.p0 = out + (size_t)code * col_stride + base;
+        return 0;
+    }
+    const int var = -1 - code;
+    sr.A = a_catch[a_index];
+    sr.p0 = out + (size_t)col[0] * col_stride + base;
+    if (var == SIMPLYP_GOF_Q) return 1;
+    if (var == SIMPLYP_GOF_TP) {
+        sr.p1 = out + (size_t)col[2] * col_stride + base;
+        sr.p2 = out + (size_t)col[3] * col_stride + base;
+        return 3;
+    }
+    const int c = var == SIMPLYP_GOF_SS ? 1 : var == SIMPLYP_GOF_PP ? 3 : 2;          // SS, PP, and TDP / SRP from the TDP flux
+    sr.p1 = out + (size_t)col[c] * col_stride + base;
+    if (var == SIMPLYP_GOF_SRP) sr.f = f_tdp[member];
+    return 2;
+}
+
+template <int KIND>
 __device__ __forceinline__ unsigned long long tq_key(const TqSeries& s, double a, double b, double c)
 {
-    double v;
-    if constexpr (KIND == 0) v = a;
-    else if constexpr (KIND == 1) v = a * s.A * 1000 / 86400;
-    else if constexpr (KIND == 2) v = ((b / a) / s.A) * s.f;
-    else v = (b / a) / s.A + (c / a) / s.A;
-    return quantile_key(v);
+    return quantile_key(tq_value<KIND>(s, a, b, c));
 }
 
 // f(key) for every participating day of the period, TQ_BATCH rows in flight.
@@ -242,32 +272,14 @@ __global__ __launch_bounds__(64) void simplyp_time_quantile_kernel(const TqArgs 
     const int raw = blockIdx.x * 64 + lane;
     const bool live = raw < g.E;
     const int slot = live ? raw : g.E - 1;                             // idle lanes of the last block shadow the last member
-    const int code = g.series[si];
-    const size_t base = (size_t)r * g.E + slot;
     TqSeries sr;
-    sr.p1 = sr.p2 = nullptr;
-    sr.A = sr.f = 1.0;
-    if (code >= 0) {
-        sr.p0 = g.out + (size_t)code * g.col_stride + base;
-        tq_periods<TMAX, 0>(g, s, sr, si, r, slot, live);
-        return;
-    }
-    const int var = -1 - code;
-    const int member = g.member_of_slot ? g.member_of_slot[slot] : slot;
-    sr.A = g.a_catch[(size_t)g.reach_of[r] * g.E + member];
-    sr.p0 = g.out + (size_t)g.col[0] * g.col_stride + base;
-    if (var == SIMPLYP_GOF_Q) {
-        tq_periods<TMAX, 1>(g, s, sr, si, r, slot, live);
-    } else if (var == SIMPLYP_GOF_TP) {
-        sr.p1 = g.out + (size_t)g.col[2] * g.col_stride + base;
-        sr.p2 = g.out + (size_t)g.col[3] * g.col_stride + base;
-        tq_periods<TMAX, 3>(g, s, sr, si, r, slot, live);
-    } else {
-        const int c = var == SIMPLYP_GOF_SS ? 1 : var == SIMPLYP_GOF_PP ? 3 : 2;      // SS, PP, and TDP / SRP from the TDP flux
-        sr.p1 = g.out + (size_t)g.col[c] * g.col_stride + base;
-        if (var == SIMPLYP_GOF_SRP) sr.f = g.f_tdp[member];
-        tq_periods<TMAX, 2>(g, s, sr, si, r, slot, live);
-    }
+    const int member = g.member_of_slot && g.series[si] < 0 ? g.member_of_slot[slot] : slot;
+    const int kind = tq_series(sr, g.series[si], g.out, g.col_stride, g.col, (size_t)r * g.E + slot,
+                               g.a_catch, g.f_tdp, (size_t)g.reach_of[r] * g.E + member, member);
+    if (kind == 0) tq_periods<TMAX, 0>(g, s, sr, si, r, slot, live);
+    else if (kind == 1) tq_periods<TMAX, 1>(g, s, sr, si, r, slot, live);
+    else if (kind == 2) tq_periods<TMAX, 2>(g, s, sr, si, r, slot, live);
+    else tq_periods<TMAX, 3>(g, s, sr, si, r, slot, live);
 }
 
 }  // namespace simplyp

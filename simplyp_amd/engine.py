@@ -29,7 +29,7 @@ ABI_SYMBOLS = ['simplyp_abi_version', 'simplyp_device_count', 'simplyp_ctx_creat
                'simplyp_stream_out', 'simplyp_waterbody', 'simplyp_gof_waterbody', 'simplyp_gof_spearman', 'simplyp_eval_units',
                'simplyp_quantiles', 'simplyp_state_bytes', 'simplyp_set_state', 'simplyp_fetch_packed',
                'simplyp_pack_roundtrip_host', 'simplyp_fetch_packed_pred', 'simplyp_pack_roundtrip_host_pred',
-               'simplyp_time_quantiles']
+               'simplyp_time_quantiles', 'simplyp_predictive_series', 'simplyp_predictive_bands']
 
 _lib = None
 
@@ -43,6 +43,7 @@ def build(force=False, verbose=False):
     srcs = [os.path.join(CSRC, 'simplyp_hip.hip'), os.path.join(CSRC, 'simplyp_kernels.hip.h'),
             os.path.join(CSRC, 'simplyp_gof.hip.h'), os.path.join(CSRC, 'simplyp_waterbody.hip.h'),
             os.path.join(CSRC, 'simplyp_quantile.hip.h'), os.path.join(CSRC, 'simplyp_time_quantile.hip.h'),
+            os.path.join(CSRC, 'simplyp_predictive.hip.h'),
             os.path.join(CSRC, 'simplyp_pack.h'),
             os.path.join(CSRC, 'simplyp_pack_stream.h'),
             os.path.join(INCLUDE, 'simplyp.h'), os.path.join(INCLUDE, 'simplyp_controller.h')]
@@ -111,6 +112,13 @@ def lib():
     L.simplyp_time_quantiles.argtypes = [vp, C.POINTER(abi.Dims), C.c_uint32, C.POINTER(C.c_int32), C.c_int32, dp, i32p, dp, dp,
                                          C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                          C.POINTER(C.c_double), C.c_int32, dp, C.POINTER(C.c_int32), C.POINTER(abi.TqInfo)]
+    pred_args = [vp, C.POINTER(abi.Dims), C.c_uint32, C.POINTER(C.c_int32), C.c_int32, dp, i32p]
+    L.simplyp_predictive_series.restype = C.c_int
+    L.simplyp_predictive_series.argtypes = pred_args + [dp, dp, C.POINTER(C.c_int32), C.c_int32, dp, C.c_uint64, C.c_int32,
+                                                        C.c_int32, dp]
+    L.simplyp_predictive_bands.restype = C.c_int
+    L.simplyp_predictive_bands.argtypes = pred_args + [vp, dp, dp, C.POINTER(C.c_int32), C.c_int32, dp, C.c_uint64, C.c_int32,
+                                                       C.POINTER(C.c_double), C.c_int32, dp, C.POINTER(abi.PredInfo)]
     L.simplyp_stream_out.restype = C.c_int
     L.simplyp_stream_out.argtypes = [vp, vp, C.c_int64]
     L.simplyp_fetch_packed.restype = C.c_int
@@ -658,6 +666,90 @@ class Engine(object):
         d = info.as_dict()
         d['n_days'] = n_days
         return stats[0], stats[1], d
+
+    def _predictive_args(self, out, out_mask, series, err_m, f_tdp, reach_params, out_reaches, member_of_slot):
+        """The arguments ``predictive_series`` and ``predictive_bands`` share, checked and on the device."""
+        torch = self.torch
+        if not torch.is_tensor(out) or out.dim() != 4 or out.dtype != torch.float64 or not out.is_contiguous() \
+                or out.device != self.tdev:
+            raise ValueError("out must be a contiguous float64 tensor [n_cols, D, n_reaches, E] on %s" % (self.tdev,))
+        ncols, D, n_or, E = (int(x) for x in out.shape)
+        oreach = _i32(out_reaches)
+        rp = None if reach_params is None else self.to_device(reach_params, torch.float64)
+        S = int(rp.shape[1]) if rp is not None else (n_or if oreach is None else max(n_or, int(oreach.max()) + 1))
+        if ncols != bin(out_mask).count('1') or n_or != (S if oreach is None else len(oreach)) \
+                or (rp is not None and int(rp.shape[2]) != E):
+            raise ValueError("out %s does not match out_mask / out_reaches / reach_params" % (tuple(out.shape),))
+        sa = np.ascontiguousarray(series, dtype=np.int32)
+        if sa.ndim != 1:
+            raise ValueError("series must be a list of series ids")
+        em = None
+        if err_m is not None:
+            if not torch.is_tensor(err_m):
+                err_m = np.ascontiguousarray(np.broadcast_to(np.asarray(err_m, dtype=np.float64), (len(sa), E)))
+            em = self.to_device(err_m, torch.float64)
+            if tuple(em.shape) != (len(sa), E):
+                raise ValueError("err_m must be a scalar or [n_series, E] (member order)")
+        ft = None if f_tdp is None else self._f_tdp(f_tdp, E)
+        if member_of_slot is not None and (member_of_slot.dtype != torch.int32 or tuple(member_of_slot.shape) != (E,)):
+            raise ValueError("member_of_slot must be an int32 device tensor with one entry per member")
+        i32 = C.POINTER(C.c_int32)
+        head = (self._h, C.byref(abi.Dims(E, S, D, 1)), int(out_mask), None if oreach is None else oreach.ctypes.data_as(i32), n_or,
+                out.data_ptr(), None if member_of_slot is None else member_of_slot.data_ptr())
+        tail = (None if ft is None else ft.data_ptr(), None if rp is None else rp.data_ptr(), sa.ctypes.data_as(i32), len(sa),
+                None if em is None else em.data_ptr())
+        return head, tail, (len(sa), D, n_or, E), [oreach, rp, sa, em, ft]
+
+    def predictive_series(self, out, out_mask, series, err_m=None, seed=0, day0=0, normals=False, f_tdp=None,
+                          reach_params=None, out_reaches=None, member_of_slot=None):
+        """The series a predictive band is taken over, materialised (``simplyp_predictive_series``): from the daily table
+        ``out`` [n_cols, D, n_reaches, E] of a previous ``run`` the named ``series`` (ids as for ``time_quantiles``), with the
+        reference's error model ``v + norm(0, m v)`` drawn on the device when ``err_m`` (a scalar or [n_series, E] in member
+        order) is given -- individual noisy realisations of every member.  The draw is a pure function of (``seed``, member,
+        ``day0`` + d, model reach, series id): ``simplyp_amd.predictive`` restates it.  ``normals=True`` returns the standard
+        normals z instead of the values.  Returns a device tensor [n_series, D, n_reaches, E], member axis ordered like ``out``'s."""
+        torch = self.torch
+        head, tail, shape, keep = self._predictive_args(out, out_mask, series, err_m, f_tdp, reach_params, out_reaches, member_of_slot)
+        table = torch.empty(shape, dtype=torch.float64, device=self.tdev)
+        with torch.cuda.device(self.tdev):
+            self._bind_stream()
+            rc = lib().simplyp_predictive_series(*(head + tail + (C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(day0),
+                                                                   1 if normals else 0, table.data_ptr())))
+        self._check(rc, 'simplyp_predictive_series')
+        del keep
+        return table
+
+    def predictive_bands(self, out, out_mask, q, series, err_m=None, seed=0, day0=0, include=None, f_tdp=None,
+                         reach_params=None, out_reaches=None, member_of_slot=None):
+        """Order statistics across the members of the series ``predictive_series`` would write, for every (series, day,
+        reach) (``simplyp_predictive_bands``): the reference's overall predictive band with ``err_m``, the parameter-only
+        band of the series without.  The series are generated and selected chunk by chunk on the device; the table is only
+        read.  ``q``, ``include`` and the rank rule as for ``quantiles``.  Returns (lower, upper, info): device tensors
+        [K, n_series, D, n_reaches]; ``interpolate_quantiles`` with ``info['n_used']`` turns them into numpy's values."""
+        torch = self.torch
+        head, tail, shape, keep = self._predictive_args(out, out_mask, series, err_m, f_tdp, reach_params, out_reaches, member_of_slot)
+        E = shape[3]
+        qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+        if qa.ndim != 1:
+            raise ValueError("q must be a list of probabilities")
+        inc = None
+        if include is not None:
+            inc = include if torch.is_tensor(include) else torch.from_numpy(np.ascontiguousarray(np.asarray(include) != 0))
+            inc = (inc != 0).to(torch.uint8).to(self.tdev).contiguous()
+            if tuple(inc.shape) != (E,):
+                raise ValueError("include must have one entry per member")
+        stats = torch.empty((2, max(len(qa), 1)) + shape[:3], dtype=torch.float64, device=self.tdev)
+        info = abi.PredInfo()
+        with torch.cuda.device(self.tdev):
+            self._bind_stream()
+            rc = lib().simplyp_predictive_bands(*(head + (None if inc is None else inc.data_ptr(),) + tail
+                                                  + (C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(day0),
+                                                     qa.ctypes.data_as(C.POINTER(C.c_double)), len(qa), stats.data_ptr(),
+                                                     C.byref(info))))
+        self._check(rc, 'simplyp_predictive_bands')
+        del keep
+        return stats[0], stats[1], info.as_dict()
+
 
 
 def interpolate_quantiles(lower, upper, q, n_used):

@@ -317,7 +317,8 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
                           reduce=None, obs_dict=None, keep_daily=True, snow_in_kernel=None, forcing_of_member=None,
                           waterbody=None, waterbody_obs=None, spearman=False, devices=None, quantiles=None,
                           quantile_members=None, initial_state=None, return_state=False, time_quantiles=None,
-                          time_quantile_series=None, time_quantile_periods=None):
+                          time_quantile_series=None, time_quantile_periods=None, predictive_series=None, predictive_m=None,
+                          predictive_seed=0, predictive_day0=0):
     """Run an ensemble of parameter sets through the engine in one call.
 
     ``overrides``: dict name -> array[E] (member parameters, see ``marshal.PM_NAMES``) or
@@ -394,6 +395,22 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     members of these per-member statistics -- e.g. the ensemble's uncertainty band of the flow-duration curve -- comes back
     under ``['time_quantiles']['quantiles']`` (same members as the daily band: ``quantile_members``, non-finite ones left out).
 
+    ``predictive_series``: a list of 1 to 32 names -- columns of the table or the six ``df_R`` names ``Q_cumecs`` ... ``SRP_mgl``
+    (``abi.TQ_DERIVED_SERIES``, what ``obs_dict`` holds observations of) -- whose bands ACROSS THE MEMBERS are selected on the
+    device for every day and reach (``simplyp_predictive_bands``): the two frames of the reference's
+    ``get_uncertainty_intervals`` (Development/2016/MCMC.ipynb).  Needs ``quantiles`` (the probabilities) and takes
+    ``quantile_members`` as given; non-finite members are left out as for ``quantiles``; the flux columns and named columns
+    missing from ``outputs`` are added.  ``predictive_m``: the error model's ``m`` of ``sigma = m * sim`` -- None (no overall
+    band), a float, an array [E], or a dict name -> float or array [E] (a series the dict does not name gets 0); finite and
+    >= 0 (``ValueError``).  With it every member's series has ``norm(0, m * sim)`` added before the percentiles are taken,
+    drawn on the device as a pure function of (``predictive_seed``, member, ``predictive_day0`` + day, reach, series):
+    ``simplyp_amd.predictive`` restates the stream, ``Engine.predictive_series`` returns the realisations themselves.  The
+    result gains ``'predictive'`` = dict(q, series, param_only = dict(data[K, n_series, D, n_reaches], lower, upper), overall =
+    the same or None without ``predictive_m``, n_members, seed, day0, info); ``visualise_results.band_coverage`` takes
+    ``overall``.  A device reduction: ``keep_daily=False`` behaves as for ``quantiles``.  ``ValueError`` with ``reduce``, with
+    ``devices=[...]`` (same reason as ``quantiles``) and for unknown names.  ``run_simply_p_ensemble_windows`` passes each
+    window its ``day0 = predictive_day0 + lo``, so the windows' bands laid end to end are the single call's, bit for bit.
+
     ``return_state=True``: the result gains ``'state'`` = dict(rows (``abi.STATE_ROWS``), reaches (all sub-catchments),
     data[S, 16, E], end = ``met_df.index[-1]``): the model state after the last day, in member order (numpy, or a device
     tensor with ``to_host=False``; ``return_state='device'`` keeps it on the device whatever ``to_host`` says -- with
@@ -450,6 +467,31 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
             tq_pod = np.ascontiguousarray(tq_pod, dtype=np.int32)
         elif time_quantile_periods is not None and time_quantile_periods != 'annual':
             raise ValueError("time_quantile_periods must be None, 'annual' or an int array [D] of period indices >= -1")
+    pr_names = pr_ids = pr_m = None
+    if predictive_series is None:
+        if predictive_m is not None:
+            raise ValueError("predictive_m given without predictive_series")
+    else:
+        if quantiles is None:
+            raise ValueError("predictive_series needs quantiles: the probabilities of the bands")
+        if reduce is not None:
+            raise ValueError("predictive_series needs the daily series: it cannot be combined with reduce")
+        if devices is not None:
+            raise ValueError("predictive_series cannot be combined with devices=[...]: a band across the whole ensemble is not a "
+                             "function of the member blocks' bands")
+        pr_names = [predictive_series] if isinstance(predictive_series, str) else list(predictive_series)
+        unknown = [c for c in pr_names if c not in marshal.ALL_COLUMNS and c not in abi.TQ_DERIVED_SERIES]
+        if unknown or not 1 <= len(pr_names) <= 32:
+            raise ValueError("predictive_series must be 1 to 32 names among the reference's columns and %s (unknown: %s)"
+                             % (abi.TQ_DERIVED_SERIES, unknown))
+        if isinstance(predictive_m, dict) and [c for c in predictive_m if c not in pr_names]:
+            raise ValueError("predictive_m names series that predictive_series does not: %s"
+                             % [c for c in predictive_m if c not in pr_names])
+        pr_ids = [abi.TQ_DERIVED + abi.TQ_DERIVED_SERIES.index(c) if c in abi.TQ_DERIVED_SERIES else marshal.ALL_COLUMNS.index(c)
+                  for c in pr_names]
+        predictive_seed, predictive_day0 = int(predictive_seed), int(predictive_day0)
+        if not 0 <= predictive_seed < 1 << 64 or not 0 <= predictive_day0 < 1 << 31:
+            raise ValueError("predictive_seed must be in [0, 2^64) and predictive_day0 in [0, 2^31)")
     marshal.prologue(p_SU, p_LU, p_SC, p)
     scs = marshal.sc_list(p)
     up_ptr, up_idx, _ = marshal.topology(p_struc, p)
@@ -466,6 +508,15 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         quantile_members = np.ascontiguousarray(np.asarray(quantile_members) != 0)
         if quantile_members.shape != (E,):
             raise ValueError("quantile_members needs one flag per member")
+    if predictive_m is not None:                     # [n_series, E] in member order
+        per = predictive_m if isinstance(predictive_m, dict) else {c: predictive_m for c in pr_names}
+        try:
+            pr_m = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(per.get(c, 0.0), dtype=np.float64), (E,))
+                                                  for c in pr_names]))
+        except (TypeError, ValueError):
+            raise ValueError("predictive_m must be a float, an array [E], or a dict name -> float or array [E]")
+        if not (np.isfinite(pr_m).all() and (pr_m >= 0).all()):
+            raise ValueError("predictive_m must be finite and >= 0")
     met_first = met_df[0] if isinstance(met_df, (list, tuple)) else met_df
     if devices is None:
         bounds = [(0, E)]
@@ -528,6 +579,10 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
             tq_pod = np.ascontiguousarray(tq_pod, dtype=np.int32)
         if tq_pod is not None and tq_pod.shape != (len(met_df),):
             raise ValueError("time_quantile_periods needs one period index per day")
+    if pr_names is not None:
+        if any(i >= abi.TQ_DERIVED for i in pr_ids):
+            cols += [c for c in ('Qr', 'Msus_kg/day', 'TDP_kg/day', 'PP_kg/day') if c not in cols]
+        cols += [c for c in pr_names if c in marshal.ALL_COLUMNS and c not in cols]
     mask = marshal.mask_of_columns(cols)
     if mask & marshal.MASK_D_SNOW and not snow_in_kernel:
         raise ValueError("output 'D_snow' is the per-member snow depth of the in-kernel snow module: needs snow_in_kernel=True "
@@ -617,6 +672,11 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
             part['tq'] = (lo_h if to_host else lo_d, up_h if to_host else up_d, tdata, tinfo)
             if quantiles is not None:            # the band across the members of the per-member statistics
                 part['tq_quant'] = eng.quantiles(eng.to_device(tdata), quantiles, include=inc)
+        if pr_names is not None:                 # the bands of the named series: parameter-only, and with the error model drawn
+            pkw = dict(seed=predictive_seed, day0=predictive_day0, include=inc, f_tdp=ft, reach_params=rp_d,
+                       out_reaches=oreach, member_of_slot=mos)
+            part['pred'] = (eng.predictive_bands(out_d, mask, quantiles, pr_ids, **pkw),
+                            None if pr_m is None else eng.predictive_bands(out_d, mask, quantiles, pr_ids, err_m=pr_m, **pkw))
         part['out_d'] = None if (reduced_on_device and not keep_daily) else out_d
         return part
 
@@ -678,6 +738,15 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         res['quantiles'] = band(*parts[0]['quant'])
         if res.get('waterbody') is not None:
             res['waterbody']['quantiles'] = band(*parts[0]['wb_quant'])
+    if pr_names is not None:
+        po, ov = parts[0]['pred']
+        po_b, ov_b = band(*po), None if ov is None else band(*ov)
+        info = dict(param_only=po_b.pop('info'), overall=None if ov_b is None else ov_b.pop('info'))
+        for b_ in (po_b, ov_b):
+            if b_ is not None:
+                del b_['q'], b_['n_members']
+        res['predictive'] = dict(q=list(quantiles), series=list(pr_names), param_only=po_b, overall=ov_b,
+                                 n_members=po[2]['n_used'], seed=predictive_seed, day0=predictive_day0, info=info)
     if time_quantiles is not None:
         tinfo = parts[0]['tq'][3]
         res['time_quantiles'] = dict(q=list(time_quantiles), series=list(tq_names), periods=tq_labels,
@@ -731,7 +800,7 @@ def run_simply_p_ensemble_windows(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_
     (``simplyp_set_state``), so the windows' tables laid end to end ARE the table of the single call, bit for bit, and so
     are the summed ``rhs_evals`` / ``steps`` / ``rejected``; a window's table exists only while the caller holds its item, so
     the peak device and host footprint is one window's: the daily series, per-year goodness of fit or percentile bands of
-    an ensemble whose whole table would not fit anywhere.  ``obs_dict`` / ``waterbody`` / ``quantiles`` / ``time_quantiles`` apply per window
+    an ensemble whose whole table would not fit anywhere.  ``obs_dict`` / ``waterbody`` / ``quantiles`` / ``time_quantiles`` / ``predictive_series`` apply per window
     (an array ``time_quantile_periods`` covers the whole run and is cut with the days).
     With ``reduce``, window boundaries must fall on period boundaries (``ValueError``).
 
@@ -758,6 +827,8 @@ def run_simply_p_ensemble_windows(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_
             if tqp is not None and not isinstance(tqp, str):         # the window's days, its periods numbered from 0
                 part = np.asarray(tqp)[lo:hi]
                 kw['time_quantile_periods'] = np.where(part >= 0, part - (part[part >= 0].min() if (part >= 0).any() else 0), -1)
+            if kw.get('predictive_series') is not None:             # the stream is indexed by the run's day, not the window's
+                kw['predictive_day0'] = int(kwargs.get('predictive_day0', 0)) + lo
             mets = [m.iloc[lo:hi] for m in met_sets]
             res = run_simply_p_ensemble(mets if isinstance(met_df, (list, tuple)) else mets[0], p_struc, p_SU, p_LU, p_SC, p,
                                         dynamic_options, initial_state=state, return_state='device', **kw)
