@@ -32,7 +32,9 @@ extern "C" {
  * 17 still with simplyp_fetch_packed_pred and simplyp_pack_roundtrip_host_pred: two more entry points, nothing else.
  * 17 still with simplyp_time_quantiles, simplyp_tq_info and SIMPLYP_TQ_DERIVED: one more entry point with its own info struct.
  * 17 still with simplyp_predictive_series, simplyp_predictive_bands and simplyp_pred_info: two more entry points, one more info
- * struct; no existing struct, enum or entry point changes. */
+ * struct; no existing struct, enum or entry point changes.
+ * 17 still with simplyp_mcmc_propose, simplyp_mcmc_log_prob, simplyp_mcmc_accept and simplyp_mcmc_info: three more entry points, one
+ * more info struct, purely additive again. */
 #define SIMPLYP_ABI_VERSION 17
 
 typedef enum {
@@ -706,6 +708,90 @@ int simplyp_predictive_bands(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_
                              const double* err_m, uint64_t seed, int32_t day0,
                              const double* q /* host [K] */, int32_t K,
                              double* order_stats, simplyp_pred_info* info);
+
+/* ---- sampling the posterior: the affine-invariant ensemble sampler of the reference's calibration notebook
+ * (Development/2016/MCMC.ipynb, cell 10: emcee.EnsembleSampler(n_walk, n_dim, log_posterior).run_mcmc(start, n_steps)), the stretch
+ * move of Goodman & Weare (2010), with the walkers' positions, the model runs and the decisions all on the device.
+ *
+ * W walkers (W even, W >= 2 n_dim, 1 <= n_dim <= 16) in two halves of h = W / 2; positions theta [n_dim][W] and log posterior
+ * lp [W] on the device.  Step t (absolute, counted from the start of the chain) moves half 0, then half 1; the active walkers of
+ * half k are i in [k h, (k + 1) h), their partners come from the other half, offset c = (1 - k) h, at the positions it holds then.
+ * One half-step is
+ *     propose -> simplyp_run + simplyp_gof on the h run points (or the caller's own target) -> log_prob -> accept
+ * The random stream is counter-based like the predictive stream's: Philox4x32-10 with key (seed & 0xffffffff, seed >> 32);
+ *     draw A  counter (i, t, 0, 0x4D434D43):  u_z = uniform(x0, x1), partner j = c + (((uint64)x2 * h) >> 32)
+ *     draw B  counter (i, t, 1, 0x4D434D43):  u_a = uniform(x0, x1)
+ * with uniform(hi, lo) = ((((uint64)hi << 32) | lo) >> 12) + 0.5) 2^-52 in (0, 1).  Then
+ *     s = (a - 1) u_z + 1,  z = (s s) / a                    emcee's g(z) on [1/a, a]
+ *     y[d] = x_j[d] + z (x_i[d] - x_j[d])
+ *     inside  = lo[d] <= y[d] < hi[d] for every d              the reference's log_prior; a NaN is outside
+ *     run point = y where inside, else x_i                   the model never sees a point outside the box
+ *     margin = (n_dim - 1) ln z + lp_y - lp[i] - ln u_a       accept iff inside, lp_y is not NaN and margin > 0
+ * Everything but the two logarithms is integer arithmetic or + * / in fp64 without contraction: partner, z, y and inside are
+ * the same bits on any implementation; simplyp_amd/mcmc.py restates the move in NumPy.  Neither the launch shape nor the time
+ * enters.  All three entries are synchronous on the context's stream and return SIMPLYP_ERR_ARG with nothing launched for an odd
+ * W or W < 2 n_dim, n_dim outside 1..16, half outside {0, 1}, a <= 1 or NaN, lo[d] >= hi[d] or a NaN bound, a target outside
+ * [-2, SIMPLYP_NP_M), a NULL required pointer. ------------------------------------------------------------------------------ */
+typedef struct {
+    double  kernel_ms;     /* the entry's kernel, HIP events on the context's stream                                        */
+    int32_t n_inside;      /* active walkers whose proposal lies inside the box (log_prob without `inside`: h)              */
+    int32_t n_accepted;    /* accept: proposals taken; 0 from the other two entries                                         */
+    int32_t n_nan;         /* log_prob, accept: proposals whose lp was NaN (log_prob turns them into -inf); 0 from propose  */
+    int32_t reserved;
+} simplyp_mcmc_info;
+
+/*
+ * simplyp_mcmc_propose -- the proposals of half `half` at step t, and the run points scattered into the arrays of the run.
+ *   lo, hi          HOST    [n_dim] the prior box
+ *   target          HOST    [n_dim] where dimension d's run point goes: 0 .. SIMPLYP_NP_M - 1 = that row of member_params,
+ *                           -1 = f_tdp, -2 = nowhere (an error-model m, which no model input holds); a row or f_tdp at most once
+ *   theta           device  [n_dim][W], only read
+ *   prop            device  [n_dim][h]  y
+ *   inside          device  [h] int32, 1 or 0
+ *   member_params   device  [SIMPLYP_NP_M][h] of an ensemble of h members, or NULL when no target is >= 0; rows that no dimension
+ *                           names are not touched
+ *   f_tdp           device  [h], or NULL when no target is -1
+ *   info            host    may be NULL
+ */
+int simplyp_mcmc_propose(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t half, double a, uint64_t seed, uint32_t t,
+                         const double* lo /* host */, const double* hi /* host */, const int32_t* target /* host */,
+                         const double* theta, double* prop, int32_t* inside, double* member_params, double* f_tdp,
+                         simplyp_mcmc_info* info);
+
+/*
+ * simplyp_mcmc_log_prob -- the log posterior of the h run points from the table simplyp_gof left on the device: the sum over the
+ * given (variable, output reach) pairs of the reference's Gaussian likelihood with sigma = m_v sim,
+ *     -0.5 n ln(2 pi) - n ln(m_v) - SUM_LOG_SIM - SUM_RELSQ / (2 m_v m_v)
+ * in that order of operations; the flat prior adds nothing inside the box.  -inf where `inside` is 0, where the member's status
+ * carries SIMPLYP_STATUS_NONFINITE, where an m_v <= 0 and where the sum is NaN (a variable with 10 or fewer observations).
+ *   gof             device  [SIMPLYP_N_GOF_STATS][SIMPLYP_N_GOF_VARS][n_out_reaches][h]
+ *   status          device  [h] as written by simplyp_run, or NULL
+ *   inside          device  [h] as written by the proposal, or NULL = all inside
+ *   pair_var, pair_reach   HOST  [n_pairs], 1 <= n_pairs <= 32: SIMPLYP_GOF_v and the position among the output reaches
+ *   m_dim           HOST    [SIMPLYP_N_GOF_VARS] the row of prop that holds the variable's m, or -1: m_const[v]
+ *   m_const         HOST    [SIMPLYP_N_GOF_VARS]
+ *   prop            device  [n_dim][h]
+ *   lp_prop         device  [h]
+ */
+int simplyp_mcmc_log_prob(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t n_out_reaches, const double* gof,
+                          const int32_t* status, const int32_t* inside,
+                          const int32_t* pair_var /* host */, const int32_t* pair_reach /* host */, int32_t n_pairs,
+                          const int32_t* m_dim /* host */, const double* m_const /* host */,
+                          const double* prop, double* lp_prop, simplyp_mcmc_info* info);
+
+/*
+ * simplyp_mcmc_accept -- the decisions of half `half` at step t, in place.  z is recomputed from the counter; lp_prop is a plain
+ * device array, so a caller may sample any target: propose, evaluate ln p at prop by its own means, accept.
+ *   prop, inside    device  as written by the proposal of the same (half, t)
+ *   lp_prop         device  [h] ln p of the proposals; -inf and NaN are refused
+ *   theta, lp       device  [n_dim][W], [W]: the active half's accepted lanes are overwritten
+ *   n_accept        device  [W] int32: + 1 where accepted
+ *   chain_row       device  [n_dim + 1][W] or NULL: the active half's positions and lp after the decision; after half 1 of a
+ *                           step every lane of the row has been written
+ */
+int simplyp_mcmc_accept(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t half, double a, uint64_t seed, uint32_t t,
+                        const double* prop, const int32_t* inside, const double* lp_prop,
+                        double* theta, double* lp, int32_t* n_accept, double* chain_row, simplyp_mcmc_info* info);
 
 /*
  * simplyp_eval_units -- the path's scalar device functions on caller-given arguments, one thread per row: how the tests pin the

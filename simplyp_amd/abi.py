@@ -89,6 +89,18 @@ class PredInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
 
 
+class McmcInfo(C.Structure):
+    """simplyp_mcmc_info of include/simplyp.h."""
+    _fields_ = [('kernel_ms', C.c_double), ('n_inside', C.c_int32), ('n_accepted', C.c_int32), ('n_nan', C.c_int32),
+                ('reserved', C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
+
+
+MCMC_TARGET_F_TDP = -1          # simplyp_mcmc_propose: the dimension goes to f_tdp
+MCMC_TARGET_NONE = -2           # ... nowhere: an error-model m
+
 TQ_DERIVED = 64                                                                       # SIMPLYP_TQ_DERIVED
 TQ_DERIVED_SERIES = ['Q_cumecs', 'SS_mgl', 'TDP_mgl', 'PP_mgl', 'TP_mgl', 'SRP_mgl']  # df_R names, in SIMPLYP_GOF_* order
 

@@ -23,6 +23,7 @@
 #include "simplyp_quantile.hip.h"
 #include "simplyp_time_quantile.hip.h"
 #include "simplyp_predictive.hip.h"
+#include "simplyp_mcmc.hip.h"
 #include "simplyp_pack_stream.h"
 
 namespace {
@@ -51,6 +52,7 @@ struct simplyp_ctx {
     DeviceBuf quant;          // simplyp_quantiles: 2 x int32 (members used, sweeps) | [E] uint8 include mask in column order
     DeviceBuf tquant;         // simplyp_time_quantiles: sweeps, rows read | day lists, ranks, output reaches
     DeviceBuf pred;           // simplyp_predictive_*: [R] int32 output reaches (256-byte slot) | a chunk of days [n_series][days][R][E]
+    DeviceBuf mcmc;           // simplyp_mcmc_*: 4 x uint32 (inside, accepted, NaN)
     DeviceBuf queue;          // ticket, error, done[n_groups] (uint32) | ckpt[CKPT_N][E] (double)
     // streamed output (simplyp_stream_out): the armed destination, the chunk flags the queue kernel raises in pinned host
     // memory, and the host thread that turns a raised flag into the D2H copies of that chunk's rows on `copy_stream`
@@ -981,6 +983,7 @@ void simplyp_ctx_destroy(simplyp_ctx* ctx)
     if (ctx->quant.ptr) (void)hipFree(ctx->quant.ptr);
     if (ctx->tquant.ptr) (void)hipFree(ctx->tquant.ptr);
     if (ctx->pred.ptr) (void)hipFree(ctx->pred.ptr);
+    if (ctx->mcmc.ptr) (void)hipFree(ctx->mcmc.ptr);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
     if (ctx->ev_main) (void)hipEventDestroy(ctx->ev_main);
@@ -2231,6 +2234,154 @@ int simplyp_predictive_bands(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_
 {
     SIMPLYP_GUARD(ctx, predictive_bands_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, include, f_tdp,
                                              reach_params, series, n_series, err_m, seed, day0, q, K, order_stats, info))
+}
+
+// ---- the stretch move (simplyp_mcmc.hip.h) ----------------------------------------------------------------------------------
+// What the three entries check alike; fills the move.
+static int mcmc_move(simplyp_ctx* ctx, const char* me, int32_t W, int32_t n_dim, int32_t half, double a, uint64_t seed, uint32_t t,
+                     simplyp::McmcMove& mv)
+{
+    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a run is pending on this context; call simplyp_sync first", me);
+    if (n_dim < 1 || n_dim > simplyp::MCMC_MAX_DIM)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_dim must be in [1, %d] (got %d)", me, simplyp::MCMC_MAX_DIM, (int)n_dim);
+    if (W < 2 || (W & 1) || W < 2 * n_dim)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: W must be even and >= 2 n_dim (got W = %d, n_dim = %d)", me, (int)W, (int)n_dim);
+    if (half < 0 || half > 1) return fail(ctx, SIMPLYP_ERR_ARG, "%s: half must be 0 or 1 (got %d)", me, (int)half);
+    if (!(a > 1.0)) return fail(ctx, SIMPLYP_ERR_ARG, "%s: the stretch scale a must be > 1 (got %g)", me, a);
+    mv.W = W; mv.h = W / 2; mv.n_dim = n_dim; mv.half = half; mv.a = a;
+    mv.key0 = (uint32_t)(seed & 0xFFFFFFFFull); mv.key1 = (uint32_t)(seed >> 32); mv.t = t;
+    return SIMPLYP_OK;
+}
+
+// The counters zeroed before a launch; read back with the launch's time afterwards.
+static int mcmc_begin(simplyp_ctx* ctx, unsigned*& counters)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = ensure(ctx, ctx->mcmc, 4 * sizeof(unsigned))) return rc;
+    counters = (unsigned*)ctx->mcmc.ptr;
+    HIP_TRY(ctx, hipMemsetAsync(counters, 0, 4 * sizeof(unsigned), ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    return SIMPLYP_OK;
+}
+
+static int mcmc_end(simplyp_ctx* ctx, simplyp_mcmc_info* info)
+{
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+    unsigned c[4] = {0, 0, 0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(c, ctx->mcmc.ptr, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (info) {
+        float ms = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+        info->kernel_ms = ms;
+        info->n_inside = (int32_t)c[0]; info->n_accepted = (int32_t)c[1]; info->n_nan = (int32_t)c[2]; info->reserved = 0;
+    }
+    return SIMPLYP_OK;
+}
+
+static int mcmc_propose_impl(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t half, double a, uint64_t seed, uint32_t t,
+                             const double* lo, const double* hi, const int32_t* target, const double* theta,
+                             double* prop, int32_t* inside, double* member_params, double* f_tdp, simplyp_mcmc_info* info)
+{
+    const char* me = "simplyp_mcmc_propose";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    simplyp::McmcProposeArgs g{};
+    if (int rc = mcmc_move(ctx, me, W, n_dim, half, a, seed, t, g.mv)) return rc;
+    if (!lo || !hi || !target || !theta || !prop || !inside)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: lo, hi, target, theta, prop and inside must not be NULL", me);
+    bool to_params = false, to_f_tdp = false;
+    for (int d = 0; d < n_dim; ++d) {
+        if (!(lo[d] < hi[d])) return fail(ctx, SIMPLYP_ERR_ARG, "%s: the box needs lo[%d] < hi[%d] (got %g, %g)", me, d, d, lo[d], hi[d]);
+        if (target[d] < simplyp::MCMC_TARGET_NONE || target[d] >= SIMPLYP_NP_M)
+            return fail(ctx, SIMPLYP_ERR_ARG, "%s: target[%d] = %d is outside [-2, %d)", me, d, (int)target[d], (int)SIMPLYP_NP_M);
+        for (int e = 0; e < d; ++e)
+            if (target[d] != simplyp::MCMC_TARGET_NONE && target[e] == target[d])
+                return fail(ctx, SIMPLYP_ERR_ARG, "%s: target[%d] and target[%d] name the same row (%d)", me, e, d, (int)target[d]);
+        to_params = to_params || target[d] >= 0;
+        to_f_tdp = to_f_tdp || target[d] == simplyp::MCMC_TARGET_F_TDP;
+        g.lo[d] = lo[d]; g.hi[d] = hi[d]; g.target[d] = target[d];
+    }
+    if ((to_params && !member_params) || (to_f_tdp && !f_tdp))
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: a target names member_params or f_tdp, which is NULL", me);
+    g.theta = theta; g.prop = prop; g.inside = inside; g.member_params = member_params; g.f_tdp = f_tdp;
+    if (int rc = mcmc_begin(ctx, g.counters)) return rc;
+    hipLaunchKernelGGL(simplyp::simplyp_mcmc_propose_kernel, dim3((unsigned)((g.mv.h + simplyp::MCMC_THREADS - 1) / simplyp::MCMC_THREADS)),
+                       dim3(simplyp::MCMC_THREADS), 0, ctx->stream, g);
+    return mcmc_end(ctx, info);
+}
+
+static int mcmc_log_prob_impl(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t n_out_reaches, const double* gof,
+                              const int32_t* status, const int32_t* inside, const int32_t* pair_var, const int32_t* pair_reach,
+                              int32_t n_pairs, const int32_t* m_dim, const double* m_const, const double* prop, double* lp_prop,
+                              simplyp_mcmc_info* info)
+{
+    const char* me = "simplyp_mcmc_log_prob";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    simplyp::McmcMove mv{};
+    if (int rc = mcmc_move(ctx, me, W, n_dim, 0, 2.0, 0, 0, mv)) return rc;
+    if (!gof || !pair_var || !pair_reach || !m_dim || !m_const || !prop || !lp_prop)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: gof, pair_var, pair_reach, m_dim, m_const, prop and lp_prop must not be NULL", me);
+    if (n_out_reaches < 1) return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_out_reaches must be >= 1 (got %d)", me, (int)n_out_reaches);
+    if (n_pairs < 1 || n_pairs > simplyp::MCMC_MAX_PAIRS)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_pairs must be in [1, %d] (got %d)", me, simplyp::MCMC_MAX_PAIRS, (int)n_pairs);
+    simplyp::McmcLogProbArgs g{};
+    for (int p = 0; p < n_pairs; ++p) {
+        if (pair_var[p] < 0 || pair_var[p] >= SIMPLYP_N_GOF_VARS || pair_reach[p] < 0 || pair_reach[p] >= n_out_reaches)
+            return fail(ctx, SIMPLYP_ERR_ARG, "%s: pair %d = (variable %d, output reach %d) is out of range", me, p, (int)pair_var[p], (int)pair_reach[p]);
+        g.pair_var[p] = pair_var[p]; g.pair_reach[p] = pair_reach[p];
+    }
+    for (int v = 0; v < SIMPLYP_N_GOF_VARS; ++v) {
+        if (m_dim[v] < -1 || m_dim[v] >= n_dim)
+            return fail(ctx, SIMPLYP_ERR_ARG, "%s: m_dim[%d] = %d is neither -1 nor a row of prop", me, v, (int)m_dim[v]);
+        g.m_dim[v] = m_dim[v]; g.m_const[v] = m_const[v];
+    }
+    g.h = mv.h; g.R = n_out_reaches; g.n_pairs = n_pairs;
+    g.gof = gof; g.status = status; g.inside = inside; g.prop = prop; g.lp_prop = lp_prop;
+    if (int rc = mcmc_begin(ctx, g.counters)) return rc;
+    hipLaunchKernelGGL(simplyp::simplyp_mcmc_log_prob_kernel, dim3((unsigned)((g.h + simplyp::MCMC_THREADS - 1) / simplyp::MCMC_THREADS)),
+                       dim3(simplyp::MCMC_THREADS), 0, ctx->stream, g);
+    return mcmc_end(ctx, info);
+}
+
+static int mcmc_accept_impl(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t half, double a, uint64_t seed, uint32_t t,
+                            const double* prop, const int32_t* inside, const double* lp_prop, double* theta, double* lp,
+                            int32_t* n_accept, double* chain_row, simplyp_mcmc_info* info)
+{
+    const char* me = "simplyp_mcmc_accept";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    simplyp::McmcAcceptArgs g{};
+    if (int rc = mcmc_move(ctx, me, W, n_dim, half, a, seed, t, g.mv)) return rc;
+    if (!prop || !inside || !lp_prop || !theta || !lp || !n_accept)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: prop, inside, lp_prop, theta, lp and n_accept must not be NULL", me);
+    g.prop = prop; g.inside = inside; g.lp_prop = lp_prop; g.theta = theta; g.lp = lp; g.n_accept = n_accept; g.chain_row = chain_row;
+    if (int rc = mcmc_begin(ctx, g.counters)) return rc;
+    hipLaunchKernelGGL(simplyp::simplyp_mcmc_accept_kernel, dim3((unsigned)((g.mv.h + simplyp::MCMC_THREADS - 1) / simplyp::MCMC_THREADS)),
+                       dim3(simplyp::MCMC_THREADS), 0, ctx->stream, g);
+    return mcmc_end(ctx, info);
+}
+
+int simplyp_mcmc_propose(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t half, double a, uint64_t seed, uint32_t t,
+                         const double* lo, const double* hi, const int32_t* target, const double* theta,
+                         double* prop, int32_t* inside, double* member_params, double* f_tdp, simplyp_mcmc_info* info)
+{
+    SIMPLYP_GUARD(ctx, mcmc_propose_impl(ctx, W, n_dim, half, a, seed, t, lo, hi, target, theta, prop, inside, member_params, f_tdp, info))
+}
+
+int simplyp_mcmc_log_prob(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t n_out_reaches, const double* gof,
+                          const int32_t* status, const int32_t* inside, const int32_t* pair_var, const int32_t* pair_reach,
+                          int32_t n_pairs, const int32_t* m_dim, const double* m_const, const double* prop, double* lp_prop,
+                          simplyp_mcmc_info* info)
+{
+    SIMPLYP_GUARD(ctx, mcmc_log_prob_impl(ctx, W, n_dim, n_out_reaches, gof, status, inside, pair_var, pair_reach, n_pairs, m_dim,
+                                          m_const, prop, lp_prop, info))
+}
+
+int simplyp_mcmc_accept(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t half, double a, uint64_t seed, uint32_t t,
+                        const double* prop, const int32_t* inside, const double* lp_prop, double* theta, double* lp,
+                        int32_t* n_accept, double* chain_row, simplyp_mcmc_info* info)
+{
+    SIMPLYP_GUARD(ctx, mcmc_accept_impl(ctx, W, n_dim, half, a, seed, t, prop, inside, lp_prop, theta, lp, n_accept, chain_row, info))
 }
 
 void* simplyp_host_alloc(int64_t bytes)

@@ -29,7 +29,8 @@ ABI_SYMBOLS = ['simplyp_abi_version', 'simplyp_device_count', 'simplyp_ctx_creat
                'simplyp_stream_out', 'simplyp_waterbody', 'simplyp_gof_waterbody', 'simplyp_gof_spearman', 'simplyp_eval_units',
                'simplyp_quantiles', 'simplyp_state_bytes', 'simplyp_set_state', 'simplyp_fetch_packed',
                'simplyp_pack_roundtrip_host', 'simplyp_fetch_packed_pred', 'simplyp_pack_roundtrip_host_pred',
-               'simplyp_time_quantiles', 'simplyp_predictive_series', 'simplyp_predictive_bands']
+               'simplyp_time_quantiles', 'simplyp_predictive_series', 'simplyp_predictive_bands',
+               'simplyp_mcmc_propose', 'simplyp_mcmc_log_prob', 'simplyp_mcmc_accept']
 
 _lib = None
 
@@ -43,7 +44,7 @@ def build(force=False, verbose=False):
     srcs = [os.path.join(CSRC, 'simplyp_hip.hip'), os.path.join(CSRC, 'simplyp_kernels.hip.h'),
             os.path.join(CSRC, 'simplyp_gof.hip.h'), os.path.join(CSRC, 'simplyp_waterbody.hip.h'),
             os.path.join(CSRC, 'simplyp_quantile.hip.h'), os.path.join(CSRC, 'simplyp_time_quantile.hip.h'),
-            os.path.join(CSRC, 'simplyp_predictive.hip.h'),
+            os.path.join(CSRC, 'simplyp_predictive.hip.h'), os.path.join(CSRC, 'simplyp_mcmc.hip.h'),
             os.path.join(CSRC, 'simplyp_pack.h'),
             os.path.join(CSRC, 'simplyp_pack_stream.h'),
             os.path.join(INCLUDE, 'simplyp.h'), os.path.join(INCLUDE, 'simplyp_controller.h')]
@@ -119,6 +120,15 @@ def lib():
     L.simplyp_predictive_bands.restype = C.c_int
     L.simplyp_predictive_bands.argtypes = pred_args + [vp, dp, dp, C.POINTER(C.c_int32), C.c_int32, dp, C.c_uint64, C.c_int32,
                                                        C.POINTER(C.c_double), C.c_int32, dp, C.POINTER(abi.PredInfo)]
+    move = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_uint32]
+    L.simplyp_mcmc_propose.restype = C.c_int
+    L.simplyp_mcmc_propose.argtypes = move + [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), dp, dp, i32p, dp, dp,
+                                              C.POINTER(abi.McmcInfo)]
+    L.simplyp_mcmc_log_prob.restype = C.c_int
+    L.simplyp_mcmc_log_prob.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, i32p, i32p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), dp, dp, C.POINTER(abi.McmcInfo)]
+    L.simplyp_mcmc_accept.restype = C.c_int
+    L.simplyp_mcmc_accept.argtypes = move + [dp, i32p, dp, dp, dp, i32p, dp, C.POINTER(abi.McmcInfo)]
     L.simplyp_stream_out.restype = C.c_int
     L.simplyp_stream_out.argtypes = [vp, vp, C.c_int64]
     L.simplyp_fetch_packed.restype = C.c_int
@@ -442,7 +452,7 @@ class Engine(object):
             self._check(lib().simplyp_eval_units(self._h, w, a.shape[0], a.data_ptr(), out.data_ptr()), 'simplyp_eval_units')
         return out.cpu().numpy()
 
-    def gof(self, out, out_mask, obs, f_tdp, reach_params, out_reaches=None, member_of_slot=None, spearman=False):
+    def gof(self, out, out_mask, obs, f_tdp, reach_params, out_reaches=None, member_of_slot=None, spearman=False, gof=None):
         """Per-member goodness-of-fit statistics (the reference's ``goodness_of_fit_stats``,
         visualise_results.py:387-474, without Spearman's r) of the daily table ``out`` of a previous ``run``.
 
@@ -451,7 +461,8 @@ class Engine(object):
         f_tdp [E] or scalar; reach_params [NP_R,S,E].  Returns (gof [n_stats,6,n_out_reaches,E] device tensor in member
         order -- rows ``abi.GOF_STATS``, variables ``abi.GOF_VARS`` -- and an info dict).  ``spearman=True`` adds the rank
         correlation (``simplyp_gof_spearman``, the remaining column of the reference's table) as
-        ``info['spearman']`` [6, n_out_reaches, E] device tensor and its cost as ``info['spearman_ms']``."""
+        ``info['spearman']`` [6, n_out_reaches, E] device tensor and its cost as ``info['spearman_ms']``.  ``gof``: a
+        float64 device tensor of the result's shape to write into instead of a new one (a loop that reduces run after run)."""
         torch = self.torch
         L = lib()
         rp = self.to_device(reach_params, torch.float64)
@@ -468,7 +479,11 @@ class Engine(object):
                             torch.float64)
         if tuple(ft.shape) != (E,):
             raise ValueError("f_tdp must be a scalar or have one entry per member")
-        gof = torch.empty((len(abi.GOF_STATS), len(abi.GOF_VARS), n_or, E), dtype=torch.float64, device=self.tdev)
+        shape = (len(abi.GOF_STATS), len(abi.GOF_VARS), n_or, E)
+        if gof is None:
+            gof = torch.empty(shape, dtype=torch.float64, device=self.tdev)
+        elif tuple(gof.shape) != shape or gof.dtype != torch.float64 or not gof.is_contiguous() or gof.device != self.tdev:
+            raise ValueError("gof must be a contiguous float64 tensor of shape %s on %s" % (shape, self.tdev))
         info = abi.GofInfo()
         dims = abi.Dims(E, S, D, 1)
         with torch.cuda.device(self.tdev):
@@ -750,6 +765,68 @@ class Engine(object):
         del keep
         return stats[0], stats[1], info.as_dict()
 
+
+    # ---- the stretch move (simplyp_mcmc_*; simplyp_amd.mcmc restates it) ----
+    @staticmethod
+    def _ptr(t):
+        return None if t is None else t.data_ptr()
+
+    def _mcmc_call(self, name, *args):
+        info = abi.McmcInfo()
+        with self.torch.cuda.device(self.tdev):
+            self._bind_stream()
+            rc = getattr(lib(), name)(*(args + (C.byref(info),)))
+        self._check(rc, name)
+        return info.as_dict()
+
+    def mcmc_propose(self, theta, half, t, lo, hi, target, prop, inside, member_params=None, f_tdp=None, a=2.0, seed=0):
+        """The proposals of half ``half`` at absolute step ``t`` (``simplyp_mcmc_propose``).  theta [n_dim, W] float64 device
+        tensor (read); lo / hi [n_dim] the prior box and target [n_dim] (a row of ``marshal.PM_NAMES``,
+        ``abi.MCMC_TARGET_F_TDP`` or ``abi.MCMC_TARGET_NONE``) on the host; prop [n_dim, W/2] float64, inside [W/2] int32,
+        member_params [NP_M, W/2] and f_tdp [W/2] device tensors that are written.  The library checks the values; the tensors'
+        shapes are the caller's.  Returns the info dict."""
+        n_dim, W = (int(x) for x in theta.shape)
+        lo = np.ascontiguousarray(lo, dtype=np.float64)
+        hi = np.ascontiguousarray(hi, dtype=np.float64)
+        tg = np.ascontiguousarray(target, dtype=np.int32)
+        if lo.shape != (n_dim,) or hi.shape != (n_dim,) or tg.shape != (n_dim,):
+            raise ValueError("lo, hi and target need one entry per dimension")
+        dbl = C.POINTER(C.c_double)
+        return self._mcmc_call('simplyp_mcmc_propose', self._h, W, n_dim, int(half), float(a),
+                               C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint32(int(t) & 0xFFFFFFFF),
+                               lo.ctypes.data_as(dbl), hi.ctypes.data_as(dbl), tg.ctypes.data_as(C.POINTER(C.c_int32)),
+                               theta.data_ptr(), self._ptr(prop), self._ptr(inside), self._ptr(member_params), self._ptr(f_tdp))
+
+    def mcmc_log_prob(self, gof, pairs, m_dim, m_const, prop, lp_prop, status=None, inside=None):
+        """The log posterior of the run points from a goodness-of-fit table (``simplyp_mcmc_log_prob``).  gof
+        [n_stats, 6, n_reaches, h] as ``Engine.gof`` returns it; pairs: list of (variable index in ``abi.GOF_VARS``, position among
+        the output reaches); m_dim [6]: the row of ``prop`` holding the variable's ``m`` or -1 for ``m_const[v]``; prop
+        [n_dim, h]; lp_prop [h] float64 device tensor (written); status / inside [h] int32 device tensors or None."""
+        n_dim, h = (int(x) for x in prop.shape)
+        pv = np.ascontiguousarray([p[0] for p in pairs], dtype=np.int32)
+        pr = np.ascontiguousarray([p[1] for p in pairs], dtype=np.int32)
+        md = np.ascontiguousarray(m_dim, dtype=np.int32)
+        mc = np.ascontiguousarray(m_const, dtype=np.float64)
+        if md.shape != (len(abi.GOF_VARS),) or mc.shape != (len(abi.GOF_VARS),):
+            raise ValueError("m_dim and m_const need one entry per variable of abi.GOF_VARS")
+        if gof.dim() != 4 or tuple(gof.shape[:2]) != (len(abi.GOF_STATS), len(abi.GOF_VARS)) or int(gof.shape[3]) != h \
+                or not gof.is_contiguous():
+            raise ValueError("gof %s does not match prop %s" % (tuple(gof.shape), tuple(prop.shape)))
+        i32 = C.POINTER(C.c_int32)
+        return self._mcmc_call('simplyp_mcmc_log_prob', self._h, 2 * h, n_dim, int(gof.shape[2]), gof.data_ptr(),
+                               self._ptr(status), self._ptr(inside), pv.ctypes.data_as(i32), pr.ctypes.data_as(i32), len(pv),
+                               md.ctypes.data_as(i32), mc.ctypes.data_as(C.POINTER(C.c_double)), prop.data_ptr(),
+                               self._ptr(lp_prop))
+
+    def mcmc_accept(self, theta, lp, n_accept, half, t, prop, inside, lp_prop, chain_row=None, a=2.0, seed=0):
+        """The decisions of half ``half`` at step ``t``, in place on theta [n_dim, W], lp [W] and n_accept [W] (int32)
+        (``simplyp_mcmc_accept``); lp_prop [W/2]: ln p of the proposals, from ``mcmc_log_prob`` or the caller's own; chain_row
+        [n_dim + 1, W] or None receives the half's positions and lp after the decision."""
+        n_dim, W = (int(x) for x in theta.shape)
+        return self._mcmc_call('simplyp_mcmc_accept', self._h, W, n_dim, int(half), float(a),
+                               C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint32(int(t) & 0xFFFFFFFF),
+                               self._ptr(prop), self._ptr(inside), self._ptr(lp_prop), theta.data_ptr(), self._ptr(lp),
+                               self._ptr(n_accept), self._ptr(chain_row))
 
 
 def interpolate_quantiles(lower, upper, q, n_used):
