@@ -34,7 +34,9 @@ extern "C" {
  * 17 still with simplyp_predictive_series, simplyp_predictive_bands and simplyp_pred_info: two more entry points, one more info
  * struct; no existing struct, enum or entry point changes.
  * 17 still with simplyp_mcmc_propose, simplyp_mcmc_log_prob, simplyp_mcmc_accept and simplyp_mcmc_info: three more entry points, one
- * more info struct, purely additive again. */
+ * more info struct, purely additive again.
+ * 17 still with simplyp_nm_propose, simplyp_nm_update, simplyp_nm_info and the SIMPLYP_NM_* constants: two more entry points, one
+ * more info struct, nothing existing changes. */
 #define SIMPLYP_ABI_VERSION 17
 
 typedef enum {
@@ -792,6 +794,84 @@ int simplyp_mcmc_log_prob(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t n_
 int simplyp_mcmc_accept(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t half, double a, uint64_t seed, uint32_t t,
                         const double* prop, const int32_t* inside, const double* lp_prop,
                         double* theta, double* lp, int32_t* n_accept, double* chain_row, simplyp_mcmc_info* info);
+
+/* ---- finding the posterior mode: multi-start Nelder-Mead, the reference's find_map (Development/2016/MAP.ipynb:
+ * scipy.optimize.fmin on the negative log posterior) for S simplexes at once, with the simplexes, the model runs and the decisions
+ * on the device.
+ *
+ * S simplexes in n_dim dimensions (1 <= n_dim <= 16, N = n_dim): vertices sim [N + 1][n_dim][S] and their values fsim [N + 1][S],
+ * f = -ln p, kept sorted by value; the box lo <= x < hi.  Every simplex owns four members of a run -- member index slot S + s --
+ * and integer state istate [SIMPLYP_NM_N_ISTATE][S].  One run of all simplexes is
+ *     propose -> simplyp_run + simplyp_gof + simplyp_mcmc_log_prob on the 4 S run points (or the caller's own target) -> update
+ * In phase STEP the slots hold scipy's four candidates, with xbar = (sim[0] + ... + sim[N - 1]) / N summed in that order and w = sim[N]:
+ *     xr = 2 xbar - w,  xe = 3 xbar - 2 w,  xc = 1.5 xbar - 0.5 w,  xcc = 0.5 xbar + 0.5 w        rho 1, chi 2, psi 0.5
+ * and update walks scipy's decision tree (_minimize_neldermead, its < and <= as they are) on their four values: the lazy algorithm's
+ * path.  The new vertex is inserted behind every vertex that is not worse.  A shrink, sim[j] = sim[0] + 0.5 (sim[j] - sim[0]) for
+ * j >= 1, puts the simplex into phase EVAL: the slots hold up to four vertices without a value, from istate's cursor on, for as many
+ * runs as that takes; then the vertices are sorted stably.  A fresh simplex starts in EVAL with cursor 0 and n_iter 0.
+ * When an iteration is complete n_iter grows by one (the initial evaluation makes it 1, like scipy's nit) and the simplex ends if
+ *     a vertex of the initial simplex has a value that is not finite                          status SIMPLYP_NM_NONFINITE_START
+ *     n_iter >= max_iter                                                                      status SIMPLYP_NM_MAXITER (scipy's 2)
+ *     max |sim[j] - sim[0]| <= xatol and max |fsim[0] - fsim[j]| <= fatol over j >= 1           status SIMPLYP_NM_CONVERGED (scipy's 0)
+ * tested in that order.  A slot that is idle holds sim[0]; the run point of a slot that is idle or outside the box is sim[0]: the
+ * model never sees a point outside the box.  Everything is + - * / and comparisons in fp64 without contraction, so any
+ * implementation gives the same bits; simplyp_amd/neldermead.py restates it in NumPy.  Both entries are synchronous on the context's
+ * stream and return SIMPLYP_ERR_ARG with nothing launched for S < 1 or S > 2^28, n_dim outside 1..16, lo[d] >= hi[d] or a NaN
+ * bound, a target outside [-2, SIMPLYP_NP_M), max_iter < 1, a negative or NaN tolerance, history_rows < 0, a NULL required pointer. */
+enum { SIMPLYP_NM_STEP = 0, SIMPLYP_NM_EVAL = 1, SIMPLYP_NM_DONE = 2 };                               /* istate row PHASE  */
+enum { SIMPLYP_NM_RUNNING = -1, SIMPLYP_NM_CONVERGED = 0, SIMPLYP_NM_MAXITER = 2, SIMPLYP_NM_NONFINITE_START = 3 };  /* STATUS */
+enum {
+    SIMPLYP_NM_PHASE = 0,        /* rows of istate                                                                    */
+    SIMPLYP_NM_CURSOR,           /* EVAL: the first vertex that has no value yet                                      */
+    SIMPLYP_NM_N_ITER,
+    SIMPLYP_NM_STATUS,
+    SIMPLYP_NM_N_REFLECT,        /* how many iterations ended in each kind of move                                    */
+    SIMPLYP_NM_N_EXPAND,
+    SIMPLYP_NM_N_CONTRACT_OUT,
+    SIMPLYP_NM_N_CONTRACT_IN,
+    SIMPLYP_NM_N_SHRINK,
+    SIMPLYP_NM_N_ISTATE
+};
+
+typedef struct {
+    double  kernel_ms;           /* the entry's kernel, HIP events on the context's stream                              */
+    int32_t n_active;            /* simplexes that are not DONE, in the state the entry leaves                          */
+    int32_t n_converged;         /* ... DONE with status CONVERGED                                                      */
+    int32_t n_shrinking;         /* ... in EVAL after a shrink                                                          */
+    int32_t n_nonfinite_start;   /* ... DONE with status NONFINITE_START                                                */
+    int32_t n_inside;            /* propose: slots that want a value and lie inside the box; 0 from update              */
+    int32_t reserved;
+} simplyp_nm_info;
+
+/*
+ * simplyp_nm_propose -- the points of the four slots of every simplex, and the run points scattered into the arrays of the run.
+ *   lo, hi          HOST    [n_dim] the box
+ *   target          HOST    [n_dim] as for simplyp_mcmc_propose: a row of member_params, -1 = f_tdp, -2 = nowhere
+ *   sim, istate     device  only read
+ *   prop            device  [n_dim][4 S] the slots' points
+ *   inside          device  [4 S] int32: 1 where the slot wants a value and its point lies inside the box, else 0
+ *   member_params   device  [SIMPLYP_NP_M][4 S] of an ensemble of 4 S members, or NULL when no target is >= 0; rows that no
+ *                           dimension names are not touched
+ *   f_tdp           device  [4 S], or NULL when no target is -1
+ */
+int simplyp_nm_propose(simplyp_ctx* ctx, int32_t S, int32_t n_dim,
+                       const double* lo /* host */, const double* hi /* host */, const int32_t* target /* host */,
+                       const double* sim, const int32_t* istate, double* prop, int32_t* inside,
+                       double* member_params, double* f_tdp, simplyp_nm_info* info);
+
+/*
+ * simplyp_nm_update -- one run's values applied, in place.  lp_prop is a plain device array, so a caller may minimise any
+ * function: propose, evaluate ln p = -f at the run points by its own means, update.
+ *   prop, inside    device  as written by the proposal
+ *   lp_prop         device  [4 S] ln p of the run points; f = -ln p, +inf where inside is 0 or ln p is NaN
+ *   sim, fsim, istate       device  the state
+ *   history         device  [history_rows][S] or NULL: row n_iter - 1 receives fsim[0] when an iteration is complete; rows past the
+ *                           end are dropped
+ */
+int simplyp_nm_update(simplyp_ctx* ctx, int32_t S, int32_t n_dim, int32_t max_iter, double xatol, double fatol,
+                      const double* prop, const int32_t* inside, const double* lp_prop,
+                      double* sim, double* fsim, int32_t* istate, double* history, int32_t history_rows,
+                      simplyp_nm_info* info);
 
 /*
  * simplyp_eval_units -- the path's scalar device functions on caller-given arguments, one thread per row: how the tests pin the

@@ -101,6 +101,20 @@ class McmcInfo(C.Structure):
 MCMC_TARGET_F_TDP = -1          # simplyp_mcmc_propose: the dimension goes to f_tdp
 MCMC_TARGET_NONE = -2           # ... nowhere: an error-model m
 
+
+class NmInfo(C.Structure):
+    """simplyp_nm_info of include/simplyp.h."""
+    _fields_ = [('kernel_ms', C.c_double), ('n_active', C.c_int32), ('n_converged', C.c_int32), ('n_shrinking', C.c_int32),
+                ('n_nonfinite_start', C.c_int32), ('n_inside', C.c_int32), ('reserved', C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
+
+
+# SIMPLYP_NM_*: the rows of istate [NM_N_ISTATE, S] (simplyp_amd.neldermead names the phases and the status values)
+NM_ISTATE = ['phase', 'cursor', 'n_iter', 'status', 'n_reflect', 'n_expand', 'n_contract_out', 'n_contract_in', 'n_shrink']
+NM_N_ISTATE = len(NM_ISTATE)
+
 TQ_DERIVED = 64                                                                       # SIMPLYP_TQ_DERIVED
 TQ_DERIVED_SERIES = ['Q_cumecs', 'SS_mgl', 'TDP_mgl', 'PP_mgl', 'TP_mgl', 'SRP_mgl']  # df_R names, in SIMPLYP_GOF_* order
 

@@ -1,18 +1,35 @@
-"""Sampling the posterior on the device: the middle of the reference's calibration notebook (Development/2016/MCMC.ipynb, cell 10),
-``emcee.EnsembleSampler(n_walk, n_dim, log_posterior).run_mcmc(start, n_steps)``, with the walkers, the model runs, the
-likelihood and the decisions all on the GPU.  ``simplyp_amd.mcmc`` is the NumPy statement of the move."""
+"""Calibration on the device: the middle of the reference's calibration notebooks (Development/2016/MCMC.ipynb, MAP.ipynb).
+
+``find_map`` is the notebooks' ``find_map`` -- ``scipy.optimize.fmin`` on the negative log posterior -- as a multi-start
+Nelder-Mead search (``simplyp_amd.neldermead`` is its NumPy statement); ``sample_posterior`` is their
+``emcee.EnsembleSampler(n_walk, n_dim, log_posterior).run_mcmc(start, n_steps)`` (``simplyp_amd.mcmc`` states the move); and
+``start_ball`` hands the one's result to the other.  The points, the model runs, the likelihood and the decisions are all on the
+GPU; both calls share the names, the checks, the marshalling and the evaluation (``_host_setup``, ``_Evaluator``)."""
 
 import time
 
 import numpy as np
 
-from . import abi, marshal, mcmc, predictive
+from . import abi, marshal, mcmc, neldermead, predictive
 
 START_SERIES = 0x53544152        # "STAR": the counter's fourth word of the start ball's normals
 
 
-def _plan(priors, variables, error_m, n_walkers):
-    """Names, box, targets and error-model wiring of a call; host only, raises ValueError."""
+def _box(priors, names):
+    """The prior box of ``names`` as (lo, hi); raises ValueError."""
+    try:
+        box = np.array([[float(priors[nm][0]), float(priors[nm][1])] for nm in names], dtype=np.float64)
+    except (TypeError, ValueError, IndexError):
+        raise ValueError("priors must map each name to a pair (lo, hi)")
+    if not (box[:, 0] < box[:, 1]).all():
+        bad = names[int(np.argmin(box[:, 0] < box[:, 1]))]
+        raise ValueError("prior of %r needs lo < hi (got %s)" % (bad, tuple(priors[bad])))
+    return box[:, 0].copy(), box[:, 1].copy()
+
+
+def _plan(priors, variables, error_m, check_shape):
+    """Names, box, targets and error-model wiring of a call; host only, raises ValueError.  ``check_shape(n_dim)`` is the
+    caller's own rule for how many points it moves."""
     if not isinstance(priors, dict) or not priors:
         raise ValueError("priors must be a dict name -> (lo, hi) with at least one entry")
     names = list(priors)
@@ -44,65 +61,16 @@ def _plan(priors, variables, error_m, n_walkers):
             if v not in error_m:
                 raise ValueError("variable %r needs its error model: sample 'm_%s' or fix it through error_m={'%s': ...}" % (v, v, v))
             m_const[vi] = float(error_m[v])
-    n_dim = len(names)
-    if n_walkers is None:
-        raise ValueError("n_walkers must be given")
-    try:
-        mcmc.check_shape(int(n_walkers), n_dim)
-    except ValueError as exc:
-        raise ValueError("sample_posterior: %s" % exc)
-    try:
-        box = np.array([[float(priors[nm][0]), float(priors[nm][1])] for nm in names], dtype=np.float64)
-    except (TypeError, ValueError, IndexError):
-        raise ValueError("priors must map each name to a pair (lo, hi)")
-    if not (box[:, 0] < box[:, 1]).all():
-        bad = names[int(np.argmin(box[:, 0] < box[:, 1]))]
-        raise ValueError("prior of %r needs lo < hi (got %s)" % (bad, tuple(priors[bad])))
-    return names, variables, box[:, 0].copy(), box[:, 1].copy(), np.array(target, dtype=np.int32), m_dim, m_const
+    check_shape(len(names))
+    lo, hi = _box(priors, names)
+    return names, variables, lo, hi, np.array(target, dtype=np.int32), m_dim, m_const
 
 
-def sample_posterior(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, priors, variables=('Q',), error_m=None,
-                     n_walkers=None, n_steps=0, start=None, seed=0, a=2.0, thin=1, state=None, record_proposals=False,
-                     step_len=1., solver=None, device=0, out_reaches=None):
-    """Sample the posterior of model parameters with the affine-invariant stretch move (Goodman & Weare 2010; the reference's
-    ``run_mcmc``), every half-step one ensemble run of ``n_walkers / 2`` members on the device.
-
-    ``priors``: dict name -> (lo, hi), the flat prior box ``lo <= x < hi`` (the reference's ``log_prior``); names are member
-    parameters (``marshal.PM_NAMES``), ``'f_TDP'``, and ``'m_<VAR>'`` -- the ``m`` of the error model ``sigma = m * sim`` --
-    for ``VAR`` in ``variables`` (names of ``abi.GOF_VARS``: the observed series the likelihood is taken over, at every
-    output reach that has more than 10 observations of it).  A variable whose ``m`` is not sampled gets it through
-    ``error_m={'Q': 0.1}``.  ``n_walkers`` even and >= twice the number of names (at most 16); ``n_steps`` steps;
-    ``a`` the stretch scale; ``seed`` the key of the counter-based random stream (``simplyp_amd.mcmc``); every ``thin``-th
-    step is kept.  ``start``: None = the notebook's ball -- the workbook's values (box centres for the ``m``) plus
-    ``1e-4 (hi - lo) z`` with ``z = predictive.standard_normal(seed, walker, dimension, 0, START_SERIES)`` -- or an array
-    [n_dim, n_walkers] inside the box; a start whose log posterior is not finite raises ``ValueError``.  ``state``: the
-    ``'state'`` of an earlier result: the chain continues from it bit for bit (``start`` is ignored).
-
-    The inputs are marshalled and uploaded once; one half-step is ``mcmc_propose`` -> ``Engine.run`` -> ``Engine.gof`` ->
-    ``mcmc_log_prob`` -> ``mcmc_accept`` on device buffers of ``n_walkers / 2`` members, and the chain comes to the host at the
-    end.  Returns dict(names, chain[n_kept, n_dim, W], log_prob[n_kept, W], acceptance_fraction[W], n_steps, seed, overrides,
-    error_m -- the last positions shaped for ``run_simply_p_ensemble(overrides=, predictive_series=list(error_m),
-    predictive_m=error_m)``, ``error_m`` keyed by the ``df_R`` series name --, state = dict(theta, lp, n_accept, t),
-    start = dict(theta, lp, t): where this call began,
-    proposals[n_steps, n_dim, W] and proposal_log_prob[n_steps, W] with ``record_proposals``, stats = per-half-step lists of
-    wall_ms, run_kernel_ms, gof_ms, sampler_ms, n_inside, n_accepted, and start_wall_ms, start_run_kernel_ms of the start's two
-    evaluations).  ``ValueError`` before any device call for an odd or
-    too small ``n_walkers``, an unknown name, ``lo >= hi``, a start outside the box, a selected variable with 10 or fewer
-    observations at every output reach, a missing ``obs_dict``, a box whose corners ``marshal.validate_ensemble`` rejects.
-    The caller's ``p_LU`` / ``p_SC`` are edited in place exactly as by ``run_simply_p``."""
+def _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables, lo, hi, out_reaches):
+    """What a calibration call works out on the host before it touches the device: the reference's prologue, the topology, the
+    observations and the (variable, output reach) pairs of the likelihood, the input checks at the box's corners, the snow rule,
+    the workbook's member parameters.  Raises ValueError."""
     from . import visualise_results as vr
-    from .model import _engine_opts
-
-    if not obs_dict:
-        raise ValueError("sample_posterior needs obs_dict: the observations the likelihood is taken over")
-    names, variables, lo, hi, target, m_dim, m_const = _plan(priors, variables, error_m, n_walkers)
-    n_dim, W = len(names), int(n_walkers)
-    h = W // 2
-    if not float(a) > 1.0:
-        raise ValueError("the stretch scale a must be > 1 (got %r)" % (a,))
-    seed, thin, n_steps = int(seed), int(thin), int(n_steps)
-    if not 0 <= seed < 1 << 64 or thin < 1 or n_steps < 0:
-        raise ValueError("seed must be in [0, 2^64), thin >= 1 and n_steps >= 0")
 
     marshal.prologue(p_SU, p_LU, p_SC, p)
     scs = marshal.sc_list(p)
@@ -132,8 +100,139 @@ def sample_posterior(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_
     snow = 'f_DDSM' in names or 'D_snow_0' in names
     if snow and not {'Precipitation', 'T_air'} <= set(met_df.columns):
         raise ValueError("sampling f_DDSM / D_snow_0 runs the snow module in the kernel: met_df needs 'Precipitation' and 'T_air'")
-
     base = marshal.member_params(p, p_LU, 1)[:, 0]
+    centre = np.array([base[marshal.PM_NAMES.index(nm)] if nm in marshal.PM_NAMES else
+                       (float(p['f_TDP']) if nm == 'f_TDP' else 0.5 * (lo[d] + hi[d])) for d, nm in enumerate(names)])
+    return dict(scs=scs, up_ptr=up_ptr, up_idx=up_idx, reaches=reaches, oreach=oreach, obs=obs, pairs=pairs, snow=snow, centre=centre)
+
+
+class _Evaluator:
+    """The device side both calls share: everything is marshalled and uploaded once, for an ensemble of ``n_members``; then
+    ``evaluate()`` is the model and the likelihood at the run points ``mp_d`` / ``ft_d`` hold, for the points in ``prop_d``: the log
+    posterior in ``lpp_d``."""
+
+    def __init__(self, order, hs, met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len, solver, device, n_members, n_dim,
+                 m_dim, m_const):
+        from . import engine
+        from .model import _engine_opts
+
+        self.eng = eng = engine.get_engine(device)
+        self.torch = torch = eng.torch
+        cols = ['Qr', 'Msus_kg/day', 'TDP_kg/day', 'PP_kg/day']              # what simplyp_gof reads
+        self.mask = marshal.mask_of_columns(cols)
+        self.opts = _engine_opts(p_SU, p, dynamic_options, step_len, solver, self.mask, snow=hs['snow'])
+        if self.opts.out_slot_order:
+            raise ValueError("%s: solver['out_slot_order'] must stay 0" % order)
+        forcing, doy = marshal.forcing_arrays(met_df, snow=hs['snow'])
+        self.f_d, self.doy_d = eng.to_device(forcing, torch.float64), eng.to_device(doy, torch.int32)
+        self.mp_d = eng.to_device(marshal.member_params(p, p_LU, n_members), torch.float64)
+        self.rp_d = eng.to_device(marshal.reach_params(p_SC, p, n_members), torch.float64)
+        self.f64 = f64 = dict(dtype=torch.float64, device=eng.tdev)
+        self.ft_d = torch.full((n_members,), float(p['f_TDP']), **f64)
+        D, R = len(met_df), len(hs['reaches'])
+        self.out_d = torch.empty((len(cols), D, R, n_members), **f64)
+        self.gof_d = torch.empty((len(abi.GOF_STATS), len(abi.GOF_VARS), R, n_members), **f64)
+        self.prop_d, self.lpp_d = torch.empty((n_dim, n_members), **f64), torch.empty((n_members,), **f64)
+        self.inside_d = torch.ones((n_members,), dtype=torch.int32, device=eng.tdev)
+        self.hs, self.m_dim, self.m_const = hs, m_dim, m_const
+
+    def evaluate(self):
+        """Returns the kernel times of the run, the goodness of fit and the log posterior, in ms."""
+        hs, eng = self.hs, self.eng
+        _, status_d, rstats = eng.run(self.f_d, self.doy_d, self.mp_d, self.rp_d, hs['up_ptr'], hs['up_idx'], self.opts,
+                                      out_reaches=hs['oreach'], out=self.out_d)
+        _, ginfo = eng.gof(self.out_d, self.mask, hs['obs'], self.ft_d, self.rp_d, out_reaches=hs['oreach'], gof=self.gof_d)
+        linfo = eng.mcmc_log_prob(self.gof_d, hs['pairs'], self.m_dim, self.m_const, self.prop_d, self.lpp_d, status=status_d,
+                                  inside=self.inside_d)
+        return rstats['kernel_ms'], ginfo['kernel_ms'], linfo['kernel_ms']
+
+
+def _shaped_for_the_ensemble(names, target, variables, m_dim, m_const, theta):
+    """Positions ``theta[n_dim, M]`` as ``run_simply_p_ensemble(overrides=, predictive_series=list(error_m), predictive_m=error_m)``
+    takes them: (overrides, error_m), ``error_m`` keyed by the ``df_R`` series name."""
+    M = theta.shape[1]
+    overrides = {nm: theta[d].copy() for d, nm in enumerate(names) if target[d] != abi.MCMC_TARGET_NONE}
+    error_m = {abi.TQ_DERIVED_SERIES[abi.GOF_VARS.index(v)]:
+               (theta[m_dim[abi.GOF_VARS.index(v)]].copy() if m_dim[abi.GOF_VARS.index(v)] >= 0
+                else np.full(M, m_const[abi.GOF_VARS.index(v)])) for v in variables}
+    return overrides, error_m
+
+
+def start_ball(centre, priors, n_walkers, seed=0):
+    """The notebook's start of a chain around a point estimate, ``param_est + 1e-4 randn``: ``centre + 1e-4 (hi - lo) z`` with
+    ``z = predictive.standard_normal(seed, walker, dimension, 0, START_SERIES)``, as ``[n_dim, n_walkers]``.  ``centre``: one value
+    per name of ``priors``, in its order -- ``find_map(...)['x'][:, best]``.  This is ``sample_posterior``'s own start for
+    ``start=None``, around the workbook's values.  ``ValueError`` where a walker leaves the prior box."""
+    if not isinstance(priors, dict) or not priors:
+        raise ValueError("priors must be a dict name -> (lo, hi) with at least one entry")
+    names = list(priors)
+    lo, hi = _box(priors, names)
+    centre = np.asarray(centre, dtype=np.float64)
+    n_dim, W = len(names), int(n_walkers)
+    if centre.shape != (n_dim,):
+        raise ValueError("centre needs one value per name of priors: %d, got shape %s" % (n_dim, centre.shape))
+    z = predictive.standard_normal(int(seed), np.arange(W)[None, :], np.arange(n_dim)[:, None], 0, START_SERIES)
+    theta0 = centre[:, None] + (1e-4 * (hi - lo))[:, None] * z
+    _check_inside(theta0, lo, hi, names)
+    return theta0
+
+
+def _check_inside(theta0, lo, hi, names):
+    if not ((theta0 >= lo[:, None]) & (theta0 < hi[:, None])).all():
+        d = int(np.argmin(((theta0 >= lo[:, None]) & (theta0 < hi[:, None])).all(axis=1)))
+        raise ValueError("the start lies outside the prior box in %r" % names[d])
+
+
+def sample_posterior(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, priors, variables=('Q',), error_m=None,
+                     n_walkers=None, n_steps=0, start=None, seed=0, a=2.0, thin=1, state=None, record_proposals=False,
+                     step_len=1., solver=None, device=0, out_reaches=None):
+    """Sample the posterior of model parameters with the affine-invariant stretch move (Goodman & Weare 2010; the reference's
+    ``run_mcmc``), every half-step one ensemble run of ``n_walkers / 2`` members on the device.
+
+    ``priors``: dict name -> (lo, hi), the flat prior box ``lo <= x < hi`` (the reference's ``log_prior``); names are member
+    parameters (``marshal.PM_NAMES``), ``'f_TDP'``, and ``'m_<VAR>'`` -- the ``m`` of the error model ``sigma = m * sim`` --
+    for ``VAR`` in ``variables`` (names of ``abi.GOF_VARS``: the observed series the likelihood is taken over, at every
+    output reach that has more than 10 observations of it).  A variable whose ``m`` is not sampled gets it through
+    ``error_m={'Q': 0.1}``.  ``n_walkers`` even and >= twice the number of names (at most 16); ``n_steps`` steps;
+    ``a`` the stretch scale; ``seed`` the key of the counter-based random stream (``simplyp_amd.mcmc``); every ``thin``-th
+    step is kept.  ``start``: None = the notebook's ball -- the workbook's values (box centres for the ``m``) plus
+    ``1e-4 (hi - lo) z`` with ``z = predictive.standard_normal(seed, walker, dimension, 0, START_SERIES)``: ``start_ball`` -- or an array
+    [n_dim, n_walkers] inside the box; a start whose log posterior is not finite raises ``ValueError``.  ``state``: the
+    ``'state'`` of an earlier result: the chain continues from it bit for bit (``start`` is ignored).
+
+    The inputs are marshalled and uploaded once; one half-step is ``mcmc_propose`` -> ``Engine.run`` -> ``Engine.gof`` ->
+    ``mcmc_log_prob`` -> ``mcmc_accept`` on device buffers of ``n_walkers / 2`` members, and the chain comes to the host at the
+    end.  Returns dict(names, chain[n_kept, n_dim, W], log_prob[n_kept, W], acceptance_fraction[W], n_steps, seed, overrides,
+    error_m -- the last positions shaped for ``run_simply_p_ensemble(overrides=, predictive_series=list(error_m),
+    predictive_m=error_m)``, ``error_m`` keyed by the ``df_R`` series name --, state = dict(theta, lp, n_accept, t),
+    start = dict(theta, lp, t): where this call began,
+    proposals[n_steps, n_dim, W] and proposal_log_prob[n_steps, W] with ``record_proposals``, stats = per-half-step lists of
+    wall_ms, run_kernel_ms, gof_ms, sampler_ms, n_inside, n_accepted, and start_wall_ms, start_run_kernel_ms of the start's two
+    evaluations).  ``ValueError`` before any device call for an odd or
+    too small ``n_walkers``, an unknown name, ``lo >= hi``, a start outside the box, a selected variable with 10 or fewer
+    observations at every output reach, a missing ``obs_dict``, a box whose corners ``marshal.validate_ensemble`` rejects.
+    The caller's ``p_LU`` / ``p_SC`` are edited in place exactly as by ``run_simply_p``."""
+    if not obs_dict:
+        raise ValueError("sample_posterior needs obs_dict: the observations the likelihood is taken over")
+
+    def check_shape(n_dim):
+        if n_walkers is None:
+            raise ValueError("n_walkers must be given")
+        try:
+            mcmc.check_shape(int(n_walkers), n_dim)
+        except ValueError as exc:
+            raise ValueError("sample_posterior: %s" % exc)
+
+    names, variables, lo, hi, target, m_dim, m_const = _plan(priors, variables, error_m, check_shape)
+    n_dim, W = len(names), int(n_walkers)
+    h = W // 2
+    if not float(a) > 1.0:
+        raise ValueError("the stretch scale a must be > 1 (got %r)" % (a,))
+    seed, thin, n_steps = int(seed), int(thin), int(n_steps)
+    if not 0 <= seed < 1 << 64 or thin < 1 or n_steps < 0:
+        raise ValueError("seed must be in [0, 2^64), thin >= 1 and n_steps >= 0")
+
+    hs = _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables, lo, hi, out_reaches)
     if state is not None:
         theta0 = np.array(state['theta'], dtype=np.float64)
         lp0 = np.array(state['lp'], dtype=np.float64)
@@ -144,40 +243,20 @@ def sample_posterior(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_
     else:
         t0, lp0, nacc0 = 0, None, np.zeros(W, dtype=np.int32)
         if start is None:
-            centre = np.array([base[marshal.PM_NAMES.index(nm)] if nm in marshal.PM_NAMES else
-                               (float(p['f_TDP']) if nm == 'f_TDP' else 0.5 * (lo[d] + hi[d])) for d, nm in enumerate(names)])
-            z = predictive.standard_normal(seed, np.arange(W)[None, :], np.arange(n_dim)[:, None], 0, START_SERIES)
-            theta0 = centre[:, None] + (1e-4 * (hi - lo))[:, None] * z
+            theta0 = start_ball(hs['centre'], priors, W, seed)
         else:
             theta0 = np.array(start, dtype=np.float64)
             if theta0.shape != (n_dim, W):
                 raise ValueError("start must have shape [n_dim, n_walkers] = %s, got %s" % ((n_dim, W), theta0.shape))
-    if not ((theta0 >= lo[:, None]) & (theta0 < hi[:, None])).all():
-        d = int(np.argmin(((theta0 >= lo[:, None]) & (theta0 < hi[:, None])).all(axis=1)))
-        raise ValueError("the start lies outside the prior box in %r" % names[d])
+    _check_inside(theta0, lo, hi, names)
     if t0 + n_steps >= 1 << 32:
         raise ValueError("the absolute step index must stay below 2^32")
 
     # ---- the device: everything is marshalled and uploaded once, for an ensemble of h members
-    from . import engine
-    eng = engine.get_engine(device)
-    torch = eng.torch
-    cols = ['Qr', 'Msus_kg/day', 'TDP_kg/day', 'PP_kg/day']              # what simplyp_gof reads
-    mask = marshal.mask_of_columns(cols)
-    opts = _engine_opts(p_SU, p, dynamic_options, step_len, solver, mask, snow=snow)
-    if opts.out_slot_order:
-        raise ValueError("sample_posterior keeps members in walker order: solver['out_slot_order'] must stay 0")
-    forcing, doy = marshal.forcing_arrays(met_df, snow=snow)
-    f_d, doy_d = eng.to_device(forcing, torch.float64), eng.to_device(doy, torch.int32)
-    mp_d = eng.to_device(marshal.member_params(p, p_LU, h), torch.float64)
-    rp_d = eng.to_device(marshal.reach_params(p_SC, p, h), torch.float64)
-    f64 = dict(dtype=torch.float64, device=eng.tdev)
-    ft_d = torch.full((h,), float(p['f_TDP']), **f64)
-    D, R = len(met_df), len(reaches)
-    out_d = torch.empty((len(cols), D, R, h), **f64)
-    gof_d = torch.empty((len(abi.GOF_STATS), len(abi.GOF_VARS), R, h), **f64)
-    prop_d, lpp_d = torch.empty((n_dim, h), **f64), torch.empty((h,), **f64)
-    inside_d = torch.ones((h,), dtype=torch.int32, device=eng.tdev)
+    ev = _Evaluator("sample_posterior keeps members in walker order", hs, met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len,
+                    solver, device, h, n_dim, m_dim, m_const)
+    eng, torch, f64 = ev.eng, ev.torch, ev.f64
+    mp_d, ft_d, prop_d, lpp_d, inside_d, evaluate = ev.mp_d, ev.ft_d, ev.prop_d, ev.lpp_d, ev.inside_d, ev.evaluate
     theta_d = eng.to_device(theta0, torch.float64)
     nacc_d = eng.to_device(nacc0, torch.int32)
     kept = [t for t in range(t0, t0 + n_steps) if (t + 1) % thin == 0]
@@ -186,13 +265,6 @@ def sample_posterior(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_
         props_d, plp_d = torch.empty((n_steps, n_dim, W), **f64), torch.empty((n_steps, W), **f64)
     stats = dict(wall_ms=[], run_kernel_ms=[], gof_ms=[], sampler_ms=[], n_inside=[], n_accepted=[],
                  start_wall_ms=[], start_run_kernel_ms=[])
-
-    def evaluate():
-        """The model and the likelihood at the run points mp_d / ft_d hold, for the proposals in prop_d: lpp_d."""
-        _, status_d, rstats = eng.run(f_d, doy_d, mp_d, rp_d, up_ptr, up_idx, opts, out_reaches=oreach, out=out_d)
-        _, ginfo = eng.gof(out_d, mask, obs, ft_d, rp_d, out_reaches=oreach, gof=gof_d)
-        linfo = eng.mcmc_log_prob(gof_d, pairs, m_dim, m_const, prop_d, lpp_d, status=status_d, inside=inside_d)
-        return rstats['kernel_ms'], ginfo['kernel_ms'], linfo['kernel_ms']
 
     if lp0 is None:                               # the start's log posterior: one evaluation per half, through the same kernels
         lp_d = torch.empty((W,), **f64)
@@ -242,13 +314,127 @@ def sample_posterior(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_
     chain = chain_d.cpu().numpy()
     theta, lp, n_accept = theta_d.cpu().numpy(), lp_d.cpu().numpy(), nacc_d.cpu().numpy()
     t_end = t0 + n_steps
+    overrides, err_m = _shaped_for_the_ensemble(names, target, variables, m_dim, m_const, theta)
     res = dict(names=names, chain=np.ascontiguousarray(chain[:, :n_dim]), log_prob=np.ascontiguousarray(chain[:, n_dim]),
                acceptance_fraction=n_accept / float(t_end) if t_end else np.zeros(W), n_steps=n_steps, seed=seed,
-               overrides={nm: theta[d].copy() for d, nm in enumerate(names) if target[d] != abi.MCMC_TARGET_NONE},
-               error_m={abi.TQ_DERIVED_SERIES[abi.GOF_VARS.index(v)]:
-                        (theta[m_dim[abi.GOF_VARS.index(v)]].copy() if m_dim[abi.GOF_VARS.index(v)] >= 0
-                         else np.full(W, m_const[abi.GOF_VARS.index(v)])) for v in variables},
+               overrides=overrides, error_m=err_m,
                state=dict(theta=theta, lp=lp, n_accept=n_accept, t=t_end), start=dict(theta=theta0, lp=lp_start, t=t0), stats=stats)
     if record_proposals:
         res['proposals'], res['proposal_log_prob'] = props_d.cpu().numpy(), plp_d.cpu().numpy()
+    return res
+
+
+def find_map(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, priors, variables=('Q',), error_m=None,
+             init_guess=None, n_starts=64, max_iter=None, xatol=1e-4, fatol=1e-4, seed=0, state=None, record_evaluations=False,
+             step_len=1., solver=None, device=0, out_reaches=None):
+    """Find the mode of the posterior (the reference's ``find_map``: ``scipy.optimize.fmin`` on the negative log posterior) with
+    ``n_starts`` Nelder-Mead simplexes at once, every run one ensemble of ``4 n_starts`` members on the device.
+
+    ``priors``, ``variables``, ``error_m``, ``out_reaches`` and the checks are ``sample_posterior``'s: the names are member
+    parameters, ``'f_TDP'`` and ``'m_<VAR>'``; the box is ``lo <= x < hi``, outside of which the target is +inf and the model is
+    never run.  The algorithm is scipy's, its coefficients, decisions and termination (``xatol``, ``fatol``; ``max_iter`` counts
+    like scipy's ``maxiter`` and defaults to its ``200 n_dim``), with an iteration's four candidates evaluated together
+    (``simplyp_amd.neldermead``).  ``init_guess``: an array [n_dim, n_starts] inside the box, or None: simplex 0 starts at the
+    workbook's values (box centres for the ``m``) and simplex ``s >= 1`` at ``lo + (hi - lo) u`` with ``u`` the uniform of Philox
+    counter ``(s, dimension, 0, neldermead.START_STREAM)`` under key ``seed`` (``neldermead.uniform_starts``).  Every initial
+    simplex is scipy's (``neldermead.initial_simplex``: a vertex that would leave the box steps inwards instead).  ``4 n_starts``
+    must be at least the number of names.  ``state``: the ``'state'`` of an earlier result, typically with a higher ``max_iter``:
+    the search continues from it bit for bit (``init_guess`` is ignored).
+
+    The inputs are marshalled and uploaded once; one run is ``nm_propose`` -> ``Engine.run`` -> ``Engine.gof`` ->
+    ``mcmc_log_prob`` -> ``nm_update`` on device buffers, until no simplex is active.  Returns dict(names, x[n_dim, S] -- the best
+    vertex of every simplex --, fun[S] = -log posterior there, best -- the index of the lowest ``fun`` --, map -- name -> value
+    at ``best`` --, overrides, error_m -- the best point shaped for ``run_simply_p_ensemble(overrides=,
+    predictive_series=list(error_m), predictive_m=error_m)``: arrays of one member --, n_iter[S] and status[S] as scipy reports
+    them (0 converged, 2 at the limit), history[max_iter, S] -- the best value after every iteration, row 0 the initial simplex,
+    NaN where a simplex had stopped --, final_simplex = (sim[n_dim + 1, n_dim, S], fsim[n_dim + 1, S]), moves -- dict kind ->
+    [S] counts --, state, start -- the state this call began from --, evaluations[n_runs, n_dim, 4 S] and evaluation_log_prob[n_runs, 4 S] with ``record_evaluations``,
+    stats = per-run lists of wall_ms, run_kernel_ms, gof_ms, optimiser_ms, n_active, n_shrinking -- the simplexes that
+    were moving and re-evaluating a shrunk simplex in that run --).  ``ValueError`` for what
+    ``sample_posterior`` rejects, an ``init_guess`` outside the box or of the wrong shape, and a start whose log posterior is not
+    finite (it names the simplex).  The caller's ``p_LU`` / ``p_SC`` are edited in place exactly as by ``run_simply_p``."""
+    if not obs_dict:
+        raise ValueError("find_map needs obs_dict: the observations the likelihood is taken over")
+    S = int(n_starts) if state is None else int(np.asarray(state['sim']).shape[-1])
+
+    def check_shape(n_dim):
+        if not 1 <= n_dim <= neldermead.MAX_DIM:
+            raise ValueError("find_map: n_dim must be in [1, %d] (got %d)" % (neldermead.MAX_DIM, n_dim))
+        if S < 1 or 4 * S < n_dim:
+            raise ValueError("find_map: n_starts must be >= 1 and 4 n_starts >= n_dim (got %d starts, n_dim = %d)" % (S, n_dim))
+
+    names, variables, lo, hi, target, m_dim, m_const = _plan(priors, variables, error_m, check_shape)
+    n_dim = len(names)
+    seed = int(seed)
+    max_iter = 200 * n_dim if max_iter is None else int(max_iter)
+    if not 0 <= seed < 1 << 64 or max_iter < 1 or not float(xatol) >= 0.0 or not float(fatol) >= 0.0:
+        raise ValueError("seed must be in [0, 2^64), max_iter >= 1, xatol and fatol >= 0")
+
+    hs = _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables, lo, hi, out_reaches)
+    if state is not None:
+        st = neldermead.copy_state({k: state[k] for k in ('sim', 'fsim', 'phase', 'cursor', 'n_iter', 'status', 'counts')})
+        if st['sim'].shape != (n_dim + 1, n_dim, S) or st['fsim'].shape != (n_dim + 1, S):
+            raise ValueError("state does not match this call: sim %s for %d names" % (st['sim'].shape, n_dim))
+        neldermead.resume(st, max_iter, xatol, fatol)
+        hist0 = np.asarray(state['history'], dtype=np.float64)
+    else:
+        if init_guess is None:
+            x0 = neldermead.uniform_starts(seed, n_dim, S, lo, hi)
+            x0[:, 0] = hs['centre']
+        else:
+            x0 = np.array(init_guess, dtype=np.float64)
+            if x0.shape != (n_dim, S):
+                raise ValueError("init_guess must have shape [n_dim, n_starts] = %s, got %s" % ((n_dim, S), x0.shape))
+        st = neldermead.new_state(neldermead.initial_simplex(x0, lo, hi))
+        hist0 = np.empty((0, S))
+    hist = np.full((max_iter, S), np.nan)
+    hist[:min(len(hist0), max_iter)] = hist0[:max_iter]
+    begin = dict(neldermead.copy_state(st), history=hist.copy())
+
+    # ---- the device: everything is marshalled and uploaded once, for an ensemble of 4 S members
+    ev = _Evaluator("find_map keeps members in slot order", hs, met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len, solver,
+                    device, neldermead.SLOTS * S, n_dim, m_dim, m_const)
+    eng, torch = ev.eng, ev.torch
+    sim_d, fsim_d = eng.to_device(st['sim'], torch.float64), eng.to_device(st['fsim'], torch.float64)
+    ist_d = eng.to_device(neldermead.pack_istate(st), torch.int32)
+    hist_d = eng.to_device(hist, torch.float64)
+    stats = dict(wall_ms=[], run_kernel_ms=[], gof_ms=[], optimiser_ms=[], n_active=[], n_shrinking=[])
+    evals, evals_lp = [], []
+    n_active = int((st['phase'] != neldermead.DONE).sum())
+    while n_active:
+        torch.cuda.synchronize(eng.tdev)
+        w0 = time.perf_counter()
+        pinfo = eng.nm_propose(sim_d, ist_d, lo, hi, target, ev.prop_d, ev.inside_d, ev.mp_d, ev.ft_d)
+        run_ms, gof_ms, lp_ms = ev.evaluate()
+        uinfo = eng.nm_update(sim_d, fsim_d, ist_d, ev.prop_d, ev.inside_d, ev.lpp_d, max_iter, xatol, fatol, history=hist_d)
+        stats['wall_ms'].append(1e3 * (time.perf_counter() - w0))
+        stats['run_kernel_ms'].append(run_ms)
+        stats['gof_ms'].append(gof_ms)
+        stats['optimiser_ms'].append(pinfo['kernel_ms'] + lp_ms + uinfo['kernel_ms'])
+        stats['n_active'].append(pinfo['n_active'])
+        stats['n_shrinking'].append(pinfo['n_shrinking'])
+        if record_evaluations:
+            evals.append(ev.prop_d.clone())
+            evals_lp.append(ev.lpp_d.clone())
+        if uinfo['n_nonfinite_start']:
+            marshal.epilogue_mutations(p_SU, p_LU, p_SC, p)
+            bad = int(np.argmax(ist_d[abi.NM_ISTATE.index('status')].cpu().numpy() == neldermead.NONFINITE_START))
+            raise ValueError("the start of simplex %d has a vertex with a non-finite log posterior: the model or the likelihood "
+                             "fails there" % bad)
+        n_active = uinfo['n_active']
+    marshal.epilogue_mutations(p_SU, p_LU, p_SC, p)
+
+    st['sim'], st['fsim'] = sim_d.cpu().numpy(), fsim_d.cpu().numpy()
+    neldermead.unpack_istate(ist_d.cpu().numpy(), st)
+    hist = hist_d.cpu().numpy()
+    x, fun = st['sim'][0].copy(), st['fsim'][0].copy()
+    best = int(np.argmin(fun))
+    overrides, err_m = _shaped_for_the_ensemble(names, target, variables, m_dim, m_const, x[:, best:best + 1])
+    res = dict(names=names, x=x, fun=fun, best=best, map={nm: float(x[d, best]) for d, nm in enumerate(names)},
+               overrides=overrides, error_m=err_m, n_iter=st['n_iter'].copy(), status=st['status'].copy(), history=hist,
+               final_simplex=(st['sim'], st['fsim']), moves={m: st['counts'][i].copy() for i, m in enumerate(neldermead.MOVES)},
+               state=dict(st, history=hist), start=begin, stats=stats)
+    if record_evaluations:
+        res['evaluations'] = torch.stack(evals).cpu().numpy() if evals else np.empty((0, n_dim, neldermead.SLOTS * S))
+        res['evaluation_log_prob'] = torch.stack(evals_lp).cpu().numpy() if evals_lp else np.empty((0, neldermead.SLOTS * S))
     return res

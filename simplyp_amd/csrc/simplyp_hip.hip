@@ -24,6 +24,7 @@
 #include "simplyp_time_quantile.hip.h"
 #include "simplyp_predictive.hip.h"
 #include "simplyp_mcmc.hip.h"
+#include "simplyp_neldermead.hip.h"
 #include "simplyp_pack_stream.h"
 
 namespace {
@@ -53,6 +54,8 @@ struct simplyp_ctx {
     DeviceBuf tquant;         // simplyp_time_quantiles: sweeps, rows read | day lists, ranks, output reaches
     DeviceBuf pred;           // simplyp_predictive_*: [R] int32 output reaches (256-byte slot) | a chunk of days [n_series][days][R][E]
     DeviceBuf mcmc;           // simplyp_mcmc_*: 4 x uint32 (inside, accepted, NaN)
+    DeviceBuf nm;             // simplyp_nm_*: 8 x uint32 counters
+    DeviceBuf nm_work;        // simplyp_nm_update: the sort's other copy of the simplexes
     DeviceBuf queue;          // ticket, error, done[n_groups] (uint32) | ckpt[CKPT_N][E] (double)
     // streamed output (simplyp_stream_out): the armed destination, the chunk flags the queue kernel raises in pinned host
     // memory, and the host thread that turns a raised flag into the D2H copies of that chunk's rows on `copy_stream`
@@ -984,6 +987,8 @@ void simplyp_ctx_destroy(simplyp_ctx* ctx)
     if (ctx->tquant.ptr) (void)hipFree(ctx->tquant.ptr);
     if (ctx->pred.ptr) (void)hipFree(ctx->pred.ptr);
     if (ctx->mcmc.ptr) (void)hipFree(ctx->mcmc.ptr);
+    if (ctx->nm.ptr) (void)hipFree(ctx->nm.ptr);
+    if (ctx->nm_work.ptr) (void)hipFree(ctx->nm_work.ptr);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
     if (ctx->ev_main) (void)hipEventDestroy(ctx->ev_main);
@@ -2382,6 +2387,116 @@ int simplyp_mcmc_accept(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t half
                         int32_t* n_accept, double* chain_row, simplyp_mcmc_info* info)
 {
     SIMPLYP_GUARD(ctx, mcmc_accept_impl(ctx, W, n_dim, half, a, seed, t, prop, inside, lp_prop, theta, lp, n_accept, chain_row, info))
+}
+
+// ---- multi-start Nelder-Mead (simplyp_neldermead.hip.h) ---------------------------------------------------------------------
+// What the two entries check alike.
+static int nm_shape(simplyp_ctx* ctx, const char* me, int32_t S, int32_t n_dim)
+{
+    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a run is pending on this context; call simplyp_sync first", me);
+    if (n_dim < 1 || n_dim > simplyp::MCMC_MAX_DIM)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_dim must be in [1, %d] (got %d)", me, simplyp::MCMC_MAX_DIM, (int)n_dim);
+    if (S < 1 || S > (1 << 28)) return fail(ctx, SIMPLYP_ERR_ARG, "%s: S must be in [1, 2^28] (got %d)", me, (int)S);
+    return SIMPLYP_OK;
+}
+
+static int nm_begin(simplyp_ctx* ctx, unsigned*& counters)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = ensure(ctx, ctx->nm, 8 * sizeof(unsigned))) return rc;
+    counters = (unsigned*)ctx->nm.ptr;
+    HIP_TRY(ctx, hipMemsetAsync(counters, 0, 8 * sizeof(unsigned), ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    return SIMPLYP_OK;
+}
+
+static int nm_end(simplyp_ctx* ctx, simplyp_nm_info* info)
+{
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+    unsigned c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(c, ctx->nm.ptr, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (info) {
+        float ms = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+        info->kernel_ms = ms;
+        info->n_active = (int32_t)c[0]; info->n_converged = (int32_t)c[1]; info->n_shrinking = (int32_t)c[2];
+        info->n_nonfinite_start = (int32_t)c[3]; info->n_inside = (int32_t)c[4]; info->reserved = 0;
+    }
+    return SIMPLYP_OK;
+}
+
+static int nm_propose_impl(simplyp_ctx* ctx, int32_t S, int32_t n_dim, const double* lo, const double* hi, const int32_t* target,
+                           const double* sim, const int32_t* istate, double* prop, int32_t* inside, double* member_params,
+                           double* f_tdp, simplyp_nm_info* info)
+{
+    const char* me = "simplyp_nm_propose";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    if (int rc = nm_shape(ctx, me, S, n_dim)) return rc;
+    if (!lo || !hi || !target || !sim || !istate || !prop || !inside)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: lo, hi, target, sim, istate, prop and inside must not be NULL", me);
+    simplyp::NmProposeArgs g{};
+    bool to_params = false, to_f_tdp = false;
+    for (int d = 0; d < n_dim; ++d) {
+        if (!(lo[d] < hi[d])) return fail(ctx, SIMPLYP_ERR_ARG, "%s: the box needs lo[%d] < hi[%d] (got %g, %g)", me, d, d, lo[d], hi[d]);
+        if (target[d] < simplyp::MCMC_TARGET_NONE || target[d] >= SIMPLYP_NP_M)
+            return fail(ctx, SIMPLYP_ERR_ARG, "%s: target[%d] = %d is outside [-2, %d)", me, d, (int)target[d], (int)SIMPLYP_NP_M);
+        for (int e = 0; e < d; ++e)
+            if (target[d] != simplyp::MCMC_TARGET_NONE && target[e] == target[d])
+                return fail(ctx, SIMPLYP_ERR_ARG, "%s: target[%d] and target[%d] name the same row (%d)", me, e, d, (int)target[d]);
+        to_params = to_params || target[d] >= 0;
+        to_f_tdp = to_f_tdp || target[d] == simplyp::MCMC_TARGET_F_TDP;
+        g.lo[d] = lo[d]; g.hi[d] = hi[d]; g.target[d] = target[d];
+    }
+    if ((to_params && !member_params) || (to_f_tdp && !f_tdp))
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: a target names member_params or f_tdp, which is NULL", me);
+    g.S = S; g.n_dim = n_dim;
+    g.sim = sim; g.istate = istate; g.prop = prop; g.inside = inside; g.member_params = member_params; g.f_tdp = f_tdp;
+    if (int rc = nm_begin(ctx, g.counters)) return rc;
+    hipLaunchKernelGGL(simplyp::simplyp_nm_propose_kernel, dim3((unsigned)((S + simplyp::NM_THREADS - 1) / simplyp::NM_THREADS)),
+                       dim3(simplyp::NM_THREADS), 0, ctx->stream, g);
+    return nm_end(ctx, info);
+}
+
+static int nm_update_impl(simplyp_ctx* ctx, int32_t S, int32_t n_dim, int32_t max_iter, double xatol, double fatol,
+                          const double* prop, const int32_t* inside, const double* lp_prop, double* sim, double* fsim,
+                          int32_t* istate, double* history, int32_t history_rows, simplyp_nm_info* info)
+{
+    const char* me = "simplyp_nm_update";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    if (int rc = nm_shape(ctx, me, S, n_dim)) return rc;
+    if (max_iter < 1) return fail(ctx, SIMPLYP_ERR_ARG, "%s: max_iter must be >= 1 (got %d)", me, (int)max_iter);
+    if (!(xatol >= 0.0) || !(fatol >= 0.0))
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: xatol and fatol must be >= 0 (got %g, %g)", me, xatol, fatol);
+    if (history_rows < 0) return fail(ctx, SIMPLYP_ERR_ARG, "%s: history_rows must be >= 0 (got %d)", me, (int)history_rows);
+    if (!prop || !inside || !lp_prop || !sim || !fsim || !istate)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: prop, inside, lp_prop, sim, fsim and istate must not be NULL", me);
+    simplyp::NmUpdateArgs g{};
+    g.S = S; g.n_dim = n_dim; g.max_iter = max_iter; g.history_rows = history ? history_rows : 0; g.xatol = xatol; g.fatol = fatol;
+    g.prop = prop; g.inside = inside; g.lp_prop = lp_prop; g.sim = sim; g.fsim = fsim; g.istate = istate; g.history = history;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = ensure(ctx, ctx->nm_work, (size_t)(n_dim + 1) * (size_t)(n_dim + 1) * (size_t)S * sizeof(double))) return rc;
+    g.work = (double*)ctx->nm_work.ptr;
+    if (int rc = nm_begin(ctx, g.counters)) return rc;
+    hipLaunchKernelGGL(simplyp::simplyp_nm_update_kernel, dim3((unsigned)((S + simplyp::NM_THREADS - 1) / simplyp::NM_THREADS)),
+                       dim3(simplyp::NM_THREADS), 0, ctx->stream, g);
+    return nm_end(ctx, info);
+}
+
+int simplyp_nm_propose(simplyp_ctx* ctx, int32_t S, int32_t n_dim, const double* lo, const double* hi, const int32_t* target,
+                       const double* sim, const int32_t* istate, double* prop, int32_t* inside, double* member_params,
+                       double* f_tdp, simplyp_nm_info* info)
+{
+    SIMPLYP_GUARD(ctx, nm_propose_impl(ctx, S, n_dim, lo, hi, target, sim, istate, prop, inside, member_params, f_tdp, info))
+}
+
+int simplyp_nm_update(simplyp_ctx* ctx, int32_t S, int32_t n_dim, int32_t max_iter, double xatol, double fatol,
+                      const double* prop, const int32_t* inside, const double* lp_prop, double* sim, double* fsim,
+                      int32_t* istate, double* history, int32_t history_rows, simplyp_nm_info* info)
+{
+    SIMPLYP_GUARD(ctx, nm_update_impl(ctx, S, n_dim, max_iter, xatol, fatol, prop, inside, lp_prop, sim, fsim, istate, history,
+                                      history_rows, info))
 }
 
 void* simplyp_host_alloc(int64_t bytes)

@@ -30,7 +30,7 @@ ABI_SYMBOLS = ['simplyp_abi_version', 'simplyp_device_count', 'simplyp_ctx_creat
                'simplyp_quantiles', 'simplyp_state_bytes', 'simplyp_set_state', 'simplyp_fetch_packed',
                'simplyp_pack_roundtrip_host', 'simplyp_fetch_packed_pred', 'simplyp_pack_roundtrip_host_pred',
                'simplyp_time_quantiles', 'simplyp_predictive_series', 'simplyp_predictive_bands',
-               'simplyp_mcmc_propose', 'simplyp_mcmc_log_prob', 'simplyp_mcmc_accept']
+               'simplyp_mcmc_propose', 'simplyp_mcmc_log_prob', 'simplyp_mcmc_accept', 'simplyp_nm_propose', 'simplyp_nm_update']
 
 _lib = None
 
@@ -45,6 +45,7 @@ def build(force=False, verbose=False):
             os.path.join(CSRC, 'simplyp_gof.hip.h'), os.path.join(CSRC, 'simplyp_waterbody.hip.h'),
             os.path.join(CSRC, 'simplyp_quantile.hip.h'), os.path.join(CSRC, 'simplyp_time_quantile.hip.h'),
             os.path.join(CSRC, 'simplyp_predictive.hip.h'), os.path.join(CSRC, 'simplyp_mcmc.hip.h'),
+            os.path.join(CSRC, 'simplyp_neldermead.hip.h'),
             os.path.join(CSRC, 'simplyp_pack.h'),
             os.path.join(CSRC, 'simplyp_pack_stream.h'),
             os.path.join(INCLUDE, 'simplyp.h'), os.path.join(INCLUDE, 'simplyp_controller.h')]
@@ -129,6 +130,12 @@ def lib():
                                         C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), dp, dp, C.POINTER(abi.McmcInfo)]
     L.simplyp_mcmc_accept.restype = C.c_int
     L.simplyp_mcmc_accept.argtypes = move + [dp, i32p, dp, dp, dp, i32p, dp, C.POINTER(abi.McmcInfo)]
+    L.simplyp_nm_propose.restype = C.c_int
+    L.simplyp_nm_propose.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                     dp, i32p, dp, i32p, dp, dp, C.POINTER(abi.NmInfo)]
+    L.simplyp_nm_update.restype = C.c_int
+    L.simplyp_nm_update.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, dp, i32p, dp, dp, dp, i32p, dp,
+                                    C.c_int32, C.POINTER(abi.NmInfo)]
     L.simplyp_stream_out.restype = C.c_int
     L.simplyp_stream_out.argtypes = [vp, vp, C.c_int64]
     L.simplyp_fetch_packed.restype = C.c_int
@@ -827,6 +834,42 @@ class Engine(object):
                                C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint32(int(t) & 0xFFFFFFFF),
                                self._ptr(prop), self._ptr(inside), self._ptr(lp_prop), theta.data_ptr(), self._ptr(lp),
                                self._ptr(n_accept), self._ptr(chain_row))
+
+    # ---- multi-start Nelder-Mead (simplyp_nm_*; simplyp_amd.neldermead restates it) ----
+    def _nm_call(self, name, *args):
+        info = abi.NmInfo()
+        with self.torch.cuda.device(self.tdev):
+            self._bind_stream()
+            rc = getattr(lib(), name)(*(args + (C.byref(info),)))
+        self._check(rc, name)
+        return info.as_dict()
+
+    def nm_propose(self, sim, istate, lo, hi, target, prop, inside, member_params=None, f_tdp=None):
+        """The points of every simplex's four slots (``simplyp_nm_propose``).  sim [n_dim + 1, n_dim, S] float64 and istate
+        [abi.NM_N_ISTATE, S] int32 device tensors (read); lo / hi [n_dim] the box and target [n_dim] (as for ``mcmc_propose``) on
+        the host; prop [n_dim, 4 S] float64, inside [4 S] int32, member_params [NP_M, 4 S] and f_tdp [4 S] device tensors that are
+        written.  The library checks the values; the tensors' shapes are the caller's.  Returns the info dict."""
+        n_dim, S = int(sim.shape[1]), int(sim.shape[2])
+        lo = np.ascontiguousarray(lo, dtype=np.float64)
+        hi = np.ascontiguousarray(hi, dtype=np.float64)
+        tg = np.ascontiguousarray(target, dtype=np.int32)
+        if int(sim.shape[0]) != n_dim + 1 or lo.shape != (n_dim,) or hi.shape != (n_dim,) or tg.shape != (n_dim,):
+            raise ValueError("sim must be [n_dim + 1, n_dim, S]; lo, hi and target need one entry per dimension")
+        dbl = C.POINTER(C.c_double)
+        return self._nm_call('simplyp_nm_propose', self._h, S, n_dim, lo.ctypes.data_as(dbl), hi.ctypes.data_as(dbl),
+                             tg.ctypes.data_as(C.POINTER(C.c_int32)), sim.data_ptr(), self._ptr(istate), self._ptr(prop),
+                             self._ptr(inside), self._ptr(member_params), self._ptr(f_tdp))
+
+    def nm_update(self, sim, fsim, istate, prop, inside, lp_prop, max_iter, xatol=1e-4, fatol=1e-4, history=None):
+        """One run's values applied in place to sim [n_dim + 1, n_dim, S], fsim [n_dim + 1, S] and istate (``simplyp_nm_update``);
+        lp_prop [4 S]: ln p of the run points, from ``mcmc_log_prob`` or the caller's own; history [rows, S] or None receives the
+        best value of every iteration that completes."""
+        n_dim, S = int(sim.shape[1]), int(sim.shape[2])
+        if int(sim.shape[0]) != n_dim + 1:
+            raise ValueError("sim must be [n_dim + 1, n_dim, S]")
+        return self._nm_call('simplyp_nm_update', self._h, S, n_dim, int(max_iter), float(xatol), float(fatol), self._ptr(prop),
+                             self._ptr(inside), self._ptr(lp_prop), sim.data_ptr(), self._ptr(fsim), self._ptr(istate),
+                             self._ptr(history), 0 if history is None else int(history.shape[0]))
 
 
 def interpolate_quantiles(lower, upper, q, n_used):
