@@ -26,6 +26,7 @@
 #include "simplyp_mcmc.hip.h"
 #include "simplyp_neldermead.hip.h"
 #include "simplyp_pack_stream.h"
+#include "simplyp_table.h"
 
 namespace {
 
@@ -1421,39 +1422,80 @@ int simplyp_run(simplyp_ctx* ctx, const simplyp_dims* dims, const simplyp_opts* 
     return simplyp_sync(ctx, stats);
 }
 
+namespace st = simplyp_table;
+static_assert(st::TARGET_F_TDP == simplyp::MCMC_TARGET_F_TDP && st::TARGET_NONE == simplyp::MCMC_TARGET_NONE, "one meaning of a target");
+
+// A rule of simplyp_table.h that says no: its message (`msg`, which `call` names) becomes the context's.
+#define TABLE_TRY(ctx, call)                                                    \
+    do {                                                                        \
+        std::string msg;                                                        \
+        if (int rc__ = (call)) return fail(ctx, rc__, "%s", msg.c_str());       \
+    } while (0)
+
+// The timed bracket of an entry: ev_start before its launches; after them ev_stop, the read-back of its device counters if it
+// has any (`bytes` from `src` to `dst`), and the wait for all of it.  *ms (an info's kernel_ms, or NULL): ev_start to ev_stop.
+static int timed_begin(simplyp_ctx* ctx)
+{
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    return SIMPLYP_OK;
+}
+
+static int timed_end(simplyp_ctx* ctx, double* ms, void* dst = nullptr, const void* src = nullptr, size_t bytes = 0)
+{
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+    if (bytes) HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float f = 0.f;
+    HIP_TRY(ctx, hipEventElapsedTime(&f, ctx->ev_start, ctx->ev_stop));
+    if (ms) *ms = f;
+    return SIMPLYP_OK;
+}
+
+static int fill_nan(simplyp_ctx* ctx, double* ptr, long long n)
+{
+    hipLaunchKernelGGL(simplyp::quantile_fill_nan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ptr, n);
+    HIP_TRY(ctx, hipGetLastError());
+    return SIMPLYP_OK;
+}
+
+// An entry's `n` device counters (uint32, at the head of `buf`): zeroed before its launch, inside the timed bracket; read
+// back into c[n] with the launch's time afterwards.
+static int counters_begin(simplyp_ctx* ctx, DeviceBuf& buf, int n, unsigned*& counters)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = ensure(ctx, buf, n * sizeof(unsigned))) return rc;
+    counters = (unsigned*)buf.ptr;
+    HIP_TRY(ctx, hipMemsetAsync(counters, 0, n * sizeof(unsigned), ctx->stream));
+    return timed_begin(ctx);
+}
+
+static int counters_end(simplyp_ctx* ctx, const DeviceBuf& buf, int n, unsigned* c, double* ms)
+{
+    HIP_TRY(ctx, hipGetLastError());
+    return timed_end(ctx, ms, c, buf.ptr, n * sizeof(unsigned));
+}
+
 // The table simplyp_gof, simplyp_gof_spearman and simplyp_waterbody read: its sizes, its output reaches, and the slots among
 // its columns of the four series the statistics and sums are built from.
-struct TableView {
-    int E, S, D, R;
-    std::vector<int32_t> reach_of;      // [R] the reach of each output row
+struct TableView : st::View {
     int col[4];
 };
 
 // Checks shared by the table reductions (`ptrs_ok`: the caller's required pointers are set).  waterbody == true: `out` is a
 // table written by simplyp_waterbody, `out_mask` its wb_mask, and the series its summed discharge and fluxes.
-static int check_table(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask, const int32_t* out_reaches,
+static int check_table(simplyp_ctx* ctx, const char* me, const simplyp_dims* dims, uint32_t out_mask, const int32_t* out_reaches,
                        int32_t n_out_reaches, bool ptrs_ok, bool waterbody, TableView& t)
 {
     if (!ctx) return SIMPLYP_ERR_ARG;
-    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "a run is pending on this context; call simplyp_sync first");
-    if (!dims || dims->E <= 0 || (!waterbody && dims->S <= 0) || dims->D <= 0) return fail(ctx, SIMPLYP_ERR_ARG, "bad dims");
-    if (!ptrs_ok) return fail(ctx, SIMPLYP_ERR_ARG, "a required pointer is NULL");
-    static const int reach_cols[4] = {SIMPLYP_OUT_QR, SIMPLYP_OUT_MSUS_FLUX, SIMPLYP_OUT_TDP_FLUX, SIMPLYP_OUT_PP_FLUX};
-    static const int wb_cols[4] = {SIMPLYP_WB_Q_CUMECS, SIMPLYP_WB_MSUS_FLUX, SIMPLYP_WB_TDP_FLUX, SIMPLYP_WB_PP_FLUX};
-    const int* want = waterbody ? wb_cols : reach_cols;
-    const uint32_t need = (1u << want[0]) | (1u << want[1]) | (1u << want[2]) | (1u << want[3]);
-    if ((out_mask & need) != need || (out_mask & ~(waterbody ? SIMPLYP_WB_MASK_ALL : (SIMPLYP_MASK_ALL | SIMPLYP_MASK_D_SNOW))) != 0u)
-        return fail(ctx, SIMPLYP_ERR_ARG, waterbody ? "wb_mask must contain Q_cumecs, Msus_kg/day, TDP_kg/day and PP_kg/day"
-                                                    : "out_mask must contain Qr, Msus_kg/day, TDP_kg/day and PP_kg/day");
-    t.E = dims->E; t.S = waterbody ? 1 : dims->S; t.D = dims->D;
-    t.R = out_reaches ? n_out_reaches : t.S;
-    if (t.R <= 0 || t.R > t.S) return fail(ctx, SIMPLYP_ERR_ARG, "bad n_out_reaches");
-    t.reach_of.resize(t.R);
-    for (int r = 0; r < t.R; ++r) {
-        t.reach_of[r] = out_reaches ? out_reaches[r] : r;
-        if (t.reach_of[r] < 0 || t.reach_of[r] >= t.S) return fail(ctx, SIMPLYP_ERR_ARG, "out_reaches[%d] out of range", r);
-    }
-    for (int i = 0; i < 4; ++i) t.col[i] = popcount32(out_mask & ((1u << want[i]) - 1u));
+    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a run is pending on this context; call simplyp_sync first", me);
+    if (!dims || dims->E <= 0 || (!waterbody && dims->S <= 0) || dims->D <= 0) return fail(ctx, SIMPLYP_ERR_ARG, "%s: bad dims", me);
+    if (!ptrs_ok) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a required pointer is NULL", me);
+    simplyp_dims d = *dims;
+    if (waterbody) d.S = 1;
+    TABLE_TRY(ctx, st::view(me, d, out_mask, waterbody ? SIMPLYP_WB_MASK_ALL : st::DAILY_COLUMNS, out_reaches, n_out_reaches, t, msg));
+    if (!st::flux_slots(out_mask, waterbody ? st::WB_FLUX_COLS : st::FLUX_COLS, t.col))
+        return fail(ctx, SIMPLYP_ERR_ARG, waterbody ? "%s: wb_mask must contain Q_cumecs, Msus_kg/day, TDP_kg/day and PP_kg/day"
+                                                    : "%s: out_mask must contain Qr, Msus_kg/day, TDP_kg/day and PP_kg/day", me);
     return SIMPLYP_OK;
 }
 
@@ -1463,9 +1505,10 @@ static int gof_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mas
                     const double* f_tdp, const double* reach_params,
                     const double* obs, double* gof, simplyp_gof_info* info, bool waterbody = false)
 {
+    const char* me = waterbody ? "simplyp_gof_waterbody" : "simplyp_gof";
     TableView t;
     const bool ptrs_ok = out && f_tdp && (waterbody || reach_params) && obs && gof;
-    if (int rc = check_table(ctx, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, waterbody, t)) return rc;
+    if (int rc = check_table(ctx, me, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, waterbody, t)) return rc;
     const int E = t.E, S = t.S, D = t.D, R = t.R;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
@@ -1568,20 +1611,16 @@ static int gof_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mas
     g.partial = (double*)ctx->gof_partial.ptr;
     g.gof = gof;
 
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    if (int rc = timed_begin(ctx)) return rc;
     hipLaunchKernelGGL(simplyp::simplyp_gof_partial_kernel<0>, dim3(groups, n_chunks_q, R), dim3(simplyp::WAVE), 0, ctx->stream, g);
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(simplyp::simplyp_gof_partial_kernel<1>, dim3(groups, n_chunks_c, R), dim3(simplyp::WAVE), 0, ctx->stream, g);
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(simplyp::simplyp_gof_finish_kernel, dim3(groups, R, NV), dim3(simplyp::WAVE), 0, ctx->stream, g);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (info) memset(info, 0, sizeof(*info));
+    if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr)) return rc;
     if (info) {
-        float ms = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
-        memset(info, 0, sizeof(*info));
-        info->kernel_ms = ms;
         info->n_q_days = (int32_t)q_day.size();
         info->n_chem_days = (int32_t)c_day.size();
         info->bytes_read = ((int64_t)q_day.size() * 8 + (int64_t)c_day.size() * 32) * E;
@@ -1609,7 +1648,7 @@ static int spearman_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t ou
 {
     TableView t;
     const bool ptrs_ok = out && f_tdp && reach_params && obs && rho;
-    if (int rc = check_table(ctx, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, false, t)) return rc;
+    if (int rc = check_table(ctx, "simplyp_gof_spearman", dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, false, t)) return rc;
     const int E = t.E, S = t.S, D = t.D, R = t.R;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     constexpr int NV = SIMPLYP_N_GOF_VARS;
@@ -1710,22 +1749,23 @@ static int waterbody_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t o
                           const int32_t* sum_reaches, int32_t n_sum,
                           uint32_t wb_mask, double* wb, simplyp_wb_info* info)
 {
+    const char* me = "simplyp_waterbody";
     TableView t;
     const bool ptrs_ok = out && f_tdp && reach_params && sum_reaches && wb;
-    if (int rc = check_table(ctx, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, false, t)) return rc;
+    if (int rc = check_table(ctx, me, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, false, t)) return rc;
     const int E = t.E, S = t.S, D = t.D, R = t.R;
     if ((wb_mask & SIMPLYP_WB_MASK_ALL) == 0u || (wb_mask & ~SIMPLYP_WB_MASK_ALL) != 0u)
-        return fail(ctx, SIMPLYP_ERR_ARG, "wb_mask must select 1..%d of the waterbody columns", (int)SIMPLYP_N_WB);
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: wb_mask must select 1..%d of the waterbody columns", me, (int)SIMPLYP_N_WB);
     if (n_sum < 1 || n_sum > simplyp::WB_MAX_REACHES)
-        return fail(ctx, SIMPLYP_ERR_ARG, "n_sum must be in [1, %d] (got %d)", simplyp::WB_MAX_REACHES, n_sum);
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_sum must be in [1, %d] (got %d)", me, simplyp::WB_MAX_REACHES, n_sum);
     simplyp::WaterbodyArgs g{};
     for (int k = 0; k < n_sum; ++k) {
         const int s = sum_reaches[k];
-        if (s < 0 || s >= S) return fail(ctx, SIMPLYP_ERR_ARG, "sum_reaches[%d] = %d out of range", k, s);
-        if (k > 0 && s <= sum_reaches[k - 1]) return fail(ctx, SIMPLYP_ERR_ARG, "sum_reaches must be strictly ascending");
+        if (s < 0 || s >= S) return fail(ctx, SIMPLYP_ERR_ARG, "%s: sum_reaches[%d] = %d out of range", me, k, s);
+        if (k > 0 && s <= sum_reaches[k - 1]) return fail(ctx, SIMPLYP_ERR_ARG, "%s: sum_reaches must be strictly ascending", me);
         int pos = -1;
         for (int r = 0; r < R; ++r) if (t.reach_of[r] == s) pos = r;
-        if (pos < 0) return fail(ctx, SIMPLYP_ERR_ARG, "reach %d is not among the table's output reaches", s);
+        if (pos < 0) return fail(ctx, SIMPLYP_ERR_ARG, "%s: reach %d is not among the table's output reaches", me, s);
         g.pos[k] = pos; g.reach[k] = s;
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1736,18 +1776,14 @@ static int waterbody_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t o
     g.member_of_slot = member_of_slot; g.f_tdp = f_tdp;
     g.a_catch = reach_params + (size_t)SIMPLYP_PR_A_CATCH * S * E;
     g.wb_mask = wb_mask; g.wb = wb;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    if (int rc = timed_begin(ctx)) return rc;
     // two member slots per lane (16-byte accesses) when every row of the tables starts 16-byte aligned
     const bool vec2 = (E % 2 == 0) && (((uintptr_t)out | (uintptr_t)wb) % 16 == 0);
     if (vec2) hipLaunchKernelGGL(simplyp::simplyp_waterbody_kernel<2>, dim3((unsigned)((E / 2 + 255) / 256), (unsigned)D), dim3(256), 0, ctx->stream, g);
     else hipLaunchKernelGGL(simplyp::simplyp_waterbody_kernel<1>, dim3((unsigned)((E + 255) / 256), (unsigned)D), dim3(256), 0, ctx->stream, g);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr)) return rc;
     if (info) {
-        float ms = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
-        info->kernel_ms = ms;
         info->bytes_moved = (int64_t)E * D * (32LL * n_sum + 8LL * popcount32(wb_mask));
     }
     return SIMPLYP_OK;
@@ -1783,13 +1819,7 @@ static int quantile_prepare(simplyp_ctx* ctx, int32_t E, const int32_t* member_o
     }
     g.E = E; g.include_slot = include ? d_mask : nullptr;
     g.T = 2 * K; g.n_passes = d_ints + 1;
-    for (int k = 0; k < K && n_used > 0; ++k) {               // numpy's 'linear' indices
-        const double h = q[k] * (double)(n_used - 1);
-        long long lo = (long long)std::floor(h);
-        lo = std::min<long long>(std::max<long long>(lo, 0), n_used - 1);
-        g.rank[2 * k] = lo;
-        g.rank[2 * k + 1] = std::min<long long>(lo + 1, n_used - 1);
-    }
+    for (int k = 0; k < K && n_used > 0; ++k) st::linear_ranks(q[k], n_used, g.rank[2 * k], g.rank[2 * k + 1]);
     return SIMPLYP_OK;
 }
 
@@ -1817,38 +1847,27 @@ static int quantiles_impl(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const dou
                           const double* q, int32_t K, double* order_stats, simplyp_quantile_info* info)
 {
     if (!ctx) return SIMPLYP_ERR_ARG;
-    if (K < 1 || K > simplyp::QUANT_MAX_K)
-        return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_quantiles: K must be in [1, %d] (got %d)", simplyp::QUANT_MAX_K, (int)K);
     if (E < 1 || n_rows < 0)
         return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_quantiles: E must be >= 1 and n_rows >= 0 (got E = %d, n_rows = %lld)", (int)E, (long long)n_rows);
     if (!table || !q || !order_stats) return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_quantiles: table, q and order_stats must not be NULL");
-    for (int k = 0; k < K; ++k)
-        if (!(q[k] >= 0.0 && q[k] <= 1.0))
-            return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_quantiles: q[%d] = %g is not a probability in [0, 1]", k, q[k]);
+    TABLE_TRY(ctx, st::check_probabilities("simplyp_quantiles", q, K, simplyp::QUANT_MAX_K, msg));
     if (info) { info->kernel_ms = 0.0; info->bytes_table = n_rows * (int64_t)E * 8; info->n_used = 0; info->n_passes = 0; }
     if (n_rows == 0) return SIMPLYP_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    if (int rc = timed_begin(ctx)) return rc;
     simplyp::QuantileArgs g{};
     int n_used = 0;
     if (int rc = quantile_prepare(ctx, E, member_of_slot, include, q, K, g, n_used)) return rc;
-    int* d_ints = g.n_passes - 1;
     const long long n_out = 2LL * K * n_rows;
     if (n_used == 0) {
-        hipLaunchKernelGGL(simplyp::quantile_fill_nan_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, ctx->stream, order_stats, n_out);
-        HIP_TRY(ctx, hipGetLastError());
+        if (int rc = fill_nan(ctx, order_stats, n_out)) return rc;
     } else {
         g.n_rows = n_rows; g.table = table; g.order_stats = order_stats; g.out_row0 = 0; g.out_stride = n_rows;
         if (int rc = quantile_launch(ctx, g, "simplyp_quantiles")) return rc;
     }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
     int n_passes = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&n_passes, d_ints + 1, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr, &n_passes, g.n_passes, sizeof(int))) return rc;
     if (info) {
-        float ms = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
-        info->kernel_ms = ms;
         info->n_used = n_used;
         info->n_passes = n_passes;
     }
@@ -1873,63 +1892,19 @@ static int time_quantiles_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint3
     if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a run is pending on this context; call simplyp_sync first", me);
     if (!dims || dims->E < 1 || dims->S < 1 || dims->D < 0)
         return fail(ctx, SIMPLYP_ERR_ARG, "%s: bad dims (E and S must be >= 1, D >= 0)", me);
-    if (K < 1 || K > simplyp::TQ_MAX_K) return fail(ctx, SIMPLYP_ERR_ARG, "%s: K must be in [1, %d] (got %d)", me, simplyp::TQ_MAX_K, (int)K);
     if (!out || !q || !order_stats) return fail(ctx, SIMPLYP_ERR_ARG, "%s: out, q and order_stats must not be NULL", me);
-    for (int k = 0; k < K; ++k)
-        if (!(q[k] >= 0.0 && q[k] <= 1.0))
-            return fail(ctx, SIMPLYP_ERR_ARG, "%s: q[%d] = %g is not a probability in [0, 1]", me, k, q[k]);
-    if (n_series < 1 || n_series > simplyp::TQ_MAX_SERIES || !series)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_series must be in [1, %d] (got %d) and series not NULL", me, simplyp::TQ_MAX_SERIES, (int)n_series);
-    if (out_mask == 0u || (out_mask & ~(SIMPLYP_MASK_ALL | SIMPLYP_MASK_D_SNOW)) != 0u)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: out_mask must select 1..%d of the columns", me, (int)SIMPLYP_N_OUT);
-    const int E = dims->E, S = dims->S, D = dims->D;
-    const int R = out_reaches ? n_out_reaches : S;
-    if (R <= 0 || R > S) return fail(ctx, SIMPLYP_ERR_ARG, "%s: bad n_out_reaches", me);
-    for (int r = 0; r < R; ++r)
-        if (out_reaches && (out_reaches[r] < 0 || out_reaches[r] >= S)) return fail(ctx, SIMPLYP_ERR_ARG, "%s: out_reaches[%d] out of range", me, r);
+    TABLE_TRY(ctx, st::check_probabilities(me, q, K, simplyp::TQ_MAX_K, msg));
+    st::View tab;
+    TABLE_TRY(ctx, st::view(me, *dims, out_mask, st::DAILY_COLUMNS, out_reaches, n_out_reaches, tab, msg));
+    const int E = tab.E, S = tab.S, D = tab.D, R = tab.R;
+    st::Series sr;
     simplyp::TqArgs g{};
-    static const int flux_cols[4] = {SIMPLYP_OUT_QR, SIMPLYP_OUT_MSUS_FLUX, SIMPLYP_OUT_TDP_FLUX, SIMPLYP_OUT_PP_FLUX};
-    const uint32_t need = (1u << flux_cols[0]) | (1u << flux_cols[1]) | (1u << flux_cols[2]) | (1u << flux_cols[3]);
-    bool derived = false;
-    for (int i = 0; i < n_series; ++i) {
-        const int id = series[i];
-        if (id >= 0 && id < SIMPLYP_N_OUT) {
-            if (!((out_mask >> id) & 1u)) return fail(ctx, SIMPLYP_ERR_ARG, "%s: series[%d] = column %d is not in out_mask", me, i, id);
-            g.series[i] = popcount32(out_mask & ((1u << id) - 1u));
-        } else if (id >= SIMPLYP_TQ_DERIVED && id < SIMPLYP_TQ_DERIVED + SIMPLYP_N_GOF_VARS) {
-            if ((out_mask & need) != need)
-                return fail(ctx, SIMPLYP_ERR_ARG, "%s: series[%d] is derived: out_mask must contain Qr, Msus_kg/day, TDP_kg/day and PP_kg/day", me, i);
-            if (!f_tdp || !reach_params) return fail(ctx, SIMPLYP_ERR_ARG, "%s: series[%d] is derived: f_tdp and reach_params must not be NULL", me, i);
-            g.series[i] = -1 - (id - SIMPLYP_TQ_DERIVED);
-            derived = true;
-        } else {
-            return fail(ctx, SIMPLYP_ERR_ARG, "%s: series[%d] = %d is neither a column nor SIMPLYP_TQ_DERIVED + a variable", me, i, id);
-        }
-    }
+    TABLE_TRY(ctx, st::resolve_series(me, series, n_series, simplyp::TQ_MAX_SERIES, out_mask, R, f_tdp, reach_params, g.series, nullptr, sr, msg));
     if (n_periods < 0 || (!period_of_day && n_periods > 1) || (period_of_day && n_periods < 1))
         return fail(ctx, SIMPLYP_ERR_ARG, "%s: period_of_day needs n_periods >= 1; without it n_periods is 0 (or 1)", me);
     const int P = std::max<int>(n_periods, 1);
-    // the periods' day lists (period_of_day's non-negative entries do not decrease: a period is a day range with holes)
-    std::vector<int32_t> day_ptr(P + 1, 0), days;
-    days.reserve((size_t)D);
-    if (!period_of_day) {
-        for (int d = 0; d < D; ++d) days.push_back(d);
-        day_ptr[1] = D;
-    } else {
-        int last = 0;
-        std::vector<int32_t> count(P, 0);
-        for (int d = 0; d < D; ++d) {
-            const int p = period_of_day[d];
-            if (p < -1 || p >= P) return fail(ctx, SIMPLYP_ERR_ARG, "%s: period_of_day[%d] = %d is outside [-1, %d)", me, d, p, P);
-            if (p < 0) continue;
-            if (p < last) return fail(ctx, SIMPLYP_ERR_ARG, "%s: period_of_day decreases at day %d (%d after %d)", me, d, p, last);
-            last = p;
-            days.push_back(d);
-            ++count[p];
-        }
-        for (int p = 0; p < P; ++p) day_ptr[p + 1] = day_ptr[p] + count[p];
-    }
-    if ((long long)n_series * R > 65535) return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_series * n_out_reaches must not exceed 65535", me);
+    std::vector<int32_t> day_ptr, days;
+    TABLE_TRY(ctx, st::period_days(me, period_of_day, D, P, days, day_ptr, msg));
     if (n_days) for (int p = 0; p < P; ++p) n_days[p] = day_ptr[p + 1] - day_ptr[p];
     if (info) { info->kernel_ms = 0.0; info->bytes_read = 0; info->n_sweeps = 0; info->n_periods = P; }
 
@@ -1941,13 +1916,7 @@ static int time_quantiles_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint3
         const long long n = day_ptr[p + 1] - day_ptr[p];
         if (n <= 0) continue;
         long long want[2 * simplyp::TQ_MAX_K];
-        for (int k = 0; k < K; ++k) {                          // numpy's 'linear' indices
-            const double h = q[k] * (double)(n - 1);
-            long long lo = (long long)std::floor(h);
-            lo = std::min<long long>(std::max<long long>(lo, 0), n - 1);
-            want[k] = lo;
-            want[K + k] = std::min<long long>(lo + 1, n - 1);
-        }
+        for (int k = 0; k < K; ++k) st::linear_ranks(q[k], n, want[k], want[K + k]);
         std::vector<long long> u(want, want + T);
         std::sort(u.begin(), u.end());
         u.erase(std::unique(u.begin(), u.end()), u.end());
@@ -1959,8 +1928,7 @@ static int time_quantiles_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint3
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const long long n_out = 2LL * K * n_series * P * R * E;
     if (days.empty()) {                                        // no day takes part in any period (D = 0 among them): all NaN
-        hipLaunchKernelGGL(simplyp::quantile_fill_nan_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, ctx->stream, order_stats, n_out);
-        HIP_TRY(ctx, hipGetLastError());
+        if (int rc = fill_nan(ctx, order_stats, n_out)) return rc;
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         return SIMPLYP_OK;
     }
@@ -1972,7 +1940,7 @@ static int time_quantiles_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint3
     const size_t o_ranks = ints.size();
     ints.insert(ints.end(), ranks.begin(), ranks.end());
     const size_t o_reach = ints.size();
-    for (int r = 0; r < R; ++r) ints.push_back(out_reaches ? out_reaches[r] : r);
+    ints.insert(ints.end(), tab.reach_of.begin(), tab.reach_of.end());
     const size_t int_bytes = ints.size() * sizeof(int32_t);
     if (int rc = ensure(ctx, ctx->tquant, 16 + int_bytes + rank_of.size())) return rc;
     char* base = (char*)ctx->tquant.ptr;
@@ -1983,29 +1951,24 @@ static int time_quantiles_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint3
 
     g.E = E; g.R = R; g.D = D; g.K = K; g.T = T; g.n_series = n_series; g.n_periods = P;
     g.out = out; g.col_stride = (long long)D * R * E;
-    for (int i = 0; i < 4; ++i) g.col[i] = popcount32(out_mask & ((1u << flux_cols[i]) - 1u));
+    st::flux_slots(out_mask, st::FLUX_COLS, g.col);
     g.member_of_slot = member_of_slot;
     g.f_tdp = f_tdp;
-    g.a_catch = derived ? reach_params + (size_t)SIMPLYP_PR_A_CATCH * S * E : nullptr;
+    g.a_catch = sr.derived ? reach_params + (size_t)SIMPLYP_PR_A_CATCH * S * E : nullptr;
     g.day = d_ints; g.day_ptr = d_ints + o_ptr; g.ranks = d_ints + o_ranks; g.reach_of = d_ints + o_reach;
     g.rank_of = (const uint8_t*)(base + 16 + int_bytes);
     g.order_stats = order_stats;
     g.rows_read = (unsigned long long*)base;
     g.n_sweeps = (int*)(base + 8);
     const dim3 grid((unsigned)((E + 63) / 64), (unsigned)std::min(P, 65535), (unsigned)(n_series * R));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    if (int rc = timed_begin(ctx)) return rc;
     // the per-rank state of 8 ranks (K <= 4) leaves room for two workgroups' histograms per CU; 32 ranks for one
     if (T <= 8) hipLaunchKernelGGL(simplyp::simplyp_time_quantile_kernel<8>, grid, dim3(64), 0, ctx->stream, g);
     else hipLaunchKernelGGL(simplyp::simplyp_time_quantile_kernel<32>, grid, dim3(64), 0, ctx->stream, g);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
     unsigned long long counters[2] = {0ull, 0ull};
-    HIP_TRY(ctx, hipMemcpyAsync(counters, base, 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr, counters, base, 16)) return rc;
     if (info) {
-        float ms = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
-        info->kernel_ms = ms;
         info->bytes_read = (int64_t)(counters[0] * 512ull);
         info->n_sweeps = (int32_t)(counters[1] & 0xFFFFFFFFull);
     }
@@ -2028,57 +1991,23 @@ int simplyp_time_quantiles(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t 
 static int predictive_setup(simplyp_ctx* ctx, const char* me, const simplyp_dims* dims, uint32_t out_mask,
                             const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
                             const double* f_tdp, const double* reach_params, const int32_t* series, int32_t n_series,
-                            const double* err_m, uint64_t seed, int32_t day0, simplyp::PredArgs& g,
-                            std::vector<int32_t>& reach_of, int64_t& loads)
+                            const double* err_m, uint64_t seed, int32_t day0, simplyp::PredArgs& g, st::View& t, st::Series& sr)
 {
     if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a run is pending on this context; call simplyp_sync first", me);
     if (!dims || dims->E < 1 || dims->S < 1 || dims->D < 0)
         return fail(ctx, SIMPLYP_ERR_ARG, "%s: bad dims (E and S must be >= 1, D >= 0: the table's daily rows)", me);
     if (!out) return fail(ctx, SIMPLYP_ERR_ARG, "%s: out must not be NULL", me);
-    if (n_series < 1 || n_series > simplyp::PRED_MAX_SERIES || !series)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_series must be in [1, %d] (got %d) and series not NULL", me, simplyp::PRED_MAX_SERIES, (int)n_series);
-    if (out_mask == 0u || (out_mask & ~(SIMPLYP_MASK_ALL | SIMPLYP_MASK_D_SNOW)) != 0u)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: out_mask must select 1..%d of the columns", me, (int)SIMPLYP_N_OUT);
     if (day0 < 0 || (long long)day0 + dims->D > 0x7FFFFFFFLL)
         return fail(ctx, SIMPLYP_ERR_ARG, "%s: day0 must be >= 0 and day0 + D fit 31 bits (got %d)", me, (int)day0);
-    const int E = dims->E, S = dims->S, D = dims->D;
-    const int R = out_reaches ? n_out_reaches : S;
-    if (R <= 0 || R > S) return fail(ctx, SIMPLYP_ERR_ARG, "%s: bad n_out_reaches", me);
-    reach_of.resize(R);
-    for (int r = 0; r < R; ++r) {
-        reach_of[r] = out_reaches ? out_reaches[r] : r;
-        if (reach_of[r] < 0 || reach_of[r] >= S) return fail(ctx, SIMPLYP_ERR_ARG, "%s: out_reaches[%d] out of range", me, r);
-    }
-    if ((long long)n_series * R > 65535) return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_series * n_out_reaches must not exceed 65535", me);
-    static const int flux_cols[4] = {SIMPLYP_OUT_QR, SIMPLYP_OUT_MSUS_FLUX, SIMPLYP_OUT_TDP_FLUX, SIMPLYP_OUT_PP_FLUX};
-    const uint32_t need = (1u << flux_cols[0]) | (1u << flux_cols[1]) | (1u << flux_cols[2]) | (1u << flux_cols[3]);
-    bool derived = false;
-    loads = 0;
-    for (int i = 0; i < n_series; ++i) {
-        const int id = series[i];
-        if (id >= 0 && id < SIMPLYP_N_OUT) {
-            if (!((out_mask >> id) & 1u)) return fail(ctx, SIMPLYP_ERR_ARG, "%s: series[%d] = column %d is not in out_mask", me, i, id);
-            g.series[i] = popcount32(out_mask & ((1u << id) - 1u));
-            loads += 1;
-        } else if (id >= SIMPLYP_TQ_DERIVED && id < SIMPLYP_TQ_DERIVED + SIMPLYP_N_GOF_VARS) {
-            if ((out_mask & need) != need)
-                return fail(ctx, SIMPLYP_ERR_ARG, "%s: series[%d] is derived: out_mask must contain Qr, Msus_kg/day, TDP_kg/day and PP_kg/day", me, i);
-            if (!f_tdp || !reach_params) return fail(ctx, SIMPLYP_ERR_ARG, "%s: series[%d] is derived: f_tdp and reach_params must not be NULL", me, i);
-            const int var = id - SIMPLYP_TQ_DERIVED;
-            g.series[i] = -1 - var;
-            loads += var == SIMPLYP_GOF_Q ? 1 : var == SIMPLYP_GOF_TP ? 3 : 2;
-            derived = true;
-        } else {
-            return fail(ctx, SIMPLYP_ERR_ARG, "%s: series[%d] = %d is neither a column nor SIMPLYP_TQ_DERIVED + a variable", me, i, id);
-        }
-        g.series_id[i] = (uint32_t)id;
-    }
+    TABLE_TRY(ctx, st::view(me, *dims, out_mask, st::DAILY_COLUMNS, out_reaches, n_out_reaches, t, msg));
+    const int E = t.E, S = t.S, D = t.D, R = t.R;
+    TABLE_TRY(ctx, st::resolve_series(me, series, n_series, simplyp::PRED_MAX_SERIES, out_mask, R, f_tdp, reach_params, g.series, g.series_id, sr, msg));
     g.E = E; g.R = R; g.n_series = n_series;
     g.out = out; g.col_stride = (long long)D * R * E;
-    for (int i = 0; i < 4; ++i) g.col[i] = popcount32(out_mask & ((1u << flux_cols[i]) - 1u));
+    st::flux_slots(out_mask, st::FLUX_COLS, g.col);
     g.member_of_slot = member_of_slot;
     g.f_tdp = f_tdp;
-    g.a_catch = derived ? reach_params + (size_t)SIMPLYP_PR_A_CATCH * S * E : nullptr;
+    g.a_catch = sr.derived ? reach_params + (size_t)SIMPLYP_PR_A_CATCH * S * E : nullptr;
     g.err_m = err_m;
     g.key0 = (uint32_t)(seed & 0xFFFFFFFFull); g.key1 = (uint32_t)(seed >> 32);
     g.day0 = (uint32_t)day0;
@@ -2118,13 +2047,13 @@ static int predictive_series_impl(simplyp_ctx* ctx, const simplyp_dims* dims, ui
     if (which == 1 && !err_m) return fail(ctx, SIMPLYP_ERR_ARG, "%s: which = 1 (the normals) needs err_m", me);
     if (!table) return fail(ctx, SIMPLYP_ERR_ARG, "%s: table must not be NULL", me);
     simplyp::PredArgs g{};
-    std::vector<int32_t> reach_of;
-    int64_t loads = 0;
+    st::View t;
+    st::Series sr;
     if (int rc = predictive_setup(ctx, me, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
-                                  series, n_series, err_m, seed, day0, g, reach_of, loads)) return rc;
+                                  series, n_series, err_m, seed, day0, g, t, sr)) return rc;
     if (dims->D == 0) return SIMPLYP_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = predictive_workspace(ctx, reach_of, 0, g)) return rc;
+    if (int rc = predictive_workspace(ctx, t.reach_of, 0, g)) return rc;
     g.normals = which;
     if (int rc = predictive_launch(ctx, g, 0, dims->D, table)) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -2146,16 +2075,13 @@ static int predictive_bands_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uin
 {
     const char* me = "simplyp_predictive_bands";
     if (!ctx) return SIMPLYP_ERR_ARG;
-    if (K < 1 || K > simplyp::QUANT_MAX_K) return fail(ctx, SIMPLYP_ERR_ARG, "%s: K must be in [1, %d] (got %d)", me, simplyp::QUANT_MAX_K, (int)K);
     if (!q || !order_stats) return fail(ctx, SIMPLYP_ERR_ARG, "%s: q and order_stats must not be NULL", me);
-    for (int k = 0; k < K; ++k)
-        if (!(q[k] >= 0.0 && q[k] <= 1.0))
-            return fail(ctx, SIMPLYP_ERR_ARG, "%s: q[%d] = %g is not a probability in [0, 1]", me, k, q[k]);
+    TABLE_TRY(ctx, st::check_probabilities(me, q, K, simplyp::QUANT_MAX_K, msg));
     simplyp::PredArgs g{};
-    std::vector<int32_t> reach_of;
-    int64_t loads = 0;
+    st::View t;
+    st::Series sr;
     if (int rc = predictive_setup(ctx, me, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
-                                  series, n_series, err_m, seed, day0, g, reach_of, loads)) return rc;
+                                  series, n_series, err_m, seed, day0, g, t, sr)) return rc;
     const int E = g.E, R = g.R, D = dims->D;
     if (info) { info->kernel_ms = 0.0; info->gen_ms = 0.0; info->bytes_read = 0; info->bytes_workspace = 0; info->n_used = 0; info->n_passes = 0; info->n_chunks = 0; }
     if (D == 0) return SIMPLYP_OK;
@@ -2172,18 +2098,16 @@ static int predictive_bands_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uin
     EventPair ev;
     HIP_TRY(ctx, hipEventCreate(&ev.a));
     HIP_TRY(ctx, hipEventCreate(&ev.b));
-    if (int rc = predictive_workspace(ctx, reach_of, (size_t)chunk_days * day_bytes, g)) return rc;
+    if (int rc = predictive_workspace(ctx, t.reach_of, (size_t)chunk_days * day_bytes, g)) return rc;
     double* work = (double*)((char*)ctx->pred.ptr + PRED_REACH_BYTES);
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    if (int rc = timed_begin(ctx)) return rc;
     simplyp::QuantileArgs s{};
     int n_used = 0;
     if (int rc = quantile_prepare(ctx, E, member_of_slot, include, q, K, s, n_used)) return rc;      // once per call
     const long long n_rows_all = (long long)n_series * D * R;
     double gen_ms = 0.0;
     if (n_used == 0) {
-        const long long n_out = 2LL * K * n_rows_all;
-        hipLaunchKernelGGL(simplyp::quantile_fill_nan_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, ctx->stream, order_stats, n_out);
-        HIP_TRY(ctx, hipGetLastError());
+        if (int rc = fill_nan(ctx, order_stats, 2LL * K * n_rows_all)) return rc;
     } else {
         s.order_stats = order_stats; s.out_stride = n_rows_all;
         for (int c = 0; c < n_chunks; ++c) {
@@ -2204,16 +2128,11 @@ static int predictive_bands_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uin
             gen_ms += ms;
         }
     }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
     int n_passes = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&n_passes, s.n_passes, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr, &n_passes, s.n_passes, sizeof(int))) return rc;
     if (info) {
-        float ms = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
-        info->kernel_ms = ms;
         info->gen_ms = gen_ms;
-        info->bytes_read = n_used == 0 ? 0 : loads * (int64_t)D * R * E * 8;
+        info->bytes_read = n_used == 0 ? 0 : sr.loads * (int64_t)D * R * E * 8;
         info->bytes_workspace = (int64_t)((size_t)chunk_days * day_bytes);
         info->n_used = n_used;
         info->n_passes = n_passes;
@@ -2258,28 +2177,11 @@ static int mcmc_move(simplyp_ctx* ctx, const char* me, int32_t W, int32_t n_dim,
     return SIMPLYP_OK;
 }
 
-// The counters zeroed before a launch; read back with the launch's time afterwards.
-static int mcmc_begin(simplyp_ctx* ctx, unsigned*& counters)
+static int mcmc_info(simplyp_ctx* ctx, simplyp_mcmc_info* info)
 {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = ensure(ctx, ctx->mcmc, 4 * sizeof(unsigned))) return rc;
-    counters = (unsigned*)ctx->mcmc.ptr;
-    HIP_TRY(ctx, hipMemsetAsync(counters, 0, 4 * sizeof(unsigned), ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    return SIMPLYP_OK;
-}
-
-static int mcmc_end(simplyp_ctx* ctx, simplyp_mcmc_info* info)
-{
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
-    unsigned c[4] = {0, 0, 0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(c, ctx->mcmc.ptr, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned c[4] = {};
+    if (int rc = counters_end(ctx, ctx->mcmc, 4, c, info ? &info->kernel_ms : nullptr)) return rc;
     if (info) {
-        float ms = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
-        info->kernel_ms = ms;
         info->n_inside = (int32_t)c[0]; info->n_accepted = (int32_t)c[1]; info->n_nan = (int32_t)c[2]; info->reserved = 0;
     }
     return SIMPLYP_OK;
@@ -2295,25 +2197,12 @@ static int mcmc_propose_impl(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t
     if (int rc = mcmc_move(ctx, me, W, n_dim, half, a, seed, t, g.mv)) return rc;
     if (!lo || !hi || !target || !theta || !prop || !inside)
         return fail(ctx, SIMPLYP_ERR_ARG, "%s: lo, hi, target, theta, prop and inside must not be NULL", me);
-    bool to_params = false, to_f_tdp = false;
-    for (int d = 0; d < n_dim; ++d) {
-        if (!(lo[d] < hi[d])) return fail(ctx, SIMPLYP_ERR_ARG, "%s: the box needs lo[%d] < hi[%d] (got %g, %g)", me, d, d, lo[d], hi[d]);
-        if (target[d] < simplyp::MCMC_TARGET_NONE || target[d] >= SIMPLYP_NP_M)
-            return fail(ctx, SIMPLYP_ERR_ARG, "%s: target[%d] = %d is outside [-2, %d)", me, d, (int)target[d], (int)SIMPLYP_NP_M);
-        for (int e = 0; e < d; ++e)
-            if (target[d] != simplyp::MCMC_TARGET_NONE && target[e] == target[d])
-                return fail(ctx, SIMPLYP_ERR_ARG, "%s: target[%d] and target[%d] name the same row (%d)", me, e, d, (int)target[d]);
-        to_params = to_params || target[d] >= 0;
-        to_f_tdp = to_f_tdp || target[d] == simplyp::MCMC_TARGET_F_TDP;
-        g.lo[d] = lo[d]; g.hi[d] = hi[d]; g.target[d] = target[d];
-    }
-    if ((to_params && !member_params) || (to_f_tdp && !f_tdp))
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: a target names member_params or f_tdp, which is NULL", me);
+    TABLE_TRY(ctx, st::check_box(me, n_dim, lo, hi, target, member_params, f_tdp, g.lo, g.hi, g.target, msg));
     g.theta = theta; g.prop = prop; g.inside = inside; g.member_params = member_params; g.f_tdp = f_tdp;
-    if (int rc = mcmc_begin(ctx, g.counters)) return rc;
+    if (int rc = counters_begin(ctx, ctx->mcmc, 4, g.counters)) return rc;
     hipLaunchKernelGGL(simplyp::simplyp_mcmc_propose_kernel, dim3((unsigned)((g.mv.h + simplyp::MCMC_THREADS - 1) / simplyp::MCMC_THREADS)),
                        dim3(simplyp::MCMC_THREADS), 0, ctx->stream, g);
-    return mcmc_end(ctx, info);
+    return mcmc_info(ctx, info);
 }
 
 static int mcmc_log_prob_impl(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t n_out_reaches, const double* gof,
@@ -2343,10 +2232,10 @@ static int mcmc_log_prob_impl(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_
     }
     g.h = mv.h; g.R = n_out_reaches; g.n_pairs = n_pairs;
     g.gof = gof; g.status = status; g.inside = inside; g.prop = prop; g.lp_prop = lp_prop;
-    if (int rc = mcmc_begin(ctx, g.counters)) return rc;
+    if (int rc = counters_begin(ctx, ctx->mcmc, 4, g.counters)) return rc;
     hipLaunchKernelGGL(simplyp::simplyp_mcmc_log_prob_kernel, dim3((unsigned)((g.h + simplyp::MCMC_THREADS - 1) / simplyp::MCMC_THREADS)),
                        dim3(simplyp::MCMC_THREADS), 0, ctx->stream, g);
-    return mcmc_end(ctx, info);
+    return mcmc_info(ctx, info);
 }
 
 static int mcmc_accept_impl(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t half, double a, uint64_t seed, uint32_t t,
@@ -2360,10 +2249,10 @@ static int mcmc_accept_impl(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t 
     if (!prop || !inside || !lp_prop || !theta || !lp || !n_accept)
         return fail(ctx, SIMPLYP_ERR_ARG, "%s: prop, inside, lp_prop, theta, lp and n_accept must not be NULL", me);
     g.prop = prop; g.inside = inside; g.lp_prop = lp_prop; g.theta = theta; g.lp = lp; g.n_accept = n_accept; g.chain_row = chain_row;
-    if (int rc = mcmc_begin(ctx, g.counters)) return rc;
+    if (int rc = counters_begin(ctx, ctx->mcmc, 4, g.counters)) return rc;
     hipLaunchKernelGGL(simplyp::simplyp_mcmc_accept_kernel, dim3((unsigned)((g.mv.h + simplyp::MCMC_THREADS - 1) / simplyp::MCMC_THREADS)),
                        dim3(simplyp::MCMC_THREADS), 0, ctx->stream, g);
-    return mcmc_end(ctx, info);
+    return mcmc_info(ctx, info);
 }
 
 int simplyp_mcmc_propose(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t half, double a, uint64_t seed, uint32_t t,
@@ -2400,27 +2289,11 @@ static int nm_shape(simplyp_ctx* ctx, const char* me, int32_t S, int32_t n_dim)
     return SIMPLYP_OK;
 }
 
-static int nm_begin(simplyp_ctx* ctx, unsigned*& counters)
+static int nm_info(simplyp_ctx* ctx, simplyp_nm_info* info)
 {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = ensure(ctx, ctx->nm, 8 * sizeof(unsigned))) return rc;
-    counters = (unsigned*)ctx->nm.ptr;
-    HIP_TRY(ctx, hipMemsetAsync(counters, 0, 8 * sizeof(unsigned), ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-    return SIMPLYP_OK;
-}
-
-static int nm_end(simplyp_ctx* ctx, simplyp_nm_info* info)
-{
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
-    unsigned c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(c, ctx->nm.ptr, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    unsigned c[8] = {};
+    if (int rc = counters_end(ctx, ctx->nm, 8, c, info ? &info->kernel_ms : nullptr)) return rc;
     if (info) {
-        float ms = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
-        info->kernel_ms = ms;
         info->n_active = (int32_t)c[0]; info->n_converged = (int32_t)c[1]; info->n_shrinking = (int32_t)c[2];
         info->n_nonfinite_start = (int32_t)c[3]; info->n_inside = (int32_t)c[4]; info->reserved = 0;
     }
@@ -2437,26 +2310,13 @@ static int nm_propose_impl(simplyp_ctx* ctx, int32_t S, int32_t n_dim, const dou
     if (!lo || !hi || !target || !sim || !istate || !prop || !inside)
         return fail(ctx, SIMPLYP_ERR_ARG, "%s: lo, hi, target, sim, istate, prop and inside must not be NULL", me);
     simplyp::NmProposeArgs g{};
-    bool to_params = false, to_f_tdp = false;
-    for (int d = 0; d < n_dim; ++d) {
-        if (!(lo[d] < hi[d])) return fail(ctx, SIMPLYP_ERR_ARG, "%s: the box needs lo[%d] < hi[%d] (got %g, %g)", me, d, d, lo[d], hi[d]);
-        if (target[d] < simplyp::MCMC_TARGET_NONE || target[d] >= SIMPLYP_NP_M)
-            return fail(ctx, SIMPLYP_ERR_ARG, "%s: target[%d] = %d is outside [-2, %d)", me, d, (int)target[d], (int)SIMPLYP_NP_M);
-        for (int e = 0; e < d; ++e)
-            if (target[d] != simplyp::MCMC_TARGET_NONE && target[e] == target[d])
-                return fail(ctx, SIMPLYP_ERR_ARG, "%s: target[%d] and target[%d] name the same row (%d)", me, e, d, (int)target[d]);
-        to_params = to_params || target[d] >= 0;
-        to_f_tdp = to_f_tdp || target[d] == simplyp::MCMC_TARGET_F_TDP;
-        g.lo[d] = lo[d]; g.hi[d] = hi[d]; g.target[d] = target[d];
-    }
-    if ((to_params && !member_params) || (to_f_tdp && !f_tdp))
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: a target names member_params or f_tdp, which is NULL", me);
+    TABLE_TRY(ctx, st::check_box(me, n_dim, lo, hi, target, member_params, f_tdp, g.lo, g.hi, g.target, msg));
     g.S = S; g.n_dim = n_dim;
     g.sim = sim; g.istate = istate; g.prop = prop; g.inside = inside; g.member_params = member_params; g.f_tdp = f_tdp;
-    if (int rc = nm_begin(ctx, g.counters)) return rc;
+    if (int rc = counters_begin(ctx, ctx->nm, 8, g.counters)) return rc;
     hipLaunchKernelGGL(simplyp::simplyp_nm_propose_kernel, dim3((unsigned)((S + simplyp::NM_THREADS - 1) / simplyp::NM_THREADS)),
                        dim3(simplyp::NM_THREADS), 0, ctx->stream, g);
-    return nm_end(ctx, info);
+    return nm_info(ctx, info);
 }
 
 static int nm_update_impl(simplyp_ctx* ctx, int32_t S, int32_t n_dim, int32_t max_iter, double xatol, double fatol,
@@ -2478,10 +2338,10 @@ static int nm_update_impl(simplyp_ctx* ctx, int32_t S, int32_t n_dim, int32_t ma
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (int rc = ensure(ctx, ctx->nm_work, (size_t)(n_dim + 1) * (size_t)(n_dim + 1) * (size_t)S * sizeof(double))) return rc;
     g.work = (double*)ctx->nm_work.ptr;
-    if (int rc = nm_begin(ctx, g.counters)) return rc;
+    if (int rc = counters_begin(ctx, ctx->nm, 8, g.counters)) return rc;
     hipLaunchKernelGGL(simplyp::simplyp_nm_update_kernel, dim3((unsigned)((S + simplyp::NM_THREADS - 1) / simplyp::NM_THREADS)),
                        dim3(simplyp::NM_THREADS), 0, ctx->stream, g);
-    return nm_end(ctx, info);
+    return nm_info(ctx, info);
 }
 
 int simplyp_nm_propose(simplyp_ctx* ctx, int32_t S, int32_t n_dim, const double* lo, const double* hi, const int32_t* target,

@@ -9,6 +9,7 @@ torch is used for plumbing only: device buffers, the current HIP stream and
 """
 
 import ctypes as C
+import glob
 import os
 import subprocess
 
@@ -41,21 +42,16 @@ class EngineError(RuntimeError):
 
 def build(force=False, verbose=False):
     """Compile the HIP library for gfx950 (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, 'simplyp_hip.hip'), os.path.join(CSRC, 'simplyp_kernels.hip.h'),
-            os.path.join(CSRC, 'simplyp_gof.hip.h'), os.path.join(CSRC, 'simplyp_waterbody.hip.h'),
-            os.path.join(CSRC, 'simplyp_quantile.hip.h'), os.path.join(CSRC, 'simplyp_time_quantile.hip.h'),
-            os.path.join(CSRC, 'simplyp_predictive.hip.h'), os.path.join(CSRC, 'simplyp_mcmc.hip.h'),
-            os.path.join(CSRC, 'simplyp_neldermead.hip.h'),
-            os.path.join(CSRC, 'simplyp_pack.h'),
-            os.path.join(CSRC, 'simplyp_pack_stream.h'),
-            os.path.join(INCLUDE, 'simplyp.h'), os.path.join(INCLUDE, 'simplyp_controller.h')]
+    main = os.path.join(CSRC, 'simplyp_hip.hip')
+    # everything the one translation unit can include: a header left out here would leave a stale library in use
+    srcs = glob.glob(os.path.join(CSRC, '*.hip')) + glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(INCLUDE, '*.h'))
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in srcs):
         return LIB_PATH
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     # -ffp-contract=off: every fused multiply-add in the kernels is written explicitly, so the chain kernel and the
     # task-queue kernel (same source, different inlining context) round identically and stay bit-for-bit equal
     cmd = [hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared',
-           '-o', LIB_PATH, srcs[0]]
+           '-o', LIB_PATH, main]
     if verbose:
         cmd.insert(1, '-Rpass-analysis=kernel-resource-usage')
     subprocess.check_call(cmd)
@@ -459,6 +455,65 @@ class Engine(object):
             self._check(lib().simplyp_eval_units(self._h, w, a.shape[0], a.data_ptr(), out.data_ptr()), 'simplyp_eval_units')
         return out.cpu().numpy()
 
+    # ---- what the reductions over a table check alike ----
+    @staticmethod
+    def _ptr(t):
+        return None if t is None else t.data_ptr()
+
+    def _f_tdp(self, f_tdp, E):
+        torch = self.torch
+        ft = self.to_device(np.ascontiguousarray(np.broadcast_to(np.asarray(f_tdp, dtype=np.float64), (E,)))
+                            if not torch.is_tensor(f_tdp) else f_tdp, torch.float64)
+        if tuple(ft.shape) != (E,):
+            raise ValueError("f_tdp must be a scalar or have one entry per member")
+        return ft
+
+    @staticmethod
+    def _q_array(q):
+        qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+        if qa.ndim != 1:
+            raise ValueError("q must be a list of probabilities")
+        return qa
+
+    def _include_mask(self, include, E):
+        torch = self.torch
+        if include is None:
+            return None
+        inc = include if torch.is_tensor(include) else torch.from_numpy(np.ascontiguousarray(np.asarray(include) != 0))
+        inc = (inc != 0).to(torch.uint8).to(self.tdev).contiguous()
+        if tuple(inc.shape) != (E,):
+            raise ValueError("include must have one entry per member")
+        return inc
+
+    def _check_member_of_slot(self, member_of_slot, E):
+        if member_of_slot is not None and (member_of_slot.dtype != self.torch.int32 or tuple(member_of_slot.shape) != (E,)):
+            raise ValueError("member_of_slot must be an int32 device tensor with one entry per member")
+
+    def _daily_table(self, out, out_mask, reach_params, out_reaches, member_of_slot, need_reach_params=False):
+        """The daily table ``out`` [n_cols, D, n_reaches, E] of a previous ``run`` and what comes with it, checked against each
+        other: ``out_mask``, ``out_reaches``, ``reach_params`` (to the device; may be None unless ``need_reach_params``) and
+        ``member_of_slot``.  Returns (head, rp, (D, n_reaches, E), keep): the arguments every table entry of the library starts
+        with, the device copy of ``reach_params``, the sizes, and what must stay alive until the call is over."""
+        torch = self.torch
+        if not torch.is_tensor(out) or out.dim() != 4 or out.dtype != torch.float64 or not out.is_contiguous() \
+                or out.device != self.tdev:
+            raise ValueError("out must be a contiguous float64 tensor [n_cols, D, n_reaches, E] on %s" % (self.tdev,))
+        ncols, D, n_or, E = (int(x) for x in out.shape)
+        oreach = _i32(out_reaches)
+        if need_reach_params and reach_params is None:
+            raise ValueError("reach_params [NP_R, S, E] is needed")
+        rp = None if reach_params is None else self.to_device(reach_params, torch.float64)
+        S = int(rp.shape[1]) if rp is not None else (n_or if oreach is None else max(n_or, int(oreach.max()) + 1))
+        if ncols != bin(out_mask).count('1') or n_or != (S if oreach is None else len(oreach)) \
+                or (rp is not None and int(rp.shape[2]) != E):
+            raise ValueError("out %s does not match out_mask / out_reaches / reach_params %s"
+                             % (tuple(out.shape), None if rp is None else tuple(rp.shape)))
+        self._check_member_of_slot(member_of_slot, E)
+        dims = abi.Dims(E, S, D, 1)
+        head = (self._h, C.byref(dims), int(out_mask), None if oreach is None else oreach.ctypes.data_as(C.POINTER(C.c_int32)), n_or,
+                out.data_ptr(), self._ptr(member_of_slot))
+        return head, rp, (D, n_or, E), [dims, oreach, rp]
+
     def gof(self, out, out_mask, obs, f_tdp, reach_params, out_reaches=None, member_of_slot=None, spearman=False, gof=None):
         """Per-member goodness-of-fit statistics (the reference's ``goodness_of_fit_stats``,
         visualise_results.py:387-474, without Spearman's r) of the daily table ``out`` of a previous ``run``.
@@ -472,58 +527,34 @@ class Engine(object):
         float64 device tensor of the result's shape to write into instead of a new one (a loop that reduces run after run)."""
         torch = self.torch
         L = lib()
-        rp = self.to_device(reach_params, torch.float64)
-        npr, S, E = rp.shape
-        ncols, D, n_or, E2 = out.shape
-        oreach = _i32(out_reaches)
-        if (E2 != E or ncols != bin(out_mask).count('1') or n_or != (S if oreach is None else len(oreach))
-                or out.dtype != torch.float64 or not out.is_contiguous()):
-            raise ValueError("out %s does not match out_mask / out_reaches / reach_params %s" % (tuple(out.shape), tuple(rp.shape)))
+        head, rp, (D, n_or, E), keep = self._daily_table(out, out_mask, reach_params, out_reaches, member_of_slot, True)
         obs = np.ascontiguousarray(obs, dtype=np.float64)
         if obs.shape != (n_or, len(abi.GOF_VARS), D):
             raise ValueError("obs must have shape %s, got %s" % ((n_or, len(abi.GOF_VARS), D), obs.shape))
-        ft = self.to_device(np.broadcast_to(np.asarray(f_tdp, dtype=np.float64), (E,)) if not torch.is_tensor(f_tdp) else f_tdp,
-                            torch.float64)
-        if tuple(ft.shape) != (E,):
-            raise ValueError("f_tdp must be a scalar or have one entry per member")
+        ft = self._f_tdp(f_tdp, E)
         shape = (len(abi.GOF_STATS), len(abi.GOF_VARS), n_or, E)
         if gof is None:
             gof = torch.empty(shape, dtype=torch.float64, device=self.tdev)
         elif tuple(gof.shape) != shape or gof.dtype != torch.float64 or not gof.is_contiguous() or gof.device != self.tdev:
             raise ValueError("gof must be a contiguous float64 tensor of shape %s on %s" % (shape, self.tdev))
         info = abi.GofInfo()
-        dims = abi.Dims(E, S, D, 1)
+        tail = (ft.data_ptr(), rp.data_ptr(), obs.ctypes.data_as(C.POINTER(C.c_double)))
         with torch.cuda.device(self.tdev):
             self._bind_stream()
-            rc = L.simplyp_gof(self._h, C.byref(dims), int(out_mask),
-                               None if oreach is None else oreach.ctypes.data_as(C.POINTER(C.c_int32)), n_or,
-                               out.data_ptr(), None if member_of_slot is None else member_of_slot.data_ptr(),
-                               ft.data_ptr(), rp.data_ptr(), obs.ctypes.data_as(C.POINTER(C.c_double)), gof.data_ptr(),
-                               C.byref(info))
+            rc = L.simplyp_gof(*(head + tail + (gof.data_ptr(), C.byref(info))))
         self._check(rc, 'simplyp_gof')
         d = info.as_dict()
         if spearman:
             rho = torch.empty((len(abi.GOF_VARS), n_or, E), dtype=torch.float64, device=self.tdev)
             sinfo = abi.GofInfo()
             with torch.cuda.device(self.tdev):
-                rc = L.simplyp_gof_spearman(self._h, C.byref(dims), int(out_mask),
-                                            None if oreach is None else oreach.ctypes.data_as(C.POINTER(C.c_int32)), n_or,
-                                            out.data_ptr(), None if member_of_slot is None else member_of_slot.data_ptr(),
-                                            ft.data_ptr(), rp.data_ptr(), obs.ctypes.data_as(C.POINTER(C.c_double)),
-                                            rho.data_ptr(), C.byref(sinfo))
+                rc = L.simplyp_gof_spearman(*(head + tail + (rho.data_ptr(), C.byref(sinfo))))
             self._check(rc, 'simplyp_gof_spearman')
             d['spearman'] = rho
             d['spearman_ms'] = sinfo.kernel_ms
+        del keep
         return gof, d
 
-
-    def _f_tdp(self, f_tdp, E):
-        torch = self.torch
-        ft = self.to_device(np.ascontiguousarray(np.broadcast_to(np.asarray(f_tdp, dtype=np.float64), (E,)))
-                            if not torch.is_tensor(f_tdp) else f_tdp, torch.float64)
-        if tuple(ft.shape) != (E,):
-            raise ValueError("f_tdp must be a scalar or have one entry per member")
-        return ft
 
     def waterbody(self, out, out_mask, sum_reaches, f_tdp, reach_params, out_reaches=None, member_of_slot=None,
                   columns=None):
@@ -534,14 +565,7 @@ class Engine(object):
         the table); f_tdp scalar or [E]; reach_params [NP_R,S,E]; columns: names from ``abi.WB_COLUMNS`` (default all 11).
         Returns (wb [n_columns, D, E] device tensor, member axis ordered like ``out``'s, and an info dict)."""
         torch = self.torch
-        L = lib()
-        rp = self.to_device(reach_params, torch.float64)
-        npr, S, E = rp.shape
-        ncols, D, n_or, E2 = out.shape
-        oreach = _i32(out_reaches)
-        if (E2 != E or ncols != bin(out_mask).count('1') or n_or != (S if oreach is None else len(oreach))
-                or out.dtype != torch.float64 or not out.is_contiguous()):
-            raise ValueError("out %s does not match out_mask / out_reaches / reach_params %s" % (tuple(out.shape), tuple(rp.shape)))
+        head, rp, (D, n_or, E), keep = self._daily_table(out, out_mask, reach_params, out_reaches, member_of_slot, True)
         cols = list(abi.WB_COLUMNS) if columns is None else list(columns)
         wb_mask = sum(1 << abi.WB_COLUMNS.index(c) for c in cols)
         cols = [c for c in abi.WB_COLUMNS if c in cols]
@@ -549,15 +573,12 @@ class Engine(object):
         ft = self._f_tdp(f_tdp, E)
         wb = torch.empty((len(cols), D, E), dtype=torch.float64, device=self.tdev)
         info = abi.WbInfo()
-        dims = abi.Dims(E, S, D, 1)
         with torch.cuda.device(self.tdev):
             self._bind_stream()
-            rc = L.simplyp_waterbody(self._h, C.byref(dims), int(out_mask),
-                                     None if oreach is None else oreach.ctypes.data_as(C.POINTER(C.c_int32)), n_or,
-                                     out.data_ptr(), None if member_of_slot is None else member_of_slot.data_ptr(),
-                                     ft.data_ptr(), rp.data_ptr(), sr.ctypes.data_as(C.POINTER(C.c_int32)), len(sr),
-                                     wb_mask, wb.data_ptr(), C.byref(info))
+            rc = lib().simplyp_waterbody(*(head + (ft.data_ptr(), rp.data_ptr(), sr.ctypes.data_as(C.POINTER(C.c_int32)), len(sr),
+                                                   wb_mask, wb.data_ptr(), C.byref(info))))
         self._check(rc, 'simplyp_waterbody')
+        del keep
         d = info.as_dict()
         d['columns'] = cols
         return wb, d
@@ -601,27 +622,17 @@ class Engine(object):
         if not torch.is_tensor(table) or table.dtype != torch.float64 or not table.is_contiguous() or table.dim() < 1 \
                 or table.device != self.tdev:
             raise ValueError("table must be a contiguous float64 tensor on %s whose last axis is the member axis" % (self.tdev,))
-        qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
-        if qa.ndim != 1:
-            raise ValueError("q must be a list of probabilities")
+        qa = self._q_array(q)
         K, E = len(qa), int(table.shape[-1])
         lead = tuple(int(x) for x in table.shape[:-1])
         n_rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
-        inc = None
-        if include is not None:
-            inc = include if torch.is_tensor(include) else torch.from_numpy(np.ascontiguousarray(np.asarray(include) != 0))
-            inc = (inc != 0).to(torch.uint8).to(self.tdev).contiguous()
-            if tuple(inc.shape) != (E,):
-                raise ValueError("include must have one entry per member")
-        if member_of_slot is not None and (member_of_slot.dtype != torch.int32 or tuple(member_of_slot.shape) != (E,)):
-            raise ValueError("member_of_slot must be an int32 device tensor with one entry per member")
+        inc = self._include_mask(include, E)
+        self._check_member_of_slot(member_of_slot, E)
         stats = torch.empty((2, max(K, 1)) + lead, dtype=torch.float64, device=self.tdev)
         info = abi.QuantileInfo()
         with torch.cuda.device(self.tdev):
             self._bind_stream()
-            rc = lib().simplyp_quantiles(self._h, E, n_rows, table.data_ptr(),
-                                         None if member_of_slot is None else member_of_slot.data_ptr(),
-                                         None if inc is None else inc.data_ptr(),
+            rc = lib().simplyp_quantiles(self._h, E, n_rows, table.data_ptr(), self._ptr(member_of_slot), self._ptr(inc),
                                          qa.ctypes.data_as(C.POINTER(C.c_double)), K, stats.data_ptr(), C.byref(info))
         self._check(rc, 'simplyp_quantiles')
         return stats[0], stats[1], info.as_dict()
@@ -643,19 +654,8 @@ class Engine(object):
         x_(floor(h)) and x_(min(floor(h) + 1, n - 1)), h = q (n - 1), n = ``info['n_days'][p]`` (NaN where n = 0);
         ``interpolate_time_quantiles`` turns them into numpy's values."""
         torch = self.torch
-        if not torch.is_tensor(out) or out.dim() != 4 or out.dtype != torch.float64 or not out.is_contiguous() \
-                or out.device != self.tdev:
-            raise ValueError("out must be a contiguous float64 tensor [n_cols, D, n_reaches, E] on %s" % (self.tdev,))
-        ncols, D, n_or, E = (int(x) for x in out.shape)
-        oreach = _i32(out_reaches)
-        rp = None if reach_params is None else self.to_device(reach_params, torch.float64)
-        S = int(rp.shape[1]) if rp is not None else (n_or if oreach is None else max(n_or, int(oreach.max()) + 1))
-        if ncols != bin(out_mask).count('1') or n_or != (S if oreach is None else len(oreach)) \
-                or (rp is not None and int(rp.shape[2]) != E):
-            raise ValueError("out %s does not match out_mask / out_reaches / reach_params" % (tuple(out.shape),))
-        qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
-        if qa.ndim != 1:
-            raise ValueError("q must be a list of probabilities")
+        head, rp, (D, n_or, E), keep = self._daily_table(out, out_mask, reach_params, out_reaches, member_of_slot)
+        qa = self._q_array(q)
         K = len(qa)
         sa = np.ascontiguousarray([c for c in range(32) if (out_mask >> c) & 1] if series is None else series, dtype=np.int32)
         if sa.ndim != 1:
@@ -668,23 +668,18 @@ class Engine(object):
             P = max(int(pod.max()) + 1, 1) if D > 0 else 1
             P = P if n_periods is None else int(n_periods)
         ft = None if f_tdp is None else self._f_tdp(f_tdp, E)
-        if member_of_slot is not None and (member_of_slot.dtype != torch.int32 or tuple(member_of_slot.shape) != (E,)):
-            raise ValueError("member_of_slot must be an int32 device tensor with one entry per member")
         stats = torch.empty((2, max(K, 1), max(len(sa), 1), max(P, 1), n_or, E), dtype=torch.float64, device=self.tdev)
         n_days = np.zeros(max(P, 1), dtype=np.int32)
         info = abi.TqInfo()
-        dims = abi.Dims(E, S, D, 1)
         i32 = C.POINTER(C.c_int32)
         with torch.cuda.device(self.tdev):
             self._bind_stream()
-            rc = lib().simplyp_time_quantiles(self._h, C.byref(dims), int(out_mask),
-                                              None if oreach is None else oreach.ctypes.data_as(i32), n_or,
-                                              out.data_ptr(), None if member_of_slot is None else member_of_slot.data_ptr(),
-                                              None if ft is None else ft.data_ptr(), None if rp is None else rp.data_ptr(),
-                                              sa.ctypes.data_as(i32), len(sa), None if pod is None else pod.ctypes.data_as(i32), P,
-                                              qa.ctypes.data_as(C.POINTER(C.c_double)), K, stats.data_ptr(),
-                                              n_days.ctypes.data_as(i32), C.byref(info))
+            rc = lib().simplyp_time_quantiles(*(head + (self._ptr(ft), self._ptr(rp), sa.ctypes.data_as(i32), len(sa),
+                                                        None if pod is None else pod.ctypes.data_as(i32), P,
+                                                        qa.ctypes.data_as(C.POINTER(C.c_double)), K, stats.data_ptr(),
+                                                        n_days.ctypes.data_as(i32), C.byref(info))))
         self._check(rc, 'simplyp_time_quantiles')
+        del keep
         d = info.as_dict()
         d['n_days'] = n_days
         return stats[0], stats[1], d
@@ -692,16 +687,7 @@ class Engine(object):
     def _predictive_args(self, out, out_mask, series, err_m, f_tdp, reach_params, out_reaches, member_of_slot):
         """The arguments ``predictive_series`` and ``predictive_bands`` share, checked and on the device."""
         torch = self.torch
-        if not torch.is_tensor(out) or out.dim() != 4 or out.dtype != torch.float64 or not out.is_contiguous() \
-                or out.device != self.tdev:
-            raise ValueError("out must be a contiguous float64 tensor [n_cols, D, n_reaches, E] on %s" % (self.tdev,))
-        ncols, D, n_or, E = (int(x) for x in out.shape)
-        oreach = _i32(out_reaches)
-        rp = None if reach_params is None else self.to_device(reach_params, torch.float64)
-        S = int(rp.shape[1]) if rp is not None else (n_or if oreach is None else max(n_or, int(oreach.max()) + 1))
-        if ncols != bin(out_mask).count('1') or n_or != (S if oreach is None else len(oreach)) \
-                or (rp is not None and int(rp.shape[2]) != E):
-            raise ValueError("out %s does not match out_mask / out_reaches / reach_params" % (tuple(out.shape),))
+        head, rp, (D, n_or, E), keep = self._daily_table(out, out_mask, reach_params, out_reaches, member_of_slot)
         sa = np.ascontiguousarray(series, dtype=np.int32)
         if sa.ndim != 1:
             raise ValueError("series must be a list of series ids")
@@ -713,14 +699,8 @@ class Engine(object):
             if tuple(em.shape) != (len(sa), E):
                 raise ValueError("err_m must be a scalar or [n_series, E] (member order)")
         ft = None if f_tdp is None else self._f_tdp(f_tdp, E)
-        if member_of_slot is not None and (member_of_slot.dtype != torch.int32 or tuple(member_of_slot.shape) != (E,)):
-            raise ValueError("member_of_slot must be an int32 device tensor with one entry per member")
-        i32 = C.POINTER(C.c_int32)
-        head = (self._h, C.byref(abi.Dims(E, S, D, 1)), int(out_mask), None if oreach is None else oreach.ctypes.data_as(i32), n_or,
-                out.data_ptr(), None if member_of_slot is None else member_of_slot.data_ptr())
-        tail = (None if ft is None else ft.data_ptr(), None if rp is None else rp.data_ptr(), sa.ctypes.data_as(i32), len(sa),
-                None if em is None else em.data_ptr())
-        return head, tail, (len(sa), D, n_or, E), [oreach, rp, sa, em, ft]
+        tail = (self._ptr(ft), self._ptr(rp), sa.ctypes.data_as(C.POINTER(C.c_int32)), len(sa), self._ptr(em))
+        return head, tail, (len(sa), D, n_or, E), keep + [sa, em, ft]
 
     def predictive_series(self, out, out_mask, series, err_m=None, seed=0, day0=0, normals=False, f_tdp=None,
                           reach_params=None, out_reaches=None, member_of_slot=None):
@@ -751,20 +731,13 @@ class Engine(object):
         torch = self.torch
         head, tail, shape, keep = self._predictive_args(out, out_mask, series, err_m, f_tdp, reach_params, out_reaches, member_of_slot)
         E = shape[3]
-        qa = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
-        if qa.ndim != 1:
-            raise ValueError("q must be a list of probabilities")
-        inc = None
-        if include is not None:
-            inc = include if torch.is_tensor(include) else torch.from_numpy(np.ascontiguousarray(np.asarray(include) != 0))
-            inc = (inc != 0).to(torch.uint8).to(self.tdev).contiguous()
-            if tuple(inc.shape) != (E,):
-                raise ValueError("include must have one entry per member")
+        qa = self._q_array(q)
+        inc = self._include_mask(include, E)
         stats = torch.empty((2, max(len(qa), 1)) + shape[:3], dtype=torch.float64, device=self.tdev)
         info = abi.PredInfo()
         with torch.cuda.device(self.tdev):
             self._bind_stream()
-            rc = lib().simplyp_predictive_bands(*(head + (None if inc is None else inc.data_ptr(),) + tail
+            rc = lib().simplyp_predictive_bands(*(head + (self._ptr(inc),) + tail
                                                   + (C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(day0),
                                                      qa.ctypes.data_as(C.POINTER(C.c_double)), len(qa), stats.data_ptr(),
                                                      C.byref(info))))
@@ -774,12 +747,9 @@ class Engine(object):
 
 
     # ---- the stretch move (simplyp_mcmc_*; simplyp_amd.mcmc restates it) ----
-    @staticmethod
-    def _ptr(t):
-        return None if t is None else t.data_ptr()
-
-    def _mcmc_call(self, name, *args):
-        info = abi.McmcInfo()
+    def _info_call(self, info_class, name, *args):
+        """The library entry ``name`` with a fresh ``info_class`` as its last argument; returns the info as a dict."""
+        info = info_class()
         with self.torch.cuda.device(self.tdev):
             self._bind_stream()
             rc = getattr(lib(), name)(*(args + (C.byref(info),)))
@@ -799,7 +769,7 @@ class Engine(object):
         if lo.shape != (n_dim,) or hi.shape != (n_dim,) or tg.shape != (n_dim,):
             raise ValueError("lo, hi and target need one entry per dimension")
         dbl = C.POINTER(C.c_double)
-        return self._mcmc_call('simplyp_mcmc_propose', self._h, W, n_dim, int(half), float(a),
+        return self._info_call(abi.McmcInfo, 'simplyp_mcmc_propose', self._h, W, n_dim, int(half), float(a),
                                C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint32(int(t) & 0xFFFFFFFF),
                                lo.ctypes.data_as(dbl), hi.ctypes.data_as(dbl), tg.ctypes.data_as(C.POINTER(C.c_int32)),
                                theta.data_ptr(), self._ptr(prop), self._ptr(inside), self._ptr(member_params), self._ptr(f_tdp))
@@ -820,7 +790,7 @@ class Engine(object):
                 or not gof.is_contiguous():
             raise ValueError("gof %s does not match prop %s" % (tuple(gof.shape), tuple(prop.shape)))
         i32 = C.POINTER(C.c_int32)
-        return self._mcmc_call('simplyp_mcmc_log_prob', self._h, 2 * h, n_dim, int(gof.shape[2]), gof.data_ptr(),
+        return self._info_call(abi.McmcInfo, 'simplyp_mcmc_log_prob', self._h, 2 * h, n_dim, int(gof.shape[2]), gof.data_ptr(),
                                self._ptr(status), self._ptr(inside), pv.ctypes.data_as(i32), pr.ctypes.data_as(i32), len(pv),
                                md.ctypes.data_as(i32), mc.ctypes.data_as(C.POINTER(C.c_double)), prop.data_ptr(),
                                self._ptr(lp_prop))
@@ -830,20 +800,12 @@ class Engine(object):
         (``simplyp_mcmc_accept``); lp_prop [W/2]: ln p of the proposals, from ``mcmc_log_prob`` or the caller's own; chain_row
         [n_dim + 1, W] or None receives the half's positions and lp after the decision."""
         n_dim, W = (int(x) for x in theta.shape)
-        return self._mcmc_call('simplyp_mcmc_accept', self._h, W, n_dim, int(half), float(a),
+        return self._info_call(abi.McmcInfo, 'simplyp_mcmc_accept', self._h, W, n_dim, int(half), float(a),
                                C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint32(int(t) & 0xFFFFFFFF),
                                self._ptr(prop), self._ptr(inside), self._ptr(lp_prop), theta.data_ptr(), self._ptr(lp),
                                self._ptr(n_accept), self._ptr(chain_row))
 
     # ---- multi-start Nelder-Mead (simplyp_nm_*; simplyp_amd.neldermead restates it) ----
-    def _nm_call(self, name, *args):
-        info = abi.NmInfo()
-        with self.torch.cuda.device(self.tdev):
-            self._bind_stream()
-            rc = getattr(lib(), name)(*(args + (C.byref(info),)))
-        self._check(rc, name)
-        return info.as_dict()
-
     def nm_propose(self, sim, istate, lo, hi, target, prop, inside, member_params=None, f_tdp=None):
         """The points of every simplex's four slots (``simplyp_nm_propose``).  sim [n_dim + 1, n_dim, S] float64 and istate
         [abi.NM_N_ISTATE, S] int32 device tensors (read); lo / hi [n_dim] the box and target [n_dim] (as for ``mcmc_propose``) on
@@ -856,9 +818,9 @@ class Engine(object):
         if int(sim.shape[0]) != n_dim + 1 or lo.shape != (n_dim,) or hi.shape != (n_dim,) or tg.shape != (n_dim,):
             raise ValueError("sim must be [n_dim + 1, n_dim, S]; lo, hi and target need one entry per dimension")
         dbl = C.POINTER(C.c_double)
-        return self._nm_call('simplyp_nm_propose', self._h, S, n_dim, lo.ctypes.data_as(dbl), hi.ctypes.data_as(dbl),
-                             tg.ctypes.data_as(C.POINTER(C.c_int32)), sim.data_ptr(), self._ptr(istate), self._ptr(prop),
-                             self._ptr(inside), self._ptr(member_params), self._ptr(f_tdp))
+        return self._info_call(abi.NmInfo, 'simplyp_nm_propose', self._h, S, n_dim, lo.ctypes.data_as(dbl), hi.ctypes.data_as(dbl),
+                               tg.ctypes.data_as(C.POINTER(C.c_int32)), sim.data_ptr(), self._ptr(istate), self._ptr(prop),
+                               self._ptr(inside), self._ptr(member_params), self._ptr(f_tdp))
 
     def nm_update(self, sim, fsim, istate, prop, inside, lp_prop, max_iter, xatol=1e-4, fatol=1e-4, history=None):
         """One run's values applied in place to sim [n_dim + 1, n_dim, S], fsim [n_dim + 1, S] and istate (``simplyp_nm_update``);
@@ -867,9 +829,9 @@ class Engine(object):
         n_dim, S = int(sim.shape[1]), int(sim.shape[2])
         if int(sim.shape[0]) != n_dim + 1:
             raise ValueError("sim must be [n_dim + 1, n_dim, S]")
-        return self._nm_call('simplyp_nm_update', self._h, S, n_dim, int(max_iter), float(xatol), float(fatol), self._ptr(prop),
-                             self._ptr(inside), self._ptr(lp_prop), sim.data_ptr(), self._ptr(fsim), self._ptr(istate),
-                             self._ptr(history), 0 if history is None else int(history.shape[0]))
+        return self._info_call(abi.NmInfo, 'simplyp_nm_update', self._h, S, n_dim, int(max_iter), float(xatol), float(fatol), self._ptr(prop),
+                               self._ptr(inside), self._ptr(lp_prop), sim.data_ptr(), self._ptr(fsim), self._ptr(istate),
+                               self._ptr(history), 0 if history is None else int(history.shape[0]))
 
 
 def interpolate_quantiles(lower, upper, q, n_used):

@@ -129,10 +129,41 @@ def test_argument_errors(engine0):
     m = helpers.marshal_scenario('tarland_2004_static', E=2, out_mask=marshal.mask_of_columns(['Qr', 'Vr']))
     out, _, _ = engine0.run(m['forcing'], m['doy'], m['member_params'], m['reach_params'], m['up_ptr'], m['up_idx'], m['opts'])
     obs = np.full((1, 6, out.shape[1]), np.nan)
-    with pytest.raises(engine.EngineError, match='out_mask must contain'):
+    with pytest.raises(engine.EngineError, match=r'\): simplyp_gof: out_mask must contain'):
         engine0.gof(out, marshal.mask_of_columns(['Qr', 'Vr']), obs, 0.7, m['reach_params'])
     with pytest.raises(ValueError, match='obs must have shape'):
         engine0.gof(out, marshal.mask_of_columns(['Qr', 'Vr']), obs[:, :, :5], 0.7, m['reach_params'])
+
+
+@pytest.mark.parametrize('entry, shape', [('simplyp_gof', (len(abi.GOF_STATS), 6)), ('simplyp_gof_spearman', (6,))])
+def test_rejected_raw_calls_name_their_entry_and_write_nothing(engine0, entry, shape):
+    import ctypes as C
+    import torch
+    L = engine.lib()
+    E, D, S = 70, 40, 2
+    mask = marshal.mask_of_columns(FLUX)
+    t = torch.ones((4, D, S, E), dtype=torch.float64, device=engine0.tdev)
+    res = torch.full(shape + (S, E), -7.0, dtype=torch.float64, device=engine0.tdev)
+    ft = torch.ones(E, dtype=torch.float64, device=engine0.tdev)
+    rp = torch.ones((len(marshal.PR_NAMES), S, E), dtype=torch.float64, device=engine0.tdev)
+    obs = np.full((S, 6, D), np.nan)
+    obs[:, 0, 5:30] = np.linspace(0.5, 2.0, 25)
+    reaches = np.arange(S + 1, dtype=np.int32) % S
+    info = abi.GofInfo()
+
+    def call(E_=E, have_obs=True, out_reaches=None, n_or=S):
+        dims = abi.Dims(E_, S, D, 1)
+        with torch.cuda.device(engine0.tdev):
+            return getattr(L, entry)(engine0._h, C.byref(dims), mask,
+                                     None if out_reaches is None else out_reaches.ctypes.data_as(C.POINTER(C.c_int32)), n_or,
+                                     t.data_ptr(), None, ft.data_ptr(), rp.data_ptr(),
+                                     obs.ctypes.data_as(C.POINTER(C.c_double)) if have_obs else None, res.data_ptr(), C.byref(info))
+    for kw in (dict(E_=0), dict(have_obs=False), dict(out_reaches=reaches, n_or=S + 1)):
+        assert call(**kw) == -1, kw                                        # SIMPLYP_ERR_ARG
+        assert L.simplyp_last_error(engine0._h).startswith(entry.encode() + b': '), kw
+    torch.cuda.synchronize()
+    assert bool((res == -7.0).all())                                       # nothing was written
+    assert call() == 0 and not bool((res == -7.0).all())
 
 
 def test_run_simply_p_ensemble_with_observations(engine0):

@@ -86,11 +86,11 @@ def test_argument_errors(engine0):
     m = ensemble(64)
     out, _, _ = engine0.run(m['forcing'], m['doy'], m['member_params'], m['reach_params'], m['up_ptr'], m['up_idx'], m['opts'],
                             out_reaches=[0, 1])
-    with pytest.raises(engine.EngineError, match='not among'):
+    with pytest.raises(engine.EngineError, match=r'\): simplyp_waterbody: .*not among'):
         engine0.waterbody(out, m['opts'].out_mask, [0, 2], 0.7, m['reach_params'], out_reaches=[0, 1])
-    with pytest.raises(engine.EngineError, match='ascending'):
+    with pytest.raises(engine.EngineError, match=r'\): simplyp_waterbody: .*ascending'):
         engine0.waterbody(out, m['opts'].out_mask, [1, 0], 0.7, m['reach_params'], out_reaches=[0, 1])
-    with pytest.raises(engine.EngineError, match='must contain'):
+    with pytest.raises(engine.EngineError, match=r'\): simplyp_waterbody: .*must contain'):
         engine0.waterbody(out[:4].contiguous(), marshal.mask_of_columns(['Vr', 'Qr', 'Msus_kg/day', 'TDP_kg/day']), [0, 1], 0.7,
                           m['reach_params'], out_reaches=[0, 1])
 
