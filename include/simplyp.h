@@ -36,7 +36,9 @@ extern "C" {
  * 17 still with simplyp_mcmc_propose, simplyp_mcmc_log_prob, simplyp_mcmc_accept and simplyp_mcmc_info: three more entry points, one
  * more info struct, purely additive again.
  * 17 still with simplyp_nm_propose, simplyp_nm_update, simplyp_nm_info and the SIMPLYP_NM_* constants: two more entry points, one
- * more info struct, nothing existing changes. */
+ * more info struct, nothing existing changes.
+ * 17 still with simplyp_sobol_design, simplyp_sobol_indices and simplyp_sobol_info: two more entry points, one more info struct,
+ * additive once more. */
 #define SIMPLYP_ABI_VERSION 17
 
 typedef enum {
@@ -872,6 +874,69 @@ int simplyp_nm_update(simplyp_ctx* ctx, int32_t S, int32_t n_dim, int32_t max_it
                       const double* prop, const int32_t* inside, const double* lp_prop,
                       double* sim, double* fsim, int32_t* istate, double* history, int32_t history_rows,
                       simplyp_nm_info* info);
+
+/*
+ * Sobol' sensitivity indices of an ensemble, bootstrapped on the device: which parameters matter for which output.  Saltelli's
+ * design, the first- and total-order estimators of Saltelli et al. 2010 with the Sobol'-Levitan centring (what
+ * scipy.stats.sobol_indices computes), and the bootstrap of both as resampling counts times per-sample terms.
+ *
+ * N base samples (2 <= N <= 32768), n_dim dimensions (1 <= n_dim <= 16) with a box lo < hi, E = N (n_dim + 2) members in
+ * blocks of N: member j N + n is A_n for j = 0, B_n for j = 1, and A_n with dimension i taken from B_n for j = 2 + i.  The unit
+ * points u[m][k][n], m = 0: A, 1: B, are the caller's or uniform(x0, x1) of Philox4x32-10 under key (seed & 0xffffffff,
+ * seed >> 32) at counter (n, k, m, 0x53454E53); x = lo + (hi - lo) u.
+ *
+ * For a row f[E] of any table whose fastest axis is the member axis, sample n is valid iff none of its n_dim + 2 members carries
+ * SIMPLYP_STATUS_NONFINITE.  With a, b, ab_i the row at A, B, AB_i minus mu = sum_valid (a + b) / (2 n_valid):
+ *     p = a + b,  s = a a + b b,  g_i = b (ab_i - a),  t_i = (a - ab_i) (a - ab_i)
+ * and for a weight vector c[N] (an invalid sample's terms and count are selected to 0, never multiplied by it)
+ *     n_c = sum c v,  P = sum c p,  S = sum c s,  G_i = sum c g_i,  T_i = sum c t_i
+ *     m1 = P / (2 n_c),  m2 = S / (2 n_c),  var = m2 - m1 m1,  S1_i = (G_i / n_c) / var,  ST_i = (0.5 (T_i / n_c)) / var
+ * each + * / in fp64 in this order without contraction.  var = 0 (a constant row) gives what IEEE gives, NaN (scipy maps it to 0).
+ * Resample 0 is c = 1, the point estimate; resample b >= 1 has c[n] = the number of j < N with idx(b, j) == n,
+ * idx(b, j) = (x_{j & 3} N) >> 32 of Philox counter (b, j >> 2, 0, 0x424F4F54).  The sums are an fp64 matrix product of the
+ * counts with the terms (v_mfma_f64_16x16x4_f64) added in one fixed order: the same call twice gives the same bits; the ratios
+ * are bit for bit the formulas above applied to the sums.  simplyp_amd/sobol.py states all of it in NumPy.
+ *
+ * Both entries are synchronous on the context's stream and return SIMPLYP_ERR_ARG with nothing launched for N outside 2..32768,
+ * n_dim outside 1..16, n_rows < 0, n_boot < 0 or > 2^20, lo[d] >= hi[d] or a NaN bound, a target outside [-2, SIMPLYP_NP_M), a
+ * row named twice, a NULL required pointer.
+ */
+typedef struct {
+    double  kernel_ms;           /* all of the entry's kernels, HIP events on the context's stream                      */
+    double  counts_ms;           /* indices: validity, row means and the resampling counts                              */
+    double  contract_ms;         /* indices: the contraction                                                            */
+    int64_t flops;               /* indices: 2 (1 + n_boot) n_rows N (2 n_dim + 2), the contraction's useful fp64 operations */
+    int64_t bytes_workspace;     /* indices: the context's workspace the call used                                      */
+    int32_t n_valid;             /* indices: valid samples                                                              */
+    int32_t n_resamples;         /* indices: 1 + n_boot                                                                 */
+} simplyp_sobol_info;
+
+/*
+ * simplyp_sobol_design -- the design of N (n_dim + 2) members, one lane per member.
+ *   lo, hi          HOST    [n_dim] the box
+ *   target          HOST    [n_dim] as for simplyp_mcmc_propose: a row of member_params, -1 = f_tdp, -2 = nowhere
+ *   unit            device  [2][n_dim][N] unit points in [0, 1) (a scrambled Sobol' sequence, say), or NULL: the Philox stream
+ *   x               device  [n_dim][E] the design
+ *   member_params   device  [SIMPLYP_NP_M][E], or NULL when no target is >= 0; rows that no dimension names are not touched
+ *   f_tdp           device  [E], or NULL when no target is -1
+ */
+int simplyp_sobol_design(simplyp_ctx* ctx, int32_t N, int32_t n_dim, uint64_t seed,
+                         const double* lo /* host */, const double* hi /* host */, const int32_t* target /* host */,
+                         const double* unit, double* x, double* member_params, double* f_tdp, simplyp_sobol_info* info);
+
+/*
+ * simplyp_sobol_indices -- the indices of every row of a table, with n_boot bootstrap resamples.
+ *   table           device  [n_rows][E], only read: period sums, a goodness-of-fit table, any table whose fastest axis is the
+ *                           member axis.  n_rows = 0 succeeds and launches nothing.
+ *   status          device  [E] int32 as simplyp_run writes it, or NULL: every sample is valid
+ *   sums            device  [1 + n_boot][n_rows][2 n_dim + 2] in the order P, S, G_0.., T_0.., or NULL
+ *   n_used          device  [1 + n_boot] int32 n_c, or NULL
+ *   indices         device  [2][n_dim][n_rows][1 + n_boot]: plane 0 S1, plane 1 ST, the resample axis fastest -- the slice
+ *                           [..., 1:] (made contiguous) is a table simplyp_quantiles takes for the percentile interval
+ * The counts live in the context's grow-only workspace.
+ */
+int simplyp_sobol_indices(simplyp_ctx* ctx, int32_t N, int32_t n_dim, int32_t n_rows, const double* table, const int32_t* status,
+                          int32_t n_boot, uint64_t seed, double* sums, int32_t* n_used, double* indices, simplyp_sobol_info* info);
 
 /*
  * simplyp_eval_units -- the path's scalar device functions on caller-given arguments, one thread per row: how the tests pin the

@@ -111,6 +111,15 @@ class NmInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
 
 
+class SobolInfo(C.Structure):
+    """simplyp_sobol_info of include/simplyp.h."""
+    _fields_ = [('kernel_ms', C.c_double), ('counts_ms', C.c_double), ('contract_ms', C.c_double), ('flops', C.c_int64),
+                ('bytes_workspace', C.c_int64), ('n_valid', C.c_int32), ('n_resamples', C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # SIMPLYP_NM_*: the rows of istate [NM_N_ISTATE, S] (simplyp_amd.neldermead names the phases and the status values)
 NM_ISTATE = ['phase', 'cursor', 'n_iter', 'status', 'n_reflect', 'n_expand', 'n_contract_out', 'n_contract_in', 'n_shrink']
 NM_N_ISTATE = len(NM_ISTATE)

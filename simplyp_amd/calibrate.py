@@ -10,21 +10,10 @@ import time
 
 import numpy as np
 
-from . import abi, marshal, mcmc, neldermead, predictive
+from . import abi, marshal, mcmc, neldermead, predictive, priors as _priors
+from .priors import box as _box
 
 START_SERIES = 0x53544152        # "STAR": the counter's fourth word of the start ball's normals
-
-
-def _box(priors, names):
-    """The prior box of ``names`` as (lo, hi); raises ValueError."""
-    try:
-        box = np.array([[float(priors[nm][0]), float(priors[nm][1])] for nm in names], dtype=np.float64)
-    except (TypeError, ValueError, IndexError):
-        raise ValueError("priors must map each name to a pair (lo, hi)")
-    if not (box[:, 0] < box[:, 1]).all():
-        bad = names[int(np.argmin(box[:, 0] < box[:, 1]))]
-        raise ValueError("prior of %r needs lo < hi (got %s)" % (bad, tuple(priors[bad])))
-    return box[:, 0].copy(), box[:, 1].copy()
 
 
 def _plan(priors, variables, error_m, check_shape):
@@ -43,10 +32,8 @@ def _plan(priors, variables, error_m, check_shape):
         raise ValueError("error_m names variables that are not selected: %s" % unknown)
     target, m_dim, m_const = [], [-1] * len(abi.GOF_VARS), [float('nan')] * len(abi.GOF_VARS)
     for d, nm in enumerate(names):
-        if nm in marshal.PM_NAMES:
-            target.append(marshal.PM_NAMES.index(nm))
-        elif nm == 'f_TDP':
-            target.append(abi.MCMC_TARGET_F_TDP)
+        if _priors.target_of(nm) is not None:
+            target.append(_priors.target_of(nm))
         elif nm.startswith('m_') and nm[2:] in variables:
             if nm[2:] in error_m:
                 raise ValueError("%s is sampled and fixed through error_m at once" % nm)
@@ -89,17 +76,8 @@ def _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables
         pairs += at
     if len(pairs) > 32:
         raise ValueError("at most 32 (variable, output reach) pairs enter the likelihood (got %d): name fewer out_reaches" % len(pairs))
-    # the reference's input checks at the box's two extreme corners (the checks are per parameter)
-    pm = [(d, nm) for d, nm in enumerate(names) if nm in marshal.PM_NAMES]
-    if pm:
-        corners = marshal.member_params(p, p_LU, 2, {nm: np.array([lo[d], hi[d]]) for d, nm in pm})
-        try:
-            marshal.validate_ensemble(corners, marshal.reach_params(p_SC, p, 2), scs)
-        except AssertionError as exc:
-            raise ValueError("the prior box holds points the model rejects: %s" % exc)
-    snow = 'f_DDSM' in names or 'D_snow_0' in names
-    if snow and not {'Precipitation', 'T_air'} <= set(met_df.columns):
-        raise ValueError("sampling f_DDSM / D_snow_0 runs the snow module in the kernel: met_df needs 'Precipitation' and 'T_air'")
+    _priors.check_corners(names, lo, hi, p, p_LU, p_SC, scs)
+    snow = _priors.snow_rule(names, met_df)
     base = marshal.member_params(p, p_LU, 1)[:, 0]
     centre = np.array([base[marshal.PM_NAMES.index(nm)] if nm in marshal.PM_NAMES else
                        (float(p['f_TDP']) if nm == 'f_TDP' else 0.5 * (lo[d] + hi[d])) for d, nm in enumerate(names)])

@@ -25,6 +25,7 @@
 #include "simplyp_predictive.hip.h"
 #include "simplyp_mcmc.hip.h"
 #include "simplyp_neldermead.hip.h"
+#include "simplyp_sobol.hip.h"
 #include "simplyp_pack_stream.h"
 #include "simplyp_table.h"
 
@@ -57,6 +58,7 @@ struct simplyp_ctx {
     DeviceBuf mcmc;           // simplyp_mcmc_*: 4 x uint32 (inside, accepted, NaN)
     DeviceBuf nm;             // simplyp_nm_*: 8 x uint32 counters
     DeviceBuf nm_work;        // simplyp_nm_update: the sort's other copy of the simplexes
+    DeviceBuf sobol;          // simplyp_sobol_indices: n_valid | valid [Npad] | mu [n_rows] | n_used [B] | counts [B][Npad] uint16 | sums
     DeviceBuf queue;          // ticket, error, done[n_groups] (uint32) | ckpt[CKPT_N][E] (double)
     // streamed output (simplyp_stream_out): the armed destination, the chunk flags the queue kernel raises in pinned host
     // memory, and the host thread that turns a raised flag into the D2H copies of that chunk's rows on `copy_stream`
@@ -990,6 +992,7 @@ void simplyp_ctx_destroy(simplyp_ctx* ctx)
     if (ctx->mcmc.ptr) (void)hipFree(ctx->mcmc.ptr);
     if (ctx->nm.ptr) (void)hipFree(ctx->nm.ptr);
     if (ctx->nm_work.ptr) (void)hipFree(ctx->nm_work.ptr);
+    if (ctx->sobol.ptr) (void)hipFree(ctx->sobol.ptr);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
     if (ctx->ev_main) (void)hipEventDestroy(ctx->ev_main);
@@ -2357,6 +2360,119 @@ int simplyp_nm_update(simplyp_ctx* ctx, int32_t S, int32_t n_dim, int32_t max_it
 {
     SIMPLYP_GUARD(ctx, nm_update_impl(ctx, S, n_dim, max_iter, xatol, fatol, prop, inside, lp_prop, sim, fsim, istate, history,
                                       history_rows, info))
+}
+
+// ---- Sobol' indices (simplyp_sobol.hip.h) -----------------------------------------------------------------------------------
+// What the two entries check alike.
+static int sobol_shape(simplyp_ctx* ctx, const char* me, int32_t N, int32_t n_dim)
+{
+    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a run is pending on this context; call simplyp_sync first", me);
+    if (N < simplyp::SOBOL_MIN_N || N > simplyp::SOBOL_MAX_N)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: N must be in [%d, %d] (got %d)", me, simplyp::SOBOL_MIN_N, simplyp::SOBOL_MAX_N, (int)N);
+    if (n_dim < 1 || n_dim > simplyp::SOBOL_MAX_DIM)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_dim must be in [1, %d] (got %d)", me, simplyp::SOBOL_MAX_DIM, (int)n_dim);
+    return SIMPLYP_OK;
+}
+
+static int sobol_design_impl(simplyp_ctx* ctx, int32_t N, int32_t n_dim, uint64_t seed, const double* lo, const double* hi,
+                             const int32_t* target, const double* unit, double* x, double* member_params, double* f_tdp,
+                             simplyp_sobol_info* info)
+{
+    const char* me = "simplyp_sobol_design";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    if (int rc = sobol_shape(ctx, me, N, n_dim)) return rc;
+    if (!lo || !hi || !target || !x) return fail(ctx, SIMPLYP_ERR_ARG, "%s: lo, hi, target and x must not be NULL", me);
+    simplyp::SobolDesignArgs g{};
+    TABLE_TRY(ctx, st::check_box(me, n_dim, lo, hi, target, member_params, f_tdp, g.lo, g.hi, g.target, msg));
+    g.N = N; g.n_dim = n_dim; g.key0 = (uint32_t)(seed & 0xFFFFFFFFull); g.key1 = (uint32_t)(seed >> 32);
+    g.unit = unit; g.x = x; g.member_params = member_params; g.f_tdp = f_tdp;
+    if (info) *info = simplyp_sobol_info{};
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = timed_begin(ctx)) return rc;
+    const int E = N * (n_dim + 2);
+    hipLaunchKernelGGL(simplyp::simplyp_sobol_design_kernel, dim3((unsigned)((E + simplyp::SOBOL_THREADS - 1) / simplyp::SOBOL_THREADS)),
+                       dim3(simplyp::SOBOL_THREADS), 0, ctx->stream, g);
+    HIP_TRY(ctx, hipGetLastError());
+    return timed_end(ctx, info ? &info->kernel_ms : nullptr);
+}
+
+static int sobol_indices_impl(simplyp_ctx* ctx, int32_t N, int32_t n_dim, int32_t n_rows, const double* table, const int32_t* status,
+                              int32_t n_boot, uint64_t seed, double* sums, int32_t* n_used, double* indices, simplyp_sobol_info* info)
+{
+    const char* me = "simplyp_sobol_indices";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    if (int rc = sobol_shape(ctx, me, N, n_dim)) return rc;
+    if (n_rows < 0) return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_rows must be >= 0 (got %d)", me, (int)n_rows);
+    if (n_boot < 0 || n_boot > simplyp::SOBOL_MAX_BOOT)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_boot must be in [0, %d] (got %d)", me, simplyp::SOBOL_MAX_BOOT, (int)n_boot);
+    if (info) { *info = simplyp_sobol_info{}; info->n_resamples = 1 + n_boot; }
+    if (n_rows == 0) return SIMPLYP_OK;
+    if (!table || !indices) return fail(ctx, SIMPLYP_ERR_ARG, "%s: table and indices must not be NULL", me);
+    const int B = 1 + n_boot, T = 2 * n_dim + 2, tiles = (T + 15) / 16;
+    if ((long long)n_rows * B > (1LL << 31) - 1 - simplyp::SOBOL_THREADS)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_rows (1 + n_boot) must stay below 2^31 (got %d rows, %d resamples)", me, (int)n_rows, B);
+    const int Npad = (N + simplyp::SOBOL_KC - 1) / simplyp::SOBOL_KC * simplyp::SOBOL_KC;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t o_valid = 256, o_mu = o_valid + up((size_t)Npad), o_used = o_mu + up((size_t)n_rows * sizeof(double));
+    const size_t o_counts = o_used + up((size_t)B * sizeof(int32_t));
+    const size_t o_sums = o_counts + up((size_t)B * Npad * sizeof(uint16_t));
+    const size_t total = o_sums + (sums ? 0 : up((size_t)B * n_rows * T * sizeof(double)));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = ensure(ctx, ctx->sobol, total)) return rc;
+    char* base = (char*)ctx->sobol.ptr;
+    simplyp::SobolArgs g{};
+    g.N = N; g.Npad = Npad; g.n_dim = n_dim; g.n_rows = n_rows; g.B = B;
+    g.key0 = (uint32_t)(seed & 0xFFFFFFFFull); g.key1 = (uint32_t)(seed >> 32);
+    g.table = table; g.status = status;
+    g.n_valid = (int32_t*)base; g.valid = (uint8_t*)(base + o_valid); g.mu = (double*)(base + o_mu);
+    g.n_used = n_used ? n_used : (int32_t*)(base + o_used);
+    g.counts = (uint16_t*)(base + o_counts);
+    g.sums = sums ? sums : (double*)(base + o_sums);
+    g.indices = indices;
+    hipEvent_t ev_contract = nullptr;
+    HIP_TRY(ctx, hipEventCreate(&ev_contract));
+    struct EventGuard { hipEvent_t e; ~EventGuard() { (void)hipEventDestroy(e); } } guard{ev_contract};
+    const dim3 threads(simplyp::SOBOL_THREADS);
+    if (int rc = timed_begin(ctx)) return rc;
+    hipLaunchKernelGGL(simplyp::simplyp_sobol_mean_kernel, dim3((unsigned)n_rows), threads, 0, ctx->stream, g);
+    const size_t lds = std::max<size_t>((size_t)Npad * sizeof(uint16_t), simplyp::SOBOL_THREADS * sizeof(uint32_t));
+    hipLaunchKernelGGL(simplyp::simplyp_sobol_counts_kernel, dim3((unsigned)B), threads, lds, ctx->stream, g);
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_main, ctx->stream));
+    const dim3 grid((unsigned)n_rows, (unsigned)((B + simplyp::SOBOL_RB - 1) / simplyp::SOBOL_RB));
+    if (tiles == 1) hipLaunchKernelGGL(simplyp::simplyp_sobol_contract_kernel<1>, grid, threads, 0, ctx->stream, g);
+    else if (tiles == 2) hipLaunchKernelGGL(simplyp::simplyp_sobol_contract_kernel<2>, grid, threads, 0, ctx->stream, g);
+    else hipLaunchKernelGGL(simplyp::simplyp_sobol_contract_kernel<3>, grid, threads, 0, ctx->stream, g);
+    HIP_TRY(ctx, hipEventRecord(ev_contract, ctx->stream));
+    const long long cells = (long long)n_rows * B;
+    hipLaunchKernelGGL(simplyp::simplyp_sobol_epilogue_kernel, dim3((unsigned)((cells + simplyp::SOBOL_THREADS - 1) / simplyp::SOBOL_THREADS)),
+                       threads, 0, ctx->stream, g);
+    HIP_TRY(ctx, hipGetLastError());
+    int32_t n_valid = 0;
+    if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr, &n_valid, g.n_valid, sizeof(n_valid))) return rc;
+    if (info) {
+        float f = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&f, ctx->ev_start, ctx->ev_main));
+        info->counts_ms = f;
+        HIP_TRY(ctx, hipEventElapsedTime(&f, ctx->ev_main, ev_contract));
+        info->contract_ms = f;
+        info->flops = 2LL * B * n_rows * N * T;
+        info->bytes_workspace = (int64_t)total;
+        info->n_valid = n_valid;
+    }
+    return SIMPLYP_OK;
+}
+
+int simplyp_sobol_design(simplyp_ctx* ctx, int32_t N, int32_t n_dim, uint64_t seed, const double* lo, const double* hi,
+                         const int32_t* target, const double* unit, double* x, double* member_params, double* f_tdp,
+                         simplyp_sobol_info* info)
+{
+    SIMPLYP_GUARD(ctx, sobol_design_impl(ctx, N, n_dim, seed, lo, hi, target, unit, x, member_params, f_tdp, info))
+}
+
+int simplyp_sobol_indices(simplyp_ctx* ctx, int32_t N, int32_t n_dim, int32_t n_rows, const double* table, const int32_t* status,
+                          int32_t n_boot, uint64_t seed, double* sums, int32_t* n_used, double* indices, simplyp_sobol_info* info)
+{
+    SIMPLYP_GUARD(ctx, sobol_indices_impl(ctx, N, n_dim, n_rows, table, status, n_boot, seed, sums, n_used, indices, info))
 }
 
 void* simplyp_host_alloc(int64_t bytes)

@@ -31,7 +31,8 @@ ABI_SYMBOLS = ['simplyp_abi_version', 'simplyp_device_count', 'simplyp_ctx_creat
                'simplyp_quantiles', 'simplyp_state_bytes', 'simplyp_set_state', 'simplyp_fetch_packed',
                'simplyp_pack_roundtrip_host', 'simplyp_fetch_packed_pred', 'simplyp_pack_roundtrip_host_pred',
                'simplyp_time_quantiles', 'simplyp_predictive_series', 'simplyp_predictive_bands',
-               'simplyp_mcmc_propose', 'simplyp_mcmc_log_prob', 'simplyp_mcmc_accept', 'simplyp_nm_propose', 'simplyp_nm_update']
+               'simplyp_mcmc_propose', 'simplyp_mcmc_log_prob', 'simplyp_mcmc_accept', 'simplyp_nm_propose', 'simplyp_nm_update',
+               'simplyp_sobol_design', 'simplyp_sobol_indices']
 
 _lib = None
 
@@ -132,6 +133,12 @@ def lib():
     L.simplyp_nm_update.restype = C.c_int
     L.simplyp_nm_update.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, dp, i32p, dp, dp, dp, i32p, dp,
                                     C.c_int32, C.POINTER(abi.NmInfo)]
+    L.simplyp_sobol_design.restype = C.c_int
+    L.simplyp_sobol_design.argtypes = [vp, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_int32), dp, dp, dp, dp, C.POINTER(abi.SobolInfo)]
+    L.simplyp_sobol_indices.restype = C.c_int
+    L.simplyp_sobol_indices.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, i32p, C.c_int32, C.c_uint64, dp, i32p, dp,
+                                        C.POINTER(abi.SobolInfo)]
     L.simplyp_stream_out.restype = C.c_int
     L.simplyp_stream_out.argtypes = [vp, vp, C.c_int64]
     L.simplyp_fetch_packed.restype = C.c_int
@@ -832,6 +839,65 @@ class Engine(object):
         return self._info_call(abi.NmInfo, 'simplyp_nm_update', self._h, S, n_dim, int(max_iter), float(xatol), float(fatol), self._ptr(prop),
                                self._ptr(inside), self._ptr(lp_prop), sim.data_ptr(), self._ptr(fsim), self._ptr(istate),
                                self._ptr(history), 0 if history is None else int(history.shape[0]))
+
+
+    # ---- Sobol' sensitivity indices (simplyp_sobol_*; simplyp_amd.sobol restates them) ----
+    def sobol_design(self, N, lo, hi, target, member_params=None, f_tdp=None, seed=0, unit=None, x=None):
+        """Saltelli's design of ``E = N (n_dim + 2)`` members on the device (``simplyp_sobol_design``): lo / hi [n_dim] the box and
+        target [n_dim] (as for ``mcmc_propose``) on the host; member_params [NP_M, E] and f_tdp [E] float64 device tensors that
+        receive the rows the targets name (the others are not touched); unit: [2, n_dim, N] unit points in [0, 1) (numpy or device
+        tensor) or None for the Philox stream of ``seed``.  The library checks the values; the tensors' shapes are the caller's.
+        Returns (x [n_dim, E] device tensor, info)."""
+        torch = self.torch
+        lo = np.ascontiguousarray(lo, dtype=np.float64)
+        hi = np.ascontiguousarray(hi, dtype=np.float64)
+        tg = np.ascontiguousarray(target, dtype=np.int32)
+        n_dim, N = int(lo.shape[0]) if lo.ndim == 1 else -1, int(N)
+        if lo.ndim != 1 or hi.shape != lo.shape or tg.shape != lo.shape:
+            raise ValueError("lo, hi and target need one entry per dimension")
+        E = max(N, 0) * (n_dim + 2)
+        un = None
+        if unit is not None:
+            un = self.to_device(unit, torch.float64)
+            if tuple(un.shape) != (2, n_dim, N):
+                raise ValueError("unit must have shape [2, n_dim, N] = %s, got %s" % ((2, n_dim, N), tuple(un.shape)))
+        if x is None:
+            x = torch.empty((n_dim, E), dtype=torch.float64, device=self.tdev)
+        dbl = C.POINTER(C.c_double)
+        info = self._info_call(abi.SobolInfo, 'simplyp_sobol_design', self._h, N, n_dim, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                               lo.ctypes.data_as(dbl), hi.ctypes.data_as(dbl), tg.ctypes.data_as(C.POINTER(C.c_int32)),
+                               self._ptr(un), x.data_ptr(), self._ptr(member_params), self._ptr(f_tdp))
+        return x, info
+
+    def sobol_indices(self, table, N, n_dim, status=None, n_boot=0, seed=0):
+        """First- and total-order Sobol' indices of every row of ``table`` with ``n_boot`` bootstrap resamples
+        (``simplyp_sobol_indices``); the table is only read.
+
+        table: contiguous float64 device tensor whose LAST axis is the member axis of a design of ``N`` base samples in ``n_dim``
+        dimensions, ``E = N (n_dim + 2)`` (a run's period sums, a goodness-of-fit table); status: the run's int32 device tensor
+        [E] or None -- a sample with a member flagged ``abi.STATUS_NONFINITE`` takes part in nothing.
+        Returns (indices, sums, n_used, info): device tensors ``(2, n_dim) + table.shape[:-1] + (1 + n_boot,)`` -- plane 0 S1, plane
+        1 ST, resample 0 the point estimate --, ``(1 + n_boot,) + table.shape[:-1] + (2 n_dim + 2,)`` in the order P, S, G_0.., T_0..,
+        and int32 ``[1 + n_boot]``.  ``quantiles`` on ``indices[..., 1:].contiguous()`` selects the percentile interval."""
+        torch = self.torch
+        if not torch.is_tensor(table) or table.dtype != torch.float64 or not table.is_contiguous() or table.dim() < 1 \
+                or table.device != self.tdev:
+            raise ValueError("table must be a contiguous float64 tensor on %s whose last axis is the member axis" % (self.tdev,))
+        N, n_dim, n_boot = int(N), int(n_dim), int(n_boot)
+        lead = tuple(int(v) for v in table.shape[:-1])
+        n_rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        if int(table.shape[-1]) != N * (n_dim + 2):
+            raise ValueError("the table's member axis has %d entries, not N (n_dim + 2) = %d" % (int(table.shape[-1]), N * (n_dim + 2)))
+        if status is not None and (not torch.is_tensor(status) or status.dtype != torch.int32 or tuple(status.shape) != (int(table.shape[-1]),)
+                                   or not status.is_contiguous()):
+            raise ValueError("status must be a contiguous int32 device tensor with one entry per member")
+        B = 1 + max(n_boot, 0)
+        ind = torch.empty((2, max(n_dim, 0)) + lead + (B,), dtype=torch.float64, device=self.tdev)
+        sums = torch.empty((B,) + lead + (2 * max(n_dim, 0) + 2,), dtype=torch.float64, device=self.tdev)
+        n_used = torch.zeros((B,), dtype=torch.int32, device=self.tdev)
+        info = self._info_call(abi.SobolInfo, 'simplyp_sobol_indices', self._h, N, n_dim, n_rows, table.data_ptr(), self._ptr(status),
+                               n_boot, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), sums.data_ptr(), n_used.data_ptr(), ind.data_ptr())
+        return ind, sums, n_used, info
 
 
 def interpolate_quantiles(lower, upper, q, n_used):
