@@ -38,7 +38,9 @@ extern "C" {
  * 17 still with simplyp_nm_propose, simplyp_nm_update, simplyp_nm_info and the SIMPLYP_NM_* constants: two more entry points, one
  * more info struct, nothing existing changes.
  * 17 still with simplyp_sobol_design, simplyp_sobol_indices and simplyp_sobol_info: two more entry points, one more info struct,
- * additive once more. */
+ * additive once more.
+ * 17 still with simplyp_pf_loglik, simplyp_pf_weights, simplyp_pf_resample, simplyp_gather_members, simplyp_pf_jitter and
+ * simplyp_pf_info: five more entry points, one more info struct, nothing existing changes. */
 #define SIMPLYP_ABI_VERSION 17
 
 typedef enum {
@@ -937,6 +939,123 @@ int simplyp_sobol_design(simplyp_ctx* ctx, int32_t N, int32_t n_dim, uint64_t se
  */
 int simplyp_sobol_indices(simplyp_ctx* ctx, int32_t N, int32_t n_dim, int32_t n_rows, const double* table, const int32_t* status,
                           int32_t n_boot, uint64_t seed, double* sums, int32_t* n_used, double* indices, simplyp_sobol_info* info);
+
+/* ---- assimilating observations as they arrive: sequential importance resampling (a particle filter) over the joint (state,
+ * parameter) space, on the device.  E particles, 1 <= E <= 2^22, each a member of the ensemble with its model state
+ * (simplyp_set_state), its rows of member_params / reach_params / f_tdp, its position theta[n_dim] and its error-model m.  One
+ * assimilation window is
+ *     simplyp_run from the particles' states (state in, state out) -> pf_loglik -> pf_weights
+ *     -> when the effective sample size sum_w^2 / sum_w2 is too small: pf_resample -> gather_members for every array a particle
+ *        owns -> pf_jitter, the rejuvenation move (the model is deterministic: duplicates would stay identical for ever)
+ * with nothing but the info structs crossing to the host.  simplyp_amd/particle.py states every rule below in NumPy and Python
+ * integers.
+ *
+ * Likelihood.  For a pair (variable v, output reach r) take the days of the window with an observation, ascending; with sim the
+ * df_R series as simplyp_time_quantiles computes it,
+ *     n = their count,  SL = sum ln sim,  SR = sum (obs / sim - 1)^2
+ *     term = -0.5 n ln(2 pi) - n ln(m) - SL - SR / (2 m m)                     in this order of operations
+ * -- the reference's Gaussian likelihood with sigma = m sim as simplyp_mcmc_log_prob states it, without the more-than-10-
+ * observations rule of simplyp_gof, so a window with two chemistry samples has a likelihood.  The increment is the sum of the
+ * terms over the pairs in the given order, started from +0.0; a pair without an observation in the window adds nothing, so a
+ * window without observations gives exactly +0.0.  The increment is -inf where the status carries SIMPLYP_STATUS_NONFINITE, where
+ * an m <= 0 and where the sum is NaN (counted in n_nan) -- a NaN simulated value on an observation day among them: a particle may
+ * not skip an observation.
+ *
+ * Weights.  lw_max is the largest finite entry of lw;  w = exp(lw - lw_max), selected to exactly 1 where lw == lw_max and to 0
+ * where lw is -inf, +inf or NaN (the last two counted in n_nan);  q = (uint64) floor(w 2^40).  A particle more than 40 ln 2 = 27.7
+ * below the maximum therefore has weight 0: the filter resolves weights to 2^-40.  T = sum q is a 64-bit integer, exact in any
+ * order; sum_w and sum_w2 are added in one fixed order.  The caller forms ESS = sum_w^2 / sum_w2 and the log of the mean weight,
+ * lw_max + ln(sum_w / E).  No finite entry: w = q = 0, T = 0, lw_max = -inf.
+ *
+ * Resampling is systematic and in integers only, so any implementation gives the same ancestors (the rules are the plain C++ of
+ * simplyp_amd/csrc/simplyp_resample.h, which the kernel and a host program share):
+ *     C_i = q_0 + ... + q_i (inclusive),  T = C_{E-1}
+ *     x = (x0 << 32) | x1 of Philox4x32-10 under key (seed & 0xffffffff, seed >> 32) at counter (t, 0, 0, 0x50465253 "PFRS")
+ *     r = the high 64 bits of x T, so 0 <= r < T
+ *     the ancestor of particle k is the smallest i with E C_i > k T + r           both sides exact, below 2^85
+ * The ancestors do not decrease with k, and particle i is taken floor(E q_i / T) or ceil(E q_i / T) times.  T = 0: the ancestors
+ * are the identity, the offspring 0, n_unique = 0, and the call succeeds -- every particle is dead, which is the caller's to report.
+ *
+ * Rejuvenation.  y[d] = centre[d] + a (theta[d][k] - centre[d]) + scale[d] z, each + * in fp64 in this order without contraction,
+ * z the standard normal of the predictive stream (simplyp_predictive_series) at counter (k, t, d, 0x50464A54 "PFJT").  The whole
+ * particle keeps its position when any y[d] falls outside lo[d] <= y < hi[d] (counted in n_outside).  a = (3 delta - 1) /
+ * (2 delta), centre = the mean and scale = sqrt(1 - a a) times the standard deviation of the resampled positions is the
+ * kernel-shrinkage move of Liu & West (2001); a = 1 is plain jitter.
+ *
+ * All five entries are synchronous on the context's stream, keep their workspace in the context's grow-only scratch, and return
+ * SIMPLYP_ERR_ARG with nothing launched for E outside 1..2^22, a NULL required pointer, n_pairs outside 1..32, a pair out of range,
+ * n_dim outside 1..16, n_rows < 0, overlapping src and dst, lo[d] >= hi[d] or a NaN bound, a target outside [-2, SIMPLYP_NP_M) or
+ * named twice, a non-finite a or centre, a scale that is negative or not finite.
+ */
+typedef struct {
+    double   kernel_ms;    /* all of the entry's kernels, HIP events on the context's stream                                 */
+    double   lw_max;       /* pf_weights: the largest finite log weight, -inf when there is none                             */
+    double   sum_w;        /* pf_weights: sum of w                                                                            */
+    double   sum_w2;       /* pf_weights: sum of w w                                                                          */
+    uint64_t T;            /* pf_weights, pf_resample: sum of q                                                               */
+    int32_t  n_alive;      /* pf_weights: particles with q > 0                                                                */
+    int32_t  n_nan;        /* pf_loglik: increments that were NaN; pf_weights: log weights that were +inf or NaN              */
+    int32_t  n_unique;     /* pf_resample: distinct ancestors                                                                 */
+    int32_t  n_bad;        /* gather_members: ancestors outside [0, E)                                                        */
+    int32_t  n_outside;    /* pf_jitter: particles that kept their position                                                   */
+    int32_t  reserved;     /* fields an entry does not name are 0                                                             */
+} simplyp_pf_info;
+
+/*
+ * simplyp_pf_loglik -- every particle's log-likelihood of a window's observations, from the daily table the window's simplyp_run
+ * left on the device; one lane per particle.
+ *   dims .. reach_params    as for simplyp_gof (out_mask must contain Qr and the three daily fluxes)
+ *   obs             HOST    [n_out_reaches][SIMPLYP_N_GOF_VARS][D], NaN = no observation
+ *   pair_var, pair_reach   HOST  [n_pairs], 1 <= n_pairs <= 32: SIMPLYP_GOF_v and the position among the output reaches
+ *   err_m           device  [n_pairs][E] member order: the pair's m for every particle
+ *   status          device  [E] as written by simplyp_run, or NULL
+ *   lw              device  [E] member order: lw = accumulate ? lw + inc : inc
+ *   inc             device  [E] member order, or NULL: the increment
+ */
+int simplyp_pf_loglik(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                      const int32_t* out_reaches, int32_t n_out_reaches,
+                      const double* out, const int32_t* member_of_slot,
+                      const double* f_tdp, const double* reach_params, const double* obs /* host */,
+                      const int32_t* pair_var /* host */, const int32_t* pair_reach /* host */, int32_t n_pairs,
+                      const double* err_m, const int32_t* status, double* lw, double* inc, int32_t accumulate,
+                      simplyp_pf_info* info);
+
+/*
+ * simplyp_pf_weights -- the normalised weights of lw [E]: w [E] fp64 and q [E] uint64, all three on the device; info carries
+ * lw_max, sum_w, sum_w2, T, n_alive and n_nan.
+ */
+int simplyp_pf_weights(simplyp_ctx* ctx, int32_t E, const double* lw, double* w, uint64_t* q, simplyp_pf_info* info);
+
+/*
+ * simplyp_pf_resample -- the ancestors of assimilation step t (absolute: counted from the start of the filter) from q [E].
+ *   ancestors       device  [E] int32, non-decreasing
+ *   offspring       device  [E] int32, or NULL: how often each particle was taken
+ * info carries T and n_unique.  The prefix sum is a device scan (wave64 cross-lane, block, block sums), the search a bisection per
+ * particle on the 128-bit products.
+ */
+int simplyp_pf_resample(simplyp_ctx* ctx, int32_t E, const uint64_t* q, uint64_t seed, uint32_t t,
+                        int32_t* ancestors, int32_t* offspring, simplyp_pf_info* info);
+
+/*
+ * simplyp_gather_members -- dst[row][k] = src[row][ancestors[k]] for a table [n_rows][E] of 8-byte words (moved as words: NaN
+ * payloads survive): the model state (S * SIMPLYP_N_STATE rows), member_params, reach_params, f_tdp, the positions, err_m.
+ * Out of place: overlapping src and dst are refused.  An ancestor outside [0, E) is never dereferenced; its destination words
+ * become NaN and the case is counted in n_bad.  n_rows = 0 succeeds and launches nothing.
+ */
+int simplyp_gather_members(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const int32_t* ancestors, const void* src, void* dst,
+                           simplyp_pf_info* info);
+
+/*
+ * simplyp_pf_jitter -- the rejuvenation move of step t, in place on theta [n_dim][E], scattered into the run's arrays.
+ *   centre, scale, lo, hi   HOST  [n_dim]
+ *   target          HOST    [n_dim] as for simplyp_mcmc_propose: a row of member_params, -1 = f_tdp, -2 = nowhere
+ *   member_params   device  [SIMPLYP_NP_M][E], or NULL when no target is >= 0; rows that no dimension names are not touched
+ *   f_tdp           device  [E], or NULL when no target is -1
+ */
+int simplyp_pf_jitter(simplyp_ctx* ctx, int32_t E, int32_t n_dim, uint64_t seed, uint32_t t, double a,
+                      const double* centre /* host */, const double* scale /* host */,
+                      const double* lo /* host */, const double* hi /* host */, const int32_t* target /* host */,
+                      double* theta, double* member_params, double* f_tdp, simplyp_pf_info* info);
 
 /*
  * simplyp_eval_units -- the path's scalar device functions on caller-given arguments, one thread per row: how the tests pin the

@@ -120,6 +120,20 @@ class SobolInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class PfInfo(C.Structure):
+    """simplyp_pf_info of include/simplyp.h."""
+    _fields_ = [('kernel_ms', C.c_double), ('lw_max', C.c_double), ('sum_w', C.c_double), ('sum_w2', C.c_double),
+                ('T', C.c_uint64), ('n_alive', C.c_int32), ('n_nan', C.c_int32), ('n_unique', C.c_int32), ('n_bad', C.c_int32),
+                ('n_outside', C.c_int32), ('reserved', C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
+
+
+PF_MAX_LOG2_E = 22              # the particle filter's entries take 1 <= E <= 2^22
+PF_WEIGHT_BITS = 40             # ... and resolve normalised weights to 2^-40
+
+
 # SIMPLYP_NM_*: the rows of istate [NM_N_ISTATE, S] (simplyp_amd.neldermead names the phases and the status values)
 NM_ISTATE = ['phase', 'cursor', 'n_iter', 'status', 'n_reflect', 'n_expand', 'n_contract_out', 'n_contract_in', 'n_shrink']
 NM_N_ISTATE = len(NM_ISTATE)

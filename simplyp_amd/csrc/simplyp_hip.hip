@@ -26,6 +26,7 @@
 #include "simplyp_mcmc.hip.h"
 #include "simplyp_neldermead.hip.h"
 #include "simplyp_sobol.hip.h"
+#include "simplyp_particle.hip.h"
 #include "simplyp_pack_stream.h"
 #include "simplyp_table.h"
 
@@ -59,6 +60,7 @@ struct simplyp_ctx {
     DeviceBuf nm;             // simplyp_nm_*: 8 x uint32 counters
     DeviceBuf nm_work;        // simplyp_nm_update: the sort's other copy of the simplexes
     DeviceBuf sobol;          // simplyp_sobol_indices: n_valid | valid [Npad] | mu [n_rows] | n_used [B] | counts [B][Npad] uint16 | sums
+    DeviceBuf pf;             // simplyp_pf_*, simplyp_gather_members: PfResult (256-byte slot) | the entry's lists, partial or prefix sums
     DeviceBuf queue;          // ticket, error, done[n_groups] (uint32) | ckpt[CKPT_N][E] (double)
     // streamed output (simplyp_stream_out): the armed destination, the chunk flags the queue kernel raises in pinned host
     // memory, and the host thread that turns a raised flag into the D2H copies of that chunk's rows on `copy_stream`
@@ -993,6 +995,7 @@ void simplyp_ctx_destroy(simplyp_ctx* ctx)
     if (ctx->nm.ptr) (void)hipFree(ctx->nm.ptr);
     if (ctx->nm_work.ptr) (void)hipFree(ctx->nm_work.ptr);
     if (ctx->sobol.ptr) (void)hipFree(ctx->sobol.ptr);
+    if (ctx->pf.ptr) (void)hipFree(ctx->pf.ptr);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
     if (ctx->ev_main) (void)hipEventDestroy(ctx->ev_main);
@@ -2473,6 +2476,220 @@ int simplyp_sobol_indices(simplyp_ctx* ctx, int32_t N, int32_t n_dim, int32_t n_
                           int32_t n_boot, uint64_t seed, double* sums, int32_t* n_used, double* indices, simplyp_sobol_info* info)
 {
     SIMPLYP_GUARD(ctx, sobol_indices_impl(ctx, N, n_dim, n_rows, table, status, n_boot, seed, sums, n_used, indices, info))
+}
+
+// ---- the particle filter's steps (simplyp_particle.hip.h) ---------------------------------------------------------------------
+constexpr size_t PF_HEAD_BYTES = 256;      // the PfResult at the head of ctx->pf
+
+// What the five entries do alike once their arguments have passed: the workspace (`work_bytes` behind the result slot), the
+// zeroed result, the start of the timed bracket.  Nothing is launched before this.
+static int pf_begin(simplyp_ctx* ctx, size_t work_bytes, simplyp::PfResult*& res, char*& work)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = ensure(ctx, ctx->pf, PF_HEAD_BYTES + work_bytes)) return rc;
+    res = (simplyp::PfResult*)ctx->pf.ptr;
+    work = (char*)ctx->pf.ptr + PF_HEAD_BYTES;
+    HIP_TRY(ctx, hipMemsetAsync(res, 0, sizeof(simplyp::PfResult), ctx->stream));
+    return timed_begin(ctx);
+}
+
+static int pf_end(simplyp_ctx* ctx, simplyp_pf_info* info)
+{
+    HIP_TRY(ctx, hipGetLastError());
+    simplyp::PfResult r{};
+    if (info) *info = simplyp_pf_info{};
+    if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr, &r, ctx->pf.ptr, sizeof(r))) return rc;
+    if (info) {
+        info->lw_max = r.lw_max; info->sum_w = r.sum_w; info->sum_w2 = r.sum_w2; info->T = r.T;
+        info->n_alive = (int32_t)r.n_alive; info->n_nan = (int32_t)r.n_nan; info->n_unique = (int32_t)r.n_unique;
+        info->n_bad = (int32_t)r.n_bad; info->n_outside = (int32_t)r.n_outside;
+    }
+    return SIMPLYP_OK;
+}
+
+static int pf_shape(simplyp_ctx* ctx, const char* me, int64_t E)
+{
+    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a run is pending on this context; call simplyp_sync first", me);
+    if (E < 1 || E > simplyp_resample::MAX_E)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: E must be in [1, 2^%d] (got %lld)", me, simplyp_resample::MAX_LOG2_E, (long long)E);
+    return SIMPLYP_OK;
+}
+
+static unsigned pf_blocks(int E) { return (unsigned)((E + simplyp::PF_THREADS - 1) / simplyp::PF_THREADS); }
+
+static int pf_loglik_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask, const int32_t* out_reaches,
+                          int32_t n_out_reaches, const double* out, const int32_t* member_of_slot, const double* f_tdp,
+                          const double* reach_params, const double* obs, const int32_t* pair_var, const int32_t* pair_reach,
+                          int32_t n_pairs, const double* err_m, const int32_t* status, double* lw, double* inc, int32_t accumulate,
+                          simplyp_pf_info* info)
+{
+    const char* me = "simplyp_pf_loglik";
+    TableView t;
+    const bool ptrs_ok = out && f_tdp && reach_params && obs && pair_var && pair_reach && err_m && lw;
+    if (int rc = check_table(ctx, me, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, false, t)) return rc;
+    if (int rc = pf_shape(ctx, me, t.E)) return rc;
+    if (n_pairs < 1 || n_pairs > simplyp::PF_MAX_PAIRS)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_pairs must be in [1, %d] (got %d)", me, simplyp::PF_MAX_PAIRS, (int)n_pairs);
+    const int E = t.E, S = t.S, D = t.D, R = t.R;
+    simplyp::PfLoglikArgs g{};
+    // the observation days of every pair in the window, ascending, and what was observed: shared by all particles
+    std::vector<int32_t> ints(t.reach_of);
+    std::vector<double> vals;
+    const size_t o_day = ints.size();
+    for (int p = 0; p < n_pairs; ++p) {
+        if (pair_var[p] < 0 || pair_var[p] >= SIMPLYP_N_GOF_VARS || pair_reach[p] < 0 || pair_reach[p] >= R)
+            return fail(ctx, SIMPLYP_ERR_ARG, "%s: pair %d = (variable %d, output reach %d) is out of range", me, p, (int)pair_var[p], (int)pair_reach[p]);
+        g.pair_var[p] = pair_var[p]; g.pair_reach[p] = pair_reach[p];
+        const double* ob = obs + ((size_t)pair_reach[p] * SIMPLYP_N_GOF_VARS + pair_var[p]) * D;
+        for (int d = 0; d < D; ++d)
+            if (ob[d] == ob[d]) { ints.push_back(d); vals.push_back(ob[d]); }
+        g.day_ptr[p + 1] = (int)vals.size();
+    }
+    if (ints.size() & 1) ints.push_back(0);
+    const size_t ibytes = ints.size() * sizeof(int32_t), dbytes = vals.size() * sizeof(double);
+    char* work = nullptr;
+    if (int rc = pf_begin(ctx, ibytes + dbytes, g.res, work)) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(work, ints.data(), ibytes, hipMemcpyHostToDevice, ctx->stream));
+    if (dbytes) HIP_TRY(ctx, hipMemcpyAsync(work + ibytes, vals.data(), dbytes, hipMemcpyHostToDevice, ctx->stream));
+    g.E = E; g.R = R; g.n_pairs = n_pairs; g.accumulate = accumulate != 0;
+    g.out = out; g.col_stride = (long long)D * R * E;
+    std::copy(t.col, t.col + 4, g.col);
+    g.reach_of = (const int32_t*)work; g.day = (const int32_t*)work + o_day; g.obs = (const double*)(work + ibytes);
+    g.member_of_slot = member_of_slot; g.f_tdp = f_tdp;
+    g.a_catch = reach_params + (size_t)SIMPLYP_PR_A_CATCH * S * E;
+    g.err_m = err_m; g.status = status; g.lw = lw; g.inc = inc;
+    hipLaunchKernelGGL(simplyp::simplyp_pf_loglik_kernel, dim3(pf_blocks(E)), dim3(simplyp::PF_THREADS), 0, ctx->stream, g);
+    return pf_end(ctx, info);          // synchronises: the host lists outlive their copies
+}
+
+static int pf_weights_impl(simplyp_ctx* ctx, int32_t E, const double* lw, double* w, uint64_t* q, simplyp_pf_info* info)
+{
+    const char* me = "simplyp_pf_weights";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    if (int rc = pf_shape(ctx, me, E)) return rc;
+    if (!lw || !w || !q) return fail(ctx, SIMPLYP_ERR_ARG, "%s: lw, w and q must not be NULL", me);
+    simplyp::PfWeightsArgs g{};
+    g.E = E; g.n_blocks = (int)pf_blocks(E);
+    g.lw = lw; g.w = w; g.q = (unsigned long long*)q;
+    char* work = nullptr;
+    if (int rc = pf_begin(ctx, (size_t)3 * g.n_blocks * sizeof(double), g.res, work)) return rc;
+    g.part_max = (double*)work; g.part_sum = (double*)work + g.n_blocks;
+    const dim3 grid((unsigned)g.n_blocks), one(1), threads(simplyp::PF_THREADS);
+    hipLaunchKernelGGL(simplyp::simplyp_pf_max_kernel, grid, threads, 0, ctx->stream, g);
+    hipLaunchKernelGGL(simplyp::simplyp_pf_max_finish_kernel, one, threads, 0, ctx->stream, g);
+    hipLaunchKernelGGL(simplyp::simplyp_pf_weights_kernel, grid, threads, 0, ctx->stream, g);
+    hipLaunchKernelGGL(simplyp::simplyp_pf_sum_finish_kernel, one, threads, 0, ctx->stream, g);
+    return pf_end(ctx, info);
+}
+
+static int pf_resample_impl(simplyp_ctx* ctx, int32_t E, const uint64_t* q, uint64_t seed, uint32_t t, int32_t* ancestors,
+                            int32_t* offspring, simplyp_pf_info* info)
+{
+    const char* me = "simplyp_pf_resample";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    if (int rc = pf_shape(ctx, me, E)) return rc;
+    if (!q || !ancestors) return fail(ctx, SIMPLYP_ERR_ARG, "%s: q and ancestors must not be NULL", me);
+    simplyp::PfResampleArgs g{};
+    g.E = E; g.n_blocks = (int)pf_blocks(E);
+    g.q = (const unsigned long long*)q; g.ancestors = ancestors; g.offspring = offspring;
+    g.key0 = (uint32_t)(seed & 0xFFFFFFFFull); g.key1 = (uint32_t)(seed >> 32); g.t = t;
+    char* work = nullptr;
+    if (int rc = pf_begin(ctx, ((size_t)E + g.n_blocks) * sizeof(uint64_t), g.res, work)) return rc;
+    g.C = (unsigned long long*)work; g.block_sum = g.C + E;
+    if (offspring) HIP_TRY(ctx, hipMemsetAsync(offspring, 0, (size_t)E * sizeof(int32_t), ctx->stream));
+    const dim3 grid((unsigned)g.n_blocks), one(1), threads(simplyp::PF_THREADS);
+    hipLaunchKernelGGL(simplyp::simplyp_pf_scan_block_kernel, grid, threads, 0, ctx->stream, g);
+    hipLaunchKernelGGL(simplyp::simplyp_pf_scan_sums_kernel, one, threads, 0, ctx->stream, g);
+    hipLaunchKernelGGL(simplyp::simplyp_pf_scan_add_kernel, grid, threads, 0, ctx->stream, g);
+    hipLaunchKernelGGL(simplyp::simplyp_pf_search_kernel, grid, threads, 0, ctx->stream, g);
+    hipLaunchKernelGGL(simplyp::simplyp_pf_offspring_kernel, grid, threads, 0, ctx->stream, g);
+    return pf_end(ctx, info);
+}
+
+static int gather_members_impl(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const int32_t* ancestors, const void* src, void* dst,
+                               simplyp_pf_info* info)
+{
+    const char* me = "simplyp_gather_members";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    if (int rc = pf_shape(ctx, me, E)) return rc;
+    if (n_rows < 0 || n_rows > (int64_t)0x7FFFFFFF)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_rows must be in [0, 2^31) (got %lld)", me, (long long)n_rows);
+    if (info) *info = simplyp_pf_info{};
+    if (n_rows == 0) return SIMPLYP_OK;
+    if (!ancestors || !src || !dst) return fail(ctx, SIMPLYP_ERR_ARG, "%s: ancestors, src and dst must not be NULL", me);
+    const uintptr_t a = (uintptr_t)src, b = (uintptr_t)dst, bytes = (uintptr_t)n_rows * (uintptr_t)E * 8u;
+    if (a < b + bytes && b < a + bytes) return fail(ctx, SIMPLYP_ERR_ARG, "%s: src and dst overlap (the gather is out of place)", me);
+    simplyp::PfGatherArgs g{};
+    g.E = E; g.n_rows = n_rows; g.ancestors = ancestors;
+    g.src = (const unsigned long long*)src; g.dst = (unsigned long long*)dst;
+    char* work = nullptr;
+    if (int rc = pf_begin(ctx, 0, g.res, work)) return rc;
+    const long long row_blocks = (n_rows + simplyp::PF_GATHER_ROWS - 1) / simplyp::PF_GATHER_ROWS;
+    hipLaunchKernelGGL(simplyp::simplyp_gather_members_kernel, dim3(pf_blocks(E), (unsigned)std::min<long long>(row_blocks, 65535)),
+                       dim3(simplyp::PF_THREADS), 0, ctx->stream, g);
+    return pf_end(ctx, info);
+}
+
+static int pf_jitter_impl(simplyp_ctx* ctx, int32_t E, int32_t n_dim, uint64_t seed, uint32_t t, double a, const double* centre,
+                          const double* scale, const double* lo, const double* hi, const int32_t* target, double* theta,
+                          double* member_params, double* f_tdp, simplyp_pf_info* info)
+{
+    const char* me = "simplyp_pf_jitter";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    if (int rc = pf_shape(ctx, me, E)) return rc;
+    if (n_dim < 1 || n_dim > simplyp::PF_MAX_DIM)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_dim must be in [1, %d] (got %d)", me, simplyp::PF_MAX_DIM, (int)n_dim);
+    if (!centre || !scale || !lo || !hi || !target || !theta)
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: centre, scale, lo, hi, target and theta must not be NULL", me);
+    if (!std::isfinite(a)) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a must be finite (got %g)", me, a);
+    simplyp::PfJitterArgs g{};
+    TABLE_TRY(ctx, st::check_box(me, n_dim, lo, hi, target, member_params, f_tdp, g.lo, g.hi, g.target, msg));
+    for (int d = 0; d < n_dim; ++d) {
+        if (!std::isfinite(centre[d]) || !(scale[d] >= 0.0) || !std::isfinite(scale[d]))
+            return fail(ctx, SIMPLYP_ERR_ARG, "%s: centre[%d] must be finite and scale[%d] finite and >= 0 (got %g, %g)", me, d, d, centre[d], scale[d]);
+        g.centre[d] = centre[d]; g.scale[d] = scale[d];
+    }
+    g.E = E; g.n_dim = n_dim; g.a = a; g.t = t;
+    g.key0 = (uint32_t)(seed & 0xFFFFFFFFull); g.key1 = (uint32_t)(seed >> 32);
+    g.theta = theta; g.member_params = member_params; g.f_tdp = f_tdp;
+    char* work = nullptr;
+    if (int rc = pf_begin(ctx, 0, g.res, work)) return rc;
+    hipLaunchKernelGGL(simplyp::simplyp_pf_jitter_kernel, dim3(pf_blocks(E)), dim3(simplyp::PF_THREADS), 0, ctx->stream, g);
+    return pf_end(ctx, info);
+}
+
+int simplyp_pf_loglik(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask, const int32_t* out_reaches,
+                      int32_t n_out_reaches, const double* out, const int32_t* member_of_slot, const double* f_tdp,
+                      const double* reach_params, const double* obs, const int32_t* pair_var, const int32_t* pair_reach,
+                      int32_t n_pairs, const double* err_m, const int32_t* status, double* lw, double* inc, int32_t accumulate,
+                      simplyp_pf_info* info)
+{
+    SIMPLYP_GUARD(ctx, pf_loglik_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params, obs,
+                                      pair_var, pair_reach, n_pairs, err_m, status, lw, inc, accumulate, info))
+}
+
+int simplyp_pf_weights(simplyp_ctx* ctx, int32_t E, const double* lw, double* w, uint64_t* q, simplyp_pf_info* info)
+{
+    SIMPLYP_GUARD(ctx, pf_weights_impl(ctx, E, lw, w, q, info))
+}
+
+int simplyp_pf_resample(simplyp_ctx* ctx, int32_t E, const uint64_t* q, uint64_t seed, uint32_t t, int32_t* ancestors,
+                        int32_t* offspring, simplyp_pf_info* info)
+{
+    SIMPLYP_GUARD(ctx, pf_resample_impl(ctx, E, q, seed, t, ancestors, offspring, info))
+}
+
+int simplyp_gather_members(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const int32_t* ancestors, const void* src, void* dst,
+                           simplyp_pf_info* info)
+{
+    SIMPLYP_GUARD(ctx, gather_members_impl(ctx, E, n_rows, ancestors, src, dst, info))
+}
+
+int simplyp_pf_jitter(simplyp_ctx* ctx, int32_t E, int32_t n_dim, uint64_t seed, uint32_t t, double a, const double* centre,
+                      const double* scale, const double* lo, const double* hi, const int32_t* target, double* theta,
+                      double* member_params, double* f_tdp, simplyp_pf_info* info)
+{
+    SIMPLYP_GUARD(ctx, pf_jitter_impl(ctx, E, n_dim, seed, t, a, centre, scale, lo, hi, target, theta, member_params, f_tdp, info))
 }
 
 void* simplyp_host_alloc(int64_t bytes)

@@ -32,7 +32,8 @@ ABI_SYMBOLS = ['simplyp_abi_version', 'simplyp_device_count', 'simplyp_ctx_creat
                'simplyp_pack_roundtrip_host', 'simplyp_fetch_packed_pred', 'simplyp_pack_roundtrip_host_pred',
                'simplyp_time_quantiles', 'simplyp_predictive_series', 'simplyp_predictive_bands',
                'simplyp_mcmc_propose', 'simplyp_mcmc_log_prob', 'simplyp_mcmc_accept', 'simplyp_nm_propose', 'simplyp_nm_update',
-               'simplyp_sobol_design', 'simplyp_sobol_indices']
+               'simplyp_sobol_design', 'simplyp_sobol_indices',
+               'simplyp_pf_loglik', 'simplyp_pf_weights', 'simplyp_pf_resample', 'simplyp_gather_members', 'simplyp_pf_jitter']
 
 _lib = None
 
@@ -139,6 +140,19 @@ def lib():
     L.simplyp_sobol_indices.restype = C.c_int
     L.simplyp_sobol_indices.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, i32p, C.c_int32, C.c_uint64, dp, i32p, dp,
                                         C.POINTER(abi.SobolInfo)]
+    pf = C.POINTER(abi.PfInfo)
+    L.simplyp_pf_loglik.restype = C.c_int
+    L.simplyp_pf_loglik.argtypes = L.simplyp_gof.argtypes[:10] + [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, dp, i32p, dp, dp,
+                                                                C.c_int32, pf]
+    L.simplyp_pf_weights.restype = C.c_int
+    L.simplyp_pf_weights.argtypes = [vp, C.c_int32, dp, dp, vp, pf]
+    L.simplyp_pf_resample.restype = C.c_int
+    L.simplyp_pf_resample.argtypes = [vp, C.c_int32, vp, C.c_uint64, C.c_uint32, i32p, i32p, pf]
+    L.simplyp_gather_members.restype = C.c_int
+    L.simplyp_gather_members.argtypes = [vp, C.c_int32, C.c_int64, i32p, vp, vp, pf]
+    L.simplyp_pf_jitter.restype = C.c_int
+    L.simplyp_pf_jitter.argtypes = [vp, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_double] + [C.POINTER(C.c_double)] * 4 \
+        + [C.POINTER(C.c_int32), dp, dp, dp, pf]
     L.simplyp_stream_out.restype = C.c_int
     L.simplyp_stream_out.argtypes = [vp, vp, C.c_int64]
     L.simplyp_fetch_packed.restype = C.c_int
@@ -898,6 +912,102 @@ class Engine(object):
         info = self._info_call(abi.SobolInfo, 'simplyp_sobol_indices', self._h, N, n_dim, n_rows, table.data_ptr(), self._ptr(status),
                                n_boot, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), sums.data_ptr(), n_used.data_ptr(), ind.data_ptr())
         return ind, sums, n_used, info
+
+
+    # ---- the particle filter's steps (simplyp_pf_*, simplyp_gather_members; simplyp_amd.particle restates them) ----
+    def _pf_vector(self, t, E, dtype, what):
+        if not self.torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != (E,) or not t.is_contiguous() or t.device != self.tdev:
+            raise ValueError("%s must be a contiguous %s tensor [%d] on %s" % (what, dtype, E, self.tdev))
+        return t
+
+    def pf_loglik(self, out, out_mask, obs, pairs, err_m, lw, f_tdp, reach_params, out_reaches=None, member_of_slot=None,
+                  status=None, inc=None, accumulate=True):
+        """Every particle's log-likelihood of the observations of the window whose daily table ``out`` [n_cols, D, n_reaches, E] a
+        ``run`` left on the device (``simplyp_pf_loglik``).  obs [n_reaches, 6, D] host array, NaN = no observation; pairs: list of
+        (variable index in ``abi.GOF_VARS``, position among the output reaches); err_m [n_pairs, E] float64 device tensor (member
+        order); lw [E] float64 device tensor: ``lw += inc`` with ``accumulate``, ``lw = inc`` without; status [E] int32 or None;
+        inc [E] float64 device tensor or None: receives the increment.  Returns the info dict."""
+        torch = self.torch
+        head, rp, (D, n_or, E), keep = self._daily_table(out, out_mask, reach_params, out_reaches, member_of_slot, True)
+        obs = np.ascontiguousarray(obs, dtype=np.float64)
+        if obs.shape != (n_or, len(abi.GOF_VARS), D):
+            raise ValueError("obs must have shape %s, got %s" % ((n_or, len(abi.GOF_VARS), D), obs.shape))
+        pv = np.ascontiguousarray([p[0] for p in pairs], dtype=np.int32)
+        pr = np.ascontiguousarray([p[1] for p in pairs], dtype=np.int32)
+        ft = self._f_tdp(f_tdp, E)
+        if not torch.is_tensor(err_m) or err_m.dtype != torch.float64 or tuple(err_m.shape) != (len(pv), E) or not err_m.is_contiguous():
+            raise ValueError("err_m must be a contiguous float64 device tensor [n_pairs, E]")
+        self._pf_vector(lw, E, torch.float64, 'lw')
+        if inc is not None:
+            self._pf_vector(inc, E, torch.float64, 'inc')
+        if status is not None:
+            self._pf_vector(status, E, torch.int32, 'status')
+        i32 = C.POINTER(C.c_int32)
+        info = self._info_call(abi.PfInfo, 'simplyp_pf_loglik', *(head + (ft.data_ptr(), rp.data_ptr(), obs.ctypes.data_as(C.POINTER(C.c_double)),
+                               pv.ctypes.data_as(i32), pr.ctypes.data_as(i32), len(pv), err_m.data_ptr(), self._ptr(status),
+                               lw.data_ptr(), self._ptr(inc), 1 if accumulate else 0)))
+        del keep
+        return info
+
+    def pf_weights(self, lw, w=None, q=None):
+        """Normalised weights of the log weights lw [E] (``simplyp_pf_weights``).  Returns (w [E] float64, q [E] int64 -- the
+        library's uint64, below 2^41 --, info with lw_max, sum_w, sum_w2, T, n_alive, n_nan)."""
+        torch = self.torch
+        E = int(lw.shape[0]) if torch.is_tensor(lw) and lw.dim() == 1 else -1
+        self._pf_vector(lw, E, torch.float64, 'lw')
+        w = torch.empty((E,), dtype=torch.float64, device=self.tdev) if w is None else self._pf_vector(w, E, torch.float64, 'w')
+        q = torch.empty((E,), dtype=torch.int64, device=self.tdev) if q is None else self._pf_vector(q, E, torch.int64, 'q')
+        info = self._info_call(abi.PfInfo, 'simplyp_pf_weights', self._h, E, lw.data_ptr(), w.data_ptr(), q.data_ptr())
+        return w, q, info
+
+    def pf_resample(self, q, seed, t, ancestors=None, offspring=True):
+        """Systematic resampling of the integer weights q [E] (int64 device tensor) at absolute assimilation step ``t``
+        (``simplyp_pf_resample``).  Returns (ancestors [E] int32, offspring [E] int32 or None, info with T and n_unique)."""
+        torch = self.torch
+        E = int(q.shape[0]) if torch.is_tensor(q) and q.dim() == 1 else -1
+        self._pf_vector(q, E, torch.int64, 'q')
+        anc = torch.empty((E,), dtype=torch.int32, device=self.tdev) if ancestors is None else self._pf_vector(ancestors, E, torch.int32, 'ancestors')
+        if offspring is True:
+            offspring = torch.empty((E,), dtype=torch.int32, device=self.tdev)
+        elif offspring is False:
+            offspring = None
+        if offspring is not None:
+            self._pf_vector(offspring, E, torch.int32, 'offspring')
+        info = self._info_call(abi.PfInfo, 'simplyp_pf_resample', self._h, E, q.data_ptr(), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                               C.c_uint32(int(t) & 0xFFFFFFFF), anc.data_ptr(), self._ptr(offspring))
+        return anc, offspring, info
+
+    def gather_members(self, src, ancestors, dst=None):
+        """``dst[..., k] = src[..., ancestors[k]]`` for a contiguous device tensor of 8-byte elements whose LAST axis is the member
+        axis (``simplyp_gather_members``): the model state, member_params, reach_params, f_tdp, positions.  Out of place.
+        Returns (dst, info with n_bad)."""
+        torch = self.torch
+        if not torch.is_tensor(src) or src.element_size() != 8 or not src.is_contiguous() or src.dim() < 1 or src.device != self.tdev:
+            raise ValueError("src must be a contiguous device tensor of 8-byte elements whose last axis is the member axis")
+        E = int(src.shape[-1])
+        self._pf_vector(ancestors, E, torch.int32, 'ancestors')
+        if dst is None:
+            dst = torch.empty_like(src)
+        elif not torch.is_tensor(dst) or dst.shape != src.shape or dst.dtype != src.dtype or not dst.is_contiguous() or dst.device != self.tdev:
+            raise ValueError("dst must be a contiguous tensor shaped and typed like src")
+        n_rows = src.numel() // E if E else 0
+        info = self._info_call(abi.PfInfo, 'simplyp_gather_members', self._h, E, C.c_int64(n_rows), ancestors.data_ptr(), src.data_ptr(),
+                               dst.data_ptr())
+        return dst, info
+
+    def pf_jitter(self, theta, t, a, centre, scale, lo, hi, target, member_params=None, f_tdp=None, seed=0):
+        """The rejuvenation move of step ``t`` in place on theta [n_dim, E] (``simplyp_pf_jitter``): a, centre / scale / lo / hi
+        [n_dim] and target [n_dim] (as for ``mcmc_propose``) on the host; member_params [NP_M, E] and f_tdp [E] device tensors
+        receive the rows the targets name.  Returns the info dict (n_outside)."""
+        n_dim, E = (int(x) for x in theta.shape)
+        arrs = [np.ascontiguousarray(x, dtype=np.float64) for x in (centre, scale, lo, hi)]
+        tg = np.ascontiguousarray(target, dtype=np.int32)
+        if any(x.shape != (n_dim,) for x in arrs) or tg.shape != (n_dim,):
+            raise ValueError("centre, scale, lo, hi and target need one entry per dimension")
+        dbl = C.POINTER(C.c_double)
+        return self._info_call(abi.PfInfo, 'simplyp_pf_jitter', self._h, E, n_dim, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                               C.c_uint32(int(t) & 0xFFFFFFFF), float(a), *([x.ctypes.data_as(dbl) for x in arrs]
+                               + [tg.ctypes.data_as(C.POINTER(C.c_int32)), theta.data_ptr(), self._ptr(member_params), self._ptr(f_tdp)]))
 
 
 def interpolate_quantiles(lower, upper, q, n_used):
