@@ -466,7 +466,9 @@ typedef struct {
 /*
  * simplyp_gof -- statistics of every member's simulated series against shared observations, from the daily table a
  * previous simplyp_run left on the device.  Variables with 10 or fewer observations get NaN rows (the reference drops
- * them, :430, :453); a day is used when the observation and the simulated value are both non-NaN (:436).
+ * them, :430, :453); a day is used when the observation and the simulated value are both non-NaN (:436).  A day whose
+ * logarithm does not exist (a negative observation, a negative simulated value) drops out of the sums of log NSE it would
+ * enter, and the mean log observation runs over the days that have one -- what the reference's NaN-skipping sums do (:442-443).
  *
  *   dims            E, S, D as in the run (n_forcing_sets ignored)
  *   out_mask, out_reaches, n_out_reaches   as passed to simplyp_run; the mask must contain Qr, Msus_kg/day,
@@ -1065,6 +1067,15 @@ int simplyp_pf_jitter(simplyp_ctx* ctx, int32_t E, int32_t n_dim, uint64_t seed,
  *               out device [n][2]  = f_x as the end-of-day flows evaluate it, f_x as the right-hand side's fused form does
  *   which = 1   in  device [n][10] = P_netInput, A_catch, Kf, Msoil, EPC0, Qs, Qq, Vs, TDPs, Plab
  *               out device [n][3]  = TDPs, Plab (clamped at 0 like :696-697), conc_TDPs
+ * and the fp64 elementary functions every kernel of the library calls (the same inline functions, not copies), whose contract
+ * is < 1 ulp for finite arguments in range (exp: |x| <= 700; log, reciprocal: normal x > 0 resp. x != 0):
+ *   which = 2   in  device [n][1]  = x
+ *               out device [n][4]  = exp(x) evaluated alone; in slot 1 of a group of two; in slot 0 and in slot 6 of a group of
+ *                                    seven, the other slots holding other rows' arguments: four columns that are bit-identical
+ *   which = 3   in  device [n][1]  = x            out device [n][1] = log(x)
+ *   which = 4   in  device [n][1]  = x            out device [n][3] = the raw hardware reciprocal, one Newton step, two steps
+ *   which = 5   in  device [n][2]  = q, b         out device [n][1] = q**b as the right-hand side forms it, exp(b log(q))
+ * Any other value of `which` is SIMPLYP_ERR_ARG.
  * Synchronous.  Not on the hot path.
  */
 int simplyp_eval_units(simplyp_ctx* ctx, int32_t which, int32_t n, const double* in, double* out);

@@ -10,7 +10,7 @@
 // observation -> only the Qr row is read; days with any chemistry observation -> Qr and the three flux rows), which the
 // wave reads through the scalar cache.  HBM-bound: 8 or 32 bytes per member and observation day against ~15 / ~130
 // fp64 operations.  The day lists are cut into `n_chunks` slices (blockIdx.y) so that a 100 000-member ensemble puts
-// several thousand waves in flight; partial sums go through a [chunk][reach][78][E] scratch table and a second kernel
+// several thousand waves in flight; partial sums go through a [chunk][reach][84][E] scratch table and a second kernel
 // adds them in chunk order (deterministic, no atomics) and finishes the statistics.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,7 +21,7 @@
 
 namespace simplyp {
 
-constexpr int GOF_NACC = 13;           // running sums per variable
+constexpr int GOF_NACC = 14;           // running sums per variable
 constexpr int GOF_NV = SIMPLYP_N_GOF_VARS;
 constexpr int GOF_BATCH_Q = 8;         // discharge days whose Qr rows are loaded together
 constexpr int GOF_BATCH_C = 4;         // chemistry days (4 rows each) loaded together
@@ -38,14 +38,14 @@ struct GofArgs {
     const int32_t* reach_of;           // [R] reach index of output reach r
     const int32_t* q_ptr;              // [R+1] offsets into q_day / q_obs
     const int32_t* q_day;              // days with a discharge observation
-    const double* q_obs;               // [Kq][2]: obs, ln obs
+    const double* q_obs;               // [Kq][4]: obs, ln obs, ln obs - shift (0 when the observation has no log), 1 (0 then)
     const int32_t* c_ptr;              // [R+1] offsets into c_day / c_obs
     const int32_t* c_day;              // days with any chemistry observation
-    const double* c_obs;               // [Kc][10]: obs of SS,TDP,PP,TP,SRP (NaN = none), then their logs
-    const double* shift;               // [R][12]: per variable mean obs, mean ln obs (conditioning shifts)
+    const double* c_obs;               // [Kc][20]: obs of SS,TDP,PP,TP,SRP (NaN = none), their logs, then as in q_obs
+    const double* shift;               // [R][12]: per variable mean obs, mean ln obs (conditioning shifts; the host applies the second six)
     const double* n_obs;               // [R][6] observation counts (0 when the variable is dropped)
     int n_chunks_q, n_chunks_c;        // slices of the discharge / chemistry day lists
-    double* partial;                   // [max(n_chunks_q, n_chunks_c)][R][6*13][E]
+    double* partial;                   // [max(n_chunks_q, n_chunks_c)][R][6*14][E]
     double* gof;                       // [SIMPLYP_N_GOF_STATS][6][R][E], member order
 };
 
@@ -53,9 +53,10 @@ struct GofAcc {
     double a[GOF_NACC];
 };
 
-// One (obs, sim) pair of one variable.  o, lo: observation and its log (wave-uniform); s: simulated value (per lane);
-// co, clo: shifts.  A NaN simulated value drops the pair (pandas dropna, visualise_results.py:436); +-inf stays.
-__device__ __forceinline__ void gof_add(GofAcc& A, double o, double lo, double s, double co, double clo)
+// One (obs, sim) pair of one variable.  o, lo: observation and its log; lop, w: the log less its shift and 1, or 0 and 0 when
+// the observation has no log (all four wave-uniform, made by the host); s: simulated value (per lane); co: shift.  A NaN
+// simulated value drops the pair (pandas dropna, visualise_results.py:436); +-inf stays.
+__device__ __forceinline__ void gof_add(GofAcc& A, double o, double lo, double lop, double w, double s, double co)
 {
     if (s != s) return;
     double ls, q;
@@ -66,7 +67,7 @@ __device__ __forceinline__ void gof_add(GofAcc& A, double o, double lo, double s
         ls = log(s);
         q = o / s - 1.0;
     }
-    const double op = o - co, sp = s - co, lop = lo - clo;
+    const double op = o - co, sp = s - co;
     const double d = o - s, dl = lo - ls;
     A.a[0] += 1.0;
     A.a[1] += op;
@@ -76,15 +77,16 @@ __device__ __forceinline__ void gof_add(GofAcc& A, double o, double lo, double s
     A.a[5] = __builtin_fma(op, sp, A.a[5]);
     A.a[6] += fabs(d);
     A.a[7] = __builtin_fma(d, d, A.a[7]);
-    A.a[8] += lop;
-    A.a[9] = __builtin_fma(lop, lop, A.a[9]);
+    A.a[8] += lop;                                // log(obs < 0) is NaN too: its lop = w = 0 leave the day out of these sums and
+    A.a[9] = __builtin_fma(lop, lop, A.a[9]);     // of their count, as nanmean / nansum leave it out (:443), without a select
+    A.a[13] += w;
     if (dl == dl) A.a[10] = __builtin_fma(dl, dl, A.a[10]);      // np.sum of a pandas Series skips NaN: log(sim < 0) drops out of :442
     A.a[11] += ls;
     A.a[12] = __builtin_fma(q, q, A.a[12]);
 }
 
-// One chemistry day: the five simulated concentrations and their pairs.  ob: 5 observations then their logs (wave-uniform,
-// NaN = none); sh: the reach's 12 shifts.
+// One chemistry day: the five simulated concentrations and their pairs.  ob: the day's row of c_obs (wave-uniform, NaN = none);
+// sh: the reach's 12 shifts.
 __device__ __forceinline__ void gof_chem_day(GofAcc (&acc)[GOF_NV], const double* ob, const double* sh, double qr, double ms,
                                              double td, double pp, double A, double f_tdp)
 {
@@ -96,14 +98,14 @@ __device__ __forceinline__ void gof_chem_day(GofAcc (&acc)[GOF_NV], const double
         SS = (ms / qr) / A; TDP = (td / qr) / A; PP = (pp / qr) / A;
     }
     const double TP = TDP + PP, SRP = TDP * f_tdp;
-    if (ob[0] == ob[0]) gof_add(acc[SIMPLYP_GOF_SS], ob[0], ob[5], SS, sh[1], sh[7]);
-    if (ob[1] == ob[1]) gof_add(acc[SIMPLYP_GOF_TDP], ob[1], ob[6], TDP, sh[2], sh[8]);
-    if (ob[2] == ob[2]) gof_add(acc[SIMPLYP_GOF_PP], ob[2], ob[7], PP, sh[3], sh[9]);
-    if (ob[3] == ob[3]) gof_add(acc[SIMPLYP_GOF_TP], ob[3], ob[8], TP, sh[4], sh[10]);
-    if (ob[4] == ob[4]) gof_add(acc[SIMPLYP_GOF_SRP], ob[4], ob[9], SRP, sh[5], sh[11]);
+    if (ob[0] == ob[0]) gof_add(acc[SIMPLYP_GOF_SS], ob[0], ob[5], ob[10], ob[15], SS, sh[1]);
+    if (ob[1] == ob[1]) gof_add(acc[SIMPLYP_GOF_TDP], ob[1], ob[6], ob[11], ob[16], TDP, sh[2]);
+    if (ob[2] == ob[2]) gof_add(acc[SIMPLYP_GOF_PP], ob[2], ob[7], ob[12], ob[17], PP, sh[3]);
+    if (ob[3] == ob[3]) gof_add(acc[SIMPLYP_GOF_TP], ob[3], ob[8], ob[13], ob[18], TP, sh[4]);
+    if (ob[4] == ob[4]) gof_add(acc[SIMPLYP_GOF_SRP], ob[4], ob[9], ob[14], ob[19], SRP, sh[5]);
 }
 
-// PART 0: discharge days (reads the Qr row only, 13 running sums); PART 1: chemistry days (Qr + three flux rows, 65
+// PART 0: discharge days (reads the Qr row only, 14 running sums); PART 1: chemistry days (Qr + three flux rows, 70
 // running sums).  Two instantiations so that the discharge pass -- most of the bytes -- is not held to the register
 // budget of the chemistry pass.
 template <int PART>
@@ -127,7 +129,7 @@ __global__ __launch_bounds__(64) void simplyp_gof_partial_kernel(const GofArgs g
         for (int j = 0; j < GOF_NACC; ++j) acc.a[j] = 0.0;
         const long long k0 = g.q_ptr[r], n = g.q_ptr[r + 1] - k0;
         const int kb = (int)(k0 + n * chunk / g.n_chunks_q), ke = (int)(k0 + n * (chunk + 1) / g.n_chunks_q);
-        const double co = sh[0], clo = sh[6];
+        const double co = sh[0];
         const double q_scale = g.a_catch ? A * 1000 / 86400 : 1.0;      // Q = Qr*A*1000/86400 (model.py:784) with the constants folded: 2 ulp
         // batches of GOF_BATCH_Q days: all row loads are issued before the first is consumed (one wave keeps 8 x 512 B
         // in flight; a load-use pair per iteration leaves HBM waiting on latency)
@@ -138,10 +140,12 @@ __global__ __launch_bounds__(64) void simplyp_gof_partial_kernel(const GofArgs g
             for (int j = 0; j < GOF_BATCH_Q; ++j) qv[j] = qr_col[(size_t)g.q_day[k + j] * day_stride];
 #pragma unroll
             for (int j = 0; j < GOF_BATCH_Q; ++j)
-                gof_add(acc, g.q_obs[2 * (k + j)], g.q_obs[2 * (k + j) + 1], qv[j] * q_scale, co, clo);
+                gof_add(acc, g.q_obs[4 * (k + j)], g.q_obs[4 * (k + j) + 1], g.q_obs[4 * (k + j) + 2], g.q_obs[4 * (k + j) + 3],
+                        qv[j] * q_scale, co);
         }
         for (; k < ke; ++k)
-            gof_add(acc, g.q_obs[2 * k], g.q_obs[2 * k + 1], qr_col[(size_t)g.q_day[k] * day_stride] * q_scale, co, clo);
+            gof_add(acc, g.q_obs[4 * k], g.q_obs[4 * k + 1], g.q_obs[4 * k + 2], g.q_obs[4 * k + 3],
+                    qr_col[(size_t)g.q_day[k] * day_stride] * q_scale, co);
 #pragma unroll
         for (int j = 0; j < GOF_NACC; ++j) p[(size_t)(SIMPLYP_GOF_Q * GOF_NACC + j) * g.E] = acc.a[j];
     } else {
@@ -166,11 +170,11 @@ __global__ __launch_bounds__(64) void simplyp_gof_partial_kernel(const GofArgs g
             }
 #pragma unroll
             for (int j = 0; j < GOF_BATCH_C; ++j)
-                gof_chem_day(acc, g.c_obs + (size_t)(k + j) * 10, sh, qv[j], mv[j], tv[j], pv[j], A, f_tdp);
+                gof_chem_day(acc, g.c_obs + (size_t)(k + j) * 20, sh, qv[j], mv[j], tv[j], pv[j], A, f_tdp);
         }
         for (; k < ke; ++k) {
             const size_t off = (size_t)g.c_day[k] * day_stride;
-            gof_chem_day(acc, g.c_obs + (size_t)k * 10, sh, qr_col[off], ms_col[off], td_col[off], pp_col[off], A, f_tdp);
+            gof_chem_day(acc, g.c_obs + (size_t)k * 20, sh, qr_col[off], ms_col[off], td_col[off], pp_col[off], A, f_tdp);
         }
 #pragma unroll
         for (int v = 1; v < GOF_NV; ++v)
@@ -203,7 +207,7 @@ __global__ __launch_bounds__(64) void simplyp_gof_finish_kernel(const GofArgs g)
         const double var_o = a[2] - a[1] * a[1] / n;             // sum (o - mean o)^2 over the paired days
         const double var_s = a[4] - a[3] * a[3] / n;
         const double cov = a[5] - a[1] * a[3] / n;
-        const double var_lo = a[9] - a[8] * a[8] / n;
+        const double var_lo = a[9] - a[8] * a[8] / a[13];        // a[13] = n unless an observation is negative
         st[SIMPLYP_GOFSTAT_NSE] = 1.0 - a[7] / var_o;                                    // :441
         st[SIMPLYP_GOFSTAT_LOG_NSE] = 1.0 - a[10] / var_lo;                              // :442-443
         st[SIMPLYP_GOFSTAT_R2] = cov * cov / (var_o * var_s);                            // :446-447

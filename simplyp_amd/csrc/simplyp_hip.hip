@@ -52,7 +52,7 @@ struct simplyp_ctx {
     DeviceBuf balance;        // [E] uint32 pilot counts + [E] int32 permutation
     DeviceBuf sorted_params;  // slot-ordered copies of member_params, reach_params, forcing_of_member
     DeviceBuf gof_lists;      // goodness-of-fit day lists, observations, shifts (simplyp_gof)
-    DeviceBuf gof_partial;    // [n_chunks][R][78][E] partial sums
+    DeviceBuf gof_partial;    // [n_chunks][R][84][E] partial sums
     DeviceBuf quant;          // simplyp_quantiles: 2 x int32 (members used, sweeps) | [E] uint8 include mask in column order
     DeviceBuf tquant;         // simplyp_time_quantiles: sweeps, rows read | day lists, ranks, output reaches
     DeviceBuf pred;           // simplyp_predictive_*: [R] int32 output reaches (256-byte slot) | a chunk of days [n_series][days][R][E]
@@ -1528,31 +1528,42 @@ static int gof_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mas
         const double* ob = obs + (size_t)r * NV * D;
         bool use[NV];
         for (int v = 0; v < NV; ++v) {
-            double n = 0.0, so = 0.0, slo = 0.0;
+            double n = 0.0, so = 0.0, slo = 0.0, nlo = 0.0;
             for (int d = 0; d < D; ++d) {
                 const double o = ob[(size_t)v * D + d];
-                if (o == o) { n += 1.0; so += o; slo += std::log(o); }
+                if (o == o) {
+                    n += 1.0; so += o;
+                    const double l = std::log(o);
+                    if (l == l) { slo += l; nlo += 1.0; }        // a negative observation has no log: skipped, as gof_add skips it
+                }
             }
             use[v] = n > 10.0;                                   // visualise_results.py:430
             n_obs[(size_t)r * NV + v] = n;
             shift[(size_t)r * 12 + v] = use[v] ? so / n : 0.0;
-            // the log shift is only a conditioning constant: keep it finite when an observation is <= 0
-            const double ml = use[v] ? slo / n : 0.0;
+            // the log shift is only a conditioning constant: keep it finite when an observation is 0
+            const double ml = use[v] && nlo > 0.0 ? slo / nlo : 0.0;
             shift[(size_t)r * 12 + 6 + v] = std::isfinite(ml) ? ml : 0.0;
         }
+        // per observation: the value, its log, the log less its shift and 1 -- or 0 and 0 when there is no log (obs < 0)
+        auto put_obs = [&](double o, int v, double* at, int stride) {
+            const double l = std::log(o);
+            at[0] = o; at[stride] = l;
+            at[2 * stride] = l == l ? l - shift[(size_t)r * 12 + 6 + v] : 0.0;
+            at[3 * stride] = l == l ? 1.0 : 0.0;
+        };
         for (int d = 0; d < D; ++d) {
             const double q = ob[d];
-            if (use[0] && q == q) { q_day.push_back(d); q_obs.push_back(q); q_obs.push_back(std::log(q)); }
+            if (use[0] && q == q) { double row[4]; put_obs(q, 0, row, 1); q_day.push_back(d); q_obs.insert(q_obs.end(), row, row + 4); }
             bool any = false;
-            double row[10];
+            double row[20];
             for (int v = 1; v < NV; ++v) {
                 const double o = ob[(size_t)v * D + d];
                 const bool have = use[v] && o == o;
-                row[v - 1] = have ? o : nan;
-                row[v + 4] = have ? std::log(o) : nan;
+                if (have) put_obs(o, v, row + v - 1, 5);
+                else for (int j = 0; j < 4; ++j) row[v - 1 + 5 * j] = nan;
                 any = any || have;
             }
-            if (any) { c_day.push_back(d); c_obs.insert(c_obs.end(), row, row + 10); }
+            if (any) { c_day.push_back(d); c_obs.insert(c_obs.end(), row, row + 20); }
         }
         q_ptr[r + 1] = (int32_t)q_day.size();
         c_ptr[r + 1] = (int32_t)c_day.size();
@@ -2740,7 +2751,7 @@ int simplyp_memcpy_d2h(simplyp_ctx* ctx, void* dst, const void* src, int64_t byt
 int simplyp_eval_units(simplyp_ctx* ctx, int32_t which, int32_t n, const double* in, double* out)
 {
     if (!ctx) return SIMPLYP_ERR_ARG;
-    if (which < 0 || which > 1 || n < 0 || (n > 0 && (!in || !out))) return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_eval_units: bad arguments");
+    if (which < 0 || which > 5 || n < 0 || (n > 0 && (!in || !out))) return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_eval_units: bad arguments");
     if (n == 0) return SIMPLYP_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipLaunchKernelGGL(simplyp::eval_units_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, (int)which, (int)n, in, out);

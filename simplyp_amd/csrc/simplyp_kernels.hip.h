@@ -122,7 +122,11 @@ __device__ __forceinline__ void sp_exp2(double x0, double x1, double& r0, double
     r0 = rs[0]; r1 = rs[1];
 }
 
-// 1/x: hardware seed + two Newton steps (full double precision for normal x).
+// 1/x: hardware seed + two Newton steps.  Faithfully rounded for normal x (< 1 ulp: the error before the last rounding is about
+// e0^4, e0 = the seed's 4.5e-8), and correctly rounded except where the exact reciprocal lies within that of a rounding boundary:
+// on the device all of 50 000 random mantissas are correctly rounded and, of the 2000 mantissas next to 1 and the 2000 next to 2,
+// the six x = 2 - i 2^-52, i = 3, 5, ..., 13 (any exponent) are not -- their reciprocals, 1/2 + i 2^-54 + i^2 2^-107 + ..., sit
+// i^2 2^-54 ulp above a midpoint and come out rounded down, 0.5 ulp off (tests/test_gpu_elementary.py::test_reciprocals).
 __device__ __forceinline__ double sp_rcp(double x)
 {
     double r = __builtin_amdgcn_rcp(x);
@@ -134,7 +138,8 @@ __device__ __forceinline__ double sp_rcp(double x)
 // log(x) for normal x > 0.  x = 2^k (1+f), sqrt(1/2) < 1+f <= sqrt(2); s = f/(2+f);
 // log(1+f) = f - hfsq + s (hfsq + R(s^2)), R = the classic degree-7 even minimax polynomial
 // (fdlibm e_log.c coefficients Lg1..Lg7).
-// One Newton step on v_rcp_f64 (raw: 4.6e-8 relative, one step: 2e-15, two: correctly rounded -- tools/micro/rcp_accuracy.hip).
+// One Newton step on v_rcp_f64 (raw: 4.6e-8 relative, one step: e0^2 + 2^-53 ~ 2e-15, two: faithful, see sp_rcp --
+// tools/micro/rcp_accuracy.hip, tests/test_gpu_elementary.py).
 // Enough for the derivatives of the auxiliary states, which are re-evaluated exactly every few steps anyway.
 __device__ __forceinline__ double sp_rcp1(double x)
 {
@@ -1336,8 +1341,9 @@ __device__ __forceinline__ int nc_type_of(double f_NC_A, double f_NC_S)     // m
 // discretized_soilP (model.py:39-56) followed by the >= 0 clamps (:696-699) and the soil-water concentration (:702-703), in two
 // phases around the day boundary's one group of exponentials (sp_expn): soil_p_rate gives b (:43), whose exp(-b) the caller
 // evaluates together with the day's other exponentials; soil_p_update does the rest.  The reference's nine divisions per call
-// (by b, by Vs, by b*Vs) share two reciprocals, 1/Vs and 1/b (sp_rcp: hardware seed + two Newton steps, correctly rounded on
-// every sample tried, tools/micro/rcp_accuracy.hip): a * (1/b) instead of a / b differs in the last bit at most -- eleven orders
+// (by b, by Vs, by b*Vs) share two reciprocals, 1/Vs and 1/b (sp_rcp: hardware seed + two Newton steps, faithfully rounded and
+// correctly rounded on every random sample tried, tests/test_gpu_elementary.py): a * (1/b) instead of a / b differs by an ulp or
+// two at most -- eleven orders
 // of magnitude below the parity bar -- and an IEEE division is ~12 instructions on this chip, a quarter of the day-boundary
 // code before round 3.  Vs == 0 (never met with water in the soil box, but the reference defines it): b = inf there, so the
 // reference gets TDPs = 0 + (TDPs - 0) * 0, sorp = 0 (:50), Plab unchanged and conc_TDPs = 0/0 = NaN; the reciprocals of 0 are
@@ -2043,6 +2049,12 @@ __global__ void gather_columns_kernel(const T* __restrict__ src, T* __restrict__
 // :702-703) to the vectors the unmodified reference functions produced, Vs == 0 included.
 //   which 0: in [n][2] = x, threshold           -> out [n][2] = f_x by gate() (end-of-day flows), f_x by the fused form of SysAug::f
 //   which 1: in [n][10] = P_netInput, A_catch, Kf, Msoil, EPC0, Qs, Qq, Vs, TDPs, Plab  -> out [n][3] = TDPs, Plab, conc_TDPs
+// and the fp64 elementary functions themselves, the very inline functions every kernel calls (tests/test_gpu_elementary.py):
+//   which 2: in [n][1] = x     -> out [n][4] = sp_exp(x); slot 1 of sp_exp2(x', x); slot 0 and slot 6 of two sp_expn<7> whose other
+//                                              slots hold the arguments x' of the rows that follow (cyclically)
+//   which 3: in [n][1] = x     -> out [n][1] = sp_log(x)
+//   which 4: in [n][1] = x     -> out [n][3] = sp_rcp_fast(x) (the raw hardware seed), sp_rcp1(x), sp_rcp(x)
+//   which 5: in [n][2] = q, b  -> out [n][1] = q**b as rhs() forms it: sp_exp(b * sp_log(q))
 __global__ void eval_units_kernel(int which, int n, const double* __restrict__ in, double* __restrict__ out)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2054,6 +2066,25 @@ __global__ void eval_units_kernel(int which, int n, const double* __restrict__ i
         double s = __builtin_fma(x, inv_d, -th * inv_d);                           // SysAug::f: s = fma(Vs, inv_d, s0), s0 = -fc inv_d
         s = __builtin_fmin(__builtin_fmax(s, 0.0), 1.0);
         out[2 * i + 1] = (s * s) * __builtin_fma(-2.0, s, 3.0);
+    } else if (which == 2) {
+        double xs[7], rs[7], e1, e2;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) xs[j] = in[(i + j) % n];                       // xs[0] = this row's x, the rest are neighbours'
+        out[4 * i] = sp_exp(xs[0]);
+        sp_exp2(xs[1], xs[0], e1, e2);
+        out[4 * i + 1] = e2;
+        sp_expn<7>(xs, rs);
+        out[4 * i + 2] = rs[0];
+        xs[0] = xs[6]; xs[6] = in[i];
+        sp_expn<7>(xs, rs);
+        out[4 * i + 3] = rs[6];
+    } else if (which == 3) {
+        out[i] = sp_log(in[i]);
+    } else if (which == 4) {
+        const double x = in[i];
+        out[3 * i] = sp_rcp_fast(x); out[3 * i + 1] = sp_rcp1(x); out[3 * i + 2] = sp_rcp(x);
+    } else if (which == 5) {
+        out[i] = sp_exp(in[2 * i + 1] * sp_log(in[2 * i]));
     } else {
         const double* a = in + 10 * (size_t)i;
         const double aP = a[0] * a[1] * 100.0 / 365.;                              // run_slot: aP_A

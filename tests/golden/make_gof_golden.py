@@ -12,6 +12,8 @@ run period exactly as the reference's read_input_data does (inputs.py:118-152).
 
 Also records, for a few perturbed simulated series (sim * fixed smooth factors; no reference model run needed: the
 statistic is a pure function of the two series), the same table -- so the restatement is pinned away from one point.
+One case negates an observation of Q and of SS: what the reference makes of a negative observation (its log is NaN and drops out
+of both sums of log NSE) is recorded, not inferred.
 
 Output: gof_golden.json.   Usage: python tests/golden/make_gof_golden.py
 """
@@ -73,7 +75,7 @@ def main():
                 sim[1]['Q_cumecs'] = sim[1]['Q_cumecs'] * f['Q']
                 for c in ('SS_mgl', 'PP_mgl', 'TP_mgl', 'TDP_mgl', 'SRP_mgl'):
                     sim[1][c] = sim[1][c] * f['C']
-                tab = gof(p_SU, sim, obs)
+                tab = gof(p_SU, sim, helpers.gof_case_observations(obs, f))
                 out['%s/%s/%s' % (name, label, case)] = dict(
                     index=list(tab.index), columns=list(tab.columns),
                     values=[[float(v) for v in row] for row in tab.to_numpy(dtype=float)])

@@ -112,7 +112,18 @@ def gof_case_factors(index):
     t = np.arange(len(index)) / 365.25
     return {'base': dict(Q=1.0, C=1.0),
             'wet': dict(Q=1.25 + 0.1 * np.sin(2 * np.pi * t), C=0.8),
-            'dry': dict(Q=0.7, C=1.4 + 0.3 * np.cos(2 * np.pi * t / 3.0))}
+            'dry': dict(Q=0.7, C=1.4 + 0.3 * np.cos(2 * np.pi * t / 3.0)),
+            # one NEGATIVE observation of Q and of SS (the k-th of each): np.log of it is NaN, which the reference's sums skip
+            'negobs': dict(Q=1.0, C=1.0, negate=dict(Q=17, SS=9))}
+
+
+def gof_case_observations(obs, factors):
+    """The observations of a case of gof_case_factors: a copy of obs_dict with the case's edits applied."""
+    out = {k: df.copy() for k, df in obs.items()}
+    for v, k in factors.get('negate', {}).items():
+        day = out[1][v].dropna().index[k]
+        out[1].loc[day, v] = -out[1].loc[day, v]
+    return out
 
 
 # Two valid integrations at the default solver's working tolerance (kernel and oracle mirror the same step rule, but an

@@ -24,7 +24,7 @@ def case_inputs(key):
     sim['Q_cumecs'] = sim['Q_cumecs'] * f['Q']
     for c in ('SS_mgl', 'PP_mgl', 'TP_mgl', 'TDP_mgl', 'SRP_mgl'):
         sim[c] = sim[c] * f['C']
-    return sim, obs
+    return sim, helpers.gof_case_observations(obs, f)
 
 
 @pytest.mark.parametrize('key', sorted(GOLD))
