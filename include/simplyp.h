@@ -40,7 +40,9 @@ extern "C" {
  * 17 still with simplyp_sobol_design, simplyp_sobol_indices and simplyp_sobol_info: two more entry points, one more info struct,
  * additive once more.
  * 17 still with simplyp_pf_loglik, simplyp_pf_weights, simplyp_pf_resample, simplyp_gather_members, simplyp_pf_jitter and
- * simplyp_pf_info: five more entry points, one more info struct, nothing existing changes. */
+ * simplyp_pf_info: five more entry points, one more info struct, nothing existing changes.
+ * 17 still with simplyp_weighted_quantiles, simplyp_predictive_bands_weighted and simplyp_wq_info: two more entry points, one more
+ * info struct; the unweighted entries and everything they return are untouched. */
 #define SIMPLYP_ABI_VERSION 17
 
 typedef enum {
@@ -716,6 +718,65 @@ int simplyp_predictive_bands(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_
                              const double* err_m, uint64_t seed, int32_t day0,
                              const double* q /* host [K] */, int32_t K,
                              double* order_stats, simplyp_pred_info* info);
+
+/* ---- weighted bands: exact quantiles across the members under the particle filter's integer weights -- the forecast band of a
+ * filter that does not resample every window, and the likelihood-weighted (GLUE) band of a Monte-Carlo ensemble.
+ *
+ * The rule, for one row over its member axis (simplyp_amd/csrc/simplyp_weighted.h and simplyp_amd/weighted.py state it too):
+ * weights are the integers simplyp_pf_weights writes, q_i = floor(w_i 2^40), 0 <= q_i <= 2^40.  A member takes part iff its
+ * include flag is set and q_i > 0; T is the sum of the participating weights (<= 2^62 with E <= 2^22).  The members are ordered
+ * as simplyp_quantiles orders them (NaN after +inf; -0.0 and +0.0 equal), C_i is the inclusive running sum of the weights in
+ * that order, and for a probability p the threshold is t = max(1, ceil(p T)), formed exactly (p = m 2^e, m < 2^53: m T fits
+ * 128 bits).  The result is the value of the first member with C_i >= t: the order statistic of rank t - 1 (zero-based) of the
+ * multiset in which member i occurs q_i times -- numpy's method='inverted_cdf' with weights=, NOT the 'linear' rule of the
+ * unweighted entries: one value per probability, nothing to interpolate.  Everything is integer arithmetic, so every output is
+ * an element of its row and every correct implementation returns the same one, bit for bit (which of -0.0 / +0.0 is free).
+ * T == 0 (nobody takes part): every output is NaN and the call succeeds. ---------------------------------------------------- */
+typedef struct {
+    double   kernel_ms;    /* all launches of the call, HIP events on the context's stream                      */
+    int64_t  bytes_table;  /* bytes of the rows selected from: n_rows * E * 8                                   */
+    uint64_t T;            /* the sum of the participating weights                                              */
+    int32_t  n_used;       /* members that took part: include set and weight > 0                                */
+    int32_t  n_passes;     /* sweeps over a row the selection made (diagnostic)                                 */
+} simplyp_wq_info;
+
+/*
+ * simplyp_weighted_quantiles -- the weighted twin of simplyp_quantiles: same tables, same member_of_slot / include.
+ *   E, n_rows       1 <= E <= 2^22; n_rows == 0 succeeds and launches nothing
+ *   weights         device  [E] uint64 in MEMBER order (looked up through member_of_slot like include), each <= 2^40
+ *   q, K            HOST    [K] probabilities in [0, 1], 1 <= K <= 16
+ *   order_stats     device  [K][n_rows]
+ *   info            host    may be NULL
+ * One launch forms the weights in column order, T, n_used and the count of weights above 2^40, read back once; then rows of
+ * <= 2048 members are sorted in LDS as (key, weight) pairs and longer rows go through a radix select on weights.  Device
+ * workspace is 8 E + 24 bytes.  Synchronous, on the context's stream.  SIMPLYP_ERR_ARG with nothing launched for E outside
+ * 1..2^22, n_rows < 0, NULL table / weights / q / order_stats, K outside 1..16, a q outside [0, 1] or NaN; SIMPLYP_ERR_ARG with
+ * order_stats unwritten for a weight above 2^40.
+ */
+int simplyp_weighted_quantiles(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double* table,
+                               const int32_t* member_of_slot, const uint8_t* include,
+                               const uint64_t* weights /* device [E], member order */,
+                               const double* q /* host [K] */, int32_t K,
+                               double* order_stats /* device [K][n_rows] */,
+                               simplyp_wq_info* info);
+
+/*
+ * simplyp_predictive_bands_weighted -- simplyp_predictive_bands under weights: the same arguments, checks, generation kernel
+ * and chunks (SIMPLYP_PRED_CHUNK_DAYS included); each chunk is selected with simplyp_weighted_quantiles' kernels, the weights
+ * are prepared once per call, and the result does not depend on the chunk length, bit for bit.
+ *   weights         device  [E] uint64 in MEMBER order, each <= 2^40
+ *   order_stats     device  [K][n_series][D][n_out_reaches]
+ * SIMPLYP_ERR_ARG as for simplyp_predictive_bands and simplyp_weighted_quantiles.
+ */
+int simplyp_predictive_bands_weighted(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                                      const int32_t* out_reaches, int32_t n_out_reaches,
+                                      const double* out, const int32_t* member_of_slot, const uint8_t* include,
+                                      const double* f_tdp, const double* reach_params,
+                                      const int32_t* series /* host [n_series] */, int32_t n_series,
+                                      const double* err_m, uint64_t seed, int32_t day0,
+                                      const double* q /* host [K] */, int32_t K,
+                                      const uint64_t* weights /* device [E], member order */,
+                                      double* order_stats, simplyp_wq_info* info);
 
 /* ---- sampling the posterior: the affine-invariant ensemble sampler of the reference's calibration notebook
  * (Development/2016/MCMC.ipynb, cell 10: emcee.EnsembleSampler(n_walk, n_dim, log_posterior).run_mcmc(start, n_steps)), the stretch

@@ -72,6 +72,14 @@ class QuantileInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class WqInfo(C.Structure):
+    """simplyp_wq_info of include/simplyp.h."""
+    _fields_ = [('kernel_ms', C.c_double), ('bytes_table', C.c_int64), ('T', C.c_uint64), ('n_used', C.c_int32), ('n_passes', C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class TqInfo(C.Structure):
     """simplyp_tq_info of include/simplyp.h."""
     _fields_ = [('kernel_ms', C.c_double), ('bytes_read', C.c_int64), ('n_sweeps', C.c_int32), ('n_periods', C.c_int32)]

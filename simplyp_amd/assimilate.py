@@ -46,7 +46,7 @@ def _rejuvenation(rejuvenate, delta, names, lo, hi):
 def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, priors, variables=('Q',), error_m=None,
                n_particles=None, window=30, start=None, initial_state=None, seed=0, resample_threshold=1.0, rejuvenate='liu_west',
                delta=0.98, quantiles=None, forecast_series=None, record=False, state=None, step_len=1., solver=None, device=0,
-               out_reaches=None):
+               out_reaches=None, forecast_weighted=False):
     """Update the parameter distribution and the model state of ``n_particles`` particles window by window as the observations
     of ``obs_dict`` arrive (sequential importance resampling), every step on the device.
 
@@ -72,7 +72,12 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
     ``quantiles``: per-window forecast bands of ``forecast_series`` (``df_R`` names or columns among %s; default: the series of
     ``variables``) through ``Engine.predictive_bands``, taken BEFORE the window's weighting: the parameter-only band, and the
     overall band of the series whose ``m`` the filter knows.  The bands are unweighted, so they are right only when the
-    particles entering every window are equally weighted: ``quantiles`` with ``resample_threshold < 1`` is a ``ValueError``.
+    particles entering every window are equally weighted: ``quantiles`` with ``resample_threshold < 1`` is a ``ValueError``
+    unless ``forecast_weighted=True``.  Then a window's bands are weighted by the particles' integer weights as they ENTER the
+    window -- the ``q`` of the previous ``pf_weights`` call, all equal at the start and right after a resampling --, selected by
+    ``Engine.predictive_bands(weights=)`` under numpy's ``method='inverted_cdf'`` rule (``simplyp_amd.weighted``; not the
+    ``'linear'`` rule of the unweighted bands); any ``resample_threshold`` is allowed and ``forecast['rule']`` is
+    ``'inverted_cdf'``.
     ``devices=[...]`` is not offered: resampling spans the whole ensemble.
 
     ``state``: the ``'state'`` of an earlier result; ``met_df`` then covers the dates that follow, and the filter continues bit
@@ -112,9 +117,9 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
     known_m = [abi.TQ_DERIVED_SERIES[abi.GOF_VARS.index(v)] for v in variables]
     fc_names = fc_ids = None
     if quantiles is not None:
-        if float(resample_threshold) < 1.0:
+        if float(resample_threshold) < 1.0 and not forecast_weighted:
             raise ValueError("quantiles needs resample_threshold >= 1: the forecast bands are unweighted, which is right only for "
-                             "equally weighted particles")
+                             "equally weighted particles (or pass forecast_weighted=True for bands under the particles' weights)")
         quantiles = [float(x) for x in np.atleast_1d(quantiles)]
         if not 1 <= len(quantiles) <= 16 or not all(0.0 <= x <= 1.0 for x in quantiles):
             raise ValueError("quantiles must be 1 to 16 probabilities in [0, 1]")
@@ -199,14 +204,18 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
             kms['run'].append(rstats['kernel_ms'])
             pilot_ms.append(rstats['pilot_ms'])
             tkw = dict(f_tdp=ft_d, reach_params=rp_d, out_reaches=hs['oreach'])
-            if quantiles is not None:                                  # before the weighting: the particles are equally weighted
+            if quantiles is not None:                                  # before the weighting
                 pkw = dict(seed=seed, day0=day0 + d_lo, **tkw)
-                lo_b, up_b, binfo = eng.predictive_bands(table_d, mask, quantiles, fc_ids, **pkw)
-                bands_po.append(engine.interpolate_quantiles(host(lo_b), host(up_b), quantiles, binfo['n_used']))
+
+                def forecast_band(ids, **kw):
+                    if forecast_weighted:                              # under the weights the particles enter the window with
+                        return host(eng.predictive_bands(table_d, mask, quantiles, ids, weights=q_d, **dict(pkw, **kw))[0])
+                    lo_b, up_b, binfo = eng.predictive_bands(table_d, mask, quantiles, ids, **dict(pkw, **kw))
+                    return engine.interpolate_quantiles(host(lo_b), host(up_b), quantiles, binfo['n_used'])
+                bands_po.append(forecast_band(fc_ids))
                 if ov_at:
                     em = m_rows([abi.GOF_VARS.index(variables[known_m.index(fc_names[i])]) for i in ov_at])
-                    lo_b, up_b, binfo = eng.predictive_bands(table_d, mask, quantiles, [fc_ids[i] for i in ov_at], err_m=em, **pkw)
-                    bands_ov.append(engine.interpolate_quantiles(host(lo_b), host(up_b), quantiles, binfo['n_used']))
+                    bands_ov.append(forecast_band([fc_ids[i] for i in ov_at], err_m=em))
             linfo = eng.pf_loglik(table_d, mask, hs['obs'][:, :, d_lo:d_hi], pairs, m_rows([v for v, _ in pairs]), lw_d, status=status_d,
                                   inc=inc_d, accumulate=True, **tkw)
             w_d, q_d, winfo = eng.pf_weights(lw_d, w_d, q_d)
@@ -239,6 +248,8 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
                 state_d, mp_d, rp_d, ft_d, theta_d = moved
                 lw_d.zero_()
                 lm_prev = 0.0
+                if forecast_weighted:                                  # the next window's particles enter it equally weighted
+                    w_d, q_d, _ = eng.pf_weights(lw_d, w_d, q_d)
                 if move is not None:
                     if move[0] == 'liu_west':
                         a = move[1]
@@ -274,6 +285,8 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
         res['forecast'] = dict(q=list(quantiles), series=list(fc_names), param_only=np.concatenate(bands_po, axis=2),
                                overall_series=[fc_names[i] for i in ov_at],
                                overall=np.concatenate(bands_ov, axis=2) if ov_at else None, day0=day0)
+        if forecast_weighted:
+            res['forecast']['rule'] = 'inverted_cdf'
     if record:
         res.update(rec)
     return res

@@ -21,6 +21,7 @@
 #include "simplyp_gof.hip.h"
 #include "simplyp_waterbody.hip.h"
 #include "simplyp_quantile.hip.h"
+#include "simplyp_weighted_quantile.hip.h"
 #include "simplyp_time_quantile.hip.h"
 #include "simplyp_predictive.hip.h"
 #include "simplyp_mcmc.hip.h"
@@ -29,6 +30,7 @@
 #include "simplyp_particle.hip.h"
 #include "simplyp_pack_stream.h"
 #include "simplyp_table.h"
+#include "simplyp_weighted.h"
 
 namespace {
 
@@ -54,6 +56,7 @@ struct simplyp_ctx {
     DeviceBuf gof_lists;      // goodness-of-fit day lists, observations, shifts (simplyp_gof)
     DeviceBuf gof_partial;    // [n_chunks][R][84][E] partial sums
     DeviceBuf quant;          // simplyp_quantiles: 2 x int32 (members used, sweeps) | [E] uint8 include mask in column order
+    DeviceBuf wquant;         // simplyp_weighted_quantiles: WqPrepared (T, members used, bad weights, sweeps) | [E] uint64 weights in column order
     DeviceBuf tquant;         // simplyp_time_quantiles: sweeps, rows read | day lists, ranks, output reaches
     DeviceBuf pred;           // simplyp_predictive_*: [R] int32 output reaches (256-byte slot) | a chunk of days [n_series][days][R][E]
     DeviceBuf mcmc;           // simplyp_mcmc_*: 4 x uint32 (inside, accepted, NaN)
@@ -989,6 +992,7 @@ void simplyp_ctx_destroy(simplyp_ctx* ctx)
     if (ctx->gof_lists.ptr) (void)hipFree(ctx->gof_lists.ptr);
     if (ctx->gof_partial.ptr) (void)hipFree(ctx->gof_partial.ptr);
     if (ctx->quant.ptr) (void)hipFree(ctx->quant.ptr);
+    if (ctx->wquant.ptr) (void)hipFree(ctx->wquant.ptr);
     if (ctx->tquant.ptr) (void)hipFree(ctx->tquant.ptr);
     if (ctx->pred.ptr) (void)hipFree(ctx->pred.ptr);
     if (ctx->mcmc.ptr) (void)hipFree(ctx->mcmc.ptr);
@@ -1898,6 +1902,78 @@ int simplyp_quantiles(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double*
     SIMPLYP_GUARD(ctx, quantiles_impl(ctx, E, n_rows, table, member_of_slot, include, q, K, order_stats, info))
 }
 
+// ---- weighted bands (simplyp_weighted.h states the rule, simplyp_weighted_quantile.hip.h selects) -----------------------------
+// What a weighted selection decides once per call: the weights in the table's column order, their sum, who takes part
+// (context workspace: WqPrepared | [E] uint64) and, from the sum read back, every probability's exact threshold.  Fills g.E,
+// g.w_slot, g.K, g.thr and g.n_passes; thr stays unset when T == 0.  A weight above 2^40 is SIMPLYP_ERR_ARG.
+static int weighted_prepare(simplyp_ctx* ctx, const char* me, int32_t E, const int32_t* member_of_slot, const uint8_t* include,
+                            const uint64_t* weights, const double* q, int32_t K, simplyp::WQuantileArgs& g, simplyp::WqPrepared& got)
+{
+    if (int rc = ensure(ctx, ctx->wquant, sizeof(simplyp::WqPrepared) + (size_t)E * sizeof(uint64_t))) return rc;
+    simplyp::WqPrepared* d_res = (simplyp::WqPrepared*)ctx->wquant.ptr;
+    unsigned long long* d_w = (unsigned long long*)((char*)ctx->wquant.ptr + sizeof(simplyp::WqPrepared));
+    hipLaunchKernelGGL(simplyp::weighted_prepare_kernel, dim3(1), dim3(1024), 0, ctx->stream, (int)E, (const unsigned long long*)weights,
+                       include, member_of_slot, d_w, d_res);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(&got, d_res, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    TABLE_TRY(ctx, simplyp_weighted::check_weights(me, got.n_bad, msg));
+    g.E = E; g.w_slot = d_w; g.K = K; g.n_passes = &d_res->n_passes;
+    for (int k = 0; k < K && got.T > 0; ++k) g.thr[k] = simplyp_weighted::weighted_threshold(q[k], got.T);
+    return SIMPLYP_OK;
+}
+
+// The weighted selection of g.n_rows rows of g.table into rows g.out_row0... of g.order_stats.
+static int weighted_launch(simplyp_ctx* ctx, const simplyp::WQuantileArgs& g, const char* me)
+{
+    if (g.E <= simplyp::WQSORT_MAX) {
+        int P = 2;
+        while (P < g.E) P <<= 1;
+        const long long rows_per_block = simplyp::WQSORT_MAX / P;
+        const long long blocks = (g.n_rows + rows_per_block - 1) / rows_per_block;
+        if (blocks > 0x7FFFFFFFLL) return fail(ctx, SIMPLYP_ERR_ARG, "%s: too many rows for one call (%lld)", me, g.n_rows);
+        hipLaunchKernelGGL(simplyp::weighted_sort_kernel, dim3((unsigned)blocks), dim3(simplyp::WQSORT_THREADS), 0, ctx->stream, g, P);
+    } else {
+        const unsigned blocks = (unsigned)std::min<long long>(g.n_rows, 65536);
+        hipLaunchKernelGGL(simplyp::weighted_select_kernel, dim3(blocks), dim3(simplyp::QSEL_THREADS), 0, ctx->stream, g);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return SIMPLYP_OK;
+}
+
+static int weighted_quantiles_impl(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double* table,
+                                   const int32_t* member_of_slot, const uint8_t* include, const uint64_t* weights,
+                                   const double* q, int32_t K, double* order_stats, simplyp_wq_info* info)
+{
+    const char* me = "simplyp_weighted_quantiles";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    TABLE_TRY(ctx, simplyp_weighted::check_table(me, E, n_rows, table, weights, q, K, order_stats, msg));
+    if (info) { info->kernel_ms = 0.0; info->bytes_table = n_rows * (int64_t)E * 8; info->T = 0; info->n_used = 0; info->n_passes = 0; }
+    if (n_rows == 0) return SIMPLYP_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = timed_begin(ctx)) return rc;
+    simplyp::WQuantileArgs g{};
+    simplyp::WqPrepared got{};
+    if (int rc = weighted_prepare(ctx, me, E, member_of_slot, include, weights, q, K, g, got)) return rc;
+    if (got.T == 0) {
+        if (int rc = fill_nan(ctx, order_stats, (long long)K * n_rows)) return rc;
+    } else {
+        g.n_rows = n_rows; g.table = table; g.order_stats = order_stats; g.out_row0 = 0; g.out_stride = n_rows;
+        if (int rc = weighted_launch(ctx, g, me)) return rc;
+    }
+    int n_passes = 0;
+    if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr, &n_passes, g.n_passes, sizeof(int))) return rc;
+    if (info) { info->T = got.T; info->n_used = got.n_used; info->n_passes = n_passes; }
+    return SIMPLYP_OK;
+}
+
+int simplyp_weighted_quantiles(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double* table,
+                               const int32_t* member_of_slot, const uint8_t* include, const uint64_t* weights,
+                               const double* q, int32_t K, double* order_stats, simplyp_wq_info* info)
+{
+    SIMPLYP_GUARD(ctx, weighted_quantiles_impl(ctx, E, n_rows, table, member_of_slot, include, weights, q, K, order_stats, info))
+}
+
 static int time_quantiles_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
                                const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
                                const double* f_tdp, const double* reach_params,
@@ -2088,12 +2164,19 @@ static int predictive_bands_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uin
                                  const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
                                  const uint8_t* include, const double* f_tdp, const double* reach_params,
                                  const int32_t* series, int32_t n_series, const double* err_m, uint64_t seed, int32_t day0,
-                                 const double* q, int32_t K, double* order_stats, simplyp_pred_info* info)
+                                 const double* q, int32_t K, double* order_stats, simplyp_pred_info* info,
+                                 bool weighted = false, const uint64_t* weights = nullptr, simplyp_wq_info* winfo = nullptr)
 {
-    const char* me = "simplyp_predictive_bands";
+    // `weighted`: simplyp_predictive_bands_weighted -- the same generation, chunks and checks; one plane of values selected under
+    // `weights` by the weighted selectors, and `winfo` instead of `info`
+    const char* me = weighted ? "simplyp_predictive_bands_weighted" : "simplyp_predictive_bands";
     if (!ctx) return SIMPLYP_ERR_ARG;
-    if (!q || !order_stats) return fail(ctx, SIMPLYP_ERR_ARG, "%s: q and order_stats must not be NULL", me);
-    TABLE_TRY(ctx, st::check_probabilities(me, q, K, simplyp::QUANT_MAX_K, msg));
+    if (weighted) {
+        TABLE_TRY(ctx, simplyp_weighted::check_selection(me, dims ? dims->E : 1, weights, q, K, order_stats, msg));
+    } else {
+        if (!q || !order_stats) return fail(ctx, SIMPLYP_ERR_ARG, "%s: q and order_stats must not be NULL", me);
+        TABLE_TRY(ctx, st::check_probabilities(me, q, K, simplyp::QUANT_MAX_K, msg));
+    }
     simplyp::PredArgs g{};
     st::View t;
     st::Series sr;
@@ -2101,6 +2184,7 @@ static int predictive_bands_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uin
                                   series, n_series, err_m, seed, day0, g, t, sr)) return rc;
     const int E = g.E, R = g.R, D = dims->D;
     if (info) { info->kernel_ms = 0.0; info->gen_ms = 0.0; info->bytes_read = 0; info->bytes_workspace = 0; info->n_used = 0; info->n_passes = 0; info->n_chunks = 0; }
+    if (winfo) { winfo->kernel_ms = 0.0; winfo->bytes_table = (int64_t)n_series * D * R * E * 8; winfo->T = 0; winfo->n_used = 0; winfo->n_passes = 0; }
     if (D == 0) return SIMPLYP_OK;
     // whole days per chunk: what 256 MiB of generated series hold, or what the environment says
     const size_t day_bytes = (size_t)n_series * R * E * sizeof(double);
@@ -2119,24 +2203,30 @@ static int predictive_bands_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uin
     double* work = (double*)((char*)ctx->pred.ptr + PRED_REACH_BYTES);
     if (int rc = timed_begin(ctx)) return rc;
     simplyp::QuantileArgs s{};
+    simplyp::WQuantileArgs ws{};
+    simplyp::WqPrepared got{};
     int n_used = 0;
-    if (int rc = quantile_prepare(ctx, E, member_of_slot, include, q, K, s, n_used)) return rc;      // once per call
+    if (weighted) {                                                                                   // once per call
+        if (int rc = weighted_prepare(ctx, me, E, member_of_slot, include, weights, q, K, ws, got)) return rc;
+        n_used = got.T > 0 ? got.n_used : 0;
+    } else if (int rc = quantile_prepare(ctx, E, member_of_slot, include, q, K, s, n_used)) return rc;
     const long long n_rows_all = (long long)n_series * D * R;
     double gen_ms = 0.0;
     if (n_used == 0) {
-        if (int rc = fill_nan(ctx, order_stats, 2LL * K * n_rows_all)) return rc;
+        if (int rc = fill_nan(ctx, order_stats, (weighted ? 1LL : 2LL) * K * n_rows_all)) return rc;
     } else {
         s.order_stats = order_stats; s.out_stride = n_rows_all;
+        ws.order_stats = order_stats; ws.out_stride = n_rows_all;
         for (int c = 0; c < n_chunks; ++c) {
             const int d_lo = (int)(c * chunk_days), nd = (int)std::min<long long>(chunk_days, D - d_lo);
             HIP_TRY(ctx, hipEventRecord(ev.a, ctx->stream));
             if (int rc = predictive_launch(ctx, g, d_lo, nd, work)) return rc;
             HIP_TRY(ctx, hipEventRecord(ev.b, ctx->stream));
             for (int i = 0; i < n_series; ++i) {               // a series' rows of the chunk are one run of rows of the result
-                s.table = work + (size_t)i * nd * R * E;
-                s.n_rows = (long long)nd * R;
-                s.out_row0 = ((long long)i * D + d_lo) * R;
-                if (int rc = quantile_launch(ctx, s, me)) return rc;
+                s.table = ws.table = work + (size_t)i * nd * R * E;
+                s.n_rows = ws.n_rows = (long long)nd * R;
+                s.out_row0 = ws.out_row0 = ((long long)i * D + d_lo) * R;
+                if (int rc = weighted ? weighted_launch(ctx, ws, me) : quantile_launch(ctx, s, me)) return rc;
             }
             // the generation's time, read while the chunk's selections run; the next chunk overwrites the workspace after them
             HIP_TRY(ctx, hipEventSynchronize(ev.b));
@@ -2146,8 +2236,11 @@ static int predictive_bands_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uin
         }
     }
     int n_passes = 0;
-    if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr, &n_passes, s.n_passes, sizeof(int))) return rc;
+    double kernel_ms = 0.0;
+    if (int rc = timed_end(ctx, &kernel_ms, &n_passes, weighted ? ws.n_passes : s.n_passes, sizeof(int))) return rc;
+    if (winfo) { winfo->kernel_ms = kernel_ms; winfo->T = got.T; winfo->n_used = got.n_used; winfo->n_passes = n_passes; }
     if (info) {
+        info->kernel_ms = kernel_ms;
         info->gen_ms = gen_ms;
         info->bytes_read = n_used == 0 ? 0 : sr.loads * (int64_t)D * R * E * 8;
         info->bytes_workspace = (int64_t)((size_t)chunk_days * day_bytes);
@@ -2175,6 +2268,17 @@ int simplyp_predictive_bands(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_
 {
     SIMPLYP_GUARD(ctx, predictive_bands_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, include, f_tdp,
                                              reach_params, series, n_series, err_m, seed, day0, q, K, order_stats, info))
+}
+
+int simplyp_predictive_bands_weighted(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                                      const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
+                                      const uint8_t* include, const double* f_tdp, const double* reach_params,
+                                      const int32_t* series, int32_t n_series, const double* err_m, uint64_t seed, int32_t day0,
+                                      const double* q, int32_t K, const uint64_t* weights, double* order_stats, simplyp_wq_info* info)
+{
+    SIMPLYP_GUARD(ctx, predictive_bands_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, include, f_tdp,
+                                             reach_params, series, n_series, err_m, seed, day0, q, K, order_stats, nullptr, true,
+                                             weights, info))
 }
 
 // ---- the stretch move (simplyp_mcmc.hip.h) ----------------------------------------------------------------------------------

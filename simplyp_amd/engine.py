@@ -33,7 +33,8 @@ ABI_SYMBOLS = ['simplyp_abi_version', 'simplyp_device_count', 'simplyp_ctx_creat
                'simplyp_time_quantiles', 'simplyp_predictive_series', 'simplyp_predictive_bands',
                'simplyp_mcmc_propose', 'simplyp_mcmc_log_prob', 'simplyp_mcmc_accept', 'simplyp_nm_propose', 'simplyp_nm_update',
                'simplyp_sobol_design', 'simplyp_sobol_indices',
-               'simplyp_pf_loglik', 'simplyp_pf_weights', 'simplyp_pf_resample', 'simplyp_gather_members', 'simplyp_pf_jitter']
+               'simplyp_pf_loglik', 'simplyp_pf_weights', 'simplyp_pf_resample', 'simplyp_gather_members', 'simplyp_pf_jitter',
+               'simplyp_weighted_quantiles', 'simplyp_predictive_bands_weighted']
 
 _lib = None
 
@@ -119,6 +120,12 @@ def lib():
     L.simplyp_predictive_bands.restype = C.c_int
     L.simplyp_predictive_bands.argtypes = pred_args + [vp, dp, dp, C.POINTER(C.c_int32), C.c_int32, dp, C.c_uint64, C.c_int32,
                                                        C.POINTER(C.c_double), C.c_int32, dp, C.POINTER(abi.PredInfo)]
+    L.simplyp_weighted_quantiles.restype = C.c_int
+    L.simplyp_weighted_quantiles.argtypes = [vp, C.c_int32, C.c_int64, dp, i32p, vp, vp, C.POINTER(C.c_double), C.c_int32, dp,
+                                             C.POINTER(abi.WqInfo)]
+    L.simplyp_predictive_bands_weighted.restype = C.c_int
+    L.simplyp_predictive_bands_weighted.argtypes = pred_args + [vp, dp, dp, C.POINTER(C.c_int32), C.c_int32, dp, C.c_uint64, C.c_int32,
+                                                                C.POINTER(C.c_double), C.c_int32, vp, dp, C.POINTER(abi.WqInfo)]
     move = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_uint32]
     L.simplyp_mcmc_propose.restype = C.c_int
     L.simplyp_mcmc_propose.argtypes = move + [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), dp, dp, i32p, dp, dp,
@@ -662,6 +669,50 @@ class Engine(object):
         self._check(rc, 'simplyp_quantiles')
         return stats[0], stats[1], info.as_dict()
 
+    def _weight_vector(self, weights, E):
+        """Integer weights [E] in member order (numpy integers or an int64 device tensor, e.g. ``pf_weights``' q) as a contiguous
+        int64 device tensor: the library reads them as uint64 and checks their values."""
+        torch = self.torch
+        if torch.is_tensor(weights):
+            if weights.dtype != torch.int64:
+                raise ValueError("weights must be an int64 tensor (pf_weights' q) or an integer array")
+            wt = weights.to(self.tdev).contiguous()
+        else:
+            wa = np.asarray(weights)
+            if wa.dtype.kind not in 'iu':
+                raise ValueError("weights must be integers (weighted.linear_weights, particle.weights(...)['q'])")
+            if wa.size and (int(wa.min()) < 0 or int(wa.max()) >= 1 << 63):
+                raise ValueError("weights must lie in [0, 2^40]")
+            wt = torch.from_numpy(np.ascontiguousarray(wa.astype(np.int64))).to(self.tdev)
+        if tuple(wt.shape) != (E,):
+            raise ValueError("weights must have one entry per member")
+        return wt
+
+    def weighted_quantiles(self, table, q, weights, include=None, member_of_slot=None):
+        """Exact quantiles across the member axis under integer weights (``simplyp_weighted_quantiles``; ``simplyp_amd.weighted``
+        states the rule): for every row and probability the value of the first member, in ``quantiles``' order, whose running
+        weight reaches ``max(1, ceil(p T))`` -- numpy's ``method='inverted_cdf'`` with ``weights=``, one value per probability.
+
+        table, q, include, member_of_slot as for ``quantiles``; weights: [E] integers in MEMBER order, each in [0, 2^40] (numpy,
+        or the int64 device tensor ``pf_weights`` returns); a member with weight 0 takes no part.
+        Returns (values, info): a device tensor of shape ``(K,) + table.shape[:-1]`` and a dict with ``T`` (the participating
+        weights' sum), ``n_used`` and ``n_passes``.  All NaN when ``T`` is 0."""
+        torch = self.torch
+        if not torch.is_tensor(table) or table.dtype != torch.float64 or not table.is_contiguous() or table.dim() < 1 \
+                or table.device != self.tdev:
+            raise ValueError("table must be a contiguous float64 tensor on %s whose last axis is the member axis" % (self.tdev,))
+        qa = self._q_array(q)
+        K, E = len(qa), int(table.shape[-1])
+        lead = tuple(int(x) for x in table.shape[:-1])
+        n_rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        inc = self._include_mask(include, E)
+        self._check_member_of_slot(member_of_slot, E)
+        wt = self._weight_vector(weights, E)
+        values = torch.empty((max(K, 1),) + lead, dtype=torch.float64, device=self.tdev)
+        info = self._info_call(abi.WqInfo, 'simplyp_weighted_quantiles', self._h, E, n_rows, table.data_ptr(), self._ptr(member_of_slot),
+                               self._ptr(inc), wt.data_ptr(), qa.ctypes.data_as(C.POINTER(C.c_double)), K, values.data_ptr())
+        return values, info
+
     def time_quantiles(self, out, out_mask, q, series=None, period_of_day=None, f_tdp=None, reach_params=None,
                        out_reaches=None, member_of_slot=None, n_periods=None):
         """Exact order statistics per member along the DAY axis (``simplyp_time_quantiles``) of the daily table ``out``
@@ -747,17 +798,28 @@ class Engine(object):
         return table
 
     def predictive_bands(self, out, out_mask, q, series, err_m=None, seed=0, day0=0, include=None, f_tdp=None,
-                         reach_params=None, out_reaches=None, member_of_slot=None):
+                         reach_params=None, out_reaches=None, member_of_slot=None, weights=None):
         """Order statistics across the members of the series ``predictive_series`` would write, for every (series, day,
         reach) (``simplyp_predictive_bands``): the reference's overall predictive band with ``err_m``, the parameter-only
         band of the series without.  The series are generated and selected chunk by chunk on the device; the table is only
         read.  ``q``, ``include`` and the rank rule as for ``quantiles``.  Returns (lower, upper, info): device tensors
-        [K, n_series, D, n_reaches]; ``interpolate_quantiles`` with ``info['n_used']`` turns them into numpy's values."""
+        [K, n_series, D, n_reaches]; ``interpolate_quantiles`` with ``info['n_used']`` turns them into numpy's values.
+        ``weights`` ([E] integers in member order, as for ``weighted_quantiles``): the bands under these weights instead
+        (``simplyp_predictive_bands_weighted``) -- returns (values [K, n_series, D, n_reaches], info) by ``weighted_quantiles``' rule."""
         torch = self.torch
         head, tail, shape, keep = self._predictive_args(out, out_mask, series, err_m, f_tdp, reach_params, out_reaches, member_of_slot)
         E = shape[3]
         qa = self._q_array(q)
         inc = self._include_mask(include, E)
+        if weights is not None:
+            wt = self._weight_vector(weights, E)
+            values = torch.empty((max(len(qa), 1),) + shape[:3], dtype=torch.float64, device=self.tdev)
+            winfo = self._info_call(abi.WqInfo, 'simplyp_predictive_bands_weighted',
+                                    *(head + (self._ptr(inc),) + tail + (C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(day0),
+                                                                          qa.ctypes.data_as(C.POINTER(C.c_double)), len(qa),
+                                                                          wt.data_ptr(), values.data_ptr())))
+            del keep
+            return values, winfo
         stats = torch.empty((2, max(len(qa), 1)) + shape[:3], dtype=torch.float64, device=self.tdev)
         info = abi.PredInfo()
         with torch.cuda.device(self.tdev):

@@ -318,7 +318,7 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
                           waterbody=None, waterbody_obs=None, spearman=False, devices=None, quantiles=None,
                           quantile_members=None, initial_state=None, return_state=False, time_quantiles=None,
                           time_quantile_series=None, time_quantile_periods=None, predictive_series=None, predictive_m=None,
-                          predictive_seed=0, predictive_day0=0):
+                          predictive_seed=0, predictive_day0=0, quantile_weights=None, quantile_log_weights=None):
     """Run an ensemble of parameter sets through the engine in one call.
 
     ``overrides``: dict name -> array[E] (member parameters, see ``marshal.PM_NAMES``) or
@@ -411,6 +411,19 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     ``devices=[...]`` (same reason as ``quantiles``) and for unknown names.  ``run_simply_p_ensemble_windows`` passes each
     window its ``day0 = predictive_day0 + lo``, so the windows' bands laid end to end are the single call's, bit for bit.
 
+    ``quantile_weights`` / ``quantile_log_weights``: one value per member -- non-negative finite linear weights, or log weights
+    such as the per-member log-likelihood ``['gof']`` gives (GLUE: weight the members by their likelihood) --, mutually exclusive.
+    With either, EVERY band across the members this call returns is weighted and selected on the device
+    (``simplyp_weighted_quantiles``, ``simplyp_predictive_bands_weighted``): the daily / reduced rows, the waterbody series, the
+    band of the per-member ``time_quantiles``, and ``predictive_series`` parameter-only and overall.  The weights become the
+    particle filter's integers -- linear ones through ``weighted.linear_weights`` on the host, log weights through
+    ``Engine.pf_weights`` on the device (``particle.weights`` restates it) -- and the band is numpy's ``method='inverted_cdf'``
+    with ``weights=``, exactly: for probability ``p`` the value of the first member, in sorted order, whose running weight reaches
+    ``max(1, ceil(p T))`` (``simplyp_amd.weighted``).  One value per probability, so ``lower``, ``upper`` and ``data`` are the same
+    array; every such result keeps its shape and gains ``rule='inverted_cdf'`` and ``weight_total`` = ``T``.  Non-finite members
+    and ``quantile_members`` are left out as without weights; a member of weight 0 takes no part.  ``ValueError`` for a wrong
+    shape, negative or non-finite linear weights, weights that are all zero, weights without ``quantiles``, and ``devices=[...]``.
+
     ``return_state=True``: the result gains ``'state'`` = dict(rows (``abi.STATE_ROWS``), reaches (all sub-catchments),
     data[S, 16, E], end = ``met_df.index[-1]``): the model state after the last day, in member order (numpy, or a device
     tensor with ``to_host=False``; ``return_state='device'`` keeps it on the device whatever ``to_host`` says -- with
@@ -438,6 +451,11 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
             raise ValueError("quantiles must be 1 to 16 probabilities in [0, 1]")
     elif quantile_members is not None:
         raise ValueError("quantile_members given without quantiles")
+    if quantile_weights is not None and quantile_log_weights is not None:
+        raise ValueError("quantile_weights and quantile_log_weights are mutually exclusive")
+    weighted_band = quantile_weights is not None or quantile_log_weights is not None
+    if weighted_band and quantiles is None:
+        raise ValueError("quantile_weights / quantile_log_weights given without quantiles")
     tq_ids = tq_pod = tq_labels = None
     if time_quantiles is None:
         if time_quantile_series is not None or time_quantile_periods is not None:
@@ -508,6 +526,19 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         quantile_members = np.ascontiguousarray(np.asarray(quantile_members) != 0)
         if quantile_members.shape != (E,):
             raise ValueError("quantile_members needs one flag per member")
+    q_lin = lw_all = None
+    if quantile_weights is not None:                 # the filter's integers, on the host
+        from . import weighted
+        w_ = np.asarray(quantile_weights, dtype=np.float64)
+        if w_.shape != (E,):
+            raise ValueError("quantile_weights needs one weight per member")
+        q_lin = weighted.linear_weights(w_).astype(np.int64)
+    if quantile_log_weights is not None:             # ... on the device, where the run lies
+        lw_all = np.ascontiguousarray(np.asarray(quantile_log_weights, dtype=np.float64))
+        if lw_all.shape != (E,):
+            raise ValueError("quantile_log_weights needs one log weight per member")
+        if not np.isfinite(lw_all).any():
+            raise ValueError("quantile_log_weights: no log weight is finite, so all weights are zero")
     if predictive_m is not None:                     # [n_series, E] in member order
         per = predictive_m if isinstance(predictive_m, dict) else {c: predictive_m for c in pr_names}
         try:
@@ -657,9 +688,21 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
             inc = (status_d & abi.STATUS_NONFINITE) == 0
             if quantile_members is not None:
                 inc = inc & eng.to_device(quantile_members[lo:hi])
-            part['quant'] = eng.quantiles(out_d, quantiles, include=inc, member_of_slot=mos)
+            q_w = None
+            if q_lin is not None:
+                q_w = eng.to_device(q_lin)
+            elif lw_all is not None:
+                q_w = eng.pf_weights(eng.to_device(lw_all))[1]
+
+            def across(table, **kw):
+                """The band across the members of ``table``: (lower, upper, info), one array twice under weights."""
+                if q_w is None:
+                    return eng.quantiles(table, quantiles, include=inc, **kw)
+                values, winfo = eng.weighted_quantiles(table, quantiles, q_w, include=inc, **kw)
+                return values, values, winfo
+            part['quant'] = across(out_d, member_of_slot=mos)
             if 'wb' in part:
-                part['wb_quant'] = eng.quantiles(wb_d, quantiles, include=inc, member_of_slot=mos)
+                part['wb_quant'] = across(wb_d, member_of_slot=mos)
         if time_quantiles is not None:
             lo_d, up_d, tinfo = eng.time_quantiles(out_d, mask, time_quantiles, series=tq_ids, period_of_day=tq_pod,
                                                    f_tdp=ft, reach_params=rp_d, out_reaches=oreach, member_of_slot=mos,
@@ -671,12 +714,17 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
             tdata = engine.interpolate_time_quantiles(lo_h, up_h, time_quantiles, tinfo['n_days'])
             part['tq'] = (lo_h if to_host else lo_d, up_h if to_host else up_d, tdata, tinfo)
             if quantiles is not None:            # the band across the members of the per-member statistics
-                part['tq_quant'] = eng.quantiles(eng.to_device(tdata), quantiles, include=inc)
+                part['tq_quant'] = across(eng.to_device(tdata))
         if pr_names is not None:                 # the bands of the named series: parameter-only, and with the error model drawn
             pkw = dict(seed=predictive_seed, day0=predictive_day0, include=inc, f_tdp=ft, reach_params=rp_d,
                        out_reaches=oreach, member_of_slot=mos)
-            part['pred'] = (eng.predictive_bands(out_d, mask, quantiles, pr_ids, **pkw),
-                            None if pr_m is None else eng.predictive_bands(out_d, mask, quantiles, pr_ids, err_m=pr_m, **pkw))
+            if q_w is None:
+                pred_band = lambda **kw: eng.predictive_bands(out_d, mask, quantiles, pr_ids, **dict(pkw, **kw))
+            else:
+                def pred_band(**kw):
+                    values, winfo = eng.predictive_bands(out_d, mask, quantiles, pr_ids, weights=q_w, **dict(pkw, **kw))
+                    return values, values, winfo
+            part['pred'] = (pred_band(), None if pr_m is None else pred_band(err_m=pr_m))
         part['out_d'] = None if (reduced_on_device and not keep_daily) else out_d
         return part
 
@@ -733,6 +781,9 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     if quantiles is not None:
         def band(lower, upper, info):
             lo_h, up_h = lower.cpu().numpy(), upper.cpu().numpy()
+            if weighted_band:                    # one value per probability: nothing to interpolate
+                return dict(q=list(quantiles), data=lo_h, lower=lo_h if to_host else lower, upper=up_h if to_host else upper,
+                            n_members=info['n_used'], info=info, rule='inverted_cdf', weight_total=int(info['T']))
             return dict(q=list(quantiles), data=engine.interpolate_quantiles(lo_h, up_h, quantiles, info['n_used']),
                         lower=lo_h if to_host else lower, upper=up_h if to_host else upper, n_members=info['n_used'], info=info)
         res['quantiles'] = band(*parts[0]['quant'])
@@ -742,11 +793,12 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         po, ov = parts[0]['pred']
         po_b, ov_b = band(*po), None if ov is None else band(*ov)
         info = dict(param_only=po_b.pop('info'), overall=None if ov_b is None else ov_b.pop('info'))
+        extra = dict(rule=po_b['rule'], weight_total=po_b['weight_total']) if weighted_band else {}
         for b_ in (po_b, ov_b):
             if b_ is not None:
                 del b_['q'], b_['n_members']
         res['predictive'] = dict(q=list(quantiles), series=list(pr_names), param_only=po_b, overall=ov_b,
-                                 n_members=po[2]['n_used'], seed=predictive_seed, day0=predictive_day0, info=info)
+                                 n_members=po[2]['n_used'], seed=predictive_seed, day0=predictive_day0, info=info, **extra)
     if time_quantiles is not None:
         tinfo = parts[0]['tq'][3]
         res['time_quantiles'] = dict(q=list(time_quantiles), series=list(tq_names), periods=tq_labels,
