@@ -42,7 +42,9 @@ extern "C" {
  * 17 still with simplyp_pf_loglik, simplyp_pf_weights, simplyp_pf_resample, simplyp_gather_members, simplyp_pf_jitter and
  * simplyp_pf_info: five more entry points, one more info struct, nothing existing changes.
  * 17 still with simplyp_weighted_quantiles, simplyp_predictive_bands_weighted and simplyp_wq_info: two more entry points, one more
- * info struct; the unweighted entries and everything they return are untouched. */
+ * info struct; the unweighted entries and everything they return are untouched.
+ * 17 still with simplyp_scores, simplyp_predictive_scores and simplyp_score_info: two more entry points, one more info struct; the
+ * ABI is only extended, no existing struct, enum or entry point changes. */
 #define SIMPLYP_ABI_VERSION 17
 
 typedef enum {
@@ -777,6 +779,86 @@ int simplyp_predictive_bands_weighted(simplyp_ctx* ctx, const simplyp_dims* dims
                                       const double* q /* host [K] */, int32_t K,
                                       const uint64_t* weights /* device [E], member order */,
                                       double* order_stats, simplyp_wq_info* info);
+
+/* ---- scores: an ensemble forecast judged against observations across the member axis -- the continuous ranked probability
+ * score (CRPS) in its two terms, and the two counts the probability integral transform (PIT) is made of.
+ *
+ * The rule, for one row over its member axis (values x_j) and one observation y (simplyp_amd/csrc/simplyp_score.h and
+ * simplyp_amd/score.py state it too).  Participation and order are simplyp_weighted_quantiles': member j takes part iff its
+ * include flag is set and its integer weight q_j > 0; weights == NULL gives every included member q_j = 1 (the special case, not
+ * a second code path); T is the sum of the participating weights; the key order has NaN after +inf, -0.0 and +0.0 equal.
+ *   below       = sum q_j [x_j < y]   and   at_or_below = sum q_j [x_j <= y]: exact integers; a NaN member is above every y.
+ *                 They are T F(y-) and T F(y) of the weighted empirical CDF whose inverse simplyp_weighted_quantiles returns.
+ *   abs_err  A  = (1/T) sum q_j |x_j - y|
+ *   spread   B  = (1/T^2) sum_k (x_(k+1) - x_(k)) C_k (T - C_k), x_(k) the participating values in key order, C_k the inclusive
+ *                 running weight: half the expected distance of two draws, over the gaps, every term >= 0
+ *   CRPS        = A - B = the integral of (F - 1{x >= y})^2: one subtraction, left to the caller
+ * A row whose y is NaN is not scored: sums NaN, counts 0.  y = +-inf is an argument error.  A participating non-finite value
+ * makes A and B of its row NaN; the counts stay exact.  T == 0: NaN and 0, and the call succeeds.
+ * The counts are the same bits in every correct implementation.  A and B are sums of non-negative terms of at most 8 roundings
+ * each, added as 1024 per-lane partials (at most 4096 terms each) and a fixed tree: within 1e-12 of their exact values, relative
+ * to themselves (CRPS therefore within 1e-12 (A + B); it cancels, so never judge it relative to itself).  No floating-point
+ * atomics: the same call twice gives the same bits, and a row's outputs depend neither on its place in the table nor on the
+ * chunks. -------------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    double   kernel_ms;       /* all launches of the call, HIP events on the context's stream                     */
+    double   gen_ms;          /* of which: generating the scored rows (simplyp_predictive_scores; else 0)         */
+    double   sort_ms;         /* of which: sorting the rows for the spread term                                   */
+    int64_t  bytes_read;      /* table bytes behind one pass over the scored rows                                 */
+    int64_t  bytes_workspace; /* bytes of a chunk of rows in the context's workspace (<= 256 MiB, or one row)     */
+    uint64_t T;               /* the sum of the participating weights                                             */
+    int32_t  n_used;          /* members that took part: include set and weight > 0                               */
+    int32_t  n_rows_scored;   /* rows with an observation                                                         */
+    int32_t  n_chunks;        /* chunks of rows the workspace was filled with                                     */
+    int32_t  reserved;        /* 0                                                                                */
+} simplyp_score_info;
+
+/*
+ * simplyp_scores -- the scores of every row of a device table [n_rows][E] (any table whose last axis is the member axis).
+ *   E, n_rows       1 <= E <= 2^22; n_rows == 0 succeeds and launches nothing
+ *   member_of_slot, include, weights   as for simplyp_weighted_quantiles; weights may be NULL (all 1)
+ *   y               HOST    [n_rows] observations, NaN = the row is not scored
+ *   sums            device  [2][n_rows]: abs_err, spread
+ *   counts          device  [2][n_rows] uint64: below, at_or_below
+ *   info            host    may be NULL
+ * Only rows with an observation are read.  Counts and A are one streaming pass per row; for B the row is sorted with its weights
+ * -- tiles of 4096 (key, weight) pairs in LDS, then stable merge passes through the context's workspace -- and one pass forms
+ * the running weight and the sum over the gaps.  Rows go through the workspace in chunks of at most 256 MiB (32 E bytes per row;
+ * SIMPLYP_SCORE_CHUNK_ROWS in the environment asks for fewer rows per chunk, never more).  Synchronous, on the context's stream.  SIMPLYP_ERR_ARG
+ * with nothing launched for E outside 1..2^22, n_rows < 0, NULL table / y / sums / counts, an infinite observation;
+ * SIMPLYP_ERR_ARG with sums and counts unwritten for a weight above 2^40.  Without any observation no row kernel runs and no
+ * row is read, but the call is not empty: the weights are still prepared and checked (a weight above 2^40 is refused whatever y
+ * holds, and T and n_used are reported), and every output is filled as "not scored" -- NaN and 0 -- because the caller's sums
+ * and counts must be defined when the call returns.
+ */
+int simplyp_scores(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double* table /* device [n_rows][E] */,
+                   const int32_t* member_of_slot, const uint8_t* include,
+                   const uint64_t* weights /* device [E], member order, or NULL */,
+                   const double* y /* HOST [n_rows], NaN = not scored */,
+                   double* sums /* device [2][n_rows]: abs_err, spread */,
+                   uint64_t* counts /* device [2][n_rows]: below, at_or_below */,
+                   simplyp_score_info* info);
+
+/*
+ * simplyp_predictive_scores -- the scores of the series simplyp_predictive_series (which = 0) would write, against observations
+ * of every (series, day, reach): only the observed rows are generated -- by the same series resolver and the same Philox
+ * counter (seed, member, day0 + d, reach, series) -- and scored by simplyp_scores' row kernels, chunk by chunk.  The result
+ * equals simplyp_predictive_series followed by simplyp_scores on the observed rows, bit for bit, sums included.
+ *   err_m           device  [n_series][E] member order, or NULL: the parameter-only forecast
+ *   weights         device  [E] uint64 in MEMBER order, each <= 2^40, or NULL (all 1)
+ *   obs             HOST    [n_series][D][n_out_reaches], NaN = no observation
+ *   sums, counts    device  [2][n_series][D][n_out_reaches]
+ * SIMPLYP_ERR_ARG as for simplyp_predictive_bands (series, mask, day0) and simplyp_scores.  D == 0 succeeds and launches nothing.
+ */
+int simplyp_predictive_scores(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                              const int32_t* out_reaches, int32_t n_out_reaches,
+                              const double* out, const int32_t* member_of_slot, const uint8_t* include,
+                              const double* f_tdp, const double* reach_params,
+                              const int32_t* series /* host [n_series] */, int32_t n_series,
+                              const double* err_m, uint64_t seed, int32_t day0,
+                              const uint64_t* weights /* device [E], member order, or NULL */,
+                              const double* obs /* HOST [n_series][D][n_out_reaches] */,
+                              double* sums, uint64_t* counts, simplyp_score_info* info);
 
 /* ---- sampling the posterior: the affine-invariant ensemble sampler of the reference's calibration notebook
  * (Development/2016/MCMC.ipynb, cell 10: emcee.EnsembleSampler(n_walk, n_dim, log_posterior).run_mcmc(start, n_steps)), the stretch

@@ -80,6 +80,19 @@ class WqInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ScoreInfo(C.Structure):
+    """simplyp_score_info of include/simplyp.h."""
+    _fields_ = [('kernel_ms', C.c_double), ('gen_ms', C.c_double), ('sort_ms', C.c_double), ('bytes_read', C.c_int64),
+                ('bytes_workspace', C.c_int64), ('T', C.c_uint64), ('n_used', C.c_int32), ('n_rows_scored', C.c_int32),
+                ('n_chunks', C.c_int32), ('reserved', C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
+
+
+SCORE_TILE = 4096               # (key, weight) pairs the scores' LDS sort takes at once (simplyp_score.h)
+
+
 class TqInfo(C.Structure):
     """simplyp_tq_info of include/simplyp.h."""
     _fields_ = [('kernel_ms', C.c_double), ('bytes_read', C.c_int64), ('n_sweeps', C.c_int32), ('n_periods', C.c_int32)]

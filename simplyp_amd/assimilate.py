@@ -46,7 +46,7 @@ def _rejuvenation(rejuvenate, delta, names, lo, hi):
 def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, priors, variables=('Q',), error_m=None,
                n_particles=None, window=30, start=None, initial_state=None, seed=0, resample_threshold=1.0, rejuvenate='liu_west',
                delta=0.98, quantiles=None, forecast_series=None, record=False, state=None, step_len=1., solver=None, device=0,
-               out_reaches=None, forecast_weighted=False):
+               out_reaches=None, forecast_weighted=False, score=False):
     """Update the parameter distribution and the model state of ``n_particles`` particles window by window as the observations
     of ``obs_dict`` arrive (sequential importance resampling), every step on the device.
 
@@ -79,6 +79,15 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
     ``'linear'`` rule of the unweighted bands); any ``resample_threshold`` is allowed and ``forecast['rule']`` is
     ``'inverted_cdf'``.
     ``devices=[...]`` is not offered: resampling spans the whole ensemble.
+
+    ``score=True``: every window's observations are scored against the forecast BEFORE that window's weighting, where the forecast
+    bands are taken (``Engine.predictive_scores``; ``simplyp_amd.score`` states the rule): CRPS in its two terms and the PIT
+    counts of every observed (series, day, reach), for each ``df_R`` series that has an observation at some output reach.  They
+    are always taken under the integer weights with which the particles ENTER the window -- all equal at the start and right
+    after a resampling --, so any ``resample_threshold`` is allowed; ``overall`` draws the error model with the ``m`` the filter
+    knows (0 for the other series; None when it knows the ``m`` of no scored series, as the ensemble call without
+    ``predictive_m``).  ``['scores']`` has the shape of ``run_simply_p_ensemble(score=True)``'s over all days of the
+    call, with ``weight_total`` and ``n_members`` one entry per window, and ``kernel_ms`` gains ``'score'``.
 
     ``state``: the ``'state'`` of an earlier result; ``met_df`` then covers the dates that follow, and the filter continues bit
     for bit (``start``, ``initial_state`` and ``seed`` are ignored).
@@ -136,6 +145,14 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
     hs = _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables, lo, hi, out_reaches)
     try:
         scs, S = hs['scs'], len(hs['scs'])
+        sc_names = sc_ids = sc_obs = None
+        if score:                                                      # the df_R series with an observation, on any date, at some output reach
+            seen = {var for SC in hs['reaches'] if SC in obs_dict for var in abi.GOF_VARS
+                    if var in obs_dict[SC].columns and obs_dict[SC][var].notna().any()}
+            sc_names = [c for c, var in zip(abi.TQ_DERIVED_SERIES, abi.GOF_VARS) if var in seen]
+            sc_ids = [abi.TQ_DERIVED + abi.TQ_DERIVED_SERIES.index(c) for c in sc_names]
+            sc_obs = np.ascontiguousarray(np.stack([hs['obs'][:, abi.TQ_DERIVED_SERIES.index(c), :].T for c in sc_names])) \
+                if sc_names else None
         if state is not None:
             theta0, lw0 = np.array(state['theta'], dtype=np.float64), np.array(state['lw'], dtype=np.float64)
             t0, day0 = int(state['t']), int(state['day'])
@@ -182,7 +199,8 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
         return torch.stack([theta_d[m_dim[v]] if m_dim[v] >= 0 else torch.full((E,), m_const[v], **f64) for v in series_vars]).contiguous()
 
     out = dict(ess=[], log_evidence=[], resampled=[], n_unique=[], n_outside=[])
-    kms = {k: [] for k in STEPS}
+    kms = {k: [] for k in STEPS + (('score',) if score else ())}
+    sc_parts = []
     pilot_ms, wall_ms = [], []
     rec = {k: [] for k in ('inc', 'q', 'ancestors', 'theta_before', 'theta_after', 'state_in', 'state_out')}
     bands_po, bands_ov = [], []
@@ -216,6 +234,19 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
                 if ov_at:
                     em = m_rows([abi.GOF_VARS.index(variables[known_m.index(fc_names[i])]) for i in ov_at])
                     bands_ov.append(forecast_band([fc_ids[i] for i in ov_at], err_m=em))
+            if sc_names:                                               # before the weighting, under the weights of entry
+                skw = dict(seed=seed, day0=day0 + d_lo, weights=q_d, include=(status_d & abi.STATUS_NONFINITE) == 0, **tkw)
+                sobs = np.ascontiguousarray(sc_obs[:, d_lo:d_hi])
+                po_w, ov_w = eng.predictive_scores(table_d, mask, sc_ids, sobs, **skw), None
+                if any(c in known_m for c in sc_names):                # the m the filter knows; 0 for the other series
+                    zero = torch.zeros((E,), **f64)
+                    em_all = torch.stack([m_rows([abi.GOF_VARS.index(variables[known_m.index(c)])])[0] if c in known_m else zero
+                                          for c in sc_names])
+                    ov_w = eng.predictive_scores(table_d, mask, sc_ids, sobs, err_m=em_all.contiguous(), **skw)
+                sc_parts.append((po_w, ov_w))
+                kms['score'].append(po_w[2]['kernel_ms'] + (0.0 if ov_w is None else ov_w[2]['kernel_ms']))
+            elif score:
+                kms['score'].append(0.0)
             linfo = eng.pf_loglik(table_d, mask, hs['obs'][:, :, d_lo:d_hi], pairs, m_rows([v for v, _ in pairs]), lw_d, status=status_d,
                                   inc=inc_d, accumulate=True, **tkw)
             w_d, q_d, winfo = eng.pf_weights(lw_d, w_d, q_d)
@@ -248,7 +279,7 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
                 state_d, mp_d, rp_d, ft_d, theta_d = moved
                 lw_d.zero_()
                 lm_prev = 0.0
-                if forecast_weighted:                                  # the next window's particles enter it equally weighted
+                if forecast_weighted or score:                         # the next window's particles enter it equally weighted
                     w_d, q_d, _ = eng.pf_weights(lw_d, w_d, q_d)
                 if move is not None:
                     if move[0] == 'liu_west':
@@ -287,9 +318,33 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
                                overall=np.concatenate(bands_ov, axis=2) if ov_at else None, day0=day0)
         if forecast_weighted:
             res['forecast']['rule'] = 'inverted_cdf'
+    if score:
+        res['scores'] = _joined_scores(sc_names, hs['reaches'], sc_obs, sc_parts, seed, day0)
     if record:
         res.update(rec)
     return res
+
+
+def _joined_scores(series, reaches, obs, parts, seed, day0):
+    """The windows' scores laid end to end along the day axis, in the shape of ``run_simply_p_ensemble(score=True)['scores']``;
+    ``weight_total``, ``n_members`` and ``info`` are one entry per window (a window's pit is taken with its own total)."""
+    from .model import _scores_result, _mean_crps
+    if not series or not parts:
+        return _scores_result([], reaches, None, 0 if obs is None else obs.shape[1], None, seed, day0)
+    at, wins = 0, []
+    for po, ov in parts:
+        n = int(po[0].shape[2])
+        wins.append(_scores_result(series, reaches, obs[:, at:at + n], n, (po, ov), seed, day0))
+        at += n
+
+    def join(key):
+        d = {k: np.concatenate([w[key][k] for w in wins], axis=1) for k in ('crps', 'abs_err', 'spread', 'below', 'at_or_below', 'pit')}
+        d['n_obs'], d['mean_crps'] = _mean_crps(d['crps'])
+        return d
+    return dict(series=list(series), reaches=list(reaches), param_only=join('param_only'),
+                overall=None if parts[0][1] is None else join('overall'),
+                weight_total=[w['weight_total'] for w in wins], n_members=[w['n_members'] for w in wins], seed=seed, day0=day0,
+                info=dict(param_only=[w['info']['param_only'] for w in wins], overall=[w['info']['overall'] for w in wins]))
 
 
 assimilate.__doc__ = assimilate.__doc__ % (FLUX, list(STEPS))

@@ -24,6 +24,7 @@
 #include "simplyp_weighted_quantile.hip.h"
 #include "simplyp_time_quantile.hip.h"
 #include "simplyp_predictive.hip.h"
+#include "simplyp_score.hip.h"
 #include "simplyp_mcmc.hip.h"
 #include "simplyp_neldermead.hip.h"
 #include "simplyp_sobol.hip.h"
@@ -31,6 +32,7 @@
 #include "simplyp_pack_stream.h"
 #include "simplyp_table.h"
 #include "simplyp_weighted.h"
+#include "simplyp_score.h"
 
 namespace {
 
@@ -59,6 +61,7 @@ struct simplyp_ctx {
     DeviceBuf wquant;         // simplyp_weighted_quantiles: WqPrepared (T, members used, bad weights, sweeps) | [E] uint64 weights in column order
     DeviceBuf tquant;         // simplyp_time_quantiles: sweeps, rows read | day lists, ranks, output reaches
     DeviceBuf pred;           // simplyp_predictive_*: [R] int32 output reaches (256-byte slot) | a chunk of days [n_series][days][R][E]
+    DeviceBuf score;          // simplyp_scores, simplyp_predictive_scores: [E] unit weights | the scored rows' lists | a chunk of rows: sorted pairs twice (, the generated rows)
     DeviceBuf mcmc;           // simplyp_mcmc_*: 4 x uint32 (inside, accepted, NaN)
     DeviceBuf nm;             // simplyp_nm_*: 8 x uint32 counters
     DeviceBuf nm_work;        // simplyp_nm_update: the sort's other copy of the simplexes
@@ -993,6 +996,7 @@ void simplyp_ctx_destroy(simplyp_ctx* ctx)
     if (ctx->gof_partial.ptr) (void)hipFree(ctx->gof_partial.ptr);
     if (ctx->quant.ptr) (void)hipFree(ctx->quant.ptr);
     if (ctx->wquant.ptr) (void)hipFree(ctx->wquant.ptr);
+    if (ctx->score.ptr) (void)hipFree(ctx->score.ptr);
     if (ctx->tquant.ptr) (void)hipFree(ctx->tquant.ptr);
     if (ctx->pred.ptr) (void)hipFree(ctx->pred.ptr);
     if (ctx->mcmc.ptr) (void)hipFree(ctx->mcmc.ptr);
@@ -2279,6 +2283,198 @@ int simplyp_predictive_bands_weighted(simplyp_ctx* ctx, const simplyp_dims* dims
     SIMPLYP_GUARD(ctx, predictive_bands_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, include, f_tdp,
                                              reach_params, series, n_series, err_m, seed, day0, q, K, order_stats, nullptr, true,
                                              weights, info))
+}
+
+// ---- scores (simplyp_score.h states the rule, simplyp_score.hip.h holds the kernels) ------------------------------------------
+namespace {
+struct ScoreEvents {
+    hipEvent_t a = nullptr, b = nullptr, c = nullptr;
+    ~ScoreEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); if (c) (void)hipEventDestroy(c); }
+};
+}  // namespace
+
+// B's sort of g.n_rows rows into the workspace: the tiles, then the merge passes.  `src`: the buffer that holds the result.
+static int score_sort_launch(simplyp_ctx* ctx, const simplyp::ScoreArgs& g, int& src)
+{
+    const int n_tiles = (g.E + simplyp::SCORE_TILE - 1) / simplyp::SCORE_TILE;
+    int P = 2;
+    while (P < std::min(g.E, simplyp::SCORE_TILE)) P <<= 1;
+    hipLaunchKernelGGL(simplyp::score_tile_sort_kernel, dim3((unsigned)n_tiles, (unsigned)g.n_rows), dim3(simplyp::SCORE_THREADS), 0, ctx->stream, g, P);
+    HIP_TRY(ctx, hipGetLastError());
+    src = 0;
+    const dim3 grid((unsigned)((g.E + simplyp::SCORE_THREADS - 1) / simplyp::SCORE_THREADS), (unsigned)g.n_rows);
+    for (long long L = simplyp::SCORE_TILE; L < g.E; L *= 2, src ^= 1) {
+        hipLaunchKernelGGL(simplyp::score_merge_kernel, grid, dim3(simplyp::SCORE_THREADS), 0, ctx->stream, g, (int)L, src);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return SIMPLYP_OK;
+}
+
+// What simplyp_scores and simplyp_predictive_scores share.  `rows`: the scored rows of the result ([n_rows_all] rows), ascending,
+// with their observations `ys`.  table != NULL: row rows[i] of it is scored row i; otherwise `pg` and `rows3` (3 ints per scored
+// row: series index, day, output reach) generate the chunk's rows into the workspace first.
+static int scores_common(simplyp_ctx* ctx, const char* me, int32_t E, const int32_t* member_of_slot, const uint8_t* include,
+                         const uint64_t* weights, const std::vector<int64_t>& rows, const std::vector<double>& ys, int64_t n_rows_all,
+                         const double* table, simplyp::PredArgs* pg, const std::vector<int32_t>& rows3, int64_t loads,
+                         double* sums, uint64_t* counts, simplyp_score_info* info)
+{
+    const int64_t n_scored = (int64_t)rows.size();
+    const bool gen = table == nullptr;
+    const uint64_t row_bytes = (uint64_t)E * 8ull * (gen ? 5ull : 4ull);
+    int64_t chunk = simplyp_score::chunk_rows(n_scored, row_bytes, 256ull << 20, std::getenv("SIMPLYP_SCORE_CHUNK_ROWS"));
+    chunk = std::min<int64_t>(chunk, 65535);
+    const size_t ones_bytes = ((size_t)E * 8 + 255) & ~(size_t)255;
+    const size_t list_bytes = ((size_t)n_scored * (8 + 8 + 8 + 12) + 255) & ~(size_t)255;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = ensure(ctx, ctx->score, ones_bytes + list_bytes + (n_scored ? (size_t)chunk * row_bytes : 0))) return rc;
+    char* base = (char*)ctx->score.ptr;
+    if (int rc = timed_begin(ctx)) return rc;
+    const uint64_t* d_weights = weights;
+    if (!weights) {
+        hipLaunchKernelGGL(simplyp::score_ones_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, ctx->stream, (unsigned long long*)base, (int)E);
+        HIP_TRY(ctx, hipGetLastError());
+        d_weights = (const uint64_t*)base;
+    }
+    simplyp::WQuantileArgs wq{};
+    simplyp::WqPrepared got{};
+    if (int rc = weighted_prepare(ctx, me, E, member_of_slot, include, d_weights, nullptr, 0, wq, got)) return rc;
+    // every row starts as "not scored"
+    if (int rc = fill_nan(ctx, sums, 2 * n_rows_all)) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(counts, 0, (size_t)(2 * n_rows_all) * sizeof(uint64_t), ctx->stream));
+    double gen_ms = 0.0, sort_ms = 0.0;
+    int n_chunks = 0;
+    if (got.T > 0 && n_scored > 0) {
+        long long* d_dst = (long long*)(base + ones_bytes);
+        double* d_y = (double*)(d_dst + n_scored);
+        int32_t* d_rows3 = (int32_t*)(d_y + n_scored);
+        HIP_TRY(ctx, hipMemcpyAsync(d_dst, rows.data(), (size_t)n_scored * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_y, ys.data(), (size_t)n_scored * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (gen) HIP_TRY(ctx, hipMemcpyAsync(d_rows3, rows3.data(), (size_t)n_scored * 12, hipMemcpyHostToDevice, ctx->stream));
+        unsigned long long* work = (unsigned long long*)(base + ones_bytes + list_bytes);
+        const size_t plane = (size_t)chunk * E;
+        simplyp::ScoreArgs g{};
+        g.E = E; g.w_slot = wq.w_slot; g.T = got.T;
+        g.sums = sums; g.counts = (unsigned long long*)counts; g.out_stride = n_rows_all;
+        g.keys[0] = work; g.keys[1] = work + plane; g.wts[0] = work + 2 * plane; g.wts[1] = work + 3 * plane;
+        ScoreEvents ev;
+        HIP_TRY(ctx, hipEventCreate(&ev.a));
+        HIP_TRY(ctx, hipEventCreate(&ev.b));
+        HIP_TRY(ctx, hipEventCreate(&ev.c));
+        for (int64_t r0 = 0; r0 < n_scored; r0 += chunk, ++n_chunks) {
+            g.n_rows = (int)std::min<int64_t>(chunk, n_scored - r0);
+            g.y = d_y + r0; g.dst = d_dst + r0;
+            HIP_TRY(ctx, hipEventRecord(ev.a, ctx->stream));
+            if (gen) {
+                pg->dst = (double*)(work + 4 * plane);
+                const dim3 grid((unsigned)((E + simplyp::PRED_THREADS - 1) / simplyp::PRED_THREADS), (unsigned)g.n_rows);
+                hipLaunchKernelGGL(simplyp::score_rows_kernel, grid, dim3(simplyp::PRED_THREADS), 0, ctx->stream, *pg,
+                                   (const int*)(d_rows3 + 3 * r0), g.n_rows);
+                HIP_TRY(ctx, hipGetLastError());
+                g.table = pg->dst; g.row = nullptr;
+            } else {
+                g.table = table; g.row = d_dst + r0;
+            }
+            HIP_TRY(ctx, hipEventRecord(ev.b, ctx->stream));
+            int src = 0;
+            if (int rc = score_sort_launch(ctx, g, src)) return rc;
+            HIP_TRY(ctx, hipEventRecord(ev.c, ctx->stream));
+            hipLaunchKernelGGL(simplyp::score_gap_kernel, dim3((unsigned)g.n_rows), dim3(simplyp::SCORE_THREADS), 0, ctx->stream, g, src);
+            HIP_TRY(ctx, hipGetLastError());
+            hipLaunchKernelGGL(simplyp::score_stream_kernel, dim3((unsigned)g.n_rows), dim3(simplyp::SCORE_THREADS), 0, ctx->stream, g);
+            HIP_TRY(ctx, hipGetLastError());
+            // the chunk's generation and sort times, read while its sums run; the next chunk overwrites the workspace after them
+            HIP_TRY(ctx, hipEventSynchronize(ev.c));
+            float ms = 0.f;
+            HIP_TRY(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
+            gen_ms += ms;
+            HIP_TRY(ctx, hipEventElapsedTime(&ms, ev.b, ev.c));
+            sort_ms += ms;
+        }
+    }
+    double kernel_ms = 0.0;
+    if (int rc = timed_end(ctx, &kernel_ms)) return rc;
+    if (info) {
+        info->kernel_ms = kernel_ms; info->gen_ms = gen_ms; info->sort_ms = sort_ms;
+        info->bytes_read = got.T > 0 ? loads * n_scored * (int64_t)E * 8 : 0;
+        info->bytes_workspace = got.T > 0 && n_scored > 0 ? (int64_t)((uint64_t)chunk * row_bytes) : 0;
+        info->T = got.T; info->n_used = got.n_used;
+        info->n_rows_scored = got.T > 0 ? (int32_t)n_scored : 0;
+        info->n_chunks = n_chunks;
+    }
+    return SIMPLYP_OK;
+}
+
+static void score_info_clear(simplyp_score_info* info)
+{
+    if (info) *info = simplyp_score_info{};
+}
+
+static int scores_impl(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double* table, const int32_t* member_of_slot,
+                       const uint8_t* include, const uint64_t* weights, const double* y, double* sums, uint64_t* counts,
+                       simplyp_score_info* info)
+{
+    const char* me = "simplyp_scores";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    TABLE_TRY(ctx, simplyp_score::check_table(me, E, n_rows, table, y, sums, counts, msg));
+    std::vector<int64_t> rows;
+    TABLE_TRY(ctx, simplyp_score::scored_rows(me, y, n_rows, rows, msg));
+    score_info_clear(info);
+    if (n_rows == 0) return SIMPLYP_OK;
+    std::vector<double> ys(rows.size());
+    for (size_t i = 0; i < rows.size(); ++i) ys[i] = y[rows[i]];
+    return scores_common(ctx, me, E, member_of_slot, include, weights, rows, ys, n_rows, table, nullptr, std::vector<int32_t>(), 1,
+                         sums, counts, info);
+}
+
+int simplyp_scores(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double* table,
+                   const int32_t* member_of_slot, const uint8_t* include, const uint64_t* weights,
+                   const double* y, double* sums, uint64_t* counts, simplyp_score_info* info)
+{
+    SIMPLYP_GUARD(ctx, scores_impl(ctx, E, n_rows, table, member_of_slot, include, weights, y, sums, counts, info))
+}
+
+static int predictive_scores_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                                  const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
+                                  const uint8_t* include, const double* f_tdp, const double* reach_params,
+                                  const int32_t* series, int32_t n_series, const double* err_m, uint64_t seed, int32_t day0,
+                                  const uint64_t* weights, const double* obs, double* sums, uint64_t* counts, simplyp_score_info* info)
+{
+    const char* me = "simplyp_predictive_scores";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    TABLE_TRY(ctx, simplyp_score::check_outputs(me, dims ? dims->E : 1, obs, sums, counts, msg));
+    simplyp::PredArgs g{};
+    st::View t;
+    st::Series sr;
+    if (int rc = predictive_setup(ctx, me, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
+                                  series, n_series, err_m, seed, day0, g, t, sr)) return rc;
+    const int R = g.R, D = dims->D;
+    const int64_t n_rows_all = (int64_t)n_series * D * R;
+    std::vector<int64_t> rows;
+    TABLE_TRY(ctx, simplyp_score::scored_rows(me, obs, n_rows_all, rows, msg));
+    score_info_clear(info);
+    if (D == 0) return SIMPLYP_OK;
+    std::vector<double> ys(rows.size());
+    std::vector<int32_t> rows3(3 * rows.size());
+    for (size_t i = 0; i < rows.size(); ++i) {
+        ys[i] = obs[rows[i]];
+        rows3[3 * i] = (int32_t)(rows[i] / ((int64_t)D * R));
+        rows3[3 * i + 1] = (int32_t)((rows[i] / R) % D);
+        rows3[3 * i + 2] = (int32_t)(rows[i] % R);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = predictive_workspace(ctx, t.reach_of, 0, g)) return rc;
+    return scores_common(ctx, me, g.E, member_of_slot, include, weights, rows, ys, n_rows_all, nullptr, &g, rows3, sr.loads,
+                         sums, counts, info);
+}
+
+int simplyp_predictive_scores(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                              const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
+                              const uint8_t* include, const double* f_tdp, const double* reach_params,
+                              const int32_t* series, int32_t n_series, const double* err_m, uint64_t seed, int32_t day0,
+                              const uint64_t* weights, const double* obs, double* sums, uint64_t* counts, simplyp_score_info* info)
+{
+    SIMPLYP_GUARD(ctx, predictive_scores_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, include, f_tdp,
+                                              reach_params, series, n_series, err_m, seed, day0, weights, obs, sums, counts, info))
 }
 
 // ---- the stretch move (simplyp_mcmc.hip.h) ----------------------------------------------------------------------------------

@@ -34,7 +34,7 @@ ABI_SYMBOLS = ['simplyp_abi_version', 'simplyp_device_count', 'simplyp_ctx_creat
                'simplyp_mcmc_propose', 'simplyp_mcmc_log_prob', 'simplyp_mcmc_accept', 'simplyp_nm_propose', 'simplyp_nm_update',
                'simplyp_sobol_design', 'simplyp_sobol_indices',
                'simplyp_pf_loglik', 'simplyp_pf_weights', 'simplyp_pf_resample', 'simplyp_gather_members', 'simplyp_pf_jitter',
-               'simplyp_weighted_quantiles', 'simplyp_predictive_bands_weighted']
+               'simplyp_weighted_quantiles', 'simplyp_predictive_bands_weighted', 'simplyp_scores', 'simplyp_predictive_scores']
 
 _lib = None
 
@@ -126,6 +126,11 @@ def lib():
     L.simplyp_predictive_bands_weighted.restype = C.c_int
     L.simplyp_predictive_bands_weighted.argtypes = pred_args + [vp, dp, dp, C.POINTER(C.c_int32), C.c_int32, dp, C.c_uint64, C.c_int32,
                                                                 C.POINTER(C.c_double), C.c_int32, vp, dp, C.POINTER(abi.WqInfo)]
+    L.simplyp_scores.restype = C.c_int
+    L.simplyp_scores.argtypes = [vp, C.c_int32, C.c_int64, dp, i32p, vp, vp, C.POINTER(C.c_double), dp, vp, C.POINTER(abi.ScoreInfo)]
+    L.simplyp_predictive_scores.restype = C.c_int
+    L.simplyp_predictive_scores.argtypes = pred_args + [vp, dp, dp, C.POINTER(C.c_int32), C.c_int32, dp, C.c_uint64, C.c_int32,
+                                                        vp, C.POINTER(C.c_double), dp, vp, C.POINTER(abi.ScoreInfo)]
     move = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_uint32]
     L.simplyp_mcmc_propose.restype = C.c_int
     L.simplyp_mcmc_propose.argtypes = move + [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), dp, dp, i32p, dp, dp,
@@ -832,6 +837,59 @@ class Engine(object):
         del keep
         return stats[0], stats[1], info.as_dict()
 
+
+    def scores(self, table, y, weights=None, include=None, member_of_slot=None):
+        """CRPS terms and PIT counts of every row of ``table`` against the observations ``y`` (``simplyp_scores``;
+        ``simplyp_amd.score`` states the rule).  table, include, member_of_slot as for ``quantiles``; weights as for
+        ``weighted_quantiles`` or None (every included member weighs 1); y: host array of shape ``table.shape[:-1]``, NaN = the
+        row is not scored, +-inf is refused.
+        Returns (sums, counts, info): device tensors of shape ``(2,) + table.shape[:-1]`` -- float64 ``abs_err`` and ``spread``
+        (CRPS = sums[0] - sums[1]), int64 ``below`` and ``at_or_below`` -- and a dict with ``T``, ``n_used``, ``n_rows_scored``,
+        ``n_chunks``, ``kernel_ms``, ``sort_ms``.  Rows without an observation and every row when ``T`` is 0: NaN and 0."""
+        torch = self.torch
+        if not torch.is_tensor(table) or table.dtype != torch.float64 or not table.is_contiguous() or table.dim() < 1 \
+                or table.device != self.tdev:
+            raise ValueError("table must be a contiguous float64 tensor on %s whose last axis is the member axis" % (self.tdev,))
+        E = int(table.shape[-1])
+        lead = tuple(int(x) for x in table.shape[:-1])
+        n_rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        ya = np.asarray(y, dtype=np.float64)
+        if ya.shape != lead:
+            raise ValueError("y must have one observation per row of the table: shape %s" % (lead,))
+        ya = np.ascontiguousarray(ya).reshape(-1)                    # (a 0-d array too)
+        inc = self._include_mask(include, E)
+        self._check_member_of_slot(member_of_slot, E)
+        wt = None if weights is None else self._weight_vector(weights, E)
+        sums = torch.empty((2,) + lead, dtype=torch.float64, device=self.tdev)
+        counts = torch.empty((2,) + lead, dtype=torch.int64, device=self.tdev)
+        info = self._info_call(abi.ScoreInfo, 'simplyp_scores', self._h, E, n_rows, table.data_ptr(), self._ptr(member_of_slot),
+                               self._ptr(inc), self._ptr(wt), ya.ctypes.data_as(C.POINTER(C.c_double)), sums.data_ptr(),
+                               counts.data_ptr())
+        return sums, counts, info
+
+    def predictive_scores(self, out, out_mask, series, obs, err_m=None, seed=0, day0=0, include=None, weights=None, f_tdp=None,
+                          reach_params=None, out_reaches=None, member_of_slot=None):
+        """The scores of the series ``predictive_series`` would write against ``obs`` [n_series, D, n_reaches] (host, NaN = no
+        observation), without materialising them (``simplyp_predictive_scores``): only the observed rows are generated, chunk
+        by chunk, and scored by ``scores``' kernels -- the same bits as ``scores(predictive_series(...), obs)``.  Arguments as
+        for ``predictive_bands``; ``weights`` None or [E] integers in member order.
+        Returns (sums, counts, info) as ``scores`` does, of shape [2, n_series, D, n_reaches]."""
+        torch = self.torch
+        head, tail, shape, keep = self._predictive_args(out, out_mask, series, err_m, f_tdp, reach_params, out_reaches, member_of_slot)
+        E = shape[3]
+        oa = np.ascontiguousarray(obs, dtype=np.float64)
+        if oa.shape != tuple(shape[:3]):
+            raise ValueError("obs must have shape [n_series, D, n_reaches] = %s" % (tuple(shape[:3]),))
+        inc = self._include_mask(include, E)
+        wt = None if weights is None else self._weight_vector(weights, E)
+        sums = torch.empty((2,) + tuple(shape[:3]), dtype=torch.float64, device=self.tdev)
+        counts = torch.empty((2,) + tuple(shape[:3]), dtype=torch.int64, device=self.tdev)
+        info = self._info_call(abi.ScoreInfo, 'simplyp_predictive_scores',
+                               *(head + (self._ptr(inc),) + tail + (C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(day0), self._ptr(wt),
+                                                                     oa.ctypes.data_as(C.POINTER(C.c_double)), sums.data_ptr(),
+                                                                     counts.data_ptr())))
+        del keep
+        return sums, counts, info
 
     # ---- the stretch move (simplyp_mcmc_*; simplyp_amd.mcmc restates it) ----
     def _info_call(self, info_class, name, *args):

@@ -318,7 +318,7 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
                           waterbody=None, waterbody_obs=None, spearman=False, devices=None, quantiles=None,
                           quantile_members=None, initial_state=None, return_state=False, time_quantiles=None,
                           time_quantile_series=None, time_quantile_periods=None, predictive_series=None, predictive_m=None,
-                          predictive_seed=0, predictive_day0=0, quantile_weights=None, quantile_log_weights=None):
+                          predictive_seed=0, predictive_day0=0, quantile_weights=None, quantile_log_weights=None, score=False):
     """Run an ensemble of parameter sets through the engine in one call.
 
     ``overrides``: dict name -> array[E] (member parameters, see ``marshal.PM_NAMES``) or
@@ -424,6 +424,23 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     and ``quantile_members`` are left out as without weights; a member of weight 0 takes no part.  ``ValueError`` for a wrong
     shape, negative or non-finite linear weights, weights that are all zero, weights without ``quantiles``, and ``devices=[...]``.
 
+    ``score=True``: the forecast is judged against the observations of ``obs_dict`` on the device (``simplyp_predictive_scores``;
+    ``simplyp_amd.score`` states the rule): the continuous ranked probability score in its two terms and the counts of the
+    probability integral transform, for every observed (series, day, reach).  The scored series are the ``df_R`` names of
+    ``predictive_series`` that have an observation at some output reach -- without ``predictive_series``, every ``df_R`` series
+    that has one.  ``quantiles`` is not needed; ``quantile_members``, ``quantile_weights`` / ``quantile_log_weights``,
+    ``predictive_m``, ``predictive_seed`` and ``predictive_day0`` mean what they mean for the bands, and non-finite members are
+    left out in the same way, so the scores and the (weighted) bands describe one distribution.  The result gains
+    ``['scores']`` = dict(series, reaches, param_only, overall, weight_total, n_members, seed, day0, info) with ``param_only``
+    = dict(crps, abs_err, spread, below, at_or_below, pit -- each [n_series, D, n_reaches], NaN (counts 0) where nothing was
+    observed --, n_obs, mean_crps [n_series, n_reaches]: the NaN-skipping mean over the days) and ``overall`` the same with the
+    error model drawn (``predictive_m``), else None; ``score.pit_histogram(below, at_or_below, weight_total, n_bins,
+    observed=~np.isnan(crps))`` turns the counts of the observed rows into a rank histogram.  Only the
+    observed rows are generated and sorted.  A device reduction: ``keep_daily=False`` behaves as for ``quantiles``.
+    ``ValueError`` without ``obs_dict``, with ``reduce`` and with ``devices=[...]``, before any device call.
+    ``run_simply_p_ensemble_windows`` passes each window its ``day0``: the windows' scores laid end to end are the single
+    call's, bit for bit.
+
     ``return_state=True``: the result gains ``'state'`` = dict(rows (``abi.STATE_ROWS``), reaches (all sub-catchments),
     data[S, 16, E], end = ``met_df.index[-1]``): the model state after the last day, in member order (numpy, or a device
     tensor with ``to_host=False``; ``return_state='device'`` keeps it on the device whatever ``to_host`` says -- with
@@ -449,12 +466,20 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         quantiles = [float(x) for x in np.atleast_1d(np.asarray(quantiles, dtype=np.float64))]
         if not 1 <= len(quantiles) <= 16 or not all(0.0 <= x <= 1.0 for x in quantiles):
             raise ValueError("quantiles must be 1 to 16 probabilities in [0, 1]")
-    elif quantile_members is not None:
+    elif quantile_members is not None and not score:
         raise ValueError("quantile_members given without quantiles")
+    if score:
+        if obs_dict is None:
+            raise ValueError("score needs obs_dict: the observations the forecast is judged against")
+        if reduce is not None:
+            raise ValueError("score needs the daily series: it cannot be combined with reduce")
+        if devices is not None:
+            raise ValueError("score cannot be combined with devices=[...]: a score of the whole ensemble is not a function of the "
+                             "member blocks' scores -- run it on one device")
     if quantile_weights is not None and quantile_log_weights is not None:
         raise ValueError("quantile_weights and quantile_log_weights are mutually exclusive")
     weighted_band = quantile_weights is not None or quantile_log_weights is not None
-    if weighted_band and quantiles is None:
+    if weighted_band and quantiles is None and not score:
         raise ValueError("quantile_weights / quantile_log_weights given without quantiles")
     tq_ids = tq_pod = tq_labels = None
     if time_quantiles is None:
@@ -487,10 +512,10 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
             raise ValueError("time_quantile_periods must be None, 'annual' or an int array [D] of period indices >= -1")
     pr_names = pr_ids = pr_m = None
     if predictive_series is None:
-        if predictive_m is not None:
+        if predictive_m is not None and not score:
             raise ValueError("predictive_m given without predictive_series")
     else:
-        if quantiles is None:
+        if quantiles is None and not score:
             raise ValueError("predictive_series needs quantiles: the probabilities of the bands")
         if reduce is not None:
             raise ValueError("predictive_series needs the daily series: it cannot be combined with reduce")
@@ -507,9 +532,14 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
                              % [c for c in predictive_m if c not in pr_names])
         pr_ids = [abi.TQ_DERIVED + abi.TQ_DERIVED_SERIES.index(c) if c in abi.TQ_DERIVED_SERIES else marshal.ALL_COLUMNS.index(c)
                   for c in pr_names]
+    if pr_names is not None or score:
         predictive_seed, predictive_day0 = int(predictive_seed), int(predictive_day0)
         if not 0 <= predictive_seed < 1 << 64 or not 0 <= predictive_day0 < 1 << 31:
             raise ValueError("predictive_seed must be in [0, 2^64) and predictive_day0 in [0, 2^31)")
+    if score:
+        if isinstance(predictive_m, dict) and pr_names is None and [c for c in predictive_m if c not in abi.TQ_DERIVED_SERIES]:
+            raise ValueError("predictive_m names series that are not df_R series: %s"
+                             % [c for c in predictive_m if c not in abi.TQ_DERIVED_SERIES])
     marshal.prologue(p_SU, p_LU, p_SC, p)
     scs = marshal.sc_list(p)
     up_ptr, up_idx, _ = marshal.topology(p_struc, p)
@@ -539,15 +569,18 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
             raise ValueError("quantile_log_weights needs one log weight per member")
         if not np.isfinite(lw_all).any():
             raise ValueError("quantile_log_weights: no log weight is finite, so all weights are zero")
-    if predictive_m is not None:                     # [n_series, E] in member order
-        per = predictive_m if isinstance(predictive_m, dict) else {c: predictive_m for c in pr_names}
+    def m_rows(names_):                              # predictive_m as [n_series, E] in member order
+        per = predictive_m if isinstance(predictive_m, dict) else {c: predictive_m for c in names_}
         try:
-            pr_m = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(per.get(c, 0.0), dtype=np.float64), (E,))
-                                                  for c in pr_names]))
+            rows = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(per.get(c, 0.0), dtype=np.float64), (E,))
+                                                  for c in names_]))
         except (TypeError, ValueError):
             raise ValueError("predictive_m must be a float, an array [E], or a dict name -> float or array [E]")
-        if not (np.isfinite(pr_m).all() and (pr_m >= 0).all()):
+        if not (np.isfinite(rows).all() and (rows >= 0).all()):
             raise ValueError("predictive_m must be finite and >= 0")
+        return rows
+    if predictive_m is not None and pr_names is not None:
+        pr_m = m_rows(pr_names)
     met_first = met_df[0] if isinstance(met_df, (list, tuple)) else met_df
     if devices is None:
         bounds = [(0, E)]
@@ -614,6 +647,7 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         if any(i >= abi.TQ_DERIVED for i in pr_ids):
             cols += [c for c in ('Qr', 'Msus_kg/day', 'TDP_kg/day', 'PP_kg/day') if c not in cols]
         cols += [c for c in pr_names if c in marshal.ALL_COLUMNS and c not in cols]
+    pr_bands = pr_names is not None and quantiles is not None
     mask = marshal.mask_of_columns(cols)
     if mask & marshal.MASK_D_SNOW and not snow_in_kernel:
         raise ValueError("output 'D_snow' is the per-member snow depth of the in-kernel snow module: needs snow_in_kernel=True "
@@ -648,6 +682,15 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
             obs = vr.observation_array(obs_dict, reaches, met_df.index)
         if wb_reaches is not None and len(wb_reaches) > 1 and waterbody_obs is not None:
             wobs = vr.observation_array({0: waterbody_obs}, [0], met_df.index)[0]
+    sc_names = sc_ids = sc_obs = sc_m = None
+    if score:                                        # the df_R series with an observation, on any date, at some output reach
+        seen = {var for SC in reaches if SC in obs_dict for var in abi.GOF_VARS
+                if var in obs_dict[SC].columns and obs_dict[SC][var].notna().any()}
+        sc_names = [c for c, var in zip(abi.TQ_DERIVED_SERIES, abi.GOF_VARS) if var in seen and (pr_names is None or c in pr_names)]
+    if sc_names:                                     # [n_series, D, n_reaches]: the layout simplyp_predictive_scores takes
+        sc_m = None if predictive_m is None else m_rows(sc_names)
+        sc_ids = [abi.TQ_DERIVED + abi.TQ_DERIVED_SERIES.index(c) for c in sc_names]
+        sc_obs = np.ascontiguousarray(np.stack([obs[:, abi.TQ_DERIVED_SERIES.index(c), :].T for c in sc_names]))
     ft_all = p['f_TDP'] if f_tdp is None else f_tdp
 
     def block_pass(eng, lo, hi):
@@ -683,7 +726,7 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
             if wobs is not None:
                 g_d, ginfo = eng.gof_waterbody(wb_d, winfo['columns'], wobs, ft, member_of_slot=mos)
                 part['wb_gof'] = (g_d.cpu().numpy() if to_host else g_d, ginfo)
-        if quantiles is not None:
+        if quantiles is not None or score:
             # who takes part: a mask in member order, built where the status lies
             inc = (status_d & abi.STATUS_NONFINITE) == 0
             if quantile_members is not None:
@@ -693,6 +736,7 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
                 q_w = eng.to_device(q_lin)
             elif lw_all is not None:
                 q_w = eng.pf_weights(eng.to_device(lw_all))[1]
+        if quantiles is not None:
 
             def across(table, **kw):
                 """The band across the members of ``table``: (lower, upper, info), one array twice under weights."""
@@ -715,7 +759,12 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
             part['tq'] = (lo_h if to_host else lo_d, up_h if to_host else up_d, tdata, tinfo)
             if quantiles is not None:            # the band across the members of the per-member statistics
                 part['tq_quant'] = across(eng.to_device(tdata))
-        if pr_names is not None:                 # the bands of the named series: parameter-only, and with the error model drawn
+        if sc_ids is not None:                   # the scores of the observed rows: parameter-only, and with the error model drawn
+            skw = dict(seed=predictive_seed, day0=predictive_day0, include=inc, weights=q_w, f_tdp=ft, reach_params=rp_d,
+                       out_reaches=oreach, member_of_slot=mos)
+            part['scores'] = (eng.predictive_scores(out_d, mask, sc_ids, sc_obs, **skw),
+                              None if sc_m is None else eng.predictive_scores(out_d, mask, sc_ids, sc_obs, err_m=sc_m, **skw))
+        if pr_bands:                             # the bands of the named series: parameter-only, and with the error model drawn
             pkw = dict(seed=predictive_seed, day0=predictive_day0, include=inc, f_tdp=ft, reach_params=rp_d,
                        out_reaches=oreach, member_of_slot=mos)
             if q_w is None:
@@ -789,7 +838,9 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         res['quantiles'] = band(*parts[0]['quant'])
         if res.get('waterbody') is not None:
             res['waterbody']['quantiles'] = band(*parts[0]['wb_quant'])
-    if pr_names is not None:
+    if score:
+        res['scores'] = _scores_result(sc_names, reaches, sc_obs, len(met_df), parts[0].get('scores'), predictive_seed, predictive_day0)
+    if pr_bands:
         po, ov = parts[0]['pred']
         po_b, ov_b = band(*po), None if ov is None else band(*ov)
         info = dict(param_only=po_b.pop('info'), overall=None if ov_b is None else ov_b.pop('info'))
@@ -838,6 +889,44 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     return res
 
 
+def _mean_crps(crps):
+    """(n_obs, mean_crps) [n_series, n_reaches] of crps [n_series, D, n_reaches]: the NaN-skipping mean over the days."""
+    n_obs = (~np.isnan(crps)).sum(axis=1)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return n_obs, np.where(n_obs > 0, np.nansum(crps, axis=1) / n_obs, np.nan)
+
+
+def _scores_result(series, reaches, obs, D, got, seed, day0):
+    """``res['scores']`` from the two ``Engine.predictive_scores`` results (parameter-only, overall or None); ``got`` None: no
+    series has an observation."""
+    from . import score as score_rules
+
+    def one(sums, counts, info):
+        sums, counts = sums.cpu().numpy(), counts.cpu().numpy()
+        T = int(info['T'])
+        seen = ~np.isnan(obs)                                    # the scored rows
+        pit = np.full(sums[0].shape, np.nan)
+        if T > 0 and T < 1 << 52:                                # (L + M) and 2 T are exact in fp64: one rounding
+            pit[seen] = (counts[0][seen] + counts[1][seen]).astype(np.float64) / float(2 * T)
+        elif T > 0:
+            pit[seen] = score_rules.pit(counts[0][seen], counts[1][seen], T)
+        crps = sums[0] - sums[1]
+        n_obs, mean_crps = _mean_crps(crps)
+        return dict(crps=crps, abs_err=sums[0], spread=sums[1], below=counts[0].astype(np.uint64), at_or_below=counts[1].astype(np.uint64),
+                    pit=pit, n_obs=n_obs, mean_crps=mean_crps), info
+    if got is None:
+        empty = lambda dt: np.zeros((0, D, len(reaches)), dtype=dt)
+        po = dict(crps=empty(np.float64), abs_err=empty(np.float64), spread=empty(np.float64), below=empty(np.uint64),
+                  at_or_below=empty(np.uint64), pit=empty(np.float64), n_obs=np.zeros((0, len(reaches)), dtype=np.int64),
+                  mean_crps=np.zeros((0, len(reaches))))
+        return dict(series=[], reaches=list(reaches), param_only=po, overall=None, weight_total=0, n_members=0, seed=seed, day0=day0,
+                    info=dict(param_only=None, overall=None))
+    po, po_info = one(*got[0])
+    ov, ov_info = (None, None) if got[1] is None else one(*got[1])
+    return dict(series=list(series), reaches=list(reaches), param_only=po, overall=ov, weight_total=int(po_info['T']),
+                n_members=int(po_info['n_used']), seed=seed, day0=day0, info=dict(param_only=po_info, overall=ov_info))
+
+
 def _torch_cat(xs):
     import torch
     return torch.cat([x.to(xs[0].device) for x in xs], dim=-1)
@@ -879,7 +968,7 @@ def run_simply_p_ensemble_windows(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_
             if tqp is not None and not isinstance(tqp, str):         # the window's days, its periods numbered from 0
                 part = np.asarray(tqp)[lo:hi]
                 kw['time_quantile_periods'] = np.where(part >= 0, part - (part[part >= 0].min() if (part >= 0).any() else 0), -1)
-            if kw.get('predictive_series') is not None:             # the stream is indexed by the run's day, not the window's
+            if kw.get('predictive_series') is not None or kw.get('score'):     # the stream is indexed by the run's day, not the window's
                 kw['predictive_day0'] = int(kwargs.get('predictive_day0', 0)) + lo
             mets = [m.iloc[lo:hi] for m in met_sets]
             res = run_simply_p_ensemble(mets if isinstance(met_df, (list, tuple)) else mets[0], p_struc, p_SU, p_LU, p_SC, p,
