@@ -44,7 +44,9 @@ extern "C" {
  * 17 still with simplyp_weighted_quantiles, simplyp_predictive_bands_weighted and simplyp_wq_info: two more entry points, one more
  * info struct; the unweighted entries and everything they return are untouched.
  * 17 still with simplyp_scores, simplyp_predictive_scores and simplyp_score_info: two more entry points, one more info struct; the
- * ABI is only extended, no existing struct, enum or entry point changes. */
+ * ABI is only extended, no existing struct, enum or entry point changes.
+ * 17 still with simplyp_pareto and simplyp_pareto_info: one more entry point, one more info struct, three constants; nothing
+ * existing changes. */
 #define SIMPLYP_ABI_VERSION 17
 
 typedef enum {
@@ -859,6 +861,62 @@ int simplyp_predictive_scores(simplyp_ctx* ctx, const simplyp_dims* dims, uint32
                               const uint64_t* weights /* device [E], member order, or NULL */,
                               const double* obs /* HOST [n_series][D][n_out_reaches] */,
                               double* sums, uint64_t* counts, simplyp_score_info* info);
+
+/* ---- Pareto counts and non-dominated ranks: the members of an ensemble compared on several objectives at once.
+ *
+ * The rule (simplyp_amd/csrc/simplyp_pareto.h and simplyp_amd/pareto.py state it too).  obj[M][E] holds M objectives of the E
+ * members, the member axis fastest and in the column order of the table it came from (member_of_slot and include as for
+ * simplyp_quantiles); sense[m] = +1: larger is better, -1: smaller is better.
+ *   A member takes part iff its include flag is set (include == NULL: every flag) and none of its M objectives is NaN.  +-inf
+ *   are ordinary values; -0.0 and +0.0 are equal.  n = the members that take part.
+ *   With y = sense x, a dominates b iff y_a[m] >= y_b[m] for every m and y_a[m] > y_b[m] for some m.  Members with identical
+ *   objectives do not dominate each other.
+ *   dominated_by[i] = the participants that dominate i;   dominates[i] = the participants i dominates
+ *   rank[i]         = 0 when nobody dominates i, else 1 + the largest rank among its dominators: the length of the longest
+ *                     chain of dominators above i = the index of the front i leaves with when the non-dominated members are
+ *                     peeled off again and again (NSGA-II's non-dominated rank).  The Pareto front is rank == 0.
+ *   A member that does not take part gets SIMPLYP_PARETO_EXCLUDED in all three outputs.  With max_fronts = F > 0 only the ranks
+ *   0 .. F-1 are resolved: a deeper participant gets SIMPLYP_PARETO_UNRANKED as its rank, its two counts are still exact.
+ * Only comparisons and integer counters: every correct implementation returns the same integers, in every run. ---------------- */
+#define SIMPLYP_PARETO_MAX_OBJ   8
+#define SIMPLYP_PARETO_EXCLUDED (-1)
+#define SIMPLYP_PARETO_UNRANKED (-2)
+typedef struct {
+    double  kernel_ms;        /* all launches of the call, HIP events on the context's stream (the host's reads between them too) */
+    int64_t pair_tests;       /* n^2 of the counts + (front x members left) of every front peeled                                  */
+    int32_t n_used;           /* n: the members that took part                                                                    */
+    int32_t n_fronts;         /* fronts resolved (<= max_fronts when that is set; 0 when rank == NULL)                            */
+    int32_t n_front0;         /* members of rank 0 (0 when rank == NULL)                                                          */
+    int32_t n_unranked;       /* participants left at SIMPLYP_PARETO_UNRANKED                                                     */
+} simplyp_pareto_info;
+
+/*
+ * simplyp_pareto -- the three outputs above for a device table of objectives.
+ *   E, M            1 <= E <= 2^24, 1 <= M <= SIMPLYP_PARETO_MAX_OBJ
+ *   obj             device  [M][E] fp64, only read
+ *   sense           HOST    [M], each +1 or -1
+ *   member_of_slot  device  [E] or NULL: column j of obj holds member member_of_slot[j]
+ *   include         device  [E] uint8 in member order, or NULL
+ *   max_fronts      0 = every rank; F > 0 = the ranks 0 .. F-1
+ *   dominated_by, dominates, rank   device [E] int32 in member order; any may be NULL, not all three.  rank == NULL: no peeling.
+ *   info            host    may be NULL
+ * Three small launches find the participants and write their keys (the order-preserving 64-bit key of simplyp_quantiles with the
+ * sense folded in and the zeros made one), compacted in column order; n is read back once.  One all-pairs launch gives both
+ * counts: a lane owns a member with its keys in registers, the other side of the pair comes through LDS tiles, and the grid's
+ * splits of that side are combined with integer atomic adds.  The ranks are peeled front by front: one launch marks the members
+ * nobody left dominates, a second takes the front's members off the counters of those that remain (front x remaining pair
+ * tests, at most about n^2 / 2 over all fronts), and the host reads two integers per front to know when to stop -- a totally
+ * ordered ensemble (M = 1 without ties) has n fronts and costs n such round trips; max_fronts bounds them.  The workspace is
+ * grow-only context scratch of (8 M + 33) E bytes; no E x E array exists.  Synchronous, on the context's stream.
+ * (SIMPLYP_PARETO_JLOAD=scalar in the environment makes the all-pairs launch read the other side from memory at wave-uniform
+ * addresses instead of LDS tiles: a measurement switch of tools/time_pareto.py, 2.4 to 2.6 times slower, the same integers.)
+ * SIMPLYP_ERR_ARG with nothing launched and nothing written for E or M out of range, a sense other than +-1, max_fronts < 0,
+ * NULL obj or sense, or all three outputs NULL.  n == 0 succeeds: every output SIMPLYP_PARETO_EXCLUDED, n_fronts 0.
+ */
+int simplyp_pareto(simplyp_ctx* ctx, int32_t E, int32_t M, const double* obj /* device [M][E] */,
+                   const int32_t* sense /* host [M] */, const int32_t* member_of_slot, const uint8_t* include,
+                   int32_t max_fronts, int32_t* dominated_by, int32_t* dominates, int32_t* rank /* device [E], any may be NULL */,
+                   simplyp_pareto_info* info);
 
 /* ---- sampling the posterior: the affine-invariant ensemble sampler of the reference's calibration notebook
  * (Development/2016/MCMC.ipynb, cell 10: emcee.EnsembleSampler(n_walk, n_dim, log_posterior).run_mcmc(start, n_steps)), the stretch

@@ -93,6 +93,23 @@ class ScoreInfo(C.Structure):
 SCORE_TILE = 4096               # (key, weight) pairs the scores' LDS sort takes at once (simplyp_score.h)
 
 
+class ParetoInfo(C.Structure):
+    """simplyp_pareto_info of include/simplyp.h."""
+    _fields_ = [('kernel_ms', C.c_double), ('pair_tests', C.c_int64), ('n_used', C.c_int32), ('n_fronts', C.c_int32),
+                ('n_front0', C.c_int32), ('n_unranked', C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+PARETO_MAX_OBJ = 8              # objectives per call (SIMPLYP_PARETO_MAX_OBJ)
+PARETO_EXCLUDED = -1            # every output of a member that takes no part
+PARETO_UNRANKED = -2            # the rank of a participant deeper than max_fronts
+PARETO_THREADS = 256            # members per workgroup of the all-pairs kernel (simplyp_pareto.hip.h)
+PARETO_JTILE = 512              # the other side of the pairs: keys staged in LDS at a time
+PARETO_JSPLIT = 2048            # and the stretch of them one workgroup takes; the grid's second axis splits the rest
+
+
 class TqInfo(C.Structure):
     """simplyp_tq_info of include/simplyp.h."""
     _fields_ = [('kernel_ms', C.c_double), ('bytes_read', C.c_int64), ('n_sweeps', C.c_int32), ('n_periods', C.c_int32)]

@@ -25,6 +25,7 @@
 #include "simplyp_time_quantile.hip.h"
 #include "simplyp_predictive.hip.h"
 #include "simplyp_score.hip.h"
+#include "simplyp_pareto.hip.h"
 #include "simplyp_mcmc.hip.h"
 #include "simplyp_neldermead.hip.h"
 #include "simplyp_sobol.hip.h"
@@ -33,6 +34,7 @@
 #include "simplyp_table.h"
 #include "simplyp_weighted.h"
 #include "simplyp_score.h"
+#include "simplyp_pareto.h"
 
 namespace {
 
@@ -62,6 +64,7 @@ struct simplyp_ctx {
     DeviceBuf tquant;         // simplyp_time_quantiles: sweeps, rows read | day lists, ranks, output reaches
     DeviceBuf pred;           // simplyp_predictive_*: [R] int32 output reaches (256-byte slot) | a chunk of days [n_series][days][R][E]
     DeviceBuf score;          // simplyp_scores, simplyp_predictive_scores: [E] unit weights | the scored rows' lists | a chunk of rows: sorted pairs twice (, the generated rows)
+    DeviceBuf pareto;         // simplyp_pareto: 8 x int32 (n, the peeling's counters) | [E] flags | block offsets | keys [M][E] | 8 x [E] int32 (members, counts, ranks, lists)
     DeviceBuf mcmc;           // simplyp_mcmc_*: 4 x uint32 (inside, accepted, NaN)
     DeviceBuf nm;             // simplyp_nm_*: 8 x uint32 counters
     DeviceBuf nm_work;        // simplyp_nm_update: the sort's other copy of the simplexes
@@ -997,6 +1000,7 @@ void simplyp_ctx_destroy(simplyp_ctx* ctx)
     if (ctx->quant.ptr) (void)hipFree(ctx->quant.ptr);
     if (ctx->wquant.ptr) (void)hipFree(ctx->wquant.ptr);
     if (ctx->score.ptr) (void)hipFree(ctx->score.ptr);
+    if (ctx->pareto.ptr) (void)hipFree(ctx->pareto.ptr);
     if (ctx->tquant.ptr) (void)hipFree(ctx->tquant.ptr);
     if (ctx->pred.ptr) (void)hipFree(ctx->pred.ptr);
     if (ctx->mcmc.ptr) (void)hipFree(ctx->mcmc.ptr);
@@ -2475,6 +2479,132 @@ int simplyp_predictive_scores(simplyp_ctx* ctx, const simplyp_dims* dims, uint32
 {
     SIMPLYP_GUARD(ctx, predictive_scores_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, include, f_tdp,
                                               reach_params, series, n_series, err_m, seed, day0, weights, obs, sums, counts, info))
+}
+
+// ---- Pareto counts and ranks (simplyp_pareto.h states the rule, simplyp_pareto.hip.h holds the kernels) ------------------------
+extern "C++" {
+template <int MODE>
+static void pareto_pairs_launch(simplyp_ctx* ctx, int M, dim3 grid, const unsigned long long* key, long long stride, int n_i,
+                                const int* ilist, int n_j, const int* jlist, int* by_count, int* of_count)
+{
+    const dim3 block(simplyp::PARETO_THREADS);
+#define PARETO_CASE(MP)                                                                                                     \
+    hipLaunchKernelGGL((simplyp::pareto_pairs_kernel<MP, MODE>), grid, block, 0, ctx->stream, key, stride, M, n_i, ilist, n_j, jlist, \
+                       by_count, of_count)
+    switch (M) {                                    // M padded to the next compiled size
+    case 1: PARETO_CASE(1); break;
+    case 2: PARETO_CASE(2); break;
+    case 3: PARETO_CASE(3); break;
+    case 4: PARETO_CASE(4); break;
+    case 5: case 6: PARETO_CASE(6); break;
+    default: PARETO_CASE(8); break;
+    }
+#undef PARETO_CASE
+}
+}  // extern "C++"
+
+static int pareto_impl(simplyp_ctx* ctx, int32_t E, int32_t M, const double* obj, const int32_t* sense, const int32_t* member_of_slot,
+                       const uint8_t* include, int32_t max_fronts, int32_t* dominated_by, int32_t* dominates, int32_t* rank,
+                       simplyp_pareto_info* info)
+{
+    const char* me = "simplyp_pareto";
+    if (!ctx) return SIMPLYP_ERR_ARG;
+    TABLE_TRY(ctx, simplyp_pareto_rules::check_args(me, E, M, obj, sense, max_fronts, dominated_by, dominates, rank, msg));
+    if (info) *info = simplyp_pareto_info{};
+    const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const int T = simplyp::PARETO_THREADS;
+    const int n_blocks = (E + T - 1) / T;
+    const size_t ints = pad((size_t)E * sizeof(int));
+    const size_t off_flag = 256, off_sum = off_flag + pad((size_t)E), off_key = off_sum + pad((size_t)n_blocks * sizeof(int));
+    const size_t off_ints = off_key + pad((size_t)M * E * sizeof(unsigned long long));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = ensure(ctx, ctx->pareto, off_ints + 8 * ints)) return rc;
+    char* base = (char*)ctx->pareto.ptr;
+    int* d_head = (int*)base;                       // [0] n, [4..7] the peeling's two pairs of counters
+    int* d_int[8];                                  // members, dominated_by, dominates, left, rank, front, alive x 2
+    for (int k = 0; k < 8; ++k) d_int[k] = (int*)(base + off_ints + k * ints);
+    simplyp::ParetoPrepArgs g{};
+    g.E = E; g.M = M; g.n_blocks = n_blocks; g.obj = obj; g.member_of_slot = member_of_slot; g.include = include;
+    for (int m = 0; m < M; ++m) g.sense[m] = sense[m];
+    g.flag = (uint8_t*)(base + off_flag); g.block_sum = (int*)(base + off_sum); g.n = d_head;
+    g.key = (unsigned long long*)(base + off_key); g.member_of = d_int[0];
+    if (int rc = timed_begin(ctx)) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(d_head, 0, 256, ctx->stream));
+    const dim3 block(T), grid_E((unsigned)n_blocks);
+    hipLaunchKernelGGL(simplyp::pareto_flag_kernel, grid_E, block, 0, ctx->stream, g);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(simplyp::pareto_scan_kernel, dim3(1), block, 0, ctx->stream, g);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(simplyp::pareto_compact_kernel, grid_E, block, 0, ctx->stream, g);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(simplyp::pareto_fill_kernel, grid_E, block, 0, ctx->stream, (int)E, SIMPLYP_PARETO_EXCLUDED, dominated_by, dominates, rank);
+    HIP_TRY(ctx, hipGetLastError());
+    int n = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&n, d_head, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n < 0 || n > E) return fail(ctx, SIMPLYP_ERR_DEVICE, "%s: the prepare kernels count %d participants of %d members", me, n, (int)E);
+    int64_t pair_tests = 0;
+    int n_fronts = 0, n_front0 = 0, n_unranked = 0;
+    if (n > 0) {
+        const dim3 grid_n((unsigned)((n + T - 1) / T));
+        const unsigned splits = (unsigned)((n + simplyp::PARETO_JSPLIT - 1) / simplyp::PARETO_JSPLIT);
+        HIP_TRY(ctx, hipMemsetAsync(d_int[1], 0, 2 * ints, ctx->stream));       // both counts
+        const char* how = std::getenv("SIMPLYP_PARETO_JLOAD");                  // "scalar": the j keys from memory, not from LDS
+        if (how && std::strcmp(how, "scalar") == 0)
+            pareto_pairs_launch<1>(ctx, M, dim3(grid_n.x, splits), g.key, E, n, nullptr, n, nullptr, d_int[1], d_int[2]);
+        else
+            pareto_pairs_launch<0>(ctx, M, dim3(grid_n.x, splits), g.key, E, n, nullptr, n, nullptr, d_int[1], d_int[2]);
+        HIP_TRY(ctx, hipGetLastError());
+        pair_tests = (int64_t)n * n;
+        if (rank) {
+            HIP_TRY(ctx, hipMemcpyAsync(d_int[3], d_int[1], (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
+            hipLaunchKernelGGL(simplyp::pareto_fill_kernel, grid_n, block, 0, ctx->stream, n, SIMPLYP_PARETO_UNRANKED, d_int[4], (int*)nullptr, (int*)nullptr);
+            HIP_TRY(ctx, hipGetLastError());
+            simplyp::ParetoPeelArgs p{};
+            p.left = d_int[3]; p.rank = d_int[4]; p.front = d_int[5];
+            int n_alive = n, side = 0;
+            while (n_alive > 0 && (max_fronts == 0 || n_fronts < max_fronts)) {
+                p.n_alive = n_alive; p.front_index = n_fronts; p.alive_out = d_int[6 + side];
+                p.counters = d_head + 4 + 2 * (n_fronts & 1); p.counters_next = d_head + 4 + 2 * ((n_fronts + 1) & 1);
+                hipLaunchKernelGGL(simplyp::pareto_mark_kernel, dim3((unsigned)((n_alive + T - 1) / T)), block, 0, ctx->stream, p);
+                HIP_TRY(ctx, hipGetLastError());
+                int got[2] = {0, 0};                // the front's size, the members that stay: the one word per front the host reads
+                HIP_TRY(ctx, hipMemcpyAsync(got, p.counters, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                if (got[0] <= 0 || got[0] + got[1] != n_alive)       // a finite strict order always has a front
+                    return fail(ctx, SIMPLYP_ERR_DEVICE, "%s: front %d takes %d of %d members and leaves %d", me, n_fronts, got[0], n_alive, got[1]);
+                if (n_fronts == 0) n_front0 = got[0];
+                ++n_fronts;
+                if (got[1] > 0 && (max_fronts == 0 || n_fronts < max_fronts)) {
+                    const dim3 grid((unsigned)((got[1] + T - 1) / T), (unsigned)((got[0] + simplyp::PARETO_JSPLIT - 1) / simplyp::PARETO_JSPLIT));
+                    pareto_pairs_launch<2>(ctx, M, grid, g.key, E, got[1], p.alive_out, got[0], p.front, d_int[3], nullptr);
+                    HIP_TRY(ctx, hipGetLastError());
+                    pair_tests += (int64_t)got[0] * got[1];
+                }
+                p.alive_in = p.alive_out;
+                side ^= 1;
+                n_alive = got[1];
+            }
+            n_unranked = n_alive;
+        }
+        hipLaunchKernelGGL(simplyp::pareto_scatter_kernel, grid_n, block, 0, ctx->stream, n, d_int[0], d_int[1], d_int[2], d_int[4],
+                           dominated_by, dominates, rank);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    double kernel_ms = 0.0;
+    if (int rc = timed_end(ctx, &kernel_ms)) return rc;
+    if (info) {
+        info->kernel_ms = kernel_ms; info->pair_tests = pair_tests; info->n_used = n;
+        info->n_fronts = n_fronts; info->n_front0 = n_front0; info->n_unranked = n_unranked;
+    }
+    return SIMPLYP_OK;
+}
+
+int simplyp_pareto(simplyp_ctx* ctx, int32_t E, int32_t M, const double* obj, const int32_t* sense, const int32_t* member_of_slot,
+                   const uint8_t* include, int32_t max_fronts, int32_t* dominated_by, int32_t* dominates, int32_t* rank,
+                   simplyp_pareto_info* info)
+{
+    SIMPLYP_GUARD(ctx, pareto_impl(ctx, E, M, obj, sense, member_of_slot, include, max_fronts, dominated_by, dominates, rank, info))
 }
 
 // ---- the stretch move (simplyp_mcmc.hip.h) ----------------------------------------------------------------------------------

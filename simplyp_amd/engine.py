@@ -34,7 +34,8 @@ ABI_SYMBOLS = ['simplyp_abi_version', 'simplyp_device_count', 'simplyp_ctx_creat
                'simplyp_mcmc_propose', 'simplyp_mcmc_log_prob', 'simplyp_mcmc_accept', 'simplyp_nm_propose', 'simplyp_nm_update',
                'simplyp_sobol_design', 'simplyp_sobol_indices',
                'simplyp_pf_loglik', 'simplyp_pf_weights', 'simplyp_pf_resample', 'simplyp_gather_members', 'simplyp_pf_jitter',
-               'simplyp_weighted_quantiles', 'simplyp_predictive_bands_weighted', 'simplyp_scores', 'simplyp_predictive_scores']
+               'simplyp_weighted_quantiles', 'simplyp_predictive_bands_weighted', 'simplyp_scores', 'simplyp_predictive_scores',
+               'simplyp_pareto']
 
 _lib = None
 
@@ -131,6 +132,9 @@ def lib():
     L.simplyp_predictive_scores.restype = C.c_int
     L.simplyp_predictive_scores.argtypes = pred_args + [vp, dp, dp, C.POINTER(C.c_int32), C.c_int32, dp, C.c_uint64, C.c_int32,
                                                         vp, C.POINTER(C.c_double), dp, vp, C.POINTER(abi.ScoreInfo)]
+    L.simplyp_pareto.restype = C.c_int
+    L.simplyp_pareto.argtypes = [vp, C.c_int32, C.c_int32, dp, C.POINTER(C.c_int32), i32p, vp, C.c_int32, i32p, i32p, i32p,
+                                 C.POINTER(abi.ParetoInfo)]
     move = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_uint32]
     L.simplyp_mcmc_propose.restype = C.c_int
     L.simplyp_mcmc_propose.argtypes = move + [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), dp, dp, i32p, dp, dp,
@@ -890,6 +894,38 @@ class Engine(object):
                                                                      counts.data_ptr())))
         del keep
         return sums, counts, info
+
+    def pareto(self, obj, sense, include=None, member_of_slot=None, max_fronts=0, counts=True, rank=True):
+        """Pareto dominance among the members on the objectives ``obj`` (``simplyp_pareto``; ``simplyp_amd.pareto`` states the
+        rule).  obj: contiguous float64 device tensor [M, E], 1 <= M <= 8, the member axis last and in the column order of the
+        table it came from; sense: M values, +1 = larger is better, -1 = smaller is better; include, member_of_slot as for
+        ``quantiles``; max_fronts: 0 resolves every rank, F > 0 the ranks 0 .. F-1 (deeper members get ``abi.PARETO_UNRANKED``).
+        ``counts=False`` / ``rank=False`` leave those outputs out (without ``rank`` no front is peeled).
+        Returns a dict: int32 device tensors [E] in member order ``dominated_by``, ``dominates`` (with ``counts``) and ``rank``
+        (with ``rank``) -- ``abi.PARETO_EXCLUDED`` for a member that is masked out or has a NaN objective -- and the info fields
+        ``n_used``, ``n_fronts``, ``n_front0``, ``n_unranked``, ``pair_tests``, ``kernel_ms``."""
+        torch = self.torch
+        if not torch.is_tensor(obj) or obj.dtype != torch.float64 or not obj.is_contiguous() or obj.dim() != 2 \
+                or obj.device != self.tdev:
+            raise ValueError("obj must be a contiguous float64 tensor [M, E] on %s" % (self.tdev,))
+        M, E = (int(x) for x in obj.shape)
+        sa = np.ascontiguousarray(np.atleast_1d(np.asarray(sense)).astype(np.int32))
+        if sa.shape != (M,):
+            raise ValueError("sense must have one entry per objective")
+        if not counts and not rank:
+            raise ValueError("counts and rank are both off: nothing to compute")
+        inc = self._include_mask(include, E)
+        self._check_member_of_slot(member_of_slot, E)
+        new = lambda: torch.empty((E,), dtype=torch.int32, device=self.tdev)
+        by, of, rk = (new() if counts else None), (new() if counts else None), (new() if rank else None)
+        info = self._info_call(abi.ParetoInfo, 'simplyp_pareto', self._h, E, M, obj.data_ptr(), sa.ctypes.data_as(C.POINTER(C.c_int32)),
+                               self._ptr(member_of_slot), self._ptr(inc), int(max_fronts), self._ptr(by), self._ptr(of), self._ptr(rk))
+        res = dict(info)
+        if counts:
+            res['dominated_by'], res['dominates'] = by, of
+        if rank:
+            res['rank'] = rk
+        return res
 
     # ---- the stretch move (simplyp_mcmc_*; simplyp_amd.mcmc restates it) ----
     def _info_call(self, info_class, name, *args):

@@ -318,7 +318,8 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
                           waterbody=None, waterbody_obs=None, spearman=False, devices=None, quantiles=None,
                           quantile_members=None, initial_state=None, return_state=False, time_quantiles=None,
                           time_quantile_series=None, time_quantile_periods=None, predictive_series=None, predictive_m=None,
-                          predictive_seed=0, predictive_day0=0, quantile_weights=None, quantile_log_weights=None, score=False):
+                          predictive_seed=0, predictive_day0=0, quantile_weights=None, quantile_log_weights=None, score=False,
+                          pareto=None, pareto_max_fronts=0):
     """Run an ensemble of parameter sets through the engine in one call.
 
     ``overrides``: dict name -> array[E] (member parameters, see ``marshal.PM_NAMES``) or
@@ -441,6 +442,18 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     ``run_simply_p_ensemble_windows`` passes each window its ``day0``: the windows' scores laid end to end are the single
     call's, bit for bit.
 
+    ``pareto=[...]``: the members are compared on several goodness-of-fit criteria at once, on the device and before the table
+    goes to the host (``simplyp_pareto``; ``simplyp_amd.pareto`` states the rule).  Each objective is ``(stat, variable)``,
+    ``(stat, variable, reach_index)`` or ``(stat, variable, reach_index, sense)`` over ``abi.GOF_STATS`` (or ``'spearman'`` with
+    ``spearman=True``) and ``abi.GOF_VARS``, at most 8; NSE, log NSE, r2 and Spearman's r are maximised, nRMSD (%) is minimised,
+    Bias (%) is minimised in absolute value, and the other rows need an explicit sense (``pareto.resolve_objectives``).  The
+    result gains ``['pareto']`` = dict(rank, dominated_by, dominates -- int32 [E]: the non-dominated rank NSGA-II sorts by (0 =
+    the Pareto front), the members that dominate each one and the members it dominates --, front = the member ids of rank 0,
+    objectives, sense, n_members, n_fronts, info).  Non-finite members, members outside ``quantile_members`` and members with a
+    NaN objective take no part and get -1; ``pareto_max_fronts=F`` resolves the ranks below F only (deeper members get -2, their
+    counts stay exact) -- a totally ordered ensemble has E fronts and one host round trip each.  ``sp.pareto_ranks(res['gof'],
+    ...)`` gives the same from a table already returned.  ``ValueError`` without ``obs_dict`` and with ``devices=[...]``.
+
     ``return_state=True``: the result gains ``'state'`` = dict(rows (``abi.STATE_ROWS``), reaches (all sub-catchments),
     data[S, 16, E], end = ``met_df.index[-1]``): the model state after the last day, in member order (numpy, or a device
     tensor with ``to_host=False``; ``return_state='device'`` keeps it on the device whatever ``to_host`` says -- with
@@ -466,7 +479,7 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         quantiles = [float(x) for x in np.atleast_1d(np.asarray(quantiles, dtype=np.float64))]
         if not 1 <= len(quantiles) <= 16 or not all(0.0 <= x <= 1.0 for x in quantiles):
             raise ValueError("quantiles must be 1 to 16 probabilities in [0, 1]")
-    elif quantile_members is not None and not score:
+    elif quantile_members is not None and not score and pareto is None:
         raise ValueError("quantile_members given without quantiles")
     if score:
         if obs_dict is None:
@@ -476,6 +489,16 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         if devices is not None:
             raise ValueError("score cannot be combined with devices=[...]: a score of the whole ensemble is not a function of the "
                              "member blocks' scores -- run it on one device")
+    pa_resolved = None
+    if pareto is not None:
+        if obs_dict is None:
+            raise ValueError("pareto needs obs_dict: the objectives are rows of the goodness-of-fit table")
+        if devices is not None:
+            raise ValueError("pareto cannot be combined with devices=[...]: dominance spans the whole ensemble, it is not a "
+                             "function of the member blocks' results -- run it on one device")
+        pareto_max_fronts = int(pareto_max_fronts)
+        if pareto_max_fronts < 0:
+            raise ValueError("pareto_max_fronts must be >= 0")
     if quantile_weights is not None and quantile_log_weights is not None:
         raise ValueError("quantile_weights and quantile_log_weights are mutually exclusive")
     weighted_band = quantile_weights is not None or quantile_log_weights is not None
@@ -691,6 +714,9 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         sc_m = None if predictive_m is None else m_rows(sc_names)
         sc_ids = [abi.TQ_DERIVED + abi.TQ_DERIVED_SERIES.index(c) for c in sc_names]
         sc_obs = np.ascontiguousarray(np.stack([obs[:, abi.TQ_DERIVED_SERIES.index(c), :].T for c in sc_names]))
+    if pareto is not None:
+        from . import pareto as pareto_rules
+        pa_resolved = pareto_rules.resolve_objectives(pareto, n_reaches=len(reaches), has_spearman=bool(spearman))
     ft_all = p['f_TDP'] if f_tdp is None else f_tdp
 
     def block_pass(eng, lo, hi):
@@ -726,7 +752,7 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
             if wobs is not None:
                 g_d, ginfo = eng.gof_waterbody(wb_d, winfo['columns'], wobs, ft, member_of_slot=mos)
                 part['wb_gof'] = (g_d.cpu().numpy() if to_host else g_d, ginfo)
-        if quantiles is not None or score:
+        if quantiles is not None or score or pareto is not None:
             # who takes part: a mask in member order, built where the status lies
             inc = (status_d & abi.STATUS_NONFINITE) == 0
             if quantile_members is not None:
@@ -736,6 +762,9 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
                 q_w = eng.to_device(q_lin)
             elif lw_all is not None:
                 q_w = eng.pf_weights(eng.to_device(lw_all))[1]
+        if pa_resolved is not None:              # the goodness-of-fit table is in member order whatever the run's is
+            part['pareto'] = eng.pareto(pareto_rules.objective_rows(gof_d, rho, pa_resolved), [r_['sense'] for r_ in pa_resolved],
+                                        include=inc, max_fronts=pareto_max_fronts)
         if quantiles is not None:
 
             def across(table, **kw):
@@ -838,6 +867,8 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
         res['quantiles'] = band(*parts[0]['quant'])
         if res.get('waterbody') is not None:
             res['waterbody']['quantiles'] = band(*parts[0]['wb_quant'])
+    if pa_resolved is not None:
+        res['pareto'] = pareto_rules.result(parts[0]['pareto'], pa_resolved)
     if score:
         res['scores'] = _scores_result(sc_names, reaches, sc_obs, len(met_df), parts[0].get('scores'), predictive_seed, predictive_day0)
     if pr_bands:
