@@ -15,13 +15,13 @@
 #include <new>
 #include <numeric>
 #include <string>
+#include <variant>
 #include <vector>
 
 #include "simplyp_kernels.hip.h"
 #include "simplyp_gof.hip.h"
 #include "simplyp_waterbody.hip.h"
 #include "simplyp_quantile.hip.h"
-#include "simplyp_weighted_quantile.hip.h"
 #include "simplyp_time_quantile.hip.h"
 #include "simplyp_predictive.hip.h"
 #include "simplyp_score.hip.h"
@@ -1852,24 +1852,37 @@ static int quantile_prepare(simplyp_ctx* ctx, int32_t E, const int32_t* member_o
     return SIMPLYP_OK;
 }
 
-// The selection of g.n_rows rows of g.table into rows g.out_row0... of g.order_stats: the LDS sort for short rows, the radix
-// select for long ones.
-static int quantile_launch(simplyp_ctx* ctx, const simplyp::QuantileArgs& g, const char* me)
+// The selection of g.n_rows rows of g.table into rows g.out_row0... of g.order_stats: the LDS sort for rows of up to `sort_max`
+// members, the radix select for longer ones.
+extern "C++" {
+template <class Args>
+static int select_launch(simplyp_ctx* ctx, const Args& g, const char* me, int sort_max, void (*sort)(Args, int), void (*select)(Args))
 {
-    if (g.E <= simplyp::QSORT_MAX) {
+    if (g.E <= sort_max) {
         int P = 2;
         while (P < g.E) P <<= 1;
-        const long long rows_per_block = simplyp::QSORT_MAX / P;
+        const long long rows_per_block = sort_max / P;
         const long long blocks = (g.n_rows + rows_per_block - 1) / rows_per_block;
         if (blocks > 0x7FFFFFFFLL) return fail(ctx, SIMPLYP_ERR_ARG, "%s: too many rows for one call (%lld)", me, g.n_rows);
-        hipLaunchKernelGGL(simplyp::quantile_sort_kernel, dim3((unsigned)blocks), dim3(simplyp::QSORT_THREADS), 0, ctx->stream, g, P);
+        hipLaunchKernelGGL(sort, dim3((unsigned)blocks), dim3(simplyp::QSORT_THREADS), 0, ctx->stream, g, P);
     } else {
         const unsigned blocks = (unsigned)std::min<long long>(g.n_rows, 65536);
-        hipLaunchKernelGGL(simplyp::quantile_select_kernel, dim3(blocks), dim3(simplyp::QSEL_THREADS), 0, ctx->stream, g);
+        hipLaunchKernelGGL(select, dim3(blocks), dim3(simplyp::QSEL_THREADS), 0, ctx->stream, g);
     }
     HIP_TRY(ctx, hipGetLastError());
     return SIMPLYP_OK;
 }
+
+static int select_launch(simplyp_ctx* ctx, const simplyp::QuantileArgs& g, const char* me)
+{
+    return select_launch(ctx, g, me, simplyp::QSORT_MAX, simplyp::quantile_sort_kernel, simplyp::quantile_select_kernel);
+}
+
+static int select_launch(simplyp_ctx* ctx, const simplyp::WQuantileArgs& g, const char* me)
+{
+    return select_launch(ctx, g, me, simplyp::WQSORT_MAX, simplyp::weighted_sort_kernel, simplyp::weighted_select_kernel);
+}
+}  // extern "C++"
 
 static int quantiles_impl(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double* table,
                           const int32_t* member_of_slot, const uint8_t* include,
@@ -1892,7 +1905,7 @@ static int quantiles_impl(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const dou
         if (int rc = fill_nan(ctx, order_stats, n_out)) return rc;
     } else {
         g.n_rows = n_rows; g.table = table; g.order_stats = order_stats; g.out_row0 = 0; g.out_stride = n_rows;
-        if (int rc = quantile_launch(ctx, g, "simplyp_quantiles")) return rc;
+        if (int rc = select_launch(ctx, g, "simplyp_quantiles")) return rc;
     }
     int n_passes = 0;
     if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr, &n_passes, g.n_passes, sizeof(int))) return rc;
@@ -1910,7 +1923,7 @@ int simplyp_quantiles(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double*
     SIMPLYP_GUARD(ctx, quantiles_impl(ctx, E, n_rows, table, member_of_slot, include, q, K, order_stats, info))
 }
 
-// ---- weighted bands (simplyp_weighted.h states the rule, simplyp_weighted_quantile.hip.h selects) -----------------------------
+// ---- weighted bands (simplyp_weighted.h states the rule, simplyp_quantile.hip.h selects) --------------------------------------
 // What a weighted selection decides once per call: the weights in the table's column order, their sum, who takes part
 // (context workspace: WqPrepared | [E] uint64) and, from the sum read back, every probability's exact threshold.  Fills g.E,
 // g.w_slot, g.K, g.thr and g.n_passes; thr stays unset when T == 0.  A weight above 2^40 is SIMPLYP_ERR_ARG.
@@ -1928,24 +1941,6 @@ static int weighted_prepare(simplyp_ctx* ctx, const char* me, int32_t E, const i
     TABLE_TRY(ctx, simplyp_weighted::check_weights(me, got.n_bad, msg));
     g.E = E; g.w_slot = d_w; g.K = K; g.n_passes = &d_res->n_passes;
     for (int k = 0; k < K && got.T > 0; ++k) g.thr[k] = simplyp_weighted::weighted_threshold(q[k], got.T);
-    return SIMPLYP_OK;
-}
-
-// The weighted selection of g.n_rows rows of g.table into rows g.out_row0... of g.order_stats.
-static int weighted_launch(simplyp_ctx* ctx, const simplyp::WQuantileArgs& g, const char* me)
-{
-    if (g.E <= simplyp::WQSORT_MAX) {
-        int P = 2;
-        while (P < g.E) P <<= 1;
-        const long long rows_per_block = simplyp::WQSORT_MAX / P;
-        const long long blocks = (g.n_rows + rows_per_block - 1) / rows_per_block;
-        if (blocks > 0x7FFFFFFFLL) return fail(ctx, SIMPLYP_ERR_ARG, "%s: too many rows for one call (%lld)", me, g.n_rows);
-        hipLaunchKernelGGL(simplyp::weighted_sort_kernel, dim3((unsigned)blocks), dim3(simplyp::WQSORT_THREADS), 0, ctx->stream, g, P);
-    } else {
-        const unsigned blocks = (unsigned)std::min<long long>(g.n_rows, 65536);
-        hipLaunchKernelGGL(simplyp::weighted_select_kernel, dim3(blocks), dim3(simplyp::QSEL_THREADS), 0, ctx->stream, g);
-    }
-    HIP_TRY(ctx, hipGetLastError());
     return SIMPLYP_OK;
 }
 
@@ -1967,7 +1962,7 @@ static int weighted_quantiles_impl(simplyp_ctx* ctx, int32_t E, int64_t n_rows, 
         if (int rc = fill_nan(ctx, order_stats, (long long)K * n_rows)) return rc;
     } else {
         g.n_rows = n_rows; g.table = table; g.order_stats = order_stats; g.out_row0 = 0; g.out_stride = n_rows;
-        if (int rc = weighted_launch(ctx, g, me)) return rc;
+        if (int rc = select_launch(ctx, g, me)) return rc;
     }
     int n_passes = 0;
     if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr, &n_passes, g.n_passes, sizeof(int))) return rc;
@@ -2166,6 +2161,21 @@ struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;
     ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
 };
+
+// What the bands select every chunk with: either selection, prepared once per call.
+struct BandSelection {
+    std::variant<simplyp::QuantileArgs, simplyp::WQuantileArgs> args;
+    simplyp::WqPrepared got{};             // under weights: their sum and the members that carry one
+    int n_used = 0;                        // members that take part; 0: every value of the result is NaN
+    int T = 0;                             // planes of the result: 2K, K under weights
+    simplyp::SelectArgs& head() { return std::visit([](auto& a) -> simplyp::SelectArgs& { return a; }, args); }
+    void set_rows(const double* table, long long n_rows, long long out_row0)
+    {
+        simplyp::SelectArgs& h = head();
+        h.table = table; h.n_rows = n_rows; h.out_row0 = out_row0;
+    }
+    int launch(simplyp_ctx* ctx, const char* me) { return std::visit([&](auto& a) { return select_launch(ctx, a, me); }, args); }
+};
 }  // namespace
 
 static int predictive_bands_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
@@ -2210,31 +2220,30 @@ static int predictive_bands_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uin
     if (int rc = predictive_workspace(ctx, t.reach_of, (size_t)chunk_days * day_bytes, g)) return rc;
     double* work = (double*)((char*)ctx->pred.ptr + PRED_REACH_BYTES);
     if (int rc = timed_begin(ctx)) return rc;
-    simplyp::QuantileArgs s{};
-    simplyp::WQuantileArgs ws{};
-    simplyp::WqPrepared got{};
-    int n_used = 0;
+    BandSelection sel;
     if (weighted) {                                                                                   // once per call
-        if (int rc = weighted_prepare(ctx, me, E, member_of_slot, include, weights, q, K, ws, got)) return rc;
-        n_used = got.T > 0 ? got.n_used : 0;
-    } else if (int rc = quantile_prepare(ctx, E, member_of_slot, include, q, K, s, n_used)) return rc;
+        if (int rc = weighted_prepare(ctx, me, E, member_of_slot, include, weights, q, K, sel.args.emplace<simplyp::WQuantileArgs>(), sel.got)) return rc;
+        sel.n_used = sel.got.T > 0 ? sel.got.n_used : 0;
+        sel.T = K;
+    } else {
+        if (int rc = quantile_prepare(ctx, E, member_of_slot, include, q, K, sel.args.emplace<simplyp::QuantileArgs>(), sel.n_used)) return rc;
+        sel.T = 2 * K;
+    }
+    const int n_used = sel.n_used;
     const long long n_rows_all = (long long)n_series * D * R;
     double gen_ms = 0.0;
     if (n_used == 0) {
-        if (int rc = fill_nan(ctx, order_stats, (weighted ? 1LL : 2LL) * K * n_rows_all)) return rc;
+        if (int rc = fill_nan(ctx, order_stats, (long long)sel.T * n_rows_all)) return rc;
     } else {
-        s.order_stats = order_stats; s.out_stride = n_rows_all;
-        ws.order_stats = order_stats; ws.out_stride = n_rows_all;
+        sel.head().order_stats = order_stats; sel.head().out_stride = n_rows_all;
         for (int c = 0; c < n_chunks; ++c) {
             const int d_lo = (int)(c * chunk_days), nd = (int)std::min<long long>(chunk_days, D - d_lo);
             HIP_TRY(ctx, hipEventRecord(ev.a, ctx->stream));
             if (int rc = predictive_launch(ctx, g, d_lo, nd, work)) return rc;
             HIP_TRY(ctx, hipEventRecord(ev.b, ctx->stream));
             for (int i = 0; i < n_series; ++i) {               // a series' rows of the chunk are one run of rows of the result
-                s.table = ws.table = work + (size_t)i * nd * R * E;
-                s.n_rows = ws.n_rows = (long long)nd * R;
-                s.out_row0 = ws.out_row0 = ((long long)i * D + d_lo) * R;
-                if (int rc = weighted ? weighted_launch(ctx, ws, me) : quantile_launch(ctx, s, me)) return rc;
+                sel.set_rows(work + (size_t)i * nd * R * E, (long long)nd * R, ((long long)i * D + d_lo) * R);
+                if (int rc = sel.launch(ctx, me)) return rc;
             }
             // the generation's time, read while the chunk's selections run; the next chunk overwrites the workspace after them
             HIP_TRY(ctx, hipEventSynchronize(ev.b));
@@ -2245,8 +2254,8 @@ static int predictive_bands_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uin
     }
     int n_passes = 0;
     double kernel_ms = 0.0;
-    if (int rc = timed_end(ctx, &kernel_ms, &n_passes, weighted ? ws.n_passes : s.n_passes, sizeof(int))) return rc;
-    if (winfo) { winfo->kernel_ms = kernel_ms; winfo->T = got.T; winfo->n_used = got.n_used; winfo->n_passes = n_passes; }
+    if (int rc = timed_end(ctx, &kernel_ms, &n_passes, sel.head().n_passes, sizeof(int))) return rc;
+    if (winfo) { winfo->kernel_ms = kernel_ms; winfo->T = sel.got.T; winfo->n_used = sel.got.n_used; winfo->n_passes = n_passes; }
     if (info) {
         info->kernel_ms = kernel_ms;
         info->gen_ms = gen_ms;

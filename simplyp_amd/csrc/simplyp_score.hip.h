@@ -9,9 +9,9 @@
 //   score_stream_kernel        counts and A: one workgroup per scored row, one streaming pass.  The counts are integer wave
 //                              reductions; A is a per-lane partial (lane t adds members t, t + 1024, ...: at most 4096 terms
 //                              for E <= 2^22) and a fixed tree over the 1024 partials in LDS
-//   score_tile_sort_kernel     B, step 1: every tile of SCORE_TILE members of a row is bitonic-sorted in LDS as (key, weight)
-//                              pairs (a member that takes no part: the padding key, weight 0, so it sorts behind everything)
-//                              and written to the workspace
+//   score_tile_sort_kernel     B, step 1: every tile of SCORE_TILE members of a row is sorted in LDS as (key, weight) pairs by
+//                              bitonic_segments (a member that takes no part: the padding key, weight 0, so it sorts behind
+//                              everything) and written to the workspace
 //   score_merge_kernel         B, step 2 (rows longer than a tile): one stable merge pass over runs of length L -- every
 //                              element finds its rank in the partner run by binary search (lower bound from the left run,
 //                              upper bound from the right) and is written to its place in the other buffer; an odd run at
@@ -29,8 +29,7 @@
 #include <stdint.h>
 
 #include "simplyp_predictive.hip.h"
-#include "simplyp_quantile.hip.h"
-#include "simplyp_weighted_quantile.hip.h"     // wq_wave_sum
+#include "simplyp_quantile.hip.h"               // keys, bitonic_segments, wq_wave_sum
 #include "simplyp_score.h"
 
 namespace simplyp {
@@ -185,22 +184,7 @@ __global__ __launch_bounds__(SCORE_THREADS) void score_tile_sort_kernel(const Sc
         wts[i] = w;
     }
     __syncthreads();
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < P / 2; t += SCORE_THREADS) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int l = i | j;
-                const bool asc = (i & k) == 0;             // i < P: the last merge (k == P) is ascending throughout
-                const unsigned long long a = keys[i], b = keys[l];
-                if ((a > b) == asc) {
-                    keys[i] = b; keys[l] = a;
-                    const unsigned long long wa = wts[i];
-                    wts[i] = wts[l]; wts[l] = wa;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_segments<SCORE_THREADS, true>(keys, wts, P, P);
     // the padding sorts last: the first `len` pairs are the tile's
     const size_t base = (size_t)r * g.E + j0;
     for (int i = tid; i < len; i += SCORE_THREADS) {

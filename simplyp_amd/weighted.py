@@ -1,4 +1,4 @@
-"""NumPy / Python-integer statement of the weighted bands (csrc/simplyp_weighted.h, csrc/simplyp_weighted_quantile.hip.h).
+"""NumPy / Python-integer statement of the weighted bands (csrc/simplyp_weighted.h, csrc/simplyp_quantile.hip.h).
 CPU only; the specification ``Engine.weighted_quantiles`` and ``Engine.predictive_bands(weights=)`` are tested against.
 
 One row of a table over its member axis, integer weights ``q`` (``0 <= q_i <= 2^40``, ``1 <= E <= 2^22``: what

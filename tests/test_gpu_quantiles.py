@@ -73,7 +73,7 @@ def check(engine0, table, q, include=None, perm=None):
     return info
 
 
-@pytest.mark.parametrize('E', [1, 2, 63, 64, 65, 1000, 4097, 100000])
+@pytest.mark.parametrize('E', [1, 2, 63, 64, 65, 1000, 2048, 4096, 4097, 9000, 100000])
 @pytest.mark.parametrize('n_rows', [1, 7, 300])
 def test_order_statistics_are_exact(engine0, E, n_rows):
     rng = np.random.default_rng(1000 * n_rows + E)
@@ -92,7 +92,7 @@ def test_few_very_long_rows(engine0):
     check(engine0, table, q_random())
 
 
-@pytest.mark.parametrize('E', [65, 1000, 4097, 20000])
+@pytest.mark.parametrize('E', [65, 1000, 4096, 4097, 20000])
 def test_member_mask_and_slot_order(engine0, E):
     rng = np.random.default_rng(E)
     table = make_table('special', 23, E, rng)

@@ -5,12 +5,12 @@ column: Qr), on one MI355X.  `python tools/time_weighted_bands.py [--members N] 
   (w) simplyp_weighted_quantiles on the device-resident table for q = [0.025, 0.5, 0.975], weights from a simplyp_pf_weights
       call on log weights that fall off with the distance of a member's mean flow from the ensemble's median (a Gaussian
       likelihood of one summary statistic)
-  (u) simplyp_quantiles on the same table in the same session: the unchanged unweighted selector, the yardstick
+  (u) simplyp_quantiles on the same table in the same session: the same select under its unweighted policy, the yardstick
   (e) (w) again with all weights equal: what the weights' spread itself costs
 and the sweeps per row of each, the quotient (w) / (u), the table bytes per second each sweep reaches, and the HBM floor of one
 sweep: 8 B per member and row at the MI355X's nominal 8 TB/s (the weight vector, 8 B per member, stays in cache).  Device events
 (info.kernel_ms), the minimum over the repeats.  With SIMPLYP_HIP_LIB naming a library built with -DSIMPLYP_WQ_NO_MERGE the same
-run times the weighted select without its wave merge."""
+run times the weighted select without its wave merge (the macro sets WQSelect::MERGE_ROUNDS in simplyp_quantile.hip.h to 0)."""
 import argparse
 import json
 import os
@@ -60,7 +60,7 @@ def main():
     floor_ms = 8.0 * E * D / (HBM_GBS * 1e9) * 1e3
     res.update(weighted_ms=w_ms, weighted_ms_all=w_all, weighted_passes=w_info['n_passes'], weighted_n_used=w_info['n_used'],
                weight_total=int(w_info['T']), unweighted_ms=u_ms, unweighted_ms_all=u_all, unweighted_passes=u_info['n_passes'],
-               equal_weights_ms=e_ms, equal_weights_passes=e_info['n_passes'], weighted_over_unweighted=w_ms / u_ms,
+               equal_weights_ms=e_ms, equal_weights_ms_all=e_all, equal_weights_passes=e_info['n_passes'], weighted_over_unweighted=w_ms / u_ms,
                hbm_floor_ms_per_sweep=floor_ms, weighted_ms_per_sweep=w_ms / max(w_info['n_passes'], 1),
                unweighted_ms_per_sweep=u_ms / max(u_info['n_passes'], 1),
                weighted_table_gbs_per_sweep=8.0 * E * D * w_info['n_passes'] / (w_ms * 1e-3) / 1e9,
