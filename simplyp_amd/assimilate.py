@@ -7,14 +7,15 @@ the model state and a forecast band are wanted each time without running thirty 
 window by window; ``simplyp_amd.particle`` states its steps in NumPy and Python integers."""
 
 import time
+from types import SimpleNamespace
 
 import numpy as np
 import pandas as pd
 
-from . import abi, marshal, particle
+from . import abi, engine, ensemble, marshal, particle, request
 from .calibrate import _plan, _host_setup, _check_inside, _shaped_for_the_ensemble
+from .model import _DeviceEnsemble, _state_blocks, _scores_result, _mean_crps
 
-FLUX = ['Qr', 'Msus_kg/day', 'TDP_kg/day', 'PP_kg/day']            # what the likelihood and the df_R series read
 STEPS = ('run', 'loglik', 'weights', 'resample', 'gather', 'jitter')
 
 
@@ -41,6 +42,90 @@ def _rejuvenation(rejuvenate, delta, names, lo, hi):
     if not (np.isfinite(frac).all() and (frac >= 0).all()):
         raise ValueError("a jitter fraction must be finite and >= 0")
     return 'fixed', frac * (hi - lo)
+
+
+def _host(x):
+    return None if x is None else x.cpu().numpy()
+
+
+def _m_rows(dev, s, c, series_vars):
+    """The error model's m [n, E] of the variables ``series_vars`` (indices of abi.GOF_VARS; None: a series without one, m = 0)."""
+    fixed = lambda v: dev.torch.full((s.theta.shape[1],), 0.0 if v is None else c.m_const[v], **dev.f64)
+    return dev.torch.stack([s.theta[c.m_dim[v]] if v is not None and c.m_dim[v] >= 0 else fixed(v) for v in series_vars]).contiguous()
+
+
+def _window(dev, hs, s, c, t, d_lo, d_hi):
+    """Window ``t`` = days [d_lo, d_hi): run, forecast, log-likelihood, weights, and the resampling when the ESS asks for it.
+    What it changes: the filter's state ``s`` (theta, lw, inc, state, w, q on the device, lm_prev) and, on resampling, the
+    particles' arrays ``dev.mp_d`` / ``rp_d`` / ``ft_d``.  ``c``: the call's settings, read only.  Returns the window's record."""
+    eng, torch, mask, E = dev.eng, dev.torch, dev.mask, s.theta.shape[1]
+    torch.cuda.synchronize(eng.tdev)
+    w0 = time.perf_counter()
+    rec = dict(theta_before=_host(s.theta), state_in=_host(s.state)) if c.record else {}
+    table_d, status_d, rstats = eng.run(dev.f_d[:, :, d_lo:d_hi].contiguous(), dev.doy_d[d_lo:d_hi].contiguous(), dev.mp_d, dev.rp_d,
+                                        hs['up_ptr'], hs['up_idx'], dev.opts, out_reaches=hs['oreach'], state_in=s.state, state_out=True)
+    s.state = rstats['state']
+    ms = dict(dict.fromkeys(STEPS + ('score',), 0.0), run=rstats['kernel_ms'])
+    win = dict(ms=ms, pilot_ms=rstats['pilot_ms'], rec=rec, n_unique=E, n_outside=0)
+    tkw = dict(f_tdp=dev.ft_d, reach_params=dev.rp_d, out_reaches=hs['oreach'])
+    pkw = dict(tkw, seed=c.seed, day0=c.day0 + d_lo)
+    if c.quantiles is not None:                                    # before the weighting
+        def band(ids, **kw):
+            if c.forecast_weighted:                                # under the weights the particles enter the window with
+                return _host(eng.predictive_bands(table_d, mask, c.quantiles, ids, weights=s.q, **dict(pkw, **kw))[0])
+            lo_b, up_b, binfo = eng.predictive_bands(table_d, mask, c.quantiles, ids, **dict(pkw, **kw))
+            return engine.interpolate_quantiles(_host(lo_b), _host(up_b), c.quantiles, binfo['n_used'])
+        win['band_po'] = band(c.fc_ids)
+        if c.ov_ids:
+            win['band_ov'] = band(c.ov_ids, err_m=_m_rows(dev, s, c, c.ov_vars))
+    if c.sc_ids:                                                   # before the weighting, under the weights of entry
+        skw = dict(pkw, weights=s.q, include=(status_d & abi.STATUS_NONFINITE) == 0)
+        sobs = np.ascontiguousarray(c.sc_obs[:, d_lo:d_hi])
+        po_w, ov_w = eng.predictive_scores(table_d, mask, c.sc_ids, sobs, **skw), None
+        if any(v is not None for v in c.sc_vars):                  # the m the filter knows; 0 for the other series
+            ov_w = eng.predictive_scores(table_d, mask, c.sc_ids, sobs, err_m=_m_rows(dev, s, c, c.sc_vars), **skw)
+        win['scores'] = (po_w, ov_w)
+        ms['score'] = po_w[2]['kernel_ms'] + (0.0 if ov_w is None else ov_w[2]['kernel_ms'])
+    linfo = eng.pf_loglik(table_d, mask, hs['obs'][:, :, d_lo:d_hi], hs['pairs'], _m_rows(dev, s, c, [v for v, _ in hs['pairs']]), s.lw,
+                          status=status_d, inc=s.inc, accumulate=True, **tkw)
+    s.w, s.q, winfo = eng.pf_weights(s.lw, s.w, s.q)
+    ms['loglik'], ms['weights'] = linfo['kernel_ms'], winfo['kernel_ms']
+    if c.record:
+        rec.update(inc=_host(s.inc), q=_host(s.q).astype(np.uint64), state_out=_host(s.state), ancestors=np.arange(E, dtype=np.int32))
+    if winfo['T'] == 0:
+        raise RuntimeError("assimilate: every particle is dead in window %d (%s to %s): no log weight is finite -- the error "
+                           "model's m or the prior box leaves no particle that explains the observations"
+                           % (t, c.index[d_lo].date(), c.index[d_hi - 1].date()))
+    lm = particle.log_mean(winfo['lw_max'], winfo['sum_w'], E)
+    win.update(ess=particle.ess(winfo['sum_w'], winfo['sum_w2']), log_evidence=lm - s.lm_prev)
+    s.lm_prev = lm
+    win['resampled'] = bool(win['ess'] < float(c.resample_threshold) * E)
+    if win['resampled']:
+        anc_d, _, rinfo = eng.pf_resample(s.q, c.seed, t, offspring=False)
+        ms['resample'], win['n_unique'] = rinfo['kernel_ms'], int(rinfo['n_unique'])
+        for owner, key in ((s, 'state'), (dev, 'mp_d'), (dev, 'rp_d'), (dev, 'ft_d'), (s, 'theta')):   # all a particle owns travels with it
+            dst, ginfo = eng.gather_members(getattr(owner, key), anc_d)
+            setattr(owner, key, dst)
+            ms['gather'] += ginfo['kernel_ms']
+        s.lw.zero_()
+        s.lm_prev = 0.0
+        if c.forecast_weighted or c.score:                         # the next window's particles enter it equally weighted
+            s.w, s.q, _ = eng.pf_weights(s.lw, s.w, s.q)
+        if c.move is not None:
+            if c.move[0] == 'liu_west':
+                a = c.move[1]
+                centre = _host(s.theta.mean(dim=1))
+                scale = np.sqrt(1.0 - a * a) * _host(s.theta.std(dim=1, unbiased=False))
+            else:
+                a, centre, scale = 1.0, np.zeros(len(c.target)), c.move[1]
+            jinfo = eng.pf_jitter(s.theta, t, a, centre, scale, c.lo, c.hi, c.target, dev.mp_d, dev.ft_d, seed=c.seed)
+            ms['jitter'], win['n_outside'] = jinfo['kernel_ms'], int(jinfo['n_outside'])
+        rec.update(ancestors=_host(anc_d))
+    if c.record:
+        rec['theta_after'] = _host(s.theta)
+    torch.cuda.synchronize(eng.tdev)
+    win['wall_ms'] = 1e3 * (time.perf_counter() - w0)
+    return win
 
 
 def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, priors, variables=('Q',), error_m=None,
@@ -100,9 +185,6 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
     ``quantiles`` --, and with ``record`` the per-window lists inc, q, ancestors, theta_before, theta_after, state_in,
     state_out).  ``ValueError`` before any device call for bad arguments; ``RuntimeError`` naming the window when every particle is
     dead there.  The caller's ``p_LU`` / ``p_SC`` are edited in place exactly as by ``run_simply_p``."""
-    from . import ensemble, engine
-    from .model import _engine_opts, _state_blocks
-
     if not obs_dict:
         raise ValueError("assimilate needs obs_dict: the observations that arrive")
     E = int(np.asarray(state['theta']).shape[1]) if state is not None else n_particles
@@ -129,30 +211,17 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
         if float(resample_threshold) < 1.0 and not forecast_weighted:
             raise ValueError("quantiles needs resample_threshold >= 1: the forecast bands are unweighted, which is right only for "
                              "equally weighted particles (or pass forecast_weighted=True for bands under the particles' weights)")
-        quantiles = [float(x) for x in np.atleast_1d(quantiles)]
-        if not 1 <= len(quantiles) <= 16 or not all(0.0 <= x <= 1.0 for x in quantiles):
-            raise ValueError("quantiles must be 1 to 16 probabilities in [0, 1]")
-        fc_names = list(known_m) if forecast_series is None else ([forecast_series] if isinstance(forecast_series, str) else list(forecast_series))
-        unknown = [c for c in fc_names if c not in abi.TQ_DERIVED_SERIES and c not in FLUX]
-        if unknown or not 1 <= len(fc_names) <= 32:
-            raise ValueError("forecast_series must be 1 to 32 names among %s and %s (unknown: %s)" % (abi.TQ_DERIVED_SERIES, FLUX, unknown))
-        fc_ids = [abi.TQ_DERIVED + abi.TQ_DERIVED_SERIES.index(c) if c in abi.TQ_DERIVED_SERIES else marshal.ALL_COLUMNS.index(c)
-                  for c in fc_names]
+        quantiles = request.probabilities('quantiles', quantiles)
+        fc_names, fc_ids, _ = request.series_ids('forecast_series', known_m if forecast_series is None else forecast_series,
+                                              "%s and %s" % (abi.TQ_DERIVED_SERIES, marshal.FLUX_COLUMNS), marshal.FLUX_COLUMNS)
     elif forecast_series is not None:
         raise ValueError("forecast_series needs quantiles: the probabilities of the bands")
     bounds = ensemble.window_bounds(met_df.index, window)
 
-    hs = _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables, lo, hi, out_reaches)
-    try:
-        scs, S = hs['scs'], len(hs['scs'])
-        sc_names = sc_ids = sc_obs = None
-        if score:                                                      # the df_R series with an observation, on any date, at some output reach
-            seen = {var for SC in hs['reaches'] if SC in obs_dict for var in abi.GOF_VARS
-                    if var in obs_dict[SC].columns and obs_dict[SC][var].notna().any()}
-            sc_names = [c for c, var in zip(abi.TQ_DERIVED_SERIES, abi.GOF_VARS) if var in seen]
-            sc_ids = [abi.TQ_DERIVED + abi.TQ_DERIVED_SERIES.index(c) for c in sc_names]
-            sc_obs = np.ascontiguousarray(np.stack([hs['obs'][:, abi.TQ_DERIVED_SERIES.index(c), :].T for c in sc_names])) \
-                if sc_names else None
+    with marshal.reference_edits(p_SU, p_LU, p_SC, p):
+        hs = _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables, lo, hi, out_reaches)
+        scs = hs['scs']
+        sc_names, sc_ids, sc_obs = request.observed_series(obs_dict, hs['reaches'], hs['obs']) if score else (None, None, None)
         if state is not None:
             theta0, lw0 = np.array(state['theta'], dtype=np.float64), np.array(state['lw'], dtype=np.float64)
             t0, day0 = int(state['t']), int(state['day'])
@@ -168,167 +237,51 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
         _check_inside(theta0, lo, hi, names)
         if t0 + len(bounds) >= 1 << 32 or day0 + len(met_df) >= 1 << 31:
             raise ValueError("the absolute window index must stay below 2^32 and the absolute day below 2^31")
-        mask = marshal.mask_of_columns(FLUX)
-        opts = _engine_opts(p_SU, p, dynamic_options, step_len, solver, mask, snow=hs['snow'])
-        if opts.out_slot_order:
-            raise ValueError("assimilate keeps members in particle order: solver['out_slot_order'] must stay 0")
-    except ValueError:
-        marshal.epilogue_mutations(p_SU, p_LU, p_SC, p)
-        raise
 
-    # ---- the device: everything is marshalled and uploaded once; from here on only info structs come back per window
-    eng = engine.get_engine(device)
-    torch = eng.torch
-    f64 = dict(dtype=torch.float64, device=eng.tdev)
-    forcing, doy = marshal.forcing_arrays(met_df, snow=hs['snow'])
-    f_d, doy_d = eng.to_device(forcing, torch.float64), eng.to_device(doy, torch.int32)
-    mp_d = eng.to_device(marshal.member_params(p, p_LU, E), torch.float64)
-    rp_d = eng.to_device(marshal.reach_params(p_SC, p, E), torch.float64)
-    ft_d = torch.full((E,), float(p['f_TDP']), **f64)
-    theta_d, lw_d, inc_d = eng.to_device(theta0, torch.float64), eng.to_device(lw0, torch.float64), torch.empty((E,), **f64)
-    for d in range(n_dim):                                             # the positions into the run's arrays
-        if target[d] >= 0:
-            mp_d[int(target[d])].copy_(theta_d[d])
-        elif target[d] == abi.MCMC_TARGET_F_TDP:
-            ft_d.copy_(theta_d[d])
-    state_d = None if st_in is None else eng.to_device(st_in, torch.float64).clone()
-    pairs = hs['pairs']
+        # ---- the device: everything is marshalled and uploaded once; from here on only info structs come back per window
+        dev = _DeviceEnsemble("assimilate keeps members in particle order", met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len,
+                              solver, device, E, marshal.FLUX_COLUMNS, hs['snow'])
+        eng, torch = dev.eng, dev.torch
+        s = SimpleNamespace(theta=eng.to_device(theta0, torch.float64), lw=eng.to_device(lw0, torch.float64),
+                            inc=torch.empty((E,), **dev.f64), state=None if st_in is None else eng.to_device(st_in, torch.float64).clone())
+        dev.write_positions(s.theta, target)
+        s.w, s.q, info = eng.pf_weights(s.lw)
+        s.lm_prev = particle.log_mean(info['lw_max'], info['sum_w'], E)
+        var_of = lambda c_: abi.GOF_VARS.index(variables[known_m.index(c_)]) if c_ in known_m else None
+        ov_at = [i for i, c_ in enumerate(fc_names or []) if c_ in known_m]
+        c = SimpleNamespace(index=met_df.index, seed=seed, day0=day0, target=target, lo=lo, hi=hi, m_dim=m_dim, m_const=m_const,
+                            resample_threshold=resample_threshold, move=move, record=record, score=score, quantiles=quantiles,
+                            forecast_weighted=forecast_weighted, fc_ids=fc_ids, ov_ids=[fc_ids[i] for i in ov_at],
+                            ov_vars=[var_of(fc_names[i]) for i in ov_at], sc_ids=sc_ids, sc_obs=sc_obs,
+                            sc_vars=[var_of(c_) for c_ in sc_names or []])
+        wins = [_window(dev, hs, s, c, t0 + n, d_lo, d_hi) for n, (d_lo, d_hi) in enumerate(bounds)]
 
-    def m_rows(series_vars):
-        """The error model's m [n, E] of the variables ``series_vars`` (indices of abi.GOF_VARS), from the positions."""
-        return torch.stack([theta_d[m_dim[v]] if m_dim[v] >= 0 else torch.full((E,), m_const[v], **f64) for v in series_vars]).contiguous()
-
-    out = dict(ess=[], log_evidence=[], resampled=[], n_unique=[], n_outside=[])
-    kms = {k: [] for k in STEPS + (('score',) if score else ())}
-    sc_parts = []
-    pilot_ms, wall_ms = [], []
-    rec = {k: [] for k in ('inc', 'q', 'ancestors', 'theta_before', 'theta_after', 'state_in', 'state_out')}
-    bands_po, bands_ov = [], []
-    ov_at = [i for i, c in enumerate(fc_names or []) if c in known_m]
-    host = lambda x: None if x is None else x.cpu().numpy()
-    w_d, q_d, info = eng.pf_weights(lw_d)
-    lm_prev = particle.log_mean(info['lw_max'], info['sum_w'], E)
-    try:
-        for n, (d_lo, d_hi) in enumerate(bounds):
-            t = t0 + n
-            torch.cuda.synchronize(eng.tdev)
-            w0 = time.perf_counter()
-            if record:
-                rec['theta_before'].append(host(theta_d))
-                rec['state_in'].append(host(state_d))
-            table_d, status_d, rstats = eng.run(f_d[:, :, d_lo:d_hi].contiguous(), doy_d[d_lo:d_hi].contiguous(), mp_d, rp_d, hs['up_ptr'],
-                                                hs['up_idx'], opts, out_reaches=hs['oreach'], state_in=state_d, state_out=True)
-            state_d = rstats['state']
-            kms['run'].append(rstats['kernel_ms'])
-            pilot_ms.append(rstats['pilot_ms'])
-            tkw = dict(f_tdp=ft_d, reach_params=rp_d, out_reaches=hs['oreach'])
-            if quantiles is not None:                                  # before the weighting
-                pkw = dict(seed=seed, day0=day0 + d_lo, **tkw)
-
-                def forecast_band(ids, **kw):
-                    if forecast_weighted:                              # under the weights the particles enter the window with
-                        return host(eng.predictive_bands(table_d, mask, quantiles, ids, weights=q_d, **dict(pkw, **kw))[0])
-                    lo_b, up_b, binfo = eng.predictive_bands(table_d, mask, quantiles, ids, **dict(pkw, **kw))
-                    return engine.interpolate_quantiles(host(lo_b), host(up_b), quantiles, binfo['n_used'])
-                bands_po.append(forecast_band(fc_ids))
-                if ov_at:
-                    em = m_rows([abi.GOF_VARS.index(variables[known_m.index(fc_names[i])]) for i in ov_at])
-                    bands_ov.append(forecast_band([fc_ids[i] for i in ov_at], err_m=em))
-            if sc_names:                                               # before the weighting, under the weights of entry
-                skw = dict(seed=seed, day0=day0 + d_lo, weights=q_d, include=(status_d & abi.STATUS_NONFINITE) == 0, **tkw)
-                sobs = np.ascontiguousarray(sc_obs[:, d_lo:d_hi])
-                po_w, ov_w = eng.predictive_scores(table_d, mask, sc_ids, sobs, **skw), None
-                if any(c in known_m for c in sc_names):                # the m the filter knows; 0 for the other series
-                    zero = torch.zeros((E,), **f64)
-                    em_all = torch.stack([m_rows([abi.GOF_VARS.index(variables[known_m.index(c)])])[0] if c in known_m else zero
-                                          for c in sc_names])
-                    ov_w = eng.predictive_scores(table_d, mask, sc_ids, sobs, err_m=em_all.contiguous(), **skw)
-                sc_parts.append((po_w, ov_w))
-                kms['score'].append(po_w[2]['kernel_ms'] + (0.0 if ov_w is None else ov_w[2]['kernel_ms']))
-            elif score:
-                kms['score'].append(0.0)
-            linfo = eng.pf_loglik(table_d, mask, hs['obs'][:, :, d_lo:d_hi], pairs, m_rows([v for v, _ in pairs]), lw_d, status=status_d,
-                                  inc=inc_d, accumulate=True, **tkw)
-            w_d, q_d, winfo = eng.pf_weights(lw_d, w_d, q_d)
-            kms['loglik'].append(linfo['kernel_ms'])
-            kms['weights'].append(winfo['kernel_ms'])
-            if record:
-                rec['inc'].append(host(inc_d))
-                rec['q'].append(host(q_d).astype(np.uint64))
-                rec['state_out'].append(host(state_d))
-            if winfo['T'] == 0:
-                raise RuntimeError("assimilate: every particle is dead in window %d (%s to %s): no log weight is finite -- the error "
-                                   "model's m or the prior box leaves no particle that explains the observations"
-                                   % (t, met_df.index[d_lo].date(), met_df.index[d_hi - 1].date()))
-            ess = particle.ess(winfo['sum_w'], winfo['sum_w2'])
-            lm = particle.log_mean(winfo['lw_max'], winfo['sum_w'], E)
-            out['ess'].append(ess)
-            out['log_evidence'].append(lm - lm_prev)
-            lm_prev = lm
-            do = ess < float(resample_threshold) * E
-            ms = dict(resample=0.0, gather=0.0, jitter=0.0)
-            n_unique, n_outside, anc_h = E, 0, None
-            if do:
-                anc_d, _, rinfo = eng.pf_resample(q_d, seed, t, offspring=False)
-                ms['resample'], n_unique = rinfo['kernel_ms'], rinfo['n_unique']
-                moved = []
-                for src in (state_d, mp_d, rp_d, ft_d, theta_d):       # everything a particle owns travels with it
-                    dst, ginfo = eng.gather_members(src, anc_d)
-                    ms['gather'] += ginfo['kernel_ms']
-                    moved.append(dst)
-                state_d, mp_d, rp_d, ft_d, theta_d = moved
-                lw_d.zero_()
-                lm_prev = 0.0
-                if forecast_weighted or score:                         # the next window's particles enter it equally weighted
-                    w_d, q_d, _ = eng.pf_weights(lw_d, w_d, q_d)
-                if move is not None:
-                    if move[0] == 'liu_west':
-                        a = move[1]
-                        centre = host(theta_d.mean(dim=1))
-                        scale = np.sqrt(1.0 - a * a) * host(theta_d.std(dim=1, unbiased=False))
-                    else:
-                        a, centre, scale = 1.0, np.zeros(n_dim), move[1]
-                    jinfo = eng.pf_jitter(theta_d, t, a, centre, scale, lo, hi, target, mp_d, ft_d, seed=seed)
-                    ms['jitter'], n_outside = jinfo['kernel_ms'], jinfo['n_outside']
-                anc_h = host(anc_d)
-            for k in ('resample', 'gather', 'jitter'):
-                kms[k].append(ms[k])
-            out['resampled'].append(bool(do))
-            out['n_unique'].append(int(n_unique))
-            out['n_outside'].append(int(n_outside))
-            if record:
-                rec['ancestors'].append(np.arange(E, dtype=np.int32) if anc_h is None else anc_h)
-                rec['theta_after'].append(host(theta_d))
-            torch.cuda.synchronize(eng.tdev)
-            wall_ms.append(1e3 * (time.perf_counter() - w0))
-    finally:
-        marshal.epilogue_mutations(p_SU, p_LU, p_SC, p)
-
-    theta, lw = host(theta_d), host(lw_d)
+    theta, lw = _host(s.theta), _host(s.lw)
     overrides, err_m = _shaped_for_the_ensemble(names, target, variables, m_dim, m_const, theta)
-    res = {k: np.array(v) for k, v in out.items()}
+    res = {k: np.array([w[k] for w in wins]) for k in ('ess', 'log_evidence', 'resampled', 'n_unique', 'n_outside')}
     res.update(names=names, windows=[(met_df.index[a_], met_df.index[b_ - 1], int(a_), int(b_)) for a_, b_ in bounds],
-               log_evidence_total=float(np.sum(res['log_evidence'])), kernel_ms=kms, pilot_ms=pilot_ms, wall_ms=wall_ms,
+               log_evidence_total=float(np.sum(res['log_evidence'])),
+               kernel_ms={k: [w['ms'][k] for w in wins] for k in STEPS + (('score',) if score else ())},
+               pilot_ms=[w['pilot_ms'] for w in wins], wall_ms=[w['wall_ms'] for w in wins],
                theta=theta, log_weights=lw, overrides=overrides, error_m=err_m,
-               state=dict(rows=list(abi.STATE_ROWS), reaches=list(scs), data=host(state_d), end=pd.Timestamp(met_df.index[-1]),
+               state=dict(rows=list(abi.STATE_ROWS), reaches=list(scs), data=_host(s.state), end=pd.Timestamp(met_df.index[-1]),
                           theta=theta.copy(), lw=lw.copy(), t=t0 + len(bounds), seed=seed, day=day0 + len(met_df)))
     if quantiles is not None:
-        res['forecast'] = dict(q=list(quantiles), series=list(fc_names), param_only=np.concatenate(bands_po, axis=2),
+        res['forecast'] = dict(q=list(quantiles), series=list(fc_names), param_only=np.concatenate([w['band_po'] for w in wins], axis=2),
                                overall_series=[fc_names[i] for i in ov_at],
-                               overall=np.concatenate(bands_ov, axis=2) if ov_at else None, day0=day0)
+                               overall=np.concatenate([w['band_ov'] for w in wins], axis=2) if ov_at else None, day0=day0)
         if forecast_weighted:
             res['forecast']['rule'] = 'inverted_cdf'
     if score:
-        res['scores'] = _joined_scores(sc_names, hs['reaches'], sc_obs, sc_parts, seed, day0)
+        res['scores'] = _joined_scores(sc_names, hs['reaches'], sc_obs, [w['scores'] for w in wins if 'scores' in w], seed, day0)
     if record:
-        res.update(rec)
+        res.update({k: [w['rec'][k] for w in wins] for k in ('inc', 'q', 'ancestors', 'theta_before', 'theta_after', 'state_in', 'state_out')})
     return res
 
 
 def _joined_scores(series, reaches, obs, parts, seed, day0):
     """The windows' scores laid end to end along the day axis, in the shape of ``run_simply_p_ensemble(score=True)['scores']``;
     ``weight_total``, ``n_members`` and ``info`` are one entry per window (a window's pit is taken with its own total)."""
-    from .model import _scores_result, _mean_crps
     if not series or not parts:
         return _scores_result([], reaches, None, 0 if obs is None else obs.shape[1], None, seed, day0)
     at, wins = 0, []
@@ -347,4 +300,4 @@ def _joined_scores(series, reaches, obs, parts, seed, day0):
                 info=dict(param_only=[w['info']['param_only'] for w in wins], overall=[w['info']['overall'] for w in wins]))
 
 
-assimilate.__doc__ = assimilate.__doc__ % (FLUX, list(STEPS))
+assimilate.__doc__ = assimilate.__doc__ % (marshal.FLUX_COLUMNS, list(STEPS))

@@ -10,7 +10,8 @@ import time
 
 import numpy as np
 
-from . import abi, marshal, mcmc, neldermead, predictive, priors as _priors
+from . import abi, marshal, mcmc, neldermead, predictive, priors as _priors, visualise_results as vr
+from .model import _DeviceEnsemble
 from .priors import box as _box
 
 START_SERIES = 0x53544152        # "STAR": the counter's fourth word of the start ball's normals
@@ -54,16 +55,10 @@ def _plan(priors, variables, error_m, check_shape):
 
 
 def _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables, lo, hi, out_reaches):
-    """What a calibration call works out on the host before it touches the device: the reference's prologue, the topology, the
+    """What a calibration call works out on the host, after the prologue and before it touches the device: the topology, the
     observations and the (variable, output reach) pairs of the likelihood, the input checks at the box's corners, the snow rule,
     the workbook's member parameters.  Raises ValueError."""
-    from . import visualise_results as vr
-
-    marshal.prologue(p_SU, p_LU, p_SC, p)
-    scs = marshal.sc_list(p)
-    up_ptr, up_idx, _ = marshal.topology(p_struc, p)
-    reaches = scs if out_reaches is None else list(out_reaches)
-    oreach = None if out_reaches is None else [scs.index(int(r)) for r in out_reaches]
+    scs, up_ptr, up_idx, reaches, oreach = marshal.catchment(p_struc, p, out_reaches)
     obs = vr.observation_array(obs_dict, reaches, met_df.index)
     n_obs = (~np.isnan(obs)).sum(axis=-1)                                 # [R, 6]
     pairs = []
@@ -85,41 +80,27 @@ def _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables
 
 
 class _Evaluator:
-    """The device side both calls share: everything is marshalled and uploaded once, for an ensemble of ``n_members``; then
-    ``evaluate()`` is the model and the likelihood at the run points ``mp_d`` / ``ft_d`` hold, for the points in ``prop_d``: the log
-    posterior in ``lpp_d``."""
+    """The device side both calls share: an ensemble of ``n_members`` uploaded once (``dev``) and the buffers of one evaluation;
+    ``evaluate()`` is the model and the likelihood at the run points ``dev.mp_d`` / ``dev.ft_d`` hold: the log posterior in ``lpp_d``."""
 
     def __init__(self, order, hs, met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len, solver, device, n_members, n_dim,
                  m_dim, m_const):
-        from . import engine
-        from .model import _engine_opts
-
-        self.eng = eng = engine.get_engine(device)
-        self.torch = torch = eng.torch
-        cols = ['Qr', 'Msus_kg/day', 'TDP_kg/day', 'PP_kg/day']              # what simplyp_gof reads
-        self.mask = marshal.mask_of_columns(cols)
-        self.opts = _engine_opts(p_SU, p, dynamic_options, step_len, solver, self.mask, snow=hs['snow'])
-        if self.opts.out_slot_order:
-            raise ValueError("%s: solver['out_slot_order'] must stay 0" % order)
-        forcing, doy = marshal.forcing_arrays(met_df, snow=hs['snow'])
-        self.f_d, self.doy_d = eng.to_device(forcing, torch.float64), eng.to_device(doy, torch.int32)
-        self.mp_d = eng.to_device(marshal.member_params(p, p_LU, n_members), torch.float64)
-        self.rp_d = eng.to_device(marshal.reach_params(p_SC, p, n_members), torch.float64)
-        self.f64 = f64 = dict(dtype=torch.float64, device=eng.tdev)
-        self.ft_d = torch.full((n_members,), float(p['f_TDP']), **f64)
+        self.dev = dev = _DeviceEnsemble(order, met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len, solver, device, n_members,
+                                         marshal.FLUX_COLUMNS, hs['snow'])        # the columns simplyp_gof reads
+        torch, f64 = dev.torch, dev.f64
         D, R = len(met_df), len(hs['reaches'])
-        self.out_d = torch.empty((len(cols), D, R, n_members), **f64)
+        self.out_d = torch.empty((len(marshal.FLUX_COLUMNS), D, R, n_members), **f64)
         self.gof_d = torch.empty((len(abi.GOF_STATS), len(abi.GOF_VARS), R, n_members), **f64)
         self.prop_d, self.lpp_d = torch.empty((n_dim, n_members), **f64), torch.empty((n_members,), **f64)
-        self.inside_d = torch.ones((n_members,), dtype=torch.int32, device=eng.tdev)
+        self.inside_d = torch.ones((n_members,), dtype=torch.int32, device=dev.eng.tdev)
         self.hs, self.m_dim, self.m_const = hs, m_dim, m_const
 
     def evaluate(self):
         """Returns the kernel times of the run, the goodness of fit and the log posterior, in ms."""
-        hs, eng = self.hs, self.eng
-        _, status_d, rstats = eng.run(self.f_d, self.doy_d, self.mp_d, self.rp_d, hs['up_ptr'], hs['up_idx'], self.opts,
+        hs, dev, eng = self.hs, self.dev, self.dev.eng
+        _, status_d, rstats = eng.run(dev.f_d, dev.doy_d, dev.mp_d, dev.rp_d, hs['up_ptr'], hs['up_idx'], dev.opts,
                                       out_reaches=hs['oreach'], out=self.out_d)
-        _, ginfo = eng.gof(self.out_d, self.mask, hs['obs'], self.ft_d, self.rp_d, out_reaches=hs['oreach'], gof=self.gof_d)
+        _, ginfo = eng.gof(self.out_d, dev.mask, hs['obs'], dev.ft_d, dev.rp_d, out_reaches=hs['oreach'], gof=self.gof_d)
         linfo = eng.mcmc_log_prob(self.gof_d, hs['pairs'], self.m_dim, self.m_const, self.prop_d, self.lpp_d, status=status_d,
                                   inside=self.inside_d)
         return rstats['kernel_ms'], ginfo['kernel_ms'], linfo['kernel_ms']
@@ -210,84 +191,79 @@ def sample_posterior(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_
     if not 0 <= seed < 1 << 64 or thin < 1 or n_steps < 0:
         raise ValueError("seed must be in [0, 2^64), thin >= 1 and n_steps >= 0")
 
-    hs = _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables, lo, hi, out_reaches)
-    if state is not None:
-        theta0 = np.array(state['theta'], dtype=np.float64)
-        lp0 = np.array(state['lp'], dtype=np.float64)
-        nacc0 = np.array(state['n_accept'], dtype=np.int32)
-        t0 = int(state['t'])
-        if theta0.shape != (n_dim, W) or lp0.shape != (W,) or nacc0.shape != (W,) or t0 < 0:
-            raise ValueError("state does not match this call: theta %s for %d names and %d walkers" % (theta0.shape, n_dim, W))
-    else:
-        t0, lp0, nacc0 = 0, None, np.zeros(W, dtype=np.int32)
-        if start is None:
-            theta0 = start_ball(hs['centre'], priors, W, seed)
+    with marshal.reference_edits(p_SU, p_LU, p_SC, p):
+        hs = _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables, lo, hi, out_reaches)
+        if state is not None:
+            theta0 = np.array(state['theta'], dtype=np.float64)
+            lp0 = np.array(state['lp'], dtype=np.float64)
+            nacc0 = np.array(state['n_accept'], dtype=np.int32)
+            t0 = int(state['t'])
+            if theta0.shape != (n_dim, W) or lp0.shape != (W,) or nacc0.shape != (W,) or t0 < 0:
+                raise ValueError("state does not match this call: theta %s for %d names and %d walkers" % (theta0.shape, n_dim, W))
         else:
-            theta0 = np.array(start, dtype=np.float64)
-            if theta0.shape != (n_dim, W):
-                raise ValueError("start must have shape [n_dim, n_walkers] = %s, got %s" % ((n_dim, W), theta0.shape))
-    _check_inside(theta0, lo, hi, names)
-    if t0 + n_steps >= 1 << 32:
-        raise ValueError("the absolute step index must stay below 2^32")
+            t0, lp0, nacc0 = 0, None, np.zeros(W, dtype=np.int32)
+            if start is None:
+                theta0 = start_ball(hs['centre'], priors, W, seed)
+            else:
+                theta0 = np.array(start, dtype=np.float64)
+                if theta0.shape != (n_dim, W):
+                    raise ValueError("start must have shape [n_dim, n_walkers] = %s, got %s" % ((n_dim, W), theta0.shape))
+        _check_inside(theta0, lo, hi, names)
+        if t0 + n_steps >= 1 << 32:
+            raise ValueError("the absolute step index must stay below 2^32")
 
-    # ---- the device: everything is marshalled and uploaded once, for an ensemble of h members
-    ev = _Evaluator("sample_posterior keeps members in walker order", hs, met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len,
-                    solver, device, h, n_dim, m_dim, m_const)
-    eng, torch, f64 = ev.eng, ev.torch, ev.f64
-    mp_d, ft_d, prop_d, lpp_d, inside_d, evaluate = ev.mp_d, ev.ft_d, ev.prop_d, ev.lpp_d, ev.inside_d, ev.evaluate
-    theta_d = eng.to_device(theta0, torch.float64)
-    nacc_d = eng.to_device(nacc0, torch.int32)
-    kept = [t for t in range(t0, t0 + n_steps) if (t + 1) % thin == 0]
-    chain_d = torch.empty((len(kept), n_dim + 1, W), **f64)
-    if record_proposals:
-        props_d, plp_d = torch.empty((n_steps, n_dim, W), **f64), torch.empty((n_steps, W), **f64)
-    stats = dict(wall_ms=[], run_kernel_ms=[], gof_ms=[], sampler_ms=[], n_inside=[], n_accepted=[],
-                 start_wall_ms=[], start_run_kernel_ms=[])
+        # ---- the device: everything is marshalled and uploaded once, for an ensemble of h members
+        ev = _Evaluator("sample_posterior keeps members in walker order", hs, met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len,
+                        solver, device, h, n_dim, m_dim, m_const)
+        dev, prop_d, lpp_d, inside_d, evaluate = ev.dev, ev.prop_d, ev.lpp_d, ev.inside_d, ev.evaluate
+        eng, torch, f64, mp_d, ft_d = dev.eng, dev.torch, dev.f64, dev.mp_d, dev.ft_d
+        theta_d = eng.to_device(theta0, torch.float64)
+        nacc_d = eng.to_device(nacc0, torch.int32)
+        kept = [t for t in range(t0, t0 + n_steps) if (t + 1) % thin == 0]
+        chain_d = torch.empty((len(kept), n_dim + 1, W), **f64)
+        if record_proposals:
+            props_d, plp_d = torch.empty((n_steps, n_dim, W), **f64), torch.empty((n_steps, W), **f64)
+        stats = dict(wall_ms=[], run_kernel_ms=[], gof_ms=[], sampler_ms=[], n_inside=[], n_accepted=[],
+                     start_wall_ms=[], start_run_kernel_ms=[])
 
-    if lp0 is None:                               # the start's log posterior: one evaluation per half, through the same kernels
-        lp_d = torch.empty((W,), **f64)
-        for k in (0, 1):
-            sl = slice(k * h, (k + 1) * h)
-            torch.cuda.synchronize(eng.tdev)
-            w0 = time.perf_counter()
-            prop_d.copy_(theta_d[:, sl])
-            for d in range(n_dim):
-                if target[d] >= 0:
-                    mp_d[int(target[d])].copy_(theta_d[d, sl])
-                elif target[d] == abi.MCMC_TARGET_F_TDP:
-                    ft_d.copy_(theta_d[d, sl])
-            run_ms = evaluate()[0]
-            lp_d[sl].copy_(lpp_d)
-            torch.cuda.synchronize(eng.tdev)
-            stats['start_wall_ms'].append(1e3 * (time.perf_counter() - w0))
-            stats['start_run_kernel_ms'].append(run_ms)
-        lp_host = lp_d.cpu().numpy()
-        if not np.isfinite(lp_host).all():
-            marshal.epilogue_mutations(p_SU, p_LU, p_SC, p)
-            raise ValueError("the start has a non-finite log posterior at walker %d (%r): the model or the likelihood fails there"
-                             % (int(np.argmin(np.isfinite(lp_host))), float(lp_host[int(np.argmin(np.isfinite(lp_host)))])))
-    else:
-        lp_d = eng.to_device(lp0, torch.float64)
+        if lp0 is None:                               # the start's log posterior: one evaluation per half, through the same kernels
+            lp_d = torch.empty((W,), **f64)
+            for k in (0, 1):
+                sl = slice(k * h, (k + 1) * h)
+                torch.cuda.synchronize(eng.tdev)
+                w0 = time.perf_counter()
+                prop_d.copy_(theta_d[:, sl])
+                dev.write_positions(theta_d[:, sl], target)
+                run_ms = evaluate()[0]
+                lp_d[sl].copy_(lpp_d)
+                torch.cuda.synchronize(eng.tdev)
+                stats['start_wall_ms'].append(1e3 * (time.perf_counter() - w0))
+                stats['start_run_kernel_ms'].append(run_ms)
+            lp_host = lp_d.cpu().numpy()
+            if not np.isfinite(lp_host).all():
+                raise ValueError("the start has a non-finite log posterior at walker %d (%r): the model or the likelihood fails there"
+                                 % (int(np.argmin(np.isfinite(lp_host))), float(lp_host[int(np.argmin(np.isfinite(lp_host)))])))
+        else:
+            lp_d = eng.to_device(lp0, torch.float64)
 
-    lp_start = lp_d.cpu().numpy()
-    for n, t in enumerate(range(t0, t0 + n_steps)):
-        row = chain_d[kept.index(t)] if (t + 1) % thin == 0 else None
-        for k in (0, 1):
-            torch.cuda.synchronize(eng.tdev)
-            w0 = time.perf_counter()
-            pinfo = eng.mcmc_propose(theta_d, k, t, lo, hi, target, prop_d, inside_d, mp_d, ft_d, a=a, seed=seed)
-            run_ms, gof_ms, lp_ms = evaluate()
-            ainfo = eng.mcmc_accept(theta_d, lp_d, nacc_d, k, t, prop_d, inside_d, lpp_d, chain_row=row, a=a, seed=seed)
-            stats['wall_ms'].append(1e3 * (time.perf_counter() - w0))
-            stats['run_kernel_ms'].append(run_ms)
-            stats['gof_ms'].append(gof_ms)
-            stats['sampler_ms'].append(pinfo['kernel_ms'] + lp_ms + ainfo['kernel_ms'])
-            stats['n_inside'].append(pinfo['n_inside'])
-            stats['n_accepted'].append(ainfo['n_accepted'])
-            if record_proposals:
-                props_d[n, :, k * h:(k + 1) * h].copy_(prop_d)
-                plp_d[n, k * h:(k + 1) * h].copy_(lpp_d)
-    marshal.epilogue_mutations(p_SU, p_LU, p_SC, p)
+        lp_start = lp_d.cpu().numpy()
+        for n, t in enumerate(range(t0, t0 + n_steps)):
+            row = chain_d[kept.index(t)] if (t + 1) % thin == 0 else None
+            for k in (0, 1):
+                torch.cuda.synchronize(eng.tdev)
+                w0 = time.perf_counter()
+                pinfo = eng.mcmc_propose(theta_d, k, t, lo, hi, target, prop_d, inside_d, mp_d, ft_d, a=a, seed=seed)
+                run_ms, gof_ms, lp_ms = evaluate()
+                ainfo = eng.mcmc_accept(theta_d, lp_d, nacc_d, k, t, prop_d, inside_d, lpp_d, chain_row=row, a=a, seed=seed)
+                stats['wall_ms'].append(1e3 * (time.perf_counter() - w0))
+                stats['run_kernel_ms'].append(run_ms)
+                stats['gof_ms'].append(gof_ms)
+                stats['sampler_ms'].append(pinfo['kernel_ms'] + lp_ms + ainfo['kernel_ms'])
+                stats['n_inside'].append(pinfo['n_inside'])
+                stats['n_accepted'].append(ainfo['n_accepted'])
+                if record_proposals:
+                    props_d[n, :, k * h:(k + 1) * h].copy_(prop_d)
+                    plp_d[n, k * h:(k + 1) * h].copy_(lpp_d)
 
     chain = chain_d.cpu().numpy()
     theta, lp, n_accept = theta_d.cpu().numpy(), lp_d.cpu().numpy(), nacc_d.cpu().numpy()
@@ -348,59 +324,58 @@ def find_map(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, pr
     if not 0 <= seed < 1 << 64 or max_iter < 1 or not float(xatol) >= 0.0 or not float(fatol) >= 0.0:
         raise ValueError("seed must be in [0, 2^64), max_iter >= 1, xatol and fatol >= 0")
 
-    hs = _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables, lo, hi, out_reaches)
-    if state is not None:
-        st = neldermead.copy_state({k: state[k] for k in ('sim', 'fsim', 'phase', 'cursor', 'n_iter', 'status', 'counts')})
-        if st['sim'].shape != (n_dim + 1, n_dim, S) or st['fsim'].shape != (n_dim + 1, S):
-            raise ValueError("state does not match this call: sim %s for %d names" % (st['sim'].shape, n_dim))
-        neldermead.resume(st, max_iter, xatol, fatol)
-        hist0 = np.asarray(state['history'], dtype=np.float64)
-    else:
-        if init_guess is None:
-            x0 = neldermead.uniform_starts(seed, n_dim, S, lo, hi)
-            x0[:, 0] = hs['centre']
+    with marshal.reference_edits(p_SU, p_LU, p_SC, p):
+        hs = _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables, lo, hi, out_reaches)
+        if state is not None:
+            st = neldermead.copy_state({k: state[k] for k in ('sim', 'fsim', 'phase', 'cursor', 'n_iter', 'status', 'counts')})
+            if st['sim'].shape != (n_dim + 1, n_dim, S) or st['fsim'].shape != (n_dim + 1, S):
+                raise ValueError("state does not match this call: sim %s for %d names" % (st['sim'].shape, n_dim))
+            neldermead.resume(st, max_iter, xatol, fatol)
+            hist0 = np.asarray(state['history'], dtype=np.float64)
         else:
-            x0 = np.array(init_guess, dtype=np.float64)
-            if x0.shape != (n_dim, S):
-                raise ValueError("init_guess must have shape [n_dim, n_starts] = %s, got %s" % ((n_dim, S), x0.shape))
-        st = neldermead.new_state(neldermead.initial_simplex(x0, lo, hi))
-        hist0 = np.empty((0, S))
-    hist = np.full((max_iter, S), np.nan)
-    hist[:min(len(hist0), max_iter)] = hist0[:max_iter]
-    begin = dict(neldermead.copy_state(st), history=hist.copy())
+            if init_guess is None:
+                x0 = neldermead.uniform_starts(seed, n_dim, S, lo, hi)
+                x0[:, 0] = hs['centre']
+            else:
+                x0 = np.array(init_guess, dtype=np.float64)
+                if x0.shape != (n_dim, S):
+                    raise ValueError("init_guess must have shape [n_dim, n_starts] = %s, got %s" % ((n_dim, S), x0.shape))
+            st = neldermead.new_state(neldermead.initial_simplex(x0, lo, hi))
+            hist0 = np.empty((0, S))
+        hist = np.full((max_iter, S), np.nan)
+        hist[:min(len(hist0), max_iter)] = hist0[:max_iter]
+        begin = dict(neldermead.copy_state(st), history=hist.copy())
 
-    # ---- the device: everything is marshalled and uploaded once, for an ensemble of 4 S members
-    ev = _Evaluator("find_map keeps members in slot order", hs, met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len, solver,
-                    device, neldermead.SLOTS * S, n_dim, m_dim, m_const)
-    eng, torch = ev.eng, ev.torch
-    sim_d, fsim_d = eng.to_device(st['sim'], torch.float64), eng.to_device(st['fsim'], torch.float64)
-    ist_d = eng.to_device(neldermead.pack_istate(st), torch.int32)
-    hist_d = eng.to_device(hist, torch.float64)
-    stats = dict(wall_ms=[], run_kernel_ms=[], gof_ms=[], optimiser_ms=[], n_active=[], n_shrinking=[])
-    evals, evals_lp = [], []
-    n_active = int((st['phase'] != neldermead.DONE).sum())
-    while n_active:
-        torch.cuda.synchronize(eng.tdev)
-        w0 = time.perf_counter()
-        pinfo = eng.nm_propose(sim_d, ist_d, lo, hi, target, ev.prop_d, ev.inside_d, ev.mp_d, ev.ft_d)
-        run_ms, gof_ms, lp_ms = ev.evaluate()
-        uinfo = eng.nm_update(sim_d, fsim_d, ist_d, ev.prop_d, ev.inside_d, ev.lpp_d, max_iter, xatol, fatol, history=hist_d)
-        stats['wall_ms'].append(1e3 * (time.perf_counter() - w0))
-        stats['run_kernel_ms'].append(run_ms)
-        stats['gof_ms'].append(gof_ms)
-        stats['optimiser_ms'].append(pinfo['kernel_ms'] + lp_ms + uinfo['kernel_ms'])
-        stats['n_active'].append(pinfo['n_active'])
-        stats['n_shrinking'].append(pinfo['n_shrinking'])
-        if record_evaluations:
-            evals.append(ev.prop_d.clone())
-            evals_lp.append(ev.lpp_d.clone())
-        if uinfo['n_nonfinite_start']:
-            marshal.epilogue_mutations(p_SU, p_LU, p_SC, p)
-            bad = int(np.argmax(ist_d[abi.NM_ISTATE.index('status')].cpu().numpy() == neldermead.NONFINITE_START))
-            raise ValueError("the start of simplex %d has a vertex with a non-finite log posterior: the model or the likelihood "
-                             "fails there" % bad)
-        n_active = uinfo['n_active']
-    marshal.epilogue_mutations(p_SU, p_LU, p_SC, p)
+        # ---- the device: everything is marshalled and uploaded once, for an ensemble of 4 S members
+        ev = _Evaluator("find_map keeps members in slot order", hs, met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len, solver,
+                        device, neldermead.SLOTS * S, n_dim, m_dim, m_const)
+        eng, torch = ev.dev.eng, ev.dev.torch
+        sim_d, fsim_d = eng.to_device(st['sim'], torch.float64), eng.to_device(st['fsim'], torch.float64)
+        ist_d = eng.to_device(neldermead.pack_istate(st), torch.int32)
+        hist_d = eng.to_device(hist, torch.float64)
+        stats = dict(wall_ms=[], run_kernel_ms=[], gof_ms=[], optimiser_ms=[], n_active=[], n_shrinking=[])
+        evals, evals_lp = [], []
+        n_active = int((st['phase'] != neldermead.DONE).sum())
+        while n_active:
+            torch.cuda.synchronize(eng.tdev)
+            w0 = time.perf_counter()
+            pinfo = eng.nm_propose(sim_d, ist_d, lo, hi, target, ev.prop_d, ev.inside_d, ev.dev.mp_d, ev.dev.ft_d)
+            run_ms, gof_ms, lp_ms = ev.evaluate()
+            uinfo = eng.nm_update(sim_d, fsim_d, ist_d, ev.prop_d, ev.inside_d, ev.lpp_d, max_iter, xatol, fatol, history=hist_d)
+            stats['wall_ms'].append(1e3 * (time.perf_counter() - w0))
+            stats['run_kernel_ms'].append(run_ms)
+            stats['gof_ms'].append(gof_ms)
+            stats['optimiser_ms'].append(pinfo['kernel_ms'] + lp_ms + uinfo['kernel_ms'])
+            stats['n_active'].append(pinfo['n_active'])
+            stats['n_shrinking'].append(pinfo['n_shrinking'])
+            if record_evaluations:
+                evals.append(ev.prop_d.clone())
+                evals_lp.append(ev.lpp_d.clone())
+            if uinfo['n_nonfinite_start']:
+                bad = int(np.argmax(ist_d[abi.NM_ISTATE.index('status')].cpu().numpy() == neldermead.NONFINITE_START))
+                raise ValueError("the start of simplex %d has a vertex with a non-finite log posterior: the model or the likelihood "
+                                 "fails there" % bad)
+            n_active = uinfo['n_active']
 
     st['sim'], st['fsim'] = sim_d.cpu().numpy(), fsim_d.cpu().numpy()
     neldermead.unpack_istate(ist_d.cpu().numpy(), st)

@@ -6,6 +6,8 @@ arrays ``include/simplyp.h`` describes, and reproduces the host-side prologue
 of the reference (model.py:311-361: derived rows, validation, in-place edits).
 """
 
+import contextlib
+
 import numpy as np
 import pandas as pd
 
@@ -50,6 +52,7 @@ ALL_COLUMNS = OUT_COLUMNS + [SNOW_COLUMN]
 MASK_D_SNOW = 1 << ALL_COLUMNS.index(SNOW_COLUMN)
 REACH5_COLUMNS = ['Vr', 'Qr', 'Msus_kg/day', 'TDP_kg/day', 'PP_kg/day']     # model.py:272-277
 MASK_REACH5 = sum(1 << OUT_COLUMNS.index(c) for c in REACH5_COLUMNS)
+FLUX_COLUMNS = ['Qr', 'Msus_kg/day', 'TDP_kg/day', 'PP_kg/day']             # what the goodness of fit and the df_R series read
 
 
 def columns_of_mask(mask):
@@ -118,6 +121,27 @@ def epilogue_mutations(p_SU, p_LU, p_SC, p):
             p_LU.loc['TDPs0', LU] = p_LU[LU]['EPC0_0'] * p['fc'] if LU == 'A' else 0
         if pd.isna(p_SC.loc['TDPeff', SC]):
             p_SC.loc['TDPeff', SC] = 0.
+
+
+@contextlib.contextmanager
+def reference_edits(p_SU, p_LU, p_SC, p):
+    """The one rule for the reference's in-place edits of ``p_LU`` / ``p_SC``: entering runs ``prologue``, leaving -- by return or
+    exception -- ``epilogue_mutations``: the frames hold what a completed ``run_simply_p`` leaves.  A raising prologue ends it."""
+    nc_types = prologue(p_SU, p_LU, p_SC, p)
+    try:
+        yield nc_types
+    finally:
+        epilogue_mutations(p_SU, p_LU, p_SC, p)
+
+
+def catchment(p_struc, p, out_reaches=None):
+    """(scs, up_ptr, up_idx, reaches, oreach) of a run, after the prologue: the sub-catchments in run order, the CSR of their
+    directly-upstream reaches, the output reaches as ids and as positions in ``scs`` (None = all)."""
+    scs = sc_list(p)
+    up_ptr, up_idx, _ = topology(p_struc, p)
+    if out_reaches is None:
+        return scs, up_ptr, up_idx, scs, None
+    return scs, up_ptr, up_idx, list(out_reaches), [scs.index(int(r)) for r in out_reaches]
 
 
 def topology(p_struc, p):

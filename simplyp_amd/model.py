@@ -13,12 +13,14 @@ them); they are not used by ``run_simply_p``.
 """
 
 import os
+from collections import namedtuple
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pandas as pd
 
-from . import abi, marshal
-from . import helper_functions as hf
+from . import abi, engine, ensemble, marshal, request, weighted
+from . import helper_functions as hf, pareto as pareto_rules, score as score_rules, visualise_results as vr
 
 
 # ------------------------------------------------------------------------------------------
@@ -136,6 +138,33 @@ def _engine_opts(p_SU, p, dynamic_options, step_len, solver, out_mask, n_periods
                          out_mask=out_mask, step_len=step_len, n_periods=n_periods, snow=snow)
 
 
+class _DeviceEnsemble(object):
+    """An ensemble of ``E`` workbook members, marshalled and uploaded once -- forcing, ``doy``, ``member_params``, ``reach_params``,
+    ``f_tdp`` -- with the options of a table of ``columns``.  Its callers keep members in their own order: ``out_slot_order`` is refused."""
+
+    def __init__(self, order, met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len, solver, device, E, columns, snow, n_periods=0):
+        self.mask = marshal.mask_of_columns(columns)
+        self.opts = _engine_opts(p_SU, p, dynamic_options, step_len, solver, self.mask, n_periods=n_periods, snow=snow)
+        if self.opts.out_slot_order:
+            raise ValueError("%s: solver['out_slot_order'] must stay 0" % order)
+        self.eng = eng = engine.get_engine(device)
+        self.torch = torch = eng.torch
+        self.f64 = dict(dtype=torch.float64, device=eng.tdev)
+        forcing, doy = marshal.forcing_arrays(met_df, snow=snow)
+        self.f_d, self.doy_d = eng.to_device(forcing, torch.float64), eng.to_device(doy, torch.int32)
+        self.mp_d = eng.to_device(marshal.member_params(p, p_LU, E), torch.float64)
+        self.rp_d = eng.to_device(marshal.reach_params(p_SC, p, E), torch.float64)
+        self.ft_d = torch.full((E,), float(p['f_TDP']), **self.f64)
+
+    def write_positions(self, theta_d, target):
+        """The positions ``theta_d[n_dim, E]`` into the run's arrays: row ``target[d]`` of ``member_params``, or ``f_tdp``."""
+        for d in range(len(target)):
+            if target[d] >= 0:
+                self.mp_d[int(target[d])].copy_(theta_d[d])
+            elif target[d] == abi.MCMC_TARGET_F_TDP:
+                self.ft_d.copy_(theta_d[d])
+
+
 def _kf_last(p_SU, p_LU, p_SC, p):
     """Kf as the reference returns it: the value of the last sub-catchment (model.py:449-453, :827)."""
     SC = marshal.sc_list(p)[-1]
@@ -143,7 +172,6 @@ def _kf_last(p_SU, p_LU, p_SC, p):
         return 10**-6 * (p_LU['A']['SoilPconc'] - p_LU['S']['SoilPconc']) / \
             hf.UC_Cinv(p_LU['A']['EPC0_init_mgl'], p_SC.loc['A_catch', SC])
     return p['Kf']
-
 
 
 def _output_dict(stats, status, solver):
@@ -211,25 +239,23 @@ def run_simply_p(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, step_len
     ``run_simply_p_ensemble`` -- the model state after the last day comes back as ``output_dict['state']``, and a later
     call over the following dates given that dict as ``initial_state`` continues the run bit for bit.
     """
-    from . import engine
 
     # derived parameters, validation, in-place edits of p_LU / p_SC (model.py:311-361)
-    marshal.prologue(p_SU, p_LU, p_SC, p)
-    scs = marshal.sc_list(p)
-    up_ptr, up_idx, up_lists = marshal.topology(p_struc, p)
-    mp = marshal.member_params(p, p_LU, 1)
-    rp = marshal.reach_params(p_SC, p, 1)
-    forcing, doy = marshal.forcing_arrays(met_df)
-    opts = _engine_opts(p_SU, p, dynamic_options, step_len, solver, marshal.MASK_ALL)
-    st_in = None if initial_state is None else _state_blocks(initial_state, scs, 1, met_df.index, [(0, 1)])[0]
+    with marshal.reference_edits(p_SU, p_LU, p_SC, p):
+        scs = marshal.sc_list(p)
+        up_ptr, up_idx, up_lists = marshal.topology(p_struc, p)
+        mp = marshal.member_params(p, p_LU, 1)
+        rp = marshal.reach_params(p_SC, p, 1)
+        forcing, doy = marshal.forcing_arrays(met_df)
+        opts = _engine_opts(p_SU, p, dynamic_options, step_len, solver, marshal.MASK_ALL)
+        st_in = None if initial_state is None else _state_blocks(initial_state, scs, 1, met_df.index, [(0, 1)])[0]
 
-    eng = engine.get_engine(device)          # raises when the HIP library / device is missing
-    out_d, status_d, stats = eng.run(forcing, doy, mp, rp, up_ptr, up_idx, opts, state_in=st_in,
-                                     state_out=True if return_state else None)
-    state_d = stats.pop('state', None)
-    out = out_d.cpu().numpy()                # [25, D, S, 1]
-    status = int(status_d.cpu().numpy()[0])
-    marshal.epilogue_mutations(p_SU, p_LU, p_SC, p)
+        eng = engine.get_engine(device)          # raises when the HIP library / device is missing
+        out_d, status_d, stats = eng.run(forcing, doy, mp, rp, up_ptr, up_idx, opts, state_in=st_in,
+                                         state_out=True if return_state else None)
+        state_d = stats.pop('state', None)
+        out = out_d.cpu().numpy()                # [25, D, S, 1]
+        status = int(status_d.cpu().numpy()[0])
 
     df_TC_dict, df_R_dict = {}, {}
     for j, SC in enumerate(scs):
@@ -290,12 +316,10 @@ def run_simply_p(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, step_len
     return (df_TC_dict, df_R_dict, Kf, output_dict)                                          # :827
 
 
-
 def _host_table(shape, pin):
     """Host array that receives an ensemble's output table: page-locked (the streamed copies then run at PCIe speed beside the
     kernel) when the host can lock that much -- not more than 60 % of what it has available, the guard bench.py applies --
     else an ordinary pageable array, which ``simplyp_stream_out`` accepts too (slower copies, same table)."""
-    from . import engine
     nbytes = int(np.prod(shape, dtype=np.int64)) * 8
     avail = None
     try:
@@ -311,6 +335,416 @@ def _host_table(shape, pin):
         except engine.EngineError:
             pass
     return np.empty(shape, dtype=np.float64)
+
+# ------------------------------------------------------------------------------------------
+# run_simply_p_ensemble in stages: request (keywords, then inputs) -> block pass per device -> assembly
+
+class _Request(object):
+    """What one ``run_simply_p_ensemble`` call asks for: its arguments under their own names (``_request``) and what the inputs make
+    of them (``_bind_*``).  Once bound it is read-only: the block passes, one host thread per device, share it and nothing else."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw, bound=False)
+
+    def __setattr__(self, name, value):
+        if self.bound:
+            raise AttributeError("the request is read-only once bound (%s)" % name)
+        self.__dict__[name] = value
+
+
+class _Bands(namedtuple('_Bands', 'q weighted to_host')):
+    """The one adapter of bands across the members, weighted or not -- of the table's rows, the waterbody series, the per-member
+    time quantiles and the predictive series: ``select`` is the device call, ``result`` the dict the caller gets."""
+
+    def select(self, eng, table, include, weights, series=None, mask=None, **kw):
+        """(lower, upper, info) of ``table``'s rows, or of the predictive ``series`` made from it; under ``weights`` one array, twice."""
+        if series is not None:
+            got = eng.predictive_bands(table, mask, self.q, series, include=include, weights=weights, **kw)
+        elif weights is None:
+            got = eng.quantiles(table, self.q, include=include, **kw)
+        else:
+            got = eng.weighted_quantiles(table, self.q, weights, include=include, **kw)
+        return got if weights is None else (got[0], got[0], got[1])
+
+    def result(self, lower, upper, info):
+        lo_h, up_h = lower.cpu().numpy(), upper.cpu().numpy()
+        # under weights there is one value per probability: nothing to interpolate
+        data = lo_h if self.weighted else engine.interpolate_quantiles(lo_h, up_h, self.q, info['n_used'])
+        res = dict(q=list(self.q), data=data, lower=lo_h if self.to_host else lower, upper=up_h if self.to_host else upper,
+                   n_members=info['n_used'], info=info)
+        return dict(res, rule='inverted_cdf', weight_total=int(info['T'])) if self.weighted else res
+
+
+def _request(**kw):
+    """Request, part 1: every check that needs nothing but the keyword arguments -- no input is read, no device touched."""
+    r = _Request(**kw)
+    if r.quantiles is not None:
+        if r.devices is not None:
+            raise ValueError("quantiles cannot be combined with devices=[...]: a quantile of the whole ensemble is not a function "
+                             "of the member blocks' quantiles -- run the band on one device")
+        r.quantiles = request.probabilities('quantiles', r.quantiles)
+    elif r.quantile_members is not None and not r.score and r.pareto is None:
+        raise ValueError("quantile_members given without quantiles")
+    if r.score:
+        if r.obs_dict is None:
+            raise ValueError("score needs obs_dict: the observations the forecast is judged against")
+        if r.reduce is not None:
+            raise ValueError("score needs the daily series: it cannot be combined with reduce")
+        if r.devices is not None:
+            raise ValueError("score cannot be combined with devices=[...]: a score of the whole ensemble is not a function of the "
+                             "member blocks' scores -- run it on one device")
+    if r.pareto is not None:
+        if r.obs_dict is None:
+            raise ValueError("pareto needs obs_dict: the objectives are rows of the goodness-of-fit table")
+        if r.devices is not None:
+            raise ValueError("pareto cannot be combined with devices=[...]: dominance spans the whole ensemble, it is not a "
+                             "function of the member blocks' results -- run it on one device")
+        r.pareto_max_fronts = int(r.pareto_max_fronts)
+        if r.pareto_max_fronts < 0:
+            raise ValueError("pareto_max_fronts must be >= 0")
+    if r.quantile_weights is not None and r.quantile_log_weights is not None:
+        raise ValueError("quantile_weights and quantile_log_weights are mutually exclusive")
+    r.weighted_band = r.quantile_weights is not None or r.quantile_log_weights is not None
+    if r.weighted_band and r.quantiles is None and not r.score:
+        raise ValueError("quantile_weights / quantile_log_weights given without quantiles")
+    r.tq_names = r.tq_ids = r.tq_pod = r.tq_labels = r.pr_names = r.pr_ids = None
+    r.tq_needs = r.pr_needs = []
+    if r.time_quantiles is None:
+        if r.time_quantile_series is not None or r.time_quantile_periods is not None:
+            raise ValueError("time_quantile_series / time_quantile_periods given without time_quantiles")
+    else:
+        if r.reduce is not None:
+            raise ValueError("time_quantiles needs the daily series: it cannot be combined with reduce")
+        r.time_quantiles = request.probabilities('time_quantiles', r.time_quantiles)
+        names = list(r.time_quantile_series) if r.time_quantile_series is not None else \
+            (list(r.outputs) if r.outputs is not None else list(marshal.REACH5_COLUMNS))
+        r.tq_names, r.tq_ids, r.tq_needs = request.series_ids('time_quantile_series', names)
+        r.tq_labels, r.tq_pod = request.skipping_periods('time_quantile_periods', r.time_quantile_periods)
+    if r.predictive_series is None:
+        if r.predictive_m is not None and not r.score:
+            raise ValueError("predictive_m given without predictive_series")
+    else:
+        if r.quantiles is None and not r.score:
+            raise ValueError("predictive_series needs quantiles: the probabilities of the bands")
+        if r.reduce is not None:
+            raise ValueError("predictive_series needs the daily series: it cannot be combined with reduce")
+        if r.devices is not None:
+            raise ValueError("predictive_series cannot be combined with devices=[...]: a band across the whole ensemble is not a "
+                             "function of the member blocks' bands")
+        r.pr_names, r.pr_ids, r.pr_needs = request.series_ids('predictive_series', r.predictive_series)
+        if isinstance(r.predictive_m, dict) and [c for c in r.predictive_m if c not in r.pr_names]:
+            raise ValueError("predictive_m names series that predictive_series does not: %s"
+                             % [c for c in r.predictive_m if c not in r.pr_names])
+    if r.pr_names is not None or r.score:
+        r.predictive_seed, r.predictive_day0 = int(r.predictive_seed), int(r.predictive_day0)
+        if not 0 <= r.predictive_seed < 1 << 64 or not 0 <= r.predictive_day0 < 1 << 31:
+            raise ValueError("predictive_seed must be in [0, 2^64) and predictive_day0 in [0, 2^31)")
+    if r.score and isinstance(r.predictive_m, dict) and r.pr_names is None and \
+            [c for c in r.predictive_m if c not in abi.TQ_DERIVED_SERIES]:
+        raise ValueError("predictive_m names series that are not df_R series: %s"
+                         % [c for c in r.predictive_m if c not in abi.TQ_DERIVED_SERIES])
+    r.pr_bands = r.pr_names is not None and r.quantiles is not None
+    r.bands = None if r.quantiles is None else _Bands(r.quantiles, r.weighted_band, r.to_host)
+    # the caller's product is a reduction of the table: keep_daily=False then drops the table itself
+    r.reduced_on_device = r.obs_dict is not None or r.quantiles is not None or r.time_quantiles is not None
+    r.want_host_table = r.to_host and (r.keep_daily or not r.reduced_on_device)
+    return r
+
+
+def _bind_members(r):
+    """Request, part 2a: the ensemble -- size, band members and weights, the blocks of ``devices``, start states, parameters, forcing."""
+    r.scs, r.up_ptr, r.up_idx = marshal.catchment(r.p_struc, r.p)[:3]
+    overrides = dict(r.overrides or {})
+    f_tdp = overrides.pop('f_TDP', None)
+    m_over, r_over = marshal.split_member_reach_overrides(overrides)
+    sizes = {np.asarray(v).shape[-1] for v in list(m_over.values()) + list(r_over.values()) + [f_tdp] if v is not None and np.ndim(v) > 0}
+    if r.n_members is None:
+        if len(sizes) != 1:
+            raise ValueError("cannot infer the ensemble size: give n_members or override arrays of one length")
+        r.n_members = sizes.pop()
+    r.E = E = int(r.n_members)
+    if r.quantile_members is not None:
+        r.quantile_members = np.ascontiguousarray(np.asarray(r.quantile_members) != 0)
+        if r.quantile_members.shape != (E,):
+            raise ValueError("quantile_members needs one flag per member")
+    r.q_lin = r.lw_all = r.pr_m = None
+    if r.quantile_weights is not None:               # the filter's integers, on the host
+        w_ = np.asarray(r.quantile_weights, dtype=np.float64)
+        if w_.shape != (E,):
+            raise ValueError("quantile_weights needs one weight per member")
+        r.q_lin = weighted.linear_weights(w_).astype(np.int64)
+    if r.quantile_log_weights is not None:           # ... on the device, where the run lies
+        r.lw_all = np.ascontiguousarray(np.asarray(r.quantile_log_weights, dtype=np.float64))
+        if r.lw_all.shape != (E,):
+            raise ValueError("quantile_log_weights needs one log weight per member")
+        if not np.isfinite(r.lw_all).any():
+            raise ValueError("quantile_log_weights: no log weight is finite, so all weights are zero")
+    if r.predictive_m is not None and r.pr_names is not None:
+        r.pr_m = request.error_model_rows(r.predictive_m, r.pr_names, E)
+    met_sets = list(r.met_df) if isinstance(r.met_df, (list, tuple)) else [r.met_df]
+    r.met_df = met_sets[0]
+    if r.devices is None:
+        r.bounds = [(0, E)]
+    else:
+        if not list(r.devices):
+            raise ValueError("devices must name at least one GPU")
+        r.bounds = [b_ for b_ in (ensemble.shard_bounds(E, len(r.devices), k) for k in range(len(r.devices))) if b_[1] > b_[0]]
+    r.state_blocks = None if r.initial_state is None else _state_blocks(r.initial_state, r.scs, E, r.met_df.index, r.bounds)
+    # the SoA arrays are marshalled straight into page-locked host memory: the uploads are asynchronous DMA transfers
+    r.pin = engine.pinned_empty
+    r.mp = marshal.member_params(r.p, r.p_LU, E, m_over, alloc=r.pin)
+    r.rp = marshal.reach_params(r.p_SC, r.p, E, r_over, alloc=r.pin)
+    if m_over or r_over:
+        marshal.validate_ensemble(r.mp, r.rp, r.scs)       # the reference's checks, for every member (model.py:321-335, :355-357)
+    if r.snow_in_kernel is None:
+        r.snow_in_kernel = 'f_DDSM' in m_over or 'D_snow_0' in m_over
+    for m in met_sets:
+        if r.snow_in_kernel and not {'Precipitation', 'T_air'} <= set(m.columns):
+            raise ValueError("the in-kernel snow module needs met_df columns 'Precipitation' and 'T_air'")
+        if not m.index.equals(r.met_df.index):
+            raise ValueError("all forcing sets must cover the same dates")
+    if len(met_sets) > 1:
+        if r.forcing_of_member is None:
+            raise ValueError("several forcing sets need forcing_of_member (one set index per member)")
+        fom = r.forcing_of_member = np.ascontiguousarray(r.forcing_of_member, dtype=np.int32)
+        if fom.shape != (E,) or fom.min() < 0 or fom.max() >= len(met_sets):
+            raise ValueError("forcing_of_member needs one index in [0, %d) per member" % len(met_sets))
+    elif r.forcing_of_member is not None:
+        raise ValueError("forcing_of_member given but met_df is a single forcing set")
+    sets = [marshal.forcing_arrays(m, snow=r.snow_in_kernel) for m in met_sets]
+    r.forcing, r.doy = np.ascontiguousarray(np.concatenate([f for f, _ in sets], axis=0)), sets[0][1]
+    r.ft_all = r.p['f_TDP'] if f_tdp is None else f_tdp
+
+
+def _bind_outputs(r):
+    """Request, part 2b: the table (columns, ``mask``, waterbody, periods, options, reaches) and what is held against it; then read-only."""
+    index, scs = r.met_df.index, r.scs
+    cols = list(r.outputs) if r.outputs is not None else list(marshal.REACH5_COLUMNS)
+    r.wb_reaches, out_reaches = None, r.out_reaches
+    if r.waterbody is not None and r.waterbody is not False:
+        if r.reduce is not None:
+            raise ValueError("the waterbody sum needs the daily series: waterbody cannot be combined with reduce")
+        if r.waterbody is True:
+            flags = r.p_struc['In_final_flux?']
+            r.wb_reaches = [int(x) for x in flags[flags == 1].index.values]                    # model.py:867
+            if len(r.wb_reaches) > len(scs):                                                     # :871-872
+                raise ValueError("Mismatch between the number of subcatchments in the 'Setup' parameter sheet \n(parameter 'n_SC') and in the 'Reach_structure' parameter sheet")
+        else:
+            r.wb_reaches = sorted(int(x) for x in r.waterbody)
+        print('Sub-catchments flowing directly into receiving waterbody: %s' % np.asarray(r.wb_reaches))   # :874
+        if out_reaches is not None:
+            out_reaches = list(out_reaches) + [x for x in r.wb_reaches if x not in out_reaches]
+    if r.obs_dict is not None or r.wb_reaches is not None:
+        if r.reduce is not None:
+            raise ValueError("goodness of fit needs the daily series: obs_dict cannot be combined with reduce")
+        cols += [c for c in marshal.FLUX_COLUMNS if c not in cols]
+    cols += [c for c in r.tq_needs if c not in cols]
+    if isinstance(r.time_quantile_periods, str):
+        r.tq_labels, r.tq_pod = request.annual_periods(index)
+    if r.tq_pod is not None and r.tq_pod.shape != (len(index),):
+        raise ValueError("time_quantile_periods needs one period index per day")
+    cols += [c for c in r.pr_needs if c not in cols]
+    r.mask = marshal.mask_of_columns(cols)
+    if r.mask & marshal.MASK_D_SNOW and not r.snow_in_kernel:
+        raise ValueError("output 'D_snow' is the per-member snow depth of the in-kernel snow module: needs snow_in_kernel=True "
+                         "(without it every member shares met_df['D_snow_end'])")
+    r.periods, r.period_of_day = (None, None) if r.reduce is None else request.reduce_periods(r.reduce, index)
+    r.opts = _engine_opts(r.p_SU, r.p, r.dynamic_options, r.step_len, r.solver, r.mask,
+                          n_periods=0 if r.periods is None else len(r.periods), snow=r.snow_in_kernel)
+    r.reaches = scs if out_reaches is None else list(out_reaches)            # the waterbody may have added to them since
+    r.oreach = None if out_reaches is None else [scs.index(int(x)) for x in out_reaches]
+    r.table_shape = (bin(r.mask).count('1'), len(index) if r.periods is None else len(r.periods), len(r.reaches))
+    r.wb_sum = r.wb_reaches is not None and len(r.wb_reaches) > 1
+    r.obs = None if r.obs_dict is None else vr.observation_array(r.obs_dict, r.reaches, index)
+    r.wobs = vr.observation_array({0: r.waterbody_obs}, [0], index)[0] if r.wb_sum and r.waterbody_obs is not None else None
+    r.sc_names = r.sc_ids = r.sc_obs = r.sc_m = r.pa_resolved = None
+    if r.score:                                      # [n_series, D, n_reaches]: the layout simplyp_predictive_scores takes
+        r.sc_names, r.sc_ids, r.sc_obs = request.observed_series(r.obs_dict, r.reaches, r.obs, r.pr_names)
+        if r.sc_names and r.predictive_m is not None:
+            r.sc_m = request.error_model_rows(r.predictive_m, r.sc_names, r.E)
+    if r.pareto is not None:
+        r.pa_resolved = pareto_rules.resolve_objectives(r.pareto, n_reaches=len(r.reaches), has_spearman=bool(r.spearman))
+    r.bound = True
+
+
+def _block_pass(r, eng, lo, hi):
+    """Members [lo, hi) on one engine context: the run, then the reductions that want the table where it lies."""
+    mask, to_host = r.mask, r.to_host
+    keep = (lambda t: t.cpu().numpy()) if to_host else (lambda t: t)                         # a device result as the caller gets it
+    whole = (lo == 0 and hi == r.E)
+    st_in = None
+    if r.state_blocks is not None:
+        st_in = r.state_blocks[r.bounds.index((lo, hi))]
+        st_in = st_in.contiguous() if hasattr(st_in, 'contiguous') else np.ascontiguousarray(st_in, dtype=np.float64)
+    mp_b = r.mp if whole else np.ascontiguousarray(r.mp[:, lo:hi])
+    rp_b = r.rp if whole else np.ascontiguousarray(r.rp[:, :, lo:hi])
+    fom_b = None if r.forcing_of_member is None else np.ascontiguousarray(r.forcing_of_member[lo:hi])
+    ft = r.ft_all if np.ndim(r.ft_all) == 0 else np.ascontiguousarray(np.asarray(r.ft_all, dtype=np.float64)[lo:hi])
+    rp_d = eng.to_device(rp_b)
+    # to_host: the table is delivered into page-locked host memory while the kernel runs (simplyp_stream_out) -- unless the
+    # caller only wants the statistics (keep_daily=False)
+    host_out = _host_table(r.table_shape + (hi - lo,), r.pin) if r.want_host_table else None
+    out_d, status_d, stats = eng.run(r.forcing, r.doy, mp_b, rp_d, r.up_ptr, r.up_idx, r.opts, out_reaches=r.oreach,
+                                     period_of_day=r.period_of_day, forcing_of_member=fom_b, host_out=host_out,
+                                     state_in=st_in, state_out=True if r.return_state else None)
+    state_d = stats.pop('state', None)
+    part = dict(stats=stats, state=state_d, status=keep(status_d), host_out=host_out, device=eng.device)
+    mos = stats.get('member_of_slot') if r.opts.out_slot_order else None
+    tkw = dict(f_tdp=ft, reach_params=rp_d, out_reaches=r.oreach, member_of_slot=mos)       # how a reduction reads the table
+    if r.obs is not None:
+        gof_d, info = eng.gof(out_d, mask, r.obs, spearman=r.spearman, **tkw)
+        rho = info.pop('spearman', None)
+        part['gof'] = (keep(gof_d), info, None if rho is None else keep(rho))
+    if r.wb_sum:
+        wb_d, winfo = eng.waterbody(out_d, mask, [r.scs.index(x) for x in r.wb_reaches], **tkw)
+        part['wb'] = (keep(wb_d), winfo)
+        if r.wobs is not None:
+            g_d, ginfo = eng.gof_waterbody(wb_d, winfo['columns'], r.wobs, ft, member_of_slot=mos)
+            part['wb_gof'] = (keep(g_d), ginfo)
+    if r.quantiles is not None or r.score or r.pareto is not None:
+        # who takes part: a mask in member order, built where the status lies; and with which weight
+        inc = (status_d & abi.STATUS_NONFINITE) == 0
+        if r.quantile_members is not None:
+            inc = inc & eng.to_device(r.quantile_members[lo:hi])
+        q_w = None if r.q_lin is None else eng.to_device(r.q_lin)
+        if r.lw_all is not None:
+            q_w = eng.pf_weights(eng.to_device(r.lw_all))[1]
+    if r.pa_resolved is not None:                # the goodness-of-fit table is in member order whatever the run's is
+        part['pareto'] = eng.pareto(pareto_rules.objective_rows(gof_d, rho, r.pa_resolved), [o['sense'] for o in r.pa_resolved],
+                                    include=inc, max_fronts=r.pareto_max_fronts)
+    if r.quantiles is not None:
+        part['quant'] = r.bands.select(eng, out_d, inc, q_w, member_of_slot=mos)
+        if 'wb' in part:
+            part['wb_quant'] = r.bands.select(eng, wb_d, inc, q_w, member_of_slot=mos)
+    if r.time_quantiles is not None:
+        lo_d, up_d, tinfo = eng.time_quantiles(out_d, mask, r.time_quantiles, series=r.tq_ids, period_of_day=r.tq_pod,
+                                               n_periods=None if r.tq_labels is None else len(r.tq_labels), **tkw)
+        if mos is not None:                      # member order, undone on the small result: slot j holds member mos[j]
+            idx = mos.long()
+            lo_d, up_d = lo_d.new_empty(lo_d.shape).index_copy_(-1, idx, lo_d), up_d.new_empty(up_d.shape).index_copy_(-1, idx, up_d)
+        lo_h, up_h = lo_d.cpu().numpy(), up_d.cpu().numpy()
+        tdata = engine.interpolate_time_quantiles(lo_h, up_h, r.time_quantiles, tinfo['n_days'])
+        part['tq'] = (lo_h if to_host else lo_d, up_h if to_host else up_d, tdata, tinfo)
+        if r.quantiles is not None:              # the band across the members of the per-member statistics
+            part['tq_quant'] = r.bands.select(eng, eng.to_device(tdata), inc, q_w)
+    pkw = dict(tkw, seed=r.predictive_seed, day0=r.predictive_day0)
+    if r.sc_ids is not None:                     # the scores of the observed rows: parameter-only, and with the error model drawn
+        skw = dict(pkw, include=inc, weights=q_w)
+        part['scores'] = (eng.predictive_scores(out_d, mask, r.sc_ids, r.sc_obs, **skw),
+                          None if r.sc_m is None else eng.predictive_scores(out_d, mask, r.sc_ids, r.sc_obs, err_m=r.sc_m, **skw))
+    if r.pr_bands:                               # the bands of the named series: parameter-only, and with the error model drawn
+        part['pred'] = (r.bands.select(eng, out_d, inc, q_w, series=r.pr_ids, mask=mask, **pkw),
+                        None if r.pr_m is None else r.bands.select(eng, out_d, inc, q_w, series=r.pr_ids, mask=mask, err_m=r.pr_m, **pkw))
+    part['out_d'] = None if (r.reduced_on_device and not r.keep_daily) else out_d
+    return part
+
+
+def _run_blocks(r):
+    """One ``_block_pass`` per member block: on ``device``, or at the same time on the entries of ``devices``."""
+    if r.devices is None:
+        return [_block_pass(r, engine.get_engine(r.device), 0, r.E)]
+    devs = [int(d) for d in r.devices]
+    if r.opts.out_slot_order:
+        raise ValueError("devices=[...] returns tables in member order: solver['out_slot_order'] must stay 0")
+    all_bounds = [ensemble.shard_bounds(r.E, len(devs), k) for k in range(len(devs))]
+    # one context per list entry (a repeated id gets a context of its own: contexts are not re-entrant)
+    engs = [engine.get_engine(d, replica=devs[:k].count(d)) for k, d in enumerate(devs)]
+    live = [(eng, lo, hi) for eng, (lo, hi) in zip(engs, all_bounds) if hi > lo]
+    if len(live) == 1:
+        return [_block_pass(r, *live[0])]
+    with ThreadPoolExecutor(max_workers=len(live)) as pool:
+        return list(pool.map(lambda a_: _block_pass(r, *a_), live))
+
+
+def _merged_stats(parts, bounds):
+    """``res['stats']``: the one block's, or sums / maxima over the blocks with the per-block dicts under ``'per_device'``."""
+    per = [pt['stats'] for pt in parts]
+    stats = per[0]
+    if len(per) > 1:
+        stats = {k: sum(d_[k] for d_ in per) for k in ('rhs_evals', 'steps', 'rejected', 'n_launches', 'streamed_chunks',
+                                                         'queue_waits')}
+        stats.update({k: max(d_[k] for d_ in per) for k in ('kernel_ms', 'pilot_ms', 'wall_ms', 'd2h_tail_ms',
+                                                            'queue_longest_wait_polls', 'queue_longest_stall_polls')})
+        for k in ('balanced', 'queued', 'lanes_per_wave', 'lanes_per_member'):
+            stats[k] = per[0][k]
+        stats['simt_efficiency'] = float(np.mean([d_['simt_efficiency'] for d_ in per]))
+        stats['per_device'] = [dict(d_, device=int(pt['device']), members=[int(lo), int(hi)])
+                               for d_, pt, (lo, hi) in zip(per, parts, bounds)]
+    stats['bounds'] = [[int(lo), int(hi)] for lo, hi in bounds]
+    return stats
+
+
+def _assemble(r, parts):
+    """The result dict from the blocks' parts: per-member products joined along the member axis, bands through ``r.bands``."""
+    to_host, first = r.to_host, parts[0]
+    cat = (lambda xs: np.concatenate(xs, axis=-1)) if to_host else (lambda xs: xs[0] if len(xs) == 1 else _torch_cat(xs))
+    gof_result = lambda key: dict(stats=list(abi.GOF_STATS), variables=list(abi.GOF_VARS), info=first[key][1],
+                                  data=cat([pt[key][0] for pt in parts]))
+    res = dict(columns=marshal.columns_of_mask(r.mask), reaches=r.reaches, periods=r.periods,
+               stats=_merged_stats(parts, r.bounds), status=cat([pt['status'] for pt in parts]))
+    if r.obs is not None:
+        res['gof'] = gof_result('gof')
+        if first['gof'][2] is not None:          # Spearman's r [6, n_reaches, E]: the rank statistic of the reference's table (:444-445)
+            res['gof']['spearman'] = cat([pt['gof'][2] for pt in parts])
+    if r.wb_sum:
+        winfo = first['wb'][1]
+        res['waterbody'] = dict(columns=winfo['columns'], reaches=r.wb_reaches, info=winfo, data=cat([pt['wb'][0] for pt in parts]))
+        if r.wobs is not None:
+            res['waterbody']['gof'] = gof_result('wb_gof')
+    elif r.wb_reaches is not None:
+        print('One or fewer reaches were selected to be included in the sum, check your reach structure parameters')   # :896
+        res['waterbody'] = None
+    if r.quantiles is not None:
+        res['quantiles'] = r.bands.result(*first['quant'])
+        if r.wb_sum:
+            res['waterbody']['quantiles'] = r.bands.result(*first['wb_quant'])
+    if r.pa_resolved is not None:
+        res['pareto'] = pareto_rules.result(first['pareto'], r.pa_resolved)
+    if r.score:
+        res['scores'] = _scores_result(r.sc_names, r.reaches, r.sc_obs, len(r.met_df), first.get('scores'), r.predictive_seed,
+                                       r.predictive_day0)
+    if r.pr_bands:
+        po, ov = first['pred']
+        po_b, ov_b = r.bands.result(*po), None if ov is None else r.bands.result(*ov)
+        info = dict(param_only=po_b.pop('info'), overall=None if ov_b is None else ov_b.pop('info'))
+        extra = dict(rule=po_b['rule'], weight_total=po_b['weight_total']) if r.weighted_band else {}
+        for b_ in (po_b, ov_b):
+            if b_ is not None:
+                del b_['q'], b_['n_members']
+        res['predictive'] = dict(q=list(r.quantiles), series=list(r.pr_names), param_only=po_b, overall=ov_b,
+                                 n_members=po[2]['n_used'], seed=r.predictive_seed, day0=r.predictive_day0, info=info, **extra)
+    if r.time_quantiles is not None:
+        tinfo = first['tq'][3]
+        res['time_quantiles'] = dict(q=list(r.time_quantiles), series=list(r.tq_names), periods=r.tq_labels,
+                                     lower=cat([pt['tq'][0] for pt in parts]), upper=cat([pt['tq'][1] for pt in parts]),
+                                     data=np.concatenate([pt['tq'][2] for pt in parts], axis=-1),
+                                     n_days=np.asarray(tinfo['n_days']), info=tinfo)
+        if r.quantiles is not None:
+            res['time_quantiles']['quantiles'] = r.bands.result(*first['tq_quant'])
+    if r.return_state:
+        sts = [pt['state'] for pt in parts]
+        if r.return_state == 'device':
+            sdata = sts[0] if len(sts) == 1 else sts
+        elif to_host:
+            sdata = np.concatenate([t.cpu().numpy() for t in sts], axis=-1)
+        else:
+            sdata = cat(sts)
+        res['state'] = dict(rows=list(abi.STATE_ROWS), reaches=list(r.scs), data=sdata, end=r.met_df.index[-1])
+    if r.reduced_on_device and not r.keep_daily:
+        res['data'] = None
+    elif not to_host:
+        res['data'] = first['out_d'] if len(parts) == 1 else [pt['out_d'] for pt in parts]
+    elif len(parts) == 1:
+        res['data'] = first['host_out']
+    else:                                        # one table in member order: every block's copied into its member range, then freed
+        res['data'] = np.empty(r.table_shape + (r.E,), dtype=np.float64)
+
+        def place(pt, lo, hi):
+            res['data'][..., lo:hi] = pt.pop('host_out')
+        with ThreadPoolExecutor(max_workers=len(parts)) as pool:
+            list(pool.map(place, parts, *zip(*r.bounds)))
+    return res
+
 
 def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, overrides=None, n_members=None,
                           outputs=None, out_reaches=None, step_len=1., solver=None, device=0, to_host=True,
@@ -470,454 +904,11 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     and ``status`` are numpy arrays, or device tensors when ``to_host`` is False.
     The caller's ``p_LU``/``p_SC`` are edited in place exactly as by ``run_simply_p``.
     """
-    from . import engine
-
-    if quantiles is not None:
-        if devices is not None:
-            raise ValueError("quantiles cannot be combined with devices=[...]: a quantile of the whole ensemble is not a function "
-                             "of the member blocks' quantiles -- run the band on one device")
-        quantiles = [float(x) for x in np.atleast_1d(np.asarray(quantiles, dtype=np.float64))]
-        if not 1 <= len(quantiles) <= 16 or not all(0.0 <= x <= 1.0 for x in quantiles):
-            raise ValueError("quantiles must be 1 to 16 probabilities in [0, 1]")
-    elif quantile_members is not None and not score and pareto is None:
-        raise ValueError("quantile_members given without quantiles")
-    if score:
-        if obs_dict is None:
-            raise ValueError("score needs obs_dict: the observations the forecast is judged against")
-        if reduce is not None:
-            raise ValueError("score needs the daily series: it cannot be combined with reduce")
-        if devices is not None:
-            raise ValueError("score cannot be combined with devices=[...]: a score of the whole ensemble is not a function of the "
-                             "member blocks' scores -- run it on one device")
-    pa_resolved = None
-    if pareto is not None:
-        if obs_dict is None:
-            raise ValueError("pareto needs obs_dict: the objectives are rows of the goodness-of-fit table")
-        if devices is not None:
-            raise ValueError("pareto cannot be combined with devices=[...]: dominance spans the whole ensemble, it is not a "
-                             "function of the member blocks' results -- run it on one device")
-        pareto_max_fronts = int(pareto_max_fronts)
-        if pareto_max_fronts < 0:
-            raise ValueError("pareto_max_fronts must be >= 0")
-    if quantile_weights is not None and quantile_log_weights is not None:
-        raise ValueError("quantile_weights and quantile_log_weights are mutually exclusive")
-    weighted_band = quantile_weights is not None or quantile_log_weights is not None
-    if weighted_band and quantiles is None and not score:
-        raise ValueError("quantile_weights / quantile_log_weights given without quantiles")
-    tq_ids = tq_pod = tq_labels = None
-    if time_quantiles is None:
-        if time_quantile_series is not None or time_quantile_periods is not None:
-            raise ValueError("time_quantile_series / time_quantile_periods given without time_quantiles")
-    else:
-        if reduce is not None:
-            raise ValueError("time_quantiles needs the daily series: it cannot be combined with reduce")
-        time_quantiles = [float(x) for x in np.atleast_1d(np.asarray(time_quantiles, dtype=np.float64))]
-        if not 1 <= len(time_quantiles) <= 16 or not all(0.0 <= x <= 1.0 for x in time_quantiles):
-            raise ValueError("time_quantiles must be 1 to 16 probabilities in [0, 1]")
-        tq_names = list(time_quantile_series) if time_quantile_series is not None else \
-            (list(outputs) if outputs is not None else list(marshal.REACH5_COLUMNS))
-        unknown = [c for c in tq_names if c not in marshal.ALL_COLUMNS and c not in abi.TQ_DERIVED_SERIES]
-        if unknown or not 1 <= len(tq_names) <= 32:
-            raise ValueError("time_quantile_series must be 1 to 32 names among the reference's columns and %s (unknown: %s)"
-                             % (abi.TQ_DERIVED_SERIES, unknown))
-        tq_ids = [abi.TQ_DERIVED + abi.TQ_DERIVED_SERIES.index(c) if c in abi.TQ_DERIVED_SERIES else marshal.ALL_COLUMNS.index(c)
-                  for c in tq_names]
-        if time_quantile_periods is not None and not isinstance(time_quantile_periods, str):
-            tq_pod = np.asarray(time_quantile_periods)
-            if tq_pod.ndim != 1 or tq_pod.dtype.kind not in 'iu' or (tq_pod < -1).any():
-                raise ValueError("time_quantile_periods must be None, 'annual' or an int array [D] of period indices >= -1")
-            named = tq_pod[tq_pod >= 0]
-            if (np.diff(named) < 0).any():
-                raise ValueError("time_quantile_periods must not decrease (apart from -1 = no period)")
-            tq_labels = np.arange(int(named.max()) + 1 if len(named) else 1)
-            tq_pod = np.ascontiguousarray(tq_pod, dtype=np.int32)
-        elif time_quantile_periods is not None and time_quantile_periods != 'annual':
-            raise ValueError("time_quantile_periods must be None, 'annual' or an int array [D] of period indices >= -1")
-    pr_names = pr_ids = pr_m = None
-    if predictive_series is None:
-        if predictive_m is not None and not score:
-            raise ValueError("predictive_m given without predictive_series")
-    else:
-        if quantiles is None and not score:
-            raise ValueError("predictive_series needs quantiles: the probabilities of the bands")
-        if reduce is not None:
-            raise ValueError("predictive_series needs the daily series: it cannot be combined with reduce")
-        if devices is not None:
-            raise ValueError("predictive_series cannot be combined with devices=[...]: a band across the whole ensemble is not a "
-                             "function of the member blocks' bands")
-        pr_names = [predictive_series] if isinstance(predictive_series, str) else list(predictive_series)
-        unknown = [c for c in pr_names if c not in marshal.ALL_COLUMNS and c not in abi.TQ_DERIVED_SERIES]
-        if unknown or not 1 <= len(pr_names) <= 32:
-            raise ValueError("predictive_series must be 1 to 32 names among the reference's columns and %s (unknown: %s)"
-                             % (abi.TQ_DERIVED_SERIES, unknown))
-        if isinstance(predictive_m, dict) and [c for c in predictive_m if c not in pr_names]:
-            raise ValueError("predictive_m names series that predictive_series does not: %s"
-                             % [c for c in predictive_m if c not in pr_names])
-        pr_ids = [abi.TQ_DERIVED + abi.TQ_DERIVED_SERIES.index(c) if c in abi.TQ_DERIVED_SERIES else marshal.ALL_COLUMNS.index(c)
-                  for c in pr_names]
-    if pr_names is not None or score:
-        predictive_seed, predictive_day0 = int(predictive_seed), int(predictive_day0)
-        if not 0 <= predictive_seed < 1 << 64 or not 0 <= predictive_day0 < 1 << 31:
-            raise ValueError("predictive_seed must be in [0, 2^64) and predictive_day0 in [0, 2^31)")
-    if score:
-        if isinstance(predictive_m, dict) and pr_names is None and [c for c in predictive_m if c not in abi.TQ_DERIVED_SERIES]:
-            raise ValueError("predictive_m names series that are not df_R series: %s"
-                             % [c for c in predictive_m if c not in abi.TQ_DERIVED_SERIES])
-    marshal.prologue(p_SU, p_LU, p_SC, p)
-    scs = marshal.sc_list(p)
-    up_ptr, up_idx, _ = marshal.topology(p_struc, p)
-    overrides = dict(overrides or {})
-    f_tdp = overrides.pop('f_TDP', None)
-    m_over, r_over = marshal.split_member_reach_overrides(overrides)
-    sizes = {np.asarray(v).shape[-1] for v in list(m_over.values()) + list(r_over.values()) + [f_tdp] if v is not None and np.ndim(v) > 0}
-    if n_members is None:
-        if len(sizes) != 1:
-            raise ValueError("cannot infer the ensemble size: give n_members or override arrays of one length")
-        n_members = sizes.pop()
-    E = int(n_members)
-    if quantile_members is not None:
-        quantile_members = np.ascontiguousarray(np.asarray(quantile_members) != 0)
-        if quantile_members.shape != (E,):
-            raise ValueError("quantile_members needs one flag per member")
-    q_lin = lw_all = None
-    if quantile_weights is not None:                 # the filter's integers, on the host
-        from . import weighted
-        w_ = np.asarray(quantile_weights, dtype=np.float64)
-        if w_.shape != (E,):
-            raise ValueError("quantile_weights needs one weight per member")
-        q_lin = weighted.linear_weights(w_).astype(np.int64)
-    if quantile_log_weights is not None:             # ... on the device, where the run lies
-        lw_all = np.ascontiguousarray(np.asarray(quantile_log_weights, dtype=np.float64))
-        if lw_all.shape != (E,):
-            raise ValueError("quantile_log_weights needs one log weight per member")
-        if not np.isfinite(lw_all).any():
-            raise ValueError("quantile_log_weights: no log weight is finite, so all weights are zero")
-    def m_rows(names_):                              # predictive_m as [n_series, E] in member order
-        per = predictive_m if isinstance(predictive_m, dict) else {c: predictive_m for c in names_}
-        try:
-            rows = np.ascontiguousarray(np.stack([np.broadcast_to(np.asarray(per.get(c, 0.0), dtype=np.float64), (E,))
-                                                  for c in names_]))
-        except (TypeError, ValueError):
-            raise ValueError("predictive_m must be a float, an array [E], or a dict name -> float or array [E]")
-        if not (np.isfinite(rows).all() and (rows >= 0).all()):
-            raise ValueError("predictive_m must be finite and >= 0")
-        return rows
-    if predictive_m is not None and pr_names is not None:
-        pr_m = m_rows(pr_names)
-    met_first = met_df[0] if isinstance(met_df, (list, tuple)) else met_df
-    if devices is None:
-        bounds = [(0, E)]
-    else:
-        from . import ensemble
-        if not list(devices):
-            raise ValueError("devices must name at least one GPU")
-        bounds = [b_ for b_ in (ensemble.shard_bounds(E, len(devices), r) for r in range(len(devices))) if b_[1] > b_[0]]
-    state_blocks = None if initial_state is None else _state_blocks(initial_state, scs, E, met_first.index, bounds)
-    # the SoA arrays are marshalled straight into page-locked host memory: the uploads are asynchronous DMA transfers
-    pin = engine.pinned_empty
-    mp = marshal.member_params(p, p_LU, E, m_over, alloc=pin)
-    rp = marshal.reach_params(p_SC, p, E, r_over, alloc=pin)
-    if m_over or r_over:
-        marshal.validate_ensemble(mp, rp, scs)       # the reference's checks, for every member (model.py:321-335, :355-357)
-    if snow_in_kernel is None:
-        snow_in_kernel = 'f_DDSM' in m_over or 'D_snow_0' in m_over
-    met_sets = list(met_df) if isinstance(met_df, (list, tuple)) else [met_df]
-    met_df = met_sets[0]
-    for m in met_sets:
-        if snow_in_kernel and not {'Precipitation', 'T_air'} <= set(m.columns):
-            raise ValueError("the in-kernel snow module needs met_df columns 'Precipitation' and 'T_air'")
-        if not m.index.equals(met_df.index):
-            raise ValueError("all forcing sets must cover the same dates")
-    if len(met_sets) > 1:
-        if forcing_of_member is None:
-            raise ValueError("several forcing sets need forcing_of_member (one set index per member)")
-        forcing_of_member = np.ascontiguousarray(forcing_of_member, dtype=np.int32)
-        if forcing_of_member.shape != (E,) or forcing_of_member.min() < 0 or forcing_of_member.max() >= len(met_sets):
-            raise ValueError("forcing_of_member needs one index in [0, %d) per member" % len(met_sets))
-    elif forcing_of_member is not None:
-        raise ValueError("forcing_of_member given but met_df is a single forcing set")
-    parts = [marshal.forcing_arrays(m, snow=snow_in_kernel) for m in met_sets]
-    forcing, doy = np.ascontiguousarray(np.concatenate([f for f, _ in parts], axis=0)), parts[0][1]
-    cols = list(outputs) if outputs is not None else list(marshal.REACH5_COLUMNS)
-    wb_reaches = None
-    if waterbody is not None and waterbody is not False:
-        if reduce is not None:
-            raise ValueError("the waterbody sum needs the daily series: waterbody cannot be combined with reduce")
-        if waterbody is True:
-            flags = p_struc['In_final_flux?']
-            wb_reaches = [int(r) for r in flags[flags == 1].index.values]                    # model.py:867
-            if len(wb_reaches) > len(scs):                                                       # :871-872
-                raise ValueError("Mismatch between the number of subcatchments in the 'Setup' parameter sheet \n(parameter 'n_SC') and in the 'Reach_structure' parameter sheet")
-        else:
-            wb_reaches = sorted(int(r) for r in waterbody)
-        print('Sub-catchments flowing directly into receiving waterbody: %s' % np.asarray(wb_reaches))   # :874
-        if out_reaches is not None:
-            out_reaches = list(out_reaches) + [r for r in wb_reaches if r not in out_reaches]
-    if obs_dict is not None or wb_reaches is not None:
-        if reduce is not None:
-            raise ValueError("goodness of fit needs the daily series: obs_dict cannot be combined with reduce")
-        cols += [c for c in ('Qr', 'Msus_kg/day', 'TDP_kg/day', 'PP_kg/day') if c not in cols]
-    if time_quantiles is not None:
-        if any(i >= abi.TQ_DERIVED for i in tq_ids):
-            cols += [c for c in ('Qr', 'Msus_kg/day', 'TDP_kg/day', 'PP_kg/day') if c not in cols]
-        cols += [c for c in tq_names if c in marshal.ALL_COLUMNS and c not in cols]
-        if time_quantile_periods is not None and isinstance(time_quantile_periods, str):
-            tq_labels, tq_pod = np.unique(np.asarray(met_df.index.year), return_inverse=True)
-            tq_pod = np.ascontiguousarray(tq_pod, dtype=np.int32)
-        if tq_pod is not None and tq_pod.shape != (len(met_df),):
-            raise ValueError("time_quantile_periods needs one period index per day")
-    if pr_names is not None:
-        if any(i >= abi.TQ_DERIVED for i in pr_ids):
-            cols += [c for c in ('Qr', 'Msus_kg/day', 'TDP_kg/day', 'PP_kg/day') if c not in cols]
-        cols += [c for c in pr_names if c in marshal.ALL_COLUMNS and c not in cols]
-    pr_bands = pr_names is not None and quantiles is not None
-    mask = marshal.mask_of_columns(cols)
-    if mask & marshal.MASK_D_SNOW and not snow_in_kernel:
-        raise ValueError("output 'D_snow' is the per-member snow depth of the in-kernel snow module: needs snow_in_kernel=True "
-                         "(without it every member shares met_df['D_snow_end'])")
-    period_of_day, periods = None, None
-    if reduce is not None:
-        if isinstance(reduce, str):
-            if reduce != 'annual':
-                raise ValueError("reduce must be None, 'annual' or an array of period indices")
-            years = np.asarray(met_df.index.year)
-            periods, period_of_day = np.unique(years, return_inverse=True)
-        else:
-            period_of_day = np.asarray(reduce)
-            if period_of_day.shape != (len(met_df),) or period_of_day.min() < 0:
-                raise ValueError("reduce array needs one non-negative period index per day")
-            periods = np.arange(int(period_of_day.max()) + 1)
-        period_of_day = np.ascontiguousarray(period_of_day, dtype=np.int32)
-    opts = _engine_opts(p_SU, p, dynamic_options, step_len, solver, mask,
-                        n_periods=0 if periods is None else len(periods), snow=snow_in_kernel)
-    oreach = None if out_reaches is None else [scs.index(int(r)) for r in out_reaches]
-
-    reaches = scs if out_reaches is None else list(out_reaches)
-    n_or_ = len(scs) if oreach is None else len(oreach)
-    rows_ = len(met_df) if periods is None else len(periods)
-    ncols_ = bin(mask).count('1')
-    reduced_on_device = obs_dict is not None or quantiles is not None or time_quantiles is not None     # the caller's product is a reduction of the table
-    want_host_table = to_host and (keep_daily or not reduced_on_device)
-    obs = wobs = None
-    if obs_dict is not None or (wb_reaches is not None and len(wb_reaches) > 1 and waterbody_obs is not None):
-        from . import visualise_results as vr
-        if obs_dict is not None:
-            obs = vr.observation_array(obs_dict, reaches, met_df.index)
-        if wb_reaches is not None and len(wb_reaches) > 1 and waterbody_obs is not None:
-            wobs = vr.observation_array({0: waterbody_obs}, [0], met_df.index)[0]
-    sc_names = sc_ids = sc_obs = sc_m = None
-    if score:                                        # the df_R series with an observation, on any date, at some output reach
-        seen = {var for SC in reaches if SC in obs_dict for var in abi.GOF_VARS
-                if var in obs_dict[SC].columns and obs_dict[SC][var].notna().any()}
-        sc_names = [c for c, var in zip(abi.TQ_DERIVED_SERIES, abi.GOF_VARS) if var in seen and (pr_names is None or c in pr_names)]
-    if sc_names:                                     # [n_series, D, n_reaches]: the layout simplyp_predictive_scores takes
-        sc_m = None if predictive_m is None else m_rows(sc_names)
-        sc_ids = [abi.TQ_DERIVED + abi.TQ_DERIVED_SERIES.index(c) for c in sc_names]
-        sc_obs = np.ascontiguousarray(np.stack([obs[:, abi.TQ_DERIVED_SERIES.index(c), :].T for c in sc_names]))
-    if pareto is not None:
-        from . import pareto as pareto_rules
-        pa_resolved = pareto_rules.resolve_objectives(pareto, n_reaches=len(reaches), has_spearman=bool(spearman))
-    ft_all = p['f_TDP'] if f_tdp is None else f_tdp
-
-    def block_pass(eng, lo, hi):
-        """Members [lo, hi) on one engine context: the run, then the reductions that want the table where it lies."""
-        whole = (lo == 0 and hi == E)
-        st_in = None
-        if state_blocks is not None:
-            st_in = state_blocks[bounds.index((lo, hi))]
-            st_in = st_in.contiguous() if hasattr(st_in, 'contiguous') else np.ascontiguousarray(st_in, dtype=np.float64)
-        mp_b = mp if whole else np.ascontiguousarray(mp[:, lo:hi])
-        rp_b = rp if whole else np.ascontiguousarray(rp[:, :, lo:hi])
-        fom_b = None if forcing_of_member is None else np.ascontiguousarray(forcing_of_member[lo:hi])
-        ft = ft_all if np.ndim(ft_all) == 0 else np.ascontiguousarray(np.asarray(ft_all, dtype=np.float64)[lo:hi])
-        rp_d = eng.to_device(rp_b)
-        # to_host: the table is delivered into page-locked host memory while the kernel runs (simplyp_stream_out) -- unless the
-        # caller only wants the statistics (keep_daily=False)
-        host_out = _host_table((ncols_, rows_, n_or_, hi - lo), pin) if want_host_table else None
-        out_d, status_d, stats = eng.run(forcing, doy, mp_b, rp_d, up_ptr, up_idx, opts, out_reaches=oreach,
-                                         period_of_day=period_of_day, forcing_of_member=fom_b, host_out=host_out,
-                                         state_in=st_in, state_out=True if return_state else None)
-        state_d = stats.pop('state', None)
-        part = dict(stats=stats, state=state_d, status=status_d.cpu().numpy() if to_host else status_d, host_out=host_out)
-        mos = stats.get('member_of_slot') if opts.out_slot_order else None
-        if obs is not None:
-            gof_d, info = eng.gof(out_d, mask, obs, ft, rp_d, out_reaches=oreach, member_of_slot=mos, spearman=spearman)
-            rho = info.pop('spearman', None)
-            part['gof'] = (gof_d.cpu().numpy() if to_host else gof_d, info,
-                           None if rho is None else (rho.cpu().numpy() if to_host else rho))
-        if wb_reaches is not None and len(wb_reaches) > 1:
-            wb_d, winfo = eng.waterbody(out_d, mask, [scs.index(r) for r in wb_reaches], ft, rp_d, out_reaches=oreach,
-                                        member_of_slot=mos)
-            part['wb'] = (wb_d.cpu().numpy() if to_host else wb_d, winfo)
-            if wobs is not None:
-                g_d, ginfo = eng.gof_waterbody(wb_d, winfo['columns'], wobs, ft, member_of_slot=mos)
-                part['wb_gof'] = (g_d.cpu().numpy() if to_host else g_d, ginfo)
-        if quantiles is not None or score or pareto is not None:
-            # who takes part: a mask in member order, built where the status lies
-            inc = (status_d & abi.STATUS_NONFINITE) == 0
-            if quantile_members is not None:
-                inc = inc & eng.to_device(quantile_members[lo:hi])
-            q_w = None
-            if q_lin is not None:
-                q_w = eng.to_device(q_lin)
-            elif lw_all is not None:
-                q_w = eng.pf_weights(eng.to_device(lw_all))[1]
-        if pa_resolved is not None:              # the goodness-of-fit table is in member order whatever the run's is
-            part['pareto'] = eng.pareto(pareto_rules.objective_rows(gof_d, rho, pa_resolved), [r_['sense'] for r_ in pa_resolved],
-                                        include=inc, max_fronts=pareto_max_fronts)
-        if quantiles is not None:
-
-            def across(table, **kw):
-                """The band across the members of ``table``: (lower, upper, info), one array twice under weights."""
-                if q_w is None:
-                    return eng.quantiles(table, quantiles, include=inc, **kw)
-                values, winfo = eng.weighted_quantiles(table, quantiles, q_w, include=inc, **kw)
-                return values, values, winfo
-            part['quant'] = across(out_d, member_of_slot=mos)
-            if 'wb' in part:
-                part['wb_quant'] = across(wb_d, member_of_slot=mos)
-        if time_quantiles is not None:
-            lo_d, up_d, tinfo = eng.time_quantiles(out_d, mask, time_quantiles, series=tq_ids, period_of_day=tq_pod,
-                                                   f_tdp=ft, reach_params=rp_d, out_reaches=oreach, member_of_slot=mos,
-                                                   n_periods=None if tq_labels is None else len(tq_labels))
-            if mos is not None:                  # member order, undone on the small result: slot j holds member mos[j]
-                idx = mos.long()
-                lo_d, up_d = lo_d.new_empty(lo_d.shape).index_copy_(-1, idx, lo_d), up_d.new_empty(up_d.shape).index_copy_(-1, idx, up_d)
-            lo_h, up_h = lo_d.cpu().numpy(), up_d.cpu().numpy()
-            tdata = engine.interpolate_time_quantiles(lo_h, up_h, time_quantiles, tinfo['n_days'])
-            part['tq'] = (lo_h if to_host else lo_d, up_h if to_host else up_d, tdata, tinfo)
-            if quantiles is not None:            # the band across the members of the per-member statistics
-                part['tq_quant'] = across(eng.to_device(tdata))
-        if sc_ids is not None:                   # the scores of the observed rows: parameter-only, and with the error model drawn
-            skw = dict(seed=predictive_seed, day0=predictive_day0, include=inc, weights=q_w, f_tdp=ft, reach_params=rp_d,
-                       out_reaches=oreach, member_of_slot=mos)
-            part['scores'] = (eng.predictive_scores(out_d, mask, sc_ids, sc_obs, **skw),
-                              None if sc_m is None else eng.predictive_scores(out_d, mask, sc_ids, sc_obs, err_m=sc_m, **skw))
-        if pr_bands:                             # the bands of the named series: parameter-only, and with the error model drawn
-            pkw = dict(seed=predictive_seed, day0=predictive_day0, include=inc, f_tdp=ft, reach_params=rp_d,
-                       out_reaches=oreach, member_of_slot=mos)
-            if q_w is None:
-                pred_band = lambda **kw: eng.predictive_bands(out_d, mask, quantiles, pr_ids, **dict(pkw, **kw))
-            else:
-                def pred_band(**kw):
-                    values, winfo = eng.predictive_bands(out_d, mask, quantiles, pr_ids, weights=q_w, **dict(pkw, **kw))
-                    return values, values, winfo
-            part['pred'] = (pred_band(), None if pr_m is None else pred_band(err_m=pr_m))
-        part['out_d'] = None if (reduced_on_device and not keep_daily) else out_d
-        return part
-
-    if devices is None:
-        parts = [block_pass(engine.get_engine(device), 0, E)]
-    else:
-        devs = [int(d) for d in devices]
-        if opts.out_slot_order:
-            raise ValueError("devices=[...] returns tables in member order: solver['out_slot_order'] must stay 0")
-        all_bounds = [ensemble.shard_bounds(E, len(devs), r) for r in range(len(devs))]
-        # one context per list entry (a repeated id gets a context of its own: contexts are not re-entrant)
-        engs = [engine.get_engine(d, replica=devs[:r].count(d)) for r, d in enumerate(devs)]
-        live = [(eng_, lo, hi) for eng_, (lo, hi) in zip(engs, all_bounds) if hi > lo]
-        if len(live) == 1:
-            parts = [block_pass(*live[0])]
-        else:
-            from concurrent.futures import ThreadPoolExecutor
-            with ThreadPoolExecutor(max_workers=len(live)) as pool:
-                parts = list(pool.map(lambda a_: block_pass(*a_), live))
-    marshal.epilogue_mutations(p_SU, p_LU, p_SC, p)
-
-    cat = (lambda xs: np.concatenate(xs, axis=-1)) if to_host else (lambda xs: xs[0] if len(xs) == 1 else _torch_cat(xs))
-    if len(parts) == 1:
-        stats = parts[0]['stats']
-    else:
-        per = [pt['stats'] for pt in parts]
-        stats = {k: sum(d_[k] for d_ in per) for k in ('rhs_evals', 'steps', 'rejected', 'n_launches', 'streamed_chunks',
-                                                         'queue_waits')}
-        stats.update({k: max(d_[k] for d_ in per) for k in ('kernel_ms', 'pilot_ms', 'wall_ms', 'd2h_tail_ms',
-                                                            'queue_longest_wait_polls', 'queue_longest_stall_polls')})
-        for k in ('balanced', 'queued', 'lanes_per_wave', 'lanes_per_member'):
-            stats[k] = per[0][k]
-        stats['simt_efficiency'] = float(np.mean([d_['simt_efficiency'] for d_ in per]))
-        stats['per_device'] = [dict(d_, device=int(dv), members=[int(lo), int(hi)])
-                               for d_, dv, (lo, hi) in zip(per, [e_.device for e_, _, _ in live], bounds)]
-    stats['bounds'] = [[int(lo), int(hi)] for lo, hi in bounds]
-    res = dict(columns=marshal.columns_of_mask(mask), reaches=reaches, periods=periods, stats=stats,
-               status=cat([pt['status'] for pt in parts]))
-    if obs is not None:
-        res['gof'] = dict(stats=list(abi.GOF_STATS), variables=list(abi.GOF_VARS), info=parts[0]['gof'][1],
-                          data=cat([pt['gof'][0] for pt in parts]))
-        if parts[0]['gof'][2] is not None:       # Spearman's r [6, n_reaches, E]: the rank statistic of the reference's table (:444-445)
-            res['gof']['spearman'] = cat([pt['gof'][2] for pt in parts])
-    if wb_reaches is not None:
-        if len(wb_reaches) > 1:
-            winfo = parts[0]['wb'][1]
-            res['waterbody'] = dict(columns=winfo['columns'], reaches=wb_reaches, info=winfo, data=cat([pt['wb'][0] for pt in parts]))
-            if wobs is not None:
-                res['waterbody']['gof'] = dict(stats=list(abi.GOF_STATS), variables=list(abi.GOF_VARS), info=parts[0]['wb_gof'][1],
-                                               data=cat([pt['wb_gof'][0] for pt in parts]))
-        else:
-            print('One or fewer reaches were selected to be included in the sum, check your reach structure parameters')   # :896
-            res['waterbody'] = None
-    if quantiles is not None:
-        def band(lower, upper, info):
-            lo_h, up_h = lower.cpu().numpy(), upper.cpu().numpy()
-            if weighted_band:                    # one value per probability: nothing to interpolate
-                return dict(q=list(quantiles), data=lo_h, lower=lo_h if to_host else lower, upper=up_h if to_host else upper,
-                            n_members=info['n_used'], info=info, rule='inverted_cdf', weight_total=int(info['T']))
-            return dict(q=list(quantiles), data=engine.interpolate_quantiles(lo_h, up_h, quantiles, info['n_used']),
-                        lower=lo_h if to_host else lower, upper=up_h if to_host else upper, n_members=info['n_used'], info=info)
-        res['quantiles'] = band(*parts[0]['quant'])
-        if res.get('waterbody') is not None:
-            res['waterbody']['quantiles'] = band(*parts[0]['wb_quant'])
-    if pa_resolved is not None:
-        res['pareto'] = pareto_rules.result(parts[0]['pareto'], pa_resolved)
-    if score:
-        res['scores'] = _scores_result(sc_names, reaches, sc_obs, len(met_df), parts[0].get('scores'), predictive_seed, predictive_day0)
-    if pr_bands:
-        po, ov = parts[0]['pred']
-        po_b, ov_b = band(*po), None if ov is None else band(*ov)
-        info = dict(param_only=po_b.pop('info'), overall=None if ov_b is None else ov_b.pop('info'))
-        extra = dict(rule=po_b['rule'], weight_total=po_b['weight_total']) if weighted_band else {}
-        for b_ in (po_b, ov_b):
-            if b_ is not None:
-                del b_['q'], b_['n_members']
-        res['predictive'] = dict(q=list(quantiles), series=list(pr_names), param_only=po_b, overall=ov_b,
-                                 n_members=po[2]['n_used'], seed=predictive_seed, day0=predictive_day0, info=info, **extra)
-    if time_quantiles is not None:
-        tinfo = parts[0]['tq'][3]
-        res['time_quantiles'] = dict(q=list(time_quantiles), series=list(tq_names), periods=tq_labels,
-                                     lower=cat([pt['tq'][0] for pt in parts]), upper=cat([pt['tq'][1] for pt in parts]),
-                                     data=np.concatenate([pt['tq'][2] for pt in parts], axis=-1),
-                                     n_days=np.asarray(tinfo['n_days']), info=tinfo)
-        if quantiles is not None:
-            res['time_quantiles']['quantiles'] = band(*parts[0]['tq_quant'])
-    if return_state:
-        sts = [pt['state'] for pt in parts]
-        if return_state == 'device':
-            sdata = sts[0] if len(sts) == 1 else sts
-        elif to_host:
-            sdata = np.concatenate([t.cpu().numpy() for t in sts], axis=-1)
-        else:
-            sdata = cat(sts)
-        res['state'] = dict(rows=list(abi.STATE_ROWS), reaches=list(scs), data=sdata, end=met_df.index[-1])
-    if reduced_on_device and not keep_daily:
-        res['data'] = None
-    elif not to_host:
-        res['data'] = parts[0]['out_d'] if len(parts) == 1 else [pt['out_d'] for pt in parts]
-    elif len(parts) == 1:
-        res['data'] = parts[0]['host_out']
-    else:
-        # one table in member order: every block's page-locked table is copied into its member range (one host thread per
-        # block; numpy releases the GIL in the copy), block by block freed
-        data = np.empty((ncols_, rows_, n_or_, E), dtype=np.float64)
-
-        def place(k):
-            lo, hi = bounds[k]
-            data[..., lo:hi] = parts[k]['host_out']
-            parts[k]['host_out'] = None
-        from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=len(parts)) as pool:
-            list(pool.map(place, range(len(parts))))
-        res['data'] = data
-    return res
+    rq = _request(**locals())
+    with marshal.reference_edits(p_SU, p_LU, p_SC, p):
+        _bind_members(rq)
+        _bind_outputs(rq)
+        return _assemble(rq, _run_blocks(rq))
 
 
 def _mean_crps(crps):
@@ -930,7 +921,6 @@ def _mean_crps(crps):
 def _scores_result(series, reaches, obs, D, got, seed, day0):
     """``res['scores']`` from the two ``Engine.predictive_scores`` results (parameter-only, overall or None); ``got`` None: no
     series has an observation."""
-    from . import score as score_rules
 
     def one(sums, counts, info):
         sums, counts = sums.cpu().numpy(), counts.cpu().numpy()
@@ -980,7 +970,6 @@ def run_simply_p_ensemble_windows(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_
     where a later run continues).  ``status`` is per window: the status of the whole run is the OR over the items (a
     member that went non-finite carries the NaN in its state and is flagged in every later window too).  Bad arguments
     raise when the generator is created, not at its first item."""
-    from . import ensemble
     met_sets = list(met_df) if isinstance(met_df, (list, tuple)) else [met_df]
     index = met_sets[0].index
     reduce = kwargs.get('reduce')

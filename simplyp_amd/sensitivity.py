@@ -10,10 +10,11 @@ import time
 
 import numpy as np
 
-from . import abi, marshal, priors as _priors, sobol
+from . import abi, engine, marshal, priors as _priors, request, sobol, visualise_results as vr
+from .model import _DeviceEnsemble, _engine_opts
 
 
-def _plan(priors, n_base, columns, reduce, obs_dict, n_boot, conf, seed, unit_samples, n_days):
+def _plan(priors, n_base, columns, reduce, obs_dict, n_boot, conf, seed, unit_samples, index):
     """Everything the call can check without the device; raises ValueError."""
     if not isinstance(priors, dict) or not priors:
         raise ValueError("priors must be a dict name -> (lo, hi) with at least one entry")
@@ -40,21 +41,12 @@ def _plan(priors, n_base, columns, reduce, obs_dict, n_boot, conf, seed, unit_sa
     bad = [c for c in columns if c not in marshal.OUT_COLUMNS]
     if bad or not columns or len(set(columns)) != len(columns):
         raise ValueError("columns must be distinct names among the reference's columns (got %s)" % columns)
-    if isinstance(reduce, str):
-        if reduce not in ('annual', 'total'):
-            raise ValueError("reduce must be 'annual', 'total' or an array of period indices")
-        period = reduce
-    else:
-        period = np.asarray(reduce)
-        if period.shape != (n_days,) or period.min() < 0:
-            raise ValueError("reduce array needs one non-negative period index per day")
-        period = np.ascontiguousarray(period, dtype=np.int32)
+    period = request.reduce_periods(reduce, index, total=True)[1]
     return names, np.array(target, dtype=np.int32), lo, hi, N, n_boot, seed, unit, columns, period
 
 
 def _intervals(eng, ind_d, n_boot, conf):
     """The percentile interval over the bootstrap axis, selected on the device: ``[2] + ind.shape[:-1]`` (NaN without resamples)."""
-    from . import engine
     shape = tuple(int(v) for v in ind_d.shape[:-1])
     if n_boot < 1:
         return np.full((2,) + shape, np.nan), 0.0
@@ -104,73 +96,51 @@ def sobol_indices(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, priors,
     ``n_base`` out of range, ``conf`` outside (0, 1), a ``unit_samples`` of the wrong shape or outside [0, 1), ``'f_TDP'``
     without ``obs_dict``.  The caller's ``p_LU`` / ``p_SC`` are edited in place exactly as by ``run_simply_p``."""
     names, target, lo, hi, N, n_boot, seed, unit, columns, period = _plan(priors, n_base, columns, reduce, obs_dict, n_boot, conf,
-                                                                            seed, unit_samples, len(met_df))
+                                                                            seed, unit_samples, met_df.index)
     n_dim = len(names)
     E = N * (n_dim + 2)
-    marshal.prologue(p_SU, p_LU, p_SC, p)
-    scs = marshal.sc_list(p)
-    up_ptr, up_idx, _ = marshal.topology(p_struc, p)
-    reaches = scs if out_reaches is None else list(out_reaches)
-    oreach = None if out_reaches is None else [scs.index(int(r)) for r in out_reaches]
-    _priors.check_corners(names, lo, hi, p, p_LU, p_SC, scs)
-    snow = _priors.snow_rule(names, met_df)
-    if isinstance(period, str):
-        period = np.unique(np.asarray(met_df.index.year), return_inverse=True)[1] if period == 'annual' else np.zeros(len(met_df))
-        period = np.ascontiguousarray(period, dtype=np.int32)
-    n_periods = int(period.max()) + 1
-    obs = None
-    if obs_dict:
-        from . import visualise_results as vr
-        obs = vr.observation_array(obs_dict, reaches, met_df.index)
+    with marshal.reference_edits(p_SU, p_LU, p_SC, p):
+        scs, up_ptr, up_idx, reaches, oreach = marshal.catchment(p_struc, p, out_reaches)
+        _priors.check_corners(names, lo, hi, p, p_LU, p_SC, scs)
+        snow = _priors.snow_rule(names, met_df)
+        obs = vr.observation_array(obs_dict, reaches, met_df.index) if obs_dict else None
 
-    # ---- the device: everything is marshalled and uploaded once
-    from . import engine
-    from .model import _engine_opts
-    eng = engine.get_engine(device)
-    torch = eng.torch
-    w0 = time.perf_counter()
-    mask = marshal.mask_of_columns(columns)
-    opts = _engine_opts(p_SU, p, dynamic_options, step_len, solver, mask, n_periods=n_periods, snow=snow)
-    if opts.out_slot_order:
-        raise ValueError("sobol_indices keeps members in design order: solver['out_slot_order'] must stay 0")
-    forcing, doy = marshal.forcing_arrays(met_df, snow=snow)
-    f_d, doy_d = eng.to_device(forcing, torch.float64), eng.to_device(doy, torch.int32)
-    mp_d = eng.to_device(marshal.member_params(p, p_LU, E), torch.float64)
-    rp_d = eng.to_device(marshal.reach_params(p_SC, p, E), torch.float64)
-    ft_d = torch.full((E,), float(p['f_TDP']), dtype=torch.float64, device=eng.tdev)
-    x_d, dinfo = eng.sobol_design(N, lo, hi, target, mp_d, ft_d, seed=seed, unit=unit)
-    out_d, status_d, rstats = eng.run(f_d, doy_d, mp_d, rp_d, up_ptr, up_idx, opts, out_reaches=oreach, period_of_day=period)
-    ind_d, sums_d, n_used_d, sinfo = eng.sobol_indices(out_d, N, n_dim, status=status_d, n_boot=n_boot, seed=seed)
-    res, q_ms = _result(eng, ind_d, sums_d, n_used_d, n_boot, conf)
-    order = [marshal.columns_of_mask(mask).index(c) for c in columns]      # the table's columns are in mask order
-    for k in ('S1', 'ST'):
-        res[k] = np.ascontiguousarray(res[k][:, order])
-    for k in ('S1_conf', 'ST_conf'):
-        res[k] = np.ascontiguousarray(res[k][:, :, order])
-    res['var'] = np.ascontiguousarray(res['var'][order])
-    stats = dict(run_kernel_ms=rstats['kernel_ms'], design_ms=dinfo['kernel_ms'], counts_ms=sinfo['counts_ms'],
-                 contract_ms=sinfo['contract_ms'], quantile_ms=q_ms)
-    res.update(names=names, columns=columns, reaches=reaches, n_valid=sinfo['n_valid'], x=x_d.cpu().numpy(),
-               status=status_d.cpu().numpy())
-    if keep_table:
-        res['table'] = np.ascontiguousarray(out_d.cpu().numpy()[order])
-    if obs is not None:
-        del out_d
-        gcols = ['Qr', 'Msus_kg/day', 'TDP_kg/day', 'PP_kg/day']              # what simplyp_gof reads
-        gmask = marshal.mask_of_columns(gcols)
-        gopts = _engine_opts(p_SU, p, dynamic_options, step_len, solver, gmask, snow=snow)
-        daily_d, gstatus_d, gstats = eng.run(f_d, doy_d, mp_d, rp_d, up_ptr, up_idx, gopts, out_reaches=oreach)
-        gof_d, _ = eng.gof(daily_d, gmask, obs, ft_d, rp_d, out_reaches=oreach)
-        del daily_d
-        gi_d, gs_d, gn_d, ginfo = eng.sobol_indices(gof_d, N, n_dim, status=gstatus_d, n_boot=n_boot, seed=seed)
-        gres, gq_ms = _result(eng, gi_d, gs_d, gn_d, n_boot, conf)
-        gres.update(stats=list(abi.GOF_STATS), variables=list(abi.GOF_VARS), n_valid=ginfo['n_valid'])
-        res['gof'] = gres
-        stats['run_kernel_ms'] += gstats['kernel_ms']
-        stats['counts_ms'] += ginfo['counts_ms']
-        stats['contract_ms'] += ginfo['contract_ms']
-        stats['quantile_ms'] += gq_ms
-    marshal.epilogue_mutations(p_SU, p_LU, p_SC, p)
+        # ---- the device: everything is marshalled and uploaded once
+        w0 = time.perf_counter()
+        dev = _DeviceEnsemble("sobol_indices keeps members in design order", met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len,
+                              solver, device, E, columns, snow, n_periods=int(period.max()) + 1)
+        eng = dev.eng
+        run = lambda opts, **kw: eng.run(dev.f_d, dev.doy_d, dev.mp_d, dev.rp_d, up_ptr, up_idx, opts, out_reaches=oreach, **kw)
+        x_d, dinfo = eng.sobol_design(N, lo, hi, target, dev.mp_d, dev.ft_d, seed=seed, unit=unit)
+        out_d, status_d, rstats = run(dev.opts, period_of_day=period)
+        ind_d, sums_d, n_used_d, sinfo = eng.sobol_indices(out_d, N, n_dim, status=status_d, n_boot=n_boot, seed=seed)
+        res, q_ms = _result(eng, ind_d, sums_d, n_used_d, n_boot, conf)
+        order = [marshal.columns_of_mask(dev.mask).index(c) for c in columns]      # the table's columns are in mask order
+        for k in ('S1', 'ST'):
+            res[k] = np.ascontiguousarray(res[k][:, order])
+        for k in ('S1_conf', 'ST_conf'):
+            res[k] = np.ascontiguousarray(res[k][:, :, order])
+        res['var'] = np.ascontiguousarray(res['var'][order])
+        stats = dict(run_kernel_ms=rstats['kernel_ms'], design_ms=dinfo['kernel_ms'], counts_ms=sinfo['counts_ms'],
+                     contract_ms=sinfo['contract_ms'], quantile_ms=q_ms)
+        res.update(names=names, columns=columns, reaches=reaches, n_valid=sinfo['n_valid'], x=x_d.cpu().numpy(),
+                   status=status_d.cpu().numpy())
+        if keep_table:
+            res['table'] = np.ascontiguousarray(out_d.cpu().numpy()[order])
+        if obs is not None:
+            del out_d
+            gmask = marshal.mask_of_columns(marshal.FLUX_COLUMNS)                  # what simplyp_gof reads
+            daily_d, gstatus_d, gstats = run(_engine_opts(p_SU, p, dynamic_options, step_len, solver, gmask, snow=snow))
+            gof_d, _ = eng.gof(daily_d, gmask, obs, dev.ft_d, dev.rp_d, out_reaches=oreach)
+            del daily_d
+            gi_d, gs_d, gn_d, ginfo = eng.sobol_indices(gof_d, N, n_dim, status=gstatus_d, n_boot=n_boot, seed=seed)
+            gres, gq_ms = _result(eng, gi_d, gs_d, gn_d, n_boot, conf)
+            gres.update(stats=list(abi.GOF_STATS), variables=list(abi.GOF_VARS), n_valid=ginfo['n_valid'])
+            res['gof'] = gres
+            stats['run_kernel_ms'] += gstats['kernel_ms']
+            stats['counts_ms'] += ginfo['counts_ms']
+            stats['contract_ms'] += ginfo['contract_ms']
+            stats['quantile_ms'] += gq_ms
     stats['wall_ms'] = 1e3 * (time.perf_counter() - w0)
     res['stats'] = stats
     return res
