@@ -438,6 +438,12 @@ void  simplyp_device_free(simplyp_ctx* ctx, void* p);
 int   simplyp_memcpy_h2d(simplyp_ctx* ctx, void* dst, const void* src, int64_t bytes);
 int   simplyp_memcpy_d2h(simplyp_ctx* ctx, void* dst, const void* src, int64_t bytes);
 
+/* ---- what every entry below has in common (the reductions over a table, the samplers' steps, simplyp_eval_units) ----------
+ * A NULL context is SIMPLYP_ERR_ARG.  While a run is pending on the context -- simplyp_run_async without its simplyp_sync --
+ * every one of them returns SIMPLYP_ERR_ARG ("<entry>: a run is pending on this context; call simplyp_sync first") and launches
+ * nothing: they time themselves with the events the pending run's statistics are read from.  A call refused for its arguments
+ * has launched nothing either and leaves `info` as it was; a call that succeeds has written every field of `info`. */
+
 /* ---- goodness of fit per member (the reference's goodness_of_fit_stats, visualise_results.py:387-474, for a whole
  * ensemble on the device) ------------------------------------------------------------ */
 enum {  /* variables, in the order of stats_var_li (visualise_results.py:400); simulated series = df_R columns

@@ -35,7 +35,14 @@ class Opts(C.Structure):
                 ('lanes_per_member', C.c_int32), ('stiff_pair', C.c_int32)]
 
 
-class Stats(C.Structure):
+class _Info(C.Structure):
+    """What the library reports of a call: a struct of include/simplyp.h read back as a dict (reserved fields left out)."""
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
+
+
+class Stats(_Info):
     _fields_ = [('rhs_evals', C.c_uint64), ('steps', C.c_uint64), ('rejected', C.c_uint64),
                 ('kernel_ms', C.c_double), ('pilot_ms', C.c_double), ('simt_efficiency', C.c_double), ('n_launches', C.c_int32), ('balanced', C.c_int32),
                 ('queued', C.c_int32), ('lanes_per_wave', C.c_int32), ('lanes_per_member', C.c_int32), ('streamed_chunks', C.c_int32),
@@ -43,63 +50,42 @@ class Stats(C.Structure):
                 ('queue_waits', C.c_uint64), ('queue_longest_wait_polls', C.c_uint32), ('pack_overflow_blocks', C.c_uint32), ('queue_longest_stall_polls', C.c_uint64),
                 ('stiff_pair', C.c_int32), ('packed_records', C.c_int32)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
 
-
-class GofInfo(C.Structure):
+class GofInfo(_Info):
     """simplyp_gof_info of include/simplyp.h."""
     _fields_ = [('kernel_ms', C.c_double), ('bytes_read', C.c_int64), ('n_q_days', C.c_int32), ('n_chem_days', C.c_int32),
                 ('n_chunks_q', C.c_int32), ('n_chunks_chem', C.c_int32)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class WbInfo(C.Structure):
+class WbInfo(_Info):
     """simplyp_wb_info of include/simplyp.h."""
     _fields_ = [('kernel_ms', C.c_double), ('bytes_moved', C.c_int64)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class QuantileInfo(C.Structure):
+class QuantileInfo(_Info):
     """simplyp_quantile_info of include/simplyp.h."""
     _fields_ = [('kernel_ms', C.c_double), ('bytes_table', C.c_int64), ('n_used', C.c_int32), ('n_passes', C.c_int32)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class WqInfo(C.Structure):
+class WqInfo(_Info):
     """simplyp_wq_info of include/simplyp.h."""
     _fields_ = [('kernel_ms', C.c_double), ('bytes_table', C.c_int64), ('T', C.c_uint64), ('n_used', C.c_int32), ('n_passes', C.c_int32)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class ScoreInfo(C.Structure):
+class ScoreInfo(_Info):
     """simplyp_score_info of include/simplyp.h."""
     _fields_ = [('kernel_ms', C.c_double), ('gen_ms', C.c_double), ('sort_ms', C.c_double), ('bytes_read', C.c_int64),
                 ('bytes_workspace', C.c_int64), ('T', C.c_uint64), ('n_used', C.c_int32), ('n_rows_scored', C.c_int32),
                 ('n_chunks', C.c_int32), ('reserved', C.c_int32)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
-
 
 SCORE_TILE = 4096               # (key, weight) pairs the scores' LDS sort takes at once (simplyp_score.h)
 
 
-class ParetoInfo(C.Structure):
+class ParetoInfo(_Info):
     """simplyp_pareto_info of include/simplyp.h."""
     _fields_ = [('kernel_ms', C.c_double), ('pair_tests', C.c_int64), ('n_used', C.c_int32), ('n_fronts', C.c_int32),
                 ('n_front0', C.c_int32), ('n_unranked', C.c_int32)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 PARETO_MAX_OBJ = 8              # objectives per call (SIMPLYP_PARETO_MAX_OBJ)
@@ -110,63 +96,44 @@ PARETO_JTILE = 512              # the other side of the pairs: keys staged in LD
 PARETO_JSPLIT = 2048            # and the stretch of them one workgroup takes; the grid's second axis splits the rest
 
 
-class TqInfo(C.Structure):
+class TqInfo(_Info):
     """simplyp_tq_info of include/simplyp.h."""
     _fields_ = [('kernel_ms', C.c_double), ('bytes_read', C.c_int64), ('n_sweeps', C.c_int32), ('n_periods', C.c_int32)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class PredInfo(C.Structure):
+class PredInfo(_Info):
     """simplyp_pred_info of include/simplyp.h."""
     _fields_ = [('kernel_ms', C.c_double), ('gen_ms', C.c_double), ('bytes_read', C.c_int64), ('bytes_workspace', C.c_int64),
                 ('n_used', C.c_int32), ('n_passes', C.c_int32), ('n_chunks', C.c_int32), ('reserved', C.c_int32)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
 
-
-class McmcInfo(C.Structure):
+class McmcInfo(_Info):
     """simplyp_mcmc_info of include/simplyp.h."""
     _fields_ = [('kernel_ms', C.c_double), ('n_inside', C.c_int32), ('n_accepted', C.c_int32), ('n_nan', C.c_int32),
                 ('reserved', C.c_int32)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
 
 
 MCMC_TARGET_F_TDP = -1          # simplyp_mcmc_propose: the dimension goes to f_tdp
 MCMC_TARGET_NONE = -2           # ... nowhere: an error-model m
 
 
-class NmInfo(C.Structure):
+class NmInfo(_Info):
     """simplyp_nm_info of include/simplyp.h."""
     _fields_ = [('kernel_ms', C.c_double), ('n_active', C.c_int32), ('n_converged', C.c_int32), ('n_shrinking', C.c_int32),
                 ('n_nonfinite_start', C.c_int32), ('n_inside', C.c_int32), ('reserved', C.c_int32)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
 
-
-class SobolInfo(C.Structure):
+class SobolInfo(_Info):
     """simplyp_sobol_info of include/simplyp.h."""
     _fields_ = [('kernel_ms', C.c_double), ('counts_ms', C.c_double), ('contract_ms', C.c_double), ('flops', C.c_int64),
                 ('bytes_workspace', C.c_int64), ('n_valid', C.c_int32), ('n_resamples', C.c_int32)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class PfInfo(C.Structure):
+class PfInfo(_Info):
     """simplyp_pf_info of include/simplyp.h."""
     _fields_ = [('kernel_ms', C.c_double), ('lw_max', C.c_double), ('sum_w', C.c_double), ('sum_w2', C.c_double),
                 ('T', C.c_uint64), ('n_alive', C.c_int32), ('n_nan', C.c_int32), ('n_unique', C.c_int32), ('n_bad', C.c_int32),
                 ('n_outside', C.c_int32), ('reserved', C.c_int32)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith('reserved')}
-
 
 PF_MAX_LOG2_E = 22              # the particle filter's entries take 1 <= E <= 2^22
 PF_WEIGHT_BITS = 40             # ... and resolve normalised weights to 2^-40

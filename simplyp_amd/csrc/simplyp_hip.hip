@@ -52,6 +52,7 @@ struct simplyp_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     hipEvent_t ev_start = nullptr, ev_main = nullptr, ev_stop = nullptr;
+    hipEvent_t ev_lap[3] = {};          // spare timing events of the analysis entries (generation, sort and contraction laps)
     DeviceBuf route;          // [n_slots][4][D][E] fp64
     DeviceBuf sched;          // int32 schedule arrays
     DeviceBuf counters;       // N_COUNTERS x uint64: rhs, steps, rejected, wave-level attempts, queue waits / longest wait / longest stall
@@ -139,6 +140,32 @@ int ensure(simplyp_ctx* ctx, DeviceBuf& b, size_t bytes)
         return fail(ctx, SIMPLYP_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(err));
     b.bytes = bytes;
     return SIMPLYP_OK;
+}
+
+// Host-side C++ (std::vector, std::thread) must not throw across the C boundary: every exported function that allocates
+// runs its body through this.
+template <class F>
+int guarded(simplyp_ctx* ctx, F&& body)
+{
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        return fail(ctx, SIMPLYP_ERR_NOMEM, "host memory allocation failed");
+    } catch (const std::exception& e) {
+        return fail(ctx, SIMPLYP_ERR_DEVICE, "unexpected host error: %s", e.what());
+    }
+}
+
+// ceil(n / threads): the blocks of a one-dimensional grid.
+template <class N>
+unsigned blocks(N n, int threads) { return (unsigned)((n + threads - 1) / threads); }
+
+// A 64-bit seed as the two halves of a Philox key.
+template <class G>
+void philox_key(uint64_t seed, G& g)
+{
+    g.key0 = (uint32_t)(seed & 0xFFFFFFFFull);
+    g.key1 = (uint32_t)(seed >> 32);
 }
 
 // One launch = a set of mutually independent chains; a chain = reaches one thread walks in order.
@@ -934,6 +961,7 @@ int simplyp_ctx_create(int device, simplyp_ctx** out)
     if (err == hipSuccess) { ctx->own_stream = true; err = hipEventCreate(&ctx->ev_start); }
     if (err == hipSuccess) err = hipEventCreate(&ctx->ev_stop);
     if (err == hipSuccess) err = hipEventCreate(&ctx->ev_main);
+    for (hipEvent_t& ev : ctx->ev_lap) if (err == hipSuccess) err = hipEventCreate(&ev);
     if (err == hipSuccess) err = hipEventCreate(&ctx->ev_copy_done);
     for (int i = 0; i < simplyp_ctx::N_COPY_STREAMS && err == hipSuccess; ++i) {
         err = hipStreamCreateWithFlags(&ctx->copy_streams[i], hipStreamNonBlocking);
@@ -1011,6 +1039,7 @@ void simplyp_ctx_destroy(simplyp_ctx* ctx)
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
     if (ctx->ev_main) (void)hipEventDestroy(ctx->ev_main);
+    for (hipEvent_t ev : ctx->ev_lap) if (ev) (void)hipEventDestroy(ev);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1028,44 +1057,30 @@ int64_t simplyp_out_bytes(const simplyp_dims* dims, const simplyp_opts* opts, in
     return (int64_t)popcount32(opts->out_mask & (SIMPLYP_MASK_ALL | SIMPLYP_MASK_D_SNOW)) * rows * nor * dims->E * (int64_t)sizeof(double);
 }
 
-static int plan_impl(int32_t S, const int32_t* up_ptr, const int32_t* up_idx, int32_t* n_launches, int32_t* n_slots,
-                     int32_t* launch_of_reach, int32_t* chain_of_reach, int32_t* pos_in_chain, int32_t* route_slot)
-{
-    if (S <= 0 || !up_ptr || (up_ptr[S] > 0 && !up_idx)) return fail(nullptr, SIMPLYP_ERR_ARG, "bad plan arguments");
-    simplyp_ctx tmp;
-    Schedule sch;
-    int rc = build_schedule(&tmp, S, up_ptr, up_idx, sch);
-    if (rc != SIMPLYP_OK) { g_create_error = tmp.error; return rc; }
-    if (n_launches) *n_launches = (int32_t)sch.launches.size();
-    if (n_slots) *n_slots = sch.n_slots;
-    for (size_t l = 0; l < sch.launches.size(); ++l) {
-        const Launch& L = sch.launches[l];
-        for (size_t c = 0; c + 1 < L.chain_ptr.size(); ++c)
-            for (int i = L.chain_ptr[c]; i < L.chain_ptr[c + 1]; ++i) {
-                const int s = L.chain_reach[i];
-                if (launch_of_reach) launch_of_reach[s] = (int32_t)l;
-                if (chain_of_reach) chain_of_reach[s] = (int32_t)c;
-                if (pos_in_chain) pos_in_chain[s] = i - L.chain_ptr[c];
-            }
-    }
-    if (route_slot) for (int s = 0; s < S; ++s) route_slot[s] = sch.route_slot[s];
-    return SIMPLYP_OK;
-}
-
-// Host-side C++ (std::vector, std::thread) must not throw across the C boundary.
-#define SIMPLYP_GUARD(ctx, call)                                                                    \
-    try {                                                                                           \
-        return call;                                                                                \
-    } catch (const std::bad_alloc&) {                                                               \
-        return fail(ctx, SIMPLYP_ERR_NOMEM, "host memory allocation failed");                       \
-    } catch (const std::exception& e) {                                                             \
-        return fail(ctx, SIMPLYP_ERR_DEVICE, "unexpected host error: %s", e.what());                \
-    }
-
 int simplyp_plan(int32_t S, const int32_t* up_ptr, const int32_t* up_idx, int32_t* n_launches, int32_t* n_slots,
                  int32_t* launch_of_reach, int32_t* chain_of_reach, int32_t* pos_in_chain, int32_t* route_slot)
 {
-    SIMPLYP_GUARD(nullptr, plan_impl(S, up_ptr, up_idx, n_launches, n_slots, launch_of_reach, chain_of_reach, pos_in_chain, route_slot))
+    return guarded(nullptr, [&]() -> int {
+        if (S <= 0 || !up_ptr || (up_ptr[S] > 0 && !up_idx)) return fail(nullptr, SIMPLYP_ERR_ARG, "bad plan arguments");
+        simplyp_ctx tmp;
+        Schedule sch;
+        int rc = build_schedule(&tmp, S, up_ptr, up_idx, sch);
+        if (rc != SIMPLYP_OK) { g_create_error = tmp.error; return rc; }
+        if (n_launches) *n_launches = (int32_t)sch.launches.size();
+        if (n_slots) *n_slots = sch.n_slots;
+        for (size_t l = 0; l < sch.launches.size(); ++l) {
+            const Launch& L = sch.launches[l];
+            for (size_t c = 0; c + 1 < L.chain_ptr.size(); ++c)
+                for (int i = L.chain_ptr[c]; i < L.chain_ptr[c + 1]; ++i) {
+                    const int s = L.chain_reach[i];
+                    if (launch_of_reach) launch_of_reach[s] = (int32_t)l;
+                    if (chain_of_reach) chain_of_reach[s] = (int32_t)c;
+                    if (pos_in_chain) pos_in_chain[s] = i - L.chain_ptr[c];
+                }
+        }
+        if (route_slot) for (int s = 0; s < S; ++s) route_slot[s] = sch.route_slot[s];
+        return SIMPLYP_OK;
+    });
 }
 
 static int run_async_body(simplyp_ctx* ctx, const simplyp_dims* dims, const simplyp_opts* opts,
@@ -1193,9 +1208,9 @@ int simplyp_run_async(simplyp_ctx* ctx, const simplyp_dims* dims, const simplyp_
                       const int32_t* out_reaches, int32_t n_out_reaches,
                       double* out, int32_t* member_status, int32_t* member_of_slot, uint32_t* member_rhs_evals)
 {
-    SIMPLYP_GUARD(ctx, run_async_impl(ctx, dims, opts, forcing, doy, period_of_day, forcing_of_member, member_params, reach_params,
+    return guarded(ctx, [&] { return run_async_impl(ctx, dims, opts, forcing, doy, period_of_day, forcing_of_member, member_params, reach_params,
                                       up_ptr, up_idx, out_reaches, n_out_reaches, out, member_status, member_of_slot,
-                                      member_rhs_evals))
+                                      member_rhs_evals); });
 }
 
 static int sync_impl(simplyp_ctx* ctx, simplyp_stats* stats)
@@ -1350,14 +1365,14 @@ static int fetch_packed_impl(simplyp_ctx* ctx, const double* dev_table, int32_t 
 int simplyp_fetch_packed(simplyp_ctx* ctx, const double* dev_table, int32_t n_cols, int32_t rows, int32_t row_doubles,
                          int32_t chunk_days, double* host_out, int64_t host_bytes, int32_t* counts)
 {
-    SIMPLYP_GUARD(ctx, fetch_packed_impl(ctx, dev_table, n_cols, rows, row_doubles, chunk_days, nullptr, host_out, host_bytes, counts, nullptr))
+    return guarded(ctx, [&] { return fetch_packed_impl(ctx, dev_table, n_cols, rows, row_doubles, chunk_days, nullptr, host_out, host_bytes, counts, nullptr); });
 }
 
 int simplyp_fetch_packed_pred(simplyp_ctx* ctx, const double* dev_table, int32_t n_cols, int32_t rows, int32_t row_doubles,
                               int32_t chunk_days, const int32_t* pred_col, double* host_out, int64_t host_bytes, int32_t* counts,
                               int64_t* bytes)
 {
-    SIMPLYP_GUARD(ctx, fetch_packed_impl(ctx, dev_table, n_cols, rows, row_doubles, chunk_days, pred_col, host_out, host_bytes, counts, bytes))
+    return guarded(ctx, [&] { return fetch_packed_impl(ctx, dev_table, n_cols, rows, row_doubles, chunk_days, pred_col, host_out, host_bytes, counts, bytes); });
 }
 
 static int pack_roundtrip_host_impl(const double* table, int32_t n_cols, int32_t rows, int32_t row_doubles, int32_t chunk_days,
@@ -1400,13 +1415,13 @@ static int pack_roundtrip_host_impl(const double* table, int32_t n_cols, int32_t
 int simplyp_pack_roundtrip_host(const double* table, int32_t n_cols, int32_t rows, int32_t row_doubles, int32_t chunk_days,
                                 double* out, int32_t* counts)
 {
-    SIMPLYP_GUARD(nullptr, pack_roundtrip_host_impl(table, n_cols, rows, row_doubles, chunk_days, nullptr, out, counts, nullptr))
+    return guarded(nullptr, [&] { return pack_roundtrip_host_impl(table, n_cols, rows, row_doubles, chunk_days, nullptr, out, counts, nullptr); });
 }
 
 int simplyp_pack_roundtrip_host_pred(const double* table, int32_t n_cols, int32_t rows, int32_t row_doubles, int32_t chunk_days,
                                      const int32_t* pred_col, double* out, int32_t* counts, int64_t* bytes)
 {
-    SIMPLYP_GUARD(nullptr, pack_roundtrip_host_impl(table, n_cols, rows, row_doubles, chunk_days, pred_col, out, counts, bytes))
+    return guarded(nullptr, [&] { return pack_roundtrip_host_impl(table, n_cols, rows, row_doubles, chunk_days, pred_col, out, counts, bytes); });
 }
 
 int64_t simplyp_state_bytes(const simplyp_dims* dims)
@@ -1450,47 +1465,108 @@ static_assert(st::TARGET_F_TDP == simplyp::MCMC_TARGET_F_TDP && st::TARGET_NONE 
         if (int rc__ = (call)) return fail(ctx, rc__, "%s", msg.c_str());       \
     } while (0)
 
-// The timed bracket of an entry: ev_start before its launches; after them ev_stop, the read-back of its device counters if it
-// has any (`bytes` from `src` to `dst`), and the wait for all of it.  *ms (an info's kernel_ms, or NULL): ev_start to ev_stop.
-static int timed_begin(simplyp_ctx* ctx)
+// The frame of an analysis entry: constructed by entry() with the context and the entry's name, opened, and then the one
+// place that says how an entry is refused, timed and checked.  open() states, in this order: a NULL context is SIMPLYP_ERR_ARG; a
+// context with a run pending is refused (ev_start / ev_stop below are that run's until simplyp_sync has read them); the
+// context's device becomes current.  Nothing of an entry runs before open() has passed.
+struct Entry {
+    simplyp_ctx* ctx;
+    const char* me;
+
+    int open() const
+    {
+        if (!ctx) return SIMPLYP_ERR_ARG;
+        if (ctx->pending) return refuse("a run is pending on this context; call simplyp_sync first");
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        return SIMPLYP_OK;
+    }
+
+    // SIMPLYP_ERR_ARG with the message "<me>: <text>".
+    __attribute__((format(printf, 2, 3))) int refuse(const char* fmt, ...) const
+    {
+        char text[512];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(text, sizeof(text), fmt, ap);
+        va_end(ap);
+        return fail(ctx, SIMPLYP_ERR_ARG, "%s: %s", me, text);
+    }
+
+    // After a launch.
+    int launched() const { HIP_TRY(ctx, hipGetLastError()); return SIMPLYP_OK; }
+
+    // The timed bracket: ev_start before the entry's launches; after them the check of the last launch, ev_stop, the read-back
+    // of the entry's device counters if it has any (`bytes` from `src` to `dst`), and the wait for all of it.  *ms (an info's
+    // kernel_ms, or NULL): ev_start to ev_stop.
+    int begin() const { HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream)); return SIMPLYP_OK; }
+
+    int end(double* ms, void* dst = nullptr, const void* src = nullptr, size_t bytes = 0) const
+    {
+        if (int rc = launched()) return rc;
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
+        if (bytes) HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        float f = 0.f;
+        HIP_TRY(ctx, hipEventElapsedTime(&f, ctx->ev_start, ctx->ev_stop));
+        if (ms) *ms = f;
+        return SIMPLYP_OK;
+    }
+};
+
+// An analysis entry: its frame opened, then its body, under guarded().
+extern "C++" {
+template <class F>
+static int entry(simplyp_ctx* ctx, const char* name, F&& body)
 {
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
+    return guarded(ctx, [&]() -> int {
+        const Entry e{ctx, name};
+        if (int rc = e.open()) return rc;
+        return body(e);
+    });
+}
+}  // extern "C++"
+
+// Host lists bound for one device buffer: the int32 lists (padded to an even count), then the double lists, in one upload.
+struct Staging {
+    std::vector<int32_t> ints;
+    std::vector<double> dbl;
+    const int32_t* d_ints = nullptr;       // after upload(): where the lists are on the device
+    const double* d_dbl = nullptr;
+
+    size_t put(const std::vector<int32_t>& v) { const size_t at = ints.size(); ints.insert(ints.end(), v.begin(), v.end()); return at; }
+    size_t put(const std::vector<double>& v) { const size_t at = dbl.size(); dbl.insert(dbl.end(), v.begin(), v.end()); return at; }
+    size_t bytes()
+    {
+        if (ints.size() & 1) ints.push_back(0);
+        return ints.size() * sizeof(int32_t) + dbl.size() * sizeof(double);
+    }
+    // To `base`, which has room for bytes(), on the entry's stream.  The lists must outlive the copies: pageable memory is staged
+    // before the call returns, and every entry synchronises its stream before it returns in any case.
+    int upload(const Entry& e, void* base)
+    {
+        simplyp_ctx* const ctx = e.ctx;
+        const size_t ibytes = ints.size() * sizeof(int32_t), dbytes = dbl.size() * sizeof(double);
+        d_ints = (const int32_t*)base;
+        d_dbl = (const double*)((char*)base + ibytes);
+        if (ibytes) HIP_TRY(ctx, hipMemcpyAsync(base, ints.data(), ibytes, hipMemcpyHostToDevice, ctx->stream));
+        if (dbytes) HIP_TRY(ctx, hipMemcpyAsync((char*)base + ibytes, dbl.data(), dbytes, hipMemcpyHostToDevice, ctx->stream));
+        return SIMPLYP_OK;
+    }
+};
+
+static int fill_nan(const Entry& e, double* ptr, long long n)
+{
+    hipLaunchKernelGGL(simplyp::quantile_fill_nan_kernel, dim3(blocks(n, 256)), dim3(256), 0, e.ctx->stream, ptr, n);
+    return e.launched();
+}
+
+// An entry's device counters, `bytes` at the head of `buf` (grown to `room`): zeroed on the entry's stream.
+static int zeroed_head(const Entry& e, DeviceBuf& buf, size_t room, size_t bytes)
+{
+    simplyp_ctx* const ctx = e.ctx;
+    if (int rc = ensure(ctx, buf, room)) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(buf.ptr, 0, bytes, ctx->stream));
     return SIMPLYP_OK;
-}
-
-static int timed_end(simplyp_ctx* ctx, double* ms, void* dst = nullptr, const void* src = nullptr, size_t bytes = 0)
-{
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
-    if (bytes) HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    float f = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&f, ctx->ev_start, ctx->ev_stop));
-    if (ms) *ms = f;
-    return SIMPLYP_OK;
-}
-
-static int fill_nan(simplyp_ctx* ctx, double* ptr, long long n)
-{
-    hipLaunchKernelGGL(simplyp::quantile_fill_nan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ptr, n);
-    HIP_TRY(ctx, hipGetLastError());
-    return SIMPLYP_OK;
-}
-
-// An entry's `n` device counters (uint32, at the head of `buf`): zeroed before its launch, inside the timed bracket; read
-// back into c[n] with the launch's time afterwards.
-static int counters_begin(simplyp_ctx* ctx, DeviceBuf& buf, int n, unsigned*& counters)
-{
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = ensure(ctx, buf, n * sizeof(unsigned))) return rc;
-    counters = (unsigned*)buf.ptr;
-    HIP_TRY(ctx, hipMemsetAsync(counters, 0, n * sizeof(unsigned), ctx->stream));
-    return timed_begin(ctx);
-}
-
-static int counters_end(simplyp_ctx* ctx, const DeviceBuf& buf, int n, unsigned* c, double* ms)
-{
-    HIP_TRY(ctx, hipGetLastError());
-    return timed_end(ctx, ms, c, buf.ptr, n * sizeof(unsigned));
 }
 
 // The table simplyp_gof, simplyp_gof_spearman and simplyp_waterbody read: its sizes, its output reaches, and the slots among
@@ -1501,34 +1577,32 @@ struct TableView : st::View {
 
 // Checks shared by the table reductions (`ptrs_ok`: the caller's required pointers are set).  waterbody == true: `out` is a
 // table written by simplyp_waterbody, `out_mask` its wb_mask, and the series its summed discharge and fluxes.
-static int check_table(simplyp_ctx* ctx, const char* me, const simplyp_dims* dims, uint32_t out_mask, const int32_t* out_reaches,
+static int check_table(const Entry& e, const simplyp_dims* dims, uint32_t out_mask, const int32_t* out_reaches,
                        int32_t n_out_reaches, bool ptrs_ok, bool waterbody, TableView& t)
 {
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a run is pending on this context; call simplyp_sync first", me);
-    if (!dims || dims->E <= 0 || (!waterbody && dims->S <= 0) || dims->D <= 0) return fail(ctx, SIMPLYP_ERR_ARG, "%s: bad dims", me);
-    if (!ptrs_ok) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a required pointer is NULL", me);
+    if (!dims || dims->E <= 0 || (!waterbody && dims->S <= 0) || dims->D <= 0) return e.refuse("bad dims");
+    if (!ptrs_ok) return e.refuse("a required pointer is NULL");
     simplyp_dims d = *dims;
     if (waterbody) d.S = 1;
-    TABLE_TRY(ctx, st::view(me, d, out_mask, waterbody ? SIMPLYP_WB_MASK_ALL : st::DAILY_COLUMNS, out_reaches, n_out_reaches, t, msg));
+    TABLE_TRY(e.ctx, st::view(e.me, d, out_mask, waterbody ? SIMPLYP_WB_MASK_ALL : st::DAILY_COLUMNS, out_reaches, n_out_reaches, t, msg));
     if (!st::flux_slots(out_mask, waterbody ? st::WB_FLUX_COLS : st::FLUX_COLS, t.col))
-        return fail(ctx, SIMPLYP_ERR_ARG, waterbody ? "%s: wb_mask must contain Q_cumecs, Msus_kg/day, TDP_kg/day and PP_kg/day"
-                                                    : "%s: out_mask must contain Qr, Msus_kg/day, TDP_kg/day and PP_kg/day", me);
+        return e.refuse(waterbody ? "wb_mask must contain Q_cumecs, Msus_kg/day, TDP_kg/day and PP_kg/day"
+                                  : "out_mask must contain Qr, Msus_kg/day, TDP_kg/day and PP_kg/day");
     return SIMPLYP_OK;
 }
 
-static int gof_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+static int gof_impl(const Entry& e, const simplyp_dims* dims, uint32_t out_mask,
                     const int32_t* out_reaches, int32_t n_out_reaches,
                     const double* out, const int32_t* member_of_slot,
                     const double* f_tdp, const double* reach_params,
                     const double* obs, double* gof, simplyp_gof_info* info, bool waterbody = false)
 {
-    const char* me = waterbody ? "simplyp_gof_waterbody" : "simplyp_gof";
+    simplyp_ctx* const ctx = e.ctx;
     TableView t;
     const bool ptrs_ok = out && f_tdp && (waterbody || reach_params) && obs && gof;
-    if (int rc = check_table(ctx, me, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, waterbody, t)) return rc;
+    if (int rc = check_table(e, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, waterbody, t)) return rc;
     const int E = t.E, S = t.S, D = t.D, R = t.R;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (info) *info = {};
 
     // Observation side, shared by all members: counts, conditioning shifts, compact day lists.
     constexpr int NV = SIMPLYP_N_GOF_VARS;
@@ -1584,8 +1658,8 @@ static int gof_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mas
     simplyp::GofArgs g{};
     std::copy(t.col, t.col + 4, g.col);
 
-    const int groups = (E + simplyp::WAVE - 1) / simplyp::WAVE;
-    // Slices per day list.  All waves of a launch take the same time, so what matters is how many rounds the chip needs:
+    const int groups = (int)blocks(E, simplyp::WAVE);
+    // Slices per day list. All waves of a launch take the same time, so what matters is how many rounds the chip needs:
     // pick the slice count with the fewest (rounds / slices), the smallest one within 3 % of the best (every slice costs a
     // row of partial sums), and keep at least 32 days per slice.
     hipDeviceProp_t prop;
@@ -1609,24 +1683,15 @@ static int gof_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mas
     const int n_chunks = std::max(n_chunks_q, n_chunks_c);
 
     // one upload: int32 block then double block
-    std::vector<int32_t> ints;
-    auto put_i = [&](const std::vector<int32_t>& v) { size_t at = ints.size(); ints.insert(ints.end(), v.begin(), v.end()); return at; };
-    const size_t o_reach = put_i(t.reach_of), o_qp = put_i(q_ptr), o_cp = put_i(c_ptr), o_qd = put_i(q_day), o_cd = put_i(c_day);
-    if (ints.size() & 1) ints.push_back(0);
-    std::vector<double> dbl;
-    auto put_d = [&](const std::vector<double>& v) { size_t at = dbl.size(); dbl.insert(dbl.end(), v.begin(), v.end()); return at; };
-    const size_t o_qo = put_d(q_obs), o_co = put_d(c_obs), o_sh = put_d(shift), o_n = put_d(n_obs);
-    const size_t ibytes = ints.size() * sizeof(int32_t), dbytes = dbl.size() * sizeof(double);
-    if (int rc = ensure(ctx, ctx->gof_lists, ibytes + dbytes)) return rc;
+    Staging up;
+    const size_t o_reach = up.put(t.reach_of), o_qp = up.put(q_ptr), o_cp = up.put(c_ptr), o_qd = up.put(q_day), o_cd = up.put(c_day);
+    const size_t o_qo = up.put(q_obs), o_co = up.put(c_obs), o_sh = up.put(shift), o_n = up.put(n_obs);
+    if (int rc = ensure(ctx, ctx->gof_lists, up.bytes())) return rc;
     const size_t pbytes = (size_t)n_chunks * R * (NV * simplyp::GOF_NACC) * E * sizeof(double);
     if (int rc = ensure(ctx, ctx->gof_partial, pbytes)) return rc;
-    char* base = (char*)ctx->gof_lists.ptr;
-    HIP_TRY(ctx, hipMemcpyAsync(base, ints.data(), ibytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(base + ibytes, dbl.data(), dbytes, hipMemcpyHostToDevice, ctx->stream));
-    // the host vectors must outlive the copies: pageable memory is staged before the call returns, and the
-    // stream is synchronised below in any case
-    const int32_t* di = (const int32_t*)base;
-    const double* dd = (const double*)(base + ibytes);
+    if (int rc = up.upload(e, ctx->gof_lists.ptr)) return rc;
+    const int32_t* di = up.d_ints;
+    const double* dd = up.d_dbl;
     g.E = E; g.R = R; g.D = D;
     g.out = out;
     g.col_stride = (long long)D * R * E;
@@ -1640,15 +1705,13 @@ static int gof_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mas
     g.partial = (double*)ctx->gof_partial.ptr;
     g.gof = gof;
 
-    if (int rc = timed_begin(ctx)) return rc;
+    if (int rc = e.begin()) return rc;
     hipLaunchKernelGGL(simplyp::simplyp_gof_partial_kernel<0>, dim3(groups, n_chunks_q, R), dim3(simplyp::WAVE), 0, ctx->stream, g);
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(simplyp::simplyp_gof_partial_kernel<1>, dim3(groups, n_chunks_c, R), dim3(simplyp::WAVE), 0, ctx->stream, g);
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(simplyp::simplyp_gof_finish_kernel, dim3(groups, R, NV), dim3(simplyp::WAVE), 0, ctx->stream, g);
-    HIP_TRY(ctx, hipGetLastError());
-    if (info) memset(info, 0, sizeof(*info));
-    if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr)) return rc;
+    if (int rc = e.end(info ? &info->kernel_ms : nullptr)) return rc;
     if (info) {
         info->n_q_days = (int32_t)q_day.size();
         info->n_chem_days = (int32_t)c_day.size();
@@ -1665,157 +1728,103 @@ int simplyp_gof(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
                 const double* f_tdp, const double* reach_params,
                 const double* obs, double* gof, simplyp_gof_info* info)
 {
-    SIMPLYP_GUARD(ctx, gof_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params, obs, gof, info))
+    return entry(ctx, "simplyp_gof", [&](const Entry& e) {
+        return gof_impl(e, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params, obs, gof, info);
+    });
 }
 
 // Spearman's r per member, variable and output reach (the one column of the reference's table that simplyp_gof leaves out).
-static int spearman_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
-                         const int32_t* out_reaches, int32_t n_out_reaches,
-                         const double* out, const int32_t* member_of_slot,
-                         const double* f_tdp, const double* reach_params,
-                         const double* obs, double* rho, simplyp_gof_info* info)
-{
-    TableView t;
-    const bool ptrs_ok = out && f_tdp && reach_params && obs && rho;
-    if (int rc = check_table(ctx, "simplyp_gof_spearman", dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, false, t)) return rc;
-    const int E = t.E, S = t.S, D = t.D, R = t.R;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    constexpr int NV = SIMPLYP_N_GOF_VARS;
-    {   // variables without (enough) observations stay NaN (visualise_results.py:430, :453)
-        std::vector<double> nanv((size_t)NV * R * E, std::nan(""));
-        HIP_TRY(ctx, hipMemcpyAsync(rho, nanv.data(), nanv.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    simplyp::SpearmanArgs g{};
-    std::copy(t.col, t.col + 4, g.col);
-    g.E = E; g.R = R; g.D = D;
-    g.out = out; g.col_stride = (long long)D * R * E;
-    g.member_of_slot = member_of_slot; g.f_tdp = f_tdp; g.rho = rho;
-    const int groups = (E + simplyp::WAVE - 1) / simplyp::WAVE;
-    double ms_total = 0.0;
-    long long pairs = 0;
-    int n_q = 0, n_c = 0;
-    for (int r = 0; r < R; ++r) {
-        for (int v = 0; v < NV; ++v) {
-            const double* ob = obs + ((size_t)r * NV + v) * D;
-            std::vector<int32_t> day;
-            std::vector<double> val;
-            for (int d = 0; d < D; ++d) if (ob[d] == ob[d]) { day.push_back(d); val.push_back(ob[d]); }
-            const int n = (int)day.size();
-            if (n <= 10) continue;                                                    // :430
-            // average ranks of the observations (ties share the mean of their positions, like pandas' rank())
-            std::vector<int> idx((size_t)n);
-            std::iota(idx.begin(), idx.end(), 0);
-            std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return val[a] < val[b]; });
-            std::vector<double> rk((size_t)n);
-            double sum_ro = 0.0, sum_ro2 = 0.0;
-            for (int i = 0; i < n;) {
-                int j = i;
-                while (j + 1 < n && val[idx[j + 1]] == val[idx[i]]) ++j;
-                const double avg = 0.5 * ((double)(i + 1) + (double)(j + 1));
-                for (int k = i; k <= j; ++k) rk[idx[k]] = avg;
-                i = j + 1;
-            }
-            for (int i = 0; i < n; ++i) { sum_ro += rk[i]; sum_ro2 += rk[i] * rk[i]; }
-            const int n_blocks = (n + simplyp::SP_TI - 1) / simplyp::SP_TI;
-            const size_t list_bytes = ((size_t)n * sizeof(int32_t) + 7) / 8 * 8;
-            if (int rc = ensure(ctx, ctx->gof_lists, list_bytes + (size_t)n * sizeof(double))) return rc;
-            if (int rc = ensure(ctx, ctx->gof_partial, ((size_t)n + (size_t)n_blocks * 3) * E * sizeof(double))) return rc;
-            char* base = (char*)ctx->gof_lists.ptr;
-            HIP_TRY(ctx, hipMemcpyAsync(base, day.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(base + list_bytes, rk.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));        // the host vectors go out of scope at the end of this iteration
-            g.n = n; g.var = v; g.r = r;
-            g.a_catch = reach_params + ((size_t)SIMPLYP_PR_A_CATCH * S + t.reach_of[r]) * E;
-            g.day = (const int32_t*)base; g.rank_obs = (const double*)(base + list_bytes);
-            g.sum_ro = sum_ro; g.sum_ro2 = sum_ro2;
-            g.vals = (double*)ctx->gof_partial.ptr; g.partial = g.vals + (size_t)n * E; g.n_blocks = n_blocks;
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
-            hipLaunchKernelGGL(simplyp::simplyp_spearman_fill_kernel, dim3(groups, (unsigned)std::min(n, 64)), dim3(simplyp::WAVE), 0, ctx->stream, g);
-            HIP_TRY(ctx, hipGetLastError());
-            hipLaunchKernelGGL(simplyp::simplyp_spearman_count_kernel, dim3(groups, (unsigned)n_blocks), dim3(simplyp::WAVE), 0, ctx->stream, g);
-            HIP_TRY(ctx, hipGetLastError());
-            hipLaunchKernelGGL(simplyp::simplyp_spearman_finish_kernel, dim3(groups), dim3(simplyp::WAVE), 0, ctx->stream, g);
-            HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            float ms = 0.f;
-            HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
-            ms_total += ms;
-            pairs += (long long)n * n;
-            if (v == SIMPLYP_GOF_Q) n_q += n; else n_c += n;
-        }
-    }
-    if (info) {
-        memset(info, 0, sizeof(*info));
-        info->kernel_ms = ms_total;
-        info->n_q_days = n_q; info->n_chem_days = n_c;
-        info->bytes_read = pairs / simplyp::SP_TI * 8 * E;       // rows of the compact table streamed past each block of SP_TI values
-    }
-    return SIMPLYP_OK;
-}
-
 int simplyp_gof_spearman(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
                          const int32_t* out_reaches, int32_t n_out_reaches,
                          const double* out, const int32_t* member_of_slot,
                          const double* f_tdp, const double* reach_params,
                          const double* obs, double* rho, simplyp_gof_info* info)
 {
-    SIMPLYP_GUARD(ctx, spearman_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params, obs, rho, info))
+    return entry(ctx, "simplyp_gof_spearman", [&](const Entry& e) -> int {
+        TableView t;
+        const bool ptrs_ok = out && f_tdp && reach_params && obs && rho;
+        if (int rc = check_table(e, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, false, t)) return rc;
+        const int E = t.E, S = t.S, D = t.D, R = t.R;
+        if (info) *info = {};
+        constexpr int NV = SIMPLYP_N_GOF_VARS;
+        {   // variables without (enough) observations stay NaN (visualise_results.py:430, :453)
+            std::vector<double> nanv((size_t)NV * R * E, std::nan(""));
+            HIP_TRY(ctx, hipMemcpyAsync(rho, nanv.data(), nanv.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        simplyp::SpearmanArgs g{};
+        std::copy(t.col, t.col + 4, g.col);
+        g.E = E; g.R = R; g.D = D;
+        g.out = out; g.col_stride = (long long)D * R * E;
+        g.member_of_slot = member_of_slot; g.f_tdp = f_tdp; g.rho = rho;
+        const int groups = (int)blocks(E, simplyp::WAVE);
+        double ms_total = 0.0;
+        long long pairs = 0;
+        int n_q = 0, n_c = 0;
+        for (int r = 0; r < R; ++r) {
+            for (int v = 0; v < NV; ++v) {
+                const double* ob = obs + ((size_t)r * NV + v) * D;
+                std::vector<int32_t> day;
+                std::vector<double> val;
+                for (int d = 0; d < D; ++d) if (ob[d] == ob[d]) { day.push_back(d); val.push_back(ob[d]); }
+                const int n = (int)day.size();
+                if (n <= 10) continue;                                                    // :430
+                // average ranks of the observations (ties share the mean of their positions, like pandas' rank())
+                std::vector<int> idx((size_t)n);
+                std::iota(idx.begin(), idx.end(), 0);
+                std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return val[a] < val[b]; });
+                std::vector<double> rk((size_t)n);
+                double sum_ro = 0.0, sum_ro2 = 0.0;
+                for (int i = 0; i < n;) {
+                    int j = i;
+                    while (j + 1 < n && val[idx[j + 1]] == val[idx[i]]) ++j;
+                    const double avg = 0.5 * ((double)(i + 1) + (double)(j + 1));
+                    for (int k = i; k <= j; ++k) rk[idx[k]] = avg;
+                    i = j + 1;
+                }
+                for (int i = 0; i < n; ++i) { sum_ro += rk[i]; sum_ro2 += rk[i] * rk[i]; }
+                const int n_blocks = (int)blocks(n, simplyp::SP_TI);
+                const size_t list_bytes = ((size_t)n * sizeof(int32_t) + 7) / 8 * 8;
+                if (int rc = ensure(ctx, ctx->gof_lists, list_bytes + (size_t)n * sizeof(double))) return rc;
+                if (int rc = ensure(ctx, ctx->gof_partial, ((size_t)n + (size_t)n_blocks * 3) * E * sizeof(double))) return rc;
+                char* base = (char*)ctx->gof_lists.ptr;
+                HIP_TRY(ctx, hipMemcpyAsync(base, day.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(base + list_bytes, rk.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));        // the host vectors go out of scope at the end of this iteration
+                g.n = n; g.var = v; g.r = r;
+                g.a_catch = reach_params + ((size_t)SIMPLYP_PR_A_CATCH * S + t.reach_of[r]) * E;
+                g.day = (const int32_t*)base; g.rank_obs = (const double*)(base + list_bytes);
+                g.sum_ro = sum_ro; g.sum_ro2 = sum_ro2;
+                g.vals = (double*)ctx->gof_partial.ptr; g.partial = g.vals + (size_t)n * E; g.n_blocks = n_blocks;
+                if (int rc = e.begin()) return rc;
+                hipLaunchKernelGGL(simplyp::simplyp_spearman_fill_kernel, dim3(groups, (unsigned)std::min(n, 64)), dim3(simplyp::WAVE), 0, ctx->stream, g);
+                HIP_TRY(ctx, hipGetLastError());
+                hipLaunchKernelGGL(simplyp::simplyp_spearman_count_kernel, dim3(groups, (unsigned)n_blocks), dim3(simplyp::WAVE), 0, ctx->stream, g);
+                HIP_TRY(ctx, hipGetLastError());
+                hipLaunchKernelGGL(simplyp::simplyp_spearman_finish_kernel, dim3(groups), dim3(simplyp::WAVE), 0, ctx->stream, g);
+                double ms = 0.0;
+                if (int rc = e.end(&ms)) return rc;
+                ms_total += ms;
+                pairs += (long long)n * n;
+                if (v == SIMPLYP_GOF_Q) n_q += n; else n_c += n;
+            }
+        }
+        if (info) {
+            info->kernel_ms = ms_total;
+            info->n_q_days = n_q; info->n_chem_days = n_c;
+            info->bytes_read = pairs / simplyp::SP_TI * 8 * E;       // rows of the compact table streamed past each block of SP_TI values
+        }
+        return SIMPLYP_OK;
+    });
 }
 
 int simplyp_gof_waterbody(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t wb_mask, const double* wb,
                           const int32_t* member_of_slot, const double* f_tdp,
                           const double* obs, double* gof, simplyp_gof_info* info)
 {
-    SIMPLYP_GUARD(ctx, gof_impl(ctx, dims, wb_mask, nullptr, 1, wb, member_of_slot, f_tdp, nullptr, obs, gof, info, true))
-}
-
-static int waterbody_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
-                          const int32_t* out_reaches, int32_t n_out_reaches,
-                          const double* out, const int32_t* member_of_slot,
-                          const double* f_tdp, const double* reach_params,
-                          const int32_t* sum_reaches, int32_t n_sum,
-                          uint32_t wb_mask, double* wb, simplyp_wb_info* info)
-{
-    const char* me = "simplyp_waterbody";
-    TableView t;
-    const bool ptrs_ok = out && f_tdp && reach_params && sum_reaches && wb;
-    if (int rc = check_table(ctx, me, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, false, t)) return rc;
-    const int E = t.E, S = t.S, D = t.D, R = t.R;
-    if ((wb_mask & SIMPLYP_WB_MASK_ALL) == 0u || (wb_mask & ~SIMPLYP_WB_MASK_ALL) != 0u)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: wb_mask must select 1..%d of the waterbody columns", me, (int)SIMPLYP_N_WB);
-    if (n_sum < 1 || n_sum > simplyp::WB_MAX_REACHES)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_sum must be in [1, %d] (got %d)", me, simplyp::WB_MAX_REACHES, n_sum);
-    simplyp::WaterbodyArgs g{};
-    for (int k = 0; k < n_sum; ++k) {
-        const int s = sum_reaches[k];
-        if (s < 0 || s >= S) return fail(ctx, SIMPLYP_ERR_ARG, "%s: sum_reaches[%d] = %d out of range", me, k, s);
-        if (k > 0 && s <= sum_reaches[k - 1]) return fail(ctx, SIMPLYP_ERR_ARG, "%s: sum_reaches must be strictly ascending", me);
-        int pos = -1;
-        for (int r = 0; r < R; ++r) if (t.reach_of[r] == s) pos = r;
-        if (pos < 0) return fail(ctx, SIMPLYP_ERR_ARG, "%s: reach %d is not among the table's output reaches", me, s);
-        g.pos[k] = pos; g.reach[k] = s;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::copy(t.col, t.col + 4, g.col);
-    g.E = E; g.R = R; g.D = D;
-    g.out = out; g.col_stride = (long long)D * R * E;
-    g.n_sum = n_sum;
-    g.member_of_slot = member_of_slot; g.f_tdp = f_tdp;
-    g.a_catch = reach_params + (size_t)SIMPLYP_PR_A_CATCH * S * E;
-    g.wb_mask = wb_mask; g.wb = wb;
-    if (int rc = timed_begin(ctx)) return rc;
-    // two member slots per lane (16-byte accesses) when every row of the tables starts 16-byte aligned
-    const bool vec2 = (E % 2 == 0) && (((uintptr_t)out | (uintptr_t)wb) % 16 == 0);
-    if (vec2) hipLaunchKernelGGL(simplyp::simplyp_waterbody_kernel<2>, dim3((unsigned)((E / 2 + 255) / 256), (unsigned)D), dim3(256), 0, ctx->stream, g);
-    else hipLaunchKernelGGL(simplyp::simplyp_waterbody_kernel<1>, dim3((unsigned)((E + 255) / 256), (unsigned)D), dim3(256), 0, ctx->stream, g);
-    HIP_TRY(ctx, hipGetLastError());
-    if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr)) return rc;
-    if (info) {
-        info->bytes_moved = (int64_t)E * D * (32LL * n_sum + 8LL * popcount32(wb_mask));
-    }
-    return SIMPLYP_OK;
+    return entry(ctx, "simplyp_gof_waterbody", [&](const Entry& e) {
+        return gof_impl(e, dims, wb_mask, nullptr, 1, wb, member_of_slot, f_tdp, nullptr, obs, gof, info, true);
+    });
 }
 
 int simplyp_waterbody(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
@@ -1825,8 +1834,42 @@ int simplyp_waterbody(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_m
                       const int32_t* sum_reaches, int32_t n_sum,
                       uint32_t wb_mask, double* wb, simplyp_wb_info* info)
 {
-    SIMPLYP_GUARD(ctx, waterbody_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
-                                      sum_reaches, n_sum, wb_mask, wb, info))
+    return entry(ctx, "simplyp_waterbody", [&](const Entry& e) -> int {
+        TableView t;
+        const bool ptrs_ok = out && f_tdp && reach_params && sum_reaches && wb;
+        if (int rc = check_table(e, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, false, t)) return rc;
+        const int E = t.E, S = t.S, D = t.D, R = t.R;
+        if ((wb_mask & SIMPLYP_WB_MASK_ALL) == 0u || (wb_mask & ~SIMPLYP_WB_MASK_ALL) != 0u)
+            return e.refuse("wb_mask must select 1..%d of the waterbody columns", (int)SIMPLYP_N_WB);
+        if (n_sum < 1 || n_sum > simplyp::WB_MAX_REACHES)
+            return e.refuse("n_sum must be in [1, %d] (got %d)", simplyp::WB_MAX_REACHES, n_sum);
+        simplyp::WaterbodyArgs g{};
+        for (int k = 0; k < n_sum; ++k) {
+            const int s = sum_reaches[k];
+            if (s < 0 || s >= S) return e.refuse("sum_reaches[%d] = %d out of range", k, s);
+            if (k > 0 && s <= sum_reaches[k - 1]) return e.refuse("sum_reaches must be strictly ascending");
+            int pos = -1;
+            for (int r = 0; r < R; ++r) if (t.reach_of[r] == s) pos = r;
+            if (pos < 0) return e.refuse("reach %d is not among the table's output reaches", s);
+            g.pos[k] = pos; g.reach[k] = s;
+        }
+        if (info) *info = {};
+        std::copy(t.col, t.col + 4, g.col);
+        g.E = E; g.R = R; g.D = D;
+        g.out = out; g.col_stride = (long long)D * R * E;
+        g.n_sum = n_sum;
+        g.member_of_slot = member_of_slot; g.f_tdp = f_tdp;
+        g.a_catch = reach_params + (size_t)SIMPLYP_PR_A_CATCH * S * E;
+        g.wb_mask = wb_mask; g.wb = wb;
+        if (int rc = e.begin()) return rc;
+        // two member slots per lane (16-byte accesses) when every row of the tables starts 16-byte aligned
+        const bool vec2 = (E % 2 == 0) && (((uintptr_t)out | (uintptr_t)wb) % 16 == 0);
+        if (vec2) hipLaunchKernelGGL(simplyp::simplyp_waterbody_kernel<2>, dim3(blocks(E / 2, 256), (unsigned)D), dim3(256), 0, ctx->stream, g);
+        else hipLaunchKernelGGL(simplyp::simplyp_waterbody_kernel<1>, dim3(blocks(E, 256), (unsigned)D), dim3(256), 0, ctx->stream, g);
+        if (int rc = e.end(info ? &info->kernel_ms : nullptr)) return rc;
+        if (info) info->bytes_moved = (int64_t)E * D * (32LL * n_sum + 8LL * popcount32(wb_mask));
+        return SIMPLYP_OK;
+    });
 }
 
 // What a selection across the members decides once per call, whatever it then selects from: the include mask in the table's
@@ -1856,80 +1899,71 @@ static int quantile_prepare(simplyp_ctx* ctx, int32_t E, const int32_t* member_o
 // members, the radix select for longer ones.
 extern "C++" {
 template <class Args>
-static int select_launch(simplyp_ctx* ctx, const Args& g, const char* me, int sort_max, void (*sort)(Args, int), void (*select)(Args))
+static int select_launch(const Entry& e, const Args& g, int sort_max, void (*sort)(Args, int), void (*select)(Args))
 {
+    simplyp_ctx* const ctx = e.ctx;
     if (g.E <= sort_max) {
         int P = 2;
         while (P < g.E) P <<= 1;
         const long long rows_per_block = sort_max / P;
-        const long long blocks = (g.n_rows + rows_per_block - 1) / rows_per_block;
-        if (blocks > 0x7FFFFFFFLL) return fail(ctx, SIMPLYP_ERR_ARG, "%s: too many rows for one call (%lld)", me, g.n_rows);
-        hipLaunchKernelGGL(sort, dim3((unsigned)blocks), dim3(simplyp::QSORT_THREADS), 0, ctx->stream, g, P);
+        const long long n_blocks = (g.n_rows + rows_per_block - 1) / rows_per_block;
+        if (n_blocks > 0x7FFFFFFFLL) return e.refuse("too many rows for one call (%lld)", g.n_rows);
+        hipLaunchKernelGGL(sort, dim3((unsigned)n_blocks), dim3(simplyp::QSORT_THREADS), 0, ctx->stream, g, P);
     } else {
-        const unsigned blocks = (unsigned)std::min<long long>(g.n_rows, 65536);
-        hipLaunchKernelGGL(select, dim3(blocks), dim3(simplyp::QSEL_THREADS), 0, ctx->stream, g);
+        const unsigned n_blocks = (unsigned)std::min<long long>(g.n_rows, 65536);
+        hipLaunchKernelGGL(select, dim3(n_blocks), dim3(simplyp::QSEL_THREADS), 0, ctx->stream, g);
     }
-    HIP_TRY(ctx, hipGetLastError());
-    return SIMPLYP_OK;
+    return e.launched();
 }
 
-static int select_launch(simplyp_ctx* ctx, const simplyp::QuantileArgs& g, const char* me)
+static int select_launch(const Entry& e, const simplyp::QuantileArgs& g)
 {
-    return select_launch(ctx, g, me, simplyp::QSORT_MAX, simplyp::quantile_sort_kernel, simplyp::quantile_select_kernel);
+    return select_launch(e, g, simplyp::QSORT_MAX, simplyp::quantile_sort_kernel, simplyp::quantile_select_kernel);
 }
 
-static int select_launch(simplyp_ctx* ctx, const simplyp::WQuantileArgs& g, const char* me)
+static int select_launch(const Entry& e, const simplyp::WQuantileArgs& g)
 {
-    return select_launch(ctx, g, me, simplyp::WQSORT_MAX, simplyp::weighted_sort_kernel, simplyp::weighted_select_kernel);
+    return select_launch(e, g, simplyp::WQSORT_MAX, simplyp::weighted_sort_kernel, simplyp::weighted_select_kernel);
 }
 }  // extern "C++"
-
-static int quantiles_impl(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double* table,
-                          const int32_t* member_of_slot, const uint8_t* include,
-                          const double* q, int32_t K, double* order_stats, simplyp_quantile_info* info)
-{
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    if (E < 1 || n_rows < 0)
-        return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_quantiles: E must be >= 1 and n_rows >= 0 (got E = %d, n_rows = %lld)", (int)E, (long long)n_rows);
-    if (!table || !q || !order_stats) return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_quantiles: table, q and order_stats must not be NULL");
-    TABLE_TRY(ctx, st::check_probabilities("simplyp_quantiles", q, K, simplyp::QUANT_MAX_K, msg));
-    if (info) { info->kernel_ms = 0.0; info->bytes_table = n_rows * (int64_t)E * 8; info->n_used = 0; info->n_passes = 0; }
-    if (n_rows == 0) return SIMPLYP_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = timed_begin(ctx)) return rc;
-    simplyp::QuantileArgs g{};
-    int n_used = 0;
-    if (int rc = quantile_prepare(ctx, E, member_of_slot, include, q, K, g, n_used)) return rc;
-    const long long n_out = 2LL * K * n_rows;
-    if (n_used == 0) {
-        if (int rc = fill_nan(ctx, order_stats, n_out)) return rc;
-    } else {
-        g.n_rows = n_rows; g.table = table; g.order_stats = order_stats; g.out_row0 = 0; g.out_stride = n_rows;
-        if (int rc = select_launch(ctx, g, "simplyp_quantiles")) return rc;
-    }
-    int n_passes = 0;
-    if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr, &n_passes, g.n_passes, sizeof(int))) return rc;
-    if (info) {
-        info->n_used = n_used;
-        info->n_passes = n_passes;
-    }
-    return SIMPLYP_OK;
-}
 
 int simplyp_quantiles(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double* table,
                       const int32_t* member_of_slot, const uint8_t* include,
                       const double* q, int32_t K, double* order_stats, simplyp_quantile_info* info)
 {
-    SIMPLYP_GUARD(ctx, quantiles_impl(ctx, E, n_rows, table, member_of_slot, include, q, K, order_stats, info))
+    return entry(ctx, "simplyp_quantiles", [&](const Entry& e) -> int {
+        if (E < 1 || n_rows < 0)
+            return e.refuse("E must be >= 1 and n_rows >= 0 (got E = %d, n_rows = %lld)", (int)E, (long long)n_rows);
+        if (!table || !q || !order_stats) return e.refuse("table, q and order_stats must not be NULL");
+        TABLE_TRY(ctx, st::check_probabilities(e.me, q, K, simplyp::QUANT_MAX_K, msg));
+        if (info) { *info = {}; info->bytes_table = n_rows * (int64_t)E * 8; }
+        if (n_rows == 0) return SIMPLYP_OK;
+        if (int rc = e.begin()) return rc;
+        simplyp::QuantileArgs g{};
+        int n_used = 0;
+        if (int rc = quantile_prepare(ctx, E, member_of_slot, include, q, K, g, n_used)) return rc;
+        const long long n_out = 2LL * K * n_rows;
+        if (n_used == 0) {
+            if (int rc = fill_nan(e, order_stats, n_out)) return rc;
+        } else {
+            g.n_rows = n_rows; g.table = table; g.order_stats = order_stats; g.out_row0 = 0; g.out_stride = n_rows;
+            if (int rc = select_launch(e, g)) return rc;
+        }
+        int n_passes = 0;
+        if (int rc = e.end(info ? &info->kernel_ms : nullptr, &n_passes, g.n_passes, sizeof(int))) return rc;
+        if (info) { info->n_used = n_used; info->n_passes = n_passes; }
+        return SIMPLYP_OK;
+    });
 }
 
 // ---- weighted bands (simplyp_weighted.h states the rule, simplyp_quantile.hip.h selects) --------------------------------------
 // What a weighted selection decides once per call: the weights in the table's column order, their sum, who takes part
 // (context workspace: WqPrepared | [E] uint64) and, from the sum read back, every probability's exact threshold.  Fills g.E,
 // g.w_slot, g.K, g.thr and g.n_passes; thr stays unset when T == 0.  A weight above 2^40 is SIMPLYP_ERR_ARG.
-static int weighted_prepare(simplyp_ctx* ctx, const char* me, int32_t E, const int32_t* member_of_slot, const uint8_t* include,
+static int weighted_prepare(const Entry& e, int32_t E, const int32_t* member_of_slot, const uint8_t* include,
                             const uint64_t* weights, const double* q, int32_t K, simplyp::WQuantileArgs& g, simplyp::WqPrepared& got)
 {
+    simplyp_ctx* const ctx = e.ctx;
     if (int rc = ensure(ctx, ctx->wquant, sizeof(simplyp::WqPrepared) + (size_t)E * sizeof(uint64_t))) return rc;
     simplyp::WqPrepared* d_res = (simplyp::WqPrepared*)ctx->wquant.ptr;
     unsigned long long* d_w = (unsigned long long*)((char*)ctx->wquant.ptr + sizeof(simplyp::WqPrepared));
@@ -1938,35 +1972,9 @@ static int weighted_prepare(simplyp_ctx* ctx, const char* me, int32_t E, const i
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(&got, d_res, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    TABLE_TRY(ctx, simplyp_weighted::check_weights(me, got.n_bad, msg));
+    TABLE_TRY(ctx, simplyp_weighted::check_weights(e.me, got.n_bad, msg));
     g.E = E; g.w_slot = d_w; g.K = K; g.n_passes = &d_res->n_passes;
     for (int k = 0; k < K && got.T > 0; ++k) g.thr[k] = simplyp_weighted::weighted_threshold(q[k], got.T);
-    return SIMPLYP_OK;
-}
-
-static int weighted_quantiles_impl(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double* table,
-                                   const int32_t* member_of_slot, const uint8_t* include, const uint64_t* weights,
-                                   const double* q, int32_t K, double* order_stats, simplyp_wq_info* info)
-{
-    const char* me = "simplyp_weighted_quantiles";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    TABLE_TRY(ctx, simplyp_weighted::check_table(me, E, n_rows, table, weights, q, K, order_stats, msg));
-    if (info) { info->kernel_ms = 0.0; info->bytes_table = n_rows * (int64_t)E * 8; info->T = 0; info->n_used = 0; info->n_passes = 0; }
-    if (n_rows == 0) return SIMPLYP_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = timed_begin(ctx)) return rc;
-    simplyp::WQuantileArgs g{};
-    simplyp::WqPrepared got{};
-    if (int rc = weighted_prepare(ctx, me, E, member_of_slot, include, weights, q, K, g, got)) return rc;
-    if (got.T == 0) {
-        if (int rc = fill_nan(ctx, order_stats, (long long)K * n_rows)) return rc;
-    } else {
-        g.n_rows = n_rows; g.table = table; g.order_stats = order_stats; g.out_row0 = 0; g.out_stride = n_rows;
-        if (int rc = select_launch(ctx, g, me)) return rc;
-    }
-    int n_passes = 0;
-    if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr, &n_passes, g.n_passes, sizeof(int))) return rc;
-    if (info) { info->T = got.T; info->n_used = got.n_used; info->n_passes = n_passes; }
     return SIMPLYP_OK;
 }
 
@@ -1974,101 +1982,25 @@ int simplyp_weighted_quantiles(simplyp_ctx* ctx, int32_t E, int64_t n_rows, cons
                                const int32_t* member_of_slot, const uint8_t* include, const uint64_t* weights,
                                const double* q, int32_t K, double* order_stats, simplyp_wq_info* info)
 {
-    SIMPLYP_GUARD(ctx, weighted_quantiles_impl(ctx, E, n_rows, table, member_of_slot, include, weights, q, K, order_stats, info))
-}
-
-static int time_quantiles_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
-                               const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
-                               const double* f_tdp, const double* reach_params,
-                               const int32_t* series, int32_t n_series, const int32_t* period_of_day, int32_t n_periods,
-                               const double* q, int32_t K, double* order_stats, int32_t* n_days, simplyp_tq_info* info)
-{
-    const char* me = "simplyp_time_quantiles";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a run is pending on this context; call simplyp_sync first", me);
-    if (!dims || dims->E < 1 || dims->S < 1 || dims->D < 0)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: bad dims (E and S must be >= 1, D >= 0)", me);
-    if (!out || !q || !order_stats) return fail(ctx, SIMPLYP_ERR_ARG, "%s: out, q and order_stats must not be NULL", me);
-    TABLE_TRY(ctx, st::check_probabilities(me, q, K, simplyp::TQ_MAX_K, msg));
-    st::View tab;
-    TABLE_TRY(ctx, st::view(me, *dims, out_mask, st::DAILY_COLUMNS, out_reaches, n_out_reaches, tab, msg));
-    const int E = tab.E, S = tab.S, D = tab.D, R = tab.R;
-    st::Series sr;
-    simplyp::TqArgs g{};
-    TABLE_TRY(ctx, st::resolve_series(me, series, n_series, simplyp::TQ_MAX_SERIES, out_mask, R, f_tdp, reach_params, g.series, nullptr, sr, msg));
-    if (n_periods < 0 || (!period_of_day && n_periods > 1) || (period_of_day && n_periods < 1))
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: period_of_day needs n_periods >= 1; without it n_periods is 0 (or 1)", me);
-    const int P = std::max<int>(n_periods, 1);
-    std::vector<int32_t> day_ptr, days;
-    TABLE_TRY(ctx, st::period_days(me, period_of_day, D, P, days, day_ptr, msg));
-    if (n_days) for (int p = 0; p < P; ++p) n_days[p] = day_ptr[p + 1] - day_ptr[p];
-    if (info) { info->kernel_ms = 0.0; info->bytes_read = 0; info->n_sweeps = 0; info->n_periods = P; }
-
-    // ranks per period: k_lo, k_hi of every probability, ascending without repeats (rows padded with their last rank)
-    const int T = 2 * K;
-    std::vector<int32_t> ranks((size_t)P * T, 0);
-    std::vector<uint8_t> rank_of((size_t)P * T, 0);
-    for (int p = 0; p < P; ++p) {
-        const long long n = day_ptr[p + 1] - day_ptr[p];
-        if (n <= 0) continue;
-        long long want[2 * simplyp::TQ_MAX_K];
-        for (int k = 0; k < K; ++k) st::linear_ranks(q[k], n, want[k], want[K + k]);
-        std::vector<long long> u(want, want + T);
-        std::sort(u.begin(), u.end());
-        u.erase(std::unique(u.begin(), u.end()), u.end());
-        for (int t = 0; t < T; ++t) ranks[(size_t)p * T + t] = (int32_t)u[std::min<size_t>(t, u.size() - 1)];
-        for (int k = 0; k < T; ++k)
-            rank_of[(size_t)p * T + k] = (uint8_t)(std::lower_bound(u.begin(), u.end(), want[k]) - u.begin());
-    }
-
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long n_out = 2LL * K * n_series * P * R * E;
-    if (days.empty()) {                                        // no day takes part in any period (D = 0 among them): all NaN
-        if (int rc = fill_nan(ctx, order_stats, n_out)) return rc;
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return entry(ctx, "simplyp_weighted_quantiles", [&](const Entry& e) -> int {
+        TABLE_TRY(ctx, simplyp_weighted::check_table(e.me, E, n_rows, table, weights, q, K, order_stats, msg));
+        if (info) { *info = {}; info->bytes_table = n_rows * (int64_t)E * 8; }
+        if (n_rows == 0) return SIMPLYP_OK;
+        if (int rc = e.begin()) return rc;
+        simplyp::WQuantileArgs g{};
+        simplyp::WqPrepared got{};
+        if (int rc = weighted_prepare(e, E, member_of_slot, include, weights, q, K, g, got)) return rc;
+        if (got.T == 0) {
+            if (int rc = fill_nan(e, order_stats, (long long)K * n_rows)) return rc;
+        } else {
+            g.n_rows = n_rows; g.table = table; g.order_stats = order_stats; g.out_row0 = 0; g.out_stride = n_rows;
+            if (int rc = select_launch(e, g)) return rc;
+        }
+        int n_passes = 0;
+        if (int rc = e.end(info ? &info->kernel_ms : nullptr, &n_passes, g.n_passes, sizeof(int))) return rc;
+        if (info) { info->T = got.T; info->n_used = got.n_used; info->n_passes = n_passes; }
         return SIMPLYP_OK;
-    }
-    // device workspace: 16 bytes of counters, then the int32 lists and the byte map -- O(D K), whatever E and the table's size
-    std::vector<int32_t> ints;
-    ints.insert(ints.end(), days.begin(), days.end());
-    const size_t o_ptr = ints.size();
-    ints.insert(ints.end(), day_ptr.begin(), day_ptr.end());
-    const size_t o_ranks = ints.size();
-    ints.insert(ints.end(), ranks.begin(), ranks.end());
-    const size_t o_reach = ints.size();
-    ints.insert(ints.end(), tab.reach_of.begin(), tab.reach_of.end());
-    const size_t int_bytes = ints.size() * sizeof(int32_t);
-    if (int rc = ensure(ctx, ctx->tquant, 16 + int_bytes + rank_of.size())) return rc;
-    char* base = (char*)ctx->tquant.ptr;
-    int32_t* d_ints = (int32_t*)(base + 16);
-    HIP_TRY(ctx, hipMemsetAsync(base, 0, 16, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_ints, ints.data(), int_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(base + 16 + int_bytes, rank_of.data(), rank_of.size(), hipMemcpyHostToDevice, ctx->stream));
-
-    g.E = E; g.R = R; g.D = D; g.K = K; g.T = T; g.n_series = n_series; g.n_periods = P;
-    g.out = out; g.col_stride = (long long)D * R * E;
-    st::flux_slots(out_mask, st::FLUX_COLS, g.col);
-    g.member_of_slot = member_of_slot;
-    g.f_tdp = f_tdp;
-    g.a_catch = sr.derived ? reach_params + (size_t)SIMPLYP_PR_A_CATCH * S * E : nullptr;
-    g.day = d_ints; g.day_ptr = d_ints + o_ptr; g.ranks = d_ints + o_ranks; g.reach_of = d_ints + o_reach;
-    g.rank_of = (const uint8_t*)(base + 16 + int_bytes);
-    g.order_stats = order_stats;
-    g.rows_read = (unsigned long long*)base;
-    g.n_sweeps = (int*)(base + 8);
-    const dim3 grid((unsigned)((E + 63) / 64), (unsigned)std::min(P, 65535), (unsigned)(n_series * R));
-    if (int rc = timed_begin(ctx)) return rc;
-    // the per-rank state of 8 ranks (K <= 4) leaves room for two workgroups' histograms per CU; 32 ranks for one
-    if (T <= 8) hipLaunchKernelGGL(simplyp::simplyp_time_quantile_kernel<8>, grid, dim3(64), 0, ctx->stream, g);
-    else hipLaunchKernelGGL(simplyp::simplyp_time_quantile_kernel<32>, grid, dim3(64), 0, ctx->stream, g);
-    HIP_TRY(ctx, hipGetLastError());
-    unsigned long long counters[2] = {0ull, 0ull};
-    if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr, counters, base, 16)) return rc;
-    if (info) {
-        info->bytes_read = (int64_t)(counters[0] * 512ull);
-        info->n_sweeps = (int32_t)(counters[1] & 0xFFFFFFFFull);
-    }
-    return SIMPLYP_OK;
+    });
 }
 
 int simplyp_time_quantiles(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
@@ -2077,27 +2009,102 @@ int simplyp_time_quantiles(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t 
                            const int32_t* series, int32_t n_series, const int32_t* period_of_day, int32_t n_periods,
                            const double* q, int32_t K, double* order_stats, int32_t* n_days, simplyp_tq_info* info)
 {
-    SIMPLYP_GUARD(ctx, time_quantiles_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
-                                           series, n_series, period_of_day, n_periods, q, K, order_stats, n_days, info))
+    return entry(ctx, "simplyp_time_quantiles", [&](const Entry& e) -> int {
+        if (!dims || dims->E < 1 || dims->S < 1 || dims->D < 0)
+            return e.refuse("bad dims (E and S must be >= 1, D >= 0)");
+        if (!out || !q || !order_stats) return e.refuse("out, q and order_stats must not be NULL");
+        TABLE_TRY(ctx, st::check_probabilities(e.me, q, K, simplyp::TQ_MAX_K, msg));
+        st::View tab;
+        TABLE_TRY(ctx, st::view(e.me, *dims, out_mask, st::DAILY_COLUMNS, out_reaches, n_out_reaches, tab, msg));
+        const int E = tab.E, S = tab.S, D = tab.D, R = tab.R;
+        st::Series sr;
+        simplyp::TqArgs g{};
+        TABLE_TRY(ctx, st::resolve_series(e.me, series, n_series, simplyp::TQ_MAX_SERIES, out_mask, R, f_tdp, reach_params, g.series, nullptr, sr, msg));
+        if (n_periods < 0 || (!period_of_day && n_periods > 1) || (period_of_day && n_periods < 1))
+            return e.refuse("period_of_day needs n_periods >= 1; without it n_periods is 0 (or 1)");
+        const int P = std::max<int>(n_periods, 1);
+        std::vector<int32_t> day_ptr, days;
+        TABLE_TRY(ctx, st::period_days(e.me, period_of_day, D, P, days, day_ptr, msg));
+        if (n_days) for (int p = 0; p < P; ++p) n_days[p] = day_ptr[p + 1] - day_ptr[p];
+        if (info) { *info = {}; info->n_periods = P; }
+
+        // ranks per period: k_lo, k_hi of every probability, ascending without repeats (rows padded with their last rank)
+        const int T = 2 * K;
+        std::vector<int32_t> ranks((size_t)P * T, 0);
+        std::vector<uint8_t> rank_of((size_t)P * T, 0);
+        for (int p = 0; p < P; ++p) {
+            const long long n = day_ptr[p + 1] - day_ptr[p];
+            if (n <= 0) continue;
+            long long want[2 * simplyp::TQ_MAX_K];
+            for (int k = 0; k < K; ++k) st::linear_ranks(q[k], n, want[k], want[K + k]);
+            std::vector<long long> u(want, want + T);
+            std::sort(u.begin(), u.end());
+            u.erase(std::unique(u.begin(), u.end()), u.end());
+            for (int t = 0; t < T; ++t) ranks[(size_t)p * T + t] = (int32_t)u[std::min<size_t>(t, u.size() - 1)];
+            for (int k = 0; k < T; ++k)
+                rank_of[(size_t)p * T + k] = (uint8_t)(std::lower_bound(u.begin(), u.end(), want[k]) - u.begin());
+        }
+
+        const long long n_out = 2LL * K * n_series * P * R * E;
+        if (days.empty()) {                                        // no day takes part in any period (D = 0 among them): all NaN
+            if (int rc = fill_nan(e, order_stats, n_out)) return rc;
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            return SIMPLYP_OK;
+        }
+        // device workspace: 16 bytes of counters, then the int32 lists and the byte map -- O(D K), whatever E and the table's size
+        Staging up;
+        const size_t o_day = up.put(days), o_ptr = up.put(day_ptr), o_ranks = up.put(ranks), o_reach = up.put(tab.reach_of);
+        const size_t int_bytes = up.bytes();
+        if (int rc = ensure(ctx, ctx->tquant, 16 + int_bytes + rank_of.size())) return rc;
+        char* base = (char*)ctx->tquant.ptr;
+        HIP_TRY(ctx, hipMemsetAsync(base, 0, 16, ctx->stream));
+        if (int rc = up.upload(e, base + 16)) return rc;
+        const int32_t* d_ints = up.d_ints;
+        HIP_TRY(ctx, hipMemcpyAsync(base + 16 + int_bytes, rank_of.data(), rank_of.size(), hipMemcpyHostToDevice, ctx->stream));
+
+        g.E = E; g.R = R; g.D = D; g.K = K; g.T = T; g.n_series = n_series; g.n_periods = P;
+        g.out = out; g.col_stride = (long long)D * R * E;
+        st::flux_slots(out_mask, st::FLUX_COLS, g.col);
+        g.member_of_slot = member_of_slot;
+        g.f_tdp = f_tdp;
+        g.a_catch = sr.derived ? reach_params + (size_t)SIMPLYP_PR_A_CATCH * S * E : nullptr;
+        g.day = d_ints + o_day; g.day_ptr = d_ints + o_ptr; g.ranks = d_ints + o_ranks; g.reach_of = d_ints + o_reach;
+        g.rank_of = (const uint8_t*)(base + 16 + int_bytes);
+        g.order_stats = order_stats;
+        g.rows_read = (unsigned long long*)base;
+        g.n_sweeps = (int*)(base + 8);
+        const dim3 grid(blocks(E, 64), (unsigned)std::min(P, 65535), (unsigned)(n_series * R));
+        if (int rc = e.begin()) return rc;
+        // the per-rank state of 8 ranks (K <= 4) leaves room for two workgroups' histograms per CU; 32 ranks for one
+        if (T <= 8) hipLaunchKernelGGL(simplyp::simplyp_time_quantile_kernel<8>, grid, dim3(64), 0, ctx->stream, g);
+        else hipLaunchKernelGGL(simplyp::simplyp_time_quantile_kernel<32>, grid, dim3(64), 0, ctx->stream, g);
+        unsigned long long counters[2] = {0ull, 0ull};
+        if (int rc = e.end(info ? &info->kernel_ms : nullptr, counters, base, 16)) return rc;
+        if (info) {
+            info->bytes_read = (int64_t)(counters[0] * 512ull);
+            info->n_sweeps = (int32_t)(counters[1] & 0xFFFFFFFFull);
+        }
+        return SIMPLYP_OK;
+    });
 }
 
 // What simplyp_predictive_series and simplyp_predictive_bands share: the checks of the table and the series, and the
 // generation kernel's arguments but for the block of days and its destination.  reach_bytes: the room the device copy of the
 // output reaches takes at the head of ctx->pred.
-static int predictive_setup(simplyp_ctx* ctx, const char* me, const simplyp_dims* dims, uint32_t out_mask,
+static int predictive_setup(const Entry& e, const simplyp_dims* dims, uint32_t out_mask,
                             const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
                             const double* f_tdp, const double* reach_params, const int32_t* series, int32_t n_series,
                             const double* err_m, uint64_t seed, int32_t day0, simplyp::PredArgs& g, st::View& t, st::Series& sr)
 {
-    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a run is pending on this context; call simplyp_sync first", me);
+    simplyp_ctx* const ctx = e.ctx;
     if (!dims || dims->E < 1 || dims->S < 1 || dims->D < 0)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: bad dims (E and S must be >= 1, D >= 0: the table's daily rows)", me);
-    if (!out) return fail(ctx, SIMPLYP_ERR_ARG, "%s: out must not be NULL", me);
+        return e.refuse("bad dims (E and S must be >= 1, D >= 0: the table's daily rows)");
+    if (!out) return e.refuse("out must not be NULL");
     if (day0 < 0 || (long long)day0 + dims->D > 0x7FFFFFFFLL)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: day0 must be >= 0 and day0 + D fit 31 bits (got %d)", me, (int)day0);
-    TABLE_TRY(ctx, st::view(me, *dims, out_mask, st::DAILY_COLUMNS, out_reaches, n_out_reaches, t, msg));
+        return e.refuse("day0 must be >= 0 and day0 + D fit 31 bits (got %d)", (int)day0);
+    TABLE_TRY(ctx, st::view(e.me, *dims, out_mask, st::DAILY_COLUMNS, out_reaches, n_out_reaches, t, msg));
     const int E = t.E, S = t.S, D = t.D, R = t.R;
-    TABLE_TRY(ctx, st::resolve_series(me, series, n_series, simplyp::PRED_MAX_SERIES, out_mask, R, f_tdp, reach_params, g.series, g.series_id, sr, msg));
+    TABLE_TRY(ctx, st::resolve_series(e.me, series, n_series, simplyp::PRED_MAX_SERIES, out_mask, R, f_tdp, reach_params, g.series, g.series_id, sr, msg));
     g.E = E; g.R = R; g.n_series = n_series;
     g.out = out; g.col_stride = (long long)D * R * E;
     st::flux_slots(out_mask, st::FLUX_COLS, g.col);
@@ -2105,7 +2112,7 @@ static int predictive_setup(simplyp_ctx* ctx, const char* me, const simplyp_dims
     g.f_tdp = f_tdp;
     g.a_catch = sr.derived ? reach_params + (size_t)SIMPLYP_PR_A_CATCH * S * E : nullptr;
     g.err_m = err_m;
-    g.key0 = (uint32_t)(seed & 0xFFFFFFFFull); g.key1 = (uint32_t)(seed >> 32);
+    philox_key(seed, g);
     g.day0 = (uint32_t)day0;
     return SIMPLYP_OK;
 }
@@ -2124,44 +2131,37 @@ static int predictive_workspace(simplyp_ctx* ctx, const std::vector<int32_t>& re
 static int predictive_launch(simplyp_ctx* ctx, simplyp::PredArgs& g, int d_lo, int n_days, double* dst)
 {
     g.d_lo = d_lo; g.n_days = n_days; g.dst = dst;
-    const int batches = (n_days + simplyp::PRED_BATCH - 1) / simplyp::PRED_BATCH;
-    const dim3 grid((unsigned)((g.E + simplyp::PRED_THREADS - 1) / simplyp::PRED_THREADS), (unsigned)std::min(batches, 65535),
-                    (unsigned)(g.n_series * g.R));
+    const int batches = (int)blocks(n_days, simplyp::PRED_BATCH);
+    const dim3 grid(blocks(g.E, simplyp::PRED_THREADS), (unsigned)std::min(batches, 65535), (unsigned)(g.n_series * g.R));
     hipLaunchKernelGGL(simplyp::simplyp_predictive_kernel, grid, dim3(simplyp::PRED_THREADS), 0, ctx->stream, g);
     HIP_TRY(ctx, hipGetLastError());
     return SIMPLYP_OK;
 }
 
-static int predictive_series_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
-                                  const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
-                                  const double* f_tdp, const double* reach_params, const int32_t* series, int32_t n_series,
-                                  const double* err_m, uint64_t seed, int32_t day0, int32_t which, double* table)
+int simplyp_predictive_series(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                              const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
+                              const double* f_tdp, const double* reach_params, const int32_t* series, int32_t n_series,
+                              const double* err_m, uint64_t seed, int32_t day0, int32_t which, double* table)
 {
-    const char* me = "simplyp_predictive_series";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    if (which < 0 || which > 1) return fail(ctx, SIMPLYP_ERR_ARG, "%s: which must be 0 (values) or 1 (normals), got %d", me, (int)which);
-    if (which == 1 && !err_m) return fail(ctx, SIMPLYP_ERR_ARG, "%s: which = 1 (the normals) needs err_m", me);
-    if (!table) return fail(ctx, SIMPLYP_ERR_ARG, "%s: table must not be NULL", me);
-    simplyp::PredArgs g{};
-    st::View t;
-    st::Series sr;
-    if (int rc = predictive_setup(ctx, me, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
-                                  series, n_series, err_m, seed, day0, g, t, sr)) return rc;
-    if (dims->D == 0) return SIMPLYP_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = predictive_workspace(ctx, t.reach_of, 0, g)) return rc;
-    g.normals = which;
-    if (int rc = predictive_launch(ctx, g, 0, dims->D, table)) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SIMPLYP_OK;
+    return entry(ctx, "simplyp_predictive_series", [&](const Entry& e) -> int {
+        if (which < 0 || which > 1) return e.refuse("which must be 0 (values) or 1 (normals), got %d", (int)which);
+        if (which == 1 && !err_m) return e.refuse("which = 1 (the normals) needs err_m");
+        if (!table) return e.refuse("table must not be NULL");
+        simplyp::PredArgs g{};
+        st::View t;
+        st::Series sr;
+        if (int rc = predictive_setup(e, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
+                                      series, n_series, err_m, seed, day0, g, t, sr)) return rc;
+        if (dims->D == 0) return SIMPLYP_OK;
+        if (int rc = predictive_workspace(ctx, t.reach_of, 0, g)) return rc;
+        g.normals = which;
+        if (int rc = predictive_launch(ctx, g, 0, dims->D, table)) return rc;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return SIMPLYP_OK;
+    });
 }
 
 namespace {
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
 // What the bands select every chunk with: either selection, prepared once per call.
 struct BandSelection {
     std::variant<simplyp::QuantileArgs, simplyp::WQuantileArgs> args;
@@ -2174,11 +2174,11 @@ struct BandSelection {
         simplyp::SelectArgs& h = head();
         h.table = table; h.n_rows = n_rows; h.out_row0 = out_row0;
     }
-    int launch(simplyp_ctx* ctx, const char* me) { return std::visit([&](auto& a) { return select_launch(ctx, a, me); }, args); }
+    int launch(const Entry& e) { return std::visit([&](auto& a) { return select_launch(e, a); }, args); }
 };
 }  // namespace
 
-static int predictive_bands_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+static int predictive_bands_impl(const Entry& e, const simplyp_dims* dims, uint32_t out_mask,
                                  const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
                                  const uint8_t* include, const double* f_tdp, const double* reach_params,
                                  const int32_t* series, int32_t n_series, const double* err_m, uint64_t seed, int32_t day0,
@@ -2187,22 +2187,21 @@ static int predictive_bands_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uin
 {
     // `weighted`: simplyp_predictive_bands_weighted -- the same generation, chunks and checks; one plane of values selected under
     // `weights` by the weighted selectors, and `winfo` instead of `info`
-    const char* me = weighted ? "simplyp_predictive_bands_weighted" : "simplyp_predictive_bands";
-    if (!ctx) return SIMPLYP_ERR_ARG;
+    simplyp_ctx* const ctx = e.ctx;
     if (weighted) {
-        TABLE_TRY(ctx, simplyp_weighted::check_selection(me, dims ? dims->E : 1, weights, q, K, order_stats, msg));
+        TABLE_TRY(ctx, simplyp_weighted::check_selection(e.me, dims ? dims->E : 1, weights, q, K, order_stats, msg));
     } else {
-        if (!q || !order_stats) return fail(ctx, SIMPLYP_ERR_ARG, "%s: q and order_stats must not be NULL", me);
-        TABLE_TRY(ctx, st::check_probabilities(me, q, K, simplyp::QUANT_MAX_K, msg));
+        if (!q || !order_stats) return e.refuse("q and order_stats must not be NULL");
+        TABLE_TRY(ctx, st::check_probabilities(e.me, q, K, simplyp::QUANT_MAX_K, msg));
     }
     simplyp::PredArgs g{};
     st::View t;
     st::Series sr;
-    if (int rc = predictive_setup(ctx, me, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
+    if (int rc = predictive_setup(e, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
                                   series, n_series, err_m, seed, day0, g, t, sr)) return rc;
     const int E = g.E, R = g.R, D = dims->D;
-    if (info) { info->kernel_ms = 0.0; info->gen_ms = 0.0; info->bytes_read = 0; info->bytes_workspace = 0; info->n_used = 0; info->n_passes = 0; info->n_chunks = 0; }
-    if (winfo) { winfo->kernel_ms = 0.0; winfo->bytes_table = (int64_t)n_series * D * R * E * 8; winfo->T = 0; winfo->n_used = 0; winfo->n_passes = 0; }
+    if (info) *info = {};
+    if (winfo) { *winfo = {}; winfo->bytes_table = (int64_t)n_series * D * R * E * 8; }
     if (D == 0) return SIMPLYP_OK;
     // whole days per chunk: what 256 MiB of generated series hold, or what the environment says
     const size_t day_bytes = (size_t)n_series * R * E * sizeof(double);
@@ -2213,16 +2212,13 @@ static int predictive_bands_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uin
     }
     chunk_days = std::min<long long>(chunk_days, D);
     const int n_chunks = (int)((D + chunk_days - 1) / chunk_days);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    EventPair ev;
-    HIP_TRY(ctx, hipEventCreate(&ev.a));
-    HIP_TRY(ctx, hipEventCreate(&ev.b));
+    const hipEvent_t gen_from = ctx->ev_lap[0], gen_to = ctx->ev_lap[1];
     if (int rc = predictive_workspace(ctx, t.reach_of, (size_t)chunk_days * day_bytes, g)) return rc;
     double* work = (double*)((char*)ctx->pred.ptr + PRED_REACH_BYTES);
-    if (int rc = timed_begin(ctx)) return rc;
+    if (int rc = e.begin()) return rc;
     BandSelection sel;
     if (weighted) {                                                                                   // once per call
-        if (int rc = weighted_prepare(ctx, me, E, member_of_slot, include, weights, q, K, sel.args.emplace<simplyp::WQuantileArgs>(), sel.got)) return rc;
+        if (int rc = weighted_prepare(e, E, member_of_slot, include, weights, q, K, sel.args.emplace<simplyp::WQuantileArgs>(), sel.got)) return rc;
         sel.n_used = sel.got.T > 0 ? sel.got.n_used : 0;
         sel.T = K;
     } else {
@@ -2233,28 +2229,28 @@ static int predictive_bands_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uin
     const long long n_rows_all = (long long)n_series * D * R;
     double gen_ms = 0.0;
     if (n_used == 0) {
-        if (int rc = fill_nan(ctx, order_stats, (long long)sel.T * n_rows_all)) return rc;
+        if (int rc = fill_nan(e, order_stats, (long long)sel.T * n_rows_all)) return rc;
     } else {
         sel.head().order_stats = order_stats; sel.head().out_stride = n_rows_all;
         for (int c = 0; c < n_chunks; ++c) {
             const int d_lo = (int)(c * chunk_days), nd = (int)std::min<long long>(chunk_days, D - d_lo);
-            HIP_TRY(ctx, hipEventRecord(ev.a, ctx->stream));
+            HIP_TRY(ctx, hipEventRecord(gen_from, ctx->stream));
             if (int rc = predictive_launch(ctx, g, d_lo, nd, work)) return rc;
-            HIP_TRY(ctx, hipEventRecord(ev.b, ctx->stream));
+            HIP_TRY(ctx, hipEventRecord(gen_to, ctx->stream));
             for (int i = 0; i < n_series; ++i) {               // a series' rows of the chunk are one run of rows of the result
                 sel.set_rows(work + (size_t)i * nd * R * E, (long long)nd * R, ((long long)i * D + d_lo) * R);
-                if (int rc = sel.launch(ctx, me)) return rc;
+                if (int rc = sel.launch(e)) return rc;
             }
             // the generation's time, read while the chunk's selections run; the next chunk overwrites the workspace after them
-            HIP_TRY(ctx, hipEventSynchronize(ev.b));
+            HIP_TRY(ctx, hipEventSynchronize(gen_to));
             float ms = 0.f;
-            HIP_TRY(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
+            HIP_TRY(ctx, hipEventElapsedTime(&ms, gen_from, gen_to));
             gen_ms += ms;
         }
     }
     int n_passes = 0;
     double kernel_ms = 0.0;
-    if (int rc = timed_end(ctx, &kernel_ms, &n_passes, sel.head().n_passes, sizeof(int))) return rc;
+    if (int rc = e.end(&kernel_ms, &n_passes, sel.head().n_passes, sizeof(int))) return rc;
     if (winfo) { winfo->kernel_ms = kernel_ms; winfo->T = sel.got.T; winfo->n_used = sel.got.n_used; winfo->n_passes = n_passes; }
     if (info) {
         info->kernel_ms = kernel_ms;
@@ -2268,23 +2264,16 @@ static int predictive_bands_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uin
     return SIMPLYP_OK;
 }
 
-int simplyp_predictive_series(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
-                              const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
-                              const double* f_tdp, const double* reach_params, const int32_t* series, int32_t n_series,
-                              const double* err_m, uint64_t seed, int32_t day0, int32_t which, double* table)
-{
-    SIMPLYP_GUARD(ctx, predictive_series_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
-                                              series, n_series, err_m, seed, day0, which, table))
-}
-
 int simplyp_predictive_bands(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
                              const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
                              const uint8_t* include, const double* f_tdp, const double* reach_params,
                              const int32_t* series, int32_t n_series, const double* err_m, uint64_t seed, int32_t day0,
                              const double* q, int32_t K, double* order_stats, simplyp_pred_info* info)
 {
-    SIMPLYP_GUARD(ctx, predictive_bands_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, include, f_tdp,
-                                             reach_params, series, n_series, err_m, seed, day0, q, K, order_stats, info))
+    return entry(ctx, "simplyp_predictive_bands", [&](const Entry& e) {
+        return predictive_bands_impl(e, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, include, f_tdp, reach_params,
+                                     series, n_series, err_m, seed, day0, q, K, order_stats, info);
+    });
 }
 
 int simplyp_predictive_bands_weighted(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
@@ -2293,29 +2282,23 @@ int simplyp_predictive_bands_weighted(simplyp_ctx* ctx, const simplyp_dims* dims
                                       const int32_t* series, int32_t n_series, const double* err_m, uint64_t seed, int32_t day0,
                                       const double* q, int32_t K, const uint64_t* weights, double* order_stats, simplyp_wq_info* info)
 {
-    SIMPLYP_GUARD(ctx, predictive_bands_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, include, f_tdp,
-                                             reach_params, series, n_series, err_m, seed, day0, q, K, order_stats, nullptr, true,
-                                             weights, info))
+    return entry(ctx, "simplyp_predictive_bands_weighted", [&](const Entry& e) {
+        return predictive_bands_impl(e, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, include, f_tdp, reach_params,
+                                     series, n_series, err_m, seed, day0, q, K, order_stats, nullptr, true, weights, info);
+    });
 }
 
 // ---- scores (simplyp_score.h states the rule, simplyp_score.hip.h holds the kernels) ------------------------------------------
-namespace {
-struct ScoreEvents {
-    hipEvent_t a = nullptr, b = nullptr, c = nullptr;
-    ~ScoreEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); if (c) (void)hipEventDestroy(c); }
-};
-}  // namespace
-
 // B's sort of g.n_rows rows into the workspace: the tiles, then the merge passes.  `src`: the buffer that holds the result.
 static int score_sort_launch(simplyp_ctx* ctx, const simplyp::ScoreArgs& g, int& src)
 {
-    const int n_tiles = (g.E + simplyp::SCORE_TILE - 1) / simplyp::SCORE_TILE;
+    const unsigned n_tiles = blocks(g.E, simplyp::SCORE_TILE);
     int P = 2;
     while (P < std::min(g.E, simplyp::SCORE_TILE)) P <<= 1;
-    hipLaunchKernelGGL(simplyp::score_tile_sort_kernel, dim3((unsigned)n_tiles, (unsigned)g.n_rows), dim3(simplyp::SCORE_THREADS), 0, ctx->stream, g, P);
+    hipLaunchKernelGGL(simplyp::score_tile_sort_kernel, dim3(n_tiles, (unsigned)g.n_rows), dim3(simplyp::SCORE_THREADS), 0, ctx->stream, g, P);
     HIP_TRY(ctx, hipGetLastError());
     src = 0;
-    const dim3 grid((unsigned)((g.E + simplyp::SCORE_THREADS - 1) / simplyp::SCORE_THREADS), (unsigned)g.n_rows);
+    const dim3 grid(blocks(g.E, simplyp::SCORE_THREADS), (unsigned)g.n_rows);
     for (long long L = simplyp::SCORE_TILE; L < g.E; L *= 2, src ^= 1) {
         hipLaunchKernelGGL(simplyp::score_merge_kernel, grid, dim3(simplyp::SCORE_THREADS), 0, ctx->stream, g, (int)L, src);
         HIP_TRY(ctx, hipGetLastError());
@@ -2326,11 +2309,12 @@ static int score_sort_launch(simplyp_ctx* ctx, const simplyp::ScoreArgs& g, int&
 // What simplyp_scores and simplyp_predictive_scores share.  `rows`: the scored rows of the result ([n_rows_all] rows), ascending,
 // with their observations `ys`.  table != NULL: row rows[i] of it is scored row i; otherwise `pg` and `rows3` (3 ints per scored
 // row: series index, day, output reach) generate the chunk's rows into the workspace first.
-static int scores_common(simplyp_ctx* ctx, const char* me, int32_t E, const int32_t* member_of_slot, const uint8_t* include,
+static int scores_common(const Entry& e, int32_t E, const int32_t* member_of_slot, const uint8_t* include,
                          const uint64_t* weights, const std::vector<int64_t>& rows, const std::vector<double>& ys, int64_t n_rows_all,
                          const double* table, simplyp::PredArgs* pg, const std::vector<int32_t>& rows3, int64_t loads,
                          double* sums, uint64_t* counts, simplyp_score_info* info)
 {
+    simplyp_ctx* const ctx = e.ctx;
     const int64_t n_scored = (int64_t)rows.size();
     const bool gen = table == nullptr;
     const uint64_t row_bytes = (uint64_t)E * 8ull * (gen ? 5ull : 4ull);
@@ -2338,21 +2322,20 @@ static int scores_common(simplyp_ctx* ctx, const char* me, int32_t E, const int3
     chunk = std::min<int64_t>(chunk, 65535);
     const size_t ones_bytes = ((size_t)E * 8 + 255) & ~(size_t)255;
     const size_t list_bytes = ((size_t)n_scored * (8 + 8 + 8 + 12) + 255) & ~(size_t)255;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (int rc = ensure(ctx, ctx->score, ones_bytes + list_bytes + (n_scored ? (size_t)chunk * row_bytes : 0))) return rc;
     char* base = (char*)ctx->score.ptr;
-    if (int rc = timed_begin(ctx)) return rc;
+    if (int rc = e.begin()) return rc;
     const uint64_t* d_weights = weights;
     if (!weights) {
-        hipLaunchKernelGGL(simplyp::score_ones_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, ctx->stream, (unsigned long long*)base, (int)E);
+        hipLaunchKernelGGL(simplyp::score_ones_kernel, dim3(blocks(E, 256)), dim3(256), 0, ctx->stream, (unsigned long long*)base, (int)E);
         HIP_TRY(ctx, hipGetLastError());
         d_weights = (const uint64_t*)base;
     }
     simplyp::WQuantileArgs wq{};
     simplyp::WqPrepared got{};
-    if (int rc = weighted_prepare(ctx, me, E, member_of_slot, include, d_weights, nullptr, 0, wq, got)) return rc;
+    if (int rc = weighted_prepare(e, E, member_of_slot, include, d_weights, nullptr, 0, wq, got)) return rc;
     // every row starts as "not scored"
-    if (int rc = fill_nan(ctx, sums, 2 * n_rows_all)) return rc;
+    if (int rc = fill_nan(e, sums, 2 * n_rows_all)) return rc;
     HIP_TRY(ctx, hipMemsetAsync(counts, 0, (size_t)(2 * n_rows_all) * sizeof(uint64_t), ctx->stream));
     double gen_ms = 0.0, sort_ms = 0.0;
     int n_chunks = 0;
@@ -2369,17 +2352,14 @@ static int scores_common(simplyp_ctx* ctx, const char* me, int32_t E, const int3
         g.E = E; g.w_slot = wq.w_slot; g.T = got.T;
         g.sums = sums; g.counts = (unsigned long long*)counts; g.out_stride = n_rows_all;
         g.keys[0] = work; g.keys[1] = work + plane; g.wts[0] = work + 2 * plane; g.wts[1] = work + 3 * plane;
-        ScoreEvents ev;
-        HIP_TRY(ctx, hipEventCreate(&ev.a));
-        HIP_TRY(ctx, hipEventCreate(&ev.b));
-        HIP_TRY(ctx, hipEventCreate(&ev.c));
+        const hipEvent_t* ev = ctx->ev_lap;         // a chunk's start, its rows generated, its rows sorted
         for (int64_t r0 = 0; r0 < n_scored; r0 += chunk, ++n_chunks) {
             g.n_rows = (int)std::min<int64_t>(chunk, n_scored - r0);
             g.y = d_y + r0; g.dst = d_dst + r0;
-            HIP_TRY(ctx, hipEventRecord(ev.a, ctx->stream));
+            HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
             if (gen) {
                 pg->dst = (double*)(work + 4 * plane);
-                const dim3 grid((unsigned)((E + simplyp::PRED_THREADS - 1) / simplyp::PRED_THREADS), (unsigned)g.n_rows);
+                const dim3 grid(blocks(E, simplyp::PRED_THREADS), (unsigned)g.n_rows);
                 hipLaunchKernelGGL(simplyp::score_rows_kernel, grid, dim3(simplyp::PRED_THREADS), 0, ctx->stream, *pg,
                                    (const int*)(d_rows3 + 3 * r0), g.n_rows);
                 HIP_TRY(ctx, hipGetLastError());
@@ -2387,25 +2367,25 @@ static int scores_common(simplyp_ctx* ctx, const char* me, int32_t E, const int3
             } else {
                 g.table = table; g.row = d_dst + r0;
             }
-            HIP_TRY(ctx, hipEventRecord(ev.b, ctx->stream));
+            HIP_TRY(ctx, hipEventRecord(ev[1], ctx->stream));
             int src = 0;
             if (int rc = score_sort_launch(ctx, g, src)) return rc;
-            HIP_TRY(ctx, hipEventRecord(ev.c, ctx->stream));
+            HIP_TRY(ctx, hipEventRecord(ev[2], ctx->stream));
             hipLaunchKernelGGL(simplyp::score_gap_kernel, dim3((unsigned)g.n_rows), dim3(simplyp::SCORE_THREADS), 0, ctx->stream, g, src);
             HIP_TRY(ctx, hipGetLastError());
             hipLaunchKernelGGL(simplyp::score_stream_kernel, dim3((unsigned)g.n_rows), dim3(simplyp::SCORE_THREADS), 0, ctx->stream, g);
             HIP_TRY(ctx, hipGetLastError());
             // the chunk's generation and sort times, read while its sums run; the next chunk overwrites the workspace after them
-            HIP_TRY(ctx, hipEventSynchronize(ev.c));
+            HIP_TRY(ctx, hipEventSynchronize(ev[2]));
             float ms = 0.f;
-            HIP_TRY(ctx, hipEventElapsedTime(&ms, ev.a, ev.b));
+            HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
             gen_ms += ms;
-            HIP_TRY(ctx, hipEventElapsedTime(&ms, ev.b, ev.c));
+            HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[1], ev[2]));
             sort_ms += ms;
         }
     }
     double kernel_ms = 0.0;
-    if (int rc = timed_end(ctx, &kernel_ms)) return rc;
+    if (int rc = e.end(&kernel_ms)) return rc;
     if (info) {
         info->kernel_ms = kernel_ms; info->gen_ms = gen_ms; info->sort_ms = sort_ms;
         info->bytes_read = got.T > 0 ? loads * n_scored * (int64_t)E * 8 : 0;
@@ -2417,67 +2397,21 @@ static int scores_common(simplyp_ctx* ctx, const char* me, int32_t E, const int3
     return SIMPLYP_OK;
 }
 
-static void score_info_clear(simplyp_score_info* info)
-{
-    if (info) *info = simplyp_score_info{};
-}
-
-static int scores_impl(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double* table, const int32_t* member_of_slot,
-                       const uint8_t* include, const uint64_t* weights, const double* y, double* sums, uint64_t* counts,
-                       simplyp_score_info* info)
-{
-    const char* me = "simplyp_scores";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    TABLE_TRY(ctx, simplyp_score::check_table(me, E, n_rows, table, y, sums, counts, msg));
-    std::vector<int64_t> rows;
-    TABLE_TRY(ctx, simplyp_score::scored_rows(me, y, n_rows, rows, msg));
-    score_info_clear(info);
-    if (n_rows == 0) return SIMPLYP_OK;
-    std::vector<double> ys(rows.size());
-    for (size_t i = 0; i < rows.size(); ++i) ys[i] = y[rows[i]];
-    return scores_common(ctx, me, E, member_of_slot, include, weights, rows, ys, n_rows, table, nullptr, std::vector<int32_t>(), 1,
-                         sums, counts, info);
-}
-
 int simplyp_scores(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const double* table,
                    const int32_t* member_of_slot, const uint8_t* include, const uint64_t* weights,
                    const double* y, double* sums, uint64_t* counts, simplyp_score_info* info)
 {
-    SIMPLYP_GUARD(ctx, scores_impl(ctx, E, n_rows, table, member_of_slot, include, weights, y, sums, counts, info))
-}
-
-static int predictive_scores_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
-                                  const int32_t* out_reaches, int32_t n_out_reaches, const double* out, const int32_t* member_of_slot,
-                                  const uint8_t* include, const double* f_tdp, const double* reach_params,
-                                  const int32_t* series, int32_t n_series, const double* err_m, uint64_t seed, int32_t day0,
-                                  const uint64_t* weights, const double* obs, double* sums, uint64_t* counts, simplyp_score_info* info)
-{
-    const char* me = "simplyp_predictive_scores";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    TABLE_TRY(ctx, simplyp_score::check_outputs(me, dims ? dims->E : 1, obs, sums, counts, msg));
-    simplyp::PredArgs g{};
-    st::View t;
-    st::Series sr;
-    if (int rc = predictive_setup(ctx, me, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
-                                  series, n_series, err_m, seed, day0, g, t, sr)) return rc;
-    const int R = g.R, D = dims->D;
-    const int64_t n_rows_all = (int64_t)n_series * D * R;
-    std::vector<int64_t> rows;
-    TABLE_TRY(ctx, simplyp_score::scored_rows(me, obs, n_rows_all, rows, msg));
-    score_info_clear(info);
-    if (D == 0) return SIMPLYP_OK;
-    std::vector<double> ys(rows.size());
-    std::vector<int32_t> rows3(3 * rows.size());
-    for (size_t i = 0; i < rows.size(); ++i) {
-        ys[i] = obs[rows[i]];
-        rows3[3 * i] = (int32_t)(rows[i] / ((int64_t)D * R));
-        rows3[3 * i + 1] = (int32_t)((rows[i] / R) % D);
-        rows3[3 * i + 2] = (int32_t)(rows[i] % R);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = predictive_workspace(ctx, t.reach_of, 0, g)) return rc;
-    return scores_common(ctx, me, g.E, member_of_slot, include, weights, rows, ys, n_rows_all, nullptr, &g, rows3, sr.loads,
-                         sums, counts, info);
+    return entry(ctx, "simplyp_scores", [&](const Entry& e) -> int {
+        TABLE_TRY(ctx, simplyp_score::check_table(e.me, E, n_rows, table, y, sums, counts, msg));
+        std::vector<int64_t> rows;
+        TABLE_TRY(ctx, simplyp_score::scored_rows(e.me, y, n_rows, rows, msg));
+        if (info) *info = {};
+        if (n_rows == 0) return SIMPLYP_OK;
+        std::vector<double> ys(rows.size());
+        for (size_t i = 0; i < rows.size(); ++i) ys[i] = y[rows[i]];
+        return scores_common(e, E, member_of_slot, include, weights, rows, ys, n_rows, table, nullptr, std::vector<int32_t>(), 1,
+                             sums, counts, info);
+    });
 }
 
 int simplyp_predictive_scores(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
@@ -2486,8 +2420,31 @@ int simplyp_predictive_scores(simplyp_ctx* ctx, const simplyp_dims* dims, uint32
                               const int32_t* series, int32_t n_series, const double* err_m, uint64_t seed, int32_t day0,
                               const uint64_t* weights, const double* obs, double* sums, uint64_t* counts, simplyp_score_info* info)
 {
-    SIMPLYP_GUARD(ctx, predictive_scores_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, include, f_tdp,
-                                              reach_params, series, n_series, err_m, seed, day0, weights, obs, sums, counts, info))
+    return entry(ctx, "simplyp_predictive_scores", [&](const Entry& e) -> int {
+        TABLE_TRY(ctx, simplyp_score::check_outputs(e.me, dims ? dims->E : 1, obs, sums, counts, msg));
+        simplyp::PredArgs g{};
+        st::View t;
+        st::Series sr;
+        if (int rc = predictive_setup(e, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params,
+                                      series, n_series, err_m, seed, day0, g, t, sr)) return rc;
+        const int R = g.R, D = dims->D;
+        const int64_t n_rows_all = (int64_t)n_series * D * R;
+        std::vector<int64_t> rows;
+        TABLE_TRY(ctx, simplyp_score::scored_rows(e.me, obs, n_rows_all, rows, msg));
+        if (info) *info = {};
+        if (D == 0) return SIMPLYP_OK;
+        std::vector<double> ys(rows.size());
+        std::vector<int32_t> rows3(3 * rows.size());
+        for (size_t i = 0; i < rows.size(); ++i) {
+            ys[i] = obs[rows[i]];
+            rows3[3 * i] = (int32_t)(rows[i] / ((int64_t)D * R));
+            rows3[3 * i + 1] = (int32_t)((rows[i] / R) % D);
+            rows3[3 * i + 2] = (int32_t)(rows[i] % R);
+        }
+        if (int rc = predictive_workspace(ctx, t.reach_of, 0, g)) return rc;
+        return scores_common(e, g.E, member_of_slot, include, weights, rows, ys, n_rows_all, nullptr, &g, rows3, sr.loads,
+                             sums, counts, info);
+    });
 }
 
 // ---- Pareto counts and ranks (simplyp_pareto.h states the rule, simplyp_pareto.hip.h holds the kernels) ------------------------
@@ -2512,210 +2469,151 @@ static void pareto_pairs_launch(simplyp_ctx* ctx, int M, dim3 grid, const unsign
 }
 }  // extern "C++"
 
-static int pareto_impl(simplyp_ctx* ctx, int32_t E, int32_t M, const double* obj, const int32_t* sense, const int32_t* member_of_slot,
-                       const uint8_t* include, int32_t max_fronts, int32_t* dominated_by, int32_t* dominates, int32_t* rank,
-                       simplyp_pareto_info* info)
-{
-    const char* me = "simplyp_pareto";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    TABLE_TRY(ctx, simplyp_pareto_rules::check_args(me, E, M, obj, sense, max_fronts, dominated_by, dominates, rank, msg));
-    if (info) *info = simplyp_pareto_info{};
-    const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const int T = simplyp::PARETO_THREADS;
-    const int n_blocks = (E + T - 1) / T;
-    const size_t ints = pad((size_t)E * sizeof(int));
-    const size_t off_flag = 256, off_sum = off_flag + pad((size_t)E), off_key = off_sum + pad((size_t)n_blocks * sizeof(int));
-    const size_t off_ints = off_key + pad((size_t)M * E * sizeof(unsigned long long));
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = ensure(ctx, ctx->pareto, off_ints + 8 * ints)) return rc;
-    char* base = (char*)ctx->pareto.ptr;
-    int* d_head = (int*)base;                       // [0] n, [4..7] the peeling's two pairs of counters
-    int* d_int[8];                                  // members, dominated_by, dominates, left, rank, front, alive x 2
-    for (int k = 0; k < 8; ++k) d_int[k] = (int*)(base + off_ints + k * ints);
-    simplyp::ParetoPrepArgs g{};
-    g.E = E; g.M = M; g.n_blocks = n_blocks; g.obj = obj; g.member_of_slot = member_of_slot; g.include = include;
-    for (int m = 0; m < M; ++m) g.sense[m] = sense[m];
-    g.flag = (uint8_t*)(base + off_flag); g.block_sum = (int*)(base + off_sum); g.n = d_head;
-    g.key = (unsigned long long*)(base + off_key); g.member_of = d_int[0];
-    if (int rc = timed_begin(ctx)) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(d_head, 0, 256, ctx->stream));
-    const dim3 block(T), grid_E((unsigned)n_blocks);
-    hipLaunchKernelGGL(simplyp::pareto_flag_kernel, grid_E, block, 0, ctx->stream, g);
-    HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(simplyp::pareto_scan_kernel, dim3(1), block, 0, ctx->stream, g);
-    HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(simplyp::pareto_compact_kernel, grid_E, block, 0, ctx->stream, g);
-    HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(simplyp::pareto_fill_kernel, grid_E, block, 0, ctx->stream, (int)E, SIMPLYP_PARETO_EXCLUDED, dominated_by, dominates, rank);
-    HIP_TRY(ctx, hipGetLastError());
-    int n = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&n, d_head, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (n < 0 || n > E) return fail(ctx, SIMPLYP_ERR_DEVICE, "%s: the prepare kernels count %d participants of %d members", me, n, (int)E);
-    int64_t pair_tests = 0;
-    int n_fronts = 0, n_front0 = 0, n_unranked = 0;
-    if (n > 0) {
-        const dim3 grid_n((unsigned)((n + T - 1) / T));
-        const unsigned splits = (unsigned)((n + simplyp::PARETO_JSPLIT - 1) / simplyp::PARETO_JSPLIT);
-        HIP_TRY(ctx, hipMemsetAsync(d_int[1], 0, 2 * ints, ctx->stream));       // both counts
-        const char* how = std::getenv("SIMPLYP_PARETO_JLOAD");                  // "scalar": the j keys from memory, not from LDS
-        if (how && std::strcmp(how, "scalar") == 0)
-            pareto_pairs_launch<1>(ctx, M, dim3(grid_n.x, splits), g.key, E, n, nullptr, n, nullptr, d_int[1], d_int[2]);
-        else
-            pareto_pairs_launch<0>(ctx, M, dim3(grid_n.x, splits), g.key, E, n, nullptr, n, nullptr, d_int[1], d_int[2]);
-        HIP_TRY(ctx, hipGetLastError());
-        pair_tests = (int64_t)n * n;
-        if (rank) {
-            HIP_TRY(ctx, hipMemcpyAsync(d_int[3], d_int[1], (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
-            hipLaunchKernelGGL(simplyp::pareto_fill_kernel, grid_n, block, 0, ctx->stream, n, SIMPLYP_PARETO_UNRANKED, d_int[4], (int*)nullptr, (int*)nullptr);
-            HIP_TRY(ctx, hipGetLastError());
-            simplyp::ParetoPeelArgs p{};
-            p.left = d_int[3]; p.rank = d_int[4]; p.front = d_int[5];
-            int n_alive = n, side = 0;
-            while (n_alive > 0 && (max_fronts == 0 || n_fronts < max_fronts)) {
-                p.n_alive = n_alive; p.front_index = n_fronts; p.alive_out = d_int[6 + side];
-                p.counters = d_head + 4 + 2 * (n_fronts & 1); p.counters_next = d_head + 4 + 2 * ((n_fronts + 1) & 1);
-                hipLaunchKernelGGL(simplyp::pareto_mark_kernel, dim3((unsigned)((n_alive + T - 1) / T)), block, 0, ctx->stream, p);
-                HIP_TRY(ctx, hipGetLastError());
-                int got[2] = {0, 0};                // the front's size, the members that stay: the one word per front the host reads
-                HIP_TRY(ctx, hipMemcpyAsync(got, p.counters, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                if (got[0] <= 0 || got[0] + got[1] != n_alive)       // a finite strict order always has a front
-                    return fail(ctx, SIMPLYP_ERR_DEVICE, "%s: front %d takes %d of %d members and leaves %d", me, n_fronts, got[0], n_alive, got[1]);
-                if (n_fronts == 0) n_front0 = got[0];
-                ++n_fronts;
-                if (got[1] > 0 && (max_fronts == 0 || n_fronts < max_fronts)) {
-                    const dim3 grid((unsigned)((got[1] + T - 1) / T), (unsigned)((got[0] + simplyp::PARETO_JSPLIT - 1) / simplyp::PARETO_JSPLIT));
-                    pareto_pairs_launch<2>(ctx, M, grid, g.key, E, got[1], p.alive_out, got[0], p.front, d_int[3], nullptr);
-                    HIP_TRY(ctx, hipGetLastError());
-                    pair_tests += (int64_t)got[0] * got[1];
-                }
-                p.alive_in = p.alive_out;
-                side ^= 1;
-                n_alive = got[1];
-            }
-            n_unranked = n_alive;
-        }
-        hipLaunchKernelGGL(simplyp::pareto_scatter_kernel, grid_n, block, 0, ctx->stream, n, d_int[0], d_int[1], d_int[2], d_int[4],
-                           dominated_by, dominates, rank);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    double kernel_ms = 0.0;
-    if (int rc = timed_end(ctx, &kernel_ms)) return rc;
-    if (info) {
-        info->kernel_ms = kernel_ms; info->pair_tests = pair_tests; info->n_used = n;
-        info->n_fronts = n_fronts; info->n_front0 = n_front0; info->n_unranked = n_unranked;
-    }
-    return SIMPLYP_OK;
-}
-
 int simplyp_pareto(simplyp_ctx* ctx, int32_t E, int32_t M, const double* obj, const int32_t* sense, const int32_t* member_of_slot,
                    const uint8_t* include, int32_t max_fronts, int32_t* dominated_by, int32_t* dominates, int32_t* rank,
                    simplyp_pareto_info* info)
 {
-    SIMPLYP_GUARD(ctx, pareto_impl(ctx, E, M, obj, sense, member_of_slot, include, max_fronts, dominated_by, dominates, rank, info))
+    return entry(ctx, "simplyp_pareto", [&](const Entry& e) -> int {
+        TABLE_TRY(ctx, simplyp_pareto_rules::check_args(e.me, E, M, obj, sense, max_fronts, dominated_by, dominates, rank, msg));
+        if (info) *info = {};
+        const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const int T = simplyp::PARETO_THREADS;
+        const int n_blocks = (int)blocks(E, T);
+        const size_t ints = pad((size_t)E * sizeof(int));
+        const size_t off_flag = 256, off_sum = off_flag + pad((size_t)E), off_key = off_sum + pad((size_t)n_blocks * sizeof(int));
+        const size_t off_ints = off_key + pad((size_t)M * E * sizeof(unsigned long long));
+        if (int rc = ensure(ctx, ctx->pareto, off_ints + 8 * ints)) return rc;
+        char* base = (char*)ctx->pareto.ptr;
+        int* d_head = (int*)base;                       // [0] n, [4..7] the peeling's two pairs of counters
+        int* d_int[8];                                  // members, dominated_by, dominates, left, rank, front, alive x 2
+        for (int k = 0; k < 8; ++k) d_int[k] = (int*)(base + off_ints + k * ints);
+        simplyp::ParetoPrepArgs g{};
+        g.E = E; g.M = M; g.n_blocks = n_blocks; g.obj = obj; g.member_of_slot = member_of_slot; g.include = include;
+        for (int m = 0; m < M; ++m) g.sense[m] = sense[m];
+        g.flag = (uint8_t*)(base + off_flag); g.block_sum = (int*)(base + off_sum); g.n = d_head;
+        g.key = (unsigned long long*)(base + off_key); g.member_of = d_int[0];
+        if (int rc = e.begin()) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(d_head, 0, 256, ctx->stream));
+        const dim3 block(T), grid_E((unsigned)n_blocks);
+        hipLaunchKernelGGL(simplyp::pareto_flag_kernel, grid_E, block, 0, ctx->stream, g);
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(simplyp::pareto_scan_kernel, dim3(1), block, 0, ctx->stream, g);
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(simplyp::pareto_compact_kernel, grid_E, block, 0, ctx->stream, g);
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(simplyp::pareto_fill_kernel, grid_E, block, 0, ctx->stream, (int)E, SIMPLYP_PARETO_EXCLUDED, dominated_by, dominates, rank);
+        HIP_TRY(ctx, hipGetLastError());
+        int n = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&n, d_head, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (n < 0 || n > E) return fail(ctx, SIMPLYP_ERR_DEVICE, "%s: the prepare kernels count %d participants of %d members", e.me, n, (int)E);
+        int64_t pair_tests = 0;
+        int n_fronts = 0, n_front0 = 0, n_unranked = 0;
+        if (n > 0) {
+            const dim3 grid_n(blocks(n, T));
+            const unsigned splits = blocks(n, simplyp::PARETO_JSPLIT);
+            HIP_TRY(ctx, hipMemsetAsync(d_int[1], 0, 2 * ints, ctx->stream));       // both counts
+            const char* how = std::getenv("SIMPLYP_PARETO_JLOAD");                  // "scalar": the j keys from memory, not from LDS
+            if (how && std::strcmp(how, "scalar") == 0)
+                pareto_pairs_launch<1>(ctx, M, dim3(grid_n.x, splits), g.key, E, n, nullptr, n, nullptr, d_int[1], d_int[2]);
+            else
+                pareto_pairs_launch<0>(ctx, M, dim3(grid_n.x, splits), g.key, E, n, nullptr, n, nullptr, d_int[1], d_int[2]);
+            HIP_TRY(ctx, hipGetLastError());
+            pair_tests = (int64_t)n * n;
+            if (rank) {
+                HIP_TRY(ctx, hipMemcpyAsync(d_int[3], d_int[1], (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
+                hipLaunchKernelGGL(simplyp::pareto_fill_kernel, grid_n, block, 0, ctx->stream, n, SIMPLYP_PARETO_UNRANKED, d_int[4], (int*)nullptr, (int*)nullptr);
+                HIP_TRY(ctx, hipGetLastError());
+                simplyp::ParetoPeelArgs p{};
+                p.left = d_int[3]; p.rank = d_int[4]; p.front = d_int[5];
+                int n_alive = n, side = 0;
+                while (n_alive > 0 && (max_fronts == 0 || n_fronts < max_fronts)) {
+                    p.n_alive = n_alive; p.front_index = n_fronts; p.alive_out = d_int[6 + side];
+                    p.counters = d_head + 4 + 2 * (n_fronts & 1); p.counters_next = d_head + 4 + 2 * ((n_fronts + 1) & 1);
+                    hipLaunchKernelGGL(simplyp::pareto_mark_kernel, dim3(blocks(n_alive, T)), block, 0, ctx->stream, p);
+                    HIP_TRY(ctx, hipGetLastError());
+                    int got[2] = {0, 0};                // the front's size, the members that stay: the one word per front the host reads
+                    HIP_TRY(ctx, hipMemcpyAsync(got, p.counters, sizeof(got), hipMemcpyDeviceToHost, ctx->stream));
+                    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                    if (got[0] <= 0 || got[0] + got[1] != n_alive)       // a finite strict order always has a front
+                        return fail(ctx, SIMPLYP_ERR_DEVICE, "%s: front %d takes %d of %d members and leaves %d", e.me, n_fronts, got[0], n_alive, got[1]);
+                    if (n_fronts == 0) n_front0 = got[0];
+                    ++n_fronts;
+                    if (got[1] > 0 && (max_fronts == 0 || n_fronts < max_fronts)) {
+                        const dim3 grid(blocks(got[1], T), blocks(got[0], simplyp::PARETO_JSPLIT));
+                        pareto_pairs_launch<2>(ctx, M, grid, g.key, E, got[1], p.alive_out, got[0], p.front, d_int[3], nullptr);
+                        HIP_TRY(ctx, hipGetLastError());
+                        pair_tests += (int64_t)got[0] * got[1];
+                    }
+                    p.alive_in = p.alive_out;
+                    side ^= 1;
+                    n_alive = got[1];
+                }
+                n_unranked = n_alive;
+            }
+            hipLaunchKernelGGL(simplyp::pareto_scatter_kernel, grid_n, block, 0, ctx->stream, n, d_int[0], d_int[1], d_int[2], d_int[4],
+                               dominated_by, dominates, rank);
+        }
+        if (int rc = e.end(info ? &info->kernel_ms : nullptr)) return rc;
+        if (info) {
+            info->pair_tests = pair_tests; info->n_used = n;
+            info->n_fronts = n_fronts; info->n_front0 = n_front0; info->n_unranked = n_unranked;
+        }
+        return SIMPLYP_OK;
+    });
 }
 
 // ---- the stretch move (simplyp_mcmc.hip.h) ----------------------------------------------------------------------------------
 // What the three entries check alike; fills the move.
-static int mcmc_move(simplyp_ctx* ctx, const char* me, int32_t W, int32_t n_dim, int32_t half, double a, uint64_t seed, uint32_t t,
+static int mcmc_move(const Entry& e, int32_t W, int32_t n_dim, int32_t half, double a, uint64_t seed, uint32_t t,
                      simplyp::McmcMove& mv)
 {
-    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a run is pending on this context; call simplyp_sync first", me);
     if (n_dim < 1 || n_dim > simplyp::MCMC_MAX_DIM)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_dim must be in [1, %d] (got %d)", me, simplyp::MCMC_MAX_DIM, (int)n_dim);
+        return e.refuse("n_dim must be in [1, %d] (got %d)", simplyp::MCMC_MAX_DIM, (int)n_dim);
     if (W < 2 || (W & 1) || W < 2 * n_dim)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: W must be even and >= 2 n_dim (got W = %d, n_dim = %d)", me, (int)W, (int)n_dim);
-    if (half < 0 || half > 1) return fail(ctx, SIMPLYP_ERR_ARG, "%s: half must be 0 or 1 (got %d)", me, (int)half);
-    if (!(a > 1.0)) return fail(ctx, SIMPLYP_ERR_ARG, "%s: the stretch scale a must be > 1 (got %g)", me, a);
+        return e.refuse("W must be even and >= 2 n_dim (got W = %d, n_dim = %d)", (int)W, (int)n_dim);
+    if (half < 0 || half > 1) return e.refuse("half must be 0 or 1 (got %d)", (int)half);
+    if (!(a > 1.0)) return e.refuse("the stretch scale a must be > 1 (got %g)", a);
     mv.W = W; mv.h = W / 2; mv.n_dim = n_dim; mv.half = half; mv.a = a;
-    mv.key0 = (uint32_t)(seed & 0xFFFFFFFFull); mv.key1 = (uint32_t)(seed >> 32); mv.t = t;
+    philox_key(seed, mv);
+    mv.t = t;
     return SIMPLYP_OK;
 }
 
-static int mcmc_info(simplyp_ctx* ctx, simplyp_mcmc_info* info)
+// What the three entries do alike once their arguments have passed: the cleared info, the four zeroed device counters, the
+// start of the timed bracket; and after their launch its end, with the counters read back into the info.
+static int mcmc_begin(const Entry& e, simplyp_mcmc_info* info, unsigned*& counters)
+{
+    if (info) *info = {};
+    if (int rc = zeroed_head(e, e.ctx->mcmc, 4 * sizeof(unsigned), 4 * sizeof(unsigned))) return rc;
+    counters = (unsigned*)e.ctx->mcmc.ptr;
+    return e.begin();
+}
+
+static int mcmc_end(const Entry& e, simplyp_mcmc_info* info)
 {
     unsigned c[4] = {};
-    if (int rc = counters_end(ctx, ctx->mcmc, 4, c, info ? &info->kernel_ms : nullptr)) return rc;
-    if (info) {
-        info->n_inside = (int32_t)c[0]; info->n_accepted = (int32_t)c[1]; info->n_nan = (int32_t)c[2]; info->reserved = 0;
-    }
+    if (int rc = e.end(info ? &info->kernel_ms : nullptr, c, e.ctx->mcmc.ptr, sizeof(c))) return rc;
+    if (info) { info->n_inside = (int32_t)c[0]; info->n_accepted = (int32_t)c[1]; info->n_nan = (int32_t)c[2]; }
     return SIMPLYP_OK;
-}
-
-static int mcmc_propose_impl(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t half, double a, uint64_t seed, uint32_t t,
-                             const double* lo, const double* hi, const int32_t* target, const double* theta,
-                             double* prop, int32_t* inside, double* member_params, double* f_tdp, simplyp_mcmc_info* info)
-{
-    const char* me = "simplyp_mcmc_propose";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    simplyp::McmcProposeArgs g{};
-    if (int rc = mcmc_move(ctx, me, W, n_dim, half, a, seed, t, g.mv)) return rc;
-    if (!lo || !hi || !target || !theta || !prop || !inside)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: lo, hi, target, theta, prop and inside must not be NULL", me);
-    TABLE_TRY(ctx, st::check_box(me, n_dim, lo, hi, target, member_params, f_tdp, g.lo, g.hi, g.target, msg));
-    g.theta = theta; g.prop = prop; g.inside = inside; g.member_params = member_params; g.f_tdp = f_tdp;
-    if (int rc = counters_begin(ctx, ctx->mcmc, 4, g.counters)) return rc;
-    hipLaunchKernelGGL(simplyp::simplyp_mcmc_propose_kernel, dim3((unsigned)((g.mv.h + simplyp::MCMC_THREADS - 1) / simplyp::MCMC_THREADS)),
-                       dim3(simplyp::MCMC_THREADS), 0, ctx->stream, g);
-    return mcmc_info(ctx, info);
-}
-
-static int mcmc_log_prob_impl(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t n_out_reaches, const double* gof,
-                              const int32_t* status, const int32_t* inside, const int32_t* pair_var, const int32_t* pair_reach,
-                              int32_t n_pairs, const int32_t* m_dim, const double* m_const, const double* prop, double* lp_prop,
-                              simplyp_mcmc_info* info)
-{
-    const char* me = "simplyp_mcmc_log_prob";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    simplyp::McmcMove mv{};
-    if (int rc = mcmc_move(ctx, me, W, n_dim, 0, 2.0, 0, 0, mv)) return rc;
-    if (!gof || !pair_var || !pair_reach || !m_dim || !m_const || !prop || !lp_prop)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: gof, pair_var, pair_reach, m_dim, m_const, prop and lp_prop must not be NULL", me);
-    if (n_out_reaches < 1) return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_out_reaches must be >= 1 (got %d)", me, (int)n_out_reaches);
-    if (n_pairs < 1 || n_pairs > simplyp::MCMC_MAX_PAIRS)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_pairs must be in [1, %d] (got %d)", me, simplyp::MCMC_MAX_PAIRS, (int)n_pairs);
-    simplyp::McmcLogProbArgs g{};
-    for (int p = 0; p < n_pairs; ++p) {
-        if (pair_var[p] < 0 || pair_var[p] >= SIMPLYP_N_GOF_VARS || pair_reach[p] < 0 || pair_reach[p] >= n_out_reaches)
-            return fail(ctx, SIMPLYP_ERR_ARG, "%s: pair %d = (variable %d, output reach %d) is out of range", me, p, (int)pair_var[p], (int)pair_reach[p]);
-        g.pair_var[p] = pair_var[p]; g.pair_reach[p] = pair_reach[p];
-    }
-    for (int v = 0; v < SIMPLYP_N_GOF_VARS; ++v) {
-        if (m_dim[v] < -1 || m_dim[v] >= n_dim)
-            return fail(ctx, SIMPLYP_ERR_ARG, "%s: m_dim[%d] = %d is neither -1 nor a row of prop", me, v, (int)m_dim[v]);
-        g.m_dim[v] = m_dim[v]; g.m_const[v] = m_const[v];
-    }
-    g.h = mv.h; g.R = n_out_reaches; g.n_pairs = n_pairs;
-    g.gof = gof; g.status = status; g.inside = inside; g.prop = prop; g.lp_prop = lp_prop;
-    if (int rc = counters_begin(ctx, ctx->mcmc, 4, g.counters)) return rc;
-    hipLaunchKernelGGL(simplyp::simplyp_mcmc_log_prob_kernel, dim3((unsigned)((g.h + simplyp::MCMC_THREADS - 1) / simplyp::MCMC_THREADS)),
-                       dim3(simplyp::MCMC_THREADS), 0, ctx->stream, g);
-    return mcmc_info(ctx, info);
-}
-
-static int mcmc_accept_impl(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t half, double a, uint64_t seed, uint32_t t,
-                            const double* prop, const int32_t* inside, const double* lp_prop, double* theta, double* lp,
-                            int32_t* n_accept, double* chain_row, simplyp_mcmc_info* info)
-{
-    const char* me = "simplyp_mcmc_accept";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    simplyp::McmcAcceptArgs g{};
-    if (int rc = mcmc_move(ctx, me, W, n_dim, half, a, seed, t, g.mv)) return rc;
-    if (!prop || !inside || !lp_prop || !theta || !lp || !n_accept)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: prop, inside, lp_prop, theta, lp and n_accept must not be NULL", me);
-    g.prop = prop; g.inside = inside; g.lp_prop = lp_prop; g.theta = theta; g.lp = lp; g.n_accept = n_accept; g.chain_row = chain_row;
-    if (int rc = counters_begin(ctx, ctx->mcmc, 4, g.counters)) return rc;
-    hipLaunchKernelGGL(simplyp::simplyp_mcmc_accept_kernel, dim3((unsigned)((g.mv.h + simplyp::MCMC_THREADS - 1) / simplyp::MCMC_THREADS)),
-                       dim3(simplyp::MCMC_THREADS), 0, ctx->stream, g);
-    return mcmc_info(ctx, info);
 }
 
 int simplyp_mcmc_propose(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t half, double a, uint64_t seed, uint32_t t,
                          const double* lo, const double* hi, const int32_t* target, const double* theta,
                          double* prop, int32_t* inside, double* member_params, double* f_tdp, simplyp_mcmc_info* info)
 {
-    SIMPLYP_GUARD(ctx, mcmc_propose_impl(ctx, W, n_dim, half, a, seed, t, lo, hi, target, theta, prop, inside, member_params, f_tdp, info))
+    return entry(ctx, "simplyp_mcmc_propose", [&](const Entry& e) -> int {
+        simplyp::McmcProposeArgs g{};
+        if (int rc = mcmc_move(e, W, n_dim, half, a, seed, t, g.mv)) return rc;
+        if (!lo || !hi || !target || !theta || !prop || !inside)
+            return e.refuse("lo, hi, target, theta, prop and inside must not be NULL");
+        TABLE_TRY(ctx, st::check_box(e.me, n_dim, lo, hi, target, member_params, f_tdp, g.lo, g.hi, g.target, msg));
+        g.theta = theta; g.prop = prop; g.inside = inside; g.member_params = member_params; g.f_tdp = f_tdp;
+        if (int rc = mcmc_begin(e, info, g.counters)) return rc;
+        hipLaunchKernelGGL(simplyp::simplyp_mcmc_propose_kernel, dim3(blocks(g.mv.h, simplyp::MCMC_THREADS)),
+                           dim3(simplyp::MCMC_THREADS), 0, ctx->stream, g);
+        return mcmc_end(e, info);
+    });
 }
 
 int simplyp_mcmc_log_prob(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t n_out_reaches, const double* gof,
@@ -2723,195 +2621,126 @@ int simplyp_mcmc_log_prob(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t n_
                           int32_t n_pairs, const int32_t* m_dim, const double* m_const, const double* prop, double* lp_prop,
                           simplyp_mcmc_info* info)
 {
-    SIMPLYP_GUARD(ctx, mcmc_log_prob_impl(ctx, W, n_dim, n_out_reaches, gof, status, inside, pair_var, pair_reach, n_pairs, m_dim,
-                                          m_const, prop, lp_prop, info))
+    return entry(ctx, "simplyp_mcmc_log_prob", [&](const Entry& e) -> int {
+        simplyp::McmcMove mv{};
+        if (int rc = mcmc_move(e, W, n_dim, 0, 2.0, 0, 0, mv)) return rc;
+        if (!gof || !pair_var || !pair_reach || !m_dim || !m_const || !prop || !lp_prop)
+            return e.refuse("gof, pair_var, pair_reach, m_dim, m_const, prop and lp_prop must not be NULL");
+        if (n_out_reaches < 1) return e.refuse("n_out_reaches must be >= 1 (got %d)", (int)n_out_reaches);
+        simplyp::McmcLogProbArgs g{};
+        TABLE_TRY(ctx, st::check_pairs(e.me, pair_var, pair_reach, n_pairs, simplyp::MCMC_MAX_PAIRS, n_out_reaches, g.pair_var, g.pair_reach, msg));
+        for (int v = 0; v < SIMPLYP_N_GOF_VARS; ++v) {
+            if (m_dim[v] < -1 || m_dim[v] >= n_dim)
+                return e.refuse("m_dim[%d] = %d is neither -1 nor a row of prop", v, (int)m_dim[v]);
+            g.m_dim[v] = m_dim[v]; g.m_const[v] = m_const[v];
+        }
+        g.h = mv.h; g.R = n_out_reaches; g.n_pairs = n_pairs;
+        g.gof = gof; g.status = status; g.inside = inside; g.prop = prop; g.lp_prop = lp_prop;
+        if (int rc = mcmc_begin(e, info, g.counters)) return rc;
+        hipLaunchKernelGGL(simplyp::simplyp_mcmc_log_prob_kernel, dim3(blocks(g.h, simplyp::MCMC_THREADS)),
+                           dim3(simplyp::MCMC_THREADS), 0, ctx->stream, g);
+        return mcmc_end(e, info);
+    });
 }
 
 int simplyp_mcmc_accept(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t half, double a, uint64_t seed, uint32_t t,
                         const double* prop, const int32_t* inside, const double* lp_prop, double* theta, double* lp,
                         int32_t* n_accept, double* chain_row, simplyp_mcmc_info* info)
 {
-    SIMPLYP_GUARD(ctx, mcmc_accept_impl(ctx, W, n_dim, half, a, seed, t, prop, inside, lp_prop, theta, lp, n_accept, chain_row, info))
+    return entry(ctx, "simplyp_mcmc_accept", [&](const Entry& e) -> int {
+        simplyp::McmcAcceptArgs g{};
+        if (int rc = mcmc_move(e, W, n_dim, half, a, seed, t, g.mv)) return rc;
+        if (!prop || !inside || !lp_prop || !theta || !lp || !n_accept)
+            return e.refuse("prop, inside, lp_prop, theta, lp and n_accept must not be NULL");
+        g.prop = prop; g.inside = inside; g.lp_prop = lp_prop; g.theta = theta; g.lp = lp; g.n_accept = n_accept; g.chain_row = chain_row;
+        if (int rc = mcmc_begin(e, info, g.counters)) return rc;
+        hipLaunchKernelGGL(simplyp::simplyp_mcmc_accept_kernel, dim3(blocks(g.mv.h, simplyp::MCMC_THREADS)),
+                           dim3(simplyp::MCMC_THREADS), 0, ctx->stream, g);
+        return mcmc_end(e, info);
+    });
 }
 
 // ---- multi-start Nelder-Mead (simplyp_neldermead.hip.h) ---------------------------------------------------------------------
 // What the two entries check alike.
-static int nm_shape(simplyp_ctx* ctx, const char* me, int32_t S, int32_t n_dim)
+static int nm_shape(const Entry& e, int32_t S, int32_t n_dim)
 {
-    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a run is pending on this context; call simplyp_sync first", me);
     if (n_dim < 1 || n_dim > simplyp::MCMC_MAX_DIM)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_dim must be in [1, %d] (got %d)", me, simplyp::MCMC_MAX_DIM, (int)n_dim);
-    if (S < 1 || S > (1 << 28)) return fail(ctx, SIMPLYP_ERR_ARG, "%s: S must be in [1, 2^28] (got %d)", me, (int)S);
+        return e.refuse("n_dim must be in [1, %d] (got %d)", simplyp::MCMC_MAX_DIM, (int)n_dim);
+    if (S < 1 || S > (1 << 28)) return e.refuse("S must be in [1, 2^28] (got %d)", (int)S);
     return SIMPLYP_OK;
 }
 
-static int nm_info(simplyp_ctx* ctx, simplyp_nm_info* info)
+// As mcmc_begin and mcmc_end, with the eight counters of the simplexes.
+static int nm_begin(const Entry& e, simplyp_nm_info* info, unsigned*& counters)
+{
+    if (info) *info = {};
+    if (int rc = zeroed_head(e, e.ctx->nm, 8 * sizeof(unsigned), 8 * sizeof(unsigned))) return rc;
+    counters = (unsigned*)e.ctx->nm.ptr;
+    return e.begin();
+}
+
+static int nm_end(const Entry& e, simplyp_nm_info* info)
 {
     unsigned c[8] = {};
-    if (int rc = counters_end(ctx, ctx->nm, 8, c, info ? &info->kernel_ms : nullptr)) return rc;
+    if (int rc = e.end(info ? &info->kernel_ms : nullptr, c, e.ctx->nm.ptr, sizeof(c))) return rc;
     if (info) {
         info->n_active = (int32_t)c[0]; info->n_converged = (int32_t)c[1]; info->n_shrinking = (int32_t)c[2];
-        info->n_nonfinite_start = (int32_t)c[3]; info->n_inside = (int32_t)c[4]; info->reserved = 0;
+        info->n_nonfinite_start = (int32_t)c[3]; info->n_inside = (int32_t)c[4];
     }
     return SIMPLYP_OK;
-}
-
-static int nm_propose_impl(simplyp_ctx* ctx, int32_t S, int32_t n_dim, const double* lo, const double* hi, const int32_t* target,
-                           const double* sim, const int32_t* istate, double* prop, int32_t* inside, double* member_params,
-                           double* f_tdp, simplyp_nm_info* info)
-{
-    const char* me = "simplyp_nm_propose";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    if (int rc = nm_shape(ctx, me, S, n_dim)) return rc;
-    if (!lo || !hi || !target || !sim || !istate || !prop || !inside)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: lo, hi, target, sim, istate, prop and inside must not be NULL", me);
-    simplyp::NmProposeArgs g{};
-    TABLE_TRY(ctx, st::check_box(me, n_dim, lo, hi, target, member_params, f_tdp, g.lo, g.hi, g.target, msg));
-    g.S = S; g.n_dim = n_dim;
-    g.sim = sim; g.istate = istate; g.prop = prop; g.inside = inside; g.member_params = member_params; g.f_tdp = f_tdp;
-    if (int rc = counters_begin(ctx, ctx->nm, 8, g.counters)) return rc;
-    hipLaunchKernelGGL(simplyp::simplyp_nm_propose_kernel, dim3((unsigned)((S + simplyp::NM_THREADS - 1) / simplyp::NM_THREADS)),
-                       dim3(simplyp::NM_THREADS), 0, ctx->stream, g);
-    return nm_info(ctx, info);
-}
-
-static int nm_update_impl(simplyp_ctx* ctx, int32_t S, int32_t n_dim, int32_t max_iter, double xatol, double fatol,
-                          const double* prop, const int32_t* inside, const double* lp_prop, double* sim, double* fsim,
-                          int32_t* istate, double* history, int32_t history_rows, simplyp_nm_info* info)
-{
-    const char* me = "simplyp_nm_update";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    if (int rc = nm_shape(ctx, me, S, n_dim)) return rc;
-    if (max_iter < 1) return fail(ctx, SIMPLYP_ERR_ARG, "%s: max_iter must be >= 1 (got %d)", me, (int)max_iter);
-    if (!(xatol >= 0.0) || !(fatol >= 0.0))
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: xatol and fatol must be >= 0 (got %g, %g)", me, xatol, fatol);
-    if (history_rows < 0) return fail(ctx, SIMPLYP_ERR_ARG, "%s: history_rows must be >= 0 (got %d)", me, (int)history_rows);
-    if (!prop || !inside || !lp_prop || !sim || !fsim || !istate)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: prop, inside, lp_prop, sim, fsim and istate must not be NULL", me);
-    simplyp::NmUpdateArgs g{};
-    g.S = S; g.n_dim = n_dim; g.max_iter = max_iter; g.history_rows = history ? history_rows : 0; g.xatol = xatol; g.fatol = fatol;
-    g.prop = prop; g.inside = inside; g.lp_prop = lp_prop; g.sim = sim; g.fsim = fsim; g.istate = istate; g.history = history;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = ensure(ctx, ctx->nm_work, (size_t)(n_dim + 1) * (size_t)(n_dim + 1) * (size_t)S * sizeof(double))) return rc;
-    g.work = (double*)ctx->nm_work.ptr;
-    if (int rc = counters_begin(ctx, ctx->nm, 8, g.counters)) return rc;
-    hipLaunchKernelGGL(simplyp::simplyp_nm_update_kernel, dim3((unsigned)((S + simplyp::NM_THREADS - 1) / simplyp::NM_THREADS)),
-                       dim3(simplyp::NM_THREADS), 0, ctx->stream, g);
-    return nm_info(ctx, info);
 }
 
 int simplyp_nm_propose(simplyp_ctx* ctx, int32_t S, int32_t n_dim, const double* lo, const double* hi, const int32_t* target,
                        const double* sim, const int32_t* istate, double* prop, int32_t* inside, double* member_params,
                        double* f_tdp, simplyp_nm_info* info)
 {
-    SIMPLYP_GUARD(ctx, nm_propose_impl(ctx, S, n_dim, lo, hi, target, sim, istate, prop, inside, member_params, f_tdp, info))
+    return entry(ctx, "simplyp_nm_propose", [&](const Entry& e) -> int {
+        if (int rc = nm_shape(e, S, n_dim)) return rc;
+        if (!lo || !hi || !target || !sim || !istate || !prop || !inside)
+            return e.refuse("lo, hi, target, sim, istate, prop and inside must not be NULL");
+        simplyp::NmProposeArgs g{};
+        TABLE_TRY(ctx, st::check_box(e.me, n_dim, lo, hi, target, member_params, f_tdp, g.lo, g.hi, g.target, msg));
+        g.S = S; g.n_dim = n_dim;
+        g.sim = sim; g.istate = istate; g.prop = prop; g.inside = inside; g.member_params = member_params; g.f_tdp = f_tdp;
+        if (int rc = nm_begin(e, info, g.counters)) return rc;
+        hipLaunchKernelGGL(simplyp::simplyp_nm_propose_kernel, dim3(blocks(S, simplyp::NM_THREADS)),
+                           dim3(simplyp::NM_THREADS), 0, ctx->stream, g);
+        return nm_end(e, info);
+    });
 }
 
 int simplyp_nm_update(simplyp_ctx* ctx, int32_t S, int32_t n_dim, int32_t max_iter, double xatol, double fatol,
                       const double* prop, const int32_t* inside, const double* lp_prop, double* sim, double* fsim,
                       int32_t* istate, double* history, int32_t history_rows, simplyp_nm_info* info)
 {
-    SIMPLYP_GUARD(ctx, nm_update_impl(ctx, S, n_dim, max_iter, xatol, fatol, prop, inside, lp_prop, sim, fsim, istate, history,
-                                      history_rows, info))
+    return entry(ctx, "simplyp_nm_update", [&](const Entry& e) -> int {
+        if (int rc = nm_shape(e, S, n_dim)) return rc;
+        if (max_iter < 1) return e.refuse("max_iter must be >= 1 (got %d)", (int)max_iter);
+        if (!(xatol >= 0.0) || !(fatol >= 0.0))
+            return e.refuse("xatol and fatol must be >= 0 (got %g, %g)", xatol, fatol);
+        if (history_rows < 0) return e.refuse("history_rows must be >= 0 (got %d)", (int)history_rows);
+        if (!prop || !inside || !lp_prop || !sim || !fsim || !istate)
+            return e.refuse("prop, inside, lp_prop, sim, fsim and istate must not be NULL");
+        simplyp::NmUpdateArgs g{};
+        g.S = S; g.n_dim = n_dim; g.max_iter = max_iter; g.history_rows = history ? history_rows : 0; g.xatol = xatol; g.fatol = fatol;
+        g.prop = prop; g.inside = inside; g.lp_prop = lp_prop; g.sim = sim; g.fsim = fsim; g.istate = istate; g.history = history;
+        if (int rc = ensure(ctx, ctx->nm_work, (size_t)(n_dim + 1) * (size_t)(n_dim + 1) * (size_t)S * sizeof(double))) return rc;
+        g.work = (double*)ctx->nm_work.ptr;
+        if (int rc = nm_begin(e, info, g.counters)) return rc;
+        hipLaunchKernelGGL(simplyp::simplyp_nm_update_kernel, dim3(blocks(S, simplyp::NM_THREADS)),
+                           dim3(simplyp::NM_THREADS), 0, ctx->stream, g);
+        return nm_end(e, info);
+    });
 }
 
 // ---- Sobol' indices (simplyp_sobol.hip.h) -----------------------------------------------------------------------------------
 // What the two entries check alike.
-static int sobol_shape(simplyp_ctx* ctx, const char* me, int32_t N, int32_t n_dim)
+static int sobol_shape(const Entry& e, int32_t N, int32_t n_dim)
 {
-    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a run is pending on this context; call simplyp_sync first", me);
     if (N < simplyp::SOBOL_MIN_N || N > simplyp::SOBOL_MAX_N)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: N must be in [%d, %d] (got %d)", me, simplyp::SOBOL_MIN_N, simplyp::SOBOL_MAX_N, (int)N);
+        return e.refuse("N must be in [%d, %d] (got %d)", simplyp::SOBOL_MIN_N, simplyp::SOBOL_MAX_N, (int)N);
     if (n_dim < 1 || n_dim > simplyp::SOBOL_MAX_DIM)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_dim must be in [1, %d] (got %d)", me, simplyp::SOBOL_MAX_DIM, (int)n_dim);
-    return SIMPLYP_OK;
-}
-
-static int sobol_design_impl(simplyp_ctx* ctx, int32_t N, int32_t n_dim, uint64_t seed, const double* lo, const double* hi,
-                             const int32_t* target, const double* unit, double* x, double* member_params, double* f_tdp,
-                             simplyp_sobol_info* info)
-{
-    const char* me = "simplyp_sobol_design";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    if (int rc = sobol_shape(ctx, me, N, n_dim)) return rc;
-    if (!lo || !hi || !target || !x) return fail(ctx, SIMPLYP_ERR_ARG, "%s: lo, hi, target and x must not be NULL", me);
-    simplyp::SobolDesignArgs g{};
-    TABLE_TRY(ctx, st::check_box(me, n_dim, lo, hi, target, member_params, f_tdp, g.lo, g.hi, g.target, msg));
-    g.N = N; g.n_dim = n_dim; g.key0 = (uint32_t)(seed & 0xFFFFFFFFull); g.key1 = (uint32_t)(seed >> 32);
-    g.unit = unit; g.x = x; g.member_params = member_params; g.f_tdp = f_tdp;
-    if (info) *info = simplyp_sobol_info{};
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = timed_begin(ctx)) return rc;
-    const int E = N * (n_dim + 2);
-    hipLaunchKernelGGL(simplyp::simplyp_sobol_design_kernel, dim3((unsigned)((E + simplyp::SOBOL_THREADS - 1) / simplyp::SOBOL_THREADS)),
-                       dim3(simplyp::SOBOL_THREADS), 0, ctx->stream, g);
-    HIP_TRY(ctx, hipGetLastError());
-    return timed_end(ctx, info ? &info->kernel_ms : nullptr);
-}
-
-static int sobol_indices_impl(simplyp_ctx* ctx, int32_t N, int32_t n_dim, int32_t n_rows, const double* table, const int32_t* status,
-                              int32_t n_boot, uint64_t seed, double* sums, int32_t* n_used, double* indices, simplyp_sobol_info* info)
-{
-    const char* me = "simplyp_sobol_indices";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    if (int rc = sobol_shape(ctx, me, N, n_dim)) return rc;
-    if (n_rows < 0) return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_rows must be >= 0 (got %d)", me, (int)n_rows);
-    if (n_boot < 0 || n_boot > simplyp::SOBOL_MAX_BOOT)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_boot must be in [0, %d] (got %d)", me, simplyp::SOBOL_MAX_BOOT, (int)n_boot);
-    if (info) { *info = simplyp_sobol_info{}; info->n_resamples = 1 + n_boot; }
-    if (n_rows == 0) return SIMPLYP_OK;
-    if (!table || !indices) return fail(ctx, SIMPLYP_ERR_ARG, "%s: table and indices must not be NULL", me);
-    const int B = 1 + n_boot, T = 2 * n_dim + 2, tiles = (T + 15) / 16;
-    if ((long long)n_rows * B > (1LL << 31) - 1 - simplyp::SOBOL_THREADS)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_rows (1 + n_boot) must stay below 2^31 (got %d rows, %d resamples)", me, (int)n_rows, B);
-    const int Npad = (N + simplyp::SOBOL_KC - 1) / simplyp::SOBOL_KC * simplyp::SOBOL_KC;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t o_valid = 256, o_mu = o_valid + up((size_t)Npad), o_used = o_mu + up((size_t)n_rows * sizeof(double));
-    const size_t o_counts = o_used + up((size_t)B * sizeof(int32_t));
-    const size_t o_sums = o_counts + up((size_t)B * Npad * sizeof(uint16_t));
-    const size_t total = o_sums + (sums ? 0 : up((size_t)B * n_rows * T * sizeof(double)));
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = ensure(ctx, ctx->sobol, total)) return rc;
-    char* base = (char*)ctx->sobol.ptr;
-    simplyp::SobolArgs g{};
-    g.N = N; g.Npad = Npad; g.n_dim = n_dim; g.n_rows = n_rows; g.B = B;
-    g.key0 = (uint32_t)(seed & 0xFFFFFFFFull); g.key1 = (uint32_t)(seed >> 32);
-    g.table = table; g.status = status;
-    g.n_valid = (int32_t*)base; g.valid = (uint8_t*)(base + o_valid); g.mu = (double*)(base + o_mu);
-    g.n_used = n_used ? n_used : (int32_t*)(base + o_used);
-    g.counts = (uint16_t*)(base + o_counts);
-    g.sums = sums ? sums : (double*)(base + o_sums);
-    g.indices = indices;
-    hipEvent_t ev_contract = nullptr;
-    HIP_TRY(ctx, hipEventCreate(&ev_contract));
-    struct EventGuard { hipEvent_t e; ~EventGuard() { (void)hipEventDestroy(e); } } guard{ev_contract};
-    const dim3 threads(simplyp::SOBOL_THREADS);
-    if (int rc = timed_begin(ctx)) return rc;
-    hipLaunchKernelGGL(simplyp::simplyp_sobol_mean_kernel, dim3((unsigned)n_rows), threads, 0, ctx->stream, g);
-    const size_t lds = std::max<size_t>((size_t)Npad * sizeof(uint16_t), simplyp::SOBOL_THREADS * sizeof(uint32_t));
-    hipLaunchKernelGGL(simplyp::simplyp_sobol_counts_kernel, dim3((unsigned)B), threads, lds, ctx->stream, g);
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_main, ctx->stream));
-    const dim3 grid((unsigned)n_rows, (unsigned)((B + simplyp::SOBOL_RB - 1) / simplyp::SOBOL_RB));
-    if (tiles == 1) hipLaunchKernelGGL(simplyp::simplyp_sobol_contract_kernel<1>, grid, threads, 0, ctx->stream, g);
-    else if (tiles == 2) hipLaunchKernelGGL(simplyp::simplyp_sobol_contract_kernel<2>, grid, threads, 0, ctx->stream, g);
-    else hipLaunchKernelGGL(simplyp::simplyp_sobol_contract_kernel<3>, grid, threads, 0, ctx->stream, g);
-    HIP_TRY(ctx, hipEventRecord(ev_contract, ctx->stream));
-    const long long cells = (long long)n_rows * B;
-    hipLaunchKernelGGL(simplyp::simplyp_sobol_epilogue_kernel, dim3((unsigned)((cells + simplyp::SOBOL_THREADS - 1) / simplyp::SOBOL_THREADS)),
-                       threads, 0, ctx->stream, g);
-    HIP_TRY(ctx, hipGetLastError());
-    int32_t n_valid = 0;
-    if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr, &n_valid, g.n_valid, sizeof(n_valid))) return rc;
-    if (info) {
-        float f = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&f, ctx->ev_start, ctx->ev_main));
-        info->counts_ms = f;
-        HIP_TRY(ctx, hipEventElapsedTime(&f, ctx->ev_main, ev_contract));
-        info->contract_ms = f;
-        info->flops = 2LL * B * n_rows * N * T;
-        info->bytes_workspace = (int64_t)total;
-        info->n_valid = n_valid;
-    }
+        return e.refuse("n_dim must be in [1, %d] (got %d)", simplyp::SOBOL_MAX_DIM, (int)n_dim);
     return SIMPLYP_OK;
 }
 
@@ -2919,13 +2748,82 @@ int simplyp_sobol_design(simplyp_ctx* ctx, int32_t N, int32_t n_dim, uint64_t se
                          const int32_t* target, const double* unit, double* x, double* member_params, double* f_tdp,
                          simplyp_sobol_info* info)
 {
-    SIMPLYP_GUARD(ctx, sobol_design_impl(ctx, N, n_dim, seed, lo, hi, target, unit, x, member_params, f_tdp, info))
+    return entry(ctx, "simplyp_sobol_design", [&](const Entry& e) -> int {
+        if (int rc = sobol_shape(e, N, n_dim)) return rc;
+        if (!lo || !hi || !target || !x) return e.refuse("lo, hi, target and x must not be NULL");
+        simplyp::SobolDesignArgs g{};
+        TABLE_TRY(ctx, st::check_box(e.me, n_dim, lo, hi, target, member_params, f_tdp, g.lo, g.hi, g.target, msg));
+        g.N = N; g.n_dim = n_dim; philox_key(seed, g);
+        g.unit = unit; g.x = x; g.member_params = member_params; g.f_tdp = f_tdp;
+        if (info) *info = {};
+        if (int rc = e.begin()) return rc;
+        const int E = N * (n_dim + 2);
+        hipLaunchKernelGGL(simplyp::simplyp_sobol_design_kernel, dim3(blocks(E, simplyp::SOBOL_THREADS)),
+                           dim3(simplyp::SOBOL_THREADS), 0, ctx->stream, g);
+        return e.end(info ? &info->kernel_ms : nullptr);
+    });
 }
 
 int simplyp_sobol_indices(simplyp_ctx* ctx, int32_t N, int32_t n_dim, int32_t n_rows, const double* table, const int32_t* status,
                           int32_t n_boot, uint64_t seed, double* sums, int32_t* n_used, double* indices, simplyp_sobol_info* info)
 {
-    SIMPLYP_GUARD(ctx, sobol_indices_impl(ctx, N, n_dim, n_rows, table, status, n_boot, seed, sums, n_used, indices, info))
+    return entry(ctx, "simplyp_sobol_indices", [&](const Entry& e) -> int {
+        if (int rc = sobol_shape(e, N, n_dim)) return rc;
+        if (n_rows < 0) return e.refuse("n_rows must be >= 0 (got %d)", (int)n_rows);
+        if (n_boot < 0 || n_boot > simplyp::SOBOL_MAX_BOOT)
+            return e.refuse("n_boot must be in [0, %d] (got %d)", simplyp::SOBOL_MAX_BOOT, (int)n_boot);
+        if (info) { *info = {}; info->n_resamples = 1 + n_boot; }
+        if (n_rows == 0) return SIMPLYP_OK;
+        if (!table || !indices) return e.refuse("table and indices must not be NULL");
+        const int B = 1 + n_boot, T = 2 * n_dim + 2, tiles = (T + 15) / 16;
+        if ((long long)n_rows * B > (1LL << 31) - 1 - simplyp::SOBOL_THREADS)
+            return e.refuse("n_rows (1 + n_boot) must stay below 2^31 (got %d rows, %d resamples)", (int)n_rows, B);
+        const int Npad = (N + simplyp::SOBOL_KC - 1) / simplyp::SOBOL_KC * simplyp::SOBOL_KC;
+        auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+        const size_t o_valid = 256, o_mu = o_valid + up((size_t)Npad), o_used = o_mu + up((size_t)n_rows * sizeof(double));
+        const size_t o_counts = o_used + up((size_t)B * sizeof(int32_t));
+        const size_t o_sums = o_counts + up((size_t)B * Npad * sizeof(uint16_t));
+        const size_t total = o_sums + (sums ? 0 : up((size_t)B * n_rows * T * sizeof(double)));
+        if (int rc = ensure(ctx, ctx->sobol, total)) return rc;
+        char* base = (char*)ctx->sobol.ptr;
+        simplyp::SobolArgs g{};
+        g.N = N; g.Npad = Npad; g.n_dim = n_dim; g.n_rows = n_rows; g.B = B;
+        philox_key(seed, g);
+        g.table = table; g.status = status;
+        g.n_valid = (int32_t*)base; g.valid = (uint8_t*)(base + o_valid); g.mu = (double*)(base + o_mu);
+        g.n_used = n_used ? n_used : (int32_t*)(base + o_used);
+        g.counts = (uint16_t*)(base + o_counts);
+        g.sums = sums ? sums : (double*)(base + o_sums);
+        g.indices = indices;
+        const hipEvent_t ev_contract = ctx->ev_lap[0];
+        const dim3 threads(simplyp::SOBOL_THREADS);
+        if (int rc = e.begin()) return rc;
+        hipLaunchKernelGGL(simplyp::simplyp_sobol_mean_kernel, dim3((unsigned)n_rows), threads, 0, ctx->stream, g);
+        const size_t lds = std::max<size_t>((size_t)Npad * sizeof(uint16_t), simplyp::SOBOL_THREADS * sizeof(uint32_t));
+        hipLaunchKernelGGL(simplyp::simplyp_sobol_counts_kernel, dim3((unsigned)B), threads, lds, ctx->stream, g);
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_main, ctx->stream));
+        const dim3 grid((unsigned)n_rows, blocks(B, simplyp::SOBOL_RB));
+        if (tiles == 1) hipLaunchKernelGGL(simplyp::simplyp_sobol_contract_kernel<1>, grid, threads, 0, ctx->stream, g);
+        else if (tiles == 2) hipLaunchKernelGGL(simplyp::simplyp_sobol_contract_kernel<2>, grid, threads, 0, ctx->stream, g);
+        else hipLaunchKernelGGL(simplyp::simplyp_sobol_contract_kernel<3>, grid, threads, 0, ctx->stream, g);
+        HIP_TRY(ctx, hipEventRecord(ev_contract, ctx->stream));
+        const long long cells = (long long)n_rows * B;
+        hipLaunchKernelGGL(simplyp::simplyp_sobol_epilogue_kernel, dim3(blocks(cells, simplyp::SOBOL_THREADS)),
+                           threads, 0, ctx->stream, g);
+        int32_t n_valid = 0;
+        if (int rc = e.end(info ? &info->kernel_ms : nullptr, &n_valid, g.n_valid, sizeof(n_valid))) return rc;
+        if (info) {
+            float f = 0.f;
+            HIP_TRY(ctx, hipEventElapsedTime(&f, ctx->ev_start, ctx->ev_main));
+            info->counts_ms = f;
+            HIP_TRY(ctx, hipEventElapsedTime(&f, ctx->ev_main, ev_contract));
+            info->contract_ms = f;
+            info->flops = 2LL * B * n_rows * N * T;
+            info->bytes_workspace = (int64_t)total;
+            info->n_valid = n_valid;
+        }
+        return SIMPLYP_OK;
+    });
 }
 
 // ---- the particle filter's steps (simplyp_particle.hip.h) ---------------------------------------------------------------------
@@ -2933,22 +2831,20 @@ constexpr size_t PF_HEAD_BYTES = 256;      // the PfResult at the head of ctx->p
 
 // What the five entries do alike once their arguments have passed: the workspace (`work_bytes` behind the result slot), the
 // zeroed result, the start of the timed bracket.  Nothing is launched before this.
-static int pf_begin(simplyp_ctx* ctx, size_t work_bytes, simplyp::PfResult*& res, char*& work)
+static int pf_open(const Entry& e, simplyp_pf_info* info, size_t work_bytes, simplyp::PfResult*& res, char*& work)
 {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = ensure(ctx, ctx->pf, PF_HEAD_BYTES + work_bytes)) return rc;
-    res = (simplyp::PfResult*)ctx->pf.ptr;
-    work = (char*)ctx->pf.ptr + PF_HEAD_BYTES;
-    HIP_TRY(ctx, hipMemsetAsync(res, 0, sizeof(simplyp::PfResult), ctx->stream));
-    return timed_begin(ctx);
+    if (info) *info = {};
+    if (int rc = zeroed_head(e, e.ctx->pf, PF_HEAD_BYTES + work_bytes, sizeof(simplyp::PfResult))) return rc;
+    res = (simplyp::PfResult*)e.ctx->pf.ptr;
+    work = (char*)e.ctx->pf.ptr + PF_HEAD_BYTES;
+    return e.begin();
 }
 
-static int pf_end(simplyp_ctx* ctx, simplyp_pf_info* info)
+// After the entry's launches: the end of the bracket, with the result read back into the info.
+static int pf_close(const Entry& e, simplyp_pf_info* info)
 {
-    HIP_TRY(ctx, hipGetLastError());
     simplyp::PfResult r{};
-    if (info) *info = simplyp_pf_info{};
-    if (int rc = timed_end(ctx, info ? &info->kernel_ms : nullptr, &r, ctx->pf.ptr, sizeof(r))) return rc;
+    if (int rc = e.end(info ? &info->kernel_ms : nullptr, &r, e.ctx->pf.ptr, sizeof(r))) return rc;
     if (info) {
         info->lw_max = r.lw_max; info->sum_w = r.sum_w; info->sum_w2 = r.sum_w2; info->T = r.T;
         info->n_alive = (int32_t)r.n_alive; info->n_nan = (int32_t)r.n_nan; info->n_unique = (int32_t)r.n_unique;
@@ -2957,155 +2853,11 @@ static int pf_end(simplyp_ctx* ctx, simplyp_pf_info* info)
     return SIMPLYP_OK;
 }
 
-static int pf_shape(simplyp_ctx* ctx, const char* me, int64_t E)
+static int pf_shape(const Entry& e, int64_t E)
 {
-    if (ctx->pending) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a run is pending on this context; call simplyp_sync first", me);
     if (E < 1 || E > simplyp_resample::MAX_E)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: E must be in [1, 2^%d] (got %lld)", me, simplyp_resample::MAX_LOG2_E, (long long)E);
+        return e.refuse("E must be in [1, 2^%d] (got %lld)", simplyp_resample::MAX_LOG2_E, (long long)E);
     return SIMPLYP_OK;
-}
-
-static unsigned pf_blocks(int E) { return (unsigned)((E + simplyp::PF_THREADS - 1) / simplyp::PF_THREADS); }
-
-static int pf_loglik_impl(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask, const int32_t* out_reaches,
-                          int32_t n_out_reaches, const double* out, const int32_t* member_of_slot, const double* f_tdp,
-                          const double* reach_params, const double* obs, const int32_t* pair_var, const int32_t* pair_reach,
-                          int32_t n_pairs, const double* err_m, const int32_t* status, double* lw, double* inc, int32_t accumulate,
-                          simplyp_pf_info* info)
-{
-    const char* me = "simplyp_pf_loglik";
-    TableView t;
-    const bool ptrs_ok = out && f_tdp && reach_params && obs && pair_var && pair_reach && err_m && lw;
-    if (int rc = check_table(ctx, me, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, false, t)) return rc;
-    if (int rc = pf_shape(ctx, me, t.E)) return rc;
-    if (n_pairs < 1 || n_pairs > simplyp::PF_MAX_PAIRS)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_pairs must be in [1, %d] (got %d)", me, simplyp::PF_MAX_PAIRS, (int)n_pairs);
-    const int E = t.E, S = t.S, D = t.D, R = t.R;
-    simplyp::PfLoglikArgs g{};
-    // the observation days of every pair in the window, ascending, and what was observed: shared by all particles
-    std::vector<int32_t> ints(t.reach_of);
-    std::vector<double> vals;
-    const size_t o_day = ints.size();
-    for (int p = 0; p < n_pairs; ++p) {
-        if (pair_var[p] < 0 || pair_var[p] >= SIMPLYP_N_GOF_VARS || pair_reach[p] < 0 || pair_reach[p] >= R)
-            return fail(ctx, SIMPLYP_ERR_ARG, "%s: pair %d = (variable %d, output reach %d) is out of range", me, p, (int)pair_var[p], (int)pair_reach[p]);
-        g.pair_var[p] = pair_var[p]; g.pair_reach[p] = pair_reach[p];
-        const double* ob = obs + ((size_t)pair_reach[p] * SIMPLYP_N_GOF_VARS + pair_var[p]) * D;
-        for (int d = 0; d < D; ++d)
-            if (ob[d] == ob[d]) { ints.push_back(d); vals.push_back(ob[d]); }
-        g.day_ptr[p + 1] = (int)vals.size();
-    }
-    if (ints.size() & 1) ints.push_back(0);
-    const size_t ibytes = ints.size() * sizeof(int32_t), dbytes = vals.size() * sizeof(double);
-    char* work = nullptr;
-    if (int rc = pf_begin(ctx, ibytes + dbytes, g.res, work)) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(work, ints.data(), ibytes, hipMemcpyHostToDevice, ctx->stream));
-    if (dbytes) HIP_TRY(ctx, hipMemcpyAsync(work + ibytes, vals.data(), dbytes, hipMemcpyHostToDevice, ctx->stream));
-    g.E = E; g.R = R; g.n_pairs = n_pairs; g.accumulate = accumulate != 0;
-    g.out = out; g.col_stride = (long long)D * R * E;
-    std::copy(t.col, t.col + 4, g.col);
-    g.reach_of = (const int32_t*)work; g.day = (const int32_t*)work + o_day; g.obs = (const double*)(work + ibytes);
-    g.member_of_slot = member_of_slot; g.f_tdp = f_tdp;
-    g.a_catch = reach_params + (size_t)SIMPLYP_PR_A_CATCH * S * E;
-    g.err_m = err_m; g.status = status; g.lw = lw; g.inc = inc;
-    hipLaunchKernelGGL(simplyp::simplyp_pf_loglik_kernel, dim3(pf_blocks(E)), dim3(simplyp::PF_THREADS), 0, ctx->stream, g);
-    return pf_end(ctx, info);          // synchronises: the host lists outlive their copies
-}
-
-static int pf_weights_impl(simplyp_ctx* ctx, int32_t E, const double* lw, double* w, uint64_t* q, simplyp_pf_info* info)
-{
-    const char* me = "simplyp_pf_weights";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    if (int rc = pf_shape(ctx, me, E)) return rc;
-    if (!lw || !w || !q) return fail(ctx, SIMPLYP_ERR_ARG, "%s: lw, w and q must not be NULL", me);
-    simplyp::PfWeightsArgs g{};
-    g.E = E; g.n_blocks = (int)pf_blocks(E);
-    g.lw = lw; g.w = w; g.q = (unsigned long long*)q;
-    char* work = nullptr;
-    if (int rc = pf_begin(ctx, (size_t)3 * g.n_blocks * sizeof(double), g.res, work)) return rc;
-    g.part_max = (double*)work; g.part_sum = (double*)work + g.n_blocks;
-    const dim3 grid((unsigned)g.n_blocks), one(1), threads(simplyp::PF_THREADS);
-    hipLaunchKernelGGL(simplyp::simplyp_pf_max_kernel, grid, threads, 0, ctx->stream, g);
-    hipLaunchKernelGGL(simplyp::simplyp_pf_max_finish_kernel, one, threads, 0, ctx->stream, g);
-    hipLaunchKernelGGL(simplyp::simplyp_pf_weights_kernel, grid, threads, 0, ctx->stream, g);
-    hipLaunchKernelGGL(simplyp::simplyp_pf_sum_finish_kernel, one, threads, 0, ctx->stream, g);
-    return pf_end(ctx, info);
-}
-
-static int pf_resample_impl(simplyp_ctx* ctx, int32_t E, const uint64_t* q, uint64_t seed, uint32_t t, int32_t* ancestors,
-                            int32_t* offspring, simplyp_pf_info* info)
-{
-    const char* me = "simplyp_pf_resample";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    if (int rc = pf_shape(ctx, me, E)) return rc;
-    if (!q || !ancestors) return fail(ctx, SIMPLYP_ERR_ARG, "%s: q and ancestors must not be NULL", me);
-    simplyp::PfResampleArgs g{};
-    g.E = E; g.n_blocks = (int)pf_blocks(E);
-    g.q = (const unsigned long long*)q; g.ancestors = ancestors; g.offspring = offspring;
-    g.key0 = (uint32_t)(seed & 0xFFFFFFFFull); g.key1 = (uint32_t)(seed >> 32); g.t = t;
-    char* work = nullptr;
-    if (int rc = pf_begin(ctx, ((size_t)E + g.n_blocks) * sizeof(uint64_t), g.res, work)) return rc;
-    g.C = (unsigned long long*)work; g.block_sum = g.C + E;
-    if (offspring) HIP_TRY(ctx, hipMemsetAsync(offspring, 0, (size_t)E * sizeof(int32_t), ctx->stream));
-    const dim3 grid((unsigned)g.n_blocks), one(1), threads(simplyp::PF_THREADS);
-    hipLaunchKernelGGL(simplyp::simplyp_pf_scan_block_kernel, grid, threads, 0, ctx->stream, g);
-    hipLaunchKernelGGL(simplyp::simplyp_pf_scan_sums_kernel, one, threads, 0, ctx->stream, g);
-    hipLaunchKernelGGL(simplyp::simplyp_pf_scan_add_kernel, grid, threads, 0, ctx->stream, g);
-    hipLaunchKernelGGL(simplyp::simplyp_pf_search_kernel, grid, threads, 0, ctx->stream, g);
-    hipLaunchKernelGGL(simplyp::simplyp_pf_offspring_kernel, grid, threads, 0, ctx->stream, g);
-    return pf_end(ctx, info);
-}
-
-static int gather_members_impl(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const int32_t* ancestors, const void* src, void* dst,
-                               simplyp_pf_info* info)
-{
-    const char* me = "simplyp_gather_members";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    if (int rc = pf_shape(ctx, me, E)) return rc;
-    if (n_rows < 0 || n_rows > (int64_t)0x7FFFFFFF)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_rows must be in [0, 2^31) (got %lld)", me, (long long)n_rows);
-    if (info) *info = simplyp_pf_info{};
-    if (n_rows == 0) return SIMPLYP_OK;
-    if (!ancestors || !src || !dst) return fail(ctx, SIMPLYP_ERR_ARG, "%s: ancestors, src and dst must not be NULL", me);
-    const uintptr_t a = (uintptr_t)src, b = (uintptr_t)dst, bytes = (uintptr_t)n_rows * (uintptr_t)E * 8u;
-    if (a < b + bytes && b < a + bytes) return fail(ctx, SIMPLYP_ERR_ARG, "%s: src and dst overlap (the gather is out of place)", me);
-    simplyp::PfGatherArgs g{};
-    g.E = E; g.n_rows = n_rows; g.ancestors = ancestors;
-    g.src = (const unsigned long long*)src; g.dst = (unsigned long long*)dst;
-    char* work = nullptr;
-    if (int rc = pf_begin(ctx, 0, g.res, work)) return rc;
-    const long long row_blocks = (n_rows + simplyp::PF_GATHER_ROWS - 1) / simplyp::PF_GATHER_ROWS;
-    hipLaunchKernelGGL(simplyp::simplyp_gather_members_kernel, dim3(pf_blocks(E), (unsigned)std::min<long long>(row_blocks, 65535)),
-                       dim3(simplyp::PF_THREADS), 0, ctx->stream, g);
-    return pf_end(ctx, info);
-}
-
-static int pf_jitter_impl(simplyp_ctx* ctx, int32_t E, int32_t n_dim, uint64_t seed, uint32_t t, double a, const double* centre,
-                          const double* scale, const double* lo, const double* hi, const int32_t* target, double* theta,
-                          double* member_params, double* f_tdp, simplyp_pf_info* info)
-{
-    const char* me = "simplyp_pf_jitter";
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    if (int rc = pf_shape(ctx, me, E)) return rc;
-    if (n_dim < 1 || n_dim > simplyp::PF_MAX_DIM)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: n_dim must be in [1, %d] (got %d)", me, simplyp::PF_MAX_DIM, (int)n_dim);
-    if (!centre || !scale || !lo || !hi || !target || !theta)
-        return fail(ctx, SIMPLYP_ERR_ARG, "%s: centre, scale, lo, hi, target and theta must not be NULL", me);
-    if (!std::isfinite(a)) return fail(ctx, SIMPLYP_ERR_ARG, "%s: a must be finite (got %g)", me, a);
-    simplyp::PfJitterArgs g{};
-    TABLE_TRY(ctx, st::check_box(me, n_dim, lo, hi, target, member_params, f_tdp, g.lo, g.hi, g.target, msg));
-    for (int d = 0; d < n_dim; ++d) {
-        if (!std::isfinite(centre[d]) || !(scale[d] >= 0.0) || !std::isfinite(scale[d]))
-            return fail(ctx, SIMPLYP_ERR_ARG, "%s: centre[%d] must be finite and scale[%d] finite and >= 0 (got %g, %g)", me, d, d, centre[d], scale[d]);
-        g.centre[d] = centre[d]; g.scale[d] = scale[d];
-    }
-    g.E = E; g.n_dim = n_dim; g.a = a; g.t = t;
-    g.key0 = (uint32_t)(seed & 0xFFFFFFFFull); g.key1 = (uint32_t)(seed >> 32);
-    g.theta = theta; g.member_params = member_params; g.f_tdp = f_tdp;
-    char* work = nullptr;
-    if (int rc = pf_begin(ctx, 0, g.res, work)) return rc;
-    hipLaunchKernelGGL(simplyp::simplyp_pf_jitter_kernel, dim3(pf_blocks(E)), dim3(simplyp::PF_THREADS), 0, ctx->stream, g);
-    return pf_end(ctx, info);
 }
 
 int simplyp_pf_loglik(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask, const int32_t* out_reaches,
@@ -3114,32 +2866,133 @@ int simplyp_pf_loglik(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_m
                       int32_t n_pairs, const double* err_m, const int32_t* status, double* lw, double* inc, int32_t accumulate,
                       simplyp_pf_info* info)
 {
-    SIMPLYP_GUARD(ctx, pf_loglik_impl(ctx, dims, out_mask, out_reaches, n_out_reaches, out, member_of_slot, f_tdp, reach_params, obs,
-                                      pair_var, pair_reach, n_pairs, err_m, status, lw, inc, accumulate, info))
+    return entry(ctx, "simplyp_pf_loglik", [&](const Entry& e) -> int {
+        TableView t;
+        const bool ptrs_ok = out && f_tdp && reach_params && obs && pair_var && pair_reach && err_m && lw;
+        if (int rc = check_table(e, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, false, t)) return rc;
+        if (int rc = pf_shape(e, t.E)) return rc;
+        const int E = t.E, S = t.S, D = t.D, R = t.R;
+        simplyp::PfLoglikArgs g{};
+        TABLE_TRY(ctx, st::check_pairs(e.me, pair_var, pair_reach, n_pairs, simplyp::PF_MAX_PAIRS, R, g.pair_var, g.pair_reach, msg));
+        // the observation days of every pair in the window, ascending, and what was observed: shared by all particles
+        Staging up;
+        up.put(t.reach_of);
+        const size_t o_day = up.ints.size();
+        for (int p = 0; p < n_pairs; ++p) {
+            const double* ob = obs + ((size_t)pair_reach[p] * SIMPLYP_N_GOF_VARS + pair_var[p]) * D;
+            for (int d = 0; d < D; ++d)
+                if (ob[d] == ob[d]) { up.ints.push_back(d); up.dbl.push_back(ob[d]); }
+            g.day_ptr[p + 1] = (int)up.dbl.size();
+        }
+        char* work = nullptr;
+        if (int rc = pf_open(e, info, up.bytes(), g.res, work)) return rc;
+        if (int rc = up.upload(e, work)) return rc;
+        g.E = E; g.R = R; g.n_pairs = n_pairs; g.accumulate = accumulate != 0;
+        g.out = out; g.col_stride = (long long)D * R * E;
+        std::copy(t.col, t.col + 4, g.col);
+        g.reach_of = up.d_ints; g.day = up.d_ints + o_day; g.obs = up.d_dbl;
+        g.member_of_slot = member_of_slot; g.f_tdp = f_tdp;
+        g.a_catch = reach_params + (size_t)SIMPLYP_PR_A_CATCH * S * E;
+        g.err_m = err_m; g.status = status; g.lw = lw; g.inc = inc;
+        hipLaunchKernelGGL(simplyp::simplyp_pf_loglik_kernel, dim3(blocks(E, simplyp::PF_THREADS)), dim3(simplyp::PF_THREADS), 0, ctx->stream, g);
+        return pf_close(e, info);          // synchronises: the host lists outlive their copies
+    });
 }
 
 int simplyp_pf_weights(simplyp_ctx* ctx, int32_t E, const double* lw, double* w, uint64_t* q, simplyp_pf_info* info)
 {
-    SIMPLYP_GUARD(ctx, pf_weights_impl(ctx, E, lw, w, q, info))
+    return entry(ctx, "simplyp_pf_weights", [&](const Entry& e) -> int {
+        if (int rc = pf_shape(e, E)) return rc;
+        if (!lw || !w || !q) return e.refuse("lw, w and q must not be NULL");
+        simplyp::PfWeightsArgs g{};
+        g.E = E; g.n_blocks = (int)blocks(E, simplyp::PF_THREADS);
+        g.lw = lw; g.w = w; g.q = (unsigned long long*)q;
+        char* work = nullptr;
+        if (int rc = pf_open(e, info, (size_t)3 * g.n_blocks * sizeof(double), g.res, work)) return rc;
+        g.part_max = (double*)work; g.part_sum = (double*)work + g.n_blocks;
+        const dim3 grid((unsigned)g.n_blocks), one(1), threads(simplyp::PF_THREADS);
+        hipLaunchKernelGGL(simplyp::simplyp_pf_max_kernel, grid, threads, 0, ctx->stream, g);
+        hipLaunchKernelGGL(simplyp::simplyp_pf_max_finish_kernel, one, threads, 0, ctx->stream, g);
+        hipLaunchKernelGGL(simplyp::simplyp_pf_weights_kernel, grid, threads, 0, ctx->stream, g);
+        hipLaunchKernelGGL(simplyp::simplyp_pf_sum_finish_kernel, one, threads, 0, ctx->stream, g);
+        return pf_close(e, info);
+    });
 }
 
 int simplyp_pf_resample(simplyp_ctx* ctx, int32_t E, const uint64_t* q, uint64_t seed, uint32_t t, int32_t* ancestors,
                         int32_t* offspring, simplyp_pf_info* info)
 {
-    SIMPLYP_GUARD(ctx, pf_resample_impl(ctx, E, q, seed, t, ancestors, offspring, info))
+    return entry(ctx, "simplyp_pf_resample", [&](const Entry& e) -> int {
+        if (int rc = pf_shape(e, E)) return rc;
+        if (!q || !ancestors) return e.refuse("q and ancestors must not be NULL");
+        simplyp::PfResampleArgs g{};
+        g.E = E; g.n_blocks = (int)blocks(E, simplyp::PF_THREADS);
+        g.q = (const unsigned long long*)q; g.ancestors = ancestors; g.offspring = offspring;
+        philox_key(seed, g); g.t = t;
+        char* work = nullptr;
+        if (int rc = pf_open(e, info, ((size_t)E + g.n_blocks) * sizeof(uint64_t), g.res, work)) return rc;
+        g.C = (unsigned long long*)work; g.block_sum = g.C + E;
+        if (offspring) HIP_TRY(ctx, hipMemsetAsync(offspring, 0, (size_t)E * sizeof(int32_t), ctx->stream));
+        const dim3 grid((unsigned)g.n_blocks), one(1), threads(simplyp::PF_THREADS);
+        hipLaunchKernelGGL(simplyp::simplyp_pf_scan_block_kernel, grid, threads, 0, ctx->stream, g);
+        hipLaunchKernelGGL(simplyp::simplyp_pf_scan_sums_kernel, one, threads, 0, ctx->stream, g);
+        hipLaunchKernelGGL(simplyp::simplyp_pf_scan_add_kernel, grid, threads, 0, ctx->stream, g);
+        hipLaunchKernelGGL(simplyp::simplyp_pf_search_kernel, grid, threads, 0, ctx->stream, g);
+        hipLaunchKernelGGL(simplyp::simplyp_pf_offspring_kernel, grid, threads, 0, ctx->stream, g);
+        return pf_close(e, info);
+    });
 }
 
 int simplyp_gather_members(simplyp_ctx* ctx, int32_t E, int64_t n_rows, const int32_t* ancestors, const void* src, void* dst,
                            simplyp_pf_info* info)
 {
-    SIMPLYP_GUARD(ctx, gather_members_impl(ctx, E, n_rows, ancestors, src, dst, info))
+    return entry(ctx, "simplyp_gather_members", [&](const Entry& e) -> int {
+        if (int rc = pf_shape(e, E)) return rc;
+        if (n_rows < 0 || n_rows > (int64_t)0x7FFFFFFF)
+            return e.refuse("n_rows must be in [0, 2^31) (got %lld)", (long long)n_rows);
+        if (info) *info = {};                           // here, not only in pf_open: no rows is a success, and the refusals below come after it
+        if (n_rows == 0) return SIMPLYP_OK;
+        if (!ancestors || !src || !dst) return e.refuse("ancestors, src and dst must not be NULL");
+        const uintptr_t a = (uintptr_t)src, b = (uintptr_t)dst, bytes = (uintptr_t)n_rows * (uintptr_t)E * 8u;
+        if (a < b + bytes && b < a + bytes) return e.refuse("src and dst overlap (the gather is out of place)");
+        simplyp::PfGatherArgs g{};
+        g.E = E; g.n_rows = n_rows; g.ancestors = ancestors;
+        g.src = (const unsigned long long*)src; g.dst = (unsigned long long*)dst;
+        char* work = nullptr;
+        if (int rc = pf_open(e, info, 0, g.res, work)) return rc;
+        const long long row_blocks = (n_rows + simplyp::PF_GATHER_ROWS - 1) / simplyp::PF_GATHER_ROWS;
+        hipLaunchKernelGGL(simplyp::simplyp_gather_members_kernel, dim3(blocks(E, simplyp::PF_THREADS), (unsigned)std::min<long long>(row_blocks, 65535)),
+                           dim3(simplyp::PF_THREADS), 0, ctx->stream, g);
+        return pf_close(e, info);
+    });
 }
 
 int simplyp_pf_jitter(simplyp_ctx* ctx, int32_t E, int32_t n_dim, uint64_t seed, uint32_t t, double a, const double* centre,
                       const double* scale, const double* lo, const double* hi, const int32_t* target, double* theta,
                       double* member_params, double* f_tdp, simplyp_pf_info* info)
 {
-    SIMPLYP_GUARD(ctx, pf_jitter_impl(ctx, E, n_dim, seed, t, a, centre, scale, lo, hi, target, theta, member_params, f_tdp, info))
+    return entry(ctx, "simplyp_pf_jitter", [&](const Entry& e) -> int {
+        if (int rc = pf_shape(e, E)) return rc;
+        if (n_dim < 1 || n_dim > simplyp::PF_MAX_DIM)
+            return e.refuse("n_dim must be in [1, %d] (got %d)", simplyp::PF_MAX_DIM, (int)n_dim);
+        if (!centre || !scale || !lo || !hi || !target || !theta)
+            return e.refuse("centre, scale, lo, hi, target and theta must not be NULL");
+        if (!std::isfinite(a)) return e.refuse("a must be finite (got %g)", a);
+        simplyp::PfJitterArgs g{};
+        TABLE_TRY(ctx, st::check_box(e.me, n_dim, lo, hi, target, member_params, f_tdp, g.lo, g.hi, g.target, msg));
+        for (int d = 0; d < n_dim; ++d) {
+            if (!std::isfinite(centre[d]) || !(scale[d] >= 0.0) || !std::isfinite(scale[d]))
+                return e.refuse("centre[%d] must be finite and scale[%d] finite and >= 0 (got %g, %g)", d, d, centre[d], scale[d]);
+            g.centre[d] = centre[d]; g.scale[d] = scale[d];
+        }
+        g.E = E; g.n_dim = n_dim; g.a = a; g.t = t;
+        philox_key(seed, g);
+        g.theta = theta; g.member_params = member_params; g.f_tdp = f_tdp;
+        char* work = nullptr;
+        if (int rc = pf_open(e, info, 0, g.res, work)) return rc;
+        hipLaunchKernelGGL(simplyp::simplyp_pf_jitter_kernel, dim3(blocks(E, simplyp::PF_THREADS)), dim3(simplyp::PF_THREADS), 0, ctx->stream, g);
+        return pf_close(e, info);
+    });
 }
 
 void* simplyp_host_alloc(int64_t bytes)
@@ -3189,14 +3042,14 @@ int simplyp_memcpy_d2h(simplyp_ctx* ctx, void* dst, const void* src, int64_t byt
 
 int simplyp_eval_units(simplyp_ctx* ctx, int32_t which, int32_t n, const double* in, double* out)
 {
-    if (!ctx) return SIMPLYP_ERR_ARG;
-    if (which < 0 || which > 5 || n < 0 || (n > 0 && (!in || !out))) return fail(ctx, SIMPLYP_ERR_ARG, "simplyp_eval_units: bad arguments");
-    if (n == 0) return SIMPLYP_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(simplyp::eval_units_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, (int)which, (int)n, in, out);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SIMPLYP_OK;
+    return entry(ctx, "simplyp_eval_units", [&](const Entry& e) -> int {
+        if (which < 0 || which > 5 || n < 0 || (n > 0 && (!in || !out))) return e.refuse("bad arguments");
+        if (n == 0) return SIMPLYP_OK;
+        hipLaunchKernelGGL(simplyp::eval_units_kernel, dim3(blocks(n, 64)), dim3(64), 0, ctx->stream, (int)which, (int)n, in, out);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return SIMPLYP_OK;
+    });
 }
 
 }  // extern "C"

@@ -187,4 +187,19 @@ inline int check_box(const char* me, int n_dim, const double* lo, const double* 
     return SIMPLYP_OK;
 }
 
+// ---- (variable, output reach) pairs -------------------------------------------------------------------------------------------
+// 1 <= n_pairs <= max_pairs; every pair names a goodness-of-fit variable and one of the table's R output reaches.  Copies the
+// two lists into the kernel argument's arrays (each with room for max_pairs entries).
+inline int check_pairs(const char* me, const int32_t* pair_var, const int32_t* pair_reach, int32_t n_pairs, int max_pairs, int R,
+                       int* g_var, int* g_reach, std::string& msg)
+{
+    if (n_pairs < 1 || n_pairs > max_pairs) return reject(msg, me, "n_pairs must be in [1, %d] (got %d)", max_pairs, (int)n_pairs);
+    for (int p = 0; p < n_pairs; ++p) {
+        if (pair_var[p] < 0 || pair_var[p] >= SIMPLYP_N_GOF_VARS || pair_reach[p] < 0 || pair_reach[p] >= R)
+            return reject(msg, me, "pair %d = (variable %d, output reach %d) is out of range", p, (int)pair_var[p], (int)pair_reach[p]);
+        g_var[p] = pair_var[p]; g_reach[p] = pair_reach[p];
+    }
+    return SIMPLYP_OK;
+}
+
 }  // namespace simplyp_table

@@ -491,15 +491,35 @@ class Engine(object):
         if a.dim() != 2 or a.shape[1] != k_in:
             raise ValueError("%s takes rows of %d values" % (which, k_in))
         out = torch.empty((a.shape[0], k_out), dtype=torch.float64, device=self.tdev)
-        with torch.cuda.device(self.tdev):
-            self._bind_stream()
-            self._check(lib().simplyp_eval_units(self._h, w, a.shape[0], a.data_ptr(), out.data_ptr()), 'simplyp_eval_units')
+        self._info_call(None, 'simplyp_eval_units', self._h, w, a.shape[0], a.data_ptr(), out.data_ptr())
         return out.cpu().numpy()
 
-    # ---- what the reductions over a table check alike ----
+    # ---- what the analysis methods do alike ----
+    def _info_call(self, info_class, name, *args, bind=True):
+        """The library entry ``name`` with a fresh ``info_class`` as its last argument (None: the entry takes none), on this
+        engine's device and ordered after torch's current stream (``bind=False``: a second entry of one public method, which the
+        first has bound already -- ``_bind_stream`` may synchronise).  Raises EngineError unless the entry returns 0; returns the
+        info as a dict."""
+        info = None if info_class is None else info_class()
+        with self.torch.cuda.device(self.tdev):
+            if bind:
+                self._bind_stream()
+            rc = getattr(lib(), name)(*(args if info is None else args + (C.byref(info),)))
+        self._check(rc, name)
+        return None if info is None else info.as_dict()
+
     @staticmethod
     def _ptr(t):
         return None if t is None else t.data_ptr()
+
+    def _member_table(self, table):
+        """(E, lead, n_rows) of a table whose LAST axis is the member axis: its members, the shape of its rows, their number."""
+        torch = self.torch
+        if not torch.is_tensor(table) or table.dtype != torch.float64 or not table.is_contiguous() or table.dim() < 1 \
+                or table.device != self.tdev:
+            raise ValueError("table must be a contiguous float64 tensor on %s whose last axis is the member axis" % (self.tdev,))
+        lead = tuple(int(x) for x in table.shape[:-1])
+        return int(table.shape[-1]), lead, (int(np.prod(lead, dtype=np.int64)) if lead else 1)
 
     def _f_tdp(self, f_tdp, E):
         torch = self.torch
@@ -567,7 +587,6 @@ class Engine(object):
         ``info['spearman']`` [6, n_out_reaches, E] device tensor and its cost as ``info['spearman_ms']``.  ``gof``: a
         float64 device tensor of the result's shape to write into instead of a new one (a loop that reduces run after run)."""
         torch = self.torch
-        L = lib()
         head, rp, (D, n_or, E), keep = self._daily_table(out, out_mask, reach_params, out_reaches, member_of_slot, True)
         obs = np.ascontiguousarray(obs, dtype=np.float64)
         if obs.shape != (n_or, len(abi.GOF_VARS), D):
@@ -578,21 +597,13 @@ class Engine(object):
             gof = torch.empty(shape, dtype=torch.float64, device=self.tdev)
         elif tuple(gof.shape) != shape or gof.dtype != torch.float64 or not gof.is_contiguous() or gof.device != self.tdev:
             raise ValueError("gof must be a contiguous float64 tensor of shape %s on %s" % (shape, self.tdev))
-        info = abi.GofInfo()
         tail = (ft.data_ptr(), rp.data_ptr(), obs.ctypes.data_as(C.POINTER(C.c_double)))
-        with torch.cuda.device(self.tdev):
-            self._bind_stream()
-            rc = L.simplyp_gof(*(head + tail + (gof.data_ptr(), C.byref(info))))
-        self._check(rc, 'simplyp_gof')
-        d = info.as_dict()
+        d = self._info_call(abi.GofInfo, 'simplyp_gof', *(head + tail + (gof.data_ptr(),)))
         if spearman:
             rho = torch.empty((len(abi.GOF_VARS), n_or, E), dtype=torch.float64, device=self.tdev)
-            sinfo = abi.GofInfo()
-            with torch.cuda.device(self.tdev):
-                rc = L.simplyp_gof_spearman(*(head + tail + (rho.data_ptr(), C.byref(sinfo))))
-            self._check(rc, 'simplyp_gof_spearman')
+            sinfo = self._info_call(abi.GofInfo, 'simplyp_gof_spearman', *(head + tail + (rho.data_ptr(),)), bind=False)
             d['spearman'] = rho
-            d['spearman_ms'] = sinfo.kernel_ms
+            d['spearman_ms'] = sinfo['kernel_ms']
         del keep
         return gof, d
 
@@ -613,14 +624,10 @@ class Engine(object):
         sr = _i32(sum_reaches)
         ft = self._f_tdp(f_tdp, E)
         wb = torch.empty((len(cols), D, E), dtype=torch.float64, device=self.tdev)
-        info = abi.WbInfo()
-        with torch.cuda.device(self.tdev):
-            self._bind_stream()
-            rc = lib().simplyp_waterbody(*(head + (ft.data_ptr(), rp.data_ptr(), sr.ctypes.data_as(C.POINTER(C.c_int32)), len(sr),
-                                                   wb_mask, wb.data_ptr(), C.byref(info))))
-        self._check(rc, 'simplyp_waterbody')
+        d = self._info_call(abi.WbInfo, 'simplyp_waterbody',
+                            *(head + (ft.data_ptr(), rp.data_ptr(), sr.ctypes.data_as(C.POINTER(C.c_int32)), len(sr), wb_mask,
+                                      wb.data_ptr())))
         del keep
-        d = info.as_dict()
         d['columns'] = cols
         return wb, d
 
@@ -628,7 +635,6 @@ class Engine(object):
         """``gof`` for the summed series: wb [n_columns, D, E] from ``waterbody`` (``columns`` as returned there, must hold
         Q_cumecs and the three summed fluxes); obs [6, D] host array.  Returns (gof [n_stats, 6, 1, E], info)."""
         torch = self.torch
-        L = lib()
         ncols, D, E = wb.shape
         wb_mask = sum(1 << abi.WB_COLUMNS.index(c) for c in columns)
         if ncols != len(columns) or wb.dtype != torch.float64 or not wb.is_contiguous():
@@ -638,15 +644,10 @@ class Engine(object):
             raise ValueError("obs must have shape %s, got %s" % ((len(abi.GOF_VARS), D), obs.shape))
         ft = self._f_tdp(f_tdp, E)
         gof = torch.empty((len(abi.GOF_STATS), len(abi.GOF_VARS), 1, E), dtype=torch.float64, device=self.tdev)
-        info = abi.GofInfo()
         dims = abi.Dims(E, 1, D, 1)
-        with torch.cuda.device(self.tdev):
-            self._bind_stream()
-            rc = L.simplyp_gof_waterbody(self._h, C.byref(dims), wb_mask, wb.data_ptr(),
-                                         None if member_of_slot is None else member_of_slot.data_ptr(), ft.data_ptr(),
-                                         obs.ctypes.data_as(C.POINTER(C.c_double)), gof.data_ptr(), C.byref(info))
-        self._check(rc, 'simplyp_gof_waterbody')
-        return gof, info.as_dict()
+        info = self._info_call(abi.GofInfo, 'simplyp_gof_waterbody', self._h, C.byref(dims), wb_mask, wb.data_ptr(),
+                               self._ptr(member_of_slot), ft.data_ptr(), obs.ctypes.data_as(C.POINTER(C.c_double)), gof.data_ptr())
+        return gof, info
 
     def quantiles(self, table, q, include=None, member_of_slot=None):
         """Exact order statistics across the member axis (``simplyp_quantiles``): the two values that bracket numpy's
@@ -660,23 +661,15 @@ class Engine(object):
         x_(min(floor(h) + 1, n - 1)), h = q (n - 1), n = ``info['n_used']``; ``interpolate_quantiles`` turns them into
         numpy's values.  All NaN when no member is included."""
         torch = self.torch
-        if not torch.is_tensor(table) or table.dtype != torch.float64 or not table.is_contiguous() or table.dim() < 1 \
-                or table.device != self.tdev:
-            raise ValueError("table must be a contiguous float64 tensor on %s whose last axis is the member axis" % (self.tdev,))
+        E, lead, n_rows = self._member_table(table)
         qa = self._q_array(q)
-        K, E = len(qa), int(table.shape[-1])
-        lead = tuple(int(x) for x in table.shape[:-1])
-        n_rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        K = len(qa)
         inc = self._include_mask(include, E)
         self._check_member_of_slot(member_of_slot, E)
         stats = torch.empty((2, max(K, 1)) + lead, dtype=torch.float64, device=self.tdev)
-        info = abi.QuantileInfo()
-        with torch.cuda.device(self.tdev):
-            self._bind_stream()
-            rc = lib().simplyp_quantiles(self._h, E, n_rows, table.data_ptr(), self._ptr(member_of_slot), self._ptr(inc),
-                                         qa.ctypes.data_as(C.POINTER(C.c_double)), K, stats.data_ptr(), C.byref(info))
-        self._check(rc, 'simplyp_quantiles')
-        return stats[0], stats[1], info.as_dict()
+        info = self._info_call(abi.QuantileInfo, 'simplyp_quantiles', self._h, E, n_rows, table.data_ptr(), self._ptr(member_of_slot),
+                               self._ptr(inc), qa.ctypes.data_as(C.POINTER(C.c_double)), K, stats.data_ptr())
+        return stats[0], stats[1], info
 
     def _weight_vector(self, weights, E):
         """Integer weights [E] in member order (numpy integers or an int64 device tensor, e.g. ``pf_weights``' q) as a contiguous
@@ -707,13 +700,9 @@ class Engine(object):
         Returns (values, info): a device tensor of shape ``(K,) + table.shape[:-1]`` and a dict with ``T`` (the participating
         weights' sum), ``n_used`` and ``n_passes``.  All NaN when ``T`` is 0."""
         torch = self.torch
-        if not torch.is_tensor(table) or table.dtype != torch.float64 or not table.is_contiguous() or table.dim() < 1 \
-                or table.device != self.tdev:
-            raise ValueError("table must be a contiguous float64 tensor on %s whose last axis is the member axis" % (self.tdev,))
+        E, lead, n_rows = self._member_table(table)
         qa = self._q_array(q)
-        K, E = len(qa), int(table.shape[-1])
-        lead = tuple(int(x) for x in table.shape[:-1])
-        n_rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        K = len(qa)
         inc = self._include_mask(include, E)
         self._check_member_of_slot(member_of_slot, E)
         wt = self._weight_vector(weights, E)
@@ -755,17 +744,12 @@ class Engine(object):
         ft = None if f_tdp is None else self._f_tdp(f_tdp, E)
         stats = torch.empty((2, max(K, 1), max(len(sa), 1), max(P, 1), n_or, E), dtype=torch.float64, device=self.tdev)
         n_days = np.zeros(max(P, 1), dtype=np.int32)
-        info = abi.TqInfo()
         i32 = C.POINTER(C.c_int32)
-        with torch.cuda.device(self.tdev):
-            self._bind_stream()
-            rc = lib().simplyp_time_quantiles(*(head + (self._ptr(ft), self._ptr(rp), sa.ctypes.data_as(i32), len(sa),
-                                                        None if pod is None else pod.ctypes.data_as(i32), P,
-                                                        qa.ctypes.data_as(C.POINTER(C.c_double)), K, stats.data_ptr(),
-                                                        n_days.ctypes.data_as(i32), C.byref(info))))
-        self._check(rc, 'simplyp_time_quantiles')
+        d = self._info_call(abi.TqInfo, 'simplyp_time_quantiles',
+                            *(head + (self._ptr(ft), self._ptr(rp), sa.ctypes.data_as(i32), len(sa),
+                                      None if pod is None else pod.ctypes.data_as(i32), P, qa.ctypes.data_as(C.POINTER(C.c_double)), K,
+                                      stats.data_ptr(), n_days.ctypes.data_as(i32))))
         del keep
-        d = info.as_dict()
         d['n_days'] = n_days
         return stats[0], stats[1], d
 
@@ -798,11 +782,8 @@ class Engine(object):
         torch = self.torch
         head, tail, shape, keep = self._predictive_args(out, out_mask, series, err_m, f_tdp, reach_params, out_reaches, member_of_slot)
         table = torch.empty(shape, dtype=torch.float64, device=self.tdev)
-        with torch.cuda.device(self.tdev):
-            self._bind_stream()
-            rc = lib().simplyp_predictive_series(*(head + tail + (C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(day0),
-                                                                   1 if normals else 0, table.data_ptr())))
-        self._check(rc, 'simplyp_predictive_series')
+        self._info_call(None, 'simplyp_predictive_series',
+                        *(head + tail + (C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(day0), 1 if normals else 0, table.data_ptr())))
         del keep
         return table
 
@@ -830,16 +811,11 @@ class Engine(object):
             del keep
             return values, winfo
         stats = torch.empty((2, max(len(qa), 1)) + shape[:3], dtype=torch.float64, device=self.tdev)
-        info = abi.PredInfo()
-        with torch.cuda.device(self.tdev):
-            self._bind_stream()
-            rc = lib().simplyp_predictive_bands(*(head + (self._ptr(inc),) + tail
-                                                  + (C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(day0),
-                                                     qa.ctypes.data_as(C.POINTER(C.c_double)), len(qa), stats.data_ptr(),
-                                                     C.byref(info))))
-        self._check(rc, 'simplyp_predictive_bands')
+        info = self._info_call(abi.PredInfo, 'simplyp_predictive_bands',
+                               *(head + (self._ptr(inc),) + tail + (C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(day0),
+                                                                     qa.ctypes.data_as(C.POINTER(C.c_double)), len(qa), stats.data_ptr())))
         del keep
-        return stats[0], stats[1], info.as_dict()
+        return stats[0], stats[1], info
 
 
     def scores(self, table, y, weights=None, include=None, member_of_slot=None):
@@ -851,12 +827,7 @@ class Engine(object):
         (CRPS = sums[0] - sums[1]), int64 ``below`` and ``at_or_below`` -- and a dict with ``T``, ``n_used``, ``n_rows_scored``,
         ``n_chunks``, ``kernel_ms``, ``sort_ms``.  Rows without an observation and every row when ``T`` is 0: NaN and 0."""
         torch = self.torch
-        if not torch.is_tensor(table) or table.dtype != torch.float64 or not table.is_contiguous() or table.dim() < 1 \
-                or table.device != self.tdev:
-            raise ValueError("table must be a contiguous float64 tensor on %s whose last axis is the member axis" % (self.tdev,))
-        E = int(table.shape[-1])
-        lead = tuple(int(x) for x in table.shape[:-1])
-        n_rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        E, lead, n_rows = self._member_table(table)
         ya = np.asarray(y, dtype=np.float64)
         if ya.shape != lead:
             raise ValueError("y must have one observation per row of the table: shape %s" % (lead,))
@@ -928,15 +899,6 @@ class Engine(object):
         return res
 
     # ---- the stretch move (simplyp_mcmc_*; simplyp_amd.mcmc restates it) ----
-    def _info_call(self, info_class, name, *args):
-        """The library entry ``name`` with a fresh ``info_class`` as its last argument; returns the info as a dict."""
-        info = info_class()
-        with self.torch.cuda.device(self.tdev):
-            self._bind_stream()
-            rc = getattr(lib(), name)(*(args + (C.byref(info),)))
-        self._check(rc, name)
-        return info.as_dict()
-
     def mcmc_propose(self, theta, half, t, lo, hi, target, prop, inside, member_params=None, f_tdp=None, a=2.0, seed=0):
         """The proposals of half ``half`` at absolute step ``t`` (``simplyp_mcmc_propose``).  theta [n_dim, W] float64 device
         tensor (read); lo / hi [n_dim] the prior box and target [n_dim] (a row of ``marshal.PM_NAMES``,
@@ -1054,15 +1016,11 @@ class Engine(object):
         1 ST, resample 0 the point estimate --, ``(1 + n_boot,) + table.shape[:-1] + (2 n_dim + 2,)`` in the order P, S, G_0.., T_0..,
         and int32 ``[1 + n_boot]``.  ``quantiles`` on ``indices[..., 1:].contiguous()`` selects the percentile interval."""
         torch = self.torch
-        if not torch.is_tensor(table) or table.dtype != torch.float64 or not table.is_contiguous() or table.dim() < 1 \
-                or table.device != self.tdev:
-            raise ValueError("table must be a contiguous float64 tensor on %s whose last axis is the member axis" % (self.tdev,))
+        E, lead, n_rows = self._member_table(table)
         N, n_dim, n_boot = int(N), int(n_dim), int(n_boot)
-        lead = tuple(int(v) for v in table.shape[:-1])
-        n_rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
-        if int(table.shape[-1]) != N * (n_dim + 2):
-            raise ValueError("the table's member axis has %d entries, not N (n_dim + 2) = %d" % (int(table.shape[-1]), N * (n_dim + 2)))
-        if status is not None and (not torch.is_tensor(status) or status.dtype != torch.int32 or tuple(status.shape) != (int(table.shape[-1]),)
+        if E != N * (n_dim + 2):
+            raise ValueError("the table's member axis has %d entries, not N (n_dim + 2) = %d" % (E, N * (n_dim + 2)))
+        if status is not None and (not torch.is_tensor(status) or status.dtype != torch.int32 or tuple(status.shape) != (E,)
                                    or not status.is_contiguous()):
             raise ValueError("status must be a contiguous int32 device tensor with one entry per member")
         B = 1 + max(n_boot, 0)
