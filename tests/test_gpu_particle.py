@@ -274,6 +274,34 @@ def test_gather_equals_numpy_take(engine0, E):
         assert info['n_bad'] == 3 and (g[:, [3, 5, E - 1]] == NAN_WORD).all() and np.array_equal(g[:, okk], np.take(src, wild[okk], axis=1))
 
 
+@pytest.mark.parametrize('E', [3, 65])
+def test_gather_past_the_grid_cap(engine0, E):
+    """The launch caps grid.y at 65535 blocks of 8 rows and simplyp_gather_members_kernel strides over the rest
+    (r0 += gridDim.y * PF_GATHER_ROWS): 8 * 65535 + 11 rows give the first 11 row blocks a second trip, the last of them a
+    partial one.  The destination is followed by 8 rows nobody may write."""
+    n_rows = 8 * 65535 + 11
+    rng = np.random.default_rng(E)
+    anc = np.sort(rng.integers(0, E, E)).astype(np.int32)
+    src = rng.integers(-2 ** 63, 2 ** 63 - 1, (n_rows, E), dtype=np.int64)               # every bit pattern, NaN payloads included
+    src[:, ::7] = bits(np.array([np.nan]))[0] | 0x5A5
+    src_d = dev(engine0, src.view(np.float64))
+    wild = anc.copy()                                                                    # three ancestors outside [0, E)
+    at = [3, 5, E - 1] if E >= 8 else [0, 1, 2]
+    wild[at] = -1, E, 2 ** 31 - 1
+    okk = np.setdiff1d(np.arange(E), at)
+    for a, n_bad in ((anc, 0), (wild, 3)):
+        whole = torch.full((n_rows + 8, E), SENTINEL, dtype=torch.float64, device=engine0.tdev)
+        _, info = engine0.gather_members(src_d, dev(engine0, a, torch.int32), whole[:n_rows])
+        got = bits(whole.cpu().numpy())
+        assert info['n_bad'] == n_bad and (got[n_rows:] == bits(np.array([SENTINEL]))[0]).all()
+        assert np.array_equal(got[:n_rows, okk], np.take(src, a[okk], axis=1))
+        if n_bad:
+            assert (got[:n_rows, at] == NAN_WORD).all()                                  # in both trips
+        else:
+            assert np.array_equal(got[:n_rows], np.take(src, a, axis=1))
+    assert np.array_equal(bits(src_d.cpu().numpy()), src)
+
+
 # ---- the rejuvenation move --------------------------------------------------------------------------------------------------------
 
 def jitter_problem(E, n_dim):

@@ -180,6 +180,33 @@ def test_values_are_the_error_model_on_the_device_normals(engine0, D, E):
     same(got_s, got[..., perm])
 
 
+def test_days_past_the_grid_cap(engine0):
+    """predictive_launch caps grid.y at 65535 batches of 4 days and pred_days strides over the rest
+    (d0 += gridDim.y * PRED_BATCH): D = 4 * 65535 + 7 days in one launch give the first two batches a second trip, the last
+    of them a partial one.  Day 262 140 is the first day of the second trip: its counter must be day0 + 262 140, its row its own."""
+    D, E, first = 4 * 65535 + 7, 3, 4 * 65535
+    pr = problem(D, E)
+    table = np.ascontiguousarray(pr['table'][:, :, 1:])                    # one output reach: model reach 2
+    kw = dict(pr['kw'], out_reaches=[2])
+    series = [COL['Vr'], DERIVED[4]]                                       # a column and TP_mgl (three loads a day)
+    t = dev(engine0, table)
+    v = np.stack([table[0], derived_numpy(table, pr['A'][[2]], pr['f'])[4]])
+    assert np.isnan(v[:, first - 1:first + 1]).sum() < v[:, first - 1:first + 1].size
+    same(engine0.predictive_series(t, MASK5, series, **kw).cpu().numpy(), v)
+    z = engine0.predictive_series(t, MASK5, series, err_m=0.1, seed=SEED, day0=DAY0, normals=True, **kw).cpu().numpy()
+    want_z = predictive.standard_normal(SEED, np.arange(E)[None, None, None, :], (DAY0 + np.arange(D))[None, :, None, None],
+                                        2, np.asarray(series)[:, None, None, None])
+    assert z.shape == want_z.shape == (2, D, 1, E)
+    worst = float(np.abs(z - want_z).max())
+    print('max |z_device - z_mirror| = %.3e = %.1f eps over %d days' % (worst, worst / EPS, D))
+    assert worst <= 2.0 ** -45
+    assert float(np.abs(z[:, first - 1:first + 1] - want_z[:, first - 1:first + 1]).max()) <= 2.0 ** -45       # either side of the cap
+    m = err_model(series, E)
+    got = engine0.predictive_series(t, MASK5, series, err_m=m, seed=SEED, day0=DAY0, **kw).cpu().numpy()
+    same(got, predictive.perturb(v, m[:, None, None, :], z))
+    same(got[:, first - 1:first + 1], predictive.perturb(v, m[:, None, None, :], z)[:, first - 1:first + 1])
+
+
 # ---- the bands --------------------------------------------------------------------------------------------------------------
 
 def expected_stats(x, q, keep=None):

@@ -1,6 +1,7 @@
 """Ensemble percentile bands selected on the device (simplyp_quantiles): the order statistics against np.sort on made-up
 tables of every shape the two kernels take, the member mask and slot order, determinism, and the band through
-run_simply_p_ensemble against np.quantile on the table the same call returns.
+run_simply_p_ensemble against np.quantile on the table the same call returns.  Rows built to sit on the select's list limit
+and a table with more rows than the select's grid has workgroups also pin n_passes to tests/selection_model.py's count.
 
 Bounds: order statistics are elements of their rows -- compared as values, exactly (np.array_equal; -0.0 == +0.0, NaN ==
 NaN).  The interpolated band against np.quantile: 4 * eps * max(|lo|, |hi|) absolute -- three roundings (difference,
@@ -12,6 +13,8 @@ import numpy as np
 import pytest
 
 import helpers
+import selection_cases as sc
+import selection_model as sm
 import simplyp_amd as sp
 from simplyp_amd import abi, engine, marshal
 
@@ -90,6 +93,69 @@ def test_few_very_long_rows(engine0):
     table[1] = rng.choice(np.array([1.0, 2.0, 3.0]), size=1200000)
     check(engine0, table, Q_FIXED)
     check(engine0, table, q_random())
+
+
+def model_of(table, q):
+    """tests/selection_model.py on every row: (lower, upper [K, n_rows], the largest sweep count)."""
+    k_lo, k_hi = sm.linear_ranks(q, table.shape[1])
+    got = [sm.member_select(row, np.concatenate([k_lo, k_hi])) for row in table]
+    v = np.stack([g[0] for g in got], axis=1)
+    return v[:len(q)], v[len(q):], max(g[1] for g in got)
+
+
+@pytest.mark.parametrize('case', sc.member_cases(), ids=lambda c: c[0])
+@pytest.mark.parametrize('n_rows', [1, 3, 17])
+def test_rows_on_the_list_limit(engine0, case, n_rows):
+    """QLIST = 64, the bucket size at which quantile_select_kernel stops refining and collects: rows of E = 4097 (the shortest
+    the select takes) whose wanted buckets hold exactly 64 or 65 members after the first digit.  n_passes tells the path:
+    2 = first digit, collect; 3 = the 65 part in the second digit; 4 = they share it and part in the third; with two groups of
+    64 and 65 the collect waits for the larger (3), unless no rank lies in it (2).  tests/selection_cases.py derives the numbers."""
+    name, n_top, n_far, narrow, probs, sweeps = case
+    table = sc.member_table(case, n_rows, np.random.default_rng(100 * n_rows + len(name)))
+    assert table.shape == (n_rows, sm.QSORT_MAX + 1)
+    info = check(engine0, table, probs)
+    lo, hi, model_sweeps = model_of(table, probs)
+    want_lo, want_hi, _ = expected(table, probs)
+    assert np.array_equal(lo, want_lo) and np.array_equal(hi, want_hi)
+    assert info['n_passes'] == model_sweeps == sweeps
+
+
+@pytest.fixture(scope='module')
+def capped(engine0):
+    """65536 + 36 rows of 4097 members (2.15 GB), made on the device from six base rows and a power of two per row."""
+    import torch
+    rng = np.random.default_rng(65536)
+    base = sc.base_rows(sc.E_SELECT, sm.QLIST, rng)
+    kind, scale = sc.capped_rows(65536, len(base), rng)
+    table = torch.from_numpy(base).to(engine0.tdev)[torch.from_numpy(kind).to(engine0.tdev)]
+    table.mul_(torch.from_numpy(scale).to(engine0.tdev)[:, None])
+    made = dict(base=base, kind=kind, scale=scale, table=table)
+    del table
+    yield made
+    made.clear()
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize('q', [Q_FIXED, q_random()], ids=['K=5', 'K=16'])
+def test_rows_past_the_grid_cap(engine0, capped, q):
+    """select_launch caps the grid at 65536 workgroups and radix_select strides over the rows (r += gridDim.x), carrying
+    collect, G, prefix, count and list_n in LDS from one row to the next behind one barrier.  Workgroup i < 36 selects row i
+    and then row 65536 + i: every ordered pair of six kinds of row (distinct, ties, flat, specials, wanted bucket of 64, of 65).
+    A power of two scales order statistics exactly, so the expected values are the base rows' times the row's scale.  The
+    flat rows take all 8 digits at any scale, so n_passes is 8: the model's maximum over the kinds."""
+    base, kind, scale, table = capped['base'], capped['kind'], capped['scale'], capped['table']
+    N = len(kind)
+    assert N == 65536 + 36 and tuple(table.shape) == (N, 4097)
+    assert {(int(kind[i]), int(kind[65536 + i])) for i in range(36)} == {(a, b) for a in range(6) for b in range(6)}
+    lower, upper, info = engine0.quantiles(table, q)
+    lo, hi, model_sweeps = model_of(base, q)
+    want_lo, want_hi, _ = expected(base, q)
+    assert np.array_equal(lo, want_lo, equal_nan=True) and np.array_equal(hi, want_hi, equal_nan=True)
+    for got, want in ((lower, want_lo), (upper, want_hi)):
+        got, want = got.cpu().numpy(), want[:, kind] * scale
+        assert got.shape == want.shape == (len(q), N)
+        assert np.array_equal(got, want, equal_nan=True), np.argwhere(~((got == want) | (np.isnan(got) & np.isnan(want))))[:5]
+    assert info['n_passes'] == model_sweeps == 8 and info['n_used'] == 4097 and info['bytes_table'] == N * 4097 * 8
 
 
 @pytest.mark.parametrize('E', [65, 1000, 4096, 4097, 20000])

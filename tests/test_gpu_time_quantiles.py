@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 
 import helpers
+import selection_cases as sc
+import selection_model as sm
 import simplyp_amd as sp
 from simplyp_amd import abi, engine, marshal
 
@@ -63,29 +65,7 @@ def same(got, want):
     return True
 
 
-def make_table(kind, shape, rng):
-    """[n_cols, D, R, E] of one kind."""
-    D = shape[1]
-    if kind == 'smooth':                                                   # positive, within a few binades, day-to-day smooth
-        t = np.exp(np.cumsum(rng.normal(scale=0.05, size=shape), axis=1) + rng.normal(size=(shape[0], 1) + shape[2:]))
-        return t
-    if kind == 'equal':
-        return np.full(shape, rng.normal())
-    if kind == 'two':
-        return rng.choice(np.array([1.5, -2.25]), size=shape)
-    if kind == 'lastbits':                                                 # differ in the last bits only
-        base = np.float64(0.7310585786300049)
-        return (np.full(shape, base).view(np.int64) + rng.integers(0, 7, size=shape)).view(np.float64)
-    assert kind == 'special'                                               # mixed sign, +-0, +-inf, denormals, a few NaN
-    t = rng.normal(size=shape) * 10.0 ** rng.integers(-3, 4, size=(shape[0], 1) + shape[2:])
-    specials = np.array([np.inf, -np.inf, 5e-324, -5e-324, 1e-310, -1e-310, -0.0, 0.0, 0.0, -0.0, np.nan, -np.nan,
-                         np.finfo(np.float64).max, -np.finfo(np.float64).max])
-    hit = rng.random(size=shape) < 0.3
-    t[hit] = rng.choice(specials, size=int(hit.sum()))
-    return t
-
-
-KINDS = ('smooth', 'equal', 'two', 'lastbits', 'special')
+make_table, KINDS = sc.time_table, sc.KINDS                               # [n_cols, D, R, E] of one kind
 
 
 def dev(engine0, a, dtype=None):
@@ -106,19 +86,33 @@ def check(engine0, table, mask, q, series, x, period_of_day=None, n_periods=None
     return info
 
 
+def check_model(engine0, table, mask, q, series, x, period_of_day=None, n_periods=None, loads=None, **kw):
+    """``check``, and the call's n_sweeps and bytes_read against tests/selection_model.py (whose values must be np.sort's too)."""
+    info = check(engine0, table, mask, q, series, x, period_of_day, n_periods, **kw)
+    lo, hi, n_sweeps, bytes_read = sm.time_quantiles(x, q, period_of_day, n_periods, loads)
+    want_lo, want_hi, _ = expected(x, q, period_of_day, n_periods)
+    same(lo, want_lo)
+    same(hi, want_hi)
+    assert (info['n_sweeps'], info['bytes_read']) == (n_sweeps, bytes_read)
+    return info
+
+
 @pytest.mark.parametrize('E', [1, 63, 64, 65, 130])
-@pytest.mark.parametrize('D', [1, 2, 255, 256, 257, 1000])
+@pytest.mark.parametrize('D', [1, 2, 127, 128, 129, 255, 256, 257, 1000])
 def test_order_statistics_are_exact(engine0, E, D):
+    """D = 127, 128, 129: TQ_LIST = 128, the days a lane collects in its first sweep; one more costs a digit first."""
     rng = np.random.default_rng(1000 * D + E)
     cols = [COL['Vr'], COL['Qr']]
     for kind in KINDS:
         for R in (1, 3):
             table = make_table(kind, (2, D, R, E), rng)
             for q in ([0.0], [0.5], [1.0], q_random(D + E)):
-                info = check(engine0, table, MASK2, q, cols, table)
+                info = (check_model if D == 129 else check)(engine0, table, MASK2, q, cols, table)
                 assert 1 <= info['n_sweeps'] <= 8 * 2 * len(q) + 1
                 if D <= 128:
                     assert info['n_sweeps'] == 1                           # collected at once
+                if D == 129:
+                    assert info['n_sweeps'] >= 2                           # a digit, then the collect (or more digits)
             # one series, the second column alone, the order reversed
             check(engine0, table, MASK2, Q_BAND, [COL['Qr']], table[1:])
             check(engine0, table, MASK2, Q_BAND, cols[::-1], table[::-1])
@@ -160,6 +154,69 @@ def test_periods(engine0, case):
         assert list(info['n_days']) == [0]
     # trailing periods that no day names exist when the caller says so
     check(engine0, table, MASK2, Q_BAND, [COL['Qr']], table[1:], period_of_day=pod, n_periods=int(pod.max()) + 3)
+
+
+def test_lanes_whose_lead_buckets_total_128_and_129(engine0):
+    """tq_select collects when __all(total <= TQ_LIST), total = the keys in a lane's lead buckets.  D = 300: every lane holds 172
+    FILL, 64 TOP and 64 FAR values (three first digits), the ranks lie among TOP and FAR: after the first digit (1 sweep) a lane
+    has two groups of 64 + 64 = 128 keys -> collect: n_sweeps = 2.  One lane with 65 FAR values (129) sends its whole wave
+    through the second digit, a sweep per group, before the collect: 1 + 2 + 1 = 4, while the other wave (6 lanes) makes 2."""
+    D, E = 300, 70
+    q = [0.6, 0.9, 1.0]                                                    # ranks 179, 180 (TOP), 269, 270, 299 (FAR)
+    rng = np.random.default_rng(128)
+    cols = [COL['Vr'], COL['Qr']]
+    table = sc.lead_bucket_table((2, D, 1, E), 64, rng)
+    info = check_model(engine0, table, MASK2, q, cols, table)
+    assert (info['n_sweeps'], info['bytes_read']) == (2, 512 * 2 * D * 2 * 2)          # 2 sweeps by 2 series x 2 waves
+    table = sc.lead_bucket_table((2, D, 1, E), 64, rng, odd_lane=(5, 65))
+    info = check_model(engine0, table, MASK2, q, cols, table)
+    assert (info['n_sweeps'], info['bytes_read']) == (4, 512 * (4 + 2) * D * 2)
+    table = sc.lead_bucket_table((2, D, 1, E), 65, rng)
+    info = check_model(engine0, table, MASK2, q, cols, table)
+    assert (info['n_sweeps'], info['bytes_read']) == (4, 512 * 4 * D * 2 * 2)
+
+
+@pytest.mark.parametrize('D', [300, 1000])
+@pytest.mark.parametrize('lanes', ['every kind in every wave', 'one equal lane, one lastbits lane'])
+def test_mixed_waves(engine0, lanes, D):
+    """tq_select decides for the 64 lanes together: __all(total <= TQ_LIST) before the collect, while (__any(cur < T)) over the
+    group indices, and the break at level == 8 that ends a wave no lane of which could collect.  Here the lanes of a wave differ: member
+    e is of kind KINDS[e % 5], or all are smooth but one 'equal' lane in the first wave and one 'lastbits' lane in the partial
+    third (E = 130) -- lanes that need 8 digits beside lanes that settle after two, lanes with one group beside lanes with
+    several (idle, on == false, in the extra sweeps)."""
+    E, R = 130, 2
+    rng = np.random.default_rng(D + len(lanes))
+    table = (sc.mixed_table if lanes.startswith('every') else sc.lone_lanes_table)((2, D, R, E), rng)
+    pod = sc.periods_130_1_200(D)
+    for q in ([0.0], Q_BAND, q_random()):
+        info = check_model(engine0, table, MASK2, q, [COL['Qr']], table[1:])
+        assert info['n_sweeps'] >= 8                                       # the 'equal' lane's wave: 8 digits and no collect
+        check_model(engine0, table, MASK2, q, [COL['Qr']], table[1:], period_of_day=pod, n_periods=4)
+
+
+def test_periods_past_the_grid_cap(engine0):
+    """The launch caps grid.y at 65535 and tq_periods strides over the periods (p += gridDim.y), re-initialising the per-lane
+    state and reusing hist as list.  65535 + 70 periods (selection_cases.capped_periods): a workgroup takes period y and then
+    65535 + y -- 200 days and then 129-300 or one, 200 days that take all 8 digits and then a smooth period, a full period and
+    then an empty one, an empty one and then a full one, one day and then a long period of each kind."""
+    P0, E = 65535, 3
+    rng = np.random.default_rng(P0)
+    table, pod, P = sc.capped_period_table(5, E, P0, rng)
+    assert P == P0 + 70 and table.shape[1] == len(pod)
+    A, f = rng.uniform(5.0, 80.0, size=(1, E)), rng.uniform(0.3, 0.95, size=E)
+    rp = np.zeros((len(marshal.PR_NAMES), 1, E))
+    rp[marshal.PR_NAMES.index('A_catch')] = A
+    x = np.stack([table[0], derived_numpy(table, A, f)[0]])                # the column Vr and the derived Q_cumecs
+    lower, upper, info = engine0.time_quantiles(dev(engine0, table), MASK5, Q_BAND, series=[COL['Vr'], DERIVED[0]], period_of_day=pod,
+                                                n_periods=P, f_tdp=f, reach_params=rp)
+    want_lo, want_hi, n_days = sc.sorted_periods(x, Q_BAND, pod, P)        # np.sort per period, the one-day periods at once
+    assert np.array_equal(info['n_days'], n_days) and n_days[64] == n_days[P0 + 33] == 0 and n_days[P0 + 64] == 250
+    same(lower.cpu().numpy(), want_lo)
+    same(upper.cpu().numpy(), want_hi)
+    lo, hi, n_sweeps, bytes_read = sm.time_quantiles(x, Q_BAND, pod, P)
+    same(lo, want_lo)
+    same(hi, want_hi)
+    assert (info['n_sweeps'], info['bytes_read']) == (n_sweeps, bytes_read) and n_sweeps >= 8
 
 
 def derived_numpy(table5, A, f):

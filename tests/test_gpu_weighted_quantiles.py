@@ -4,7 +4,9 @@ is integer arithmetic, there is no tolerance anywhere.
 
 Sizes are where the kernels can go wrong: E around the wavefront (63, 64, 65), around the LDS sort's longest row (2048, 2049)
 and the unweighted sort's (4096, 4097), rows the radix select sweeps in one, two and three trips of 4096 members with a ragged
-tail (4097, 9000); 1, 3 and 17 rows pack a sort workgroup fully, partly and leave a partial last workgroup."""
+tail (4097, 9000); 1, 3 and 17 rows pack a sort workgroup fully, partly and leave a partial last workgroup.  Rows whose wanted
+buckets hold exactly 32 or 33 weighted members, and 65536 + 36 rows (more than the select's grid has workgroups), also pin
+n_passes to the count of tests/selection_model.py."""
 
 import ctypes as C
 import os
@@ -16,6 +18,8 @@ import helpers
 import simplyp_amd as sp
 from simplyp_amd import abi, engine, marshal, weighted
 
+import selection_cases as sc
+import selection_model as sm
 import weighted_cases as wc
 
 pytestmark = pytest.mark.gpu
@@ -99,6 +103,70 @@ def test_all_equal_rows_and_rows_over_600_binades(engine0, E):
     wide = np.ldexp(rng.uniform(1, 2, (3, E)), rng.integers(-300, 301, (3, E))) * rng.choice([-1.0, 1.0], (3, E))
     _, info = check(engine0, wide, q, wc.PROBS + [float(p) for p in rng.uniform(0, 1, 11)], what=('wide', E))
     assert 1 <= info['n_passes'] <= 8
+
+
+def model_of(table, q, probs):
+    """tests/selection_model.py on every row: (values [K, n_rows], the largest sweep count)."""
+    T = sum(int(v) for v in q)
+    got = [sm.member_select(row, [weighted.threshold(p, T) for p in probs], weights=q) for row in table]
+    return np.stack([g[0] for g in got], axis=1), max(g[1] for g in got)
+
+
+@pytest.mark.parametrize('case', sc.weighted_cases(), ids=lambda c: c[0])
+@pytest.mark.parametrize('n_rows', [1, 3, 17])
+def test_rows_on_the_list_limit(engine0, case, n_rows):
+    """WQLIST = 32, the bucket size at which weighted_select_kernel collects -- counted in members that carry a weight (chist),
+    not in weight (hist): rows of E = 2049 (the shortest the select takes) whose wanted buckets hold exactly 32 or 33 such
+    members after the first digit, and one of 33 members of which one has weight 0, which counts as 32.  n_passes tells the
+    path: 2 = first digit, collect; 3 = the 33 part in the second digit; 4 = in the third; two groups of 32 and 33: 3 with a
+    threshold in the larger, 2 without.  tests/selection_cases.py derives the numbers."""
+    rng = np.random.default_rng(100 * n_rows + len(case[0]))
+    q = wc.weights('zeros30', sc.E_WSELECT, rng)
+    table, probs, _ = sc.weighted_table(case, q, n_rows, rng)
+    assert table.shape == (n_rows, sm.WQSORT_MAX + 1)
+    _, info = check(engine0, table, q, probs, what=case[0])
+    values, model_sweeps = model_of(table, q, probs)
+    assert wc.same_bits(values, weighted.quantiles(table, q, probs))
+    assert info['n_passes'] == model_sweeps == case[5]
+
+
+@pytest.fixture(scope='module')
+def capped(engine0):
+    """65536 + 36 rows of 2049 members (1.07 GB), made on the device from six base rows and a power of two per row."""
+    import torch
+    rng = np.random.default_rng(65536)
+    q = wc.weights('zeros30', sc.E_WSELECT, rng)
+    base = sc.base_rows(sc.E_WSELECT, sm.WQLIST, rng, weights=q)
+    kind, scale = sc.capped_rows(65536, len(base), rng)
+    table = torch.from_numpy(base).to(engine0.tdev)[torch.from_numpy(kind).to(engine0.tdev)]
+    table.mul_(torch.from_numpy(scale).to(engine0.tdev)[:, None])
+    made = dict(q=q, base=base, kind=kind, scale=scale, table=table)
+    del table
+    yield made
+    made.clear()
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize('K', [5, 16])
+def test_rows_past_the_grid_cap(engine0, capped, K):
+    """select_launch caps the grid at 65536 workgroups and radix_select<WQSelect> strides over the rows (r += gridDim.x),
+    carrying collect, G, prefix, count and list_n in LDS from one row to the next behind one barrier.  Workgroup i < 36 selects
+    row i and then row 65536 + i: every ordered pair of six kinds of row (distinct, ties, flat, specials, wanted bucket of 32, of
+    33).  A power of two scales the values exactly and leaves their order alone, so the expected values are the base rows' times
+    the row's scale.  The flat rows take all 8 digits at any scale, so n_passes is 8: the model's maximum over the kinds."""
+    q, base, kind, scale, table = (capped[k] for k in ('q', 'base', 'kind', 'scale', 'table'))
+    N = len(kind)
+    assert N == 65536 + 36 and tuple(table.shape) == (N, 2049)
+    assert {(int(kind[i]), int(kind[65536 + i])) for i in range(36)} == {(a, b) for a in range(6) for b in range(6)}
+    probs = wc.PROBS + [float(p) for p in np.random.default_rng(K).uniform(0, 1, K - 5)]
+    got, info = engine0.weighted_quantiles(table, probs, q)
+    values, model_sweeps = model_of(base, q, probs)
+    want = weighted.quantiles(base, q, probs)
+    assert wc.same_bits(np.nan_to_num(values, nan=7.0), np.nan_to_num(want, nan=7.0))
+    got, want = got.cpu().numpy(), want[:, kind] * scale
+    assert got.shape == want.shape == (K, N)
+    assert np.array_equal(got, want, equal_nan=True), np.argwhere(~((got == want) | (np.isnan(got) & np.isnan(want))))[:5]
+    assert info['n_passes'] == model_sweeps == 8 and info['T'] == sum(int(v) for v in q) and info['bytes_table'] == N * 2049 * 8
 
 
 @pytest.mark.parametrize('E', [65, 2049, 4097])
