@@ -15,7 +15,7 @@ How the reference is driven:
     either as shipped (rtol=0.01, default atol, mxstep=5000) or at rtol=atol=1e-12
     ("tight": the converged solution of the reference's own equations = the parity oracle).
 
-Usage:  python tests/golden/make_golden.py [--long] [--only NAME|mc|unit|knee|heldout|wide|dry|dry-check|c4mc|c4deep|steplen|drynet|branch]
+Usage:  python tests/golden/make_golden.py [--long] [--only NAME|mc|unit|knee|heldout|wide|dry|dry-check|c4mc|c4deep|steplen|drynet|branch|closable]
 """
 
 import argparse
@@ -733,6 +733,30 @@ def branch_fixture(n_proc):
     print('branch_network.npz written')
 
 
+# The closable configuration (--only closable): confluence3_nc_2004 with alpha = 0 (no evapotranspiration) and k_M = 1 (sediment delivery
+# linear in Qr), everything else as the scenario has it, the whole year at rtol = atol = 1e-12: all 25 columns of every reach.  In this
+# configuration the water, sediment, PP and TDP budgets of a reach close from the columns alone (tests/budgets.py); the fixture holds
+# the reference's own table to them.
+CLOSABLE = dict(alpha=0.0, k_M=1.0)
+
+
+def closable_fixture(mods, switch):
+    from simplyp_amd import marshal
+    sc = copy.deepcopy(scenarios(False)['confluence3_nc_2004'])
+    for k, v in CLOSABLE.items():
+        sc['p'][k] = v
+    r = run_reference(mods, switch, sc, 1e-12)
+    print('confluence3_closable_2004: wall %.1f s  nfe/day %.1f' % (r['wall'], r['nfe_per_day']))
+    scs = sorted(r['df_R'])
+    tab = np.stack([np.stack([(r['df_R'][SC] if c in r['df_R'][SC].columns else r['df_TC'][SC])[c].to_numpy(dtype=float) for SC in scs],
+                             axis=1) for c in marshal.OUT_COLUMNS])                     # [25, D, S]
+    np.savez_compressed(os.path.join(HERE, 'confluence3_closable_2004.npz'), out=tab, columns=np.array(marshal.OUT_COLUMNS),
+                        reaches=np.array(scs), scenario=np.array('confluence3_nc_2004'), names=np.array(sorted(CLOSABLE)),
+                        values=np.array([CLOSABLE[k] for k in sorted(CLOSABLE)]), odeint_rtol_atol=np.array((1e-12, 1e-12)),
+                        n_days=np.array(tab.shape[1]), meta=np.array('the whole year %s .. %s' % (r['met'].index[0].date(), r['met'].index[-1].date())))
+    print('confluence3_closable_2004.npz written')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--long', action='store_true', help='also run the 1981-2010 scenario (minutes)')
@@ -786,6 +810,10 @@ def main():
     switch = OdeintSwitch()
     mods['model'].odeint = switch
     rng = np.random.default_rng(20240601)
+
+    if args.only == 'closable':
+        closable_fixture(mods, switch)
+        return
 
     if args.only in (None, 'mc'):
         monte_carlo_members(mods, switch)

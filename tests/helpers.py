@@ -355,6 +355,81 @@ def branch_network_problem(solver=None):
     return pr, tables
 
 
+def random_network_problem(seed, E=40):
+    """A random upstream graph: 12 reaches, 0-2 upstream reaches each, a reach may feed several downstream reaches; every reach one of
+    confluence3_nc_2004's three (newly-converted land of either kind, or none) with its own area, length, slope and TDPeff (blank on
+    about a third); `E` members with fc, T_g, a_Q and E_M perturbed.  One year, both dynamic options on; opts: the default solver."""
+    from simplyp_amd import marshal, abi
+    rng = np.random.default_rng(100 + seed)
+    S = 12
+    base = marshal_scenario('confluence3_nc_2004', E=E)
+    rp0 = base['reach_params']                                   # [NP_R, 3, E]
+    rp = np.empty((marshal.NP_R, S, E))
+    for s in range(S):
+        rp[:, s, :] = rp0[:, rng.integers(0, 3), :]
+    ix = marshal.PR_NAMES.index
+    rp[ix('A_catch')] = rng.uniform(5.0, 60.0, (S, 1))
+    rp[ix('L_reach')] = rng.uniform(2000.0, 12000.0, (S, 1))
+    rp[ix('S_reach')] = rng.uniform(0.3, 2.5, (S, 1))
+    rp[ix('TDPeff')] = np.where(rng.random((S, 1)) < 0.3, np.nan, rng.uniform(0.0, 0.4, (S, 1)))
+    up_ptr, up_idx = [0], []
+    for s in range(S):
+        k = 0 if s == 0 else int(rng.integers(0, 3))
+        ups = sorted(rng.choice(s, size=min(k, s), replace=False).tolist()) if k else []
+        up_idx += ups
+        up_ptr.append(len(up_idx))
+    mp = base['member_params'].copy()
+    for pname, lo, hi in (('fc', 0.9, 1.1), ('T_g', 0.7, 1.4), ('a_Q', 0.7, 1.5), ('E_M', 0.5, 2.0)):
+        mp[marshal.PM_NAMES.index(pname)] *= rng.uniform(lo, hi, E)
+    opts = abi.make_opts(None, dynamic_epc0=True, dynamic_erod=True, run_mode_cal=True, sc_qr0=S - 1, out_mask=marshal.MASK_ALL)
+    return dict(base, member_params=mp, reach_params=rp, up_ptr=np.asarray(up_ptr, dtype=np.int32), up_idx=np.asarray(up_idx, dtype=np.int32),
+                opts=opts)
+
+
+BUDGET_SCENARIOS = ['tarland_2004_dynamic', 'tarland_2004_dynamic+snow', 'chain4_val_2004', 'confluence3_nc_2004', 'stiff_chain12_2004',
+                    'branch', 'random1', 'random2', 'random3']
+
+
+def budget_problem(name, E, solver=None, step_len=1.0, closable=True, seed=7):
+    """Arrays + opts of a scenario of BUDGET_SCENARIOS for the budgets of tests/budgets.py: a golden scenario ('+snow': the snow module
+    in the kernel, with f_DDSM and D_snow_0 perturbed and the D_snow column in the table), the branching network ('branch', 1981,
+    members of config C4's draw) or a random 12-reach graph ('randomN' = random_network_problem(N)), all 25 columns.  closable: alpha = 0
+    and k_M = 1 for every member, and fc, T_g, a_Q, b_Q, beta, f_quick, E_M, T_s_A, T_s_S, Qg_min perturbed per member (member 0 keeps
+    the scenario's values); else the members as the scenario has them.  m['columns'] names the table's columns."""
+    from simplyp_amd import marshal, abi
+    snow = name.endswith('+snow')
+    if name == 'branch':
+        m = branch_network_inputs(max(E, 2), '1981-01-01', '1981-12-31', members=[-1] + list(range(E - 1)), solver=solver)
+    elif name.startswith('random'):
+        m = random_network_problem(int(name[len('random'):]), E)
+        o = abi.make_opts(solver, dynamic_epc0=True, dynamic_erod=True, run_mode_cal=True, sc_qr0=m['opts'].sc_qr0, out_mask=marshal.MASK_ALL)
+        m['opts'] = o
+    else:
+        m = marshal_scenario(name.split('+')[0], E=E, solver=solver, snow=snow)
+    m['opts'].step_len = float(step_len)
+    m['columns'] = list(marshal.OUT_COLUMNS)
+    mp = np.array(m['member_params'], dtype=np.float64)
+    rng = np.random.default_rng(seed)
+    if snow:
+        m['opts'].out_mask = marshal.MASK_ALL | marshal.MASK_D_SNOW
+        m['columns'] = list(marshal.ALL_COLUMNS)
+        mp[marshal.PM_NAMES.index('f_DDSM'), 1:] *= rng.uniform(0.5, 2.0, E - 1)
+        mp[marshal.PM_NAMES.index('D_snow_0'), 1:] = rng.uniform(0.0, 30.0, E - 1)
+    if closable:
+        mp[marshal.PM_NAMES.index('alpha')] = 0.0
+        mp[marshal.PM_NAMES.index('k_M')] = 1.0
+        for pname, lo, hi, cap in (('fc', 0.85, 1.15, None), ('T_g', 0.6, 1.6, None), ('a_Q', 0.6, 1.6, None), ('b_Q', 0.9, 1.1, 0.95),
+                                   ('beta', 0.8, 1.2, 0.95), ('f_quick', 0.3, 3.0, 0.5), ('E_M', 0.5, 2.0, None), ('T_s_A', 0.5, 2.0, None),
+                                   ('T_s_S', 0.5, 2.0, None), ('Qg_min', 0.2, 3.0, None)):
+            row = mp[marshal.PM_NAMES.index(pname)]
+            row[1:] *= rng.uniform(lo, hi, E - 1)
+            if cap is not None:
+                np.minimum(row, cap, out=row)
+    m['member_params'] = np.ascontiguousarray(mp)
+    m.setdefault('out_reaches', None)
+    return m
+
+
 def steplen_cases():
     """[(scenario name, step_len)] of tests/golden/step_len.npz (tests/golden/make_golden.py --only steplen)."""
     z = np.load(os.path.join(GOLDEN, 'step_len.npz'), allow_pickle=False)

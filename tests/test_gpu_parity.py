@@ -628,28 +628,8 @@ def test_random_reach_networks_match_the_oracle(engine0, oracle_lib, seed):
     model.py:508-544) -- 1e-9 with RK4 (rounding only: the kernel's hoisted day constants against the oracle's literal
     formulas, carried through up to 7 reaches in series; measured 1.9e-10), 10 x rtol with the default solver -- and bit-identical to each other."""
     import torch
-    rng = np.random.default_rng(100 + seed)
     S, E = 12, 40
-    base = helpers.marshal_scenario('confluence3_nc_2004', E=E)
-    rp0 = base['reach_params']                                   # [NP_R, 3, E]
-    rp = np.empty((marshal.NP_R, S, E))
-    for s in range(S):
-        rp[:, s, :] = rp0[:, rng.integers(0, 3), :]
-    ix = marshal.PR_NAMES.index
-    rp[ix('A_catch')] = rng.uniform(5.0, 60.0, (S, 1))
-    rp[ix('L_reach')] = rng.uniform(2000.0, 12000.0, (S, 1))
-    rp[ix('S_reach')] = rng.uniform(0.3, 2.5, (S, 1))
-    rp[ix('TDPeff')] = np.where(rng.random((S, 1)) < 0.3, np.nan, rng.uniform(0.0, 0.4, (S, 1)))
-    up_ptr, up_idx = [0], []
-    for s in range(S):
-        k = 0 if s == 0 else int(rng.integers(0, 3))
-        ups = sorted(rng.choice(s, size=min(k, s), replace=False).tolist()) if k else []
-        up_idx += ups
-        up_ptr.append(len(up_idx))
-    mp = base['member_params'].copy()
-    for pname, lo, hi in (('fc', 0.9, 1.1), ('T_g', 0.7, 1.4), ('a_Q', 0.7, 1.5), ('E_M', 0.5, 2.0)):
-        mp[marshal.PM_NAMES.index(pname)] *= rng.uniform(lo, hi, E)
-    m = dict(base, member_params=mp, reach_params=rp, up_ptr=np.asarray(up_ptr, dtype=np.int32), up_idx=np.asarray(up_idx, dtype=np.int32))
+    m = helpers.random_network_problem(seed, E)
     for solver, tol in ((dict(integrator='rk4', substeps=96), 1e-9), (None, helpers.TOL_WORKING)):      # (24 substeps are unstable on the big confluences)
         m['opts'] = abi.make_opts(solver, dynamic_epc0=True, dynamic_erod=True, run_mode_cal=True, sc_qr0=S - 1, out_mask=marshal.MASK_ALL)
         ref, ref_status, _ = cpu_run(oracle_lib, m, n_threads=8)
