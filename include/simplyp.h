@@ -230,7 +230,37 @@ typedef struct {
                                 tables on chains (C4's, the stiff 12-reach one, dry headwaters), a one-level confluence and a
                                 branching 22-reach network (tests/golden/branch_network.npz: 3.2e-7 there, 1.1 x Cash-Karp
                                 alone); other topologies and regimes are not.  -1 is the conservative switch: Cash-Karp alone. */
+    /* ---- forcing uncertainty (simplyp_run / simplyp_run_async only; all zero = off, and the run takes the path it took before
+       these fields existed).  Appended at the end of the struct: a caller COMPILED AGAINST THE SHORTER STRUCT MUST BE REBUILT
+       (the library reads these fields of whatever it is handed); one that memsets sizeof(simplyp_opts) needs no other change.
+       With forcing_error = 1 every member reads a forcing set of its own, made on the device before the pilot and the main
+       launches from the caller's base sets (`forcing`, `forcing_of_member`):
+           z      = the counter-based normal of simplyp_predictive_bands at the counter
+                    (forcing_member0 + e, forcing_group_of_day[r][d], r, SIMPLYP_FORCING_STREAM), key forcing_seed
+           row 0  (P, or Precipitation with opts.snow), row 1 (PET):
+                    v' = (v * scale[e]) * exp(sigma_r * z - 0.5 * sigma_r * sigma_r)      mean-one lognormal multiplier
+           row 2  (T_air, opts.snow only):
+                    v' = (v + offset[e]) + sigma_2 * z
+       evaluated in that order without fused multiply-adds.  sigma_r = 0: no draw, the row is v * scale (v + offset); no
+       forcing_shift either: the base value bit for bit.  A dry day stays exactly 0.  A draw depends on (seed, member id, group id,
+       row) and on nothing else; autocorrelated errors are not offered (no noise state is carried between runs).            */
+    int32_t  forcing_error;             /* 1: on                                                                             */
+    uint32_t forcing_member0;           /* id of the call's member 0 in the stream (a member block of a larger ensemble)     */
+    uint64_t forcing_seed;              /* key of the stream                                                                 */
+    double   forcing_sigma[3];          /* per row, finite and in [0, 2]; [2] > 0 needs opts.snow                            */
+    const int32_t* forcing_group_of_day[3]; /* device [D] each, ids in [0, 2^31): the days of one group share one draw per member
+                                           and row (the day's ordinal: daily errors; year * 12 + month - 1: monthly; a storm id; one
+                                           id: a constant multiplier per member).  Required for a row with sigma > 0        */
+    const double*  forcing_shift;       /* device [forcing_shift_rows][E] in member order -- P scale, PET scale, T_air offset --
+                                           or NULL: no scale, no offset                                                      */
+    int32_t  forcing_shift_rows;        /* rows of forcing_shift: 0 with NULL, else 2 (the scales) or 3 (and the T_air offset:
+                                           needs opts.snow)                                                                  */
+    int32_t  forcing_reserved;          /* 0                                                                                 */
+    double*  forcing_table;             /* device [E][2 or 3][D] fp64, caller-owned workspace the sets are written to (required):
+                                           the layout `forcing` has with n_forcing_sets = E; valid after the run             */
 } simplyp_opts;
+
+#define SIMPLYP_FORCING_STREAM 0x464F5243u   /* "FORC": the fourth word of the counter of a forcing draw */
 
 typedef struct {
     uint64_t rhs_evals;      /* right-hand-side evaluations, all members/reaches/days      */

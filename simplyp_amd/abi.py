@@ -16,6 +16,9 @@ STATE_ROWS = ['VsA', 'VsS', 'Vg', 'Vr', 'Qr', 'Msus', 'TDPr', 'PPr', 'Plab_A', '
               'conc_TDPs_A', 'conc_TDPs_NC', 'h_next', 'D_snow']
 N_STATE = len(STATE_ROWS)
 
+FORCING_STREAM = 0x464F5243                  # SIMPLYP_FORCING_STREAM ("FORC"): the fourth counter word of a forcing draw
+FORCING_ROWS = ['P', 'PET', 'T_air']         # rows of a forcing set ('P' is Precipitation with the in-kernel snow module)
+
 STATUS_NONFINITE = 1
 STATUS_STEPCAP = 2
 
@@ -32,7 +35,16 @@ class Opts(C.Structure):
                 ('step_len', C.c_double), ('project_vr', C.c_int32), ('balance', C.c_int32),
                 ('balance_pilot_days', C.c_int32), ('out_slot_order', C.c_int32),
                 ('time_chunk_days', C.c_int32), ('n_periods', C.c_int32), ('snow', C.c_int32), ('lanes_per_wave', C.c_int32),
-                ('lanes_per_member', C.c_int32), ('stiff_pair', C.c_int32)]
+                ('lanes_per_member', C.c_int32), ('stiff_pair', C.c_int32),
+                # forcing uncertainty (all zero = off); Engine.run(forcing_error=) fills them on a copy of the caller's options
+                ('forcing_error', C.c_int32), ('forcing_member0', C.c_uint32), ('forcing_seed', C.c_uint64),
+                ('forcing_sigma', C.c_double * 3), ('forcing_group_of_day', C.c_void_p * 3), ('forcing_shift', C.c_void_p),
+                ('forcing_shift_rows', C.c_int32), ('forcing_reserved', C.c_int32), ('forcing_table', C.c_void_p)]
+
+    def copy(self):
+        o = Opts()
+        C.memmove(C.byref(o), C.byref(self), C.sizeof(Opts))
+        return o
 
 
 class _Info(C.Structure):

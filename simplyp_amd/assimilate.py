@@ -13,6 +13,7 @@ import numpy as np
 import pandas as pd
 
 from . import abi, engine, ensemble, marshal, particle, request
+from . import forcing as forcing_rules
 from .calibrate import _plan, _host_setup, _check_inside, _shaped_for_the_ensemble
 from .model import _DeviceEnsemble, _state_blocks, _scores_result, _mean_crps
 
@@ -63,8 +64,12 @@ def _window(dev, hs, s, c, t, d_lo, d_hi):
     w0 = time.perf_counter()
     rec = dict(theta_before=_host(s.theta), state_in=_host(s.state)) if c.record else {}
     table_d, status_d, rstats = eng.run(dev.f_d[:, :, d_lo:d_hi].contiguous(), dev.doy_d[d_lo:d_hi].contiguous(), dev.mp_d, dev.rp_d,
-                                        hs['up_ptr'], hs['up_idx'], dev.opts, out_reaches=hs['oreach'], state_in=s.state, state_out=True)
+                                        hs['up_ptr'], hs['up_idx'], dev.opts, out_reaches=hs['oreach'], state_in=s.state, state_out=True,
+                                        forcing_error=forcing_rules.day_window(c.forcing, d_lo, d_hi),
+                                        keep_forcing_table=c.record and c.forcing is not None)
     s.state = rstats['state']
+    if 'forcing_table' in rstats:
+        rec['forcing_table'] = _host(rstats['forcing_table'])
     ms = dict(dict.fromkeys(STEPS + ('score',), 0.0), run=rstats['kernel_ms'])
     win = dict(ms=ms, pilot_ms=rstats['pilot_ms'], rec=rec, n_unique=E, n_outside=0)
     tkw = dict(f_tdp=dev.ft_d, reach_params=dev.rp_d, out_reaches=hs['oreach'])
@@ -131,7 +136,7 @@ def _window(dev, hs, s, c, t, d_lo, d_hi):
 def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, priors, variables=('Q',), error_m=None,
                n_particles=None, window=30, start=None, initial_state=None, seed=0, resample_threshold=1.0, rejuvenate='liu_west',
                delta=0.98, quantiles=None, forecast_series=None, record=False, state=None, step_len=1., solver=None, device=0,
-               out_reaches=None, forecast_weighted=False, score=False):
+               out_reaches=None, forecast_weighted=False, score=False, forcing_error=None):
     """Update the parameter distribution and the model state of ``n_particles`` particles window by window as the observations
     of ``obs_dict`` arrive (sequential importance resampling), every step on the device.
 
@@ -173,6 +178,12 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
     knows (0 for the other series; None when it knows the ``m`` of no scored series, as the ensemble call without
     ``predictive_m``).  ``['scores']`` has the shape of ``run_simply_p_ensemble(score=True)``'s over all days of the
     call, with ``weight_total`` and ``n_members`` one entry per window, and ``kernel_ms`` gains ``'score'``.
+
+    ``forcing_error``: input noise, as ``run_simply_p_ensemble`` takes it (``simplyp_amd.forcing``): every window's run draws each
+    particle's own rainfall, PET and air temperature on the device, keyed on (``seed``, the particle's index, the calendar group
+    id, the forcing row).  Siblings of one ancestor therefore diverge after a resampling through their forcing as well as through
+    the rejuvenation move, and because the group ids are absolute a continuation from ``state`` draws what the one call would.
+    With ``record`` the per-window list ``forcing_table`` [E, 2 or 3, days] is kept.
 
     ``state``: the ``'state'`` of an earlier result; ``met_df`` then covers the dates that follow, and the filter continues bit
     for bit (``start``, ``initial_state`` and ``seed`` are ignored).
@@ -221,6 +232,7 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
     with marshal.reference_edits(p_SU, p_LU, p_SC, p):
         hs = _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables, lo, hi, out_reaches)
         scs = hs['scs']
+        fe = forcing_rules.resolve(forcing_error, met_df.index, E, hs['snow'], seed)
         sc_names, sc_ids, sc_obs = request.observed_series(obs_dict, hs['reaches'], hs['obs']) if score else (None, None, None)
         if state is not None:
             theta0, lw0 = np.array(state['theta'], dtype=np.float64), np.array(state['lw'], dtype=np.float64)
@@ -253,7 +265,7 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
                             resample_threshold=resample_threshold, move=move, record=record, score=score, quantiles=quantiles,
                             forecast_weighted=forecast_weighted, fc_ids=fc_ids, ov_ids=[fc_ids[i] for i in ov_at],
                             ov_vars=[var_of(fc_names[i]) for i in ov_at], sc_ids=sc_ids, sc_obs=sc_obs,
-                            sc_vars=[var_of(c_) for c_ in sc_names or []])
+                            sc_vars=[var_of(c_) for c_ in sc_names or []], forcing=fe)
         wins = [_window(dev, hs, s, c, t0 + n, d_lo, d_hi) for n, (d_lo, d_hi) in enumerate(bounds)]
 
     theta, lw = _host(s.theta), _host(s.lw)
@@ -275,7 +287,8 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
     if score:
         res['scores'] = _joined_scores(sc_names, hs['reaches'], sc_obs, [w['scores'] for w in wins if 'scores' in w], seed, day0)
     if record:
-        res.update({k: [w['rec'][k] for w in wins] for k in ('inc', 'q', 'ancestors', 'theta_before', 'theta_after', 'state_in', 'state_out')})
+        res.update({k: [w['rec'][k] for w in wins] for k in ('inc', 'q', 'ancestors', 'theta_before', 'theta_after', 'state_in', 'state_out')
+                    + (('forcing_table',) if fe is not None else ())})
     return res
 
 

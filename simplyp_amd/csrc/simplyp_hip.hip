@@ -24,6 +24,7 @@
 #include "simplyp_quantile.hip.h"
 #include "simplyp_time_quantile.hip.h"
 #include "simplyp_predictive.hip.h"
+#include "simplyp_forcing.hip.h"
 #include "simplyp_score.hip.h"
 #include "simplyp_pareto.hip.h"
 #include "simplyp_mcmc.hip.h"
@@ -58,6 +59,7 @@ struct simplyp_ctx {
     DeviceBuf counters;       // N_COUNTERS x uint64: rhs, steps, rejected, wave-level attempts, queue waits / longest wait / longest stall
     DeviceBuf balance;        // [E] uint32 pilot counts + [E] int32 permutation
     DeviceBuf sorted_params;  // slot-ordered copies of member_params, reach_params, forcing_of_member
+    DeviceBuf forcing_ident;  // opts.forcing_error: [E] int32 identity member -> set map of the generated table
     DeviceBuf gof_lists;      // goodness-of-fit day lists, observations, shifts (simplyp_gof)
     DeviceBuf gof_partial;    // [n_chunks][R][84][E] partial sums
     DeviceBuf quant;          // simplyp_quantiles: 2 x int32 (members used, sweeps) | [E] uint8 include mask in column order
@@ -497,6 +499,52 @@ int check_args(simplyp_ctx* ctx, const simplyp_dims* dims, const simplyp_opts* o
     if (opts->out_slot_order && !member_of_slot)
         return fail(ctx, SIMPLYP_ERR_ARG, "out_slot_order = 1 needs member_of_slot");
     if (up_ptr[dims->S] > 0 && !up_idx) return fail(ctx, SIMPLYP_ERR_ARG, "up_idx is NULL but up_ptr lists upstream reaches");
+    if (opts->forcing_error) {
+        static const char* const row_name[3] = {"P", "PET", "T_air"};
+        if (!opts->forcing_table)
+            return fail(ctx, SIMPLYP_ERR_ARG, "forcing_error needs forcing_table: the device workspace [E][%d][D] the members' forcing is written to",
+                        opts->snow ? 3 : 2);
+        for (int r = 0; r < 3; ++r) {
+            const double sg = opts->forcing_sigma[r];
+            if (!std::isfinite(sg) || sg < 0.0 || sg > 2.0)
+                return fail(ctx, SIMPLYP_ERR_ARG, "forcing_sigma[%d] (%s) must be finite and in [0, 2] (got %g)", r, row_name[r], sg);
+            if (sg > 0.0 && !opts->forcing_group_of_day[r])
+                return fail(ctx, SIMPLYP_ERR_ARG, "forcing_sigma[%d] (%s) > 0 needs forcing_group_of_day[%d]: the group id of every day", r,
+                            row_name[r], r);
+        }
+        if (opts->forcing_sigma[2] > 0.0 && !opts->snow)
+            return fail(ctx, SIMPLYP_ERR_ARG, "forcing_sigma[2] > 0 perturbs T_air, a forcing row only with the snow module in the kernel (opts.snow = 1)");
+        if (opts->forcing_shift ? (opts->forcing_shift_rows != 2 && opts->forcing_shift_rows != 3) : opts->forcing_shift_rows != 0)
+            return fail(ctx, SIMPLYP_ERR_ARG, "forcing_shift_rows must be 2 or 3 with forcing_shift and 0 without (got %d)", opts->forcing_shift_rows);
+        if ((long long)dims->E * ((dims->D + simplyp::FORCING_THREADS - 1) / simplyp::FORCING_THREADS) > 0x7fffffffLL)
+            return fail(ctx, SIMPLYP_ERR_ARG, "forcing_error: E x ceil(D / %d) must stay below 2^31", simplyp::FORCING_THREADS);
+        if (opts->forcing_shift_rows == 3 && !opts->snow)
+            return fail(ctx, SIMPLYP_ERR_ARG, "a T_air offset (forcing_shift_rows = 3) needs the snow module in the kernel (opts.snow = 1)");
+    }
+    return SIMPLYP_OK;
+}
+
+// opts.forcing_error: writes every member's forcing set into opts.forcing_table and the identity member -> set map into the
+// context's scratch, on the run's stream; `a` then reads the table as E forcing sets.
+int generate_forcing(simplyp_ctx* ctx, const simplyp_opts& opts, simplyp::KernelArgs& a)
+{
+    if (int rc = ensure(ctx, ctx->forcing_ident, (size_t)a.E * sizeof(int32_t))) return rc;
+    simplyp::ForcingErrorArgs g{};
+    g.E = a.E; g.D = a.D; g.rows = opts.snow ? 3 : 2;
+    g.day_blocks = (a.D + simplyp::FORCING_THREADS - 1) / simplyp::FORCING_THREADS;
+    g.base = a.forcing; g.forcing_of_member = a.forcing_of_member;
+    for (int r = 0; r < 3; ++r) {
+        g.sigma[r] = r < g.rows ? opts.forcing_sigma[r] : 0.0;
+        g.group[r] = g.sigma[r] > 0.0 ? opts.forcing_group_of_day[r] : nullptr;
+    }
+    g.shift = opts.forcing_shift; g.shift_rows = opts.forcing_shift ? opts.forcing_shift_rows : 0;
+    g.key0 = (uint32_t)(opts.forcing_seed & 0xffffffffu); g.key1 = (uint32_t)(opts.forcing_seed >> 32);
+    g.member0 = opts.forcing_member0;
+    g.table = opts.forcing_table; g.ident = (int32_t*)ctx->forcing_ident.ptr;
+    const unsigned blocks = (unsigned)a.E * (unsigned)g.day_blocks;       // (check_args: fits the grid)
+    hipLaunchKernelGGL(simplyp::simplyp_forcing_error_kernel, dim3(blocks), dim3(simplyp::FORCING_THREADS), 0, ctx->stream, g);
+    HIP_TRY(ctx, hipGetLastError());
+    a.forcing = opts.forcing_table; a.n_sets = a.E; a.forcing_of_member = g.ident;
     return SIMPLYP_OK;
 }
 
@@ -1022,6 +1070,7 @@ void simplyp_ctx_destroy(simplyp_ctx* ctx)
     if (ctx->counters.ptr) (void)hipFree(ctx->counters.ptr);
     if (ctx->balance.ptr) (void)hipFree(ctx->balance.ptr);
     if (ctx->sorted_params.ptr) (void)hipFree(ctx->sorted_params.ptr);
+    if (ctx->forcing_ident.ptr) (void)hipFree(ctx->forcing_ident.ptr);
     if (ctx->queue.ptr) (void)hipFree(ctx->queue.ptr);
     if (ctx->gof_lists.ptr) (void)hipFree(ctx->gof_lists.ptr);
     if (ctx->gof_partial.ptr) (void)hipFree(ctx->gof_partial.ptr);
@@ -1133,6 +1182,8 @@ static int run_async_body(simplyp_ctx* ctx, const simplyp_dims* dims, const simp
     a.lanes = shape.lanes; a.team_shift = shape.team == 4 ? 2 : 0;
     std::vector<ChainLaunch> launches, pilot;
     if ((rc = upload_schedule(ctx, sch, topo, up_ptr, up_idx, out_reaches, a, launches, pilot)) != SIMPLYP_OK) return rc;
+    // forcing uncertainty: the members' own sets first; the pilot and the main launches then read them like any per-member forcing
+    if (opts->forcing_error && (rc = generate_forcing(ctx, *opts, a)) != SIMPLYP_OK) return rc;
 
     HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
     if (shape.balance && (rc = balance_members(ctx, *opts, shape, sch, pilot, a)) != SIMPLYP_OK) return rc;

@@ -353,7 +353,7 @@ class Engine(object):
 
     def run(self, forcing, doy, member_params, reach_params, up_ptr, up_idx, opts, forcing_of_member=None,
             out_reaches=None, out=None, member_rhs=None, member_of_slot=None, period_of_day=None, host_out=None,
-            defer_sync=False, state_in=None, state_out=None):
+            defer_sync=False, state_in=None, state_out=None, forcing_error=None, keep_forcing_table=False):
         """Integrate every (member, reach) through all days on the device.
 
         forcing [n_sets,2,D] (rows P, PET; [n_sets,3,D] = Precipitation, PET, T_air with ``opts.snow``), doy [D], member_params [NP_M,E], reach_params [NP_R,S,E] may be numpy
@@ -374,7 +374,11 @@ class Engine(object):
         ``abi.STATE_ROWS``, member order) the run starts from instead of the cold initial conditions (numpy or device
         tensor), and a float64 device tensor of that shape that receives the state after the last day (``True`` allocates
         one; the same tensor may serve as both).  The end state comes back as ``stats['state']``; with ``defer_sync`` it is
-        valid after ``finish``.
+        valid after ``finish``.  ``forcing_error``: forcing uncertainty -- the resolved dict of ``simplyp_amd.forcing.resolve``
+        (sigma [3], groups, shift, seed, member0): every member's own forcing set is drawn on the device from ``forcing`` /
+        ``forcing_of_member`` before the run's launches (``simplyp_opts.forcing_*``) into a table [E, rows, D] allocated here,
+        which ``keep_forcing_table=True`` returns as ``stats['forcing_table']`` (``ValueError`` naming its size when it does not
+        fit the device's free memory); ``opts`` itself is left as it is.
         """
         torch = self.torch
         L = lib()
@@ -428,6 +432,9 @@ class Engine(object):
                              % ((S, abi.N_STATE, E), self.tdev))
         if state_out is not None:
             assert state_out.numel() * 8 == L.simplyp_state_bytes(C.byref(dims))
+        fe_keep = None
+        if forcing_error is not None:
+            opts, fe_keep = self._forcing_opts(opts, forcing_error, E, D, two)
         status = torch.empty((E,), dtype=torch.int32, device=self.tdev)
         if opts.out_slot_order and member_of_slot is None:
             member_of_slot = torch.empty((E,), dtype=torch.int32, device=self.tdev)
@@ -460,7 +467,7 @@ class Engine(object):
                 rc = L.simplyp_run(*(args + (C.byref(stats),)))
         self._check(rc, 'simplyp_run')
         if defer_sync:
-            keep = [f, dy, pod, fom, mp, rp, host_out, st_in]          # inputs stay alive until the run is over
+            keep = [f, dy, pod, fom, mp, rp, host_out, st_in, fe_keep, opts]          # inputs stay alive until the run is over
 
             def finish():
                 with torch.cuda.device(self.tdev):
@@ -474,7 +481,36 @@ class Engine(object):
             sd['member_of_slot'] = member_of_slot
         if state_out is not None:
             sd['state'] = state_out
+        if keep_forcing_table and fe_keep is not None:
+            sd['forcing_table'] = fe_keep[0]
         return out, status, sd
+
+    def _forcing_opts(self, opts, fe, E, D, rows):
+        """(a copy of ``opts`` with the forcing_* fields filled from the resolved ``fe``, [table, the device arrays they point at])."""
+        from . import forcing as forcing_rules
+        torch = self.torch
+        forcing_rules.check_resolved(fe, E, D, rows)
+        nbytes = E * rows * D * 8
+        with torch.cuda.device(self.tdev):
+            free = torch.cuda.mem_get_info(self.tdev)[0] + torch.cuda.memory_reserved(self.tdev) - torch.cuda.memory_allocated(self.tdev)
+        if nbytes > free:
+            raise ValueError("forcing_error: the members' forcing table [E = %d, %d, D = %d] takes %d bytes (%.2f GB), the device has "
+                             "%.2f GB free next to the output table -- run fewer members per call, or windows of fewer days"
+                             % (E, rows, D, nbytes, nbytes / 1e9, free / 1e9))
+        table = torch.empty((E, rows, D), dtype=torch.float64, device=self.tdev)
+        groups = [None if g is None else self.to_device(g, torch.int32) for g in fe['groups']]
+        shift = None if fe.get('shift') is None else self.to_device(fe['shift'], torch.float64)
+        o = opts.copy()
+        o.forcing_error = 1
+        o.forcing_member0 = int(fe.get('member0', 0))
+        o.forcing_seed = int(fe.get('seed', 0))
+        for r in range(3):
+            o.forcing_sigma[r] = float(fe['sigma'][r])
+            o.forcing_group_of_day[r] = None if groups[r] is None else groups[r].data_ptr()
+        o.forcing_shift = None if shift is None else shift.data_ptr()
+        o.forcing_shift_rows = 0 if shift is None else int(shift.shape[0])
+        o.forcing_table = table.data_ptr()
+        return o, [table, groups, shift]
 
 
     def eval_units(self, which, rows):

@@ -20,6 +20,7 @@ import numpy as np
 import pandas as pd
 
 from . import abi, engine, ensemble, marshal, request, weighted
+from . import forcing as forcing_rules
 from . import helper_functions as hf, pareto as pareto_rules, score as score_rules, visualise_results as vr
 
 
@@ -483,6 +484,9 @@ def _bind_members(r):
         r.pr_m = request.error_model_rows(r.predictive_m, r.pr_names, E)
     met_sets = list(r.met_df) if isinstance(r.met_df, (list, tuple)) else [r.met_df]
     r.met_df = met_sets[0]
+    if r.snow_in_kernel is None:
+        r.snow_in_kernel = 'f_DDSM' in m_over or 'D_snow_0' in m_over
+    r.forcing_error = forcing_rules.resolve(r.forcing_error, r.met_df.index, E, r.snow_in_kernel, r.forcing_seed)
     if r.devices is None:
         r.bounds = [(0, E)]
     else:
@@ -496,8 +500,6 @@ def _bind_members(r):
     r.rp = marshal.reach_params(r.p_SC, r.p, E, r_over, alloc=r.pin)
     if m_over or r_over:
         marshal.validate_ensemble(r.mp, r.rp, r.scs)       # the reference's checks, for every member (model.py:321-335, :355-357)
-    if r.snow_in_kernel is None:
-        r.snow_in_kernel = 'f_DDSM' in m_over or 'D_snow_0' in m_over
     for m in met_sets:
         if r.snow_in_kernel and not {'Precipitation', 'T_air'} <= set(m.columns):
             raise ValueError("the in-kernel snow module needs met_df columns 'Precipitation' and 'T_air'")
@@ -586,7 +588,8 @@ def _block_pass(r, eng, lo, hi):
     host_out = _host_table(r.table_shape + (hi - lo,), r.pin) if r.want_host_table else None
     out_d, status_d, stats = eng.run(r.forcing, r.doy, mp_b, rp_d, r.up_ptr, r.up_idx, r.opts, out_reaches=r.oreach,
                                      period_of_day=r.period_of_day, forcing_of_member=fom_b, host_out=host_out,
-                                     state_in=st_in, state_out=True if r.return_state else None)
+                                     state_in=st_in, state_out=True if r.return_state else None,
+                                     forcing_error=forcing_rules.member_block(r.forcing_error, lo, hi))
     state_d = stats.pop('state', None)
     part = dict(stats=stats, state=state_d, status=keep(status_d), host_out=host_out, device=eng.device)
     mos = stats.get('member_of_slot') if r.opts.out_slot_order else None
@@ -753,7 +756,7 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
                           quantile_members=None, initial_state=None, return_state=False, time_quantiles=None,
                           time_quantile_series=None, time_quantile_periods=None, predictive_series=None, predictive_m=None,
                           predictive_seed=0, predictive_day0=0, quantile_weights=None, quantile_log_weights=None, score=False,
-                          pareto=None, pareto_max_fronts=0):
+                          pareto=None, pareto_max_fronts=0, forcing_error=None, forcing_seed=0):
     """Run an ensemble of parameter sets through the engine in one call.
 
     ``overrides``: dict name -> array[E] (member parameters, see ``marshal.PM_NAMES``) or
@@ -888,6 +891,23 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     counts stay exact) -- a totally ordered ensemble has E fronts and one host round trip each.  ``sp.pareto_ranks(res['gof'],
     ...)`` gives the same from a table already returned.  ``ValueError`` without ``obs_dict`` and with ``devices=[...]``.
 
+    ``forcing_error``: forcing uncertainty -- every member gets rainfall, PET and air temperature of its own, drawn on the device
+    from the shared sets as part of the run (``simplyp_amd.forcing`` states the error model; nothing per member crosses PCIe)::
+
+        forcing_error={'P':     {'sigma': 0.3, 'groups': 'day' | 'month' | 'year' | int_array[D], 'scale': float | [E]},
+                       'PET':   {'sigma': 0.1, 'groups': ..., 'scale': ...},
+                       'T_air': {'sigma': 0.5, 'groups': ..., 'offset': float | [E]}}      # T_air needs snow_in_kernel=True
+
+    ``sigma`` (in [0, 2]): the standard deviation of a mean-one lognormal multiplier of P and PET, of an additive normal error of
+    T_air; the days of one group share one draw per member (``'day'``, the default: daily errors; ``'month'`` / ``'year'``: one per
+    calendar month / year; an int array of ids in [0, 2^31): storm events, seasons, or a single id for one constant multiplier
+    per member).  ``scale`` / ``offset``: a delta-change ensemble -- each member's precipitation factor and temperature offset.
+    With several forcing sets each member's own set is perturbed.  A draw is a pure function of (``forcing_seed``, member, group
+    id, row): ``devices=[...]`` and ``run_simply_p_ensemble_windows`` give the single call's tables bit for bit.  The table of
+    the members' sets, [E, 2 or 3, D] fp64, lives on the device beside the output table for the length of the call
+    (``ValueError`` naming its size when it does not fit).  ``ValueError`` before any device call for an unknown key, a ``sigma``
+    outside [0, 2], an array of the wrong length, group ids outside [0, 2^31) and ``'T_air'`` without the in-kernel snow module.
+
     ``return_state=True``: the result gains ``'state'`` = dict(rows (``abi.STATE_ROWS``), reaches (all sub-catchments),
     data[S, 16, E], end = ``met_df.index[-1]``): the model state after the last day, in member order (numpy, or a device
     tensor with ``to_host=False``; ``return_state='device'`` keeps it on the device whatever ``to_host`` says -- with
@@ -976,6 +996,8 @@ def run_simply_p_ensemble_windows(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_
     bounds = ensemble.window_bounds(index, window, reduce=reduce)
     if 'return_state' in kwargs:
         raise ValueError("run_simply_p_ensemble_windows always returns the state (on the device)")
+    if kwargs.get('forcing_error') is not None:
+        forcing_rules.cut_group_arrays(kwargs['forcing_error'], len(index), 0, len(index))
 
     def gen():
         state = initial_state
@@ -990,6 +1012,8 @@ def run_simply_p_ensemble_windows(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_
                 kw['time_quantile_periods'] = np.where(part >= 0, part - (part[part >= 0].min() if (part >= 0).any() else 0), -1)
             if kw.get('predictive_series') is not None or kw.get('score'):     # the stream is indexed by the run's day, not the window's
                 kw['predictive_day0'] = int(kwargs.get('predictive_day0', 0)) + lo
+            if kw.get('forcing_error') is not None:                  # group arrays cover the whole run; calendar ids are absolute anyway
+                kw['forcing_error'] = forcing_rules.cut_group_arrays(kw['forcing_error'], len(index), lo, hi)
             mets = [m.iloc[lo:hi] for m in met_sets]
             res = run_simply_p_ensemble(mets if isinstance(met_df, (list, tuple)) else mets[0], p_struc, p_SU, p_LU, p_SC, p,
                                         dynamic_options, initial_state=state, return_state='device', **kw)
