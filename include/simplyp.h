@@ -46,7 +46,10 @@ extern "C" {
  * 17 still with simplyp_scores, simplyp_predictive_scores and simplyp_score_info: two more entry points, one more info struct; the
  * ABI is only extended, no existing struct, enum or entry point changes.
  * 17 still with simplyp_pareto and simplyp_pareto_info: one more entry point, one more info struct, three constants; nothing
- * existing changes. */
+ * existing changes.
+ * 17 still with autocorrelated forcing errors and seasonal change factors: forcing_rho, forcing_noise_in / _out,
+ * forcing_shift_group_of_day and forcing_shift_groups are appended to simplyp_opts after forcing_table (all zero = off), as the
+ * forcing_* fields before them were; no entry point is added and none changes. */
 #define SIMPLYP_ABI_VERSION 17
 
 typedef enum {
@@ -243,7 +246,17 @@ typedef struct {
                     v' = (v + offset[e]) + sigma_2 * z
        evaluated in that order without fused multiply-adds.  sigma_r = 0: no draw, the row is v * scale (v + offset); no
        forcing_shift either: the base value bit for bit.  A dry day stays exactly 0.  A draw depends on (seed, member id, group id,
-       row) and on nothing else; autocorrelated errors are not offered (no noise state is carried between runs).            */
+       row) and on nothing else.
+       Autocorrelated errors (forcing_rho[r] > 0): z of row r is an AR(1) over consecutive groups along the days.  Day d starts
+       a step when its group id differs from the previous day's (for d = 0: from the last group id of forcing_noise_in, none
+       without one); at a step, with eps the draw above at the day's group id,
+           z = eps                                        when there is no previous z: a stationary start
+           z = (forcing_rho[r] * z_prev) + (c * eps)      otherwise, c = sqrt(1 - rho * rho) in fp64
+       each product and the sum rounded; the other days reuse z.  A group id that comes back after other ids is a new step that
+       reuses its eps.  The noise state is a table [6][E] of doubles in member order: rows 0-2 z of P, PET, T_air, rows 3-5 that
+       row's last group id as an exact double, -1.0 = none (a row without rho: 0.0 / -1.0 on output, ignored on input).  A run
+       over D1 + D2 days equals a run over D1 days followed by one over D2 days handed the first one's state, bit for bit,
+       wherever the cut falls.  AR orders above one, correlation between rows and a rho per member are not offered.          */
     int32_t  forcing_error;             /* 1: on                                                                             */
     uint32_t forcing_member0;           /* id of the call's member 0 in the stream (a member block of a larger ensemble)     */
     uint64_t forcing_seed;              /* key of the stream                                                                 */
@@ -258,6 +271,15 @@ typedef struct {
     int32_t  forcing_reserved;          /* 0                                                                                 */
     double*  forcing_table;             /* device [E][2 or 3][D] fp64, caller-owned workspace the sets are written to (required):
                                            the layout `forcing` has with n_forcing_sets = E; valid after the run             */
+    double   forcing_rho[3];            /* per row, finite and in [0, 0.999]: lag-one correlation between consecutive groups;
+                                           > 0 needs forcing_sigma > 0 and forcing_group_of_day of that row                  */
+    const double*  forcing_noise_in;    /* device [6][E] or NULL: stationary start                                           */
+    double*        forcing_noise_out;   /* device [6][E] or NULL; may be the same buffer as forcing_noise_in                 */
+    const int32_t* forcing_shift_group_of_day; /* device [D], ids in [0, forcing_shift_groups) (an id outside reads the nearest
+                                           end), or NULL: seasonal change factors, e.g. month - 1                            */
+    int32_t  forcing_shift_groups;      /* 0: forcing_shift is [rows][E] as before; G in [1, 4096]: [rows][G][E], needs the array
+                                           above                                                                             */
+    int32_t  forcing_reserved2;         /* 0                                                                                 */
 } simplyp_opts;
 
 #define SIMPLYP_FORCING_STREAM 0x464F5243u   /* "FORC": the fourth word of the counter of a forcing draw */

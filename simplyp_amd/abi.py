@@ -18,6 +18,10 @@ N_STATE = len(STATE_ROWS)
 
 FORCING_STREAM = 0x464F5243                  # SIMPLYP_FORCING_STREAM ("FORC"): the fourth counter word of a forcing draw
 FORCING_ROWS = ['P', 'PET', 'T_air']         # rows of a forcing set ('P' is Precipitation with the in-kernel snow module)
+# rows of the forcing noise state [6, E] (simplyp_opts.forcing_noise_in / _out): z of each row, then each row's last group id
+# as an exact float64 (-1.0: none)
+FORCING_NOISE_ROWS = ['z_P', 'z_PET', 'z_T_air', 'group_P', 'group_PET', 'group_T_air']
+FORCING_RHO_MAX, FORCING_SHIFT_GROUPS_MAX = 0.999, 4096
 
 STATUS_NONFINITE = 1
 STATUS_STEPCAP = 2
@@ -39,7 +43,10 @@ class Opts(C.Structure):
                 # forcing uncertainty (all zero = off); Engine.run(forcing_error=) fills them on a copy of the caller's options
                 ('forcing_error', C.c_int32), ('forcing_member0', C.c_uint32), ('forcing_seed', C.c_uint64),
                 ('forcing_sigma', C.c_double * 3), ('forcing_group_of_day', C.c_void_p * 3), ('forcing_shift', C.c_void_p),
-                ('forcing_shift_rows', C.c_int32), ('forcing_reserved', C.c_int32), ('forcing_table', C.c_void_p)]
+                ('forcing_shift_rows', C.c_int32), ('forcing_reserved', C.c_int32), ('forcing_table', C.c_void_p),
+                # autocorrelated errors and seasonal change factors (all zero = off)
+                ('forcing_rho', C.c_double * 3), ('forcing_noise_in', C.c_void_p), ('forcing_noise_out', C.c_void_p),
+                ('forcing_shift_group_of_day', C.c_void_p), ('forcing_shift_groups', C.c_int32), ('forcing_reserved2', C.c_int32)]
 
     def copy(self):
         o = Opts()

@@ -63,11 +63,16 @@ def _window(dev, hs, s, c, t, d_lo, d_hi):
     torch.cuda.synchronize(eng.tdev)
     w0 = time.perf_counter()
     rec = dict(theta_before=_host(s.theta), state_in=_host(s.state)) if c.record else {}
+    if c.record and c.noisy:
+        rec['forcing_noise_in'] = _host(s.noise)
     table_d, status_d, rstats = eng.run(dev.f_d[:, :, d_lo:d_hi].contiguous(), dev.doy_d[d_lo:d_hi].contiguous(), dev.mp_d, dev.rp_d,
                                         hs['up_ptr'], hs['up_idx'], dev.opts, out_reaches=hs['oreach'], state_in=s.state, state_out=True,
                                         forcing_error=forcing_rules.day_window(c.forcing, d_lo, d_hi),
-                                        keep_forcing_table=c.record and c.forcing is not None)
-    s.state = rstats['state']
+                                        keep_forcing_table=c.record and c.forcing is not None,
+                                        forcing_noise_in=s.noise, forcing_noise_out=True if c.noisy else None)
+    s.state, s.noise = rstats['state'], rstats.get('forcing_noise')
+    if c.record and c.noisy:
+        rec['forcing_noise_out'] = _host(s.noise)
     if 'forcing_table' in rstats:
         rec['forcing_table'] = _host(rstats['forcing_table'])
     ms = dict(dict.fromkeys(STEPS + ('score',), 0.0), run=rstats['kernel_ms'])
@@ -108,7 +113,8 @@ def _window(dev, hs, s, c, t, d_lo, d_hi):
     if win['resampled']:
         anc_d, _, rinfo = eng.pf_resample(s.q, c.seed, t, offspring=False)
         ms['resample'], win['n_unique'] = rinfo['kernel_ms'], int(rinfo['n_unique'])
-        for owner, key in ((s, 'state'), (dev, 'mp_d'), (dev, 'rp_d'), (dev, 'ft_d'), (s, 'theta')):   # all a particle owns travels with it
+        for owner, key in ((s, 'state'), (dev, 'mp_d'), (dev, 'rp_d'), (dev, 'ft_d'), (s, 'theta')) + (((s, 'noise'),) if c.noisy else ()):
+            # all a particle owns travels with it, the noise state of its forcing errors included
             dst, ginfo = eng.gather_members(getattr(owner, key), anc_d)
             setattr(owner, key, dst)
             ms['gather'] += ginfo['kernel_ms']
@@ -183,7 +189,12 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
     particle's own rainfall, PET and air temperature on the device, keyed on (``seed``, the particle's index, the calendar group
     id, the forcing row).  Siblings of one ancestor therefore diverge after a resampling through their forcing as well as through
     the rejuvenation move, and because the group ids are absolute a continuation from ``state`` draws what the one call would.
-    With ``record`` the per-window list ``forcing_table`` [E, 2 or 3, days] is kept.
+    With ``record`` the per-window list ``forcing_table`` [E, 2 or 3, days] is kept.  With a ``rho`` (autocorrelated errors) the
+    noise state [6, n_particles] (``abi.FORCING_NOISE_ROWS``) is something a particle owns: it starts stationary or comes from
+    ``state``, goes into and out of every window's run, is gathered with the ancestors on resampling and returned as
+    ``['state']['forcing_noise']``; ``record`` keeps ``forcing_noise_in`` (None for a stationary start) and ``forcing_noise_out``
+    (after the window's run, before its resampling) per window.  After a resampling two offspring of one ancestor share
+    ``z_prev`` and then draw their own ``eps``, because the member id of a draw is the particle's slot.
 
     ``state``: the ``'state'`` of an earlier result; ``met_df`` then covers the dates that follow, and the filter continues bit
     for bit (``start``, ``initial_state`` and ``seed`` are ignored).
@@ -246,6 +257,10 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
             if theta0.shape != (n_dim, E):
                 raise ValueError("start must have shape [n_dim, n_particles] = %s, got %s" % ((n_dim, E), theta0.shape))
             st_in = None if initial_state is None else _state_blocks(initial_state, scs, E, met_df.index, [(0, E)])[0]
+        noisy = forcing_rules.any_rho(fe)
+        nz_in = None
+        if noisy and state is not None and state.get('forcing_noise') is not None:
+            nz_in = forcing_rules.check_noise(_host(state['forcing_noise']) if hasattr(state['forcing_noise'], 'cpu') else state['forcing_noise'], E)
         _check_inside(theta0, lo, hi, names)
         if t0 + len(bounds) >= 1 << 32 or day0 + len(met_df) >= 1 << 31:
             raise ValueError("the absolute window index must stay below 2^32 and the absolute day below 2^31")
@@ -255,7 +270,8 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
                               solver, device, E, marshal.FLUX_COLUMNS, hs['snow'])
         eng, torch = dev.eng, dev.torch
         s = SimpleNamespace(theta=eng.to_device(theta0, torch.float64), lw=eng.to_device(lw0, torch.float64),
-                            inc=torch.empty((E,), **dev.f64), state=None if st_in is None else eng.to_device(st_in, torch.float64).clone())
+                            inc=torch.empty((E,), **dev.f64), state=None if st_in is None else eng.to_device(st_in, torch.float64).clone(),
+                            noise=None if nz_in is None else eng.to_device(nz_in, torch.float64).clone())
         dev.write_positions(s.theta, target)
         s.w, s.q, info = eng.pf_weights(s.lw)
         s.lm_prev = particle.log_mean(info['lw_max'], info['sum_w'], E)
@@ -265,7 +281,7 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
                             resample_threshold=resample_threshold, move=move, record=record, score=score, quantiles=quantiles,
                             forecast_weighted=forecast_weighted, fc_ids=fc_ids, ov_ids=[fc_ids[i] for i in ov_at],
                             ov_vars=[var_of(fc_names[i]) for i in ov_at], sc_ids=sc_ids, sc_obs=sc_obs,
-                            sc_vars=[var_of(c_) for c_ in sc_names or []], forcing=fe)
+                            sc_vars=[var_of(c_) for c_ in sc_names or []], forcing=fe, noisy=noisy)
         wins = [_window(dev, hs, s, c, t0 + n, d_lo, d_hi) for n, (d_lo, d_hi) in enumerate(bounds)]
 
     theta, lw = _host(s.theta), _host(s.lw)
@@ -278,6 +294,8 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
                theta=theta, log_weights=lw, overrides=overrides, error_m=err_m,
                state=dict(rows=list(abi.STATE_ROWS), reaches=list(scs), data=_host(s.state), end=pd.Timestamp(met_df.index[-1]),
                           theta=theta.copy(), lw=lw.copy(), t=t0 + len(bounds), seed=seed, day=day0 + len(met_df)))
+    if noisy:
+        res['state']['forcing_noise'] = _host(s.noise)
     if quantiles is not None:
         res['forecast'] = dict(q=list(quantiles), series=list(fc_names), param_only=np.concatenate([w['band_po'] for w in wins], axis=2),
                                overall_series=[fc_names[i] for i in ov_at],
@@ -288,7 +306,7 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
         res['scores'] = _joined_scores(sc_names, hs['reaches'], sc_obs, [w['scores'] for w in wins if 'scores' in w], seed, day0)
     if record:
         res.update({k: [w['rec'][k] for w in wins] for k in ('inc', 'q', 'ancestors', 'theta_before', 'theta_after', 'state_in', 'state_out')
-                    + (('forcing_table',) if fe is not None else ())})
+                    + (('forcing_table',) if fe is not None else ()) + (('forcing_noise_in', 'forcing_noise_out') if noisy else ())})
     return res
 
 

@@ -520,6 +520,32 @@ int check_args(simplyp_ctx* ctx, const simplyp_dims* dims, const simplyp_opts* o
             return fail(ctx, SIMPLYP_ERR_ARG, "forcing_error: E x ceil(D / %d) must stay below 2^31", simplyp::FORCING_THREADS);
         if (opts->forcing_shift_rows == 3 && !opts->snow)
             return fail(ctx, SIMPLYP_ERR_ARG, "a T_air offset (forcing_shift_rows = 3) needs the snow module in the kernel (opts.snow = 1)");
+        bool any_rho = false;
+        for (int r = 0; r < 3; ++r) {
+            const double rho = opts->forcing_rho[r];
+            if (!std::isfinite(rho) || rho < 0.0 || rho > 0.999)
+                return fail(ctx, SIMPLYP_ERR_ARG, "forcing_rho[%d] (%s) must be finite and in [0, 0.999] (got %g)", r, row_name[r], rho);
+            if (rho > 0.0 && !(opts->forcing_sigma[r] > 0.0))
+                return fail(ctx, SIMPLYP_ERR_ARG, "forcing_rho[%d] (%s) > 0 needs forcing_sigma[%d] > 0: there is no error to correlate", r,
+                            row_name[r], r);
+            any_rho = any_rho || rho > 0.0;
+        }
+        if (!any_rho && (opts->forcing_noise_in || opts->forcing_noise_out))
+            return fail(ctx, SIMPLYP_ERR_ARG, "forcing_noise_in / forcing_noise_out need some forcing_rho > 0: without one no noise state exists");
+        if (any_rho && (long long)dims->E * (opts->snow ? 3 : 2) > 0x7fffffffLL)
+            return fail(ctx, SIMPLYP_ERR_ARG, "forcing_rho: E x rows must stay below 2^31");
+        const int G = opts->forcing_shift_groups;
+        if (G < 0 || G > 4096)
+            return fail(ctx, SIMPLYP_ERR_ARG, "forcing_shift_groups must be 0 or in [1, 4096] (got %d)", G);
+        if (G >= 1 && (!opts->forcing_shift_group_of_day || !opts->forcing_shift))
+            return fail(ctx, SIMPLYP_ERR_ARG, "forcing_shift_groups = %d needs forcing_shift_group_of_day and forcing_shift [rows][%d][E]", G, G);
+        if (G == 0 && opts->forcing_shift_group_of_day)
+            return fail(ctx, SIMPLYP_ERR_ARG, "forcing_shift_group_of_day needs forcing_shift_groups >= 1: the number of shift groups");
+        if (opts->forcing_reserved2)
+            return fail(ctx, SIMPLYP_ERR_ARG, "forcing_reserved2 must be 0");
+    } else if (opts->forcing_rho[0] != 0.0 || opts->forcing_rho[1] != 0.0 || opts->forcing_rho[2] != 0.0 || opts->forcing_noise_in ||
+               opts->forcing_noise_out || opts->forcing_shift_group_of_day || opts->forcing_shift_groups) {
+        return fail(ctx, SIMPLYP_ERR_ARG, "forcing_rho, forcing_noise_in / _out, forcing_shift_group_of_day and forcing_shift_groups need forcing_error = 1");
     }
     return SIMPLYP_OK;
 }
@@ -538,11 +564,25 @@ int generate_forcing(simplyp_ctx* ctx, const simplyp_opts& opts, simplyp::Kernel
         g.group[r] = g.sigma[r] > 0.0 ? opts.forcing_group_of_day[r] : nullptr;
     }
     g.shift = opts.forcing_shift; g.shift_rows = opts.forcing_shift ? opts.forcing_shift_rows : 0;
+    g.shift_groups = opts.forcing_shift_groups; g.shift_group = opts.forcing_shift_group_of_day;
+    bool ar1 = false;
+    for (int r = 0; r < g.rows; ++r) {
+        g.rho[r] = opts.forcing_rho[r];
+        g.c[r] = std::sqrt(1.0 - g.rho[r] * g.rho[r]);
+        ar1 = ar1 || g.rho[r] > 0.0;
+    }
+    g.noise_in = opts.forcing_noise_in; g.noise_out = opts.forcing_noise_out;
     g.key0 = (uint32_t)(opts.forcing_seed & 0xffffffffu); g.key1 = (uint32_t)(opts.forcing_seed >> 32);
     g.member0 = opts.forcing_member0;
     g.table = opts.forcing_table; g.ident = (int32_t*)ctx->forcing_ident.ptr;
-    const unsigned blocks = (unsigned)a.E * (unsigned)g.day_blocks;       // (check_args: fits the grid)
-    hipLaunchKernelGGL(simplyp::simplyp_forcing_error_kernel, dim3(blocks), dim3(simplyp::FORCING_THREADS), 0, ctx->stream, g);
+    if (ar1) {                                                            // one wave per (member, row)
+        const long long waves = (long long)a.E * g.rows;                  // (check_args: below 2^31)
+        const unsigned blocks = (unsigned)((waves + simplyp::FORCING_AR1_WAVES - 1) / simplyp::FORCING_AR1_WAVES);
+        hipLaunchKernelGGL(simplyp::simplyp_forcing_ar1_kernel, dim3(blocks), dim3(simplyp::FORCING_THREADS), 0, ctx->stream, g);
+    } else {
+        const unsigned blocks = (unsigned)a.E * (unsigned)g.day_blocks;   // (check_args: fits the grid)
+        hipLaunchKernelGGL(simplyp::simplyp_forcing_error_kernel, dim3(blocks), dim3(simplyp::FORCING_THREADS), 0, ctx->stream, g);
+    }
     HIP_TRY(ctx, hipGetLastError());
     a.forcing = opts.forcing_table; a.n_sets = a.E; a.forcing_of_member = g.ident;
     return SIMPLYP_OK;

@@ -353,7 +353,8 @@ class Engine(object):
 
     def run(self, forcing, doy, member_params, reach_params, up_ptr, up_idx, opts, forcing_of_member=None,
             out_reaches=None, out=None, member_rhs=None, member_of_slot=None, period_of_day=None, host_out=None,
-            defer_sync=False, state_in=None, state_out=None, forcing_error=None, keep_forcing_table=False):
+            defer_sync=False, state_in=None, state_out=None, forcing_error=None, keep_forcing_table=False,
+            forcing_noise_in=None, forcing_noise_out=None):
         """Integrate every (member, reach) through all days on the device.
 
         forcing [n_sets,2,D] (rows P, PET; [n_sets,3,D] = Precipitation, PET, T_air with ``opts.snow``), doy [D], member_params [NP_M,E], reach_params [NP_R,S,E] may be numpy
@@ -378,7 +379,11 @@ class Engine(object):
         (sigma [3], groups, shift, seed, member0): every member's own forcing set is drawn on the device from ``forcing`` /
         ``forcing_of_member`` before the run's launches (``simplyp_opts.forcing_*``) into a table [E, rows, D] allocated here,
         which ``keep_forcing_table=True`` returns as ``stats['forcing_table']`` (``ValueError`` naming its size when it does not
-        fit the device's free memory); ``opts`` itself is left as it is.
+        fit the device's free memory); ``opts`` itself is left as it is.  ``forcing_noise_in`` / ``forcing_noise_out`` (need a
+        ``forcing_error`` with some ``rho > 0``): the noise state ``[6, E]`` (``abi.FORCING_NOISE_ROWS``, member order) the
+        autocorrelated rows continue instead of a stationary start (numpy or device tensor), and a float64 device tensor of that
+        shape that receives the state after the last day (``True`` allocates one; the same tensor may serve as both).  It comes
+        back as ``stats['forcing_noise']``; with ``defer_sync`` it is valid after ``finish``.
         """
         torch = self.torch
         L = lib()
@@ -433,8 +438,13 @@ class Engine(object):
         if state_out is not None:
             assert state_out.numel() * 8 == L.simplyp_state_bytes(C.byref(dims))
         fe_keep = None
+        if forcing_noise_out is False:
+            forcing_noise_out = None
         if forcing_error is not None:
-            opts, fe_keep = self._forcing_opts(opts, forcing_error, E, D, two)
+            opts, fe_keep = self._forcing_opts(opts, forcing_error, E, D, two, forcing_noise_in, forcing_noise_out)
+            forcing_noise_out = fe_keep[4]
+        elif forcing_noise_in is not None or forcing_noise_out is not None:
+            raise ValueError("forcing_noise_in / forcing_noise_out need forcing_error with some rho > 0")
         status = torch.empty((E,), dtype=torch.int32, device=self.tdev)
         if opts.out_slot_order and member_of_slot is None:
             member_of_slot = torch.empty((E,), dtype=torch.int32, device=self.tdev)
@@ -483,13 +493,28 @@ class Engine(object):
             sd['state'] = state_out
         if keep_forcing_table and fe_keep is not None:
             sd['forcing_table'] = fe_keep[0]
+        if forcing_noise_out is not None:
+            sd['forcing_noise'] = forcing_noise_out
         return out, status, sd
 
-    def _forcing_opts(self, opts, fe, E, D, rows):
-        """(a copy of ``opts`` with the forcing_* fields filled from the resolved ``fe``, [table, the device arrays they point at])."""
+    def _forcing_opts(self, opts, fe, E, D, rows, noise_in=None, noise_out=None):
+        """(a copy of ``opts`` with the forcing_* fields filled from the resolved ``fe`` and the noise state, [table, the device
+        arrays they point at: groups, shift, noise in, noise out, shift groups])."""
         from . import forcing as forcing_rules
         torch = self.torch
         forcing_rules.check_resolved(fe, E, D, rows)
+        n_noise = len(abi.FORCING_NOISE_ROWS)
+        if (noise_in is not None or noise_out is not None) and not forcing_rules.any_rho(fe):
+            raise ValueError("forcing_noise_in / forcing_noise_out need forcing_error with some rho > 0")
+        if noise_in is not None:
+            if not (torch.is_tensor(noise_in) and noise_in.device == self.tdev and noise_in.dtype == torch.float64 and noise_in.is_contiguous()):
+                noise_in = self.to_device(noise_in, torch.float64)
+            if tuple(noise_in.shape) != (n_noise, E):
+                raise ValueError("forcing_noise_in must have shape %s, got %s" % ((n_noise, E), tuple(noise_in.shape)))
+        if noise_out is not None and noise_out is not True and (
+                not torch.is_tensor(noise_out) or tuple(noise_out.shape) != (n_noise, E) or noise_out.dtype != torch.float64
+                or not noise_out.is_contiguous() or noise_out.device != self.tdev):
+            raise ValueError("forcing_noise_out must be True or a contiguous float64 tensor of shape %s on %s" % ((n_noise, E), self.tdev))
         nbytes = E * rows * D * 8
         with torch.cuda.device(self.tdev):
             free = torch.cuda.mem_get_info(self.tdev)[0] + torch.cuda.memory_reserved(self.tdev) - torch.cuda.memory_allocated(self.tdev)
@@ -498,8 +523,11 @@ class Engine(object):
                              "%.2f GB free next to the output table -- run fewer members per call, or windows of fewer days"
                              % (E, rows, D, nbytes, nbytes / 1e9, free / 1e9))
         table = torch.empty((E, rows, D), dtype=torch.float64, device=self.tdev)
+        if noise_out is True:
+            noise_out = torch.empty((n_noise, E), dtype=torch.float64, device=self.tdev)
         groups = [None if g is None else self.to_device(g, torch.int32) for g in fe['groups']]
         shift = None if fe.get('shift') is None else self.to_device(fe['shift'], torch.float64)
+        sgroups = None if fe.get('shift_groups') is None else self.to_device(fe['shift_groups'], torch.int32)
         o = opts.copy()
         o.forcing_error = 1
         o.forcing_member0 = int(fe.get('member0', 0))
@@ -510,7 +538,13 @@ class Engine(object):
         o.forcing_shift = None if shift is None else shift.data_ptr()
         o.forcing_shift_rows = 0 if shift is None else int(shift.shape[0])
         o.forcing_table = table.data_ptr()
-        return o, [table, groups, shift]
+        for r in range(3):
+            o.forcing_rho[r] = 0.0 if fe.get('rho') is None else float(fe['rho'][r])
+        o.forcing_noise_in = None if noise_in is None else noise_in.data_ptr()
+        o.forcing_noise_out = None if noise_out is None else noise_out.data_ptr()
+        o.forcing_shift_group_of_day = None if sgroups is None else sgroups.data_ptr()
+        o.forcing_shift_groups = 0 if sgroups is None else int(shift.shape[1])
+        return o, [table, groups, shift, noise_in, noise_out, sgroups]
 
 
     def eval_units(self, which, rows):

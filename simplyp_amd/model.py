@@ -228,6 +228,27 @@ def _state_blocks(initial_state, scs, E, index, bounds):
     return [data[..., lo:hi] for lo, hi in bounds]
 
 
+def _noise_blocks(initial_state, E, bounds):
+    """The forcing noise state an ``initial_state`` dict carries under ``'forcing_noise'`` ([6, E], or a list of per-block
+    tensors split as ``bounds``) as one table per member block of ``bounds``; None -- a stationary start -- for a dict without
+    it, a bare array or None.  Host only."""
+    noise = initial_state.get('forcing_noise') if isinstance(initial_state, dict) else None
+    if noise is None:
+        return None
+    n = len(abi.FORCING_NOISE_ROWS)
+    if isinstance(noise, (list, tuple)):
+        blocks = list(noise)
+        if len(blocks) != len(bounds) or any(tuple(b.shape) != (n, hi - lo) for b, (lo, hi) in zip(blocks, bounds)):
+            raise ValueError("initial_state['forcing_noise'] blocks %s do not match [%d, members of each device block %s]"
+                             % ([tuple(b.shape) for b in blocks], n, [hi - lo for lo, hi in bounds]))
+        return blocks
+    if tuple(noise.shape) != (n, E):
+        raise ValueError("initial_state['forcing_noise'] must have shape [%d, E] = %s, got %s" % (n, (n, E), tuple(noise.shape)))
+    if len(bounds) == 1:
+        return [noise]
+    return [noise[:, lo:hi] for lo, hi in bounds]
+
+
 def run_simply_p(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, step_len=1., solver=None, device=0,
                  initial_state=None, return_state=False):
     """Simple hydrology, sediment and phosphorus model (reference model.py:193-827).
@@ -494,6 +515,8 @@ def _bind_members(r):
             raise ValueError("devices must name at least one GPU")
         r.bounds = [b_ for b_ in (ensemble.shard_bounds(E, len(r.devices), k) for k in range(len(r.devices))) if b_[1] > b_[0]]
     r.state_blocks = None if r.initial_state is None else _state_blocks(r.initial_state, r.scs, E, r.met_df.index, r.bounds)
+    r.noisy = forcing_rules.any_rho(r.forcing_error)             # autocorrelated forcing errors: a noise state travels with the model's
+    r.noise_blocks = _noise_blocks(r.initial_state, E, r.bounds) if r.noisy else None
     # the SoA arrays are marshalled straight into page-locked host memory: the uploads are asynchronous DMA transfers
     r.pin = engine.pinned_empty
     r.mp = marshal.member_params(r.p, r.p_LU, E, m_over, alloc=r.pin)
@@ -578,6 +601,10 @@ def _block_pass(r, eng, lo, hi):
     if r.state_blocks is not None:
         st_in = r.state_blocks[r.bounds.index((lo, hi))]
         st_in = st_in.contiguous() if hasattr(st_in, 'contiguous') else np.ascontiguousarray(st_in, dtype=np.float64)
+    nz_in = None
+    if r.noise_blocks is not None:
+        nz_in = r.noise_blocks[r.bounds.index((lo, hi))]
+        nz_in = nz_in.contiguous() if hasattr(nz_in, 'contiguous') else np.ascontiguousarray(nz_in, dtype=np.float64)
     mp_b = r.mp if whole else np.ascontiguousarray(r.mp[:, lo:hi])
     rp_b = r.rp if whole else np.ascontiguousarray(r.rp[:, :, lo:hi])
     fom_b = None if r.forcing_of_member is None else np.ascontiguousarray(r.forcing_of_member[lo:hi])
@@ -589,9 +616,11 @@ def _block_pass(r, eng, lo, hi):
     out_d, status_d, stats = eng.run(r.forcing, r.doy, mp_b, rp_d, r.up_ptr, r.up_idx, r.opts, out_reaches=r.oreach,
                                      period_of_day=r.period_of_day, forcing_of_member=fom_b, host_out=host_out,
                                      state_in=st_in, state_out=True if r.return_state else None,
-                                     forcing_error=forcing_rules.member_block(r.forcing_error, lo, hi))
+                                     forcing_error=forcing_rules.member_block(r.forcing_error, lo, hi),
+                                     forcing_noise_in=nz_in, forcing_noise_out=True if r.return_state and r.noisy else None)
     state_d = stats.pop('state', None)
-    part = dict(stats=stats, state=state_d, status=keep(status_d), host_out=host_out, device=eng.device)
+    part = dict(stats=stats, state=state_d, status=keep(status_d), host_out=host_out, device=eng.device,
+                noise=stats.pop('forcing_noise', None))
     mos = stats.get('member_of_slot') if r.opts.out_slot_order else None
     tkw = dict(f_tdp=ft, reach_params=rp_d, out_reaches=r.oreach, member_of_slot=mos)       # how a reduction reads the table
     if r.obs is not None:
@@ -733,6 +762,14 @@ def _assemble(r, parts):
         else:
             sdata = cat(sts)
         res['state'] = dict(rows=list(abi.STATE_ROWS), reaches=list(r.scs), data=sdata, end=r.met_df.index[-1])
+        if r.noisy:                                  # the forcing noise state, delivered as the model state is
+            nzs = [pt['noise'] for pt in parts]
+            if r.return_state == 'device':
+                res['state']['forcing_noise'] = nzs[0] if len(nzs) == 1 else nzs
+            elif to_host:
+                res['state']['forcing_noise'] = np.concatenate([t.cpu().numpy() for t in nzs], axis=-1)
+            else:
+                res['state']['forcing_noise'] = cat(nzs)
     if r.reduced_on_device and not r.keep_daily:
         res['data'] = None
     elif not to_host:
@@ -907,6 +944,15 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     the members' sets, [E, 2 or 3, D] fp64, lives on the device beside the output table for the length of the call
     (``ValueError`` naming its size when it does not fit).  ``ValueError`` before any device call for an unknown key, a ``sigma``
     outside [0, 2], an array of the wrong length, group ids outside [0, 2^31) and ``'T_air'`` without the in-kernel snow module.
+    ``'rho'`` (in [0, 0.999], needs ``sigma > 0``): autocorrelated errors -- the lag-one correlation of a row's normal between
+    consecutive groups along the days (AR(1), stationary at the start; ``simplyp_amd.forcing`` defines it).  The noise state
+    ``[6, E]`` (``abi.FORCING_NOISE_ROWS``) then travels with the model state: with ``return_state`` the result's ``'state'``
+    gains ``'forcing_noise'`` (delivered as ``data`` is; per block under ``devices=[...]`` with ``'device'``), and an
+    ``initial_state`` dict that carries it continues the noise -- a dict without it, or a bare array, is a stationary start --, so
+    windows laid end to end still give the one call's tables bit for bit, wherever they cut a month.  Without a ``rho`` no key is
+    added.  ``'scale_groups'`` (``'offset_groups'`` of T_air) = ``'month_of_year'`` | int array [D] of ids in [0, G), G <= 4096:
+    seasonal change factors -- ``scale`` / ``offset`` is then [G, E] or [G], one entry per shift group (12 calendar months:
+    wetter winters, drier summers); the rows share one array of shift groups.
 
     ``return_state=True``: the result gains ``'state'`` = dict(rows (``abi.STATE_ROWS``), reaches (all sub-catchments),
     data[S, 16, E], end = ``met_df.index[-1]``): the model state after the last day, in member order (numpy, or a device

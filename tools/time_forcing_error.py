@@ -5,6 +5,8 @@ Three device-resident timings with torch events, one warm-up and three repeats e
   2. the same run handed the kept table explicitly as E forcing sets: (1) - (2) is the generator;
   3. the shared-forcing run of today: (2) - (3) is what per-member forcing reads cost the main kernel.
 Prints one JSON line; ``--md FILE`` also writes the figures as a table.  ``--members`` / ``--days`` shrink the problem.
+``--rho`` makes the errors of P autocorrelated (the AR(1) generator kernel instead of the independent one), ``--groups`` picks
+``'day'`` | ``'month'`` | ``'year'`` groups.
 """
 
 import argparse
@@ -23,6 +25,8 @@ def main():
     ap.add_argument('--members', type=int, default=100000)
     ap.add_argument('--days', type=int, default=0, help='0 = all 10 957')
     ap.add_argument('--sigma', type=float, default=0.3)
+    ap.add_argument('--rho', type=float, default=0.0, help='lag-one correlation of the P errors; > 0: the AR(1) generator')
+    ap.add_argument('--groups', default='day', choices=['day', 'month', 'year'])
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--md', default=None)
     args = ap.parse_args()
@@ -35,7 +39,7 @@ def main():
         pr['forcing'], pr['doy'], pr['met'] = pr['forcing'][:, :, :args.days].copy(), pr['doy'][:args.days].copy(), pr['met'].iloc[:args.days]
     D = pr['forcing'].shape[2]
     eng = engine.get_engine(0)
-    fe = forcing.resolve({'P': {'sigma': args.sigma}}, pr['met'].index, E, False, seed=1)
+    fe = forcing.resolve({'P': {'sigma': args.sigma, 'rho': args.rho, 'groups': args.groups}}, pr['met'].index, E, False, seed=1)
     dev = {k: eng.to_device(pr[k]) for k in ('forcing', 'doy', 'member_params', 'reach_params')}
     out = torch.empty((5, D, 1, E), dtype=torch.float64, device=eng.tdev)
     mos = torch.empty((E,), dtype=torch.int32, device=eng.tdev)
@@ -67,7 +71,7 @@ def main():
         ms3, st3 = timed(lambda: one(dev['forcing']))
     table_bytes = E * 2 * D * 8
     gen_ms = float(np.median(ms1) - np.median(ms2))
-    res = dict(members=E, days=D, sigma_P=args.sigma, table_bytes=table_bytes,
+    res = dict(members=E, days=D, sigma_P=args.sigma, rho_P=args.rho, groups=args.groups, table_bytes=table_bytes,
                with_forcing_error_ms=ms1, explicit_table_ms=ms2, shared_forcing_ms=ms3,
                kernel_ms=[st1['kernel_ms'], st2['kernel_ms'], st3['kernel_ms']], pilot_ms=[st1['pilot_ms'], st2['pilot_ms'], st3['pilot_ms']],
                rhs_per_member_day=[st['rhs_evals'] / float(E * D) for st in (st1, st2, st3)],
@@ -78,8 +82,8 @@ def main():
     if args.md:
         med = lambda x: float(np.median(x))
         with open(args.md, 'w') as fh:
-            fh.write("| run (%d members x %d days, sigma_P = %g, daily groups) | median ms | repeats ms | main launch ms | pilot ms |\n|---|---|---|---|---|\n"
-                     % (E, D, args.sigma))
+            fh.write("| run (%d members x %d days, sigma_P = %g, rho_P = %g, %s groups) | median ms | repeats ms | main launch ms | pilot ms |\n|---|---|---|---|---|\n"
+                     % (E, D, args.sigma, args.rho, args.groups))
             for name, ms, k in (('1. forcing_error', ms1, 0), ('2. kept table given explicitly', ms2, 1), ('3. shared forcing', ms3, 2)):
                 fh.write("| %s | %.1f | %s | %.1f | %.1f |\n" % (name, med(ms), ', '.join('%.1f' % x for x in ms), res['kernel_ms'][k], res['pilot_ms'][k]))
             fh.write("\nRight-hand sides per member-day: %s; SIMT efficiency: %s.\n"
