@@ -429,8 +429,9 @@ int simplyp_stream_out(simplyp_ctx* ctx, double* host_out, int64_t host_bytes);
  * send each (time chunk, column) as one packed record in which every row of a block (64 members, one day) is stored at the bit
  * width of its widest difference: the wave that computed a task packs its own rows before it releases the task, the copier
  * sends the record into a pinned staging ring, and a pool of host threads decodes it into `host_out` with non-temporal stores.
- * SIMPLYP_OUT_PP_FLUX is coded against Msus[d] * (PP[d-1] / Msus[d-1]) instead of the previous day when SIMPLYP_OUT_MSUS_FLUX
- * is in the table too.  A block with a difference of more than 56 bits counts as an overflow block (it simply has wide rows); a
+ * SIMPLYP_OUT_PP_FLUX is coded against Msus[d] * (PP[d-1] / Msus[d-1]), or against Msus[d] times that ratio extrapolated from
+ * the two days before, whichever makes a span of 64 rows of a block smaller, instead of the previous day when
+ * SIMPLYP_OUT_MSUS_FLUX is in the table too.  A block with a difference of more than 56 bits counts as an overflow block (it simply has wide rows); a
  * record with more of them than an eighth of its blocks plus three, or whose body outgrows 7 bytes per value, travels as raw
  * fp64.  The result is bit for bit the table of the raw stream; the device table is untouched.  simplyp_sync returns after the
  * pool has drained, on every path.
@@ -448,7 +449,7 @@ int simplyp_stream_out(simplyp_ctx* ctx, double* host_out, int64_t host_bytes);
  *
  * simplyp_fetch_packed_pred, simplyp_pack_roundtrip_host_pred -- the same two with a predictor per column and the bytes:
  * pred_col (host, [n_cols], NULL = all -1): -1 = a column is coded against its previous day, k < the column's own index = against
- * X[d] * (Y[d-1] / X[d-1]) with X = column k.  bytes (host, may be NULL): [0] bytes of all packed records as they cross the link,
+ * X[d] * r[d-1] or X[d] * (2 r[d-1] - r[d-2]) with r = Y / X and X = column k, chosen per block and span (simplyp_pack.h).  bytes (host, may be NULL): [0] bytes of all packed records as they cross the link,
  * [1] bytes of their raw first rows.
  */
 int simplyp_fetch_packed(simplyp_ctx* ctx, const double* dev_table, int32_t n_cols, int32_t rows, int32_t row_doubles,

@@ -22,6 +22,7 @@
 #include "simplyp_gof.hip.h"
 #include "simplyp_waterbody.hip.h"
 #include "simplyp_quantile.hip.h"
+#include "simplyp_order.hip.h"
 #include "simplyp_time_quantile.hip.h"
 #include "simplyp_predictive.hip.h"
 #include "simplyp_forcing.hip.h"
@@ -399,6 +400,60 @@ void order_members(const std::vector<uint32_t>& cost, int n_win, int E, std::vec
     });
     perm.resize((size_t)E);
     for (int e = 0; e < E; ++e) perm[e] = (int32_t)(uint32_t)key[e];
+}
+
+// order_members' rule on the device (simplyp_order.hip.h): d_cost -> d_perm on the run's stream, nothing copied and nothing
+// waited for.  The workspace follows d_perm in ctx->balance (order_workspace_bytes).
+bool order_on_device(int E)
+{
+    const char* env = getenv("SIMPLYP_ORDER_HOST");           // read at every run: 1 = the host's order_members
+    return !(env && atoi(env) == 1) && E <= simplyp::ORD_MAX_E;
+}
+
+int order_sort_keys(int E)
+{
+    int P = simplyp::ORD_CHUNK;
+    while (P < E) P <<= 1;
+    return P;
+}
+
+size_t order_workspace_bytes(int E)
+{
+    const size_t n_groups = ((size_t)E + simplyp::ORD_THREADS - 1) / simplyp::ORD_THREADS;
+    return 8 + (size_t)order_sort_keys(E) * sizeof(unsigned long long) +
+           (n_groups * (2 * simplyp::ORD_WIN + simplyp::ORD_NCOV) + 2 * simplyp::ORD_WIN) * sizeof(double) + 2 * simplyp::ORD_WIN * sizeof(float);
+}
+
+int order_members_device(simplyp_ctx* ctx, const uint32_t* d_cost, int32_t* d_perm, void* work, int E)
+{
+    namespace sp = simplyp;
+    sp::OrderArgs g;
+    g.E = E;
+    g.P = order_sort_keys(E);
+    g.n_groups = (E + sp::ORD_THREADS - 1) / sp::ORD_THREADS;
+    g.nb1 = std::max(1, std::min(sp::ORD_MAX_BLOCKS, E / sp::ORD_MIN_BLOCK));
+    g.nb2 = std::max(1, std::min(sp::ORD_MAX_SUB, E / (g.nb1 * sp::ORD_MIN_BLOCK)));
+    g.cost = d_cost;
+    g.key = (unsigned long long*)(((uintptr_t)work + 7) & ~(uintptr_t)7);
+    g.part_stats = (double*)(g.key + g.P);
+    g.part_cov = g.part_stats + (size_t)g.n_groups * 2 * sp::ORD_WIN;
+    g.moments = g.part_cov + (size_t)g.n_groups * sp::ORD_NCOV;
+    g.vec = (float*)(g.moments + 2 * sp::ORD_WIN);
+    g.perm = d_perm;
+    const dim3 wg(sp::ORD_THREADS);
+    hipLaunchKernelGGL(sp::order_stats_kernel, dim3((unsigned)(g.P / sp::ORD_THREADS)), wg, 0, ctx->stream, g);
+    hipLaunchKernelGGL(sp::order_cov_kernel, dim3((unsigned)g.n_groups), wg, 0, ctx->stream, g);
+    hipLaunchKernelGGL(sp::order_pca_kernel, dim3(1), dim3(64), 0, ctx->stream, g);
+    const dim3 chunks((unsigned)(g.P / sp::ORD_CHUNK));
+    hipLaunchKernelGGL(sp::order_sort_chunk_kernel, chunks, wg, 0, ctx->stream, g.key, 2);
+    for (int k = 2 * sp::ORD_CHUNK; k <= g.P; k <<= 1) {
+        for (int j = k >> 1; j >= sp::ORD_CHUNK; j >>= 1)
+            hipLaunchKernelGGL(sp::order_sort_stride_kernel, dim3((unsigned)(g.P / 2 / 256)), dim3(256), 0, ctx->stream, g.key, g.P, k, j);
+        hipLaunchKernelGGL(sp::order_sort_chunk_kernel, chunks, wg, 0, ctx->stream, g.key, k);
+    }
+    hipLaunchKernelGGL(sp::order_blocks_kernel, dim3((unsigned)g.nb1), wg, 0, ctx->stream, g);
+    HIP_TRY(ctx, hipGetLastError());
+    return SIMPLYP_OK;
 }
 
 // Host side of the streamed output: wait for the kernel to raise a chunk's flag (or for the run to be over), then enqueue the
@@ -787,7 +842,10 @@ int balance_members(simplyp_ctx* ctx, const simplyp_opts& opts, const RunShape& 
     constexpr int PILOT_WINDOWS = 8;
     const int win_days = std::max(1, shape.pilot_days / PILOT_WINDOWS);
     const int win_stride = std::max(win_days, std::min(80, (D - win_days) / (PILOT_WINDOWS - 1)));      // ~1.6 years covered
-    if (int rc = ensure(ctx, ctx->balance, (size_t)E * (PILOT_WINDOWS * sizeof(uint32_t) + sizeof(int32_t)))) return rc;
+    static_assert(PILOT_WINDOWS == simplyp::ORD_WIN, "the device's ordering kernels are written for the pilot's windows");
+    const bool on_device = order_on_device(E);
+    const size_t order_in_out = (size_t)E * (PILOT_WINDOWS * sizeof(uint32_t) + sizeof(int32_t));
+    if (int rc = ensure(ctx, ctx->balance, order_in_out + (on_device ? order_workspace_bytes(E) : 0))) return rc;
     uint32_t* d_cost = (uint32_t*)ctx->balance.ptr;
     int32_t* d_perm = (int32_t*)(d_cost + (size_t)PILOT_WINDOWS * E);
     HIP_TRY(ctx, hipMemsetAsync(d_cost, 0, (size_t)PILOT_WINDOWS * E * sizeof(uint32_t), ctx->stream));
@@ -806,13 +864,30 @@ int balance_members(simplyp_ctx* ctx, const simplyp_opts& opts, const RunShape& 
     p.member_rhs = d_cost;
     for (const ChainLaunch& c : pilot)
         if (int rc = launch_chains(ctx, opts, shape, p, c, (unsigned)PILOT_WINDOWS)) return rc;
-    std::vector<uint32_t> cost((size_t)PILOT_WINDOWS * E);
-    HIP_TRY(ctx, hipMemcpyAsync(cost.data(), d_cost, cost.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<int32_t> perm;
-    order_members(cost, PILOT_WINDOWS, E, perm);
-    HIP_TRY(ctx, hipMemcpyAsync(d_perm, perm.data(), (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (on_device) {
+        if (int rc = order_members_device(ctx, d_cost, d_perm, (unsigned char*)ctx->balance.ptr + order_in_out, E)) return rc;
+    } else {
+        // SIMPLYP_DEBUG: the host's share of the pilot, step by step
+        const bool dbg = getenv("SIMPLYP_DEBUG") != nullptr;
+        using clk = std::chrono::steady_clock;
+        auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
+        if (dbg) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        clk::time_point t0 = clk::now();
+        std::vector<uint32_t> cost((size_t)PILOT_WINDOWS * E);
+        HIP_TRY(ctx, hipMemcpyAsync(cost.data(), d_cost, cost.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        const double ms_d2h = ms_since(t0);
+        t0 = clk::now();
+        std::vector<int32_t> perm;
+        order_members(cost, PILOT_WINDOWS, E, perm);
+        const double ms_order = ms_since(t0);
+        t0 = clk::now();
+        HIP_TRY(ctx, hipMemcpyAsync(d_perm, perm.data(), (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (dbg)
+            fprintf(stderr, "[simplyp] member order on the host, E=%d: costs to the host %.3f ms, order_members %.3f ms, order to the device %.3f ms\n",
+                    E, ms_d2h, ms_order, ms_since(t0));
+    }
     // the pilot's bookkeeping must not leak into the real run
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters.ptr, 0, simplyp_ctx::N_COUNTERS * sizeof(unsigned long long), ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(a.status, 0, (size_t)E * sizeof(int32_t), ctx->stream));

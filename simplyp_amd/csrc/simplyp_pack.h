@@ -4,16 +4,24 @@
 //
 // Per (column, member): z = zigzag(u[d] - p[d]) modulo 2^64, where u[d] is the day's pattern and p[d] its prediction:
 //   pred_col = -1   p[d] = u[d-1], the previous day of the same column;
-//   pred_col =  k   p[d] = pattern of X[d] * (Y[d-1] / X[d-1]) in fp64, X = column k of the same chunk, Y = this column --
-//                   one division and one multiplication, each correctly rounded on both sides of the link (predict());
-//                   where that pattern is +-0 or has an all-ones exponent, p[d] = u[d-1] instead.
+//   pred_col =  k   X = column k of the same chunk, Y = this column, r1 = Y[d-1] / X[d-1], r2 = the r1 of the row before (the
+//                   same fp64 value, carried along the chunk, not recomputed).  Per 64-member block and span of 64 delta rows
+//                   the encoder chooses (predict2())
+//                     first order    p[d] = pattern of X[d] * r1, or
+//                     second order   p[d] = pattern of X[d] * ((r1 + r1) - r2): the ratio extrapolated one day,
+//                   whichever makes the span smaller (first order on a tie, and where second order alone would make the block
+//                   an overflow block).  Division, multiplication, doubling and subtraction are separate IEEE operations,
+//                   correctly rounded on both sides of the link.  A second-order pattern that is +-0 or has an all-ones
+//                   exponent is replaced by the first-order pattern, and such a first-order pattern by u[d-1].  The first delta
+//                   row of a chunk has no r2 and is first order in any span.
 // All members see the same weather, so the 64 members of a block have small z on the same days and large z on the same days:
 // every row of a block (64 members, one day) is stored at the bit width of its widest z.
 //
 // One record per (time chunk, column), contiguous so that it is one plain copy:
 //   row 0      [E] fp64          the chunk's first day, raw: chunks decode independently of each other
 //   directory  [G] entries       per 64-member block: [n_spans] uint32 -- where each span of 64 delta rows starts in the body,
-//                                in 8-byte words -- then one width byte (0 .. 64) per delta row (entry padded to 4 bytes)
+//                                in 8-byte words -- then one width byte (0 .. 64) per delta row (entry padded to 4 bytes);
+//                                bit 7 (ORDER2) of a span's first width byte: the span is coded second order
 //   body                         per span its rows one after the other; a row of width w is the 64 z at w bits each, value i at
 //                                bit i * w: 8 * w bytes.  Spans take their place with one atomic add on the record's word
 //                                cursor, so their order is whatever the run made it.  8 bytes of padding follow the last row.
@@ -55,6 +63,23 @@ SIMPLYP_PACK_HD inline uint64_t predict(uint64_t x, uint64_t x_prev, uint64_t y_
     const double p = __builtin_bit_cast(double, x) * (__builtin_bit_cast(double, y_prev) / __builtin_bit_cast(double, x_prev));
     const uint64_t pb = __builtin_bit_cast(uint64_t, p), mag = pb & 0x7FFFFFFFFFFFFFFFull;
     return (mag == 0ull || (mag >> 52) == 0x7FFull) ? y_prev : pb;
+}
+
+constexpr unsigned char ORDER2 = 0x80;        // in a span's first width byte: the span is coded second order
+
+// Both orders of the ratio predictor.  r1 = Y[d-1] / X[d-1] comes back for the next row, whose r_prev it is; p1 is predict()'s
+// pattern, p2 that of X[d] * (2 r1 - r_prev) with p1 in its place where it is unusable.  One division as before; the doubling
+// is exact (or inf, and then the product is unusable).
+SIMPLYP_PACK_HD inline void predict2(uint64_t x, uint64_t x_prev, uint64_t y_prev, double r_prev, double& r1, uint64_t& p1, uint64_t& p2)
+{
+    const double xd = __builtin_bit_cast(double, x);
+    r1 = __builtin_bit_cast(double, y_prev) / __builtin_bit_cast(double, x_prev);
+    const uint64_t b1 = __builtin_bit_cast(uint64_t, xd * r1), m1 = b1 & 0x7FFFFFFFFFFFFFFFull;
+    p1 = (m1 == 0ull || (m1 >> 52) == 0x7FFull) ? y_prev : b1;
+    const double twice = r1 + r1;
+    const double slope = twice - r_prev;
+    const uint64_t b2 = __builtin_bit_cast(uint64_t, xd * slope), m2 = b2 & 0x7FFFFFFFFFFFFFFFull;
+    p2 = (m2 == 0ull || (m2 >> 52) == 0x7FFull) ? p1 : b2;
 }
 
 // Overflow blocks a record with n_groups blocks may hold: an eighth of them (the model's flux columns need 2.3 %), and three
@@ -175,12 +200,15 @@ __device__ __forceinline__ void pack_block(const double* rows, const double* xro
     unsigned char* dir = rec + L.off_dir + (size_t)g * L.dir_stride;
     unsigned long long* body = (unsigned long long*)(rec + L.off_body);
     unsigned long long big = 0ull;
+    double rprev = 0.0;                                        // r1 of the row before (ratio columns), carried over the spans
     for (int s = 0; s < L.n_spans; ++s) {
         const int d_first = 1 + s * SPAN, n = min(SPAN, nd - d_first);      // rows d_first .. d_first + n - 1
         unsigned long long prev = live ? src[(size_t)(d_first - 1) * stride] : 0ull;
         unsigned long long xprev = (live && ratio) ? xsrc[(size_t)(d_first - 1) * stride] : 0ull;
         const unsigned long long prev0 = prev, xprev0 = xprev;
-        int wmine = 0;
+        const double rprev0 = rprev;
+        unsigned long long big1 = 0ull, big2 = 0ull;           // this span's, under either order
+        int wmine = 0, wmine2 = 0;
         for (int k0 = 0; k0 < n; k0 += BATCH) {
             unsigned long long u[BATCH], x[BATCH];
 #pragma unroll
@@ -190,17 +218,45 @@ __device__ __forceinline__ void pack_block(const double* rows, const double* xro
                 x[i] = (in && ratio) ? xsrc[(size_t)(d_first + k0 + i) * stride] : 0ull;
             }
             int wv[BATCH];
+            if (ratio) {
+                int wv2[BATCH];
 #pragma unroll
-            for (int i = 0; i < BATCH; ++i) {
-                const bool in = live && k0 + i < n;
-                const unsigned long long z = in ? encode(u[i], ratio ? predict(x[i], xprev, prev) : prev) : 0ull;
-                prev = u[i]; xprev = x[i];
-                big |= z >> Z_BITS;
-                wv[i] = width_of(z);
+                for (int i = 0; i < BATCH; ++i) {
+                    const bool in = live && k0 + i < n;
+                    double r1;
+                    uint64_t p1, p2;
+                    predict2(x[i], xprev, prev, rprev, r1, p1, p2);
+                    if (d_first + k0 + i == 1) p2 = p1;        // the chunk's first delta row
+                    const unsigned long long z1 = in ? encode(u[i], p1) : 0ull, z2 = in ? encode(u[i], p2) : 0ull;
+                    prev = u[i]; xprev = x[i]; rprev = r1;
+                    big1 |= z1 >> Z_BITS; big2 |= z2 >> Z_BITS;
+                    wv[i] = width_of(z1); wv2[i] = width_of(z2);
+                }
+                const int w2 = wave_max_rows(wv2, lane);
+                if ((lane & ~(BATCH - 1)) == k0) wmine2 = w2;
+            } else {
+#pragma unroll
+                for (int i = 0; i < BATCH; ++i) {
+                    const bool in = live && k0 + i < n;
+                    const unsigned long long z = in ? encode(u[i], prev) : 0ull;
+                    prev = u[i];
+                    big1 |= z >> Z_BITS;
+                    wv[i] = width_of(z);
+                }
             }
             const int w = wave_max_rows(wv, lane);             // of row k0 + (lane & 7)
             if ((lane & ~(BATCH - 1)) == k0) wmine = w;
         }
+        const double rend = rprev;
+        // second order where it makes the span smaller and does not make an overflow block of a clean one (wave-uniform)
+        bool order2 = false;
+        if (ratio) {
+            int t1 = wmine, t2 = wmine2;
+            for (int m = 1; m < GROUP; m <<= 1) { t1 += __shfl_xor(t1, m); t2 += __shfl_xor(t2, m); }
+            order2 = t2 < t1 && !(__ballot(big2 != 0ull) != 0ull && __ballot(big1 != 0ull) == 0ull);
+        }
+        if (order2) wmine = wmine2;
+        big |= order2 ? big2 : big1;
         int inc = wmine;                                       // inclusive lane prefix sum of the widths = words
         for (int o = 1; o < GROUP; o <<= 1) {
             const int t = __shfl_up(inc, o);
@@ -215,9 +271,9 @@ __device__ __forceinline__ void pack_block(const double* rows, const double* xro
         }
         if ((size_t)base + total > L.body_cap_words) continue; // (wave-uniform) past the capacity: the record travels raw
         if (lane == 0) ((uint32_t*)dir)[s] = base;
-        if (lane < n) dir[L.off_widths + (size_t)(d_first - 1 + lane)] = (unsigned char)wmine;
+        if (lane < n) dir[L.off_widths + (size_t)(d_first - 1 + lane)] = (unsigned char)(wmine | ((order2 && lane == 0) ? ORDER2 : 0));
         if (total == 0u) continue;
-        prev = prev0; xprev = xprev0;
+        prev = prev0; xprev = xprev0; rprev = rprev0;
         for (int k0 = 0; k0 < n; k0 += BATCH) {
             unsigned long long u[BATCH], x[BATCH];
 #pragma unroll
@@ -232,7 +288,17 @@ __device__ __forceinline__ void pack_block(const double* rows, const double* xro
 #pragma unroll
             for (int i = 0; i < BATCH; ++i) {
                 const bool in = live && k0 + i < n;
-                const unsigned long long z = in ? encode(u[i], ratio ? predict(x[i], xprev, prev) : prev) : 0ull;
+                unsigned long long p = prev;
+                if (order2) {
+                    double r1;
+                    uint64_t p1, p2;
+                    predict2(x[i], xprev, prev, rprev, r1, p1, p2);
+                    p = d_first + k0 + i == 1 ? p1 : p2;
+                    rprev = r1;
+                } else if (ratio) {
+                    p = predict(x[i], xprev, prev);
+                }
+                const unsigned long long z = in ? encode(u[i], p) : 0ull;
                 prev = u[i]; xprev = x[i];
                 const int w = __builtin_amdgcn_readlane(wmine, k0 + i);       // (0 beyond the span's last row)
                 const int bit = lane * w, wi = bit >> 6, sh = bit & 63;
@@ -251,6 +317,7 @@ __device__ __forceinline__ void pack_block(const double* rows, const double* xro
             }
             lds_order();
         }
+        rprev = rend;
     }
     if (__ballot(big != 0ull) != 0ull && lane == 0) atomicAdd(count, 1u);
 }
@@ -322,44 +389,57 @@ inline void encode_record_host(const double* rows, const double* xrows, size_t s
     memcpy(rec, src, E * sizeof(uint64_t));
     uint64_t* body = (uint64_t*)(rec + L.off_body);
     uint64_t n_big = 0, cursor = 0;
-    uint64_t z[SPAN][GROUP];
+    // z[0]: previous day or first order, z[1]: second order (ratio columns only)
+    static thread_local uint64_t z[2][SPAN][GROUP];
     for (int g = 0; g < G; ++g) {
         const size_t e0 = (size_t)g * GROUP;
         unsigned char* dir = rec + L.off_dir + (size_t)g * L.dir_stride;
         bool big = false;
+        double rprev[GROUP] = {};
         for (int s = 0; s < L.n_spans; ++s) {
             const int d_first = 1 + s * SPAN, n = nd - d_first < SPAN ? nd - d_first : SPAN;
-            int w[SPAN];
-            uint64_t total = 0;
+            int w[2][SPAN];
+            uint64_t total[2] = {0, 0};
+            bool span_big[2] = {false, false};
             for (int k = 0; k < n; ++k) {
                 const size_t d = (size_t)(d_first + k);
-                uint64_t any = 0;
+                uint64_t any[2] = {0, 0};
                 for (int i = 0; i < GROUP; ++i) {
                     const size_t e = e0 + (size_t)i;
-                    uint64_t v = 0;
+                    uint64_t v[2] = {0, 0};
                     if (e < E) {
                         const uint64_t yp = src[(d - 1) * stride + e];
-                        const uint64_t p = xsrc ? predict(xsrc[d * stride + e], xsrc[(d - 1) * stride + e], yp) : yp;
-                        v = encode(src[d * stride + e], p);
+                        uint64_t p1 = yp, p2 = yp;
+                        if (xsrc) {
+                            double r1;
+                            predict2(xsrc[d * stride + e], xsrc[(d - 1) * stride + e], yp, rprev[i], r1, p1, p2);
+                            if (d == 1) p2 = p1;
+                            rprev[i] = r1;
+                        }
+                        v[0] = encode(src[d * stride + e], p1);
+                        v[1] = encode(src[d * stride + e], p2);
                     }
-                    z[k][i] = v;
-                    any |= v;
+                    for (int o = 0; o < 2; ++o) { z[o][k][i] = v[o]; any[o] |= v[o]; }
                 }
-                big = big || !fits(any);
-                w[k] = width_of(any);
-                total += (uint64_t)w[k];
+                for (int o = 0; o < 2; ++o) {
+                    span_big[o] = span_big[o] || !fits(any[o]);
+                    w[o][k] = width_of(any[o]);
+                    total[o] += (uint64_t)w[o][k];
+                }
             }
+            const int o = (xsrc && total[1] < total[0] && !(span_big[1] && !span_big[0])) ? 1 : 0;
+            big = big || span_big[o];
             const uint64_t base = cursor;
-            cursor += total;
-            if (base + total > L.body_cap_words) continue;
+            cursor += total[o];
+            if (base + total[o] > L.body_cap_words) continue;
             const uint32_t b32 = (uint32_t)base;
             memcpy(dir + (size_t)s * 4, &b32, 4);
             uint64_t* at = body + base;
             for (int k = 0; k < n; ++k) {
-                dir[L.off_widths + (size_t)(d_first - 1 + k)] = (unsigned char)w[k];
-                memset(at, 0, (size_t)w[k] * 8);
-                pack_row_host(z[k], w[k], at);
-                at += w[k];
+                dir[L.off_widths + (size_t)(d_first - 1 + k)] = (unsigned char)(w[o][k] | ((o && k == 0) ? ORDER2 : 0));
+                memset(at, 0, (size_t)w[o][k] * 8);
+                pack_row_host(z[o][k], w[o][k], at);
+                at += w[o][k];
             }
         }
         if (big) ++n_big;
@@ -384,10 +464,22 @@ inline void unpack_row_scalar(const unsigned char* row, int w, uint64_t* z)
     }
 }
 
-// out[i] = pred[i] + unzigzag(z[i]) for a whole block row; `z` becomes the row's values (the next row's previous day).
-inline void finish_row_scalar(uint64_t* run, const uint64_t* z, const uint64_t* x, const uint64_t* x_prev, int n)
+// One member of a ratio column's row: r_prev becomes this row's r1 whatever the order, so that a second-order span can
+// follow a first-order one.
+inline void finish_ratio(uint64_t& run, uint64_t z, uint64_t x, uint64_t x_prev, double& r_prev, bool order2)
 {
-    if (x) for (int i = 0; i < n; ++i) run[i] = decode(z[i], predict(x[i], x_prev[i], run[i]));
+    double r1;
+    uint64_t p1, p2;
+    predict2(x, x_prev, run, r_prev, r1, p1, p2);
+    r_prev = r1;
+    run = decode(z, order2 ? p2 : p1);
+}
+
+// out[i] = pred[i] + unzigzag(z[i]) for a whole block row; `z` becomes the row's values (the next row's previous day).
+// r_prev[64] is the block's running ratio (ratio columns), order2 what the row's span says (false on a chunk's first delta row).
+inline void finish_row_scalar(uint64_t* run, const uint64_t* z, const uint64_t* x, const uint64_t* x_prev, double* r_prev, bool order2, int n)
+{
+    if (x) for (int i = 0; i < n; ++i) finish_ratio(run[i], z[i], x[i], x_prev[i], r_prev[i], order2);
     else for (int i = 0; i < GROUP; ++i) run[i] = decode(z[i], run[i]);
 }
 
@@ -416,8 +508,10 @@ __attribute__((target("avx2"))) inline void unpack_row_avx2(const unsigned char*
     }
 }
 
-// The same arithmetic as finish_row_scalar, four values per turn.  _mm256_div_pd and _mm256_mul_pd are the IEEE operations.
-__attribute__((target("avx2"))) inline void finish_row_avx2(uint64_t* run, const uint64_t* z, const uint64_t* x, const uint64_t* x_prev, int n)
+// The same arithmetic as finish_row_scalar, four values per turn.  _mm256_div_pd, _mm256_mul_pd, _mm256_add_pd and
+// _mm256_sub_pd are the IEEE operations.
+__attribute__((target("avx2"))) inline void finish_row_avx2(uint64_t* run, const uint64_t* z, const uint64_t* x, const uint64_t* x_prev,
+                                                            double* r_prev, bool order2, int n)
 {
     const __m256i one = _mm256_set1_epi64x(1), zero = _mm256_setzero_si256();
     const __m256i absmask = _mm256_set1_epi64x(0x7FFFFFFFFFFFFFFFll), expmask = _mm256_set1_epi64x(0x7FF0000000000000ll);
@@ -433,10 +527,18 @@ __attribute__((target("avx2"))) inline void finish_row_avx2(uint64_t* run, const
             const __m256i mag = _mm256_and_si256(pb, absmask);
             const __m256i bad = _mm256_or_si256(_mm256_cmpeq_epi64(mag, zero), _mm256_cmpeq_epi64(_mm256_and_si256(pb, expmask), expmask));
             p = _mm256_blendv_epi8(pb, p, bad);
+            if (order2) {
+                const __m256d slope = _mm256_sub_pd(_mm256_add_pd(q, q), _mm256_loadu_pd(r_prev + i));
+                const __m256i pb2 = _mm256_castpd_si256(_mm256_mul_pd(_mm256_loadu_pd((const double*)(x + i)), slope));
+                const __m256i mag2 = _mm256_and_si256(pb2, absmask);
+                const __m256i bad2 = _mm256_or_si256(_mm256_cmpeq_epi64(mag2, zero), _mm256_cmpeq_epi64(_mm256_and_si256(pb2, expmask), expmask));
+                p = _mm256_blendv_epi8(pb2, p, bad2);
+            }
+            _mm256_storeu_pd(r_prev + i, q);
         }
         _mm256_storeu_si256((__m256i*)(run + i), _mm256_add_epi64(p, d));
     }
-    if (x) for (; i < n; ++i) run[i] = decode(z[i], predict(x[i], x_prev[i], run[i]));
+    if (x) for (; i < n; ++i) finish_ratio(run[i], z[i], x[i], x_prev[i], r_prev[i], order2);
 }
 
 // The common row in one pass: a full block, 1 <= w <= 56, previous-day prediction, `out` 32-byte aligned.  unpack_row_avx2,
@@ -486,6 +588,7 @@ inline void decode_range(const unsigned char* rec, const Layout& L, int nd, size
     static const bool have_avx2 = __builtin_cpu_supports("avx2");
 #endif
     alignas(32) uint64_t run[GROUP], z[GROUP];
+    alignas(32) double r_prev[GROUP];
     const unsigned char* body = rec + L.off_body;
     for (size_t b0 = e0; b0 < e1; b0 += GROUP) {
         const int n = (int)(e1 - b0 < (size_t)GROUP ? e1 - b0 : (size_t)GROUP);
@@ -496,13 +599,17 @@ inline void decode_range(const unsigned char* rec, const Layout& L, int nd, size
         const uint64_t* x = xdst ? (const uint64_t*)xdst + b0 : nullptr;
         store_row(out, run, n);
         const unsigned char* row = body;
+        bool span_order2 = false;
+        memset(r_prev, 0, sizeof(r_prev));
         for (int d = 1; d < nd; ++d) {
             if ((d - 1) % SPAN == 0) {
                 uint32_t base;
                 memcpy(&base, dir + (size_t)((d - 1) / SPAN) * 4, 4);
                 row = body + (size_t)base * 8;
+                span_order2 = (dir[L.off_widths + (size_t)(d - 1)] & ORDER2) != 0;
             }
-            const int w = dir[L.off_widths + (size_t)(d - 1)];
+            const int w = dir[L.off_widths + (size_t)(d - 1)] & (ORDER2 - 1);
+            const bool order2 = span_order2 && d > 1;
             out += stride;
             const uint64_t* xd = x ? x + (size_t)d * stride : nullptr;
             const uint64_t* xp = x ? x + (size_t)(d - 1) * stride : nullptr;
@@ -516,14 +623,14 @@ inline void decode_range(const unsigned char* rec, const Layout& L, int nd, size
                 if (w == 0) memset(z, 0, sizeof(z));
                 else if (w <= Z_BITS) unpack_row_avx2(row, w, z);
                 else unpack_row_scalar(row, w, z);
-                finish_row_avx2(run, z, xd, xp, n);
+                finish_row_avx2(run, z, xd, xp, r_prev, order2, n);
                 store_row_avx2(out, run, n);
                 row += (size_t)w * 8;
                 continue;
             }
 #endif
             unpack_row_scalar(row, w, z);
-            finish_row_scalar(run, z, xd, xp, n);
+            finish_row_scalar(run, z, xd, xp, r_prev, order2, n);
             store_row(out, run, n);
             row += (size_t)w * 8;
         }

@@ -1,7 +1,7 @@
 // pack_gate.hip -- go / no-go for the packed output stream, without a model run: the real shapes (one pinned destination of
 // the whole table, the pinned staging ring, a device buffer of packed records -- random bits under a valid directory whose row
-// widths are each column's mean on the model's table (51, 51, 52, 52 bits, and 38 for the last column,
-// which is decoded against the third with the ratio predictor) --, the real schedule
+// widths are each column's mean on the model's table (51, 51, 52, 52 bits, and 35 for the last column,
+// which is decoded against the third with the second-order ratio predictor: its spans carry the ORDER2 flag) --, the real schedule
 // (two copy streams taken in turn, one record per chunk-column, the library's router, dispatcher and decode pool from
 // simplyp_pack_stream.h), against the raw copies of the same table in the same session.
 //
@@ -35,7 +35,8 @@ __global__ void fill_kernel(unsigned long long* p, size_t n)
     }
 }
 
-// A valid directory for every block of every record: one span, every row `w` bits wide, blocks in order.
+// A valid directory for every block of every record: one span, every row `w` bits wide, blocks in order; the span of a column
+// that has a predictor column is flagged second order.
 __global__ void directory_kernel(unsigned char* dev, simplyp_pack::Table t, int G, const int* width_of_col)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -45,6 +46,7 @@ __global__ void directory_kernel(unsigned char* dev, simplyp_pack::Table t, int 
     unsigned char* dir = dev + (size_t)rec * t.stride + L.off_dir + (size_t)g * L.dir_stride;
     *(uint32_t*)dir = (uint32_t)((size_t)g * L.rows * w);
     for (int r = 0; r < L.rows; ++r) dir[L.off_widths + r] = (unsigned char)w;
+    if (L.rows > 0 && t.pred[rec % t.n_cols] >= 0) dir[L.off_widths] |= simplyp_pack::ORDER2;
 }
 
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -77,7 +79,7 @@ int main(int argc, char** argv)
     if (!getenv("PACK_GATE_NO_BIND")) printf("main thread bound to the GPU's NUMA node: %d (-1 = not bound)\n", simplyp_pack::bind_thread_to_gpu_node(0));
     CHECK(hipMalloc((void**)&dev, dev_bytes));
     hipLaunchKernelGGL(fill_kernel, dim3(4096), dim3(256), 0, 0, (unsigned long long*)dev, dev_bytes / 8);
-    const int widths[5] = {51, 51, 52, 52, 38};
+    const int widths[5] = {51, 51, 52, 52, 35};
     std::vector<int> width_of_col((size_t)n_cols);
     for (int j = 0; j < n_cols; ++j) width_of_col[(size_t)j] = widths[j % 5];
     int* dev_widths = nullptr;
