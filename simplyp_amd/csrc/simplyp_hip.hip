@@ -1415,8 +1415,10 @@ static int sync_impl(simplyp_ctx* ctx, simplyp_stats* stats)
                         "%llu polls (bound: SIMPLYP_QUEUE_MAX_POLLS); results are incomplete", c[6]);
     }
     if (copied && ctx->copy_plan.pack_dev && getenv("SIMPLYP_DEBUG"))
-        fprintf(stderr, "[simplyp] packed stream: %d records packed (%zu bytes on the link), %d raw\n", ctx->tally.n_packed,
-                ctx->tally.link_bytes, ctx->tally.n_raw);
+        fprintf(stderr, "[simplyp] packed stream: %d records packed (%zu bytes on the link), %d raw (%zu bytes on the link: %d past the "
+                "capacity, %d not smaller than raw, %d follow a raw predictor column)\n", ctx->tally.n_packed, ctx->tally.link_bytes,
+                ctx->tally.n_raw, ctx->tally.raw_bytes, ctx->tally.raw_why[simplyp_pack::RAW_PAST_CAPACITY],
+                ctx->tally.raw_why[simplyp_pack::RAW_NOT_SMALLER], ctx->tally.raw_why[simplyp_pack::RAW_FOLLOWS]);
     if (copied && ctx->copy_plan.pack_dev && ctx->tally.n_raw && getenv("SIMPLYP_DEBUG"))
         for (int j = 0; j < ctx->copy_plan.table.n_cols; ++j) fprintf(stderr, "[simplyp] packed stream: column %d: %d raw\n", j, ctx->tally.raw_of_col[j]);
     if (stats) {

@@ -26,8 +26,10 @@
 //                                bit i * w: 8 * w bytes.  Spans take their place with one atomic add on the record's word
 //                                cursor, so their order is whatever the run made it.  8 bytes of padding follow the last row.
 // Two counters per record live outside it (one array per run, zeroed with one memset): [0] blocks that hold any z >= 2^56
-// ("overflow blocks"), [1] the word cursor.  A record with more than overflow_capacity() overflow blocks, or whose body passes
-// its fixed capacity, travels raw: the copier then sends that chunk-column from the fp64 table.
+// ("overflow blocks"), [1] the word cursor.  A record travels raw -- the copier then sends that chunk-column from the fp64
+// table -- when its body passes its fixed capacity, or when it has more than overflow_capacity() overflow blocks and its
+// packed copy would not be smaller than its rows (route_of()).  The count of overflow blocks alone sends nothing raw: it is a
+// reported statistic, and it sizes the record's capacity.
 #pragma once
 
 #include <stddef.h>
@@ -82,8 +84,11 @@ SIMPLYP_PACK_HD inline void predict2(uint64_t x, uint64_t x_prev, uint64_t y_pre
     p2 = (m2 == 0ull || (m2 >> 52) == 0x7FFull) ? p1 : b2;
 }
 
-// Overflow blocks a record with n_groups blocks may hold: an eighth of them (the model's flux columns need 2.3 %), and three
-// more so that a small ensemble does not go raw for two unlucky blocks.
+// Overflow blocks a record's capacity allows for: an eighth of its n_groups blocks (the model's flux columns need 2.3 %), and
+// three more for a small ensemble -- each counted as wholly raw fp64 in Layout::body_cap_words, which fixes the record stride,
+// the ring slots and the pack buffer.  That is what a block with a z >= 2^56 cost when it was stored whole and raw; now it
+// merely has some wide rows, so a record may hold more such blocks than this and still fit and travel packed: beyond this
+// count route_of() goes by the size of the packed copy.
 SIMPLYP_PACK_HD inline unsigned overflow_capacity(int n_groups) { return (unsigned)n_groups / 8u + 3u; }
 
 struct Layout {
@@ -113,9 +118,21 @@ SIMPLYP_PACK_HD inline Layout layout(size_t E, int nd, unsigned cap)
 
 // What crosses the link for a record whose cursor stands at `words`.
 SIMPLYP_PACK_HD inline size_t copy_bytes(const Layout& L, size_t words) { return L.off_body + words * 8 + 8; }
-SIMPLYP_PACK_HD inline bool travels_raw(const Layout& L, unsigned overflow_blocks, size_t words, unsigned cap)
+
+// Why a record travels raw (Tally counts them apart).  RAW_FOLLOWS is the router's: the column is predicted from a raw one.
+enum Route { PACKED = 0, RAW_PAST_CAPACITY = 1, RAW_NOT_SMALLER = 2, RAW_FOLLOWS = 3 };
+
+// Packed or raw by the record's own counters; `raw_bytes` is what its rows would put on the link (Table::raw_bytes).
+//   past the capacity   the device skipped the spans beyond it, so the record is incomplete;
+//   not smaller         more overflow blocks than `cap` AND a packed copy at least as large as the rows.  Many overflow blocks
+//                       alone decide nothing: such a block has some wide rows, and the record usually stays well below its rows.
+//                       The size alone decides nothing either: a small ragged record (200 members in 256 lanes) would go raw
+//                       for its padding.
+SIMPLYP_PACK_HD inline Route route_of(const Layout& L, unsigned overflow_blocks, size_t words, unsigned cap, size_t raw_bytes)
 {
-    return overflow_blocks > cap || words > L.body_cap_words;
+    if (words > L.body_cap_words) return RAW_PAST_CAPACITY;
+    if (overflow_blocks > cap && copy_bytes(L, words) >= raw_bytes) return RAW_NOT_SMALLER;
+    return PACKED;
 }
 
 // A [n_cols][rows][E] fp64 table cut into chunks of `chunk_days` rows (the last one may be shorter), and its records: record

@@ -111,13 +111,16 @@ struct Tally {
     unsigned n_overflow = 0;                  // overflow blocks of the packed ones
     size_t link_bytes = 0;                    // what the packed ones put on the link
     int raw_of_col[32] = {};                  // records routed raw, per column
+    int raw_why[4] = {};                      // n_raw by reason, indexed by Route ([PACKED] stays 0)
+    size_t raw_bytes = 0;                     // what the raw ones put on the link
 };
 
 // Packed or raw, for every record of chunk `c` in column order -- the one place that decides it.  counters(j, overflow_blocks,
-// words) hands over record (c, j)'s two counters.  A record travels raw when its own counters say so (travels_raw), and when the
-// column it is predicted from travels raw in this chunk: its decoder reads that column's rows from the host table, where a raw
-// copy lands in no order with the decode pool.  Per column either packed(job) -- the record at `dev_recs` (null: the caller
-// keeps the record itself) to the columns of the table at `host` -- or raw(offset in doubles, bytes) of that table.
+// words) hands over record (c, j)'s two counters.  A record travels raw when its own counters and the size of its rows say so
+// (route_of), and when the column it is predicted from travels raw in this chunk: its decoder reads that column's rows from the
+// host table, where a raw copy lands in no order with the decode pool.  Per column either packed(job) -- the record at
+// `dev_recs` (null: the caller keeps the record itself) to the columns of the table at `host` -- or raw(offset in doubles,
+// bytes) of that table.
 template <class Counters, class Packed, class Raw>
 void route_chunk(const Table& t, int c, const unsigned char* dev_recs, double* host, Tally& tally, Counters&& counters, Packed&& packed,
                  Raw&& raw)
@@ -129,9 +132,11 @@ void route_chunk(const Table& t, int c, const unsigned char* dev_recs, double* h
         size_t words = 0;
         counters(j, overflow_blocks, words);
         const int k = t.pred[j];
-        is_raw[j] = travels_raw(L, overflow_blocks, words, t.cap) || (k >= 0 && is_raw[k]);
+        Route why = route_of(L, overflow_blocks, words, t.cap, t.raw_bytes(c));
+        if (why == PACKED && k >= 0 && is_raw[k]) why = RAW_FOLLOWS;
+        is_raw[j] = why != PACKED;
         if (is_raw[j]) {
-            ++tally.n_raw; ++tally.raw_of_col[j];
+            ++tally.n_raw; ++tally.raw_of_col[j]; ++tally.raw_why[why]; tally.raw_bytes += t.raw_bytes(c);
             raw(t.offset(j, c), t.raw_bytes(c));
             continue;
         }
