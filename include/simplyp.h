@@ -49,8 +49,10 @@ extern "C" {
  * existing changes.
  * 17 still with autocorrelated forcing errors and seasonal change factors: forcing_rho, forcing_noise_in / _out,
  * forcing_shift_group_of_day and forcing_shift_groups are appended to simplyp_opts after forcing_table (all zero = off), as the
- * forcing_* fields before them were; no entry point is added and none changes. */
-#define SIMPLYP_ABI_VERSION 17
+ * forcing_* fields before them were; no entry point is added and none changes.
+ * 18: simplyp_order_members, the members' lane-slot order of a balanced run from a caller-given cost table; nothing existing
+ * changes. */
+#define SIMPLYP_ABI_VERSION 18
 
 typedef enum {
     SIMPLYP_OK = 0,
@@ -1339,6 +1341,29 @@ int simplyp_pf_jitter(simplyp_ctx* ctx, int32_t E, int32_t n_dim, uint64_t seed,
  * Synchronous.  Not on the hot path.
  */
 int simplyp_eval_units(simplyp_ctx* ctx, int32_t which, int32_t n, const double* in, double* out);
+
+/*
+ * simplyp_order_members -- the members' lane-slot order of a balanced run (opts.balance) from a caller-given cost table, without
+ * the run around it: how the tests pin the device's ordering kernels and the host rule they restate to one statement of what a
+ * correct order is.  Blocks of the total-cost order (cost summed over the windows mod 2^32, descending, the member id breaking
+ * ties), nb1 = clamp(E / 256, 1, 24) of them with borders at E b / nb1; inside a block nb2 = clamp(E / (256 nb1), 1, 6)
+ * sub-blocks by the 2nd principal component of the standardised log2(cost + 1) table, the 3rd inside a sub-block, the directions
+ * alternating.
+ *   E               members, >= 1; where = 0 takes at most 196608 (24 blocks of one 8192-key LDS sort)
+ *   cost            device  [8][E] uint32: what a pilot would have counted in each of its 8 windows
+ *   where           0 = the kernels a balanced run launches (the same launch sequence, on a workspace of this entry's own that
+ *                   only grows), 1 = the host rule on a copy of `cost` (what SIMPLYP_ORDER_HOST=1 and larger ensembles use)
+ *   perm            device  [E] int32: the member of each lane slot
+ *   diag            device  [68] doubles, or NULL: mean[8] and 1 / deviation[8] of the log costs per window, the 36 covariances
+ *                   of the standardised windows (i <= j, row by row), the eigenvectors v2[8], v3[8] of the 2nd and 3rd largest
+ *                   eigenvalue as the projection uses them (fp32, widened)
+ *   keys            device  [E] uint64, or NULL; where = 0 only: the sorted total-cost keys
+ *                   (0xFFFFFFFF - total) << 32 | member, without the all-ones pads that sort behind them
+ * Any other `where`, where = 0 above the limit, keys with where = 1, E < 1 and a NULL cost or perm are SIMPLYP_ERR_ARG.
+ * Synchronous.  Not on the hot path.
+ */
+int simplyp_order_members(simplyp_ctx* ctx, int32_t E, const uint32_t* cost, int32_t where, int32_t* perm, double* diag,
+                          uint64_t* keys);
 
 #ifdef __cplusplus
 }

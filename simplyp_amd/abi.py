@@ -2,7 +2,7 @@
 
 import ctypes as C
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 INTEG_RK4 = 0
 INTEG_CASHKARP = 1

@@ -1,4 +1,4 @@
-// simplyp_order.hip.h -- the members' lane-slot order computed on the device (gfx950): order_members' rule (simplyp_hip.hip)
+// simplyp_order.hip.h -- the members' lane-slot order computed on the device (gfx950): order_members' rule (simplyp_order.h)
 // as kernels that read the pilot's cost table d_cost[8][E] and write d_perm[E] on the run's stream, so that the host neither
 // copies the costs nor waits for them.
 //
@@ -287,6 +287,25 @@ __global__ __launch_bounds__(ORD_THREADS) void order_blocks_kernel(const OrderAr
     __syncthreads();
     bitonic_segments<ORD_THREADS, false>(keys, nullptr, P, P);
     for (int i = threadIdx.x; i < cnt; i += ORD_THREADS) g.perm[lo + i] = (int32_t)(keys[i] & ((1ull << ORD_ID_BITS) - 1ull));
+}
+
+// ---- what the kernels above left in the workspace, for simplyp_order_members (not on a run's path) ------------------------------
+// One wavefront.  diag: mean[8], inv[8] as order_cov_kernel stored them; the 36 covariances, each the sum order_pca_kernel forms
+// (the workgroups' partials in index order, then / E: the same additions, so the same bits); v2[8], v3[8] widened to double.
+__global__ __launch_bounds__(64) void order_diag_kernel(int E, int n_groups, const double* part_cov, const double* moments,
+                                                        const float* vec, double* diag)
+{
+    const int lane = threadIdx.x;
+    if (lane < 2 * ORD_WIN) {
+        diag[lane] = moments[lane];
+        diag[2 * ORD_WIN + ORD_NCOV + lane] = (double)vec[lane];
+    }
+    if (lane < ORD_NCOV) {
+        double s = 0.0;
+        for (int b = 0; b < n_groups; ++b) s += part_cov[(size_t)b * ORD_NCOV + lane];
+        s /= E;
+        diag[2 * ORD_WIN + lane] = s;
+    }
 }
 
 }  // namespace simplyp

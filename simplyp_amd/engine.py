@@ -35,7 +35,7 @@ ABI_SYMBOLS = ['simplyp_abi_version', 'simplyp_device_count', 'simplyp_ctx_creat
                'simplyp_sobol_design', 'simplyp_sobol_indices',
                'simplyp_pf_loglik', 'simplyp_pf_weights', 'simplyp_pf_resample', 'simplyp_gather_members', 'simplyp_pf_jitter',
                'simplyp_weighted_quantiles', 'simplyp_predictive_bands_weighted', 'simplyp_scores', 'simplyp_predictive_scores',
-               'simplyp_pareto']
+               'simplyp_pareto', 'simplyp_order_members']
 
 _lib = None
 
@@ -197,6 +197,8 @@ def lib():
     L.simplyp_device_free.argtypes = [vp, vp]
     L.simplyp_eval_units.restype = C.c_int
     L.simplyp_eval_units.argtypes = [vp, C.c_int32, C.c_int32, dp, dp]
+    L.simplyp_order_members.restype = C.c_int
+    L.simplyp_order_members.argtypes = [vp, C.c_int32, vp, C.c_int32, i32p, dp, vp]
     for name in ('simplyp_memcpy_h2d', 'simplyp_memcpy_d2h'):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = [vp, vp, vp, C.c_int64]
@@ -563,6 +565,35 @@ class Engine(object):
         out = torch.empty((a.shape[0], k_out), dtype=torch.float64, device=self.tdev)
         self._info_call(None, 'simplyp_eval_units', self._h, w, a.shape[0], a.data_ptr(), out.data_ptr())
         return out.cpu().numpy()
+
+    def order_members(self, cost, where='device', diag=False, keys=False):
+        """The members' lane-slot order of a balanced run from a given cost table (``simplyp_order_members``): ``cost`` [8, E]
+        (anything numpy turns into uint32, or an int32 device tensor holding the same bits), ``where`` = 'device' (the kernels a
+        balanced run launches) or 'host' (the host rule on a copy).  Returns the permutation [E] as a numpy int32 array, or a
+        tuple that starts with it when more is asked for: ``diag=True`` adds the [68] doubles mean[8], 1 / deviation[8], the 36
+        covariances (i <= j, row by row), v2[8], v3[8]; ``keys=True`` ('device' only) the [E] sorted total-cost keys as
+        uint64."""
+        torch = self.torch
+        w = {'device': 0, 'host': 1}[where]
+        if torch.is_tensor(cost):
+            c = cost
+            if c.dtype != torch.int32 or c.device != self.tdev or not c.is_contiguous():
+                raise ValueError("a cost tensor must be a contiguous int32 tensor on %s" % self.tdev)
+        else:
+            c = self.to_device(np.ascontiguousarray(cost, dtype=np.uint32).view(np.int32))
+        if c.dim() != 2 or c.shape[0] != 8:
+            raise ValueError("cost must have shape [8, E], got %s" % (tuple(c.shape),))
+        E = int(c.shape[1])
+        perm = torch.empty((max(E, 1),), dtype=torch.int32, device=self.tdev)
+        d = torch.empty((68,), dtype=torch.float64, device=self.tdev) if diag else None
+        k = torch.empty((max(E, 1),), dtype=torch.int64, device=self.tdev) if keys else None
+        self._info_call(None, 'simplyp_order_members', self._h, E, c.data_ptr(), w, perm.data_ptr(), self._ptr(d), self._ptr(k))
+        got = [perm.cpu().numpy()]
+        if diag:
+            got.append(d.cpu().numpy())
+        if keys:
+            got.append(k.cpu().numpy().view(np.uint64))
+        return got[0] if len(got) == 1 else tuple(got)
 
     # ---- what the analysis methods do alike ----
     def _info_call(self, info_class, name, *args, bind=True):

@@ -187,6 +187,15 @@ def cases(h, dev):
     add('simplyp_pf_jitter', 'a = inf', (h, 4, 1, seed, C.c_uint32(1), float('inf'), hd(0.5), hd(0.1), lo, up, tg, dev, None, None), abi.PfInfo)
     add('simplyp_eval_units', 'which = 6', (h, 6, 1, dev, dev), None)
     add('simplyp_eval_units', 'n = -1', (h, 0, -1, dev, dev), None)
+
+    def order(label, E=4, cost=dev, where=0, perm=dev, keys=None):
+        add('simplyp_order_members', label, (h, E, cost, where, perm, None, keys), None)
+    order('E = 0', E=0)
+    order('cost = NULL', cost=None)
+    order('perm = NULL', perm=None)
+    order('where = 2', where=2)
+    order('where = 0, E = 196609', E=196609)
+    order('where = 1 with keys', where=1, keys=dev)
     out.append(keep)
     return out
 

@@ -5,6 +5,7 @@ order bit for bit, and lanes of a wavefront as alike as the host's order makes t
 import numpy as np
 import pytest
 
+import order_model
 from simplyp_amd import marshal, synthetic
 from test_gpu_stream_packed import perturbed, run
 
@@ -42,15 +43,21 @@ def compare_orders(engine0, monkeypatch, m, E):
     mos_h, table_h, status_h, st_h = ordered_run(engine0, monkeypatch, m, host=True)
     assert sorted(mos_h.tolist()) == list(range(E))
     assert blocks_by_total_cost(mos) == blocks_by_total_cost(mos_h)
+    # order_model's exact block test, the host's order standing for the sorted keys (their low halves are the members): what
+    # the sub-blocks (E >= 12288) are cut from.  Inside a block the two may differ where fp32 PC2 values all but tie.
+    got, want = order_model.blocks_by_total_cost(mos_h.astype(np.uint64), mos)
+    assert len(got) == order_model.shape(E)[0] and all(np.array_equal(a, b) for a, b in zip(got, want))
     assert np.array_equal(table.view(np.uint64), table_h.view(np.uint64)) and np.array_equal(table2.view(np.uint64), table_h.view(np.uint64))
     assert np.array_equal(status, status_h)
     return st, st_h
 
 
-@pytest.mark.parametrize('E', [1, 63, 300, 6145])
+@pytest.mark.parametrize('E', [1, 63, 300, 6145, 8193, 12288])
 def test_device_order_against_host_order(engine0, monkeypatch, E):
-    """6145 members: 24 blocks of 256 by total cost, one sub-block each; 300: one block; 63 and 1: less than a wavefront."""
-    m = perturbed('tarland_2004_dynamic', E, out_mask=marshal.MASK_REACH5, solver=BALANCED)
+    """6145 members: 24 blocks of 256 by total cost, one sub-block each; 300: one block; 63 and 1: less than a wavefront.
+    8193: the sort's first stride in global memory; 12288: two sub-blocks per block (one output column: three tables stay small)."""
+    m = perturbed('tarland_2004_dynamic', E, out_mask=marshal.MASK_REACH5 if E <= 6145 else 1 << marshal.OUT_COLUMNS.index('Qr'),
+                  solver=BALANCED)
     compare_orders(engine0, monkeypatch, m, E)
 
 

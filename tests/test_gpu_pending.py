@@ -49,7 +49,7 @@ def test_every_analysis_entry_refuses_while_a_run_is_pending(engine0):
     first = {}
     for entry, label, a, info_class in todo:
         first.setdefault(entry, (a, info_class))
-    assert len(first) == 26
+    assert len(first) == 27
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
         out, status, st = engine0.run(*args, defer_sync=True)

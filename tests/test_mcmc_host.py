@@ -36,7 +36,7 @@ def test_exports_and_layout(tmp_path):
     assert declared == {'simplyp_mcmc_propose', 'simplyp_mcmc_log_prob', 'simplyp_mcmc_accept'}
     for name in declared:
         assert name in engine.ABI_SYMBOLS and hasattr(L, name), name
-    assert L.simplyp_abi_version() == abi.ABI_VERSION == 17
+    assert L.simplyp_abi_version() == abi.ABI_VERSION == 18
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % HEADER, 'int main(void){',
              'printf("size %zu\\n", sizeof(simplyp_mcmc_info));']
     for f, _ in abi.McmcInfo._fields_:

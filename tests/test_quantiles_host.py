@@ -39,7 +39,7 @@ def test_library_exports_the_entry():
     engine.build()
     assert 'simplyp_quantiles' in engine.ABI_SYMBOLS
     assert hasattr(engine.lib(), 'simplyp_quantiles')
-    assert engine.lib().simplyp_abi_version() == abi.ABI_VERSION == 17
+    assert engine.lib().simplyp_abi_version() == abi.ABI_VERSION == 18
 
 
 def test_quantile_info_layout(tmp_path):

@@ -243,7 +243,7 @@ def test_exports_and_layout(tmp_path):
     assert declared == {'simplyp_scores', 'simplyp_predictive_scores'}
     for name in declared:
         assert name in engine.ABI_SYMBOLS and hasattr(L, name), name
-    assert L.simplyp_abi_version() == abi.ABI_VERSION == 17
+    assert L.simplyp_abi_version() == abi.ABI_VERSION == 18
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % HEADER, 'int main(void){',
              'printf("size %zu\\n", sizeof(simplyp_score_info));']
     for f, _ in abi.ScoreInfo._fields_:

@@ -36,7 +36,7 @@ def test_library_exports_the_entry():
     engine.build()
     assert 'simplyp_time_quantiles' in engine.ABI_SYMBOLS
     assert hasattr(engine.lib(), 'simplyp_time_quantiles')
-    assert engine.lib().simplyp_abi_version() == abi.ABI_VERSION == 17
+    assert engine.lib().simplyp_abi_version() == abi.ABI_VERSION == 18
     assert abi.TQ_DERIVED == 64 and abi.TQ_DERIVED_SERIES == ['Q_cumecs', 'SS_mgl', 'TDP_mgl', 'PP_mgl', 'TP_mgl', 'SRP_mgl']
 
 
