@@ -2,9 +2,11 @@
  * simplyp_controller.h -- the constants of the knee-aware step controller of integrator 2
  * (SIMPLYP_INTEG_CASHKARP_AUG), in ONE place.
  *
- * Plain C macros, no code: included by the device kernels (simplyp_amd/csrc/simplyp_kernels.hip.h: SysAug::*, read by
- * ck_day<SysAug> and ck_day_quad) and by the CPU oracle (oracle/simplyp_oracle.c: cashkarp_aug_day), so that the copies of
- * the controller cannot drift apart.  Not part of the C ABI: nothing here is visible to a caller of libsimplyp_hip.so.
+ * Plain C macros, no code: included by the device kernels (simplyp_amd/csrc/simplyp_kernels.hip.h: SysAug::* and the shared
+ * ck_* pieces -- ck_open_step, ck_propose, ck_choose_pair, ck_damping, ck_step_factor -- that the one-lane
+ * kernel ck_day<SysAug> and the four-lane kernel ck_day_quad both call) and by the CPU oracle (oracle/simplyp_oracle.c:
+ * cashkarp_aug_day), so that the device's one statement of the controller and the oracle's independent restatement of it cannot
+ * drift apart.  Not part of the C ABI: nothing here is visible to a caller of libsimplyp_hip.so.
  *
  * What they steer: the reference's gate f_x (model.py:23-37) is a smooth step, C1 only -- its second
  * derivative jumps at both ends ("knees") of its 1 %-wide zone.  Three gates sit in the right-hand side: soil box A and S at

@@ -384,7 +384,7 @@ struct SysAug {
     // The step size carried on is not reduced by such a cut.  Wave-level attempts per day on the bench ensemble 22.2 -> 18.7
     // (fewer rejections, and lanes that cross a knee no longer hold their wave for 2-3 extra attempts); inflation stays for
     // knees in the step's last tenth or just beyond its end; knees within its first KNEE_LO are left alone (benign).
-    // DAY_START: a day starts with this share of the step size carried over midnight (see ck_day).
+    // DAY_START: a day starts with this share of the step size carried over midnight (see ck_open_step).
     // (A step aimed at a knee of the groundwater gate keeps a factor KNEE_GW: where the first slope misjudges the crossing
     // time the knee sits well inside the step, and that gate does not forgive it -- one member-day of the 100 000 at 1.5e-6.)
     static constexpr double KNEE_LO = SIMPLYP_CTRL_KNEE_LO, KNEE_HI = SIMPLYP_CTRL_KNEE_HI, KNEE_OVER = SIMPLYP_CTRL_KNEE_OVER,
@@ -524,22 +524,134 @@ struct CkCounters { unsigned rhs, steps, rejected, wave_trips; bool capped, pois
 constexpr int TAB_STRIDE = 26;
 enum { TA21 = 0, TA31, TA32, TA41, TA42, TA43, TA51, TA52, TA53, TA54, TA61, TA62, TA63, TA64, TA65,
        TB1, TB3, TB4, TB6, TE1, TE3, TE4, TE5, TE6, TAB_N };
+// Cash-Karp's coefficients (the second pair's row: SIMPLYP_STIFF_* in include/simplyp_controller.h); E_i = b_i - bhat_i
+struct Tableau { double v[TAB_N]; };
+constexpr Tableau CASH_KARP = {{1.0 / 5, 3.0 / 40, 9.0 / 40, 3.0 / 10, -9.0 / 10, 6.0 / 5, -11.0 / 54, 5.0 / 2, -70.0 / 27, 35.0 / 27,
+                                1631.0 / 55296, 175.0 / 512, 575.0 / 13824, 44275.0 / 110592, 253.0 / 4096,
+                                37.0 / 378, 250.0 / 621, 125.0 / 594, 512.0 / 1771,
+                                37.0 / 378 - 2825.0 / 27648, 250.0 / 621 - 18575.0 / 48384, 125.0 / 594 - 13525.0 / 55296, -277.0 / 14336,
+                                512.0 / 1771 - 1.0 / 4}};
 __device__ __forceinline__ void tableau_to_lds(double* s_tab, int lane)
 {
-    const double ck[TAB_N] = {1.0 / 5, 3.0 / 40, 9.0 / 40, 3.0 / 10, -9.0 / 10, 6.0 / 5, -11.0 / 54, 5.0 / 2, -70.0 / 27, 35.0 / 27,
-                              1631.0 / 55296, 175.0 / 512, 575.0 / 13824, 44275.0 / 110592, 253.0 / 4096,
-                              37.0 / 378, 250.0 / 621, 125.0 / 594, 512.0 / 1771,
-                              37.0 / 378 - 2825.0 / 27648, 250.0 / 621 - 18575.0 / 48384, 125.0 / 594 - 13525.0 / 55296, -277.0 / 14336,
-                              512.0 / 1771 - 1.0 / 4};
+    const Tableau ck = CASH_KARP;
     const double st[TAB_N] = {SIMPLYP_STIFF_A21, SIMPLYP_STIFF_A31, SIMPLYP_STIFF_A32, SIMPLYP_STIFF_A41, SIMPLYP_STIFF_A42, SIMPLYP_STIFF_A43,
                               SIMPLYP_STIFF_A51, SIMPLYP_STIFF_A52, SIMPLYP_STIFF_A53, SIMPLYP_STIFF_A54,
                               SIMPLYP_STIFF_A61, SIMPLYP_STIFF_A62, SIMPLYP_STIFF_A63, SIMPLYP_STIFF_A64, SIMPLYP_STIFF_A65,
                               SIMPLYP_STIFF_B1, SIMPLYP_STIFF_B3, SIMPLYP_STIFF_B4, SIMPLYP_STIFF_B6,
                               SIMPLYP_STIFF_E1, SIMPLYP_STIFF_E3, SIMPLYP_STIFF_E4, SIMPLYP_STIFF_E5, SIMPLYP_STIFF_E6};
-    if (lane < TAB_N) { s_tab[lane] = ck[lane]; s_tab[TAB_STRIDE + lane] = st[lane]; }
+    if (lane < TAB_N) { s_tab[lane] = ck.v[lane]; s_tab[TAB_STRIDE + lane] = st[lane]; }
     __syncthreads();
 }
 
+// ---- The pieces of an adaptive attempt that ck_day (one member per lane) and ck_day_quad (one member per DPP quad) share ----------
+// (the six-stage sweep, the settle, the day's carried state t, h, alive, trip and the flag-dependent end of the step proposal stay
+// written out in each kernel: as shared functions they lengthen the attempt loop, profiles/controller_refactor.md)
+// The constants of an attempt in registers: Cash-Karp's row of the tableau, and two literals of the step proposal.
+template <typename R> struct CkRegs { R w[TAB_N]; R huge, c11; };
+template <bool STIFF, typename R>
+__device__ __forceinline__ void ck_regs(CkRegs<R>& tb)
+{
+    // Keep the tableau in scalar registers across the attempt loop.  Left alone, the compiler re-materialises each 64-bit
+    // literal with two s_mov_b32 right before its use -- free when other waves fill the issue slots, but these kernels run
+    // one wave per SIMD, where every scalar instruction costs a full slot (tools/micro/valu_rates.hip: 2.6 ns, the price of
+    // an fp64 FMA).  Passing the values through an empty asm with an "s" operand makes them opaque: -1.4 % kernel time.
+    // (STIFF reads its coefficients from LDS, see ck_coef: only the two it selects between literals are used from here)
+#pragma unroll
+    for (int i = 0; i < TAB_N; ++i) {
+        tb.w[i] = (R)CASH_KARP.v[i];
+        if constexpr (!STIFF) asm volatile("" : "+s"(tb.w[i]));
+    }
+    tb.huge = sp_huge<R>(); tb.c11 = (R)1.1;
+    asm volatile("" : "+s"(tb.huge));
+    asm volatile("" : "+s"(tb.c11));
+}
+// A coefficient of the attempt's pair.  STIFF: read from this lane's row of the LDS table (row offset toff, set once the attempt's
+// pair is known); else the SGPR constant.
+// (an integer row offset into the __shared__ table, not a pointer: a selected / laundered pointer loses its address space and
+// the reads become flat loads with a full wait behind each)
+template <bool STIFF, typename R>
+__device__ __forceinline__ R ck_coef(const CkRegs<R>& tb, const double* s_tab, const int toff, const int idx)
+{
+    return STIFF ? (R)s_tab[toff + idx] : tb.w[idx];
+}
+// STIFF: this lane's row of the tableau is read from LDS ONE STAGE AHEAD of its use -- what stage s+1 needs is requested before
+// the right-hand side of stage s is evaluated (~60 fp64 instructions: the read's latency), and a scheduling barrier keeps the
+// request there.  Left to the compiler each group of reads sat 5-8 instructions before its s_waitcnt (it sinks them to their
+// uses to save registers): eight exposed LDS round trips per attempt, ~12 % of the network kernel's time
+// (profiles/r04_c4: 2.26 ns per instruction against 2.00 for the single-reach kernel at the same clock and mix).
+template <bool STIFF> __device__ __forceinline__ void ck_fetched() { if constexpr (STIFF) __builtin_amdgcn_sched_barrier(0); }
+
+// The day's opening step.  `rate` (STIFF only) is the reach's relaxation rate cQ Qr**b_Q at midnight.
+template <class SYS, bool STIFF, typename R>
+__device__ __forceinline__ R ck_open_step(const double h_carry, const R T, const R rate)
+{
+    R h = (R)h_carry;
+    // (the step size carried over the day boundary belongs to the smooth end of a day; the forcing jumps at midnight, and the
+    // first attempt of the new day with it was rejected on 85 % of the member-days: SYS::DAY_START of it is the better guess)
+    if constexpr (SYS::KINK_AWARE) h *= (R)SYS::DAY_START;
+    if (!(h > (R)0) || h > T) h = T;
+    if constexpr (STIFF) {
+        // (opts.stiff_pair) ... and at most SIMPLYP_STIFF_Z_START relaxation times of the reach: the day opens with its transient
+        const R h0 = (R)SIMPLYP_STIFF_Z_START * sp_rcp1(rate);
+        h = (h > h0) ? h0 : h;
+    }
+    return h;
+}
+
+// The step an attempt proposes: the carried size, stretched or halved to land on the day's end.  (What hangs on a lane's flags --
+// all that is left of the day on the last attempt the step cap allows, the STIFF cap that attempt is exempt from, zero on a lane
+// that has finished -- stays in the kernels: a bool passed through a function turns the parent's selects into and / or, and the
+// loops of the four-lane STIFF kernel and of integrator 1 came out 3 instructions longer.)
+template <typename R>
+__device__ __forceinline__ R ck_propose(const R h, const R rem, const R c11)
+{
+    R hh = h;
+    hh = (rem < (R)2 * h) ? (R)0.5 * rem : hh;      // (selects, not branches: the loop is long enough without them)
+    hh = (rem <= c11 * h) ? rem : hh;
+    return hh;
+}
+
+// Which pair takes this attempt (STIFF; oracle: erk_aug_day): Cash-Karp unless the step is longer than SIMPLYP_STIFF_Z_ON relaxation
+// times of the reach -- then the second pair, except for an attempt with a knee within reach or aimed at one (what the knee rules
+// were tuned on is Cash-Karp's estimate): that one is shortened to Cash-Karp's stability interval instead.  The choice depends on
+// the member's own state only.  Returns whether the second pair takes it; sets its row offset.
+template <typename R>
+__device__ __forceinline__ bool ck_choose_pair(R& hh, int& toff, const R rate, const bool kneeish, const bool last_chance, const bool alive)
+{
+    const bool longstep = hh * rate > (R)SIMPLYP_STIFF_Z_ON;
+    const bool stiff = longstep && !kneeish;
+    const R hz = (R)SIMPLYP_STIFF_Z_ON * sp_rcp1(rate);
+    hh = (longstep && kneeish && !last_chance && alive) ? hz : hh;
+    toff = stiff ? TAB_STRIDE : 0;
+    return stiff;
+}
+
+// Damping-aware weights (STIFF; include/simplyp_controller.h, SIMPLYP_DAMP_*; oracle: erk_aug_day): what the reach forgets at the
+// rate lam = rate - b_Q (dQr/dt) / Qr is allowed F x the tolerance, F = clamp(min(lam T / PHI, 1 + lam (T - t - h)), 1, FMAX).
+template <typename R>
+__device__ __forceinline__ R ck_damping(const R bQ, const R Qr, const R dQr, const R rate, const R T, const R left)
+{
+    const R qd = (bQ * dQr) * sp_rcp_fast(Qr);
+    R lam = rate - qd;
+    lam = sp_min(lam, rate);
+    const R F = sp_min((lam * T) * (R)(1.0 / SIMPLYP_DAMP_PHI), sp_fma(lam, left, (R)1));
+    return sp_min(sp_max(F, (R)1), (R)SIMPLYP_DAMP_FMAX);
+}
+
+// The step-size factor 0.9 err^(-1/5) in fp32 (v_log_f32 / v_exp_f32): a step-size factor needs no more.  err == 0 gives +inf -> 5;
+// err == inf gives 0 -> 0.2 (err is never NaN: v_max_f64 drops NaNs).
+// (raw v_log_f32 / v_exp_f32: the library versions add denormal-range fix-ups, ~12 instructions, for arguments
+// whose factor is clamped to 5 anyway)
+// (an attempt of the second pair carries a third-order estimate: exponent -1/4)
+template <bool STIFF>
+__device__ __forceinline__ float ck_step_factor(const float err, const bool stiff)
+{
+    const float fexp = (STIFF && stiff) ? (float)SIMPLYP_STIFF_ERR_EXP : -0.2f;
+    const float fac = (float)SIMPLYP_CTRL_SAFETY * __builtin_amdgcn_exp2f(fexp * __builtin_amdgcn_logf(err));
+    return fminf(fmaxf(fac, (float)SIMPLYP_CTRL_FAC_MIN), (float)SIMPLYP_CTRL_FAC_MAX);
+}
+
+// One member per lane.  Lanes that have reached T idle with a zero step until the slowest lane of the wavefront is done.
 template <class SYS, bool STIFF = false>
 __device__ __forceinline__ void ck_day(typename SYS::real (&y)[SYS::NS], double (&yq)[4], const typename SYS::dayconst& c,
                                        const double T_, const double rtol_, const double atol_, int max_steps, double& h_carry,
@@ -548,51 +660,18 @@ __device__ __forceinline__ void ck_day(typename SYS::real (&y)[SYS::NS], double 
     static_assert(!STIFF || SYS::KINK_AWARE, "the second pair exists for the knee-aware fp64 scheme only");
     typedef typename SYS::real R;       // working precision of the stages (the daily integrals yq stay fp64)
     constexpr int NS = SYS::NS;
+    constexpr int RATE = STIFF ? 9 : 0;         // (STIFF) the reach's relaxation rate is the carried state y[9] = cQ Qr**b_Q itself
     const R T = (R)T_, rtol = (R)rtol_, atol = (R)atol_;
     R rtol_aux = rtol, atol_aux = atol;
     if constexpr (SYS::KINK_AWARE) { rtol_aux = (R)SYS::AUX_WEIGHT * rtol; atol_aux = (R)SYS::AUX_WEIGHT * atol; }
-    R a21 = 1.0 / 5;
-    R a31 = 3.0 / 40, a32 = 9.0 / 40;
-    R a41 = 3.0 / 10, a42 = -9.0 / 10, a43 = 6.0 / 5;
-    R a51 = -11.0 / 54, a52 = 5.0 / 2, a53 = -70.0 / 27, a54 = 35.0 / 27;
-    R a61 = 1631.0 / 55296, a62 = 175.0 / 512, a63 = 575.0 / 13824, a64 = 44275.0 / 110592, a65 = 253.0 / 4096;
-    R b1 = 37.0 / 378, b3 = 250.0 / 621, b4 = 125.0 / 594, b6 = 512.0 / 1771;
-    R e1 = 37.0 / 378 - 2825.0 / 27648, e3 = 250.0 / 621 - 18575.0 / 48384,
-      e4 = 125.0 / 594 - 13525.0 / 55296, e5 = -277.0 / 14336, e6 = 512.0 / 1771 - 1.0 / 4;
-    // Keep the tableau in scalar registers across the attempt loop.  Left alone, the compiler re-materialises each 64-bit
-    // literal with two s_mov_b32 right before its use -- free when other waves fill the issue slots, but this kernel runs
-    // one wave per SIMD, where every scalar instruction costs a full slot (tools/micro/valu_rates.hip: 2.6 ns, the price of
-    // an fp64 FMA).  Passing the values through an empty asm with an "s" operand makes them opaque: -1.4 % kernel time.
-#define SP_KEEP_SCALAR(x) asm volatile("" : "+s"(x))
-    if constexpr (!STIFF) {
-    SP_KEEP_SCALAR(a21); SP_KEEP_SCALAR(a31); SP_KEEP_SCALAR(a32); SP_KEEP_SCALAR(a41); SP_KEEP_SCALAR(a42); SP_KEEP_SCALAR(a43);
-    SP_KEEP_SCALAR(a51); SP_KEEP_SCALAR(a52); SP_KEEP_SCALAR(a53); SP_KEEP_SCALAR(a54);
-    SP_KEEP_SCALAR(a61); SP_KEEP_SCALAR(a62); SP_KEEP_SCALAR(a63); SP_KEEP_SCALAR(a64); SP_KEEP_SCALAR(a65);
-    SP_KEEP_SCALAR(b1); SP_KEEP_SCALAR(b3); SP_KEEP_SCALAR(b4); SP_KEEP_SCALAR(b6);
-    SP_KEEP_SCALAR(e1); SP_KEEP_SCALAR(e3); SP_KEEP_SCALAR(e4); SP_KEEP_SCALAR(e5); SP_KEEP_SCALAR(e6);
-    }
-    R huge = sp_huge<R>(), c11 = (R)1.1;
-    SP_KEEP_SCALAR(huge); SP_KEEP_SCALAR(c11);
-#undef SP_KEEP_SCALAR
-    // STIFF: a coefficient is read from this lane's row of the LDS table (row offset toff, set once the attempt's pair is known); else the
-    // SGPR constant
-    // (an integer row offset into the __shared__ table, not a pointer: a selected / laundered pointer loses its address space and
-    // the reads become flat loads with a full wait behind each)
-#define TC(name, idx) (STIFF ? (R)s_tab[toff + (idx)] : name)
+    CkRegs<R> tb;
+    ck_regs<STIFF>(tb);
+    const R huge = tb.huge;
     int toff = 0;
-    R t = 0, h = (R)h_carry;
-    // (the step size carried over the day boundary belongs to the smooth end of a day; the forcing jumps at midnight, and the
-    // first attempt of the new day with it was rejected on 85 % of the member-days: SYS::DAY_START of it is the better guess)
-    if constexpr (SYS::KINK_AWARE) h *= (R)SYS::DAY_START;
-    if (!(h > (R)0) || h > T) h = T;
-    if constexpr (STIFF) {
-        // (opts.stiff_pair) ... and at most SIMPLYP_STIFF_Z_START relaxation times of the reach: the day opens with its transient
-        const R h0 = (R)SIMPLYP_STIFF_Z_START * sp_rcp1(y[9]);
-        h = (h > h0) ? h0 : h;
-    }
-    // attempts made today by every lane that is still alive: lanes attempt in lockstep (one attempt per trip of the loop
-    // below for everyone who has not finished), so one wave-uniform counter serves them all -- and the step cap and the
-    // resync schedule derived from it are scalar branches
+    R t = 0, h = ck_open_step<SYS, STIFF>(h_carry, T, y[RATE]);
+    // attempts made today by every lane that is still alive: lanes attempt in lockstep (one attempt per trip of the loop below for
+    // everyone who has not finished), so one wave-uniform counter serves them all -- and the step cap and the resync schedule
+    // derived from it are scalar branches
     int trip = 0;
     unsigned n_alive = 0, n_acc = 0;       // this lane's attempts and accepted steps today (the counters are settled after the loop)
     bool gave_up_today = false;
@@ -618,26 +697,19 @@ __device__ __forceinline__ void ck_day(typename SYS::real (&y)[SYS::NS], double 
     do {
         ++cnt.wave_trips;                 // one attempt issued for the whole wavefront, whoever still needs it
         const R rem = T - t;
-        R hh = h;
-        hh = (rem < (R)2 * h) ? (R)0.5 * rem : hh;      // (selects, not branches: the loop is long enough without them)
-        hh = (rem <= c11 * h) ? rem : hh;
         const bool last_chance = (trip + 1 >= max_steps);
+        R hh = ck_propose(h, rem, tb.c11);
         if (last_chance) hh = rem;
-        if constexpr (STIFF) {
-            // (opts.stiff_pair) no attempt reaches further than SIMPLYP_STIFF_CAP relaxation times of the reach; the rate is the carried
-            // state y[9] = cQ Qr**b_Q itself
-            const R hcap = (R)SIMPLYP_STIFF_CAP * sp_rcp1(y[9]);
-            hh = (!last_chance && hh > hcap) ? hcap : hh;
-        }
+        // (opts.stiff_pair) no attempt reaches further than SIMPLYP_STIFF_CAP relaxation times of the reach
+        if constexpr (STIFF) { const R hcap = (R)SIMPLYP_STIFF_CAP * sp_rcp1(y[RATE]); hh = (!last_chance && hh > hcap) ? hcap : hh; }
         if (!alive) hh = 0;
 
         R k1[NS], k2[NS], k3[NS], k4[NS], k5[NS], k6[NS], kq[4], yt[NS];
         R sq[4], eq[4];                          // sum b_s kq_s, sum e_s kq_s
-        // stage weights premultiplied by the step (per lane): one FMA per (component, earlier stage)
         SYS::f(y, c, k1, kq);
         if constexpr (!STIFF) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { sq[i] = b1 * kq[i]; if (SYS::QUAD_IN_NORM) eq[i] = e1 * kq[i]; }
+        for (int i = 0; i < 4; ++i) { sq[i] = tb.w[TB1] * kq[i]; if (SYS::QUAD_IN_NORM) eq[i] = tb.w[TE1] * kq[i]; }
         }
         bool targeted = false;
         bool stiff = false;      // this attempt is taken by the stability-optimised pair (STIFF only)
@@ -673,59 +745,43 @@ __device__ __forceinline__ void ck_day(typename SYS::real (&y)[SYS::NS], double 
             // expansive reach: the estimate of a step that starts there is multiplied by EXPAND
             kfac = kfac * ((c.bQ * k1[3] > y[3] * y[9]) ? (R)SYS::EXPAND : (R)1);
             if constexpr (STIFF) {
-                // Which pair takes this attempt (oracle: erk_aug_day): Cash-Karp unless the step is longer than SIMPLYP_STIFF_Z_ON relaxation
-                // times of the reach -- then the second pair, except for an attempt with a knee within reach or aimed at one (what the knee
-                // rules were tuned on is Cash-Karp's estimate): that one is shortened to Cash-Karp's stability interval instead.  The choice
-                // depends on the lane's own state only.
-                const bool longstep = hh * y[9] > (R)SIMPLYP_STIFF_Z_ON;
-                const bool kneeish = cs || gw || targeted;
-                stiff = longstep && !kneeish;
-                const R hz = (R)SIMPLYP_STIFF_Z_ON * sp_rcp1(y[9]);
-                hh = (longstep && kneeish && !last_chance && alive) ? hz : hh;
-                toff = stiff ? TAB_STRIDE : 0;
+                stiff = ck_choose_pair(hh, toff, y[RATE], cs || gw || targeted, last_chance, alive);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) sq[i] = (stiff ? (R)SIMPLYP_STIFF_B1 : b1) * kq[i];      // (first use of the row: see c21 below)
+                for (int i = 0; i < 4; ++i) sq[i] = (stiff ? (R)SIMPLYP_STIFF_B1 : tb.w[TB1]) * kq[i];      // (first use of the row: see c21 below)
             }
         }
-        // STIFF: this lane's row of the tableau is read from LDS ONE STAGE AHEAD of its use -- what stage s+1 needs is requested before
-        // the right-hand side of stage s is evaluated (~60 fp64 instructions: the read's latency), and a scheduling barrier keeps the
-        // request there.  Left to the compiler each group of reads sat 5-8 instructions before its s_waitcnt (it sinks them to their
-        // uses to save registers): eight exposed LDS round trips per attempt, ~12 % of the network kernel's time
-        // (profiles/r04_c4: 2.26 ns per instruction against 2.00 for the single-reach kernel at the same clock and mix).
-#define SP_FETCHED() do { if constexpr (STIFF) __builtin_amdgcn_sched_barrier(0); } while (0)
-        // (what is needed the moment the pair is chosen -- a21, and b1 above -- is a select between two literals, not a read)
-        const R c21 = (STIFF && stiff) ? (R)SIMPLYP_STIFF_A21 : a21;
-        const R c31 = TC(a31, TA31), c32 = TC(a32, TA32);
-        SP_FETCHED();
+        const R c21 = (STIFF && stiff) ? (R)SIMPLYP_STIFF_A21 : tb.w[TA21];
+        const R c31 = ck_coef<STIFF>(tb, s_tab, toff, TA31), c32 = ck_coef<STIFF>(tb, s_tab, toff, TA32);
+        ck_fetched<STIFF>();
         {
             const R h21 = hh * c21;
 #pragma unroll
             for (int i = 0; i < NS; ++i) yt[i] = sp_fma(h21, k1[i], y[i]);
         }
-        const R c41 = TC(a41, TA41), c42 = TC(a42, TA42), c43 = TC(a43, TA43), cb3 = TC(b3, TB3);
-        SP_FETCHED();
+        const R c41 = ck_coef<STIFF>(tb, s_tab, toff, TA41), c42 = ck_coef<STIFF>(tb, s_tab, toff, TA42), c43 = ck_coef<STIFF>(tb, s_tab, toff, TA43), cb3 = ck_coef<STIFF>(tb, s_tab, toff, TB3);
+        ck_fetched<STIFF>();
         SYS::f(yt, c, k2, kq);
         {
             const R h31 = hh * c31, h32 = hh * c32;
 #pragma unroll
             for (int i = 0; i < NS; ++i) yt[i] = sp_fma(h32, k2[i], sp_fma(h31, k1[i], y[i]));
         }
-        const R c51 = TC(a51, TA51), c52 = TC(a52, TA52), c53 = TC(a53, TA53), c54 = TC(a54, TA54), cb4 = TC(b4, TB4);
-        SP_FETCHED();
+        const R c51 = ck_coef<STIFF>(tb, s_tab, toff, TA51), c52 = ck_coef<STIFF>(tb, s_tab, toff, TA52), c53 = ck_coef<STIFF>(tb, s_tab, toff, TA53), c54 = ck_coef<STIFF>(tb, s_tab, toff, TA54), cb4 = ck_coef<STIFF>(tb, s_tab, toff, TB4);
+        ck_fetched<STIFF>();
         SYS::f(yt, c, k3, kq);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { sq[i] = sp_fma(cb3, kq[i], sq[i]); if (SYS::QUAD_IN_NORM) eq[i] = sp_fma(e3, kq[i], eq[i]); }
+        for (int i = 0; i < 4; ++i) { sq[i] = sp_fma(cb3, kq[i], sq[i]); if (SYS::QUAD_IN_NORM) eq[i] = sp_fma(tb.w[TE3], kq[i], eq[i]); }
         {
             const R h41 = hh * c41, h42 = hh * c42, h43 = hh * c43;
 #pragma unroll
             for (int i = 0; i < NS; ++i)
                 yt[i] = sp_fma(h43, k3[i], sp_fma(h42, k2[i], sp_fma(h41, k1[i], y[i])));
         }
-        const R c61 = TC(a61, TA61), c62 = TC(a62, TA62), c63 = TC(a63, TA63), c64 = TC(a64, TA64), c65 = TC(a65, TA65);
-        SP_FETCHED();
+        const R c61 = ck_coef<STIFF>(tb, s_tab, toff, TA61), c62 = ck_coef<STIFF>(tb, s_tab, toff, TA62), c63 = ck_coef<STIFF>(tb, s_tab, toff, TA63), c64 = ck_coef<STIFF>(tb, s_tab, toff, TA64), c65 = ck_coef<STIFF>(tb, s_tab, toff, TA65);
+        ck_fetched<STIFF>();
         SYS::f(yt, c, k4, kq);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { sq[i] = sp_fma(cb4, kq[i], sq[i]); if (SYS::QUAD_IN_NORM) eq[i] = sp_fma(e4, kq[i], eq[i]); }
+        for (int i = 0; i < 4; ++i) { sq[i] = sp_fma(cb4, kq[i], sq[i]); if (SYS::QUAD_IN_NORM) eq[i] = sp_fma(tb.w[TE4], kq[i], eq[i]); }
         {
             const R h51 = hh * c51, h52 = hh * c52, h53 = hh * c53, h54 = hh * c54;
 #pragma unroll
@@ -734,7 +790,7 @@ __device__ __forceinline__ void ck_day(typename SYS::real (&y)[SYS::NS], double 
         }
         SYS::f(yt, c, k5, kq);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) if (SYS::QUAD_IN_NORM) eq[i] = sp_fma(e5, kq[i], eq[i]);
+        for (int i = 0; i < 4; ++i) if (SYS::QUAD_IN_NORM) eq[i] = sp_fma(tb.w[TE5], kq[i], eq[i]);
         {
             const R h61 = hh * c61, h62 = hh * c62, h63 = hh * c63, h64 = hh * c64, h65 = hh * c65;
 #pragma unroll
@@ -744,16 +800,15 @@ __device__ __forceinline__ void ck_day(typename SYS::real (&y)[SYS::NS], double 
         }
         // (the error weights: requested before the last right-hand side, which all six stage derivatives share the register file with --
         // the update weights only after it)
-        const R ce1 = TC(e1, TE1), ce3 = TC(e3, TE3), ce4 = TC(e4, TE4), ce5 = TC(e5, TE5), ce6 = TC(e6, TE6);
-        SP_FETCHED();
+        const R ce1 = ck_coef<STIFF>(tb, s_tab, toff, TE1), ce3 = ck_coef<STIFF>(tb, s_tab, toff, TE3), ce4 = ck_coef<STIFF>(tb, s_tab, toff, TE4), ce5 = ck_coef<STIFF>(tb, s_tab, toff, TE5), ce6 = ck_coef<STIFF>(tb, s_tab, toff, TE6);
+        ck_fetched<STIFF>();
         SYS::f(yt, c, k6, kq);
-        const R cb1 = TC(b1, TB1), cb3u = TC(b3, TB3), cb4u = TC(b4, TB4), cb6 = TC(b6, TB6);
-        SP_FETCHED();
+        const R cb1 = ck_coef<STIFF>(tb, s_tab, toff, TB1), cb3u = ck_coef<STIFF>(tb, s_tab, toff, TB3), cb4u = ck_coef<STIFF>(tb, s_tab, toff, TB4), cb6 = ck_coef<STIFF>(tb, s_tab, toff, TB6);
+        ck_fetched<STIFF>();
         if constexpr (!STIFF) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { sq[i] = sp_fma(cb6, kq[i], sq[i]); if (SYS::QUAD_IN_NORM) eq[i] = sp_fma(e6, kq[i], eq[i]); }
+        for (int i = 0; i < 4; ++i) { sq[i] = sp_fma(cb6, kq[i], sq[i]); if (SYS::QUAD_IN_NORM) eq[i] = sp_fma(tb.w[TE6], kq[i], eq[i]); }
         }
-
         // embedded error estimate and scaled error norm.  The scale uses the Euler predictor y + h k1 for "the new value":
         // the 5th-order increment itself is only formed once the step is accepted (weights premultiplied by the accept mask).
         R err = 0, chk = 0;
@@ -782,15 +837,8 @@ __device__ __forceinline__ void ck_day(typename SYS::real (&y)[SYS::NS], double 
             const R sc = sp_fma(rtol_aux, sp_absmax(y[10], sp_fma(hh, k1[10], y[10])), atol_aux);
             const R ra = sp_abs(he) * sp_rcp_fast(sc);
             if constexpr (STIFF) {
-                // Damping-aware weights (include/simplyp_controller.h, SIMPLYP_DAMP_*; oracle: erk_aug_day): what the reach forgets at the
-                // rate lam = rate - b_Q (dQr/dt) / Qr is allowed F x the tolerance, F = clamp(min(lam T / PHI, 1 + lam (T - t - h)), 1, FMAX).
-                // (Same operations in the same order as ck_day_quad's: the two kernels agree bit for bit.)
                 err_fast = sp_max(err_fast, ra);
-                const R qd = (c.bQ * k1[3]) * sp_rcp_fast(y[3]);
-                R lam = y[9] - qd;
-                lam = sp_min(lam, y[9]);
-                R F = sp_min((lam * T) * (R)(1.0 / SIMPLYP_DAMP_PHI), sp_fma(lam, rem - hh, (R)1));
-                F = sp_min(sp_max(F, (R)1), (R)SIMPLYP_DAMP_FMAX);
+                const R F = ck_damping(c.bQ, y[3], k1[3], y[RATE], T, rem - hh);
                 err = sp_max(err, err_fast * sp_rcp_fast(F));
             } else {
                 err = sp_max(err, ra);
@@ -815,14 +863,7 @@ __device__ __forceinline__ void ck_day(typename SYS::real (&y)[SYS::NS], double 
         const bool bad = !(err < huge) || !(sp_abs(chk) < huge);
 
         ++trip;
-        // 0.9 err^(-1/5) in fp32 (v_log_f32 / v_exp_f32): a step-size factor needs no more.  err == 0 gives +inf -> 5;
-        // err == inf gives 0 -> 0.2 (err is never NaN: v_max_f64 drops NaNs).
-        // (raw v_log_f32 / v_exp_f32: the library versions add denormal-range fix-ups, ~12 instructions, for arguments
-        // whose factor is clamped to 5 anyway)
-        // (an attempt of the second pair carries a third-order estimate: exponent -1/4)
-        const float fexp = (STIFF && stiff) ? (float)SIMPLYP_STIFF_ERR_EXP : -0.2f;
-        float fac = (float)SIMPLYP_CTRL_SAFETY * __builtin_amdgcn_exp2f(fexp * __builtin_amdgcn_logf((float)err));
-        fac = fminf(fmaxf(fac, (float)SIMPLYP_CTRL_FAC_MIN), (float)SIMPLYP_CTRL_FAC_MAX);
+        float fac = ck_step_factor<STIFF>((float)err, stiff);
         const bool accept = alive && !bad && (err <= (R)1 || last_chance);
         bool give_up = false;
         n_alive += alive ? 1u : 0u;
@@ -840,7 +881,8 @@ __device__ __forceinline__ void ck_day(typename SYS::real (&y)[SYS::NS], double 
             if (alive && bad) fac = (float)SIMPLYP_CTRL_FAC_MIN;
 #pragma unroll
             for (int i = 0; i < NS; ++i) {
-                k1[i] = bad ? (R)0 : k1[i]; k3[i] = bad ? (R)0 : k3[i]; k4[i] = bad ? (R)0 : k4[i]; k6[i] = bad ? (R)0 : k6[i];
+                const R z1 = k1[i], z3 = k3[i], z4 = k4[i], z6 = k6[i];      // (read first, then select: no conditional stores)
+                k1[i] = bad ? (R)0 : z1; k3[i] = bad ? (R)0 : z3; k4[i] = bad ? (R)0 : z4; k6[i] = bad ? (R)0 : z6;
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) dq[i] = bad ? (R)0 : dq[i];
@@ -884,8 +926,6 @@ __device__ __forceinline__ void ck_day(typename SYS::real (&y)[SYS::NS], double 
     cnt.steps += n_acc;
     cnt.rejected += n_alive - n_acc - (gave_up_today ? 1u : 0u);
     h_carry = (double)h;
-#undef TC
-#undef SP_FETCHED
 }
 
 // ---------------------------------------------------------------------------------------
@@ -908,7 +948,8 @@ __device__ __forceinline__ void ck_day(typename SYS::real (&y)[SYS::NS], double 
 // lane needs from its quad mates (QsA, QsS, Qg, pbc, pk, the reach's dQr/Qr) travels by DPP quad_perm moves (two 32-bit
 // moves per double, no LDS).  Per-lane coefficient tables (QuadConst) with 0 / 1 / -1 entries select each lane's formula
 // through FMAs that are exact for those entries, so EVERY value is produced by the same IEEE operations in the same order as
-// in SysAug::f / ck_day<SysAug>: results are bit-identical to the one-lane kernels (tested), step sequence included.
+// in SysAug::f, and the attempt itself is the one-lane kernel's (the ck_* pieces above): results are bit-identical to the one-lane
+// kernels (tested), step sequence included.
 // 505 instructions per attempt instead of 747 (tools/isa_stats.py); measured 1.42 x (profiles/r02_experiments.md).
 
 template <int CTRL>
@@ -1019,7 +1060,7 @@ __device__ __forceinline__ void quad_rhs(const double (&x)[3], const QuadConst& 
     qv = __builtin_fma(k.mP, x[0], o);
 }
 
-// ck_day<SysAug> for a quad.  z[7] (the physical states VsA VsS Vg Qr Msus TDPr PPr) and yq[4] hold the member's state on every
+// One member per DPP quad.  z[7] (the physical states VsA VsS Vg Qr Msus TDPr PPr) and yq[4] hold the member's state on every
 // lane of the quad, on entry and on return; aux1 is THIS lane's carried function for the day's start (lane 0: exp(-mu VsA),
 // 1: exp(-mu VsS), 2: Qr**k_M, 3: cQ Qr**b_Q -- evaluated by run_slot at the day boundary, one exponential per lane).
 template <bool STIFF = false>
@@ -1029,36 +1070,14 @@ __device__ __forceinline__ void ck_day_quad(double (&z)[7], const double aux1, d
 {
     typedef double R;
     const bool j_lt2 = j < 2, j_eq2 = j == 2, j_eq3 = j == 3;
-    const QuadConst k = quad_const(c, j);
+    const QuadConst qc = quad_const(c, j);
     const R rtol_aux = SysAug::AUX_WEIGHT * rtol, atol_aux = SysAug::AUX_WEIGHT * atol;
-    R a21 = 1.0 / 5;
-    R a31 = 3.0 / 40, a32 = 9.0 / 40;
-    R a41 = 3.0 / 10, a42 = -9.0 / 10, a43 = 6.0 / 5;
-    R a51 = -11.0 / 54, a52 = 5.0 / 2, a53 = -70.0 / 27, a54 = 35.0 / 27;
-    R a61 = 1631.0 / 55296, a62 = 175.0 / 512, a63 = 575.0 / 13824, a64 = 44275.0 / 110592, a65 = 253.0 / 4096;
-    R b1 = 37.0 / 378, b3 = 250.0 / 621, b4 = 125.0 / 594, b6 = 512.0 / 1771;
-    R e1 = 37.0 / 378 - 2825.0 / 27648, e3 = 250.0 / 621 - 18575.0 / 48384,
-      e4 = 125.0 / 594 - 13525.0 / 55296, e5 = -277.0 / 14336, e6 = 512.0 / 1771 - 1.0 / 4;
-#define SP_KEEP_SCALAR(x) asm volatile("" : "+s"(x))
-    if constexpr (!STIFF) {
-    SP_KEEP_SCALAR(a21); SP_KEEP_SCALAR(a31); SP_KEEP_SCALAR(a32); SP_KEEP_SCALAR(a41); SP_KEEP_SCALAR(a42); SP_KEEP_SCALAR(a43);
-    SP_KEEP_SCALAR(a51); SP_KEEP_SCALAR(a52); SP_KEEP_SCALAR(a53); SP_KEEP_SCALAR(a54);
-    SP_KEEP_SCALAR(a61); SP_KEEP_SCALAR(a62); SP_KEEP_SCALAR(a63); SP_KEEP_SCALAR(a64); SP_KEEP_SCALAR(a65);
-    SP_KEEP_SCALAR(b1); SP_KEEP_SCALAR(b3); SP_KEEP_SCALAR(b4); SP_KEEP_SCALAR(b6);
-    SP_KEEP_SCALAR(e1); SP_KEEP_SCALAR(e3); SP_KEEP_SCALAR(e4); SP_KEEP_SCALAR(e5); SP_KEEP_SCALAR(e6);
-    }
-    R huge = sp_huge<R>(), c11 = (R)1.1;
-    SP_KEEP_SCALAR(huge); SP_KEEP_SCALAR(c11);
-#undef SP_KEEP_SCALAR
-#define TC(name, idx) (STIFF ? s_tab[toff + (idx)] : name)
+    CkRegs<R> tb;
+    ck_regs<STIFF>(tb);
+    const R huge = tb.huge;
     int toff = 0;
-    R t = 0, h = (R)h_carry * SysAug::DAY_START;
-    if (!(h > (R)0) || h > T) h = T;
-    if constexpr (STIFF) {
-        // ck_day<SysAug, true>'s cap on the day's first step: the reach lane's carried function is the rate cQ Qr**b_Q
-        const R h0 = quad_bcast<3>(SIMPLYP_STIFF_Z_START * sp_rcp1(aux1));
-        h = (h > h0) ? h0 : h;
-    }
+    // (STIFF) the reach lane's carried function is the reach's relaxation rate cQ Qr**b_Q
+    R t = 0, h = ck_open_step<SysAug, STIFF>(h_carry, T, STIFF ? quad_bcast<3>(aux1) : (R)0);
     int trip = 0;
     unsigned n_alive = 0, n_acc = 0;
     bool gave_up_today = false;
@@ -1091,26 +1110,21 @@ __device__ __forceinline__ void ck_day_quad(double (&z)[7], const double aux1, d
     do {
         ++cnt.wave_trips;
         const R rem = T - t;
-        R hh = h;
-        hh = (rem < (R)2 * h) ? (R)0.5 * rem : hh;
-        hh = (rem <= c11 * h) ? rem : hh;
         const bool last_chance = (trip + 1 >= max_steps);
+        const R rate = STIFF ? quad_bcast<3>(y[1]) : (R)0;       // (STIFF) the reach lane holds the rate cQ Qr**b_Q (its slot 1)
+        R hh = ck_propose(h, rem, tb.c11);
         if (last_chance) hh = rem;
-        if constexpr (STIFF) {
-            // ck_day<SysAug, true>'s cap: the reach lane holds the rate cQ Qr**b_Q (its slot 1)
-            const R hcap = quad_bcast<3>(SIMPLYP_STIFF_CAP * sp_rcp1(y[1]));
-            hh = (!last_chance && hh > hcap) ? hcap : hh;
-        }
+        if constexpr (STIFF) { const R hcap = (R)SIMPLYP_STIFF_CAP * sp_rcp1(rate); hh = (!last_chance && hh > hcap) ? hcap : hh; }
         if (!alive) hh = 0;
 
         R k1[3], k2[3], k3[3], k4[3], k5[3], k6[3], kq, yt[3];
         R sq;
-        quad_rhs(y, k, j_lt2, j_eq2, k1, kq);
-        if constexpr (!STIFF) sq = b1 * kq;
+        quad_rhs(y, qc, j_lt2, j_eq2, k1, kq);
+        if constexpr (!STIFF) sq = tb.w[TB1] * kq;
         bool targeted = false;
         bool kneeish = false, stiff = false;
         R kfac = 1.0;
-        // Knee logic of ck_day<SysAug>, with a wave-uniform shortcut in front.  This lane's gate argument moves along the first
+        // The knee logic (SysAug::KINK_AWARE), with a wave-uniform shortcut in front.  This lane's gate argument moves along the first
         // slope as g(t) = g + sl t; it has a knee (g = 0 or g = gd) at a time in (a, b) exactly when g(a) and g(b), or g(a) - gd
         // and g(b) - gd, differ in sign -- four FMAs and two sign tests, no reciprocal.  With (a, b) = (0.9 KNEE_LO hh,
         // 1.1 KINK_REACH hh), a window 10 % wider on both sides than everything the logic below looks at (its times carry the
@@ -1118,17 +1132,17 @@ __device__ __forceinline__ void ck_day_quad(double (&z)[7], const double aux1, d
         // leave the step alone (no targeting, factor 1): skipping it then changes nothing, bit for bit.  The waves this kernel
         // exists for carry 1 to 16 members and most of their attempts are far from every knee (a 64-member wave of the one-lane
         // kernel nearly always has some lane near one: no shortcut there).
-        const R g = sp_fma(y[0] - k.eoff, k.gs, k.g0), sl = k1[0] * k.gs;
-        const R gdg = k.gd - g;
+        const R g = sp_fma(y[0] - qc.eoff, qc.gs, qc.g0), sl = k1[0] * qc.gs;
+        const R gdg = qc.gd - g;
         bool near_knee;
         {
-            const R ta = (0.9 * SysAug::KNEE_LO) * hh, tb = (1.1 * SysAug::KINK_REACH) * hh;
-            const R e0 = sp_fma(sl, ta, g), e1 = sp_fma(sl, tb, g);
-            const R f0 = sp_fma(sl, ta, -gdg), f1 = sp_fma(sl, tb, -gdg);
+            const R ta = (0.9 * SysAug::KNEE_LO) * hh, tz = (1.1 * SysAug::KINK_REACH) * hh;
+            const R e0 = sp_fma(sl, ta, g), e1 = sp_fma(sl, tz, g);
+            const R f0 = sp_fma(sl, ta, -gdg), f1 = sp_fma(sl, tz, -gdg);
             near_knee = (sp_sign_xor(e0, e1) | sp_sign_xor(f0, f1)) < 0;
         }
         if (__any(near_knee)) {
-            // times to the knees along the first slope, as in ck_day<SysAug>: this lane's gate, then the quad's minimum
+            // times to the knees along the first slope: this lane's gate, then the quad's minimum
             const R tlo = SysAug::KNEE_LO * hh;
             const R r = sp_rcp_fast(sl);
             const R t0 = (0.0 - g) * r, t1 = gdg * r;
@@ -1142,7 +1156,7 @@ __device__ __forceinline__ void ck_day_quad(double (&z)[7], const double aux1, d
             // what the lanes of the quad see within KINK_REACH x the step (1: a soil knee, 2: a groundwater knee, 4: Vg / T_g
             // below the upper knee of its gate), OR-ed; then the one-lane kernel's choice of factor
             const R look = SysAug::KINK_REACH * hh;
-            int kink = (tn < look ? k.kbit : 0) | (gdg > 0.0 ? k.lowbit : 0);
+            int kink = (tn < look ? qc.kbit : 0) | (gdg > 0.0 ? qc.lowbit : 0);
             kink |= __builtin_amdgcn_update_dpp(0, kink, SP_QP(1, 0, 3, 2), 0xf, 0xf, true);
             kink |= __builtin_amdgcn_update_dpp(0, kink, SP_QP(2, 3, 0, 1), 0xf, 0xf, true);
             const bool gw = (kink & 2) != 0 || (kink & 5) == 5;
@@ -1151,39 +1165,32 @@ __device__ __forceinline__ void ck_day_quad(double (&z)[7], const double aux1, d
         }
         {
             // expansive reach (SysAug::EXPAND): the reach lane holds Qr, cQ Qr**b_Q and the first slope of Qr; its verdict goes to the quad
-            const int expanding = __builtin_amdgcn_update_dpp(0, (k.c1 * k1[0] > y[0] * y[1]) ? 1 : 0, SP_QP(3, 3, 3, 3), 0xf, 0xf, true);
+            const int expanding = __builtin_amdgcn_update_dpp(0, (qc.c1 * k1[0] > y[0] * y[1]) ? 1 : 0, SP_QP(3, 3, 3, 3), 0xf, 0xf, true);
             kfac = kfac * (expanding ? SysAug::EXPAND : 1.0);
         }
         if constexpr (STIFF) {
-            // ck_day<SysAug, true>'s choice of the pair, from the reach lane's rate (same operations: bit-identical decisions)
-            const bool longstep = quad_bcast<3>(hh * y[1]) > SIMPLYP_STIFF_Z_ON;
-            stiff = longstep && !kneeish;
-            const R hz = quad_bcast<3>(SIMPLYP_STIFF_Z_ON * sp_rcp1(y[1]));
-            hh = (longstep && kneeish && !last_chance && alive) ? hz : hh;
-            toff = stiff ? TAB_STRIDE : 0;
-            sq = (stiff ? (R)SIMPLYP_STIFF_B1 : b1) * kq;
+            stiff = ck_choose_pair(hh, toff, rate, kneeish, last_chance, alive);
+            sq = (stiff ? (R)SIMPLYP_STIFF_B1 : tb.w[TB1]) * kq;
         }
-        // (STIFF: the tableau row is read from LDS one stage ahead of its use, as in ck_day)
-#define SP_FETCHED() do { if constexpr (STIFF) __builtin_amdgcn_sched_barrier(0); } while (0)
-        const R c21 = (STIFF && stiff) ? (R)SIMPLYP_STIFF_A21 : a21;
-        const R c31 = TC(a31, TA31), c32 = TC(a32, TA32);
-        SP_FETCHED();
+        const R c21 = (STIFF && stiff) ? (R)SIMPLYP_STIFF_A21 : tb.w[TA21];
+        const R c31 = ck_coef<STIFF>(tb, s_tab, toff, TA31), c32 = ck_coef<STIFF>(tb, s_tab, toff, TA32);
+        ck_fetched<STIFF>();
         {
             const R h21 = hh * c21;
 #pragma unroll
             for (int i = 0; i < 3; ++i) yt[i] = sp_fma(h21, k1[i], y[i]);
         }
-        const R c41 = TC(a41, TA41), c42 = TC(a42, TA42), c43 = TC(a43, TA43), cb3 = TC(b3, TB3);
-        SP_FETCHED();
-        quad_rhs(yt, k, j_lt2, j_eq2, k2, kq);
+        const R c41 = ck_coef<STIFF>(tb, s_tab, toff, TA41), c42 = ck_coef<STIFF>(tb, s_tab, toff, TA42), c43 = ck_coef<STIFF>(tb, s_tab, toff, TA43), cb3 = ck_coef<STIFF>(tb, s_tab, toff, TB3);
+        ck_fetched<STIFF>();
+        quad_rhs(yt, qc, j_lt2, j_eq2, k2, kq);
         {
             const R h31 = hh * c31, h32 = hh * c32;
 #pragma unroll
             for (int i = 0; i < 3; ++i) yt[i] = sp_fma(h32, k2[i], sp_fma(h31, k1[i], y[i]));
         }
-        const R c51 = TC(a51, TA51), c52 = TC(a52, TA52), c53 = TC(a53, TA53), c54 = TC(a54, TA54), cb4 = TC(b4, TB4);
-        SP_FETCHED();
-        quad_rhs(yt, k, j_lt2, j_eq2, k3, kq);
+        const R c51 = ck_coef<STIFF>(tb, s_tab, toff, TA51), c52 = ck_coef<STIFF>(tb, s_tab, toff, TA52), c53 = ck_coef<STIFF>(tb, s_tab, toff, TA53), c54 = ck_coef<STIFF>(tb, s_tab, toff, TA54), cb4 = ck_coef<STIFF>(tb, s_tab, toff, TB4);
+        ck_fetched<STIFF>();
+        quad_rhs(yt, qc, j_lt2, j_eq2, k3, kq);
         sq = sp_fma(cb3, kq, sq);
         {
             const R h41 = hh * c41, h42 = hh * c42, h43 = hh * c43;
@@ -1191,9 +1198,9 @@ __device__ __forceinline__ void ck_day_quad(double (&z)[7], const double aux1, d
             for (int i = 0; i < 3; ++i)
                 yt[i] = sp_fma(h43, k3[i], sp_fma(h42, k2[i], sp_fma(h41, k1[i], y[i])));
         }
-        const R c61 = TC(a61, TA61), c62 = TC(a62, TA62), c63 = TC(a63, TA63), c64 = TC(a64, TA64), c65 = TC(a65, TA65);
-        SP_FETCHED();
-        quad_rhs(yt, k, j_lt2, j_eq2, k4, kq);
+        const R c61 = ck_coef<STIFF>(tb, s_tab, toff, TA61), c62 = ck_coef<STIFF>(tb, s_tab, toff, TA62), c63 = ck_coef<STIFF>(tb, s_tab, toff, TA63), c64 = ck_coef<STIFF>(tb, s_tab, toff, TA64), c65 = ck_coef<STIFF>(tb, s_tab, toff, TA65);
+        ck_fetched<STIFF>();
+        quad_rhs(yt, qc, j_lt2, j_eq2, k4, kq);
         sq = sp_fma(cb4, kq, sq);
         {
             const R h51 = hh * c51, h52 = hh * c52, h53 = hh * c53, h54 = hh * c54;
@@ -1201,9 +1208,9 @@ __device__ __forceinline__ void ck_day_quad(double (&z)[7], const double aux1, d
             for (int i = 0; i < 3; ++i)
                 yt[i] = sp_fma(h54, k4[i], sp_fma(h53, k3[i], sp_fma(h52, k2[i], sp_fma(h51, k1[i], y[i]))));
         }
-        const R ce1 = TC(e1, TE1), ce3 = TC(e3, TE3), ce4 = TC(e4, TE4), ce5 = TC(e5, TE5), ce6 = TC(e6, TE6);
-        SP_FETCHED();
-        quad_rhs(yt, k, j_lt2, j_eq2, k5, kq);
+        const R ce1 = ck_coef<STIFF>(tb, s_tab, toff, TE1), ce3 = ck_coef<STIFF>(tb, s_tab, toff, TE3), ce4 = ck_coef<STIFF>(tb, s_tab, toff, TE4), ce5 = ck_coef<STIFF>(tb, s_tab, toff, TE5), ce6 = ck_coef<STIFF>(tb, s_tab, toff, TE6);
+        ck_fetched<STIFF>();
+        quad_rhs(yt, qc, j_lt2, j_eq2, k5, kq);
         {
             const R h61 = hh * c61, h62 = hh * c62, h63 = hh * c63, h64 = hh * c64, h65 = hh * c65;
 #pragma unroll
@@ -1211,14 +1218,13 @@ __device__ __forceinline__ void ck_day_quad(double (&z)[7], const double aux1, d
                 yt[i] = sp_fma(h65, k5[i], sp_fma(h64, k4[i], sp_fma(h63, k3[i],
                         sp_fma(h62, k2[i], sp_fma(h61, k1[i], y[i])))));
         }
-        const R cb1 = TC(b1, TB1), cb3u = TC(b3, TB3), cb4u = TC(b4, TB4), cb6 = TC(b6, TB6);
-        SP_FETCHED();
-        quad_rhs(yt, k, j_lt2, j_eq2, k6, kq);
+        const R cb1 = ck_coef<STIFF>(tb, s_tab, toff, TB1), cb3u = ck_coef<STIFF>(tb, s_tab, toff, TB3), cb4u = ck_coef<STIFF>(tb, s_tab, toff, TB4), cb6 = ck_coef<STIFF>(tb, s_tab, toff, TB6);
+        ck_fetched<STIFF>();
+        quad_rhs(yt, qc, j_lt2, j_eq2, k6, kq);
         sq = sp_fma(cb6, kq, sq);
-
         // error norm over the 7 physical states = slots 0 and 2 of the quad (lane 3's slot 2 is identically 0 and adds
         // nothing); the maximum over the quad is exact in any order.  The finiteness test looks at the increments of the reach
-        // states (Qr, Msus, TDPr, PPr), as ck_day<SysAug>'s `chk` does: a non-finite one makes the lane's error infinite.
+        // states (Qr, Msus, TDPr, PPr): a non-finite one makes the lane's error infinite.
         const R he1 = hh * ce1, he3 = hh * ce3, he4 = hh * ce4, he5 = hh * ce5, he6 = hh * ce6;
         R err = 0, err_fast = 0;
         R he_s[3];
@@ -1226,11 +1232,11 @@ __device__ __forceinline__ void ck_day_quad(double (&z)[7], const double aux1, d
         for (int i = 0; i < 3; i += 2) {
             const R he = sp_fma(he1, k1[i], sp_fma(he3, k3[i], sp_fma(he4, k4[i], sp_fma(he5, k5[i], he6 * k6[i]))));
             he_s[i] = he;
-            // slot 0 of the soil lanes is measured from field capacity, like ck_day<SysAug> does for components 0 and 1
-            const R ref = (i == 0) ? y[0] - k.eoff : y[i];
+            // slot 0 of the soil lanes is measured from field capacity (SysAug::SOIL_REL)
+            const R ref = (i == 0) ? y[0] - qc.eoff : y[i];
             const R pred = sp_fma(hh, k1[i], ref);
             R w = sp_absmax(ref, pred);
-            if (i == 0) w = sp_max(w, k.efloor);
+            if (i == 0) w = sp_max(w, qc.efloor);
             const R sc = sp_fma(rtol, w, atol);
             const R ri = sp_abs(he) * sp_rcp_fast(sc);
             // (STIFF: slot 0 of the reach lane -- Qr -- and slot 2 -- the masses -- are what the reach forgets: see below)
@@ -1240,15 +1246,11 @@ __device__ __forceinline__ void ck_day_quad(double (&z)[7], const double aux1, d
             // Qr**k_M (slot 1 of the groundwater lane) in the norm at AUX_WEIGHT x the tolerance; x 0 on the other lanes
             const R he = sp_fma(he1, k1[1], sp_fma(he3, k3[1], sp_fma(he4, k4[1], sp_fma(he5, k5[1], he6 * k6[1]))));
             const R sc = sp_fma(rtol_aux, sp_absmax(y[1], sp_fma(hh, k1[1], y[1])), atol_aux);
-            const R ra = (sp_abs(he) * sp_rcp_fast(sc)) * k.auxm;
+            const R ra = (sp_abs(he) * sp_rcp_fast(sc)) * qc.auxm;
             if constexpr (STIFF) {
-                // ck_day<SysAug, true>'s damping-aware weights: the factor from the reach lane's Qr (slot 0), rate (slot 1) and dQr/dt
+                // the damping-aware weights' factor from the reach lane's Qr (slot 0), rate (slot 1) and dQr/dt
                 err_fast = sp_max(err_fast, ra);
-                const R qd = (c.bQ * k1[0]) * sp_rcp_fast(y[0]);
-                R lam = y[1] - qd;
-                lam = sp_min(lam, y[1]);
-                R F = sp_min((lam * T) * (R)(1.0 / SIMPLYP_DAMP_PHI), sp_fma(lam, rem - hh, (R)1));
-                F = sp_min(sp_max(F, (R)1), (R)SIMPLYP_DAMP_FMAX);
+                const R F = ck_damping(c.bQ, y[0], k1[0], y[1], T, rem - hh);
                 const R G = quad_bcast<3>(sp_rcp_fast(F));
                 err = sp_max(err, err_fast * G);
             } else {
@@ -1264,11 +1266,8 @@ __device__ __forceinline__ void ck_day_quad(double (&z)[7], const double aux1, d
         err *= kfac;
         R dq = hh * sq;
         const bool bad = !(err < huge);
-
         ++trip;
-        const float fexp = (STIFF && stiff) ? (float)SIMPLYP_STIFF_ERR_EXP : -0.2f;
-        float fac = (float)SIMPLYP_CTRL_SAFETY * __builtin_amdgcn_exp2f(fexp * __builtin_amdgcn_logf((float)err));
-        fac = fminf(fmaxf(fac, (float)SIMPLYP_CTRL_FAC_MIN), (float)SIMPLYP_CTRL_FAC_MAX);
+        float fac = ck_step_factor<STIFF>((float)err, stiff);
         const bool accept = alive && !bad && (err <= (R)1 || last_chance);
         bool give_up = false;
         n_alive += alive ? 1u : 0u;
@@ -1281,7 +1280,8 @@ __device__ __forceinline__ void ck_day_quad(double (&z)[7], const double aux1, d
             if (alive && bad) fac = (float)SIMPLYP_CTRL_FAC_MIN;
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
-                k1[i] = bad ? (R)0 : k1[i]; k3[i] = bad ? (R)0 : k3[i]; k4[i] = bad ? (R)0 : k4[i]; k6[i] = bad ? (R)0 : k6[i];
+                const R z1 = k1[i], z3 = k3[i], z4 = k4[i], z6 = k6[i];      // (read first, then select: no conditional stores)
+                k1[i] = bad ? (R)0 : z1; k3[i] = bad ? (R)0 : z3; k4[i] = bad ? (R)0 : z4; k6[i] = bad ? (R)0 : z6;
             }
             dq = bad ? (R)0 : dq;
         }
@@ -1326,8 +1326,6 @@ __device__ __forceinline__ void ck_day_quad(double (&z)[7], const double aux1, d
     z[0] = quad_bcast<0>(y[0]); z[1] = quad_bcast<1>(y[0]); z[2] = quad_bcast<2>(y[0]); z[3] = quad_bcast<3>(y[0]);
     z[4] = quad_bcast<0>(y[2]); z[5] = quad_bcast<1>(y[2]); z[6] = quad_bcast<2>(y[2]);
     yq[0] = quad_bcast<3>(yqv); yq[1] = quad_bcast<0>(yqv); yq[2] = quad_bcast<1>(yqv); yq[3] = quad_bcast<2>(yqv);
-#undef TC
-#undef SP_FETCHED
 }
 #undef SP_QP
 

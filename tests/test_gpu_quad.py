@@ -106,6 +106,24 @@ def test_quad_status_words(engine0):
     assert np.array_equal(got.cpu().numpy()[..., ok], ref.cpu().numpy()[..., ok], equal_nan=True)
 
 
+def test_quad_step_cap_on_a_network(engine0):
+    """The step cap on a reach network: the default solver switches the second pair on there, so the last-chance attempt, the
+    flag and the give-up of both pairs are compared between the one-lane and the four-lane kernel.  At 12 attempts a day every
+    member of this network is also STATUS_NONFINITE (status 3 on all 8, with one lane and with four), so the table comparison below
+    covers no member here: what this case pins are the status words, member_rhs and the counters."""
+    import torch
+    m = perturbed('confluence3_nc_2004', 8, solver=dict(max_steps=12))
+    (ref, rs, rst, rhs1), (got, gs, gst, rhs4) = both(engine0, m)
+    assert rst['stiff_pair'] == 1 and gst['stiff_pair'] == 1
+    # (at 12 attempts a day every member of this network also gives up somewhere: the same attempts, member by member, all the same)
+    assert bool(torch.equal(rhs4, rhs1))
+    assert (gst['rhs_evals'], gst['steps'], gst['rejected']) == (rst['rhs_evals'], rst['steps'], rst['rejected'])
+    rs, gs = rs.cpu().numpy(), gs.cpu().numpy()
+    assert np.array_equal(rs, gs) and (rs & abi.STATUS_STEPCAP).any()
+    ok = (rs & abi.STATUS_NONFINITE) == 0
+    assert np.array_equal(got.cpu().numpy()[..., ok], ref.cpu().numpy()[..., ok], equal_nan=True)
+
+
 def test_quad_is_chosen_for_small_ensembles_only(engine0):
     n_simd = 1024
     m = perturbed('tarland_2004_static', 300, out_mask=marshal.MASK_REACH5)
