@@ -51,7 +51,9 @@ extern "C" {
  * forcing_shift_group_of_day and forcing_shift_groups are appended to simplyp_opts after forcing_table (all zero = off), as the
  * forcing_* fields before them were; no entry point is added and none changes.
  * 18: simplyp_order_members, the members' lane-slot order of a balanced run from a caller-given cost table; nothing existing
- * changes. */
+ * changes.
+ * 18 still with simplyp_eval_units' which = 6 (the right-hand sides) and which = 7 (the step-rule pieces): adding values of
+ * `which` is purely additive -- the values before keep their rows, and what was refused as unknown (8 and above) still is. */
 #define SIMPLYP_ABI_VERSION 18
 
 typedef enum {
@@ -1337,6 +1339,24 @@ int simplyp_pf_jitter(simplyp_ctx* ctx, int32_t E, int32_t n_dim, uint64_t seed,
  *   which = 3   in  device [n][1]  = x            out device [n][1] = log(x)
  *   which = 4   in  device [n][1]  = x            out device [n][3] = the raw hardware reciprocal, one Newton step, two steps
  *   which = 5   in  device [n][2]  = q, b         out device [n][1] = q**b as the right-hand side forms it, exp(b log(q))
+ * and the device's four statements of the model's right-hand side and the pieces of the step rule (again the inline functions the
+ * time-stepping kernels call), so that each can be held to a plain statement of the equations point by point:
+ *   which = 6   in  device [n][51] = the carried states VsA VsS Vg Vr Qr Msus TDPr PPr, then the 43 parameters of the reference's
+ *                                    ode_f in the order of tests/golden/unit_vectors.npz 'ode_p_names' (NC_type as 0 / 1 / 2)
+ *               out device [n][77] = the literal form: dy[8], q[4] (the daily integrands Qr, Msus Qr/Vr, TDPr Qr/Vr, PPr Qr/Vr);
+ *                                    the augmented form: dz[11] (VsA VsS Vg Qr Msus TDPr PPr, exp(-mu VsA), exp(-mu VsS),
+ *                                    cQ Qr**b_Q, Qr**k_M), q[4] and the four auxiliary states it was given, formed as a run forms
+ *                                    them before a day; the four-lane form: each lane's d[3] and integrand (16 values), then
+ *                                    the augmented form on the auxiliary states those lanes formed: dz[11], q[4]; the fp32 form on
+ *                                    constants and states rounded to float: dz[11], q[4], widened.  The day constants are
+ *                                    assembled by the functions a run assembles them with.  Four lanes per row.
+ *   which = 7   in  device [n][19] = the opening step's h_carry, T, rate; the proposal's h, rem, 1.1; the pair choice's hh, rate,
+ *                                    kneeish, last_chance, alive; the damping weight's b_Q, Qr, dQr/dt, rate, T, what is left of
+ *                                    the day; the step factor's err, stiff -- flags as 0 / 1
+ *               out device [n][11] = the opening step of integrator 2, of integrator 2 with the second pair, of integrator 1, of
+ *                                    integrator 3 (fp32); the proposed step; hh after the pair choice, the tableau's row offset,
+ *                                    the returned flag; the damping factor F; the step-size factor without and with the second
+ *                                    pair (fp32, widened)
  * Any other value of `which` is SIMPLYP_ERR_ARG.
  * Synchronous.  Not on the hot path.
  */

@@ -64,6 +64,25 @@ def ode_f(y12, p43):
     return dy
 
 
+def _ode_aug(fn, y12, p43):
+    y = np.ascontiguousarray(y12, dtype=np.float64)
+    p = np.ascontiguousarray(p43, dtype=np.float64)
+    dz = np.empty(15)
+    fn(_p(y, C.c_double), _p(p, C.c_double), _p(dz, C.c_double))
+    return dz
+
+
+def ode_aug(y12, p43):
+    """The augmented form at the state ``y12`` (Vr, slot 3, is not read): d/dt of VsA VsS Vg Qr Msus TDPr PPr, exp(-mu VsA),
+    exp(-mu VsS), Qr**b_Q, Qr**k_M, then the four daily integrands."""
+    return _ode_aug(lib().simplyp_oracle_ode_aug, y12, p43)
+
+
+def ode_aug_f32(y12, p43):
+    """The fp32 mirror of the augmented form, states and constants rounded to float as a day of integrator 3 rounds them."""
+    return _ode_aug(lib().simplyp_oracle_ode_aug_f32, y12, p43)
+
+
 def run(forcing, doy, member_params, reach_params, up_ptr, up_idx, opts, forcing_of_member=None,
         out_reaches=None, n_threads=1):
     """Same contract as simplyp_amd.engine.Engine.run, on host arrays.

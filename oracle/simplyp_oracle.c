@@ -951,7 +951,7 @@ void simplyp_oracle_soilp(const double* in10, double* out2)
                       &out2[0], &out2[1]);
 }
 
-void simplyp_oracle_ode_f(const double* y12, const double* p43, double* dy12)
+static void params_from_p43(const double* p43, ode_params* pp)
 {   /* p43 in the order of unit_vectors.npz 'ode_p_names' */
     ode_params p;
     p.P = p43[0]; p.E = p43[1]; p.mu = p43[2]; p.Qq_i = p43[3]; p.Qr_US_i = p43[4];
@@ -965,5 +965,44 @@ void simplyp_oracle_ode_f(const double* y12, const double* p43, double* dy12)
     p.conc_TDPs_A = p43[33]; p.conc_TDPs_NC = p43[34]; p.PlabA_i = p43[35]; p.PlabNC_i = p43[36];
     p.Msoil = p43[37]; p.TDPeff = p43[38]; p.TDPg = p43[39]; p.E_PP = p43[40]; p.P_inactive = p43[41];
     p.Qg_min = p43[42];
+    *pp = p;
+}
+
+void simplyp_oracle_ode_f(const double* y12, const double* p43, double* dy12)
+{
+    ode_params p;
+    params_from_p43(p43, &p);
     ode_f(y12, &p, dy12);
+}
+
+/* ode_aug at the state y12 (slot 3, Vr, is not read: the form takes it from its invariant), the auxiliary states and invKv formed
+ * the way erk_aug_day forms them.  dz15 = d/dt of VsA VsS Vg Qr Msus TDPr PPr EA ES pb pk | the four daily integrands. */
+void simplyp_oracle_ode_aug(const double* y12, const double* p43, double* dz15)
+{
+    ode_params p;
+    double z[NZ];
+    params_from_p43(p43, &p);
+    const double Kv = p.L_reach / (p.a_Q * 8.64 * 10000), invKv = 1.0 / Kv;
+    z[0] = y12[0]; z[1] = y12[1]; z[2] = y12[2]; z[3] = y12[4]; z[4] = y12[6]; z[5] = y12[8]; z[6] = y12[10];
+    z[7] = exp(-p.mu * y12[0]); z[8] = exp(-p.mu * y12[1]);
+    z[9] = pow(y12[4], p.b_Q); z[10] = pow(y12[4], p.k_M);
+    z[11] = z[12] = z[13] = z[14] = 0.0;
+    ode_aug(z, &p, invKv, dz15);
+}
+
+/* ode_aug_f32 at the state y12, states and constants rounded to float the way cashkarp_aug_f32_day rounds them; widened. */
+void simplyp_oracle_ode_aug_f32(const double* y12, const double* p43, double* dz15)
+{
+    ode_params p;
+    dayconst_f c;
+    float z[11], dz[11], q[4];
+    params_from_p43(p43, &p);
+    dayconst_from_params(&p, &c);
+    z[0] = (float)y12[0]; z[1] = (float)y12[1]; z[2] = (float)y12[2]; z[3] = (float)y12[4];
+    z[4] = (float)y12[6]; z[5] = (float)y12[8]; z[6] = (float)y12[10];
+    z[7] = (float)exp(-p.mu * y12[0]); z[8] = (float)exp(-p.mu * y12[1]);
+    z[9] = (float)pow(y12[4], p.b_Q); z[10] = (float)pow(y12[4], p.k_M);
+    ode_aug_f32(z, &c, dz, q);
+    for (int i = 0; i < 11; ++i) dz15[i] = (double)dz[i];
+    for (int i = 0; i < 4; ++i) dz15[11 + i] = (double)q[i];
 }

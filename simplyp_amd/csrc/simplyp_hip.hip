@@ -3082,9 +3082,14 @@ int simplyp_memcpy_d2h(simplyp_ctx* ctx, void* dst, const void* src, int64_t byt
 int simplyp_eval_units(simplyp_ctx* ctx, int32_t which, int32_t n, const double* in, double* out)
 {
     return entry(ctx, "simplyp_eval_units", [&](const Entry& e) -> int {
-        if (which < 0 || which > 5 || n < 0 || (n > 0 && (!in || !out))) return e.refuse("bad arguments");
+        if (which < 0 || which > 7 || n < 0 || (n > 0 && (!in || !out))) return e.refuse("bad arguments");
         if (n == 0) return SIMPLYP_OK;
-        hipLaunchKernelGGL(simplyp::eval_units_kernel, dim3(blocks(n, 64)), dim3(64), 0, ctx->stream, (int)which, (int)n, in, out);
+        if (which == 6)             // the right-hand sides: four lanes per row
+            hipLaunchKernelGGL(simplyp::eval_rhs_kernel, dim3(blocks(n, 16)), dim3(64), 0, ctx->stream, (int)n, in, out);
+        else if (which == 7)        // the step-rule pieces
+            hipLaunchKernelGGL(simplyp::eval_step_kernel, dim3(blocks(n, 64)), dim3(64), 0, ctx->stream, (int)n, in, out);
+        else
+            hipLaunchKernelGGL(simplyp::eval_units_kernel, dim3(blocks(n, 64)), dim3(64), 0, ctx->stream, (int)which, (int)n, in, out);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         return SIMPLYP_OK;

@@ -210,6 +210,62 @@ struct DayConst {
     double dgq;         // 0.01 Qg_min: width of the groundwater gate (:121); 0 when Qg_min is 0 (a plain step at 0)
 };
 
+// How a DayConst is assembled, from plain scalars: what run_slot calls per reach and per day, and what the unit kernel of
+// simplyp_eval_units (which = 6) calls to hand the four statements of the right-hand side the constants the run would.
+// The part that is constant over a reach's run.  Kv = L_reach / (a_Q 86400): Vr = Kv Qr**(1 - b_Q)   (model.py:457-459).
+__device__ __forceinline__ void dayconst_reach(DayConst& c, const double mu, const double fc, const double T_s_A, const double T_s_S,
+                                               const double T_g, const double Qg_min, const double beta, const double f_A,
+                                               const double f_S, const double a_Q, const double b_Q, const double k_M,
+                                               const double L_reach, const double TDPg, const double A_catch, const double Kv)
+{
+    c.mu = mu; c.fc = fc; c.inv_d = 1.0 / (0.01 * fc);
+    c.invTsA = 1.0 / T_s_A; c.invTsS = 1.0 / T_s_S;
+    c.invTg = 1.0 / T_g; c.Qgmin = Qg_min;
+    c.inv_dg = (Qg_min * 0.01 > 0.0) ? 1.0 / (Qg_min * 0.01) : 1.0e300;   // threshold 0 -> plain step
+    c.beta = beta; c.fA = f_A; c.fS = f_S;
+    c.omb = 1.0 - beta;
+    c.cQ = a_Q * (8.64 * 10000) / ((1 - b_Q) * L_reach);
+    c.bQ = b_Q; c.kM = k_M;
+    c.tg = TDPg * A_catch;                                                                    // :163
+    c.invKv = 1.0 / Kv;
+    c.wA0 = -fc * c.invTsA; c.wS0 = -fc * c.invTsS; c.s0 = -fc * c.inv_d;
+    c.invKvc = c.invKv / c.cQ;
+    c.dgate = 0.01 * fc;
+    c.dgq = 0.01 * Qg_min;
+}
+
+// The part that changes from day to day (forcing, upstream inputs, erodibility, soil P), after dayconst_reach.
+// wA = f_A (1 - f_NC_A), wNC = f_A f_NC_A + f_S f_NC_S: the TDP source weights (:155-161); p0 = P_inactive / Msoil.
+__device__ __forceinline__ void dayconst_day(DayConst& c, const double P, const double f_quick, const double alpha, const double PET,
+                                             const double Qq, const double QrUS, const double f_Ar, const double f_IG, const double f_S,
+                                             const double Esus_A, const double Esus_IG, const double Esus_S, const double MsusUS,
+                                             const double wA, const double wNC, const double conc_A, const double conc_NC,
+                                             const int nc_type, const double TDPeff, const double TDPrUS, const double Plab_A,
+                                             const double Plab_NC, const double P_inactive, const double invMsoil, const double p0,
+                                             const double E_PP, const double f_NC_Ar, const double f_NC_IG, const double f_NC_S,
+                                             const double PPrUS)
+{
+    c.c0 = P * (1 - f_quick);
+    c.aE = alpha * PET;
+    c.c0m = c.c0 - c.aE;
+    c.qin = Qq + QrUS;
+    c.Esum = f_Ar * Esus_A + f_IG * Esus_IG + f_S * Esus_S;
+    c.MsusUS = MsusUS;
+    {
+        const double tNC = c.omb * wNC * conc_NC;             // soil-water TDP via QsNC (:156-157)
+        c.tA = c.omb * wA * conc_A + (nc_type == 1 ? tNC : 0.0);
+        c.tS = (nc_type == 1 ? 0.0 : tNC);
+        c.tconst = Qq * (wA * conc_A + wNC * conc_NC) + TDPeff + TDPrUS;      // :159-165
+    }
+    {
+        const double pA = (Plab_A + P_inactive) * invMsoil, pN = (Plab_NC + P_inactive) * invMsoil;
+        c.cPP = E_PP * (f_Ar * Esus_A * ((1 - f_NC_Ar) * pA + f_NC_Ar * pN)
+                        + f_IG * Esus_IG * ((1 - f_NC_IG) * pA + f_NC_IG * pN)
+                        + f_S * Esus_S * ((1 - f_NC_S) * p0 + f_NC_S * pN));           // :171-176
+    }
+    c.PPrUS = PPrUS;
+}
+
 // f_x(x, threshold, 0.01) with u = x - threshold and inv_d = 1/(0.01 threshold) (model.py:23-37):
 // 0 below the threshold, 1 above threshold + d, 3s^2 - 2s^3 in between -- as one clamped cubic.
 __device__ __forceinline__ double gate(double u, double inv_d)
@@ -1490,20 +1546,7 @@ __device__ __forceinline__ void run_slot(const KernelArgs& a, double* s_P, doubl
 
         // per-reach pieces of the day constants
         DayConst c;
-        c.mu = mu; c.fc = fc; c.inv_d = 1.0 / (0.01 * fc);
-        c.invTsA = 1.0 / T_s_A; c.invTsS = 1.0 / T_s_S;
-        c.invTg = 1.0 / T_g; c.Qgmin = Qg_min;
-        c.inv_dg = (Qg_min * 0.01 > 0.0) ? 1.0 / (Qg_min * 0.01) : 1.0e300;   // threshold 0 -> plain step
-        c.beta = beta; c.fA = f_A; c.fS = f_S;
-        c.omb = 1.0 - beta;
-        c.cQ = a_Q * (8.64 * 10000) / ((1 - b_Q) * L_reach);
-        c.bQ = b_Q; c.kM = k_M;
-        c.tg = MPv(SIMPLYP_PM_TDPG) * A_catch;                                                    // :163
-        c.invKv = 1.0 / Kv;
-        c.wA0 = -fc * c.invTsA; c.wS0 = -fc * c.invTsS; c.s0 = -fc * c.inv_d;
-        c.invKvc = c.invKv / c.cQ;
-        c.dgate = 0.01 * fc;
-        c.dgq = 0.01 * Qg_min;
+        dayconst_reach(c, mu, fc, T_s_A, T_s_S, T_g, Qg_min, beta, f_A, f_S, a_Q, b_Q, k_M, L_reach, MPv(SIMPLYP_PM_TDPG), A_catch, Kv);
 
         const double slopeA = RPv(SIMPLYP_PR_S_AR, s), slopeIG = RPv(SIMPLYP_PR_S_IG, s), slopeS = RPv(SIMPLYP_PR_S_SN, s);
         const double ES = MPv(SIMPLYP_PM_E_M) * RPv(SIMPLYP_PR_S_REACH, s);
@@ -1633,25 +1676,8 @@ __device__ __forceinline__ void run_slot(const KernelArgs& a, double* s_P, doubl
                 }
 
                 // ---- day constants of the right-hand side ----
-                c.c0 = P * (1 - f_quick);
-                c.aE = alpha * PET;
-                c.c0m = c.c0 - c.aE;
-                c.qin = Qq + QrUS;
-                c.Esum = f_Ar * Esus_A + f_IG * Esus_IG + f_S * Esus_S;
-                c.MsusUS = MsusUS;
-                {
-                    const double tNC = c.omb * wNC * conc_NC;             // soil-water TDP via QsNC (:156-157)
-                    c.tA = c.omb * wA * conc_A + (nc_type == 1 ? tNC : 0.0);
-                    c.tS = (nc_type == 1 ? 0.0 : tNC);
-                    c.tconst = Qq * (wA * conc_A + wNC * conc_NC) + TDPeff + TDPrUS;      // :159-165
-                }
-                {
-                    const double pA = (Plab_A + P_inactive) * invMsoil, pN = (Plab_NC + P_inactive) * invMsoil;
-                    c.cPP = E_PP * (f_Ar * Esus_A * ((1 - f_NC_Ar) * pA + f_NC_Ar * pN)
-                                    + f_IG * Esus_IG * ((1 - f_NC_IG) * pA + f_NC_IG * pN)
-                                    + f_S * Esus_S * ((1 - f_NC_S) * p0 + f_NC_S * pN));           // :171-176
-                }
-                c.PPrUS = PPrUS;
+                dayconst_day(c, P, f_quick, alpha, PET, Qq, QrUS, f_Ar, f_IG, f_S, Esus_A, Esus_IG, Esus_S, MsusUS, wA, wNC, conc_A, conc_NC,
+                             nc_type, TDPeff, TDPrUS, Plab_A, Plab_NC, P_inactive, invMsoil, p0, E_PP, f_NC_Ar, f_NC_IG, f_NC_S, PPrUS);
 
                 // ---- integrate the day (replaces odeint, model.py:640) ----
                 double yq[4] = {0.0, 0.0, 0.0, 0.0};                                              // :618
@@ -2093,6 +2119,141 @@ __global__ void eval_units_kernel(int which, int n, const double* __restrict__ i
         soil_p_update(aP, KfMsoil, a[4], a[7], r, emb, TDPs, Plab, conc);
         out[3 * i] = TDPs; out[3 * i + 1] = Plab; out[3 * i + 2] = conc;
     }
+}
+
+// simplyp_eval_units, which = 6: the four statements of the right-hand side -- rhs (the literal form), SysAug::f, quad_rhs,
+// SysAugF::f -- at caller-given states, on a DayConst assembled by dayconst_reach / dayconst_day as run_slot assembles it.
+// Four lanes per row (quad_rhs needs its quad); a row past the end is shadowed by the last row and stores nothing.
+//   in  [n][51] = VsA VsS Vg Vr Qr Msus TDPr PPr, then the 43 parameters of the reference's ode_f in the order of
+//                 tests/golden/unit_vectors.npz 'ode_p_names' (NC_type as 0 / 1 / 2)
+//   out [n][77] =  0 rhs: dy[8], q[4]
+//                 12 SysAug::f: dz[11], q[4], then the auxiliary states it was given (exp(-mu VsA), exp(-mu VsS), cQ Qr**b_Q,
+//                    Qr**k_M, formed as run_slot forms them before a day: sp_log, sp_expn<4>, cQ folded in)
+//                 31 quad_rhs: lane j's d[3], qv at 31 + 4 j (its carried function formed as run_slot's TEAM == 4 branch does)
+//                 47 SysAug::f on the auxiliary states the quad's lanes formed: dz[11], q[4]
+//                 62 SysAugF::f on DayConstF(c) and the states rounded to float: dz[11], q[4], widened
+constexpr int UNIT_RHS_IN = 51, UNIT_RHS_OUT = 77;
+__global__ __launch_bounds__(WAVE) void eval_rhs_kernel(int n, const double* __restrict__ in, double* __restrict__ out)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int row_raw = t >> 2, j = t & 3;
+    const bool live = row_raw < n;
+    const int row = live ? row_raw : n - 1;
+    const double* a = in + (size_t)UNIT_RHS_IN * row;
+    double y[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) y[i] = a[i];
+    const double* p = a + 8;
+    const double P = p[0], PET = p[1], mu = p[2], Qq = p[3], QrUS = p[4], Esus_A = p[5], Esus_S = p[6], Esus_IG = p[7];
+    const double MsusUS = p[8], TDPrUS = p[9], PPrUS = p[10], f_A = p[11], f_Ar = p[12], f_IG = p[13], f_S = p[14], f_NC_A = p[15];
+    const double f_NC_Ar = p[16], f_NC_IG = p[17], f_NC_S = p[18];
+    const int nc_type = (int)p[19];
+    const double f_quick = p[20], alpha = p[21], beta = p[22], T_s_A = p[23], T_s_S = p[24], T_g = p[25], fc = p[26];
+    const double L_reach = p[27], A_catch = p[28], a_Q = p[29], b_Q = p[30], k_M = p[32], conc_A = p[33], conc_NC = p[34];
+    const double Plab_A = p[35], Plab_NC = p[36], Msoil = p[37], TDPeff = p[38], TDPg = p[39], E_PP = p[40], P_inactive = p[41];
+    const double Qg_min = p[42];
+
+    // run_slot's per-reach scalars around the two assemblies
+    const double Kv = L_reach / (a_Q * 8.64 * 10000);
+    const double wA = f_A * (1 - f_NC_A);
+    const double wNC = f_A * f_NC_A + f_S * f_NC_S;
+    const double invMsoil = 1.0 / Msoil;
+    const double p0 = P_inactive * invMsoil;
+    DayConst c;
+    dayconst_reach(c, mu, fc, T_s_A, T_s_S, T_g, Qg_min, beta, f_A, f_S, a_Q, b_Q, k_M, L_reach, TDPg, A_catch, Kv);
+    dayconst_day(c, P, f_quick, alpha, PET, Qq, QrUS, f_Ar, f_IG, f_S, Esus_A, Esus_IG, Esus_S, MsusUS, wA, wNC, conc_A, conc_NC,
+                 nc_type, TDPeff, TDPrUS, Plab_A, Plab_NC, P_inactive, invMsoil, p0, E_PP, f_NC_Ar, f_NC_IG, f_NC_S, PPrUS);
+
+    double* o = out + (size_t)UNIT_RHS_OUT * row;
+    const bool w0 = live && j == 0;
+    {
+        double dy[8], q[4];
+        rhs(y, c, dy, q);
+        if (w0) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) o[i] = dy[i];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[8 + i] = q[i];
+        }
+    }
+    // the auxiliary states of a day's start (run_slot: HAS_AUX)
+    const double lq = sp_log(y[4]);
+    const double xs[4] = {-mu * y[0], -mu * y[1], b_Q * lq, k_M * lq};
+    double rs[4];
+    sp_expn<4>(xs, rs);
+    double z[11], dz[11], q[4];
+    z[0] = y[0]; z[1] = y[1]; z[2] = y[2]; z[3] = y[4]; z[4] = y[5]; z[5] = y[6]; z[6] = y[7];
+    z[7] = rs[0]; z[8] = rs[1]; z[9] = rs[2] * c.cQ; z[10] = rs[3];
+    SysAug::f(z, c, dz, q);
+    if (w0) {
+#pragma unroll
+        for (int i = 0; i < 11; ++i) o[12 + i] = dz[i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { o[23 + i] = q[i]; o[27 + i] = z[7 + i]; }
+    }
+    // one sub-system per lane, this lane's carried function as run_slot's TEAM == 4 branch forms it
+    const double aux1 = sp_exp(sel4(j, -mu * y[0], -mu * y[1], k_M * lq, b_Q * lq)) * (j == 3 ? c.cQ : 1.0);
+    {
+        const QuadConst qc = quad_const(c, j);
+        double x[3], d[3], qv;
+        x[0] = sel4(j, z[0], z[1], z[2], z[3]);
+        x[1] = aux1;
+        x[2] = sel4(j, z[4], z[5], z[6], 0.0);
+        quad_rhs(x, qc, j < 2, j == 2, d, qv);
+        if (live) { o[31 + 4 * j] = d[0]; o[32 + 4 * j] = d[1]; o[33 + 4 * j] = d[2]; o[34 + 4 * j] = qv; }
+    }
+    z[7] = quad_bcast<0>(aux1); z[8] = quad_bcast<1>(aux1); z[10] = quad_bcast<2>(aux1); z[9] = quad_bcast<3>(aux1);
+    SysAug::f(z, c, dz, q);
+    if (w0) {
+#pragma unroll
+        for (int i = 0; i < 11; ++i) o[47 + i] = dz[i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[58 + i] = q[i];
+    }
+    {
+        // run_slot, SIMPLYP_INTEG_CASHKARP_AUG_F32: carried state, auxiliary states (cQ not folded in) and day constants rounded to float
+        float zf[11], dzf[11], qf[4];
+#pragma unroll
+        for (int i = 0; i < 7; ++i) zf[i] = (float)z[i];
+        zf[7] = (float)rs[0]; zf[8] = (float)rs[1]; zf[9] = (float)rs[2]; zf[10] = (float)rs[3];
+        const DayConstF cf(c);
+        SysAugF::f(zf, cf, dzf, qf);
+        if (w0) {
+#pragma unroll
+            for (int i = 0; i < 11; ++i) o[62 + i] = (double)dzf[i];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o[73 + i] = (double)qf[i];
+        }
+    }
+}
+
+// simplyp_eval_units, which = 7: the pieces of an adaptive attempt that ck_day and ck_day_quad share, on caller-given arguments;
+// one thread per row, flags as 0 / 1.
+//   in  [n][19] = ck_open_step: h_carry, T, rate | ck_propose: h, rem, c11 | ck_choose_pair: hh, rate, kneeish, last_chance, alive
+//                 | ck_damping: bQ, Qr, dQr, rate, T, left | ck_step_factor: err, stiff
+//   out [n][11] = ck_open_step<SysAug, false>, <SysAug, true>, <SysLiteral, false>, <SysAugF, false> | ck_propose
+//                 | ck_choose_pair: hh after, toff, the returned flag | ck_damping | ck_step_factor<false>, <true>
+constexpr int UNIT_STEP_IN = 19, UNIT_STEP_OUT = 11;
+__global__ void eval_step_kernel(int n, const double* __restrict__ in, double* __restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* a = in + (size_t)UNIT_STEP_IN * i;
+    double* o = out + (size_t)UNIT_STEP_OUT * i;
+    o[0] = ck_open_step<SysAug, false>(a[0], a[1], a[2]);
+    o[1] = ck_open_step<SysAug, true>(a[0], a[1], a[2]);
+    o[2] = ck_open_step<SysLiteral, false>(a[0], a[1], a[2]);
+    o[3] = (double)ck_open_step<SysAugF, false>(a[0], (float)a[1], (float)a[2]);
+    o[4] = ck_propose(a[3], a[4], a[5]);
+    double hh = a[6];
+    int toff = -1;
+    const bool second = ck_choose_pair(hh, toff, a[7], a[8] != 0.0, a[9] != 0.0, a[10] != 0.0);
+    o[5] = hh; o[6] = (double)toff; o[7] = second ? 1.0 : 0.0;
+    o[8] = ck_damping(a[11], a[12], a[13], a[14], a[15], a[16]);
+    const float err = (float)a[17];
+    const bool stiff = a[18] != 0.0;
+    o[9] = (double)ck_step_factor<false>(err, stiff);
+    o[10] = (double)ck_step_factor<true>(err, stiff);
 }
 
 }  // namespace simplyp

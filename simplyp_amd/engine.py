@@ -555,10 +555,13 @@ class Engine(object):
         [n, 10] = the arguments of the reference's discretized_soilP -> [n, 3] = TDPs, Plab, conc_TDPs); and the fp64
         elementary functions every kernel calls: 'exp' (rows [n, 1] = x -> [n, 4]: exp(x) evaluated alone, in slot 1 of a group
         of two, in slots 0 and 6 of a group of seven), 'log' (rows [n, 1] -> [n, 1]), 'rcp' (rows [n, 1] -> [n, 3]: the raw
-        hardware reciprocal, one Newton step, two Newton steps) and 'pow' (rows [n, 2] = q, b -> [n, 1] = exp(b log(q)))."""
+        hardware reciprocal, one Newton step, two Newton steps) and 'pow' (rows [n, 2] = q, b -> [n, 1] = exp(b log(q))); and
+        'rhs' (rows [n, 51] = the 8 carried states and the 43 parameters of ode_f -> [n, 77]: the literal, the augmented, the
+        four-lane and the fp32 statement of the right-hand side) and 'step' (rows [n, 19] = the arguments of the five pieces of
+        the step rule -> [n, 11]); the columns are listed at ``simplyp_eval_units`` in include/simplyp.h."""
         torch = self.torch
         w, k_in, k_out = {'f_x': (0, 2, 2), 'soilp': (1, 10, 3), 'exp': (2, 1, 4), 'log': (3, 1, 1), 'rcp': (4, 1, 3),
-                           'pow': (5, 2, 1)}[which]
+                           'pow': (5, 2, 1), 'rhs': (6, 51, 77), 'step': (7, 19, 11)}[which]
         a = self.to_device(np.ascontiguousarray(rows, dtype=np.float64), torch.float64)
         if a.dim() != 2 or a.shape[1] != k_in:
             raise ValueError("%s takes rows of %d values" % (which, k_in))

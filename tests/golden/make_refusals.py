@@ -185,7 +185,7 @@ def cases(h, dev):
     for n_dim in (0, 17):
         add('simplyp_pf_jitter', 'n_dim = %d' % n_dim, (h, 4, n_dim, seed, C.c_uint32(1), 0.5, hd(0.5), hd(0.1), lo, up, tg, dev, None, None), abi.PfInfo)
     add('simplyp_pf_jitter', 'a = inf', (h, 4, 1, seed, C.c_uint32(1), float('inf'), hd(0.5), hd(0.1), lo, up, tg, dev, None, None), abi.PfInfo)
-    add('simplyp_eval_units', 'which = 6', (h, 6, 1, dev, dev), None)
+    add('simplyp_eval_units', 'which = 8', (h, 8, 1, dev, dev), None)
     add('simplyp_eval_units', 'n = -1', (h, 0, -1, dev, dev), None)
 
     def order(label, E=4, cost=dev, where=0, perm=dev, keys=None):

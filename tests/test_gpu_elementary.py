@@ -88,5 +88,5 @@ def test_unknown_function_is_an_argument_error(engine0):
     from simplyp_amd import engine
     L = engine.lib()
     t = torch.ones(4, dtype=torch.float64, device=engine0.tdev)
-    for which in (-1, 6):
+    for which in (-1, 8):
         assert L.simplyp_eval_units(engine0._h, which, 1, t.data_ptr(), t.data_ptr()) == -1
