@@ -27,11 +27,27 @@ STATUS_NONFINITE = 1
 STATUS_STEPCAP = 2
 
 
+# The C types of the header's prototypes as ctypes (engine.prototypes reads the header with them).  A pointer to one of the structs
+# below is POINTER(its class) -- each class names its struct in ``c_name``, the one place the pairing is written -- and every other
+# pointer (data, simplyp_ctx*, simplyp_ctx**, void*) is a c_void_p.
+C_SCALARS = {'int': C.c_int, 'int32_t': C.c_int32, 'uint32_t': C.c_uint32, 'int64_t': C.c_int64, 'uint64_t': C.c_uint64,
+             'double': C.c_double}
+C_RETURNS = dict(C_SCALARS, **{'const char*': C.c_char_p, 'void*': C.c_void_p, 'void': None})
+
+
+def structs():
+    """{C name: class} of the mirrors in this module."""
+    return {cls.c_name: cls for cls in globals().values()
+            if isinstance(cls, type) and issubclass(cls, C.Structure) and 'c_name' in vars(cls)}
+
+
 class Dims(C.Structure):
+    c_name = 'simplyp_dims'
     _fields_ = [('E', C.c_int32), ('S', C.c_int32), ('D', C.c_int32), ('n_forcing_sets', C.c_int32)]
 
 
 class Opts(C.Structure):
+    c_name = 'simplyp_opts'
     _fields_ = [('integrator', C.c_int32), ('substeps', C.c_int32),
                 ('rtol', C.c_double), ('atol', C.c_double),
                 ('max_steps', C.c_int32), ('dynamic_epc0', C.c_int32), ('dynamic_erod', C.c_int32),
@@ -62,6 +78,7 @@ class _Info(C.Structure):
 
 
 class Stats(_Info):
+    c_name = 'simplyp_stats'
     _fields_ = [('rhs_evals', C.c_uint64), ('steps', C.c_uint64), ('rejected', C.c_uint64),
                 ('kernel_ms', C.c_double), ('pilot_ms', C.c_double), ('simt_efficiency', C.c_double), ('n_launches', C.c_int32), ('balanced', C.c_int32),
                 ('queued', C.c_int32), ('lanes_per_wave', C.c_int32), ('lanes_per_member', C.c_int32), ('streamed_chunks', C.c_int32),
@@ -71,28 +88,28 @@ class Stats(_Info):
 
 
 class GofInfo(_Info):
-    """simplyp_gof_info of include/simplyp.h."""
+    c_name = 'simplyp_gof_info'
     _fields_ = [('kernel_ms', C.c_double), ('bytes_read', C.c_int64), ('n_q_days', C.c_int32), ('n_chem_days', C.c_int32),
                 ('n_chunks_q', C.c_int32), ('n_chunks_chem', C.c_int32)]
 
 
 class WbInfo(_Info):
-    """simplyp_wb_info of include/simplyp.h."""
+    c_name = 'simplyp_wb_info'
     _fields_ = [('kernel_ms', C.c_double), ('bytes_moved', C.c_int64)]
 
 
 class QuantileInfo(_Info):
-    """simplyp_quantile_info of include/simplyp.h."""
+    c_name = 'simplyp_quantile_info'
     _fields_ = [('kernel_ms', C.c_double), ('bytes_table', C.c_int64), ('n_used', C.c_int32), ('n_passes', C.c_int32)]
 
 
 class WqInfo(_Info):
-    """simplyp_wq_info of include/simplyp.h."""
+    c_name = 'simplyp_wq_info'
     _fields_ = [('kernel_ms', C.c_double), ('bytes_table', C.c_int64), ('T', C.c_uint64), ('n_used', C.c_int32), ('n_passes', C.c_int32)]
 
 
 class ScoreInfo(_Info):
-    """simplyp_score_info of include/simplyp.h."""
+    c_name = 'simplyp_score_info'
     _fields_ = [('kernel_ms', C.c_double), ('gen_ms', C.c_double), ('sort_ms', C.c_double), ('bytes_read', C.c_int64),
                 ('bytes_workspace', C.c_int64), ('T', C.c_uint64), ('n_used', C.c_int32), ('n_rows_scored', C.c_int32),
                 ('n_chunks', C.c_int32), ('reserved', C.c_int32)]
@@ -102,7 +119,7 @@ SCORE_TILE = 4096               # (key, weight) pairs the scores' LDS sort takes
 
 
 class ParetoInfo(_Info):
-    """simplyp_pareto_info of include/simplyp.h."""
+    c_name = 'simplyp_pareto_info'
     _fields_ = [('kernel_ms', C.c_double), ('pair_tests', C.c_int64), ('n_used', C.c_int32), ('n_fronts', C.c_int32),
                 ('n_front0', C.c_int32), ('n_unranked', C.c_int32)]
 
@@ -116,18 +133,18 @@ PARETO_JSPLIT = 2048            # and the stretch of them one workgroup takes; t
 
 
 class TqInfo(_Info):
-    """simplyp_tq_info of include/simplyp.h."""
+    c_name = 'simplyp_tq_info'
     _fields_ = [('kernel_ms', C.c_double), ('bytes_read', C.c_int64), ('n_sweeps', C.c_int32), ('n_periods', C.c_int32)]
 
 
 class PredInfo(_Info):
-    """simplyp_pred_info of include/simplyp.h."""
+    c_name = 'simplyp_pred_info'
     _fields_ = [('kernel_ms', C.c_double), ('gen_ms', C.c_double), ('bytes_read', C.c_int64), ('bytes_workspace', C.c_int64),
                 ('n_used', C.c_int32), ('n_passes', C.c_int32), ('n_chunks', C.c_int32), ('reserved', C.c_int32)]
 
 
 class McmcInfo(_Info):
-    """simplyp_mcmc_info of include/simplyp.h."""
+    c_name = 'simplyp_mcmc_info'
     _fields_ = [('kernel_ms', C.c_double), ('n_inside', C.c_int32), ('n_accepted', C.c_int32), ('n_nan', C.c_int32),
                 ('reserved', C.c_int32)]
 
@@ -137,19 +154,19 @@ MCMC_TARGET_NONE = -2           # ... nowhere: an error-model m
 
 
 class NmInfo(_Info):
-    """simplyp_nm_info of include/simplyp.h."""
+    c_name = 'simplyp_nm_info'
     _fields_ = [('kernel_ms', C.c_double), ('n_active', C.c_int32), ('n_converged', C.c_int32), ('n_shrinking', C.c_int32),
                 ('n_nonfinite_start', C.c_int32), ('n_inside', C.c_int32), ('reserved', C.c_int32)]
 
 
 class SobolInfo(_Info):
-    """simplyp_sobol_info of include/simplyp.h."""
+    c_name = 'simplyp_sobol_info'
     _fields_ = [('kernel_ms', C.c_double), ('counts_ms', C.c_double), ('contract_ms', C.c_double), ('flops', C.c_int64),
                 ('bytes_workspace', C.c_int64), ('n_valid', C.c_int32), ('n_resamples', C.c_int32)]
 
 
 class PfInfo(_Info):
-    """simplyp_pf_info of include/simplyp.h."""
+    c_name = 'simplyp_pf_info'
     _fields_ = [('kernel_ms', C.c_double), ('lw_max', C.c_double), ('sum_w', C.c_double), ('sum_w2', C.c_double),
                 ('T', C.c_uint64), ('n_alive', C.c_int32), ('n_nan', C.c_int32), ('n_unique', C.c_int32), ('n_bad', C.c_int32),
                 ('n_outside', C.c_int32), ('reserved', C.c_int32)]

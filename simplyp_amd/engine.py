@@ -11,6 +11,7 @@ torch is used for plumbing only: device buffers, the current HIP stream and
 import ctypes as C
 import glob
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -22,26 +23,45 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB_PATH = os.environ.get('SIMPLYP_HIP_LIB') or os.path.join(CSRC, 'libsimplyp_hip.so')   # env: experiments only
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 
-# every symbol include/simplyp.h declares
-ABI_SYMBOLS = ['simplyp_abi_version', 'simplyp_device_count', 'simplyp_ctx_create', 'simplyp_ctx_destroy',
-               'simplyp_last_error', 'simplyp_ctx_set_stream', 'simplyp_out_bytes', 'simplyp_run',
-               'simplyp_run_async', 'simplyp_sync', 'simplyp_plan', 'simplyp_host_alloc', 'simplyp_host_free',
-               'simplyp_device_alloc', 'simplyp_device_free', 'simplyp_memcpy_h2d', 'simplyp_memcpy_d2h', 'simplyp_gof',
-               'simplyp_stream_out', 'simplyp_waterbody', 'simplyp_gof_waterbody', 'simplyp_gof_spearman', 'simplyp_eval_units',
-               'simplyp_quantiles', 'simplyp_state_bytes', 'simplyp_set_state', 'simplyp_fetch_packed',
-               'simplyp_pack_roundtrip_host', 'simplyp_fetch_packed_pred', 'simplyp_pack_roundtrip_host_pred',
-               'simplyp_time_quantiles', 'simplyp_predictive_series', 'simplyp_predictive_bands',
-               'simplyp_mcmc_propose', 'simplyp_mcmc_log_prob', 'simplyp_mcmc_accept', 'simplyp_nm_propose', 'simplyp_nm_update',
-               'simplyp_sobol_design', 'simplyp_sobol_indices',
-               'simplyp_pf_loglik', 'simplyp_pf_weights', 'simplyp_pf_resample', 'simplyp_gather_members', 'simplyp_pf_jitter',
-               'simplyp_weighted_quantiles', 'simplyp_predictive_bands_weighted', 'simplyp_scores', 'simplyp_predictive_scores',
-               'simplyp_pareto', 'simplyp_order_members']
-
 _lib = None
 
 
 class EngineError(RuntimeError):
     pass
+
+
+def prototypes(text):
+    """[(name, restype, argtypes)] of every ``ret simplyp_name(params);`` that header text declares, in its order, with the types
+    of abi.C_SCALARS / abi.C_RETURNS.  Whatever else follows a ``simplyp_name(`` raises: nothing is skipped."""
+    text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)                        # comments
+    text = re.sub(r'^[ \t]*#(?:[^\n]*\\\n)*[^\n]*', ' ', text, flags=re.M)            # preprocessor lines and their continuations
+    structs = abi.structs()
+    squeeze = lambda t: re.sub(r'\s*\*', '*', ' '.join(t.split()))                    # 'const  char *' -> 'const char*'
+    out = []
+    for m in re.finditer(r'\b(simplyp_\w+)\s*\(', text):
+        name = m.group(1)
+        start = max(text.rfind(c, 0, m.start()) for c in ';{}') + 1
+        ret = squeeze(text[start:m.start()])
+        params = re.match(r'([^()]*)\)\s*;', text[m.end():])
+        if ret not in abi.C_RETURNS or params is None:
+            raise EngineError("include/simplyp.h: cannot read the declaration of %s" % name)
+        argtypes = []
+        for param in [squeeze(x) for x in params.group(1).split(',')] if squeeze(params.group(1)) != 'void' else []:
+            pm = re.fullmatch(r'(?:const )?(\w+)(?:(\*+) ?| )\w+', param)
+            base, stars = pm.groups() if pm else (None, None)
+            if stars:
+                argtypes.append(C.POINTER(structs[base]) if stars == '*' and base in structs else C.c_void_p)
+            elif base in abi.C_SCALARS:
+                argtypes.append(abi.C_SCALARS[base])
+            else:
+                raise EngineError("include/simplyp.h: %s: no ctypes type for the parameter '%s'" % (name, param))
+        out.append((name, abi.C_RETURNS[ret], argtypes))
+    return out
+
+
+with open(os.path.join(INCLUDE, 'simplyp.h')) as _fh:
+    PROTOTYPES = prototypes(_fh.read())
+ABI_SYMBOLS = [_name for _name, _, _ in PROTOTYPES]         # every symbol include/simplyp.h declares
 
 
 def build(force=False, verbose=False):
@@ -75,133 +95,9 @@ def lib():
     # library binds to the runtime that owns the process' device tensors and streams.
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
-    vp, i32p, dp = C.c_void_p, C.c_void_p, C.c_void_p
-    L.simplyp_abi_version.restype = C.c_int
-    L.simplyp_device_count.restype = C.c_int
-    L.simplyp_ctx_create.restype = C.c_int
-    L.simplyp_ctx_create.argtypes = [C.c_int, C.POINTER(vp)]
-    L.simplyp_ctx_destroy.restype = None
-    L.simplyp_ctx_destroy.argtypes = [vp]
-    L.simplyp_last_error.restype = C.c_char_p
-    L.simplyp_last_error.argtypes = [vp]
-    L.simplyp_ctx_set_stream.restype = C.c_int
-    L.simplyp_ctx_set_stream.argtypes = [vp, vp]
-    L.simplyp_out_bytes.restype = C.c_int64
-    L.simplyp_out_bytes.argtypes = [C.POINTER(abi.Dims), C.POINTER(abi.Opts), C.c_int32]
-    run_args = [vp, C.POINTER(abi.Dims), C.POINTER(abi.Opts), dp, i32p, i32p, i32p, dp, dp,
-                C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, dp, i32p]
-    L.simplyp_run.restype = C.c_int
-    L.simplyp_run.argtypes = run_args + [vp, vp, C.POINTER(abi.Stats)]
-    L.simplyp_run_async.restype = C.c_int
-    L.simplyp_run_async.argtypes = run_args + [vp, vp]
-    L.simplyp_sync.restype = C.c_int
-    L.simplyp_sync.argtypes = [vp, C.POINTER(abi.Stats)]
-    L.simplyp_gof.restype = C.c_int
-    L.simplyp_gof.argtypes = [vp, C.POINTER(abi.Dims), C.c_uint32, C.POINTER(C.c_int32), C.c_int32, dp, i32p, dp, dp,
-                              C.POINTER(C.c_double), dp, C.POINTER(abi.GofInfo)]
-    L.simplyp_gof_spearman.restype = C.c_int
-    L.simplyp_gof_spearman.argtypes = L.simplyp_gof.argtypes
-    L.simplyp_waterbody.restype = C.c_int
-    L.simplyp_waterbody.argtypes = [vp, C.POINTER(abi.Dims), C.c_uint32, C.POINTER(C.c_int32), C.c_int32, dp, i32p, dp, dp,
-                                    C.POINTER(C.c_int32), C.c_int32, C.c_uint32, dp, C.POINTER(abi.WbInfo)]
-    L.simplyp_gof_waterbody.restype = C.c_int
-    L.simplyp_gof_waterbody.argtypes = [vp, C.POINTER(abi.Dims), C.c_uint32, dp, i32p, dp, C.POINTER(C.c_double), dp,
-                                        C.POINTER(abi.GofInfo)]
-    L.simplyp_quantiles.restype = C.c_int
-    L.simplyp_quantiles.argtypes = [vp, C.c_int32, C.c_int64, dp, i32p, vp, C.POINTER(C.c_double), C.c_int32, dp,
-                                    C.POINTER(abi.QuantileInfo)]
-    L.simplyp_time_quantiles.restype = C.c_int
-    L.simplyp_time_quantiles.argtypes = [vp, C.POINTER(abi.Dims), C.c_uint32, C.POINTER(C.c_int32), C.c_int32, dp, i32p, dp, dp,
-                                         C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
-                                         C.POINTER(C.c_double), C.c_int32, dp, C.POINTER(C.c_int32), C.POINTER(abi.TqInfo)]
-    pred_args = [vp, C.POINTER(abi.Dims), C.c_uint32, C.POINTER(C.c_int32), C.c_int32, dp, i32p]
-    L.simplyp_predictive_series.restype = C.c_int
-    L.simplyp_predictive_series.argtypes = pred_args + [dp, dp, C.POINTER(C.c_int32), C.c_int32, dp, C.c_uint64, C.c_int32,
-                                                        C.c_int32, dp]
-    L.simplyp_predictive_bands.restype = C.c_int
-    L.simplyp_predictive_bands.argtypes = pred_args + [vp, dp, dp, C.POINTER(C.c_int32), C.c_int32, dp, C.c_uint64, C.c_int32,
-                                                       C.POINTER(C.c_double), C.c_int32, dp, C.POINTER(abi.PredInfo)]
-    L.simplyp_weighted_quantiles.restype = C.c_int
-    L.simplyp_weighted_quantiles.argtypes = [vp, C.c_int32, C.c_int64, dp, i32p, vp, vp, C.POINTER(C.c_double), C.c_int32, dp,
-                                             C.POINTER(abi.WqInfo)]
-    L.simplyp_predictive_bands_weighted.restype = C.c_int
-    L.simplyp_predictive_bands_weighted.argtypes = pred_args + [vp, dp, dp, C.POINTER(C.c_int32), C.c_int32, dp, C.c_uint64, C.c_int32,
-                                                                C.POINTER(C.c_double), C.c_int32, vp, dp, C.POINTER(abi.WqInfo)]
-    L.simplyp_scores.restype = C.c_int
-    L.simplyp_scores.argtypes = [vp, C.c_int32, C.c_int64, dp, i32p, vp, vp, C.POINTER(C.c_double), dp, vp, C.POINTER(abi.ScoreInfo)]
-    L.simplyp_predictive_scores.restype = C.c_int
-    L.simplyp_predictive_scores.argtypes = pred_args + [vp, dp, dp, C.POINTER(C.c_int32), C.c_int32, dp, C.c_uint64, C.c_int32,
-                                                        vp, C.POINTER(C.c_double), dp, vp, C.POINTER(abi.ScoreInfo)]
-    L.simplyp_pareto.restype = C.c_int
-    L.simplyp_pareto.argtypes = [vp, C.c_int32, C.c_int32, dp, C.POINTER(C.c_int32), i32p, vp, C.c_int32, i32p, i32p, i32p,
-                                 C.POINTER(abi.ParetoInfo)]
-    move = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_uint32]
-    L.simplyp_mcmc_propose.restype = C.c_int
-    L.simplyp_mcmc_propose.argtypes = move + [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), dp, dp, i32p, dp, dp,
-                                              C.POINTER(abi.McmcInfo)]
-    L.simplyp_mcmc_log_prob.restype = C.c_int
-    L.simplyp_mcmc_log_prob.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, i32p, i32p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                        C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), dp, dp, C.POINTER(abi.McmcInfo)]
-    L.simplyp_mcmc_accept.restype = C.c_int
-    L.simplyp_mcmc_accept.argtypes = move + [dp, i32p, dp, dp, dp, i32p, dp, C.POINTER(abi.McmcInfo)]
-    L.simplyp_nm_propose.restype = C.c_int
-    L.simplyp_nm_propose.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
-                                     dp, i32p, dp, i32p, dp, dp, C.POINTER(abi.NmInfo)]
-    L.simplyp_nm_update.restype = C.c_int
-    L.simplyp_nm_update.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, dp, i32p, dp, dp, dp, i32p, dp,
-                                    C.c_int32, C.POINTER(abi.NmInfo)]
-    L.simplyp_sobol_design.restype = C.c_int
-    L.simplyp_sobol_design.argtypes = [vp, C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                       C.POINTER(C.c_int32), dp, dp, dp, dp, C.POINTER(abi.SobolInfo)]
-    L.simplyp_sobol_indices.restype = C.c_int
-    L.simplyp_sobol_indices.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, i32p, C.c_int32, C.c_uint64, dp, i32p, dp,
-                                        C.POINTER(abi.SobolInfo)]
-    pf = C.POINTER(abi.PfInfo)
-    L.simplyp_pf_loglik.restype = C.c_int
-    L.simplyp_pf_loglik.argtypes = L.simplyp_gof.argtypes[:10] + [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, dp, i32p, dp, dp,
-                                                                C.c_int32, pf]
-    L.simplyp_pf_weights.restype = C.c_int
-    L.simplyp_pf_weights.argtypes = [vp, C.c_int32, dp, dp, vp, pf]
-    L.simplyp_pf_resample.restype = C.c_int
-    L.simplyp_pf_resample.argtypes = [vp, C.c_int32, vp, C.c_uint64, C.c_uint32, i32p, i32p, pf]
-    L.simplyp_gather_members.restype = C.c_int
-    L.simplyp_gather_members.argtypes = [vp, C.c_int32, C.c_int64, i32p, vp, vp, pf]
-    L.simplyp_pf_jitter.restype = C.c_int
-    L.simplyp_pf_jitter.argtypes = [vp, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_double] + [C.POINTER(C.c_double)] * 4 \
-        + [C.POINTER(C.c_int32), dp, dp, dp, pf]
-    L.simplyp_stream_out.restype = C.c_int
-    L.simplyp_stream_out.argtypes = [vp, vp, C.c_int64]
-    L.simplyp_fetch_packed.restype = C.c_int
-    L.simplyp_fetch_packed.argtypes = [vp, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int32)]
-    L.simplyp_pack_roundtrip_host.restype = C.c_int
-    L.simplyp_pack_roundtrip_host.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.POINTER(C.c_int32)]
-    L.simplyp_fetch_packed_pred.restype = C.c_int
-    L.simplyp_fetch_packed_pred.argtypes = [vp, dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), vp, C.c_int64,
-                                            C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
-    L.simplyp_pack_roundtrip_host_pred.restype = C.c_int
-    L.simplyp_pack_roundtrip_host_pred.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), vp,
-                                                   C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
-    L.simplyp_state_bytes.restype = C.c_int64
-    L.simplyp_state_bytes.argtypes = [C.POINTER(abi.Dims)]
-    L.simplyp_set_state.restype = C.c_int
-    L.simplyp_set_state.argtypes = [vp, vp, vp]
-    L.simplyp_plan.restype = C.c_int
-    L.simplyp_plan.argtypes = [C.c_int32] + [C.POINTER(C.c_int32)] * 8
-    L.simplyp_host_alloc.restype = vp
-    L.simplyp_host_alloc.argtypes = [C.c_int64]
-    L.simplyp_host_free.restype = None
-    L.simplyp_host_free.argtypes = [vp]
-    L.simplyp_device_alloc.restype = vp
-    L.simplyp_device_alloc.argtypes = [vp, C.c_int64]
-    L.simplyp_device_free.restype = None
-    L.simplyp_device_free.argtypes = [vp, vp]
-    L.simplyp_eval_units.restype = C.c_int
-    L.simplyp_eval_units.argtypes = [vp, C.c_int32, C.c_int32, dp, dp]
-    L.simplyp_order_members.restype = C.c_int
-    L.simplyp_order_members.argtypes = [vp, C.c_int32, vp, C.c_int32, i32p, dp, vp]
-    for name in ('simplyp_memcpy_h2d', 'simplyp_memcpy_d2h'):
-        getattr(L, name).restype = C.c_int
-        getattr(L, name).argtypes = [vp, vp, vp, C.c_int64]
+    for name, restype, argtypes in PROTOTYPES:
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.simplyp_abi_version() != abi.ABI_VERSION:
         raise EngineError("libsimplyp_hip.so has ABI %d, the Python host expects %d -- rebuild"
                           % (L.simplyp_abi_version(), abi.ABI_VERSION))

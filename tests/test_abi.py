@@ -2,17 +2,16 @@
 mirrors match the header's struct layout."""
 
 import ctypes as C
+import functools
+import inspect
 import os
 import re
 
+import pytest
+
 from simplyp_amd import abi, engine, marshal
 
-HEADER = os.path.join(os.path.dirname(engine.HERE), 'include', 'simplyp.h')
-
-
-def header_text():
-    with open(HEADER) as fh:
-        return fh.read()
+from c_header import c_values, header_text
 
 
 def test_library_exports_every_declared_symbol():
@@ -22,7 +21,8 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(engine.ABI_SYMBOLS), declared ^ set(engine.ABI_SYMBOLS)
     for name in declared:
         assert hasattr(L, name), name
-    assert L.simplyp_abi_version() == abi.ABI_VERSION == int(re.search(r'#define SIMPLYP_ABI_VERSION (\d+)', header_text()).group(1))
+    # the one place the number is written out: a bump is a deliberate edit here
+    assert L.simplyp_abi_version() == abi.ABI_VERSION == int(re.search(r'#define SIMPLYP_ABI_VERSION (\d+)', header_text()).group(1)) == 18
 
 
 def test_enums_match_python_tables():
@@ -46,26 +46,69 @@ def test_enums_match_python_tables():
     assert len(re.findall(r'SIMPLYP_GOFSTAT_[A-Z0-9_]+', gs)) == len(abi.GOF_STATS) == 8
 
 
-def test_struct_layouts(tmp_path):
-    """ctypes mirrors vs the C compiler's view of include/simplyp.h (sizeof / offsetof of every field)."""
-    import subprocess
-    structs = {'simplyp_dims': abi.Dims, 'simplyp_opts': abi.Opts, 'simplyp_stats': abi.Stats,
-               'simplyp_gof_info': abi.GofInfo, 'simplyp_wb_info': abi.WbInfo}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % HEADER, 'int main(void){']
-    for cname, cls in structs.items():
-        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
-        for f, _ in cls._fields_:
-            lines.append('printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (cname, f, cname, f))
-    lines += ['return 0;}']
-    src = tmp_path / 'layout.c'
-    src.write_text('\n'.join(lines))
-    exe = tmp_path / 'layout'
-    subprocess.check_call(['gcc', '-o', str(exe), str(src)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().splitlines())
-    for cname, cls in structs.items():
-        assert int(got[cname]) == C.sizeof(cls), cname
-        for f, _ in cls._fields_:
-            assert int(got['%s.%s' % (cname, f)]) == getattr(cls, f).offset, (cname, f)
+STRUCTS = [cls for _, cls in inspect.getmembers(abi, inspect.isclass) if issubclass(cls, C.Structure) and hasattr(cls, '_fields_')]
+
+
+@functools.lru_cache(maxsize=None)
+def layout_values():
+    """sizeof of every mirrored struct, offsetof and sizeof of every field: one run of the C compiler for all the cases."""
+    exprs = []
+    for cls in STRUCTS:
+        if 'c_name' in vars(cls):
+            exprs.append('sizeof(%s)' % cls.c_name)
+            for f, _ in cls._fields_:
+                exprs += ['offsetof(%s, %s)' % (cls.c_name, f), 'sizeof(((%s*)0)->%s)' % (cls.c_name, f)]
+    return c_values(exprs)
+
+
+@pytest.mark.parametrize('cls', STRUCTS, ids=lambda cls: cls.__name__)
+def test_struct_layouts(cls):
+    """A ctypes mirror vs its struct in include/simplyp.h: the header's field names, and the C compiler's offset and size of every
+    field and size of the struct."""
+    assert 'c_name' in vars(cls), 'abi.%s does not name its struct of the header' % cls.__name__
+    body = re.search(r'typedef struct \{([^{}]*)\}\s*%s\s*;' % cls.c_name, re.sub(r'/\*.*?\*/', ' ', header_text(), flags=re.S))
+    assert body, 'the header has no struct %s' % cls.c_name
+    assert abi.structs()[cls.c_name] is cls
+    # every field and no other: tail padding can keep the size of a struct that lost its last field
+    assert [f for f, _ in cls._fields_] == re.findall(r'(\w+)\s*(?:\[\w+\])?\s*[,;]', body.group(1)), cls.c_name
+    got = layout_values()
+    for f, _ in cls._fields_:
+        where = '%s.%s' % (cls.c_name, f)
+        assert got['offsetof(%s, %s)' % (cls.c_name, f)] == getattr(cls, f).offset, where
+        assert got['sizeof(((%s*)0)->%s)' % (cls.c_name, f)] == getattr(cls, f).size, where
+    assert got['sizeof(%s)' % cls.c_name] == C.sizeof(cls), cls.c_name
+
+
+def test_every_struct_of_a_prototype_has_a_mirror():
+    """A struct pointer without a class in abi.py would be bound as a plain c_void_p, unchecked."""
+    txt = re.sub(r'/\*.*?\*/', ' ', header_text(), flags=re.S)
+    declared = set(re.findall(r'\}\s*(simplyp_\w+)\s*;', re.sub(r'typedef enum \{.*?\}', '', txt, flags=re.S)))
+    named = set(re.findall(r'\b(simplyp_\w+)\s*\*', txt)) & declared
+    assert named and named <= set(abi.structs()), named - set(abi.structs())
+    assert len(STRUCTS) == len(abi.structs()) and set(abi.structs()) <= declared
+
+
+def test_prototypes_are_the_headers():
+    """The argtypes and restypes the binding derives from the header, pinned where the widths and kinds mix."""
+    vp, i32, info = C.c_void_p, C.c_int32, C.POINTER
+    proto = {name: (restype, argtypes) for name, restype, argtypes in engine.prototypes(header_text())}
+    assert list(proto) == engine.ABI_SYMBOLS and len(proto) == 51
+    assert set(proto) == set(re.findall(r'\b(simplyp_[a-z0-9_]+)\s*\(', header_text()))
+    assert proto['simplyp_quantiles'][1] == [vp, i32, C.c_int64, vp, vp, vp, vp, i32, vp, info(abi.QuantileInfo)]
+    assert proto['simplyp_pf_jitter'][1] == [vp, i32, i32, C.c_uint64, C.c_uint32, C.c_double] + [vp] * 8 + [info(abi.PfInfo)]
+    assert proto['simplyp_ctx_create'][1] == [C.c_int, vp]
+    assert proto['simplyp_last_error'][0] is C.c_char_p and proto['simplyp_host_alloc'][0] is vp
+    assert proto['simplyp_out_bytes'][0] is C.c_int64 and proto['simplyp_ctx_destroy'][0] is None
+    engine.build()
+    L = engine.lib()                                               # ... and they are what the loaded library carries
+    for name, (restype, argtypes) in proto.items():
+        assert getattr(L, name).restype is restype and list(getattr(L, name).argtypes) == argtypes, name
+
+
+@pytest.mark.parametrize('name,decl', [('simplyp_x', 'int simplyp_x(float v);'), ('simplyp_y', 'int simplyp_y(int (*cb)(int));')])
+def test_parser_refuses_what_it_cannot_type(name, decl):
+    with pytest.raises(engine.EngineError, match=name):
+        engine.prototypes('int simplyp_ok(int32_t a);\n' + decl)
 
 
 def test_out_bytes_and_host_argument_errors():

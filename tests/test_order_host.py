@@ -5,16 +5,14 @@ tests/test_gpu_order_direct.py puts to the device's kernels goes through the sam
 that the checker's derived bounds hold for a rule that is known to be right -- and, with three wrong orders made from a right one,
 that it does not pass by looseness."""
 
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_program
 import order_model as om
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, 'order_host_main.cpp')
 MAX_UNCONSTRAINED = 0.01                # of the adjacent pairs of a pilot-like table: a condition on the INPUTS (change them, not this)
 _done = {}
 
@@ -23,9 +21,7 @@ _done = {}
 def host_order(tmp_path_factory):
     """run(cost) -> (perm, diag) of the stand-alone host program; the sanitizers abort the child on any finding."""
     work = tmp_path_factory.mktemp('order_host')
-    exe = str(work / 'order_host_main')
-    subprocess.check_call(['g++', '-std=c++17', '-O1', '-g', '-Wall', '-Wextra', '-Werror', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=all', '-pthread', '-o', exe, SRC])
+    exe = host_program.build('order_host_main.cpp', '-pthread')
 
     def run(cost):
         E = cost.shape[1]

@@ -1,36 +1,24 @@
 """Pareto dominance on the CPU: the plain C++ rules of simplyp_amd/csrc/simplyp_pareto.h (tests/pareto_host_main.cpp includes the
 header, is built once per session with the host compiler under AddressSanitizer and UBSan, and runs as a child process that
 reads cases as text) against simplyp_amd/pareto.py's statement in NumPy and Python integers, that statement against a case
-enumerated by hand, the key map, the ctypes mirror of the info struct, and the objective resolver.  No GPU needed."""
+enumerated by hand, the key map, the header's and the kernels' constants, and the objective resolver.  No GPU needed."""
 
-import ctypes as C
 import os
-import subprocess
+import re
 
 import numpy as np
 import pytest
 
-from simplyp_amd import abi, pareto
+from simplyp_amd import abi, engine, pareto
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-HEADER = os.path.join(os.path.dirname(HERE), 'include', 'simplyp.h')
-ME = 'entry_under_test'
+import host_program
+from c_header import c_values
+from host_program import ME, rejected
 
 
 @pytest.fixture(scope='session')
-def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp('pareto_host') / 'pareto_host_main')
-    subprocess.check_call(['g++', '-std=c++17', '-O1', '-g', '-Wall', '-Wextra', '-Werror', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=all', '-o', exe, os.path.join(HERE, 'pareto_host_main.cpp')])
-
-    def run(cases):
-        """cases: lines of text -> per case (rc, rest of its line); the sanitizers abort the child on any finding."""
-        p = subprocess.run([exe], input='\n'.join(cases) + '\n', capture_output=True, text=True, timeout=120)
-        assert p.returncode == 0 and p.stderr == '', p.stderr
-        lines = p.stdout.splitlines()
-        assert len(lines) == len(cases)
-        return [(int(l.split(' ', 1)[0]), l.split(' ', 1)[1] if ' ' in l else '') for l in lines]
-    return run
+def driver():
+    return host_program.case_runner(host_program.build('pareto_host_main.cpp'), timeout=120)
 
 
 def hexf(v):
@@ -177,34 +165,19 @@ def test_argument_checks(driver):
     assert [rc for rc, _ in ok] == [0] * 8, ok
     bad = driver([check(E=0), check(E=-3), check(E=(1 << 24) + 1), check(M=0), check(M=9), check(M=-1), check(obj=0), check(sense=None),
                   check(sense=[1, 0]), check(sense=[2, 1]), check(M=3, sense=[1, 1, -2]), check(F=-1), check(by=0, of=0, rank=0)])
-    for rc, msg in bad:
-        assert rc == -1 and msg.startswith(ME + ': '), (rc, msg)
+    rejected(bad)
     # the reference path of the driver goes through the same checks
     (rc, msg), = driver(['ref 1 2 -1 1 0x1p+0 0x1p+1 null null'])
     assert rc == -1 and msg.startswith(ME + ': ') and 'max_fronts' in msg
 
 
-def test_info_struct_layout(tmp_path):
-    """abi.ParetoInfo against the C compiler's view of simplyp_pareto_info, and the constants."""
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % HEADER, 'int main(void){',
-             'printf("size %zu\\n", sizeof(simplyp_pareto_info));']
-    for f, _ in abi.ParetoInfo._fields_:
-        lines.append('printf("%s %%zu\\n", offsetof(simplyp_pareto_info, %s));' % (f, f))
-    lines += ['printf("max_obj %d\\n", SIMPLYP_PARETO_MAX_OBJ);', 'printf("excluded %d\\n", SIMPLYP_PARETO_EXCLUDED);',
-              'printf("unranked %d\\n", SIMPLYP_PARETO_UNRANKED);', 'return 0;}']
-    src = tmp_path / 'layout.c'
-    src.write_text('\n'.join(lines))
-    exe = tmp_path / 'layout'
-    subprocess.check_call(['gcc', '-o', str(exe), str(src)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().splitlines())
-    assert int(got['size']) == C.sizeof(abi.ParetoInfo)
-    for f, _ in abi.ParetoInfo._fields_:
-        assert int(got[f]) == getattr(abi.ParetoInfo, f).offset, f
-    assert (int(got['max_obj']), int(got['excluded']), int(got['unranked'])) == (abi.PARETO_MAX_OBJ, abi.PARETO_EXCLUDED, abi.PARETO_UNRANKED)
+def test_constants():
+    """The header's constants against abi's, and the kernels' constants."""
+    got = c_values(['SIMPLYP_PARETO_MAX_OBJ', 'SIMPLYP_PARETO_EXCLUDED', 'SIMPLYP_PARETO_UNRANKED'])
+    assert (got['SIMPLYP_PARETO_MAX_OBJ'], got['SIMPLYP_PARETO_EXCLUDED'], got['SIMPLYP_PARETO_UNRANKED']) == (abi.PARETO_MAX_OBJ, abi.PARETO_EXCLUDED, abi.PARETO_UNRANKED)
     # the kernels' constants, as the header of the kernels states them
-    with open(os.path.join(os.path.dirname(HERE), 'simplyp_amd', 'csrc', 'simplyp_pareto.hip.h')) as fh:
+    with open(os.path.join(engine.CSRC, 'simplyp_pareto.hip.h')) as fh:
         txt = fh.read()
-    import re
     for name in ('THREADS', 'JTILE', 'JSPLIT'):
         assert int(re.search(r'constexpr int PARETO_%s = (\d+);' % name, txt).group(1)) == getattr(abi, 'PARETO_' + name)
     assert abi.PARETO_JSPLIT % abi.PARETO_JTILE == 0

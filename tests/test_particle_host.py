@@ -1,38 +1,28 @@
 """The particle filter's rules on the CPU: the integer resampling rule of simplyp_amd/csrc/simplyp_resample.h against its
 statement in Python integers (simplyp_amd/particle.py), the mirror's own properties, the weights, the window likelihood against
-the reference's, the layout of simplyp_pf_info, and the whole loop with a toy model.  tests/particle_host_main.cpp includes the
+the reference's, the size of simplyp_pf_info, and the whole loop with a toy model.  tests/particle_host_main.cpp includes the
 header, is built once per session with the host compiler under AddressSanitizer and UBSan, and runs as a child process that
 reads cases as text.  No GPU needed."""
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import helpers
+import host_program
+from c_header import c_values
 from oracle import gof as ogof
 from simplyp_amd import abi, engine, particle, visualise_results as vr
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 ONE = 1 << particle.WEIGHT_BITS
 
 
 @pytest.fixture(scope='session')
-def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp('particle_host') / 'particle_host_main')
-    subprocess.check_call(['g++', '-std=c++17', '-O1', '-g', '-Wall', '-Wextra', '-Werror', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=all', '-o', exe, os.path.join(HERE, 'particle_host_main.cpp')])
-
-    def run(cases):
-        """cases: lines of text -> one list of integers per case; the sanitizers abort the child on any finding."""
-        p = subprocess.run([exe], input='\n'.join(cases) + '\n', capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0 and p.stderr == '', p.stderr
-        lines = p.stdout.splitlines()
-        assert len(lines) == len(cases)
-        return [[int(x) for x in l.split()] for l in lines]
-    return run
+def driver():
+    """cases: lines of text -> one list of integers per case."""
+    run = host_program.case_runner(host_program.build('particle_host_main.cpp'), timeout=300)
+    return lambda cases: [[rc] + [int(x) for x in rest.split()] for rc, rest in run(cases)]
 
 
 def patterns(E, rng):
@@ -177,20 +167,8 @@ def test_loglik_increment_is_the_reference_likelihood_without_its_ten_observatio
     assert np.isfinite(inc[0]) and inc[1] == -np.inf and inc[2] == -np.inf
 
 
-def test_pf_info_layout(tmp_path):
-    """The ctypes mirror vs the C compiler's view of simplyp_pf_info (sizeof / offsetof of every field)."""
-    header = os.path.join(os.path.dirname(engine.HERE), 'include', 'simplyp.h')
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % header, 'int main(void){',
-             'printf("size %zu\\n", sizeof(simplyp_pf_info));']
-    lines += ['printf("%s %%zu\\n", offsetof(simplyp_pf_info, %s));' % (f, f) for f, _ in abi.PfInfo._fields_]
-    src = tmp_path / 'layout.c'
-    src.write_text('\n'.join(lines + ['return 0;}']))
-    exe = tmp_path / 'layout'
-    subprocess.check_call(['gcc', '-o', str(exe), str(src)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().splitlines())
-    assert int(got['size']) == C.sizeof(abi.PfInfo) == 64
-    for f, _ in abi.PfInfo._fields_:
-        assert int(got[f]) == getattr(abi.PfInfo, f).offset, f
+def test_pf_info_size_and_exports():
+    assert c_values(['sizeof(simplyp_pf_info)'])['sizeof(simplyp_pf_info)'] == C.sizeof(abi.PfInfo) == 64
     assert {'simplyp_pf_loglik', 'simplyp_pf_weights', 'simplyp_pf_resample', 'simplyp_gather_members', 'simplyp_pf_jitter'} <= set(engine.ABI_SYMBOLS)
 
 

@@ -8,10 +8,8 @@ Tolerances: the counts are integers and compared with ==.  The header's referenc
 n <= 200 terms of a few roundings each and one rounding to double stay below 200 * 4 * 2^-64 + 2^-53 = 1.6e-16 relative, inside
 the 1e-15 asked of it."""
 
-import ctypes as C
 import os
 import re
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -19,33 +17,17 @@ import pytest
 
 from simplyp_amd import abi, engine, score
 
+import host_program
 import weighted_cases as wc
+from c_header import header_text
+from host_program import rejected
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-HEADER = os.path.join(os.path.dirname(engine.HERE), 'include', 'simplyp.h')
-ME = 'entry_under_test'
 SIZES = (1, 2, 7, 64, 200)
 
 
 @pytest.fixture(scope='session')
-def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp('score_host') / 'score_host_main')
-    subprocess.check_call(['g++', '-std=c++17', '-O1', '-g', '-Wall', '-Wextra', '-Werror', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=all', '-o', exe, os.path.join(HERE, 'score_host_main.cpp')])
-
-    def run(cases):
-        """cases: lines of text -> per case (rc, rest of its line); the sanitizers abort the child on any finding."""
-        p = subprocess.run([exe], input='\n'.join(cases) + '\n', capture_output=True, text=True, timeout=120)
-        assert p.returncode == 0 and p.stderr == '', p.stderr
-        lines = p.stdout.splitlines()
-        assert len(lines) == len(cases)
-        return [(int(l.split(' ', 1)[0]), l.split(' ', 1)[1] if ' ' in l else '') for l in lines]
-    return run
-
-
-def rejected(results):
-    for rc, msg in results:
-        assert rc == -1 and msg.startswith(ME + ': '), (rc, msg)
+def driver():
+    return host_program.case_runner(host_program.build('score_host_main.cpp'), timeout=120)
 
 
 def as_float(bits):
@@ -234,28 +216,13 @@ def test_argument_checks(driver):
     rejected(driver([check(E=0), check(E=(1 << 22) + 1), check(n_rows=-1), check(table=0), check(y=0), check(sums=0), check(counts=0)]))
 
 
-def test_exports_and_layout(tmp_path):
+def test_exports_and_tile():
     engine.build()
     L = engine.lib()
-    with open(HEADER) as fh:
-        txt = fh.read()
-    declared = set(re.findall(r'\b(simplyp_[a-z0-9_]*scores)\s*\(', txt))
+    declared = set(re.findall(r'\b(simplyp_[a-z0-9_]*scores)\s*\(', header_text()))
     assert declared == {'simplyp_scores', 'simplyp_predictive_scores'}
     for name in declared:
         assert name in engine.ABI_SYMBOLS and hasattr(L, name), name
-    assert L.simplyp_abi_version() == abi.ABI_VERSION == 18
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % HEADER, 'int main(void){',
-             'printf("size %zu\\n", sizeof(simplyp_score_info));']
-    for f, _ in abi.ScoreInfo._fields_:
-        lines.append('printf("%s %%zu\\n", offsetof(simplyp_score_info, %s));' % (f, f))
-    lines.append('return 0;}')
-    src = tmp_path / 'layout.c'
-    src.write_text('\n'.join(lines))
-    subprocess.check_call(['gcc', '-o', str(tmp_path / 'layout'), str(src)])
-    got = dict(l.split() for l in subprocess.check_output([str(tmp_path / 'layout')]).decode().splitlines())
-    assert int(got['size']) == C.sizeof(abi.ScoreInfo)
-    for f, _ in abi.ScoreInfo._fields_:
-        assert int(got[f]) == getattr(abi.ScoreInfo, f).offset, f
     m = re.search(r'constexpr int SCORE_TILE = (\d+);', open(os.path.join(engine.CSRC, 'simplyp_score.h')).read())
     assert int(m.group(1)) == abi.SCORE_TILE
 

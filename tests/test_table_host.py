@@ -3,16 +3,15 @@ numpy's 'linear' ranks, period day lists, the prior box), exercised on the CPU: 
 header, is built once per session with the host compiler under AddressSanitizer and UBSan, and runs as a child process that
 reads cases as text.  No GPU needed; the same rules are what the GPU tests of every entry reject bad arguments through."""
 
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from simplyp_amd import abi, marshal
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ME = 'entry_under_test'
+import host_program
+from host_program import rejected
+
 COL = {c: i for i, c in enumerate(marshal.OUT_COLUMNS)}
 FLUX = ['Qr', 'Msus_kg/day', 'TDP_kg/day', 'PP_kg/day']
 LEGAL = (1 << 26) - 1                   # SIMPLYP_MASK_ALL | SIMPLYP_MASK_D_SNOW
@@ -20,28 +19,12 @@ DERIVED = [abi.TQ_DERIVED + v for v in range(6)]
 
 
 @pytest.fixture(scope='session')
-def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp('table_host') / 'table_host_main')
-    subprocess.check_call(['g++', '-std=c++17', '-O1', '-g', '-Wall', '-Wextra', '-Werror', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=all', '-o', exe, os.path.join(HERE, 'table_host_main.cpp')])
-
-    def run(cases):
-        """cases: lines of text -> per case (rc, rest of its line); the sanitizers abort the child on any finding."""
-        p = subprocess.run([exe], input='\n'.join(cases) + '\n', capture_output=True, text=True, timeout=120)
-        assert p.returncode == 0 and p.stderr == '', p.stderr
-        lines = p.stdout.splitlines()
-        assert len(lines) == len(cases)
-        return [(int(l.split(' ', 1)[0]), l.split(' ', 1)[1] if ' ' in l else '') for l in lines]
-    return run
+def driver():
+    return host_program.case_runner(host_program.build('table_host_main.cpp'), timeout=120)
 
 
 def arr(a):
     return 'null' if a is None else ' '.join([str(len(a))] + [x.hex() if isinstance(x, float) else str(int(x)) for x in a])
-
-
-def rejected(results):
-    for rc, msg in results:
-        assert rc == -1 and msg.startswith(ME + ': '), (rc, msg)
 
 
 def ints(text):

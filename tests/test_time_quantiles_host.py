@@ -1,13 +1,9 @@
-"""Host side of the per-member quantiles over time (simplyp_time_quantiles): the exported symbol, the ctypes mirror of its
-info struct, the host interpolation between the two order statistics the device returns (per-period day counts), and the
-refusals of run_simply_p_ensemble, which come before any device is touched.  No GPU needed.
+"""Host side of the per-member quantiles over time (simplyp_time_quantiles): the exported symbol, the header's
+constant and the fields of its info struct, the host interpolation between the two order statistics the device returns
+(per-period day counts), and the refusals of run_simply_p_ensemble, which come before any device is touched.  No GPU needed.
 
 The interpolation is compared with np.quantile(x, q, axis=0, method='linear') BIT FOR BIT: interpolate_quantiles forms
 h = q (n - 1), gamma = h - floor(h) and the lerp exactly as numpy does, from the same two sorted elements."""
-
-import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,7 +11,7 @@ import pytest
 import simplyp_amd as sp
 from simplyp_amd import abi, engine
 
-HEADER = os.path.join(engine.INCLUDE, 'simplyp.h')
+from c_header import c_values
 
 
 def brackets(x, q):
@@ -36,28 +32,9 @@ def test_library_exports_the_entry():
     engine.build()
     assert 'simplyp_time_quantiles' in engine.ABI_SYMBOLS
     assert hasattr(engine.lib(), 'simplyp_time_quantiles')
-    assert engine.lib().simplyp_abi_version() == abi.ABI_VERSION == 18
+    assert c_values(['SIMPLYP_TQ_DERIVED'])['SIMPLYP_TQ_DERIVED'] == abi.TQ_DERIVED
+    assert [f for f, _ in abi.TqInfo._fields_] == ['kernel_ms', 'bytes_read', 'n_sweeps', 'n_periods']
     assert abi.TQ_DERIVED == 64 and abi.TQ_DERIVED_SERIES == ['Q_cumecs', 'SS_mgl', 'TDP_mgl', 'PP_mgl', 'TP_mgl', 'SRP_mgl']
-
-
-def test_tq_info_layout(tmp_path):
-    """abi.TqInfo vs the C compiler's view of simplyp_tq_info (sizeof / offsetof of every field), and the header's constant."""
-    cname, cls = 'simplyp_tq_info', abi.TqInfo
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % HEADER, 'int main(void){',
-             'printf("%s %%zu\\n", sizeof(%s));' % (cname, cname), 'printf("derived %d\\n", (int)SIMPLYP_TQ_DERIVED);']
-    for f, _ in cls._fields_:
-        lines.append('printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (cname, f, cname, f))
-    lines += ['return 0;}']
-    src = tmp_path / 'layout.c'
-    src.write_text('\n'.join(lines))
-    exe = tmp_path / 'layout'
-    subprocess.check_call(['gcc', '-o', str(exe), str(src)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)]).decode().splitlines())
-    assert int(got[cname]) == C.sizeof(cls)
-    assert int(got['derived']) == abi.TQ_DERIVED
-    assert [f for f, _ in cls._fields_] == ['kernel_ms', 'bytes_read', 'n_sweeps', 'n_periods']
-    for f, _ in cls._fields_:
-        assert int(got['%s.%s' % (cname, f)]) == getattr(cls, f).offset, f
 
 
 Q16 = np.concatenate([[0.0, 0.05, 0.5, 0.95, 1.0], np.random.default_rng(16).uniform(0, 1, 11)])

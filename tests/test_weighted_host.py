@@ -4,8 +4,6 @@ built once per session with the host compiler under AddressSanitizer and UBSan, 
 text.  The header is compared with simplyp_amd/weighted.py's statement in Python integers, and that with numpy's
 ``method='inverted_cdf'`` where numpy's floating-point CDF cannot round.  No GPU needed."""
 
-import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -13,31 +11,14 @@ import pytest
 
 from simplyp_amd import weighted
 
+import host_program
 import weighted_cases as wc
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ME = 'entry_under_test'
+from host_program import rejected
 
 
 @pytest.fixture(scope='session')
-def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp('weighted_host') / 'weighted_host_main')
-    subprocess.check_call(['g++', '-std=c++17', '-O1', '-g', '-Wall', '-Wextra', '-Werror', '-fsanitize=address,undefined',
-                           '-fno-sanitize-recover=all', '-o', exe, os.path.join(HERE, 'weighted_host_main.cpp')])
-
-    def run(cases):
-        """cases: lines of text -> per case (rc, rest of its line); the sanitizers abort the child on any finding."""
-        p = subprocess.run([exe], input='\n'.join(cases) + '\n', capture_output=True, text=True, timeout=120)
-        assert p.returncode == 0 and p.stderr == '', p.stderr
-        lines = p.stdout.splitlines()
-        assert len(lines) == len(cases)
-        return [(int(l.split(' ', 1)[0]), l.split(' ', 1)[1] if ' ' in l else '') for l in lines]
-    return run
-
-
-def rejected(results):
-    for rc, msg in results:
-        assert rc == -1 and msg.startswith(ME + ': '), (rc, msg)
+def driver():
+    return host_program.case_runner(host_program.build('weighted_host_main.cpp'), timeout=120)
 
 
 def test_threshold_is_exact(driver):
