@@ -234,9 +234,12 @@ typedef struct {
                                 damping-aware error weights (SIMPLYP_DAMP_*: the estimate of what a fast reach forgets within a
                                 fraction of the day -- its flow, its three masses -- is discounted accordingly).  Same <= 1e-6
                                 parity bar; 40 % fewer right-hand sides on BASELINE config C4.  Pinned to reference-made
-                                tables on chains (C4's, the stiff 12-reach one, dry headwaters), a one-level confluence and a
-                                branching 22-reach network (tests/golden/branch_network.npz: 3.2e-7 there, 1.1 x Cash-Karp
-                                alone); other topologies and regimes are not.  -1 is the conservative switch: Cash-Karp alone. */
+                                tables on chains (C4's, the stiff 12-reach one, dry headwaters), a one-level confluence, a
+                                two-level one of five reaches (tests/golden/net5_*.npz: static EPC0 on newly-converted land of
+                                both kinds, with and without dynamic erodibility, and S-type new land paired with a last
+                                sub-catchment of type A or without new land; 1.2e-7) and a branching 22-reach network
+                                (tests/golden/branch_network.npz: 3.2e-7 there, 1.1 x Cash-Karp alone); other topologies and
+                                regimes are not.  -1 is the conservative switch: Cash-Karp alone. */
     /* ---- forcing uncertainty (simplyp_run / simplyp_run_async only; all zero = off, and the run takes the path it took before
        these fields existed).  Appended at the end of the struct: a caller COMPILED AGAINST THE SHORTER STRUCT MUST BE REBUILT
        (the library reads these fields of whatever it is handed); one that memsets sizeof(simplyp_opts) needs no other change.

@@ -15,7 +15,7 @@ How the reference is driven:
     either as shipped (rtol=0.01, default atol, mxstep=5000) or at rtol=atol=1e-12
     ("tight": the converged solution of the reference's own equations = the parity oracle).
 
-Usage:  python tests/golden/make_golden.py [--long] [--only NAME|mc|unit|knee|heldout|wide|dry|dry-check|c4mc|c4deep|steplen|drynet|branch|closable]
+Usage:  python tests/golden/make_golden.py [--long] [--only NAME (a scenario of scenarios(), e.g. net5_static_2004)|mc|unit|knee|heldout|wide|dry|dry-check|c4mc|c4deep|steplen|drynet|branch|closable]
 """
 
 import argparse
@@ -227,6 +227,33 @@ def scenarios(long_run):
     s['p_SU'] = s['p_SU'].copy(); s['p_SU']['n_SC'] = 12
     s['p']['SC_Qr0'] = 12.0
     out['stiff_chain12_2004'] = s
+
+    # 6. five reaches (1, 2 -> 3; 3, 4 -> 5) with newly-converted land of both kinds on four of them, under the option combinations the
+    #    scenarios above leave out: static EPC0 (with a non-zero EPC0 of semi-natural land, so that the static EPC0 of new agricultural
+    #    land is not 0), dynamic EPC0 without dynamic erodibility, and S-type new land on SC 1 and 4 while the *last* sub-catchment, whose
+    #    type the reference's day boundary uses for every reach (model.py:676, the leaked loop variable), is 'A' or has no new land at all.
+    net5 = [dict(A_catch=21.3, f_Ar=0.25, f_IG=0.25, f_S=0.5, f_NC_S=0.2, L_reach=6200., S_reach=1.4, S_Ar=3., TDPeff=0.02),
+            dict(A_catch=30.4, f_Ar=0.125, f_IG=0.375, f_S=0.5, f_NC_Ar=0.3, f_NC_IG=0.1, L_reach=8100., S_reach=0.9, f_spr=0.4,
+                 TDPeff=np.nan),
+            dict(A_catch=40.0, f_Ar=0.2, f_IG=0.3, f_S=0.5, L_reach=4000., S_reach=0.5, TDPeff=0.1),
+            dict(A_catch=12.0, f_Ar=0.5, f_IG=0.25, f_S=0.25, f_NC_S=0.35, L_reach=3000., S_reach=2.0, f_spr=0.8),
+            dict(A_catch=51.7, f_Ar=0.2, f_IG=0.3, f_S=0.5, f_NC_IG=0.25, L_reach=9000., S_reach=0.8, TDPeff=0.3)]
+    for name, epc0, erod, mode, last_has_nc in (('net5_static_2004', 'n', 'n', 'cal', True),
+                                                ('net5_static_erod_val_2004', 'n', 'y', 'val', True),
+                                                ('net5_dynamic_leakA_2004', 'y', 'y', 'cal', True),
+                                                ('net5_dynamic_leaknone_2004', 'y', 'n', 'val', False)):
+        s = base('2004-01-01', '2004-12-31')
+        s['dyn'] = dict(Dynamic_EPC0=epc0, Dynamic_erodibility=erod)
+        cols = [dict(c) for c in net5]
+        if not last_has_nc:
+            del cols[4]['f_NC_IG']
+        s['p'], s['p_SC'], s['p_struc'] = make_multi_reach(s['p'], s['p_SC'], s['p_struc'], cols,
+                                                           upstream=[np.nan, np.nan, '1, 2', np.nan, '3, 4'], final_flux=[0, 0, 0, 0, 1])
+        s['p_SU'] = s['p_SU'].copy(); s['p_SU']['n_SC'] = 5; s['p_SU']['run_mode'] = mode
+        s['p']['SC_Qr0'] = 5.0
+        if epc0 == 'n':
+            s['p_LU'] = s['p_LU'].copy(); s['p_LU'].loc['EPC0_init_mgl', 'S'] = 0.02
+        out[name] = s
 
     if long_run:
         s = base('1981-01-01', '2010-12-31')

@@ -387,7 +387,8 @@ def random_network_problem(seed, E=40):
 
 
 BUDGET_SCENARIOS = ['tarland_2004_dynamic', 'tarland_2004_dynamic+snow', 'chain4_val_2004', 'confluence3_nc_2004', 'stiff_chain12_2004',
-                    'branch', 'random1', 'random2', 'random3']
+                    'branch', 'random1', 'random2', 'random3',
+                    'net5_static_2004', 'net5_static_erod_val_2004', 'net5_dynamic_leakA_2004', 'net5_dynamic_leaknone_2004']
 
 
 def budget_problem(name, E, solver=None, step_len=1.0, closable=True, seed=7):

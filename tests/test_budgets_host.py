@@ -90,7 +90,8 @@ def golden_out(name, label='tight'):
 GOLDEN_RTOL = 1e-12       # odeint's rtol = atol of the 'tight' tables
 
 
-@pytest.mark.parametrize('name', ['confluence3_nc_2004', 'chain4_val_2004', 'stiff_chain12_2004'])
+@pytest.mark.parametrize('name', ['confluence3_nc_2004', 'chain4_val_2004', 'stiff_chain12_2004', 'net5_static_2004',
+                                  'net5_static_erod_val_2004', 'net5_dynamic_leakA_2004', 'net5_dynamic_leaknone_2004'])
 def test_ratio_identity_and_et_bracket_on_the_reference_tables(name):
     """The workbook's alpha = 1 and k_M = 2 (1.7 on the chain): the PP : sediment input ratio at rounding level, ET strictly inside
     (0, alpha x PET) on every reach and day of the reference's own tables."""

@@ -39,6 +39,12 @@ COVER = [
     ('random3', 'cashkarp_projected', 1, -1, -1, 0, 1.0, ''),
     ('chain4_val_2004', 'aug', 1, 64, -1, 1, 1.0, 'subset'),
     ('stiff_chain12_2004', 'cashkarp', 1, -1, -1, 0, 1.0, ''),
+    # five reaches, new land of both kinds: static EPC0 (constant EPC0 and soil-water concentrations, new land included), dynamic EPC0 with
+    # S-type new land while the last sub-catchment is 'A' / has none
+    ('net5_static_2004', 'f32', 1, 64, -1, 0, 1.0, ''),
+    ('net5_static_erod_val_2004', 'aug', 4, -1, 1, 1, 1.0, ''),
+    ('net5_dynamic_leakA_2004', 'aug', 1, 64, -1, 0, 1.0, ''),
+    ('net5_dynamic_leaknone_2004', 'aug', 4, 64, 1, 0, 2.0, 'subset'),
 ]
 
 

@@ -24,7 +24,10 @@ from simplyp_amd import abi, engine, ensemble, marshal, synthetic
 
 pytestmark = pytest.mark.gpu
 
-SCENARIOS = ['tarland_2004_static', 'tarland_2004_dynamic', 'confluence3_nc_2004', 'chain4_val_2004', 'stiff_chain12_2004']
+SCENARIOS = ['tarland_2004_static', 'tarland_2004_dynamic', 'confluence3_nc_2004', 'chain4_val_2004', 'stiff_chain12_2004',
+             # five reaches with new land of both kinds: static EPC0 (the EPC0 of new land selected by the reach's own type, constant all
+             # year), and S-type new land whose day boundary runs on the hydrology of the last sub-catchment's type ('A' / none)
+             'net5_static_2004', 'net5_static_erod_val_2004', 'net5_dynamic_leakA_2004', 'net5_dynamic_leaknone_2004']
 REACH_COLS = ['Vr', 'Qr_EndOfDay', 'Qr', 'Msus_EndOfDay', 'Msus_kg/day', 'TDPr_EndOfDay', 'TDP_kg/day',
               'PPr_EndOfDay', 'PP_kg/day']
 FLOOR = 1e-12      # columns that are identically 0 (e.g. NC columns without NC land) compare absolutely
@@ -401,7 +404,8 @@ def test_load_balancer_groups_members_with_similar_step_patterns(engine0):
     assert eff[0] < 0.70 and eff[1] > 0.74 and eff[1] - eff[0] > 0.12, eff
 
 
-@pytest.mark.parametrize('name', ['tarland_2004_dynamic', 'chain4_val_2004', 'confluence3_nc_2004'])
+@pytest.mark.parametrize('name', ['tarland_2004_dynamic', 'chain4_val_2004', 'confluence3_nc_2004', 'net5_static_2004',
+                                  'net5_dynamic_leakA_2004'])
 def test_load_balanced_run_is_bitwise_identical(engine0, name):
     """opts.balance = 1 (pilot run + cost-sorted lane slots, routing series kept in slot order): outputs,
     status and per-member work come back in member order and equal the unbalanced run bit for bit."""
@@ -526,7 +530,7 @@ def test_time_reduced_output_equals_sums_of_daily_rows(engine0):
                                  overrides=over, reduce='monthly')
 
 
-@pytest.mark.parametrize('name', ['chain4_val_2004', 'confluence3_nc_2004'])
+@pytest.mark.parametrize('name', ['chain4_val_2004', 'confluence3_nc_2004', 'net5_static_2004', 'net5_dynamic_leakA_2004'])
 def test_pipelined_queue_on_reach_networks_is_bitwise_identical(engine0, name):
     """Multi-reach networks through the task-queue kernel: (reach, chunk, group) tasks in dependency order,
     upstream series through ring buffers of a few chunks, state handed over between chunks.  Same results bit for
@@ -595,7 +599,8 @@ def test_fp32_stage_mode(engine0, name):
     assert abs(worst['cashkarp_aug_f32_rhs'] - worst['cashkarp_aug_rhs']) < 0.10 * worst['cashkarp_aug_rhs'], worst
 
 
-@pytest.mark.parametrize('name', ['tarland_2004_dynamic', 'tarland_1981_2010_dynamic', 'chain4_val_2004', 'confluence3_nc_2004'])
+@pytest.mark.parametrize('name', ['tarland_2004_dynamic', 'tarland_1981_2010_dynamic', 'chain4_val_2004', 'confluence3_nc_2004',
+                                  'net5_static_erod_val_2004'])
 def test_fp32_stage_mode_against_its_oracle_mirror(engine0, oracle_lib, name):
     """The fp32-stage kernel against the oracle's same-arithmetic mirror (cashkarp_aug_f32_day: float stages, float step
     control, double daily integrals), daily flux columns, end-of-day flow and the slow stores, all reaches.  What

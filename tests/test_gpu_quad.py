@@ -55,6 +55,9 @@ CASES = [
     ('chain4_val_2004', 45, dict(balance=1)),                           # validation mode, Qg_min = 0 (plain step gate), cost-ordered slots
     ('tarland_2004_dynamic', 64, dict(rtol=1e-5, atol=1e-9)),           # loose tolerance: many rejected steps
     ('tarland_2004_dynamic', 64, dict(rtol=1e-11, atol=1e-14)),         # tight
+    ('net5_static_2004', 70, dict(time_chunk_days=64)),                 # static EPC0, new land of both kinds on five reaches, pipelined queue
+    ('net5_static_2004', 45, dict(time_chunk_days=-1)),                 # same through the chain kernel
+    ('net5_dynamic_leaknone_2004', 55, dict(balance=1)),                # S-type new land on a last sub-catchment without any, cost-ordered slots
 ]
 
 

@@ -162,10 +162,11 @@ def network_problem(name, queue):
 
 
 @pytest.mark.parametrize('queue', [0, 1])
-@pytest.mark.parametrize('name', ['chain4_val_2004', 'stiff_chain12_2004', 'branch'])
+@pytest.mark.parametrize('name', ['chain4_val_2004', 'stiff_chain12_2004', 'branch', 'net5_static_erod_val_2004'])
 def test_split_equals_unsplit_on_networks(engine0, name, queue):
-    """The 4-reach chain, the stiff 12-reach chain and the branching 22-reach network over two years, the second pair on, cut at day
-    300: one state per (reach, member), chain kernel and pipelined task queue."""
+    """The 4-reach chain, the stiff 12-reach chain, the branching 22-reach network and the five reaches under static EPC0 (constant conc_*,
+    Plab_NC and TDPs_NC rows of S-type new land) over two years, the second pair on, cut at day 300: one state per (reach, member), chain
+    kernel and pipelined task queue."""
     m = network_problem(name, queue)
     whole = run(engine0, m)
     S = m['reach_params'].shape[1]

@@ -142,6 +142,34 @@ def test_prologue_side_effects_and_validation():
         marshal.prologue(p_SU, p_LU, p_SC, p)
 
 
+@pytest.mark.parametrize('name,last', [('net5_static_2004', 'A'), ('net5_dynamic_leaknone_2004', 'None')])
+def test_prologue_side_effects_on_the_five_reach_scenarios(name, last):
+    """The same in-place edits on five sub-catchments with S-type new land on SC 1 and 4, A-type on SC 2 (blank TDPeff -> 0) and on SC 5
+    (or none there), under static EPC0 with a non-zero EPC0 of semi-natural land and under dynamic EPC0: the NC_type row, EPC0_0, Plab0,
+    TDPs0 against what the reference left in p_LU / p_SC."""
+    met, p_struc, p_SU, p_LU, p_SC, p, dyn = helpers.scenario_inputs(name)
+    assert np.isnan(p_SC.loc['TDPeff', 2]) and (dyn['Dynamic_EPC0'] == 'n') == (name == 'net5_static_2004')
+    nc = marshal.prologue(p_SU, p_LU, p_SC, p)
+    assert nc == {1: 'S', 2: 'A', 3: 'None', 4: 'S', 5: last}
+    assert list(p_SC.loc['NC_type']) == ['S', 'A', 'None', 'S', last]
+    marshal.epilogue_mutations(p_SU, p_LU, p_SC, p)
+    after = helpers.meta()[name]
+    assert after['p_SC_after']['2']['TDPeff'] == 0.0 and after['p_LU_after']['S']['EPC0_0'] is not None
+    if name == 'net5_static_2004':
+        assert after['p_LU_after']['S']['EPC0_0'] > 0.0           # the static EPC0 that new agricultural land starts from is not 0
+    for col, rows in after['p_LU_after'].items():
+        for k, v in rows.items():
+            got = p_LU.loc[k, col]
+            assert (np.isnan(got) if v is None else got == pytest.approx(v, rel=1e-15)), (k, col)
+    for col, rows in after['p_SC_after'].items():
+        for k, v in rows.items():
+            got = p_SC.loc[k, int(col)]
+            if isinstance(v, str):
+                assert got == v
+            else:
+                assert got == pytest.approx(v, rel=1e-15), (k, col)
+
+
 def test_topology_parsing_rules():
     """Upstream cell may be blank, an int, or a string list (model.py:480-487)."""
     p = pd.Series({'SC_list': np.arange(1, 5)}, dtype=object)

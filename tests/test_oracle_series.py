@@ -16,7 +16,10 @@ import pytest
 import helpers
 from simplyp_amd import marshal
 
-SCENARIOS = ['tarland_2004_static', 'tarland_2004_dynamic', 'confluence3_nc_2004', 'chain4_val_2004', 'stiff_chain12_2004']
+SCENARIOS = ['tarland_2004_static', 'tarland_2004_dynamic', 'confluence3_nc_2004', 'chain4_val_2004', 'stiff_chain12_2004',
+             # five reaches, new land of both kinds: static EPC0 (with and without dynamic erodibility), and S-type new land while the last
+             # sub-catchment -- whose type the day boundary uses for every reach -- is 'A' / has none (dynamic EPC0 without erodibility)
+             'net5_static_2004', 'net5_static_erod_val_2004', 'net5_dynamic_leakA_2004', 'net5_dynamic_leaknone_2004']
 REACH_COLS = ['Vr', 'Qr_EndOfDay', 'Qr', 'Msus_EndOfDay', 'Msus_kg/day', 'TDPr_EndOfDay', 'TDP_kg/day',
               'PPr_EndOfDay', 'PP_kg/day']
 
