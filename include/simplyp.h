@@ -50,6 +50,8 @@ extern "C" {
  * 17 still with autocorrelated forcing errors and seasonal change factors: forcing_rho, forcing_noise_in / _out,
  * forcing_shift_group_of_day and forcing_shift_groups are appended to simplyp_opts after forcing_table (all zero = off), as the
  * forcing_* fields before them were; no entry point is added and none changes.
+ * 18 still with Thornthwaite PET from each member's air temperature: forcing_reserved (always 0 before) is now forcing_pet_model,
+ * and its plan stands behind the table in the forcing_table workspace; simplyp_opts keeps its size and every offset.
  * 18: simplyp_order_members, the members' lane-slot order of a balanced run from a caller-given cost table; nothing existing
  * changes.
  * 18 still with simplyp_eval_units' which = 6 (the right-hand sides) and which = 7 (the step-rule pieces): adding values of
@@ -275,9 +277,12 @@ typedef struct {
                                            or NULL: no scale, no offset                                                      */
     int32_t  forcing_shift_rows;        /* rows of forcing_shift: 0 with NULL, else 2 (the scales) or 3 (and the T_air offset:
                                            needs opts.snow)                                                                  */
-    int32_t  forcing_reserved;          /* 0                                                                                 */
+    int32_t  forcing_pet_model;         /* 0: off; 1: Thornthwaite PET from the member's own T_air row (below).  This is the
+                                           slot of the former forcing_reserved, which had to be 0: same offset, same size    */
     double*  forcing_table;             /* device [E][2 or 3][D] fp64, caller-owned workspace the sets are written to (required):
-                                           the layout `forcing` has with n_forcing_sets = E; valid after the run             */
+                                           the layout `forcing` has with n_forcing_sets = E; valid after the run.  With
+                                           forcing_pet_model = 1 the workspace is SIMPLYP_FORCING_PET_PLAN_BYTES(D) longer: the
+                                           caller's plan stands behind the table (below) and is only read                    */
     double   forcing_rho[3];            /* per row, finite and in [0, 0.999]: lag-one correlation between consecutive groups;
                                            > 0 needs forcing_sigma > 0 and forcing_group_of_day of that row                  */
     const double*  forcing_noise_in;    /* device [6][E] or NULL: stationary start                                           */
@@ -287,7 +292,39 @@ typedef struct {
     int32_t  forcing_shift_groups;      /* 0: forcing_shift is [rows][E] as before; G in [1, 4096]: [rows][G][E], needs the array
                                            above                                                                             */
     int32_t  forcing_reserved2;         /* 0                                                                                 */
+    /* ---- Thornthwaite PET from each member's own air temperature (forcing_pet_model = 1; forcing_error = 1 and opts.snow = 1
+       only).  No field is added for it: the struct keeps its size and every offset, forcing_pet_model is the former
+       forcing_reserved, and the plan travels in the workspace.  The PET row of member e is
+           PET[e][d] = TH[e][d] * F[e][d]
+       TH: Thornthwaite's 1948 rule (below) applied to the member's FINAL T_air row of the table, (base + offset) + sigma z as
+       the generator wrote it; F: exactly what the generator writes for a base PET of 1.0, (1.0 * scale) * exp(sigma z - 0.5
+       sigma sigma), 1.0 bit for bit with neither.  The base PET row is not read.  The kernel runs on the run's stream after the
+       generator and before the pilot and the main launches.
+       The run must be whole calendar years of daily values, Y = D / 365 of them (integer division; D - 365 Y leap days, at most
+       Y / 4 + 1, else the call is refused), Y <= SIMPLYP_FORCING_PET_YEARS_MAX, M = 12 Y months counted from the first January,
+       year y = m / 12.  The plan is made by the caller from the calendar and the latitude and stands behind the table, at
+       forcing_table + E * 3 * D doubles, in this order:
+           double  daylight[M]   L, the month's mean daylight hours at the latitude (FAO-56 eq. 24, 25, 34)
+           int32_t month[2][M]   the day index of the month's first day; N = its number of days (<= 31; days outside the run
+                                 are left out of the sum)
+           int32_t day[3][D]     j = the month whose 16th is the node at or before day d (0 before the first node; outside
+                                 [0, M) reads the nearest end); k = days since that node (0 after the last node and before the
+                                 first); n = days from node j to node j + 1
+       and the rule, every operation rounded once, no fused multiply-add, pow(x, y) = exp(y * log(x)) for x > 0, 0.0 for
+       x == 0, NaN otherwise:
+           T_m   = (sum of the month's T_air, left to right in day order) / N;   T_m = T_m * (T_m >= 0 ? 1 : 0)
+           I_y   = sum over the year's months in order of (T_m / 5 > 0 ? pow(T_m / 5, 1.514) : 0)
+           a_y   = (((6.75e-7 * ((I * I) * I)) - (7.71e-5 * (I * I))) + (1.792e-2 * I)) + 0.49239
+           V_m   = ((((1.6 * (L / 12)) * (N / 30)) * pow((10 * T_m) / I_y, a_y)) * 10) / N          mm per day, on the 16th
+           TH[d] = V_j                                            when k == 0
+                   V_j + ((V_j+1 - V_j) / n) * k                  otherwise
+       A year whose monthly means are all <= 0 has I = 0 and V = 0 / 0 = NaN: the member's PET is NaN there and its run ends
+       with the non-finite status.  The cap on the years: the monthly values live in LDS.                                     */
 } simplyp_opts;
+
+#define SIMPLYP_FORCING_PET_YEARS_MAX 64     /* years of a Thornthwaite plan: 2 x 768 monthly doubles of LDS per workgroup */
+/* bytes of the plan behind forcing_table for a run of D days: daylight[M], month[2][M], day[3][D], M = 12 * (D / 365) */
+#define SIMPLYP_FORCING_PET_PLAN_BYTES(D) (16LL * 12 * ((D) / 365) + 12LL * (D))
 
 #define SIMPLYP_FORCING_STREAM 0x464F5243u   /* "FORC": the fourth word of the counter of a forcing draw */
 

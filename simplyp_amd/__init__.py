@@ -14,7 +14,7 @@ from .calibrate import sample_posterior, find_map, start_ball      # noqa: F401
 from .pareto import pareto_ranks                                    # noqa: F401
 from .sensitivity import sobol_indices      # noqa: F401
 from .assimilate import assimilate      # noqa: F401
-from .inputs import read_input_data, snow_hydrol_inputs, daily_PET      # noqa: F401
+from .inputs import read_input_data, snow_hydrol_inputs, daily_PET, thornthwaite_PET      # noqa: F401
 from .helper_functions import UC_Q, UC_Qinv, UC_C, UC_Cinv, UC_V, lin_interp   # noqa: F401
 from .visualise_results import (plot_snow, plot_terrestrial, plot_in_stream, plot_instream_summed,   # noqa: F401
                                 goodness_of_fit_stats)
@@ -22,7 +22,7 @@ from .visualise_results import (plot_snow, plot_terrestrial, plot_in_stream, plo
 __all__ = [
     'f_x', 'discretized_soilP', 'ode_f', 'run_simply_p', 'run_simply_p_ensemble', 'run_simply_p_ensemble_windows',
     'derived_P_species', 'sum_to_waterbody', 'sample_posterior', 'find_map', 'start_ball', 'sobol_indices', 'assimilate',
-    'read_input_data', 'snow_hydrol_inputs', 'daily_PET',
+    'read_input_data', 'snow_hydrol_inputs', 'daily_PET', 'thornthwaite_PET',
     'UC_Q', 'UC_Qinv', 'UC_C', 'UC_Cinv', 'UC_V', 'lin_interp',
     'plot_snow', 'plot_terrestrial', 'plot_in_stream', 'plot_instream_summed', 'goodness_of_fit_stats',
 ]

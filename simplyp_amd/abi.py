@@ -22,6 +22,13 @@ FORCING_ROWS = ['P', 'PET', 'T_air']         # rows of a forcing set ('P' is Pre
 # as an exact float64 (-1.0: none)
 FORCING_NOISE_ROWS = ['z_P', 'z_PET', 'z_T_air', 'group_P', 'group_PET', 'group_T_air']
 FORCING_RHO_MAX, FORCING_SHIFT_GROUPS_MAX = 0.999, 4096
+FORCING_PET_MODELS = {'thornthwaite': 1}     # simplyp_opts.forcing_pet_model
+FORCING_PET_YEARS_MAX = 64                   # SIMPLYP_FORCING_PET_YEARS_MAX
+
+
+def forcing_pet_plan_bytes(D):
+    """SIMPLYP_FORCING_PET_PLAN_BYTES: the plan behind the forcing table, daylight[M], month[2][M], day[3][D], M = 12 (D // 365)."""
+    return 16 * 12 * (D // 365) + 12 * D
 
 STATUS_NONFINITE = 1
 STATUS_STEPCAP = 2
@@ -59,7 +66,7 @@ class Opts(C.Structure):
                 # forcing uncertainty (all zero = off); Engine.run(forcing_error=) fills them on a copy of the caller's options
                 ('forcing_error', C.c_int32), ('forcing_member0', C.c_uint32), ('forcing_seed', C.c_uint64),
                 ('forcing_sigma', C.c_double * 3), ('forcing_group_of_day', C.c_void_p * 3), ('forcing_shift', C.c_void_p),
-                ('forcing_shift_rows', C.c_int32), ('forcing_reserved', C.c_int32), ('forcing_table', C.c_void_p),
+                ('forcing_shift_rows', C.c_int32), ('forcing_pet_model', C.c_int32), ('forcing_table', C.c_void_p),
                 # autocorrelated errors and seasonal change factors (all zero = off)
                 ('forcing_rho', C.c_double * 3), ('forcing_noise_in', C.c_void_p), ('forcing_noise_out', C.c_void_p),
                 ('forcing_shift_group_of_day', C.c_void_p), ('forcing_shift_groups', C.c_int32), ('forcing_reserved2', C.c_int32)]

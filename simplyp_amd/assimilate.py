@@ -239,6 +239,7 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
     elif forecast_series is not None:
         raise ValueError("forecast_series needs quantiles: the probabilities of the bands")
     bounds = ensemble.window_bounds(met_df.index, window)
+    forcing_rules.refuse_pet_model(forcing_error, 'assimilate')
 
     with marshal.reference_edits(p_SU, p_LU, p_SC, p):
         hs = _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables, lo, hi, out_reaches)

@@ -64,6 +64,7 @@ struct ForcingErrorArgs {
     uint32_t key0, key1, member0;
     double* table;                         // [E][rows][D]
     int32_t* ident;                        // [E]: e
+    int pet_model;                         // != 0: row 1 is written as F, the row of a base PET of 1.0 (simplyp_forcing_pet_kernel)
 };
 
 // The scale / offset of (row r, member e, day d).
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(FORCING_THREADS) void simplyp_forcing_error_kernel(
 #pragma unroll                                             // (r a constant: the argument block's arrays are read, not indexed)
     for (int r = 0; r < 3; ++r) {
         if (r >= g.rows) break;
-        double v = src[(size_t)r * D];
+        double v = r == 1 && g.pet_model ? 1.0 : src[(size_t)r * D];
         if (r < g.shift_rows) {
             const double sh = forcing_shift_at(g, r, e, d);
             v = r < 2 ? v * sh : v + sh;
@@ -140,7 +141,7 @@ __device__ __forceinline__ void forcing_ar1_row(const ForcingErrorArgs& g, const
         const bool live = d < g.D;
         double v = 0.0;
         if (live) {
-            v = src[d];
+            v = r == 1 && g.pet_model ? 1.0 : src[d];
             if (r < g.shift_rows) {
                 const double sh = forcing_shift_at(g, r, e, d);
                 v = r < 2 ? v * sh : v + sh;
@@ -192,6 +193,106 @@ __global__ __launch_bounds__(FORCING_THREADS) void simplyp_forcing_ar1_kernel(co
         forcing_ar1_row(g, 1, e, lane);
     } else {
         forcing_ar1_row(g, 2, e, lane);
+    }
+}
+
+// ---- Thornthwaite PET from each member's own T_air row (opts.forcing_pet_model = 1; include/simplyp.h states the rule and the
+// plan, simplyp_amd/forcing.py thornthwaite_rows is its NumPy statement, operation for operation).  Runs after a generator
+// above, which wrote the member's final T_air row and, into the PET row, F = the row of a base PET of 1.0 (pet_model there).
+//
+// One workgroup per member (the table is [E][3][D]: the snow module's layout), three stages with barriers between them:
+//   1. monthly means.  The T_air row goes through LDS in tiles of PET_TILE_MONTHS whole months: all lanes load the tile's days
+//      along d (full segments), then one lane per month adds its <= 31 days from LDS left to right -- the order the statement
+//      fixes -- and leaves the clamped mean and its heat-index term (T_m / 5)^1.514 in LDS.
+//   2. per year, one lane: I = the 12 terms added in order, and the exponent a; then per month, one lane: the node value
+//      PET_m / N, written over the heat-index term.
+//   3. lanes along d again: every day reads its two node values from LDS, interpolates, multiplies by F and stores in place --
+//      full segments, the T_air row read once, the PET row read (only with a scale or a sigma) and written once.
+// LDS: the tile (15.5 KB), two arrays of 12 x PET_YEARS_MAX doubles (12 KB) and two of PET_YEARS_MAX; no scratch.  Plan entries
+// are clamped where they index memory: a plan that does not fit the run gives wrong numbers, never an access outside the row.
+constexpr int PET_THREADS = 256;
+constexpr int PET_YEARS_MAX = SIMPLYP_FORCING_PET_YEARS_MAX;
+constexpr int PET_MONTHS_MAX = 12 * PET_YEARS_MAX;
+constexpr int PET_TILE_MONTHS = 64;
+constexpr int PET_TILE_DAYS = PET_TILE_MONTHS * 31;
+
+struct ForcingPetArgs {
+    int E, D, M, Y;                        // M = 12 Y months
+    const int32_t* day;                    // [3][D]: j, k, n
+    const int32_t* month;                  // [2][M]: first day, N
+    const double* daylight;                // [M]: L
+    double* table;                         // [E][3][D]
+    int has_f;                             // the generator wrote an F other than 1.0: a PET scale or sigma
+};
+
+// x^y = exp(y log x) for x > 0; exactly 0 for x == 0 (either sign); NaN for a NaN (0 / 0 of a year with I = 0).
+__device__ __forceinline__ double forcing_pow(double x, double y)
+{
+    const double p = sp_exp(y * sp_log(x > 0.0 ? x : 1.0));
+    return x > 0.0 ? p : x == 0.0 ? 0.0 : __builtin_nan("");
+}
+
+__global__ __launch_bounds__(PET_THREADS) void simplyp_forcing_pet_kernel(const ForcingPetArgs g)
+{
+    __shared__ double tile[PET_TILE_DAYS];
+    __shared__ double t_m[PET_MONTHS_MAX];                 // the clamped monthly mean
+    __shared__ double val[PET_MONTHS_MAX];                 // the heat-index term, then the node value
+    __shared__ double heat[PET_YEARS_MAX], expo[PET_YEARS_MAX];
+    const int e = (int)blockIdx.x, tid = (int)threadIdx.x;     // (host: E blocks, M <= PET_MONTHS_MAX, Y <= PET_YEARS_MAX)
+    const int D = g.D, M = g.M;
+    const double* t_air = g.table + ((size_t)e * 3 + 2) * (size_t)D;
+    double* pet = g.table + ((size_t)e * 3 + 1) * (size_t)D;
+    const int32_t* first = g.month;
+    const int32_t* ndays = g.month + M;
+
+    for (int m0 = 0; m0 < M; m0 += PET_TILE_MONTHS) {      // uniform trip count: barriers inside
+        const int base = min(max(first[m0], 0), D);
+        const int count = min(PET_TILE_DAYS, D - base);
+        for (int i = tid; i < count; i += PET_THREADS) tile[i] = t_air[base + i];
+        __syncthreads();
+        const int m = m0 + tid;
+        if (tid < PET_TILE_MONTHS && m < M) {
+            const unsigned off = (unsigned)first[m] - (unsigned)base;
+            const int nd = min(max(ndays[m], 0), 31);
+            double s = 0.0;
+            for (int i = 0; i < nd; ++i) {
+                const unsigned idx = off + (unsigned)i;
+                if (idx < (unsigned)count) s = s + tile[idx];
+            }
+            const double t = s / (double)nd;
+            const double adj = t * (t >= 0.0 ? 1.0 : 0.0);
+            const double x = adj / 5.0;
+            t_m[m] = adj;
+            val[m] = x > 0.0 ? forcing_pow(x, 1.514) : 0.0;
+        }
+        __syncthreads();                                   // also: the tile is free for the next load
+    }
+
+    for (int y = tid; y < g.Y; y += PET_THREADS) {
+        double I = 0.0;
+        for (int j = 0; j < 12; ++j) I = I + val[y * 12 + j];
+        const double I2 = I * I, I3 = I2 * I;
+        heat[y] = I;
+        expo[y] = (((6.75e-07 * I3) - (7.71e-05 * I2)) + (1.792e-02 * I)) + 0.49239;
+    }
+    __syncthreads();
+    for (int m = tid; m < M; m += PET_THREADS) {
+        const int y = m / 12;
+        const double N = (double)min(max(ndays[m], 0), 31);
+        const double p = forcing_pow((10.0 * t_m[m]) / heat[y], expo[y]);
+        val[m] = ((((1.6 * (g.daylight[m] / 12.0)) * (N / 30.0)) * p) * 10.0) / N;
+    }
+    __syncthreads();
+
+    const int32_t* node = g.day;
+    const int32_t* pos = g.day + (size_t)D;
+    const int32_t* len = g.day + 2 * (size_t)D;
+    for (int d = tid; d < D; d += PET_THREADS) {
+        const int j = min(max(node[d], 0), M - 1);
+        const int k = pos[d];
+        const double y0 = val[j], y1 = val[min(j + 1, M - 1)];
+        const double th = k == 0 ? y0 : y0 + ((y1 - y0) / (double)len[d]) * (double)k;
+        pet[d] = g.has_f ? th * pet[d] : th;
     }
 }
 

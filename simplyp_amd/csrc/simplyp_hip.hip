@@ -468,6 +468,20 @@ int check_args(simplyp_ctx* ctx, const simplyp_dims* dims, const simplyp_opts* o
             return fail(ctx, SIMPLYP_ERR_ARG, "forcing_shift_group_of_day needs forcing_shift_groups >= 1: the number of shift groups");
         if (opts->forcing_reserved2)
             return fail(ctx, SIMPLYP_ERR_ARG, "forcing_reserved2 must be 0");
+        if (opts->forcing_pet_model != 0 && opts->forcing_pet_model != 1)
+            return fail(ctx, SIMPLYP_ERR_ARG, "forcing_pet_model must be 0 (off) or 1 (Thornthwaite) (got %d)", opts->forcing_pet_model);
+        if (opts->forcing_pet_model) {
+            if (!opts->snow)
+                return fail(ctx, SIMPLYP_ERR_ARG, "forcing_pet_model = 1 derives PET from the member's T_air row, a forcing row only with the snow module in the kernel (opts.snow = 1)");
+            const int years = dims->D / 365;                                   // whole calendar years: 365 each and the leap days
+            if (years < 1 || dims->D - 365 * years > years / 4 + 1)
+                return fail(ctx, SIMPLYP_ERR_ARG, "forcing_pet_model = 1 needs whole calendar years of daily values: D = %d is no 365 x years + leap days", dims->D);
+            if (years > SIMPLYP_FORCING_PET_YEARS_MAX)
+                return fail(ctx, SIMPLYP_ERR_ARG, "forcing_pet_model = 1 takes at most %d years: the monthly values of a member live in LDS (D = %d is %d)",
+                            (int)SIMPLYP_FORCING_PET_YEARS_MAX, dims->D, years);
+        }
+    } else if (opts->forcing_pet_model) {
+        return fail(ctx, SIMPLYP_ERR_ARG, "forcing_pet_model needs forcing_error = 1");
     } else if (opts->forcing_rho[0] != 0.0 || opts->forcing_rho[1] != 0.0 || opts->forcing_rho[2] != 0.0 || opts->forcing_noise_in ||
                opts->forcing_noise_out || opts->forcing_shift_group_of_day || opts->forcing_shift_groups) {
         return fail(ctx, SIMPLYP_ERR_ARG, "forcing_rho, forcing_noise_in / _out, forcing_shift_group_of_day and forcing_shift_groups need forcing_error = 1");
@@ -500,6 +514,7 @@ int generate_forcing(simplyp_ctx* ctx, const simplyp_opts& opts, simplyp::Kernel
     g.key0 = (uint32_t)(opts.forcing_seed & 0xffffffffu); g.key1 = (uint32_t)(opts.forcing_seed >> 32);
     g.member0 = opts.forcing_member0;
     g.table = opts.forcing_table; g.ident = (int32_t*)ctx->forcing_ident.ptr;
+    g.pet_model = opts.forcing_pet_model;
     if (ar1) {                                                            // one wave per (member, row)
         const long long waves = (long long)a.E * g.rows;                  // (check_args: below 2^31)
         const unsigned blocks = (unsigned)((waves + simplyp::FORCING_AR1_WAVES - 1) / simplyp::FORCING_AR1_WAVES);
@@ -509,6 +524,17 @@ int generate_forcing(simplyp_ctx* ctx, const simplyp_opts& opts, simplyp::Kernel
         hipLaunchKernelGGL(simplyp::simplyp_forcing_error_kernel, dim3(blocks), dim3(simplyp::FORCING_THREADS), 0, ctx->stream, g);
     }
     HIP_TRY(ctx, hipGetLastError());
+    if (opts.forcing_pet_model) {                                         // PET from the T_air row just written, one block per member
+        simplyp::ForcingPetArgs p{};
+        p.E = a.E; p.D = a.D; p.Y = a.D / 365; p.M = 12 * p.Y;                // (check_args: snow, whole years, Y <= cap)
+        p.daylight = opts.forcing_table + (size_t)a.E * 3 * (size_t)a.D;     // the plan behind the table: daylight[M], month[2][M], day[3][D]
+        p.month = (const int32_t*)(p.daylight + p.M);
+        p.day = p.month + 2 * p.M;
+        p.table = opts.forcing_table;
+        p.has_f = g.sigma[1] > 0.0 || g.shift_rows >= 2;
+        hipLaunchKernelGGL(simplyp::simplyp_forcing_pet_kernel, dim3((unsigned)a.E), dim3(simplyp::PET_THREADS), 0, ctx->stream, p);
+        HIP_TRY(ctx, hipGetLastError());
+    }
     a.forcing = opts.forcing_table; a.n_sets = a.E; a.forcing_of_member = g.ident;
     return SIMPLYP_OK;
 }

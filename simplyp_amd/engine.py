@@ -397,7 +397,8 @@ class Engine(object):
 
     def _forcing_opts(self, opts, fe, E, D, rows, noise_in=None, noise_out=None):
         """(a copy of ``opts`` with the forcing_* fields filled from the resolved ``fe`` and the noise state, [table, the device
-        arrays they point at: groups, shift, noise in, noise out, shift groups])."""
+        arrays they point at: groups, shift, noise in, noise out, shift groups]); the table is a view of a workspace that
+        also holds the plan of a PET model behind it."""
         from . import forcing as forcing_rules
         torch = self.torch
         forcing_rules.check_resolved(fe, E, D, rows)
@@ -414,13 +415,16 @@ class Engine(object):
                 or not noise_out.is_contiguous() or noise_out.device != self.tdev):
             raise ValueError("forcing_noise_out must be True or a contiguous float64 tensor of shape %s on %s" % ((n_noise, E), self.tdev))
         nbytes = E * rows * D * 8
+        pet = fe.get('pet')
+        plan_bytes = 0 if pet is None else abi.forcing_pet_plan_bytes(D)      # the plan of a PET model stands behind the table
         with torch.cuda.device(self.tdev):
             free = torch.cuda.mem_get_info(self.tdev)[0] + torch.cuda.memory_reserved(self.tdev) - torch.cuda.memory_allocated(self.tdev)
-        if nbytes > free:
+        if nbytes + plan_bytes > free:
             raise ValueError("forcing_error: the members' forcing table [E = %d, %d, D = %d] takes %d bytes (%.2f GB), the device has "
                              "%.2f GB free next to the output table -- run fewer members per call, or windows of fewer days"
                              % (E, rows, D, nbytes, nbytes / 1e9, free / 1e9))
-        table = torch.empty((E, rows, D), dtype=torch.float64, device=self.tdev)
+        work = torch.empty((E * rows * D + (plan_bytes + 7) // 8,), dtype=torch.float64, device=self.tdev)
+        table = work[:E * rows * D].view(E, rows, D)
         if noise_out is True:
             noise_out = torch.empty((n_noise, E), dtype=torch.float64, device=self.tdev)
         groups = [None if g is None else self.to_device(g, torch.int32) for g in fe['groups']]
@@ -442,6 +446,15 @@ class Engine(object):
         o.forcing_noise_out = None if noise_out is None else noise_out.data_ptr()
         o.forcing_shift_group_of_day = None if sgroups is None else sgroups.data_ptr()
         o.forcing_shift_groups = 0 if sgroups is None else int(shift.shape[1])
+        if pet is not None:                                      # daylight [M], month [2, M], day [3, D]: include/simplyp.h
+            M = int(pet['months'])
+            assert M == 12 * (D // 365) and len(pet['node']) == D
+            tail = work[E * rows * D:]
+            tail[:M] = self.to_device(pet['daylight'], torch.float64)
+            ints = tail[M:].view(torch.int32)
+            ints[:2 * M] = self.to_device(np.concatenate([pet['first'], pet['days']]), torch.int32)
+            ints[2 * M:2 * M + 3 * D] = self.to_device(np.concatenate([pet['node'], pet['k'], pet['n']]), torch.int32)
+            o.forcing_pet_model = int(pet['model'])
         return o, [table, groups, shift, noise_in, noise_out, sgroups]
 
 

@@ -36,8 +36,17 @@ Seasonal change factors: ``scale`` (``offset``) may be ``[G, E]`` or ``[G]`` tog
 ``'month_of_year'`` (ids month - 1, G = 12) or an int array [D] with ids in [0, G) --: day ``d`` takes the entry of its shift
 group.  The rows share one shift-group array; ``G`` lies in [1, 4096].
 
+Thornthwaite PET from the member's own air temperature (``'PET': {'model': 'thornthwaite', 'latitude': deg}``, snow module
+only): the member's PET row is ``TH * F`` -- ``TH`` = ``thornthwaite_rows`` of the member's FINAL T_air row above, ``F`` = the PET
+row the formulas above give for a base PET of 1.0 (the scale and the lognormal multiplier; 1.0 bit for bit with neither).  The
+base PET column is not read.  ``thornthwaite_plan`` makes the calendar side once per call on the host; ``thornthwaite_rows``
+states the rule (the reference's inputs.py:232-312, :416-508, quirks included) in the device's order of operations.
+
 The public calls take ``forcing_error`` as a dict of dicts (``resolve``); ``Engine.run`` takes what ``resolve`` returns.
 """
+
+import calendar
+import math
 
 import numpy as np
 
@@ -45,7 +54,9 @@ from . import abi, predictive
 
 SIGMA_MAX = 2.0
 RHO_MAX, SHIFT_GROUPS_MAX = abi.FORCING_RHO_MAX, abi.FORCING_SHIFT_GROUPS_MAX
-_ROW_KEYS = [('sigma', 'groups', 'scale', 'rho', 'scale_groups'), ('sigma', 'groups', 'scale', 'rho', 'scale_groups'),
+PET_YEARS_MAX = abi.FORCING_PET_YEARS_MAX
+_ROW_KEYS = [('sigma', 'groups', 'scale', 'rho', 'scale_groups'),
+             ('sigma', 'groups', 'scale', 'rho', 'scale_groups', 'model', 'latitude'),
              ('sigma', 'groups', 'offset', 'rho', 'offset_groups')]
 _ORDINAL_1970 = 719163                       # date(1970, 1, 1).toordinal()
 
@@ -112,6 +123,131 @@ def _grouped_shift(what, key, value, ids, G, E):
     return np.ascontiguousarray(val)
 
 
+def daylight_hours(latitude, leap):
+    """Mean daylight hours [12] of the months of a (leap) year at ``latitude`` degrees: FAO-56 eq. 24 (solar declination of the
+    day of the year), eq. 25 (sunset hour angle, its cosine clipped to [-1, 1]: polar day and night) and eq. 34, the days of a
+    month added in order and divided by their number."""
+    phi = latitude * (math.pi / 180.0)
+    out, doy = [], 1
+    for n in (31, 29 if leap else 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31):
+        total = 0.0
+        for _ in range(n):
+            dec = 0.409 * math.sin((2.0 * math.pi / 365.0) * doy - 1.39)
+            total += (24.0 / math.pi) * math.acos(min(max(-math.tan(phi) * math.tan(dec), -1.0), 1.0))
+            doy += 1
+        out.append(total / n)
+    return out
+
+
+def thornthwaite_plan(index, latitude, max_years=PET_YEARS_MAX):
+    """The calendar side of Thornthwaite PET for the daily dates ``index`` at ``latitude`` degrees, made once per call: dict(D,
+    months M = 12 x years, years, latitude; per month m counted from the first January: first (int32 [M], the day index of its
+    first day), days (int32 [M], N = daysinmonth), daylight (float64 [M], L); per day d: node (int32 [D], j = the month whose
+    16th is the node at or before d, 0 before the first node), k (int32 [D], days since that node; 0 before the first node and
+    after the last), n (int32 [D], days from node j to node j + 1)).  L of a year comes from the normal-year table until the
+    record's first leap year and from the leap-year table in EVERY year from then on: the reference's loop assigns the leap
+    table and never assigns back, and a drop-in reproduces that.  ``ValueError`` for a latitude outside [-90, 90], dates that
+    are not consecutive days, a record that does not run from a 1 January to a 31 December, and more than ``max_years``
+    years (the device's cap; None on the host: no cap)."""
+    try:
+        latitude = float(latitude)
+    except (TypeError, ValueError):
+        raise ValueError("Thornthwaite PET needs a latitude in degrees (got %r)" % (latitude,))
+    if not -90.0 <= latitude <= 90.0:
+        raise ValueError("Thornthwaite PET: latitude must lie in [-90, 90] degrees (got %r)" % (latitude,))
+    D = len(index)
+    ordinal = calendar_groups(index, 'day') if D else np.zeros(0, dtype=np.int64)
+    if D == 0 or not np.array_equal(ordinal - ordinal[0], np.arange(D)):
+        raise ValueError("Thornthwaite PET needs daily met data: one row per consecutive day")
+    year, month, dom = (np.asarray(getattr(index, a), dtype=np.int64) for a in ('year', 'month', 'day'))
+    for at, ok in ((0, month[0] == 1 and dom[0] == 1), (-1, month[-1] == 12 and dom[-1] == 31)):
+        if not ok:
+            raise ValueError("PET calc requires input met data for whole calendar years. Year %d does not run from 1 January to "
+                             "31 December. Check input met data, or change the start/end dates in the parameter file" % year[at])
+    years = int(year[-1] - year[0] + 1)
+    if max_years is not None and years > max_years:
+        raise ValueError("Thornthwaite PET on the device takes at most %d years per call (got %d)" % (max_years, years))
+    M = 12 * years
+    m_of_day = (year - year[0]) * 12 + month - 1
+    first = np.searchsorted(m_of_day, np.arange(M)).astype(np.int64)
+    days = np.diff(np.append(first, D))
+    tables, sticky, daylight = (daylight_hours(latitude, False), daylight_hours(latitude, True)), False, []
+    for y in range(int(year[0]), int(year[-1]) + 1):
+        sticky = sticky or calendar.isleap(y)
+        daylight.extend(tables[sticky])
+    x_node = first + 15                                          # the 16th of every month
+    node = np.clip(np.searchsorted(x_node, np.arange(D), side='right') - 1, 0, M - 1)
+    nxt = np.minimum(node + 1, M - 1)
+    inside = (np.arange(D) >= x_node[0]) & (nxt > node)
+    k = np.where(inside, np.arange(D) - x_node[node], 0)
+    n = np.where(nxt > node, x_node[nxt] - x_node[node], 1)
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    return dict(D=D, months=M, years=years, latitude=latitude, first=i32(first), days=i32(days),
+                daylight=np.ascontiguousarray(daylight, dtype=np.float64), node=i32(node), k=i32(k), n=i32(n))
+
+
+def _pow(x, y):
+    """x^y as the device has it: exp(y log x) for x > 0, exactly 0.0 for x == 0, NaN otherwise."""
+    with np.errstate(all='ignore'):
+        p = np.exp(y * np.log(np.where(x > 0.0, x, 1.0)))
+    return np.where(x > 0.0, p, np.where(x == 0.0, 0.0, np.nan))
+
+
+def thornthwaite_rows(t_air, plan, monthly=False):
+    """Thornthwaite's daily PET [E, D] (mm/day) of the air temperature rows ``t_air`` [E, D] under ``plan``
+    (``thornthwaite_plan``): the statement the device copies.  Every operation is rounded once, in the order written, no fused
+    multiply-add::
+
+        T_m   = (T_air of the month's days added left to right in day order) / N;   T_m = T_m * (T_m >= 0)
+        I_y   = the year's twelve (T_m / 5) ** 1.514 added in month order, 0.0 where T_m / 5 is not > 0
+        a_y   = (((6.75e-7 * ((I * I) * I)) - (7.71e-5 * (I * I))) + (1.792e-2 * I)) + 0.49239
+        PET_m = (((1.6 * (L / 12)) * (N / 30)) * ((10 * T_m) / I_y) ** a_y) * 10             mm per month
+        V_m   = PET_m / N                                                                     mm per day, on the 16th
+        TH[d] = V_j when k == 0, else V_j + ((V_(j+1) - V_j) / n) * k                         j, k, n of day d from the plan
+
+    with ``x ** y`` = ``exp(y * log(x))`` for ``x > 0``, exactly ``0.0`` for ``x == 0`` and NaN otherwise.  A year whose monthly
+    means are all <= 0 has ``I = 0`` and ``PET_m = 0 / 0`` = NaN, as in the reference; every day that interpolates from one of
+    its nodes is NaN.  (The reference's pandas step treats such nodes as missing and bridges up to 32 days on either side of
+    them from the finite nodes around; a record that mixes such years with others differs there, and is non-finite in both.)
+    ``monthly=True``: returns (TH, the clamped T_m [E, M], PET_m [E, M])."""
+    t = np.asarray(t_air, dtype=np.float64)
+    E, D = t.shape
+    if D != plan['D']:
+        raise ValueError("thornthwaite_rows: the plan covers %d days, the rows have %d" % (plan['D'], D))
+    M, days = plan['months'], plan['days'].astype(np.int64)
+    N = days.astype(np.float64)
+    at = np.minimum(plan['first'].astype(np.int64)[:, None] + np.arange(31)[None, :], D - 1)       # [M, 31]
+    s = np.zeros((E, M))
+    for i in range(31):                                          # (+ 0.0 past the month's end leaves the sum as it is)
+        s = s + np.where(i < days, t[:, at[:, i]], 0.0)
+    with np.errstate(all='ignore'):
+        tm = s / N
+        tm = tm * (tm >= 0.0)
+        x = tm / 5.0
+        term = np.where(x > 0.0, _pow(x, 1.514), 0.0)
+        I = np.zeros((E, M // 12))
+        for j in range(12):
+            I = I + term[:, j::12]
+        I2 = I * I
+        I3 = I2 * I
+        a = (((6.75e-07 * I3) - (7.71e-05 * I2)) + (1.792e-02 * I)) + 0.49239
+        p = _pow((10.0 * tm) / np.repeat(I, 12, axis=1), np.repeat(a, 12, axis=1))
+        pet_m = (((1.6 * (plan['daylight'] / 12.0)) * (N / 30.0)) * p) * 10.0
+        v = pet_m / N
+        j, k, n = plan['node'].astype(np.int64), plan['k'], plan['n']
+        y0, y1 = v[:, j], v[:, np.minimum(j + 1, M - 1)]
+        th = np.where(k == 0, y0, y0 + ((y1 - y0) / n.astype(np.float64)) * k.astype(np.float64))
+    return (th, tm, pet_m) if monthly else th
+
+
+def refuse_pet_model(forcing_error, where):
+    """``ValueError`` when the public ``forcing_error`` asks for a PET model in a call that runs the days in windows."""
+    row = forcing_error.get('PET') if isinstance(forcing_error, dict) else None
+    if isinstance(row, dict) and row.get('model') is not None:
+        raise ValueError("forcing_error['PET']['model'] is not offered in %s: the daily interpolation between the monthly values "
+                         "crosses year boundaries, so windows laid end to end would not be the one call" % where)
+
+
 def resolve(forcing_error, index, E, snow, seed=0, member0=0):
     """The public ``forcing_error`` -- ``{'P': {'sigma':, 'groups':, 'rho':, 'scale':, 'scale_groups':}, 'PET': {...}, 'T_air':
     {'sigma':, 'groups':, 'rho':, 'offset':, 'offset_groups':}}``, every key optional, ``groups`` = ``'day'`` (default) |
@@ -123,7 +259,10 @@ def resolve(forcing_error, index, E, snow, seed=0, member0=0):
     (int32 [D] or None: the one array the rows share), seed, member0).  None for None.  ``ValueError`` for an unknown key, a
     sigma that is not finite or outside [0, 2], a rho that is not finite or outside [0, 0.999] or comes without sigma, an array of
     the wrong shape, group ids outside [0, 2^31), shift group ids outside [0, G), G outside [1, 4096], rows with different shift
-    groups, ``'T_air'`` without the in-kernel snow module, a seed outside [0, 2^64)."""
+    groups, ``'T_air'`` without the in-kernel snow module, a seed outside [0, 2^64).  ``'PET'`` also takes ``'model':
+    'thornthwaite'`` with ``'latitude'`` in degrees: the result's ``pet`` is then the plan of ``thornthwaite_plan`` with ``model``
+    = ``abi.FORCING_PET_MODELS['thornthwaite']`` (None otherwise); ``ValueError`` for another model, a missing latitude or one
+    outside [-90, 90], dates that are not whole calendar years of consecutive days (at most ``PET_YEARS_MAX``), no snow module."""
     if forcing_error is None:
         return None
     if not isinstance(forcing_error, dict):
@@ -139,7 +278,7 @@ def resolve(forcing_error, index, E, snow, seed=0, member0=0):
         raise ValueError("forcing_seed must be in [0, 2^64)")
     if not 0 <= member0 or member0 + E > 1 << 32:
         raise ValueError("forcing member ids must stay below 2^32")
-    sigma, rho, groups, shift, sg, n_groups = np.zeros(3), np.zeros(3), [None] * 3, [None] * 3, None, 0
+    sigma, rho, groups, shift, sg, n_groups, pet = np.zeros(3), np.zeros(3), [None] * 3, [None] * 3, None, 0, None
     for r, name in enumerate(abi.FORCING_ROWS):
         row = forcing_error.get(name)
         if row is None:
@@ -161,6 +300,17 @@ def resolve(forcing_error, index, E, snow, seed=0, member0=0):
             raise ValueError("%s['rho'] must be finite and in [0, %g] (got %r)" % (what, RHO_MAX, row.get('rho')))
         if rho[r] > 0.0 and not sigma[r] > 0.0:
             raise ValueError("%s['rho'] > 0 needs 'sigma' > 0: there is no error to correlate" % what)
+        if row.get('model') is not None:
+            if row['model'] not in abi.FORCING_PET_MODELS:
+                raise ValueError("%s['model'] must be one of %s (got %r)" % (what, sorted(abi.FORCING_PET_MODELS), row['model']))
+            if not snow:
+                raise ValueError("%s['model'] needs the in-kernel snow module (snow_in_kernel=True): without it the members have "
+                                 "no T_air row to derive PET from" % what)
+            if row.get('latitude') is None:
+                raise ValueError("%s['model'] needs %s['latitude'] in degrees" % (what, what))
+            pet = dict(thornthwaite_plan(index, row['latitude']), model=abi.FORCING_PET_MODELS[row['model']])
+        elif row.get('latitude') is not None:
+            raise ValueError("%s['latitude'] needs %s['model']" % (what, what))
         g = _groups("%s['groups']" % what, row.get('groups', 'day'), index)
         groups[r] = g if sigma[r] > 0.0 else None
         key = _ROW_KEYS[r][2]
@@ -189,7 +339,7 @@ def resolve(forcing_error, index, E, snow, seed=0, member0=0):
             rows = [np.broadcast_to(x, (n_groups, E)) for x in rows]
         sh = np.ascontiguousarray(np.stack(rows))
     return dict(sigma=sigma, rho=rho, groups=groups, shift=sh, shift_groups=None if sg is None else np.ascontiguousarray(sg, dtype=np.int32),
-                seed=seed, member0=member0)
+                seed=seed, member0=member0, pet=pet)
 
 
 def any_rho(fe):
@@ -212,6 +362,13 @@ def check_resolved(fe, E, D, rows):
             raise ValueError("forcing_error: rho needs one finite entry in [0, %g] per forcing row %s" % (RHO_MAX, abi.FORCING_ROWS))
         if ((rho > 0.0) & ~(sigma > 0.0)).any() or any(rho[r] > 0.0 and fe['groups'][r] is None for r in range(3)):
             raise ValueError("forcing_error: rho > 0 needs sigma > 0 and the group ids of that row")
+    pet = fe.get('pet')
+    if pet is not None:
+        if rows != 3:
+            raise ValueError("forcing_error: a PET model needs the T_air row of the in-kernel snow module")
+        if pet['D'] != D or pet['months'] != 12 * pet['years'] or not 1 <= pet['years'] <= PET_YEARS_MAX:
+            raise ValueError("forcing_error: the PET plan covers %d days in %d months of %d years, the run has %d days (at most %d "
+                             "whole years)" % (pet['D'], pet['months'], pet['years'], D, PET_YEARS_MAX))
     sh, sg = fe.get('shift'), fe.get('shift_groups')
     if sg is None:
         if sh is not None and (np.ndim(sh) != 2 or np.shape(sh)[0] not in (2, 3) or np.shape(sh)[1] != E):
@@ -262,6 +419,8 @@ def day_window(fe, lo, hi):
     when handed the noise state of the days before)."""
     if fe is None:
         return None
+    if fe.get('pet') is not None and (lo, hi) != (0, fe['pet']['D']):
+        raise ValueError("forcing_error: a PET model does not run in windows of days (its interpolation crosses year boundaries)")
     sg = fe.get('shift_groups')
     return dict(fe, groups=[None if g is None else np.ascontiguousarray(g[lo:hi]) for g in fe['groups']],
                 shift_groups=None if sg is None else np.ascontiguousarray(sg[lo:hi]))
@@ -331,7 +490,7 @@ def table(base, fe, forcing_of_member=None, E=None, noise=None, return_noise=Fal
     noise_out[3:] = -1.0
     out = base[fom].copy()                                       # [E, rows, D]
     for r in range(rows):
-        v = out[:, r, :]
+        v = np.ones((E, D)) if r == 1 and fe.get('pet') is not None else out[:, r, :]     # a PET model: F, the row of a base of 1.0
         if sh is not None and r < sh.shape[0]:
             s_ = sh[r][:, None] if sg is None else sh[r][np.asarray(sg, dtype=np.int64), :].T        # [E, 1] or [E, D]
             v = v * s_ if r < 2 else v + s_
@@ -343,4 +502,6 @@ def table(base, fe, forcing_of_member=None, E=None, noise=None, return_noise=Fal
                 z = normals(fe, r, E)
             v = v * multiplier(sgm, z) if r < 2 else v + sgm * z
         out[:, r, :] = v
+    if fe.get('pet') is not None:
+        out[:, 1, :] = thornthwaite_rows(out[:, 2, :], fe['pet']) * out[:, 1, :]
     return (out, noise_out) if return_noise else out

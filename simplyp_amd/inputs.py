@@ -90,7 +90,7 @@ def read_input_data(params_fpath, setup_overrides=None):
         met_df.rename(columns={'Precipitation': 'P'}, inplace=True)
 
     if 'PET' not in met_df.columns:
-        met_df = daily_PET(latitude=p['latitude'], met_df=met_df)
+        met_df = thornthwaite_PET(latitude=p['latitude'], met_df=met_df)
         print('PET estimated using the Thornthwaite method')
 
     # Observations (ref :118-152)
@@ -162,7 +162,33 @@ def daily_PET(latitude, met_df):
 
     Out of scope for the time-stepping hot path:
     supply a ``PET`` column in the met data, as the Tarland example does.
+
+    This name stays the stub it was (tests/test_host.py pins its
+    ``NotImplementedError``); ``thornthwaite_PET`` below is the reference's
+    function under a new name, and ``read_input_data`` calls that one.
     """
     raise NotImplementedError(
         "daily_PET (Thornthwaite) is not part of the MI355X engine; "
         "provide a 'PET' column in the meteorological input file")
+
+
+def thornthwaite_PET(latitude, met_df):
+    """Daily Thornthwaite (1948) PET from air temperature: what the reference's
+    ``daily_PET`` (inputs.py:232-312, :416-508) computes, quirks included.
+
+    ``latitude`` in degrees, ``met_df`` daily with a column ``T_air`` over whole
+    calendar years (``ValueError`` otherwise, as in the reference).  Returns
+    ``met_df`` with a column ``PET`` (mm/day), replacing one that is there:
+    monthly PET from the monthly mean temperatures, the year's heat index and
+    the month's mean daylight hours, divided by the days of the month, placed
+    on the 16th and interpolated linearly in between (constant before the first
+    and after the last 16th).  The rule is stated once, in
+    ``simplyp_amd.forcing.thornthwaite_rows`` -- the same statement the device
+    kernel copies for ``forcing_error={'PET': {'model': 'thornthwaite'}}``.
+    """
+    from . import forcing
+    plan = forcing.thornthwaite_plan(met_df.index, latitude, max_years=None)
+    pet = forcing.thornthwaite_rows(met_df['T_air'].to_numpy(dtype=float)[None, :], plan)[0]
+    met_df = met_df.drop(columns=['PET']) if 'PET' in met_df.columns else met_df.copy()
+    met_df['PET'] = pet
+    return met_df

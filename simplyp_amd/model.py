@@ -953,6 +953,14 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     added.  ``'scale_groups'`` (``'offset_groups'`` of T_air) = ``'month_of_year'`` | int array [D] of ids in [0, G), G <= 4096:
     seasonal change factors -- ``scale`` / ``offset`` is then [G, E] or [G], one entry per shift group (12 calendar months:
     wetter winters, drier summers); the rows share one array of shift groups.
+    ``'PET': {'model': 'thornthwaite', 'latitude': 57.1, ...}`` (needs ``snow_in_kernel=True``): every member's PET is derived on
+    the device from that member's own final air temperature -- base + offset + error -- by Thornthwaite's 1948 rule as the
+    reference's ``daily_PET`` has it (``simplyp_amd.forcing.thornthwaite_rows``), so a warmer member also evaporates more; the
+    met data's PET column is not read, and ``sigma`` / ``groups`` / ``rho`` / ``scale`` / ``scale_groups`` of the PET entry
+    multiply the derived PET as they multiply the column otherwise.  The record must cover whole calendar years, at most 64
+    (``ValueError``, as for a latitude outside [-90, 90]); a year whose monthly mean temperatures are all <= 0 gives NaN, as in
+    the reference, and that member the non-finite status.  Not offered in ``run_simply_p_ensemble_windows`` and ``assimilate``
+    (``ValueError``): the daily interpolation crosses year boundaries.
 
     ``return_state=True``: the result gains ``'state'`` = dict(rows (``abi.STATE_ROWS``), reaches (all sub-catchments),
     data[S, 16, E], end = ``met_df.index[-1]``): the model state after the last day, in member order (numpy, or a device
@@ -1043,6 +1051,7 @@ def run_simply_p_ensemble_windows(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_
     if 'return_state' in kwargs:
         raise ValueError("run_simply_p_ensemble_windows always returns the state (on the device)")
     if kwargs.get('forcing_error') is not None:
+        forcing_rules.refuse_pet_model(kwargs['forcing_error'], 'run_simply_p_ensemble_windows')
         forcing_rules.cut_group_arrays(kwargs['forcing_error'], len(index), 0, len(index))
 
     def gen():
