@@ -7,7 +7,7 @@ the plotting functions of the reference's visualise_results.py are outside the s
 section 2, row 16): the names exist and raise NotImplementedError.
 """
 
-from . import helper_functions, inputs, marshal, abi, visualise_results, predictive, mcmc, neldermead, sobol, particle, score, pareto   # noqa: F401
+from . import helper_functions, inputs, marshal, abi, visualise_results, predictive, mcmc, neldermead, sobol, particle, score, pareto, residuals   # noqa: F401
 from .model import (f_x, discretized_soilP, ode_f, run_simply_p, run_simply_p_ensemble,   # noqa: F401
                     run_simply_p_ensemble_windows, derived_P_species, sum_to_waterbody)
 from .calibrate import sample_posterior, find_map, start_ball      # noqa: F401

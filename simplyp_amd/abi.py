@@ -196,6 +196,7 @@ WB_MASK_ALL = (1 << len(WB_COLUMNS)) - 1
 
 GOF_VARS = ['Q', 'SS', 'TDP', 'PP', 'TP', 'SRP']                                      # SIMPLYP_GOF_*
 GOF_STATS = ['N obs', 'NSE', 'log NSE', 'r2', 'Bias (%)', 'nRMSD (%)', 'sum_log_sim', 'sum_relsq']   # SIMPLYP_GOFSTAT_*
+LAG_STATS = ['n_link', 'sq_head', 'sq_tail', 'cross']                                 # SIMPLYP_LAGSTAT_* (simplyp_gof_lag)
 
 
 # Solver settings used when the caller does not choose: Cash-Karp 5(4) with per-thread step

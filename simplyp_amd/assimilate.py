@@ -142,14 +142,16 @@ def _window(dev, hs, s, c, t, d_lo, d_hi):
 def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, priors, variables=('Q',), error_m=None,
                n_particles=None, window=30, start=None, initial_state=None, seed=0, resample_threshold=1.0, rejuvenate='liu_west',
                delta=0.98, quantiles=None, forecast_series=None, record=False, state=None, step_len=1., solver=None, device=0,
-               out_reaches=None, forecast_weighted=False, score=False, forcing_error=None):
+               out_reaches=None, forecast_weighted=False, score=False, forcing_error=None, error_phi=None):
     """Update the parameter distribution and the model state of ``n_particles`` particles window by window as the observations
     of ``obs_dict`` arrive (sequential importance resampling), every step on the device.
 
     ``priors``, ``variables``, ``error_m``, ``out_reaches`` and their checks are ``sample_posterior``'s: names are member
     parameters, ``'f_TDP'`` and ``'m_<VAR>'`` -- which makes the error model's ``m`` a filtered dimension --, the box is
     ``lo <= x < hi``, and a selected variable needs more than 10 observations over the whole period at some output reach (a
-    single window needs none).  ``window``: as ``ensemble.window_bounds`` takes it (days per window, ``'annual'``, or start dates).
+    single window needs none).  The errors are independent from day to day: ``'phi_<VAR>'`` names and ``error_phi`` -- the AR(1)
+    error model of ``sample_posterior`` -- are a ``ValueError`` here, because a window's likelihood would need each particle's last
+    residual of the window before, carried through resampling.  ``window``: as ``ensemble.window_bounds`` takes it (days per window, ``'annual'``, or start dates).
     ``start``: None = uniform in the box (``particle.uniform_start``), or an array [n_dim, n_particles] inside it, for example
     ``sample_posterior(...)['state']['theta']``: the hand-over from calibration to operation.  ``initial_state``: as in
     ``run_simply_p_ensemble`` (None: the cold initial conditions).  ``seed``: the key of the counter-based random streams.
@@ -219,7 +221,10 @@ def assimilate(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, 
         except ValueError as exc:
             raise ValueError("assimilate: %s" % exc)
 
-    names, variables, lo, hi, target, m_dim, m_const = _plan(priors, variables, error_m, check_shape)
+    if error_phi or (isinstance(priors, dict) and any(str(nm).startswith('phi_') for nm in priors)):
+        raise ValueError("assimilate takes no lag-one coefficient ('phi_<VAR>' names, error_phi): the window likelihood has "
+                         "independent errors")
+    names, variables, lo, hi, target, m_dim, m_const, _ = _plan(priors, variables, error_m, check_shape)
     n_dim, E = len(names), int(E)
     seed = int(state['seed']) if state is not None else int(seed)
     if not 0 <= seed < 1 << 64:

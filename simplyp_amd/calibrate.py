@@ -17,9 +17,11 @@ from .priors import box as _box
 START_SERIES = 0x53544152        # "STAR": the counter's fourth word of the start ball's normals
 
 
-def _plan(priors, variables, error_m, check_shape):
+def _plan(priors, variables, error_m, check_shape, error_phi=None):
     """Names, box, targets and error-model wiring of a call; host only, raises ValueError.  ``check_shape(n_dim)`` is the
-    caller's own rule for how many points it moves."""
+    caller's own rule for how many points it moves.  The last item is None when no variable has a lag-one coefficient -- neither
+    a sampled ``'phi_<VAR>'`` nor one fixed through ``error_phi`` -- and (phi_dim, phi_const, the variables that have one)
+    otherwise, wired like (m_dim, m_const) with ``phi_const = 0`` (independent errors) for the variables that have none."""
     if not isinstance(priors, dict) or not priors:
         raise ValueError("priors must be a dict name -> (lo, hi) with at least one entry")
     names = list(priors)
@@ -31,7 +33,15 @@ def _plan(priors, variables, error_m, check_shape):
     unknown = [v for v in error_m if v not in variables]
     if unknown:
         raise ValueError("error_m names variables that are not selected: %s" % unknown)
+    error_phi = dict(error_phi or {})
+    unknown = [v for v in error_phi if v not in variables]
+    if unknown:
+        raise ValueError("error_phi names variables that are not selected: %s" % unknown)
+    for v, x in error_phi.items():
+        if not -1.0 < float(x) < 1.0:
+            raise ValueError("error_phi[%r] = %r is not inside (-1, 1)" % (v, x))
     target, m_dim, m_const = [], [-1] * len(abi.GOF_VARS), [float('nan')] * len(abi.GOF_VARS)
+    phi_dim, phi_const = [-1] * len(abi.GOF_VARS), [0.0] * len(abi.GOF_VARS)
     for d, nm in enumerate(names):
         if _priors.target_of(nm) is not None:
             target.append(_priors.target_of(nm))
@@ -40,18 +50,36 @@ def _plan(priors, variables, error_m, check_shape):
                 raise ValueError("%s is sampled and fixed through error_m at once" % nm)
             target.append(abi.MCMC_TARGET_NONE)
             m_dim[abi.GOF_VARS.index(nm[2:])] = d
+        elif nm.startswith('phi_') and nm[4:] in abi.GOF_VARS:
+            if nm[4:] not in variables:
+                raise ValueError("%s: variable %r is not selected (variables = %s)" % (nm, nm[4:], variables))
+            if nm[4:] in error_phi:
+                raise ValueError("%s is sampled and fixed through error_phi at once" % nm)
+            try:
+                plo, phi_hi = (float(x) for x in priors[nm])
+            except (TypeError, ValueError):
+                raise ValueError("priors[%r] must be (lo, hi)" % nm)
+            if not (-1.0 < plo and phi_hi < 1.0):
+                raise ValueError("the box of %s must lie inside (-1, 1): the AR(1) model is stationary for |phi| < 1 only (got %r)"
+                                 % (nm, (plo, phi_hi)))
+            target.append(abi.MCMC_TARGET_NONE)
+            phi_dim[abi.GOF_VARS.index(nm[4:])] = d
         else:
-            raise ValueError("unknown parameter %r: sampled names are %s, 'f_TDP' and 'm_<VAR>' for the selected variables %s"
-                             % (nm, marshal.PM_NAMES, variables))
+            raise ValueError("unknown parameter %r: sampled names are %s, 'f_TDP', and 'm_<VAR>' and 'phi_<VAR>' for the selected "
+                             "variables %s" % (nm, marshal.PM_NAMES, variables))
     for v in variables:
         vi = abi.GOF_VARS.index(v)
         if m_dim[vi] < 0:
             if v not in error_m:
                 raise ValueError("variable %r needs its error model: sample 'm_%s' or fix it through error_m={'%s': ...}" % (v, v, v))
             m_const[vi] = float(error_m[v])
+        if v in error_phi:
+            phi_const[vi] = float(error_phi[v])
     check_shape(len(names))
     lo, hi = _box(priors, names)
-    return names, variables, lo, hi, np.array(target, dtype=np.int32), m_dim, m_const
+    with_phi = [v for v in variables if v in error_phi or phi_dim[abi.GOF_VARS.index(v)] >= 0]
+    phi = (phi_dim, phi_const, with_phi) if with_phi else None
+    return names, variables, lo, hi, np.array(target, dtype=np.int32), m_dim, m_const, phi
 
 
 def _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables, lo, hi, out_reaches):
@@ -84,7 +112,7 @@ class _Evaluator:
     ``evaluate()`` is the model and the likelihood at the run points ``dev.mp_d`` / ``dev.ft_d`` hold: the log posterior in ``lpp_d``."""
 
     def __init__(self, order, hs, met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len, solver, device, n_members, n_dim,
-                 m_dim, m_const):
+                 m_dim, m_const, phi=None):
         self.dev = dev = _DeviceEnsemble(order, met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len, solver, device, n_members,
                                          marshal.FLUX_COLUMNS, hs['snow'])        # the columns simplyp_gof reads
         torch, f64 = dev.torch, dev.f64
@@ -93,16 +121,26 @@ class _Evaluator:
         self.gof_d = torch.empty((len(abi.GOF_STATS), len(abi.GOF_VARS), R, n_members), **f64)
         self.prop_d, self.lpp_d = torch.empty((n_dim, n_members), **f64), torch.empty((n_members,), **f64)
         self.inside_d = torch.ones((n_members,), dtype=torch.int32, device=dev.eng.tdev)
-        self.hs, self.m_dim, self.m_const = hs, m_dim, m_const
+        self.hs, self.m_dim, self.m_const, self.phi = hs, m_dim, m_const, phi
+        self.lag_ms = None                            # the last evaluation's lag-one pass; stays None without a phi
+        if phi is not None:
+            self.lag_d = torch.empty((len(abi.LAG_STATS), len(abi.GOF_VARS), R, n_members), **f64)
 
     def evaluate(self):
-        """Returns the kernel times of the run, the goodness of fit and the log posterior, in ms."""
+        """Returns the kernel times of the run, the goodness of fit and the log posterior, in ms.  With a lag-one coefficient
+        (``phi``) the lag-one sums are taken between the last two and the AR(1) log posterior replaces the independent one."""
         hs, dev, eng = self.hs, self.dev, self.dev.eng
         _, status_d, rstats = eng.run(dev.f_d, dev.doy_d, dev.mp_d, dev.rp_d, hs['up_ptr'], hs['up_idx'], dev.opts,
                                       out_reaches=hs['oreach'], out=self.out_d)
         _, ginfo = eng.gof(self.out_d, dev.mask, hs['obs'], dev.ft_d, dev.rp_d, out_reaches=hs['oreach'], gof=self.gof_d)
-        linfo = eng.mcmc_log_prob(self.gof_d, hs['pairs'], self.m_dim, self.m_const, self.prop_d, self.lpp_d, status=status_d,
-                                  inside=self.inside_d)
+        if self.phi is None:
+            linfo = eng.mcmc_log_prob(self.gof_d, hs['pairs'], self.m_dim, self.m_const, self.prop_d, self.lpp_d, status=status_d,
+                                      inside=self.inside_d)
+        else:
+            _, ainfo = eng.gof_lag(self.out_d, dev.mask, hs['obs'], dev.ft_d, dev.rp_d, out_reaches=hs['oreach'], lag=self.lag_d)
+            self.lag_ms = ainfo['kernel_ms']
+            linfo = eng.mcmc_log_prob_ar1(self.gof_d, self.lag_d, hs['pairs'], self.m_dim, self.m_const, self.phi[0], self.phi[1],
+                                          self.prop_d, self.lpp_d, status=status_d, inside=self.inside_d)
         return rstats['kernel_ms'], ginfo['kernel_ms'], linfo['kernel_ms']
 
 
@@ -115,6 +153,18 @@ def _shaped_for_the_ensemble(names, target, variables, m_dim, m_const, theta):
                (theta[m_dim[abi.GOF_VARS.index(v)]].copy() if m_dim[abi.GOF_VARS.index(v)] >= 0
                 else np.full(M, m_const[abi.GOF_VARS.index(v)])) for v in variables}
     return overrides, error_m
+
+
+def _shaped_phi(phi, theta):
+    """The lag-one coefficients at positions ``theta[n_dim, M]``, keyed like ``error_m``: one array [M] per variable that has a
+    ``phi``, sampled or fixed; {} without any."""
+    if phi is None:
+        return {}
+    phi_dim, phi_const, with_phi = phi
+    M = theta.shape[1]
+    at = lambda v: abi.GOF_VARS.index(v)
+    return {abi.TQ_DERIVED_SERIES[at(v)]: (theta[phi_dim[at(v)]].copy() if phi_dim[at(v)] >= 0 else np.full(M, phi_const[at(v)]))
+            for v in with_phi}
 
 
 def start_ball(centre, priors, n_walkers, seed=0):
@@ -144,7 +194,7 @@ def _check_inside(theta0, lo, hi, names):
 
 def sample_posterior(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, priors, variables=('Q',), error_m=None,
                      n_walkers=None, n_steps=0, start=None, seed=0, a=2.0, thin=1, state=None, record_proposals=False,
-                     step_len=1., solver=None, device=0, out_reaches=None):
+                     step_len=1., solver=None, device=0, out_reaches=None, error_phi=None):
     """Sample the posterior of model parameters with the affine-invariant stretch move (Goodman & Weare 2010; the reference's
     ``run_mcmc``), every half-step one ensemble run of ``n_walkers / 2`` members on the device.
 
@@ -152,7 +202,14 @@ def sample_posterior(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_
     parameters (``marshal.PM_NAMES``), ``'f_TDP'``, and ``'m_<VAR>'`` -- the ``m`` of the error model ``sigma = m * sim`` --
     for ``VAR`` in ``variables`` (names of ``abi.GOF_VARS``: the observed series the likelihood is taken over, at every
     output reach that has more than 10 observations of it).  A variable whose ``m`` is not sampled gets it through
-    ``error_m={'Q': 0.1}``.  ``n_walkers`` even and >= twice the number of names (at most 16); ``n_steps`` steps;
+    ``error_m={'Q': 0.1}``.  ``'phi_<VAR>'`` samples the lag-one coefficient of an AR(1) error model for ``VAR``
+    (``simplyp_amd.residuals``: the standardised residuals are autocorrelated along runs of consecutive observation days and
+    independent across gaps; the box must lie inside (-1, 1) and the start is its centre), ``error_phi={'Q': 0.6}`` fixes it, and
+    a variable with neither has independent errors.  With any ``phi`` an evaluation is ``Engine.gof`` -> ``Engine.gof_lag`` ->
+    ``mcmc_log_prob_ar1``, ``stats`` gains ``lag_ms`` and the result's ``error_phi`` holds the last positions' coefficients,
+    keyed like ``error_m``; with none the call does exactly what it did without the option.  Per-day predictive bands do not
+    depend on ``phi`` (the per-day marginal of the standardised residual stays N(0, 1)), so ``predictive_series=`` takes no
+    ``phi``.  ``n_walkers`` even and >= twice the number of names (at most 16); ``n_steps`` steps;
     ``a`` the stretch scale; ``seed`` the key of the counter-based random stream (``simplyp_amd.mcmc``); every ``thin``-th
     step is kept.  ``start``: None = the notebook's ball -- the workbook's values (box centres for the ``m``) plus
     ``1e-4 (hi - lo) z`` with ``z = predictive.standard_normal(seed, walker, dimension, 0, START_SERIES)``: ``start_ball`` -- or an array
@@ -182,7 +239,7 @@ def sample_posterior(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_
         except ValueError as exc:
             raise ValueError("sample_posterior: %s" % exc)
 
-    names, variables, lo, hi, target, m_dim, m_const = _plan(priors, variables, error_m, check_shape)
+    names, variables, lo, hi, target, m_dim, m_const, phi = _plan(priors, variables, error_m, check_shape, error_phi)
     n_dim, W = len(names), int(n_walkers)
     h = W // 2
     if not float(a) > 1.0:
@@ -214,7 +271,7 @@ def sample_posterior(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_
 
         # ---- the device: everything is marshalled and uploaded once, for an ensemble of h members
         ev = _Evaluator("sample_posterior keeps members in walker order", hs, met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len,
-                        solver, device, h, n_dim, m_dim, m_const)
+                        solver, device, h, n_dim, m_dim, m_const, phi)
         dev, prop_d, lpp_d, inside_d, evaluate = ev.dev, ev.prop_d, ev.lpp_d, ev.inside_d, ev.evaluate
         eng, torch, f64, mp_d, ft_d = dev.eng, dev.torch, dev.f64, dev.mp_d, dev.ft_d
         theta_d = eng.to_device(theta0, torch.float64)
@@ -225,6 +282,8 @@ def sample_posterior(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_
             props_d, plp_d = torch.empty((n_steps, n_dim, W), **f64), torch.empty((n_steps, W), **f64)
         stats = dict(wall_ms=[], run_kernel_ms=[], gof_ms=[], sampler_ms=[], n_inside=[], n_accepted=[],
                      start_wall_ms=[], start_run_kernel_ms=[])
+        if phi is not None:
+            stats['lag_ms'] = []
 
         if lp0 is None:                               # the start's log posterior: one evaluation per half, through the same kernels
             lp_d = torch.empty((W,), **f64)
@@ -258,6 +317,8 @@ def sample_posterior(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_
                 stats['wall_ms'].append(1e3 * (time.perf_counter() - w0))
                 stats['run_kernel_ms'].append(run_ms)
                 stats['gof_ms'].append(gof_ms)
+                if phi is not None:
+                    stats['lag_ms'].append(ev.lag_ms)
                 stats['sampler_ms'].append(pinfo['kernel_ms'] + lp_ms + ainfo['kernel_ms'])
                 stats['n_inside'].append(pinfo['n_inside'])
                 stats['n_accepted'].append(ainfo['n_accepted'])
@@ -271,7 +332,7 @@ def sample_posterior(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_
     overrides, err_m = _shaped_for_the_ensemble(names, target, variables, m_dim, m_const, theta)
     res = dict(names=names, chain=np.ascontiguousarray(chain[:, :n_dim]), log_prob=np.ascontiguousarray(chain[:, n_dim]),
                acceptance_fraction=n_accept / float(t_end) if t_end else np.zeros(W), n_steps=n_steps, seed=seed,
-               overrides=overrides, error_m=err_m,
+               overrides=overrides, error_m=err_m, error_phi=_shaped_phi(phi, theta),
                state=dict(theta=theta, lp=lp, n_accept=n_accept, t=t_end), start=dict(theta=theta0, lp=lp_start, t=t0), stats=stats)
     if record_proposals:
         res['proposals'], res['proposal_log_prob'] = props_d.cpu().numpy(), plp_d.cpu().numpy()
@@ -280,12 +341,12 @@ def sample_posterior(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_
 
 def find_map(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, priors, variables=('Q',), error_m=None,
              init_guess=None, n_starts=64, max_iter=None, xatol=1e-4, fatol=1e-4, seed=0, state=None, record_evaluations=False,
-             step_len=1., solver=None, device=0, out_reaches=None):
+             step_len=1., solver=None, device=0, out_reaches=None, error_phi=None):
     """Find the mode of the posterior (the reference's ``find_map``: ``scipy.optimize.fmin`` on the negative log posterior) with
     ``n_starts`` Nelder-Mead simplexes at once, every run one ensemble of ``4 n_starts`` members on the device.
 
-    ``priors``, ``variables``, ``error_m``, ``out_reaches`` and the checks are ``sample_posterior``'s: the names are member
-    parameters, ``'f_TDP'`` and ``'m_<VAR>'``; the box is ``lo <= x < hi``, outside of which the target is +inf and the model is
+    ``priors``, ``variables``, ``error_m``, ``error_phi``, ``out_reaches`` and the checks are ``sample_posterior``'s: the names are
+    member parameters, ``'f_TDP'``, ``'m_<VAR>'`` and ``'phi_<VAR>'``; the box is ``lo <= x < hi``, outside of which the target is +inf and the model is
     never run.  The algorithm is scipy's, its coefficients, decisions and termination (``xatol``, ``fatol``; ``max_iter`` counts
     like scipy's ``maxiter`` and defaults to its ``200 n_dim``), with an iteration's four candidates evaluated together
     (``simplyp_amd.neldermead``).  ``init_guess``: an array [n_dim, n_starts] inside the box, or None: simplex 0 starts at the
@@ -317,7 +378,7 @@ def find_map(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, pr
         if S < 1 or 4 * S < n_dim:
             raise ValueError("find_map: n_starts must be >= 1 and 4 n_starts >= n_dim (got %d starts, n_dim = %d)" % (S, n_dim))
 
-    names, variables, lo, hi, target, m_dim, m_const = _plan(priors, variables, error_m, check_shape)
+    names, variables, lo, hi, target, m_dim, m_const, phi = _plan(priors, variables, error_m, check_shape, error_phi)
     n_dim = len(names)
     seed = int(seed)
     max_iter = 200 * n_dim if max_iter is None else int(max_iter)
@@ -348,12 +409,14 @@ def find_map(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, pr
 
         # ---- the device: everything is marshalled and uploaded once, for an ensemble of 4 S members
         ev = _Evaluator("find_map keeps members in slot order", hs, met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len, solver,
-                        device, neldermead.SLOTS * S, n_dim, m_dim, m_const)
+                        device, neldermead.SLOTS * S, n_dim, m_dim, m_const, phi)
         eng, torch = ev.dev.eng, ev.dev.torch
         sim_d, fsim_d = eng.to_device(st['sim'], torch.float64), eng.to_device(st['fsim'], torch.float64)
         ist_d = eng.to_device(neldermead.pack_istate(st), torch.int32)
         hist_d = eng.to_device(hist, torch.float64)
         stats = dict(wall_ms=[], run_kernel_ms=[], gof_ms=[], optimiser_ms=[], n_active=[], n_shrinking=[])
+        if phi is not None:
+            stats['lag_ms'] = []
         evals, evals_lp = [], []
         n_active = int((st['phase'] != neldermead.DONE).sum())
         while n_active:
@@ -365,6 +428,8 @@ def find_map(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, pr
             stats['wall_ms'].append(1e3 * (time.perf_counter() - w0))
             stats['run_kernel_ms'].append(run_ms)
             stats['gof_ms'].append(gof_ms)
+            if phi is not None:
+                stats['lag_ms'].append(ev.lag_ms)
             stats['optimiser_ms'].append(pinfo['kernel_ms'] + lp_ms + uinfo['kernel_ms'])
             stats['n_active'].append(pinfo['n_active'])
             stats['n_shrinking'].append(pinfo['n_shrinking'])
@@ -384,7 +449,7 @@ def find_map(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, pr
     best = int(np.argmin(fun))
     overrides, err_m = _shaped_for_the_ensemble(names, target, variables, m_dim, m_const, x[:, best:best + 1])
     res = dict(names=names, x=x, fun=fun, best=best, map={nm: float(x[d, best]) for d, nm in enumerate(names)},
-               overrides=overrides, error_m=err_m, n_iter=st['n_iter'].copy(), status=st['status'].copy(), history=hist,
+               overrides=overrides, error_m=err_m, error_phi=_shaped_phi(phi, x[:, best:best + 1]), n_iter=st['n_iter'].copy(), status=st['status'].copy(), history=hist,
                final_simplex=(st['sim'], st['fsim']), moves={m: st['counts'][i].copy() for i, m in enumerate(neldermead.MOVES)},
                state=dict(st, history=hist), start=begin, stats=stats)
     if record_evaluations:

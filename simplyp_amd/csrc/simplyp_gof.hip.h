@@ -56,17 +56,23 @@ struct GofAcc {
 // One (obs, sim) pair of one variable.  o, lo: observation and its log; lop, w: the log less its shift and 1, or 0 and 0 when
 // the observation has no log (all four wave-uniform, made by the host); s: simulated value (per lane); co: shift.  A NaN
 // simulated value drops the pair (pandas dropna, visualise_results.py:436); +-inf stays.
+// The relative residual obs / sim - 1 of one pair and ln sim (`ls`): the one place both are formed, for the sums here and the
+// lag-one sums of simplyp_gof_lag.hip.h alike.
+__device__ __forceinline__ double gof_rel(double o, double s, double& ls)
+{
+    if (s > 1e-290 && s < 1e290) {          // every ordinary value: own log / reciprocal (~1 ulp, a third of libm's cost)
+        ls = sp_log(s);
+        return o * sp_rcp(s) - 1.0;
+    }
+    ls = log(s);                            // 0, negative, infinite: IEEE results as numpy gives them (-inf, nan, ...)
+    return o / s - 1.0;
+}
+
 __device__ __forceinline__ void gof_add(GofAcc& A, double o, double lo, double lop, double w, double s, double co)
 {
     if (s != s) return;
-    double ls, q;
-    if (s > 1e-290 && s < 1e290) {          // every ordinary value: own log / reciprocal (~1 ulp, a third of libm's cost)
-        ls = sp_log(s);
-        q = o * sp_rcp(s) - 1.0;
-    } else {                                // 0, negative, infinite: IEEE results as numpy gives them (-inf, nan, ...)
-        ls = log(s);
-        q = o / s - 1.0;
-    }
+    double ls;
+    const double q = gof_rel(o, s, ls);
     const double op = o - co, sp = s - co;
     const double d = o - s, dl = lo - ls;
     A.a[0] += 1.0;
@@ -87,17 +93,31 @@ __device__ __forceinline__ void gof_add(GofAcc& A, double o, double lo, double l
 
 // One chemistry day: the five simulated concentrations and their pairs.  ob: the day's row of c_obs (wave-uniform, NaN = none);
 // sh: the reach's 12 shifts.
-__device__ __forceinline__ void gof_chem_day(GofAcc (&acc)[GOF_NV], const double* ob, const double* sh, double qr, double ms,
-                                             double td, double pp, double A, double f_tdp)
+// The five simulated concentrations of one day from its Qr and flux rows.
+__device__ __forceinline__ void gof_chem_sim(double qr, double ms, double td, double pp, double A, double f_tdp,
+                                             double& SS, double& TDP, double& PP, double& TP, double& SRP)
 {
-    double SS, TDP, PP;
     if (qr > 1e-290 && qr < 1e290) {          // (flux/Qr)/A with one reciprocal (2 ulp); literal divisions otherwise
         const double inv = sp_rcp(qr * A);
         SS = ms * inv; TDP = td * inv; PP = pp * inv;
     } else {
         SS = (ms / qr) / A; TDP = (td / qr) / A; PP = (pp / qr) / A;
     }
-    const double TP = TDP + PP, SRP = TDP * f_tdp;
+    TP = TDP + PP; SRP = TDP * f_tdp;
+}
+
+// What a Qr value is multiplied by to give the discharge: Q = Qr*A*1000/86400 (model.py:784) with the constants folded (2 ulp);
+// a waterbody series holds the discharge itself.
+__device__ __forceinline__ double gof_q_scale(bool reach_table, double A)
+{
+    return reach_table ? A * 1000 / 86400 : 1.0;
+}
+
+__device__ __forceinline__ void gof_chem_day(GofAcc (&acc)[GOF_NV], const double* ob, const double* sh, double qr, double ms,
+                                             double td, double pp, double A, double f_tdp)
+{
+    double SS, TDP, PP, TP, SRP;
+    gof_chem_sim(qr, ms, td, pp, A, f_tdp, SS, TDP, PP, TP, SRP);
     if (ob[0] == ob[0]) gof_add(acc[SIMPLYP_GOF_SS], ob[0], ob[5], ob[10], ob[15], SS, sh[1]);
     if (ob[1] == ob[1]) gof_add(acc[SIMPLYP_GOF_TDP], ob[1], ob[6], ob[11], ob[16], TDP, sh[2]);
     if (ob[2] == ob[2]) gof_add(acc[SIMPLYP_GOF_PP], ob[2], ob[7], ob[12], ob[17], PP, sh[3]);
@@ -130,7 +150,7 @@ __global__ __launch_bounds__(64) void simplyp_gof_partial_kernel(const GofArgs g
         const long long k0 = g.q_ptr[r], n = g.q_ptr[r + 1] - k0;
         const int kb = (int)(k0 + n * chunk / g.n_chunks_q), ke = (int)(k0 + n * (chunk + 1) / g.n_chunks_q);
         const double co = sh[0];
-        const double q_scale = g.a_catch ? A * 1000 / 86400 : 1.0;      // Q = Qr*A*1000/86400 (model.py:784) with the constants folded: 2 ulp
+        const double q_scale = gof_q_scale(g.a_catch != nullptr, A);
         // batches of GOF_BATCH_Q days: all row loads are issued before the first is consumed (one wave keeps 8 x 512 B
         // in flight; a load-use pair per iteration leaves HBM waiting on latency)
         int k = kb;

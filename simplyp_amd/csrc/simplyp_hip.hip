@@ -20,6 +20,7 @@
 
 #include "simplyp_kernels.hip.h"
 #include "simplyp_gof.hip.h"
+#include "simplyp_gof_lag.hip.h"
 #include "simplyp_waterbody.hip.h"
 #include "simplyp_quantile.hip.h"
 #include "simplyp_order.hip.h"
@@ -1656,25 +1657,29 @@ static int check_table(const Entry& e, const simplyp_dims* dims, uint32_t out_ma
     return SIMPLYP_OK;
 }
 
-static int gof_impl(const Entry& e, const simplyp_dims* dims, uint32_t out_mask,
-                    const int32_t* out_reaches, int32_t n_out_reaches,
-                    const double* out, const int32_t* member_of_slot,
-                    const double* f_tdp, const double* reach_params,
-                    const double* obs, double* gof, simplyp_gof_info* info, bool waterbody = false)
-{
-    simplyp_ctx* const ctx = e.ctx;
-    TableView t;
-    const bool ptrs_ok = out && f_tdp && (waterbody || reach_params) && obs && gof;
-    if (int rc = check_table(e, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, waterbody, t)) return rc;
-    const int E = t.E, S = t.S, D = t.D, R = t.R;
-    if (info) *info = {};
+// The observation side of simplyp_gof and simplyp_gof_lag, shared by all members: counts, conditioning shifts, and per output
+// reach the compact lists of discharge days and of chemistry days, each entry with whether it is the day after the entry before it.
+struct ObsLists {
+    std::vector<double> n_obs, shift;              // [R][6], [R][12]
+    std::vector<int32_t> q_ptr, c_ptr, q_day, c_day, q_succ, c_succ;
+    std::vector<double> q_obs, c_obs;              // [Kq][4], [Kc][20]: GofArgs
+};
 
-    // Observation side, shared by all members: counts, conditioning shifts, compact day lists.
+static void obs_lists(const double* obs, int R, int D, ObsLists& L)
+{
     constexpr int NV = SIMPLYP_N_GOF_VARS;
-    std::vector<double> n_obs((size_t)R * NV, 0.0), shift((size_t)R * 12, 0.0);
-    std::vector<int32_t> q_ptr(R + 1, 0), c_ptr(R + 1, 0), q_day, c_day;
-    std::vector<double> q_obs, c_obs;
+    L.n_obs.assign((size_t)R * NV, 0.0);
+    L.shift.assign((size_t)R * 12, 0.0);
+    L.q_ptr.assign(R + 1, 0);
+    L.c_ptr.assign(R + 1, 0);
+    std::vector<double>&n_obs = L.n_obs, &shift = L.shift, &q_obs = L.q_obs, &c_obs = L.c_obs;
+    std::vector<int32_t>&q_ptr = L.q_ptr, &c_ptr = L.c_ptr, &q_day = L.q_day, &c_day = L.c_day;
     const double nan = std::nan("");
+    // the first entry of a reach's list is nobody's successor: the list before it is another reach's
+    auto push_day = [](std::vector<int32_t>& day, std::vector<int32_t>& succ, size_t first, int d) {
+        succ.push_back(day.size() > first && day.back() == d - 1 ? 1 : 0);
+        day.push_back(d);
+    };
     for (int r = 0; r < R; ++r) {
         const double* ob = obs + (size_t)r * NV * D;
         bool use[NV];
@@ -1704,7 +1709,12 @@ static int gof_impl(const Entry& e, const simplyp_dims* dims, uint32_t out_mask,
         };
         for (int d = 0; d < D; ++d) {
             const double q = ob[d];
-            if (use[0] && q == q) { double row[4]; put_obs(q, 0, row, 1); q_day.push_back(d); q_obs.insert(q_obs.end(), row, row + 4); }
+            if (use[0] && q == q) {
+                double row[4];
+                put_obs(q, 0, row, 1);
+                push_day(q_day, L.q_succ, (size_t)q_ptr[r], d);
+                q_obs.insert(q_obs.end(), row, row + 4);
+            }
             bool any = false;
             double row[20];
             for (int v = 1; v < NV; ++v) {
@@ -1714,16 +1724,37 @@ static int gof_impl(const Entry& e, const simplyp_dims* dims, uint32_t out_mask,
                 else for (int j = 0; j < 4; ++j) row[v - 1 + 5 * j] = nan;
                 any = any || have;
             }
-            if (any) { c_day.push_back(d); c_obs.insert(c_obs.end(), row, row + 20); }
+            if (any) { push_day(c_day, L.c_succ, (size_t)c_ptr[r], d); c_obs.insert(c_obs.end(), row, row + 20); }
         }
         q_ptr[r + 1] = (int32_t)q_day.size();
         c_ptr[r + 1] = (int32_t)c_day.size();
     }
+}
 
+// What simplyp_gof and simplyp_gof_lag set up alike once the table has passed: the lists on the device, the slices per day list,
+// the partial-sum workspace for `nacc` running sums per variable, and the kernels' common arguments.  `partial_q` / `partial_c`:
+// the entry's own discharge and chemistry kernels, whose occupancy the slice rule reads.
+struct GofSetup {
+    ObsLists L;
     simplyp::GofArgs g{};
+    const int32_t* d_q_succ = nullptr;
+    const int32_t* d_c_succ = nullptr;
+    int groups = 0;
+};
+
+static int gof_setup(const Entry& e, const TableView& t, const double* out, const int32_t* member_of_slot, const double* f_tdp,
+                     const double* reach_params, const double* obs, bool waterbody, int nacc, const void* partial_q,
+                     const void* partial_c, GofSetup& u)
+{
+    simplyp_ctx* const ctx = e.ctx;
+    constexpr int NV = SIMPLYP_N_GOF_VARS;
+    const int E = t.E, S = t.S, D = t.D, R = t.R;
+    obs_lists(obs, R, D, u.L);
+    ObsLists& L = u.L;
+    simplyp::GofArgs& g = u.g;
     std::copy(t.col, t.col + 4, g.col);
 
-    const int groups = (int)blocks(E, simplyp::WAVE);
+    const int groups = u.groups = (int)blocks(E, simplyp::WAVE);
     // Slices per day list. All waves of a launch take the same time, so what matters is how many rounds the chip needs:
     // pick the slice count with the fewest (rounds / slices), the smallest one within 3 % of the best (every slice costs a
     // row of partial sums), and keep at least 32 days per slice.
@@ -1743,16 +1774,17 @@ static int gof_impl(const Entry& e, const simplyp_dims* dims, uint32_t out_mask,
         }
         return best;
     };
-    const int n_chunks_q = pick_chunks((const void*)simplyp::simplyp_gof_partial_kernel<0>, q_day.size());
-    const int n_chunks_c = pick_chunks((const void*)simplyp::simplyp_gof_partial_kernel<1>, c_day.size());
+    const int n_chunks_q = pick_chunks(partial_q, L.q_day.size());
+    const int n_chunks_c = pick_chunks(partial_c, L.c_day.size());
     const int n_chunks = std::max(n_chunks_q, n_chunks_c);
 
     // one upload: int32 block then double block
     Staging up;
-    const size_t o_reach = up.put(t.reach_of), o_qp = up.put(q_ptr), o_cp = up.put(c_ptr), o_qd = up.put(q_day), o_cd = up.put(c_day);
-    const size_t o_qo = up.put(q_obs), o_co = up.put(c_obs), o_sh = up.put(shift), o_n = up.put(n_obs);
+    const size_t o_reach = up.put(t.reach_of), o_qp = up.put(L.q_ptr), o_cp = up.put(L.c_ptr), o_qd = up.put(L.q_day), o_cd = up.put(L.c_day);
+    const size_t o_qs = up.put(L.q_succ), o_cs = up.put(L.c_succ);
+    const size_t o_qo = up.put(L.q_obs), o_co = up.put(L.c_obs), o_sh = up.put(L.shift), o_n = up.put(L.n_obs);
     if (int rc = ensure(ctx, ctx->gof_lists, up.bytes())) return rc;
-    const size_t pbytes = (size_t)n_chunks * R * (NV * simplyp::GOF_NACC) * E * sizeof(double);
+    const size_t pbytes = (size_t)n_chunks * R * (NV * nacc) * E * sizeof(double);
     if (int rc = ensure(ctx, ctx->gof_partial, pbytes)) return rc;
     if (int rc = up.upload(e, ctx->gof_lists.ptr)) return rc;
     const int32_t* di = up.d_ints;
@@ -1764,27 +1796,99 @@ static int gof_impl(const Entry& e, const simplyp_dims* dims, uint32_t out_mask,
     g.f_tdp = f_tdp;
     g.a_catch = waterbody ? nullptr : reach_params + (size_t)SIMPLYP_PR_A_CATCH * S * E;
     g.reach_of = di + o_reach; g.q_ptr = di + o_qp; g.c_ptr = di + o_cp; g.q_day = di + o_qd; g.c_day = di + o_cd;
+    u.d_q_succ = di + o_qs; u.d_c_succ = di + o_cs;
     g.q_obs = dd + o_qo; g.c_obs = dd + o_co; g.shift = dd + o_sh; g.n_obs = dd + o_n;
     g.n_chunks_q = n_chunks_q;
     g.n_chunks_c = n_chunks_c;
     g.partial = (double*)ctx->gof_partial.ptr;
+    return SIMPLYP_OK;
+}
+
+static void gof_info(const GofSetup& u, int E, simplyp_gof_info* info)
+{
+    info->n_q_days = (int32_t)u.L.q_day.size();
+    info->n_chem_days = (int32_t)u.L.c_day.size();
+    info->bytes_read = ((int64_t)u.L.q_day.size() * 8 + (int64_t)u.L.c_day.size() * 32) * E;
+    info->n_chunks_q = u.g.n_chunks_q;
+    info->n_chunks_chem = u.g.n_chunks_c;
+}
+
+static int gof_impl(const Entry& e, const simplyp_dims* dims, uint32_t out_mask,
+                    const int32_t* out_reaches, int32_t n_out_reaches,
+                    const double* out, const int32_t* member_of_slot,
+                    const double* f_tdp, const double* reach_params,
+                    const double* obs, double* gof, simplyp_gof_info* info, bool waterbody = false)
+{
+    simplyp_ctx* const ctx = e.ctx;
+    TableView t;
+    const bool ptrs_ok = out && f_tdp && (waterbody || reach_params) && obs && gof;
+    if (int rc = check_table(e, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, waterbody, t)) return rc;
+    if (info) *info = {};
+    constexpr int NV = SIMPLYP_N_GOF_VARS;
+    GofSetup u;
+    if (int rc = gof_setup(e, t, out, member_of_slot, f_tdp, reach_params, obs, waterbody, simplyp::GOF_NACC,
+                           (const void*)simplyp::simplyp_gof_partial_kernel<0>, (const void*)simplyp::simplyp_gof_partial_kernel<1>, u))
+        return rc;
+    simplyp::GofArgs& g = u.g;
     g.gof = gof;
+    const int groups = u.groups, R = t.R;
 
     if (int rc = e.begin()) return rc;
-    hipLaunchKernelGGL(simplyp::simplyp_gof_partial_kernel<0>, dim3(groups, n_chunks_q, R), dim3(simplyp::WAVE), 0, ctx->stream, g);
+    hipLaunchKernelGGL(simplyp::simplyp_gof_partial_kernel<0>, dim3(groups, g.n_chunks_q, R), dim3(simplyp::WAVE), 0, ctx->stream, g);
     HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(simplyp::simplyp_gof_partial_kernel<1>, dim3(groups, n_chunks_c, R), dim3(simplyp::WAVE), 0, ctx->stream, g);
+    hipLaunchKernelGGL(simplyp::simplyp_gof_partial_kernel<1>, dim3(groups, g.n_chunks_c, R), dim3(simplyp::WAVE), 0, ctx->stream, g);
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(simplyp::simplyp_gof_finish_kernel, dim3(groups, R, NV), dim3(simplyp::WAVE), 0, ctx->stream, g);
     if (int rc = e.end(info ? &info->kernel_ms : nullptr)) return rc;
-    if (info) {
-        info->n_q_days = (int32_t)q_day.size();
-        info->n_chem_days = (int32_t)c_day.size();
-        info->bytes_read = ((int64_t)q_day.size() * 8 + (int64_t)c_day.size() * 32) * E;
-        info->n_chunks_q = n_chunks_q;
-        info->n_chunks_chem = n_chunks_c;
-    }
+    if (info) gof_info(u, t.E, info);
     return SIMPLYP_OK;
+}
+
+// The lag-one sums (simplyp_gof_lag.hip.h): simplyp_gof's setup with four running sums per variable and its own kernels.
+int simplyp_gof_lag(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
+                    const int32_t* out_reaches, int32_t n_out_reaches,
+                    const double* out, const int32_t* member_of_slot,
+                    const double* f_tdp, const double* reach_params,
+                    const double* obs, double* lag, simplyp_gof_info* info)
+{
+    return entry(ctx, "simplyp_gof_lag", [&](const Entry& e) -> int {
+        TableView t;
+        const bool ptrs_ok = out && f_tdp && reach_params && obs && lag;
+        if (int rc = check_table(e, dims, out_mask, out_reaches, n_out_reaches, ptrs_ok, false, t)) return rc;
+        if (info) *info = {};
+        constexpr int NV = SIMPLYP_N_GOF_VARS;
+        GofSetup u;
+        if (int rc = gof_setup(e, t, out, member_of_slot, f_tdp, reach_params, obs, false, simplyp::LAG_NACC,
+                               (const void*)simplyp::simplyp_gof_lag_partial_kernel<0>,
+                               (const void*)simplyp::simplyp_gof_lag_partial_kernel<1>, u))
+            return rc;
+        simplyp::GofLagArgs a{};
+        a.g = u.g; a.q_succ = u.d_q_succ; a.c_succ = u.d_c_succ; a.lag = lag;
+        const int groups = u.groups, R = t.R;
+        if (int rc = e.begin()) return rc;
+        hipLaunchKernelGGL(simplyp::simplyp_gof_lag_partial_kernel<0>, dim3(groups, a.g.n_chunks_q, R), dim3(simplyp::WAVE), 0, ctx->stream, a);
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(simplyp::simplyp_gof_lag_partial_kernel<1>, dim3(groups, a.g.n_chunks_c, R), dim3(simplyp::WAVE), 0, ctx->stream, a);
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(simplyp::simplyp_gof_lag_finish_kernel, dim3(groups, R, NV), dim3(simplyp::WAVE), 0, ctx->stream, a);
+        if (int rc = e.end(info ? &info->kernel_ms : nullptr)) return rc;
+        if (info) {
+            gof_info(u, t.E, info);
+            // the rows a slice re-reads: its first entry continues a segment (the kernels' slice bounds)
+            auto rereads = [&](const std::vector<int32_t>& ptr, const std::vector<int32_t>& succ, int n_chunks) {
+                int64_t n = 0;
+                for (int r = 0; r < R; ++r)
+                    for (int c = 0; c < n_chunks; ++c) {
+                        const long long k0 = ptr[r], len = ptr[r + 1] - k0;
+                        const long long kb = k0 + len * c / n_chunks, ke = k0 + len * (c + 1) / n_chunks;
+                        if (kb < ke && succ[(size_t)kb]) ++n;
+                    }
+                return n;
+            };
+            info->bytes_read += (rereads(u.L.q_ptr, u.L.q_succ, a.g.n_chunks_q) * 8 + rereads(u.L.c_ptr, u.L.c_succ, a.g.n_chunks_c) * 32) * t.E;
+        }
+        return SIMPLYP_OK;
+    });
 }
 
 int simplyp_gof(simplyp_ctx* ctx, const simplyp_dims* dims, uint32_t out_mask,
@@ -2681,29 +2785,74 @@ int simplyp_mcmc_propose(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t hal
     });
 }
 
+// What the two log-probability entries check alike (`ptrs_ok`, `ptr_names`: the caller's required pointers); fills the
+// kernel's arguments but its counters.
+static int mcmc_log_prob_args(const Entry& e, int32_t W, int32_t n_dim, int32_t n_out_reaches, bool ptrs_ok, const char* ptr_names,
+                              const double* gof, const int32_t* status, const int32_t* inside, const int32_t* pair_var,
+                              const int32_t* pair_reach, int32_t n_pairs, const int32_t* m_dim, const double* m_const,
+                              const double* prop, double* lp_prop, simplyp::McmcLogProbArgs& g)
+{
+    simplyp_ctx* const ctx = e.ctx;
+    simplyp::McmcMove mv{};
+    if (int rc = mcmc_move(e, W, n_dim, 0, 2.0, 0, 0, mv)) return rc;
+    if (!ptrs_ok) return e.refuse("%s must not be NULL", ptr_names);
+    if (n_out_reaches < 1) return e.refuse("n_out_reaches must be >= 1 (got %d)", (int)n_out_reaches);
+    TABLE_TRY(ctx, st::check_pairs(e.me, pair_var, pair_reach, n_pairs, simplyp::MCMC_MAX_PAIRS, n_out_reaches, g.pair_var, g.pair_reach, msg));
+    for (int v = 0; v < SIMPLYP_N_GOF_VARS; ++v) {
+        if (m_dim[v] < -1 || m_dim[v] >= n_dim)
+            return e.refuse("m_dim[%d] = %d is neither -1 nor a row of prop", v, (int)m_dim[v]);
+        g.m_dim[v] = m_dim[v]; g.m_const[v] = m_const[v];
+    }
+    g.h = mv.h; g.R = n_out_reaches; g.n_pairs = n_pairs;
+    g.gof = gof; g.status = status; g.inside = inside; g.prop = prop; g.lp_prop = lp_prop;
+    return SIMPLYP_OK;
+}
+
 int simplyp_mcmc_log_prob(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t n_out_reaches, const double* gof,
                           const int32_t* status, const int32_t* inside, const int32_t* pair_var, const int32_t* pair_reach,
                           int32_t n_pairs, const int32_t* m_dim, const double* m_const, const double* prop, double* lp_prop,
                           simplyp_mcmc_info* info)
 {
     return entry(ctx, "simplyp_mcmc_log_prob", [&](const Entry& e) -> int {
-        simplyp::McmcMove mv{};
-        if (int rc = mcmc_move(e, W, n_dim, 0, 2.0, 0, 0, mv)) return rc;
-        if (!gof || !pair_var || !pair_reach || !m_dim || !m_const || !prop || !lp_prop)
-            return e.refuse("gof, pair_var, pair_reach, m_dim, m_const, prop and lp_prop must not be NULL");
-        if (n_out_reaches < 1) return e.refuse("n_out_reaches must be >= 1 (got %d)", (int)n_out_reaches);
         simplyp::McmcLogProbArgs g{};
-        TABLE_TRY(ctx, st::check_pairs(e.me, pair_var, pair_reach, n_pairs, simplyp::MCMC_MAX_PAIRS, n_out_reaches, g.pair_var, g.pair_reach, msg));
-        for (int v = 0; v < SIMPLYP_N_GOF_VARS; ++v) {
-            if (m_dim[v] < -1 || m_dim[v] >= n_dim)
-                return e.refuse("m_dim[%d] = %d is neither -1 nor a row of prop", v, (int)m_dim[v]);
-            g.m_dim[v] = m_dim[v]; g.m_const[v] = m_const[v];
-        }
-        g.h = mv.h; g.R = n_out_reaches; g.n_pairs = n_pairs;
-        g.gof = gof; g.status = status; g.inside = inside; g.prop = prop; g.lp_prop = lp_prop;
+        if (int rc = mcmc_log_prob_args(e, W, n_dim, n_out_reaches, gof && pair_var && pair_reach && m_dim && m_const && prop && lp_prop,
+                                        "gof, pair_var, pair_reach, m_dim, m_const, prop and lp_prop", gof, status, inside, pair_var,
+                                        pair_reach, n_pairs, m_dim, m_const, prop, lp_prop, g))
+            return rc;
         if (int rc = mcmc_begin(e, info, g.counters)) return rc;
         hipLaunchKernelGGL(simplyp::simplyp_mcmc_log_prob_kernel, dim3(blocks(g.h, simplyp::MCMC_THREADS)),
                            dim3(simplyp::MCMC_THREADS), 0, ctx->stream, g);
+        return mcmc_end(e, info);
+    });
+}
+
+int simplyp_mcmc_log_prob_ar1(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t n_out_reaches, const double* gof,
+                              const double* lag, const int32_t* status, const int32_t* inside, const int32_t* pair_var,
+                              const int32_t* pair_reach, int32_t n_pairs, const int32_t* m_dim, const double* m_const,
+                              const int32_t* phi_dim, const double* phi_const, const double* prop, double* lp_prop,
+                              simplyp_mcmc_info* info)
+{
+    return entry(ctx, "simplyp_mcmc_log_prob_ar1", [&](const Entry& e) -> int {
+        simplyp::McmcLogProbAr1Args a{};
+        if (int rc = mcmc_log_prob_args(e, W, n_dim, n_out_reaches,
+                                        gof && lag && pair_var && pair_reach && m_dim && m_const && phi_dim && phi_const && prop && lp_prop,
+                                        "gof, lag, pair_var, pair_reach, m_dim, m_const, phi_dim, phi_const, prop and lp_prop", gof,
+                                        status, inside, pair_var, pair_reach, n_pairs, m_dim, m_const, prop, lp_prop, a.b))
+            return rc;
+        for (int v = 0; v < SIMPLYP_N_GOF_VARS; ++v) {
+            if (phi_dim[v] < -1 || phi_dim[v] >= n_dim)
+                return e.refuse("phi_dim[%d] = %d is neither -1 nor a row of prop", v, (int)phi_dim[v]);
+            a.phi_dim[v] = phi_dim[v]; a.phi_const[v] = phi_const[v];
+        }
+        for (int p = 0; p < n_pairs; ++p) {
+            const int v = pair_var[p];
+            if (phi_dim[v] == -1 && !(phi_const[v] > -1.0 && phi_const[v] < 1.0))
+                return e.refuse("phi_const[%d] = %g is not inside (-1, 1)", v, phi_const[v]);
+        }
+        a.lag = lag;
+        if (int rc = mcmc_begin(e, info, a.b.counters)) return rc;
+        hipLaunchKernelGGL(simplyp::simplyp_mcmc_log_prob_ar1_kernel, dim3(blocks(a.b.h, simplyp::MCMC_THREADS)),
+                           dim3(simplyp::MCMC_THREADS), 0, ctx->stream, a);
         return mcmc_end(e, info);
     });
 }

@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "../../include/simplyp.h"
+#include "../../include/simplyp_residuals.h"    // SIMPLYP_LAGSTAT_*
 #include "simplyp_kernels.hip.h"           // sp_log
 #include "simplyp_predictive.hip.h"        // philox4x32_10, philox_uniform
 
@@ -147,6 +148,56 @@ __global__ __launch_bounds__(MCMC_THREADS) void simplyp_mcmc_log_prob_kernel(con
     const bool finite_run = g.status ? (g.status[k] & SIMPLYP_STATUS_NONFINITE) == 0 : true;
     const bool is_nan = sum != sum;
     g.lp_prop[k] = (in && finite_run && m_ok && !is_nan) ? sum : -__builtin_huge_val();
+    mcmc_count(g.counters + 0, in);
+    mcmc_count(g.counters + 2, is_nan);
+}
+
+// The same with an AR(1) error model along linked rows (simplyp_gof_lag.hip.h; simplyp_amd/residuals.py states it): per pair
+//     s = (1 - phi)(1 + phi),  q = SUM_RELSQ + ((phi phi)(A + B) - (2 phi) C) / s,
+//     -0.5 n ln(2 pi) - n ln m - sum_log_sim - q / (2 m m) - 0.5 n_link ln s,          left to right.
+// At phi = 0: s = 1, q = SUM_RELSQ + 0 / 1 and sp_log(1) = +0 exactly (f = 0 makes every term of it 0), so the term has the bits
+// of simplyp_mcmc_log_prob_kernel's.
+struct McmcLogProbAr1Args {
+    McmcLogProbArgs b;
+    int phi_dim[SIMPLYP_N_GOF_VARS];       // row of prop that holds the variable's phi, or -1: phi_const
+    double phi_const[SIMPLYP_N_GOF_VARS];
+    const double* lag;                     // [N_LAG_STATS][N_GOF_VARS][R][h]
+};
+
+__global__ __launch_bounds__(MCMC_THREADS) void simplyp_mcmc_log_prob_ar1_kernel(const McmcLogProbAr1Args a)
+{
+    const McmcLogProbArgs& g = a.b;
+    const int k = blockIdx.x * MCMC_THREADS + threadIdx.x;
+    if (k >= g.h) return;
+    const size_t var_stride = (size_t)g.R * g.h, stat_stride = (size_t)SIMPLYP_N_GOF_VARS * var_stride;
+    double sum = 0.0;
+    bool m_ok = true, phi_ok = true;
+    for (int p = 0; p < g.n_pairs; ++p) {
+        const int v = g.pair_var[p];
+        const double m = g.m_dim[v] >= 0 ? g.prop[(size_t)g.m_dim[v] * g.h + k] : g.m_const[v];
+        const double phi_in = a.phi_dim[v] >= 0 ? g.prop[(size_t)a.phi_dim[v] * g.h + k] : a.phi_const[v];
+        const size_t at = (size_t)v * var_stride + (size_t)g.pair_reach[p] * g.h + k;
+        const double n = g.gof[(size_t)SIMPLYP_GOFSTAT_N_OBS * stat_stride + at];
+        const double sls = g.gof[(size_t)SIMPLYP_GOFSTAT_SUM_LOG_SIM * stat_stride + at];
+        const double srq = g.gof[(size_t)SIMPLYP_GOFSTAT_SUM_RELSQ * stat_stride + at];
+        const double nl = a.lag[(size_t)SIMPLYP_LAGSTAT_N_LINK * stat_stride + at];
+        const double A = a.lag[(size_t)SIMPLYP_LAGSTAT_SQ_HEAD * stat_stride + at];
+        const double B = a.lag[(size_t)SIMPLYP_LAGSTAT_SQ_TAIL * stat_stride + at];
+        const double Cx = a.lag[(size_t)SIMPLYP_LAGSTAT_CROSS * stat_stride + at];
+        const bool in_range = phi_in > -1.0 && phi_in < 1.0;          // NaN fails both
+        m_ok = m_ok && (m > 0.0);
+        phi_ok = phi_ok && in_range;
+        const double phi = in_range ? phi_in : 0.0;
+        const double lm = m > 0.0 ? sp_log(m) : 0.0;
+        const double s = (1.0 - phi) * (1.0 + phi);
+        const double q = srq + ((phi * phi) * (A + B) - (2.0 * phi) * Cx) / s;
+        const double term = ((((-0.5 * n) * 1.8378770664093453) - n * lm - sls) - q / ((2.0 * m) * m)) - (0.5 * nl) * sp_log(s);
+        sum = p == 0 ? term : sum + term;
+    }
+    const bool in = g.inside ? g.inside[k] != 0 : true;
+    const bool finite_run = g.status ? (g.status[k] & SIMPLYP_STATUS_NONFINITE) == 0 : true;
+    const bool is_nan = sum != sum;
+    g.lp_prop[k] = (in && finite_run && m_ok && phi_ok && !is_nan) ? sum : -__builtin_huge_val();
     mcmc_count(g.counters + 0, in);
     mcmc_count(g.counters + 2, is_nan);
 }

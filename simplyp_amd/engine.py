@@ -62,6 +62,10 @@ def prototypes(text):
 with open(os.path.join(INCLUDE, 'simplyp.h')) as _fh:
     PROTOTYPES = prototypes(_fh.read())
 ABI_SYMBOLS = [_name for _name, _, _ in PROTOTYPES]         # every symbol include/simplyp.h declares
+# include/simplyp_residuals.h: the extension header (the lag-one sums and the AR(1) log-probability), read the same way
+with open(os.path.join(INCLUDE, 'simplyp_residuals.h')) as _fh:
+    RESIDUALS_PROTOTYPES = prototypes(_fh.read())
+RESIDUALS_SYMBOLS = [_name for _name, _, _ in RESIDUALS_PROTOTYPES]
 
 
 def build(force=False, verbose=False):
@@ -95,8 +99,10 @@ def lib():
     # library binds to the runtime that owns the process' device tensors and streams.
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
-    for name, restype, argtypes in PROTOTYPES:
-        fn = getattr(L, name)
+    for name, restype, argtypes in PROTOTYPES + RESIDUALS_PROTOTYPES:
+        fn = getattr(L, name, None)
+        if fn is None:
+            raise EngineError("libsimplyp_hip.so lacks the declared symbol %s -- rebuild" % name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.simplyp_abi_version() != abi.ABI_VERSION:
         raise EngineError("libsimplyp_hip.so has ABI %d, the Python host expects %d -- rebuild"
@@ -620,6 +626,26 @@ class Engine(object):
         del keep
         return gof, d
 
+    def gof_lag(self, out, out_mask, obs, f_tdp, reach_params, out_reaches=None, member_of_slot=None, lag=None):
+        """Per-member lag-one sums of the relative residuals ``obs / sim - 1`` (``simplyp_gof_lag``; ``simplyp_amd.residuals``
+        states them) of the daily table ``out`` of a previous ``run``.  Arguments as for ``gof``.  Returns (lag
+        [4, 6, n_out_reaches, E] device tensor in member order -- rows ``abi.LAG_STATS``, variables ``abi.GOF_VARS``, NaN rows for
+        variables with 10 or fewer observations -- and an info dict).  ``lag``: a tensor of that shape to write into."""
+        torch = self.torch
+        head, rp, (D, n_or, E), keep = self._daily_table(out, out_mask, reach_params, out_reaches, member_of_slot, True)
+        obs = np.ascontiguousarray(obs, dtype=np.float64)
+        if obs.shape != (n_or, len(abi.GOF_VARS), D):
+            raise ValueError("obs must have shape %s, got %s" % ((n_or, len(abi.GOF_VARS), D), obs.shape))
+        ft = self._f_tdp(f_tdp, E)
+        shape = (len(abi.LAG_STATS), len(abi.GOF_VARS), n_or, E)
+        if lag is None:
+            lag = torch.empty(shape, dtype=torch.float64, device=self.tdev)
+        elif tuple(lag.shape) != shape or lag.dtype != torch.float64 or not lag.is_contiguous() or lag.device != self.tdev:
+            raise ValueError("lag must be a contiguous float64 tensor of shape %s on %s" % (shape, self.tdev))
+        d = self._info_call(abi.GofInfo, 'simplyp_gof_lag', *(head + (ft.data_ptr(), rp.data_ptr(),
+                                                                      obs.ctypes.data_as(C.POINTER(C.c_double)), lag.data_ptr())))
+        del keep
+        return lag, d
 
     def waterbody(self, out, out_mask, sum_reaches, f_tdp, reach_params, out_reaches=None, member_of_slot=None,
                   columns=None):
@@ -950,6 +976,30 @@ class Engine(object):
                                self._ptr(status), self._ptr(inside), pv.ctypes.data_as(i32), pr.ctypes.data_as(i32), len(pv),
                                md.ctypes.data_as(i32), mc.ctypes.data_as(C.POINTER(C.c_double)), prop.data_ptr(),
                                self._ptr(lp_prop))
+
+    def mcmc_log_prob_ar1(self, gof, lag, pairs, m_dim, m_const, phi_dim, phi_const, prop, lp_prop, status=None, inside=None):
+        """``mcmc_log_prob`` with the AR(1) error model of ``simplyp_amd.residuals`` (``simplyp_mcmc_log_prob_ar1``).  lag
+        [4, 6, n_reaches, h] as ``Engine.gof_lag`` returns it; phi_dim [6]: the row of ``prop`` holding the variable's ``phi`` or
+        -1 for ``phi_const[v]`` (0 = independent errors); the rest as for ``mcmc_log_prob``."""
+        n_dim, h = (int(x) for x in prop.shape)
+        pv = np.ascontiguousarray([p[0] for p in pairs], dtype=np.int32)
+        pr = np.ascontiguousarray([p[1] for p in pairs], dtype=np.int32)
+        md = np.ascontiguousarray(m_dim, dtype=np.int32)
+        mc = np.ascontiguousarray(m_const, dtype=np.float64)
+        pd = np.ascontiguousarray(phi_dim, dtype=np.int32)
+        pc = np.ascontiguousarray(phi_const, dtype=np.float64)
+        NV = len(abi.GOF_VARS)
+        if md.shape != (NV,) or mc.shape != (NV,) or pd.shape != (NV,) or pc.shape != (NV,):
+            raise ValueError("m_dim, m_const, phi_dim and phi_const need one entry per variable of abi.GOF_VARS")
+        if gof.dim() != 4 or tuple(gof.shape[:2]) != (len(abi.GOF_STATS), NV) or int(gof.shape[3]) != h or not gof.is_contiguous():
+            raise ValueError("gof %s does not match prop %s" % (tuple(gof.shape), tuple(prop.shape)))
+        if tuple(lag.shape) != (len(abi.LAG_STATS),) + tuple(gof.shape[1:]) or not lag.is_contiguous():
+            raise ValueError("lag %s does not match gof %s" % (tuple(lag.shape), tuple(gof.shape)))
+        i32, dbl = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        return self._info_call(abi.McmcInfo, 'simplyp_mcmc_log_prob_ar1', self._h, 2 * h, n_dim, int(gof.shape[2]), gof.data_ptr(),
+                               lag.data_ptr(), self._ptr(status), self._ptr(inside), pv.ctypes.data_as(i32), pr.ctypes.data_as(i32),
+                               len(pv), md.ctypes.data_as(i32), mc.ctypes.data_as(dbl), pd.ctypes.data_as(i32),
+                               pc.ctypes.data_as(dbl), prop.data_ptr(), self._ptr(lp_prop))
 
     def mcmc_accept(self, theta, lp, n_accept, half, t, prop, inside, lp_prop, chain_row=None, a=2.0, seed=0):
         """The decisions of half ``half`` at step ``t``, in place on theta [n_dim, W], lp [W] and n_accept [W] (int32)

@@ -19,7 +19,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pandas as pd
 
-from . import abi, engine, ensemble, marshal, request, weighted
+from . import abi, engine, ensemble, marshal, request, residuals, weighted
 from . import forcing as forcing_rules
 from . import helper_functions as hf, pareto as pareto_rules, score as score_rules, visualise_results as vr
 
@@ -415,6 +415,8 @@ def _request(**kw):
         if r.devices is not None:
             raise ValueError("score cannot be combined with devices=[...]: a score of the whole ensemble is not a function of the "
                              "member blocks' scores -- run it on one device")
+    if r.residual_lag and r.obs_dict is None:
+        raise ValueError("residual_lag needs obs_dict: the observations the residuals are taken against")
     if r.pareto is not None:
         if r.obs_dict is None:
             raise ValueError("pareto needs obs_dict: the objectives are rows of the goodness-of-fit table")
@@ -627,6 +629,9 @@ def _block_pass(r, eng, lo, hi):
         gof_d, info = eng.gof(out_d, mask, r.obs, spearman=r.spearman, **tkw)
         rho = info.pop('spearman', None)
         part['gof'] = (keep(gof_d), info, None if rho is None else keep(rho))
+        if r.residual_lag:
+            lag_d, linfo = eng.gof_lag(out_d, mask, r.obs, **tkw)
+            part['lag'] = (keep(lag_d), linfo)
     if r.wb_sum:
         wb_d, winfo = eng.waterbody(out_d, mask, [r.scs.index(x) for x in r.wb_reaches], **tkw)
         part['wb'] = (keep(wb_d), winfo)
@@ -718,6 +723,11 @@ def _assemble(r, parts):
         res['gof'] = gof_result('gof')
         if first['gof'][2] is not None:          # Spearman's r [6, n_reaches, E]: the rank statistic of the reference's table (:444-445)
             res['gof']['spearman'] = cat([pt['gof'][2] for pt in parts])
+        if r.residual_lag:
+            lag = cat([pt['lag'][0] for pt in parts])
+            tail, cross = lag[abi.LAG_STATS.index('sq_tail')], lag[abi.LAG_STATS.index('cross')]
+            res['residual_lag'] = dict({k: lag[i] for i, k in enumerate(abi.LAG_STATS)}, variables=list(abi.GOF_VARS),
+                                       phi_hat=residuals.phi_hat(tail, cross) if to_host else cross / tail, info=first['lag'][1])
     if r.wb_sum:
         winfo = first['wb'][1]
         res['waterbody'] = dict(columns=winfo['columns'], reaches=r.wb_reaches, info=winfo, data=cat([pt['wb'][0] for pt in parts]))
@@ -793,7 +803,7 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
                           quantile_members=None, initial_state=None, return_state=False, time_quantiles=None,
                           time_quantile_series=None, time_quantile_periods=None, predictive_series=None, predictive_m=None,
                           predictive_seed=0, predictive_day0=0, quantile_weights=None, quantile_log_weights=None, score=False,
-                          pareto=None, pareto_max_fronts=0, forcing_error=None, forcing_seed=0):
+                          pareto=None, pareto_max_fronts=0, forcing_error=None, forcing_seed=0, residual_lag=False):
     """Run an ensemble of parameter sets through the engine in one call.
 
     ``overrides``: dict name -> array[E] (member parameters, see ``marshal.PM_NAMES``) or
@@ -817,6 +827,13 @@ def run_simply_p_ensemble(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options,
     uses ``p['f_TDP']`` or ``overrides['f_TDP']`` (array[E]).  ``spearman=True`` adds the table's rank statistic under
     ``['gof']['spearman']`` [6, n_reaches, E] (counted on the device, ~0.1-0.2 s for 100 000 members).  ``keep_daily=False`` drops the daily table once the
     statistics exist (``data`` is None): the 44 GB of a 100 000-member run never leave the device.
+    ``residual_lag=True`` (needs ``obs_dict``): the autocorrelation check the reference's calibration notebook ends with
+    (Development/2016/MCMC.ipynb cell 21), for every member and without a table transfer -- the lag-one sums of the relative
+    residuals ``obs / sim - 1`` over the days whose predecessor is observed too (``simplyp_gof_lag``; ``simplyp_amd.residuals``
+    states them) under ``'residual_lag'`` = dict(variables, n_link, sq_head, sq_tail, cross -- each [6, n_reaches, E] --,
+    phi_hat = cross / sq_tail, the conditional maximum-likelihood lag-one coefficient, info).  A device reduction like the
+    goodness of fit: it works with ``keep_daily=False`` and with ``devices=[...]``, and per window in
+    ``run_simply_p_ensemble_windows``, where a link does not cross a window's edge (a window's first day has no predecessor).
 
     ``waterbody``: the reference's ``sum_to_waterbody`` (model.py:851-900) for every member, on the device: ``True`` sums
     the sub-catchments flagged ``p_struc['In_final_flux?'] == 1``, a list sums the given sub-catchment ids.  Like the
