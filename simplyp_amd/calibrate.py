@@ -4,13 +4,15 @@
 Nelder-Mead search (``simplyp_amd.neldermead`` is its NumPy statement); ``sample_posterior`` is their
 ``emcee.EnsembleSampler(n_walk, n_dim, log_posterior).run_mcmc(start, n_steps)`` (``simplyp_amd.mcmc`` states the move); and
 ``start_ball`` hands the one's result to the other.  The points, the model runs, the likelihood and the decisions are all on the
-GPU; both calls share the names, the checks, the marshalling and the evaluation (``_host_setup``, ``_Evaluator``)."""
+GPU; both calls share the names, the checks, the marshalling and the evaluation (``_host_setup``, ``_Evaluator``).
+``find_pareto`` is the multi-objective calibration the notebooks stop short of: NSGA-II over several goodness-of-fit criteria at
+once (``simplyp_amd.nsga2`` states the rule), on the same set-up without a likelihood."""
 
 import time
 
 import numpy as np
 
-from . import abi, marshal, mcmc, neldermead, predictive, priors as _priors, visualise_results as vr
+from . import abi, marshal, mcmc, neldermead, nsga2, pareto, predictive, priors as _priors, visualise_results as vr
 from .model import _DeviceEnsemble
 from .priors import box as _box
 
@@ -126,13 +128,20 @@ class _Evaluator:
         if phi is not None:
             self.lag_d = torch.empty((len(abi.LAG_STATS), len(abi.GOF_VARS), R, n_members), **f64)
 
-    def evaluate(self):
-        """Returns the kernel times of the run, the goodness of fit and the log posterior, in ms.  With a lag-one coefficient
-        (``phi``) the lag-one sums are taken between the last two and the AR(1) log posterior replaces the independent one."""
+    def run_gof(self):
+        """The model at the run points and the goodness-of-fit table ``gof_d`` of its output: (the members' status on the device,
+        the run's stats, the table's info)."""
         hs, dev, eng = self.hs, self.dev, self.dev.eng
         _, status_d, rstats = eng.run(dev.f_d, dev.doy_d, dev.mp_d, dev.rp_d, hs['up_ptr'], hs['up_idx'], dev.opts,
                                       out_reaches=hs['oreach'], out=self.out_d)
         _, ginfo = eng.gof(self.out_d, dev.mask, hs['obs'], dev.ft_d, dev.rp_d, out_reaches=hs['oreach'], gof=self.gof_d)
+        return status_d, rstats, ginfo
+
+    def evaluate(self):
+        """Returns the kernel times of the run, the goodness of fit and the log posterior, in ms.  With a lag-one coefficient
+        (``phi``) the lag-one sums are taken between the last two and the AR(1) log posterior replaces the independent one."""
+        hs, dev, eng = self.hs, self.dev, self.dev.eng
+        status_d, rstats, ginfo = self.run_gof()
         if self.phi is None:
             linfo = eng.mcmc_log_prob(self.gof_d, hs['pairs'], self.m_dim, self.m_const, self.prop_d, self.lpp_d, status=status_d,
                                       inside=self.inside_d)
@@ -455,4 +464,193 @@ def find_map(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, pr
     if record_evaluations:
         res['evaluations'] = torch.stack(evals).cpu().numpy() if evals else np.empty((0, n_dim, neldermead.SLOTS * S))
         res['evaluation_log_prob'] = torch.stack(evals_lp).cpu().numpy() if evals_lp else np.empty((0, neldermead.SLOTS * S))
+    return res
+
+
+def _pareto_plan(priors, objectives, n_pop, n_gen, seed, eta_c, eta_m, p_cross, p_mut, n_reaches=1 << 30):
+    """Names, box, targets, objectives and operator settings of ``find_pareto``; host only, raises ValueError."""
+    if not isinstance(priors, dict) or not priors:
+        raise ValueError("priors must be a dict name -> (lo, hi) with at least one entry")
+    names = list(priors)
+    target = []
+    for nm in names:
+        if nm.startswith('m_') or nm.startswith('phi_'):
+            raise ValueError("find_pareto takes no error-model parameter (%r): no likelihood is involved" % nm)
+        if _priors.target_of(nm) is None:
+            raise ValueError("unknown parameter %r: searched names are %s and 'f_TDP'" % (nm, marshal.PM_NAMES))
+        target.append(_priors.target_of(nm))
+    if n_pop is None:
+        raise ValueError("n_pop must be given")
+    try:
+        objectives = [tuple(o) for o in objectives]
+    except TypeError:
+        raise ValueError("objectives must be a list of (stat, variable[, reach_index[, sense]])")
+    if any(len(o) and o[0] == 'spearman' for o in objectives):
+        raise ValueError("find_pareto takes no 'spearman' objective in this version")
+    resolved = pareto.resolve_objectives(objectives, n_reaches=n_reaches)
+    try:
+        nsga2.check_shape(int(n_pop), len(names), len(resolved))
+    except ValueError as exc:
+        raise ValueError("find_pareto: %s" % exc)
+    k_c, k_m = nsga2.k_of_eta(eta_c, 'eta_c'), nsga2.k_of_eta(eta_m, 'eta_m')
+    p_cross = nsga2.check_probability(p_cross, 'p_cross')
+    p_mut = nsga2.check_probability(1.0 / len(names) if p_mut is None else p_mut, 'p_mut')
+    if not 0 <= int(seed) < 1 << 64 or int(n_gen) < 0:
+        raise ValueError("seed must be in [0, 2^64) and n_gen >= 0")
+    lo, hi = _box(priors, names)
+    return names, lo, hi, np.array(target, dtype=np.int32), resolved, k_c, k_m, p_cross, p_mut
+
+
+def find_pareto(met_df, p_struc, p_SU, p_LU, p_SC, p, dynamic_options, obs_dict, priors, objectives, n_pop=None, n_gen=0,
+                start=None, seed=0, eta_c=15, eta_m=15, p_cross=0.9, p_mut=None, state=None, record_children=False,
+                step_len=1., solver=None, device=0, out_reaches=None):
+    """Move a population towards the Pareto front of several goodness-of-fit criteria with NSGA-II (Deb et al. 2002), every
+    generation one ensemble run of ``n_pop`` members on the device.
+
+    ``priors``: dict name -> (lo, hi), the closed box ``lo <= x <= hi`` of member parameters (``marshal.PM_NAMES``) and
+    ``'f_TDP'``, at most 16; ``'m_<VAR>'`` / ``'phi_<VAR>'`` are refused: no likelihood is involved.  ``objectives``: as for
+    ``pareto_ranks`` (``pareto.resolve_objectives``: NSE, log NSE and r2 are maximised, nRMSD (%) is minimised, Bias (%) is
+    minimised in absolute value, a fourth element gives the sense), 1 to 8 of them, each at an output reach with more than 10
+    observations of its variable; ``'spearman'`` is refused in this version.  ``n_pop`` even, in [4, 65536]; ``n_gen``
+    generations after the initial population's; ``eta_c`` / ``eta_m``: the distribution indices of the crossover and the
+    mutation, one of 1, 3, 7, 15, 31; ``p_cross``; ``p_mut`` (None: ``1 / n_dim``); ``seed`` the key of the counter-based
+    stream.  ``start``: None = ``lo + (hi - lo) u`` drawn on the device, or an array [n_dim, n_pop] inside the box.
+    ``state``: the ``'state'`` of an earlier result: the search continues at its generation count, bit for bit (``start`` is
+    ignored).  ``simplyp_amd.nsga2`` states the whole rule.
+
+    The inputs are marshalled and uploaded once; a generation is ``nsga2_offspring`` -> ``Engine.run`` -> ``Engine.gof`` -> the
+    objective rows -> ``Engine.pareto`` on the 2 ``n_pop`` parents and children, a member with a non-finite objective or a
+    non-finite run left out -> ``nsga2_crowding`` -> ``nsga2_select``, all on device buffers.  Returns dict(names, x[n_dim, n_pop]
+    sorted best first, objectives[M, n_pop] -- the statistics as the goodness-of-fit table has them: a bias keeps its sign --,
+    labels, sense, absolute -- which objectives are ranked by their absolute value --, rank[n_pop], crowding[n_pop], front -- the
+    indices of rank 0 --, overrides -- ``x`` shaped for ``run_simply_p_ensemble(overrides=)`` --, history = dict(n_front0,
+    n_fronts, n_invalid: one entry per evaluated generation, counted in the set that was ranked; best[n, M]: the best value of
+    every objective as it is ranked among the survivors), with ``record_children`` children[n, n_dim, n_pop],
+    children_objectives[n, M, n_pop], children_valid[n, n_pop] and survivors[n, n_pop], ranks[n, n_pop], crowdings[n, n_pop]
+    after every evaluated generation (the initial population is the first "children" of a search that starts here),
+    state = dict(theta, objectives, rank, crowd, t), seed, stats = per-generation lists of wall_ms, run_kernel_ms, gof_ms,
+    pareto_ms, crowding_ms, select_ms, offspring_ms).  Every ``ValueError`` comes before any device call.  The caller's
+    ``p_LU`` / ``p_SC`` are edited in place exactly as by ``run_simply_p``."""
+    if not obs_dict:
+        raise ValueError("find_pareto needs obs_dict: the observations the criteria are taken over")
+    names, lo, hi, target, resolved, k_c, k_m, p_cross, p_mut = _pareto_plan(priors, objectives, n_pop, n_gen, seed, eta_c, eta_m,
+                                                                             p_cross, p_mut)
+    n_dim, N, M, n_gen, seed = len(names), int(n_pop), len(resolved), int(n_gen), int(seed)
+    variables = list(dict.fromkeys(r['variable'] for r in resolved))
+
+    with marshal.reference_edits(p_SU, p_LU, p_SC, p):
+        hs = _host_setup(met_df, p_struc, p_SU, p_LU, p_SC, p, obs_dict, names, variables, lo, hi, out_reaches)
+        resolved = pareto.resolve_objectives(objectives, n_reaches=len(hs['reaches']))
+        n_obs = (~np.isnan(hs['obs'])).sum(axis=-1)
+        for r in resolved:
+            if n_obs[r['reach'], r['var_index']] <= 10:
+                raise ValueError("objective %s: 10 or fewer observations of %r at that output reach: its statistics are NaN"
+                                 % (r['label'], r['variable']))
+        sense = [r['sense'] for r in resolved]
+        absolute = np.array([r['absolute'] for r in resolved], dtype=bool)
+        raw = [dict(r, absolute=False) for r in resolved]
+        inside = lambda x: bool(((x >= lo[:, None]) & (x <= hi[:, None])).all())
+        if state is not None:
+            st0 = dict(theta=np.array(state['theta'], dtype=np.float64), objectives=np.array(state['objectives'], dtype=np.float64),
+                       rank=np.array(state['rank'], dtype=np.int32), crowd=np.array(state['crowd'], dtype=np.float64))
+            t0 = int(state['t'])
+            if st0['theta'].shape != (n_dim, N) or st0['objectives'].shape != (M, N) or st0['rank'].shape != (N,) \
+                    or st0['crowd'].shape != (N,) or t0 < 0:
+                raise ValueError("state does not match this call: theta %s for %d names and %d members" % (st0['theta'].shape, n_dim, N))
+            if not inside(st0['theta']):
+                raise ValueError("the state lies outside the box")
+        else:
+            t0 = 0
+            if start is not None:
+                start = np.array(start, dtype=np.float64)
+                if start.shape != (n_dim, N):
+                    raise ValueError("start must have shape [n_dim, n_pop] = %s, got %s" % ((n_dim, N), start.shape))
+                if not inside(start):
+                    d = int(np.argmin(((start >= lo[:, None]) & (start <= hi[:, None])).all(axis=1)))
+                    raise ValueError("the start lies outside the box in %r" % names[d])
+        if t0 + n_gen >= 1 << 32:
+            raise ValueError("the absolute generation count must stay below 2^32")
+
+        # ---- the device: everything is marshalled and uploaded once, for an ensemble of n_pop members
+        ev = _Evaluator("find_pareto keeps members in population order", hs, met_df, p_SU, p_LU, p_SC, p, dynamic_options, step_len,
+                        solver, device, N, n_dim, None, None)
+        dev = ev.dev
+        eng, torch, f64 = dev.eng, dev.torch, dev.f64
+        child_d = ev.prop_d                                              # [n_dim, N]
+        par_d = torch.empty((2, N), dtype=torch.int32, device=eng.tdev) if record_children else None
+        abs_d = torch.from_numpy(absolute).to(eng.tdev)
+        sense_d = torch.tensor([float(s) for s in sense], **f64)[:, None]
+        stats = {k: [] for k in ('wall_ms', 'run_kernel_ms', 'gof_ms', 'pareto_ms', 'crowding_ms', 'select_ms', 'offspring_ms')}
+        hist = dict(n_front0=[], n_fronts=[], n_invalid=[])
+        best, rec = [], {k: [] for k in ('children', 'children_objectives', 'children_valid', 'survivors', 'ranks', 'crowdings')}
+
+        def ranked(rows):
+            return torch.where(abs_d[:, None], rows.abs(), rows)
+
+        def generation(theta_d, obj_d, rank_d, off_ms):
+            """The children in ``child_d`` (their run points are in place) evaluated and the set of parents (None: generation 0)
+            and children reduced to N survivors: (theta, objectives, rank, crowd) on the device, sorted best first."""
+            status_d, rstats, ginfo = ev.run_gof()
+            cobj = pareto.objective_rows(ev.gof_d, None, raw)
+            valid = torch.isfinite(cobj).all(dim=0) & ((status_d & abi.STATUS_NONFINITE) == 0)
+            if theta_d is None:
+                pool, include = torch.cat([child_d, cobj]), valid
+            else:
+                pool = torch.cat([torch.cat([theta_d, child_d], dim=1), torch.cat([obj_d, cobj], dim=1)])
+                include = torch.cat([rank_d >= 0, valid])
+            robj = ranked(pool[n_dim:]).contiguous()
+            pr = eng.pareto(robj, sense, include=include, counts=False)
+            crowd_all, cinfo = eng.nsga2_crowding(robj, sense, pr['rank'])
+            sel = eng.nsga2_select(N, pr['rank'], crowd_all, rows=pool.contiguous())
+            new_theta, new_obj = sel['rows'][:n_dim].contiguous(), sel['rows'][n_dim:].contiguous()
+            hist['n_front0'].append(int(pr['n_front0']))
+            hist['n_fronts'].append(int(pr['n_fronts']))
+            hist['n_invalid'].append(int(pool.shape[1]) - int(pr['n_used']))
+            y = torch.where((sel['rank'] >= 0)[None, :], ranked(new_obj) * sense_d, torch.full_like(new_obj, -float('inf')))
+            best.append(y.max(dim=1).values * sense_d[:, 0])
+            if record_children:
+                for k, v in (('children', child_d), ('children_objectives', cobj), ('children_valid', valid),
+                             ('survivors', sel['survivor']), ('ranks', sel['rank']), ('crowdings', sel['crowd'])):
+                    rec[k].append(v.clone())
+            for k, v in (('run_kernel_ms', rstats['kernel_ms']), ('gof_ms', ginfo['kernel_ms']), ('pareto_ms', pr['kernel_ms']),
+                         ('crowding_ms', cinfo['kernel_ms']), ('select_ms', sel['kernel_ms']), ('offspring_ms', off_ms)):
+                stats[k].append(v)
+            return new_theta, new_obj, sel['rank'], sel['crowd']
+
+        if state is None:
+            torch.cuda.synchronize(eng.tdev)
+            w0 = time.perf_counter()
+            if start is None:
+                off_ms = eng.nsga2_init(child_d, lo, hi, target, dev.mp_d, dev.ft_d, seed=seed)['kernel_ms']
+            else:
+                child_d.copy_(eng.to_device(start, torch.float64))
+                dev.write_positions(child_d, target)
+                off_ms = 0.0
+            theta_d, obj_d, rank_d, crowd_d = generation(None, None, None, off_ms)
+            torch.cuda.synchronize(eng.tdev)
+            stats['wall_ms'].append(1e3 * (time.perf_counter() - w0))
+        else:
+            theta_d, obj_d = eng.to_device(st0['theta'], torch.float64), eng.to_device(st0['objectives'], torch.float64)
+            rank_d, crowd_d = eng.to_device(st0['rank'], torch.int32), eng.to_device(st0['crowd'], torch.float64)
+        for t in range(t0 + 1, t0 + n_gen + 1):
+            torch.cuda.synchronize(eng.tdev)
+            w0 = time.perf_counter()
+            oinfo = eng.nsga2_offspring(theta_d, rank_d, crowd_d, t, lo, hi, target, child_d, parents=par_d, member_params=dev.mp_d,
+                                        f_tdp=dev.ft_d, k_c=k_c, k_m=k_m, p_cross=p_cross, p_mut=p_mut, seed=seed)
+            theta_d, obj_d, rank_d, crowd_d = generation(theta_d, obj_d, rank_d, oinfo['kernel_ms'])
+            torch.cuda.synchronize(eng.tdev)
+            stats['wall_ms'].append(1e3 * (time.perf_counter() - w0))
+
+    x, obj = theta_d.cpu().numpy(), obj_d.cpu().numpy()
+    rank, crowd = rank_d.cpu().numpy(), crowd_d.cpu().numpy()
+    hist['best'] = torch.stack(best).cpu().numpy() if best else np.empty((0, M))
+    res = dict(names=names, x=x, objectives=obj, labels=[r['label'] for r in resolved], sense=sense, absolute=absolute, rank=rank,
+               crowding=crowd, front=np.flatnonzero(rank == 0), overrides={nm: x[d].copy() for d, nm in enumerate(names)},
+               history=hist, seed=seed, state=dict(theta=x.copy(), objectives=obj.copy(), rank=rank.copy(), crowd=crowd.copy(), t=t0 + n_gen),
+               stats=stats)
+    if record_children:
+        shapes = dict(children=(0, n_dim, N), children_objectives=(0, M, N), children_valid=(0, N), survivors=(0, N), ranks=(0, N),
+                      crowdings=(0, N))
+        for k, v in rec.items():
+            res[k] = torch.stack(v).cpu().numpy() if v else np.empty(shapes[k])
     return res

@@ -31,6 +31,7 @@
 #include "simplyp_pareto.hip.h"
 #include "simplyp_mcmc.hip.h"
 #include "simplyp_neldermead.hip.h"
+#include "simplyp_nsga2.hip.h"
 #include "simplyp_sobol.hip.h"
 #include "simplyp_particle.hip.h"
 #include "simplyp_pack_stream.h"
@@ -73,6 +74,7 @@ struct simplyp_ctx {
     DeviceBuf pareto;         // simplyp_pareto: 8 x int32 (n, the peeling's counters) | [E] flags | block offsets | keys [M][E] | 8 x [E] int32 (members, counts, ranks, lists)
     DeviceBuf mcmc;           // simplyp_mcmc_*: 4 x uint32 (inside, accepted, NaN)
     DeviceBuf nm;             // simplyp_nm_*: 8 x uint32 counters
+    DeviceBuf nsga2;          // simplyp_nsga2_crowding: keys [M][n] | running keys [4][M][n] (uint64); the counters are `mcmc`'s
     DeviceBuf nm_work;        // simplyp_nm_update: the sort's other copy of the simplexes
     DeviceBuf sobol;          // simplyp_sobol_indices: n_valid | valid [Npad] | mu [n_rows] | n_used [B] | counts [B][Npad] uint16 | sums
     DeviceBuf pf;             // simplyp_pf_*, simplyp_gather_members: PfResult (256-byte slot) | the entry's lists, partial or prefix sums
@@ -1094,6 +1096,7 @@ void simplyp_ctx_destroy(simplyp_ctx* ctx)
     if (ctx->pred.ptr) (void)hipFree(ctx->pred.ptr);
     if (ctx->mcmc.ptr) (void)hipFree(ctx->mcmc.ptr);
     if (ctx->nm.ptr) (void)hipFree(ctx->nm.ptr);
+    if (ctx->nsga2.ptr) (void)hipFree(ctx->nsga2.ptr);
     if (ctx->nm_work.ptr) (void)hipFree(ctx->nm_work.ptr);
     if (ctx->sobol.ptr) (void)hipFree(ctx->sobol.ptr);
     if (ctx->pf.ptr) (void)hipFree(ctx->pf.ptr);
@@ -2871,6 +2874,117 @@ int simplyp_mcmc_accept(simplyp_ctx* ctx, int32_t W, int32_t n_dim, int32_t half
         hipLaunchKernelGGL(simplyp::simplyp_mcmc_accept_kernel, dim3(blocks(g.mv.h, simplyp::MCMC_THREADS)),
                            dim3(simplyp::MCMC_THREADS), 0, ctx->stream, g);
         return mcmc_end(e, info);
+    });
+}
+
+// ---- NSGA-II (include/simplyp_nsga2.h; simplyp_nsga2.h holds the checks and the variation, simplyp_nsga2.hip.h the kernels) ------
+namespace sn = simplyp_nsga2;
+
+// What the init and offspring entries fill alike once their own checks have passed: the box, the targets, the key.
+static int nsga2_vary_args(const Entry& e, int32_t N, int32_t n_dim, uint64_t seed, uint32_t t, const double* lo, const double* hi,
+                           const int32_t* target, double* member_params, double* f_tdp, simplyp::Nsga2VaryArgs& g)
+{
+    simplyp_ctx* const ctx = e.ctx;
+    TABLE_TRY(ctx, st::check_box(e.me, n_dim, lo, hi, target, member_params, f_tdp, g.lo, g.hi, g.target, msg));
+    g.N = N; g.n_dim = n_dim; g.t = t;
+    philox_key(seed, g);
+    g.member_params = member_params; g.f_tdp = f_tdp;
+    return SIMPLYP_OK;
+}
+
+int simplyp_nsga2_init(simplyp_ctx* ctx, int32_t N, int32_t n_dim, uint64_t seed, const double* lo, const double* hi,
+                       const int32_t* target, double* theta, double* member_params, double* f_tdp, simplyp_mcmc_info* info)
+{
+    return entry(ctx, "simplyp_nsga2_init", [&](const Entry& e) -> int {
+        TABLE_TRY(ctx, sn::check_init(e.me, N, n_dim, theta, msg));
+        simplyp::Nsga2VaryArgs g{};
+        if (int rc = nsga2_vary_args(e, N, n_dim, seed, 0u, lo, hi, target, member_params, f_tdp, g)) return rc;
+        g.child = theta;
+        if (int rc = mcmc_begin(e, info, g.counters)) return rc;
+        hipLaunchKernelGGL(simplyp::nsga2_init_kernel, dim3(blocks(N, simplyp::NSGA2_THREADS)), dim3(simplyp::NSGA2_THREADS), 0,
+                           ctx->stream, g);
+        return mcmc_end(e, info);
+    });
+}
+
+int simplyp_nsga2_offspring(simplyp_ctx* ctx, int32_t N, int32_t n_dim, uint64_t seed, uint32_t t, int32_t k_c, int32_t k_m,
+                            double p_cross, double p_mut, const double* lo, const double* hi, const int32_t* target,
+                            const double* theta, const int32_t* rank, const double* crowd, double* child, int32_t* parents,
+                            double* member_params, double* f_tdp, simplyp_mcmc_info* info)
+{
+    return entry(ctx, "simplyp_nsga2_offspring", [&](const Entry& e) -> int {
+        TABLE_TRY(ctx, sn::check_offspring(e.me, N, n_dim, k_c, k_m, p_cross, p_mut, theta, rank, crowd, child, msg));
+        simplyp::Nsga2VaryArgs g{};
+        if (int rc = nsga2_vary_args(e, N, n_dim, seed, t, lo, hi, target, member_params, f_tdp, g)) return rc;
+        g.k_c = k_c; g.k_m = k_m; g.p_cross = p_cross; g.p_mut = p_mut;
+        g.theta = theta; g.rank = rank; g.crowd = crowd; g.child = child; g.parents = parents;
+        if (int rc = mcmc_begin(e, info, g.counters)) return rc;
+        hipLaunchKernelGGL(simplyp::nsga2_offspring_kernel, dim3(blocks(N / 2, simplyp::NSGA2_THREADS)), dim3(simplyp::NSGA2_THREADS), 0,
+                           ctx->stream, g);
+        return mcmc_end(e, info);
+    });
+}
+
+int simplyp_nsga2_crowding(simplyp_ctx* ctx, int32_t n, int32_t M, const double* obj, const int32_t* sense, const int32_t* rank,
+                           double* crowd, simplyp_pareto_info* info)
+{
+    return entry(ctx, "simplyp_nsga2_crowding", [&](const Entry& e) -> int {
+        TABLE_TRY(ctx, sn::check_crowding(e.me, n, M, obj, sense, rank, crowd, msg));
+        if (info) *info = {};
+        const size_t plane = (size_t)M * (size_t)n * sizeof(unsigned long long);
+        if (int rc = ensure(ctx, ctx->nsga2, 5 * plane)) return rc;
+        if (int rc = zeroed_head(e, ctx->mcmc, 4 * sizeof(unsigned), 4 * sizeof(unsigned))) return rc;
+        simplyp::Nsga2KeyArgs k{};
+        k.n = n; k.M = M; k.obj = obj;
+        for (int m = 0; m < M; ++m) k.sense[m] = sense[m];
+        k.key = (unsigned long long*)ctx->nsga2.ptr;
+        k.run = k.key + (size_t)M * n;
+        unsigned* const counters = (unsigned*)ctx->mcmc.ptr;
+        const dim3 block(simplyp::NSGA2_THREADS), grid_n(blocks(n, simplyp::NSGA2_THREADS));
+        const dim3 grid_pairs(grid_n.x, blocks(n, simplyp::NSGA2_JSPLIT));
+        if (int rc = e.begin()) return rc;
+        hipLaunchKernelGGL(simplyp::nsga2_keys_kernel, grid_n, block, 0, ctx->stream, k);
+        HIP_TRY(ctx, hipGetLastError());
+#define NSGA2_CASE(MP)                                                                                                      \
+    hipLaunchKernelGGL((simplyp::nsga2_crowd_pairs_kernel<MP>), grid_pairs, block, 0, ctx->stream, k.key, (int)M, (int)n, rank, k.run)
+        switch (M) {                                    // M padded to the next compiled size
+        case 1: NSGA2_CASE(1); break;
+        case 2: NSGA2_CASE(2); break;
+        case 3: NSGA2_CASE(3); break;
+        case 4: NSGA2_CASE(4); break;
+        case 5: case 6: NSGA2_CASE(6); break;
+        default: NSGA2_CASE(8); break;
+        }
+#undef NSGA2_CASE
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(simplyp::nsga2_crowd_finish_kernel, grid_n, block, 0, ctx->stream, (int)n, (int)M, rank, k.run, crowd, counters);
+        unsigned c[4] = {};
+        if (int rc = e.end(info ? &info->kernel_ms : nullptr, c, counters, sizeof(c))) return rc;
+        if (info) { info->pair_tests = (int64_t)n * n; info->n_used = (int32_t)c[0]; }
+        return SIMPLYP_OK;
+    });
+}
+
+int simplyp_nsga2_select(simplyp_ctx* ctx, int32_t n, int32_t N, const int32_t* rank, const double* crowd, int32_t* position,
+                         int32_t* survivor, int32_t n_rows, const double* rows_in, double* rows_out, int32_t* rank_out,
+                         double* crowd_out, simplyp_pareto_info* info)
+{
+    return entry(ctx, "simplyp_nsga2_select", [&](const Entry& e) -> int {
+        TABLE_TRY(ctx, sn::check_select(e.me, n, N, rank, crowd, position, survivor, n_rows, rows_in, rows_out, msg));
+        if (info) *info = {};
+        simplyp::Nsga2GatherArgs g{};
+        g.n = n; g.N = N; g.n_rows = n_rows; g.position = position; g.rank = rank; g.crowd = crowd; g.rows_in = rows_in;
+        g.survivor = survivor; g.rank_out = rank_out; g.crowd_out = crowd_out; g.rows_out = rows_out;
+        const dim3 block(simplyp::NSGA2_THREADS), grid_n(blocks(n, simplyp::NSGA2_THREADS));
+        if (int rc = e.begin()) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(position, 0, (size_t)n * sizeof(int32_t), ctx->stream));
+        hipLaunchKernelGGL(simplyp::nsga2_position_kernel, dim3(grid_n.x, blocks(n, simplyp::NSGA2_JSPLIT)), block, 0, ctx->stream,
+                           (int)n, rank, crowd, position);
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(simplyp::nsga2_gather_kernel, grid_n, block, 0, ctx->stream, g);
+        if (int rc = e.end(info ? &info->kernel_ms : nullptr)) return rc;
+        if (info) { info->pair_tests = (int64_t)n * n; info->n_used = N; }
+        return SIMPLYP_OK;
     });
 }
 

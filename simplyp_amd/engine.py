@@ -66,6 +66,10 @@ ABI_SYMBOLS = [_name for _name, _, _ in PROTOTYPES]         # every symbol inclu
 with open(os.path.join(INCLUDE, 'simplyp_residuals.h')) as _fh:
     RESIDUALS_PROTOTYPES = prototypes(_fh.read())
 RESIDUALS_SYMBOLS = [_name for _name, _, _ in RESIDUALS_PROTOTYPES]
+# include/simplyp_nsga2.h: the extension header of NSGA-II's pieces (initial population, crowding, selection, offspring)
+with open(os.path.join(INCLUDE, 'simplyp_nsga2.h')) as _fh:
+    NSGA2_PROTOTYPES = prototypes(_fh.read())
+NSGA2_SYMBOLS = [_name for _name, _, _ in NSGA2_PROTOTYPES]
 
 
 def build(force=False, verbose=False):
@@ -99,7 +103,7 @@ def lib():
     # library binds to the runtime that owns the process' device tensors and streams.
     import torch  # noqa: F401
     L = C.CDLL(LIB_PATH)
-    for name, restype, argtypes in PROTOTYPES + RESIDUALS_PROTOTYPES:
+    for name, restype, argtypes in PROTOTYPES + RESIDUALS_PROTOTYPES + NSGA2_PROTOTYPES:
         fn = getattr(L, name, None)
         if fn is None:
             raise EngineError("libsimplyp_hip.so lacks the declared symbol %s -- rebuild" % name)
@@ -1038,6 +1042,88 @@ class Engine(object):
         return self._info_call(abi.NmInfo, 'simplyp_nm_update', self._h, S, n_dim, int(max_iter), float(xatol), float(fatol), self._ptr(prop),
                                self._ptr(inside), self._ptr(lp_prop), sim.data_ptr(), self._ptr(fsim), self._ptr(istate),
                                self._ptr(history), 0 if history is None else int(history.shape[0]))
+
+    # ---- NSGA-II (simplyp_nsga2_*, include/simplyp_nsga2.h; simplyp_amd.nsga2 states the rule) ----
+    @staticmethod
+    def _box_args(n_dim, lo, hi, target):
+        lo = np.ascontiguousarray(lo, dtype=np.float64)
+        hi = np.ascontiguousarray(hi, dtype=np.float64)
+        tg = np.ascontiguousarray(target, dtype=np.int32)
+        if lo.shape != (n_dim,) or hi.shape != (n_dim,) or tg.shape != (n_dim,):
+            raise ValueError("lo, hi and target need one entry per dimension")
+        dbl = C.POINTER(C.c_double)
+        return (lo.ctypes.data_as(dbl), hi.ctypes.data_as(dbl), tg.ctypes.data_as(C.POINTER(C.c_int32))), (lo, hi, tg)
+
+    def nsga2_init(self, theta, lo, hi, target, member_params=None, f_tdp=None, seed=0):
+        """The initial population into theta [n_dim, N] (float64 device tensor, written) and its scatter into member_params
+        [NP_M, N] / f_tdp [N] (``simplyp_nsga2_init``).  lo / hi / target [n_dim] on the host, as for ``mcmc_propose``.  The
+        library checks the values; the tensors' shapes are the caller's.  Returns the info dict."""
+        n_dim, N = (int(x) for x in theta.shape)
+        ptrs, keep = self._box_args(n_dim, lo, hi, target)
+        info = self._info_call(abi.McmcInfo, 'simplyp_nsga2_init', self._h, N, n_dim, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                               *ptrs, theta.data_ptr(), self._ptr(member_params), self._ptr(f_tdp))
+        del keep
+        return info
+
+    def nsga2_crowding(self, obj, sense, rank, crowd=None):
+        """The crowding distance of every member within its front (``simplyp_nsga2_crowding``).  obj: contiguous float64 device
+        tensor [M, n]; sense: M values +1 / -1; rank [n] int32 device tensor as ``pareto`` returns it (< 0: crowding 0).
+        Returns (crowd [n] float64 device tensor, info dict)."""
+        torch = self.torch
+        if not torch.is_tensor(obj) or obj.dtype != torch.float64 or not obj.is_contiguous() or obj.dim() != 2 or obj.device != self.tdev:
+            raise ValueError("obj must be a contiguous float64 tensor [M, n] on %s" % (self.tdev,))
+        M, n = (int(x) for x in obj.shape)
+        sa = np.ascontiguousarray(np.atleast_1d(np.asarray(sense)).astype(np.int32))
+        if sa.shape != (M,):
+            raise ValueError("sense must have one entry per objective")
+        if rank.dtype != torch.int32 or tuple(rank.shape) != (n,) or not rank.is_contiguous():
+            raise ValueError("rank must be a contiguous int32 tensor with one entry per member")
+        if crowd is None:
+            crowd = torch.empty((n,), dtype=torch.float64, device=self.tdev)
+        info = self._info_call(abi.ParetoInfo, 'simplyp_nsga2_crowding', self._h, n, M, obj.data_ptr(),
+                               sa.ctypes.data_as(C.POINTER(C.c_int32)), rank.data_ptr(), crowd.data_ptr())
+        return crowd, info
+
+    def nsga2_select(self, N, rank, crowd, rows=None, rows_out=None, rank_out=None, crowd_out=None):
+        """Environmental selection of a set of n members down to N (``simplyp_nsga2_select``).  rank [n] int32, crowd [n] float64
+        device tensors; rows: None or a contiguous float64 device tensor [n_rows, n] whose survivors' columns are gathered into
+        rows_out [n_rows, N].  Returns dict(position [n], survivor [N] int32, rank [N], crowd [N], rows [n_rows, N] or None) of
+        device tensors, sorted best first, plus the info fields."""
+        torch = self.torch
+        n, N = int(rank.shape[0]), int(N)
+        if rank.dtype != torch.int32 or crowd.dtype != torch.float64 or tuple(crowd.shape) != (n,) or not rank.is_contiguous() \
+                or not crowd.is_contiguous():
+            raise ValueError("rank must be int32 [n] and crowd float64 [n], contiguous")
+        n_rows = 0
+        if rows is not None:
+            if rows.dtype != torch.float64 or rows.dim() != 2 or int(rows.shape[1]) != n or not rows.is_contiguous():
+                raise ValueError("rows must be a contiguous float64 tensor [n_rows, n]")
+            n_rows = int(rows.shape[0])
+            if rows_out is None:
+                rows_out = torch.empty((n_rows, max(N, 0)), dtype=torch.float64, device=self.tdev)
+        i32 = dict(dtype=torch.int32, device=self.tdev)
+        position, survivor = torch.empty((n,), **i32), torch.empty((max(N, 0),), **i32)
+        rank_out = torch.empty((max(N, 0),), **i32) if rank_out is None else rank_out
+        crowd_out = torch.empty((max(N, 0),), dtype=torch.float64, device=self.tdev) if crowd_out is None else crowd_out
+        info = self._info_call(abi.ParetoInfo, 'simplyp_nsga2_select', self._h, n, N, rank.data_ptr(), crowd.data_ptr(),
+                               position.data_ptr(), survivor.data_ptr(), n_rows, self._ptr(rows), self._ptr(rows_out),
+                               rank_out.data_ptr(), crowd_out.data_ptr())
+        return dict(info, position=position, survivor=survivor, rank=rank_out, crowd=crowd_out, rows=rows_out)
+
+    def nsga2_offspring(self, theta, rank, crowd, t, lo, hi, target, child, parents=None, member_params=None, f_tdp=None,
+                        k_c=4, k_m=4, p_cross=0.9, p_mut=None, seed=0):
+        """The children of generation ``t`` from parents theta [n_dim, N] with rank [N] int32 and crowd [N] float64, into child
+        [n_dim, N], parents [2, N] int32 (or None) and member_params / f_tdp (``simplyp_nsga2_offspring``).  k_c, k_m: the
+        distribution indices are ``2^k - 1``; p_mut None = 1 / n_dim.  Returns the info dict (``n_accepted``: the pairs that crossed)."""
+        n_dim, N = (int(x) for x in theta.shape)
+        ptrs, keep = self._box_args(n_dim, lo, hi, target)
+        p_mut = 1.0 / n_dim if p_mut is None else float(p_mut)
+        info = self._info_call(abi.McmcInfo, 'simplyp_nsga2_offspring', self._h, N, n_dim, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+                               C.c_uint32(int(t) & 0xFFFFFFFF), int(k_c), int(k_m), float(p_cross), p_mut, *ptrs, theta.data_ptr(),
+                               self._ptr(rank), self._ptr(crowd), self._ptr(child), self._ptr(parents), self._ptr(member_params),
+                               self._ptr(f_tdp))
+        del keep
+        return info
 
 
     # ---- Sobol' sensitivity indices (simplyp_sobol_*; simplyp_amd.sobol restates them) ----
